@@ -17,7 +17,12 @@ the per-document results closes the timed region.  Default: weak scaling (every 
 `--total-docs D` (BASELINE configs[3]: 400 000 documents over 8 GPUs): strong scaling, the D documents are dealt round-robin
 to the ranks (dist.shard_indices) and every rank runs ceil(shard / B) steps, the last one on a partial batch.
 
-Prints ONE JSON line (rank 0).  `roofline` (the dominant MFMA-bound kernel) and `roofline_hbm` (every HBM-bound kernel role) are
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`,
+mean exit layer and exit distribution of the timed documents); everything below is measured only with `--full`.  `--dump-outputs DIR`
+writes what the last timed step returned on rank 0 (`logits`, `exit_layer`, `confidence`) as DIR/<name>.npy: with the same arguments
+the inputs are the same from run to run, so two builds can be compared output for output.
+
+With `--full`: `roofline` (the dominant MFMA-bound kernel) and `roofline_hbm` (every HBM-bound kernel role) are
 measured live with HIP events around the launches (ee_profile) on a schedule pinned after the warm-up (ee_set_probe_mask), so that
 the timed steps, the profiled step and the rocprofv3 child passes all run the same launch sequence; `cpu_baseline` times the CPU
 oracle (full depth, every exit, simulated policy — the reference's own semantics) on a bounded sample, at B = 1 (the reference's
@@ -110,6 +115,12 @@ def parse(argv=None):
                          "token ids) through feed.DeviceFeeder -> early_exit and report feed_inclusive_docs_per_sec (0 = skip)")
     ap.add_argument("--sweep-vectors", type=int, default=1500000, help="--workload sweep: threshold vectors (EE/large_scale.py:179-180)")
     ap.add_argument("--sweep-docs", type=int, default=40000, help="--workload sweep: documents of the confidence table")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else: clock held, executed flops, the single-batch, K | V-probe, "
+                         "one-term and fixed-work rates, rooflines and rocprofv3 counter passes, small batches, the streamed run, the CPU "
+                         "baseline and its parity sample (each still subject to its own --no-* switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy in float32 / float64")
     ap.add_argument("--dry-launch", action="store_true",
                     help="rehearse the launch only: every rank joins a gloo group, reports its RANK / WORLD_SIZE and exits "
                          "without touching the GPU (CPU test of the --gpus N path)")
@@ -117,6 +128,26 @@ def parse(argv=None):
                     help="CPU rehearsal of the whole rank body (threshold broadcast -> sharded steps -> all-gather -> max over ranks -> "
                          "line) with a stand-in engine on gloo: no GPU, the line says so and is not a measurement")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 60_000_000          # the dump's budget is 64 MB in all: room for the .npy headers
+
+
+def dump_outputs(d, arrays, seed=0):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (float32 inputs) or float64 (everything else, exact for the int32 exit
+    indices).  Arrays share their leading (document / vector) axis; over 60 MB in all, the same fixed seeded sample of rows is written for
+    every array, and its row indices as DIR/sample_rows.npy."""
+    arrays = {k: np.asarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = next(iter(arrays.values())).shape[0]
+        rows = int(DUMP_LIMIT_BYTES // (total / n + 8))          # + 8 bytes per row for its index
+        keep = np.sort(np.random.default_rng(seed).choice(n, size=rows, replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+        arrays["sample_rows"] = keep.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
 
 
 def _free_port():
@@ -338,8 +369,10 @@ def sweep_workload(a):
                          "unit": "T lane-op/s", "frac": cmp_per_s / valu_peak, "avg_launch_ms": kms, "lane_ops_per_vector_document": ops_per_pair,
                          "algorithmic_hbm_bytes_per_launch": alg_bytes, "hbm_GBps_algorithmic": alg_bytes / (kms * 1e-3) / 1e9,
                          "traffic": None}}
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"accuracy": res[0].cpu().numpy(), "mean_exit": res[1].cpu().numpy()}, seed=a.seed)
     # numpy baseline on a bounded sample of the vectors: the reference's own expression (EE/large_scale.py:46-84)
-    if a.cpu_docs != 0:
+    if a.full and a.cpu_docs != 0:
         conf = conf_d.cpu().numpy()
         corr = corr_d.cpu().numpy()
         nv = 0
@@ -662,36 +695,41 @@ def main(argv=None):
     sync()
     # shader-clock stamps around the timed region (s_memtime / s_memrealtime per XCD, one-wave kernels on the launch stream): the clock the
     # chip HELD over these steps, which differs by +-5 % between the boxes of a pool under the same load
-    stamp0 = eng.clock_stamp() if not stub else None
+    stamp0 = eng.clock_stamp() if (a.full and not stub) else None
     t0 = time.perf_counter()
 
     # no data-path collective; the one all-gather of the per-document results closes the timed region (RCCL over xGMI)
     gathered = pkg.dist.run_sharded(run_local, n_job, rank, world)
     out = run_local.last
-    stamp1 = eng.clock_stamp() if not stub else None
+    stamp1 = eng.clock_stamp() if stamp0 is not None else None
     sync()
     if world > 1:
         dist.barrier()
     sync()
     dt = time.perf_counter() - t0
-    clock_ghz, clock_per_xcd = eng.clock_ghz(stamp0, stamp1) if not stub else (None, [])
+    clock_ghz, clock_per_xcd = eng.clock_ghz(stamp0, stamp1) if stamp0 is not None else (None, [])
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"logits": out.logits.cpu().numpy(), "exit_layer": out.exit_layer.cpu().numpy(),
+                                      "confidence": out.confidence.cpu().numpy()}, seed=a.seed)
     layer_of_exit = np.array(list(EXIT_LAYERS) + [cfg.num_hidden_layers])
     # work and stage populations of the HEADLINE schedule's last step (rounds 1-3 read them behind the K | V-probe A/B below, whose forward
     # projects Q | K | V for every row: executed_tflops was 3.5 % high)
     counts = eng.stage_counts()
-    fl = eng.flops()
+    fl = eng.flops() if a.full else None
     # executed work of the WHOLE job, not of its last step: the batches differ (+-3 % flops), so every batch is run once more, untimed, and
     # its executed flops are read back (ee_last_flops synchronises: it cannot be asked inside the clock)
     fl_job = None
-    if len(batches) > 1 and not strong and not stub:
+    if a.full and len(batches) > 1 and not strong and not stub:
         fl_job = 0.0
         for i in range(steps):
             step(i=i)
             fl_job += eng.flops()["total"]
-    out0 = out if (len(batches) == 1 or stub) else step(i=0)      # batch 0's results: the documents the CPU baseline re-computes
+    out0 = None
+    if a.full:
+        out0 = out if (len(batches) == 1 or stub) else step(i=0)      # batch 0's results: the documents the CPU baseline re-computes
     # rounds 1-5's headline, kept beside the new one: every step re-runs ONE resident batch (batch 0)
     resident_rate = None
-    if world == 1 and len(batches) > 1 and not stub and not strong and not a.thresholds:
+    if a.full and world == 1 and len(batches) > 1 and not stub and not strong and not a.thresholds:
         step(i=0); sync()
         t1 = time.perf_counter()
         for _ in range(a.steps):
@@ -700,7 +738,7 @@ def main(argv=None):
         resident_rate = a.steps * B / (time.perf_counter() - t1)
     # A/B beside the headline (N = 1): the same steps with the K | V probe (exit rows bit-identical to the dump-all rows)
     kv_probe_rate = None
-    if world == 1 and a.xprobe and not stub and not a.whole_layers and not strong and not a.thresholds:   # (not in the pinned profile / PMC child runs)
+    if a.full and world == 1 and a.xprobe and not stub and not a.whole_layers and not strong and not a.thresholds:   # (not in the pinned profile / PMC child runs)
         step(xprobe=False); sync()
         t1 = time.perf_counter()
         for i in range(a.steps):
@@ -726,7 +764,7 @@ def main(argv=None):
     # Reported beside the headline, NEVER as `value` (SURVEY 8d config 2 / BASELINE.md section 4: "bf16 throughput mode reports its measured
     # deviation separately"): the same steps with ONE f16 MFMA term per MAC in the layer GEMMs and the attention (MMEE_FLAG_ONE_TERM)
     lowprec = None
-    if (world == 1 and not stub and not beit and eng.precision == "split" and not a.whole_layers and not strong and not a.thresholds
+    if (a.full and world == 1 and not stub and not beit and eng.precision == "split" and not a.whole_layers and not strong and not a.thresholds
             and a.workload == "config2"):
         step(one_term=True); sync()
         t1 = time.perf_counter()
@@ -749,7 +787,7 @@ def main(argv=None):
     # every exit head, nobody leaves -- fixed work, mix-independent); (ii) the same batch under thresholds calibrated for release fractions
     # 0.1 and 0.3 (same calibration batch); each with its own clock stamps, so that docs/s per GHz can be compared between leases ----------
     extra_rates = None
-    if world == 1 and not stub and not strong and not a.thresholds and not a.no_extra_rates and calib_conf is not None:
+    if a.full and world == 1 and not stub and not strong and not a.thresholds and not a.no_extra_rates and calib_conf is not None:
         ceiling = PEAK_F32_MFMA_TFLOPS if eng.precision in ("fp32", "f32") else PEAK_F16_MFMA_TFLOPS / SPLIT_TERMS
 
         def timed(fn, nsteps):
@@ -833,13 +871,15 @@ def main(argv=None):
         "mean_exit_layer": float(layer_of_exit[exits].mean()), "mean_exit_index": float(exits.mean()),
         "exit_distribution": {str(int(layer_of_exit[e])): float((exits == e).mean()) for e in range(len(layer_of_exit))},
         "stage_docs_last_step_rank0": counts["docs"],
-        "executed_tflop_per_step_rank0": (fl_job / steps if fl_job is not None else fl["total"]) / 1e12,
-        # (strong scaling: the LAST step is a partial batch, so its flops over the mean step time would mean nothing)
-        "executed_tflops_rank0": None if strong else (fl_job / dt if fl_job is not None else fl["total"] / (dt / steps)) / 1e12,
-        # the WHOLE step against the matrix-pipe ceiling of its precision (split: f16 dense peak / 3 terms; fp32: the f32 MFMA peak): every
-        # kernel of the step is in the numerator's time, only executed GEMM / attention / probe flops in its work
-        "step_frac_of_ceiling": None if strong else ((fl_job / dt if fl_job is not None else fl["total"] / (dt / steps)) / 1e12) /
-                                (PEAK_F32_MFMA_TFLOPS if eng.precision in ("fp32", "f32") else PEAK_F16_MFMA_TFLOPS / SPLIT_TERMS),
+        **({
+            "executed_tflop_per_step_rank0": (fl_job / steps if fl_job is not None else fl["total"]) / 1e12,
+            # (strong scaling: the LAST step is a partial batch, so its flops over the mean step time would mean nothing)
+            "executed_tflops_rank0": None if strong else (fl_job / dt if fl_job is not None else fl["total"] / (dt / steps)) / 1e12,
+            # the WHOLE step against the matrix-pipe ceiling of its precision (split: f16 dense peak / 3 terms; fp32: the f32 MFMA peak): every
+            # kernel of the step is in the numerator's time, only executed GEMM / attention / probe flops in its work
+            "step_frac_of_ceiling": None if strong else ((fl_job / dt if fl_job is not None else fl["total"] / (dt / steps)) / 1e12) /
+                                    (PEAK_F32_MFMA_TFLOPS if eng.precision in ("fp32", "f32") else PEAK_F16_MFMA_TFLOPS / SPLIT_TERMS),
+        } if a.full else {}),
         # round 6: what the timed steps ran over
         "distinct_documents": {"resident_batches": len(batches), "documents_per_rank": len(batches) * B,
                                "every_timed_document_distinct": bool(not strong and len(batches) >= steps),
@@ -856,7 +896,7 @@ def main(argv=None):
         line["metric"] = "docs_per_sec (STUB ENGINE on CPU over gloo: rehearsal of the rank body, not a measurement)"
         line["gathered_checksum"] = float((g_logits.double().sum() + g_exit.double().sum() + g_conf.double().sum()).item())
 
-    if rank == 0 and not a.no_profile and not stub:
+    if rank == 0 and a.full and not a.no_profile and not stub:
         # ---- rooflines, live: HIP events around every launch of one more (untimed) step of the SAME pinned schedule --------------
         eng.profile(True)
         step(**({"serial": True} if getattr(eng, "n", 1) > 1 else {}))      # micro-batches one after the other: overlapping launches would be timed twice
@@ -984,10 +1024,10 @@ def main(argv=None):
                 line["roofline"]["traffic_error"] = "; ".join(v for v in passes.values() if isinstance(v, str)) or "counter rows for the FFN-up kernel not found in the pmc output"
             line["roofline"]["traffic_detail"] = detail
 
-    if rank == 0 and world == 1 and not stub and not strong and not a.no_small_batch and not a.thresholds and not a.no_extra_rates:
+    if rank == 0 and a.full and world == 1 and not stub and not strong and not a.no_small_batch and not a.thresholds and not a.no_extra_rates:
         line["small_batch"] = small_batch_block(pkg, a, cfg, W, ee, batches[0], B, T, thr, temps, dev, beit)
 
-    if rank == 0 and world == 1 and a.stream_docs > 0 and not beit and not stub and not strong:
+    if rank == 0 and a.full and world == 1 and a.stream_docs > 0 and not beit and not stub and not strong:
         # ---- streaming run: every document distinct, host packing + PCIe + device preprocessing inside the clock (the reference's
         # loop being replaced: EE/utils.py:93-98, 169-173).  The headline `value` stays the resident-batch rate. ---------------------
         # Round 6: the streamed pages are scans (strokes + sensor noise through the device resize), the resident generator
@@ -1036,7 +1076,7 @@ def main(argv=None):
                                           "buffer, one async H2D copy per batch, resize/normalise/pad on a side stream) -> ee_forward; "
                                           "host packing, PCIe and preprocessing are inside the clock, page synthesis is not"}
 
-    if rank == 0 and world == 1 and a.cpu_docs != 0 and not stub:
+    if rank == 0 and a.full and world == 1 and a.cpu_docs != 0 and not stub:
         # ---- CPU baseline (N = 1 runs only): the oracle = the reference's semantics (every layer, every exit, simulated policy) ------
         oracle = importlib.import_module("oracle.ee_oracle")
         otorch = importlib.import_module("oracle.ee_oracle_torch")

@@ -223,7 +223,7 @@ def test_holes_in_the_attention_mask_stay_rows(pkg, oracle):
     eng.close()
 
 
-def test_idx16_attention_form_is_bit_identical_to_the_word_index(pkg):
+def test_idx16_attention_form_is_bit_identical_to_the_word_index(pkg, tmp_path):
     """Round 6 experiment kept in the DIAGNOSTIC library (MMEE_ATTN_IDX=16): the 16-bit pair index + delta table form of the attention kernel
     returns the bits of the shipped 32-bit form (tools/attn_xp_check.py: 24 base-shape documents through every layer)."""
     import os
@@ -231,10 +231,10 @@ def test_idx16_attention_form_is_bit_identical_to_the_word_index(pkg):
     import sys
     from .conftest import ROOT
     diag = os.path.join(ROOT, "multi-modal-early-exit_amd", "libmmee_hip_diag.so")
-    if not os.path.exists(diag):
-        pytest.skip("diagnostic library not built (make -C multi-modal-early-exit_amd/csrc diag)")
+    # build() makes only the release library: a fresh checkout builds the diagnostic one here (make is a no-op when it is up to date)
+    subprocess.run(["make", "-C", os.path.join(ROOT, "multi-modal-early-exit_amd", "csrc"), "diag", "-j8"], check=True, stdout=subprocess.DEVNULL)
     tool = os.path.join(ROOT, "tools", "attn_xp_check.py")
-    ref = os.path.join("/tmp", f"mmee_idx32_{os.getpid()}.pt")
+    ref = str(tmp_path / "idx32.pt")
     env = dict(os.environ, MMEE_LIB=diag)
     r = subprocess.run([sys.executable, tool, "save", ref], env=dict(env, MMEE_ATTN_IDX="32"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]

@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."
 export MMEE_LIB=$PWD/multi-modal-early-exit_amd/libmmee_hip_diag.so
 for o in "$@"; do
     echo "== MMEE_GEMM_ORDER=$o"
-    MMEE_GEMM_ORDER=$o timeout -k 10 400 python bench.py --steps 6 --warmup 2 --cpu-docs 0 --stream-docs 0 --no-extra-rates --no-small-batch 2>/dev/null | python -c "
+    MMEE_GEMM_ORDER=$o timeout -k 10 400 python bench.py --full --steps 6 --warmup 2 --cpu-docs 0 --stream-docs 0 --no-extra-rates --no-small-batch 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']
