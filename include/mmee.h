@@ -323,7 +323,9 @@ int ee_profile(ee_handle* h, int32_t enable);
 int ee_profile_read(ee_handle* h, int32_t idx, char* name_out, int32_t name_cap, double* total_ms, int32_t* launches);
 
 /* Micro-benchmark / unit-test hook: ONE launch of the path's GEMM kernel, Cout[M,N] = epi(A[M,K] W[N,K]^T + bias (+ resid)),
- * epi 0 = bias, 1 = GELU(erf), 2 = + residual, 3 = tanh; all pointers dev float; N % 128 == 0, K % 32 == 0.
+ * epi 0 = bias, 1 = GELU(erf), 2 = + residual, 3 = tanh; all pointers dev float; N % 128 == 0, K % 32 == 0.  epi | 256 selects the
+ * LDS-DMA staging kernel (the one the path launches); a bare epi runs the register-staged kernel.  epi | 16 = static grid stride
+ * instead of the work queues.
  * wgs_per_cu sizes the persistent grid (0 = default).  row_src (dev int32 [M] or NULL) gathers the A (and residual) rows as
  * the layer after an exit stage does.  clk_probe (dev, 2 x grid uint64, or NULL): per workgroup
  * {shader cycles, 100 MHz real-time ticks} spent in the kernel, i.e. the clock the chip held (diagnostic). */
@@ -334,7 +336,8 @@ int ee_debug_gemm(const float* A, const float* W, const float* bias, const float
  * W [N, K] are converted to split-f16 rows with the given power-of-two scales, then `iters` launches of the kernel compute
  * Cout = epi(A[row_src ? row_src[r] : r] W^T + bias (+ resid)).  out_split != 0: Cout receives split-f16 rows (64-byte
  * groups [hi 16 f16 | lo 16 f16]) scaled by out_scale instead of f32.  ms_out (host float[2], may be NULL): [0] = average
- * milliseconds per launch, [1] = shader clock in GHz when a diagnostic bit is set in epi (bits 4..: timing diagnostics).  N % 256 == 0, K % 16 == 0. */
+ * milliseconds per launch, [1] = shader clock in GHz when a diagnostic bit is set in epi (bits 4..: timing diagnostics).  N % 256 == 0, K % 32 == 0
+ * (gemm_split_supports).  row_src must be non-decreasing: the kernel addresses the gathered A rows of a tile as offsets from its first one. */
 int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const float* resid, float* Cout, int32_t M, int32_t N,
                         int32_t K, int32_t epi, int32_t out_split, float a_scale, float w_scale, float out_scale,
                         const int32_t* row_src, int32_t rows_A, int32_t iters, float* ms_out, void* stream);

@@ -1863,7 +1863,7 @@ int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const
     if (dbg) return fail(nullptr, "ee_debug_gemm_split: timing variants (wrong results) exist in the diagnostic library only (make diag)");
 #endif
     if (!A || !W || !Cout || M < 1 || rows_A < 1 || !mmee::gemm_split_supports(N, K) || epi < 0 || epi > 3 || iters < 1)
-        return fail(nullptr, "ee_debug_gemm_split: bad argument (N %% 256, K %% 16)");
+        return fail(nullptr, "ee_debug_gemm_split: bad argument (N %% 256, K %% 32)");
     if (epi == EPI_RESID && !resid) return fail(nullptr, "ee_debug_gemm_split: residual epilogue without a residual");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipDeviceProp_t prop;

@@ -1,6 +1,7 @@
 """Randomised cross-check of the exit-layer schedules (GPU box only): for random shapes / exit sets / strategies / thresholds the
 probe-first, whole-layer, default, pinned and cost-model-suggested schedules and the dump-all rows must agree bit for bit, and the X-space probe within tolerance.  Not a test (minutes); run after touching
-the layer loop of csrc/capi.hip:  python tools/fuzz_schedules.py [n_cases [seed]]"""
+the layer loop of csrc/capi.hip:  python tools/fuzz_schedules.py [n_cases [seed [large|big]]].  Each case draws its label count from
+{2, 10, 16, 64}."""
 import importlib
 import os
 import sys
@@ -28,9 +29,10 @@ def one(case, rng):
     emb = [[], ["vision_avg"], ["text_avg", "text_visual_concat"]][int(rng.integers(0, 3))]
     ee = dict(exits=emb + exits, encoder_layer_strategy=strat)
     H = 768 if BIG else HS[int(rng.integers(0, len(HS)))]
+    K = int(rng.choice([2, 10, 16, 64]))                                 # label count: the exit kernels index by K (ee_create takes 1..64)
     cs = {256: (40, 48), 768: (128, 128), 1024: (171, 170)}[H]           # 6 spatial slices: 4 coordinate + 2 shape sizes sum to H
     cfg = pkg.ModelConfig.base(EE_config=ee, num_hidden_layers=L, hidden_size=H, intermediate_size=4 * H if H >= 768 else 512,
-                               num_attention_heads=H // 64, coordinate_size=cs[0], shape_size=cs[1])
+                               num_attention_heads=H // 64, coordinate_size=cs[0], shape_size=cs[1], num_labels=K)
     B = int(rng.choice([100, 300, 512] if BIG else [1, 5, 33, 96]))
     T = 512 if BIG else int(rng.choice([16, 130, 512]))
     W = pkg.synth.make_weights(cfg, seed=int(rng.integers(1, 1 << 30)), head_gain=6.0)
@@ -83,7 +85,7 @@ def one(case, rng):
     xok = bool((~diff | near).all()) and float(np.abs(lgx[~diff] - outs[0][1][~diff]).max(initial=0.0)) <= 1e-4
     xrows = eng.layer_plan()["rows_qkv"]
     ok = ok and xok
-    print(f"case {case}: L={L} H={H} exits={ee['exits']} {strat} B={B} T={T} dense={dense} temps={temps is not None} "
+    print(f"case {case}: L={L} H={H} K={K} exits={ee['exits']} {strat} B={B} T={T} dense={dense} temps={temps is not None} "
           f"left at {np.bincount(ex, minlength=E1).tolist()} probes {outs[0][3]} pinned {outs[3][3]} suggested {outs[4][3]} xprobe dlogit "
           f"{float(np.abs(lgx[~diff] - outs[0][1][~diff]).max(initial=0.0)):.1e} flips {int(diff.sum())} rows_qkv {xrows}: {'ok' if ok else 'MISMATCH'}", flush=True)
     eng.close()
