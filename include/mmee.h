@@ -19,6 +19,8 @@
  *                                                 87-104; called from EE/eval.py:87-98).
  *   ee_threshold_sweep                          <- thresh.opt1 / large_scale.opt0_2D vectorised exit-index search
  *                                                 (EE/thresh.py:184-215, EE/large_scale.py:68-84).
+ *   ee_set_patience / ee_patience_scan /        <- EarlyExitInference.PATIENCE, declared by the reference (EE/models/EE_modules.py:
+ *   ee_patience_sweep                              123-124, PABEE: Zhou et al., NeurIPS 2020) but not implemented there; semantics below.
  *
  * Conventions: every function returns 0 on success, non-zero on error (message via ee_last_error).  All pointers
  * marked "dev" are device (HBM) pointers borrowed from the caller for the duration of the enqueued work; kernels are
@@ -42,8 +44,18 @@ extern "C" {
 enum { MMEE_EXIT_VISION_AVG = 0, MMEE_EXIT_TEXT_AVG = 1, MMEE_EXIT_TEXT_VISUAL_CONCAT = 2 };
 /* encoder_layer_strategy (EE/models/EE_modules.py:167-172) */
 enum { MMEE_STRATEGY_RAMP = 0, MMEE_STRATEGY_GATE = 1 };
-/* inference_strategy (EE/models/EE_modules.py:116-146): max_confidence exits on crit > thr, entropy on crit < thr */
-enum { MMEE_CRIT_MAX_CONFIDENCE = 0, MMEE_CRIT_ENTROPY = 1 };
+/* inference_strategy (EE/models/EE_modules.py:116-146): max_confidence exits on crit > thr, entropy on crit < thr, patience as below */
+enum { MMEE_CRIT_MAX_CONFIDENCE = 0, MMEE_CRIT_ENTROPY = 1, MMEE_CRIT_PATIENCE = 2 };
+/*
+ * MMEE_CRIT_PATIENCE (patience-based early exit, PABEE).  Exits e = 0 .. E in the path's order (embedding exits vision, text, concat, then
+ * encoder exits ascending, then the final classifier).  p_e(n) = argmax of document n's policy logits at exit e, taken on exactly the float32
+ * values written to out_all_logits, (float)((double)z / T_e) (ramps: the head's logits; gates: classifier(gate input)); ties resolve to the
+ * first maximal index (numpy argmax).  Run counter: c_0 = 0; c_e = c_{e-1} + 1 if p_e == p_{e-1}, else 0.  Document n leaves at the first e
+ * with c_e >= t, or at E if there is none (t > E: every document runs to the final exit).  The patience t >= 1 is set by ee_set_patience.
+ * Outputs keep their contract: out_logits = the scaled logits of the chosen exit, out_conf = the float64 max-softmax of those scaled logits
+ * (rounded to float32), out_all_crit (dump-all) = the same max-softmax at every exit, out_head_crit = the max-softmax of the raw head logits.
+ * Thresholds are ignored (may be NULL); temperatures act only through the scaled logits.
+ */
 /* model family: LayoutLMv3 (text + layout + image, the reference's EE model) or BEiT / DiT (image only; BASELINE configs[4],
  * the reference's "dit" branch EE/configs.py:429-449 — exit heads there are this build's extrapolation) */
 enum { MMEE_ARCH_LAYOUTLMV3 = 0, MMEE_ARCH_BEIT = 1 };
@@ -136,7 +148,8 @@ const char* ee_expected_tensor_name(const ee_handle* h, int32_t i);
  *   input_ids      dev int64 (B,T)        attention_mask  dev int64 (B,T) or NULL (= ones)
  *   bbox           dev int64 (B,T,4)      pixel_values    dev float (B,C,R,R)
  *   token_type_ids dev int64 (B,T) or NULL (= zeros)      position_ids dev int64 (B,T) or NULL (= pad-aware cumsum)
- *   thresholds     host double [E+1]: exit e leaves when sign(crit_e, thresholds[e]) (strict); entry E (final) unused
+ *   thresholds     host double [E+1]: exit e leaves when sign(crit_e, thresholds[e]) (strict); entry E (final) unused.
+ *                  Ignored (may be NULL) under MMEE_CRIT_PATIENCE, which needs ee_set_patience before its first thresholded forward
  *   temperatures   host double [E+1] or NULL: logits of exit e are divided by temperatures[e] before the criterion
  *                  and in every returned logit (calibrated logits, EE/eval.py:321-323)
  * outputs (any may be NULL except out_exit):
@@ -165,11 +178,13 @@ int ee_forward(ee_handle* h, const int64_t* input_ids, const int64_t* attention_
  * The graph is bound to the POINTERS it was captured with -- inputs and outputs are static buffers the caller refills / reads between
  * replays -- and to (B, T, flags, which outputs were non-NULL) and to the handle's exit-layer schedule at capture time (ee_set_probe_mask).
  * Thresholds and temperatures are NOT baked in: the decide kernels read them from a device vector that every ee_graph_launch refreshes.
+ * Neither is the patience: under MMEE_CRIT_PATIENCE the decide kernels read t from the same vector, which ee_graph_launch fills with the
+ * handle's CURRENT patience (ee_set_patience between replays takes effect).  The criterion itself is bound at capture.
  * `stream` must be a created stream (the legacy null stream cannot be captured).  Not capturable: the one-shot side inputs / outputs
  * (ee_set_inputs_embeds, ee_set_hidden_states_out, ee_set_head_mask, ee_set_attentions_out) and an armed ee_profile.
  *
  * ee_graph_launch replays it on `stream` (any stream, the null stream included) with this launch's thresholds (host double [E+1]; may be NULL
- * for a graph captured with MMEE_FLAG_NO_EXIT) and temperatures (host double [E+1] or NULL = 1.0: a division by 1.0 is exact, so a graph
+ * for a graph captured with MMEE_FLAG_NO_EXIT or under MMEE_CRIT_PATIENCE) and temperatures (host double [E+1] or NULL = 1.0: a division by 1.0 is exact, so a graph
  * replayed without temperatures returns the bits of the eager call without them).  Same arithmetic, same launch order, same bits as
  * ee_forward on the same inputs (tests/test_gpu_round6.py).  Error reporting, ee_last_stage_counts, ee_last_flops and ee_last_layer_plan work
  * as after ee_forward.  Rows of out_all_* / out_head_* that a replay does not reach keep what the buffers held before (as ee_forward).
@@ -202,6 +217,10 @@ int ee_last_layer_plan(ee_handle* h, int32_t* rows_qkv, int32_t* rows_main, int3
  * overrides `model.config.exit_config["inference_strategy"]` after the model has been built (EE/utils.py:62-78); the Python mirror forwards that
  * write here so that those lines run unchanged. */
 int ee_set_criterion(ee_handle* h, int32_t criterion);
+/* The patience t (>= 1; smaller values are rejected) of every later forward and graph launch under MMEE_CRIT_PATIENCE.  Part of the handle's
+ * state until changed.  Per document, the decide kernels keep (argmax at the previous exit, run counter) in the handle's workspace, indexed
+ * by the document's slot in the call and rewritten at exit 0, which every document reaches: nothing carries over from one forward to the next. */
+int ee_set_patience(ee_handle* h, int32_t t);
 
 /* Pin the exit-layer schedule.  DEFAULT (enabled == 0): every layer that ends in a decision is probed first.  Rounds 2-4 chose per layer
  * from the stage populations of "the handle's most recent FINISHED forward" -- a timing-dependent host decision, and under MMEE_FLAG_XPROBE
@@ -256,6 +275,21 @@ int ee_set_attentions_out(ee_handle* h, float* out);
  */
 int ee_policy_scan(const double* logits, int32_t E1, int32_t N, int32_t K, const double* thresholds,
                    int32_t* exits, double* predictions, double* confidence, int32_t* counts, void* stream);
+/*
+ * The patience policy (MMEE_CRIT_PATIENCE semantics) on a dumped logits array: logits dev double (E1,N,K), patience >= 1.  p_e is the argmax
+ * of the float64 row (first maximum).  exits dev int32 (N,), predictions dev double (N,K) or NULL (the row of the chosen exit), confidence
+ * dev double (N,) or NULL (its float64 max-softmax), counts dev int32 [E1] or NULL (documents per exit).
+ */
+int ee_patience_scan(const double* logits, int32_t E1, int32_t N, int32_t K, int32_t patience, int32_t* exits, double* predictions,
+                     double* confidence, int32_t* counts, void* stream);
+/*
+ * V patience values at once over one dumped array (the patience counterpart of ee_threshold_sweep / EE/eval.py:186-210): logits dev double
+ * (E1,N,K) with E1 <= 128, references dev int64 (N,), patiences dev int32 (V,).  exit(v,n) as ee_patience_scan with t = patiences[v];
+ * acc[v] = #{n : argmax logits[exit(v,n), n] == references[n]} / N, mean_exit[v] = sum_n exit(v,n) / N (integer sums, then one division:
+ * deterministic).  Outputs dev: acc double (V,), mean_exit double (V,), exit_hist int32 (V,E1) or NULL.
+ */
+int ee_patience_sweep(const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, const int32_t* patiences, int32_t V,
+                      double* acc, double* mean_exit, int32_t* exit_hist, void* stream);
 
 /*
  * The row of the north star's ONE all-gather, for hosts that call RCCL themselves (the Python host does the same with tensor views, dist.py):

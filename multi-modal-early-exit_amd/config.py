@@ -16,6 +16,7 @@ import operator
 import os
 from dataclasses import dataclass, field, asdict
 from enum import Enum
+from numbers import Integral
 from typing import Any, Callable, Dict, List, Optional, Sequence, Union
 
 EMBEDDING_EXITS = ("vision_avg", "text_avg", "text_visual_concat")  # fixed evaluation order, EE/models/LayoutLMv3.py:465-605
@@ -42,7 +43,7 @@ class EarlyExitInference(_StrEnum):
     LTE = "lte"
 
     def get_sign(self) -> Callable:
-        # EE/models/EE_modules.py:137-144: max_confidence exits when crit > thr, entropy when crit < thr
+        # EE/models/EE_modules.py:137-144: max_confidence exits when crit > thr, entropy when crit < thr; patience has no threshold
         if self == EarlyExitInference.MAX_CONFIDENCE:
             return operator.gt
         if self == EarlyExitInference.ENTROPY:
@@ -56,6 +57,8 @@ class EarlyExitInference(_StrEnum):
             return 0
         if self == EarlyExitInference.ENTROPY:
             return 1
+        if self == EarlyExitInference.PATIENCE:
+            return 2
         raise NotImplementedError(f"{self} not implemented")
 
 
@@ -96,6 +99,13 @@ def parse_exits(exits: Union[str, Sequence[Union[str, int]]]) -> List[Union[str,
     return list(exits)
 
 
+def check_patience(t) -> int:
+    """The patience of MMEE_CRIT_PATIENCE: an integer >= 1 (bools and fractional values are refused)."""
+    if isinstance(t, bool) or not isinstance(t, Integral) or int(t) < 1:
+        raise ValueError(f"patience must be an integer >= 1, got {t!r}")
+    return int(t)
+
+
 class ExitConfig:
     """Same keys/defaults as EE/models/EE_modules.py:175-195."""
 
@@ -106,6 +116,10 @@ class ExitConfig:
         self.exits = parse_exits(kwargs.get("exits", ["text_avg", "vision_avg", 1, 4, 8]))
         self.encoder_layer_strategy = EarlyExitHead(kwargs.get("encoder_layer_strategy", "ramp"))
         self.exit_head_num_layers = kwargs.get("exit_head_num_layers", 2)
+        # inference_strategy == "patience": exit once the prediction has stayed the same for `patience` exits in a row (include/mmee.h)
+        self.patience = kwargs.get("patience", None)
+        if self.patience is not None:
+            self.patience = check_patience(self.patience)
 
     # ---- derived views used by the hot path -------------------------------------------------
     @property
@@ -132,6 +146,7 @@ class ExitConfig:
             "exits": list(self.exits),
             "encoder_layer_strategy": str(self.encoder_layer_strategy),
             "exit_head_num_layers": self.exit_head_num_layers,
+            "patience": self.patience,
         }
 
 

@@ -97,6 +97,8 @@ struct ee_handle {
     int *doc_orig, *doc_off, *x_src, *meta_src;   // [(E+2)][max_docs+1]
     StageCounts* counts;                          // [(E+2)]
     double* thr_dev = nullptr;                    // scratch for ee_policy_scan
+    int32_t patience = 0;                         // ee_set_patience (0: not set); read by the decide launches under MMEE_CRIT_PATIENCE
+    int* pat_state = nullptr;                     // [2][max_docs]: argmax at the previous exit, run counter (by original document slot)
     // optional per-kernel event timing (ee_profile)
     bool prof_on = false;
     struct ProfRec { int id; hipEvent_t a, b; double flops; };
@@ -134,9 +136,10 @@ struct ee_handle {
     // thresholds / temperatures live in a device buffer the decide kernels read, refreshed in front of every replay
     struct GraphRec {
         hipGraphExec_t exec = nullptr;
-        double* thr_dev = nullptr;                // [2 * (E + 1)]: thresholds, then temperatures (1.0 when the launch passes none)
+        double* thr_dev = nullptr;                // [2 * (E + 1) + 1]: thresholds, then temperatures (1.0 when the launch passes none), then the patience
         int n_exits1 = 0;
         bool no_exit = false;
+        bool patience = false;                    // captured under MMEE_CRIT_PATIENCE: launches need no thresholds
         // bookkeeping of the captured forward, restored by every launch (ee_last_stage_counts / ee_last_flops / ee_last_layer_plan read it)
         int last_B = 0, last_T = 0, last_stages = 0;
         uint32_t last_flags = 0;
@@ -277,7 +280,7 @@ const char* const kProfNames[] = {
     "gemm_ffn_up|gemm_f32_kernel<1,0>",
     "gemm_ffn_down|gemm_f32_kernel<2,0>",
     "exit_head|gemm_f32_kernel<3,0>+head_out_kernel",
-    "exit_decide|exit_decide_kernel",
+    "exit_decide|exit_decide_kernel (patience: exit_decide_patience_kernel)",
     "compact|compact_rows_kernel",
     "gather_cls|gather_cls_kernel",
     "cls_probe|attention_idx_kernel+gemm_split_kernel<.., 1>+ln_rows_kernel+gather_cls_kernel (CLS rows of an exit layer, before its decision)",
@@ -591,6 +594,7 @@ int ee_create(const ee_config* c, ee_handle** out) {
         rc |= dev_alloc(h, &h->meta_src, st);
         rc |= dev_alloc(h, &h->counts, (size_t)(E + 2));
         rc |= dev_alloc(h, &h->thr_dev, 256);
+        rc |= dev_alloc(h, &h->pat_state, 2 * Bm);
     }
     if (rc) {
         g_create_error = h->err.empty() ? g_create_error : h->err;
@@ -846,7 +850,11 @@ int forward_body(ee_handle* h, const int64_t* input_ids, const int64_t* attentio
     if (B < 1 || B > c.max_docs) return fail(h, "ee_forward: B=%d outside [1, max_docs=%d]", B, c.max_docs);
     if (!beit && (T < 1 || T > c.max_text_len)) return fail(h, "ee_forward: T=%d outside [1, max_text_len=%d]", T, c.max_text_len);
     const int E = c.n_embedding_exits + c.n_encoder_exits;
-    if (!thresholds && !cap && !(flags & MMEE_FLAG_NO_EXIT)) return fail(h, "ee_forward: thresholds required unless MMEE_FLAG_NO_EXIT");
+    const bool patience = c.criterion == MMEE_CRIT_PATIENCE;
+    if (!thresholds && !cap && !patience && !(flags & MMEE_FLAG_NO_EXIT))
+        return fail(h, "ee_forward: thresholds required unless MMEE_FLAG_NO_EXIT or MMEE_CRIT_PATIENCE");
+    if (patience && h->patience < 1 && !(flags & MMEE_FLAG_NO_EXIT))
+        return fail(h, "ee_forward: the patience criterion needs ee_set_patience(h, t) with t >= 1 before the first forward");
     if ((head_mask || attn_out) && (flags & (MMEE_FLAG_NO_EXIT | MMEE_FLAG_WHOLE_LAYERS)) != (MMEE_FLAG_NO_EXIT | MMEE_FLAG_WHOLE_LAYERS))
         return fail(h, "ee_forward: head_mask / attention maps exist in dump-all mode with whole layers only (MMEE_FLAG_NO_EXIT | MMEE_FLAG_WHOLE_LAYERS)");
     if ((head_mask || attn_out) && beit) return fail(h, "ee_forward: head_mask / attention maps are built for the LayoutLMv3 layers only");
@@ -1085,7 +1093,17 @@ int forward_body(ee_handle* h, const int64_t* input_ids, const int64_t* attentio
         d.out_logits = out_logits; d.out_exit = out_exit; d.out_conf = out_conf;
         d.out_all_logits = out_all_logits; d.out_all_crit = out_all_crit;
         d.out_head_logits = out_head_logits; d.out_head_crit = out_head_crit;
-        { ProfScope ps(h, P_DECIDE, s); launch_decide(d, s); }
+        if (patience) {
+            PatienceArgs pa{};
+            pa.t = h->patience;
+            if (cap) pa.t_ptr = cap->thr_dev + 2 * (E + 1);                               // replays read the patience of THEIR launch
+            pa.prev = h->pat_state; pa.run = h->pat_state + c.max_docs;
+            ProfScope ps(h, P_DECIDE, s);
+            launch_decide_patience(d, pa, s);
+        } else {
+            ProfScope ps(h, P_DECIDE, s);
+            launch_decide(d, s);
+        }
         h->exit_stage[exit_index] = cur;
         if (!is_final) {
             ProfScope ps(h, P_COMPACT, s);
@@ -1470,7 +1488,8 @@ int ee_graph_capture(ee_handle* h, const int64_t* input_ids, const int64_t* atte
     ee_handle::GraphRec g;
     g.n_exits1 = E1;
     g.no_exit = (flags & MMEE_FLAG_NO_EXIT) != 0;
-    if (dev_alloc(h, &g.thr_dev, (size_t)2 * E1)) return 1;
+    g.patience = h->cfg.criterion == MMEE_CRIT_PATIENCE;
+    if (dev_alloc(h, &g.thr_dev, (size_t)2 * E1 + 1)) return 1;
     // (2) the launch list again, captured
     hipGraph_t graph = nullptr;
     HIP_OK(h, hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
@@ -1494,17 +1513,19 @@ int ee_graph_launch(ee_handle* h, int32_t graph_id, const double* thresholds, co
     if (!h) return 1;
     if (graph_id < 0 || graph_id >= (int32_t)h->graphs.size() || !h->graphs[graph_id].exec) return fail(h, "ee_graph_launch: no such graph (%d)", graph_id);
     const ee_handle::GraphRec& g = h->graphs[graph_id];
-    if (!thresholds && !g.no_exit) return fail(h, "ee_graph_launch: thresholds required (the graph was captured without MMEE_FLAG_NO_EXIT)");
+    if (!thresholds && !g.no_exit && !g.patience)
+        return fail(h, "ee_graph_launch: thresholds required (the graph was captured without MMEE_FLAG_NO_EXIT or MMEE_CRIT_PATIENCE)");
     if (h->prof_on) return fail(h, "ee_graph_launch: ee_profile times eager launches; disarm it first");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int rc_pre = forward_pre(h, s);
     if (rc_pre) return rc_pre;
     ThrPack p{};
-    p.n = 2 * g.n_exits1;
+    p.n = 2 * g.n_exits1 + 1;
     for (int i = 0; i < g.n_exits1; ++i) {
         p.v[i] = thresholds ? thresholds[i] : 0.0;
         p.v[g.n_exits1 + i] = temperatures ? temperatures[i] : 1.0;
     }
+    p.v[2 * g.n_exits1] = (double)h->patience;
     hipLaunchKernelGGL(set_thresholds_kernel, dim3(1), dim3(64), 0, s, p, g.thr_dev);
     HIP_OK(h, hipGraphLaunch(g.exec, s));
     h->last_B = g.last_B; h->last_T = g.last_T; h->last_stages = g.last_stages; h->last_flags = g.last_flags; h->last_gate_heads = g.last_gate_heads;
@@ -1568,8 +1589,16 @@ int ee_set_attentions_out(ee_handle* h, float* out) {
 
 int ee_set_criterion(ee_handle* h, int32_t criterion) {
     if (!h) return 1;
-    if (criterion != MMEE_CRIT_MAX_CONFIDENCE && criterion != MMEE_CRIT_ENTROPY) return fail(h, "ee_set_criterion: unknown criterion %d", criterion);
+    if (criterion != MMEE_CRIT_MAX_CONFIDENCE && criterion != MMEE_CRIT_ENTROPY && criterion != MMEE_CRIT_PATIENCE)
+        return fail(h, "ee_set_criterion: unknown criterion %d", criterion);
     h->cfg.criterion = criterion;      // read by the decide kernel's arguments of every later ee_forward
+    return 0;
+}
+
+int ee_set_patience(ee_handle* h, int32_t t) {
+    if (!h) return 1;
+    if (t < 1) return fail(h, "ee_set_patience: t=%d, the patience must be >= 1", t);
+    h->patience = t;                   // eager forwards pass it by value; ee_graph_launch writes it to the graph's device vector
     return 0;
 }
 
@@ -1719,6 +1748,29 @@ int ee_policy_scan(const double* logits, int32_t E1, int32_t N, int32_t K, const
     if (N > 0) launch_policy_scan(logits, E1, N, K, thr_dev, exits, predictions, confidence, counts, s);
     (void)hipFreeAsync(thr_dev, s);
     return launch_status(nullptr, "ee_policy_scan");
+}
+
+int ee_patience_scan(const double* logits, int32_t E1, int32_t N, int32_t K, int32_t patience, int32_t* exits, double* predictions,
+                     double* confidence, int32_t* counts, void* stream) {
+    if (patience < 1 || E1 < 1 || N < 0 || K < 1 || (N > 0 && (!logits || !exits))) return fail(nullptr, "ee_patience_scan: bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_patience_scan: no HIP device");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (counts && hipMemsetAsync(counts, 0, sizeof(int) * E1, s) != hipSuccess) return fail(nullptr, "ee_patience_scan: memset failed");
+    if (N > 0) launch_patience_scan(logits, E1, N, K, patience, exits, predictions, confidence, counts, s);
+    return launch_status(nullptr, "ee_patience_scan");
+}
+
+int ee_patience_sweep(const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, const int32_t* patiences, int32_t V,
+                      double* acc, double* mean_exit, int32_t* exit_hist, void* stream) {
+    if (!logits || !references || !patiences || !acc || !mean_exit || E1 < 1 || E1 > 128 || N < 1 || K < 1 || V < 0)
+        return fail(nullptr, "ee_patience_sweep: bad argument (E1 <= 128, N >= 1)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_patience_sweep: no HIP device");
+    if (V > 0 && !launch_patience_sweep(logits, reinterpret_cast<const long long*>(references), E1, N, K, patiences, V, acc, mean_exit, exit_hist,
+                                        reinterpret_cast<hipStream_t>(stream)))
+        return fail(nullptr, "ee_patience_sweep: hipMallocAsync failed");
+    return launch_status(nullptr, "ee_patience_sweep");
 }
 
 int ee_pack_results(const float* logits, const int32_t* exit_layer, const float* confidence, int32_t n, int32_t K, int32_t* rows, void* stream) {

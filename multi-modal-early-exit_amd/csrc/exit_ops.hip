@@ -102,8 +102,13 @@ __device__ inline double crit_f64(const float* z, int K, double temp, int criter
 //   thread <-> document: criterion (f64), exit test, scatter of leavers to the output arrays;
 //   survivors: wave ballot -> popcount prefix -> cross-wave prefix in LDS -> running carry = new dense index,
 //   and the same scan over row counts = new dense row offset.
+// PATIENCE (PABEE, MMEE_CRIT_PATIENCE): the exit test is "the argmax of the scaled logits has stayed the same for t exits in a row"
+// instead of a threshold test.  The criterion written to the outputs is the max-softmax; the run state of document `orig` is
+// (p.prev[orig], p.run[orig]), indexed by the original slot so that compaction never moves it, and written unconditionally at
+// exit 0, which every document reaches (no reset launch).  The max_confidence / entropy kernel is the PATIENCE = false instantiation.
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void exit_decide_body(const DecideArgs& a) {
+template <bool PATIENCE>
+__device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const PatienceArgs& p) {
     __shared__ int s_cnt[16], s_rows[16];
     __shared__ unsigned long long s_sq[16];
     __shared__ int s_carry_docs, s_carry_rows;
@@ -111,6 +116,8 @@ __device__ __forceinline__ void exit_decide_body(const DecideArgs& a) {
     const int n = a.counts->n_docs;
     const double thr = a.thr_ptr ? a.thr_ptr[a.exit_index] : a.thr;
     const double temp = a.temp_ptr ? a.temp_ptr[a.exit_index] : a.temp;
+    int patience = 0;
+    if constexpr (PATIENCE) patience = p.t_ptr ? (int)p.t_ptr[0] : p.t;
     if (tid == 0) { s_carry_docs = 0; s_carry_rows = 0; }
     unsigned long long sq = 0;
     __syncthreads();
@@ -123,8 +130,25 @@ __device__ __forceinline__ void exit_decide_body(const DecideArgs& a) {
             orig = a.doc_orig[i];
             len = a.doc_off[i + 1] - a.doc_off[i];
             const float* z = a.pol_logits + (size_t)i * a.K;
-            const double crit = crit_f64(z, a.K, temp, a.criterion);
-            bool leave = a.criterion == 0 ? (crit > thr) : (crit < thr);   // strict, EE/policy.py:33
+            double crit;
+            bool leave;
+            if constexpr (PATIENCE) {
+                crit = crit_f64(z, a.K, temp, 0);
+                // argmax of the scaled logits as they are written out (two f32 logits can round to one scaled value); first maximum wins
+                float best = (float)((double)z[0] / temp);
+                int am = 0;
+                for (int k = 1; k < a.K; ++k) {
+                    const float v = (float)((double)z[k] / temp);
+                    if (v > best) { best = v; am = k; }
+                }
+                const int run = (a.exit_index > 0 && p.prev[orig] == am) ? p.run[orig] + 1 : 0;
+                p.prev[orig] = am;
+                p.run[orig] = run;
+                leave = run >= patience;
+            } else {
+                crit = crit_f64(z, a.K, temp, a.criterion);
+                leave = a.criterion == 0 ? (crit > thr) : (crit < thr);   // strict, EE/policy.py:33
+            }
             if (a.no_exit) leave = false;
             if (a.is_final) leave = true;
             if (a.out_all_logits) {
@@ -139,7 +163,7 @@ __device__ __forceinline__ void exit_decide_body(const DecideArgs& a) {
             }
             if (a.head_logits && a.out_head_crit)
                 a.out_head_crit[(size_t)a.exit_index * a.B + orig] =
-                    crit_f32(a.head_logits + (size_t)i * a.Kh, a.Kh, a.criterion);
+                    crit_f32(a.head_logits + (size_t)i * a.Kh, a.Kh, PATIENCE ? 0 : a.criterion);
             if (leave) {
                 if (a.out_logits)
                     for (int k = 0; k < a.K; ++k) a.out_logits[(size_t)orig * a.K + k] = (float)((double)z[k] / temp);
@@ -187,10 +211,14 @@ __device__ __forceinline__ void exit_decide_body(const DecideArgs& a) {
     }
 }
 
-__global__ __launch_bounds__(1024) void exit_decide_kernel(DecideArgs a) { exit_decide_body(a); }
+__global__ __launch_bounds__(1024) void exit_decide_kernel(DecideArgs a) { exit_decide_body<false>(a, PatienceArgs{}); }
+__global__ __launch_bounds__(1024) void exit_decide_patience_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<true>(a, p); }
 
 void launch_decide(const DecideArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(exit_decide_kernel, dim3(1), dim3(1024), 0, s, a);
+}
+void launch_decide_patience(const DecideArgs& a, const PatienceArgs& p, hipStream_t s) {
+    hipLaunchKernelGGL(exit_decide_patience_kernel, dim3(1), dim3(1024), 0, s, a, p);
 }
 
 // Round 6: the head's output projection and the decision were built as ONE launch (every workgroup writes its documents' logits, fences,
@@ -352,6 +380,142 @@ void launch_policy_scan(const double* logits, int E1, int N, int K, const double
     if (grid > 4096) grid = 4096;
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(policy_scan_kernel, dim3(grid), dim3(256), 0, s, logits, E1, N, K, thr_dev, exits, pred, conf, counts);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Patience (PABEE) on a dumped (E1, N, K) float64 array, thread per document, in the shape of policy_scan_kernel:
+//   p_e = argmax_k logits[e][n][k] (first maximum), c_0 = 0, c_e = p_e == p_{e-1} ? c_{e-1} + 1 : 0,
+//   exit = first e with c_e >= t, else E1 - 1; confidence = float64 max-softmax of the row at that exit.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int argmax_f64(const double* z, int K) {
+    double m = z[0];
+    int am = 0;
+    for (int k = 1; k < K; ++k)
+        if (z[k] > m) { m = z[k]; am = k; }
+    return am;
+}
+
+__global__ __launch_bounds__(256) void patience_scan_kernel(const double* __restrict__ logits, int E1, int N, int K, int t,
+                                                            int* __restrict__ exits, double* __restrict__ pred,
+                                                            double* __restrict__ conf_out, int* __restrict__ counts) {
+    for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += gridDim.x * 256) {
+        int chosen = E1 - 1, prev = -1, run = 0;
+        for (int e = 0; e < E1; ++e) {
+            const int am = argmax_f64(logits + ((size_t)e * N + n) * K, K);
+            run = (e > 0 && am == prev) ? run + 1 : 0;
+            prev = am;
+            if (run >= t) { chosen = e; break; }
+        }
+        const double* z = logits + ((size_t)chosen * N + n) * K;
+        exits[n] = chosen;
+        if (conf_out) {
+            double m = z[0];
+            for (int k = 1; k < K; ++k) m = fmax(m, z[k]);
+            double s = 0.0;
+            for (int k = 0; k < K; ++k) s += exp(z[k] - m);
+            conf_out[n] = 1.0 / s;
+        }
+        if (pred)
+            for (int k = 0; k < K; ++k) pred[(size_t)n * K + k] = z[k];
+        if (counts) atomicAdd(&counts[chosen], 1);
+    }
+}
+
+void launch_patience_scan(const double* logits, int E1, int N, int K, int t, int* exits, double* pred, double* conf, int* counts,
+                          hipStream_t s) {
+    int grid = (N + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(patience_scan_kernel, dim3(grid), dim3(256), 0, s, logits, E1, N, K, t, exits, pred, conf, counts);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Patience sweep: V patience values over one dumped (E1, N, K) array.  Thread per document; the run sequence is computed ONCE:
+// since c_e grows by exactly one inside a run, the first exit with c_e >= t is the first with c_e == t, so the walk records
+// first[c] (c = 1 .. longest run) in LDS as (exit << 1 | correct) and every t is then one lookup (t beyond the longest run: the final
+// exit).  Hits, exit sums and the histogram are integers (per-block LDS sums, one 64-bit atomic per block and value): the results do not
+// depend on the order of arrival.  E1 <= kPatMaxE1.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kPatMaxE1 = 128;
+constexpr int kPatBlock = 128;
+
+__global__ __launch_bounds__(kPatBlock) void patience_sweep_kernel(const double* __restrict__ logits, const long long* __restrict__ refs,
+                                                                   int E1, int N, int K, const int* __restrict__ pats, int V,
+                                                                   unsigned long long* __restrict__ sums, int* __restrict__ hist) {
+    __shared__ unsigned short s_first[(kPatMaxE1 - 1) * kPatBlock];
+    __shared__ int s_hist[kPatMaxE1];
+    __shared__ unsigned long long s_red[kPatBlock / 64][2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = blockIdx.x * kPatBlock + tid;
+    const bool active = n < N;
+    int longest = 0;
+    unsigned rec0 = 0, recE = 0;                                     // records of exit 0 (t < 1) and of the final exit
+    if (active) {
+        const long long ref = refs[n];
+        int prev = -1, run = 0;
+        for (int e = 0; e < E1; ++e) {
+            const int am = argmax_f64(logits + ((size_t)e * N + n) * K, K);
+            run = (e > 0 && am == prev) ? run + 1 : 0;
+            prev = am;
+            const unsigned rec = ((unsigned)e << 1) | (am == ref ? 1u : 0u);
+            if (e == 0) rec0 = rec;
+            if (e == E1 - 1) recE = rec;
+            if (run > longest) { longest = run; s_first[(run - 1) * kPatBlock + tid] = (unsigned short)rec; }
+        }
+    }
+    for (int v = 0; v < V; ++v) {
+        const int t = pats[v];
+        if (hist) {
+            for (int e = tid; e < E1; e += kPatBlock) s_hist[e] = 0;
+            __syncthreads();
+        }
+        unsigned long long hits = 0, exs = 0;
+        if (active) {
+            const unsigned rec = t < 1 ? rec0 : t <= longest ? (unsigned)s_first[(t - 1) * kPatBlock + tid] : recE;
+            hits = rec & 1u;
+            exs = rec >> 1;
+            if (hist) atomicAdd(&s_hist[rec >> 1], 1);
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            hits += __shfl_xor(hits, o, 64);
+            exs += __shfl_xor(exs, o, 64);
+        }
+        if (lane == 0) { s_red[wave][0] = hits; s_red[wave][1] = exs; }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long h = 0, x = 0;
+            for (int w = 0; w < kPatBlock / 64; ++w) { h += s_red[w][0]; x += s_red[w][1]; }
+            atomicAdd(&sums[2 * v], h);
+            atomicAdd(&sums[2 * v + 1], x);
+        }
+        if (hist)
+            for (int e = tid; e < E1; e += kPatBlock)
+                if (s_hist[e]) atomicAdd(&hist[(size_t)v * E1 + e], s_hist[e]);
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void patience_sweep_finish_kernel(const unsigned long long* __restrict__ sums, int V, int N,
+                                                                    double* __restrict__ acc, double* __restrict__ mean_exit) {
+    for (int v = blockIdx.x * 256 + threadIdx.x; v < V; v += gridDim.x * 256) {
+        acc[v] = (double)sums[2 * v] / (double)N;
+        mean_exit[v] = (double)sums[2 * v + 1] / (double)N;
+    }
+}
+
+bool launch_patience_sweep(const double* logits, const long long* refs, int E1, int N, int K, const int* pats, int V, double* acc,
+                           double* mean_exit, int* hist, hipStream_t s) {
+    unsigned long long* sums = nullptr;
+    if (hipMallocAsync((void**)&sums, sizeof(unsigned long long) * 2 * V, s) != hipSuccess) return false;
+    (void)hipMemsetAsync(sums, 0, sizeof(unsigned long long) * 2 * V, s);
+    if (hist) (void)hipMemsetAsync(hist, 0, sizeof(int) * (size_t)V * E1, s);
+    hipLaunchKernelGGL(patience_sweep_kernel, dim3((N + kPatBlock - 1) / kPatBlock), dim3(kPatBlock), 0, s, logits, refs, E1, N, K, pats, V,
+                       sums, hist);
+    int grid = (V + 255) / 256;
+    if (grid > 1024) grid = 1024;
+    hipLaunchKernelGGL(patience_sweep_finish_kernel, dim3(grid), dim3(256), 0, s, sums, V, N, acc, mean_exit);
+    (void)hipFreeAsync(sums, s);
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

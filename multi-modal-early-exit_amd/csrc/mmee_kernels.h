@@ -64,7 +64,7 @@ struct HeadOutArgs {
 
 // thresholds, then temperatures, of one ee_graph_launch: a kernel ARGUMENT of set_thresholds_kernel (no host buffer has to outlive the call)
 struct ThrPack {
-    double v[2 * (64 + 4)];          // 2 x (MMEE_MAX_ENCODER_EXITS + 3 embedding exits + final)
+    double v[2 * (64 + 4) + 1];      // 2 x (MMEE_MAX_ENCODER_EXITS + 3 embedding exits + final), then the patience
     int n;
 };
 
@@ -95,6 +95,14 @@ struct DecideArgs {
     float* out_all_crit;             // (E+1,B)
     float* out_head_logits;          // (E,B,Kh)
     float* out_head_crit;            // (E,B)
+};
+
+// patience (MMEE_CRIT_PATIENCE): the decide kernel's second argument
+struct PatienceArgs {
+    int t;                           // exit once the argmax has stayed the same for t exits in a row
+    const double* t_ptr;             // captured-graph forwards: t at [0] of the device vector every ee_graph_launch refreshes; null: `t`
+    int* prev;                       // [max_docs] argmax at the document's previous exit, by original slot
+    int* run;                        // [max_docs] run counter c_e, by original slot
 };
 
 // X-space CLS probe (xprobe.hip)
@@ -147,6 +155,7 @@ void launch_patch_mean(const float* X, int H, const int* x_phys, const int* doc_
                        int max_docs, hipStream_t s);
 void launch_head_out(const HeadOutArgs& a, int max_docs, hipStream_t s);
 void launch_decide(const DecideArgs& a, hipStream_t s);
+void launch_decide_patience(const DecideArgs& a, const PatienceArgs& p, hipStream_t s);
 void launch_pack_results(const float* logits, const int* exit_layer, const float* conf, int n, int K, int* rows, hipStream_t s);
 void launch_unpack_results(const int* rows, int n, int K, float* logits, int* exit_layer, float* conf, hipStream_t s);
 void launch_compact_rows(const StageCounts* n_counts, const int* n_doc_off, const int* n_x_src, const int* n_meta_src,
@@ -166,6 +175,10 @@ void launch_gather_cls(const float* X, int H, const int* x_phys, const int* doc_
                        float* out, int max_docs, hipStream_t s, float split_inv = 0.f);
 void launch_policy_scan(const double* logits, int E1, int N, int K, const double* thr_dev, int* exits, double* pred,
                         double* conf, int* counts, hipStream_t s);
+void launch_patience_scan(const double* logits, int E1, int N, int K, int t, int* exits, double* pred, double* conf, int* counts,
+                          hipStream_t s);
+bool launch_patience_sweep(const double* logits, const long long* refs, int E1, int N, int K, const int* pats, int V, double* acc,
+                           double* mean_exit, int* hist, hipStream_t s);
 void launch_threshold_sweep(const double* conf, const unsigned char* correct, int E1, int N, const double* thr, int V,
                             double* acc, double* mean_exit, int* hist, hipStream_t s);
 void launch_msp_table(const double* logits, const long long* refs, int E1, int N, int K, double* conf, unsigned char* correct,

@@ -15,7 +15,7 @@ from typing import Dict, Mapping, Optional, Sequence, Union
 import numpy as np
 
 from . import capi
-from .config import ModelConfig
+from .config import ModelConfig, check_patience
 
 try:  # torch is plumbing (device tensors / streams); importing it must not be the reason the product "works"
     import torch
@@ -104,6 +104,9 @@ class EarlyExitEngine:
         with torch.cuda.device(self.device):
             capi.check(self.lib.ee_create(C.byref(c), C.byref(self._h)), None, "ee_create")
         self._finalized = False
+        self.patience = None
+        if ec.patience is not None:
+            self.set_patience(ec.patience)
 
     # ---- lifetime ------------------------------------------------------------------------------------------------
     def close(self):
@@ -190,11 +193,15 @@ class EarlyExitEngine:
                 want_all: bool = False, want_head: bool = False, want_hidden_cls: bool = False,
                 validate: bool = False, whole_layers: bool = False, probe_always: bool = False, xprobe: Optional[bool] = None,
                 one_term: bool = False, inputs_embeds=None, want_hidden_states: bool = False, out=None, head_mask=None,
-                want_attentions: bool = False, _capture: bool = False) -> EngineOutput:
+                want_attentions: bool = False, patience: Optional[int] = None, _capture: bool = False) -> EngineOutput:
         """``out``: optional preallocated ``(logits (B,K) f32, exit_layer (B,) i32, confidence (B,) f32)`` device tensors (contiguous; row
-        slices of larger tensors qualify) the kernels write into instead of fresh allocations -- MicroBatchedEngine hands each half its slice."""
+        slices of larger tensors qualify) the kernels write into instead of fresh allocations -- MicroBatchedEngine hands each half its slice.
+        ``patience``: when given, ``set_patience(patience)`` before the call (the criterion must be "patience" for it to matter); under the
+        patience criterion ``thresholds`` are ignored."""
         if not self._finalized:
             raise capi.MMEEError("load_weights() has not been called")
+        if patience is not None:
+            self.set_patience(patience)
         R = self.cfg.input_size
         px = self._dev(pixel_values, torch.float32, "pixel_values")
         emb = None
@@ -427,13 +434,22 @@ class EarlyExitEngine:
         return layers
 
     def set_criterion(self, strategy):
-        """Exit criterion of every later forward ("max_confidence" / "entropy"; ee_set_criterion).  The reference's driver overrides
+        """Exit criterion of every later forward ("max_confidence" / "entropy" / "patience"; ee_set_criterion).  The reference's driver overrides
         ``model.config.exit_config["inference_strategy"]`` after construction (EE/utils.py:62-78); modeling.py forwards that write here."""
         from .config import EarlyExitInference
         st = strategy if isinstance(strategy, EarlyExitInference) else EarlyExitInference(str(strategy))
         capi.check(self.lib.ee_set_criterion(self._h, st.code), self._h, "ee_set_criterion")
         self.exit_config.inference_strategy = st
         return st
+
+    def set_patience(self, t: int) -> int:
+        """Patience of every later forward and graph launch under the "patience" criterion (ee_set_patience): a document leaves at the first
+        exit where its argmax has stayed the same for ``t`` exits in a row (include/mmee.h).  Captured graphs read the current value at every
+        launch."""
+        t = check_patience(t)
+        capi.check(self.lib.ee_set_patience(self._h, t), self._h, "ee_set_patience")
+        self.patience = t
+        return t
 
     def clock_stamp(self):
         """Device tensor of capi.CLOCK_STAMP_WORDS int64: one (s_memtime, s_memrealtime) pair per CU as seen by one-wave workgroups enqueued on
@@ -477,10 +493,13 @@ class CapturedForward:
         self.engine, self.graph_id, self.inputs, self.outputs = engine, graph_id, inputs, outputs
 
     def launch(self, thresholds: Optional[Union[float, Sequence[float]]] = None, temperatures: Optional[Sequence[float]] = None,
-               validate: bool = False) -> EngineOutput:
+               validate: bool = False, patience: Optional[int] = None) -> EngineOutput:
         """Replay on torch's current stream with this launch's thresholds / temperatures; returns ``self.outputs`` (the same tensors every
-        time: copy what must outlive the next launch)."""
+        time: copy what must outlive the next launch).  ``patience``: ``engine.set_patience(patience)`` first; a graph captured under the
+        patience criterion replays with the engine's current patience either way."""
         eng = self.engine
+        if patience is not None:
+            eng.set_patience(patience)
         E = eng.E
         if thresholds is None:
             thresholds = eng.exit_config.global_threshold

@@ -182,6 +182,11 @@ class MicroBatchedEngine:
             st = e.set_criterion(strategy)
         return st
 
+    def set_patience(self, t: int) -> int:
+        for e in self.engines:
+            t = e.set_patience(t)
+        return t
+
     def clock_stamp(self):
         return self.engines[0].clock_stamp()
 

@@ -106,7 +106,7 @@ class LayoutLMv3EEForSequenceClassification:
             exit_config={"training_strategy": ec.training_strategy, "inference_strategy": ec.inference_strategy,
                          "global_threshold": ec.global_threshold, "exits": list(ec.exits),
                          "encoder_layer_strategy": ec.encoder_layer_strategy,
-                         "exit_head_num_layers": ec.exit_head_num_layers},
+                         "exit_head_num_layers": ec.exit_head_num_layers, "patience": ec.patience},
             EE_config=dict(config.EE_config), num_labels=config.num_labels,
             id2label={i: f"LABEL_{i}" for i in range(config.num_labels)}, use_return_dict=True,
             hidden_size=config.hidden_size, num_hidden_layers=config.num_hidden_layers)
@@ -156,8 +156,10 @@ class LayoutLMv3EEForSequenceClassification:
         return ((k, v) for k, v in self._weights.items())
 
     def exit_criterion(self, logits):
-        """``max_confidence`` / ``entropy`` on a logits tensor (EE/models/EE_modules.py:149-160)."""
+        """``max_confidence`` / ``entropy`` on a logits tensor (EE/models/EE_modules.py:149-160).  Patience has no per-exit criterion
+        (the reference's ``get_function`` has none for it, EE/models/EE_modules.py:130-137): ``NotImplementedError``."""
         self._sync_exit_config()
+        self._refuse_patience("exit_criterion")
         if str(self.model_config.exit_config.inference_strategy) == "max_confidence":
             return torch.softmax(logits, dim=1).max(dim=1)[0]
         e = torch.exp(logits)
@@ -169,8 +171,10 @@ class LayoutLMv3EEForSequenceClassification:
         ``model.config.exit_config["inference_strategy"]`` (EE/utils.py:62-78) never reaches its forward -- results agree there only because
         ``build_model`` merges the CLI configuration into ``EE_config`` BEFORE construction (EE/configs.py:389-393).  Here the dictionary is
         re-read at every call: a changed criterion is pushed down to the kernels (ee_set_criterion) AND into ``model_config.EE_config``, so that
-        ``exit_criterion()``, ``to_hf_dict()`` and the handle agree; ``early_exit`` reads the threshold from the same dictionary.  A strategy
-        the kernels do not implement (patience / lte) raises, as ``EarlyExitInference.get_sign`` does in the reference."""
+        ``exit_criterion()``, ``to_hf_dict()`` and the handle agree; ``early_exit`` reads the threshold (or, under patience, ``["patience"]``)
+        from the same dictionary.  Patience is an ``early_exit`` policy only: ``forward`` and ``exit_criterion`` raise ``NotImplementedError``
+        under it (``exit_states[j][1]`` is a per-exit criterion, and patience has none).  ``lte`` raises, as ``EarlyExitInference`` does in
+        the reference."""
         want = self.config.exit_config["inference_strategy"]
         want = str(getattr(want, "value", want))
         if want != str(self.engine.exit_config.inference_strategy):
@@ -178,6 +182,26 @@ class LayoutLMv3EEForSequenceClassification:
         if str(self.model_config.EE_config.get("inference_strategy")) != want:
             self.model_config.EE_config["inference_strategy"] = want
             self.config.EE_config["inference_strategy"] = want
+
+    def _is_patience(self) -> bool:
+        want = self.config.exit_config["inference_strategy"]
+        return str(getattr(want, "value", want)) == "patience"
+
+    def _refuse_patience(self, what):
+        if self._is_patience():
+            raise NotImplementedError(f"{what}: inference_strategy 'patience' has no per-exit criterion (exit_states[j][1]); "
+                                      "patience is an early_exit policy")
+
+    def _patience_kw(self, patience, kw):
+        """Under inference_strategy == "patience": the ``patience=`` argument, else ``config.exit_config["patience"]``; neither is a ValueError."""
+        if not self._is_patience():
+            if patience is not None:
+                raise ValueError("patience= is an argument of the 'patience' inference_strategy")
+            return
+        t = patience if patience is not None else self.config.exit_config.get("patience")
+        if t is None:
+            raise ValueError("inference_strategy 'patience' needs config.exit_config['patience'] or a patience= argument")
+        kw["patience"] = t
 
     # ---- chunked engine call -------------------------------------------------------------------------------------------
     def _run(self, tensors: Dict[str, Any], **kw) -> EngineOutput:
@@ -204,11 +228,16 @@ class LayoutLMv3EEForSequenceClassification:
     def forward(self, input_ids=None, attention_mask=None, bbox=None, pixel_values=None, labels=None,
                 token_type_ids=None, position_ids=None, head_mask=None, inputs_embeds=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None, **kwargs) -> EESequenceClassifierOutput:
+        """Every exit for every document (dump-all).  Under ``inference_strategy == "patience"`` this raises ``NotImplementedError``:
+        ``exit_states[j][1]`` is ``exit_criterion(logits)`` and the reference's ``get_function`` has no criterion for patience
+        (EE/models/EE_modules.py:130-137); patience is served by ``early_exit`` and ``Policy.patience_policy``."""
         if (input_ids is None and inputs_embeds is None) or pixel_values is None:
             # (the reference's own forward cannot run these either: with pixel_values=None `visual_embeddings` is unbound at
             # EE/models/LayoutLMv3.py:550, with neither input_ids nor inputs_embeds `embedding_output` is at :565)
             raise ValueError("the HIP path implements the multimodal evaluation input: input_ids (or inputs_embeds) AND pixel_values "
                              "(EE/utils.py:93-98); text-only / image-only calls are not built")
+        self._sync_exit_config()
+        self._refuse_patience("forward")
         # head_mask / output_attentions (EE/models/LayoutLMv3.py:382-385, 631-641, 219-220): served by side kernels of this dump-all forward
         # (csrc/attention_maps.hip); the fused attention kernels of the fast path never materialise a map
         out = self._run(dict(input_ids=input_ids, attention_mask=attention_mask, bbox=bbox, pixel_values=pixel_values,
@@ -259,10 +288,12 @@ class LayoutLMv3EEForSequenceClassification:
     # ---- the fast path ------------------------------------------------------------------------------------------------
     def early_exit(self, input_ids, attention_mask=None, bbox=None, pixel_values=None, token_type_ids=None,
                    position_ids=None, thresholds: Optional[Union[float, Sequence[float]]] = None,
-                   temperatures: Optional[Sequence[float]] = None, **kw) -> EngineOutput:
+                   temperatures: Optional[Sequence[float]] = None, patience: Optional[int] = None, **kw) -> EngineOutput:
         """(logits, exit_layer, confidence) with the policy test on the device: identical to running ``forward`` on
         everything and then ``Policy(...)`` (EE/eval.py:87-98), but deeper layers only see the surviving documents.
-        ``thresholds`` defaults to ``config.exit_config["global_threshold"]``."""
+        ``thresholds`` defaults to ``config.exit_config["global_threshold"]``.  Under ``inference_strategy == "patience"`` the thresholds are
+        ignored and the patience is ``patience=`` or ``config.exit_config["patience"]`` (``ValueError`` when neither is set)."""
+        self._patience_kw(patience, kw)
         if thresholds is None:
             thresholds = self.config.exit_config["global_threshold"]
         self._small_batch_schedule(pixel_values, kw)
@@ -306,13 +337,16 @@ class DiTEEForImageClassification(LayoutLMv3EEForSequenceClassification):
             raise ValueError("pixel_values is required")
         if head_mask is not None or output_attentions:
             raise NotImplementedError("head_mask / attention maps are not part of the evaluation hot path")
+        self._sync_exit_config()
+        self._refuse_patience("forward")
         out = self._run(dict(pixel_values=pixel_values), dump_all=True, want_all=True, want_head=True, validate=True,
                         want_hidden_states=bool(output_hidden_states))      # BeitEncoder: embedding output + every layer's output, (B, Pv, H)
         return self._pack(out, labels, return_dict)
 
     __call__ = forward
 
-    def early_exit(self, pixel_values=None, thresholds=None, temperatures=None, **kw) -> EngineOutput:
+    def early_exit(self, pixel_values=None, thresholds=None, temperatures=None, patience=None, **kw) -> EngineOutput:
+        self._patience_kw(patience, kw)
         if thresholds is None:
             thresholds = self.config.exit_config["global_threshold"]
         self._small_batch_schedule(pixel_values, kw)

@@ -48,14 +48,43 @@ def policy_scan_device(logits, thresholds, device=None, want_conf: bool = False)
     return exits, pred, conf, counts
 
 
+def patience_scan_device(logits, patience: int, device=None, want_conf: bool = False):
+    """Patience (include/mmee.h MMEE_CRIT_PATIENCE) on a dumped array: the first exit where the argmax has stayed the same for ``patience``
+    exits in a row, else the last exit.  Same inputs and returns as ``policy_scan_device`` (ee_patience_scan)."""
+    from .config import check_patience
+    t = check_patience(patience)
+    lib = capi.load()
+    dev = _require_torch_cuda(device)
+    if isinstance(logits, np.ndarray):
+        L = torch.from_numpy(np.ascontiguousarray(logits)).to(dev, dtype=torch.float64)
+    else:
+        L = logits.to(dev, dtype=torch.float64).contiguous()
+    if L.dim() != 3:
+        raise ValueError("logits must have shape (num_exits + 1, num_samples, num_labels)")
+    E1, N, K = L.shape
+    exits = torch.empty((N,), dtype=torch.int32, device=dev)
+    pred = torch.empty((N, K), dtype=torch.float64, device=dev)
+    conf = torch.empty((N,), dtype=torch.float64, device=dev) if want_conf else None
+    counts = torch.zeros((E1,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        rc = lib.ee_patience_scan(C.c_void_p(L.data_ptr()), E1, N, K, t, C.c_void_p(exits.data_ptr()), C.c_void_p(pred.data_ptr()),
+                                  C.c_void_p(conf.data_ptr()) if conf is not None else None, C.c_void_p(counts.data_ptr()), stream)
+    capi.check(rc, None, "ee_patience_scan")
+    return exits, pred, conf, counts
+
+
 class Policy:
     def __init__(self, logits, config) -> None:
         self.logits = logits
         self.config = config
 
-    def _finish(self, thresholds):
+    def _finish(self, thresholds=None, patience=None):
         num_exits, num_samples = self.logits.shape[0], self.logits.shape[1]
-        exits, pred, _, counts = policy_scan_device(self.logits, thresholds)
+        if patience is not None:
+            exits, pred, _, counts = patience_scan_device(self.logits, patience)
+        else:
+            exits, pred, _, counts = policy_scan_device(self.logits, thresholds)
         exits_store = exits.cpu().numpy().astype(np.int32)
         tgt = self.config.get("device", "cpu")
         predictions = pred.to(tgt) if str(tgt) != str(pred.device) else pred
@@ -66,6 +95,14 @@ class Policy:
     def max_confidence_global_thresholding_policy(self):
         """EE/policy.py:12-53: one global threshold ``config["exit_threshold"]``."""
         return self._finish(float(self.config["exit_threshold"]))
+
+    def patience_policy(self):
+        """Patience-based early exit (PABEE; the reference declares it, EE/models/EE_modules.py:123-124, and implements no policy for it):
+        ``config["patience"]`` = t >= 1, exit at the first e where the argmax has been the same for t exits in a row, else the last.
+        ``config["exit_policy"] = "patience_policy"`` selects it through EE/eval.py:91-98's ``getattr`` dispatch."""
+        if self.config.get("patience") is None:
+            raise ValueError('patience_policy needs config["patience"] (an integer >= 1)')
+        return self._finish(patience=self.config["patience"])
 
     def accuracy_calibration_heuristic(self):
         """EE/policy.py:55-111: per-exit thresholds minmax_eps(1 - accuracy/ece)."""

@@ -36,6 +36,31 @@ def msp_table(logits, references=None, device=None):
     return conf, corr
 
 
+def patience_sweep(logits, references, patiences, want_hist: bool = False, device=None):
+    """Every patience value of ``patiences`` (V,) over one dumped array ``logits`` (E1,N,K) with labels ``references`` (N,): for each t the
+    exits of the patience policy (include/mmee.h), the accuracy of the predictions at those exits and the mean exit (ee_patience_sweep: the
+    run sequence of a document is computed once for all t; integer sums, deterministic).  Returns device tensors
+    ``(accuracy (V,), mean_exit (V,), hist (V,E1) | None)``."""
+    from .config import check_patience
+    lib = capi.load()
+    dev = _require_torch_cuda(device)
+    to = lambda x, dt: (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else torch.as_tensor(x)).to(dev, dt).contiguous()
+    pats = [check_patience(t) for t in np.asarray(patiences).reshape(-1).tolist()]
+    L, refs = to(logits, torch.float64), to(references, torch.int64)
+    if L.dim() != 3 or tuple(refs.shape) != (L.shape[1],):
+        raise ValueError("logits (E1,N,K), references (N,)")
+    E1, N, K = L.shape
+    V = len(pats)
+    pt = torch.tensor(pats, dtype=torch.int32, device=dev)
+    acc = torch.empty((V,), dtype=torch.float64, device=dev)
+    mex = torch.empty((V,), dtype=torch.float64, device=dev)
+    hist = torch.empty((V, E1), dtype=torch.int32, device=dev) if want_hist else None
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    with torch.cuda.device(dev):
+        capi.check(lib.ee_patience_sweep(p(L), p(refs), E1, N, K, p(pt), V, p(acc), p(mex), p(hist), _stream()), None, "ee_patience_sweep")
+    return acc, mex, hist
+
+
 def threshold_sweep(conf, correct, thresholds, want_hist: bool = False, device=None):
     """For each threshold vector v: exits = (conf >= thr[v][:, None]).argmax(0); returns device tensors
     ``(accuracy (V,), mean_exit (V,), hist (V,E1) | None)``."""
