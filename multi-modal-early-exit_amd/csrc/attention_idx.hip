@@ -911,7 +911,7 @@ bool attention_idx_supports(const AttnArgs& a) {
     if (a.idx16 && !(a.pair_idx && a.lut1 && a.keymask && a.doc_flags && a.n1 >= 1 && a.n1 <= T1V_MAX && a.n_visual >= 0)) return false;
     return a.ctx_split && (a.pair_idx == nullptr || (a.bins1 >= 1 && a.bins1 <= BINS_MAX && a.bins2 >= 1 && a.bins2 <= BINS_MAX));
 }
-// can a handle with these bucket tables / this delta range run the 16-bit index?  (capi.hip decides once per handle)
+// can a handle with these bucket tables / this delta range run the 16-bit index?  (ee_create in capi.hip decides once per handle)
 bool attention_idx16_fits(int bins1, int bins2, int n1) { return bins1 >= 1 && bins1 <= BINS_MAX && bins2 >= 1 && bins2 <= BINS_MAX && n1 >= 1 && n1 <= T1V_MAX; }
 
 template <bool BIAS, int XP, int TERMS = 3, int IDX = 32>

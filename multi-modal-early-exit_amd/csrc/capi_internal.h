@@ -1,0 +1,214 @@
+// What the translation units of the C-ABI (include/mmee.h) share: the handle, its parameter / weight records, the error helpers every entry
+// point returns through, the allocator and the profiling scope.  Private to csrc/capi*.hip:
+//   capi.hip          the handle's error ring and allocator, and the loader (ee_create, ee_load_tensor, ee_finalize, ee_destroy)
+//   capi_forward.hip  the forward schedule (Forward, ee_forward) and its captured-graph form (ee_graph_*)
+//   capi_query.hip    what reads the last forward back or arms the next one (ee_profile*, ee_last_*, ee_suggest_probe_mask, ee_set_*)
+//   capi_tools.hip    entry points that never see a handle (clock stamps, policy sweeps, pack / unpack, image feed, ee_debug_*)
+#pragma once
+#include <cstdint>
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/mmee.h"
+#include "mmee_kernels.h"
+
+namespace mmee {
+namespace capi {
+
+struct Param {
+    float* ptr = nullptr;
+    std::vector<int64_t> shape;
+    bool loaded = false;
+    size_t numel() const {
+        size_t n = 1;
+        for (auto d : shape) n *= (size_t)d;
+        return n;
+    }
+};
+
+struct LayerW {
+    float *qkv_w, *qkv_b, *ao_w, *ao_b, *ao_g, *ao_beta, *f1_w, *f1_b, *f2_w, *f2_b, *f_g, *f_beta;
+    float *lam1 = nullptr, *lam2 = nullptr;   // BEiT layer scale (lambda_1 / lambda_2)
+    // MMEE_PREC_F32_SPLIT: the four big weights as split-f16 rows (built by ee_finalize) and 1 / weight scale
+    float *qkv_s = nullptr, *ao_s = nullptr, *f1_s = nullptr, *f2_s = nullptr;
+    float qkv_inv = 1.f, ao_inv = 1.f, f1_inv = 1.f, f2_inv = 1.f;
+};
+struct HeadW {
+    float *dense_w = nullptr, *dense_b = nullptr, *out_w = nullptr, *out_b = nullptr;
+    float* dense_s = nullptr;           // split precision: split-f16 rows of dense_w (the head's dense runs on the split GEMM kernel)
+    float dense_inv = 1.f;
+    int out_dim = 0;
+};
+// bookkeeping of a forward (ee_last_stage_counts / ee_suggest_probe_mask / ee_last_flops / ee_last_layer_plan read that of the last one)
+struct ForwardRecord {
+    int last_B = 0, last_T = 0, last_stages = 0;
+    uint32_t last_flags = 0;
+    bool last_gate_heads = true;                  // gate strategy: were the 2-way gate heads evaluated
+    std::vector<int> layer_stage;                 // stage whose rows the layer's attention / attention-out / FFN ran on; -1: none (probe only)
+    std::vector<int> layer_qkv_stage;             // stage whose rows the layer's Q|K|V projection ran on
+    std::vector<int> layer_probe_stage;           // stage whose CLS rows were probed before the layer's exit decision; -1: no probe
+    std::vector<int> layer_xprobe;                // 1: the layer's probe ran in X space
+    std::vector<int> exit_stage;                  // stage whose documents reached each exit
+};
+
+}  // namespace capi
+}  // namespace mmee
+
+struct ee_handle {
+    ee_config cfg;
+    std::string err;
+    int num_cus = 256;
+    bool finalized = false;
+    std::map<std::string, mmee::capi::Param> params;
+    std::vector<std::string> names;
+    std::vector<void*> allocs;
+    // model pointers
+    float *word, *type, *pos, *xtab, *ytab, *htab, *wtab, *emb_g, *emb_b;
+    float *patch_w, *patch_b, *cls_token, *pos_embed, *norm_g, *norm_b, *ln_g, *ln_b;
+    float *rel1, *relx, *rely;
+    std::vector<mmee::capi::LayerW> layers;
+    mmee::capi::HeadW emb_heads[3];
+    std::vector<mmee::capi::HeadW> enc_heads;
+    mmee::capi::HeadW classifier;
+    // derived
+    float *t1 = nullptr, *tx = nullptr, *ty = nullptr;
+    int n1 = 0, c1 = 0, n2 = 0, c2 = 0;
+    // workspace
+    float *Xs = nullptr, *Ys = nullptr;           // split-f16 copies of X / Y rows (MMEE_PREC_F32_SPLIT)
+    float* patch_s = nullptr;                     // split rows of the patch projection weight (when its shape fits the split kernel)
+    float patch_inv = 1.f;
+    float* absmax_dev = nullptr;
+    bool split = false;
+    unsigned* pair_idx = nullptr;                 // split mode, LayoutLMv3: one word per (query, key) pair of every document (attention_idx.hip)
+    unsigned char *lut1_dev = nullptr, *lut2_dev = nullptr;
+    int idx_nb = 0;
+    size_t idx_stride = 0;                        // dwords per document slab of pair_idx
+    // round 6, 16-bit pair index (attention_idx.hip IDX16): pair_idx holds 2 bytes per pair; the X-space probe reads the 32-bit words of query
+    // block 0 from pair_idx0 ([max_docs][idx_nb][1024]); key masks per (document, key tile), "a key inside the document is masked" per document
+    bool idx16 = false;
+    unsigned* pair_idx0 = nullptr;
+    unsigned* keymask = nullptr;
+    int* doc_flags = nullptr;
+    float* cls_f32 = nullptr;                     // split mode: CLS rows of the active documents rebuilt from the split planes
+    // CLS probe (probe-first layers): one row per active document
+    float *Yc = nullptr, *Ycs = nullptr, *H1c = nullptr, *Xc = nullptr, *Xcs = nullptr;
+    int* xp_order = nullptr;                      // [max_docs + 1]: documents by falling length, ticket counter
+    float *Qc = nullptr, *xp_u = nullptr, *xp_s0 = nullptr, *xp_c = nullptr, *xp_part = nullptr;      // X-space probe (xprobe.hip): CLS queries, u, q.b_k, weighted row sums
+    int* iota = nullptr;                          // 0 .. max_docs-1
+    float *X, *Y, *QKV, *CTX, *H1, *vis_raw, *text_part, *vis_part, *cat_part, *pooled[3], *hid, *hid2, *head_logits, *pol_logits;
+    int *text_dst, *emb_pos, *ntext, *row_src, *err_flag;
+    int* queue_heads = nullptr;                   // one work-queue counter per persistent launch of a forward
+    int n_queue_heads = 0, next_queue_head = 0;
+    mmee::RowMeta* meta[2];
+    int *doc_orig, *doc_off, *x_src, *meta_src;   // [(E+2)][max_docs+1]
+    mmee::StageCounts* counts;                    // [(E+2)]
+    double* thr_dev = nullptr;                    // scratch for ee_policy_scan
+    int32_t patience = 0;                         // ee_set_patience (0: not set); read by the decide launches under MMEE_CRIT_PATIENCE
+    int* pat_state = nullptr;                     // [2][max_docs]: argmax at the previous exit, run counter (by original document slot)
+    // optional per-kernel event timing (ee_profile)
+    bool prof_on = false;
+    struct ProfRec { int id; hipEvent_t a, b; double flops; };
+    std::vector<ProfRec> prof_recs;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;
+    size_t prof_used = 0;
+    // the workspace is shared by consecutive forwards: a forward enqueued on another stream than the previous one first
+    // waits for it (one handle = one forward in flight)
+    hipEvent_t fwd_done = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool has_fwd = false;
+    // err_flag of every forward, copied to a pinned host word of its own behind it (a ring: the caller may enqueue several forwards before
+    // any has finished).  A later call reports the oldest unreported error of a FINISHED forward without synchronising; a slot is only
+    // reused after its forward has been waited for and checked, so no error is ever overwritten unseen.
+    struct ErrSlot { hipEvent_t done = nullptr; bool pending = false; };
+    static constexpr int kErrSlots = 8;
+    ErrSlot errs[kErrSlots];
+    int* err_host = nullptr;                      // [kErrSlots] pinned
+    unsigned err_seq = 0;                         // forwards enqueued so far
+    mmee::capi::ForwardRecord rec;                // bookkeeping of the last forward
+    bool mask_on = false;                         // ee_set_probe_mask: the exit-layer schedule is pinned
+    const float* next_inputs_embeds = nullptr;    // ee_set_inputs_embeds: read by the next ee_forward, then cleared
+    float* next_hidden_out = nullptr;             // ee_set_hidden_states_out: filled by the next ee_forward, then cleared
+    const float* next_head_mask = nullptr;        // ee_set_head_mask: (L, heads) factors of the next ee_forward, then cleared
+    float* next_attn_out = nullptr;               // ee_set_attentions_out: (L, B, heads, S, S) filled by the next ee_forward, then cleared
+    uint64_t probe_mask = 0;
+    // captured-graph forms of ee_forward (ee_graph_capture): the launch list of one (inputs, B, T, flags, outputs) configuration as a hipGraphExec;
+    // thresholds / temperatures live in a device buffer the decide kernels read, refreshed in front of every replay
+    struct GraphRec {
+        hipGraphExec_t exec = nullptr;
+        double* thr_dev = nullptr;                // [2 * (E + 1) + 1]: thresholds, then temperatures (1.0 when the launch passes none), then the patience
+        int n_exits1 = 0;
+        bool no_exit = false;
+        bool patience = false;                    // captured under MMEE_CRIT_PATIENCE: launches need no thresholds
+        mmee::capi::ForwardRecord rec;            // bookkeeping of the captured forward, restored by every launch
+    };
+    std::vector<GraphRec> graphs;
+};
+
+namespace mmee {
+namespace capi {
+
+// Defined in capi.hip, once.  h == nullptr: the message goes to the library-wide slot ee_last_error(NULL) reads.
+int fail(ee_handle* h, const char* fmt, ...);
+
+#define HIP_OK(h, expr)                                                                                      \
+    do {                                                                                                     \
+        hipError_t e_ = (expr);                                                                              \
+        if (e_ != hipSuccess) return mmee::capi::fail(h, "%s failed: %s", #expr, hipGetErrorString(e_));     \
+    } while (0)
+
+// What every entry point that launches kernels returns through: a failed dynamic-LDS opt-in of one of ITS launchers (recorded per thread,
+// mmee_common.h) with the kernel's name, else the launch error, else 0.
+int launch_status(ee_handle* h, const char* who);
+
+// Error flags of forwards that were enqueued earlier and not reported yet, oldest first.  wait = false: only forwards that have finished
+// (stops at the first one still running: one handle's forwards finish in order); wait = true: waits for each.  all = false: returns at
+// the first forward with flags (the others stay pending); all = true: ORs every pending forward's flags.
+int take_errors(ee_handle* h, bool wait, bool all);
+int report_errors(ee_handle* h, int err, const char* whose);
+
+// HF relative_position_bucket as a LUT over delta in [-max_delta, max_delta] (capi.hip; ee_finalize and ee_bucket_lut)
+void bucket_lut_host(int num_buckets, int max_distance, int max_delta, unsigned char* out);
+
+template <typename T>
+int dev_alloc(ee_handle* h, T** p, size_t count) {
+    void* q = nullptr;
+    hipError_t e = hipMalloc(&q, count * sizeof(T) + 256);
+    if (e != hipSuccess) return fail(h, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
+    // the allocator hands back whatever the previous owner left: zero it, so that no kernel can ever act on another handle's stale
+    // counters or indices (tools/fuzz_schedules.py found a stale ticket counter this way; a few milliseconds per handle)
+    if (hipMemset(q, 0, count * sizeof(T) + 256) != hipSuccess) return fail(h, "hipMemset of a new allocation failed");
+    h->allocs.push_back(q);
+    *p = reinterpret_cast<T*>(q);
+    return 0;
+}
+
+// kernel roles reported by ee_profile_read (their names: kProfNames in capi_query.hip)
+enum { P_PREP = 0, P_EMBT, P_GPATCH, P_EMBV, P_GQKV, P_ATTN, P_GAO, P_LN, P_GUP, P_GDOWN, P_HEAD, P_DECIDE, P_COMPACT, P_GCLS, P_PROBE,
+       P_PAIRIDX, P_PSPLIT, P_HEADOUT, P_COUNT };
+
+struct ProfScope {
+    ee_handle* h;
+    hipStream_t s;
+    hipEvent_t b = nullptr;
+    ProfScope(ee_handle* h_, int id, hipStream_t s_) : h(h_), s(s_) {
+        if (!h->prof_on) return;
+        if (h->prof_used == h->prof_pool.size()) {
+            hipEvent_t a, bb;
+            (void)hipEventCreate(&a);
+            (void)hipEventCreate(&bb);
+            h->prof_pool.push_back({a, bb});
+        }
+        auto& ev = h->prof_pool[h->prof_used++];
+        h->prof_recs.push_back({id, ev.first, ev.second, 0.0});
+        b = ev.second;
+        (void)hipEventRecord(ev.first, s);
+    }
+    ~ProfScope() {
+        if (b) (void)hipEventRecord(b, s);
+    }
+};
+
+}  // namespace capi
+}  // namespace mmee

@@ -1,0 +1,235 @@
+// What reads the last forward of a handle back (ee_profile*, ee_last_stage_counts, ee_last_flops, ee_last_layer_plan, ee_suggest_probe_mask)
+// and the one-line setters that arm the next one (ee_set_*).
+#include <cstring>
+#include <vector>
+
+#include "capi_internal.h"
+
+using namespace mmee;
+using namespace mmee::capi;
+
+namespace {
+
+// kernel roles reported by ee_profile_read; the HIP symbol each role launches is in the second column
+const char* const kProfNames[] = {
+    "prep|doc_prep_kernel+doc_scan_kernel+row_meta_kernel",
+    "embed_text|embed_text_kernel",
+    "gemm_patch|patch_split_kernel+gemm_split_kernel<.., 0, false> (f32: gemm_f32_kernel<0,1>)",
+    "embed_visual|embed_visual_kernel+pool_finish_kernel",
+    "gemm_qkv|gemm_f32_kernel<0,0>",
+    "attention|attention_f32_kernel",
+    "gemm_attn_out|gemm_f32_kernel<2,0>",
+    "layernorm|ln_rows_kernel",
+    "gemm_ffn_up|gemm_f32_kernel<1,0>",
+    "gemm_ffn_down|gemm_f32_kernel<2,0>",
+    "exit_head|gemm_f32_kernel<3,0>+head_out_kernel",
+    "exit_decide|exit_decide_kernel (patience: exit_decide_patience_kernel)",
+    "compact|compact_rows_kernel",
+    "gather_cls|gather_cls_kernel",
+    "cls_probe|attention_idx_kernel+gemm_split_kernel<.., 1>+ln_rows_kernel+gather_cls_kernel (CLS rows of an exit layer, before its decision)",
+    // nested roles: each is timed INSIDE the role named in brackets (so a sum over roles must leave them out)
+    "pair_index|pair_index_kernel [inside prep]",
+    "patch_split|patch_split_kernel [inside gemm_patch]",
+    "head_out|head_out_kernel [inside exit_head]",
+};
+
+// Synchronises the stream, then copies the first n StageCounts (of the last forward) to the host.
+int read_stage_counts(ee_handle* h, void* stream, int n, std::vector<StageCounts>& sc) {
+    HIP_OK(h, hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
+    sc.resize(n);
+    HIP_OK(h, hipMemcpy(sc.data(), h->counts, sizeof(StageCounts) * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ee_profile(ee_handle* h, int32_t enable) {
+    if (!h) return 1;
+    h->prof_on = enable != 0;
+    h->prof_recs.clear();
+    h->prof_used = 0;
+    return 0;
+}
+
+int ee_profile_read(ee_handle* h, int32_t idx, char* name_out, int32_t name_cap, double* total_ms, int32_t* launches) {
+    if (!h) return 1;
+    if (idx < 0 || idx >= P_COUNT) return 2;
+    (void)hipDeviceSynchronize();
+    double ms = 0.0;
+    int n = 0;
+    for (auto& r : h->prof_recs)
+        if (r.id == idx) {
+            float t = 0.f;
+            if (hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) { ms += t; ++n; }
+        }
+    if (name_out && name_cap > 0) {
+        strncpy(name_out, kProfNames[idx], name_cap - 1);
+        name_out[name_cap - 1] = 0;
+    }
+    if (total_ms) *total_ms = ms;
+    if (launches) *launches = n;
+    return 0;
+}
+
+int ee_last_stage_counts(ee_handle* h, int32_t* docs_out, int32_t* rows_out, int32_t cap, int32_t* n_stages_out, void* stream) {
+    if (!h || !h->rec.last_stages) return fail(h, "ee_last_stage_counts: no forward has run");
+    const ForwardRecord& r = h->rec;
+    std::vector<StageCounts> sc;
+    if (read_stage_counts(h, stream, r.last_stages, sc)) return 1;
+    const int err = take_errors(h, true, true);       // every forward enqueued so far has finished: all of their flags are reported here
+    if (n_stages_out) *n_stages_out = r.last_stages;
+    for (int i = 0; i < r.last_stages && i < cap; ++i) {
+        if (docs_out) docs_out[i] = sc[r.exit_stage[i]].n_docs;
+        if (rows_out) rows_out[i] = sc[r.exit_stage[i]].n_rows;
+    }
+    return report_errors(h, err, "a forward since the last check");
+}
+
+int ee_set_inputs_embeds(ee_handle* h, const float* embeds) {
+    if (!h) return 1;
+    if (embeds && h->cfg.arch == MMEE_ARCH_BEIT) return fail(h, "ee_set_inputs_embeds: an image-only model has no text embeddings");
+    h->next_inputs_embeds = embeds;
+    return 0;
+}
+
+int ee_set_hidden_states_out(ee_handle* h, float* out) {
+    if (!h) return 1;
+    h->next_hidden_out = out;
+    return 0;
+}
+
+int ee_set_head_mask(ee_handle* h, const float* mask) {
+    if (!h) return 1;
+    h->next_head_mask = mask;
+    return 0;
+}
+
+int ee_set_attentions_out(ee_handle* h, float* out) {
+    if (!h) return 1;
+    h->next_attn_out = out;
+    return 0;
+}
+
+int ee_set_criterion(ee_handle* h, int32_t criterion) {
+    if (!h) return 1;
+    if (criterion != MMEE_CRIT_MAX_CONFIDENCE && criterion != MMEE_CRIT_ENTROPY && criterion != MMEE_CRIT_PATIENCE)
+        return fail(h, "ee_set_criterion: unknown criterion %d", criterion);
+    h->cfg.criterion = criterion;      // read by the decide kernel's arguments of every later ee_forward
+    return 0;
+}
+
+int ee_set_patience(ee_handle* h, int32_t t) {
+    if (!h) return 1;
+    if (t < 1) return fail(h, "ee_set_patience: t=%d, the patience must be >= 1", t);
+    h->patience = t;                   // eager forwards pass it by value; ee_graph_launch writes it to the graph's device vector
+    return 0;
+}
+
+int ee_set_probe_mask(ee_handle* h, int32_t enabled, uint64_t mask) {
+    if (!h) return 1;
+    h->mask_on = enabled != 0;
+    h->probe_mask = mask;
+    return 0;
+}
+
+// The cost model that used to pick the schedule inside ee_forward from "whichever earlier forward had finished" (rounds 2-4), as an explicit,
+// deterministic query: which exit layers are worth probing first, judged from the stage populations of the LAST forward on this handle.  A
+// probe pays when the rows it saves (attention, attention-out, FFN -- and under MMEE_FLAG_XPROBE the Q | K | V projection -- of the documents
+// that leave) cost more than the probe itself (a pass over every K | V row, or every LayerNorm row in X space, for the CLS queries + three
+// latency-bound GEMMs on one row per document).  Rates as measured on MI355X.
+int ee_suggest_probe_mask(ee_handle* h, uint32_t flags, uint64_t* mask_out, void* stream) {
+    if (!h || !mask_out) return fail(h, "ee_suggest_probe_mask: null argument");
+    const ForwardRecord& r = h->rec;
+    if (!r.last_stages) return fail(h, "ee_suggest_probe_mask: no forward has run");
+    if (r.last_flags & MMEE_FLAG_NO_EXIT) return fail(h, "ee_suggest_probe_mask: the last forward was a dump (nobody left): run a thresholded forward first");
+    std::vector<StageCounts> sc;
+    if (read_stage_counts(h, stream, r.last_stages + 1, sc)) return 1;
+    const ee_config& c = h->cfg;
+    const bool beit = c.arch == MMEE_ARCH_BEIT;
+    const double H = c.hidden_size, I = c.intermediate_size;
+    const int L = c.num_hidden_layers;
+    uint64_t mask = 0;
+    bool xs = false;
+    if (h->split && !beit && (flags & MMEE_FLAG_XPROBE) && h->Qc && h->pair_idx && c.rel_pos_bins <= 64 && c.rel_2d_pos_bins <= 64) {
+        mmee::XProbeArgs chk{};
+        chk.H = c.hidden_size; chk.heads = c.num_attention_heads; chk.bins1 = c.rel_pos_bins; chk.bins2 = c.rel_2d_pos_bins; chk.pair_idx = h->pair_idx;
+        const int G = c.input_size / c.patch_size;
+        xs = mmee::xprobe_supports(chk, r.last_T + G * G + 1);
+    }
+    for (int k = 0; k < c.n_encoder_exits && h->split; ++k) {
+        const int l = c.encoder_exit_layers[k] - 1;
+        if (l == L - 1) continue;                     // the last layer: always the probe alone (LayoutLMv3) / always whole (BEiT mean pooling)
+        const int st = c.n_embedding_exits + k;      // stage whose documents reach this decision
+        if (st + 1 > r.last_stages) break;
+        const double rows = sc[st].n_rows, leave = (double)sc[st].n_rows - (double)sc[st + 1].n_rows;
+        if (rows <= 0) { mask |= 1ull << l; continue; }
+        const double len = (double)sc[st].sum_len_sq / rows;      // mean keys per query
+        const double t_row = 2.0 * (H * H + 2.0 * H * I + (xs ? 3.0 * H * H : 0.0)) / 380e12 + 4.0 * len * H / 200e12;
+        const double cost = ((2.0 * H + I) / 32.0) * 0.9e-6 + (xs ? 180e-6 + rows * 4.0 * H / 4.5e12 : 100e-6 + rows * 8.0 * H / 3.6e12);
+        if (leave * t_row > 1.1 * cost) mask |= 1ull << l;
+    }
+    *mask_out = mask;
+    return 0;
+}
+
+int ee_last_flops(ee_handle* h, double* gemm_flops, double* attn_flops, void* stream) {
+    if (!h || !h->rec.last_stages) return fail(h, "ee_last_flops: no forward has run");
+    const ForwardRecord& r = h->rec;
+    std::vector<StageCounts> sc;
+    if (read_stage_counts(h, stream, r.last_stages, sc)) return 1;
+    const ee_config& c = h->cfg;
+    const double H = c.hidden_size, I = c.intermediate_size;
+    const int G = c.input_size / c.patch_size;
+    double gf = 2.0 * r.last_B * G * G * (double)(c.num_channels * c.patch_size * c.patch_size) * H, af = 0.0;
+    for (int l = 0; l < c.num_hidden_layers; ++l) {      // the CLS probes are not in here: ee_last_layer_plan reports them
+        if (r.layer_qkv_stage[l] >= 0) gf += 2.0 * sc[r.layer_qkv_stage[l]].n_rows * 3.0 * H * H;
+        if (r.layer_stage[l] >= 0) {
+            const StageCounts& s = sc[r.layer_stage[l]];
+            gf += 2.0 * s.n_rows * (H * H + 2.0 * H * I);
+            af += 4.0 * (double)s.sum_len_sq * H;
+        }
+    }
+    const int E = r.last_stages - 1;
+    const double ko = c.strategy == MMEE_STRATEGY_RAMP ? c.num_labels : 2;
+    for (int e = 0; e <= E; ++e) {
+        const double n = sc[r.exit_stage[e]].n_docs;
+        const bool fin = e == E;
+        const double dense = (fin || c.exit_head_num_layers == 2) ? 2.0 * H * H : 0.0;
+        const bool gate = !fin && c.strategy == MMEE_STRATEGY_GATE;
+        if (!gate || r.last_gate_heads) gf += n * (dense + 2.0 * H * (fin ? c.num_labels : ko));
+        if (gate) gf += n * (2.0 * H * H + 2.0 * H * c.num_labels);
+    }
+    if (gemm_flops) *gemm_flops = gf;
+    if (attn_flops) *attn_flops = af;
+    return 0;
+}
+
+int ee_last_layer_plan(ee_handle* h, int32_t* rows_qkv, int32_t* rows_main, int32_t* docs_probe, int32_t cap, double* probe_flops, void* stream) {
+    if (!h || !h->rec.last_stages) return fail(h, "ee_last_layer_plan: no forward has run");
+    const ForwardRecord& r = h->rec;
+    std::vector<StageCounts> sc;
+    if (read_stage_counts(h, stream, r.last_stages, sc)) return 1;
+    const ee_config& c = h->cfg;
+    const double H = c.hidden_size, I = c.intermediate_size;
+    double pf = 0.0;
+    for (int l = 0; l < c.num_hidden_layers; ++l) {
+        const int q = r.layer_qkv_stage[l], m = r.layer_stage[l], p = r.layer_probe_stage[l];
+        if (l < cap) {
+            if (rows_qkv) rows_qkv[l] = q >= 0 ? sc[q].n_rows : 0;
+            if (rows_main) rows_main[l] = m >= 0 ? sc[m].n_rows : 0;
+            if (docs_probe) docs_probe[l] = p >= 0 ? sc[p].n_docs : 0;
+        }
+        // probe: 32 queries x every key of the document (QK^T and PV), then attention-out + FFN on one row per document
+        if (p >= 0) {
+            if (r.layer_xprobe[l])      // X space: q, u, v projections of one row per document + two passes of heads x H per row
+                pf += 6.0 * sc[p].n_docs * H * H + 4.0 * (double)sc[p].n_rows * c.num_attention_heads * H + 2.0 * sc[p].n_docs * (H * H + 2.0 * H * I);
+            else pf += 4.0 * 32.0 * sc[p].n_rows * H + 2.0 * sc[p].n_docs * (H * H + 2.0 * H * I);
+        }
+    }
+    if (probe_flops) *probe_flops = pf;
+    return 0;
+}
+
+}  // extern "C"

@@ -271,7 +271,7 @@ __device__ __forceinline__ void split_store_tile16(const GemmArgs& g, float* sme
     if (OUT_SPLIT) split_flag_overflow(amax, g.err_flag);
 }
 
-// TAG only names the instantiation (1 = the CLS-probe launches of capi.hip, so that a profiler keeps them apart from the
+// TAG only names the instantiation (1 = the CLS-probe launches of capi_forward.hip, so that a profiler keeps them apart from the
 // layer's own GEMMs); the code is the same, and so is every result bit.
 // TERMS = 1 (MMEE_FLAG_ONE_TERM): only hi x hi -- plain f16 operands, f32 accumulate; the lo planes are fetched with their rows but never read.
 template <typename Cfg, int EPI, bool OUT_SPLIT, bool DIAG = false, int TAG = 0, int TERMS = 3>

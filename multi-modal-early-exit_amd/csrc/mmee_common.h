@@ -28,7 +28,7 @@ inline int diag_env_int(const char* name, int dflt) {
 // and a failed opt-in is neither discarded nor left to surface as a generic launch error: it is recorded with the kernel's name and the
 // byte count, and ee_forward / the stand-alone entry points report it (take_lds_error).  Round 6: the slot is PER THREAD -- a
 // launcher runs on the thread of the entry point that called it, so the failure is reported by THAT call (every entry point that launches
-// drains the slot before it returns: launch_status() in capi.hip), never by an unrelated forward of another handle or thread.
+// drains the slot before it returns: launch_status() in capi.hip, declared in capi_internal.h), never by an unrelated forward of another handle or thread.
 struct LdsOptInError {
     std::mutex mu;
     int code = 0;
@@ -427,7 +427,7 @@ struct AttnArgs {
     const float *w1, *wx, *wy;       // rel_pos_bias / rel_pos_x_bias / rel_pos_y_bias weights, [heads][bins]
     int bins1, bins2;
     float inv_sqrt_d;
-    // probe-first layers (capi.hip): the split attention kernels only
+    // probe-first layers (capi_forward.hip): the split attention kernels only
     const int* qkv_doc_off;          // [n_docs] row offsets of the documents' Q | K | V rows when those are still in the previous stage's
                                      // numbering; null: doc_off
     int q_limit;                     // > 0: only queries < q_limit of every document (the CLS probe asks for the first block)

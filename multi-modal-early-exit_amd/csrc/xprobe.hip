@@ -1,7 +1,7 @@
 // The CLS probe of an exit layer in X SPACE (precision mode MMEE_PREC_F32_SPLIT, LayoutLMv3; MMEE_FLAG_XPROBE).
 //
 // An exit head reads ONE row of a layer's output, the CLS row (EE/models/LayoutLMv3.py:226, 757-768), and probe-first layers decide from that
-// row before the rest of the layer runs (capi.hip).  The probe of rounds 1-2 still projected Q | K | V for EVERY row of the stage first (the
+// row before the rest of the layer runs (capi_forward.hip).  The probe of rounds 1-2 still projected Q | K | V for EVERY row of the stage first (the
 // CLS query attends to all keys and values of its document) and then streamed all K | V rows once more (1.46 GB at the first exit of the
 // bench batch).  But the CLS context does not need K and V as matrices.  With q = (W_q x_cls + b_q) / sqrt(d) of one head (HF:243-263):
 //     score_j = q . k_j = q . (W_k x_j + b_k) = (W_k^T q) . x_j + q . b_k                       u := W_k^T q  (H values per head)
@@ -9,7 +9,7 @@
 // (p = softmax of the biased, masked scores, HF:265-288; sum p = 1).  So the probe reads the LayerNorm rows x_j themselves -- 3 KB per row
 // instead of 6 KB of K | V, and no Q | K | V projection has to exist yet: the layer's Q | K | V GEMM then runs for the documents that STAY
 // only, and not at all in the last layer.  Four small launches:
-//   1. Q of the CLS rows: the split GEMM on one row per document (capi.hip; W_q is the first third of the fused Q | K | V weight),
+//   1. Q of the CLS rows: the split GEMM on one row per document (capi_forward.hip; W_q is the first third of the fused Q | K | V weight),
 //   2. xprobe_u_kernel     u[d][h][:] = W_k,h^T q[d][h], s0[d][h] = q . b_k, the power-of-two plane scale of u, and the documents'
 //                          order by falling length (weights streamed once per 8 documents),
 //   3. xprobe_attn_kernel  one workgroup per document, longest first; its rows cross HBM -> LDS once (LDS-DMA, 16-row tiles, ring of

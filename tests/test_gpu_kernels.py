@@ -45,7 +45,7 @@ def _first_c_tiles(N, cus):
 
 
 def _w_scale(W):
-    """ee_finalize's weight scale (ee_finalize in csrc/capi.hip): the power of two that puts max|w| in [2^12, 2^13), capped at 2^8."""
+    """ee_finalize's weight scale (build_split under ee_finalize in csrc/capi.hip): the power of two that puts max|w| in [2^12, 2^13), capped at 2^8."""
     mx = float(W.abs().max())
     e = 8 if mx == 0.0 else min(8, 13 - int(np.frexp(mx)[1]))
     return float(2.0 ** e)

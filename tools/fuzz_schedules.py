@@ -1,6 +1,6 @@
 """Randomised cross-check of the exit-layer schedules (GPU box only): for random shapes / exit sets / strategies / thresholds the
 probe-first, whole-layer, default, pinned and cost-model-suggested schedules and the dump-all rows must agree bit for bit, and the X-space probe within tolerance.  Not a test (minutes); run after touching
-the layer loop of csrc/capi.hip:  python tools/fuzz_schedules.py [n_cases [seed [large|big]]].  Each case draws its label count from
+the layer loop of csrc/capi_forward.hip:  python tools/fuzz_schedules.py [n_cases [seed [large|big]]].  Each case draws its label count from
 {2, 10, 16, 64}."""
 import importlib
 import os
