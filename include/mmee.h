@@ -21,6 +21,9 @@
  *                                                 (EE/thresh.py:184-215, EE/large_scale.py:68-84).
  *   ee_set_patience / ee_patience_scan /        <- EarlyExitInference.PATIENCE, declared by the reference (EE/models/EE_modules.py:
  *   ee_patience_sweep                              123-124, PABEE: Zhou et al., NeurIPS 2020) but not implemented there; semantics below.
+ *   ee_config.use_lte / ee_lte_scan             <- learning-to-exit (BERxiT's LTE): encoder.lte_classifier = nn.Linear(hidden_size, 1) + sigmoid on
+ *                                                  the CLS row after every exit layer, `lte_output < lte_th[i]` leaves (EE/models/LayoutLMv3.py:
+ *                                                  140-149, 229-268; switched on by EE_config["use_lte"]); semantics below.
  *
  * Conventions: every function returns 0 on success, non-zero on error (message via ee_last_error).  All pointers
  * marked "dev" are device (HBM) pointers borrowed from the caller for the duration of the enqueued work; kernels are
@@ -37,7 +40,7 @@
 extern "C" {
 #endif
 
-#define MMEE_ABI_VERSION 3
+#define MMEE_ABI_VERSION 4
 #define MMEE_MAX_ENCODER_EXITS 64
 
 /* embedding-level exits, in the order the reference evaluates them (EE/models/LayoutLMv3.py:465-605) */
@@ -55,6 +58,22 @@ enum { MMEE_CRIT_MAX_CONFIDENCE = 0, MMEE_CRIT_ENTROPY = 1, MMEE_CRIT_PATIENCE =
  * Outputs keep their contract: out_logits = the scaled logits of the chosen exit, out_conf = the float64 max-softmax of those scaled logits
  * (rounded to float32), out_all_crit (dump-all) = the same max-softmax at every exit, out_head_crit = the max-softmax of the raw head logits.
  * Thresholds are ignored (may be NULL); temperatures act only through the scaled logits.
+ */
+/*
+ * ee_config.use_lte (learning-to-exit, LTE).  The exit decision is a learned gate instead of a criterion on the logits.  Two more parameters
+ * are expected, after all the others: layoutlmv3.encoder.lte_classifier.weight (1, H) and layoutlmv3.encoder.lte_classifier.bias (1,).
+ * Score of encoder exit e and of the final classifier:  u_e(n) = 1 / (1 + exp(-(w . x_e(n) + b))),  x_e(n) = the float32 CLS row leaving that
+ * layer, i.e. the row the exit's head reads and out_hidden_cls reports (split precision: rebuilt exactly as (hi + lo) / 16).  Arithmetic is
+ * float64 throughout: the float32 inputs widened, a fixed summation order (lane l of one wave sums columns 4l + 256k + j in the order k, j;
+ * the 64 lane sums are then added by a butterfly) that does not depend on which documents share the launch, exp and the comparison in float64;
+ * the stored value is rounded to float32.  Document n leaves at the first encoder exit e with u_e(n) < thresholds[e] (strict, as
+ * `lte_output < self.lte_th[i]`), else at the final exit.  Embedding-level exits have no CLS row: they are evaluated (their rows appear in the
+ * dump-all outputs), never release anybody, and their criterion row holds 1.0f.  MMEE_FLAG_NO_EXIT and the final exit behave as without LTE.
+ * out_all_crit[e] and out_conf carry the LTE score ("the criterion value, lower is surer", as under entropy); out_logits, out_all_logits,
+ * out_head_logits and out_head_crit are exactly what they are without use_lte (out_head_crit stays ee_config.criterion on the raw head
+ * logits); temperatures act on the returned logits only; the score does not look at the head (ramps, gates, 1- and 2-layer heads).
+ * Refused: use_lte with MMEE_CRIT_PATIENCE (at ee_create or through ee_set_criterion) and with MMEE_ARCH_BEIT.  Bound at ee_create: captured
+ * graphs keep reading the thresholds from the device vector of each ee_graph_launch.
  */
 /* model family: LayoutLMv3 (text + layout + image, the reference's EE model) or BEiT / DiT (image only; BASELINE configs[4],
  * the reference's "dit" branch EE/configs.py:429-449 — exit heads there are this build's extrapolation) */
@@ -124,6 +143,8 @@ typedef struct ee_config {
     int32_t use_abs_pos;                            /* BEiT: use_absolute_position_embeddings */
     int32_t layer_scale;                            /* BEiT: layer_scale_init_value > 0 (lambda_1 / lambda_2 present) */
     int32_t use_mean_pooling;                       /* BEiT: must be 1 (DiT); pooled = LayerNorm(mean of patch tokens) */
+    /* learning-to-exit (appended in ABI version 4) */
+    int32_t use_lte;                                /* EE_config["use_lte"]: the exit test is the LTE score (semantics above) */
 } ee_config;
 
 int ee_create(const ee_config* cfg, ee_handle** out);
@@ -149,6 +170,7 @@ const char* ee_expected_tensor_name(const ee_handle* h, int32_t i);
  *   bbox           dev int64 (B,T,4)      pixel_values    dev float (B,C,R,R)
  *   token_type_ids dev int64 (B,T) or NULL (= zeros)      position_ids dev int64 (B,T) or NULL (= pad-aware cumsum)
  *   thresholds     host double [E+1]: exit e leaves when sign(crit_e, thresholds[e]) (strict); entry E (final) unused.
+ *                  Under ee_config.use_lte: encoder exit e leaves when u_e < thresholds[e] (strict); entries of embedding exits unused.
  *                  Ignored (may be NULL) under MMEE_CRIT_PATIENCE, which needs ee_set_patience before its first thresholded forward
  *   temperatures   host double [E+1] or NULL: logits of exit e are divided by temperatures[e] before the criterion
  *                  and in every returned logit (calibrated logits, EE/eval.py:321-323)
@@ -282,6 +304,14 @@ int ee_policy_scan(const double* logits, int32_t E1, int32_t N, int32_t K, const
  */
 int ee_patience_scan(const double* logits, int32_t E1, int32_t N, int32_t K, int32_t patience, int32_t* exits, double* predictions,
                      double* confidence, int32_t* counts, void* stream);
+/*
+ * The LTE policy (ee_config.use_lte semantics) on dumped arrays: scores dev double (E1,N) (the LTE score of every exit; rows of embedding
+ * exits hold 1.0, which no threshold <= 1 releases), logits dev double (E1,N,K) or NULL with predictions NULL, thresholds host double [E1]
+ * (entry E1-1 unused).  exit(n) = the first e < E1-1 with scores[e,n] < thresholds[e] (strict), else E1-1.  exits dev int32 (N,),
+ * predictions dev double (N,K) or NULL (the logits row of the chosen exit), counts dev int32 [E1] or NULL (documents per exit).
+ */
+int ee_lte_scan(const double* scores, const double* logits, int32_t E1, int32_t N, int32_t K, const double* thresholds, int32_t* exits,
+                double* predictions, int32_t* counts, void* stream);
 /*
  * V patience values at once over one dumped array (the patience counterpart of ee_threshold_sweep / EE/eval.py:186-210): logits dev double
  * (E1,N,K) with E1 <= 128, references dev int64 (N,), patiences dev int32 (V,).  exit(v,n) as ee_patience_scan with t = patiences[v];

@@ -9,7 +9,7 @@ import ctypes as C
 import os
 from typing import Optional
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 MAX_ENCODER_EXITS = 64
 EXIT_KIND = {"vision_avg": 0, "text_avg": 1, "text_visual_concat": 2}
 FLAG_DENSE_ROWS = 1
@@ -51,6 +51,7 @@ class EEConfig(C.Structure):
         ("exit_head_num_layers", C.c_int32), ("strategy", C.c_int32), ("criterion", C.c_int32),
         ("max_docs", C.c_int32), ("max_text_len", C.c_int32), ("precision", C.c_int32),
         ("arch", C.c_int32), ("use_abs_pos", C.c_int32), ("layer_scale", C.c_int32), ("use_mean_pooling", C.c_int32),
+        ("use_lte", C.c_int32),
     ]
 
 
@@ -84,6 +85,7 @@ SYMBOLS = {
     "ee_set_attentions_out": (C.c_int, [_vp, _vp]),
     "ee_policy_scan": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _vp]),
     "ee_patience_scan": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ee_lte_scan": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _vp, _vp, _vp]),
     "ee_patience_sweep": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "ee_pack_results": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "ee_unpack_results": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),

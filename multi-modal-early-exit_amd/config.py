@@ -120,6 +120,9 @@ class ExitConfig:
         self.patience = kwargs.get("patience", None)
         if self.patience is not None:
             self.patience = check_patience(self.patience)
+        # learning-to-exit (EE/models/LayoutLMv3.py:140): the exit test is sigmoid(lte_classifier(CLS row)) < threshold (include/mmee.h);
+        # the reference's real switch -- inference_strategy = "lte" stays unimplemented, as its get_function() is
+        self.use_lte = bool(kwargs.get("use_lte", False))
 
     # ---- derived views used by the hot path -------------------------------------------------
     @property
@@ -147,6 +150,7 @@ class ExitConfig:
             "encoder_layer_strategy": str(self.encoder_layer_strategy),
             "exit_head_num_layers": self.exit_head_num_layers,
             "patience": self.patience,
+            "use_lte": self.use_lte,
         }
 
 

@@ -158,6 +158,10 @@ int check_config(const ee_config& c) {
     if (c.precision == MMEE_PREC_F32_SPLIT && (c.num_attention_heads < 1 || c.rel_pos_bins < 2 || c.rel_2d_pos_bins < 2) && !beit)
         return fail(nullptr, "bad relative-position configuration");
     if (c.exit_head_num_layers != 1 && c.exit_head_num_layers != 2) return fail(nullptr, "exit_head_num_layers must be 1 or 2");
+    if (c.use_lte && beit)
+        return fail(nullptr, "use_lte: learning-to-exit is built for MMEE_ARCH_LAYOUTLMV3 only (the BEiT / DiT variant has no lte_classifier)");
+    if (c.use_lte && c.criterion == MMEE_CRIT_PATIENCE)
+        return fail(nullptr, "use_lte: learning-to-exit and MMEE_CRIT_PATIENCE are two exit decisions; a handle takes one of them");
     return 0;
 }
 
@@ -271,6 +275,10 @@ int register_layoutlmv3(ee_handle* h) {
     for (int k = 0; k < c.n_encoder_exits && !rc; ++k)
         rc |= add_head(h, p + "encoder.early_exits." + std::to_string(k), &h->enc_heads[k], H, out_dim, two);
     rc |= add_head(h, "classifier", &h->classifier, H, K, true);       // HF:799-823, always dense + out_proj
+    if (c.use_lte) {                                                   // one gate shared by all exits, EE/models/LayoutLMv3.py:140-142
+        rc |= add_param(h, p + "encoder.lte_classifier.weight", &h->lte_w, {1, H});
+        rc |= add_param(h, p + "encoder.lte_classifier.bias", &h->lte_b, {1});
+    }
     return rc;
 }
 
@@ -359,6 +367,7 @@ int alloc_workspace(ee_handle* h) {
     rc |= dev_alloc(h, &h->counts, (size_t)(E + 2));
     rc |= dev_alloc(h, &h->thr_dev, 256);
     rc |= dev_alloc(h, &h->pat_state, 2 * Bm);
+    if (c.use_lte) rc |= dev_alloc(h, &h->lte_score, Bm);
     return rc;
 }
 

@@ -480,7 +480,10 @@ struct Forward {
 
     // in_split / split_rows: the same input rows as split planes (LayerNorm outputs scaled by kSplitScaleX), when they exist: the head's
     // dense then runs on the split GEMM kernel (128 x 128 tiles of the CLS-probe launches) instead of the f32 MFMA kernel
-    void run_head(const HeadW& hw, const float* in, int ld, const int* gather, float* hid, float* out, const float* in_split, const int* split_rows) {
+    // lte: the launch of the output projection also leaves the LTE scores of these rows in h->lte_score (head_out_lte_kernel)
+    struct LteRows { const float* in; int ld; const int* gather; float split_inv; };
+    void run_head(const HeadW& hw, const float* in, int ld, const int* gather, float* hid, float* out, const float* in_split, const int* split_rows,
+                  const LteRows* lte = nullptr) {
         const int* n_docs_ptr = &h->counts[cur].n_docs;
         const float* hin = in;
         int hld = ld;
@@ -503,6 +506,10 @@ struct Forward {
         HeadOutArgs ho{};
         ho.in = hin; ho.ld = hld; ho.gather = hg; ho.W = hw.out_w; ho.b = hw.out_b; ho.H = H; ho.Ko = hw.out_dim;
         ho.n_docs_ptr = n_docs_ptr; ho.out = out;
+        if (lte) {
+            ho.lte_in = lte->in; ho.lte_ld = lte->ld; ho.lte_gather = lte->gather; ho.lte_split_inv = lte->split_inv;
+            ho.lte_w = h->lte_w; ho.lte_b = h->lte_b; ho.lte_out = h->lte_score;
+        }
         { ProfScope po(h, P_HEADOUT, s); launch_head_out(ho, B, s); }
     }
 
@@ -520,26 +527,31 @@ struct Forward {
 
     void x_dense() { x_phys = S_doc_off(cur); use_row_src = false; }      // a layer wrote X densely in the numbering of stage `cur`
 
-    // exit head (or the final classifier), decision, compaction of the documents that stay
+    // exit head (or the final classifier), decision, compaction of the documents that stay.  cls_row: `in` is the CLS row leaving a layer
+    // (false: the pooled input of an embedding-level exit).  use_lte: the launch that projects the policy logits -- the one head launch every
+    // exit has -- also scores the CLS rows, read where the head reads them: the split planes when they exist (the probes leave no f32 copy
+    // for 2-layer heads), else the f32 rows.  No launch is added.
     void run_exit(const HeadW* hw, const float* in, int ld, const int* gather, bool is_final, const float* in_split = nullptr,
-                  const int* split_rows = nullptr) {
+                  const int* split_rows = nullptr, bool cls_row = true) {
         const float* pol;
         const float* head = nullptr;
         int Kh = K;
+        const LteRows lte_rows = in_split ? LteRows{in_split, H, split_rows, 1.0f / mmee::kSplitScaleX} : LteRows{in, ld, gather, 0.f};
+        const LteRows* lte = (c.use_lte && cls_row) ? &lte_rows : nullptr;
         {
             ProfScope ps(h, P_HEAD, s);
             if (is_final) {
-                run_head(h->classifier, in, ld, gather, h->hid, h->pol_logits, in_split, split_rows);
+                run_head(h->classifier, in, ld, gather, h->hid, h->pol_logits, in_split, split_rows, lte);
                 pol = h->pol_logits;
             } else if (c.strategy == MMEE_STRATEGY_GATE) {
                 // the policy only ever sees classifier(gate input) (EE/utils.py:183-188); the 2-way gate logits (exit_states) are
                 // computed when the caller asked for them (the dump of model.forward), not in the fast path
                 const bool want_gate = a.out_head_logits || a.out_head_crit;
                 if (want_gate) run_head(*hw, in, ld, gather, h->hid, h->head_logits, in_split, split_rows);
-                run_head(h->classifier, in, ld, gather, h->hid2, h->pol_logits, in_split, split_rows);  // gated_logits, EE/models/LayoutLMv3.py:768
+                run_head(h->classifier, in, ld, gather, h->hid2, h->pol_logits, in_split, split_rows, lte);  // gated_logits, EE/models/LayoutLMv3.py:768
                 pol = h->pol_logits; head = want_gate ? h->head_logits : nullptr; Kh = 2;      // 2-way gate heads, EE/models/LayoutLMv3.py:83
             } else {
-                run_head(*hw, in, ld, gather, h->hid, h->head_logits, in_split, split_rows);
+                run_head(*hw, in, ld, gather, h->hid, h->head_logits, in_split, split_rows, lte);
                 pol = h->head_logits; head = h->head_logits; Kh = K;
             }
         }
@@ -562,6 +574,10 @@ struct Forward {
             pa.prev = h->pat_state; pa.run = h->pat_state + c.max_docs;
             ProfScope ps(h, P_DECIDE, s);
             launch_decide_patience(d, pa, s);
+        } else if (c.use_lte) {
+            d.lte_score = lte ? h->lte_score : nullptr;
+            ProfScope ps(h, P_DECIDE, s);
+            launch_decide_lte(d, s);
         } else {
             ProfScope ps(h, P_DECIDE, s);
             launch_decide(d, s);
@@ -683,7 +699,7 @@ struct Forward {
         x_phys = S_x_src(0);
         for (int i = 0; i < c.n_embedding_exits; ++i) {
             const int kind = c.embedding_exits[i];
-            run_exit(&h->emb_heads[kind], h->pooled[kind], H, S_doc_orig(cur), false);
+            run_exit(&h->emb_heads[kind], h->pooled[kind], H, S_doc_orig(cur), false, nullptr, nullptr, false);
         }
         gather_hidden(0, x_out(), x_phys, x_inv());
         dump_hidden(0);

@@ -107,6 +107,9 @@ struct ee_handle {
     double* thr_dev = nullptr;                    // scratch for ee_policy_scan
     int32_t patience = 0;                         // ee_set_patience (0: not set); read by the decide launches under MMEE_CRIT_PATIENCE
     int* pat_state = nullptr;                     // [2][max_docs]: argmax at the previous exit, run counter (by original document slot)
+    // learning-to-exit (ee_config.use_lte): encoder.lte_classifier (weight [H], bias [1]) and the float64 scores of the exit being decided
+    float *lte_w = nullptr, *lte_b = nullptr;
+    double* lte_score = nullptr;                  // [max_docs], by the stage's document index
     // optional per-kernel event timing (ee_profile)
     bool prof_on = false;
     struct ProfRec { int id; hipEvent_t a, b; double flops; };

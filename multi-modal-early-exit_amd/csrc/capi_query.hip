@@ -22,15 +22,15 @@ const char* const kProfNames[] = {
     "layernorm|ln_rows_kernel",
     "gemm_ffn_up|gemm_f32_kernel<1,0>",
     "gemm_ffn_down|gemm_f32_kernel<2,0>",
-    "exit_head|gemm_f32_kernel<3,0>+head_out_kernel",
-    "exit_decide|exit_decide_kernel (patience: exit_decide_patience_kernel)",
+    "exit_head|gemm_f32_kernel<3,0>+head_out_kernel (use_lte: head_out_lte_kernel)",
+    "exit_decide|exit_decide_kernel (patience: exit_decide_patience_kernel, use_lte: exit_decide_lte_kernel)",
     "compact|compact_rows_kernel",
     "gather_cls|gather_cls_kernel",
     "cls_probe|attention_idx_kernel+gemm_split_kernel<.., 1>+ln_rows_kernel+gather_cls_kernel (CLS rows of an exit layer, before its decision)",
     // nested roles: each is timed INSIDE the role named in brackets (so a sum over roles must leave them out)
     "pair_index|pair_index_kernel [inside prep]",
     "patch_split|patch_split_kernel [inside gemm_patch]",
-    "head_out|head_out_kernel [inside exit_head]",
+    "head_out|head_out_kernel / head_out_lte_kernel [inside exit_head]",
 };
 
 // Synchronises the stream, then copies the first n StageCounts (of the last forward) to the host.
@@ -116,6 +116,8 @@ int ee_set_criterion(ee_handle* h, int32_t criterion) {
     if (!h) return 1;
     if (criterion != MMEE_CRIT_MAX_CONFIDENCE && criterion != MMEE_CRIT_ENTROPY && criterion != MMEE_CRIT_PATIENCE)
         return fail(h, "ee_set_criterion: unknown criterion %d", criterion);
+    if (criterion == MMEE_CRIT_PATIENCE && h->cfg.use_lte)
+        return fail(h, "ee_set_criterion: MMEE_CRIT_PATIENCE on a use_lte handle: learning-to-exit and patience are two exit decisions");
     h->cfg.criterion = criterion;      // read by the decide kernel's arguments of every later ee_forward
     return 0;
 }

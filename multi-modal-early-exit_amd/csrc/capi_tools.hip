@@ -69,6 +69,23 @@ int ee_patience_scan(const double* logits, int32_t E1, int32_t N, int32_t K, int
     return launch_status(nullptr, "ee_patience_scan");
 }
 
+int ee_lte_scan(const double* scores, const double* logits, int32_t E1, int32_t N, int32_t K, const double* thresholds, int32_t* exits,
+                double* predictions, int32_t* counts, void* stream) {
+    if (!thresholds || E1 < 1 || E1 > 256 || N < 0 || K < 1 || (N > 0 && (!scores || !exits)) || (predictions && !logits))
+        return fail(nullptr, "ee_lte_scan: bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_lte_scan: no HIP device");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    double* thr_dev = nullptr;
+    if (hipMallocAsync((void**)&thr_dev, sizeof(double) * E1, s) != hipSuccess) return fail(nullptr, "ee_lte_scan: hipMallocAsync failed");
+    if (hipMemcpyAsync(thr_dev, thresholds, sizeof(double) * E1, hipMemcpyHostToDevice, s) != hipSuccess)
+        return fail(nullptr, "ee_lte_scan: threshold copy failed");
+    if (counts && hipMemsetAsync(counts, 0, sizeof(int) * E1, s) != hipSuccess) return fail(nullptr, "ee_lte_scan: memset failed");
+    if (N > 0) launch_lte_scan(scores, logits, E1, N, K, thr_dev, exits, predictions, counts, s);
+    (void)hipFreeAsync(thr_dev, s);
+    return launch_status(nullptr, "ee_lte_scan");
+}
+
 int ee_patience_sweep(const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, const int32_t* patiences, int32_t V,
                       double* acc, double* mean_exit, int32_t* exit_hist, void* stream) {
     if (!logits || !references || !patiences || !acc || !mean_exit || E1 < 1 || E1 > 128 || N < 1 || K < 1 || V < 0)

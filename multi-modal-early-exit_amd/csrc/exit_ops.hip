@@ -18,7 +18,11 @@ namespace mmee {
 // ---------------------------------------------------------------------------------------------------------------
 // out[i][c] = <in[row(i)], W[c]> + b[c]; one wave per document
 // ---------------------------------------------------------------------------------------------------------------
-template <int WAVES>
+// LTE (ee_config.use_lte): the same wave also scores its document, u = sigmoid(w . x + b) on the CLS row the exit's head reads (a second row
+// source: the head of a 2-layer exit reads its dense layer's output here).  float64 throughout, in a fixed order: lane l adds its columns
+// 4l + 256k + j in the order k, j; the lane sums go through one butterfly.  Nothing depends on which documents share the launch.  The
+// LTE = false instantiation is the kernel as it was.
+template <int WAVES, bool LTE>
 __device__ __forceinline__ void head_out_body(const HeadOutArgs& a) {
     const int n = *a.n_docs_ptr;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -45,16 +49,35 @@ __device__ __forceinline__ void head_out_body(const HeadOutArgs& a) {
             s = wave_sum(s);
             if (lane == 0) a.out[(size_t)i * a.Ko + o] = s + a.b[o];
         }
+        if constexpr (LTE) {
+            const float* lx = a.lte_in + (size_t)(a.lte_gather ? a.lte_gather[i] : i) * a.lte_ld;
+            double t = 0.0;
+#pragma unroll
+            for (int k = 0; k < kMaxNV; ++k) {
+                const int c = 4 * lane + 256 * k;
+                if (c < a.H) {
+                    const f32x4 v = a.lte_split_inv != 0.f ? load_split4(lx, c, a.lte_split_inv) : *reinterpret_cast<const f32x4*>(lx + c);
+                    const f32x4 wv = *reinterpret_cast<const f32x4*>(a.lte_w + c);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) t += (double)v[j] * (double)wv[j];
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+            if (lane == 0) a.lte_out[i] = 1.0 / (1.0 + exp(-(t + (double)a.lte_b[0])));
+        }
     }
 }
 
-__global__ __launch_bounds__(256) void head_out_kernel(HeadOutArgs a) { head_out_body<4>(a); }
+__global__ __launch_bounds__(256) void head_out_kernel(HeadOutArgs a) { head_out_body<4, false>(a); }
+__global__ __launch_bounds__(256) void head_out_lte_kernel(HeadOutArgs a) { head_out_body<4, true>(a); }
 
 void launch_head_out(const HeadOutArgs& a, int max_docs, hipStream_t s) {
     int grid = (max_docs + 3) / 4;
     if (grid > 1024) grid = 1024;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(head_out_kernel, dim3(grid), dim3(256), 0, s, a);
+    if (a.lte_out) hipLaunchKernelGGL(head_out_lte_kernel, dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(head_out_kernel, dim3(grid), dim3(256), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -105,10 +128,15 @@ __device__ inline double crit_f64(const float* z, int K, double temp, int criter
 // PATIENCE (PABEE, MMEE_CRIT_PATIENCE): the exit test is "the argmax of the scaled logits has stayed the same for t exits in a row"
 // instead of a threshold test.  The criterion written to the outputs is the max-softmax; the run state of document `orig` is
 // (p.prev[orig], p.run[orig]), indexed by the original slot so that compaction never moves it, and written unconditionally at
-// exit 0, which every document reaches (no reset launch).  The max_confidence / entropy kernel is the PATIENCE = false instantiation.
+// exit 0, which every document reaches (no reset launch).
+// LTE (ee_config.use_lte): the test is "the float64 score head_out_lte_kernel left in a.lte_score is strictly below the threshold"; the score
+// is what the outputs carry as the criterion.  Embedding exits have no score (a.lte_score null): 1.0, nobody leaves.
+// The max_confidence / entropy kernel is the DECIDE_THRESHOLD instantiation.
 // ---------------------------------------------------------------------------------------------------------------
-template <bool PATIENCE>
+enum { DECIDE_THRESHOLD = 0, DECIDE_PATIENCE = 1, DECIDE_LTE = 2 };
+template <int MODE>
 __device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const PatienceArgs& p) {
+    constexpr bool PATIENCE = MODE == DECIDE_PATIENCE;
     __shared__ int s_cnt[16], s_rows[16];
     __shared__ unsigned long long s_sq[16];
     __shared__ int s_carry_docs, s_carry_rows;
@@ -145,6 +173,9 @@ __device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const Pati
                 p.prev[orig] = am;
                 p.run[orig] = run;
                 leave = run >= patience;
+            } else if constexpr (MODE == DECIDE_LTE) {
+                crit = a.lte_score ? a.lte_score[i] : 1.0;
+                leave = a.lte_score && crit < thr;                        // strict, EE/models/LayoutLMv3.py:262
             } else {
                 crit = crit_f64(z, a.K, temp, a.criterion);
                 leave = a.criterion == 0 ? (crit > thr) : (crit < thr);   // strict, EE/policy.py:33
@@ -211,14 +242,18 @@ __device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const Pati
     }
 }
 
-__global__ __launch_bounds__(1024) void exit_decide_kernel(DecideArgs a) { exit_decide_body<false>(a, PatienceArgs{}); }
-__global__ __launch_bounds__(1024) void exit_decide_patience_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<true>(a, p); }
+__global__ __launch_bounds__(1024) void exit_decide_kernel(DecideArgs a) { exit_decide_body<DECIDE_THRESHOLD>(a, PatienceArgs{}); }
+__global__ __launch_bounds__(1024) void exit_decide_patience_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<DECIDE_PATIENCE>(a, p); }
+__global__ __launch_bounds__(1024) void exit_decide_lte_kernel(DecideArgs a) { exit_decide_body<DECIDE_LTE>(a, PatienceArgs{}); }
 
 void launch_decide(const DecideArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(exit_decide_kernel, dim3(1), dim3(1024), 0, s, a);
 }
 void launch_decide_patience(const DecideArgs& a, const PatienceArgs& p, hipStream_t s) {
     hipLaunchKernelGGL(exit_decide_patience_kernel, dim3(1), dim3(1024), 0, s, a, p);
+}
+void launch_decide_lte(const DecideArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(exit_decide_lte_kernel, dim3(1), dim3(1024), 0, s, a);
 }
 
 // Round 6: the head's output projection and the decision were built as ONE launch (every workgroup writes its documents' logits, fences,
@@ -427,6 +462,34 @@ void launch_patience_scan(const double* logits, int E1, int N, int K, int t, int
     if (grid > 4096) grid = 4096;
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(patience_scan_kernel, dim3(grid), dim3(256), 0, s, logits, E1, N, K, t, exits, pred, conf, counts);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// LTE on dumped arrays (ee_lte_scan), thread per document, in the shape of policy_scan_kernel: the first e < E1 - 1 whose score is
+// strictly below its threshold, else E1 - 1.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void lte_scan_kernel(const double* __restrict__ scores, const double* __restrict__ logits, int E1, int N,
+                                                       int K, const double* __restrict__ thr, int* __restrict__ exits,
+                                                       double* __restrict__ pred, int* __restrict__ counts) {
+    for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += gridDim.x * 256) {
+        int chosen = E1 - 1;
+        for (int e = 0; e < E1 - 1; ++e)
+            if (scores[(size_t)e * N + n] < thr[e]) { chosen = e; break; }
+        exits[n] = chosen;
+        if (pred) {
+            const double* z = logits + ((size_t)chosen * N + n) * K;
+            for (int k = 0; k < K; ++k) pred[(size_t)n * K + k] = z[k];
+        }
+        if (counts) atomicAdd(&counts[chosen], 1);
+    }
+}
+
+void launch_lte_scan(const double* scores, const double* logits, int E1, int N, int K, const double* thr_dev, int* exits, double* pred,
+                     int* counts, hipStream_t s) {
+    int grid = (N + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(lte_scan_kernel, dim3(grid), dim3(256), 0, s, scores, logits, E1, N, K, thr_dev, exits, pred, counts);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -60,6 +60,14 @@ struct HeadOutArgs {
     int H, Ko;
     const int* n_docs_ptr;
     float* out;                      // [n_docs][Ko]
+    // learning-to-exit (ee_config.use_lte): a second row source and one more output, walked by the same wave.  lte_out null: no score
+    const float* lte_in;             // CLS rows the exit's head reads: f32 rows, or split-f16 planes when lte_split_inv != 0
+    int lte_ld;
+    const int* lte_gather;           // optional: the row of active doc i is lte_in[lte_gather[i]]
+    float lte_split_inv;             // 1 / plane scale of split rows; 0: f32 rows
+    const float* lte_w;              // [H]  encoder.lte_classifier.weight
+    const float* lte_b;              // [1]
+    double* lte_out;                 // [n_docs] u = sigmoid(w . x + b), float64
 };
 
 // thresholds, then temperatures, of one ee_graph_launch: a kernel ARGUMENT of set_thresholds_kernel (no host buffer has to outlive the call)
@@ -76,6 +84,7 @@ struct DecideArgs {
     const double* thr_ptr;           // captured-graph forwards (ee_graph_capture): threshold / temperature of exit e at [exit_index] of device
     const double* temp_ptr;          // vectors refreshed in front of every replay; null: the by-value arguments above
     int criterion, is_final, no_exit, exit_index, B;
+    const double* lte_score;         // LTE decide kernel: [n_docs] float64 scores of this exit; null (embedding exits): score 1, nobody leaves
     // current stage
     const StageCounts* counts;
     const int* doc_orig;
@@ -156,6 +165,7 @@ void launch_patch_mean(const float* X, int H, const int* x_phys, const int* doc_
 void launch_head_out(const HeadOutArgs& a, int max_docs, hipStream_t s);
 void launch_decide(const DecideArgs& a, hipStream_t s);
 void launch_decide_patience(const DecideArgs& a, const PatienceArgs& p, hipStream_t s);
+void launch_decide_lte(const DecideArgs& a, hipStream_t s);
 void launch_pack_results(const float* logits, const int* exit_layer, const float* conf, int n, int K, int* rows, hipStream_t s);
 void launch_unpack_results(const int* rows, int n, int K, float* logits, int* exit_layer, float* conf, hipStream_t s);
 void launch_compact_rows(const StageCounts* n_counts, const int* n_doc_off, const int* n_x_src, const int* n_meta_src,
@@ -177,6 +187,8 @@ void launch_policy_scan(const double* logits, int E1, int N, int K, const double
                         double* conf, int* counts, hipStream_t s);
 void launch_patience_scan(const double* logits, int E1, int N, int K, int t, int* exits, double* pred, double* conf, int* counts,
                           hipStream_t s);
+void launch_lte_scan(const double* scores, const double* logits, int E1, int N, int K, const double* thr_dev, int* exits, double* pred,
+                     int* counts, hipStream_t s);
 bool launch_patience_sweep(const double* logits, const long long* refs, int E1, int N, int K, const int* pats, int V, double* acc,
                            double* mean_exit, int* hist, hipStream_t s);
 void launch_threshold_sweep(const double* conf, const unsigned char* correct, int E1, int N, const double* thr, int V,

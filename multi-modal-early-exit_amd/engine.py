@@ -97,6 +97,8 @@ class EarlyExitEngine:
         c.use_abs_pos = int(cfg.use_absolute_position_embeddings)
         c.layer_scale = int(cfg.layer_scale_init_value > 0)
         c.use_mean_pooling = int(cfg.use_mean_pooling)
+        self.use_lte = bool(ec.use_lte)     # bound at ee_create: two more parameters, the LTE score as the exit test (include/mmee.h)
+        c.use_lte = int(self.use_lte)
         if self.beit:
             c.max_text_len = self.max_text_len = 0
         self.precision = precision          # resolved: "fp32" or "split"

@@ -36,6 +36,7 @@ class MicroBatchedEngine:
         self.device, self.cfg, self.exit_config = e0.device, e0.cfg, e0.exit_config
         self.E, self.K, self.Kh, self.precision, self.beit = e0.E, e0.K, e0.Kh, e0.precision, e0.beit
         self.xprobe_default = e0.xprobe_default
+        self.use_lte = e0.use_lte
         self.max_text_len = e0.max_text_len
         with torch.cuda.device(self.device):
             self.streams = [torch.cuda.Stream(device=self.device) for _ in range(self.n)]

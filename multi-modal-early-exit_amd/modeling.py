@@ -106,7 +106,7 @@ class LayoutLMv3EEForSequenceClassification:
             exit_config={"training_strategy": ec.training_strategy, "inference_strategy": ec.inference_strategy,
                          "global_threshold": ec.global_threshold, "exits": list(ec.exits),
                          "encoder_layer_strategy": ec.encoder_layer_strategy,
-                         "exit_head_num_layers": ec.exit_head_num_layers, "patience": ec.patience},
+                         "exit_head_num_layers": ec.exit_head_num_layers, "patience": ec.patience, "use_lte": ec.use_lte},
             EE_config=dict(config.EE_config), num_labels=config.num_labels,
             id2label={i: f"LABEL_{i}" for i in range(config.num_labels)}, use_return_dict=True,
             hidden_size=config.hidden_size, num_hidden_layers=config.num_hidden_layers)
@@ -266,13 +266,19 @@ class LayoutLMv3EEForSequenceClassification:
                 for j in range(E):
                     exit_losses.append(F.cross_entropy(out.head_logits[j], lab))
                     exit_criteria.append(out.head_crit[j])
-        exit_criteria.append(out.all_crit[E])                  # :871-872
+        # :871-872.  use_lte: all_crit carries the LTE scores (include/mmee.h), so the final entry -- exit_criterion(logits) in the reference --
+        # is, like the losses above, an evaluation by-product of the returned logits
+        use_lte = bool(getattr(self.engine, "use_lte", False))
+        exit_criteria.append(self.exit_criterion(logits) if use_lte else out.all_crit[E])
+        # lte_output (EE/models/LayoutLMv3.py:234-237, 304): one (B,) score per encoder exit
+        n_emb = len(self.model_config.exit_config.embedding_exits)
+        lte_output = [out.all_crit[j] for j in range(n_emb, E)] if use_lte else None
         # output_hidden_states (EE/models/LayoutLMv3.py:887-896 passes the encoder's tuple through): L + 1 tensors of (B, T + Pv, H)
         hidden_states = None if out.hidden_states is None else tuple(out.hidden_states[l] for l in range(out.hidden_states.shape[0]))
         attentions = None if out.attentions is None else tuple(out.attentions[l] for l in range(out.attentions.shape[0]))      # L x (B, heads, S, S)
         res = EESequenceClassifierOutput(loss=loss, logits=logits, hidden_states=hidden_states, attentions=attentions,
                                          exit_losses=exit_losses, exit_criteria=exit_criteria, exit_states=exit_states,
-                                         gated_logits=gated)
+                                         gated_logits=gated, lte_output=lte_output)
         if return_dict is False:
             # EE/models/LayoutLMv3.py:883-885: `(logits,) + outputs[1:]`, the loss in front when labels were passed, where `outputs` is the
             # backbone's own tuple `(sequence_output, [all_hidden_states], [all_attentions])` (:287-296, 654-655) -- the exit fields exist
@@ -292,7 +298,9 @@ class LayoutLMv3EEForSequenceClassification:
         """(logits, exit_layer, confidence) with the policy test on the device: identical to running ``forward`` on
         everything and then ``Policy(...)`` (EE/eval.py:87-98), but deeper layers only see the surviving documents.
         ``thresholds`` defaults to ``config.exit_config["global_threshold"]``.  Under ``inference_strategy == "patience"`` the thresholds are
-        ignored and the patience is ``patience=`` or ``config.exit_config["patience"]`` (``ValueError`` when neither is set)."""
+        ignored and the patience is ``patience=`` or ``config.exit_config["patience"]`` (``ValueError`` when neither is set).  Under
+        ``EE_config["use_lte"]`` the default threshold is the same ``global_threshold``, repeated for every exit, as the reference's
+        ``enable_lte()`` repeats its one threshold (EE/models/LayoutLMv3.py:147-149); ``confidence`` is the LTE score."""
         self._patience_kw(patience, kw)
         if thresholds is None:
             thresholds = self.config.exit_config["global_threshold"]

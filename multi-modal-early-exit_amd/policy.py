@@ -74,14 +74,41 @@ def patience_scan_device(logits, patience: int, device=None, want_conf: bool = F
     return exits, pred, conf, counts
 
 
+def lte_scan_device(scores, logits, thresholds, device=None):
+    """Learning-to-exit (include/mmee.h ``use_lte``) on dumped arrays: the first exit e < E1 - 1 whose score is strictly below its threshold,
+    else the last exit.  ``scores`` (E1,N) (rows of embedding-level exits hold 1.0), ``logits`` (E1,N,K), ``thresholds`` scalar or (E1,).
+    Returns device tensors (exits int32, predictions float64, counts int32) (ee_lte_scan)."""
+    lib = capi.load()
+    dev = _require_torch_cuda(device)
+    to = lambda x: (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x).to(dev, dtype=torch.float64).contiguous()
+    S, L = to(scores), to(logits)
+    if L.dim() != 3 or tuple(S.shape) != tuple(L.shape[:2]):
+        raise ValueError("scores must have shape (num_exits + 1, num_samples) and logits (num_exits + 1, num_samples, num_labels)")
+    E1, N, K = L.shape
+    thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float64).reshape(-1), (E1,)) if np.ndim(thresholds) \
+        else np.full((E1,), float(thresholds))
+    thr_c = (C.c_double * E1)(*[float(t) for t in thr])
+    exits = torch.empty((N,), dtype=torch.int32, device=dev)
+    pred = torch.empty((N, K), dtype=torch.float64, device=dev)
+    counts = torch.zeros((E1,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        rc = lib.ee_lte_scan(C.c_void_p(S.data_ptr()), C.c_void_p(L.data_ptr()), E1, N, K, thr_c, C.c_void_p(exits.data_ptr()),
+                             C.c_void_p(pred.data_ptr()), C.c_void_p(counts.data_ptr()), stream)
+    capi.check(rc, None, "ee_lte_scan")
+    return exits, pred, counts
+
+
 class Policy:
     def __init__(self, logits, config) -> None:
         self.logits = logits
         self.config = config
 
-    def _finish(self, thresholds=None, patience=None):
+    def _finish(self, thresholds=None, patience=None, lte_scores=None):
         num_exits, num_samples = self.logits.shape[0], self.logits.shape[1]
-        if patience is not None:
+        if lte_scores is not None:
+            exits, pred, counts = lte_scan_device(lte_scores, self.logits, thresholds)
+        elif patience is not None:
             exits, pred, _, counts = patience_scan_device(self.logits, patience)
         else:
             exits, pred, _, counts = policy_scan_device(self.logits, thresholds)
@@ -103,6 +130,20 @@ class Policy:
         if self.config.get("patience") is None:
             raise ValueError('patience_policy needs config["patience"] (an integer >= 1)')
         return self._finish(patience=self.config["patience"])
+
+    def lte_policy(self):
+        """Learning-to-exit (EE/models/LayoutLMv3.py:229-268 on dumped arrays): ``config["lte_scores"]`` (E1,N), the ``all_crit`` rows of a
+        ``use_lte`` dump; exit at the first e before the last whose score is strictly below ``config["lte_thresholds"][e]`` (per exit) or,
+        without that key, the global ``config["exit_threshold"]``.  ``config["exit_policy"] = "lte_policy"`` selects it through
+        EE/eval.py:91-98's ``getattr`` dispatch."""
+        if self.config.get("lte_scores") is None:
+            raise ValueError('lte_policy needs config["lte_scores"] (the (num_exits + 1, num_samples) LTE scores of the dump)')
+        thr = self.config.get("lte_thresholds")
+        if thr is None:
+            if self.config.get("exit_threshold") is None:
+                raise ValueError('lte_policy needs config["lte_thresholds"] (per exit) or config["exit_threshold"]')
+            thr = float(self.config["exit_threshold"])
+        return self._finish(thr, lte_scores=self.config["lte_scores"])
 
     def accuracy_calibration_heuristic(self):
         """EE/policy.py:55-111: per-exit thresholds minmax_eps(1 - accuracy/ece)."""

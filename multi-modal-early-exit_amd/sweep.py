@@ -61,6 +61,17 @@ def patience_sweep(logits, references, patiences, want_hist: bool = False, devic
     return acc, mex, hist
 
 
+def lte_sweep(scores, correct, thresholds, want_hist: bool = False, device=None):
+    """Many LTE threshold vectors over one table of scores: ``threshold_sweep`` on ``-scores`` / ``-thresholds`` (negation is exact), so
+    exits = (scores <= thr[v][:, None]).argmax(0) -- the first exit whose score is AT OR BELOW its threshold, exit 0 when none is.  The
+    policy (``Policy.lte_policy``, the forward pass) is strict (``<``) and falls back to the LAST exit: the same strict / non-strict,
+    first / last difference the reference's sweep (EE/thresh.py:184-215) has against its policy (EE/policy.py:33).  No kernel of its own.
+    ``scores`` (E1,N), ``correct`` (E1,N), ``thresholds`` (V,E1); returns ``(accuracy (V,), mean_exit (V,), hist (V,E1) | None)``."""
+    dev = _require_torch_cuda(device)
+    to = lambda x: (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x).to(dev, torch.float64)
+    return threshold_sweep(-to(scores), correct, -to(thresholds), want_hist=want_hist, device=dev)
+
+
 def threshold_sweep(conf, correct, thresholds, want_hist: bool = False, device=None):
     """For each threshold vector v: exits = (conf >= thr[v][:, None]).argmax(0); returns device tensors
     ``(accuracy (V,), mean_exit (V,), hist (V,E1) | None)``."""

@@ -95,6 +95,11 @@ def make_weights(cfg: ModelConfig, seed: int = 1234, head_gain: float = 30.0, ln
     # final classifier = HF LayoutLMv3ClassificationHead (HF:799-823), always 2-layer
     lin("classifier.dense", H, H, gain=2.0)
     lin("classifier.out_proj", K, H, gain=head_gain)
+    if ec.use_lte:
+        # drawn last, so that every other tensor is the one the same seed gives without use_lte.  sigma = 1.5 / sqrt(H): pre-activations on
+        # LayerNorm-ed CLS rows (unit-order entries) spread over order 1, so the scores spread over (0, 1) and every exit has takers
+        w[p + "encoder.lte_classifier.weight"] = _normal(rng, (1, H), 1.5 / np.sqrt(H))
+        w[p + "encoder.lte_classifier.bias"] = np.zeros((1,), dtype=np.float32)
     return w
 
 
