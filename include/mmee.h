@@ -21,6 +21,8 @@
  *                                                 (EE/thresh.py:184-215, EE/large_scale.py:68-84).
  *   ee_set_patience / ee_patience_scan /        <- EarlyExitInference.PATIENCE, declared by the reference (EE/models/EE_modules.py:
  *   ee_patience_sweep                              123-124, PABEE: Zhou et al., NeurIPS 2020) but not implemented there; semantics below.
+ *   ee_set_exit_rule / ee_set_patience_vector / <- no counterpart: the reference implements neither rule.  Patient-and-confident (PCEE-BERT, Zhang et al.,
+ *   ee_rule_scan / ee_rule_sweep                   NAACL Findings 2022) and PABEE's patience-or-threshold hybrid, on the events and counters above; semantics below.
  *   ee_config.use_lte / ee_lte_scan             <- learning-to-exit (BERxiT's LTE): encoder.lte_classifier = nn.Linear(hidden_size, 1) + sigmoid on
  *                                                  the CLS row after every exit layer, `lte_output < lte_th[i]` leaves (EE/models/LayoutLMv3.py:
  *                                                  140-149, 229-268; switched on by EE_config["use_lte"]); semantics below.
@@ -54,7 +56,8 @@ enum { MMEE_CRIT_MAX_CONFIDENCE = 0, MMEE_CRIT_ENTROPY = 1, MMEE_CRIT_PATIENCE =
  * encoder exits ascending, then the final classifier).  p_e(n) = argmax of document n's policy logits at exit e, taken on exactly the float32
  * values written to out_all_logits, (float)((double)z / T_e) (ramps: the head's logits; gates: classifier(gate input)); ties resolve to the
  * first maximal index (numpy argmax).  Run counter: c_0 = 0; c_e = c_{e-1} + 1 if p_e == p_{e-1}, else 0.  Document n leaves at the first e
- * with c_e >= t, or at E if there is none (t > E: every document runs to the final exit).  The patience t >= 1 is set by ee_set_patience.
+ * with c_e >= t, or at E if there is none (t > E: every document runs to the final exit).  The patience t >= 1 is set by ee_set_patience, or per
+ * exit by ee_set_patience_vector (c_e >= t_e).
  * Outputs keep their contract: out_logits = the scaled logits of the chosen exit, out_conf = the float64 max-softmax of those scaled logits
  * (rounded to float32), out_all_crit (dump-all) = the same max-softmax at every exit, out_head_crit = the max-softmax of the raw head logits.
  * Thresholds are ignored (may be NULL); temperatures act only through the scaled logits.
@@ -75,6 +78,28 @@ enum { MMEE_CRIT_MAX_CONFIDENCE = 0, MMEE_CRIT_ENTROPY = 1, MMEE_CRIT_PATIENCE =
  * Refused: use_lte with MMEE_CRIT_PATIENCE (at ee_create or through ee_set_criterion) and with MMEE_ARCH_BEIT.  Bound at ee_create: captured
  * graphs keep reading the thresholds from the device vector of each ee_graph_launch.
  */
+/*
+ * Exit rules (ee_set_exit_rule): what a handle makes of its criterion / LTE test and PABEE's counter together.  Exits e = 0 .. E in the path's
+ * order, E1 = E + 1.  A handle keeps its criterion and its use_lte setting.
+ *   Event of exit e: today's test, unchanged.  max_confidence: f_e = crit_e > thr_e; entropy: f_e = crit_e < thr_e; use_lte: f_e = u_e < thr_e
+ *   (embedding exits never fire under LTE).  All compares strict; crit_e is the float64 criterion on the scaled logits, u_e the float64 score.
+ *   Agreement: PABEE's counter exactly as under MMEE_CRIT_PATIENCE: c_0 = 0, c_e = c_{e-1} + 1 if argmax z_e == argmax z_{e-1}, else 0, the
+ *   argmax taken on the scaled float32 logits as written out, the first maximum winning.
+ *   Patience: a per-exit vector t_e >= 1, e = 0 .. E (ee_set_patience_vector; the final exit's entry is ignored).  ee_set_patience(h, t) is
+ *   that value at every exit.
+ *   MMEE_RULE_PLAIN  = 0  the test alone, as before: leave at the first e with f_e.  The default.
+ *   MMEE_RULE_STREAK = 1  patient and confident (PCEE): s_e = f_e ? s_{e-1} + 1 : 0 with s_{-1} = 0; leave at the first e with s_e >= t_e.
+ *                         With t = 1 this is MMEE_RULE_PLAIN exactly.
+ *   MMEE_RULE_EITHER = 2  patience or threshold: leave at the first e with f_e or c_e >= t_e: the minimum of the PLAIN exit and the PABEE exit.
+ * If no exit qualifies the document leaves at the final exit E.  MMEE_FLAG_NO_EXIT and the final exit behave as without a rule; every output
+ * carries what it carries without one (out_conf: the criterion or LTE score of the exit the document leaves at): only WHICH exit changes.
+ * Per document the decide kernels keep the streak (STREAK) or (previous argmax, c_e) (EITHER) where MMEE_CRIT_PATIENCE keeps its state: by the
+ * document's slot in the call, rewritten at exit 0, nothing carried from one forward to the next, no launch added.
+ * Refused, each with a message: a rule other than PLAIN under MMEE_CRIT_PATIENCE (PABEE has no threshold event; ee_set_exit_rule and
+ * ee_set_criterion both check), a STREAK or EITHER forward without a patience set, any patience entry below 1, a patience vector whose length
+ * is not E + 1.  MMEE_CRIT_PATIENCE itself also takes the vector: c_e >= t_e (per-exit patience).
+ */
+enum { MMEE_RULE_PLAIN = 0, MMEE_RULE_STREAK = 1, MMEE_RULE_EITHER = 2 };
 /* model family: LayoutLMv3 (text + layout + image, the reference's EE model) or BEiT / DiT (image only; BASELINE configs[4],
  * the reference's "dit" branch EE/configs.py:429-449 — exit heads there are this build's extrapolation) */
 enum { MMEE_ARCH_LAYOUTLMV3 = 0, MMEE_ARCH_BEIT = 1 };
@@ -200,8 +225,9 @@ int ee_forward(ee_handle* h, const int64_t* input_ids, const int64_t* attention_
  * The graph is bound to the POINTERS it was captured with -- inputs and outputs are static buffers the caller refills / reads between
  * replays -- and to (B, T, flags, which outputs were non-NULL) and to the handle's exit-layer schedule at capture time (ee_set_probe_mask).
  * Thresholds and temperatures are NOT baked in: the decide kernels read them from a device vector that every ee_graph_launch refreshes.
- * Neither is the patience: under MMEE_CRIT_PATIENCE the decide kernels read t from the same vector, which ee_graph_launch fills with the
- * handle's CURRENT patience (ee_set_patience between replays takes effect).  The criterion itself is bound at capture.
+ * Neither is the patience: under MMEE_CRIT_PATIENCE, MMEE_RULE_STREAK and MMEE_RULE_EITHER the decide kernel of exit e reads t_e from the
+ * same vector (E + 1 entries behind the temperatures), which ee_graph_launch fills with the handle's CURRENT patience (ee_set_patience /
+ * ee_set_patience_vector between replays take effect).  The criterion and the exit rule themselves are bound at capture.
  * `stream` must be a created stream (the legacy null stream cannot be captured).  Not capturable: the one-shot side inputs / outputs
  * (ee_set_inputs_embeds, ee_set_hidden_states_out, ee_set_head_mask, ee_set_attentions_out) and an armed ee_profile.
  *
@@ -243,6 +269,12 @@ int ee_set_criterion(ee_handle* h, int32_t criterion);
  * state until changed.  Per document, the decide kernels keep (argmax at the previous exit, run counter) in the handle's workspace, indexed
  * by the document's slot in the call and rewritten at exit 0, which every document reaches: nothing carries over from one forward to the next. */
 int ee_set_patience(ee_handle* h, int32_t t);
+/* The per-exit patience t[0 .. E] (n must be E + 1, every entry >= 1; the final exit's entry is ignored) of every later forward and graph launch
+ * under MMEE_CRIT_PATIENCE, MMEE_RULE_STREAK and MMEE_RULE_EITHER.  Copied: the caller's array need not outlive the call.  ee_set_patience stays
+ * the broadcast and replaces the vector. */
+int ee_set_patience_vector(ee_handle* h, const int32_t* t, int32_t n);
+/* The exit rule (MMEE_RULE_*, semantics above) of every LATER ee_forward and ee_graph_capture; MMEE_RULE_PLAIN after ee_create. */
+int ee_set_exit_rule(ee_handle* h, int32_t rule);
 
 /* Pin the exit-layer schedule.  DEFAULT (enabled == 0): every layer that ends in a decision is probed first.  Rounds 2-4 chose per layer
  * from the stage populations of "the handle's most recent FINISHED forward" -- a timing-dependent host decision, and under MMEE_FLAG_XPROBE
@@ -312,6 +344,30 @@ int ee_patience_scan(const double* logits, int32_t E1, int32_t N, int32_t K, int
  */
 int ee_lte_scan(const double* scores, const double* logits, int32_t E1, int32_t N, int32_t K, const double* thresholds, int32_t* exits,
                 double* predictions, int32_t* counts, void* stream);
+/*
+ * MMEE_RULE_STREAK / MMEE_RULE_EITHER on dumped arrays.  criterion dev double (E1,N): the criterion table (max-softmax: ee_msp_table; entropy)
+ * or the LTE scores; sign +1: the event is criterion > threshold (max_confidence), -1: criterion < threshold (entropy, LTE; rows of embedding
+ * exits hold 1.0 under LTE, which no threshold <= 1 releases).  logits dev double (E1,N,K) for the agreement counter (argmax of the float64
+ * row, first maximum) and the predictions; may be NULL under MMEE_RULE_STREAK with predictions NULL.  thresholds host double [E1], patience
+ * host int32 [E1] (every entry >= 1; entries E1-1 unused); 1 <= E1 <= 256.  exits dev int32 (N,), predictions dev double (N,K) or NULL (the logits row of the
+ * chosen exit), confidence dev double (N,) or NULL (the criterion entry of the chosen exit), counts dev int32 [E1] or NULL.
+ */
+int ee_rule_scan(const double* criterion, double sign, const double* logits, int32_t E1, int32_t N, int32_t K, const double* thresholds,
+                 const int32_t* patience, int32_t rule, int32_t* exits, double* predictions, double* confidence, int32_t* counts, void* stream);
+/*
+ * V threshold vectors x P patience values at once (the rule counterpart of ee_threshold_sweep at its search scale, EE/large_scale.py:42-84), with
+ * the POLICY's semantics, as ee_patience_sweep follows its policy's: the event is conf[e,n] > thr[v,e] (strict; a NaN threshold never fires; for
+ * a '<' criterion pass the negated table and thresholds, which is exact), exit(v,p,n) as ee_rule_scan with the scalar patience patiences[p] at
+ * every exit, the final exit when nothing qualifies.  conf dev double (E1,N), logits dev double (E1,N,K), references dev int64 (N,), thr dev
+ * double (V,E1), patiences HOST int32 [P] (each >= 1); E1 <= 64, N < 2^24, P <= 128.  Outputs dev: acc double (V,P) = #{n : argmax
+ * logits[exit, n] == references[n]} / N, mean_exit double (V,P), exit_hist int32 (V,P,E1) or NULL; integer sums, then one division: deterministic.
+ * A document's streak is walked once per threshold vector and every patience value is a lookup.  Two kernels give the same integers: E1 = 7,
+ * P <= 8, no histogram and 8 V >= N (the reference's search shape; enough vectors to pay for the O(N^2) ranking pass, the condition
+ * ee_threshold_sweep uses) runs on integer ranks, one thread per threshold vector; every other call, and a call whose rank workspace
+ * (104 N + 28 V bytes) cannot be allocated, runs one workgroup per threshold vector on the float64 table.
+ */
+int ee_rule_sweep(const double* conf, const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, const double* thr, int32_t V,
+                  const int32_t* patiences, int32_t P, int32_t rule, double* acc, double* mean_exit, int32_t* exit_hist, void* stream);
 /*
  * V patience values at once over one dumped array (the patience counterpart of ee_threshold_sweep / EE/eval.py:186-210): logits dev double
  * (E1,N,K) with E1 <= 128, references dev int64 (N,), patiences dev int32 (V,).  exit(v,n) as ee_patience_scan with t = patiences[v];

@@ -19,6 +19,7 @@ FLAG_PROBE_ALWAYS = 8
 FLAG_XPROBE = 16
 FLAG_ONE_TERM = 32
 CRIT_MAX_CONFIDENCE, CRIT_ENTROPY, CRIT_PATIENCE = 0, 1, 2
+RULE_PLAIN, RULE_STREAK, RULE_EITHER = 0, 1, 2
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 CLOCK_STAMP_WORDS = 4096       # MMEE_CLOCK_STAMP_WORDS
 
@@ -77,6 +78,8 @@ SYMBOLS = {
     "ee_set_probe_mask": (C.c_int, [_vp, _i32, C.c_uint64]),
     "ee_set_criterion": (C.c_int, [_vp, _i32]),
     "ee_set_patience": (C.c_int, [_vp, _i32]),
+    "ee_set_patience_vector": (C.c_int, [_vp, C.POINTER(_i32), _i32]),
+    "ee_set_exit_rule": (C.c_int, [_vp, _i32]),
     "ee_suggest_probe_mask": (C.c_int, [_vp, _u32, C.POINTER(C.c_uint64), _vp]),
     "ee_clock_stamp": (C.c_int, [_vp, _vp]),
     "ee_set_inputs_embeds": (C.c_int, [_vp, _vp]),
@@ -86,6 +89,8 @@ SYMBOLS = {
     "ee_policy_scan": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _vp]),
     "ee_patience_scan": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ee_lte_scan": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _vp, _vp, _vp]),
+    "ee_rule_scan": (C.c_int, [_vp, C.c_double, _vp, _i32, _i32, _i32, C.POINTER(C.c_double), C.POINTER(_i32), _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ee_rule_sweep": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, C.POINTER(_i32), _i32, _i32, _vp, _vp, _vp, _vp]),
     "ee_patience_sweep": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "ee_pack_results": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "ee_unpack_results": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),

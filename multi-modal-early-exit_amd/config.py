@@ -62,6 +62,18 @@ class EarlyExitInference(_StrEnum):
         raise NotImplementedError(f"{self} not implemented")
 
 
+class ExitRule(_StrEnum):
+    """What the exit decision makes of the criterion / LTE test and PABEE's agreement counter together (include/mmee.h MMEE_RULE_*)."""
+    PLAIN = "plain"                                     # the test alone
+    PATIENT_CONFIDENT = "patient_confident"             # PCEE: the test has held at `patience` exits in a row
+    PATIENCE_OR_THRESHOLD = "patience_or_threshold"     # the test fires, or the prediction has been stable for `patience` exits
+
+    @property
+    def code(self) -> int:
+        """Integer handed to the C-ABI (``ee_set_exit_rule`` / ``ee_rule_scan`` / ``ee_rule_sweep``)."""
+        return {"plain": 0, "patient_confident": 1, "patience_or_threshold": 2}[self.value]
+
+
 class EarlyExitHead(_StrEnum):
     GATE = "gate"
     RAMP = "ramp"
@@ -106,6 +118,21 @@ def check_patience(t) -> int:
     return int(t)
 
 
+def check_patience_spec(t, num_exits1: Optional[int] = None) -> Union[int, List[int]]:
+    """A patience as ``EE_config["patience"]`` and ``forward(patience=)`` take it: one integer >= 1 (that value at every exit) or a per-exit
+    sequence of them, one entry per exit and the final classifier (``num_exits1`` entries when given; the final one is ignored)."""
+    if isinstance(t, (str, bytes)):
+        return check_patience(t)
+    try:
+        entries = list(t)
+    except TypeError:                   # not iterable (a 0-d array included): one value
+        return check_patience(t.item() if hasattr(t, "item") else t)
+    out = [check_patience(x.item() if hasattr(x, "item") else x) for x in entries]
+    if num_exits1 is not None and len(out) != num_exits1:
+        raise ValueError(f"a per-exit patience needs {num_exits1} entries (every exit and the final classifier), got {len(out)}")
+    return out
+
+
 class ExitConfig:
     """Same keys/defaults as EE/models/EE_modules.py:175-195."""
 
@@ -117,9 +144,15 @@ class ExitConfig:
         self.encoder_layer_strategy = EarlyExitHead(kwargs.get("encoder_layer_strategy", "ramp"))
         self.exit_head_num_layers = kwargs.get("exit_head_num_layers", 2)
         # inference_strategy == "patience": exit once the prediction has stayed the same for `patience` exits in a row (include/mmee.h)
+        # an int, or a per-exit list (one entry per exit and the final classifier); also the patience of the two combined exit rules
         self.patience = kwargs.get("patience", None)
         if self.patience is not None:
-            self.patience = check_patience(self.patience)
+            self.patience = check_patience_spec(self.patience, self.num_exits + 1)
+        # exit_rule: "plain" | "patient_confident" | "patience_or_threshold" (include/mmee.h MMEE_RULE_*): the criterion / LTE test combined
+        # with a streak or with PABEE's counter.  The reference implements neither; PABEE itself has no threshold test to combine
+        self.exit_rule = ExitRule(kwargs.get("exit_rule", None) or "plain")
+        if self.exit_rule != ExitRule.PLAIN and self.inference_strategy == EarlyExitInference.PATIENCE:
+            raise ValueError(f'exit_rule "{self.exit_rule}" builds on a threshold test, which inference_strategy "patience" does not have')
         # learning-to-exit (EE/models/LayoutLMv3.py:140): the exit test is sigmoid(lte_classifier(CLS row)) < threshold (include/mmee.h);
         # the reference's real switch -- inference_strategy = "lte" stays unimplemented, as its get_function() is
         self.use_lte = bool(kwargs.get("use_lte", False))
@@ -151,6 +184,7 @@ class ExitConfig:
             "exit_head_num_layers": self.exit_head_num_layers,
             "patience": self.patience,
             "use_lte": self.use_lte,
+            "exit_rule": str(self.exit_rule),
         }
 
 

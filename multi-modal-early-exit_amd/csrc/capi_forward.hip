@@ -132,8 +132,12 @@ struct Forward {
         if (!beit && (T < 1 || T > c.max_text_len)) return fail(h, "ee_forward: T=%d outside [1, max_text_len=%d]", T, c.max_text_len);
         if (!a.thresholds && !cap && !patience && !no_exit)
             return fail(h, "ee_forward: thresholds required unless MMEE_FLAG_NO_EXIT or MMEE_CRIT_PATIENCE");
-        if (patience && h->patience < 1 && !no_exit)
+        if (patience && !h->has_patience() && !no_exit)
             return fail(h, "ee_forward: the patience criterion needs ee_set_patience(h, t) with t >= 1 before the first forward");
+        if (h->rule != MMEE_RULE_PLAIN && patience)
+            return fail(h, "ee_forward: MMEE_RULE_STREAK / MMEE_RULE_EITHER build on a threshold event, which MMEE_CRIT_PATIENCE does not have");
+        if (h->rule != MMEE_RULE_PLAIN && !h->has_patience() && !no_exit)
+            return fail(h, "ee_forward: MMEE_RULE_STREAK / MMEE_RULE_EITHER need a patience: ee_set_patience or ee_set_patience_vector before the forward");
         if ((head_mask || attn_out) && (a.flags & (MMEE_FLAG_NO_EXIT | MMEE_FLAG_WHOLE_LAYERS)) != (MMEE_FLAG_NO_EXIT | MMEE_FLAG_WHOLE_LAYERS))
             return fail(h, "ee_forward: head_mask / attention maps exist in dump-all mode with whole layers only (MMEE_FLAG_NO_EXIT | MMEE_FLAG_WHOLE_LAYERS)");
         if ((head_mask || attn_out) && beit) return fail(h, "ee_forward: head_mask / attention maps are built for the LayoutLMv3 layers only");
@@ -567,13 +571,15 @@ struct Forward {
         d.out_logits = a.out_logits; d.out_exit = a.out_exit; d.out_conf = a.out_conf;
         d.out_all_logits = a.out_all_logits; d.out_all_crit = a.out_all_crit;
         d.out_head_logits = a.out_head_logits; d.out_head_crit = a.out_head_crit;
-        if (patience) {
+        if (patience || h->rule != MMEE_RULE_PLAIN) {
             PatienceArgs pa{};
-            pa.t = h->patience;
-            if (cap) pa.t_ptr = cap->thr_dev + 2 * (E + 1);                               // replays read the patience of THEIR launch
+            pa.t = h->has_patience() ? h->patience_at(exit_index) : 0;                    // not set: a dump-all call, where nobody leaves
+            if (cap) pa.t_ptr = cap->thr_dev + 2 * (E + 1) + exit_index;                  // replays read the patience of THEIR launch
             pa.prev = h->pat_state; pa.run = h->pat_state + c.max_docs;
+            if (c.use_lte) d.lte_score = lte ? h->lte_score : nullptr;
             ProfScope ps(h, P_DECIDE, s);
-            launch_decide_patience(d, pa, s);
+            if (patience) launch_decide_patience(d, pa, s);
+            else launch_decide_rule(d, pa, h->rule, c.use_lte != 0, s);
         } else if (c.use_lte) {
             d.lte_score = lte ? h->lte_score : nullptr;
             ProfScope ps(h, P_DECIDE, s);
@@ -757,7 +763,7 @@ int ee_graph_capture(ee_handle* h, const int64_t* input_ids, const int64_t* atte
     g.n_exits1 = E1;
     g.no_exit = (flags & MMEE_FLAG_NO_EXIT) != 0;
     g.patience = h->cfg.criterion == MMEE_CRIT_PATIENCE;
-    if (dev_alloc(h, &g.thr_dev, (size_t)2 * E1 + 1)) return 1;
+    if (dev_alloc(h, &g.thr_dev, (size_t)3 * E1)) return 1;
     // (2) the launch list again, captured
     hipGraph_t graph = nullptr;
     HIP_OK(h, hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
@@ -785,12 +791,12 @@ int ee_graph_launch(ee_handle* h, int32_t graph_id, const double* thresholds, co
     const int rc_pre = forward_pre(h, s);
     if (rc_pre) return rc_pre;
     ThrPack p{};
-    p.n = 2 * g.n_exits1 + 1;
+    p.n = 3 * g.n_exits1;
     for (int i = 0; i < g.n_exits1; ++i) {
         p.v[i] = thresholds ? thresholds[i] : 0.0;
         p.v[g.n_exits1 + i] = temperatures ? temperatures[i] : 1.0;
+        p.v[2 * g.n_exits1 + i] = (double)h->patience_at(i);
     }
-    p.v[2 * g.n_exits1] = (double)h->patience;
     hipLaunchKernelGGL(set_thresholds_kernel, dim3(1), dim3(64), 0, s, p, g.thr_dev);
     HIP_OK(h, hipGraphLaunch(g.exec, s));
     h->rec = g.rec;

@@ -105,7 +105,11 @@ struct ee_handle {
     int *doc_orig, *doc_off, *x_src, *meta_src;   // [(E+2)][max_docs+1]
     mmee::StageCounts* counts;                    // [(E+2)]
     double* thr_dev = nullptr;                    // scratch for ee_policy_scan
-    int32_t patience = 0;                         // ee_set_patience (0: not set); read by the decide launches under MMEE_CRIT_PATIENCE
+    int32_t patience = 0;                         // ee_set_patience (0: not set): the patience of every exit unless patience_vec is set
+    std::vector<int32_t> patience_vec;            // ee_set_patience_vector: [E + 1] per-exit patience (empty: the broadcast above)
+    int32_t rule = MMEE_RULE_PLAIN;               // ee_set_exit_rule: what the decide launches make of the criterion / LTE event
+    bool has_patience() const { return patience >= 1 || !patience_vec.empty(); }
+    int32_t patience_at(int e) const { return patience_vec.empty() ? patience : patience_vec[e]; }
     int* pat_state = nullptr;                     // [2][max_docs]: argmax at the previous exit, run counter (by original document slot)
     // learning-to-exit (ee_config.use_lte): encoder.lte_classifier (weight [H], bias [1]) and the float64 scores of the exit being decided
     float *lte_w = nullptr, *lte_b = nullptr;
@@ -140,7 +144,7 @@ struct ee_handle {
     // thresholds / temperatures live in a device buffer the decide kernels read, refreshed in front of every replay
     struct GraphRec {
         hipGraphExec_t exec = nullptr;
-        double* thr_dev = nullptr;                // [2 * (E + 1) + 1]: thresholds, then temperatures (1.0 when the launch passes none), then the patience
+        double* thr_dev = nullptr;                // [3 * (E + 1)]: thresholds, then temperatures (1.0 when the launch passes none), then the per-exit patience
         int n_exits1 = 0;
         bool no_exit = false;
         bool patience = false;                    // captured under MMEE_CRIT_PATIENCE: launches need no thresholds

@@ -23,7 +23,7 @@ const char* const kProfNames[] = {
     "gemm_ffn_up|gemm_f32_kernel<1,0>",
     "gemm_ffn_down|gemm_f32_kernel<2,0>",
     "exit_head|gemm_f32_kernel<3,0>+head_out_kernel (use_lte: head_out_lte_kernel)",
-    "exit_decide|exit_decide_kernel (patience: exit_decide_patience_kernel, use_lte: exit_decide_lte_kernel)",
+    "exit_decide|exit_decide_kernel (patience: exit_decide_patience_kernel, use_lte: exit_decide_lte_kernel; exit rules: exit_decide_[lte_]{streak,either}_kernel)",
     "compact|compact_rows_kernel",
     "gather_cls|gather_cls_kernel",
     "cls_probe|attention_idx_kernel+gemm_split_kernel<.., 1>+ln_rows_kernel+gather_cls_kernel (CLS rows of an exit layer, before its decision)",
@@ -118,7 +118,20 @@ int ee_set_criterion(ee_handle* h, int32_t criterion) {
         return fail(h, "ee_set_criterion: unknown criterion %d", criterion);
     if (criterion == MMEE_CRIT_PATIENCE && h->cfg.use_lte)
         return fail(h, "ee_set_criterion: MMEE_CRIT_PATIENCE on a use_lte handle: learning-to-exit and patience are two exit decisions");
+    if (criterion == MMEE_CRIT_PATIENCE && h->rule != MMEE_RULE_PLAIN)
+        return fail(h, "ee_set_criterion: MMEE_CRIT_PATIENCE under exit rule %d: PABEE has no threshold event for MMEE_RULE_STREAK / MMEE_RULE_EITHER "
+                       "to build on (ee_set_exit_rule(h, MMEE_RULE_PLAIN) first)", h->rule);
     h->cfg.criterion = criterion;      // read by the decide kernel's arguments of every later ee_forward
+    return 0;
+}
+
+int ee_set_exit_rule(ee_handle* h, int32_t rule) {
+    if (!h) return 1;
+    if (rule != MMEE_RULE_PLAIN && rule != MMEE_RULE_STREAK && rule != MMEE_RULE_EITHER) return fail(h, "ee_set_exit_rule: unknown rule %d", rule);
+    if (rule != MMEE_RULE_PLAIN && h->cfg.criterion == MMEE_CRIT_PATIENCE)
+        return fail(h, "ee_set_exit_rule: rule %d under MMEE_CRIT_PATIENCE: PABEE has no threshold event for MMEE_RULE_STREAK / MMEE_RULE_EITHER to build on",
+                    rule);
+    h->rule = rule;                    // picks the decide kernel of every later ee_forward / ee_graph_capture
     return 0;
 }
 
@@ -126,6 +139,17 @@ int ee_set_patience(ee_handle* h, int32_t t) {
     if (!h) return 1;
     if (t < 1) return fail(h, "ee_set_patience: t=%d, the patience must be >= 1", t);
     h->patience = t;                   // eager forwards pass it by value; ee_graph_launch writes it to the graph's device vector
+    h->patience_vec.clear();           // the broadcast replaces a per-exit vector
+    return 0;
+}
+
+int ee_set_patience_vector(ee_handle* h, const int32_t* t, int32_t n) {
+    if (!h) return 1;
+    const int E1 = h->cfg.n_embedding_exits + h->cfg.n_encoder_exits + 1;
+    if (!t || n != E1) return fail(h, "ee_set_patience_vector: %d entries, the handle has E + 1 = %d exits (one entry per exit, the final one ignored)", n, E1);
+    for (int e = 0; e < n; ++e)
+        if (t[e] < 1) return fail(h, "ee_set_patience_vector: t[%d]=%d, every patience must be >= 1", e, t[e]);
+    h->patience_vec.assign(t, t + n);
     return 0;
 }
 

@@ -86,6 +86,56 @@ int ee_lte_scan(const double* scores, const double* logits, int32_t E1, int32_t 
     return launch_status(nullptr, "ee_lte_scan");
 }
 
+int ee_rule_scan(const double* criterion, double sign, const double* logits, int32_t E1, int32_t N, int32_t K, const double* thresholds,
+                 const int32_t* patience, int32_t rule, int32_t* exits, double* predictions, double* confidence, int32_t* counts, void* stream) {
+    if (!thresholds || !patience || E1 < 1 || E1 > 256 || N < 0 || K < 1 || (N > 0 && (!criterion || !exits)) || (sign != 1.0 && sign != -1.0))
+        return fail(nullptr, "ee_rule_scan: bad argument (1 <= E1 <= 256, sign is +1 or -1)");
+    if (rule != MMEE_RULE_STREAK && rule != MMEE_RULE_EITHER) return fail(nullptr, "ee_rule_scan: rule %d is neither MMEE_RULE_STREAK nor MMEE_RULE_EITHER", rule);
+    if (!logits && (rule == MMEE_RULE_EITHER || predictions)) return fail(nullptr, "ee_rule_scan: MMEE_RULE_EITHER and predictions need the logits");
+    for (int e = 0; e < E1; ++e)
+        if (patience[e] < 1) return fail(nullptr, "ee_rule_scan: patience[%d]=%d, every patience must be >= 1", e, patience[e]);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_rule_scan: no HIP device");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    double* thr_dev = nullptr;                                       // thresholds [E1] doubles, then the patience [E1] ints
+    if (hipMallocAsync((void**)&thr_dev, (sizeof(double) + sizeof(int)) * E1, s) != hipSuccess) return fail(nullptr, "ee_rule_scan: hipMallocAsync failed");
+    int* pat_dev = reinterpret_cast<int*>(thr_dev + E1);
+    if (hipMemcpyAsync(thr_dev, thresholds, sizeof(double) * E1, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(pat_dev, patience, sizeof(int) * E1, hipMemcpyHostToDevice, s) != hipSuccess ||
+        (counts && hipMemsetAsync(counts, 0, sizeof(int) * E1, s) != hipSuccess)) {
+        (void)hipFreeAsync(thr_dev, s);
+        return fail(nullptr, "ee_rule_scan: threshold / patience copy or counts memset failed");
+    }
+    if (N > 0) launch_rule_scan(criterion, sign, logits, E1, N, K, thr_dev, pat_dev, rule, exits, predictions, confidence, counts, s);
+    (void)hipFreeAsync(thr_dev, s);
+    return launch_status(nullptr, "ee_rule_scan");
+}
+
+int ee_rule_sweep(const double* conf, const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, const double* thr, int32_t V,
+                  const int32_t* patiences, int32_t P, int32_t rule, double* acc, double* mean_exit, int32_t* exit_hist, void* stream) {
+    if (!conf || !logits || !references || !thr || !patiences || !acc || !mean_exit || E1 < 1 || E1 > 64 || N < 1 || N >= (1 << 24) || K < 1 || V < 0 ||
+        P < 1 || P > 128)
+        return fail(nullptr, "ee_rule_sweep: bad argument (E1 <= 64, 1 <= N < 2^24, 1 <= P <= 128)");
+    if (rule != MMEE_RULE_STREAK && rule != MMEE_RULE_EITHER) return fail(nullptr, "ee_rule_sweep: rule %d is neither MMEE_RULE_STREAK nor MMEE_RULE_EITHER", rule);
+    for (int j = 0; j < P; ++j)
+        if (patiences[j] < 1) return fail(nullptr, "ee_rule_sweep: patiences[%d]=%d, every patience must be >= 1", j, patiences[j]);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_rule_sweep: no HIP device");
+    if (V == 0) return 0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int* pats_dev = nullptr;
+    if (hipMallocAsync((void**)&pats_dev, sizeof(int) * P, s) != hipSuccess) return fail(nullptr, "ee_rule_sweep: hipMallocAsync failed");
+    if (hipMemcpyAsync(pats_dev, patiences, sizeof(int) * P, hipMemcpyHostToDevice, s) != hipSuccess) {
+        (void)hipFreeAsync(pats_dev, s);
+        return fail(nullptr, "ee_rule_sweep: patience copy failed");
+    }
+    const bool ok = launch_rule_sweep(conf, logits, reinterpret_cast<const long long*>(references), E1, N, K, thr, V, patiences, pats_dev, P, rule, acc,
+                                      mean_exit, exit_hist, s);
+    (void)hipFreeAsync(pats_dev, s);
+    if (!ok) return fail(nullptr, "ee_rule_sweep: hipMallocAsync failed");
+    return launch_status(nullptr, "ee_rule_sweep");
+}
+
 int ee_patience_sweep(const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, const int32_t* patiences, int32_t V,
                       double* acc, double* mean_exit, int32_t* exit_hist, void* stream) {
     if (!logits || !references || !patiences || !acc || !mean_exit || E1 < 1 || E1 > 128 || N < 1 || K < 1 || V < 0)

@@ -70,9 +70,9 @@ struct HeadOutArgs {
     double* lte_out;                 // [n_docs] u = sigmoid(w . x + b), float64
 };
 
-// thresholds, then temperatures, of one ee_graph_launch: a kernel ARGUMENT of set_thresholds_kernel (no host buffer has to outlive the call)
+// thresholds, then temperatures, then the per-exit patience, of one ee_graph_launch: a kernel ARGUMENT of set_thresholds_kernel (no host buffer has to outlive the call)
 struct ThrPack {
-    double v[2 * (64 + 4) + 1];      // 2 x (MMEE_MAX_ENCODER_EXITS + 3 embedding exits + final), then the patience
+    double v[3 * (64 + 4)];          // 3 x (MMEE_MAX_ENCODER_EXITS + 3 embedding exits + final): thresholds, temperatures, per-exit patience
     int n;
 };
 
@@ -106,12 +106,13 @@ struct DecideArgs {
     float* out_head_crit;            // (E,B)
 };
 
-// patience (MMEE_CRIT_PATIENCE): the decide kernel's second argument
+// patience (MMEE_CRIT_PATIENCE, MMEE_RULE_STREAK, MMEE_RULE_EITHER): the decide kernel's second argument
 struct PatienceArgs {
-    int t;                           // exit once the argmax has stayed the same for t exits in a row
-    const double* t_ptr;             // captured-graph forwards: t at [0] of the device vector every ee_graph_launch refreshes; null: `t`
+    int t;                           // THIS exit's patience t_e: exit once the argmax has stayed the same (STREAK: the event has held) for t exits in a row
+    const double* t_ptr;             // captured-graph forwards: t_e at [0] (the host points it at this exit's entry of the device vector every
+                                     // ee_graph_launch refreshes); null: `t`
     int* prev;                       // [max_docs] argmax at the document's previous exit, by original slot
-    int* run;                        // [max_docs] run counter c_e, by original slot
+    int* run;                        // [max_docs] run counter c_e (MMEE_RULE_STREAK: the streak s_e), by original slot
 };
 
 // X-space CLS probe (xprobe.hip)
@@ -166,6 +167,7 @@ void launch_head_out(const HeadOutArgs& a, int max_docs, hipStream_t s);
 void launch_decide(const DecideArgs& a, hipStream_t s);
 void launch_decide_patience(const DecideArgs& a, const PatienceArgs& p, hipStream_t s);
 void launch_decide_lte(const DecideArgs& a, hipStream_t s);
+void launch_decide_rule(const DecideArgs& a, const PatienceArgs& p, int rule, bool lte, hipStream_t s);   // rule: MMEE_RULE_STREAK / _EITHER
 void launch_pack_results(const float* logits, const int* exit_layer, const float* conf, int n, int K, int* rows, hipStream_t s);
 void launch_unpack_results(const int* rows, int n, int K, float* logits, int* exit_layer, float* conf, hipStream_t s);
 void launch_compact_rows(const StageCounts* n_counts, const int* n_doc_off, const int* n_x_src, const int* n_meta_src,
@@ -189,6 +191,10 @@ void launch_patience_scan(const double* logits, int E1, int N, int K, int t, int
                           hipStream_t s);
 void launch_lte_scan(const double* scores, const double* logits, int E1, int N, int K, const double* thr_dev, int* exits, double* pred,
                      int* counts, hipStream_t s);
+void launch_rule_scan(const double* crit, double sign, const double* logits, int E1, int N, int K, const double* thr_dev, const int* pat_dev,
+                      int rule, int* exits, double* pred, double* conf, int* counts, hipStream_t s);
+bool launch_rule_sweep(const double* conf, const double* logits, const long long* refs, int E1, int N, int K, const double* thr, int V,
+                       const int* pats_host, const int* pats_dev, int P, int rule, double* acc, double* mean_exit, int* hist, hipStream_t s);
 bool launch_patience_sweep(const double* logits, const long long* refs, int E1, int N, int K, const int* pats, int V, double* acc,
                            double* mean_exit, int* hist, hipStream_t s);
 void launch_threshold_sweep(const double* conf, const unsigned char* correct, int E1, int N, const double* thr, int V,

@@ -15,7 +15,7 @@ from typing import Dict, Mapping, Optional, Sequence, Union
 import numpy as np
 
 from . import capi
-from .config import ModelConfig, check_patience
+from .config import ExitRule, ModelConfig, check_patience_spec
 
 try:  # torch is plumbing (device tensors / streams); importing it must not be the reason the product "works"
     import torch
@@ -109,6 +109,9 @@ class EarlyExitEngine:
         self.patience = None
         if ec.patience is not None:
             self.set_patience(ec.patience)
+        self.exit_rule = ExitRule.PLAIN
+        if ec.exit_rule != ExitRule.PLAIN:
+            self.set_exit_rule(ec.exit_rule)
 
     # ---- lifetime ------------------------------------------------------------------------------------------------
     def close(self):
@@ -195,15 +198,19 @@ class EarlyExitEngine:
                 want_all: bool = False, want_head: bool = False, want_hidden_cls: bool = False,
                 validate: bool = False, whole_layers: bool = False, probe_always: bool = False, xprobe: Optional[bool] = None,
                 one_term: bool = False, inputs_embeds=None, want_hidden_states: bool = False, out=None, head_mask=None,
-                want_attentions: bool = False, patience: Optional[int] = None, _capture: bool = False) -> EngineOutput:
+                want_attentions: bool = False, patience: Optional[Union[int, Sequence[int]]] = None, exit_rule=None,
+                _capture: bool = False) -> EngineOutput:
         """``out``: optional preallocated ``(logits (B,K) f32, exit_layer (B,) i32, confidence (B,) f32)`` device tensors (contiguous; row
         slices of larger tensors qualify) the kernels write into instead of fresh allocations -- MicroBatchedEngine hands each half its slice.
-        ``patience``: when given, ``set_patience(patience)`` before the call (the criterion must be "patience" for it to matter); under the
-        patience criterion ``thresholds`` are ignored."""
+        ``patience``: when given, ``set_patience(patience)`` before the call (an int, or one entry per exit; it matters under the "patience"
+        criterion and under the two combined exit rules); under the patience criterion ``thresholds`` are ignored.  ``exit_rule``: when
+        given, ``set_exit_rule(exit_rule)`` before the call.  Both stay set for later calls; a capture binds the rule."""
         if not self._finalized:
             raise capi.MMEEError("load_weights() has not been called")
         if patience is not None:
             self.set_patience(patience)
+        if exit_rule is not None:
+            self.set_exit_rule(exit_rule)
         R = self.cfg.input_size
         px = self._dev(pixel_values, torch.float32, "pixel_values")
         emb = None
@@ -444,14 +451,27 @@ class EarlyExitEngine:
         self.exit_config.inference_strategy = st
         return st
 
-    def set_patience(self, t: int) -> int:
+    def set_patience(self, t: Union[int, Sequence[int]]):
         """Patience of every later forward and graph launch under the "patience" criterion (ee_set_patience): a document leaves at the first
         exit where its argmax has stayed the same for ``t`` exits in a row (include/mmee.h).  Captured graphs read the current value at every
-        launch."""
-        t = check_patience(t)
-        capi.check(self.lib.ee_set_patience(self._h, t), self._h, "ee_set_patience")
+        launch.  A sequence is a per-exit patience, one entry per exit and the final classifier (ee_set_patience_vector).  The same value
+        serves the exit rules "patient_confident" and "patience_or_threshold" (``set_exit_rule``)."""
+        t = check_patience_spec(t, self.E + 1)
+        if isinstance(t, list):
+            capi.check(self.lib.ee_set_patience_vector(self._h, (C.c_int32 * len(t))(*t), len(t)), self._h, "ee_set_patience_vector")
+        else:
+            capi.check(self.lib.ee_set_patience(self._h, t), self._h, "ee_set_patience")
         self.patience = t
         return t
+
+    def set_exit_rule(self, rule) -> ExitRule:
+        """Exit rule of every later forward and capture (ee_set_exit_rule; include/mmee.h MMEE_RULE_*): "plain" (the criterion / LTE test
+        alone), "patient_confident" (the test has held at ``patience`` exits in a row) or "patience_or_threshold" (the test fires, or the
+        prediction has been stable for ``patience`` exits).  Refused under the "patience" criterion, which has no threshold test."""
+        r = rule if isinstance(rule, ExitRule) else ExitRule(str(rule))
+        capi.check(self.lib.ee_set_exit_rule(self._h, r.code), self._h, "ee_set_exit_rule")
+        self.exit_rule = r
+        return r
 
     def clock_stamp(self):
         """Device tensor of capi.CLOCK_STAMP_WORDS int64: one (s_memtime, s_memrealtime) pair per CU as seen by one-wave workgroups enqueued on
@@ -495,10 +515,10 @@ class CapturedForward:
         self.engine, self.graph_id, self.inputs, self.outputs = engine, graph_id, inputs, outputs
 
     def launch(self, thresholds: Optional[Union[float, Sequence[float]]] = None, temperatures: Optional[Sequence[float]] = None,
-               validate: bool = False, patience: Optional[int] = None) -> EngineOutput:
+               validate: bool = False, patience: Optional[Union[int, Sequence[int]]] = None) -> EngineOutput:
         """Replay on torch's current stream with this launch's thresholds / temperatures; returns ``self.outputs`` (the same tensors every
-        time: copy what must outlive the next launch).  ``patience``: ``engine.set_patience(patience)`` first; a graph captured under the
-        patience criterion replays with the engine's current patience either way."""
+        time: copy what must outlive the next launch).  ``patience``: ``engine.set_patience(patience)`` first (an int or one entry per exit); a
+        graph captured under the patience criterion or a combined exit rule replays with the engine's current patience either way."""
         eng = self.engine
         if patience is not None:
             eng.set_patience(patience)

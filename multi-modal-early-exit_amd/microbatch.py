@@ -183,10 +183,23 @@ class MicroBatchedEngine:
             st = e.set_criterion(strategy)
         return st
 
-    def set_patience(self, t: int) -> int:
+    def set_patience(self, t):
         for e in self.engines:
             t = e.set_patience(t)
         return t
+
+    def set_exit_rule(self, rule):
+        for e in self.engines:
+            rule = e.set_exit_rule(rule)
+        return rule
+
+    @property
+    def patience(self):
+        return self.engines[0].patience
+
+    @property
+    def exit_rule(self):
+        return self.engines[0].exit_rule
 
     def clock_stamp(self):
         return self.engines[0].clock_stamp()

@@ -106,7 +106,8 @@ class LayoutLMv3EEForSequenceClassification:
             exit_config={"training_strategy": ec.training_strategy, "inference_strategy": ec.inference_strategy,
                          "global_threshold": ec.global_threshold, "exits": list(ec.exits),
                          "encoder_layer_strategy": ec.encoder_layer_strategy,
-                         "exit_head_num_layers": ec.exit_head_num_layers, "patience": ec.patience, "use_lte": ec.use_lte},
+                         "exit_head_num_layers": ec.exit_head_num_layers, "patience": ec.patience, "use_lte": ec.use_lte,
+                         "exit_rule": str(ec.exit_rule)},
             EE_config=dict(config.EE_config), num_labels=config.num_labels,
             id2label={i: f"LABEL_{i}" for i in range(config.num_labels)}, use_return_dict=True,
             hidden_size=config.hidden_size, num_hidden_layers=config.num_hidden_layers)
@@ -193,14 +194,20 @@ class LayoutLMv3EEForSequenceClassification:
                                       "patience is an early_exit policy")
 
     def _patience_kw(self, patience, kw):
-        """Under inference_strategy == "patience": the ``patience=`` argument, else ``config.exit_config["patience"]``; neither is a ValueError."""
-        if not self._is_patience():
+        """``config.exit_config["exit_rule"]`` (re-read at every call, like the criterion) goes down as ``exit_rule=``.  Under
+        inference_strategy == "patience" or a rule other than "plain": the ``patience=`` argument, else ``config.exit_config["patience"]``
+        (an int or a per-exit list); neither is a ValueError."""
+        rule = str(self.config.exit_config.get("exit_rule") or "plain")
+        kw.setdefault("exit_rule", rule)
+        if not self._is_patience() and str(kw["exit_rule"]) == "plain":
             if patience is not None:
-                raise ValueError("patience= is an argument of the 'patience' inference_strategy")
+                raise ValueError("patience= is an argument of the 'patience' inference_strategy and of the exit rules "
+                                 "'patient_confident' / 'patience_or_threshold'")
             return
         t = patience if patience is not None else self.config.exit_config.get("patience")
         if t is None:
-            raise ValueError("inference_strategy 'patience' needs config.exit_config['patience'] or a patience= argument")
+            raise ValueError("inference_strategy 'patience' and the exit rules 'patient_confident' / 'patience_or_threshold' need "
+                             "config.exit_config['patience'] or a patience= argument")
         kw["patience"] = t
 
     # ---- chunked engine call -------------------------------------------------------------------------------------------
@@ -300,7 +307,9 @@ class LayoutLMv3EEForSequenceClassification:
         ``thresholds`` defaults to ``config.exit_config["global_threshold"]``.  Under ``inference_strategy == "patience"`` the thresholds are
         ignored and the patience is ``patience=`` or ``config.exit_config["patience"]`` (``ValueError`` when neither is set).  Under
         ``EE_config["use_lte"]`` the default threshold is the same ``global_threshold``, repeated for every exit, as the reference's
-        ``enable_lte()`` repeats its one threshold (EE/models/LayoutLMv3.py:147-149); ``confidence`` is the LTE score."""
+        ``enable_lte()`` repeats its one threshold (EE/models/LayoutLMv3.py:147-149); ``confidence`` is the LTE score.  Under
+        ``config.exit_config["exit_rule"]`` "patient_confident" / "patience_or_threshold" the thresholds feed the rule's event and the patience
+        is read as under "patience" (include/mmee.h MMEE_RULE_*); ``forward`` (dump-all) does not look at the rule."""
         self._patience_kw(patience, kw)
         if thresholds is None:
             thresholds = self.config.exit_config["global_threshold"]

@@ -99,14 +99,59 @@ def lte_scan_device(scores, logits, thresholds, device=None):
     return exits, pred, counts
 
 
+def rule_scan_device(criterion, logits, thresholds, patience, rule, sign: float = 1.0, device=None, want_conf: bool = False):
+    """The combined exit rules (include/mmee.h MMEE_RULE_*) on dumped arrays (ee_rule_scan).  ``criterion`` (E1,N): the criterion table
+    (``sweep.msp_table`` for max-softmax) or the LTE scores; ``sign`` +1: the test is ``criterion > threshold``, -1: ``criterion <
+    threshold`` (entropy, LTE).  ``logits`` (E1,N,K); ``thresholds`` scalar or (E1,); ``patience`` an int or one entry per exit; ``rule``
+    "patient_confident" (the test has held at ``patience`` exits in a row) or "patience_or_threshold" (the test fires, or the argmax has been
+    the same for ``patience`` exits).  Returns device tensors (exits int32, predictions float64, confidence float64 | None = the criterion
+    entry of the chosen exit, counts int32)."""
+    from .config import ExitRule, check_patience_spec
+    r = rule if isinstance(rule, ExitRule) else ExitRule(str(rule))
+    if r == ExitRule.PLAIN:
+        raise ValueError('rule_scan_device evaluates "patient_confident" and "patience_or_threshold"; "plain" is policy_scan_device')
+    if float(sign) not in (1.0, -1.0):
+        raise ValueError("sign must be +1 (criterion > threshold) or -1 (criterion < threshold)")
+    lib = capi.load()
+    dev = _require_torch_cuda(device)
+    to = lambda x: (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x).to(dev, dtype=torch.float64).contiguous()
+    Cr, L = to(criterion), to(logits)
+    if L.dim() != 3 or tuple(Cr.shape) != tuple(L.shape[:2]):
+        raise ValueError("criterion must have shape (num_exits + 1, num_samples) and logits (num_exits + 1, num_samples, num_labels)")
+    E1, N, K = L.shape
+    t = check_patience_spec(patience, E1)
+    pat_c = (C.c_int32 * E1)(*(t if isinstance(t, list) else [t] * E1))
+    thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float64).reshape(-1), (E1,)) if np.ndim(thresholds) \
+        else np.full((E1,), float(thresholds))
+    thr_c = (C.c_double * E1)(*[float(x) for x in thr])
+    exits = torch.empty((N,), dtype=torch.int32, device=dev)
+    pred = torch.empty((N, K), dtype=torch.float64, device=dev)
+    conf = torch.empty((N,), dtype=torch.float64, device=dev) if want_conf else None
+    counts = torch.zeros((E1,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        rc = lib.ee_rule_scan(C.c_void_p(Cr.data_ptr()), float(sign), C.c_void_p(L.data_ptr()), E1, N, K, thr_c, pat_c, r.code,
+                              C.c_void_p(exits.data_ptr()), C.c_void_p(pred.data_ptr()),
+                              C.c_void_p(conf.data_ptr()) if conf is not None else None, C.c_void_p(counts.data_ptr()), stream)
+    capi.check(rc, None, "ee_rule_scan")
+    return exits, pred, conf, counts
+
+
 class Policy:
     def __init__(self, logits, config) -> None:
         self.logits = logits
         self.config = config
 
-    def _finish(self, thresholds=None, patience=None, lte_scores=None):
+    def _finish(self, thresholds=None, patience=None, lte_scores=None, rule=None):
         num_exits, num_samples = self.logits.shape[0], self.logits.shape[1]
-        if lte_scores is not None:
+        if rule is not None:
+            if lte_scores is not None:
+                crit, sign = lte_scores, -1.0
+            else:
+                from .sweep import msp_table
+                crit, sign = msp_table(self.logits)[0], 1.0
+            exits, pred, _, counts = rule_scan_device(crit, self.logits, thresholds, patience, rule, sign=sign)
+        elif lte_scores is not None:
             exits, pred, counts = lte_scan_device(lte_scores, self.logits, thresholds)
         elif patience is not None:
             exits, pred, _, counts = patience_scan_device(self.logits, patience)
@@ -144,6 +189,31 @@ class Policy:
                 raise ValueError('lte_policy needs config["lte_thresholds"] (per exit) or config["exit_threshold"]')
             thr = float(self.config["exit_threshold"])
         return self._finish(thr, lte_scores=self.config["lte_scores"])
+
+    def _rule_policy(self, rule):
+        if self.config.get("patience") is None:
+            raise ValueError(f'{rule}_policy needs config["patience"] (an integer >= 1, or one per exit)')
+        lte = self.config.get("lte_scores")
+        thr = self.config.get("lte_thresholds" if lte is not None else "exit_thresholds")
+        if thr is None:
+            if self.config.get("exit_threshold") is None:
+                raise ValueError(f'{rule}_policy needs config["exit_thresholds"] (per exit) or config["exit_threshold"]')
+            thr = float(self.config["exit_threshold"])
+        return self._finish(thr, patience=self.config["patience"], lte_scores=lte, rule=rule)
+
+    def patient_confident_policy(self):
+        """Patient and confident (PCEE-BERT, Zhang et al. 2022; include/mmee.h MMEE_RULE_STREAK; the reference has no counterpart): exit at the
+        first e where the confidence test ``max-softmax > threshold`` has held at ``config["patience"]`` exits in a row (an int, or one
+        entry per exit), else the last.  Thresholds: ``config["exit_thresholds"]`` (per exit) or the global ``config["exit_threshold"]``.
+        With ``config["lte_scores"]`` the test is the LTE one (``score < config["lte_thresholds"][e]`` or the global threshold).
+        ``config["exit_policy"] = "patient_confident_policy"`` selects it through EE/eval.py:91-98's ``getattr`` dispatch."""
+        return self._rule_policy("patient_confident")
+
+    def patience_or_threshold_policy(self):
+        """Patience or threshold (PABEE's hybrid; include/mmee.h MMEE_RULE_EITHER): exit at the first e where the confidence test fires or
+        the argmax has stayed the same for ``config["patience"]`` exits in a row: the earlier of the threshold policy's and
+        ``patience_policy``'s exits.  Same configuration keys as ``patient_confident_policy``."""
+        return self._rule_policy("patience_or_threshold")
 
     def accuracy_calibration_heuristic(self):
         """EE/policy.py:55-111: per-exit thresholds minmax_eps(1 - accuracy/ece)."""

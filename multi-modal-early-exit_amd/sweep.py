@@ -61,6 +61,42 @@ def patience_sweep(logits, references, patiences, want_hist: bool = False, devic
     return acc, mex, hist
 
 
+def rule_sweep(criterion, logits, references, thresholds, patiences, rule, sign: float = 1.0, want_hist: bool = False, device=None):
+    """V threshold vectors x P patience values of a combined exit rule ("patient_confident" / "patience_or_threshold", include/mmee.h
+    MMEE_RULE_*) in one call (ee_rule_sweep), with the POLICY's semantics -- strict compares, the final exit when nothing qualifies -- as
+    ``patience_sweep`` follows its policy's, not ``threshold_sweep``'s ``>=`` / exit 0.  ``criterion`` (E1,N): ``msp_table(logits)[0]`` or any
+    other criterion table; ``sign`` +1: the test is ``criterion > threshold``, -1: ``criterion < threshold`` (table and thresholds are
+    negated, which is exact); ``logits`` (E1,N,K), ``references`` (N,), ``thresholds`` (V,E1), ``patiences`` (P,) integers >= 1, each used at
+    every exit.  A document's streak is walked once per threshold vector; every patience value is a lookup.  Returns device tensors
+    ``(accuracy (V,P), mean_exit (V,P), hist (V,P,E1) | None)``, all from integer sums."""
+    from .config import ExitRule, check_patience
+    r = rule if isinstance(rule, ExitRule) else ExitRule(str(rule))
+    if r == ExitRule.PLAIN:
+        raise ValueError('rule_sweep evaluates "patient_confident" and "patience_or_threshold"')
+    if float(sign) not in (1.0, -1.0):
+        raise ValueError("sign must be +1 or -1")
+    lib = capi.load()
+    dev = _require_torch_cuda(device)
+    to = lambda x, dt: (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else torch.as_tensor(x)).to(dev, dt).contiguous()
+    pats = [check_patience(t) for t in np.asarray(patiences).reshape(-1).tolist()]
+    cf, L, refs, th = to(criterion, torch.float64), to(logits, torch.float64), to(references, torch.int64), to(thresholds, torch.float64)
+    if L.dim() != 3 or tuple(cf.shape) != tuple(L.shape[:2]) or tuple(refs.shape) != (L.shape[1],) or th.dim() != 2 or th.shape[1] != L.shape[0]:
+        raise ValueError("criterion (E1,N), logits (E1,N,K), references (N,), thresholds (V,E1)")
+    if float(sign) < 0:
+        cf, th = -cf, -th
+    E1, N, K = L.shape
+    V, P = th.shape[0], len(pats)
+    pt = (C.c_int32 * P)(*pats)
+    acc = torch.empty((V, P), dtype=torch.float64, device=dev)
+    mex = torch.empty((V, P), dtype=torch.float64, device=dev)
+    hist = torch.empty((V, P, E1), dtype=torch.int32, device=dev) if want_hist else None
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    with torch.cuda.device(dev):
+        capi.check(lib.ee_rule_sweep(p(cf), p(L), p(refs), E1, N, K, p(th), V, pt, P, r.code, p(acc), p(mex), p(hist), _stream()), None,
+                   "ee_rule_sweep")
+    return acc, mex, hist
+
+
 def lte_sweep(scores, correct, thresholds, want_hist: bool = False, device=None):
     """Many LTE threshold vectors over one table of scores: ``threshold_sweep`` on ``-scores`` / ``-thresholds`` (negation is exact), so
     exits = (scores <= thr[v][:, None]).argmax(0) -- the first exit whose score is AT OR BELOW its threshold, exit 0 when none is.  The
