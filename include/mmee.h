@@ -133,11 +133,24 @@ enum {
                                   deviation separately"): the layer GEMMs and the attention of an MMEE_PREC_F32_SPLIT LayoutLMv3 handle run ONE f16
                                   MFMA term per MAC (hi planes only, f32 accumulate) instead of three; CLS probes and exit heads keep three.  Logits
                                   leave the 1e-4 bar and exit indices may flip: bench.py reports rate, max |dlogit| and flip rate as `lowprec` */
-    MMEE_FLAG_XPROBE = 16      /* probe-first layers take the CLS context in X space (csrc/xprobe.hip): score_j = (W_k^T q) . x_j + q . b_k,
+    MMEE_FLAG_XPROBE = 16,     /* probe-first layers take the CLS context in X space (csrc/xprobe.hip): score_j = (W_k^T q) . x_j + q . b_k,
                                   ctx = W_v (sum_j p_j x_j) + b_v.  No Q | K | V projection exists when the decision is taken: the layer's
                                   Q | K | V GEMM then runs for the documents that STAY only, and not at all in the last layer.  A
                                   re-association of the same arithmetic (~1e-6 on the CLS row): exit indices and the 1e-4 logit bar hold,
                                   bit-identity with MMEE_FLAG_WHOLE_LAYERS does not.  LayoutLMv3, MMEE_PREC_F32_SPLIT, no dump-all */
+    MMEE_FLAG_LOW_LATENCY = 64 /* small batches (the reference's eval_batch_size = 1, EE/configs.py:36): in the rest of every LayoutLMv3 layer
+                                  (attention, attention output, FFN) the attention-output and FFN-down GEMMs run as S-way split-K whenever
+                                  ee_low_latency_k_splits gives S > 1 for this call's static row count B * (T + patches + 1): S workgroups per
+                                  128 x 128 output tile, each over K / S, writing alpha * acc of its part and no bias.  The LayerNorm that
+                                  follows completes the row from the S parts in the order p = 0, 1, ..., then the bias, then the residual.
+                                  A re-association of the whole-layer arithmetic: within the 1e-4 bar of the goldens, with equal exit
+                                  indices; NOT bit-identical to the same call without the flag, nor to the K | V probe (a flagged forward
+                                  is bit-identical to its own dump-all rows under MMEE_FLAG_WHOLE_LAYERS).  The bits depend only on
+                                  (B, T, flags, handle configuration), never on batch mates or on timing: S comes from the static row
+                                  count, so the launch list stays a pure function of the call and a captured graph binds it.  Where the rule
+                                  gives S = 1 for both GEMMs the flag changes nothing, neither a launch nor a bit.  Q | K | V, FFN-up,
+                                  attention, probes and the exit tail are as without the flag.  Refused, each with a message: on an
+                                  MMEE_PREC_F32 handle, on an MMEE_ARCH_BEIT handle, together with MMEE_FLAG_ONE_TERM */
 };
 
 typedef struct ee_handle ee_handle;
@@ -260,6 +273,17 @@ int ee_last_flops(ee_handle* h, double* gemm_flops, double* attn_flops, void* st
  * ee_last_flops leaves out. */
 int ee_last_layer_plan(ee_handle* h, int32_t* rows_qkv, int32_t* rows_main, int32_t* docs_probe, int32_t cap, double* probe_flops,
                        void* stream);
+
+/* The split-K rule of MMEE_FLAG_LOW_LATENCY: how many parts S the k-loop of a residual GEMM with N output columns and inner size K is divided
+ * into when the call has max_rows = B * (T + patches + 1) rows, on a chip of num_cus compute units.  A pure function: no handle, no GPU.
+ * S is the largest of {8, 4, 2} that divides the K / 32 k-stages, leaves every part at least 3 stages (the depth of the kernel's stage ring) and
+ * keeps ceil(max_rows / 128) * (N / 128) * S <= 2 * num_cus -- the 128 x 128 tiles of the launch times S still fit the chip at two workgroups
+ * per CU -- else 1.  Non-increasing in max_rows.  Arguments outside the kernel's shapes (N % 128, K % 32, anything < 1) give 1.
+ * (Measured against the bound <= num_cus at B = 1, 2, 4, T = 512, LayoutLMv3-base: profiles/low_latency_ab.txt.) */
+int32_t ee_low_latency_k_splits(int32_t max_rows, int32_t N, int32_t K, int32_t num_cus);
+/* The S the handle's most recent forward (or graph launch) used for the attention-output and the FFN-down GEMMs of its layers: 1 / 1 when
+ * MMEE_FLAG_LOW_LATENCY was off or the rule declined.  Either pointer may be NULL.  Does not synchronise. */
+int ee_last_k_splits(ee_handle* h, int32_t* attn_out, int32_t* ffn_down);
 
 /* The exit criterion of every LATER ee_forward (MMEE_CRIT_*; ee_config.criterion is its initial value).  The reference's evaluation driver
  * overrides `model.config.exit_config["inference_strategy"]` after the model has been built (EE/utils.py:62-78); the Python mirror forwards that

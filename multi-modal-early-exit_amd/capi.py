@@ -18,6 +18,7 @@ FLAG_WHOLE_LAYERS = 4
 FLAG_PROBE_ALWAYS = 8
 FLAG_XPROBE = 16
 FLAG_ONE_TERM = 32
+FLAG_LOW_LATENCY = 64
 CRIT_MAX_CONFIDENCE, CRIT_ENTROPY, CRIT_PATIENCE = 0, 1, 2
 RULE_PLAIN, RULE_STREAK, RULE_EITHER = 0, 1, 2
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
@@ -75,6 +76,8 @@ SYMBOLS = {
     "ee_last_stage_counts": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _i32, C.POINTER(_i32), _vp]),
     "ee_last_flops": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
     "ee_last_layer_plan": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, C.POINTER(C.c_double), _vp]),
+    "ee_low_latency_k_splits": (_i32, [_i32, _i32, _i32, _i32]),
+    "ee_last_k_splits": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "ee_set_probe_mask": (C.c_int, [_vp, _i32, C.c_uint64]),
     "ee_set_criterion": (C.c_int, [_vp, _i32]),
     "ee_set_patience": (C.c_int, [_vp, _i32]),

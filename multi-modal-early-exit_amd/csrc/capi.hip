@@ -317,6 +317,10 @@ int alloc_workspace(ee_handle* h) {
                 rc |= dev_alloc(h, &h->xp_order, Bm + 1);
                 rc |= dev_alloc(h, &h->xp_c, Bm * (size_t)c.num_attention_heads * H);
                 rc |= dev_alloc(h, &h->xp_part, 4 * Bm * H);      // split-K parts of the probe's FFN-down rows
+                // MMEE_FLAG_LOW_LATENCY: the parts of a layer's residual GEMM.  ee_low_latency_k_splits keeps (128 x 128 tiles) x S <= 2 * num_cus,
+                // so the buffer is that many tiles (33.5 MB at 256 CUs) whatever H and max_docs are
+                h->ll_part_floats = (size_t)2 * h->num_cus * 128 * 128;
+                rc |= dev_alloc(h, &h->ll_part, h->ll_part_floats);
             }
             if (!rc) {
                 std::vector<int> io(Bm);

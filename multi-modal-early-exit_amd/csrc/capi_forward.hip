@@ -94,6 +94,11 @@ struct Forward {
     // (LayoutLMv3 handles only, as include/mmee.h says: on a BEiT / DiT handle validate() refuses the flag -- ADVICE r04: it used to give an
     // undocumented mix of one-term residual GEMMs and three-term everything else)
     const bool one_term = (a.flags & MMEE_FLAG_ONE_TERM) && sp && !beit;
+    // MMEE_FLAG_LOW_LATENCY: the attention-output and FFN-down GEMMs of layer_rest as split-K, S per role from ee_low_latency_k_splits on the
+    // call's STATIC row count (run() sets ks_ao / ks_down once the call is valid): the launch list stays a pure function of the call
+    const bool low_latency = (a.flags & MMEE_FLAG_LOW_LATENCY) && sp && !beit;
+    int ks_ao = 1, ks_down = 1;
+    size_t ll_stride = 0;                    // floats between two parts: (rows padded to whole 128-row tiles) x H
     // split precision attention: attention_idx.hip (pair index built once per forward; default) or, with MMEE_ATTN_V=2 or bucket tables
     // beyond 64 bins, attention_pair.hip (clamped Delta tables gathered per layer and head)
     const bool use_idx = sp && attn_variant() == 0 && c.rel_pos_bins <= 64 && c.rel_2d_pos_bins <= 64;
@@ -145,6 +150,12 @@ struct Forward {
             return fail(h, "ee_forward: attention maps are (B, heads, S, S) in the padded layout: pass MMEE_FLAG_DENSE_ROWS (S <= 1280)");
         if ((a.flags & MMEE_FLAG_ONE_TERM) && (beit || !sp))
             return fail(h, "ee_forward: MMEE_FLAG_ONE_TERM exists for MMEE_PREC_F32_SPLIT LayoutLMv3 handles only");
+        if ((a.flags & MMEE_FLAG_LOW_LATENCY) && (beit || !sp))
+            return fail(h, "ee_forward: MMEE_FLAG_LOW_LATENCY exists for MMEE_PREC_F32_SPLIT LayoutLMv3 handles only (the split-K residual GEMMs are "
+                           "split-precision kernels; %s)", beit ? "this is an MMEE_ARCH_BEIT handle" : "this is an MMEE_PREC_F32 handle");
+        if ((a.flags & MMEE_FLAG_LOW_LATENCY) && (a.flags & MMEE_FLAG_ONE_TERM))
+            return fail(h, "ee_forward: MMEE_FLAG_LOW_LATENCY together with MMEE_FLAG_ONE_TERM: the split-K parts are three-term GEMMs, the one-term mode "
+                           "is a reported deviation; pick one");
         if (hs_out && (a.flags & (MMEE_FLAG_NO_EXIT | MMEE_FLAG_WHOLE_LAYERS)) != (MMEE_FLAG_NO_EXIT | MMEE_FLAG_WHOLE_LAYERS))
             return fail(h, "ee_forward: hidden states are collected in dump-all mode with whole layers only (MMEE_FLAG_NO_EXIT | MMEE_FLAG_WHOLE_LAYERS)");
         if (cap && (hs_out || embeds_in || head_mask || attn_out || h->prof_on))
@@ -208,6 +219,14 @@ struct Forward {
     // LayerNorm of the rows src[rows[r]] (rows null: dense) into f32 rows (dst) or split planes scaled by kSplitScaleX (dst_split)
     void ln_rows(const float* src, const int* rows, float* dst, float* dst_split, const float* gamma, const float* beta, const int* n_ptr, int max_n) {
         launch_ln_rows(src, dst, rows, n_ptr, max_n, H, gamma, beta, c.layer_norm_eps, cus, s, dst_split, mmee::kSplitScaleX, h->err_flag);
+    }
+
+    // low latency: LayerNorm of the rows completed from the S split-K parts in ll_part (+ bias + residual row resid[resid_rows[r]]; null: dense)
+    // into split planes
+    void ln_parts(const float* bias, const float* resid, const int* resid_rows, float* dst_split, const float* gamma, const float* beta, int parts,
+                  const int* n_ptr) {
+        launch_ln_rows(h->ll_part, nullptr, nullptr, n_ptr, max_rows, H, gamma, beta, c.layer_norm_eps, cus, s, dst_split, mmee::kSplitScaleX, h->err_flag,
+                       parts, ll_stride, bias, resid, resid_rows, 1.0f / mmee::kSplitScaleX);
     }
 
     // the layer output X as its readers find it: split planes of Xs (scaled by kSplitScaleX) or f32 rows of X
@@ -406,19 +425,35 @@ struct Forward {
             mmee::launch_head_scale_ctx(h->CTX, H, rp, max_rows, H, head_mask + (size_t)l * c.num_attention_heads, sp ? 1 : 0, mmee::kSplitScaleCtx, cus,
                                         h->err_flag, s);
         GemmArgs g = attn_out_gemm(w, sp);
-        g.A = h->CTX; g.lda = H; g.C = h->Y; g.ldc = H; g.resid = sp ? h->Xs : h->X; g.ldr = H; g.resid_row_src = x_rows;
-        g.resid_split_inv = sp ? 1.0f / mmee::kSplitScaleX : 0.f; g.role_tag = 2; g.m_ptr = rp; g.tile_counter = next_head();
-        { ProfScope ps(h, P_GAO, s); run_gemm(g, EPI_RESID); }
-        // split mode: the LayerNorm output exists only as split planes (22 bits); its readers (next GEMM, residual adds, exit heads) take it from there
-        { ProfScope ps(h, P_LN, s); ln_rows(h->Y, nullptr, sp ? nullptr : h->Y, sp ? h->Ys : nullptr, w.ao_g, w.ao_beta, rp, max_rows); }
+        g.A = h->CTX; g.lda = H; g.role_tag = 2; g.m_ptr = rp;
+        if (ks_ao > 1) {
+            // low latency: S parts of alpha * acc into ll_part, no bias; the LayerNorm launch adds the parts in order, the bias, the residual
+            // (Xs read through x_rows after a compaction) and writes Ys
+            g.bias = nullptr; g.C = h->ll_part; g.ldc = H; g.k_splits = ks_ao; g.split_stride = ll_stride;
+            { ProfScope ps(h, P_GAO, s); run_gemm(g, EPI_BIAS); }
+            { ProfScope ps(h, P_LN, s); ln_parts(w.ao_b, h->Xs, x_rows, h->Ys, w.ao_g, w.ao_beta, ks_ao, rp); }
+        } else {
+            g.C = h->Y; g.ldc = H; g.resid = sp ? h->Xs : h->X; g.ldr = H; g.resid_row_src = x_rows;
+            g.resid_split_inv = sp ? 1.0f / mmee::kSplitScaleX : 0.f; g.tile_counter = next_head();
+            { ProfScope ps(h, P_GAO, s); run_gemm(g, EPI_RESID); }
+            // split mode: the LayerNorm output exists only as split planes (22 bits); its readers (next GEMM, residual adds, exit heads) take it from there
+            { ProfScope ps(h, P_LN, s); ln_rows(h->Y, nullptr, sp ? nullptr : h->Y, sp ? h->Ys : nullptr, w.ao_g, w.ao_beta, rp, max_rows); }
+        }
         g = ffn_up_gemm(w, sp);
         g.A = sp ? h->Ys : h->Y; g.lda = H; g.C = h->H1; g.ldc = I; g.m_ptr = rp; g.tile_counter = next_head();
         { ProfScope ps(h, P_GUP, s); run_gemm(g, EPI_GELU); }
         g = ffn_down_gemm(w, sp);
-        g.A = h->H1; g.lda = I; g.C = h->X; g.ldc = H; g.resid = sp ? h->Ys : h->Y; g.ldr = H;
-        g.resid_split_inv = sp ? 1.0f / mmee::kSplitScaleX : 0.f; g.role_tag = 3; g.m_ptr = rp; g.tile_counter = next_head();
-        { ProfScope ps(h, P_GDOWN, s); run_gemm(g, EPI_RESID); }
-        { ProfScope ps(h, P_LN, s); ln_rows(h->X, nullptr, sp ? nullptr : h->X, sp ? h->Xs : nullptr, w.f_g, w.f_beta, rp, max_rows); }
+        g.A = h->H1; g.lda = I; g.role_tag = 3; g.m_ptr = rp;
+        if (ks_down > 1) {      // the same with the FFN's bias, the residual Ys (dense: this layer wrote it) and Xs as the output
+            g.bias = nullptr; g.C = h->ll_part; g.ldc = H; g.k_splits = ks_down; g.split_stride = ll_stride;
+            { ProfScope ps(h, P_GDOWN, s); run_gemm(g, EPI_BIAS); }
+            { ProfScope ps(h, P_LN, s); ln_parts(w.f2_b, h->Ys, nullptr, h->Xs, w.f_g, w.f_beta, ks_down, rp); }
+        } else {
+            g.C = h->X; g.ldc = H; g.resid = sp ? h->Ys : h->Y; g.ldr = H;
+            g.resid_split_inv = sp ? 1.0f / mmee::kSplitScaleX : 0.f; g.tile_counter = next_head();
+            { ProfScope ps(h, P_GDOWN, s); run_gemm(g, EPI_RESID); }
+            { ProfScope ps(h, P_LN, s); ln_rows(h->X, nullptr, sp ? nullptr : h->X, sp ? h->Xs : nullptr, w.f_g, w.f_beta, rp, max_rows); }
+        }
         h->rec.layer_stage[l] = cur;
     }
 
@@ -468,7 +503,7 @@ struct Forward {
             g.bias = nullptr; g.C = h->xp_part; g.ldc = H; g.k_splits = kSplitK; g.split_stride = (size_t)B * H;
             launch_gemm_split(g, EPI_BIAS, B, cus, s);
             launch_ln_rows(h->xp_part, nullptr, nullptr, nd, B, H, w.f_g, w.f_beta, c.layer_norm_eps, cus, s, h->Xcs, mmee::kSplitScaleX, h->err_flag,
-                           kSplitK, (size_t)B * H, w.f2_b, h->Ycs, 1.0f / mmee::kSplitScaleX);
+                           kSplitK, (size_t)B * H, w.f2_b, h->Ycs, nullptr, 1.0f / mmee::kSplitScaleX);
         } else {
             g.C = h->Xc; g.ldc = H; g.resid = h->Ycs; g.ldr = H; g.resid_split_inv = 1.0f / mmee::kSplitScaleX;
             launch_gemm_split(g, EPI_RESID, B, cus, s);
@@ -680,6 +715,13 @@ struct Forward {
         if (const int rc = validate()) return rc;
         max_len = T + Pv;
         max_rows = B * max_len;
+        if (low_latency && h->ll_part) {
+            ll_stride = (size_t)((max_rows + 127) / 128) * 128 * H;
+            ks_ao = ee_low_latency_k_splits(max_rows, H, H, cus);
+            ks_down = ee_low_latency_k_splits(max_rows, H, I, cus);
+            if ((size_t)ks_ao * ll_stride > h->ll_part_floats) ks_ao = 1;          // (the rule's bound is the buffer's size: never taken)
+            if ((size_t)ks_down * ll_stride > h->ll_part_floats) ks_down = 1;
+        }
         if (!cap) { const int rc_pre = forward_pre(h, s); if (rc_pre) return rc_pre; }
         // (a kernel, not hipMemsetAsync: the same launch list then serves the eager call and the captured graph -- replays whose memset NODES were
         //  preceded by an eager forward on the handle came back with an unzeroed error word on ROCm 7.2, tools/graph_debug2.py)
@@ -702,6 +744,7 @@ struct Forward {
         r.layer_probe_stage.assign(L, -1);
         r.layer_xprobe.assign(L, 0);
         r.exit_stage.assign(E + 1, 0);
+        r.ks_attn_out = ks_ao; r.ks_ffn_down = ks_down;
         x_phys = S_x_src(0);
         for (int i = 0; i < c.n_embedding_exits; ++i) {
             const int kind = c.embedding_exits[i];

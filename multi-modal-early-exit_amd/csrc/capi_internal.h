@@ -51,6 +51,7 @@ struct ForwardRecord {
     std::vector<int> layer_probe_stage;           // stage whose CLS rows were probed before the layer's exit decision; -1: no probe
     std::vector<int> layer_xprobe;                // 1: the layer's probe ran in X space
     std::vector<int> exit_stage;                  // stage whose documents reached each exit
+    int ks_attn_out = 1, ks_ffn_down = 1;         // MMEE_FLAG_LOW_LATENCY: split-K parts of the layers' attention-output / FFN-down GEMMs (ee_last_k_splits)
 };
 
 }  // namespace capi
@@ -96,6 +97,8 @@ struct ee_handle {
     float *Yc = nullptr, *Ycs = nullptr, *H1c = nullptr, *Xc = nullptr, *Xcs = nullptr;
     int* xp_order = nullptr;                      // [max_docs + 1]: documents by falling length, ticket counter
     float *Qc = nullptr, *xp_u = nullptr, *xp_s0 = nullptr, *xp_c = nullptr, *xp_part = nullptr;      // X-space probe (xprobe.hip): CLS queries, u, q.b_k, weighted row sums
+    float* ll_part = nullptr;                     // MMEE_FLAG_LOW_LATENCY: split-K parts of a layer's residual GEMM (split precision, LayoutLMv3)
+    size_t ll_part_floats = 0;                    //   2 * num_cus tiles of 128 x 128 floats, the bound of ee_low_latency_k_splits, whatever H, B, T
     int* iota = nullptr;                          // 0 .. max_docs-1
     float *X, *Y, *QKV, *CTX, *H1, *vis_raw, *text_part, *vis_part, *cat_part, *pooled[3], *hid, *hid2, *head_logits, *pol_logits;
     int *text_dst, *emb_pos, *ntext, *row_src, *err_flag;

@@ -87,6 +87,13 @@ int ee_last_stage_counts(ee_handle* h, int32_t* docs_out, int32_t* rows_out, int
     return report_errors(h, err, "a forward since the last check");
 }
 
+int ee_last_k_splits(ee_handle* h, int32_t* attn_out, int32_t* ffn_down) {
+    if (!h || !h->rec.last_stages) return fail(h, "ee_last_k_splits: no forward has run");
+    if (attn_out) *attn_out = h->rec.ks_attn_out;
+    if (ffn_down) *ffn_down = h->rec.ks_ffn_down;
+    return 0;
+}
+
 int ee_set_inputs_embeds(ee_handle* h, const float* embeds) {
     if (!h) return 1;
     if (embeds && h->cfg.arch == MMEE_ARCH_BEIT) return fail(h, "ee_set_inputs_embeds: an image-only model has no text embeddings");

@@ -15,6 +15,23 @@ int ee_bucket_lut(int32_t num_buckets, int32_t max_distance, int32_t max_delta, 
     return 0;
 }
 
+// The split-K rule of MMEE_FLAG_LOW_LATENCY (include/mmee.h): the largest S of {8, 4, 2} that divides the K / 32 k-stages of the 128 x 128 tile
+// configuration, leaves every part at least 3 stages (its stage ring is three deep: a shorter part would never fill it) and keeps
+// tiles x S <= MMEE_LL_TILES_PER_CU x num_cus; else 1.  The tiles are those of the static row count, so S is a function of the call.
+// MMEE_LL_TILES_PER_CU: 2 (two workgroups of the launch per CU) against 1, measured at B = 1, 2, 4 with tools/low_latency_ab.py on two builds
+// of this file (profiles/low_latency_ab.txt).  The parts buffer of ee_create is sized for 2.
+#ifndef MMEE_LL_TILES_PER_CU
+#define MMEE_LL_TILES_PER_CU 2
+#endif
+static_assert(MMEE_LL_TILES_PER_CU == 1 || MMEE_LL_TILES_PER_CU == 2, "the parts buffer holds 2 x num_cus tiles");
+int32_t ee_low_latency_k_splits(int32_t max_rows, int32_t N, int32_t K, int32_t num_cus) {
+    if (max_rows < 1 || N < 128 || N % 128 != 0 || K < 32 || K % 32 != 0 || num_cus < 1) return 1;
+    const long stages = K / 32, tiles = (((long)max_rows + 127) / 128) * (N / 128);
+    for (int S = 8; S >= 2; S /= 2)
+        if (stages % S == 0 && stages / S >= 3 && tiles * S <= (long)MMEE_LL_TILES_PER_CU * num_cus) return S;
+    return 1;
+}
+
 // Shader-clock stamps (bench.py: docs_per_sec_per_ghz).  s_memtime counts shader clocks, s_memrealtime a constant 100 MHz.  The shader-clock
 // counters of different CUs are NOT aligned with each other (measured, round 5: pairing a stamp taken on one CU with a later stamp taken on
 // another CU of the same XCD gave 1.5 ... 3.3 "GHz" over a few milliseconds), so a stamp records one (s_memtime, s_memrealtime) pair PER CU --

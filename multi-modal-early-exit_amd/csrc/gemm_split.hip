@@ -56,6 +56,14 @@ void launch_gemm_split(const GemmArgs& a_in, int epi, int max_m, int num_cus, hi
         if (!a.out_split && epi == EPI_TANH) { launch_split_one<CfgP, EPI_TANH, false, false, 1>(a, max_m, num_cus, s); return; }      // dense + tanh of an exit head
         // not a shape the probe launches: the default configuration below computes the same bits
     }
+    // MMEE_FLAG_LOW_LATENCY: a layer's attention-output / FFN-down GEMM as S-way split-K (capi_forward.hip layer_rest; S from
+    // ee_low_latency_k_splits).  The instantiation of the probe's split-K launch, static tile assignment: part p of a tile is alpha * acc over its
+    // K / S, no bias (the caller passes none); the LayerNorm kernel behind it adds the parts in order, the bias and the residual.
+    if (a.k_splits > 1 && !a.out_split && epi == EPI_BIAS && a.terms != 1) {
+        a.tile_counter = nullptr;
+        launch_split_one<CfgP, EPI_BIAS, false, false, 1>(a, max_m, num_cus, s);
+        return;
+    }
     a.k_splits = 1;      // every kernel below writes ONE part
     // Round 6, small batches (the reference evaluates at eval_batch_size = 1, EE/configs.py:36; bench.py `small_batch`): a forward of one document is
     // 709 rows -- 27 of the default 256 x 256 tiles in the Q|K|V projection, 9 in the attention-output GEMM, on 256 CUs.  When the default tiles

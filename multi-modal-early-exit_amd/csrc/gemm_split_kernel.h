@@ -283,7 +283,8 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
     const int M = g.m_ptr ? *g.m_ptr : g.m_static;
     const int tiles_m = (M + BM - 1) / BM;
     const int tiles_n = g.N / BN;
-    // split-K (the CLS-probe launches, TAG 1, only): K is divided over k_splits workgroups per tile, part p goes to C + p * split_stride
+    // split-K (TAG 1 only: the CLS-probe launches, and the layers' residual GEMMs under MMEE_FLAG_LOW_LATENCY): K is divided over k_splits
+    // workgroups per tile, part p goes to C + p * split_stride
     constexpr bool KSPLIT = TAG == 1;
     const int ksp = KSPLIT && g.k_splits > 1 ? g.k_splits : 1;
     const int n_tiles = tiles_m * tiles_n * ksp;

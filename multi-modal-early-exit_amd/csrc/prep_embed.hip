@@ -429,13 +429,15 @@ __global__ __launch_bounds__(256) void pool_finish_kernel(const float* __restric
 
 // row LayerNorm over the packed rows of the active stage: dst[r] = LN(src[row_src ? row_src[r] : r]) (dst may be src or
 // null); dst_split, when given, receives the same row as split-f16 planes (the A operand of the next split GEMM)
-// pre (CLS-probe rows under MMEE_FLAG_XPROBE only): the row is first completed from the n_parts split-K partial planes of the GEMM in
-// front (src + p * part_stride, added in order p = 0, 1, ...), its bias and the residual row (split planes scaled by 1 / resid_inv).
+// pre (CLS-probe rows under MMEE_FLAG_XPROBE; the layers' residual GEMMs under MMEE_FLAG_LOW_LATENCY): the row is first completed from the
+// n_parts split-K partial planes of the GEMM in front (src + p * part_stride, added in order p = 0, 1, ...), its bias and the residual row
+// (split planes scaled by 1 / resid_inv; row resid_rows[r], or r when resid_rows is null: after a compaction a layer's X rows are gathered).
 struct LnPre {
     int n_parts;
     size_t part_stride;
     const float* bias;
     const char* resid;
+    const int* resid_rows;
     float resid_inv;
 };
 template <int NV, bool PRE, bool FULL = false>      // PRE is a separate instantiation: the layers' own LayerNorm launches carry none of its code
@@ -463,7 +465,7 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const float* __restrict__ 
                 if (FULL || c < H) {
                     for (int q = 1; q < pre.n_parts; ++q) x[i] += *reinterpret_cast<const f32x4*>(p + (size_t)q * pre.part_stride + c);
                     if (pre.bias) x[i] += *reinterpret_cast<const f32x4*>(pre.bias + c);
-                    if (pre.resid) x[i] += load_split4(pre.resid + (size_t)r * H * 4, c, pre.resid_inv);
+                    if (pre.resid) x[i] += load_split4(pre.resid + (size_t)(pre.resid_rows ? pre.resid_rows[r] : r) * H * 4, c, pre.resid_inv);
                 }
             }
         }
@@ -608,9 +610,9 @@ void launch_pool_finish(const float* part, int chunks, int H, float count, float
 
 void launch_ln_rows(const float* src, float* dst, const int* row_src, const int* n_rows_ptr, int max_rows, int H,
                     const float* g, const float* b, float eps, int num_cus, hipStream_t s, void* dst_split_v, float split_scale, int* err_flag,
-                    int pre_parts, size_t pre_stride, const float* pre_bias, const void* pre_resid, float pre_resid_inv) {
+                    int pre_parts, size_t pre_stride, const float* pre_bias, const void* pre_resid, const int* pre_resid_rows, float pre_resid_inv) {
     char* dst_split = reinterpret_cast<char*>(dst_split_v);
-    const LnPre pre{pre_parts, pre_stride, pre_bias, reinterpret_cast<const char*>(pre_resid), pre_resid_inv};
+    const LnPre pre{pre_parts, pre_stride, pre_bias, reinterpret_cast<const char*>(pre_resid), pre_resid_rows, pre_resid_inv};
     int grid = (max_rows + 3) / 4;
     const int cap = num_cus * 8;
     if (grid > cap) grid = cap;

@@ -199,12 +199,15 @@ class EarlyExitEngine:
                 validate: bool = False, whole_layers: bool = False, probe_always: bool = False, xprobe: Optional[bool] = None,
                 one_term: bool = False, inputs_embeds=None, want_hidden_states: bool = False, out=None, head_mask=None,
                 want_attentions: bool = False, patience: Optional[Union[int, Sequence[int]]] = None, exit_rule=None,
-                _capture: bool = False) -> EngineOutput:
+                low_latency: bool = False, _capture: bool = False) -> EngineOutput:
         """``out``: optional preallocated ``(logits (B,K) f32, exit_layer (B,) i32, confidence (B,) f32)`` device tensors (contiguous; row
         slices of larger tensors qualify) the kernels write into instead of fresh allocations -- MicroBatchedEngine hands each half its slice.
         ``patience``: when given, ``set_patience(patience)`` before the call (an int, or one entry per exit; it matters under the "patience"
         criterion and under the two combined exit rules); under the patience criterion ``thresholds`` are ignored.  ``exit_rule``: when
-        given, ``set_exit_rule(exit_rule)`` before the call.  Both stay set for later calls; a capture binds the rule."""
+        given, ``set_exit_rule(exit_rule)`` before the call.  Both stay set for later calls; a capture binds the rule.
+        ``low_latency``: MMEE_FLAG_LOW_LATENCY, for batches of a few documents (the reference's ``eval_batch_size = 1``): the attention-output and
+        FFN-down GEMMs of every layer run as split-K wherever ``capi`` ``ee_low_latency_k_splits`` allows it for this (B, T) -- see
+        ``last_k_splits()``.  Same exits, logits within the 1e-4 bar, not the bits of the call without it; split precision, LayoutLMv3 only."""
         if not self._finalized:
             raise capi.MMEEError("load_weights() has not been called")
         if patience is not None:
@@ -315,7 +318,8 @@ class EarlyExitEngine:
                 att = torch.empty((L_, B, nh, S, S), dtype=torch.float32, device=dev)
         flags = ((capi.FLAG_NO_EXIT if dump_all else 0) | (capi.FLAG_DENSE_ROWS if dense_rows else 0) |
                  (capi.FLAG_WHOLE_LAYERS if whole_layers else 0) | (capi.FLAG_PROBE_ALWAYS if probe_always else 0) |
-                 (capi.FLAG_XPROBE if xprobe else 0) | (capi.FLAG_ONE_TERM if one_term else 0))
+                 (capi.FLAG_XPROBE if xprobe else 0) | (capi.FLAG_ONE_TERM if one_term else 0) |
+                 (capi.FLAG_LOW_LATENCY if low_latency else 0))
         # one_term: REPORTED low-precision mode (one f16 MFMA term per MAC instead of three in the layer GEMMs and the attention); outside the
         # 1e-4 bar by construction, exit indices may flip -- bench.py's `lowprec` field, never a result to rely on
         # xprobe: probe-first layers take the CLS context in X space (no Q | K | V for documents that leave); same exits, logits within
@@ -386,6 +390,13 @@ class EarlyExitEngine:
             capi.check(self.lib.ee_last_stage_counts(self._h, docs, rows, n, C.byref(ns), stream), self._h,
                        "ee_last_stage_counts")
         return {"docs": list(docs)[:ns.value], "rows": list(rows)[:ns.value]}
+
+    def last_k_splits(self):
+        """(attention-output, FFN-down): the split-K parts the layers' two residual GEMMs ran with in the last forward or graph launch
+        (ee_last_k_splits); (1, 1) without ``low_latency`` or where the rule declined.  Does not synchronise."""
+        a, d = C.c_int32(), C.c_int32()
+        capi.check(self.lib.ee_last_k_splits(self._h, C.byref(a), C.byref(d)), self._h, "ee_last_k_splits")
+        return a.value, d.value
 
     def profile(self, enable: bool = True):
         """Arm / disarm per-kernel HIP-event timing of the following forward calls."""

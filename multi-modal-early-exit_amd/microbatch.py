@@ -67,7 +67,10 @@ class MicroBatchedEngine:
     def forward(self, input_ids=None, attention_mask=None, bbox=None, pixel_values=None, token_type_ids=None, position_ids=None,
                 inputs_embeds=None, serial: bool = False, **kw) -> EngineOutput:
         """Same arguments and result as ``EarlyExitEngine.forward``.  ``serial``: run the slices one after the other on the CURRENT stream
-        (per-kernel HIP-event profiling needs launches that do not overlap; same results)."""
+        (per-kernel HIP-event profiling needs launches that do not overlap; same results).  ``low_latency`` is not taken: that mode is for
+        batches of a few documents, micro-batches are for large ones."""
+        if kw.pop("low_latency", False):
+            raise ValueError("low_latency is a small-batch mode of EarlyExitEngine; MicroBatchedEngine runs large batches")
         ref = pixel_values if pixel_values is not None else input_ids
         if ref is None:
             raise ValueError("pixel_values is required")

@@ -301,7 +301,8 @@ class LayoutLMv3EEForSequenceClassification:
     # ---- the fast path ------------------------------------------------------------------------------------------------
     def early_exit(self, input_ids, attention_mask=None, bbox=None, pixel_values=None, token_type_ids=None,
                    position_ids=None, thresholds: Optional[Union[float, Sequence[float]]] = None,
-                   temperatures: Optional[Sequence[float]] = None, patience: Optional[int] = None, **kw) -> EngineOutput:
+                   temperatures: Optional[Sequence[float]] = None, patience: Optional[int] = None, low_latency: bool = False,
+                   **kw) -> EngineOutput:
         """(logits, exit_layer, confidence) with the policy test on the device: identical to running ``forward`` on
         everything and then ``Policy(...)`` (EE/eval.py:87-98), but deeper layers only see the surviving documents.
         ``thresholds`` defaults to ``config.exit_config["global_threshold"]``.  Under ``inference_strategy == "patience"`` the thresholds are
@@ -309,8 +310,11 @@ class LayoutLMv3EEForSequenceClassification:
         ``EE_config["use_lte"]`` the default threshold is the same ``global_threshold``, repeated for every exit, as the reference's
         ``enable_lte()`` repeats its one threshold (EE/models/LayoutLMv3.py:147-149); ``confidence`` is the LTE score.  Under
         ``config.exit_config["exit_rule"]`` "patient_confident" / "patience_or_threshold" the thresholds feed the rule's event and the patience
-        is read as under "patience" (include/mmee.h MMEE_RULE_*); ``forward`` (dump-all) does not look at the rule."""
+        is read as under "patience" (include/mmee.h MMEE_RULE_*); ``forward`` (dump-all) does not look at the rule.
+        ``low_latency=True`` (batches of a few documents, one handle): the engine's split-K mode, ``EarlyExitEngine.forward(low_latency=True)``."""
         self._patience_kw(patience, kw)
+        if low_latency:
+            kw["low_latency"] = True
         if thresholds is None:
             thresholds = self.config.exit_config["global_threshold"]
         self._small_batch_schedule(pixel_values, kw)
