@@ -10,6 +10,7 @@
 //     ee_finalize) and the additive key mask, and writes it to (B, heads, S, S) -- 24 MB per document and layer at S = 709, which is why
 //     nothing else ever does this;
 //   * head_scale_ctx_kernel: context columns of head h times head_mask[l][h] after the fused attention kernel (probs * m @ V == m * (probs @ V)).
+// Also here, equally off the hot path: build_value_tables_kernel, which composes those per-head value tables once at ee_finalize.
 #include "mmee_common.h"
 #include "mmee_kernels.h"
 
@@ -138,6 +139,27 @@ void launch_head_scale_ctx(float* ctx, int ld, const int* n_rows_ptr, int max_ro
     int grid = (int)(blocks < (size_t)num_cus * 16 ? blocks : (size_t)num_cus * 16);
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(head_scale_ctx_kernel, dim3(grid), dim3(256), 0, s, ctx, ld, n_rows_ptr, H, head_scale, split, scale, err_flag);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// value tables of the relative-position bias: t[h][delta + c] = W[h][lut[delta + c]] / sqrt(d)
+// ---------------------------------------------------------------------------------------------------------------
+__global__ void build_value_tables_kernel(const float* w1, const float* wx, const float* wy, const unsigned char* lut1,
+                                          const unsigned char* lut2, int heads, int bins1, int bins2, int n1, int n2,
+                                          float inv_sqrt_d, float* t1, float* tx, float* ty) {
+    const int h = blockIdx.x;
+    for (int i = threadIdx.x; i < n1; i += blockDim.x) t1[(size_t)h * n1 + i] = w1[(size_t)h * bins1 + lut1[i]] * inv_sqrt_d;
+    for (int i = threadIdx.x; i < n2; i += blockDim.x) {
+        tx[(size_t)h * n2 + i] = wx[(size_t)h * bins2 + lut2[i]] * inv_sqrt_d;
+        ty[(size_t)h * n2 + i] = wy[(size_t)h * bins2 + lut2[i]] * inv_sqrt_d;
+    }
+}
+
+void launch_build_value_tables(const float* w1, const float* wx, const float* wy, const unsigned char* lut1,
+                               const unsigned char* lut2, int heads, int bins1, int bins2, int n1, int n2, float inv_sqrt_d,
+                               float* t1, float* tx, float* ty, hipStream_t s) {
+    hipLaunchKernelGGL(build_value_tables_kernel, dim3(heads), dim3(256), 0, s, w1, wx, wy, lut1, lut2, heads, bins1, bins2,
+                       n1, n2, inv_sqrt_d, t1, tx, ty);
 }
 
 }  // namespace mmee

@@ -606,22 +606,17 @@ struct Forward {
         d.out_logits = a.out_logits; d.out_exit = a.out_exit; d.out_conf = a.out_conf;
         d.out_all_logits = a.out_all_logits; d.out_all_crit = a.out_all_crit;
         d.out_head_logits = a.out_head_logits; d.out_head_crit = a.out_head_crit;
-        if (patience || h->rule != MMEE_RULE_PLAIN) {
-            PatienceArgs pa{};
+        if (c.use_lte) d.lte_score = lte ? h->lte_score : nullptr;
+        PatienceArgs pa{};
+        const bool stateful = patience || h->rule != MMEE_RULE_PLAIN;
+        if (stateful) {
             pa.t = h->has_patience() ? h->patience_at(exit_index) : 0;                    // not set: a dump-all call, where nobody leaves
             if (cap) pa.t_ptr = cap->thr_dev + 2 * (E + 1) + exit_index;                  // replays read the patience of THEIR launch
             pa.prev = h->pat_state; pa.run = h->pat_state + c.max_docs;
-            if (c.use_lte) d.lte_score = lte ? h->lte_score : nullptr;
+        }
+        {
             ProfScope ps(h, P_DECIDE, s);
-            if (patience) launch_decide_patience(d, pa, s);
-            else launch_decide_rule(d, pa, h->rule, c.use_lte != 0, s);
-        } else if (c.use_lte) {
-            d.lte_score = lte ? h->lte_score : nullptr;
-            ProfScope ps(h, P_DECIDE, s);
-            launch_decide_lte(d, s);
-        } else {
-            ProfScope ps(h, P_DECIDE, s);
-            launch_decide(d, s);
+            launch_decide(d, stateful ? &pa : nullptr, patience ? DECIDE_PATIENCE : c.use_lte ? DECIDE_LTE : DECIDE_THRESHOLD, h->rule, s);
         }
         h->rec.exit_stage[exit_index] = cur;
         if (!is_final) compact();

@@ -1,11 +1,40 @@
 // Entry points of libmmee_hip.so that never see a handle: bucket LUT, shader-clock stamps, policy / patience / threshold sweeps, temperature
 // fit, result packing, the device-side input feed, and the ee_debug_* hooks that run one kernel on caller-provided buffers.
+#include <string.h>
+
 #include <vector>
 
 #include "capi_internal.h"
 
 using namespace mmee;
 using namespace mmee::capi;
+
+namespace {
+
+// false (and the error message of `who` set) when there is no HIP device
+bool have_device(const char* who) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev >= 1) return true;
+    fail(nullptr, "%s: no HIP device", who);
+    return false;
+}
+
+// A small host vector on the device for the length of one entry point: hipMallocAsync + hipMemcpyAsync here, hipFreeAsync (in stream order) on
+// every way out of the scope.  err: null, or what failed.
+template <typename T>
+struct TempUpload {
+    T* dev = nullptr;
+    hipStream_t s;
+    const char* err = nullptr;
+    TempUpload(const T* host, size_t n, hipStream_t stream) : s(stream) {
+        if (hipMallocAsync((void**)&dev, sizeof(T) * n, s) != hipSuccess) { dev = nullptr; err = "hipMallocAsync failed"; }
+        else if (hipMemcpyAsync(dev, host, sizeof(T) * n, hipMemcpyHostToDevice, s) != hipSuccess) err = "host-to-device copy failed";
+    }
+    TempUpload(const TempUpload&) = delete;
+    ~TempUpload() { if (dev) (void)hipFreeAsync(dev, s); }
+};
+
+}  // namespace
 
 extern "C" {
 
@@ -50,8 +79,7 @@ __global__ void clock_stamp_kernel(unsigned long long* __restrict__ out) {
 
 int ee_clock_stamp(uint64_t* out_dev, void* stream) {
     if (!out_dev) return fail(nullptr, "ee_clock_stamp: null argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_clock_stamp: no HIP device");
+    if (!have_device("ee_clock_stamp")) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (hipMemsetAsync(out_dev, 0, MMEE_CLOCK_STAMP_WORDS * sizeof(uint64_t), s) != hipSuccess) return fail(nullptr, "ee_clock_stamp: memset failed");
     hipLaunchKernelGGL(clock_stamp_kernel, dim3(2048), dim3(64), 0, s, reinterpret_cast<unsigned long long*>(out_dev));
@@ -62,27 +90,28 @@ int ee_policy_scan(const double* logits, int32_t E1, int32_t N, int32_t K, const
                    double* predictions, double* confidence, int32_t* counts, void* stream) {
     if (!thresholds || E1 < 1 || E1 > 256 || N < 0 || K < 1 || (N > 0 && (!logits || !exits)))
         return fail(nullptr, "ee_policy_scan: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_policy_scan: no HIP device");
+    if (!have_device("ee_policy_scan")) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    double* thr_dev = nullptr;
-    if (hipMallocAsync((void**)&thr_dev, sizeof(double) * E1, s) != hipSuccess) return fail(nullptr, "ee_policy_scan: hipMallocAsync failed");
-    if (hipMemcpyAsync(thr_dev, thresholds, sizeof(double) * E1, hipMemcpyHostToDevice, s) != hipSuccess)
-        return fail(nullptr, "ee_policy_scan: threshold copy failed");
+    const TempUpload<double> thr(thresholds, E1, s);
+    if (thr.err) return fail(nullptr, "ee_policy_scan: threshold %s", thr.err);
     if (counts && hipMemsetAsync(counts, 0, sizeof(int) * E1, s) != hipSuccess) return fail(nullptr, "ee_policy_scan: memset failed");
-    if (N > 0) launch_policy_scan(logits, E1, N, K, thr_dev, exits, predictions, confidence, counts, s);
-    (void)hipFreeAsync(thr_dev, s);
+    ScanArgs a{};
+    a.logits = logits; a.sign = 1.0; a.thr = thr.dev; a.E1 = E1; a.N = N; a.K = K;
+    a.exits = exits; a.pred = predictions; a.conf = confidence; a.counts = counts;
+    if (N > 0) launch_exit_scan(a, SCAN_MSP, RULE_PLAIN, s);
     return launch_status(nullptr, "ee_policy_scan");
 }
 
 int ee_patience_scan(const double* logits, int32_t E1, int32_t N, int32_t K, int32_t patience, int32_t* exits, double* predictions,
                      double* confidence, int32_t* counts, void* stream) {
     if (patience < 1 || E1 < 1 || N < 0 || K < 1 || (N > 0 && (!logits || !exits))) return fail(nullptr, "ee_patience_scan: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_patience_scan: no HIP device");
+    if (!have_device("ee_patience_scan")) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (counts && hipMemsetAsync(counts, 0, sizeof(int) * E1, s) != hipSuccess) return fail(nullptr, "ee_patience_scan: memset failed");
-    if (N > 0) launch_patience_scan(logits, E1, N, K, patience, exits, predictions, confidence, counts, s);
+    ScanArgs a{};
+    a.logits = logits; a.pat_all = patience; a.E1 = E1; a.N = N; a.K = K;
+    a.exits = exits; a.pred = predictions; a.conf = confidence; a.counts = counts;
+    if (N > 0) launch_exit_scan(a, SCAN_NONE, RULE_AGREE, s);
     return launch_status(nullptr, "ee_patience_scan");
 }
 
@@ -90,16 +119,15 @@ int ee_lte_scan(const double* scores, const double* logits, int32_t E1, int32_t 
                 double* predictions, int32_t* counts, void* stream) {
     if (!thresholds || E1 < 1 || E1 > 256 || N < 0 || K < 1 || (N > 0 && (!scores || !exits)) || (predictions && !logits))
         return fail(nullptr, "ee_lte_scan: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_lte_scan: no HIP device");
+    if (!have_device("ee_lte_scan")) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    double* thr_dev = nullptr;
-    if (hipMallocAsync((void**)&thr_dev, sizeof(double) * E1, s) != hipSuccess) return fail(nullptr, "ee_lte_scan: hipMallocAsync failed");
-    if (hipMemcpyAsync(thr_dev, thresholds, sizeof(double) * E1, hipMemcpyHostToDevice, s) != hipSuccess)
-        return fail(nullptr, "ee_lte_scan: threshold copy failed");
+    const TempUpload<double> thr(thresholds, E1, s);
+    if (thr.err) return fail(nullptr, "ee_lte_scan: threshold %s", thr.err);
     if (counts && hipMemsetAsync(counts, 0, sizeof(int) * E1, s) != hipSuccess) return fail(nullptr, "ee_lte_scan: memset failed");
-    if (N > 0) launch_lte_scan(scores, logits, E1, N, K, thr_dev, exits, predictions, counts, s);
-    (void)hipFreeAsync(thr_dev, s);
+    ScanArgs a{};
+    a.logits = logits; a.crit = scores; a.sign = -1.0; a.thr = thr.dev; a.E1 = E1; a.N = N; a.K = K;      // score < threshold
+    a.exits = exits; a.pred = predictions; a.counts = counts;
+    if (N > 0) launch_exit_scan(a, SCAN_TABLE, RULE_PLAIN, s);
     return launch_status(nullptr, "ee_lte_scan");
 }
 
@@ -111,20 +139,18 @@ int ee_rule_scan(const double* criterion, double sign, const double* logits, int
     if (!logits && (rule == MMEE_RULE_EITHER || predictions)) return fail(nullptr, "ee_rule_scan: MMEE_RULE_EITHER and predictions need the logits");
     for (int e = 0; e < E1; ++e)
         if (patience[e] < 1) return fail(nullptr, "ee_rule_scan: patience[%d]=%d, every patience must be >= 1", e, patience[e]);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_rule_scan: no HIP device");
+    if (!have_device("ee_rule_scan")) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    double* thr_dev = nullptr;                                       // thresholds [E1] doubles, then the patience [E1] ints
-    if (hipMallocAsync((void**)&thr_dev, (sizeof(double) + sizeof(int)) * E1, s) != hipSuccess) return fail(nullptr, "ee_rule_scan: hipMallocAsync failed");
-    int* pat_dev = reinterpret_cast<int*>(thr_dev + E1);
-    if (hipMemcpyAsync(thr_dev, thresholds, sizeof(double) * E1, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(pat_dev, patience, sizeof(int) * E1, hipMemcpyHostToDevice, s) != hipSuccess ||
-        (counts && hipMemsetAsync(counts, 0, sizeof(int) * E1, s) != hipSuccess)) {
-        (void)hipFreeAsync(thr_dev, s);
-        return fail(nullptr, "ee_rule_scan: threshold / patience copy or counts memset failed");
-    }
-    if (N > 0) launch_rule_scan(criterion, sign, logits, E1, N, K, thr_dev, pat_dev, rule, exits, predictions, confidence, counts, s);
-    (void)hipFreeAsync(thr_dev, s);
+    std::vector<double> packed(E1 + (E1 + 1) / 2);                   // thresholds [E1] doubles, then the patience [E1] ints: one upload
+    memcpy(packed.data(), thresholds, sizeof(double) * E1);
+    memcpy(packed.data() + E1, patience, sizeof(int) * E1);
+    const TempUpload<double> up(packed.data(), packed.size(), s);
+    if (up.err) return fail(nullptr, "ee_rule_scan: threshold / patience %s", up.err);
+    if (counts && hipMemsetAsync(counts, 0, sizeof(int) * E1, s) != hipSuccess) return fail(nullptr, "ee_rule_scan: memset failed");
+    ScanArgs a{};
+    a.logits = logits; a.crit = criterion; a.sign = sign; a.thr = up.dev; a.pat = reinterpret_cast<const int*>(up.dev + E1);
+    a.E1 = E1; a.N = N; a.K = K; a.exits = exits; a.pred = predictions; a.conf = confidence; a.counts = counts;
+    if (N > 0) launch_exit_scan(a, SCAN_TABLE, rule, s);
     return launch_status(nullptr, "ee_rule_scan");
 }
 
@@ -136,20 +162,14 @@ int ee_rule_sweep(const double* conf, const double* logits, const int64_t* refer
     if (rule != MMEE_RULE_STREAK && rule != MMEE_RULE_EITHER) return fail(nullptr, "ee_rule_sweep: rule %d is neither MMEE_RULE_STREAK nor MMEE_RULE_EITHER", rule);
     for (int j = 0; j < P; ++j)
         if (patiences[j] < 1) return fail(nullptr, "ee_rule_sweep: patiences[%d]=%d, every patience must be >= 1", j, patiences[j]);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_rule_sweep: no HIP device");
+    if (!have_device("ee_rule_sweep")) return 1;
     if (V == 0) return 0;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int* pats_dev = nullptr;
-    if (hipMallocAsync((void**)&pats_dev, sizeof(int) * P, s) != hipSuccess) return fail(nullptr, "ee_rule_sweep: hipMallocAsync failed");
-    if (hipMemcpyAsync(pats_dev, patiences, sizeof(int) * P, hipMemcpyHostToDevice, s) != hipSuccess) {
-        (void)hipFreeAsync(pats_dev, s);
-        return fail(nullptr, "ee_rule_sweep: patience copy failed");
-    }
-    const bool ok = launch_rule_sweep(conf, logits, reinterpret_cast<const long long*>(references), E1, N, K, thr, V, patiences, pats_dev, P, rule, acc,
-                                      mean_exit, exit_hist, s);
-    (void)hipFreeAsync(pats_dev, s);
-    if (!ok) return fail(nullptr, "ee_rule_sweep: hipMallocAsync failed");
+    const TempUpload<int> pats(patiences, P, s);
+    if (pats.err) return fail(nullptr, "ee_rule_sweep: patience %s", pats.err);
+    if (!launch_rule_sweep(conf, logits, reinterpret_cast<const long long*>(references), E1, N, K, thr, V, patiences, pats.dev, P, rule, acc, mean_exit,
+                           exit_hist, s))
+        return fail(nullptr, "ee_rule_sweep: hipMallocAsync failed");
     return launch_status(nullptr, "ee_rule_sweep");
 }
 
@@ -157,8 +177,7 @@ int ee_patience_sweep(const double* logits, const int64_t* references, int32_t E
                       double* acc, double* mean_exit, int32_t* exit_hist, void* stream) {
     if (!logits || !references || !patiences || !acc || !mean_exit || E1 < 1 || E1 > 128 || N < 1 || K < 1 || V < 0)
         return fail(nullptr, "ee_patience_sweep: bad argument (E1 <= 128, N >= 1)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_patience_sweep: no HIP device");
+    if (!have_device("ee_patience_sweep")) return 1;
     if (V > 0 && !launch_patience_sweep(logits, reinterpret_cast<const long long*>(references), E1, N, K, patiences, V, acc, mean_exit, exit_hist,
                                         reinterpret_cast<hipStream_t>(stream)))
         return fail(nullptr, "ee_patience_sweep: hipMallocAsync failed");
@@ -167,16 +186,14 @@ int ee_patience_sweep(const double* logits, const int64_t* references, int32_t E
 
 int ee_pack_results(const float* logits, const int32_t* exit_layer, const float* confidence, int32_t n, int32_t K, int32_t* rows, void* stream) {
     if (n < 0 || K < 1 || (n > 0 && (!logits || !exit_layer || !confidence || !rows))) return fail(nullptr, "ee_pack_results: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_pack_results: no HIP device");
+    if (!have_device("ee_pack_results")) return 1;
     if (n > 0) launch_pack_results(logits, exit_layer, confidence, n, K, rows, reinterpret_cast<hipStream_t>(stream));
     return launch_status(nullptr, "ee_pack_results");
 }
 
 int ee_unpack_results(const int32_t* rows, int32_t n, int32_t K, float* logits, int32_t* exit_layer, float* confidence, void* stream) {
     if (n < 0 || K < 1 || (n > 0 && !rows)) return fail(nullptr, "ee_unpack_results: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_unpack_results: no HIP device");
+    if (!have_device("ee_unpack_results")) return 1;
     if (n > 0) launch_unpack_results(rows, n, K, logits, exit_layer, confidence, reinterpret_cast<hipStream_t>(stream));
     return launch_status(nullptr, "ee_unpack_results");
 }
@@ -185,8 +202,7 @@ int ee_threshold_sweep(const double* conf, const uint8_t* correct, int32_t E1, i
                        double* mean_exit, int32_t* exit_hist, void* stream) {
     if (!conf || !correct || !thr || !acc || !mean_exit || E1 < 1 || E1 > 64 || N < 1 || V < 0)
         return fail(nullptr, "ee_threshold_sweep: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_threshold_sweep: no HIP device");
+    if (!have_device("ee_threshold_sweep")) return 1;
     if (V > 0) launch_threshold_sweep(conf, correct, E1, N, thr, V, acc, mean_exit, exit_hist, reinterpret_cast<hipStream_t>(stream));
     return launch_status(nullptr, "ee_threshold_sweep");
 }
@@ -194,8 +210,7 @@ int ee_threshold_sweep(const double* conf, const uint8_t* correct, int32_t E1, i
 int ee_msp_table(const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, double* conf, uint8_t* correct,
                  void* stream) {
     if (!logits || !conf || E1 < 1 || N < 1 || K < 1) return fail(nullptr, "ee_msp_table: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_msp_table: no HIP device");
+    if (!have_device("ee_msp_table")) return 1;
     launch_msp_table(logits, (const long long*)references, E1, N, K, conf, correct, reinterpret_cast<hipStream_t>(stream));
     return launch_status(nullptr, "ee_msp_table");
 }
@@ -203,8 +218,7 @@ int ee_msp_table(const double* logits, const int64_t* references, int32_t E1, in
 int ee_temperature_fit(const double* logits, const int64_t* labels, int32_t E1, int32_t N, int32_t K, int32_t max_iter,
                        double* temperature, double* nll, double* accuracy, double* avg_confidence, int32_t* iterations, void* stream) {
     if (!logits || !labels || !temperature || E1 < 1 || N < 1 || K < 2) return fail(nullptr, "ee_temperature_fit: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_temperature_fit: no HIP device");
+    if (!have_device("ee_temperature_fit")) return 1;
     launch_temperature_fit(logits, (const long long*)labels, E1, N, K, max_iter > 0 ? max_iter : 100, temperature, nll, accuracy,
                            avg_confidence, iterations, reinterpret_cast<hipStream_t>(stream));
     return launch_status(nullptr, "ee_temperature_fit");
@@ -215,8 +229,7 @@ int ee_preprocess_images(const uint8_t* images, const void* desc, int32_t B, int
                          size_t workspace_bytes, float* pixel_values, uint8_t* resized_u8, void* stream) {
     constexpr int KMAX = 64;
     if (!images || !desc || !workspace || !pixel_values || B < 1 || R < 1 || max_h < 1) return fail(nullptr, "ee_preprocess_images: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_preprocess_images: no HIP device");
+    if (!have_device("ee_preprocess_images")) return 1;
     // workspace layout: lut[256] f32 | bounds[B*2*R] int2 | kk[B*2*R*KMAX] int | tmp[B*max_h*R*3] u8
     const size_t o_lut = 0, o_b = 1024, o_k = o_b + sizeof(int2) * (size_t)B * 2 * R;
     const size_t o_t = (o_k + sizeof(int) * (size_t)B * 2 * R * KMAX + 255) & ~(size_t)255;
@@ -246,8 +259,7 @@ size_t ee_preprocess_workspace_bytes(int32_t B, int32_t R, int32_t max_h) {
 int ee_collate_pad(const int64_t* ids, const int64_t* boxes, const int64_t* offsets, int32_t B, int32_t T, int64_t pad_id,
                    int64_t* out_ids, int64_t* out_mask, int64_t* out_bbox, void* stream) {
     if (!ids || !boxes || !offsets || !out_ids || !out_mask || !out_bbox || B < 1 || T < 1) return fail(nullptr, "ee_collate_pad: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, "ee_collate_pad: no HIP device");
+    if (!have_device("ee_collate_pad")) return 1;
     launch_collate_pad((const long long*)ids, (const long long*)boxes, (const long long*)offsets, B, T, pad_id,
                        (long long*)out_ids, (long long*)out_mask, (long long*)out_bbox, reinterpret_cast<hipStream_t>(stream));
     return launch_status(nullptr, "ee_collate_pad");

@@ -1,459 +1,25 @@
-// Exit heads' output projection, the on-device exit decision (confidence test -> wavefront ballot -> prefix sum ->
-// stream compaction of the document list), row-map expansion, and the policy / threshold-sweep kernels.
+// The handle-free tools on dumped (E1, N, K) arrays: the exit policies as one scan kernel, the patience / threshold / rule sweeps, the
+// max-softmax table, the temperature fit, and result packing.  (The forward pass's own exit stage: exit_stage.hip.)
 //
 // What this replaces in the reference:
-//   * LayoutLMv3Exit.out_proj (EE/models/LayoutLMv3.py:92) / classifier.out_proj (HF:821) : head_out_kernel
-//   * max_confidence / entropy criteria (EE/models/EE_modules.py:149-160)                   : crit_f32 / crit_f64
-//   * Policy.max_confidence_global_thresholding_policy / accuracy_calibration_heuristic (EE/policy.py:28-45, 87-104):
-//     the nested Python loop "first exit whose float64 max-softmax is strictly above its threshold, else the last"
-//     becomes (a) exit_decide_kernel inside the forward pass — documents that satisfy the test are scattered to the
-//     outputs and removed, deeper layers run on the survivors only — and (b) policy_scan_kernel on a dumped
-//     (E+1,N,K) array, bit-identical in its integer outputs.
+//   * Policy.max_confidence_global_thresholding_policy / accuracy_calibration_heuristic (EE/policy.py:28-45, 87-104): the nested Python loop
+//     "first exit whose float64 max-softmax is strictly above its threshold, else the last" is exit_scan_kernel<SCAN_MSP, RULE_PLAIN>,
+//     bit-identical in its integer outputs.
 //   * thresh.opt0_2D / large_scale.check_2D_threshold (EE/thresh.py:184-215, EE/large_scale.py:42-84): threshold_sweep.
-// All of it is HBM/latency-bound integer + small-vector work; none of it is shaped into a GEMM.
 #include "mmee_kernels.h"
 
 namespace mmee {
 
-// ---------------------------------------------------------------------------------------------------------------
-// out[i][c] = <in[row(i)], W[c]> + b[c]; one wave per document
-// ---------------------------------------------------------------------------------------------------------------
-// LTE (ee_config.use_lte): the same wave also scores its document, u = sigmoid(w . x + b) on the CLS row the exit's head reads (a second row
-// source: the head of a 2-layer exit reads its dense layer's output here).  float64 throughout, in a fixed order: lane l adds its columns
-// 4l + 256k + j in the order k, j; the lane sums go through one butterfly.  Nothing depends on which documents share the launch.  The
-// LTE = false instantiation is the kernel as it was.
-template <int WAVES, bool LTE>
-__device__ __forceinline__ void head_out_body(const HeadOutArgs& a) {
-    const int n = *a.n_docs_ptr;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = blockIdx.x * WAVES + wave; i < n; i += gridDim.x * WAVES) {
-        const int row = a.gather ? a.gather[i] : i;
-        const float* x = a.in + (size_t)row * a.ld;
-        f32x4 xv[kMaxNV];
-#pragma unroll
-        for (int k = 0; k < kMaxNV; ++k) {
-            const int c = 4 * lane + 256 * k;
-            xv[k] = (c < a.H) ? *reinterpret_cast<const f32x4*>(x + c) : f32x4{0, 0, 0, 0};
-        }
-        for (int o = 0; o < a.Ko; ++o) {
-            const float* w = a.W + (size_t)o * a.H;
-            float s = 0.f;
-#pragma unroll
-            for (int k = 0; k < kMaxNV; ++k) {
-                const int c = 4 * lane + 256 * k;
-                if (c < a.H) {
-                    const f32x4 wv = *reinterpret_cast<const f32x4*>(w + c);
-                    s += (xv[k][0] * wv[0] + xv[k][1] * wv[1]) + (xv[k][2] * wv[2] + xv[k][3] * wv[3]);
-                }
-            }
-            s = wave_sum(s);
-            if (lane == 0) a.out[(size_t)i * a.Ko + o] = s + a.b[o];
-        }
-        if constexpr (LTE) {
-            const float* lx = a.lte_in + (size_t)(a.lte_gather ? a.lte_gather[i] : i) * a.lte_ld;
-            double t = 0.0;
-#pragma unroll
-            for (int k = 0; k < kMaxNV; ++k) {
-                const int c = 4 * lane + 256 * k;
-                if (c < a.H) {
-                    const f32x4 v = a.lte_split_inv != 0.f ? load_split4(lx, c, a.lte_split_inv) : *reinterpret_cast<const f32x4*>(lx + c);
-                    const f32x4 wv = *reinterpret_cast<const f32x4*>(a.lte_w + c);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) t += (double)v[j] * (double)wv[j];
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-            if (lane == 0) a.lte_out[i] = 1.0 / (1.0 + exp(-(t + (double)a.lte_b[0])));
-        }
-    }
+// float64 max-softmax of one row, as the policy computes it (scipy.special.softmax on the float64 store, EE/policy.py:30-32)
+__device__ __forceinline__ double max_softmax_f64(const double* z, int K) {
+    double m = z[0];
+    for (int k = 1; k < K; ++k) m = fmax(m, z[k]);
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) s += exp(z[k] - m);
+    return 1.0 / s;
 }
 
-__global__ __launch_bounds__(256) void head_out_kernel(HeadOutArgs a) { head_out_body<4, false>(a); }
-__global__ __launch_bounds__(256) void head_out_lte_kernel(HeadOutArgs a) { head_out_body<4, true>(a); }
-
-void launch_head_out(const HeadOutArgs& a, int max_docs, hipStream_t s) {
-    int grid = (max_docs + 3) / 4;
-    if (grid > 1024) grid = 1024;
-    if (grid < 1) grid = 1;
-    if (a.lte_out) hipLaunchKernelGGL(head_out_lte_kernel, dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(head_out_kernel, dim3(grid), dim3(256), 0, s, a);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// criteria
-// ---------------------------------------------------------------------------------------------------------------
-// float32, as the model computes exit_states[j][1] (EE/models/EE_modules.py:149-160)
-__device__ inline float crit_f32(const float* z, int K, int criterion) {
-    if (criterion == 0) {
-        float m = z[0];
-        for (int k = 1; k < K; ++k) m = fmaxf(m, z[k]);
-        float s = 0.f;
-        for (int k = 0; k < K; ++k) s += expf(z[k] - m);
-        return 1.0f / s;
-    }
-    float A = 0.f, B = 0.f;                       // entropy: log(sum e^x) - sum(x e^x)/sum(e^x), no max shift
-    for (int k = 0; k < K; ++k) {
-        const float e = expf(z[k]);
-        A += e;
-        B += z[k] * e;
-    }
-    return logf(A) - B / A;
-}
-
-// float64 on (double)logit / T, as the policy computes it (scipy.special.softmax on the float64 store, EE/policy.py:30-32)
-__device__ inline double crit_f64(const float* z, int K, double temp, int criterion) {
-    if (criterion == 0) {
-        double m = (double)z[0] / temp;
-        for (int k = 1; k < K; ++k) m = fmax(m, (double)z[k] / temp);
-        double s = 0.0;
-        for (int k = 0; k < K; ++k) s += exp((double)z[k] / temp - m);
-        return 1.0 / s;
-    }
-    double A = 0.0, B = 0.0;
-    for (int k = 0; k < K; ++k) {
-        const double x = (double)z[k] / temp;
-        const double e = exp(x);
-        A += e;
-        B += x * e;
-    }
-    return log(A) - B / A;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// The exit stage: one workgroup of 1024 threads walks the active documents in chunks of 1024.
-//   thread <-> document: criterion (f64), exit test, scatter of leavers to the output arrays;
-//   survivors: wave ballot -> popcount prefix -> cross-wave prefix in LDS -> running carry = new dense index,
-//   and the same scan over row counts = new dense row offset.
-// PATIENCE (PABEE, MMEE_CRIT_PATIENCE): the exit test is "the argmax of the scaled logits has stayed the same for t exits in a row"
-// instead of a threshold test.  The criterion written to the outputs is the max-softmax; the run state of document `orig` is
-// (p.prev[orig], p.run[orig]), indexed by the original slot so that compaction never moves it, and written unconditionally at
-// exit 0, which every document reaches (no reset launch).
-// LTE (ee_config.use_lte): the test is "the float64 score head_out_lte_kernel left in a.lte_score is strictly below the threshold"; the score
-// is what the outputs carry as the criterion.  Embedding exits have no score (a.lte_score null): 1.0, nobody leaves.
-// The max_confidence / entropy kernel is the DECIDE_THRESHOLD instantiation.
-// RULE (ee_set_exit_rule; THRESHOLD and LTE modes): the mode's test is the EVENT f_e and the rule decides on it.  MMEE_RULE_STREAK: the event
-// must have held at t_e exits in a row (s_e = f_e ? s_{e-1} + 1 : 0 in p.run[orig]).  MMEE_RULE_EITHER: the event, or PABEE's counter
-// c_e >= t_e ((p.prev[orig], p.run[orig]) exactly as under PATIENCE).  The same state arrays, written unconditionally at exit 0; t_e is the
-// launch's own patience (by value, or at p.t_ptr[0]: the host hands every exit its own entry).  RULE_PLAIN compiles to the kernels as they were.
-// ---------------------------------------------------------------------------------------------------------------
-enum { DECIDE_THRESHOLD = 0, DECIDE_PATIENCE = 1, DECIDE_LTE = 2 };
-enum { RULE_PLAIN = 0, RULE_STREAK = 1, RULE_EITHER = 2 };     // MMEE_RULE_*
-
-// PABEE's counter: argmax of the scaled logits as they are written out (two f32 logits can round to one scaled value; first maximum wins),
-// c_e = the argmax equals the one at the previous exit ? c_{e-1} + 1 : 0, state by original slot
-__device__ __forceinline__ int agreement_run(const float* z, int K, double temp, int exit_index, int orig, const PatienceArgs& p) {
-    float best = (float)((double)z[0] / temp);
-    int am = 0;
-    for (int k = 1; k < K; ++k) {
-        const float v = (float)((double)z[k] / temp);
-        if (v > best) { best = v; am = k; }
-    }
-    const int run = (exit_index > 0 && p.prev[orig] == am) ? p.run[orig] + 1 : 0;
-    p.prev[orig] = am;
-    p.run[orig] = run;
-    return run;
-}
-
-template <int MODE, int RULE = RULE_PLAIN>
-__device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const PatienceArgs& p) {
-    constexpr bool PATIENCE = MODE == DECIDE_PATIENCE;
-    static_assert(RULE == RULE_PLAIN || !PATIENCE, "PABEE has no threshold event to build a rule on");
-    __shared__ int s_cnt[16], s_rows[16];
-    __shared__ unsigned long long s_sq[16];
-    __shared__ int s_carry_docs, s_carry_rows;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = a.counts->n_docs;
-    const double thr = a.thr_ptr ? a.thr_ptr[a.exit_index] : a.thr;
-    const double temp = a.temp_ptr ? a.temp_ptr[a.exit_index] : a.temp;
-    int patience = 0;
-    if constexpr (PATIENCE || RULE != RULE_PLAIN) patience = p.t_ptr ? (int)p.t_ptr[0] : p.t;
-    if (tid == 0) { s_carry_docs = 0; s_carry_rows = 0; }
-    unsigned long long sq = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + tid;
-        const bool active = i < n;
-        bool keep = false;
-        int len = 0, orig = 0;
-        if (active) {
-            orig = a.doc_orig[i];
-            len = a.doc_off[i + 1] - a.doc_off[i];
-            const float* z = a.pol_logits + (size_t)i * a.K;
-            double crit;
-            bool leave;
-            if constexpr (PATIENCE) {
-                crit = crit_f64(z, a.K, temp, 0);
-                leave = agreement_run(z, a.K, temp, a.exit_index, orig, p) >= patience;
-            } else if constexpr (MODE == DECIDE_LTE) {
-                crit = a.lte_score ? a.lte_score[i] : 1.0;
-                leave = a.lte_score && crit < thr;                        // strict, EE/models/LayoutLMv3.py:262
-            } else {
-                crit = crit_f64(z, a.K, temp, a.criterion);
-                leave = a.criterion == 0 ? (crit > thr) : (crit < thr);   // strict, EE/policy.py:33
-            }
-            if constexpr (RULE == RULE_STREAK) {
-                const int streak = leave ? (a.exit_index > 0 ? p.run[orig] : 0) + 1 : 0;
-                p.run[orig] = streak;
-                leave = streak >= patience;
-            } else if constexpr (RULE == RULE_EITHER) {
-                const bool agreed = agreement_run(z, a.K, temp, a.exit_index, orig, p) >= patience;
-                leave = leave || agreed;
-            }
-            if (a.no_exit) leave = false;
-            if (a.is_final) leave = true;
-            if (a.out_all_logits) {
-                float* o = a.out_all_logits + ((size_t)a.exit_index * a.B + orig) * a.K;
-                for (int k = 0; k < a.K; ++k) o[k] = (float)((double)z[k] / temp);
-            }
-            if (a.out_all_crit) a.out_all_crit[(size_t)a.exit_index * a.B + orig] = (float)crit;
-            if (a.head_logits && a.out_head_logits) {
-                const float* hz = a.head_logits + (size_t)i * a.Kh;
-                float* o = a.out_head_logits + ((size_t)a.exit_index * a.B + orig) * a.Kh;
-                for (int k = 0; k < a.Kh; ++k) o[k] = hz[k];
-            }
-            if (a.head_logits && a.out_head_crit)
-                a.out_head_crit[(size_t)a.exit_index * a.B + orig] =
-                    crit_f32(a.head_logits + (size_t)i * a.Kh, a.Kh, PATIENCE ? 0 : a.criterion);
-            if (leave) {
-                if (a.out_logits)
-                    for (int k = 0; k < a.K; ++k) a.out_logits[(size_t)orig * a.K + k] = (float)((double)z[k] / temp);
-                a.out_exit[orig] = a.exit_index;
-                if (a.out_conf) a.out_conf[orig] = (float)crit;
-            }
-            keep = !leave;
-        }
-        // ---- wavefront ballot + prefix sums ------------------------------------------------------------------
-        const unsigned long long ballot = __ballot(keep);
-        const int before = __popcll(ballot & ((1ull << lane) - 1ull));       // survivors in lower lanes
-        const int klen = keep ? len : 0;
-        const int rows_incl = wave_incl_scan(klen, lane);
-        if (lane == 63) { s_cnt[wave] = __popcll(ballot); s_rows[wave] = rows_incl; }
-        if (keep) sq += (unsigned long long)len * (unsigned long long)len;
-        __syncthreads();
-        int wdocs = 0, wrows = 0, tdocs = 0, trows = 0;
-        for (int w = 0; w < 16; ++w) {
-            if (w < wave) { wdocs += s_cnt[w]; wrows += s_rows[w]; }
-            tdocs += s_cnt[w];
-            trows += s_rows[w];
-        }
-        const int cd = s_carry_docs, cr = s_carry_rows;
-        if (keep) {
-            const int k = cd + wdocs + before;
-            a.n_doc_orig[k] = orig;
-            a.n_doc_off[k] = cr + wrows + rows_incl - len;
-            a.n_x_src[k] = a.x_phys[i];
-            a.n_meta_src[k] = a.doc_off[i];
-        }
-        __syncthreads();
-        if (tid == 0) { s_carry_docs = cd + tdocs; s_carry_rows = cr + trows; }
-        __syncthreads();
-    }
-    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
-    if (lane == 0) s_sq[wave] = sq;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long t = 0;
-        for (int w = 0; w < 16; ++w) t += s_sq[w];
-        a.n_doc_off[s_carry_docs] = s_carry_rows;
-        a.n_counts->n_docs = s_carry_docs;
-        a.n_counts->n_rows = s_carry_rows;
-        a.n_counts->sum_len_sq = t;
-    }
-}
-
-__global__ __launch_bounds__(1024) void exit_decide_kernel(DecideArgs a) { exit_decide_body<DECIDE_THRESHOLD>(a, PatienceArgs{}); }
-__global__ __launch_bounds__(1024) void exit_decide_patience_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<DECIDE_PATIENCE>(a, p); }
-__global__ __launch_bounds__(1024) void exit_decide_lte_kernel(DecideArgs a) { exit_decide_body<DECIDE_LTE>(a, PatienceArgs{}); }
-
-void launch_decide(const DecideArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(exit_decide_kernel, dim3(1), dim3(1024), 0, s, a);
-}
-void launch_decide_patience(const DecideArgs& a, const PatienceArgs& p, hipStream_t s) {
-    hipLaunchKernelGGL(exit_decide_patience_kernel, dim3(1), dim3(1024), 0, s, a, p);
-}
-void launch_decide_lte(const DecideArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(exit_decide_lte_kernel, dim3(1), dim3(1024), 0, s, a);
-}
-
-__global__ __launch_bounds__(1024) void exit_decide_streak_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<DECIDE_THRESHOLD, RULE_STREAK>(a, p); }
-__global__ __launch_bounds__(1024) void exit_decide_either_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<DECIDE_THRESHOLD, RULE_EITHER>(a, p); }
-__global__ __launch_bounds__(1024) void exit_decide_lte_streak_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<DECIDE_LTE, RULE_STREAK>(a, p); }
-__global__ __launch_bounds__(1024) void exit_decide_lte_either_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<DECIDE_LTE, RULE_EITHER>(a, p); }
-
-// rule: RULE_STREAK or RULE_EITHER; lte: the event is the LTE test (a.lte_score) instead of the criterion test
-void launch_decide_rule(const DecideArgs& a, const PatienceArgs& p, int rule, bool lte, hipStream_t s) {
-    auto k = rule == RULE_STREAK ? (lte ? exit_decide_lte_streak_kernel : exit_decide_streak_kernel)
-                                 : (lte ? exit_decide_lte_either_kernel : exit_decide_either_kernel);
-    hipLaunchKernelGGL(k, dim3(1), dim3(1024), 0, s, a, p);
-}
-
-// Round 6: the head's output projection and the decision were built as ONE launch (every workgroup writes its documents' logits, fences,
-// takes a ticket; the last arrival runs the scan: nobody waits, same bits, 91 GPU tests green) and measured on config 3 (2 x 512 documents, 48 exits per step):
-// 52.7 us per exit against 31 + 16 us for the two launches -- the fences and the serial scan behind the last arrival cost what the launch saved.  Removed.
-
-// new dense row r of surviving document k  <-  physical X row n_x_src[k] + t, metadata row n_meta_src[k] + t
-__global__ __launch_bounds__(256) void compact_rows_kernel(const StageCounts* n_counts, const int* __restrict__ n_doc_off,
-                                                           const int* __restrict__ n_x_src, const int* __restrict__ n_meta_src,
-                                                           const RowMeta* __restrict__ meta_old, RowMeta* __restrict__ meta_new,
-                                                           int* __restrict__ row_src) {
-    const int n = n_counts->n_docs;
-    for (int k = blockIdx.x; k < n; k += gridDim.x) {
-        const int off = n_doc_off[k], len = n_doc_off[k + 1] - off;
-        const int xs = n_x_src[k], ms = n_meta_src[k];
-        for (int t = threadIdx.x; t < len; t += 256) {
-            row_src[off + t] = xs + t;
-            meta_new[off + t] = meta_old[ms + t];
-        }
-    }
-}
-
-void launch_compact_rows(const StageCounts* n_counts, const int* n_doc_off, const int* n_x_src, const int* n_meta_src,
-                         const RowMeta* meta_old, RowMeta* meta_new, int* row_src, int max_docs, int num_cus, hipStream_t s) {
-    int grid = max_docs < num_cus * 8 ? max_docs : num_cus * 8;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(compact_rows_kernel, dim3(grid), dim3(256), 0, s, n_counts, n_doc_off, n_x_src, n_meta_src,
-                       meta_old, meta_new, row_src);
-}
-
-// (logits f32 (n,K), exit_layer i32 (n), confidence f32 (n)) <-> the row of the ONE all-gather of the north star: K + 2 int32 words per document
-// (the floats travel as their bit patterns: integer copies and collectives never flush, canonicalise or round them)
-__global__ __launch_bounds__(256) void pack_results_kernel(const float* __restrict__ logits, const int* __restrict__ exit_layer,
-                                                           const float* __restrict__ conf, int n, int K, int* __restrict__ rows) {
-    const long total = (long)n * (K + 2);
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int d = (int)(i / (K + 2)), c = (int)(i - (long)d * (K + 2));
-        rows[i] = c < K ? __float_as_int(logits[(size_t)d * K + c]) : c == K ? exit_layer[d] : __float_as_int(conf[d]);
-    }
-}
-__global__ __launch_bounds__(256) void unpack_results_kernel(const int* __restrict__ rows, int n, int K, float* __restrict__ logits,
-                                                             int* __restrict__ exit_layer, float* __restrict__ conf) {
-    const long total = (long)n * (K + 2);
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int d = (int)(i / (K + 2)), c = (int)(i - (long)d * (K + 2));
-        const int v = rows[i];
-        if (c < K) { if (logits) logits[(size_t)d * K + c] = __int_as_float(v); }
-        else if (c == K) { if (exit_layer) exit_layer[d] = v; }
-        else if (conf) conf[d] = __int_as_float(v);
-    }
-}
-void launch_pack_results(const float* logits, const int* exit_layer, const float* conf, int n, int K, int* rows, hipStream_t s) {
-    long total = (long)n * (K + 2);
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(pack_results_kernel, dim3(grid), dim3(256), 0, s, logits, exit_layer, conf, n, K, rows);
-}
-void launch_unpack_results(const int* rows, int n, int K, float* logits, int* exit_layer, float* conf, hipStream_t s) {
-    long total = (long)n * (K + 2);
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(unpack_results_kernel, dim3(grid), dim3(256), 0, s, rows, n, K, logits, exit_layer, conf);
-}
-
-// out[orig][:] = X[x_phys[i]][:]   (CLS rows, parity/debug output)
-// CLS row of every active document -> out[doc_orig ? doc_orig[i] : i].  split_inv != 0: X holds split-f16 rows (1 / scale = split_inv)
-__global__ __launch_bounds__(256) void gather_cls_kernel(const float* __restrict__ X, int H, const int* __restrict__ x_phys,
-                                                         const int* __restrict__ doc_orig, const int* __restrict__ n_docs_ptr,
-                                                         float* __restrict__ out, float split_inv) {
-    const int n = *n_docs_ptr;
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        const float* src = X + (size_t)x_phys[i] * H;
-        float* dst = out + (size_t)(doc_orig ? doc_orig[i] : i) * H;
-        if (split_inv != 0.f) {
-            for (int c = 4 * threadIdx.x; c < H; c += 1024) *reinterpret_cast<f32x4*>(dst + c) = load_split4(src, c, split_inv);
-        } else {
-            for (int c = threadIdx.x; c < H; c += 256) dst[c] = src[c];
-        }
-    }
-}
-
-// Hidden states in the reference's padded layout (ee_set_hidden_states_out): position p of document d is text token p (packed row
-// text_dst[d * T + p], < 0 when the ragged layout dropped it: zeros) or visual row p - T (packed behind the document's ntext[d] text rows).
-__global__ __launch_bounds__(256) void rows_to_padded_kernel(const float* __restrict__ X, float split_inv, int H, int B, int T, int Pv,
-                                                             const int* __restrict__ text_dst, const int* __restrict__ ntext,
-                                                             const int* __restrict__ doc_off, float* __restrict__ out) {
-    const int S = T + Pv;
-    for (long r = blockIdx.x; r < (long)B * S; r += gridDim.x) {
-        const int d = (int)(r / S), p = (int)(r - (long)d * S);
-        int row;
-        if (p < T) {
-            const int t = text_dst[(size_t)d * T + p];
-            row = t < 0 ? -1 : doc_off[d] + t;
-        } else {
-            row = doc_off[d] + (text_dst ? ntext[d] : 0) + (p - T);
-        }
-        float* dst = out + (size_t)r * H;
-        if (row < 0) {
-            for (int c = threadIdx.x; c < H; c += 256) dst[c] = 0.f;
-        } else if (split_inv != 0.f) {
-            const float* src = X + (size_t)row * H;
-            for (int c = 4 * threadIdx.x; c < H; c += 1024) *reinterpret_cast<f32x4*>(dst + c) = load_split4(src, c, split_inv);
-        } else {
-            const float* src = X + (size_t)row * H;
-            for (int c = threadIdx.x; c < H; c += 256) dst[c] = src[c];
-        }
-    }
-}
-void launch_rows_to_padded(const float* X, float split_inv, int H, int B, int T, int Pv, const int* text_dst, const int* ntext, const int* doc_off,
-                           float* out, hipStream_t s) {
-    long rows = (long)B * (T + Pv);
-    int grid = rows < 4096 ? (int)rows : 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(rows_to_padded_kernel, dim3(grid), dim3(256), 0, s, X, split_inv, H, B, T, Pv, text_dst, ntext, doc_off, out);
-}
-
-void launch_gather_cls(const float* X, int H, const int* x_phys, const int* doc_orig, const int* n_docs_ptr, float* out,
-                       int max_docs, hipStream_t s, float split_inv) {
-    int grid = max_docs < 2048 ? max_docs : 2048;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(gather_cls_kernel, dim3(grid), dim3(256), 0, s, X, H, x_phys, doc_orig, n_docs_ptr, out, split_inv);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Policy on a dumped (E1, N, K) float64 array: thread per document, scan exits in order.
-// ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void policy_scan_kernel(const double* __restrict__ logits, int E1, int N, int K,
-                                                          const double* __restrict__ thr, int* __restrict__ exits,
-                                                          double* __restrict__ pred, double* __restrict__ conf_out,
-                                                          int* __restrict__ counts) {
-    for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += gridDim.x * 256) {
-        int chosen = E1 - 1;
-        double cchosen = 0.0;
-        for (int e = 0; e < E1; ++e) {
-            const double* z = logits + ((size_t)e * N + n) * K;
-            double m = z[0];
-            for (int k = 1; k < K; ++k) m = fmax(m, z[k]);
-            double s = 0.0;
-            for (int k = 0; k < K; ++k) s += exp(z[k] - m);
-            const double c = 1.0 / s;
-            cchosen = c;
-            if (c > thr[e]) { chosen = e; break; }
-        }
-        exits[n] = chosen;
-        if (conf_out) conf_out[n] = cchosen;
-        if (pred) {
-            const double* z = logits + ((size_t)chosen * N + n) * K;
-            for (int k = 0; k < K; ++k) pred[(size_t)n * K + k] = z[k];
-        }
-        if (counts) atomicAdd(&counts[chosen], 1);
-    }
-}
-
-void launch_policy_scan(const double* logits, int E1, int N, int K, const double* thr_dev, int* exits, double* pred,
-                        double* conf, int* counts, hipStream_t s) {
-    int grid = (N + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(policy_scan_kernel, dim3(grid), dim3(256), 0, s, logits, E1, N, K, thr_dev, exits, pred, conf, counts);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Patience (PABEE) on a dumped (E1, N, K) float64 array, thread per document, in the shape of policy_scan_kernel:
-//   p_e = argmax_k logits[e][n][k] (first maximum), c_0 = 0, c_e = p_e == p_{e-1} ? c_{e-1} + 1 : 0,
-//   exit = first e with c_e >= t, else E1 - 1; confidence = float64 max-softmax of the row at that exit.
-// ---------------------------------------------------------------------------------------------------------------
+// argmax of one float64 row, first maximum (as numpy)
 __device__ __forceinline__ int argmax_f64(const double* z, int K) {
     double m = z[0];
     int am = 0;
@@ -462,112 +28,64 @@ __device__ __forceinline__ int argmax_f64(const double* z, int K) {
     return am;
 }
 
-__global__ __launch_bounds__(256) void patience_scan_kernel(const double* __restrict__ logits, int E1, int N, int K, int t,
-                                                            int* __restrict__ exits, double* __restrict__ pred,
-                                                            double* __restrict__ conf_out, int* __restrict__ counts) {
-    for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += gridDim.x * 256) {
-        int chosen = E1 - 1, prev = -1, run = 0;
-        for (int e = 0; e < E1; ++e) {
-            const int am = argmax_f64(logits + ((size_t)e * N + n) * K, K);
-            run = (e > 0 && am == prev) ? run + 1 : 0;
-            prev = am;
-            if (run >= t) { chosen = e; break; }
-        }
-        const double* z = logits + ((size_t)chosen * N + n) * K;
-        exits[n] = chosen;
-        if (conf_out) {
-            double m = z[0];
-            for (int k = 1; k < K; ++k) m = fmax(m, z[k]);
-            double s = 0.0;
-            for (int k = 0; k < K; ++k) s += exp(z[k] - m);
-            conf_out[n] = 1.0 / s;
-        }
-        if (pred)
-            for (int k = 0; k < K; ++k) pred[(size_t)n * K + k] = z[k];
-        if (counts) atomicAdd(&counts[chosen], 1);
-    }
-}
-
-void launch_patience_scan(const double* logits, int E1, int N, int K, int t, int* exits, double* pred, double* conf, int* counts,
-                          hipStream_t s) {
-    int grid = (N + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(patience_scan_kernel, dim3(grid), dim3(256), 0, s, logits, E1, N, K, t, exits, pred, conf, counts);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// LTE on dumped arrays (ee_lte_scan), thread per document, in the shape of policy_scan_kernel: the first e < E1 - 1 whose score is
-// strictly below its threshold, else E1 - 1.
+// The exit decision on dumped arrays (ee_policy_scan, ee_patience_scan, ee_lte_scan, ee_rule_scan): thread per document, exits in order,
+// the first e < E1 - 1 that qualifies, else the final exit E1 - 1, whose own test and patience are never looked at.
+//   event      f_e = sign * crit_e > sign * thr[e]   (sign = +1: confidence, strict '>'; -1: entropy / LTE score, strict '<'; negation is exact)
+//              crit_e: SCAN_MSP the float64 max-softmax of the row, SCAN_TABLE crit[e][n], SCAN_NONE no event
+//   agreement  c_e (PABEE): p_e = argmax_k logits[e][n][k] (first maximum), c_0 = 0, c_e = p_e == p_{e-1} ? c_{e-1} + 1 : 0
+//   RULE_PLAIN: f_e;   RULE_STREAK: s_e = f_e ? s_{e-1} + 1 : 0, s_e >= pat[e];   RULE_EITHER: f_e or c_e >= pat[e];   RULE_AGREE: c_e >= pat[e]
+// confidence = SCAN_TABLE: crit at the chosen exit; else the float64 max-softmax of the chosen row.  The logits are read only where the
+// instantiation needs a row (SCAN_MSP, the agreement, pred, SCAN_NONE's confidence): they may be null otherwise.
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void lte_scan_kernel(const double* __restrict__ scores, const double* __restrict__ logits, int E1, int N,
-                                                       int K, const double* __restrict__ thr, int* __restrict__ exits,
-                                                       double* __restrict__ pred, int* __restrict__ counts) {
-    for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += gridDim.x * 256) {
-        int chosen = E1 - 1;
-        for (int e = 0; e < E1 - 1; ++e)
-            if (scores[(size_t)e * N + n] < thr[e]) { chosen = e; break; }
-        exits[n] = chosen;
-        if (pred) {
-            const double* z = logits + ((size_t)chosen * N + n) * K;
-            for (int k = 0; k < K; ++k) pred[(size_t)n * K + k] = z[k];
-        }
-        if (counts) atomicAdd(&counts[chosen], 1);
-    }
-}
-
-void launch_lte_scan(const double* scores, const double* logits, int E1, int N, int K, const double* thr_dev, int* exits, double* pred,
-                     int* counts, hipStream_t s) {
-    int grid = (N + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(lte_scan_kernel, dim3(grid), dim3(256), 0, s, scores, logits, E1, N, K, thr_dev, exits, pred, counts);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// The two combined rules on dumped arrays (ee_rule_scan), thread per document, in the shape of policy_scan_kernel / patience_scan_kernel.
-//   event      f_e = sign * crit[e][n] > sign * thr[e]   (sign = +1: confidence, strict '>'; -1: entropy / LTE score, strict '<'; negation is exact)
-//   agreement  c_e as patience_scan_kernel (argmax of the float64 row, first maximum)
-//   RULE_STREAK: s_e = f_e ? s_{e-1} + 1 : 0, leave at the first e with s_e >= pat[e];   RULE_EITHER: the first e with f_e or c_e >= pat[e]
-// else the final exit E1 - 1, whose own test and patience are never looked at.  confidence = crit at the chosen exit.
-// ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rule_scan_kernel(const double* __restrict__ crit, double sign, const double* __restrict__ logits, int E1,
-                                                        int N, int K, const double* __restrict__ thr, const int* __restrict__ pat, int rule,
-                                                        int* __restrict__ exits, double* __restrict__ pred, double* __restrict__ conf_out,
-                                                        int* __restrict__ counts) {
-    for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += gridDim.x * 256) {
-        int chosen = E1 - 1, prev = -1, run = 0, streak = 0;
-        for (int e = 0; e < E1 - 1; ++e) {
-            const bool f = sign * crit[(size_t)e * N + n] > sign * thr[e];
-            bool leave;
-            if (rule == RULE_STREAK) {
-                streak = f ? streak + 1 : 0;
-                leave = streak >= pat[e];
-            } else {
-                const int am = argmax_f64(logits + ((size_t)e * N + n) * K, K);
-                run = (e > 0 && am == prev) ? run + 1 : 0;
-                prev = am;
-                leave = f || run >= pat[e];
+template <int EVENT, int RULE>
+__global__ __launch_bounds__(256) void exit_scan_kernel(ScanArgs a) {
+    static_assert((EVENT == SCAN_NONE) == (RULE == RULE_AGREE), "without an event only the agreement can decide, and RULE_AGREE looks at no event");
+    for (int n = blockIdx.x * 256 + threadIdx.x; n < a.N; n += gridDim.x * 256) {
+        const auto row = [&](int e) { return a.logits + ((size_t)e * a.N + n) * a.K; };
+        int chosen = a.E1 - 1, prev = -1, run = 0, streak = 0;
+        double crit = 0.0;
+        for (int e = 0; e < a.E1 - 1; ++e) {
+            bool leave = false;
+            if constexpr (EVENT != SCAN_NONE) {
+                crit = EVENT == SCAN_MSP ? max_softmax_f64(row(e), a.K) : a.crit[(size_t)e * a.N + n];
+                leave = a.sign * crit > a.sign * a.thr[e];
+            }
+            if constexpr (RULE != RULE_PLAIN) {
+                const int pat = a.pat ? a.pat[e] : a.pat_all;
+                if constexpr (RULE == RULE_STREAK) {
+                    streak = leave ? streak + 1 : 0;
+                    leave = streak >= pat;
+                } else {
+                    const int am = argmax_f64(row(e), a.K);
+                    run = (e > 0 && am == prev) ? run + 1 : 0;
+                    prev = am;
+                    leave = leave || run >= pat;
+                }
             }
             if (leave) { chosen = e; break; }
         }
-        exits[n] = chosen;
-        if (conf_out) conf_out[n] = crit[(size_t)chosen * N + n];
-        if (pred) {
-            const double* z = logits + ((size_t)chosen * N + n) * K;
-            for (int k = 0; k < K; ++k) pred[(size_t)n * K + k] = z[k];
+        a.exits[n] = chosen;
+        if (a.conf) {
+            if constexpr (EVENT == SCAN_TABLE) a.conf[n] = a.crit[(size_t)chosen * a.N + n];
+            else a.conf[n] = (EVENT == SCAN_MSP && chosen < a.E1 - 1) ? crit : max_softmax_f64(row(chosen), a.K);
         }
-        if (counts) atomicAdd(&counts[chosen], 1);
+        if (a.pred) {
+            const double* z = row(chosen);
+            for (int k = 0; k < a.K; ++k) a.pred[(size_t)n * a.K + k] = z[k];
+        }
+        if (a.counts) atomicAdd(&a.counts[chosen], 1);
     }
 }
 
-void launch_rule_scan(const double* crit, double sign, const double* logits, int E1, int N, int K, const double* thr_dev, const int* pat_dev,
-                      int rule, int* exits, double* pred, double* conf, int* counts, hipStream_t s) {
-    int grid = (N + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(rule_scan_kernel, dim3(grid), dim3(256), 0, s, crit, sign, logits, E1, N, K, thr_dev, pat_dev, rule, exits, pred, conf,
-                       counts);
+// the five (event, rule) pairs the entry points ask for
+void launch_exit_scan(const ScanArgs& a, int event, int rule, hipStream_t s) {
+    void (*k)(ScanArgs) = event == SCAN_MSP    ? exit_scan_kernel<SCAN_MSP, RULE_PLAIN>
+                          : event == SCAN_NONE ? exit_scan_kernel<SCAN_NONE, RULE_AGREE>
+                          : rule == RULE_PLAIN ? exit_scan_kernel<SCAN_TABLE, RULE_PLAIN>
+                          : rule == RULE_STREAK ? exit_scan_kernel<SCAN_TABLE, RULE_STREAK>
+                                                : exit_scan_kernel<SCAN_TABLE, RULE_EITHER>;
+    hipLaunchKernelGGL(k, dim3(grid_1d(a.N, 256, 4096)), dim3(256), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -652,9 +170,7 @@ bool launch_patience_sweep(const double* logits, const long long* refs, int E1, 
     if (hist) (void)hipMemsetAsync(hist, 0, sizeof(int) * (size_t)V * E1, s);
     hipLaunchKernelGGL(patience_sweep_kernel, dim3((N + kPatBlock - 1) / kPatBlock), dim3(kPatBlock), 0, s, logits, refs, E1, N, K, pats, V,
                        sums, hist);
-    int grid = (V + 255) / 256;
-    if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(patience_sweep_finish_kernel, dim3(grid), dim3(256), 0, s, sums, V, N, acc, mean_exit);
+    hipLaunchKernelGGL(patience_sweep_finish_kernel, dim3(grid_1d(V, 256, 1024)), dim3(256), 0, s, sums, V, N, acc, mean_exit);
     (void)hipFreeAsync(sums, s);
     return true;
 }
@@ -817,38 +333,49 @@ __global__ __launch_bounds__(256, 2) void sweep_main_kernel(const unsigned* __re
     }
 }
 
+// The ranking step of the two ranked sweeps: rec (zeroed, then sweep_rank_kernel), sorted, and T = the thresholds' ranks (sweep_thr_kernel).
+// ok == false: an allocation failed and nothing was launched.  The workspace is freed in stream order when the object goes out of scope.
+struct SweepRanks {
+    unsigned *rec = nullptr, *T = nullptr;
+    double* sorted = nullptr;
+    hipStream_t s;
+    bool ok;
+    SweepRanks(const double* conf, const unsigned char* correct, int E1, int E1P, int N, const double* thr, int V, int strict, hipStream_t stream)
+        : s(stream) {
+        ok = hipMallocAsync((void**)&rec, (size_t)N * E1P * 4, s) == hipSuccess && hipMallocAsync((void**)&T, (size_t)V * E1 * 4, s) == hipSuccess &&
+             hipMallocAsync((void**)&sorted, (size_t)E1 * N * 8, s) == hipSuccess;
+        if (!ok) { (void)hipGetLastError(); return; }
+        (void)hipMemsetAsync(rec, 0, (size_t)N * E1P * 4, s);
+        hipLaunchKernelGGL(sweep_rank_kernel, dim3((N + 255) / 256, E1), dim3(256), 0, s, conf, correct, E1, E1P, N, rec, sorted);
+        const long long VE = (long long)V * E1;
+        hipLaunchKernelGGL(sweep_thr_kernel, dim3(grid_1d(VE, 256, 65536)), dim3(256), 0, s, sorted, thr, E1, N, VE, T, strict);
+    }
+    SweepRanks(const SweepRanks&) = delete;
+    ~SweepRanks() {
+        if (rec) (void)hipFreeAsync(rec, s);
+        if (T) (void)hipFreeAsync(T, s);
+        if (sorted) (void)hipFreeAsync(sorted, s);
+    }
+};
+
 void launch_threshold_sweep(const double* conf, const unsigned char* correct, int E1, int N, const double* thr, int V,
                             double* acc, double* mean_exit, int* hist, hipStream_t s) {
     // ranks: the integer sweep (no histogram, N < 2^24, enough vectors to pay for the O(N^2) ranking pass)
     const bool ranked = !hist && N < (1 << 24) && E1 <= 64 && (long long)V * 8 >= (long long)N;
     if (ranked) {
         const int E1P = (E1 + 3) & ~3;
-        unsigned *rec = nullptr, *T = nullptr;
-        double* sorted = nullptr;
-        if (hipMallocAsync((void**)&rec, (size_t)N * E1P * 4, s) == hipSuccess && hipMallocAsync((void**)&T, (size_t)V * E1 * 4, s) == hipSuccess &&
-            hipMallocAsync((void**)&sorted, (size_t)E1 * N * 8, s) == hipSuccess) {
-            (void)hipMemsetAsync(rec, 0, (size_t)N * E1P * 4, s);
-            hipLaunchKernelGGL(sweep_rank_kernel, dim3((N + 255) / 256, E1), dim3(256), 0, s, conf, correct, E1, E1P, N, rec, sorted);
-            const long long VE = (long long)V * E1;
-            int g2 = (int)((VE + 255) / 256 < 65536 ? (VE + 255) / 256 : 65536);
-            hipLaunchKernelGGL(sweep_thr_kernel, dim3(g2), dim3(256), 0, s, sorted, thr, E1, N, VE, T, 0);
+        const SweepRanks r(conf, correct, E1, E1P, N, thr, V, 0, s);
+        if (r.ok) {                                                  // else: the direct kernel needs no workspace
             const int grid = (V + 255) / 256;
             const size_t lds = 64 * 1024;
             (void)ensure_dynamic_lds<&sweep_main_kernel<7>>("sweep_main_kernel", (int)lds);
             (void)ensure_dynamic_lds<&sweep_main_kernel<0>>("sweep_main_kernel", (int)lds);
-            if (E1 == 7) hipLaunchKernelGGL((sweep_main_kernel<7>), dim3(grid), dim3(256), lds, s, rec, T, E1, E1P, N, V, acc, mean_exit);
-            else hipLaunchKernelGGL((sweep_main_kernel<0>), dim3(grid), dim3(256), lds, s, rec, T, E1, E1P, N, V, acc, mean_exit);
-            (void)hipFreeAsync(rec, s); (void)hipFreeAsync(T, s); (void)hipFreeAsync(sorted, s);
+            if (E1 == 7) hipLaunchKernelGGL((sweep_main_kernel<7>), dim3(grid), dim3(256), lds, s, r.rec, r.T, E1, E1P, N, V, acc, mean_exit);
+            else hipLaunchKernelGGL((sweep_main_kernel<0>), dim3(grid), dim3(256), lds, s, r.rec, r.T, E1, E1P, N, V, acc, mean_exit);
             return;
         }
-        (void)hipGetLastError();                                     // allocation failed: the direct kernel needs no workspace
-        if (rec) (void)hipFreeAsync(rec, s);
-        if (T) (void)hipFreeAsync(T, s);
-        if (sorted) (void)hipFreeAsync(sorted, s);
     }
-    int grid = V < 8192 ? V : 8192;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(threshold_sweep_kernel, dim3(grid), dim3(256), 0, s, conf, correct, E1, N, thr, V, acc, mean_exit, hist);
+    hipLaunchKernelGGL(threshold_sweep_kernel, dim3(grid_1d(V, 1, 8192)), dim3(256), 0, s, conf, correct, E1, N, thr, V, acc, mean_exit, hist);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1040,49 +567,37 @@ bool launch_rule_sweep(const double* conf, const double* logits, const long long
         if (correct) (void)hipFreeAsync(correct, s);
         return false;
     }
-    int g0 = (N + 255) / 256;
-    if (g0 > 4096) g0 = 4096;
+    const int g0 = grid_1d(N, 256, 4096);
     hipLaunchKernelGGL(rule_table_kernel, dim3(g0), dim3(256), 0, s, logits, refs, E1, N, K, correct, agree);
     // the ranked kernel: the reference's shape, no histogram, enough vectors to pay for the O(N^2) ranking pass (as launch_threshold_sweep)
     bool done = false;
     if (!hist && E1 == 7 && P <= kRuleFastP && N < (1 << 24) && (long long)V * 8 >= (long long)N) {
         constexpr int E1P = 8;
-        unsigned *rec = nullptr, *aux = nullptr, *T = nullptr;
-        double* sorted = nullptr;
-        if (hipMallocAsync((void**)&rec, (size_t)N * E1P * 4, s) == hipSuccess && hipMallocAsync((void**)&aux, (size_t)N * 16, s) == hipSuccess &&
-            hipMallocAsync((void**)&T, (size_t)V * E1 * 4, s) == hipSuccess && hipMallocAsync((void**)&sorted, (size_t)E1 * N * 8, s) == hipSuccess) {
+        unsigned* aux = nullptr;
+        const SweepRanks r(conf, correct, E1, E1P, N, thr, V, 1, s);
+        if (r.ok && hipMallocAsync((void**)&aux, (size_t)N * 16, s) == hipSuccess) {
             RulePats pt{};
             pt.P = P;
             for (int j = 0; j < kRuleFastP; ++j) pt.t[j] = j < P ? pats_host[j] : 1;
-            (void)hipMemsetAsync(rec, 0, (size_t)N * E1P * 4, s);
-            hipLaunchKernelGGL(sweep_rank_kernel, dim3((N + 255) / 256, E1), dim3(256), 0, s, conf, correct, E1, E1P, N, rec, sorted);
             hipLaunchKernelGGL(rule_aux_kernel, dim3(g0), dim3(256), 0, s, correct, agree, E1, N, pt, aux);
-            const long long VE = (long long)V * E1;
-            const int g2 = (int)((VE + 255) / 256 < 65536 ? (VE + 255) / 256 : 65536);
-            hipLaunchKernelGGL(sweep_thr_kernel, dim3(g2), dim3(256), 0, s, sorted, thr, E1, N, VE, T, 1);
             const size_t lds = 64 * 1024;
             const bool ok = ensure_dynamic_lds<&rule_main_kernel<7, RULE_STREAK>>("rule_main_kernel", (int)lds) == hipSuccess &&
                             ensure_dynamic_lds<&rule_main_kernel<7, RULE_EITHER>>("rule_main_kernel", (int)lds) == hipSuccess;
             if (ok) {
                 const int grid = (V + 255) / 256;
                 if (rule == RULE_STREAK)
-                    hipLaunchKernelGGL((rule_main_kernel<7, RULE_STREAK>), dim3(grid), dim3(256), lds, s, rec, aux, T, N, V, pt, acc, mean_exit);
+                    hipLaunchKernelGGL((rule_main_kernel<7, RULE_STREAK>), dim3(grid), dim3(256), lds, s, r.rec, aux, r.T, N, V, pt, acc, mean_exit);
                 else
-                    hipLaunchKernelGGL((rule_main_kernel<7, RULE_EITHER>), dim3(grid), dim3(256), lds, s, rec, aux, T, N, V, pt, acc, mean_exit);
+                    hipLaunchKernelGGL((rule_main_kernel<7, RULE_EITHER>), dim3(grid), dim3(256), lds, s, r.rec, aux, r.T, N, V, pt, acc, mean_exit);
                 done = true;
             }
         } else {
             (void)hipGetLastError();                                 // allocation failed: the direct kernel needs no workspace
         }
-        if (rec) (void)hipFreeAsync(rec, s);
         if (aux) (void)hipFreeAsync(aux, s);
-        if (T) (void)hipFreeAsync(T, s);
-        if (sorted) (void)hipFreeAsync(sorted, s);
     }
     if (!done) {
-        int grid = V < 8192 ? V : 8192;
-        if (grid < 1) grid = 1;
-        hipLaunchKernelGGL(rule_sweep_kernel, dim3(grid), dim3(256), 0, s, conf, correct, agree, E1, N, thr, V, pats_dev, P, rule, acc, mean_exit, hist);
+        hipLaunchKernelGGL(rule_sweep_kernel, dim3(grid_1d(V, 1, 8192)), dim3(256), 0, s, conf, correct, agree, E1, N, thr, V, pats_dev, P, rule, acc, mean_exit, hist);
     }
     (void)hipFreeAsync(correct, s);
     (void)hipFreeAsync(agree, s);
@@ -1109,10 +624,7 @@ __global__ __launch_bounds__(256) void msp_table_kernel(const double* __restrict
 
 void launch_msp_table(const double* logits, const long long* refs, int E1, int N, int K, double* conf, unsigned char* correct,
                       hipStream_t s) {
-    size_t total = (size_t)E1 * N;
-    int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(msp_table_kernel, dim3(grid), dim3(256), 0, s, logits, refs, E1, N, K, conf, correct);
+    hipLaunchKernelGGL(msp_table_kernel, dim3(grid_1d((long long)E1 * N, 256, 4096)), dim3(256), 0, s, logits, refs, E1, N, K, conf, correct);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1204,25 +716,32 @@ void launch_temperature_fit(const double* logits, const long long* labels, int E
                        acc_out, conf_out, iters_out);
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// value tables of the relative-position bias: t[h][delta + c] = W[h][lut[delta + c]] / sqrt(d)
-// ---------------------------------------------------------------------------------------------------------------
-__global__ void build_value_tables_kernel(const float* w1, const float* wx, const float* wy, const unsigned char* lut1,
-                                          const unsigned char* lut2, int heads, int bins1, int bins2, int n1, int n2,
-                                          float inv_sqrt_d, float* t1, float* tx, float* ty) {
-    const int h = blockIdx.x;
-    for (int i = threadIdx.x; i < n1; i += blockDim.x) t1[(size_t)h * n1 + i] = w1[(size_t)h * bins1 + lut1[i]] * inv_sqrt_d;
-    for (int i = threadIdx.x; i < n2; i += blockDim.x) {
-        tx[(size_t)h * n2 + i] = wx[(size_t)h * bins2 + lut2[i]] * inv_sqrt_d;
-        ty[(size_t)h * n2 + i] = wy[(size_t)h * bins2 + lut2[i]] * inv_sqrt_d;
+// (logits f32 (n,K), exit_layer i32 (n), confidence f32 (n)) <-> the row of the ONE all-gather of the north star: K + 2 int32 words per document
+// (the floats travel as their bit patterns: integer copies and collectives never flush, canonicalise or round them)
+__global__ __launch_bounds__(256) void pack_results_kernel(const float* __restrict__ logits, const int* __restrict__ exit_layer,
+                                                           const float* __restrict__ conf, int n, int K, int* __restrict__ rows) {
+    const long total = (long)n * (K + 2);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int d = (int)(i / (K + 2)), c = (int)(i - (long)d * (K + 2));
+        rows[i] = c < K ? __float_as_int(logits[(size_t)d * K + c]) : c == K ? exit_layer[d] : __float_as_int(conf[d]);
     }
 }
-
-void launch_build_value_tables(const float* w1, const float* wx, const float* wy, const unsigned char* lut1,
-                               const unsigned char* lut2, int heads, int bins1, int bins2, int n1, int n2, float inv_sqrt_d,
-                               float* t1, float* tx, float* ty, hipStream_t s) {
-    hipLaunchKernelGGL(build_value_tables_kernel, dim3(heads), dim3(256), 0, s, w1, wx, wy, lut1, lut2, heads, bins1, bins2,
-                       n1, n2, inv_sqrt_d, t1, tx, ty);
+__global__ __launch_bounds__(256) void unpack_results_kernel(const int* __restrict__ rows, int n, int K, float* __restrict__ logits,
+                                                             int* __restrict__ exit_layer, float* __restrict__ conf) {
+    const long total = (long)n * (K + 2);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int d = (int)(i / (K + 2)), c = (int)(i - (long)d * (K + 2));
+        const int v = rows[i];
+        if (c < K) { if (logits) logits[(size_t)d * K + c] = __int_as_float(v); }
+        else if (c == K) { if (exit_layer) exit_layer[d] = v; }
+        else if (conf) conf[d] = __int_as_float(v);
+    }
+}
+void launch_pack_results(const float* logits, const int* exit_layer, const float* conf, int n, int K, int* rows, hipStream_t s) {
+    hipLaunchKernelGGL(pack_results_kernel, dim3(grid_1d((long)n * (K + 2), 256, 4096)), dim3(256), 0, s, logits, exit_layer, conf, n, K, rows);
+}
+void launch_unpack_results(const int* rows, int n, int K, float* logits, int* exit_layer, float* conf, hipStream_t s) {
+    hipLaunchKernelGGL(unpack_results_kernel, dim3(grid_1d((long)n * (K + 2), 256, 4096)), dim3(256), 0, s, rows, n, K, logits, exit_layer, conf);
 }
 
 }  // namespace mmee

@@ -1,0 +1,358 @@
+// The forward pass's exit stage: the exit heads' output projection, the criteria, the on-device exit decision (confidence test -> wavefront
+// ballot -> prefix sum -> stream compaction of the document list), row-map expansion, and the CLS / padded hidden-state outputs.
+//
+// What this replaces in the reference:
+//   * LayoutLMv3Exit.out_proj (EE/models/LayoutLMv3.py:92) / classifier.out_proj (HF:821) : head_out_kernel
+//   * max_confidence / entropy criteria (EE/models/EE_modules.py:149-160)                   : crit_f32 / crit_f64
+//   * Policy.max_confidence_global_thresholding_policy / accuracy_calibration_heuristic (EE/policy.py:28-45, 87-104):
+//     the nested Python loop "first exit whose float64 max-softmax is strictly above its threshold, else the last"
+//     becomes exit_decide_kernel inside the forward pass: documents that satisfy the test are scattered to the
+//     outputs and removed, deeper layers run on the survivors only.  (The same policy on a dumped array: exit_ops.hip.)
+// All of it is HBM/latency-bound integer + small-vector work; none of it is shaped into a GEMM.
+#include "mmee_kernels.h"
+
+namespace mmee {
+
+// ---------------------------------------------------------------------------------------------------------------
+// out[i][c] = <in[row(i)], W[c]> + b[c]; one wave per document
+// ---------------------------------------------------------------------------------------------------------------
+// LTE (ee_config.use_lte): the same wave also scores its document, u = sigmoid(w . x + b) on the CLS row the exit's head reads (a second row
+// source: the head of a 2-layer exit reads its dense layer's output here).  float64 throughout, in a fixed order: lane l adds its columns
+// 4l + 256k + j in the order k, j; the lane sums go through one butterfly.  Nothing depends on which documents share the launch.  The
+// LTE = false instantiation is the kernel as it was.
+template <int WAVES, bool LTE>
+__device__ __forceinline__ void head_out_body(const HeadOutArgs& a) {
+    const int n = *a.n_docs_ptr;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = blockIdx.x * WAVES + wave; i < n; i += gridDim.x * WAVES) {
+        const int row = a.gather ? a.gather[i] : i;
+        const float* x = a.in + (size_t)row * a.ld;
+        f32x4 xv[kMaxNV];
+#pragma unroll
+        for (int k = 0; k < kMaxNV; ++k) {
+            const int c = 4 * lane + 256 * k;
+            xv[k] = (c < a.H) ? *reinterpret_cast<const f32x4*>(x + c) : f32x4{0, 0, 0, 0};
+        }
+        for (int o = 0; o < a.Ko; ++o) {
+            const float* w = a.W + (size_t)o * a.H;
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < kMaxNV; ++k) {
+                const int c = 4 * lane + 256 * k;
+                if (c < a.H) {
+                    const f32x4 wv = *reinterpret_cast<const f32x4*>(w + c);
+                    s += (xv[k][0] * wv[0] + xv[k][1] * wv[1]) + (xv[k][2] * wv[2] + xv[k][3] * wv[3]);
+                }
+            }
+            s = wave_sum(s);
+            if (lane == 0) a.out[(size_t)i * a.Ko + o] = s + a.b[o];
+        }
+        if constexpr (LTE) {
+            const float* lx = a.lte_in + (size_t)(a.lte_gather ? a.lte_gather[i] : i) * a.lte_ld;
+            double t = 0.0;
+#pragma unroll
+            for (int k = 0; k < kMaxNV; ++k) {
+                const int c = 4 * lane + 256 * k;
+                if (c < a.H) {
+                    const f32x4 v = a.lte_split_inv != 0.f ? load_split4(lx, c, a.lte_split_inv) : *reinterpret_cast<const f32x4*>(lx + c);
+                    const f32x4 wv = *reinterpret_cast<const f32x4*>(a.lte_w + c);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) t += (double)v[j] * (double)wv[j];
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+            if (lane == 0) a.lte_out[i] = 1.0 / (1.0 + exp(-(t + (double)a.lte_b[0])));
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void head_out_kernel(HeadOutArgs a) { head_out_body<4, false>(a); }
+__global__ __launch_bounds__(256) void head_out_lte_kernel(HeadOutArgs a) { head_out_body<4, true>(a); }
+
+void launch_head_out(const HeadOutArgs& a, int max_docs, hipStream_t s) {
+    const int grid = grid_1d(max_docs, 4, 1024);
+    if (a.lte_out) hipLaunchKernelGGL(head_out_lte_kernel, dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(head_out_kernel, dim3(grid), dim3(256), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// criteria
+// ---------------------------------------------------------------------------------------------------------------
+// float32, as the model computes exit_states[j][1] (EE/models/EE_modules.py:149-160)
+__device__ inline float crit_f32(const float* z, int K, int criterion) {
+    if (criterion == 0) {
+        float m = z[0];
+        for (int k = 1; k < K; ++k) m = fmaxf(m, z[k]);
+        float s = 0.f;
+        for (int k = 0; k < K; ++k) s += expf(z[k] - m);
+        return 1.0f / s;
+    }
+    float A = 0.f, B = 0.f;                       // entropy: log(sum e^x) - sum(x e^x)/sum(e^x), no max shift
+    for (int k = 0; k < K; ++k) {
+        const float e = expf(z[k]);
+        A += e;
+        B += z[k] * e;
+    }
+    return logf(A) - B / A;
+}
+
+// float64 on (double)logit / T, as the policy computes it (scipy.special.softmax on the float64 store, EE/policy.py:30-32)
+__device__ inline double crit_f64(const float* z, int K, double temp, int criterion) {
+    if (criterion == 0) {
+        double m = (double)z[0] / temp;
+        for (int k = 1; k < K; ++k) m = fmax(m, (double)z[k] / temp);
+        double s = 0.0;
+        for (int k = 0; k < K; ++k) s += exp((double)z[k] / temp - m);
+        return 1.0 / s;
+    }
+    double A = 0.0, B = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const double x = (double)z[k] / temp;
+        const double e = exp(x);
+        A += e;
+        B += x * e;
+    }
+    return log(A) - B / A;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The exit stage: one workgroup of 1024 threads walks the active documents in chunks of 1024.
+//   thread <-> document: criterion (f64), exit test, scatter of leavers to the output arrays;
+//   survivors: wave ballot -> popcount prefix -> cross-wave prefix in LDS -> running carry = new dense index,
+//   and the same scan over row counts = new dense row offset.
+// PATIENCE (PABEE, MMEE_CRIT_PATIENCE): the exit test is "the argmax of the scaled logits has stayed the same for t exits in a row"
+// instead of a threshold test.  The criterion written to the outputs is the max-softmax; the run state of document `orig` is
+// (p.prev[orig], p.run[orig]), indexed by the original slot so that compaction never moves it, and written unconditionally at
+// exit 0, which every document reaches (no reset launch).
+// LTE (ee_config.use_lte): the test is "the float64 score head_out_lte_kernel left in a.lte_score is strictly below the threshold"; the score
+// is what the outputs carry as the criterion.  Embedding exits have no score (a.lte_score null): 1.0, nobody leaves.
+// The max_confidence / entropy kernel is the DECIDE_THRESHOLD instantiation.
+// RULE (ee_set_exit_rule; THRESHOLD and LTE modes): the mode's test is the EVENT f_e and the rule decides on it.  MMEE_RULE_STREAK: the event
+// must have held at t_e exits in a row (s_e = f_e ? s_{e-1} + 1 : 0 in p.run[orig]).  MMEE_RULE_EITHER: the event, or PABEE's counter
+// c_e >= t_e ((p.prev[orig], p.run[orig]) exactly as under PATIENCE).  The same state arrays, written unconditionally at exit 0; t_e is the
+// launch's own patience (by value, or at p.t_ptr[0]: the host hands every exit its own entry).  RULE_PLAIN compiles to the kernels as they were.
+// ---------------------------------------------------------------------------------------------------------------
+// PABEE's counter: argmax of the scaled logits as they are written out (two f32 logits can round to one scaled value; first maximum wins),
+// c_e = the argmax equals the one at the previous exit ? c_{e-1} + 1 : 0, state by original slot
+__device__ __forceinline__ int agreement_run(const float* z, int K, double temp, int exit_index, int orig, const PatienceArgs& p) {
+    float best = (float)((double)z[0] / temp);
+    int am = 0;
+    for (int k = 1; k < K; ++k) {
+        const float v = (float)((double)z[k] / temp);
+        if (v > best) { best = v; am = k; }
+    }
+    const int run = (exit_index > 0 && p.prev[orig] == am) ? p.run[orig] + 1 : 0;
+    p.prev[orig] = am;
+    p.run[orig] = run;
+    return run;
+}
+
+template <int MODE, int RULE = RULE_PLAIN>
+__device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const PatienceArgs& p) {
+    constexpr bool PATIENCE = MODE == DECIDE_PATIENCE;
+    static_assert(RULE == RULE_PLAIN || !PATIENCE, "PABEE has no threshold event to build a rule on");
+    __shared__ int s_cnt[16], s_rows[16];
+    __shared__ unsigned long long s_sq[16];
+    __shared__ int s_carry_docs, s_carry_rows;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = a.counts->n_docs;
+    const double thr = a.thr_ptr ? a.thr_ptr[a.exit_index] : a.thr;
+    const double temp = a.temp_ptr ? a.temp_ptr[a.exit_index] : a.temp;
+    int patience = 0;
+    if constexpr (PATIENCE || RULE != RULE_PLAIN) patience = p.t_ptr ? (int)p.t_ptr[0] : p.t;
+    if (tid == 0) { s_carry_docs = 0; s_carry_rows = 0; }
+    unsigned long long sq = 0;
+    __syncthreads();
+    for (int base = 0; base < n; base += 1024) {
+        const int i = base + tid;
+        const bool active = i < n;
+        bool keep = false;
+        int len = 0, orig = 0;
+        if (active) {
+            orig = a.doc_orig[i];
+            len = a.doc_off[i + 1] - a.doc_off[i];
+            const float* z = a.pol_logits + (size_t)i * a.K;
+            double crit;
+            bool leave;
+            if constexpr (PATIENCE) {
+                crit = crit_f64(z, a.K, temp, 0);
+                leave = agreement_run(z, a.K, temp, a.exit_index, orig, p) >= patience;
+            } else if constexpr (MODE == DECIDE_LTE) {
+                crit = a.lte_score ? a.lte_score[i] : 1.0;
+                leave = a.lte_score && crit < thr;                        // strict, EE/models/LayoutLMv3.py:262
+            } else {
+                crit = crit_f64(z, a.K, temp, a.criterion);
+                leave = a.criterion == 0 ? (crit > thr) : (crit < thr);   // strict, EE/policy.py:33
+            }
+            if constexpr (RULE == RULE_STREAK) {
+                const int streak = leave ? (a.exit_index > 0 ? p.run[orig] : 0) + 1 : 0;
+                p.run[orig] = streak;
+                leave = streak >= patience;
+            } else if constexpr (RULE == RULE_EITHER) {
+                const bool agreed = agreement_run(z, a.K, temp, a.exit_index, orig, p) >= patience;
+                leave = leave || agreed;
+            }
+            if (a.no_exit) leave = false;
+            if (a.is_final) leave = true;
+            if (a.out_all_logits) {
+                float* o = a.out_all_logits + ((size_t)a.exit_index * a.B + orig) * a.K;
+                for (int k = 0; k < a.K; ++k) o[k] = (float)((double)z[k] / temp);
+            }
+            if (a.out_all_crit) a.out_all_crit[(size_t)a.exit_index * a.B + orig] = (float)crit;
+            if (a.head_logits && a.out_head_logits) {
+                const float* hz = a.head_logits + (size_t)i * a.Kh;
+                float* o = a.out_head_logits + ((size_t)a.exit_index * a.B + orig) * a.Kh;
+                for (int k = 0; k < a.Kh; ++k) o[k] = hz[k];
+            }
+            if (a.head_logits && a.out_head_crit)
+                a.out_head_crit[(size_t)a.exit_index * a.B + orig] =
+                    crit_f32(a.head_logits + (size_t)i * a.Kh, a.Kh, PATIENCE ? 0 : a.criterion);
+            if (leave) {
+                if (a.out_logits)
+                    for (int k = 0; k < a.K; ++k) a.out_logits[(size_t)orig * a.K + k] = (float)((double)z[k] / temp);
+                a.out_exit[orig] = a.exit_index;
+                if (a.out_conf) a.out_conf[orig] = (float)crit;
+            }
+            keep = !leave;
+        }
+        // ---- wavefront ballot + prefix sums ------------------------------------------------------------------
+        const unsigned long long ballot = __ballot(keep);
+        const int before = __popcll(ballot & ((1ull << lane) - 1ull));       // survivors in lower lanes
+        const int klen = keep ? len : 0;
+        const int rows_incl = wave_incl_scan(klen, lane);
+        if (lane == 63) { s_cnt[wave] = __popcll(ballot); s_rows[wave] = rows_incl; }
+        if (keep) sq += (unsigned long long)len * (unsigned long long)len;
+        __syncthreads();
+        int wdocs = 0, wrows = 0, tdocs = 0, trows = 0;
+        for (int w = 0; w < 16; ++w) {
+            if (w < wave) { wdocs += s_cnt[w]; wrows += s_rows[w]; }
+            tdocs += s_cnt[w];
+            trows += s_rows[w];
+        }
+        const int cd = s_carry_docs, cr = s_carry_rows;
+        if (keep) {
+            const int k = cd + wdocs + before;
+            a.n_doc_orig[k] = orig;
+            a.n_doc_off[k] = cr + wrows + rows_incl - len;
+            a.n_x_src[k] = a.x_phys[i];
+            a.n_meta_src[k] = a.doc_off[i];
+        }
+        __syncthreads();
+        if (tid == 0) { s_carry_docs = cd + tdocs; s_carry_rows = cr + trows; }
+        __syncthreads();
+    }
+    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+    if (lane == 0) s_sq[wave] = sq;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long t = 0;
+        for (int w = 0; w < 16; ++w) t += s_sq[w];
+        a.n_doc_off[s_carry_docs] = s_carry_rows;
+        a.n_counts->n_docs = s_carry_docs;
+        a.n_counts->n_rows = s_carry_rows;
+        a.n_counts->sum_len_sq = t;
+    }
+}
+
+__global__ __launch_bounds__(1024) void exit_decide_kernel(DecideArgs a) { exit_decide_body<DECIDE_THRESHOLD>(a, PatienceArgs{}); }
+__global__ __launch_bounds__(1024) void exit_decide_patience_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<DECIDE_PATIENCE>(a, p); }
+__global__ __launch_bounds__(1024) void exit_decide_lte_kernel(DecideArgs a) { exit_decide_body<DECIDE_LTE>(a, PatienceArgs{}); }
+__global__ __launch_bounds__(1024) void exit_decide_streak_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<DECIDE_THRESHOLD, RULE_STREAK>(a, p); }
+__global__ __launch_bounds__(1024) void exit_decide_either_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<DECIDE_THRESHOLD, RULE_EITHER>(a, p); }
+__global__ __launch_bounds__(1024) void exit_decide_lte_streak_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<DECIDE_LTE, RULE_STREAK>(a, p); }
+__global__ __launch_bounds__(1024) void exit_decide_lte_either_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<DECIDE_LTE, RULE_EITHER>(a, p); }
+
+// mode: DECIDE_*, rule: RULE_PLAIN / _STREAK / _EITHER.  The plain threshold and LTE kernels keep no state and take no PatienceArgs (p may be null)
+void launch_decide(const DecideArgs& a, const PatienceArgs* p, int mode, int rule, hipStream_t s) {
+    using Plain = void (*)(DecideArgs);
+    using Stateful = void (*)(DecideArgs, PatienceArgs);
+    static const Plain plain[3] = {exit_decide_kernel, nullptr, exit_decide_lte_kernel};
+    static const Stateful stateful[3][3] = {{nullptr, exit_decide_streak_kernel, exit_decide_either_kernel},
+                                            {exit_decide_patience_kernel, nullptr, nullptr},
+                                            {nullptr, exit_decide_lte_streak_kernel, exit_decide_lte_either_kernel}};
+    if (plain[mode] && rule == RULE_PLAIN) hipLaunchKernelGGL(plain[mode], dim3(1), dim3(1024), 0, s, a);
+    else hipLaunchKernelGGL(stateful[mode][rule], dim3(1), dim3(1024), 0, s, a, *p);
+}
+
+// Round 6: the head's output projection and the decision were built as ONE launch (every workgroup writes its documents' logits, fences,
+// takes a ticket; the last arrival runs the scan: nobody waits, same bits, 91 GPU tests green) and measured on config 3 (2 x 512 documents, 48 exits per step):
+// 52.7 us per exit against 31 + 16 us for the two launches -- the fences and the serial scan behind the last arrival cost what the launch saved.  Removed.
+
+// new dense row r of surviving document k  <-  physical X row n_x_src[k] + t, metadata row n_meta_src[k] + t
+__global__ __launch_bounds__(256) void compact_rows_kernel(const StageCounts* n_counts, const int* __restrict__ n_doc_off,
+                                                           const int* __restrict__ n_x_src, const int* __restrict__ n_meta_src,
+                                                           const RowMeta* __restrict__ meta_old, RowMeta* __restrict__ meta_new,
+                                                           int* __restrict__ row_src) {
+    const int n = n_counts->n_docs;
+    for (int k = blockIdx.x; k < n; k += gridDim.x) {
+        const int off = n_doc_off[k], len = n_doc_off[k + 1] - off;
+        const int xs = n_x_src[k], ms = n_meta_src[k];
+        for (int t = threadIdx.x; t < len; t += 256) {
+            row_src[off + t] = xs + t;
+            meta_new[off + t] = meta_old[ms + t];
+        }
+    }
+}
+
+void launch_compact_rows(const StageCounts* n_counts, const int* n_doc_off, const int* n_x_src, const int* n_meta_src,
+                         const RowMeta* meta_old, RowMeta* meta_new, int* row_src, int max_docs, int num_cus, hipStream_t s) {
+    hipLaunchKernelGGL(compact_rows_kernel, dim3(grid_1d(max_docs, 1, num_cus * 8)), dim3(256), 0, s, n_counts, n_doc_off, n_x_src, n_meta_src,
+                       meta_old, meta_new, row_src);
+}
+
+// out[orig][:] = X[x_phys[i]][:]   (CLS rows, parity/debug output)
+// CLS row of every active document -> out[doc_orig ? doc_orig[i] : i].  split_inv != 0: X holds split-f16 rows (1 / scale = split_inv)
+__global__ __launch_bounds__(256) void gather_cls_kernel(const float* __restrict__ X, int H, const int* __restrict__ x_phys,
+                                                         const int* __restrict__ doc_orig, const int* __restrict__ n_docs_ptr,
+                                                         float* __restrict__ out, float split_inv) {
+    const int n = *n_docs_ptr;
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        const float* src = X + (size_t)x_phys[i] * H;
+        float* dst = out + (size_t)(doc_orig ? doc_orig[i] : i) * H;
+        if (split_inv != 0.f) {
+            for (int c = 4 * threadIdx.x; c < H; c += 1024) *reinterpret_cast<f32x4*>(dst + c) = load_split4(src, c, split_inv);
+        } else {
+            for (int c = threadIdx.x; c < H; c += 256) dst[c] = src[c];
+        }
+    }
+}
+
+// Hidden states in the reference's padded layout (ee_set_hidden_states_out): position p of document d is text token p (packed row
+// text_dst[d * T + p], < 0 when the ragged layout dropped it: zeros) or visual row p - T (packed behind the document's ntext[d] text rows).
+__global__ __launch_bounds__(256) void rows_to_padded_kernel(const float* __restrict__ X, float split_inv, int H, int B, int T, int Pv,
+                                                             const int* __restrict__ text_dst, const int* __restrict__ ntext,
+                                                             const int* __restrict__ doc_off, float* __restrict__ out) {
+    const int S = T + Pv;
+    for (long r = blockIdx.x; r < (long)B * S; r += gridDim.x) {
+        const int d = (int)(r / S), p = (int)(r - (long)d * S);
+        int row;
+        if (p < T) {
+            const int t = text_dst[(size_t)d * T + p];
+            row = t < 0 ? -1 : doc_off[d] + t;
+        } else {
+            row = doc_off[d] + (text_dst ? ntext[d] : 0) + (p - T);
+        }
+        float* dst = out + (size_t)r * H;
+        if (row < 0) {
+            for (int c = threadIdx.x; c < H; c += 256) dst[c] = 0.f;
+        } else if (split_inv != 0.f) {
+            const float* src = X + (size_t)row * H;
+            for (int c = 4 * threadIdx.x; c < H; c += 1024) *reinterpret_cast<f32x4*>(dst + c) = load_split4(src, c, split_inv);
+        } else {
+            const float* src = X + (size_t)row * H;
+            for (int c = threadIdx.x; c < H; c += 256) dst[c] = src[c];
+        }
+    }
+}
+void launch_rows_to_padded(const float* X, float split_inv, int H, int B, int T, int Pv, const int* text_dst, const int* ntext, const int* doc_off,
+                           float* out, hipStream_t s) {
+    hipLaunchKernelGGL(rows_to_padded_kernel, dim3(grid_1d((long)B * (T + Pv), 1, 4096)), dim3(256), 0, s, X, split_inv, H, B, T, Pv, text_dst, ntext, doc_off, out);
+}
+
+void launch_gather_cls(const float* X, int H, const int* x_phys, const int* doc_orig, const int* n_docs_ptr, float* out,
+                       int max_docs, hipStream_t s, float split_inv) {
+    hipLaunchKernelGGL(gather_cls_kernel, dim3(grid_1d(max_docs, 1, 2048)), dim3(256), 0, s, X, H, x_phys, doc_orig, n_docs_ptr, out, split_inv);
+}
+
+}  // namespace mmee

@@ -67,6 +67,12 @@ inline hipError_t ensure_dynamic_lds(const char* name, int bytes) {
     return rc;
 }
 
+// workgroups of a one-dimensional launch: ceil(work / per_block), at most cap, at least 1
+inline int grid_1d(long long work, int per_block, long long cap) {
+    const long long g = (work + per_block - 1) / per_block;
+    return (int)(g < 1 ? 1 : g > cap ? cap : g);
+}
+
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

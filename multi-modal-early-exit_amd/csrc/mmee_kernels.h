@@ -1,4 +1,5 @@
-// Parameter blocks + launchers of the row / exit kernels (prep_embed.hip, exit_ops.hip).
+// Parameter blocks + launchers of the row kernels (prep_embed.hip), the forward pass's exit stage (exit_stage.hip) and the handle-free
+// tools on dumped arrays (exit_ops.hip).
 #pragma once
 #include "mmee_common.h"
 
@@ -115,6 +116,26 @@ struct PatienceArgs {
     int* run;                        // [max_docs] run counter c_e (MMEE_RULE_STREAK: the streak s_e), by original slot
 };
 
+// how launch_decide picks its kernel: the exit test (MODE) and the rule built on it (RULE = MMEE_RULE_*; DECIDE_PATIENCE takes RULE_PLAIN only)
+enum { DECIDE_THRESHOLD = 0, DECIDE_PATIENCE = 1, DECIDE_LTE = 2 };
+enum { RULE_PLAIN = 0, RULE_STREAK = 1, RULE_EITHER = 2, RULE_AGREE = 3 };      // RULE_AGREE: PABEE's counter alone (exit_scan_kernel only)
+
+// exit_scan_kernel<EVENT, RULE>: the exit decision on dumped arrays (ee_policy_scan, ee_patience_scan, ee_lte_scan, ee_rule_scan)
+enum { SCAN_MSP = 0, SCAN_TABLE = 1, SCAN_NONE = 2 };      // the event's criterion: float64 max-softmax of the logits row, crit[e][n], no event
+struct ScanArgs {
+    const double* logits;            // (E1,N,K); read for SCAN_MSP, RULE_EITHER, RULE_AGREE and for `pred` only: may be null otherwise
+    const double* crit;              // (E1,N) SCAN_TABLE's criterion
+    double sign;                     // the event is sign * criterion > sign * thr[e] (+1: '>', -1: '<'; multiplying by +-1 is exact)
+    const double* thr;               // [E1] on the device; null for SCAN_NONE
+    const int* pat;                  // [E1] per-exit patience on the device, or null: pat_all at every exit
+    int pat_all;
+    int E1, N, K;
+    int* exits;                      // (N)
+    double* pred;                    // (N,K) or null: the logits row of the chosen exit
+    double* conf;                    // (N) or null: SCAN_TABLE: crit at the chosen exit, else the float64 max-softmax of its row
+    int* counts;                     // [E1] or null, zeroed by the caller
+};
+
 // X-space CLS probe (xprobe.hip)
 struct XProbeArgs {
     const char* xs;                  // split rows of X (LayerNorm output), H * 4 bytes per row, scaled by 1 / xs_inv
@@ -164,10 +185,7 @@ void launch_embed_beit(const float* patch, const float* cls, const float* pos, i
 void launch_patch_mean(const float* X, int H, const int* x_phys, const int* doc_off, const int* n_docs_ptr, float* pooled,
                        int max_docs, hipStream_t s);
 void launch_head_out(const HeadOutArgs& a, int max_docs, hipStream_t s);
-void launch_decide(const DecideArgs& a, hipStream_t s);
-void launch_decide_patience(const DecideArgs& a, const PatienceArgs& p, hipStream_t s);
-void launch_decide_lte(const DecideArgs& a, hipStream_t s);
-void launch_decide_rule(const DecideArgs& a, const PatienceArgs& p, int rule, bool lte, hipStream_t s);   // rule: MMEE_RULE_STREAK / _EITHER
+void launch_decide(const DecideArgs& a, const PatienceArgs* p, int mode, int rule, hipStream_t s);   // p: null where (mode, rule) keeps no state
 void launch_pack_results(const float* logits, const int* exit_layer, const float* conf, int n, int K, int* rows, hipStream_t s);
 void launch_unpack_results(const int* rows, int n, int K, float* logits, int* exit_layer, float* conf, hipStream_t s);
 void launch_compact_rows(const StageCounts* n_counts, const int* n_doc_off, const int* n_x_src, const int* n_meta_src,
@@ -185,14 +203,7 @@ void launch_rows_to_padded(const float* X, float split_inv, int H, int B, int T,
                            float* out, hipStream_t s);
 void launch_gather_cls(const float* X, int H, const int* x_phys, const int* doc_orig, const int* n_docs_ptr,
                        float* out, int max_docs, hipStream_t s, float split_inv = 0.f);
-void launch_policy_scan(const double* logits, int E1, int N, int K, const double* thr_dev, int* exits, double* pred,
-                        double* conf, int* counts, hipStream_t s);
-void launch_patience_scan(const double* logits, int E1, int N, int K, int t, int* exits, double* pred, double* conf, int* counts,
-                          hipStream_t s);
-void launch_lte_scan(const double* scores, const double* logits, int E1, int N, int K, const double* thr_dev, int* exits, double* pred,
-                     int* counts, hipStream_t s);
-void launch_rule_scan(const double* crit, double sign, const double* logits, int E1, int N, int K, const double* thr_dev, const int* pat_dev,
-                      int rule, int* exits, double* pred, double* conf, int* counts, hipStream_t s);
+void launch_exit_scan(const ScanArgs& a, int event, int rule, hipStream_t s);
 bool launch_rule_sweep(const double* conf, const double* logits, const long long* refs, int E1, int N, int K, const double* thr, int V,
                        const int* pats_host, const int* pats_dev, int P, int rule, double* acc, double* mean_exit, int* hist, hipStream_t s);
 bool launch_patience_sweep(const double* logits, const long long* refs, int E1, int N, int K, const int* pats, int V, double* acc,

@@ -17,6 +17,41 @@ from . import capi
 from .engine import _require_torch_cuda, torch
 
 
+def _on(dev, x, dtype):
+    """``x`` (numpy array, tensor or sequence) as a contiguous tensor of ``dtype`` on ``dev``."""
+    t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else torch.as_tensor(x)
+    return t.to(dev, dtype=dtype).contiguous()
+
+
+def _f64_on(dev, x):
+    return _on(dev, x, torch.float64)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _threshold_vector(thresholds, E1):
+    """A scalar or (E1,) thresholds as the ``double[E1]`` the C ABI reads."""
+    thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float64).reshape(-1), (E1,)) if np.ndim(thresholds) \
+        else np.full((E1,), float(thresholds))
+    return (C.c_double * E1)(*[float(t) for t in thr])
+
+
+def _run_scan(name, dev, shape, want_conf, call):
+    """Allocates the outputs of a scan over logits of ``shape`` (E1,N,K) and runs ``call(exits, pred, conf, counts, stream)`` -- the ctypes
+    call of entry point ``name`` -- on the current stream of ``dev``.  Returns (exits, pred, conf | None, counts)."""
+    E1, N, K = shape
+    exits = torch.empty((N,), dtype=torch.int32, device=dev)
+    pred = torch.empty((N, K), dtype=torch.float64, device=dev)
+    conf = torch.empty((N,), dtype=torch.float64, device=dev) if want_conf else None
+    counts = torch.zeros((E1,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = call(_ptr(exits), _ptr(pred), _ptr(conf), _ptr(counts), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    capi.check(rc, None, name)
+    return exits, pred, conf, counts
+
+
 def policy_scan_device(logits, thresholds, device=None, want_conf: bool = False):
     """First exit whose float64 max-softmax is strictly above its threshold, else the last exit.
 
@@ -25,27 +60,13 @@ def policy_scan_device(logits, thresholds, device=None, want_conf: bool = False)
     confidence float64 | None, counts int32)."""
     lib = capi.load()
     dev = _require_torch_cuda(device)
-    if isinstance(logits, np.ndarray):
-        L = torch.from_numpy(np.ascontiguousarray(logits)).to(dev, dtype=torch.float64)
-    else:
-        L = logits.to(dev, dtype=torch.float64).contiguous()
+    L = _f64_on(dev, logits)
     if L.dim() != 3:
         raise ValueError("logits must have shape (num_exits + 1, num_samples, num_labels)")
     E1, N, K = L.shape
-    thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float64).reshape(-1), (E1,)) if np.ndim(thresholds) \
-        else np.full((E1,), float(thresholds))
-    thr_c = (C.c_double * E1)(*[float(t) for t in thr])
-    exits = torch.empty((N,), dtype=torch.int32, device=dev)
-    pred = torch.empty((N, K), dtype=torch.float64, device=dev)
-    conf = torch.empty((N,), dtype=torch.float64, device=dev) if want_conf else None
-    counts = torch.zeros((E1,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        rc = lib.ee_policy_scan(C.c_void_p(L.data_ptr()), E1, N, K, thr_c, C.c_void_p(exits.data_ptr()),
-                                C.c_void_p(pred.data_ptr()), C.c_void_p(conf.data_ptr()) if conf is not None else None,
-                                C.c_void_p(counts.data_ptr()), stream)
-    capi.check(rc, None, "ee_policy_scan")
-    return exits, pred, conf, counts
+    thr_c = _threshold_vector(thresholds, E1)
+    return _run_scan("ee_policy_scan", dev, L.shape, want_conf,
+                     lambda exits, pred, conf, counts, stream: lib.ee_policy_scan(_ptr(L), E1, N, K, thr_c, exits, pred, conf, counts, stream))
 
 
 def patience_scan_device(logits, patience: int, device=None, want_conf: bool = False):
@@ -55,23 +76,12 @@ def patience_scan_device(logits, patience: int, device=None, want_conf: bool = F
     t = check_patience(patience)
     lib = capi.load()
     dev = _require_torch_cuda(device)
-    if isinstance(logits, np.ndarray):
-        L = torch.from_numpy(np.ascontiguousarray(logits)).to(dev, dtype=torch.float64)
-    else:
-        L = logits.to(dev, dtype=torch.float64).contiguous()
+    L = _f64_on(dev, logits)
     if L.dim() != 3:
         raise ValueError("logits must have shape (num_exits + 1, num_samples, num_labels)")
     E1, N, K = L.shape
-    exits = torch.empty((N,), dtype=torch.int32, device=dev)
-    pred = torch.empty((N, K), dtype=torch.float64, device=dev)
-    conf = torch.empty((N,), dtype=torch.float64, device=dev) if want_conf else None
-    counts = torch.zeros((E1,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        rc = lib.ee_patience_scan(C.c_void_p(L.data_ptr()), E1, N, K, t, C.c_void_p(exits.data_ptr()), C.c_void_p(pred.data_ptr()),
-                                  C.c_void_p(conf.data_ptr()) if conf is not None else None, C.c_void_p(counts.data_ptr()), stream)
-    capi.check(rc, None, "ee_patience_scan")
-    return exits, pred, conf, counts
+    return _run_scan("ee_patience_scan", dev, L.shape, want_conf,
+                     lambda exits, pred, conf, counts, stream: lib.ee_patience_scan(_ptr(L), E1, N, K, t, exits, pred, conf, counts, stream))
 
 
 def lte_scan_device(scores, logits, thresholds, device=None):
@@ -80,22 +90,14 @@ def lte_scan_device(scores, logits, thresholds, device=None):
     Returns device tensors (exits int32, predictions float64, counts int32) (ee_lte_scan)."""
     lib = capi.load()
     dev = _require_torch_cuda(device)
-    to = lambda x: (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x).to(dev, dtype=torch.float64).contiguous()
-    S, L = to(scores), to(logits)
+    S, L = _f64_on(dev, scores), _f64_on(dev, logits)
     if L.dim() != 3 or tuple(S.shape) != tuple(L.shape[:2]):
         raise ValueError("scores must have shape (num_exits + 1, num_samples) and logits (num_exits + 1, num_samples, num_labels)")
     E1, N, K = L.shape
-    thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float64).reshape(-1), (E1,)) if np.ndim(thresholds) \
-        else np.full((E1,), float(thresholds))
-    thr_c = (C.c_double * E1)(*[float(t) for t in thr])
-    exits = torch.empty((N,), dtype=torch.int32, device=dev)
-    pred = torch.empty((N, K), dtype=torch.float64, device=dev)
-    counts = torch.zeros((E1,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        rc = lib.ee_lte_scan(C.c_void_p(S.data_ptr()), C.c_void_p(L.data_ptr()), E1, N, K, thr_c, C.c_void_p(exits.data_ptr()),
-                             C.c_void_p(pred.data_ptr()), C.c_void_p(counts.data_ptr()), stream)
-    capi.check(rc, None, "ee_lte_scan")
+    thr_c = _threshold_vector(thresholds, E1)
+    exits, pred, _, counts = _run_scan(
+        "ee_lte_scan", dev, L.shape, False,
+        lambda exits, pred, conf, counts, stream: lib.ee_lte_scan(_ptr(S), _ptr(L), E1, N, K, thr_c, exits, pred, counts, stream))
     return exits, pred, counts
 
 
@@ -114,27 +116,16 @@ def rule_scan_device(criterion, logits, thresholds, patience, rule, sign: float 
         raise ValueError("sign must be +1 (criterion > threshold) or -1 (criterion < threshold)")
     lib = capi.load()
     dev = _require_torch_cuda(device)
-    to = lambda x: (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x).to(dev, dtype=torch.float64).contiguous()
-    Cr, L = to(criterion), to(logits)
+    Cr, L = _f64_on(dev, criterion), _f64_on(dev, logits)
     if L.dim() != 3 or tuple(Cr.shape) != tuple(L.shape[:2]):
         raise ValueError("criterion must have shape (num_exits + 1, num_samples) and logits (num_exits + 1, num_samples, num_labels)")
     E1, N, K = L.shape
     t = check_patience_spec(patience, E1)
     pat_c = (C.c_int32 * E1)(*(t if isinstance(t, list) else [t] * E1))
-    thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float64).reshape(-1), (E1,)) if np.ndim(thresholds) \
-        else np.full((E1,), float(thresholds))
-    thr_c = (C.c_double * E1)(*[float(x) for x in thr])
-    exits = torch.empty((N,), dtype=torch.int32, device=dev)
-    pred = torch.empty((N, K), dtype=torch.float64, device=dev)
-    conf = torch.empty((N,), dtype=torch.float64, device=dev) if want_conf else None
-    counts = torch.zeros((E1,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        rc = lib.ee_rule_scan(C.c_void_p(Cr.data_ptr()), float(sign), C.c_void_p(L.data_ptr()), E1, N, K, thr_c, pat_c, r.code,
-                              C.c_void_p(exits.data_ptr()), C.c_void_p(pred.data_ptr()),
-                              C.c_void_p(conf.data_ptr()) if conf is not None else None, C.c_void_p(counts.data_ptr()), stream)
-    capi.check(rc, None, "ee_rule_scan")
-    return exits, pred, conf, counts
+    thr_c = _threshold_vector(thresholds, E1)
+    return _run_scan("ee_rule_scan", dev, L.shape, want_conf,
+                     lambda exits, pred, conf, counts, stream: lib.ee_rule_scan(_ptr(Cr), float(sign), _ptr(L), E1, N, K, thr_c, pat_c, r.code,
+                                                                                exits, pred, conf, counts, stream))
 
 
 class Policy:

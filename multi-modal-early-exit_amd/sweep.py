@@ -13,6 +13,7 @@ import numpy as np
 
 from . import capi
 from .engine import _require_torch_cuda, torch
+from .policy import _f64_on, _on, _ptr
 
 
 def _stream():
@@ -23,16 +24,15 @@ def msp_table(logits, references=None, device=None):
     """(conf float64 (E1,N), correct uint8 (E1,N) | None) on the device from logits (E1,N,K)."""
     lib = capi.load()
     dev = _require_torch_cuda(device)
-    L = (torch.from_numpy(np.ascontiguousarray(logits)) if isinstance(logits, np.ndarray) else logits).to(dev, torch.float64).contiguous()
+    L = _f64_on(dev, logits)
     E1, N, K = L.shape
     conf = torch.empty((E1, N), dtype=torch.float64, device=dev)
     refs = corr = None
     if references is not None:
-        refs = (torch.from_numpy(np.ascontiguousarray(references)) if isinstance(references, np.ndarray) else references).to(dev, torch.int64).contiguous()
+        refs = _on(dev, references, torch.int64)
         corr = torch.empty((E1, N), dtype=torch.uint8, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     with torch.cuda.device(dev):
-        capi.check(lib.ee_msp_table(p(L), p(refs), E1, N, K, p(conf), p(corr), _stream()), None, "ee_msp_table")
+        capi.check(lib.ee_msp_table(_ptr(L), _ptr(refs), E1, N, K, _ptr(conf), _ptr(corr), _stream()), None, "ee_msp_table")
     return conf, corr
 
 
@@ -44,9 +44,8 @@ def patience_sweep(logits, references, patiences, want_hist: bool = False, devic
     from .config import check_patience
     lib = capi.load()
     dev = _require_torch_cuda(device)
-    to = lambda x, dt: (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else torch.as_tensor(x)).to(dev, dt).contiguous()
     pats = [check_patience(t) for t in np.asarray(patiences).reshape(-1).tolist()]
-    L, refs = to(logits, torch.float64), to(references, torch.int64)
+    L, refs = _f64_on(dev, logits), _on(dev, references, torch.int64)
     if L.dim() != 3 or tuple(refs.shape) != (L.shape[1],):
         raise ValueError("logits (E1,N,K), references (N,)")
     E1, N, K = L.shape
@@ -55,9 +54,9 @@ def patience_sweep(logits, references, patiences, want_hist: bool = False, devic
     acc = torch.empty((V,), dtype=torch.float64, device=dev)
     mex = torch.empty((V,), dtype=torch.float64, device=dev)
     hist = torch.empty((V, E1), dtype=torch.int32, device=dev) if want_hist else None
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     with torch.cuda.device(dev):
-        capi.check(lib.ee_patience_sweep(p(L), p(refs), E1, N, K, p(pt), V, p(acc), p(mex), p(hist), _stream()), None, "ee_patience_sweep")
+        capi.check(lib.ee_patience_sweep(_ptr(L), _ptr(refs), E1, N, K, _ptr(pt), V, _ptr(acc), _ptr(mex), _ptr(hist), _stream()), None,
+                   "ee_patience_sweep")
     return acc, mex, hist
 
 
@@ -77,9 +76,8 @@ def rule_sweep(criterion, logits, references, thresholds, patiences, rule, sign:
         raise ValueError("sign must be +1 or -1")
     lib = capi.load()
     dev = _require_torch_cuda(device)
-    to = lambda x, dt: (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else torch.as_tensor(x)).to(dev, dt).contiguous()
     pats = [check_patience(t) for t in np.asarray(patiences).reshape(-1).tolist()]
-    cf, L, refs, th = to(criterion, torch.float64), to(logits, torch.float64), to(references, torch.int64), to(thresholds, torch.float64)
+    cf, L, refs, th = _f64_on(dev, criterion), _f64_on(dev, logits), _on(dev, references, torch.int64), _f64_on(dev, thresholds)
     if L.dim() != 3 or tuple(cf.shape) != tuple(L.shape[:2]) or tuple(refs.shape) != (L.shape[1],) or th.dim() != 2 or th.shape[1] != L.shape[0]:
         raise ValueError("criterion (E1,N), logits (E1,N,K), references (N,), thresholds (V,E1)")
     if float(sign) < 0:
@@ -90,10 +88,9 @@ def rule_sweep(criterion, logits, references, thresholds, patiences, rule, sign:
     acc = torch.empty((V, P), dtype=torch.float64, device=dev)
     mex = torch.empty((V, P), dtype=torch.float64, device=dev)
     hist = torch.empty((V, P, E1), dtype=torch.int32, device=dev) if want_hist else None
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     with torch.cuda.device(dev):
-        capi.check(lib.ee_rule_sweep(p(cf), p(L), p(refs), E1, N, K, p(th), V, pt, P, r.code, p(acc), p(mex), p(hist), _stream()), None,
-                   "ee_rule_sweep")
+        capi.check(lib.ee_rule_sweep(_ptr(cf), _ptr(L), _ptr(refs), E1, N, K, _ptr(th), V, pt, P, r.code, _ptr(acc), _ptr(mex), _ptr(hist),
+                                     _stream()), None, "ee_rule_sweep")
     return acc, mex, hist
 
 
@@ -104,8 +101,7 @@ def lte_sweep(scores, correct, thresholds, want_hist: bool = False, device=None)
     first / last difference the reference's sweep (EE/thresh.py:184-215) has against its policy (EE/policy.py:33).  No kernel of its own.
     ``scores`` (E1,N), ``correct`` (E1,N), ``thresholds`` (V,E1); returns ``(accuracy (V,), mean_exit (V,), hist (V,E1) | None)``."""
     dev = _require_torch_cuda(device)
-    to = lambda x: (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x).to(dev, torch.float64)
-    return threshold_sweep(-to(scores), correct, -to(thresholds), want_hist=want_hist, device=dev)
+    return threshold_sweep(-_f64_on(dev, scores), correct, -_f64_on(dev, thresholds), want_hist=want_hist, device=dev)
 
 
 def threshold_sweep(conf, correct, thresholds, want_hist: bool = False, device=None):
@@ -113,8 +109,7 @@ def threshold_sweep(conf, correct, thresholds, want_hist: bool = False, device=N
     ``(accuracy (V,), mean_exit (V,), hist (V,E1) | None)``."""
     lib = capi.load()
     dev = _require_torch_cuda(device)
-    to = lambda x, dt: (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x).to(dev, dt).contiguous()
-    cf, cr, th = to(conf, torch.float64), to(correct, torch.uint8), to(thresholds, torch.float64)
+    cf, cr, th = _f64_on(dev, conf), _on(dev, correct, torch.uint8), _f64_on(dev, thresholds)
     E1, N = cf.shape
     if th.dim() != 2 or th.shape[1] != E1 or tuple(cr.shape) != (E1, N):
         raise ValueError("conf (E1,N), correct (E1,N), thresholds (V,E1)")
@@ -122,8 +117,7 @@ def threshold_sweep(conf, correct, thresholds, want_hist: bool = False, device=N
     acc = torch.empty((V,), dtype=torch.float64, device=dev)
     mex = torch.empty((V,), dtype=torch.float64, device=dev)
     hist = torch.empty((V, E1), dtype=torch.int32, device=dev) if want_hist else None
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     with torch.cuda.device(dev):
-        capi.check(lib.ee_threshold_sweep(p(cf), p(cr), E1, N, p(th), V, p(acc), p(mex), p(hist), _stream()), None,
+        capi.check(lib.ee_threshold_sweep(_ptr(cf), _ptr(cr), E1, N, _ptr(th), V, _ptr(acc), _ptr(mex), _ptr(hist), _stream()), None,
                    "ee_threshold_sweep")
     return acc, mex, hist

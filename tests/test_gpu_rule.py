@@ -120,6 +120,43 @@ def test_rule_scan_and_policy_vs_restatement(pkg, E1, N, K):
             assert dist == {e: int(counts[e]) / N for e in range(E1)}
 
 
+def test_scans_that_need_no_logits_accept_a_null_pointer(pkg):
+    """The C ABI's null paths, which the Python wrappers never take: ee_lte_scan without predictions and ee_rule_scan under MMEE_RULE_STREAK
+    without predictions read no logits row, so `logits = NULL` is accepted and gives exactly the exits and counts of the call with the logits;
+    MMEE_RULE_EITHER counts argmax agreement and is refused without them.  (3, 70, 4): more than one wave, less than one block, and
+    E1 - 1 = 2 exits that carry a test."""
+    import ctypes as C
+    import torch
+    E1, N, K = 3, 70, 4
+    PAT = [2, 2, 1]                                  # exit 1 is left only where the test held at exit 0 AND exit 1: the streak is carried
+    store, _ = _planted_store(E1, N, K, seed=5)
+    crit = msp_table(store)
+    thr = np.quantile(crit, 0.6, axis=1)
+    lib = pkg.capi.load()
+    logits, table = torch.from_numpy(store).cuda(), torch.from_numpy(crit).cuda()
+    thr_c, pat_c = (C.c_double * E1)(*thr.tolist()), (C.c_int32 * E1)(*PAT)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+
+    def run(call):
+        exits = torch.full((N,), -1, dtype=torch.int32, device="cuda")
+        counts = torch.full((E1,), -1, dtype=torch.int32, device="cuda")
+        rc = call(ptr(exits), ptr(counts))
+        return rc, _np(exits), _np(counts)
+
+    lte = lambda lg: run(lambda ex, cn: lib.ee_lte_scan(ptr(table), ptr(lg), E1, N, K, thr_c, ex, None, cn, stream))
+    rule = lambda lg, r: run(lambda ex, cn: lib.ee_rule_scan(ptr(table), 1.0, ptr(lg), E1, N, K, thr_c, pat_c, r, ex, None, None, cn, stream))
+    for name, with_logits, without in (("ee_lte_scan", lte(logits), lte(None)), ("ee_rule_scan STREAK", rule(logits, STREAK), rule(None, STREAK))):
+        assert with_logits[0] == 0 and without[0] == 0, (name, pkg.capi.last_error())
+        assert np.array_equal(without[1], with_logits[1]) and np.array_equal(without[2], with_logits[2]), name
+        assert without[2].sum() == N and (without[2] > 0).sum() >= 2, (name, without[2])           # the tests decide: not one exit for all
+    assert np.array_equal(lte(None)[1], plain_exits(crit, thr, -1))
+    assert np.array_equal(rule(None, STREAK)[1], rule_exits(crit, store, thr, PAT, STREAK, +1))
+    assert rule(logits, EITHER)[0] == 0
+    rc, exits, _ = rule(None, EITHER)
+    assert rc != 0 and "logits" in pkg.capi.last_error() and (exits == -1).all()
+
+
 # ---- 2. sweep against the restatement ------------------------------------------------------------------------------------------------------
 def _sweep_inputs(E1, N, K, V, seed):
     """Criterion table with duplicate confidences (a twentieth of the entries copy another document's), V threshold vectors at random
