@@ -49,8 +49,22 @@ extern "C" {
 enum { MMEE_EXIT_VISION_AVG = 0, MMEE_EXIT_TEXT_AVG = 1, MMEE_EXIT_TEXT_VISUAL_CONCAT = 2 };
 /* encoder_layer_strategy (EE/models/EE_modules.py:167-172) */
 enum { MMEE_STRATEGY_RAMP = 0, MMEE_STRATEGY_GATE = 1 };
-/* inference_strategy (EE/models/EE_modules.py:116-146): max_confidence exits on crit > thr, entropy on crit < thr, patience as below */
-enum { MMEE_CRIT_MAX_CONFIDENCE = 0, MMEE_CRIT_ENTROPY = 1, MMEE_CRIT_PATIENCE = 2 };
+/* inference_strategy (EE/models/EE_modules.py:116-146): max_confidence exits on crit > thr, entropy on crit < thr, patience and margin as below */
+enum { MMEE_CRIT_MAX_CONFIDENCE = 0, MMEE_CRIT_ENTROPY = 1, MMEE_CRIT_PATIENCE = 2, MMEE_CRIT_MARGIN = 3 };
+/*
+ * MMEE_CRIT_MARGIN (top-1 minus top-2 softmax probability; the third confidence scoring function the reference names, CSF_dict in
+ * EE/large_scale.py:12-18 and EE/thresh.py:55-61, whose own top12_margin_np subtracts the two SMALLEST raw logits and is never called: this
+ * text, not that function, is the specification).  For one document at one exit, z the float32 policy logits and T the exit's temperature:
+ *     x_k = (double)z_k / T,   m1 = max_k x_k,   m2 = the second largest value counting multiplicity (a maximum attained twice: m2 = m1),
+ *     S = sum_k exp(x_k - m1) added in label order k = 0 .. K-1,   margin = (1 - exp(m2 - m1)) / S   in float64.
+ * K = 1: the second probability is 0 and margin = 1.0.  In this form the margin is >= 0 exactly and exactly 0 on a tie; it lies in [0, 1] like the
+ * max-softmax, so thresholds stay comparable.  The test is margin > thr, strict (higher is surer, as for max_confidence); a NaN criterion never
+ * fires; if nothing fires the document leaves at the final exit.  The float32 form -- the same expression in float32 on the head's own logits, no
+ * temperature -- is what the model reports as exit_states[j][1] and the handle as out_head_crit.  Everything else is as for the two other threshold
+ * criteria: per-exit thresholds and temperatures, MMEE_FLAG_NO_EXIT, MMEE_RULE_STREAK / MMEE_RULE_EITHER with the margin test as their event,
+ * use_lte (the criterion then only feeds out_head_crit), captured graphs (the criterion is bound at capture; thresholds and temperatures are read
+ * from the vector of each launch).  It adds no launch: a margin forward issues exactly the launches of its max_confidence twin.
+ */
 /*
  * MMEE_CRIT_PATIENCE (patience-based early exit, PABEE).  Exits e = 0 .. E in the path's order (embedding exits vision, text, concat, then
  * encoder exits ascending, then the final classifier).  p_e(n) = argmax of document n's policy logits at exit e, taken on exactly the float32
@@ -81,7 +95,7 @@ enum { MMEE_CRIT_MAX_CONFIDENCE = 0, MMEE_CRIT_ENTROPY = 1, MMEE_CRIT_PATIENCE =
 /*
  * Exit rules (ee_set_exit_rule): what a handle makes of its criterion / LTE test and PABEE's counter together.  Exits e = 0 .. E in the path's
  * order, E1 = E + 1.  A handle keeps its criterion and its use_lte setting.
- *   Event of exit e: today's test, unchanged.  max_confidence: f_e = crit_e > thr_e; entropy: f_e = crit_e < thr_e; use_lte: f_e = u_e < thr_e
+ *   Event of exit e: today's test, unchanged.  max_confidence, margin: f_e = crit_e > thr_e; entropy: f_e = crit_e < thr_e; use_lte: f_e = u_e < thr_e
  *   (embedding exits never fire under LTE).  All compares strict; crit_e is the float64 criterion on the scaled logits, u_e the float64 score.
  *   Agreement: PABEE's counter exactly as under MMEE_CRIT_PATIENCE: c_0 = 0, c_e = c_{e-1} + 1 if argmax z_e == argmax z_{e-1}, else 0, the
  *   argmax taken on the scaled float32 logits as written out, the first maximum winning.
@@ -354,6 +368,15 @@ int ee_set_attentions_out(ee_handle* h, float* out);
 int ee_policy_scan(const double* logits, int32_t E1, int32_t N, int32_t K, const double* thresholds,
                    int32_t* exits, double* predictions, double* confidence, int32_t* counts, void* stream);
 /*
+ * The same policy under any threshold criterion: criterion is MMEE_CRIT_MAX_CONFIDENCE, MMEE_CRIT_ENTROPY or MMEE_CRIT_MARGIN (patience --
+ * ee_patience_scan -- and unknown codes are refused with a message), computed in float64 from the row as ee_csf_table computes it.  exit(n) = the
+ * first e < E1-1 whose criterion passes thresholds[e] in the criterion's direction (strict: '>' for max_confidence and margin, '<' for entropy),
+ * else E1-1.  Arguments as ee_policy_scan (1 <= E1 <= 256); confidence = the criterion at the chosen exit.  With MMEE_CRIT_MAX_CONFIDENCE it is
+ * ee_policy_scan bit for bit.  Needs no table workspace.
+ */
+int ee_criterion_scan(const double* logits, int32_t E1, int32_t N, int32_t K, int32_t criterion, const double* thresholds, int32_t* exits,
+                      double* predictions, double* confidence, int32_t* counts, void* stream);
+/*
  * The patience policy (MMEE_CRIT_PATIENCE semantics) on a dumped logits array: logits dev double (E1,N,K), patience >= 1.  p_e is the argmax
  * of the float64 row (first maximum).  exits dev int32 (N,), predictions dev double (N,K) or NULL (the row of the chosen exit), confidence
  * dev double (N,) or NULL (its float64 max-softmax), counts dev int32 [E1] or NULL (documents per exit).
@@ -369,7 +392,7 @@ int ee_patience_scan(const double* logits, int32_t E1, int32_t N, int32_t K, int
 int ee_lte_scan(const double* scores, const double* logits, int32_t E1, int32_t N, int32_t K, const double* thresholds, int32_t* exits,
                 double* predictions, int32_t* counts, void* stream);
 /*
- * MMEE_RULE_STREAK / MMEE_RULE_EITHER on dumped arrays.  criterion dev double (E1,N): the criterion table (max-softmax: ee_msp_table; entropy)
+ * MMEE_RULE_STREAK / MMEE_RULE_EITHER on dumped arrays.  criterion dev double (E1,N): the criterion table (ee_csf_table; max-softmax: ee_msp_table)
  * or the LTE scores; sign +1: the event is criterion > threshold (max_confidence), -1: criterion < threshold (entropy, LTE; rows of embedding
  * exits hold 1.0 under LTE, which no threshold <= 1 releases).  logits dev double (E1,N,K) for the agreement counter (argmax of the float64
  * row, first maximum) and the predictions; may be NULL under MMEE_RULE_STREAK with predictions NULL.  thresholds host double [E1], patience
@@ -426,6 +449,13 @@ int ee_threshold_sweep(const double* conf, const uint8_t* correct, int32_t E1, i
  * correct[e,n] = (argmax_k logits[e,n,k] == references[n]).  logits dev double (E1,N,K); references dev int64 (N,) or NULL
  * with correct NULL. */
 int ee_msp_table(const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, double* conf,
+                 uint8_t* correct, void* stream);
+/* The table of any of the three confidence scoring functions (CSF_dict, EE/thresh.py:55-61), for ee_threshold_sweep, ee_rule_scan and
+ * ee_rule_sweep: criterion MMEE_CRIT_MAX_CONFIDENCE (ee_msp_table bit for bit), MMEE_CRIT_ENTROPY (the reference's expression log A - B / A with
+ * A = sum e^z, B = sum z e^z, no max shift, EE/thresh.py:41-45; LOWER is surer: sweep it negated, scan it with sign -1) or MMEE_CRIT_MARGIN (above,
+ * T = 1).  Patience and unknown codes are refused with a message.  logits dev double (E1,N,K), table dev double (E1,N), correct dev uint8 (E1,N) or
+ * NULL, references dev int64 (N,) (may be NULL with correct NULL). */
+int ee_csf_table(const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, int32_t criterion, double* table,
                  uint8_t* correct, void* stream);
 
 /*

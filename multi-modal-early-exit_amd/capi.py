@@ -19,7 +19,7 @@ FLAG_PROBE_ALWAYS = 8
 FLAG_XPROBE = 16
 FLAG_ONE_TERM = 32
 FLAG_LOW_LATENCY = 64
-CRIT_MAX_CONFIDENCE, CRIT_ENTROPY, CRIT_PATIENCE = 0, 1, 2
+CRIT_MAX_CONFIDENCE, CRIT_ENTROPY, CRIT_PATIENCE, CRIT_MARGIN = 0, 1, 2, 3
 RULE_PLAIN, RULE_STREAK, RULE_EITHER = 0, 1, 2
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 CLOCK_STAMP_WORDS = 4096       # MMEE_CLOCK_STAMP_WORDS
@@ -90,6 +90,7 @@ SYMBOLS = {
     "ee_set_head_mask": (C.c_int, [_vp, _vp]),
     "ee_set_attentions_out": (C.c_int, [_vp, _vp]),
     "ee_policy_scan": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _vp]),
+    "ee_criterion_scan": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _vp]),
     "ee_patience_scan": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ee_lte_scan": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _vp, _vp, _vp]),
     "ee_rule_scan": (C.c_int, [_vp, C.c_double, _vp, _i32, _i32, _i32, C.POINTER(C.c_double), C.POINTER(_i32), _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -99,6 +100,7 @@ SYMBOLS = {
     "ee_unpack_results": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ee_threshold_sweep": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "ee_msp_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ee_csf_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_debug_gemm": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_debug_gemm_split": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp,
                                       _i32, _i32, C.POINTER(C.c_float), _vp]),

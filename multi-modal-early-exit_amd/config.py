@@ -41,10 +41,12 @@ class EarlyExitInference(_StrEnum):
     ENTROPY = "entropy"
     PATIENCE = "patience"
     LTE = "lte"
+    MARGIN = "margin"                                   # top-1 minus top-2 softmax probability (include/mmee.h MMEE_CRIT_MARGIN)
 
     def get_sign(self) -> Callable:
-        # EE/models/EE_modules.py:137-144: max_confidence exits when crit > thr, entropy when crit < thr; patience has no threshold
-        if self == EarlyExitInference.MAX_CONFIDENCE:
+        # EE/models/EE_modules.py:137-144: max_confidence exits when crit > thr, entropy when crit < thr; patience has no threshold;
+        # margin is a confidence like max_confidence (higher is surer)
+        if self in (EarlyExitInference.MAX_CONFIDENCE, EarlyExitInference.MARGIN):
             return operator.gt
         if self == EarlyExitInference.ENTROPY:
             return operator.lt
@@ -59,6 +61,8 @@ class EarlyExitInference(_StrEnum):
             return 1
         if self == EarlyExitInference.PATIENCE:
             return 2
+        if self == EarlyExitInference.MARGIN:
+            return 3
         raise NotImplementedError(f"{self} not implemented")
 
 

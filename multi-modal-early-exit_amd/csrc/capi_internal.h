@@ -14,6 +14,9 @@
 #include "../../include/mmee.h"
 #include "mmee_kernels.h"
 
+static_assert(mmee::CRIT_MAX_CONFIDENCE == MMEE_CRIT_MAX_CONFIDENCE && mmee::CRIT_ENTROPY == MMEE_CRIT_ENTROPY &&
+              mmee::CRIT_PATIENCE == MMEE_CRIT_PATIENCE && mmee::CRIT_MARGIN == MMEE_CRIT_MARGIN, "the kernels' criterion codes are the ABI's");
+
 namespace mmee {
 namespace capi {
 

@@ -121,7 +121,7 @@ int ee_set_attentions_out(ee_handle* h, float* out) {
 
 int ee_set_criterion(ee_handle* h, int32_t criterion) {
     if (!h) return 1;
-    if (criterion != MMEE_CRIT_MAX_CONFIDENCE && criterion != MMEE_CRIT_ENTROPY && criterion != MMEE_CRIT_PATIENCE)
+    if (criterion != MMEE_CRIT_MAX_CONFIDENCE && criterion != MMEE_CRIT_ENTROPY && criterion != MMEE_CRIT_PATIENCE && criterion != MMEE_CRIT_MARGIN)
         return fail(h, "ee_set_criterion: unknown criterion %d", criterion);
     if (criterion == MMEE_CRIT_PATIENCE && h->cfg.use_lte)
         return fail(h, "ee_set_criterion: MMEE_CRIT_PATIENCE on a use_lte handle: learning-to-exit and patience are two exit decisions");

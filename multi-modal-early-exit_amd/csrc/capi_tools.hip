@@ -102,6 +102,26 @@ int ee_policy_scan(const double* logits, int32_t E1, int32_t N, int32_t K, const
     return launch_status(nullptr, "ee_policy_scan");
 }
 
+int ee_criterion_scan(const double* logits, int32_t E1, int32_t N, int32_t K, int32_t criterion, const double* thresholds, int32_t* exits,
+                      double* predictions, double* confidence, int32_t* counts, void* stream) {
+    if (!thresholds || E1 < 1 || E1 > 256 || N < 0 || K < 1 || (N > 0 && (!logits || !exits)))
+        return fail(nullptr, "ee_criterion_scan: bad argument (1 <= E1 <= 256, N >= 0, K >= 1, logits / thresholds / exits not NULL)");
+    if (criterion != MMEE_CRIT_MAX_CONFIDENCE && criterion != MMEE_CRIT_ENTROPY && criterion != MMEE_CRIT_MARGIN)
+        return fail(nullptr, "ee_criterion_scan: criterion %d is not a threshold criterion (MMEE_CRIT_MAX_CONFIDENCE, _ENTROPY, _MARGIN; "
+                             "patience: ee_patience_scan)", criterion);
+    if (!have_device("ee_criterion_scan")) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const TempUpload<double> thr(thresholds, E1, s);
+    if (thr.err) return fail(nullptr, "ee_criterion_scan: threshold %s", thr.err);
+    if (counts && hipMemsetAsync(counts, 0, sizeof(int) * E1, s) != hipSuccess) return fail(nullptr, "ee_criterion_scan: memset failed");
+    ScanArgs a{};
+    a.logits = logits; a.sign = crit_sign(criterion); a.thr = thr.dev; a.E1 = E1; a.N = N; a.K = K;
+    a.exits = exits; a.pred = predictions; a.conf = confidence; a.counts = counts;
+    const int event = criterion == MMEE_CRIT_ENTROPY ? SCAN_ENTROPY : criterion == MMEE_CRIT_MARGIN ? SCAN_MARGIN : SCAN_MSP;
+    if (N > 0) launch_exit_scan(a, event, RULE_PLAIN, s);
+    return launch_status(nullptr, "ee_criterion_scan");
+}
+
 int ee_patience_scan(const double* logits, int32_t E1, int32_t N, int32_t K, int32_t patience, int32_t* exits, double* predictions,
                      double* confidence, int32_t* counts, void* stream) {
     if (patience < 1 || E1 < 1 || N < 0 || K < 1 || (N > 0 && (!logits || !exits))) return fail(nullptr, "ee_patience_scan: bad argument");
@@ -211,8 +231,20 @@ int ee_msp_table(const double* logits, const int64_t* references, int32_t E1, in
                  void* stream) {
     if (!logits || !conf || E1 < 1 || N < 1 || K < 1) return fail(nullptr, "ee_msp_table: bad argument");
     if (!have_device("ee_msp_table")) return 1;
-    launch_msp_table(logits, (const long long*)references, E1, N, K, conf, correct, reinterpret_cast<hipStream_t>(stream));
+    launch_csf_table(logits, (const long long*)references, E1, N, K, MMEE_CRIT_MAX_CONFIDENCE, conf, correct, reinterpret_cast<hipStream_t>(stream));
     return launch_status(nullptr, "ee_msp_table");
+}
+
+int ee_csf_table(const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, int32_t criterion, double* table,
+                 uint8_t* correct, void* stream) {
+    if (!logits || !table || E1 < 1 || N < 1 || K < 1 || (correct && !references))
+        return fail(nullptr, "ee_csf_table: bad argument (logits / table not NULL, E1, N, K >= 1, correct needs the references)");
+    if (criterion != MMEE_CRIT_MAX_CONFIDENCE && criterion != MMEE_CRIT_ENTROPY && criterion != MMEE_CRIT_MARGIN)
+        return fail(nullptr, "ee_csf_table: criterion %d has no table (MMEE_CRIT_MAX_CONFIDENCE, _ENTROPY, _MARGIN have; patience is no "
+                             "function of one row)", criterion);
+    if (!have_device("ee_csf_table")) return 1;
+    launch_csf_table(logits, (const long long*)references, E1, N, K, criterion, table, correct, reinterpret_cast<hipStream_t>(stream));
+    return launch_status(nullptr, "ee_csf_table");
 }
 
 int ee_temperature_fit(const double* logits, const int64_t* labels, int32_t E1, int32_t N, int32_t K, int32_t max_iter,

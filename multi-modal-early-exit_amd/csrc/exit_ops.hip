@@ -1,5 +1,5 @@
 // The handle-free tools on dumped (E1, N, K) arrays: the exit policies as one scan kernel, the patience / threshold / rule sweeps, the
-// max-softmax table, the temperature fit, and result packing.  (The forward pass's own exit stage: exit_stage.hip.)
+// criterion tables (max-softmax, entropy, margin), the temperature fit, and result packing.  (The forward pass's own exit stage: exit_stage.hip.)
 //
 // What this replaces in the reference:
 //   * Policy.max_confidence_global_thresholding_policy / accuracy_calibration_heuristic (EE/policy.py:28-45, 87-104): the nested Python loop
@@ -19,6 +19,39 @@ __device__ __forceinline__ double max_softmax_f64(const double* z, int K) {
     return 1.0 / s;
 }
 
+// float64 entropy of one row, the reference's expression: log A - B / A with A = sum e^z, B = sum z e^z, no max shift (EE/thresh.py:41-45)
+__device__ __forceinline__ double entropy_f64(const double* z, int K) {
+    double A = 0.0, B = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const double e = exp(z[k]);
+        A += e;
+        B += z[k] * e;
+    }
+    return log(A) - B / A;
+}
+
+// float64 margin of one row (MMEE_CRIT_MARGIN, include/mmee.h): (1 - exp(m2 - m1)) / S, m1 the maximum, m2 the second largest value counting
+// multiplicity (the pass that finds the maximum keeps both), S = sum_k exp(z_k - m1) in label order.  >= 0, exactly 0 on a tie, 1 when K = 1
+__device__ __forceinline__ double margin_f64(const double* z, int K) {
+    double m1 = z[0], m2 = -INFINITY;
+    for (int k = 1; k < K; ++k) {
+        m2 = z[k] > m1 ? m1 : fmax(m2, z[k]);
+        m1 = fmax(m1, z[k]);
+    }
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) s += exp(z[k] - m1);
+    return (1.0 - exp(m2 - m1)) / s;
+}
+
+// the criterion a scan event computes from the row itself
+template <int EVENT>
+__device__ __forceinline__ double row_crit_f64(const double* z, int K) {
+    static_assert(EVENT == SCAN_MSP || EVENT == SCAN_ENTROPY || EVENT == SCAN_MARGIN, "events that read the logits row");
+    if constexpr (EVENT == SCAN_ENTROPY) return entropy_f64(z, K);
+    else if constexpr (EVENT == SCAN_MARGIN) return margin_f64(z, K);
+    else return max_softmax_f64(z, K);
+}
+
 // argmax of one float64 row, first maximum (as numpy)
 __device__ __forceinline__ int argmax_f64(const double* z, int K) {
     double m = z[0];
@@ -32,11 +65,12 @@ __device__ __forceinline__ int argmax_f64(const double* z, int K) {
 // The exit decision on dumped arrays (ee_policy_scan, ee_patience_scan, ee_lte_scan, ee_rule_scan): thread per document, exits in order,
 // the first e < E1 - 1 that qualifies, else the final exit E1 - 1, whose own test and patience are never looked at.
 //   event      f_e = sign * crit_e > sign * thr[e]   (sign = +1: confidence, strict '>'; -1: entropy / LTE score, strict '<'; negation is exact)
-//              crit_e: SCAN_MSP the float64 max-softmax of the row, SCAN_TABLE crit[e][n], SCAN_NONE no event
+//              crit_e: SCAN_MSP / SCAN_ENTROPY / SCAN_MARGIN the float64 max-softmax / entropy / margin of the row, SCAN_TABLE crit[e][n],
+//              SCAN_NONE no event
 //   agreement  c_e (PABEE): p_e = argmax_k logits[e][n][k] (first maximum), c_0 = 0, c_e = p_e == p_{e-1} ? c_{e-1} + 1 : 0
 //   RULE_PLAIN: f_e;   RULE_STREAK: s_e = f_e ? s_{e-1} + 1 : 0, s_e >= pat[e];   RULE_EITHER: f_e or c_e >= pat[e];   RULE_AGREE: c_e >= pat[e]
-// confidence = SCAN_TABLE: crit at the chosen exit; else the float64 max-softmax of the chosen row.  The logits are read only where the
-// instantiation needs a row (SCAN_MSP, the agreement, pred, SCAN_NONE's confidence): they may be null otherwise.
+// confidence = the event's criterion at the chosen exit; SCAN_NONE: the float64 max-softmax of the chosen row.  The logits are read only where the
+// instantiation needs a row (the row events, the agreement, pred, SCAN_NONE's confidence): they may be null otherwise.
 // ---------------------------------------------------------------------------------------------------------------
 template <int EVENT, int RULE>
 __global__ __launch_bounds__(256) void exit_scan_kernel(ScanArgs a) {
@@ -48,7 +82,8 @@ __global__ __launch_bounds__(256) void exit_scan_kernel(ScanArgs a) {
         for (int e = 0; e < a.E1 - 1; ++e) {
             bool leave = false;
             if constexpr (EVENT != SCAN_NONE) {
-                crit = EVENT == SCAN_MSP ? max_softmax_f64(row(e), a.K) : a.crit[(size_t)e * a.N + n];
+                if constexpr (EVENT == SCAN_TABLE) crit = a.crit[(size_t)e * a.N + n];
+                else crit = row_crit_f64<EVENT>(row(e), a.K);
                 leave = a.sign * crit > a.sign * a.thr[e];
             }
             if constexpr (RULE != RULE_PLAIN) {
@@ -68,7 +103,8 @@ __global__ __launch_bounds__(256) void exit_scan_kernel(ScanArgs a) {
         a.exits[n] = chosen;
         if (a.conf) {
             if constexpr (EVENT == SCAN_TABLE) a.conf[n] = a.crit[(size_t)chosen * a.N + n];
-            else a.conf[n] = (EVENT == SCAN_MSP && chosen < a.E1 - 1) ? crit : max_softmax_f64(row(chosen), a.K);
+            else if constexpr (EVENT == SCAN_NONE) a.conf[n] = max_softmax_f64(row(chosen), a.K);
+            else a.conf[n] = chosen < a.E1 - 1 ? crit : row_crit_f64<EVENT>(row(chosen), a.K);
         }
         if (a.pred) {
             const double* z = row(chosen);
@@ -78,9 +114,11 @@ __global__ __launch_bounds__(256) void exit_scan_kernel(ScanArgs a) {
     }
 }
 
-// the five (event, rule) pairs the entry points ask for
+// the seven (event, rule) pairs the entry points ask for
 void launch_exit_scan(const ScanArgs& a, int event, int rule, hipStream_t s) {
-    void (*k)(ScanArgs) = event == SCAN_MSP    ? exit_scan_kernel<SCAN_MSP, RULE_PLAIN>
+    void (*k)(ScanArgs) = event == SCAN_MSP       ? exit_scan_kernel<SCAN_MSP, RULE_PLAIN>
+                          : event == SCAN_ENTROPY ? exit_scan_kernel<SCAN_ENTROPY, RULE_PLAIN>
+                          : event == SCAN_MARGIN ? exit_scan_kernel<SCAN_MARGIN, RULE_PLAIN>
                           : event == SCAN_NONE ? exit_scan_kernel<SCAN_NONE, RULE_AGREE>
                           : rule == RULE_PLAIN ? exit_scan_kernel<SCAN_TABLE, RULE_PLAIN>
                           : rule == RULE_STREAK ? exit_scan_kernel<SCAN_TABLE, RULE_STREAK>
@@ -604,8 +642,10 @@ bool launch_rule_sweep(const double* conf, const double* logits, const long long
     return true;
 }
 
-// conf[e][n] = max softmax (f64) of logits[e][n][:], correct[e][n] = (argmax == reference[n])   (first maximum wins, as numpy)
-__global__ __launch_bounds__(256) void msp_table_kernel(const double* __restrict__ logits, const long long* __restrict__ refs,
+// The criterion table of the sweeps and rule scans (ee_csf_table; ee_msp_table is its CRIT_MAX_CONFIDENCE instantiation):
+// table[e][n] = max softmax / entropy / margin (f64) of logits[e][n][:], correct[e][n] = (argmax == reference[n])   (first maximum wins, as numpy)
+template <int CRIT>
+__global__ __launch_bounds__(256) void csf_table_kernel(const double* __restrict__ logits, const long long* __restrict__ refs,
                                                         int E1, int N, int K, double* __restrict__ conf,
                                                         unsigned char* __restrict__ correct) {
     const size_t total = (size_t)E1 * N;
@@ -615,16 +655,25 @@ __global__ __launch_bounds__(256) void msp_table_kernel(const double* __restrict
         int am = 0;
         for (int k = 1; k < K; ++k)
             if (z[k] > m) { m = z[k]; am = k; }
-        double s = 0.0;
-        for (int k = 0; k < K; ++k) s += exp(z[k] - m);
-        conf[i] = 1.0 / s;
+        if constexpr (CRIT == CRIT_MAX_CONFIDENCE) {
+            double s = 0.0;
+            for (int k = 0; k < K; ++k) s += exp(z[k] - m);
+            conf[i] = 1.0 / s;
+        } else if constexpr (CRIT == CRIT_ENTROPY) {
+            conf[i] = entropy_f64(z, K);
+        } else {
+            conf[i] = margin_f64(z, K);
+        }
         if (correct) correct[i] = refs ? (unsigned char)(refs[i % N] == am) : 0;
     }
 }
 
-void launch_msp_table(const double* logits, const long long* refs, int E1, int N, int K, double* conf, unsigned char* correct,
+void launch_csf_table(const double* logits, const long long* refs, int E1, int N, int K, int criterion, double* table, unsigned char* correct,
                       hipStream_t s) {
-    hipLaunchKernelGGL(msp_table_kernel, dim3(grid_1d((long long)E1 * N, 256, 4096)), dim3(256), 0, s, logits, refs, E1, N, K, conf, correct);
+    void (*k)(const double*, const long long*, int, int, int, double*, unsigned char*) =
+        criterion == CRIT_ENTROPY ? csf_table_kernel<CRIT_ENTROPY> : criterion == CRIT_MARGIN ? csf_table_kernel<CRIT_MARGIN>
+                                                                                                : csf_table_kernel<CRIT_MAX_CONFIDENCE>;
+    hipLaunchKernelGGL(k, dim3(grid_1d((long long)E1 * N, 256, 4096)), dim3(256), 0, s, logits, refs, E1, N, K, table, correct);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,7 @@
 //
 // What this replaces in the reference:
 //   * LayoutLMv3Exit.out_proj (EE/models/LayoutLMv3.py:92) / classifier.out_proj (HF:821) : head_out_kernel
-//   * max_confidence / entropy criteria (EE/models/EE_modules.py:149-160)                   : crit_f32 / crit_f64
+//   * max_confidence / entropy criteria (EE/models/EE_modules.py:149-160), and the margin   : crit_f32 / crit_f64
 //   * Policy.max_confidence_global_thresholding_policy / accuracy_calibration_heuristic (EE/policy.py:28-45, 87-104):
 //     the nested Python loop "first exit whose float64 max-softmax is strictly above its threshold, else the last"
 //     becomes exit_decide_kernel inside the forward pass: documents that satisfy the test are scattered to the
@@ -79,14 +79,26 @@ void launch_head_out(const HeadOutArgs& a, int max_docs, hipStream_t s) {
 // ---------------------------------------------------------------------------------------------------------------
 // criteria
 // ---------------------------------------------------------------------------------------------------------------
+// Margin (MMEE_CRIT_MARGIN; include/mmee.h): top-1 minus top-2 softmax probability, (1 - exp(m2 - m1)) / S with m1 the maximum, m2 the second
+// largest value counting multiplicity and S = sum_k exp(x_k - m1) in label order.  m1 and S are the max-softmax's own two passes; m2 comes from a
+// third pass that skips ONE label holding m1 (no exp inside it: the decide kernels sit at their register limit in the second pass, and a value
+// kept live through it went to scratch).  K = 1: m2 = -inf, exp = 0, margin 1.
 // float32, as the model computes exit_states[j][1] (EE/models/EE_modules.py:149-160)
 __device__ inline float crit_f32(const float* z, int K, int criterion) {
-    if (criterion == 0) {
+    if (criterion != CRIT_ENTROPY) {
         float m = z[0];
         for (int k = 1; k < K; ++k) m = fmaxf(m, z[k]);
         float s = 0.f;
         for (int k = 0; k < K; ++k) s += expf(z[k] - m);
-        return 1.0f / s;
+        if (criterion != CRIT_MARGIN) return 1.0f / s;
+        float m2 = -INFINITY;
+        bool seen = false;
+        for (int k = 0; k < K; ++k) {
+            const bool first = z[k] == m && !seen;
+            seen = seen || first;
+            m2 = first ? m2 : fmaxf(m2, z[k]);
+        }
+        return (1.0f - expf(m2 - m)) / s;
     }
     float A = 0.f, B = 0.f;                       // entropy: log(sum e^x) - sum(x e^x)/sum(e^x), no max shift
     for (int k = 0; k < K; ++k) {
@@ -99,12 +111,21 @@ __device__ inline float crit_f32(const float* z, int K, int criterion) {
 
 // float64 on (double)logit / T, as the policy computes it (scipy.special.softmax on the float64 store, EE/policy.py:30-32)
 __device__ inline double crit_f64(const float* z, int K, double temp, int criterion) {
-    if (criterion == 0) {
+    if (criterion != CRIT_ENTROPY) {
         double m = (double)z[0] / temp;
         for (int k = 1; k < K; ++k) m = fmax(m, (double)z[k] / temp);
         double s = 0.0;
         for (int k = 0; k < K; ++k) s += exp((double)z[k] / temp - m);
-        return 1.0 / s;
+        if (criterion != CRIT_MARGIN) return 1.0 / s;
+        double m2 = -INFINITY;
+        bool seen = false;
+        for (int k = 0; k < K; ++k) {
+            const double x = (double)z[k] / temp;
+            const bool first = x == m && !seen;
+            seen = seen || first;
+            m2 = first ? m2 : fmax(m2, x);
+        }
+        return (1.0 - exp(m2 - m)) / s;
     }
     double A = 0.0, B = 0.0;
     for (int k = 0; k < K; ++k) {
@@ -127,7 +148,7 @@ __device__ inline double crit_f64(const float* z, int K, double temp, int criter
 // exit 0, which every document reaches (no reset launch).
 // LTE (ee_config.use_lte): the test is "the float64 score head_out_lte_kernel left in a.lte_score is strictly below the threshold"; the score
 // is what the outputs carry as the criterion.  Embedding exits have no score (a.lte_score null): 1.0, nobody leaves.
-// The max_confidence / entropy kernel is the DECIDE_THRESHOLD instantiation.
+// The max_confidence / entropy / margin kernel is the DECIDE_THRESHOLD instantiation.
 // RULE (ee_set_exit_rule; THRESHOLD and LTE modes): the mode's test is the EVENT f_e and the rule decides on it.  MMEE_RULE_STREAK: the event
 // must have held at t_e exits in a row (s_e = f_e ? s_{e-1} + 1 : 0 in p.run[orig]).  MMEE_RULE_EITHER: the event, or PABEE's counter
 // c_e >= t_e ((p.prev[orig], p.run[orig]) exactly as under PATIENCE).  The same state arrays, written unconditionally at exit 0; t_e is the
@@ -176,14 +197,14 @@ __device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const Pati
             double crit;
             bool leave;
             if constexpr (PATIENCE) {
-                crit = crit_f64(z, a.K, temp, 0);
+                crit = crit_f64(z, a.K, temp, CRIT_MAX_CONFIDENCE);
                 leave = agreement_run(z, a.K, temp, a.exit_index, orig, p) >= patience;
             } else if constexpr (MODE == DECIDE_LTE) {
                 crit = a.lte_score ? a.lte_score[i] : 1.0;
                 leave = a.lte_score && crit < thr;                        // strict, EE/models/LayoutLMv3.py:262
             } else {
                 crit = crit_f64(z, a.K, temp, a.criterion);
-                leave = a.criterion == 0 ? (crit > thr) : (crit < thr);   // strict, EE/policy.py:33
+                leave = crit_fires(a.criterion, crit, thr);               // strict, EE/policy.py:33
             }
             if constexpr (RULE == RULE_STREAK) {
                 const int streak = leave ? (a.exit_index > 0 ? p.run[orig] : 0) + 1 : 0;
@@ -207,7 +228,7 @@ __device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const Pati
             }
             if (a.head_logits && a.out_head_crit)
                 a.out_head_crit[(size_t)a.exit_index * a.B + orig] =
-                    crit_f32(a.head_logits + (size_t)i * a.Kh, a.Kh, PATIENCE ? 0 : a.criterion);
+                    crit_f32(a.head_logits + (size_t)i * a.Kh, a.Kh, PATIENCE ? CRIT_MAX_CONFIDENCE : a.criterion);
             if (leave) {
                 if (a.out_logits)
                     for (int k = 0; k < a.K; ++k) a.out_logits[(size_t)orig * a.K + k] = (float)((double)z[k] / temp);

@@ -116,14 +116,21 @@ struct PatienceArgs {
     int* run;                        // [max_docs] run counter c_e (MMEE_RULE_STREAK: the streak s_e), by original slot
 };
 
+// ee_config.criterion (include/mmee.h MMEE_CRIT_*; capi_internal.h asserts the values agree)
+enum { CRIT_MAX_CONFIDENCE = 0, CRIT_ENTROPY = 1, CRIT_PATIENCE = 2, CRIT_MARGIN = 3 };
+// the direction of a threshold criterion: max-softmax and margin leave on crit > thr, entropy on crit < thr; strict, so a NaN never fires
+__host__ __device__ inline bool crit_fires(int criterion, double crit, double thr) { return criterion == CRIT_ENTROPY ? crit < thr : crit > thr; }
+__host__ __device__ inline double crit_sign(int criterion) { return criterion == CRIT_ENTROPY ? -1.0 : 1.0; }
+
 // how launch_decide picks its kernel: the exit test (MODE) and the rule built on it (RULE = MMEE_RULE_*; DECIDE_PATIENCE takes RULE_PLAIN only)
 enum { DECIDE_THRESHOLD = 0, DECIDE_PATIENCE = 1, DECIDE_LTE = 2 };
 enum { RULE_PLAIN = 0, RULE_STREAK = 1, RULE_EITHER = 2, RULE_AGREE = 3 };      // RULE_AGREE: PABEE's counter alone (exit_scan_kernel only)
 
 // exit_scan_kernel<EVENT, RULE>: the exit decision on dumped arrays (ee_policy_scan, ee_patience_scan, ee_lte_scan, ee_rule_scan)
-enum { SCAN_MSP = 0, SCAN_TABLE = 1, SCAN_NONE = 2 };      // the event's criterion: float64 max-softmax of the logits row, crit[e][n], no event
+// the event's criterion: float64 max-softmax of the logits row, crit[e][n], no event, float64 entropy / margin of the logits row
+enum { SCAN_MSP = 0, SCAN_TABLE = 1, SCAN_NONE = 2, SCAN_ENTROPY = 3, SCAN_MARGIN = 4 };
 struct ScanArgs {
-    const double* logits;            // (E1,N,K); read for SCAN_MSP, RULE_EITHER, RULE_AGREE and for `pred` only: may be null otherwise
+    const double* logits;            // (E1,N,K); read for SCAN_MSP / _ENTROPY / _MARGIN, RULE_EITHER, RULE_AGREE and for `pred` only: may be null otherwise
     const double* crit;              // (E1,N) SCAN_TABLE's criterion
     double sign;                     // the event is sign * criterion > sign * thr[e] (+1: '>', -1: '<'; multiplying by +-1 is exact)
     const double* thr;               // [E1] on the device; null for SCAN_NONE
@@ -132,7 +139,7 @@ struct ScanArgs {
     int E1, N, K;
     int* exits;                      // (N)
     double* pred;                    // (N,K) or null: the logits row of the chosen exit
-    double* conf;                    // (N) or null: SCAN_TABLE: crit at the chosen exit, else the float64 max-softmax of its row
+    double* conf;                    // (N) or null: the event's criterion at the chosen exit (SCAN_NONE: the float64 max-softmax of its row)
     int* counts;                     // [E1] or null, zeroed by the caller
 };
 
@@ -210,7 +217,8 @@ bool launch_patience_sweep(const double* logits, const long long* refs, int E1, 
                            double* mean_exit, int* hist, hipStream_t s);
 void launch_threshold_sweep(const double* conf, const unsigned char* correct, int E1, int N, const double* thr, int V,
                             double* acc, double* mean_exit, int* hist, hipStream_t s);
-void launch_msp_table(const double* logits, const long long* refs, int E1, int N, int K, double* conf, unsigned char* correct,
+// criterion: CRIT_MAX_CONFIDENCE, CRIT_ENTROPY or CRIT_MARGIN
+void launch_csf_table(const double* logits, const long long* refs, int E1, int N, int K, int criterion, double* table, unsigned char* correct,
                       hipStream_t s);
 void launch_temperature_fit(const double* logits, const long long* labels, int E1, int N, int K, int max_iter, double* T_out,
                             double* nll_out, double* acc_out, double* conf_out, int* iters_out, hipStream_t s);

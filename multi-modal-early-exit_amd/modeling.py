@@ -157,12 +157,21 @@ class LayoutLMv3EEForSequenceClassification:
         return ((k, v) for k, v in self._weights.items())
 
     def exit_criterion(self, logits):
-        """``max_confidence`` / ``entropy`` on a logits tensor (EE/models/EE_modules.py:149-160).  Patience has no per-exit criterion
-        (the reference's ``get_function`` has none for it, EE/models/EE_modules.py:130-137): ``NotImplementedError``."""
+        """``max_confidence`` / ``entropy`` on a logits tensor (EE/models/EE_modules.py:149-160), and ``margin`` (include/mmee.h
+        MMEE_CRIT_MARGIN: top-1 minus top-2 softmax probability as ``(1 - exp(m2 - m1)) / S``, exactly 0 on a tie, 1 for a single label).
+        Patience has no per-exit criterion (the reference's ``get_function`` has none for it, EE/models/EE_modules.py:130-137):
+        ``NotImplementedError``."""
         self._sync_exit_config()
         self._refuse_patience("exit_criterion")
-        if str(self.model_config.exit_config.inference_strategy) == "max_confidence":
+        strategy = str(self.model_config.exit_config.inference_strategy)
+        if strategy == "max_confidence":
             return torch.softmax(logits, dim=1).max(dim=1)[0]
+        if strategy == "margin":
+            if logits.shape[1] == 1:
+                return torch.ones_like(logits[:, 0])
+            top = torch.topk(logits, 2, dim=1)[0]
+            s = torch.exp(logits - top[:, :1]).sum(1)
+            return (1.0 - torch.exp(top[:, 1] - top[:, 0])) / s
         e = torch.exp(logits)
         return torch.log(e.sum(1)) - (logits * e).sum(1) / e.sum(1)
 

@@ -69,6 +69,33 @@ def policy_scan_device(logits, thresholds, device=None, want_conf: bool = False)
                      lambda exits, pred, conf, counts, stream: lib.ee_policy_scan(_ptr(L), E1, N, K, thr_c, exits, pred, conf, counts, stream))
 
 
+def threshold_criterion(criterion):
+    """``criterion`` ("max_confidence" / "entropy" / "margin", or the enum) as an ``EarlyExitInference`` that has a threshold test on one
+    logits row; patience, lte and unknown names are a ``ValueError``."""
+    from .config import EarlyExitInference
+    st = criterion if isinstance(criterion, EarlyExitInference) else EarlyExitInference(str(criterion))
+    if st not in (EarlyExitInference.MAX_CONFIDENCE, EarlyExitInference.ENTROPY, EarlyExitInference.MARGIN):
+        raise ValueError(f'criterion "{st}" is not a threshold criterion on a logits row: choose "max_confidence", "entropy" or "margin"')
+    return st
+
+
+def criterion_scan_device(logits, thresholds, criterion, device=None, want_conf: bool = False):
+    """``policy_scan_device`` under any threshold criterion (ee_criterion_scan): the first exit whose float64 ``criterion`` ("max_confidence",
+    "entropy", "margin"; include/mmee.h) strictly passes its threshold in the criterion's direction (``>``; entropy ``<``), else the last exit.
+    Same inputs and returns; the confidence is the criterion at the chosen exit.  "max_confidence" is ``policy_scan_device`` bit for bit."""
+    st = threshold_criterion(criterion)
+    lib = capi.load()
+    dev = _require_torch_cuda(device)
+    L = _f64_on(dev, logits)
+    if L.dim() != 3:
+        raise ValueError("logits must have shape (num_exits + 1, num_samples, num_labels)")
+    E1, N, K = L.shape
+    thr_c = _threshold_vector(thresholds, E1)
+    return _run_scan("ee_criterion_scan", dev, L.shape, want_conf,
+                     lambda exits, pred, conf, counts, stream: lib.ee_criterion_scan(_ptr(L), E1, N, K, st.code, thr_c, exits, pred, conf, counts,
+                                                                                     stream))
+
+
 def patience_scan_device(logits, patience: int, device=None, want_conf: bool = False):
     """Patience (include/mmee.h MMEE_CRIT_PATIENCE) on a dumped array: the first exit where the argmax has stayed the same for ``patience``
     exits in a row, else the last exit.  Same inputs and returns as ``policy_scan_device`` (ee_patience_scan)."""
@@ -133,15 +160,18 @@ class Policy:
         self.logits = logits
         self.config = config
 
-    def _finish(self, thresholds=None, patience=None, lte_scores=None, rule=None):
+    def _finish(self, thresholds=None, patience=None, lte_scores=None, rule=None, criterion=None):
         num_exits, num_samples = self.logits.shape[0], self.logits.shape[1]
         if rule is not None:
             if lte_scores is not None:
                 crit, sign = lte_scores, -1.0
             else:
-                from .sweep import msp_table
-                crit, sign = msp_table(self.logits)[0], 1.0
+                from .sweep import csf_table
+                st = threshold_criterion(criterion or "max_confidence")
+                crit, sign = csf_table(self.logits, criterion=st)[0], (-1.0 if st.value == "entropy" else 1.0)
             exits, pred, _, counts = rule_scan_device(crit, self.logits, thresholds, patience, rule, sign=sign)
+        elif criterion is not None:
+            exits, pred, _, counts = criterion_scan_device(self.logits, thresholds, criterion)
         elif lte_scores is not None:
             exits, pred, counts = lte_scan_device(lte_scores, self.logits, thresholds)
         elif patience is not None:
@@ -158,6 +188,28 @@ class Policy:
     def max_confidence_global_thresholding_policy(self):
         """EE/policy.py:12-53: one global threshold ``config["exit_threshold"]``."""
         return self._finish(float(self.config["exit_threshold"]))
+
+    def _exit_thresholds(self, who):
+        """``config["exit_thresholds"]`` (per exit) or the global ``config["exit_threshold"]``."""
+        thr = self.config.get("exit_thresholds")
+        if thr is None:
+            if self.config.get("exit_threshold") is None:
+                raise ValueError(f'{who} needs config["exit_thresholds"] (per exit) or config["exit_threshold"]')
+            thr = float(self.config["exit_threshold"])
+        return thr
+
+    def entropy_global_thresholding_policy(self):
+        """The thresholding policy under the entropy criterion (CSF "entropy", EE/thresh.py:41-45, 55-61): the first exit whose float64
+        entropy ``log A - B / A`` is strictly BELOW its threshold, else the last.  Thresholds: ``config["exit_thresholds"]`` (per exit) or the
+        global ``config["exit_threshold"]``.  ``config["exit_policy"] = "entropy_global_thresholding_policy"`` selects it through
+        EE/eval.py:91-98's ``getattr`` dispatch."""
+        return self._finish(self._exit_thresholds("entropy_global_thresholding_policy"), criterion="entropy")
+
+    def margin_global_thresholding_policy(self):
+        """The thresholding policy under the margin criterion (include/mmee.h MMEE_CRIT_MARGIN: top-1 minus top-2 softmax probability): the
+        first exit whose float64 margin is strictly above its threshold, else the last.  Same configuration keys as
+        ``entropy_global_thresholding_policy``."""
+        return self._finish(self._exit_thresholds("margin_global_thresholding_policy"), criterion="margin")
 
     def patience_policy(self):
         """Patience-based early exit (PABEE; the reference declares it, EE/models/EE_modules.py:123-124, and implements no policy for it):
@@ -190,13 +242,15 @@ class Policy:
             if self.config.get("exit_threshold") is None:
                 raise ValueError(f'{rule}_policy needs config["exit_thresholds"] (per exit) or config["exit_threshold"]')
             thr = float(self.config["exit_threshold"])
-        return self._finish(thr, patience=self.config["patience"], lte_scores=lte, rule=rule)
+        return self._finish(thr, patience=self.config["patience"], lte_scores=lte, rule=rule, criterion=self.config.get("criterion", "max_confidence"))
 
     def patient_confident_policy(self):
         """Patient and confident (PCEE-BERT, Zhang et al. 2022; include/mmee.h MMEE_RULE_STREAK; the reference has no counterpart): exit at the
         first e where the confidence test ``max-softmax > threshold`` has held at ``config["patience"]`` exits in a row (an int, or one
         entry per exit), else the last.  Thresholds: ``config["exit_thresholds"]`` (per exit) or the global ``config["exit_threshold"]``.
         With ``config["lte_scores"]`` the test is the LTE one (``score < config["lte_thresholds"][e]`` or the global threshold).
+        ``config["criterion"]`` ("max_confidence", the default; "entropy"; "margin") picks the table and the direction of the test
+        (``sweep.csf_table``).
         ``config["exit_policy"] = "patient_confident_policy"`` selects it through EE/eval.py:91-98's ``getattr`` dispatch."""
         return self._rule_policy("patient_confident")
 

@@ -36,6 +36,34 @@ def msp_table(logits, references=None, device=None):
     return conf, corr
 
 
+def csf_table(logits, references=None, criterion="max_confidence", as_csf: bool = False, device=None):
+    """The table of one of the three confidence scoring functions (CSF_dict, EE/thresh.py:55-61) on the device (ee_csf_table):
+    ``(table float64 (E1,N), correct uint8 (E1,N) | None)`` from logits (E1,N,K).  ``criterion``: "max_confidence" (``msp_table`` bit for bit),
+    "entropy" (the reference's ``log A - B / A``, lower is surer) or "margin" (include/mmee.h MMEE_CRIT_MARGIN).  ``as_csf=True`` returns the
+    value the reference thresholds with ``>=`` -- the entropy negated (exact), the other two unchanged -- so that ``threshold_sweep`` and
+    ``rule_sweep`` (sign +1) take the table directly."""
+    from .policy import threshold_criterion
+    st = threshold_criterion(criterion)
+    lib = capi.load()
+    dev = _require_torch_cuda(device)
+    L = _f64_on(dev, logits)
+    if L.dim() != 3:
+        raise ValueError("logits must have shape (num_exits + 1, num_samples, num_labels)")
+    E1, N, K = L.shape
+    table = torch.empty((E1, N), dtype=torch.float64, device=dev)
+    refs = corr = None
+    if references is not None:
+        refs = _on(dev, references, torch.int64)
+        if tuple(refs.shape) != (N,):
+            raise ValueError("references (N,)")
+        corr = torch.empty((E1, N), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        capi.check(lib.ee_csf_table(_ptr(L), _ptr(refs), E1, N, K, st.code, _ptr(table), _ptr(corr), _stream()), None, "ee_csf_table")
+    if as_csf and st.value == "entropy":
+        table = -table
+    return table, corr
+
+
 def patience_sweep(logits, references, patiences, want_hist: bool = False, device=None):
     """Every patience value of ``patiences`` (V,) over one dumped array ``logits`` (E1,N,K) with labels ``references`` (N,): for each t the
     exits of the patience policy (include/mmee.h), the accuracy of the predictions at those exits and the mean exit (ee_patience_sweep: the
