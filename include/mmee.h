@@ -152,7 +152,7 @@ enum {
                                   Q | K | V GEMM then runs for the documents that STAY only, and not at all in the last layer.  A
                                   re-association of the same arithmetic (~1e-6 on the CLS row): exit indices and the 1e-4 logit bar hold,
                                   bit-identity with MMEE_FLAG_WHOLE_LAYERS does not.  LayoutLMv3, MMEE_PREC_F32_SPLIT, no dump-all */
-    MMEE_FLAG_LOW_LATENCY = 64 /* small batches (the reference's eval_batch_size = 1, EE/configs.py:36): in the rest of every LayoutLMv3 layer
+    MMEE_FLAG_LOW_LATENCY = 64,/* small batches (the reference's eval_batch_size = 1, EE/configs.py:36): in the rest of every LayoutLMv3 layer
                                   (attention, attention output, FFN) the attention-output and FFN-down GEMMs run as S-way split-K whenever
                                   ee_low_latency_k_splits gives S > 1 for this call's static row count B * (T + patches + 1): S workgroups per
                                   128 x 128 output tile, each over K / S, writing alpha * acc of its part and no bias.  The LayerNorm that
@@ -165,6 +165,12 @@ enum {
                                   gives S = 1 for both GEMMs the flag changes nothing, neither a launch nor a bit.  Q | K | V, FFN-up,
                                   attention, probes and the exit tail are as without the flag.  Refused, each with a message: on an
                                   MMEE_PREC_F32 handle, on an MMEE_ARCH_BEIT handle, together with MMEE_FLAG_ONE_TERM */
+    MMEE_FLAG_STREAM_RESULTS = 128 /* deliver the documents to the host as they leave: behind every exit's decide launch one more launch packs the
+                                  rows of the documents that left there into a pinned buffer of the handle and an event is recorded; ee_stream_next
+                                  (below) waits for the next exit's event and returns its rows.  out_logits and out_conf must be non-NULL; every
+                                  out_* tensor is filled exactly as without the flag (same launches in front, same bits).  Adds E + 1 launches.
+                                  Refused, each with a message: together with MMEE_FLAG_NO_EXIT (nobody leaves early: nothing to stream) and in
+                                  ee_graph_capture (events between launches are not part of a captured launch list) */
 };
 
 typedef struct ee_handle ee_handle;
@@ -272,6 +278,27 @@ int ee_graph_capture(ee_handle* h, const int64_t* input_ids, const int64_t* atte
                      float* out_head_logits, float* out_head_crit, float* out_hidden_cls, void* stream, int32_t* graph_id);
 int ee_graph_launch(ee_handle* h, int32_t graph_id, const double* thresholds, const double* temperatures, void* stream);
 int ee_graph_destroy(ee_handle* h, int32_t graph_id);
+
+/*
+ * The result stream of the handle's most recent ee_forward with MMEE_FLAG_STREAM_RESULTS: one chunk per evaluated exit, in the path's order
+ * e = 0 .. E (embedding exits, encoder exits ascending, the final classifier), E + 1 chunks per forward.  ee_stream_next BLOCKS the calling
+ * thread until the next undelivered exit has been decided on the device (hipEventSynchronize on an event recorded behind that exit's launches:
+ * no flag is polled, deeper layers keep running for the documents that stay), then returns *exit_index = e, *n_rows = the number of documents
+ * that left at e (possibly 0) and *rows = host int32 (n_rows, K + 3): per document the K + 2 words of ee_pack_results -- the logits' float32 bit
+ * patterns, the exit index, the confidence's bit pattern -- followed by the document's slot in the call (its row of out_*).  After the last
+ * chunk it returns 0 with *exit_index = -1, *n_rows = 0, *rows = NULL.
+ *   - rows within a chunk ascend by slot; every row of chunk e carries exit index e;
+ *   - the union over the E + 1 chunks is every document of the call exactly once (n_rows sums to B);
+ *   - the row's bits are the bits out_logits / out_exit / out_conf hold at that slot once the forward has finished;
+ *   - the chunk sizes are the differences of ee_last_stage_counts' document counts.
+ * The pointer addresses pinned memory of the handle, written by the device: read it, do not write it; it stays valid until the next
+ * ee_forward with the flag on this handle.  That forward drops whatever the caller has not read yet (the earlier forward's out_* stay
+ * complete) and, before it enqueues anything, waits on the host for the earlier flagged forward's last exit, so the buffer is never rewritten
+ * under a reader.  A forward without the flag leaves the stream alone.  One caller thread per handle, as everywhere.
+ * Error reporting is unchanged: out-of-range inputs and split-precision overflows are reported by ee_last_stage_counts or the next forward as
+ * today; the chunks are what out_* will hold.  Refused with a message: a handle on which no flagged forward has run.
+ */
+int ee_stream_next(ee_handle* h, int32_t* exit_index, const int32_t** rows, int32_t* n_rows);
 
 /* Per-stage statistics of the last ee_forward (synchronises with `stream`): active documents and packed rows entering
  * each of the E+1 exit stages.  n_stages_out receives E+1. */

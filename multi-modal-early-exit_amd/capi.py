@@ -19,6 +19,7 @@ FLAG_PROBE_ALWAYS = 8
 FLAG_XPROBE = 16
 FLAG_ONE_TERM = 32
 FLAG_LOW_LATENCY = 64
+FLAG_STREAM_RESULTS = 128
 CRIT_MAX_CONFIDENCE, CRIT_ENTROPY, CRIT_PATIENCE, CRIT_MARGIN = 0, 1, 2, 3
 RULE_PLAIN, RULE_STREAK, RULE_EITHER = 0, 1, 2
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
@@ -73,6 +74,7 @@ SYMBOLS = {
                                    C.POINTER(C.c_double), _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32)]),
     "ee_graph_launch": (C.c_int, [_vp, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
     "ee_graph_destroy": (C.c_int, [_vp, _i32]),
+    "ee_stream_next": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(C.POINTER(_i32)), C.POINTER(_i32)]),
     "ee_last_stage_counts": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _i32, C.POINTER(_i32), _vp]),
     "ee_last_flops": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
     "ee_last_layer_plan": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, C.POINTER(C.c_double), _vp]),

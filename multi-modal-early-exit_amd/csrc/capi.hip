@@ -523,6 +523,8 @@ int ee_destroy(ee_handle* h) {
     if (h->fwd_done) (void)hipEventDestroy(h->fwd_done);
     if (h->err_host) (void)hipHostFree(h->err_host);
     for (auto& es : h->errs) if (es.done) (void)hipEventDestroy(es.done);
+    for (auto& ev : h->stream_ev) (void)hipEventDestroy(ev);
+    if (h->stream_host) (void)hipHostFree(h->stream_host);
     for (void* q : h->allocs) (void)hipFree(q);
     delete h;
     return 0;

@@ -99,6 +99,8 @@ struct Forward {
     const bool low_latency = (a.flags & MMEE_FLAG_LOW_LATENCY) && sp && !beit;
     int ks_ao = 1, ks_down = 1;
     size_t ll_stride = 0;                    // floats between two parts: (rows padded to whole 128-row tiles) x H
+    // MMEE_FLAG_STREAM_RESULTS: behind every exit's decide launch, the leavers' rows into the handle's pinned segment buffer and an event (result_stream.hip)
+    const bool stream_results = a.flags & MMEE_FLAG_STREAM_RESULTS;
     // split precision attention: attention_idx.hip (pair index built once per forward; default) or, with MMEE_ATTN_V=2 or bucket tables
     // beyond 64 bins, attention_pair.hip (clamped Delta tables gathered per layer and head)
     const bool use_idx = sp && attn_variant() == 0 && c.rel_pos_bins <= 64 && c.rel_2d_pos_bins <= 64;
@@ -158,6 +160,13 @@ struct Forward {
                            "is a reported deviation; pick one");
         if (hs_out && (a.flags & (MMEE_FLAG_NO_EXIT | MMEE_FLAG_WHOLE_LAYERS)) != (MMEE_FLAG_NO_EXIT | MMEE_FLAG_WHOLE_LAYERS))
             return fail(h, "ee_forward: hidden states are collected in dump-all mode with whole layers only (MMEE_FLAG_NO_EXIT | MMEE_FLAG_WHOLE_LAYERS)");
+        if (stream_results && no_exit)
+            return fail(h, "ee_forward: MMEE_FLAG_STREAM_RESULTS together with MMEE_FLAG_NO_EXIT: nobody leaves early in dump-all mode, there is nothing to stream");
+        if (stream_results && cap)
+            return fail(h, "ee_graph_capture: MMEE_FLAG_STREAM_RESULTS belongs to eager calls (the events between the launches are not part of a captured "
+                           "launch list)");
+        if (stream_results && (!a.out_logits || !a.out_conf))
+            return fail(h, "ee_forward: MMEE_FLAG_STREAM_RESULTS needs out_logits and out_conf (a streamed row carries both)");
         if (cap && (hs_out || embeds_in || head_mask || attn_out || h->prof_on))
             return fail(h, "ee_graph_capture: the one-shot side inputs / outputs (inputs_embeds, hidden states, head mask, attention maps) and ee_profile "
                            "belong to eager calls");
@@ -619,8 +628,45 @@ struct Forward {
             launch_decide(d, stateful ? &pa : nullptr, patience ? DECIDE_PATIENCE : c.use_lte ? DECIDE_LTE : DECIDE_THRESHOLD, h->rule, s);
         }
         h->rec.exit_stage[exit_index] = cur;
+        if (stream_results) emit_leavers(is_final);
         if (!is_final) compact();
         exit_index += 1;
+    }
+
+    // result stream: the rows of the documents that left at this exit (those of stage `cur` that are not in stage cur + 1; the final exit: everybody)
+    // into the next free rows of the pinned segment buffer, then the event ee_stream_next waits on.  Eager calls only (validate()).
+    void emit_leavers(bool is_final) {
+        EmitArgs e{};
+        e.counts = &h->counts[cur]; e.doc_orig = S_doc_orig(cur);
+        if (!is_final) { e.n_counts = &h->counts[cur + 1]; e.n_doc_orig = S_doc_orig(cur + 1); }
+        e.out_logits = a.out_logits; e.out_exit = a.out_exit; e.out_conf = a.out_conf;
+        e.K = K; e.exit_index = exit_index; e.cap = c.max_docs;
+        e.done = h->stream_done; e.rows = h->stream_dev; e.cum = h->stream_dev + (size_t)c.max_docs * (K + 3);
+        { ProfScope ps(h, P_EMIT, s); launch_emit_leavers(e, s); }
+        (void)hipEventRecord(h->stream_ev[exit_index], s);
+    }
+
+    // the segment buffer and the events of the result stream, at the handle's first flagged forward; a later one first waits (on the host) for the
+    // last event of the one before, so that no segment is rewritten under a reader, and starts the delivery over
+    int stream_begin() {
+        if (!h->stream_host) {
+            const size_t words = (size_t)c.max_docs * (K + 3) + (size_t)(E + 1);
+            HIP_OK(h, hipHostMalloc((void**)&h->stream_host, words * sizeof(int32_t), hipHostMallocMapped));
+            memset(h->stream_host, 0, words * sizeof(int32_t));
+            void* dev = nullptr;
+            HIP_OK(h, hipHostGetDevicePointer(&dev, h->stream_host, 0));
+            h->stream_dev = reinterpret_cast<int32_t*>(dev);
+        }
+        if (!h->stream_done && dev_alloc(h, &h->stream_done, 1)) return 1;
+        while ((int)h->stream_ev.size() < E + 1) {
+            hipEvent_t ev = nullptr;
+            HIP_OK(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            h->stream_ev.push_back(ev);
+        }
+        if (h->stream_armed) HIP_OK(h, hipEventSynchronize(h->stream_ev[E]));
+        h->stream_armed = false;                  // until this forward's launch list is complete: every one of its events recorded
+        h->stream_next = 0;
+        return 0;
     }
 
     // hidden CLS rows of the active documents into out_hidden_cls[slot] (slot 0: the embeddings, l + 1: the output of layer l);
@@ -718,6 +764,7 @@ struct Forward {
             if ((size_t)ks_down * ll_stride > h->ll_part_floats) ks_down = 1;
         }
         if (!cap) { const int rc_pre = forward_pre(h, s); if (rc_pre) return rc_pre; }
+        if (stream_results) { const int rc_st = stream_begin(); if (rc_st) return rc_st; }
         // (a kernel, not hipMemsetAsync: the same launch list then serves the eager call and the captured graph -- replays whose memset NODES were
         //  preceded by an eager forward on the handle came back with an unzeroed error word on ROCm 7.2, tools/graph_debug2.py)
         hipLaunchKernelGGL(zero_words_kernel, dim3(32), dim3(256), 0, s, h->err_flag, 4, h->queue_heads, h->n_queue_heads);
@@ -752,6 +799,7 @@ struct Forward {
         // the caller decides whether to pin it).  The same inputs therefore always run the same launch sequence and return the same bits.
         for (int l = 0; l < L; ++l) layer(l);
         final_exit();
+        if (stream_results) h->stream_armed = true;
         r.last_B = B; r.last_T = T; r.last_stages = E + 1; r.last_flags = a.flags;
         r.last_gate_heads = a.out_head_logits || a.out_head_crit;
         if (!cap) { const int rc_post = forward_post(h, s); if (rc_post) return rc_post; }
@@ -785,6 +833,9 @@ int ee_graph_capture(ee_handle* h, const int64_t* input_ids, const int64_t* atte
     if (!h || !graph_id) return fail(h, "ee_graph_capture: null argument");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (!s) return fail(h, "ee_graph_capture: the legacy null stream cannot be captured; pass a created stream");
+    if (flags & MMEE_FLAG_STREAM_RESULTS)          // before the eager warm-up call, which would otherwise run (and stream) first
+        return fail(h, "ee_graph_capture: MMEE_FLAG_STREAM_RESULTS belongs to eager calls (the events between the launches are not part of a captured "
+                       "launch list)");
     const int E1 = h->cfg.n_embedding_exits + h->cfg.n_encoder_exits + 1;
     const ForwardArgs a{input_ids, attention_mask, bbox, pixel_values, token_type_ids, position_ids, B, T, thresholds, temperatures, flags,
                         out_logits, out_exit, out_conf, out_all_logits, out_all_crit, out_head_logits, out_head_crit, out_hidden_cls, stream};

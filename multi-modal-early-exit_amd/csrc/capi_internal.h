@@ -2,7 +2,7 @@
 // point returns through, the allocator and the profiling scope.  Private to csrc/capi*.hip:
 //   capi.hip          the handle's error ring and allocator, and the loader (ee_create, ee_load_tensor, ee_finalize, ee_destroy)
 //   capi_forward.hip  the forward schedule (Forward, ee_forward) and its captured-graph form (ee_graph_*)
-//   capi_query.hip    what reads the last forward back or arms the next one (ee_profile*, ee_last_*, ee_suggest_probe_mask, ee_set_*)
+//   capi_query.hip    what reads the last forward back or arms the next one (ee_profile*, ee_stream_next, ee_last_*, ee_suggest_probe_mask, ee_set_*)
 //   capi_tools.hip    entry points that never see a handle (clock stamps, policy sweeps, pack / unpack, image feed, ee_debug_*)
 #pragma once
 #include <cstdint>
@@ -157,6 +157,14 @@ struct ee_handle {
         mmee::capi::ForwardRecord rec;            // bookkeeping of the captured forward, restored by every launch
     };
     std::vector<GraphRec> graphs;
+    // result stream (MMEE_FLAG_STREAM_RESULTS): one pinned, device-mapped buffer of max_docs rows of K + 3 words and E + 1 cumulative counts behind
+    // them, allocated at the first flagged forward; the emit launches store into it directly and ee_stream_next hands out its segments
+    int32_t* stream_host = nullptr;               // what the host reads
+    int32_t* stream_dev = nullptr;                // the same memory as the kernels address it
+    int* stream_done = nullptr;                   // device word: the running leaver count of the forward in flight
+    std::vector<hipEvent_t> stream_ev;            // [E + 1], timing disabled: recorded behind the emit launch of every exit
+    bool stream_armed = false;                    // a flagged forward has been enqueued: its events are recorded
+    int stream_next = 0;                          // the next exit ee_stream_next delivers
 };
 
 namespace mmee {
@@ -199,7 +207,7 @@ int dev_alloc(ee_handle* h, T** p, size_t count) {
 
 // kernel roles reported by ee_profile_read (their names: kProfNames in capi_query.hip)
 enum { P_PREP = 0, P_EMBT, P_GPATCH, P_EMBV, P_GQKV, P_ATTN, P_GAO, P_LN, P_GUP, P_GDOWN, P_HEAD, P_DECIDE, P_COMPACT, P_GCLS, P_PROBE,
-       P_PAIRIDX, P_PSPLIT, P_HEADOUT, P_COUNT };
+       P_PAIRIDX, P_PSPLIT, P_HEADOUT, P_EMIT, P_COUNT };
 
 struct ProfScope {
     ee_handle* h;

@@ -1,4 +1,4 @@
-// What reads the last forward of a handle back (ee_profile*, ee_last_stage_counts, ee_last_flops, ee_last_layer_plan, ee_suggest_probe_mask)
+// What reads the last forward of a handle back (ee_profile*, ee_stream_next, ee_last_stage_counts, ee_last_flops, ee_last_layer_plan, ee_suggest_probe_mask)
 // and the one-line setters that arm the next one (ee_set_*).
 #include <cstring>
 #include <vector>
@@ -31,7 +31,10 @@ const char* const kProfNames[] = {
     "pair_index|pair_index_kernel [inside prep]",
     "patch_split|patch_split_kernel [inside gemm_patch]",
     "head_out|head_out_kernel / head_out_lte_kernel [inside exit_head]",
+    // (not nested) MMEE_FLAG_STREAM_RESULTS: one launch behind every exit's decide launch
+    "emit_leavers|emit_leavers_kernel",
 };
+static_assert(sizeof(kProfNames) / sizeof(kProfNames[0]) == P_COUNT, "one name per profile role");
 
 // Synchronises the stream, then copies the first n StageCounts (of the last forward) to the host.
 int read_stage_counts(ee_handle* h, void* stream, int n, std::vector<StageCounts>& sc) {
@@ -91,6 +94,24 @@ int ee_last_k_splits(ee_handle* h, int32_t* attn_out, int32_t* ffn_down) {
     if (!h || !h->rec.last_stages) return fail(h, "ee_last_k_splits: no forward has run");
     if (attn_out) *attn_out = h->rec.ks_attn_out;
     if (ffn_down) *ffn_down = h->rec.ks_ffn_down;
+    return 0;
+}
+
+int ee_stream_next(ee_handle* h, int32_t* exit_index, const int32_t** rows, int32_t* n_rows) {
+    if (!h || !exit_index || !rows || !n_rows) return fail(h, "ee_stream_next: null argument");
+    if (!h->stream_armed) return fail(h, "ee_stream_next: no forward with MMEE_FLAG_STREAM_RESULTS has run on this handle");
+    const int E1 = (int)h->stream_ev.size(), W = h->cfg.num_labels + 3;
+    *exit_index = -1; *rows = nullptr; *n_rows = 0;
+    if (h->stream_next >= E1) return 0;           // every chunk of the last flagged forward has been delivered
+    const int e = h->stream_next;
+    HIP_OK(h, hipEventSynchronize(h->stream_ev[e]));
+    const int32_t* cum = h->stream_host + (size_t)h->cfg.max_docs * W;
+    const int lo = e ? cum[e - 1] : 0, hi = cum[e];
+    if (lo < 0 || hi < lo || hi > h->cfg.max_docs)
+        return fail(h, "ee_stream_next: exit %d reports documents [%d, %d) of at most %d: the forward did not run to this exit (see ee_last_stage_counts)", e,
+                    lo, hi, h->cfg.max_docs);
+    *exit_index = e; *rows = h->stream_host + (size_t)lo * W; *n_rows = hi - lo;
+    h->stream_next = e + 1;
     return 0;
 }
 

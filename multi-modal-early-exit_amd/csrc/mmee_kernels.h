@@ -116,6 +116,24 @@ struct PatienceArgs {
     int* run;                        // [max_docs] run counter c_e (MMEE_RULE_STREAK: the streak s_e), by original slot
 };
 
+// result stream (MMEE_FLAG_STREAM_RESULTS; result_stream.hip): the launch behind an exit's decide launch
+struct EmitArgs {
+    // the stage that reached the exit, and the stage of the documents that stay (n_doc_orig null: the final exit, everybody leaves)
+    const StageCounts* counts;
+    const int* doc_orig;
+    const StageCounts* n_counts;
+    const int* n_doc_orig;
+    // what the decide launch wrote, by original slot
+    const float* out_logits;         // (B,K)
+    const int* out_exit;             // (B)
+    const float* out_conf;           // (B)
+    int K, exit_index;
+    int cap;                         // rows the segment buffer holds (max_docs): nothing is stored past it
+    int* done;                       // device word: leavers of the exits before this one (read at exit_index > 0, rewritten by every launch)
+    int* rows;                       // host-visible [cap][K + 3]: logit bit patterns, exit index, confidence bit pattern, original slot
+    int* cum;                        // host-visible [E + 1]: leavers through exit e
+};
+
 // ee_config.criterion (include/mmee.h MMEE_CRIT_*; capi_internal.h asserts the values agree)
 enum { CRIT_MAX_CONFIDENCE = 0, CRIT_ENTROPY = 1, CRIT_PATIENCE = 2, CRIT_MARGIN = 3 };
 // the direction of a threshold criterion: max-softmax and margin leave on crit > thr, entropy on crit < thr; strict, so a NaN never fires
@@ -193,6 +211,7 @@ void launch_patch_mean(const float* X, int H, const int* x_phys, const int* doc_
                        int max_docs, hipStream_t s);
 void launch_head_out(const HeadOutArgs& a, int max_docs, hipStream_t s);
 void launch_decide(const DecideArgs& a, const PatienceArgs* p, int mode, int rule, hipStream_t s);   // p: null where (mode, rule) keeps no state
+void launch_emit_leavers(const EmitArgs& a, hipStream_t s);      // result_stream.hip
 void launch_pack_results(const float* logits, const int* exit_layer, const float* conf, int n, int K, int* rows, hipStream_t s);
 void launch_unpack_results(const int* rows, int n, int K, float* logits, int* exit_layer, float* conf, hipStream_t s);
 void launch_compact_rows(const StageCounts* n_counts, const int* n_doc_off, const int* n_x_src, const int* n_meta_src,

@@ -38,6 +38,56 @@ class EngineOutput:
     attentions: Optional["torch.Tensor"] = None      # (L,B,heads,T+Pv,T+Pv): attention probabilities of every layer (after the head mask)
 
 
+@dataclass
+class ResultChunk:
+    """The documents that left at one exit (``EarlyExitEngine.forward_stream``): host numpy arrays, copies of the handle's pinned segment."""
+    exit_index: int                         # the exit, in the path's order; E = final classifier
+    doc_index: np.ndarray                   # (n,)  int32   -- the documents' slots in the call, ascending
+    logits: np.ndarray                      # (n,K) float32 -- bit-equal to output.logits[doc_index]
+    exit_layer: np.ndarray                  # (n,)  int32   -- exit_index, n times
+    confidence: np.ndarray                  # (n,)  float32 -- bit-equal to output.confidence[doc_index]
+
+
+def unpack_stream_rows(words, K: int):
+    """(n, K + 3) int32 rows of ee_stream_next -> (doc_index int32 (n,), logits float32 (n,K), exit_layer int32 (n,), confidence float32 (n,)).
+    The first K + 2 words of a row are the row of ``dist.pack_results`` (floats as their bit patterns: views, never conversions), the last
+    one is the document's slot in the call.  Pure: numpy in, numpy copies out."""
+    from .dist import unpack_results
+    if not isinstance(words, np.ndarray) or words.dtype != np.int32:
+        raise TypeError(f"streamed result rows are int32 words, got {getattr(words, 'dtype', type(words))}")
+    if words.ndim != 2 or words.shape[1] != K + 3:
+        raise ValueError(f"streamed result rows are (n, K + 3) = (n, {K + 3}) words, got {words.shape}")
+    w = np.ascontiguousarray(words)
+    lg, ex, cf = unpack_results(torch.from_numpy(w[:, :K + 2].copy()))
+    return w[:, K + 2].copy(), lg.numpy().reshape(-1, K), ex.numpy(), cf.numpy()
+
+
+class ResultStream:
+    """What ``EarlyExitEngine.forward_stream`` returns: iterate it for one ``ResultChunk`` per evaluated exit, in the path's order, each as soon
+    as the device has decided that exit (the iterator blocks in ee_stream_next, on an event; deeper layers keep running meanwhile).
+    ``output`` is the forward's usual ``EngineOutput`` of device tensors, complete once the stream has drained (or after a synchronise).
+    A later ``forward_stream`` on the engine drops the chunks not read yet: iterating the older stream then raises ``MMEEError``."""
+
+    def __init__(self, engine: "EarlyExitEngine", output: Optional[EngineOutput] = None):
+        self.engine, self.output = engine, output
+        self._generation = engine._stream_generation
+
+    def __iter__(self):
+        return self
+
+    def __next__(self) -> ResultChunk:
+        eng = self.engine
+        if self._generation != eng._stream_generation:
+            raise capi.MMEEError("this result stream was dropped by a later forward_stream() on the engine (its output tensors stay complete)")
+        e, n, rows = C.c_int32(), C.c_int32(), C.POINTER(C.c_int32)()
+        capi.check(eng.lib.ee_stream_next(eng._h, C.byref(e), C.byref(rows), C.byref(n)), eng._h, "ee_stream_next")
+        if e.value < 0:
+            raise StopIteration
+        W = eng.K + 3
+        words = np.ctypeslib.as_array(rows, shape=(n.value, W)).copy() if n.value else np.zeros((0, W), dtype=np.int32)
+        return ResultChunk(e.value, *unpack_stream_rows(words, eng.K))
+
+
 def _require_torch_cuda(device=None):
     if torch is None:
         raise capi.MMEEUnavailable(f"PyTorch-ROCm is required for device tensors: {_torch_err}")
@@ -106,6 +156,7 @@ class EarlyExitEngine:
         with torch.cuda.device(self.device):
             capi.check(self.lib.ee_create(C.byref(c), C.byref(self._h)), None, "ee_create")
         self._finalized = False
+        self._stream_generation = 0         # forward_stream() calls so far: a ResultStream belongs to one of them
         self.patience = None
         if ec.patience is not None:
             self.set_patience(ec.patience)
@@ -199,7 +250,7 @@ class EarlyExitEngine:
                 validate: bool = False, whole_layers: bool = False, probe_always: bool = False, xprobe: Optional[bool] = None,
                 one_term: bool = False, inputs_embeds=None, want_hidden_states: bool = False, out=None, head_mask=None,
                 want_attentions: bool = False, patience: Optional[Union[int, Sequence[int]]] = None, exit_rule=None,
-                low_latency: bool = False, _capture: bool = False) -> EngineOutput:
+                low_latency: bool = False, _capture: bool = False, _stream: bool = False) -> EngineOutput:
         """``out``: optional preallocated ``(logits (B,K) f32, exit_layer (B,) i32, confidence (B,) f32)`` device tensors (contiguous; row
         slices of larger tensors qualify) the kernels write into instead of fresh allocations -- MicroBatchedEngine hands each half its slice.
         ``patience``: when given, ``set_patience(patience)`` before the call (an int, or one entry per exit; it matters under the "patience"
@@ -319,7 +370,7 @@ class EarlyExitEngine:
         flags = ((capi.FLAG_NO_EXIT if dump_all else 0) | (capi.FLAG_DENSE_ROWS if dense_rows else 0) |
                  (capi.FLAG_WHOLE_LAYERS if whole_layers else 0) | (capi.FLAG_PROBE_ALWAYS if probe_always else 0) |
                  (capi.FLAG_XPROBE if xprobe else 0) | (capi.FLAG_ONE_TERM if one_term else 0) |
-                 (capi.FLAG_LOW_LATENCY if low_latency else 0))
+                 (capi.FLAG_LOW_LATENCY if low_latency else 0) | (capi.FLAG_STREAM_RESULTS if _stream else 0))
         # one_term: REPORTED low-precision mode (one f16 MFMA term per MAC instead of three in the layer GEMMs and the attention); outside the
         # 1e-4 bar by construction, exit indices may flip -- bench.py's `lowprec` field, never a result to rely on
         # xprobe: probe-first layers take the CLS context in X space (no Q | K | V for documents that leave); same exits, logits within
@@ -364,6 +415,22 @@ class EarlyExitEngine:
         return EngineOutput(out_logits, out_exit, out_conf, all_logits, all_crit, head_logits, head_crit, hidden, hs, att)
 
     __call__ = forward
+
+    def forward_stream(self, *args, **kw) -> ResultStream:
+        """``forward`` with MMEE_FLAG_STREAM_RESULTS (include/mmee.h): same arguments, same device outputs (``.output``), and the returned
+        ``ResultStream`` yields the documents to the host as they leave -- one ``ResultChunk`` per evaluated exit, E + 1 in all, the first ones
+        while the deeper layers still run for the documents that stay.  Costs one small launch per exit.  Nobody leaves early in dump-all mode
+        and the side outputs of ``model.forward`` belong to it, so ``dump_all``, ``want_hidden_states``, ``head_mask``, ``want_attentions`` and
+        ``_capture`` raise ``ValueError``.  One stream per engine at a time: the next ``forward_stream`` drops what was not read."""
+        for k in ("dump_all", "want_hidden_states", "want_attentions", "_capture"):
+            if kw.get(k):
+                raise ValueError(f"forward_stream: {k} does not go with a result stream (nobody leaves early in dump-all mode; captured graphs "
+                                 "carry no events)")
+        if kw.get("head_mask") is not None:
+            raise ValueError("forward_stream: head_mask belongs to the dump-all forward")
+        out = self.forward(*args, _stream=True, **kw)
+        self._stream_generation += 1
+        return ResultStream(self, out)
 
     def capture(self, *args, **kw) -> "CapturedForward":
         """The forward as a captured launch list (ee_graph_capture; round 6): same arguments as ``forward``.  The call runs once eagerly --

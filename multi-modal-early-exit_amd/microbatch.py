@@ -11,6 +11,10 @@ Stream semantics are those of ``EarlyExitEngine.forward``: the call only enqueue
 current stream holds at the call (inputs, the memory of the output tensors), and the current stream waits for both halves before anything
 enqueued after the call runs -- to the caller the forward behaves as if it ran on the current stream.
 
+Result streams (``EarlyExitEngine.forward_stream``) are out of scope here: every handle has a stream of its own, and how to interleave the
+chunks of ``n`` handles that decide their exits at different times is a host policy of its own.  ``forward_stream`` raises; callers that
+want the documents as they leave use one ``EarlyExitEngine``, or drive the engines of ``self.engines`` themselves.
+
 The reference has no counterpart (batch size 1, one stream: EE/utils.py:169-193).
 """
 from __future__ import annotations
@@ -63,6 +67,10 @@ class MicroBatchedEngine:
         n = min(self.n, B)
         base, extra = divmod(B, n)
         return [base + (1 if i < extra else 0) for i in range(n)]
+
+    def forward_stream(self, *args, **kw):
+        """Not built (module docstring): interleaving the result streams of several handles is a host policy of its own."""
+        raise NotImplementedError("MicroBatchedEngine has no result stream: use EarlyExitEngine.forward_stream (one handle, one stream)")
 
     def forward(self, input_ids=None, attention_mask=None, bbox=None, pixel_values=None, token_type_ids=None, position_ids=None,
                 inputs_embeds=None, serial: bool = False, **kw) -> EngineOutput:

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import capi
 from .config import ExitConfig, ModelConfig
-from .engine import EarlyExitEngine, EngineOutput, load_checkpoint_tensors, torch
+from .engine import EarlyExitEngine, EngineOutput, ResultStream, load_checkpoint_tensors, torch
 
 
 class _ModelOutput(OrderedDict):
@@ -330,6 +330,29 @@ class LayoutLMv3EEForSequenceClassification:
         return self._run(dict(input_ids=input_ids, attention_mask=attention_mask, bbox=bbox, pixel_values=pixel_values,
                               token_type_ids=token_type_ids, position_ids=position_ids),
                          thresholds=thresholds, temperatures=temperatures, **kw)
+
+    def early_exit_stream(self, input_ids=None, attention_mask=None, bbox=None, pixel_values=None, token_type_ids=None,
+                          position_ids=None, thresholds: Optional[Union[float, Sequence[float]]] = None,
+                          temperatures: Optional[Sequence[float]] = None, patience: Optional[int] = None, low_latency: bool = False,
+                          **kw) -> ResultStream:
+        """``early_exit`` that delivers the documents as they leave (``EarlyExitEngine.forward_stream``): the same arguments, defaults and
+        small-batch schedule choice; the returned ``ResultStream`` yields one ``ResultChunk`` of host arrays per exit while deeper layers
+        still run, and its ``.output`` is what ``early_exit`` returns.  One handle, one call: the batch must fit the engine's ``max_docs``,
+        and a ``MicroBatchedEngine`` has no result stream."""
+        self._patience_kw(patience, kw)
+        if low_latency:
+            kw["low_latency"] = True
+        if thresholds is None:
+            thresholds = self.config.exit_config["global_threshold"]
+        self._small_batch_schedule(pixel_values, kw)
+        self._sync_exit_config()
+        if int(pixel_values.shape[0]) > self.engine.max_docs:
+            raise ValueError(f"early_exit_stream: {int(pixel_values.shape[0])} documents, the engine holds max_docs = {self.engine.max_docs} "
+                             "(a result stream belongs to one forward)")
+        tensors = dict(pixel_values=pixel_values) if self.engine.beit else dict(
+            input_ids=input_ids, attention_mask=attention_mask, bbox=bbox, pixel_values=pixel_values, token_type_ids=token_type_ids,
+            position_ids=position_ids)
+        return self.engine.forward_stream(**tensors, thresholds=thresholds, temperatures=temperatures, **kw)
 
     SMALL_BATCH_WHOLE_LAYERS = 16
 
