@@ -543,6 +543,29 @@ int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const
                         int32_t K, int32_t epi, int32_t out_split, float a_scale, float w_scale, float out_scale,
                         const int32_t* row_src, int32_t rows_A, int32_t iters, float* ms_out, void* stream);
 
+/* Unit-test hook of the fused attention kernels: ONE launch of one kernel of the path on caller-provided DEVICE buffers; no handle.
+ *   qkv            f32 [qkv_rows][3 H], H = 64 * heads: Q (already divided by sqrt(d)) | K | V of every row
+ *   doc_off        int32 [n_docs + 1], doc_off[0] = 0: the ragged documents; row r of document d is context row doc_off[d] + r
+ *   qkv_doc_off    NULL, or int32 [n_docs]: first Q | K | V row of every document when those rows lie elsewhere (probe-first layers)
+ *   pos, x0, y1    int32 per row: the 1-D position index in [0, max_pos], bbox x0 / y1 in [0, max_coord]; masked: != 0 = not an attention key
+ *   w1, wx, wy     f32 [heads][bins1], [heads][bins2], [heads][bins2]: rel_pos_bias / rel_pos_x_bias / rel_pos_y_bias (NULL for _IDX_NOBIAS)
+ *   kernel         MMEE_ATTN_KERNEL_*; use_queue: != 0 work queues, 0 static grid stride; q_limit > 0: the first q_limit queries of every document
+ *   terms          3, or 1 (MMEE_ATTN_KERNEL_IDX only): the f16 MFMA terms per product (MMEE_FLAG_ONE_TERM)
+ *   ctx            out, [rows][H] exactly as the kernel writes it: f32 rows (MMEE_ATTN_KERNEL_F32) or split-f16 rows (64-byte groups
+ *                  [hi 16 f16 | lo 16 f16]) scaled by 64; rows the kernel does not write keep their bytes
+ *   err_flag_out   host int32: the kernel's error word after the launch (16 = a value left the range of the split planes)
+ * The operands are built by the path's own code: row metadata, bucket LUTs, value tables, split Q | K | V rows (scale 16), pair index,
+ * stage counts, zeroed queue counters; max_len = the longest document.  What the kernels' *_supports() predicates refuse is refused here.
+ * Synchronises the stream. */
+#define MMEE_ATTN_KERNEL_F32 0          /* attention_f32.hip */
+#define MMEE_ATTN_KERNEL_PAIR 1         /* attention_pair.hip (bucket tables beyond 64 bins) */
+#define MMEE_ATTN_KERNEL_IDX 2          /* attention_idx.hip with the 32-bit pair index */
+#define MMEE_ATTN_KERNEL_IDX_NOBIAS 3   /* attention_idx.hip without a pair index: no bias, no key mask (image-only models) */
+int ee_debug_attention(const float* qkv, int32_t qkv_rows, const int32_t* doc_off, int32_t n_docs, const int32_t* qkv_doc_off, const int32_t* pos,
+                       const int32_t* x0, const int32_t* y1, const int32_t* masked, const float* w1, const float* wx, const float* wy, int32_t heads,
+                       int32_t bins1, int32_t bins2, int32_t max_rel_pos, int32_t max_rel_2d_pos, int32_t max_pos, int32_t max_coord, int32_t kernel,
+                       int32_t use_queue, int32_t q_limit, int32_t terms, void* ctx, int32_t* err_flag_out, void* stream);
+
 /* Diagnostic of the two-heads-per-item attention kernel (attention_pair.hip): with MMEE_ATTN_STAMPS=1 in the environment the
  * launches run a build with in-kernel s_memtime stamps; this call synchronises, copies the eight phase sums (shader cycles summed over
  * waves: 0 wait for the tile's LDS-DMA, 1 DMA issue, 2 bias gathers, 3 Q K^T MFMAs, 4 / 5 softmax + P V of head A / B, 6 item prologue,

@@ -24,6 +24,7 @@ CRIT_MAX_CONFIDENCE, CRIT_ENTROPY, CRIT_PATIENCE, CRIT_MARGIN = 0, 1, 2, 3
 RULE_PLAIN, RULE_STREAK, RULE_EITHER = 0, 1, 2
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 CLOCK_STAMP_WORDS = 4096       # MMEE_CLOCK_STAMP_WORDS
+ATTN_KERNEL_F32, ATTN_KERNEL_PAIR, ATTN_KERNEL_IDX, ATTN_KERNEL_IDX_NOBIAS = 0, 1, 2, 3
 
 _LIB_NAME = "libmmee_hip.so"
 _LIB_PATH = os.environ.get("MMEE_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), _LIB_NAME)
@@ -107,6 +108,8 @@ SYMBOLS = {
     "ee_debug_gemm_split": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp,
                                       _i32, _i32, C.POINTER(C.c_float), _vp]),
     "ee_debug_attn_stamps": (C.c_int, [_vp]),
+    "ee_debug_attention": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                     _i32, _i32, _i32, _vp, C.POINTER(_i32), _vp]),
     "ee_temperature_fit": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ee_preprocess_images": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp]),
     "ee_preprocess_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32]),

@@ -63,6 +63,11 @@ static_assert(WGS * LDS_BYTES <= 160 * 1024 && OFF_TY + 4 * BINS_MAX < 65536, "L
 static_assert(WGS * ((LDS_BYTES16 + 1279) / 1280) <= 128 && WGS * ((LDS_BYTES + 1279) / 1280) <= 128 && OFF_T1V + 4 * 31 < 65536,
               "LDS budget in 1280-byte granules (three workgroups per CU) / 16-bit instruction offsets");
 constexpr float kNegBig = -1.0e30f;
+// The reference maximum starts ABOVE the masked-key sentinel: a first key tile whose keys are all masked (left padding: key 0 masked as well) then
+// leaves it where it is, and its exponents are fma(-1e30, c, 10 + 1e29 c) = -huge, p = 0.  Started AT the sentinel, the exponent was the
+// difference of two products of 1e30 rounded apart -- +-1e20 instead of 10 -- and the tile left inf (then NaN) in l and O.  Any real score
+// moves the reference from either start with alpha = 0, so every other input keeps its bits.
+constexpr float kMrefInit = -1.0e29f;
 constexpr float kLog2e = 1.44269504088896340736f;
 constexpr float kPShift = 10.0f;              // probabilities carry 2^10 into the split planes
 constexpr float kLazyLog2 = 5.0f;             // the running maximum lags by at most 2^5
@@ -521,7 +526,7 @@ __global__ __launch_bounds__(256, WGS) void attention_idx_kernel(const AttnArgs 
         HeadState st;
 #pragma unroll
         for (int e = 0; e < 16; ++e) { st.o0[e] = 0.f; st.o1[e] = 0.f; }
-        st.mref = kNegBig;
+        st.mref = kMrefInit;
         st.l = 0.f;
 
         // ---- softmax (lazy rescaling, 2^10 folded into the exponent) + O^T += V^T P^T on a finished score tile; vs = this lane's V read

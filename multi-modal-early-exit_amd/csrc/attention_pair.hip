@@ -56,6 +56,11 @@ struct Lds {
 };
 constexpr int kDefaultHP = 1;
 constexpr float kNegBig = -1.0e30f;
+// The reference maximum starts ABOVE the masked-key sentinel: a first key tile whose keys are all masked (left padding: key 0 masked as well) then
+// leaves it where it is, and its exponents are fma(-1e30, c, 10 + 1e29 c) = -huge, p = 0.  Started AT the sentinel, the exponent was the
+// difference of two products of 1e30 rounded apart -- +-1e20 instead of 10 -- and the tile left inf (then NaN) in l and O.  Any real score
+// moves the reference from either start with alpha = 0, so every other input keeps its bits.
+constexpr float kMrefInit = -1.0e29f;
 constexpr float kLog2e = 1.44269504088896340736f;
 constexpr float kPShift = 10.0f;              // probabilities carry 2^10 into the split planes
 constexpr float kLazyLog2 = 5.0f;             // the running maximum lags by at most 2^5
@@ -110,7 +115,7 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 // MODE = 0 the path's kernel; 1 stamped diagnostic build (phase sums go to `stamps`, a buffer nothing else reads; its run time means
 //        nothing, the SHARES do); 2 timing variants selected by `dbg` (wrong results).  Modes 1 and 2 are never in the path.
 template <int HP, int MODE>
-__global__ __launch_bounds__(256, Lds<HP>::WGS) void attention_pair_kernel(const AttnArgs a, const int r1, const int r2, const int any_masked,
+__global__ __launch_bounds__(256, Lds<HP>::WGS) void attention_pair_kernel(const AttnArgs a, const int r1, const int r2,
                                                                           unsigned long long* __restrict__ stamps, const int dbg) {
     using L = Lds<HP>;
     constexpr bool DIAG = MODE == 1;
@@ -200,6 +205,8 @@ __global__ __launch_bounds__(256, Lds<HP>::WGS) void attention_pair_kernel(const
         const int qlen = a.q_limit > 0 && a.q_limit < len ? a.q_limit : len;      // queries wanted (CLS probe: the first block only)
         const int q0 = qt * QT;
         if (q0 >= qlen) continue;                      // uniform over the workgroup
+        // a masked key inside the document (a hole in the attention mask, a pad row under MMEE_FLAG_DENSE_ROWS): every tile reads the key flags
+        const bool doc_masked = a.doc_flags[a.doc_orig[doc]] != 0;
         unsigned long long tprev = 0;
         if (DIAG) tprev = stamp_now();
 
@@ -274,7 +281,7 @@ __global__ __launch_bounds__(256, Lds<HP>::WGS) void attention_pair_kernel(const
         for (int hd = 0; hd < HP; ++hd) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) { hs[hd].o0[e] = 0.f; hs[hd].o1[e] = 0.f; }
-            hs[hd].mref = kNegBig;
+            hs[hd].mref = kMrefInit;
             hs[hd].l = 0.f;
         }
 
@@ -351,7 +358,7 @@ __global__ __launch_bounds__(256, Lds<HP>::WGS) void attention_pair_kernel(const
         auto compute = [&](int kt, const int buf, const bool more) __attribute__((always_inline)) {
             const unsigned sbase = (unsigned)L::OFF_STAGE + (unsigned)buf * L::STAGE_BYTES;
             const int k0 = kt * KT;
-            const bool slow = any_masked || (k0 + KT > len);
+            const bool slow = doc_masked || (k0 + KT > len);
             if (!wave_active) {
                 if (more) {
 #pragma unroll
@@ -479,11 +486,11 @@ unsigned long long* attention_pair_stamps() { return g_attn_pair_stamps; }
 
 bool attention_pair_supports(const AttnArgs& a, int max_rel_pos, int max_rel_2d_pos) {
     const int r1 = max_rel_pos < a.c1 ? max_rel_pos : a.c1, r2 = max_rel_2d_pos < a.c2 ? max_rel_2d_pos : a.c2;
-    return r1 <= R1MAX && r2 <= R2MAX && a.ctx_split;
+    return r1 <= R1MAX && r2 <= R2MAX && a.ctx_split && a.doc_flags && a.doc_orig;
 }
 
 template <int HP>
-static void launch_pair_hp(const AttnArgs& a, int max_docs, int num_cus, int r1, int r2, int any_masked, unsigned long long* stamps, int dbg,
+static void launch_pair_hp(const AttnArgs& a, int max_docs, int num_cus, int r1, int r2, unsigned long long* stamps, int dbg,
                            hipStream_t s) {
     (void)ensure_dynamic_lds<&attention_pair_kernel<HP, 0>>("attention_pair_kernel", Lds<HP>::BYTES);
 #ifdef MMEE_DIAG
@@ -497,17 +504,18 @@ static void launch_pair_hp(const AttnArgs& a, int max_docs, int num_cus, int r1,
     if (grid < 1) grid = 1;
     const size_t lds = Lds<HP>::BYTES;
 #ifdef MMEE_DIAG      // stamped build and timing variants (wrong results): diagnostic library only
-    if (stamps) { hipLaunchKernelGGL((attention_pair_kernel<HP, 1>), dim3(grid), dim3(256), lds, s, a, r1, r2, any_masked, stamps, 0); return; }
-    if (dbg) { hipLaunchKernelGGL((attention_pair_kernel<HP, 2>), dim3(grid), dim3(256), lds, s, a, r1, r2, any_masked, (unsigned long long*)nullptr, dbg); return; }
+    if (stamps) { hipLaunchKernelGGL((attention_pair_kernel<HP, 1>), dim3(grid), dim3(256), lds, s, a, r1, r2, stamps, 0); return; }
+    if (dbg) { hipLaunchKernelGGL((attention_pair_kernel<HP, 2>), dim3(grid), dim3(256), lds, s, a, r1, r2, (unsigned long long*)nullptr, dbg); return; }
 #endif
     (void)stamps; (void)dbg;
-    hipLaunchKernelGGL((attention_pair_kernel<HP, 0>), dim3(grid), dim3(256), lds, s, a, r1, r2, any_masked, (unsigned long long*)nullptr, 0);
+    hipLaunchKernelGGL((attention_pair_kernel<HP, 0>), dim3(grid), dim3(256), lds, s, a, r1, r2, (unsigned long long*)nullptr, 0);
 }
 
 // max_rel_pos / max_rel_2d_pos: the distances at which the 1D / 2D buckets saturate (HF:392-413); the tables are clamped there.
-// any_masked: the batch may hold masked keys inside documents (MMEE_FLAG_DENSE_ROWS keeps pad rows); the tail of a document's
-// last key tile is always masked.  MMEE_ATTN_HP=1 / 2 picks the heads per work item (A/B switch; 2 needs an even head count).
-void launch_attention_pair(const AttnArgs& a, int max_docs, int num_cus, int max_rel_pos, int max_rel_2d_pos, int any_masked, hipStream_t s) {
+// a.doc_flags[a.doc_orig[doc]] != 0: the document holds a masked key inside (a hole in the attention mask; MMEE_FLAG_DENSE_ROWS keeps pad
+// rows) and every key tile of it reads the key flags; the tail of a document's last key tile is always masked.
+// MMEE_ATTN_HP=1 / 2 picks the heads per work item (A/B switch; 2 needs an even head count).
+void launch_attention_pair(const AttnArgs& a, int max_docs, int num_cus, int max_rel_pos, int max_rel_2d_pos, hipStream_t s) {
     const int r1 = max_rel_pos < a.c1 ? max_rel_pos : a.c1, r2 = max_rel_2d_pos < a.c2 ? max_rel_2d_pos : a.c2;
     // diagnostic library only (diag_env_int reads nothing in the release library): MMEE_ATTN_STAMPS=1 stamped build, phase sums readable
     // through ee_debug_attn_stamps; MMEE_ATTN_DBG timing variants (wrong results); MMEE_ATTN_HP heads per work item
@@ -521,8 +529,8 @@ void launch_attention_pair(const AttnArgs& a, int max_docs, int num_cus, int max
     int hp = hp_env == 1 || hp_env == 2 ? hp_env : kDefaultHP;
     if (a.heads % 2) hp = 1;
     g_attn_pair_stamps = stamps;
-    if (hp == 2) launch_pair_hp<2>(a, max_docs, num_cus, r1, r2, any_masked, stamps, dbg, s);
-    else launch_pair_hp<1>(a, max_docs, num_cus, r1, r2, any_masked, stamps, dbg, s);
+    if (hp == 2) launch_pair_hp<2>(a, max_docs, num_cus, r1, r2, stamps, dbg, s);
+    else launch_pair_hp<1>(a, max_docs, num_cus, r1, r2, stamps, dbg, s);
 }
 
 }  // namespace mmee

@@ -343,8 +343,8 @@ int alloc_workspace(ee_handle* h) {
             if (h->idx16) {
                 rc |= dev_alloc(h, &h->pair_idx0, Bm * (size_t)h->idx_nb * 1024);
                 rc |= dev_alloc(h, &h->keymask, Bm * (size_t)h->idx_nb);
-                rc |= dev_alloc(h, &h->doc_flags, Bm);
             }
+            rc |= dev_alloc(h, &h->doc_flags, Bm);      // attention_pair.hip (and IDX16): "a key inside the document is masked", by original document
         }
     }
     rc |= dev_alloc(h, &h->vis_raw, Bm * NP * H);

@@ -285,6 +285,8 @@ struct Forward {
         {
             ProfScope ps(h, P_PREP, s);
             launch_prep(pa, s);
+            // attention_pair.hip skips the key flags in the full key tiles of a document without a masked key inside: one word per document
+            if (sp && !use_idx) launch_doc_flags(h->meta[0], S_doc_off(0), B, h->doc_flags, s);
             if (h->pair_idx && use_idx) {    // bucket indices of every (query, key) pair, once per forward: shared by all heads and layers
                 ProfScope pi(h, P_PAIRIDX, s);
 #ifdef MMEE_DIAG
@@ -368,7 +370,7 @@ struct Forward {
     // attention_idx.hip whenever that kernel supports the shape; LayoutLMv3 only when the pair index is built (use_idx)
     void run_attn(const AttnArgs& at) {
         if (sp && (beit || use_idx) && mmee::attention_idx_supports(at)) mmee::launch_attention_idx(at, B, cus, s);
-        else if (sp) launch_attention_pair(at, B, cus, c.max_rel_pos, c.max_rel_2d_pos, (a.flags & MMEE_FLAG_DENSE_ROWS) ? 1 : 0, s);
+        else if (sp) launch_attention_pair(at, B, cus, c.max_rel_pos, c.max_rel_2d_pos, s);
         else launch_attention_f32(at, B, cus, s);
     }
 
@@ -772,7 +774,7 @@ struct Forward {
         if (h->prof_on) { h->prof_recs.clear(); h->prof_used = 0; }
         if (sp && !use_idx) {          // attention_pair.hip holds Delta tables up to fixed distances: refuse what it cannot hold
             AttnArgs chk{};
-            chk.ctx_split = 1; chk.c1 = h->c1; chk.c2 = h->c2;
+            chk.ctx_split = 1; chk.c1 = h->c1; chk.c2 = h->c2; chk.doc_flags = h->doc_flags; chk.doc_orig = S_doc_orig(0);
             if (!mmee::attention_pair_supports(chk, c.max_rel_pos, c.max_rel_2d_pos))
                 return fail(h, "ee_forward: the split-precision attention kernels cannot hold this relative-position configuration "
                                "(bins %d / %d, distances %d / %d); use MMEE_PREC_F32", c.rel_pos_bins, c.rel_2d_pos_bins, c.max_rel_pos, c.max_rel_2d_pos);

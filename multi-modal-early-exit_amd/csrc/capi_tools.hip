@@ -34,6 +34,30 @@ struct TempUpload {
     ~TempUpload() { if (dev) (void)hipFreeAsync(dev, s); }
 };
 
+// ee_debug_attention: the rows' metadata from the caller's integers, by the expression of row_meta_kernel (make_row_meta)
+__global__ void debug_row_meta_kernel(const int* __restrict__ pos, const int* __restrict__ x0, const int* __restrict__ y1,
+                                      const int* __restrict__ masked, int rows, int coord_hi, RowMeta* __restrict__ meta) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < rows) meta[i] = make_row_meta(pos[i], x0[i], y1[i], coord_hi, masked[i] == 0);
+}
+
+// Device scratch of one debug entry point: zeroed hipMalloc, freed on every way out of the scope.
+struct Scratch {
+    std::vector<void*> ptrs;
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    ~Scratch() { for (void* p : ptrs) (void)hipFree(p); }
+    template <typename T>
+    bool get(T** out, size_t count) {
+        void* q = nullptr;
+        if (hipMalloc(&q, count * sizeof(T) + 256) != hipSuccess) return false;
+        ptrs.push_back(q);
+        if (hipMemset(q, 0, count * sizeof(T) + 256) != hipSuccess) return false;
+        *out = reinterpret_cast<T*>(q);
+        return true;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -409,6 +433,135 @@ int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const
     (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads);
     if (err != hipSuccess || hipGetLastError() != hipSuccess) return fail(nullptr, "ee_debug_gemm_split: launch failed: %s", hipGetErrorString(err));
     return 0;
+}
+
+int ee_debug_attention(const float* qkv, int32_t qkv_rows, const int32_t* doc_off, int32_t n_docs, const int32_t* qkv_doc_off, const int32_t* pos,
+                       const int32_t* x0, const int32_t* y1, const int32_t* masked, const float* w1, const float* wx, const float* wy, int32_t heads,
+                       int32_t bins1, int32_t bins2, int32_t max_rel_pos, int32_t max_rel_2d_pos, int32_t max_pos, int32_t max_coord, int32_t kernel,
+                       int32_t use_queue, int32_t q_limit, int32_t terms, void* ctx, int32_t* err_flag_out, void* stream) {
+    const char* who = "ee_debug_attention";
+    const bool f32k = kernel == MMEE_ATTN_KERNEL_F32, pairk = kernel == MMEE_ATTN_KERNEL_PAIR, idxk = kernel == MMEE_ATTN_KERNEL_IDX,
+               plaink = kernel == MMEE_ATTN_KERNEL_IDX_NOBIAS;
+    if (!f32k && !pairk && !idxk && !plaink) return fail(nullptr, "%s: kernel %d is none of MMEE_ATTN_KERNEL_F32, _PAIR, _IDX, _IDX_NOBIAS", who, kernel);
+    if (!qkv || !doc_off || !pos || !x0 || !y1 || !masked || !ctx || !err_flag_out || n_docs < 1 || heads < 1 || heads > 64 || qkv_rows < 1 ||
+        q_limit < 0 || max_pos < 0 || max_pos > 4095 || max_coord < 0 || max_coord > 65535)
+        return fail(nullptr, "%s: bad argument (pointers not NULL, n_docs >= 1, 1 <= heads <= 64, q_limit >= 0, max_pos <= 4095, max_coord <= 65535)", who);
+    if (!plaink && (!w1 || !wx || !wy || bins1 < 4 || bins1 > 256 || bins2 < 4 || bins2 > 256 || max_rel_pos < 1 || max_rel_2d_pos < 1))
+        return fail(nullptr, "%s: the bias needs w1 / wx / wy, 4 <= bins <= 256 and max_rel_pos, max_rel_2d_pos >= 1", who);
+    if (terms != 3 && !(terms == 1 && idxk)) return fail(nullptr, "%s: terms is 3, or 1 for MMEE_ATTN_KERNEL_IDX (the one-term mode is built for that kernel only)", who);
+    if (f32k && (q_limit > 0 || qkv_doc_off)) return fail(nullptr, "%s: attention_f32 takes neither q_limit nor qkv_doc_off (probe-first layers are split-precision)", who);
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipDeviceProp_t prop;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(nullptr, "%s: no device", who);
+    const int cus = prop.multiProcessorCount, H = 64 * heads;
+
+    // ---- the documents: offsets, lengths, every row inside the buffers, every integer inside its range (host copies: this is a test hook) ----
+    std::vector<int> off(n_docs + 1), qoff;
+    if (hipMemcpy(off.data(), doc_off, sizeof(int) * (n_docs + 1), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of doc_off failed", who);
+    if (qkv_doc_off) {
+        qoff.resize(n_docs);
+        if (hipMemcpy(qoff.data(), qkv_doc_off, sizeof(int) * n_docs, hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of qkv_doc_off failed", who);
+    }
+    if (off[0] != 0) return fail(nullptr, "%s: doc_off[0] = %d, must be 0", who, off[0]);
+    int max_len = 0;
+    unsigned long long sum_sq = 0;
+    for (int d = 0; d < n_docs; ++d) {
+        const int len = off[d + 1] - off[d];
+        if (len < 1) return fail(nullptr, "%s: document %d has %d rows", who, d, len);
+        const int q = qkv_doc_off ? qoff[d] : off[d];
+        if (q < 0 || (long)q + len > qkv_rows) return fail(nullptr, "%s: the Q | K | V rows of document %d (%d .. %d) leave the %d rows of qkv", who, d, q, q + len, qkv_rows);
+        max_len = len > max_len ? len : max_len;
+        sum_sq += (unsigned long long)len * len;
+    }
+    const int rows = off[n_docs];
+    {
+        std::vector<int> hp(rows), hx(rows), hy(rows), hm(rows);
+        if (hipMemcpy(hp.data(), pos, sizeof(int) * rows, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hx.data(), x0, sizeof(int) * rows, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(hy.data(), y1, sizeof(int) * rows, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hm.data(), masked, sizeof(int) * rows, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(nullptr, "%s: copy of the row integers failed", who);
+        for (int i = 0; i < rows; ++i) {
+            if (hp[i] < 0 || hp[i] > max_pos) return fail(nullptr, "%s: pos[%d] = %d outside [0, max_pos = %d]", who, i, hp[i], max_pos);
+            if (hx[i] < 0 || hx[i] > max_coord || hy[i] < 0 || hy[i] > max_coord)
+                return fail(nullptr, "%s: x0 / y1 of row %d = %d / %d outside [0, max_coord = %d]", who, i, hx[i], hy[i], max_coord);
+            if (plaink && hm[i] != 0) return fail(nullptr, "%s: row %d is masked, and the image-only form of attention_idx (no pair index) has no key mask", who, i);
+        }
+    }
+
+    // ---- the operands, by the path's own code ----
+    Scratch sc;
+    const char* oom = "%s: hipMalloc of the scratch failed";
+    AttnArgs at{};
+    at.c1 = max_pos; at.n1 = 2 * max_pos + 1; at.c2 = max_coord; at.n2 = 2 * max_coord + 1;
+    at.H = H; at.heads = heads; at.max_len = max_len; at.ld = 3 * H; at.ldc = H; at.ctx = static_cast<float*>(ctx);
+    at.doc_off = doc_off; at.qkv_doc_off = qkv_doc_off; at.q_limit = q_limit; at.terms = terms;
+    at.ctx_split = f32k ? 0 : 1; at.ctx_scale = kSplitScaleCtx; at.qkv_scale = kSplitScaleQKV;
+    at.w1 = w1; at.wx = wx; at.wy = wy; at.bins1 = bins1; at.bins2 = bins2; at.inv_sqrt_d = 0.125f;      // 1 / sqrt(64)
+    RowMeta* meta = nullptr;
+    StageCounts* counts = nullptr;
+    int *err_flag = nullptr, *heads_q = nullptr, *doc_orig = nullptr, *doc_flags = nullptr;
+    if (!sc.get(&meta, rows) || !sc.get(&counts, 1) || !sc.get(&err_flag, 1) || !sc.get(&heads_q, 128) || !sc.get(&doc_orig, n_docs) || !sc.get(&doc_flags, n_docs))
+        return fail(nullptr, oom, who);
+    hipLaunchKernelGGL(debug_row_meta_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, pos, x0, y1, masked, rows, max_coord, meta);
+    const StageCounts hc{n_docs, rows, sum_sq};
+    std::vector<int> iota(n_docs);
+    for (int d = 0; d < n_docs; ++d) iota[d] = d;
+    if (hipMemcpyAsync(counts, &hc, sizeof(hc), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(doc_orig, iota.data(), sizeof(int) * n_docs, hipMemcpyHostToDevice, s) != hipSuccess)
+        return fail(nullptr, "%s: host-to-device copy failed", who);
+    launch_doc_flags(meta, doc_off, n_docs, doc_flags, s);
+    at.meta = meta; at.counts = counts; at.err_flag = err_flag; at.doc_orig = doc_orig; at.doc_flags = doc_flags;
+    at.item_counter = use_queue ? heads_q : nullptr;      // 8 XCD-local counters x 16 ints, zeroed
+    unsigned char *lut1 = nullptr, *lut2 = nullptr;
+    std::vector<unsigned char> l1(at.n1), l2(at.n2);      // outlive the asynchronous copies below: the stream is synchronised before the return
+    if (!plaink) {
+        float *t1 = nullptr, *tx = nullptr, *ty = nullptr;
+        if (!sc.get(&lut1, (size_t)at.n1 + 4) || !sc.get(&lut2, (size_t)at.n2 + 4) || !sc.get(&t1, (size_t)heads * at.n1) ||
+            !sc.get(&tx, (size_t)heads * at.n2) || !sc.get(&ty, (size_t)heads * at.n2))
+            return fail(nullptr, oom, who);
+        bucket_lut_host(bins1, max_rel_pos, at.c1, l1.data());
+        bucket_lut_host(bins2, max_rel_2d_pos, at.c2, l2.data());
+        if (hipMemcpyAsync(lut1, l1.data(), at.n1, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(lut2, l2.data(), at.n2, hipMemcpyHostToDevice, s) != hipSuccess)
+            return fail(nullptr, "%s: host-to-device copy failed", who);
+        launch_build_value_tables(w1, wx, wy, lut1, lut2, heads, bins1, bins2, at.n1, at.n2, at.inv_sqrt_d, t1, tx, ty, s);
+        at.t1 = t1; at.tx = tx; at.ty = ty; at.lut1 = lut1;
+    }
+    if (f32k) {
+        at.qkv = qkv;
+        if (attention_f32_lds_bytes(at) > 160 * 1024) return fail(nullptr, "%s: the value tables of max_pos %d / max_coord %d do not fit attention_f32's LDS", who, max_pos, max_coord);
+        launch_attention_f32(at, n_docs, cus, s);
+    } else {
+        float* qkv_s = nullptr;
+        if (!sc.get(&qkv_s, (size_t)qkv_rows * 3 * H)) return fail(nullptr, oom, who);
+        launch_split_rows(qkv, qkv_s, nullptr, qkv_rows, qkv_rows, 3 * H, kSplitScaleQKV, cus, s, err_flag);
+        at.qkv = qkv_s;
+        if (idxk) {
+            at.idx_nb = (max_len + 31) / 32;
+            at.idx_doc_stride = (size_t)at.idx_nb * at.idx_nb * 1024;
+            unsigned* pair_idx = nullptr;
+            if (!sc.get(&pair_idx, (size_t)n_docs * at.idx_doc_stride)) return fail(nullptr, oom, who);
+            at.pair_idx = pair_idx;
+        }
+        if (pairk) {
+            if (!attention_pair_supports(at, max_rel_pos, max_rel_2d_pos))
+                return fail(nullptr, "%s: attention_pair holds Delta tables of distances <= 128 / 256 (got %d / %d)", who, max_rel_pos, max_rel_2d_pos);
+            launch_attention_pair(at, n_docs, cus, max_rel_pos, max_rel_2d_pos, s);
+        } else {
+            if (!attention_idx_supports(at)) return fail(nullptr, "%s: attention_idx holds bucket tables of <= 64 bins (got %d / %d)", who, bins1, bins2);
+            if (idxk) {
+                if ((size_t)max_len * sizeof(RowMeta) + (size_t)at.n1 + at.n2 + 32 > 64 * 1024)
+                    return fail(nullptr, "%s: the pair-index kernel stages max_len rows and both LUTs in 64 KB of LDS (max_len %d, max_pos %d, max_coord %d)", who, max_len, max_pos, max_coord);
+                launch_pair_index(meta, doc_off, n_docs, at.idx_nb, lut1, at.c1, at.n1, lut2, at.c2, at.n2, bins1, const_cast<unsigned*>(at.pair_idx), at.idx_doc_stride, max_len, s);
+            }
+            launch_attention_idx(at, n_docs, cus, s);
+        }
+    }
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(nullptr, "%s: launch failed: %s", who, hipGetErrorString(e));
+    if (hipMemcpy(err_flag_out, err_flag, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of err_flag failed", who);
+    return launch_status(nullptr, who);
 }
 
 }  // extern "C"

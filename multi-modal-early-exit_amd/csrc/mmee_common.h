@@ -91,6 +91,16 @@ struct RowMeta {
     int pos, x0, y1, flags;
 };
 constexpr float kKeyMasked = -3.0e38f;
+// One row's metadata from the model's integers (row_meta_kernel in prep_embed.hip; ee_debug_attention): pos = the 1-D position index,
+// x0 / y1 = bbox[..., 0] / bbox[..., 3] clamped to the coordinate range [0, coord_hi], valid = the row is an attention key.
+__host__ __device__ inline RowMeta make_row_meta(int pos, long long x0, long long y1, int coord_hi, bool valid) {
+    RowMeta m;
+    m.pos = 4 * pos;
+    m.x0 = 4 * (int)(x0 < 0 ? 0 : (x0 > coord_hi ? coord_hi : x0));
+    m.y1 = 4 * (int)(y1 < 0 ? 0 : (y1 > coord_hi ? coord_hi : y1));
+    m.flags = __builtin_bit_cast(int, valid ? 0.0f : kKeyMasked);
+    return m;
+}
 
 // Device-resident description of one exit stage (documents still active when the stage starts).
 struct StageCounts {
@@ -443,7 +453,8 @@ struct AttnArgs {
     const unsigned char* lut1;       // [n1] 1-D bucket of delta + c1 (the delta table of a head is w1[head][lut1[.]])
     int n_visual;                    // visual rows at the end of every document (row j of a document: token j, then patch j - n_text)
     const unsigned* keymask;         // [orig doc][idx_nb]: bit j <-> key 32 kb + j masked (past the document, pad row, hole)
-    const int* doc_flags;            // [orig doc]: != 0 when a key INSIDE the document is masked (rare: MMEE_FLAG_DENSE_ROWS, holes)
+    const int* doc_flags;            // [orig doc]: != 0 when a key INSIDE the document is masked (rare: MMEE_FLAG_DENSE_ROWS, holes); read by
+                                     // attention_pair.hip (launch_doc_flags) and by the IDX16 form
 };
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -470,7 +481,7 @@ void launch_attention_idx(const AttnArgs& a, int max_docs, int num_cus, hipStrea
 void launch_pair_index(const RowMeta* meta, const int* doc_off, int n_docs, int nb, const unsigned char* lut1, int c1, int n1,
                        const unsigned char* lut2, int c2, int n2, int bins1, unsigned* out, size_t doc_stride, int max_len, hipStream_t s);
 bool attention_pair_supports(const AttnArgs& a, int max_rel_pos, int max_rel_2d_pos);
-void launch_attention_pair(const AttnArgs& a, int max_docs, int num_cus, int max_rel_pos, int max_rel_2d_pos, int any_masked, hipStream_t s);
+void launch_attention_pair(const AttnArgs& a, int max_docs, int num_cus, int max_rel_pos, int max_rel_2d_pos, hipStream_t s);
 size_t gemm_f32_lds_bytes();
 void set_gemm_wgs_per_cu(int n);
 void launch_gemm_f32_stamped(const GemmArgs& a, int epi, int grid, hipStream_t s);   // diagnostic build with in-kernel stamps

@@ -198,6 +198,8 @@ void launch_preprocess_images(const unsigned char* images, const ImageDesc* desc
 void launch_collate_pad(const long long* ids, const long long* boxes, const long long* offsets, int B, int T, long long pad_id,
                         long long* out_ids, long long* out_mask, long long* out_bbox, hipStream_t s);
 void launch_prep(const PrepArgs& a, hipStream_t s);
+// doc_flags[d] = 1 when a key INSIDE document d is masked (any row of it with RowMeta.flags != 0), else 0; d in the numbering of doc_off
+void launch_doc_flags(const RowMeta* meta, const int* doc_off, int n_docs, int* doc_flags, hipStream_t s);
 void launch_prep_uniform(int B, int Pv, int* doc_off, int* x_src, int* doc_orig, RowMeta* meta, StageCounts* counts, hipStream_t s);
 void launch_embed_text(const EmbedArgs& a, hipStream_t s);
 void launch_embed_visual(const EmbedArgs& a, hipStream_t s);

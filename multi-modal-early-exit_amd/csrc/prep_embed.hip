@@ -150,14 +150,8 @@ __global__ __launch_bounds__(256) void row_meta_kernel(PrepArgs a) {
     for (int j = tid; j < T; j += 256) {
         const int dst = a.text_dst[(size_t)b * T + j];
         if (dst >= 0) {
-            RowMeta m;
-            m.pos = 4 * j;
-            long long x0 = a.bbox[((size_t)b * T + j) * 4 + 0], y1 = a.bbox[((size_t)b * T + j) * 4 + 3];
-            m.x0 = 4 * (int)(x0 < 0 ? 0 : (x0 > hi ? hi : x0));
-            m.y1 = 4 * (int)(y1 < 0 ? 0 : (y1 > hi ? hi : y1));
             const bool valid = a.attention_mask ? (a.attention_mask[(size_t)b * T + j] != 0) : true;
-            m.flags = __float_as_int(valid ? 0.0f : kKeyMasked);
-            a.meta[off + dst] = m;
+            a.meta[off + dst] = make_row_meta(j, a.bbox[((size_t)b * T + j) * 4 + 0], a.bbox[((size_t)b * T + j) * 4 + 3], hi, valid);
         }
     }
     for (int v = tid; v < a.Pv; v += 256) {
@@ -174,6 +168,24 @@ __global__ __launch_bounds__(256) void row_meta_kernel(PrepArgs a) {
         m.flags = __float_as_int(0.0f);
         a.meta[off + nt + v] = m;
     }
+}
+
+// "A key inside this document is masked" (a hole in the attention mask; a pad row under MMEE_FLAG_DENSE_ROWS), one word per document: what
+// attention_pair.hip reads once per work item to decide whether the document's full key tiles may skip the key flags.  The decision follows
+// from the rows themselves, on the device: one wave per document over its rows' flags.
+__global__ __launch_bounds__(64) void doc_flags_kernel(const RowMeta* __restrict__ meta, const int* __restrict__ doc_off, int n_docs,
+                                                       int* __restrict__ doc_flags) {
+    const int d = blockIdx.x;
+    if (d >= n_docs) return;
+    const int off = doc_off[d], len = doc_off[d + 1] - off;
+    int any = 0;
+    for (int i = threadIdx.x; i < len; i += 64) any |= meta[off + i].flags != 0 ? 1 : 0;
+    any = __any(any) ? 1 : 0;
+    if (threadIdx.x == 0) doc_flags[d] = any;
+}
+
+void launch_doc_flags(const RowMeta* meta, const int* doc_off, int n_docs, int* doc_flags, hipStream_t s) {
+    hipLaunchKernelGGL(doc_flags_kernel, dim3(n_docs), dim3(64), 0, s, meta, doc_off, n_docs, doc_flags);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -355,6 +355,40 @@ def test_wide_bucket_tables_run_the_delta_table_attention(pkg, oracle, bins):
     eng.close()
 
 
+def test_wide_bucket_tables_mask_holes_in_full_key_tiles(pkg, oracle):
+    """csrc/attention_pair.hip and holes in the attention mask (the two tests above and test_gpu_round6.py's holes test never met): a hole stays a
+    row, masked as a key, and the pair kernel's fast key tiles never read a key's flags -- so whether a document takes them must follow from
+    the document (a per-document word the row-metadata pass raises), not from MMEE_FLAG_DENSE_ROWS.  Holes inside FULL 32-key tiles, both row
+    layouts, against the live oracle."""
+    ee = dict(exits=["text_visual_concat", 1, 2, 3], encoder_layer_strategy="ramp")
+    cfg = pkg.ModelConfig.tiny(EE_config=ee, hidden_size=256, num_attention_heads=4, intermediate_size=512, num_hidden_layers=3,
+                               coordinate_size=48, shape_size=32, rel_pos_bins=128, rel_2d_pos_bins=64)
+    W = pkg.synth.make_weights(cfg, seed=22)
+    docs = pkg.synth.make_documents(cfg, 6, seed=22, text_len=64, min_words=20)
+    rng = np.random.default_rng(5)
+    am = docs["attention_mask"]
+    in_full_tile = 0
+    for b in range(6):                                   # holes in the valid range (never position 0), one document masked almost entirely
+        n = int(am[b].sum())
+        holes = rng.choice(np.arange(1, n - 1), size=(n - 3) if b == 5 else max(1, n // 4), replace=False)
+        am[b, holes] = 0
+        rows = int(np.nonzero(am[b])[0].max()) + 1 + 17    # the prefix up to the last kept token + (64 / 16)^2 + 1 visual rows
+        in_full_tile += int(((holes // 32 + 1) * 32 <= rows).sum())
+    assert in_full_tile >= 6
+    ref = oracle.forward_all(cfg, W, docs, ee["exits"], strategy="ramp")
+    eng = pkg.EarlyExitEngine(cfg, max_docs=6, max_text_len=64, precision="split", xprobe=False)
+    assert eng.precision == "split"
+    eng.load_weights(W)
+    args = (docs["input_ids"], docs["attention_mask"], docs["bbox"], docs["pixel_values"])
+    errs = {}
+    for dense in (False, True):
+        out = eng.forward(*args, dump_all=True, want_all=True, validate=True, dense_rows=dense)
+        errs[dense] = float(np.abs(_np(out.all_logits) - ref["logits_store"]).max())
+        report_measured(f"wide_buckets_holes[dense={int(dense)}]", "max|dlogit| vs oracle", errs[dense])
+    eng.close()
+    assert errs[False] <= LOGIT_TOL and errs[True] <= LOGIT_TOL, errs
+
+
 @pytest.mark.parametrize("precision", ["split", "fp32"])
 def test_bench_size_early_exit_properties(pkg, oracle, precision):
     """BASELINE configs[1] shape (base, exits 2/4/6/8/10 + final, T = 512, ragged documents) at a size no CPU oracle
