@@ -18,6 +18,7 @@
  *   ee_policy_scan                              <- Policy.* on a dumped (E+1, N, K) logits array (EE/policy.py:28-45,
  *                                                 87-104; called from EE/eval.py:87-98).
  *   ee_threshold_sweep                          <- thresh.opt1 / large_scale.opt0_2D vectorised exit-index search
+ *   ee_threshold_search                         <- large_scale.generate_thresholds + the sweep + the Pareto front the reference stops short of
  *                                                 (EE/thresh.py:184-215, EE/large_scale.py:68-84).
  *   ee_set_patience / ee_patience_scan /        <- EarlyExitInference.PATIENCE, declared by the reference (EE/models/EE_modules.py:
  *   ee_patience_sweep                              123-124, PABEE: Zhou et al., NeurIPS 2020) but not implemented there; semantics below.
@@ -484,6 +485,52 @@ int ee_msp_table(const double* logits, const int64_t* references, int32_t E1, in
  * NULL, references dev int64 (N,) (may be NULL with correct NULL). */
 int ee_csf_table(const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, int32_t criterion, double* table,
                  uint8_t* correct, void* stream);
+
+/*
+ * The threshold search: which thresholds should a deployment run?  Candidate thresholds from the percentiles of the confidence table, V candidate
+ * vectors scored as ee_threshold_sweep / ee_rule_sweep score them, and the accuracy / mean-exit Pareto front of the scores, in one call on the
+ * device (EE/large_scale.py:46-65 builds the candidates on the host and stops at a dump of every vector's result).  No threshold is uploaded and
+ * no per-vector result has to come back.
+ *
+ * Inputs: conf dev double (E1,N) (for a '<' criterion pass the negated table, which is exact; the thresholds that come back are then negated too),
+ * correct dev uint8 (E1,N), P = thresholds per exit; 2 <= E1 <= 64, 1 <= N < 2^24, 2 <= P <= 64.
+ *
+ * Percentile table, dev double (E1,P): table[e][j] = np.percentile(conf[e], linspace(0, 100, P)[j]) (linear method) for e < E1-1, bit for bit:
+ *   q_j = (j * (100 / (P-1))) / 100, the last one 100 / 100; virtual index x = (N-1) * q_j in double; x >= N-1: lo = hi = N-1, t = x + 1; else
+ *   lo = floor(x), hi = lo + 1, t = x - lo (functions of N and P only, computed once on the host).  With a = sorted[e][lo], b = sorted[e][hi]:
+ *   table = a + (b - a) * t, and b - (b - a) * (1 - t) where t >= 0.5 -- numpy's two-branch lerp, every product rounded before it is added (no fma).
+ *   Row E1-1 is 0.0, as generate_thresholds leaves it.
+ * Rank table trank[e][j] (internal): the rank of table[e][j] in the sorted row e by the sweeps' rule -- #{m : conf[e][m] < table[e][j]} under
+ *   MMEE_SEARCH_REFERENCE, #{m : conf[e][m] <= table[e][j]} under MMEE_SEARCH_POLICY -- so that the integers of a search are exactly those
+ *   ee_threshold_sweep / the policy give for the reported vectors.
+ *
+ * Candidate vectors: V of them, vector v = E1 digits d_e(v) in [0, P), its thresholds table[e][d_e(v)]; the final exit's digit is unused.
+ *   MMEE_SEARCH_GRID      the whole grid: V = P^(E1-1) (the argument V is ignored), d_e(v) = (v / P^e) % P.  Refused when V >= 2^32.
+ *   MMEE_SEARCH_SAMPLED   1 <= V < 2^32 draws: d_e(v) = ((splitmix64(seed + (v * E1 + e + 1) * 0x9E3779B97F4A7C15) >> 32) * P) >> 32 in 64-bit
+ *                         wrap-around arithmetic, splitmix64(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *                         z ^ z >> 31.  A pure function of (seed, v, e).
+ *   MMEE_SEARCH_MIXTURES  mixtures dev uint8 (V,E1), 1 <= V < 2^32: the caller's digits (the reference's np.random.seed(42) draw, for one).  A
+ *                         digit >= P is the caller's error: it is clamped to P-1 so that nothing is read out of bounds.
+ *
+ * Exit rule per (vector, document):
+ *   MMEE_SEARCH_REFERENCE  ee_threshold_sweep's: the first e with conf[e,n] >= threshold, exit 0 when none fires (the zero last row fires for
+ *                          every confidence >= 0).
+ *   MMEE_SEARCH_POLICY     what a forward does: the first e < E1-1 with conf[e,n] > threshold (strict), else the final exit E1-1; the last
+ *                          threshold is unused.
+ * Per vector: hits(v) = sum_n correct[exit, n], exit_sum(v) = sum_n exit, integers; acc / mean_exit dev double (V,) or NULL = sum / N.
+ *
+ * Front: over exit_sum = 0 .. N (E1-1) (N (E1-1) + 1 buckets, refused above 2^26), bucket[exit_sum] = max_v (hits << 32 | (0xFFFFFFFF - v)):
+ * the most hits among the vectors of one exit sum, ties to the LOWEST v.  A bucket is on the front iff some vector has its exit sum and its hits
+ * exceed the hits of every bucket of lower exit sum: the strict Pareto front of (fewer exits, more hits).  Deterministic; no sort.  Outputs dev,
+ * ascending by exit sum: front_count int32 [1], front_exit_sum int32, front_hits int32, front_vector uint32 (N+1 entries each) and
+ * front_thresholds double (N+1, E1) = table[e][d_e(v)] of the entry's vector (column E1-1: 0.0).  Hits rise strictly along the front, so N+1
+ * entries always suffice; entries past front_count are not written.
+ */
+enum { MMEE_SEARCH_GRID = 0, MMEE_SEARCH_SAMPLED = 1, MMEE_SEARCH_MIXTURES = 2 };
+enum { MMEE_SEARCH_REFERENCE = 0, MMEE_SEARCH_POLICY = 1 };
+int ee_threshold_search(const double* conf, const uint8_t* correct, int32_t E1, int32_t N, int32_t P, int32_t source, int64_t V, uint64_t seed,
+                        const uint8_t* mixtures, int32_t semantics, double* table, double* acc, double* mean_exit, int32_t* front_count,
+                        int32_t* front_exit_sum, int32_t* front_hits, uint32_t* front_vector, double* front_thresholds, void* stream);
 
 /*
  * Per-exit temperature fit on the device (TemperatureScaler.set_temperature, EE/generic_scaling.py:64-111, as driven per

@@ -22,6 +22,8 @@ FLAG_LOW_LATENCY = 64
 FLAG_STREAM_RESULTS = 128
 CRIT_MAX_CONFIDENCE, CRIT_ENTROPY, CRIT_PATIENCE, CRIT_MARGIN = 0, 1, 2, 3
 RULE_PLAIN, RULE_STREAK, RULE_EITHER = 0, 1, 2
+SEARCH_GRID, SEARCH_SAMPLED, SEARCH_MIXTURES = 0, 1, 2
+SEARCH_REFERENCE, SEARCH_POLICY = 0, 1
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 CLOCK_STAMP_WORDS = 4096       # MMEE_CLOCK_STAMP_WORDS
 ATTN_KERNEL_F32, ATTN_KERNEL_PAIR, ATTN_KERNEL_IDX, ATTN_KERNEL_IDX_NOBIAS = 0, 1, 2, 3
@@ -102,6 +104,7 @@ SYMBOLS = {
     "ee_pack_results": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "ee_unpack_results": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ee_threshold_sweep": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "ee_threshold_search": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.c_int64, C.c_uint64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ee_msp_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_csf_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_debug_gemm": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),

@@ -1,5 +1,6 @@
 // Entry points of libmmee_hip.so that never see a handle: bucket LUT, shader-clock stamps, policy / patience / threshold sweeps, temperature
 // fit, result packing, the device-side input feed, and the ee_debug_* hooks that run one kernel on caller-provided buffers.
+#include <math.h>
 #include <string.h>
 
 #include <vector>
@@ -249,6 +250,57 @@ int ee_threshold_sweep(const double* conf, const uint8_t* correct, int32_t E1, i
     if (!have_device("ee_threshold_sweep")) return 1;
     if (V > 0) launch_threshold_sweep(conf, correct, E1, N, thr, V, acc, mean_exit, exit_hist, reinterpret_cast<hipStream_t>(stream));
     return launch_status(nullptr, "ee_threshold_sweep");
+}
+
+int ee_threshold_search(const double* conf, const uint8_t* correct, int32_t E1, int32_t N, int32_t P, int32_t source, int64_t V, uint64_t seed,
+                        const uint8_t* mixtures, int32_t semantics, double* table, double* acc, double* mean_exit, int32_t* front_count,
+                        int32_t* front_exit_sum, int32_t* front_hits, uint32_t* front_vector, double* front_thresholds, void* stream) {
+    const char* who = "ee_threshold_search";
+    if (!conf || !correct || !table || !front_count || !front_exit_sum || !front_hits || !front_vector || !front_thresholds)
+        return fail(nullptr, "%s: NULL argument (conf, correct, table and the five front outputs are required; acc and mean_exit may be NULL)", who);
+    if (E1 < 2 || E1 > 64) return fail(nullptr, "%s: E1 = %d, need 2 <= E1 <= 64", who, E1);
+    if (N < 1 || N >= (1 << 24)) return fail(nullptr, "%s: N = %d, need 1 <= N < 2^24 (a rank takes 24 bits of a record)", who, N);
+    if (P < 2 || P > 64) return fail(nullptr, "%s: P = %d thresholds per exit, need 2 <= P <= 64", who, P);
+    if (semantics != MMEE_SEARCH_REFERENCE && semantics != MMEE_SEARCH_POLICY)
+        return fail(nullptr, "%s: semantics %d is neither MMEE_SEARCH_REFERENCE nor MMEE_SEARCH_POLICY", who, semantics);
+    if (source == MMEE_SEARCH_GRID) {
+        unsigned long long grid = 1;
+        for (int e = 0; e < E1 - 1 && grid < (1ull << 32); ++e) grid *= (unsigned long long)P;
+        if (grid >= (1ull << 32))
+            return fail(nullptr, "%s: the grid of P = %d thresholds at %d exits has P^(E1-1) >= 2^32 vectors; sample it (MMEE_SEARCH_SAMPLED with V < 2^32)", who, P, E1 - 1);
+        V = (int64_t)grid;
+    } else if (source == MMEE_SEARCH_SAMPLED || source == MMEE_SEARCH_MIXTURES) {
+        if (V < 1 || V >= (1ll << 32)) return fail(nullptr, "%s: V = %lld vectors, need 1 <= V < 2^32", who, (long long)V);
+        if (source == MMEE_SEARCH_MIXTURES && !mixtures) return fail(nullptr, "%s: MMEE_SEARCH_MIXTURES without mixtures (NULL)", who);
+    } else {
+        return fail(nullptr, "%s: source %d is none of MMEE_SEARCH_GRID, _SAMPLED, _MIXTURES", who, source);
+    }
+    const long long n_buckets = (long long)N * (E1 - 1) + 1;
+    if (n_buckets > (1ll << 26))
+        return fail(nullptr, "%s: N (E1-1) + 1 = %lld exit-sum buckets, more than 2^26", who, n_buckets);
+    if (!have_device(who)) return 1;
+    // the percentiles' (lower index, upper index, weight): numpy's linspace, true_divide, (n - 1) * q, floor, in double
+    SearchPercentiles pc{};
+    const double step = 100.0 / (double)(P - 1);
+    for (int j = 0; j < P; ++j) {
+        const double perc = j == P - 1 ? 100.0 : (double)j * step;
+        const double x = (double)(N - 1) * (perc / 100.0);
+        if (x >= (double)(N - 1)) {
+            pc.lo[j] = pc.hi[j] = N - 1;                            // numpy: previous = next = -1, gamma = x - (-1); the neighbours are equal
+            pc.t[j] = x + 1.0;
+        } else {
+            const double f = floor(x);
+            pc.lo[j] = (int)f;
+            pc.hi[j] = (int)f + 1;
+            pc.t[j] = x - f;
+        }
+    }
+    SearchArgs a{};
+    a.conf = conf; a.correct = correct; a.E1 = E1; a.N = N; a.P = P; a.source = source; a.semantics = semantics; a.V = (unsigned)V; a.seed = seed;
+    a.mixtures = mixtures; a.table = table; a.acc = acc; a.mean_exit = mean_exit; a.front_count = front_count; a.front_exit_sum = front_exit_sum;
+    a.front_hits = front_hits; a.front_vector = front_vector; a.front_thresholds = front_thresholds;
+    if (!launch_threshold_search(a, pc, reinterpret_cast<hipStream_t>(stream))) return fail(nullptr, "%s: hipMallocAsync of the workspace failed", who);
+    return launch_status(nullptr, who);
 }
 
 int ee_msp_table(const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, double* conf, uint8_t* correct,

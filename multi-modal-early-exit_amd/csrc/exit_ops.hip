@@ -371,30 +371,25 @@ __global__ __launch_bounds__(256, 2) void sweep_main_kernel(const unsigned* __re
     }
 }
 
-// The ranking step of the two ranked sweeps: rec (zeroed, then sweep_rank_kernel), sorted, and T = the thresholds' ranks (sweep_thr_kernel).
-// ok == false: an allocation failed and nothing was launched.  The workspace is freed in stream order when the object goes out of scope.
-struct SweepRanks {
-    unsigned *rec = nullptr, *T = nullptr;
-    double* sorted = nullptr;
-    hipStream_t s;
-    bool ok;
-    SweepRanks(const double* conf, const unsigned char* correct, int E1, int E1P, int N, const double* thr, int V, int strict, hipStream_t stream)
-        : s(stream) {
-        ok = hipMallocAsync((void**)&rec, (size_t)N * E1P * 4, s) == hipSuccess && hipMallocAsync((void**)&T, (size_t)V * E1 * 4, s) == hipSuccess &&
-             hipMallocAsync((void**)&sorted, (size_t)E1 * N * 8, s) == hipSuccess;
-        if (!ok) { (void)hipGetLastError(); return; }
-        (void)hipMemsetAsync(rec, 0, (size_t)N * E1P * 4, s);
-        hipLaunchKernelGGL(sweep_rank_kernel, dim3((N + 255) / 256, E1), dim3(256), 0, s, conf, correct, E1, E1P, N, rec, sorted);
-        const long long VE = (long long)V * E1;
-        hipLaunchKernelGGL(sweep_thr_kernel, dim3(grid_1d(VE, 256, 65536)), dim3(256), 0, s, sorted, thr, E1, N, VE, T, strict);
-    }
-    SweepRanks(const SweepRanks&) = delete;
-    ~SweepRanks() {
-        if (rec) (void)hipFreeAsync(rec, s);
-        if (T) (void)hipFreeAsync(T, s);
-        if (sorted) (void)hipFreeAsync(sorted, s);
-    }
-};
+// The ranking step of the ranked sweeps and of the threshold search (SweepRanks, mmee_kernels.h): rec (zeroed, then sweep_rank_kernel), sorted,
+// and, with thr, T = the thresholds' ranks (sweep_thr_kernel).
+SweepRanks::SweepRanks(const double* conf, const unsigned char* correct, int E1, int E1P, int N, const double* thr, int V, int strict, hipStream_t stream)
+    : s(stream) {
+    const bool with_T = thr && V > 0;
+    ok = hipMallocAsync((void**)&rec, (size_t)N * E1P * 4, s) == hipSuccess && (!with_T || hipMallocAsync((void**)&T, (size_t)V * E1 * 4, s) == hipSuccess) &&
+         hipMallocAsync((void**)&sorted, (size_t)E1 * N * 8, s) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); return; }
+    (void)hipMemsetAsync(rec, 0, (size_t)N * E1P * 4, s);
+    hipLaunchKernelGGL(sweep_rank_kernel, dim3((N + 255) / 256, E1), dim3(256), 0, s, conf, correct, E1, E1P, N, rec, sorted);
+    if (!with_T) return;
+    const long long VE = (long long)V * E1;
+    hipLaunchKernelGGL(sweep_thr_kernel, dim3(grid_1d(VE, 256, 65536)), dim3(256), 0, s, sorted, thr, E1, N, VE, T, strict);
+}
+SweepRanks::~SweepRanks() {
+    if (rec) (void)hipFreeAsync(rec, s);
+    if (T) (void)hipFreeAsync(T, s);
+    if (sorted) (void)hipFreeAsync(sorted, s);
+}
 
 void launch_threshold_sweep(const double* conf, const unsigned char* correct, int E1, int N, const double* thr, int V,
                             double* acc, double* mean_exit, int* hist, hipStream_t s) {

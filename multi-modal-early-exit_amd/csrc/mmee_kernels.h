@@ -232,12 +232,54 @@ void launch_rows_to_padded(const float* X, float split_inv, int H, int B, int T,
 void launch_gather_cls(const float* X, int H, const int* x_phys, const int* doc_orig, const int* n_docs_ptr,
                        float* out, int max_docs, hipStream_t s, float split_inv = 0.f);
 void launch_exit_scan(const ScanArgs& a, int event, int rule, hipStream_t s);
+// The ranking step of the ranked sweeps and of the threshold search (exit_ops.hip): rec[n][e] = rank << 8 | correct << 6 | e of every document
+// (rows of E1P words), sorted (E1, N) = every exit's confidences ascending and, when thr is given, T (V, E1) = the thresholds' rank words.
+// ok == false: an allocation failed and nothing was launched.  The workspace is freed in stream order when the object goes out of scope.
+struct SweepRanks {
+    unsigned *rec = nullptr, *T = nullptr;
+    double* sorted = nullptr;
+    hipStream_t s;
+    bool ok;
+    SweepRanks(const double* conf, const unsigned char* correct, int E1, int E1P, int N, const double* thr, int V, int strict, hipStream_t stream);
+    SweepRanks(const SweepRanks&) = delete;
+    ~SweepRanks();
+};
 bool launch_rule_sweep(const double* conf, const double* logits, const long long* refs, int E1, int N, int K, const double* thr, int V,
                        const int* pats_host, const int* pats_dev, int P, int rule, double* acc, double* mean_exit, int* hist, hipStream_t s);
 bool launch_patience_sweep(const double* logits, const long long* refs, int E1, int N, int K, const int* pats, int V, double* acc,
                            double* mean_exit, int* hist, hipStream_t s);
 void launch_threshold_sweep(const double* conf, const unsigned char* correct, int E1, int N, const double* thr, int V,
                             double* acc, double* mean_exit, int* hist, hipStream_t s);
+// ee_threshold_search (threshold_search.hip; include/mmee.h MMEE_SEARCH_*, capi_internal.h asserts the values agree)
+enum { SEARCH_GRID = 0, SEARCH_SAMPLED = 1, SEARCH_MIXTURES = 2 };
+enum { SEARCH_REFERENCE = 0, SEARCH_POLICY = 1 };
+// the P percentiles as (lower index, upper index, weight) in the sorted row: functions of N and P only, computed on the host in numpy's own
+// index arithmetic.  A kernel ARGUMENT of search_table_kernel.
+struct SearchPercentiles {
+    int lo[64], hi[64];
+    double t[64];
+};
+// where the candidate vectors' digits come from: a kernel argument of search_main_kernel and search_front_kernel
+struct SearchVectors {
+    int source;                      // SEARCH_*
+    unsigned V;                      // vectors, 1 <= V < 2^32
+    unsigned long long seed;         // SEARCH_SAMPLED
+    const unsigned char* mixtures;   // SEARCH_MIXTURES: (V,E1) digits
+};
+struct SearchArgs {
+    const double* conf;              // (E1,N)
+    const unsigned char* correct;    // (E1,N)
+    int E1, N, P, source, semantics;
+    unsigned V;
+    unsigned long long seed;
+    const unsigned char* mixtures;
+    double* table;                   // (E1,P)
+    double *acc, *mean_exit;         // (V,) or null
+    int *front_count, *front_exit_sum, *front_hits;      // [1], [N + 1], [N + 1]
+    unsigned* front_vector;          // [N + 1]
+    double* front_thresholds;        // (N + 1, E1)
+};
+bool launch_threshold_search(const SearchArgs& a, const SearchPercentiles& pc, hipStream_t s);
 // criterion: CRIT_MAX_CONFIDENCE, CRIT_ENTROPY or CRIT_MARGIN
 void launch_csf_table(const double* logits, const long long* refs, int E1, int N, int K, int criterion, double* table, unsigned char* correct,
                       hipStream_t s);

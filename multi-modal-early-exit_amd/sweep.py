@@ -8,6 +8,8 @@ handles one threshold vector.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 
@@ -149,3 +151,149 @@ def threshold_sweep(conf, correct, thresholds, want_hist: bool = False, device=N
         capi.check(lib.ee_threshold_sweep(_ptr(cf), _ptr(cr), E1, N, _ptr(th), V, _ptr(acc), _ptr(mex), _ptr(hist), _stream()), None,
                    "ee_threshold_sweep")
     return acc, mex, hist
+
+
+_MASK64 = (1 << 64) - 1
+
+
+def search_digits(source, v, E1: int, P: int, seed: int = 0, mixtures=None):
+    """The E1 - 1 digits of candidate vector ``v`` of a threshold search, by the rules of include/mmee.h (MMEE_SEARCH_GRID / _SAMPLED /
+    _MIXTURES): plain Python integers, no device."""
+    v = int(v)
+    if source == capi.SEARCH_GRID:
+        return [(v // P ** e) % P for e in range(E1 - 1)]
+    if source == capi.SEARCH_SAMPLED:
+        out = []
+        for e in range(E1 - 1):
+            z = (seed + (v * E1 + e + 1) * 0x9E3779B97F4A7C15) & _MASK64
+            z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+            z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+            z ^= z >> 31
+            out.append(((z >> 32) * P) >> 32)
+        return out
+    return [min(int(d), P - 1) for d in np.asarray(mixtures)[v, :E1 - 1]]
+
+
+@dataclass
+class SearchResult:
+    """What ``threshold_search`` found.  The front is on the host (numpy), ascending by mean exit and, strictly, by accuracy; ``accuracy`` /
+    ``mean_exit`` of all V vectors (``want_all=True``) stay device tensors.  Thresholds are REAL thresholds of the criterion (for entropy: the
+    negated table negated back), so that a row goes to ``forward(thresholds=)`` unchanged."""
+    table: np.ndarray                       # (E1, P) candidate thresholds per exit; row E1 - 1 is 0
+    front_thresholds: np.ndarray            # (F, E1)
+    front_accuracy: np.ndarray              # (F,) hits / N
+    front_mean_exit: np.ndarray             # (F,) exit_sum / N
+    front_vector: np.ndarray                # (F,) uint32 indices of the front's vectors
+    front_hits: np.ndarray                  # (F,) int32
+    front_exit_sum: np.ndarray              # (F,) int32
+    num_vectors: int
+    num_samples: int
+    source: int
+    seed: int = 0
+    mixtures: Optional[np.ndarray] = None
+    accuracy: Optional["torch.Tensor"] = None
+    mean_exit: Optional["torch.Tensor"] = None
+
+    def digits(self, v):
+        """The percentile index per exit (E1 - 1 of them) of candidate vector ``v``: ``table[e, digits(v)[e]]`` are its thresholds."""
+        if not 0 <= int(v) < self.num_vectors:
+            raise IndexError(f"vector {v} of {self.num_vectors}")
+        return search_digits(self.source, v, self.table.shape[0], self.table.shape[1], self.seed, self.mixtures)
+
+    def select(self, min_accuracy=None, max_mean_exit=None):
+        """One operating point of the front as a plain list of E1 floats (what ``EarlyExitEngine.forward(thresholds=)`` and
+        ``model.early_exit(thresholds=)`` take): with ``min_accuracy`` the entry of LOWEST mean exit whose accuracy reaches it, with
+        ``max_mean_exit`` the entry of HIGHEST accuracy within the budget.  Exactly one of the two; ``ValueError`` when no entry qualifies."""
+        return self.front_thresholds[self.select_index(min_accuracy, max_mean_exit)].tolist()
+
+    def select_index(self, min_accuracy=None, max_mean_exit=None) -> int:
+        if (min_accuracy is None) == (max_mean_exit is None):
+            raise ValueError("select takes exactly one of min_accuracy and max_mean_exit")
+        if min_accuracy is not None:
+            ok = np.nonzero(self.front_accuracy >= float(min_accuracy))[0]
+            if not len(ok):
+                raise ValueError(f"no front entry reaches accuracy {min_accuracy} (best: {self.front_accuracy.max() if len(self.front_accuracy) else None})")
+            return int(ok[0])                   # accuracy rises along the front: the first is the cheapest
+        ok = np.nonzero(self.front_mean_exit <= float(max_mean_exit))[0]
+        if not len(ok):
+            raise ValueError(f"no front entry has a mean exit <= {max_mean_exit} (lowest: {self.front_mean_exit.min() if len(self.front_mean_exit) else None})")
+        return int(ok[-1])
+
+
+_SEARCH_SEMANTICS = {"reference": capi.SEARCH_REFERENCE, "policy": capi.SEARCH_POLICY}
+
+
+def threshold_search(logits, references=None, criterion="max_confidence", num_per_exit: int = 10, mixtures="grid", seed: int = 42,
+                     semantics: str = "policy", want_all: bool = False, device=None) -> SearchResult:
+    """Which thresholds should a deployment run?  Candidate thresholds = ``num_per_exit`` percentiles of every exit's criterion table
+    (``np.percentile(table[e], linspace(0, 100, num_per_exit))`` bit for bit), candidate vectors = ``mixtures`` of them, each scored on the
+    dumped array, and the accuracy / mean-exit Pareto front of the scores, all on the device (ee_threshold_search; include/mmee.h).
+
+    ``logits`` (E1,N,K) with ``references`` (N,), or a precomputed pair ``(table, correct)`` as ``csf_table(..., as_csf=True)`` returns it
+    (``references`` is then not read).  ``mixtures``: ``"grid"`` -- all ``num_per_exit ** (E1 - 1)`` vectors --, an int V -- V vectors drawn by the
+    counter-based hash of ``seed`` --, or an integer array (V,E1) of percentile indices (the reference's own ``np.random.randint`` draw, for
+    one).  ``semantics``: ``"policy"`` -- what a forward does: strict compare, the final exit when nothing fires -- or ``"reference"`` --
+    ``threshold_sweep``'s ``>=`` / exit 0.  ``want_all`` also returns the accuracy and mean exit of every vector (device tensors)."""
+    from .policy import threshold_criterion
+    st = threshold_criterion(criterion)
+    if semantics not in _SEARCH_SEMANTICS:
+        raise ValueError(f'semantics "{semantics}": choose "policy" or "reference"')
+    P = int(num_per_exit)
+    if not 2 <= P <= 64:
+        raise ValueError(f"num_per_exit = {num_per_exit}: 2 .. 64 thresholds per exit")
+    pair = isinstance(logits, tuple)
+    if pair:
+        if len(logits) != 2:
+            raise ValueError("a precomputed table is the pair (table (E1,N), correct (E1,N))")
+        E1 = int(logits[0].shape[0])
+    else:
+        if references is None:
+            raise ValueError("logits need the references")
+        E1 = int(np.shape(logits)[0])
+    mix_host = None
+    if isinstance(mixtures, str):
+        if mixtures != "grid":
+            raise ValueError('mixtures: "grid", a number of sampled vectors, or an array (V,E1) of percentile indices')
+        source, V = capi.SEARCH_GRID, P ** (E1 - 1)
+        if V >= 1 << 32:
+            raise ValueError(f"the grid of {P} thresholds at {E1 - 1} exits has {P}^{E1 - 1} >= 2^32 vectors: sample it (mixtures=V)")
+    elif np.ndim(mixtures) == 0:
+        source, V = capi.SEARCH_SAMPLED, int(mixtures)
+        if not 1 <= V < 1 << 32:
+            raise ValueError("mixtures = V: 1 <= V < 2^32 sampled vectors")
+    else:
+        mix_host = mixtures.cpu().numpy() if torch is not None and isinstance(mixtures, torch.Tensor) else np.asarray(mixtures)
+        if mix_host.ndim != 2 or mix_host.shape[1] != E1 or mix_host.shape[0] < 1 or mix_host.dtype.kind not in "iu":
+            raise ValueError(f"mixtures: an integer array (V,{E1}) of percentile indices, V >= 1")
+        if mix_host[:, :E1 - 1].min() < 0 or mix_host[:, :E1 - 1].max() >= P:
+            raise ValueError(f"mixtures: every percentile index must be in [0, {P})")
+        mix_host = np.clip(mix_host, 0, P - 1).astype(np.uint8)        # the final exit's digit is unused
+        source, V = capi.SEARCH_MIXTURES, int(mix_host.shape[0])
+    lib = capi.load()
+    dev = _require_torch_cuda(device)
+    if pair:
+        cf, cr = _f64_on(dev, logits[0]), _on(dev, logits[1], torch.uint8)
+    else:
+        cf, cr = csf_table(logits, references, criterion=st, as_csf=True, device=dev)
+    if cf.dim() != 2 or tuple(cr.shape) != tuple(cf.shape):
+        raise ValueError("table (E1,N), correct (E1,N)")
+    E1, N = cf.shape
+    mix = torch.from_numpy(mix_host).to(dev) if mix_host is not None else None
+    table = torch.empty((E1, P), dtype=torch.float64, device=dev)
+    acc = torch.empty((V,), dtype=torch.float64, device=dev) if want_all else None
+    mex = torch.empty((V,), dtype=torch.float64, device=dev) if want_all else None
+    f_count = torch.zeros((1,), dtype=torch.int32, device=dev)
+    f_sum = torch.empty((N + 1,), dtype=torch.int32, device=dev)
+    f_hits = torch.empty((N + 1,), dtype=torch.int32, device=dev)
+    f_vec = torch.empty((N + 1,), dtype=torch.int32, device=dev)        # uint32 words
+    f_thr = torch.empty((N + 1, E1), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        capi.check(lib.ee_threshold_search(_ptr(cf), _ptr(cr), E1, N, P, source, V, int(seed) & _MASK64, _ptr(mix), _SEARCH_SEMANTICS[semantics],
+                                           _ptr(table), _ptr(acc), _ptr(mex), _ptr(f_count), _ptr(f_sum), _ptr(f_hits), _ptr(f_vec), _ptr(f_thr),
+                                           _stream()), None, "ee_threshold_search")
+    F = int(f_count.item())
+    sign = -1.0 if st.value == "entropy" else 1.0                       # the search ran on the negated entropy: real thresholds back (exact)
+    hits, sums = f_hits[:F].cpu().numpy(), f_sum[:F].cpu().numpy()
+    return SearchResult(table=sign * table.cpu().numpy(), front_thresholds=sign * f_thr[:F].cpu().numpy(), front_accuracy=hits / float(N),
+                        front_mean_exit=sums / float(N), front_vector=f_vec[:F].cpu().numpy().view(np.uint32), front_hits=hits, front_exit_sum=sums,
+                        num_vectors=V, num_samples=int(N), source=source, seed=int(seed) & _MASK64, mixtures=mix_host, accuracy=acc, mean_exit=mex)
