@@ -20,6 +20,8 @@
  *   ee_threshold_sweep                          <- thresh.opt1 / large_scale.opt0_2D vectorised exit-index search
  *   ee_threshold_search                         <- large_scale.generate_thresholds + the sweep + the Pareto front the reference stops short of
  *                                                 (EE/thresh.py:184-215, EE/large_scale.py:68-84).
+ *   ee_threshold_search_cost                    <- the same search against the reference's efficiency figures: per-exit cost weighted by the exit
+ *                                                 distribution ("GFLOPs reduction", "Latency reduction": EE/eval.py:62-84, EE/analysis.py:29-102).
  *   ee_set_patience / ee_patience_scan /        <- EarlyExitInference.PATIENCE, declared by the reference (EE/models/EE_modules.py:
  *   ee_patience_sweep                              123-124, PABEE: Zhou et al., NeurIPS 2020) but not implemented there; semantics below.
  *   ee_set_exit_rule / ee_set_patience_vector / <- no counterpart: the reference implements neither rule.  Patient-and-confident (PCEE-BERT, Zhang et al.,
@@ -531,6 +533,37 @@ enum { MMEE_SEARCH_REFERENCE = 0, MMEE_SEARCH_POLICY = 1 };
 int ee_threshold_search(const double* conf, const uint8_t* correct, int32_t E1, int32_t N, int32_t P, int32_t source, int64_t V, uint64_t seed,
                         const uint8_t* mixtures, int32_t semantics, double* table, double* acc, double* mean_exit, int32_t* front_count,
                         int32_t* front_exit_sum, int32_t* front_hits, uint32_t* front_vector, double* front_thresholds, void* stream);
+
+/*
+ * The cost-weighted threshold search: the same candidates, scored the same way, but the front is the one of accuracy against COST.  The mean exit
+ * index is not what a forward pays: exits sit behind different numbers of layers, and in the packed layout a long document pays many times what a
+ * short one pays for the same layer.
+ *
+ * Inputs: those of ee_threshold_search plus cost, dev uint32 (E1,N): cost[e][n] is what document n costs when it leaves at exit e, in units the
+ * caller chooses (sweep.exit_costs gives the path's algorithmic FLOPs).  No monotonicity in e is assumed.  The percentile table, the three digit
+ * sources and both exit rules (MMEE_SEARCH_REFERENCE / MMEE_SEARCH_POLICY) are exactly those of ee_threshold_search.
+ *
+ * Per vector: hits(v) and exit_sum(v) as above, and cost_sum(v) = sum_n cost[exit(v, n)][n] as an exact uint64 (N < 2^24 and 32-bit entries keep it
+ * below 2^56: nothing can overflow).  acc / mean_exit dev double (V,) or NULL as above; cost_sum dev uint64 (V,) or NULL.
+ *
+ * Front: the strict Pareto front of (cost_sum down, hits up).  Vector v is on it iff no vector has cost_sum <= and hits >= with one of the two
+ * strict; among vectors of equal (cost_sum, hits) the LOWEST index is the one reported.  As it is computed: over hits = 0 .. N (N + 1 buckets, so
+ * ee_threshold_search's bucket limit does not apply), best[h] = the minimum over {v : hits(v) = h} of (cost_sum, v) compared lexicographically;
+ * bucket h is on the front iff it is not empty and its cost_sum is below that of every non-empty bucket with MORE hits.  Deterministic: the result
+ * does not depend on the launch shape, on the order in which atomics arrive, or on a sort.  Outputs dev, ascending in cost_sum -- which is also
+ * strictly ascending in hits --, at most N + 1 entries: front_count int32 [1], front_cost_sum uint64, front_exit_sum int32 (the exit sum of the
+ * entry's vector: NOT monotone along this front), front_hits int32, front_vector uint32 (N+1 entries each) and front_thresholds double (N+1, E1) as
+ * above; entries past front_count are not written.
+ *
+ * With cost[e][n] = e the front equals ee_threshold_search's entry for entry: cost_sum = exit_sum, the same hits, vectors and threshold bits.
+ *
+ * Refusals: every one of ee_threshold_search except the bucket limit, plus a NULL cost and a NULL front_cost_sum; all before any device call.  The
+ * call only enqueues on `stream`: nothing is uploaded or downloaded.
+ */
+int ee_threshold_search_cost(const double* conf, const uint8_t* correct, const uint32_t* cost, int32_t E1, int32_t N, int32_t P, int32_t source,
+                             int64_t V, uint64_t seed, const uint8_t* mixtures, int32_t semantics, double* table, double* acc, double* mean_exit,
+                             uint64_t* cost_sum, int32_t* front_count, uint64_t* front_cost_sum, int32_t* front_exit_sum, int32_t* front_hits,
+                             uint32_t* front_vector, double* front_thresholds, void* stream);
 
 /*
  * Per-exit temperature fit on the device (TemperatureScaler.set_temperature, EE/generic_scaling.py:64-111, as driven per

@@ -252,12 +252,8 @@ int ee_threshold_sweep(const double* conf, const uint8_t* correct, int32_t E1, i
     return launch_status(nullptr, "ee_threshold_sweep");
 }
 
-int ee_threshold_search(const double* conf, const uint8_t* correct, int32_t E1, int32_t N, int32_t P, int32_t source, int64_t V, uint64_t seed,
-                        const uint8_t* mixtures, int32_t semantics, double* table, double* acc, double* mean_exit, int32_t* front_count,
-                        int32_t* front_exit_sum, int32_t* front_hits, uint32_t* front_vector, double* front_thresholds, void* stream) {
-    const char* who = "ee_threshold_search";
-    if (!conf || !correct || !table || !front_count || !front_exit_sum || !front_hits || !front_vector || !front_thresholds)
-        return fail(nullptr, "%s: NULL argument (conf, correct, table and the five front outputs are required; acc and mean_exit may be NULL)", who);
+// The refusals ee_threshold_search and ee_threshold_search_cost share, in this order, before any device call; GRID sets *V.  0: accepted.
+static int search_refuse(const char* who, int32_t E1, int32_t N, int32_t P, int32_t source, int64_t* V, const uint8_t* mixtures, int32_t semantics) {
     if (E1 < 2 || E1 > 64) return fail(nullptr, "%s: E1 = %d, need 2 <= E1 <= 64", who, E1);
     if (N < 1 || N >= (1 << 24)) return fail(nullptr, "%s: N = %d, need 1 <= N < 2^24 (a rank takes 24 bits of a record)", who, N);
     if (P < 2 || P > 64) return fail(nullptr, "%s: P = %d thresholds per exit, need 2 <= P <= 64", who, P);
@@ -268,18 +264,18 @@ int ee_threshold_search(const double* conf, const uint8_t* correct, int32_t E1, 
         for (int e = 0; e < E1 - 1 && grid < (1ull << 32); ++e) grid *= (unsigned long long)P;
         if (grid >= (1ull << 32))
             return fail(nullptr, "%s: the grid of P = %d thresholds at %d exits has P^(E1-1) >= 2^32 vectors; sample it (MMEE_SEARCH_SAMPLED with V < 2^32)", who, P, E1 - 1);
-        V = (int64_t)grid;
+        *V = (int64_t)grid;
     } else if (source == MMEE_SEARCH_SAMPLED || source == MMEE_SEARCH_MIXTURES) {
-        if (V < 1 || V >= (1ll << 32)) return fail(nullptr, "%s: V = %lld vectors, need 1 <= V < 2^32", who, (long long)V);
+        if (*V < 1 || *V >= (1ll << 32)) return fail(nullptr, "%s: V = %lld vectors, need 1 <= V < 2^32", who, (long long)*V);
         if (source == MMEE_SEARCH_MIXTURES && !mixtures) return fail(nullptr, "%s: MMEE_SEARCH_MIXTURES without mixtures (NULL)", who);
     } else {
         return fail(nullptr, "%s: source %d is none of MMEE_SEARCH_GRID, _SAMPLED, _MIXTURES", who, source);
     }
-    const long long n_buckets = (long long)N * (E1 - 1) + 1;
-    if (n_buckets > (1ll << 26))
-        return fail(nullptr, "%s: N (E1-1) + 1 = %lld exit-sum buckets, more than 2^26", who, n_buckets);
-    if (!have_device(who)) return 1;
-    // the percentiles' (lower index, upper index, weight): numpy's linspace, true_divide, (n - 1) * q, floor, in double
+    return 0;
+}
+
+// the percentiles' (lower index, upper index, weight): numpy's linspace, true_divide, (n - 1) * q, floor, in double
+static SearchPercentiles search_percentiles(int N, int P) {
     SearchPercentiles pc{};
     const double step = 100.0 / (double)(P - 1);
     for (int j = 0; j < P; ++j) {
@@ -295,11 +291,46 @@ int ee_threshold_search(const double* conf, const uint8_t* correct, int32_t E1, 
             pc.t[j] = x - f;
         }
     }
+    return pc;
+}
+
+int ee_threshold_search(const double* conf, const uint8_t* correct, int32_t E1, int32_t N, int32_t P, int32_t source, int64_t V, uint64_t seed,
+                        const uint8_t* mixtures, int32_t semantics, double* table, double* acc, double* mean_exit, int32_t* front_count,
+                        int32_t* front_exit_sum, int32_t* front_hits, uint32_t* front_vector, double* front_thresholds, void* stream) {
+    const char* who = "ee_threshold_search";
+    if (!conf || !correct || !table || !front_count || !front_exit_sum || !front_hits || !front_vector || !front_thresholds)
+        return fail(nullptr, "%s: NULL argument (conf, correct, table and the five front outputs are required; acc and mean_exit may be NULL)", who);
+    if (search_refuse(who, E1, N, P, source, &V, mixtures, semantics)) return 1;
+    const long long n_buckets = (long long)N * (E1 - 1) + 1;
+    if (n_buckets > (1ll << 26))
+        return fail(nullptr, "%s: N (E1-1) + 1 = %lld exit-sum buckets, more than 2^26", who, n_buckets);
+    if (!have_device(who)) return 1;
+    const SearchPercentiles pc = search_percentiles(N, P);
     SearchArgs a{};
     a.conf = conf; a.correct = correct; a.E1 = E1; a.N = N; a.P = P; a.source = source; a.semantics = semantics; a.V = (unsigned)V; a.seed = seed;
     a.mixtures = mixtures; a.table = table; a.acc = acc; a.mean_exit = mean_exit; a.front_count = front_count; a.front_exit_sum = front_exit_sum;
     a.front_hits = front_hits; a.front_vector = front_vector; a.front_thresholds = front_thresholds;
     if (!launch_threshold_search(a, pc, reinterpret_cast<hipStream_t>(stream))) return fail(nullptr, "%s: hipMallocAsync of the workspace failed", who);
+    return launch_status(nullptr, who);
+}
+
+int ee_threshold_search_cost(const double* conf, const uint8_t* correct, const uint32_t* cost, int32_t E1, int32_t N, int32_t P, int32_t source,
+                             int64_t V, uint64_t seed, const uint8_t* mixtures, int32_t semantics, double* table, double* acc, double* mean_exit,
+                             uint64_t* cost_sum, int32_t* front_count, uint64_t* front_cost_sum, int32_t* front_exit_sum, int32_t* front_hits,
+                             uint32_t* front_vector, double* front_thresholds, void* stream) {
+    const char* who = "ee_threshold_search_cost";
+    if (!conf || !correct || !cost || !table || !front_count || !front_cost_sum || !front_exit_sum || !front_hits || !front_vector || !front_thresholds)
+        return fail(nullptr, "%s: NULL argument (conf, correct, cost, table and the six front outputs are required; acc, mean_exit and cost_sum may be NULL)", who);
+    if (search_refuse(who, E1, N, P, source, &V, mixtures, semantics)) return 1;
+    if (!have_device(who)) return 1;
+    const SearchPercentiles pc = search_percentiles(N, P);
+    SearchCostArgs c{};
+    SearchArgs& a = c.base;
+    a.conf = conf; a.correct = correct; a.E1 = E1; a.N = N; a.P = P; a.source = source; a.semantics = semantics; a.V = (unsigned)V; a.seed = seed;
+    a.mixtures = mixtures; a.table = table; a.acc = acc; a.mean_exit = mean_exit; a.front_count = front_count; a.front_exit_sum = front_exit_sum;
+    a.front_hits = front_hits; a.front_vector = front_vector; a.front_thresholds = front_thresholds;
+    c.cost = cost; c.cost_sum = reinterpret_cast<unsigned long long*>(cost_sum); c.front_cost_sum = reinterpret_cast<unsigned long long*>(front_cost_sum);
+    if (!launch_threshold_search_cost(c, pc, reinterpret_cast<hipStream_t>(stream))) return fail(nullptr, "%s: hipMallocAsync of the workspace failed", who);
     return launch_status(nullptr, who);
 }
 

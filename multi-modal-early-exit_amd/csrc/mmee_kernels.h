@@ -280,6 +280,14 @@ struct SearchArgs {
     double* front_thresholds;        // (N + 1, E1)
 };
 bool launch_threshold_search(const SearchArgs& a, const SearchPercentiles& pc, hipStream_t s);
+// ee_threshold_search_cost (threshold_search_cost.hip): the same search, the front of (cost_sum down, hits up)
+struct SearchCostArgs {
+    SearchArgs base;                 // front_exit_sum: the exit sum of each entry's vector
+    const unsigned* cost;            // (E1,N): what document n costs when it leaves at exit e
+    unsigned long long* cost_sum;    // (V,) or null
+    unsigned long long* front_cost_sum;      // [N + 1]
+};
+bool launch_threshold_search_cost(const SearchCostArgs& a, const SearchPercentiles& pc, hipStream_t s);
 // criterion: CRIT_MAX_CONFIDENCE, CRIT_ENTROPY or CRIT_MARGIN
 void launch_csf_table(const double* logits, const long long* refs, int E1, int N, int K, int criterion, double* table, unsigned char* correct,
                       hipStream_t s);

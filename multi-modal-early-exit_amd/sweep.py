@@ -193,6 +193,11 @@ class SearchResult:
     mixtures: Optional[np.ndarray] = None
     accuracy: Optional["torch.Tensor"] = None
     mean_exit: Optional["torch.Tensor"] = None
+    # a cost-weighted search (``threshold_search(cost=)``): the front is the one of (cost_sum down, hits up), ascending by cost and, strictly,
+    # by accuracy; ``front_exit_sum`` / ``front_mean_exit`` stay filled but are NOT monotone along it
+    front_cost_sum: Optional[np.ndarray] = None      # (F,) uint64
+    front_mean_cost: Optional[np.ndarray] = None     # (F,) cost_sum / N
+    cost_sum: Optional["torch.Tensor"] = None        # (V,) int64 device tensor (``want_all=True``)
 
     def digits(self, v):
         """The percentile index per exit (E1 - 1 of them) of candidate vector ``v``: ``table[e, digits(v)[e]]`` are its thresholds."""
@@ -200,20 +205,32 @@ class SearchResult:
             raise IndexError(f"vector {v} of {self.num_vectors}")
         return search_digits(self.source, v, self.table.shape[0], self.table.shape[1], self.seed, self.mixtures)
 
-    def select(self, min_accuracy=None, max_mean_exit=None):
+    def select(self, min_accuracy=None, max_mean_exit=None, max_mean_cost=None):
         """One operating point of the front as a plain list of E1 floats (what ``EarlyExitEngine.forward(thresholds=)`` and
-        ``model.early_exit(thresholds=)`` take): with ``min_accuracy`` the entry of LOWEST mean exit whose accuracy reaches it, with
-        ``max_mean_exit`` the entry of HIGHEST accuracy within the budget.  Exactly one of the two; ``ValueError`` when no entry qualifies."""
-        return self.front_thresholds[self.select_index(min_accuracy, max_mean_exit)].tolist()
+        ``model.early_exit(thresholds=)`` take): with ``min_accuracy`` the CHEAPEST entry whose accuracy reaches it (lowest mean exit; on a
+        cost result lowest mean cost), with ``max_mean_exit`` / ``max_mean_cost`` the entry of HIGHEST accuracy within the budget.  Exactly one
+        of the three; ``max_mean_exit`` belongs to a result without costs and ``max_mean_cost`` to one with them.  ``ValueError`` when no
+        entry qualifies."""
+        return self.front_thresholds[self.select_index(min_accuracy, max_mean_exit, max_mean_cost)].tolist()
 
-    def select_index(self, min_accuracy=None, max_mean_exit=None) -> int:
-        if (min_accuracy is None) == (max_mean_exit is None):
-            raise ValueError("select takes exactly one of min_accuracy and max_mean_exit")
+    def select_index(self, min_accuracy=None, max_mean_exit=None, max_mean_cost=None) -> int:
+        if sum(x is not None for x in (min_accuracy, max_mean_exit, max_mean_cost)) != 1:
+            raise ValueError("select takes exactly one of min_accuracy, max_mean_exit and max_mean_cost")
+        with_cost = self.front_cost_sum is not None
+        if max_mean_exit is not None and with_cost:
+            raise ValueError("this front is ordered by cost, the mean exit is not monotone along it: give the budget as max_mean_cost")
+        if max_mean_cost is not None and not with_cost:
+            raise ValueError("max_mean_cost needs a cost-weighted result: threshold_search(cost=...)")
         if min_accuracy is not None:
             ok = np.nonzero(self.front_accuracy >= float(min_accuracy))[0]
             if not len(ok):
                 raise ValueError(f"no front entry reaches accuracy {min_accuracy} (best: {self.front_accuracy.max() if len(self.front_accuracy) else None})")
             return int(ok[0])                   # accuracy rises along the front: the first is the cheapest
+        if max_mean_cost is not None:
+            ok = np.nonzero(self.front_mean_cost <= float(max_mean_cost))[0]
+            if not len(ok):
+                raise ValueError(f"no front entry has a mean cost <= {max_mean_cost} (lowest: {self.front_mean_cost.min() if len(self.front_mean_cost) else None})")
+            return int(ok[-1])
         ok = np.nonzero(self.front_mean_exit <= float(max_mean_exit))[0]
         if not len(ok):
             raise ValueError(f"no front entry has a mean exit <= {max_mean_exit} (lowest: {self.front_mean_exit.min() if len(self.front_mean_exit) else None})")
@@ -224,7 +241,7 @@ _SEARCH_SEMANTICS = {"reference": capi.SEARCH_REFERENCE, "policy": capi.SEARCH_P
 
 
 def threshold_search(logits, references=None, criterion="max_confidence", num_per_exit: int = 10, mixtures="grid", seed: int = 42,
-                     semantics: str = "policy", want_all: bool = False, device=None) -> SearchResult:
+                     semantics: str = "policy", want_all: bool = False, device=None, cost=None) -> SearchResult:
     """Which thresholds should a deployment run?  Candidate thresholds = ``num_per_exit`` percentiles of every exit's criterion table
     (``np.percentile(table[e], linspace(0, 100, num_per_exit))`` bit for bit), candidate vectors = ``mixtures`` of them, each scored on the
     dumped array, and the accuracy / mean-exit Pareto front of the scores, all on the device (ee_threshold_search; include/mmee.h).
@@ -233,7 +250,12 @@ def threshold_search(logits, references=None, criterion="max_confidence", num_pe
     (``references`` is then not read).  ``mixtures``: ``"grid"`` -- all ``num_per_exit ** (E1 - 1)`` vectors --, an int V -- V vectors drawn by the
     counter-based hash of ``seed`` --, or an integer array (V,E1) of percentile indices (the reference's own ``np.random.randint`` draw, for
     one).  ``semantics``: ``"policy"`` -- what a forward does: strict compare, the final exit when nothing fires -- or ``"reference"`` --
-    ``threshold_sweep``'s ``>=`` / exit 0.  ``want_all`` also returns the accuracy and mean exit of every vector (device tensors)."""
+    ``threshold_sweep``'s ``>=`` / exit 0.  ``want_all`` also returns the accuracy and mean exit of every vector (device tensors).
+
+    ``cost``: an integer array (E1,) -- a per-exit cost, the same for every document: the reference's per-exit FLOPs, or its latency
+    ``(e + 1) / (E + 1)`` in integer units -- or (E1,N) -- what document n costs when it leaves at exit e (``exit_costs``), values in
+    [0, 2^32).  The front is then the accuracy / cost front (ee_threshold_search_cost): ``front_cost_sum`` / ``front_mean_cost`` are filled,
+    the entries ascend by cost, and ``want_all`` also returns every vector's ``cost_sum``.  Without it the call is the exit-index search."""
     from .policy import threshold_criterion
     st = threshold_criterion(criterion)
     if semantics not in _SEARCH_SEMANTICS:
@@ -269,6 +291,16 @@ def threshold_search(logits, references=None, criterion="max_confidence", num_pe
             raise ValueError(f"mixtures: every percentile index must be in [0, {P})")
         mix_host = np.clip(mix_host, 0, P - 1).astype(np.uint8)        # the final exit's digit is unused
         source, V = capi.SEARCH_MIXTURES, int(mix_host.shape[0])
+    cost_host = None
+    if cost is not None:
+        cost_host = cost.cpu().numpy() if torch is not None and isinstance(cost, torch.Tensor) else np.asarray(cost)
+        if cost_host.dtype.kind not in "iu":
+            raise ValueError(f"cost: an integer array, not {cost_host.dtype} (round it in the unit you choose)")
+        n_docs = int(logits[0].shape[1]) if pair else int(np.shape(logits)[1])
+        if cost_host.shape not in ((E1,), (E1, n_docs)):
+            raise ValueError(f"cost: shape ({E1},) or ({E1},{n_docs}), not {cost_host.shape}")
+        if cost_host.size and (int(cost_host.min()) < 0 or int(cost_host.max()) >= 1 << 32):
+            raise ValueError("cost: every value must be in [0, 2^32)")
     lib = capi.load()
     dev = _require_torch_cuda(device)
     if pair:
@@ -287,13 +319,66 @@ def threshold_search(logits, references=None, criterion="max_confidence", num_pe
     f_hits = torch.empty((N + 1,), dtype=torch.int32, device=dev)
     f_vec = torch.empty((N + 1,), dtype=torch.int32, device=dev)        # uint32 words
     f_thr = torch.empty((N + 1, E1), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        capi.check(lib.ee_threshold_search(_ptr(cf), _ptr(cr), E1, N, P, source, V, int(seed) & _MASK64, _ptr(mix), _SEARCH_SEMANTICS[semantics],
-                                           _ptr(table), _ptr(acc), _ptr(mex), _ptr(f_count), _ptr(f_sum), _ptr(f_hits), _ptr(f_vec), _ptr(f_thr),
-                                           _stream()), None, "ee_threshold_search")
-    F = int(f_count.item())
     sign = -1.0 if st.value == "entropy" else 1.0                       # the search ran on the negated entropy: real thresholds back (exact)
+    extra = {}
+    if cost_host is None:
+        with torch.cuda.device(dev):
+            capi.check(lib.ee_threshold_search(_ptr(cf), _ptr(cr), E1, N, P, source, V, int(seed) & _MASK64, _ptr(mix), _SEARCH_SEMANTICS[semantics],
+                                               _ptr(table), _ptr(acc), _ptr(mex), _ptr(f_count), _ptr(f_sum), _ptr(f_hits), _ptr(f_vec), _ptr(f_thr),
+                                               _stream()), None, "ee_threshold_search")
+        F = int(f_count.item())
+    else:
+        c2 = cost_host if cost_host.ndim == 2 else np.broadcast_to(cost_host[:, None], (E1, N))
+        cs = torch.from_numpy(np.ascontiguousarray(c2.astype(np.uint32)).view(np.int32)).to(dev)      # uint32 words
+        csum = torch.empty((V,), dtype=torch.int64, device=dev) if want_all else None                  # uint64 words below 2^56
+        f_cost = torch.empty((N + 1,), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            capi.check(lib.ee_threshold_search_cost(_ptr(cf), _ptr(cr), _ptr(cs), E1, N, P, source, V, int(seed) & _MASK64, _ptr(mix),
+                                                    _SEARCH_SEMANTICS[semantics], _ptr(table), _ptr(acc), _ptr(mex), _ptr(csum), _ptr(f_count),
+                                                    _ptr(f_cost), _ptr(f_sum), _ptr(f_hits), _ptr(f_vec), _ptr(f_thr), _stream()), None,
+                       "ee_threshold_search_cost")
+        F = int(f_count.item())
+        costs = f_cost[:F].cpu().numpy().view(np.uint64)
+        extra = dict(front_cost_sum=costs, front_mean_cost=costs / float(N), cost_sum=csum)
     hits, sums = f_hits[:F].cpu().numpy(), f_sum[:F].cpu().numpy()
     return SearchResult(table=sign * table.cpu().numpy(), front_thresholds=sign * f_thr[:F].cpu().numpy(), front_accuracy=hits / float(N),
                         front_mean_exit=sums / float(N), front_vector=f_vec[:F].cpu().numpy().view(np.uint32), front_hits=hits, front_exit_sum=sums,
-                        num_vectors=V, num_samples=int(N), source=source, seed=int(seed) & _MASK64, mixtures=mix_host, accuracy=acc, mean_exit=mex)
+                        num_vectors=V, num_samples=int(N), source=source, seed=int(seed) & _MASK64, mixtures=mix_host, accuracy=acc, mean_exit=mex,
+                        **extra)
+
+
+def exit_costs(cfg, attention_mask=None, text_rows=None, unit: float = 1e6) -> np.ndarray:
+    """The path's own cost model, for ``threshold_search(cost=)``: ``(E1, N) uint32``, entry (e, n) = the work of document n when it leaves at
+    exit e, in units of ``unit`` FLOPs (``np.rint(F / unit)``).  No device is needed.
+
+    ``F(e, n) = 2 num_patches (C p^2) H  +  l_e (2 S_n (4 H^2 + 2 H I) + 4 S_n^2 H)  +  (e + 1) (2 H^2 + 2 H K)``: the patch projection, ``l_e``
+    encoder layers -- the layer exit e sits behind: 0 for the embedding-level exits, ``num_hidden_layers`` for the final one -- of four H x H
+    and two H x I GEMMs and the two attention products over the document's ``S_n`` rows, and the e + 1 exit heads evaluated on the way.
+    ``S_n`` = the text rows the packed layout keeps (the index of the last kept position of ``attention_mask`` (N,T) + 1; or ``text_rows`` (N,)
+    directly) + ``cfg.visual_len``; for ``arch="beit"`` ``S_n = visual_len`` (N from ``text_rows``' or the mask's length).
+
+    This is ALGORITHMIC work, the figure ``roofline.achieved`` divides by: not measured time, and neither the probes nor the exit tail are in
+    it.  ``ValueError`` when an entry would reach 2^32: choose a larger ``unit``."""
+    if (attention_mask is None) == (text_rows is None):
+        raise ValueError("exit_costs takes exactly one of attention_mask (N,T) and text_rows (N,)")
+    if attention_mask is not None:
+        am = attention_mask.cpu().numpy() if torch is not None and isinstance(attention_mask, torch.Tensor) else np.asarray(attention_mask)
+        if am.ndim != 2:
+            raise ValueError("attention_mask (N,T)")
+        kept = am != 0
+        rows = np.where(kept.any(1), am.shape[1] - np.argmax(kept[:, ::-1], axis=1), 0).astype(np.int64)
+    else:
+        rows = np.asarray(text_rows).astype(np.int64).reshape(-1)
+        if rows.size and rows.min() < 0:
+            raise ValueError("text_rows must be >= 0")
+    ee = cfg.exit_config
+    layers = [0] * len(ee.embedding_exits) + list(ee.encoder_exit_layers) + [cfg.num_hidden_layers]
+    H, I, K = cfg.hidden_size, cfg.intermediate_size, cfg.num_labels
+    S = (np.zeros_like(rows) if cfg.arch == "beit" else rows) + cfg.visual_len
+    per_layer = 2 * S * (4 * H * H + 2 * H * I) + 4 * S * S * H                                 # (N,) int64: exact
+    patch = 2 * cfg.num_patches * (cfg.num_channels * cfg.patch_size ** 2) * H
+    F = patch + np.asarray(layers, dtype=np.int64)[:, None] * per_layer[None, :] + (np.arange(len(layers), dtype=np.int64)[:, None] + 1) * (2 * H * H + 2 * H * K)
+    out = np.rint(F / float(unit))
+    if out.size and out.max() >= float(1 << 32):
+        raise ValueError(f"exit_costs: {out.max():.0f} units of {unit:g} FLOPs do not fit 32 bits: choose a larger unit")
+    return out.astype(np.uint32)
