@@ -566,6 +566,62 @@ int ee_threshold_search_cost(const double* conf, const uint8_t* correct, const u
                              uint32_t* front_vector, double* front_thresholds, void* stream);
 
 /*
+ * The evaluation report: the seven metrics the reference scores every exit and every policy's predictions with (METRICS of evaluate_checkpoint,
+ * EE/eval.py:175-181; calc_metrics, EE/utils.py:226-237) plus the average confidence, on the device, from a dumped array that never leaves it.
+ *
+ * Inputs, all dev.  The logits form: logits double (E1,N,K), references int64 (N,) with values in [0,K) (a value outside is the caller's error: it
+ * is clamped for the lookups and never counts as correct).  The table form (logits == NULL): conf double (E1,N) with values in [0,1], correct uint8
+ * (E1,N), as ee_csf_table / ee_msp_table write them; K is not read.  temperatures double (E1,) or NULL (logits form).  exits int32 (N,) or NULL: one
+ * exit per document, from a policy scan, a forward or a threshold vector.  n_bins: the ECE bins, <= 0: max(1, min(N - 1, 100)); at most 1024.
+ * 1 <= E1 <= 256, 1 <= N <= 2^20 (refused above: the counting sort is O(N^2) per row), K >= 1.
+ *
+ * Outputs, dev: out double (R, MMEE_METRIC_COUNT), R = E1 + (exits ? 1 : 0), one row per exit and, with exits, row E1 = the OPERATING POINT:
+ * document n scored on logits[exits[n]][n] (table form: conf / correct[exits[n]][n]), what eval_model reports for a policy's predictions
+ * (EE/eval.py:87-112).  An exit outside [0,E1) is clamped for the lookup, never dereferenced, and not counted in exit_hist.  confusion int64
+ * (R,K,K) or NULL: confusion[r][ref][pred] (logits form only; refused in the table form).  exit_hist int64 (E1,) or NULL: the count of exits == e
+ * (needs exits).
+ *
+ * Per (row, document), float64 throughout as the reference evaluates the float64 store; integer quantities keep integer types:
+ *   z = logits / T_e when temperatures are given (the operating point: the temperature of the document's own exit); p = softmax(z), max-subtracted
+ *   pred = the FIRST maximum of z (np.argmax);  conf = max p = 1 / sum_k exp(z_k - max);  correct = (pred == ref)
+ *   brier = sum_k (p_k - [k == ref])^2;   nll = log sum_k exp(z_k - max) - (z_ref - max)
+ * Per row:
+ *   accuracy = hits / N.   f1_micro: the same number (single-label multiclass: sklearn's micro F1 is the accuracy).
+ *   f1_macro from the integer confusion counts: per class 2TP / (2TP + FP + FN), 0 where the denominator is 0, averaged over the classes that occur
+ *     in the references or the predictions (sklearn's unique_labels), not over all K.
+ *   brier, nll, avg_conf: means over N.
+ *   ece: calibration.expected_calibration_error with its defaults, the arguments of ece_logits (EE/metrics.py:479-498).  ONLY this scheme:
+ *     equal-mass edges sorted_conf[(k N) / n_bins], k = 0 .. n_bins-1, plus 1.0; bin = searchsorted(edges, conf, side="right") - 1, clipped to
+ *     [0, n_bins); integer document / hit counts per bin; sum_b (cnt_b / N) |hit_b / cnt_b - edges[b+1]| (upper-edge proxy, p = 1), bins in order.
+ *   aurc: StatsCache.rc_curve_stats + aurc (EE/metrics.py:346-424; AURC_DISPLAY_SCALE = 1).  The documents in ascending conf, TIES IN DOCUMENT
+ *     ORDER (a stable sort: the order of ee_threshold_sweep's ranking pass); r_i = 1 - correct_i in that order, S_i = sum_{j >= i} r_j (integers).
+ *     risks = [S_0 / N]; t = 0; for i = 0 .. N-2: t += 1, and if i == 0 or c_i != c_{i-1}: append risk S_{i+1} / (N-1-i) and weight t / N, t = 0.
+ *     If t > 0 at the end: append the last risk again, with weight t / N.  AURC = sum_j (risk_j + risk_{j+1}) / 2 * w_j; N = 1: no weights, 0.
+ *     The reference sorts with numpy's unstable argsort and its result DOES depend on the order inside a tie; the document-order rule is this
+ *     library's contract.
+ *   In the table form brier, nll and f1_macro are not computed: their entries are NaN.
+ * Deviations from the reference, deliberate: (1) its nll passes the logits to sklearn's log_loss, which current sklearn refuses for values above 1;
+ * on softmax probabilities it is the plain mean of -log p_ref, which is what is computed here.  (2), (3) its brier_loss and aurc_logits guess from
+ * isclose(sum(x), N) whether an input is already probabilities / correctness; here the inputs are always logits and labels.
+ *
+ * Deterministic: integer atomics for the counts, every float sum in a fixed order; two calls on the same input give the same bits.  The call only
+ * enqueues on `stream` (workspace from the stream's pool); nothing is uploaded or downloaded.  Refusals, all before any device call: out NULL,
+ * logits without references, the table form without conf / correct or with confusion, exit_hist without exits, E1, N, K, n_bins out of range.
+ */
+#define MMEE_METRIC_ACCURACY 0
+#define MMEE_METRIC_BRIER    1
+#define MMEE_METRIC_NLL      2
+#define MMEE_METRIC_F1_MICRO 3
+#define MMEE_METRIC_F1_MACRO 4
+#define MMEE_METRIC_ECE      5
+#define MMEE_METRIC_AURC     6
+#define MMEE_METRIC_AVG_CONF 7
+#define MMEE_METRIC_COUNT    8
+int ee_exit_metrics(const double* logits, const int64_t* references, const double* conf, const uint8_t* correct, const double* temperatures,
+                    const int32_t* exits, int32_t E1, int32_t N, int32_t K, int32_t n_bins, double* out, int64_t* confusion, int64_t* exit_hist,
+                    void* stream);
+
+/*
  * Per-exit temperature fit on the device (TemperatureScaler.set_temperature, EE/generic_scaling.py:64-111, as driven per
  * exit by calibrate(), EE/eval.py:313-337): for every exit e, T[e] = argmin_T mean NLL(softmax(logits[e] / T), labels),
  * starting from T = 1, by Newton iterations on 1/T (the objective is convex in 1/T).  logits dev double (E1,N,K),

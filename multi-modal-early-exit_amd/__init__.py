@@ -17,4 +17,6 @@ from . import harness  # noqa: F401,E402
 from . import dist  # noqa: F401,E402
 from . import sweep  # noqa: F401,E402
 from . import calibration  # noqa: F401,E402
+from . import metrics  # noqa: F401,E402
+from .metrics import ExitReport, exit_report  # noqa: F401,E402
 from . import feed  # noqa: F401,E402

@@ -24,6 +24,9 @@ CRIT_MAX_CONFIDENCE, CRIT_ENTROPY, CRIT_PATIENCE, CRIT_MARGIN = 0, 1, 2, 3
 RULE_PLAIN, RULE_STREAK, RULE_EITHER = 0, 1, 2
 SEARCH_GRID, SEARCH_SAMPLED, SEARCH_MIXTURES = 0, 1, 2
 SEARCH_REFERENCE, SEARCH_POLICY = 0, 1
+# the columns of ee_exit_metrics' output rows (MMEE_METRIC_*)
+(METRIC_ACCURACY, METRIC_BRIER, METRIC_NLL, METRIC_F1_MICRO, METRIC_F1_MACRO, METRIC_ECE, METRIC_AURC, METRIC_AVG_CONF,
+ METRIC_COUNT) = range(9)
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 CLOCK_STAMP_WORDS = 4096       # MMEE_CLOCK_STAMP_WORDS
 ATTN_KERNEL_F32, ATTN_KERNEL_PAIR, ATTN_KERNEL_IDX, ATTN_KERNEL_IDX_NOBIAS = 0, 1, 2, 3
@@ -109,6 +112,7 @@ SYMBOLS = {
                                            _vp, _vp, _vp]),
     "ee_msp_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_csf_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ee_exit_metrics": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ee_debug_gemm": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_debug_gemm_split": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp,
                                       _i32, _i32, C.POINTER(C.c_float), _vp]),

@@ -1,5 +1,6 @@
 // Entry points of libmmee_hip.so that never see a handle: bucket LUT, shader-clock stamps, policy / patience / threshold sweeps, temperature
-// fit, result packing, the device-side input feed, and the ee_debug_* hooks that run one kernel on caller-provided buffers.
+// fit, the evaluation report (ee_exit_metrics), result packing, the device-side input feed, and the ee_debug_* hooks that run one kernel on
+// caller-provided buffers.
 #include <math.h>
 #include <string.h>
 
@@ -352,6 +353,34 @@ int ee_csf_table(const double* logits, const int64_t* references, int32_t E1, in
     if (!have_device("ee_csf_table")) return 1;
     launch_csf_table(logits, (const long long*)references, E1, N, K, criterion, table, correct, reinterpret_cast<hipStream_t>(stream));
     return launch_status(nullptr, "ee_csf_table");
+}
+
+static_assert(kMetricAccuracy == MMEE_METRIC_ACCURACY && kMetricBrier == MMEE_METRIC_BRIER && kMetricNll == MMEE_METRIC_NLL &&
+              kMetricF1Micro == MMEE_METRIC_F1_MICRO && kMetricF1Macro == MMEE_METRIC_F1_MACRO && kMetricEce == MMEE_METRIC_ECE &&
+              kMetricAurc == MMEE_METRIC_AURC && kMetricAvgConf == MMEE_METRIC_AVG_CONF && kMetricCount == MMEE_METRIC_COUNT,
+              "the kernels' metric columns are the ABI's");
+int ee_exit_metrics(const double* logits, const int64_t* references, const double* conf, const uint8_t* correct, const double* temperatures,
+                    const int32_t* exits, int32_t E1, int32_t N, int32_t K, int32_t n_bins, double* out, int64_t* confusion, int64_t* exit_hist,
+                    void* stream) {
+    const char* who = "ee_exit_metrics";
+    if (!out) return fail(nullptr, "%s: NULL argument (out is required)", who);
+    if (logits && !references) return fail(nullptr, "%s: NULL argument (logits need the references)", who);
+    if (!logits && (!conf || !correct)) return fail(nullptr, "%s: NULL argument (without logits the table form needs conf and correct)", who);
+    if (!logits && confusion) return fail(nullptr, "%s: the table form has no predictions: confusion must be NULL", who);
+    if (exit_hist && !exits) return fail(nullptr, "%s: exit_hist counts the values of exits, which is NULL", who);
+    if (E1 < 1 || E1 > 256) return fail(nullptr, "%s: E1 = %d, need 1 <= E1 <= 256", who, E1);
+    if (N < 1) return fail(nullptr, "%s: N = %d, need N >= 1", who, N);
+    if (N > kMetricsMaxN) return fail(nullptr, "%s: N = %d, more than 2^20: the counting sort of a row is O(N^2)", who, N);
+    if (logits && K < 1) return fail(nullptr, "%s: K = %d, need K >= 1", who, K);
+    if (n_bins > kMetricsMaxBins) return fail(nullptr, "%s: n_bins = %d, more than %d", who, n_bins, kMetricsMaxBins);
+    if (!have_device(who)) return 1;
+    MetricsArgs a{};
+    a.logits = logits; a.references = reinterpret_cast<const long long*>(references); a.conf = conf; a.correct = correct;
+    a.temperatures = temperatures; a.exits = exits; a.E1 = E1; a.N = N; a.K = logits ? K : 1;
+    a.n_bins = n_bins > 0 ? n_bins : (N - 1 < 1 ? 1 : N - 1 > 100 ? 100 : N - 1);
+    a.out = out; a.confusion = reinterpret_cast<unsigned long long*>(confusion); a.exit_hist = reinterpret_cast<unsigned long long*>(exit_hist);
+    if (!launch_exit_metrics(a, reinterpret_cast<hipStream_t>(stream))) return fail(nullptr, "%s: hipMallocAsync of the workspace failed", who);
+    return launch_status(nullptr, who);
 }
 
 int ee_temperature_fit(const double* logits, const int64_t* labels, int32_t E1, int32_t N, int32_t K, int32_t max_iter,

@@ -288,6 +288,24 @@ struct SearchCostArgs {
     unsigned long long* front_cost_sum;      // [N + 1]
 };
 bool launch_threshold_search_cost(const SearchCostArgs& a, const SearchPercentiles& pc, hipStream_t s);
+// ee_exit_metrics (exit_metrics.hip; include/mmee.h MMEE_METRIC_*, capi_tools.hip asserts the values agree)
+enum { kMetricAccuracy = 0, kMetricBrier = 1, kMetricNll = 2, kMetricF1Micro = 3, kMetricF1Macro = 4, kMetricEce = 5, kMetricAurc = 6,
+       kMetricAvgConf = 7, kMetricCount = 8 };
+constexpr int kMetricsMaxBins = 1024;        // the ECE edges and bin counts of one row live in LDS
+constexpr int kMetricsMaxN = 1 << 20;        // the counting sort is O(N^2) per row
+struct MetricsArgs {
+    const double* logits;            // (E1,N,K), or null: the table form
+    const long long* references;     // (N,) with the logits
+    const double* conf;              // (E1,N), table form
+    const unsigned char* correct;    // (E1,N), table form
+    const double* temperatures;      // (E1,) or null
+    const int* exits;                // (N,) or null: the operating point, row E1 of the outputs
+    int E1, N, K, n_bins;            // n_bins resolved by the caller: 1 .. kMetricsMaxBins
+    double* out;                     // (R, kMetricCount), R = E1 + (exits ? 1 : 0)
+    unsigned long long* confusion;   // (R,K,K) int64 counts or null (kept in the workspace then)
+    unsigned long long* exit_hist;   // (E1,) int64 counts or null
+};
+bool launch_exit_metrics(const MetricsArgs& a, hipStream_t s);
 // criterion: CRIT_MAX_CONFIDENCE, CRIT_ENTROPY or CRIT_MARGIN
 void launch_csf_table(const double* logits, const long long* refs, int E1, int N, int K, int criterion, double* table, unsigned char* correct,
                       hipStream_t s);
