@@ -702,6 +702,51 @@ int ee_debug_attention(const float* qkv, int32_t qkv_rows, const int32_t* doc_of
                        int32_t bins1, int32_t bins2, int32_t max_rel_pos, int32_t max_rel_2d_pos, int32_t max_pos, int32_t max_coord, int32_t kernel,
                        int32_t use_queue, int32_t q_limit, int32_t terms, void* ctx, int32_t* err_flag_out, void* stream);
 
+/* Unit-test hooks of the row kernels (csrc/prep_embed.hip), the counterparts of ee_debug_attention: the path's own launchers on
+ * caller-provided DEVICE buffers; no handle.  Each synchronises the stream and writes the kernels' error word to the host int32
+ * err_flag_out (1 token id, 2 bbox, 4 position id, 8 token_type id out of range; 16 a value left the range of the split planes).  Every
+ * table and output must be as large as the shapes say: the hooks check shapes, not buffer sizes.  Refused, not launched: a hidden size
+ * that is no multiple of 128 or above 1024, 4 cs + 2 ss != H, split rows where H % 256 != 0.
+ *
+ * ee_debug_prep: doc_prep / doc_scan / row_meta.  input_ids, attention_mask (or NULL), position_ids (or NULL), token_type_ids (or NULL)
+ *   int64 (B,T); bbox int64 (B,T,4); G = patches per side (Pv = G G + 1 visual rows per document); the range limits pad_id, vocab,
+ *   max_2d, max_pos, type_vocab; dense_rows != 0 keeps trailing pad rows (MMEE_FLAG_DENSE_ROWS).  Outputs, int32: text_dst (B,T) the row
+ *   inside the document or -1, emb_pos (B,T), ntext (B), doc_off (B + 1), x_src (B), doc_orig (B), meta (rows,4) = {4 pos, 4 x0, 4 y1,
+ *   float bits of the key mask} per packed row, counts = 16 bytes {int32 n_docs, int32 n_rows, uint64 sum_len_sq}.
+ *
+ * ee_debug_embed: prep, embed_text, embed_visual (embed_visual_rows when neither vis_part nor cat_part is given), then pool_finish for
+ *   every partial-sum buffer given.  Tables: word (vocab,H), type (type_vocab,H), pos (max_pos,H), xtab / ytab (max_2d,cs), htab / wtab
+ *   (max_2d,ss); inputs_embeds (B,T,H) or NULL; vis_raw (B,Pv - 1,H) = the patch projection's output, cls_token (H), pos_embed (Pv,H).
+ *   LayerNorms: text_ln_* / text_eps = embeddings.LayerNorm, vis_ln_* / vis_eps = layoutlmv3.norm, ln2_* / eps2 = layoutlmv3.LayerNorm.
+ *   Exactly one of X (f32 rows) and Xs (split-f16 rows scaled by split_scale) receives the B (T + Pv) packed rows at most.  text_part
+ *   (B,ceil(T/32),H), vis_part (B,ceil(Pv/32),H), cat_part (B,ceil(T/32) + ceil(Pv/32),H): scratch, each with its pooled_* (B,H) output.
+ *
+ * ee_debug_ln_rows: one launch_ln_rows.  dst[r] = LayerNorm(src[row_src ? row_src[r] : r]) for r < *n_rows (a DEVICE word, <= max_rows);
+ *   dst may be src or NULL; dst_split (or NULL) receives the rows as split-f16 planes scaled by split_scale.  pre_parts >= 1: the row is
+ *   first completed from pre_parts split-K planes (src + p pre_stride), pre_bias (or NULL) and the residual row pre_resid_rows[r] (or r)
+ *   of pre_resid (split-f16 rows scaled by 1 / pre_resid_inv, or NULL).  The grid is sized by max_rows and the device's CU count. */
+typedef struct ee_debug_embed_args {
+    const int64_t *input_ids, *attention_mask, *bbox, *position_ids, *token_type_ids;
+    int32_t B, T, G, pad_id, vocab, max_2d, max_pos, type_vocab, dense_rows, H, cs, ss;
+    const float *word, *type, *pos, *xtab, *ytab, *htab, *wtab, *inputs_embeds;
+    const float *text_ln_g, *text_ln_b, *vis_ln_g, *vis_ln_b, *ln2_g, *ln2_b;
+    float text_eps, vis_eps, eps2, split_scale;
+    const float *cls_token, *pos_embed, *vis_raw;
+    float* X;
+    void* Xs;
+    float *text_part, *vis_part, *cat_part;
+    float *pooled_text, *pooled_vis, *pooled_cat;
+} ee_debug_embed_args;
+int ee_debug_prep(const int64_t* input_ids, const int64_t* attention_mask, const int64_t* bbox, const int64_t* position_ids,
+                  const int64_t* token_type_ids, int32_t B, int32_t T, int32_t G, int32_t pad_id, int32_t vocab, int32_t max_2d, int32_t max_pos,
+                  int32_t type_vocab, int32_t dense_rows, int32_t* text_dst, int32_t* emb_pos, int32_t* ntext, int32_t* doc_off, int32_t* x_src,
+                  int32_t* doc_orig, int32_t* meta, void* counts, int32_t* err_flag_out, void* stream);
+int ee_debug_embed(const ee_debug_embed_args* args, int32_t* err_flag_out, void* stream);
+int ee_debug_ln_rows(const float* src, float* dst, const int32_t* row_src, const int32_t* n_rows, int32_t max_rows, int32_t H, const float* gamma,
+                     const float* beta, float eps, void* dst_split, float split_scale, int32_t pre_parts, size_t pre_stride,
+                     const float* pre_bias, const void* pre_resid, const int32_t* pre_resid_rows, float pre_resid_inv, int32_t* err_flag_out,
+                     void* stream);
+
 /* Diagnostic of the two-heads-per-item attention kernel (attention_pair.hip): with MMEE_ATTN_STAMPS=1 in the environment the
  * launches run a build with in-kernel s_memtime stamps; this call synchronises, copies the eight phase sums (shader cycles summed over
  * waves: 0 wait for the tile's LDS-DMA, 1 DMA issue, 2 bias gathers, 3 Q K^T MFMAs, 4 / 5 softmax + P V of head A / B, 6 item prologue,

@@ -66,6 +66,19 @@ class EEConfig(C.Structure):
 
 # every symbol include/mmee.h declares: (restype, argtypes)
 _vp, _i32, _u32 = C.c_void_p, C.c_int32, C.c_uint32
+
+
+class DebugEmbedArgs(C.Structure):
+    """ee_debug_embed_args of include/mmee.h: device pointers (or None) and sizes."""
+    _fields_ = ([(n, _vp) for n in ("input_ids", "attention_mask", "bbox", "position_ids", "token_type_ids")]
+                + [(n, _i32) for n in ("B", "T", "G", "pad_id", "vocab", "max_2d", "max_pos", "type_vocab", "dense_rows", "H", "cs", "ss")]
+                + [(n, _vp) for n in ("word", "type", "pos", "xtab", "ytab", "htab", "wtab", "inputs_embeds",
+                                      "text_ln_g", "text_ln_b", "vis_ln_g", "vis_ln_b", "ln2_g", "ln2_b")]
+                + [(n, C.c_float) for n in ("text_eps", "vis_eps", "eps2", "split_scale")]
+                + [(n, _vp) for n in ("cls_token", "pos_embed", "vis_raw", "X", "Xs", "text_part", "vis_part", "cat_part",
+                                      "pooled_text", "pooled_vis", "pooled_cat")])
+
+
 SYMBOLS = {
     "ee_create": (C.c_int, [C.POINTER(EEConfig), C.POINTER(_vp)]),
     "ee_destroy": (C.c_int, [_vp]),
@@ -119,6 +132,11 @@ SYMBOLS = {
     "ee_debug_attn_stamps": (C.c_int, [_vp]),
     "ee_debug_attention": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                      _i32, _i32, _i32, _vp, C.POINTER(_i32), _vp]),
+    "ee_debug_prep": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                C.POINTER(_i32), _vp]),
+    "ee_debug_embed": (C.c_int, [C.POINTER(DebugEmbedArgs), C.POINTER(_i32), _vp]),
+    "ee_debug_ln_rows": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, C.c_float, _vp, C.c_float, _i32, C.c_size_t, _vp, _vp, _vp, C.c_float,
+                                   C.POINTER(_i32), _vp]),
     "ee_temperature_fit": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ee_preprocess_images": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp]),
     "ee_preprocess_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32]),

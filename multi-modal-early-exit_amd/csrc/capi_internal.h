@@ -207,6 +207,32 @@ int dev_alloc(ee_handle* h, T** p, size_t count) {
     return 0;
 }
 
+// ---- shared by the handle-free entry points (capi_tools.hip, capi_debug_rows.hip) ----
+// false (and the error message of `who` set) when there is no HIP device
+inline bool have_device(const char* who) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev >= 1) return true;
+    fail(nullptr, "%s: no HIP device", who);
+    return false;
+}
+
+// Device scratch of one debug entry point: zeroed hipMalloc, freed on every way out of the scope.
+struct Scratch {
+    std::vector<void*> ptrs;
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    ~Scratch() { for (void* p : ptrs) (void)hipFree(p); }
+    template <typename T>
+    bool get(T** out, size_t count) {
+        void* q = nullptr;
+        if (hipMalloc(&q, count * sizeof(T) + 256) != hipSuccess) return false;
+        ptrs.push_back(q);
+        if (hipMemset(q, 0, count * sizeof(T) + 256) != hipSuccess) return false;
+        *out = reinterpret_cast<T*>(q);
+        return true;
+    }
+};
+
 // kernel roles reported by ee_profile_read (their names: kProfNames in capi_query.hip)
 enum { P_PREP = 0, P_EMBT, P_GPATCH, P_EMBV, P_GQKV, P_ATTN, P_GAO, P_LN, P_GUP, P_GDOWN, P_HEAD, P_DECIDE, P_COMPACT, P_GCLS, P_PROBE,
        P_PAIRIDX, P_PSPLIT, P_HEADOUT, P_EMIT, P_COUNT };

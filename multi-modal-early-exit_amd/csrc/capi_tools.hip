@@ -13,14 +13,6 @@ using namespace mmee::capi;
 
 namespace {
 
-// false (and the error message of `who` set) when there is no HIP device
-bool have_device(const char* who) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev >= 1) return true;
-    fail(nullptr, "%s: no HIP device", who);
-    return false;
-}
-
 // A small host vector on the device for the length of one entry point: hipMallocAsync + hipMemcpyAsync here, hipFreeAsync (in stream order) on
 // every way out of the scope.  err: null, or what failed.
 template <typename T>
@@ -42,23 +34,6 @@ __global__ void debug_row_meta_kernel(const int* __restrict__ pos, const int* __
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < rows) meta[i] = make_row_meta(pos[i], x0[i], y1[i], coord_hi, masked[i] == 0);
 }
-
-// Device scratch of one debug entry point: zeroed hipMalloc, freed on every way out of the scope.
-struct Scratch {
-    std::vector<void*> ptrs;
-    Scratch() = default;
-    Scratch(const Scratch&) = delete;
-    ~Scratch() { for (void* p : ptrs) (void)hipFree(p); }
-    template <typename T>
-    bool get(T** out, size_t count) {
-        void* q = nullptr;
-        if (hipMalloc(&q, count * sizeof(T) + 256) != hipSuccess) return false;
-        ptrs.push_back(q);
-        if (hipMemset(q, 0, count * sizeof(T) + 256) != hipSuccess) return false;
-        *out = reinterpret_cast<T*>(q);
-        return true;
-    }
-};
 
 }  // namespace
 

@@ -897,3 +897,38 @@ def test_output_hidden_states_vs_oracle(pkg, oracle):
         torch.cuda.synchronize()
         assert bool((hs == 7.0).all())
         eng.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,cs,ss", [(384, 64, 64), (512, 96, 64), (640, 96, 128), (896, 160, 128)])
+def test_untested_hidden_sizes_vs_oracle(pkg, oracle, H, cs, ss):
+    """The hidden sizes ee_create accepts and no other forward runs: the two-vector row kernels (384, 512) and the masked forms of the three- and
+    four-vector ones (640, 896).  Two layers, head dim 64, intermediate 2 H, three ragged documents, every exit kind, dump-all against
+    oracle.forward_all; `output_hidden_states` compares EVERY row, not row 0 alone.  f32, and split where the hidden size allows it."""
+    ee = dict(exits=["vision_avg", "text_avg", "text_visual_concat", 1, 2], encoder_layer_strategy="ramp")
+    cfg = pkg.ModelConfig.tiny(EE_config=ee, hidden_size=H, num_attention_heads=H // 64, intermediate_size=2 * H, num_hidden_layers=2,
+                               coordinate_size=cs, shape_size=ss)
+    W = pkg.synth.make_weights(cfg, seed=71)
+    B, T = 3, 40
+    docs = pkg.synth.make_documents(cfg, B, seed=72, text_len=T, min_words=3)
+    lengths = (docs["attention_mask"] != 0).sum(1)
+    assert len(set(lengths.tolist())) > 1 and (lengths < T).any()                        # ragged
+    ref = oracle.forward_all(cfg, W, docs, ee["exits"], return_hidden_cls=True, return_hidden_states=True)
+    kw = dict(input_ids=docs["input_ids"], attention_mask=docs["attention_mask"], bbox=docs["bbox"], pixel_values=docs["pixel_values"])
+    for precision in ("fp32", "split") if H % 256 == 0 else ("fp32",):
+        eng = pkg.EarlyExitEngine(cfg, max_docs=B, max_text_len=T, precision=precision, xprobe=False)
+        assert eng.precision == precision
+        eng.load_weights(W)
+        out = eng.forward(**kw, dump_all=True, want_all=True, want_hidden_cls=True, validate=True)
+        for name, got, want, tol in (("hidden_cls", out.hidden_cls, ref["hidden_cls"], 5e-5), ("all_logits", out.all_logits, ref["logits_store"], LOGIT_TOL)):
+            err = float(np.abs(_np(got) - want).max())
+            report_measured(f"hidden_size[{H},{precision}]", f"max|d {name}|", err)
+            assert err <= tol, (name, precision, err)
+        hs = eng.forward(**kw, dump_all=True, want_all=True, want_hidden_states=True, validate=True)
+        err = float(np.abs(_np(hs.hidden_states) - ref["hidden_states"]).max())
+        report_measured(f"hidden_size[{H},{precision}]", "max|d hidden_states|, every row", err)
+        assert err < LOGIT_TOL, (precision, err)
+        eng.close()
+    if H % 256:
+        with pytest.raises(pkg.capi.MMEEError, match="multiples of 256"):
+            pkg.EarlyExitEngine(cfg, max_docs=B, max_text_len=T, precision="split", xprobe=False)
