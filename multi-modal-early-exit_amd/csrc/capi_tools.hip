@@ -35,6 +35,31 @@ __global__ void debug_row_meta_kernel(const int* __restrict__ pos, const int* __
     if (i < rows) meta[i] = make_row_meta(pos[i], x0[i], y1[i], coord_hi, masked[i] == 0);
 }
 
+// The common tail of the threshold scans: device check, the thresholds (n_up doubles: ee_rule_scan packs its patience behind them) to the
+// device, counts zeroed, one launch.  what: the upload's name in the error message.
+int run_threshold_scan(const char* who, const char* what, ScanArgs a, const double* thr_host, size_t n_up, int event, int rule, void* stream) {
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const TempUpload<double> up(thr_host, n_up, s);
+    if (up.err) return fail(nullptr, "%s: %s %s", who, what, up.err);
+    if (a.counts && hipMemsetAsync(a.counts, 0, sizeof(int) * a.E1, s) != hipSuccess) return fail(nullptr, "%s: memset failed", who);
+    a.thr = up.dev;
+    if (n_up > (size_t)a.E1) a.pat = reinterpret_cast<const int*>(up.dev + a.E1);
+    if (a.N > 0) launch_exit_scan(a, event, rule, s);
+    return launch_status(nullptr, who);
+}
+
+// the parameters ee_threshold_search and ee_threshold_search_cost share
+SearchArgs search_args(const double* conf, const uint8_t* correct, int32_t E1, int32_t N, int32_t P, int32_t source, int64_t V, uint64_t seed,
+                       const uint8_t* mixtures, int32_t semantics, double* table, double* acc, double* mean_exit, int32_t* front_count,
+                       int32_t* front_exit_sum, int32_t* front_hits, uint32_t* front_vector, double* front_thresholds) {
+    SearchArgs a{};
+    a.conf = conf; a.correct = correct; a.E1 = E1; a.N = N; a.P = P; a.source = source; a.semantics = semantics; a.V = (unsigned)V; a.seed = seed;
+    a.mixtures = mixtures; a.table = table; a.acc = acc; a.mean_exit = mean_exit; a.front_count = front_count; a.front_exit_sum = front_exit_sum;
+    a.front_hits = front_hits; a.front_vector = front_vector; a.front_thresholds = front_thresholds;
+    return a;
+}
+
 }  // namespace
 
 extern "C" {
@@ -91,16 +116,10 @@ int ee_policy_scan(const double* logits, int32_t E1, int32_t N, int32_t K, const
                    double* predictions, double* confidence, int32_t* counts, void* stream) {
     if (!thresholds || E1 < 1 || E1 > 256 || N < 0 || K < 1 || (N > 0 && (!logits || !exits)))
         return fail(nullptr, "ee_policy_scan: bad argument");
-    if (!have_device("ee_policy_scan")) return 1;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const TempUpload<double> thr(thresholds, E1, s);
-    if (thr.err) return fail(nullptr, "ee_policy_scan: threshold %s", thr.err);
-    if (counts && hipMemsetAsync(counts, 0, sizeof(int) * E1, s) != hipSuccess) return fail(nullptr, "ee_policy_scan: memset failed");
     ScanArgs a{};
-    a.logits = logits; a.sign = 1.0; a.thr = thr.dev; a.E1 = E1; a.N = N; a.K = K;
+    a.logits = logits; a.sign = 1.0; a.E1 = E1; a.N = N; a.K = K;
     a.exits = exits; a.pred = predictions; a.conf = confidence; a.counts = counts;
-    if (N > 0) launch_exit_scan(a, SCAN_MSP, RULE_PLAIN, s);
-    return launch_status(nullptr, "ee_policy_scan");
+    return run_threshold_scan("ee_policy_scan", "threshold", a, thresholds, E1, SCAN_MSP, RULE_PLAIN, stream);
 }
 
 int ee_criterion_scan(const double* logits, int32_t E1, int32_t N, int32_t K, int32_t criterion, const double* thresholds, int32_t* exits,
@@ -110,17 +129,11 @@ int ee_criterion_scan(const double* logits, int32_t E1, int32_t N, int32_t K, in
     if (criterion != MMEE_CRIT_MAX_CONFIDENCE && criterion != MMEE_CRIT_ENTROPY && criterion != MMEE_CRIT_MARGIN)
         return fail(nullptr, "ee_criterion_scan: criterion %d is not a threshold criterion (MMEE_CRIT_MAX_CONFIDENCE, _ENTROPY, _MARGIN; "
                              "patience: ee_patience_scan)", criterion);
-    if (!have_device("ee_criterion_scan")) return 1;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const TempUpload<double> thr(thresholds, E1, s);
-    if (thr.err) return fail(nullptr, "ee_criterion_scan: threshold %s", thr.err);
-    if (counts && hipMemsetAsync(counts, 0, sizeof(int) * E1, s) != hipSuccess) return fail(nullptr, "ee_criterion_scan: memset failed");
     ScanArgs a{};
-    a.logits = logits; a.sign = crit_sign(criterion); a.thr = thr.dev; a.E1 = E1; a.N = N; a.K = K;
+    a.logits = logits; a.sign = crit_sign(criterion); a.E1 = E1; a.N = N; a.K = K;
     a.exits = exits; a.pred = predictions; a.conf = confidence; a.counts = counts;
     const int event = criterion == MMEE_CRIT_ENTROPY ? SCAN_ENTROPY : criterion == MMEE_CRIT_MARGIN ? SCAN_MARGIN : SCAN_MSP;
-    if (N > 0) launch_exit_scan(a, event, RULE_PLAIN, s);
-    return launch_status(nullptr, "ee_criterion_scan");
+    return run_threshold_scan("ee_criterion_scan", "threshold", a, thresholds, E1, event, RULE_PLAIN, stream);
 }
 
 int ee_patience_scan(const double* logits, int32_t E1, int32_t N, int32_t K, int32_t patience, int32_t* exits, double* predictions,
@@ -140,16 +153,10 @@ int ee_lte_scan(const double* scores, const double* logits, int32_t E1, int32_t 
                 double* predictions, int32_t* counts, void* stream) {
     if (!thresholds || E1 < 1 || E1 > 256 || N < 0 || K < 1 || (N > 0 && (!scores || !exits)) || (predictions && !logits))
         return fail(nullptr, "ee_lte_scan: bad argument");
-    if (!have_device("ee_lte_scan")) return 1;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const TempUpload<double> thr(thresholds, E1, s);
-    if (thr.err) return fail(nullptr, "ee_lte_scan: threshold %s", thr.err);
-    if (counts && hipMemsetAsync(counts, 0, sizeof(int) * E1, s) != hipSuccess) return fail(nullptr, "ee_lte_scan: memset failed");
     ScanArgs a{};
-    a.logits = logits; a.crit = scores; a.sign = -1.0; a.thr = thr.dev; a.E1 = E1; a.N = N; a.K = K;      // score < threshold
+    a.logits = logits; a.crit = scores; a.sign = -1.0; a.E1 = E1; a.N = N; a.K = K;      // score < threshold
     a.exits = exits; a.pred = predictions; a.counts = counts;
-    if (N > 0) launch_exit_scan(a, SCAN_TABLE, RULE_PLAIN, s);
-    return launch_status(nullptr, "ee_lte_scan");
+    return run_threshold_scan("ee_lte_scan", "threshold", a, thresholds, E1, SCAN_TABLE, RULE_PLAIN, stream);
 }
 
 int ee_rule_scan(const double* criterion, double sign, const double* logits, int32_t E1, int32_t N, int32_t K, const double* thresholds,
@@ -160,19 +167,13 @@ int ee_rule_scan(const double* criterion, double sign, const double* logits, int
     if (!logits && (rule == MMEE_RULE_EITHER || predictions)) return fail(nullptr, "ee_rule_scan: MMEE_RULE_EITHER and predictions need the logits");
     for (int e = 0; e < E1; ++e)
         if (patience[e] < 1) return fail(nullptr, "ee_rule_scan: patience[%d]=%d, every patience must be >= 1", e, patience[e]);
-    if (!have_device("ee_rule_scan")) return 1;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     std::vector<double> packed(E1 + (E1 + 1) / 2);                   // thresholds [E1] doubles, then the patience [E1] ints: one upload
     memcpy(packed.data(), thresholds, sizeof(double) * E1);
     memcpy(packed.data() + E1, patience, sizeof(int) * E1);
-    const TempUpload<double> up(packed.data(), packed.size(), s);
-    if (up.err) return fail(nullptr, "ee_rule_scan: threshold / patience %s", up.err);
-    if (counts && hipMemsetAsync(counts, 0, sizeof(int) * E1, s) != hipSuccess) return fail(nullptr, "ee_rule_scan: memset failed");
     ScanArgs a{};
-    a.logits = logits; a.crit = criterion; a.sign = sign; a.thr = up.dev; a.pat = reinterpret_cast<const int*>(up.dev + E1);
+    a.logits = logits; a.crit = criterion; a.sign = sign;
     a.E1 = E1; a.N = N; a.K = K; a.exits = exits; a.pred = predictions; a.conf = confidence; a.counts = counts;
-    if (N > 0) launch_exit_scan(a, SCAN_TABLE, rule, s);
-    return launch_status(nullptr, "ee_rule_scan");
+    return run_threshold_scan("ee_rule_scan", "threshold / patience", a, packed.data(), packed.size(), SCAN_TABLE, rule, stream);
 }
 
 int ee_rule_sweep(const double* conf, const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, const double* thr, int32_t V,
@@ -282,10 +283,8 @@ int ee_threshold_search(const double* conf, const uint8_t* correct, int32_t E1, 
         return fail(nullptr, "%s: N (E1-1) + 1 = %lld exit-sum buckets, more than 2^26", who, n_buckets);
     if (!have_device(who)) return 1;
     const SearchPercentiles pc = search_percentiles(N, P);
-    SearchArgs a{};
-    a.conf = conf; a.correct = correct; a.E1 = E1; a.N = N; a.P = P; a.source = source; a.semantics = semantics; a.V = (unsigned)V; a.seed = seed;
-    a.mixtures = mixtures; a.table = table; a.acc = acc; a.mean_exit = mean_exit; a.front_count = front_count; a.front_exit_sum = front_exit_sum;
-    a.front_hits = front_hits; a.front_vector = front_vector; a.front_thresholds = front_thresholds;
+    const SearchArgs a = search_args(conf, correct, E1, N, P, source, V, seed, mixtures, semantics, table, acc, mean_exit, front_count, front_exit_sum,
+                                     front_hits, front_vector, front_thresholds);
     if (!launch_threshold_search(a, pc, reinterpret_cast<hipStream_t>(stream))) return fail(nullptr, "%s: hipMallocAsync of the workspace failed", who);
     return launch_status(nullptr, who);
 }
@@ -301,10 +300,8 @@ int ee_threshold_search_cost(const double* conf, const uint8_t* correct, const u
     if (!have_device(who)) return 1;
     const SearchPercentiles pc = search_percentiles(N, P);
     SearchCostArgs c{};
-    SearchArgs& a = c.base;
-    a.conf = conf; a.correct = correct; a.E1 = E1; a.N = N; a.P = P; a.source = source; a.semantics = semantics; a.V = (unsigned)V; a.seed = seed;
-    a.mixtures = mixtures; a.table = table; a.acc = acc; a.mean_exit = mean_exit; a.front_count = front_count; a.front_exit_sum = front_exit_sum;
-    a.front_hits = front_hits; a.front_vector = front_vector; a.front_thresholds = front_thresholds;
+    c.base = search_args(conf, correct, E1, N, P, source, V, seed, mixtures, semantics, table, acc, mean_exit, front_count, front_exit_sum, front_hits,
+                         front_vector, front_thresholds);
     c.cost = cost; c.cost_sum = reinterpret_cast<unsigned long long*>(cost_sum); c.front_cost_sum = reinterpret_cast<unsigned long long*>(front_cost_sum);
     if (!launch_threshold_search_cost(c, pc, reinterpret_cast<hipStream_t>(stream))) return fail(nullptr, "%s: hipMallocAsync of the workspace failed", who);
     return launch_status(nullptr, who);

@@ -5,14 +5,15 @@
 //   1. metrics_rows_kernel   thread per (row, document): softmax of the (scaled) logits row, conf / correct into an (R, N) table (the operating-
 //                            point row gathers through `exits`), confusion[ref][pred] and the exit histogram by INTEGER atomics, and one float64
 //                            partial per block for the Brier, NLL and confidence sums (fixed tree inside the block).
-//   2. metrics_sort_kernel   every row's (conf, correct) into its stable ascending place by counting, the scheme of sweep_rank_kernel
-//                            (exit_ops.hip): place = #{m : c_m < c_n} + #{m < n : c_m == c_n}.  O(N^2) per row.
+//   2. metrics_sort_kernel   every row's (conf, correct) into its stable ascending place by counting (stable_rank_by_counting,
+//                            ranked_common.h): place = #{m : c_m < c_n} + #{m < n : c_m == c_n}.  O(N^2) per row.
 //   3. metrics_curve_kernel  one workgroup of 1024 threads per row over the sorted row: hits and the equal-mass ECE bins (integer counts in LDS),
-//                            then the risk-coverage curve in chunks of 1024 with running carries (the pattern of search_front_kernel), then the
-//                            means, F1 and the `out` row.
+//                            then the risk-coverage curve in chunks of 1024 with running carries (the scheme of block1024_scan,
+//                            ranked_common.h, written out: through the helper the kernel measured 7.5 % slower, see
+//                            profiles/ranked_common_ab.txt), then the means, F1 and the `out` row.
 // No floating-point atomic anywhere: every float sum has a fixed order (tree inside a chunk or block, chunks and blocks in order), so the
 // output bits are a function of the inputs alone.
-#include "mmee_kernels.h"
+#include "ranked_common.h"
 
 namespace mmee {
 
@@ -94,22 +95,10 @@ __global__ __launch_bounds__(256) void metrics_sort_kernel(const double* __restr
     __shared__ double tile[2048];
     const int r = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
     const double* row = tconf + (size_t)r * N;
-    const double c = n < N ? row[n] : 0.0;
-    unsigned lt = 0, eq_before = 0;
-    for (int m0 = 0; m0 < N; m0 += 2048) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < 2048; i += 256) tile[i] = m0 + i < N ? row[m0 + i] : 0.0;
-        __syncthreads();
-        const int cnt = N - m0 < 2048 ? N - m0 : 2048;
-        for (int i = 0; i < cnt; ++i) {
-            const double x = tile[i];
-            lt += x < c ? 1u : 0u;
-            eq_before += (x == c && m0 + i < n) ? 1u : 0u;
-        }
-    }
+    const uint2 place = stable_rank_by_counting(row, N, n, tile);   // (lt, eq_before)
     if (n < N) {
-        const size_t at = (size_t)r * N + lt + eq_before;            // lt + eq_before < N: a permutation of the row
-        sconf[at] = c;
+        const size_t at = (size_t)r * N + place.x + place.y;         // lt + eq_before < N: a permutation of the row
+        sconf[at] = row[n];
         scorr[at] = tcorr[(size_t)r * N + n];
     }
 }

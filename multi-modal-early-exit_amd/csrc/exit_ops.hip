@@ -6,7 +6,7 @@
 //     "first exit whose float64 max-softmax is strictly above its threshold, else the last" is exit_scan_kernel<SCAN_MSP, RULE_PLAIN>,
 //     bit-identical in its integer outputs.
 //   * thresh.opt0_2D / large_scale.check_2D_threshold (EE/thresh.py:184-215, EE/large_scale.py:42-84): threshold_sweep.
-#include "mmee_kernels.h"
+#include "ranked_common.h"
 
 namespace mmee {
 
@@ -260,14 +260,13 @@ __global__ __launch_bounds__(256) void threshold_sweep_kernel(const double* __re
 //     p[e][n] = #{m : conf[e][m] < conf[e][n]},   t[v][e] = #{m : conf[e][m] < thr[v][e]}      =>      conf[e][n] >= thr[v][e]  <=>  p[e][n] >= t[v][e]
 // (>=: every element below thr is below conf, so t <= p; <: conf itself and everything below it is below thr, so t >= p + 1).  Exact for any
 // doubles, ties and duplicates included (NaN confidences do not occur: they are softmax maxima).
-//   1. sweep_rank_kernel   p by counting (N^2 / exit, 1.1e10 double compares at 7 x 40 000: ~1 ms) and, with the tie index from the same pass,
-//                          the sorted confidences of every exit;
+//   1. sweep_rank_kernel   p by counting (stable_rank_by_counting, ranked_common.h: N^2 / exit, 1.1e10 double compares at 7 x 40 000: ~1 ms)
+//                          and, with the tie index from the same pass, the sorted confidences of every exit;
 //   2. sweep_thr_kernel    t by binary search in the sorted row;
 //   3. sweep_main_kernel   one THREAD per threshold vector (its E1 ranks in registers, its two sums in registers: no reduction across
-//                          lanes), the documents streamed through LDS as records  rec[e] = p << 8 | correct << 6 | e  that every lane reads
-//                          at the same address (broadcast).  exit = first e with rec[e] >= t[e] << 8, else 0 (numpy argmax of an all-False
-//                          column): r = rec[0]; for e = E1 - 1 .. 0: r = rec[e] >= T[e] ? rec[e] : r  -- two vector instructions per exit --
-//                          and the payload bits of r give (correct, exit).  Integer work per (vector, document): 2 E1 + 4 instructions.
+//                          lanes), the documents streamed through LDS as records  rec[e] = p << 8 | correct << 6 | e: ranked_walk
+//                          (ranked_common.h), which hands over the selected record; its payload bits give (correct, exit).  Integer work
+//                          per (vector, document): 2 E1 + 4 instructions.
 // The table is read once per 256 vectors from L2 (1.3 MB x V / 256).  Needs N < 2^24 and E1 <= 64; the histogram output stays on the kernel above.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sweep_rank_kernel(const double* __restrict__ conf, const unsigned char* __restrict__ correct, int E1, int E1P,
@@ -275,22 +274,10 @@ __global__ __launch_bounds__(256) void sweep_rank_kernel(const double* __restric
     __shared__ double tile[2048];
     const int e = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
     const double* row = conf + (size_t)e * N;
-    const double c = n < N ? row[n] : 0.0;
-    unsigned lt = 0, eq_before = 0;
-    for (int m0 = 0; m0 < N; m0 += 2048) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < 2048; i += 256) tile[i] = m0 + i < N ? row[m0 + i] : 0.0;
-        __syncthreads();
-        const int cnt = N - m0 < 2048 ? N - m0 : 2048;
-        for (int i = 0; i < cnt; ++i) {
-            const double x = tile[i];
-            lt += x < c ? 1u : 0u;
-            eq_before += (x == c && m0 + i < n) ? 1u : 0u;
-        }
-    }
+    const uint2 place = stable_rank_by_counting(row, N, n, tile);   // (lt, eq_before), ranked_common.h
     if (n < N) {
-        rec[(size_t)n * E1P + e] = (lt << 8) | ((unsigned)(correct[(size_t)e * N + n] ? 1u : 0u) << 6) | (unsigned)e;
-        sorted[(size_t)e * N + lt + eq_before] = c;                  // equal values take consecutive places in document order
+        rec[(size_t)n * E1P + e] = (place.x << 8) | ((unsigned)(correct[(size_t)e * N + n] ? 1u : 0u) << 6) | (unsigned)e;
+        sorted[(size_t)e * N + place.x + place.y] = row[n];          // equal values take consecutive places in document order
     }
 }
 
@@ -325,46 +312,14 @@ __global__ __launch_bounds__(256, 2) void sweep_main_kernel(const unsigned* __re
         for (int e = 0; e < E1C; ++e) tq[e] = T[(size_t)vv * E1 + e];
     }
     unsigned n_correct = 0, sum_exit = 0;
-    for (int n0 = 0; n0 < N; n0 += chunk) {
-        const int cnt = N - n0 < chunk ? N - n0 : chunk;
-        __syncthreads();
-        {
-            const uint4* src = reinterpret_cast<const uint4*>(rec + (size_t)n0 * E1P);
-            uint4* dst = reinterpret_cast<uint4*>(s_rec);
-            const int n16 = cnt * E1P / 4;
-            for (int i = threadIdx.x; i < n16; i += 256) dst[i] = src[i];
-        }
-        __syncthreads();
-        if (E1C > 0) {
-#pragma unroll 4
-            for (int i = 0; i < cnt; ++i) {
-                const unsigned* d = s_rec + i * E1P;                 // the same address in every lane: a broadcast read
-                const unsigned d0 = d[0];
-                unsigned r = d0;                                     // no exit fires: exit 0
-#pragma unroll
-                for (int e = E1C - 1; e >= 1; --e) {
-                    const unsigned x = d[e];
-                    r = x >= tq[e] ? x : r;
-                }
-                r = d0 >= tq[0] ? d0 : r;                            // exit 0 fires: it is the first
-                n_correct += (r >> 6) & 1u;
-                sum_exit += r & 63u;
-            }
-        } else {
-            for (int i = 0; i < cnt; ++i) {
-                const unsigned* d = s_rec + i * E1P;
-                const unsigned d0 = d[0];
-                unsigned r = d0;
-                for (int e = E1 - 1; e >= 1; --e) {
-                    const unsigned x = d[e];
-                    r = x >= T[(size_t)vv * E1 + e] ? x : r;
-                }
-                r = d0 >= T[(size_t)vv * E1] ? d0 : r;
-                n_correct += (r >> 6) & 1u;
-                sum_exit += r & 63u;
-            }
-        }
-    }
+    const auto rank_word = [&](int e) {
+        if constexpr (E1C > 0) return tq[e];
+        else return T[(size_t)vv * E1 + e];
+    };
+    ranked_walk<E1C>(rec, s_rec, E1, E1P, N, chunk, rank_word, [](int, int) {}, [&](int, unsigned r) {
+        n_correct += (r >> 6) & 1u;
+        sum_exit += r & 63u;
+    });
     if (v < V) {
         acc[v] = (double)n_correct / (double)N;
         mean_exit[v] = (double)sum_exit / (double)N;

@@ -253,8 +253,7 @@ void launch_threshold_sweep(const double* conf, const unsigned char* correct, in
 // ee_threshold_search (threshold_search.hip; include/mmee.h MMEE_SEARCH_*, capi_internal.h asserts the values agree)
 enum { SEARCH_GRID = 0, SEARCH_SAMPLED = 1, SEARCH_MIXTURES = 2 };
 enum { SEARCH_REFERENCE = 0, SEARCH_POLICY = 1 };
-// the P percentiles as (lower index, upper index, weight) in the sorted row: functions of N and P only, computed on the host in numpy's own
-// index arithmetic.  A kernel ARGUMENT of search_table_kernel.
+// the P percentiles as (lower index, upper index, weight) in the sorted row, from N and P in numpy's index arithmetic: search_table_kernel's ARGUMENT
 struct SearchPercentiles {
     int lo[64], hi[64];
     double t[64];
@@ -280,6 +279,7 @@ struct SearchArgs {
     double* front_thresholds;        // (N + 1, E1)
 };
 bool launch_threshold_search(const SearchArgs& a, const SearchPercentiles& pc, hipStream_t s);
+void launch_search_table(const double* sorted, int E1, int N, int P, const SearchPercentiles& pc, int strict, double* table, unsigned* trank, hipStream_t s);
 // ee_threshold_search_cost (threshold_search_cost.hip): the same search, the front of (cost_sum down, hits up)
 struct SearchCostArgs {
     SearchArgs base;                 // front_exit_sum: the exit sum of each entry's vector

@@ -7,16 +7,38 @@
 //   search_table_kernel   E1 x P threads: table[e][j] = the j-th of P percentiles of exit e, one lerp of two neighbours of the sorted row, and
 //                         trank[e][j] = its rank word by sweep_thr_kernel's rule.  A candidate vector is E1 digits in [0, P): its E1 rank words
 //                         are E1 lookups in this E1 x P table -- no threshold is uploaded and none is searched per vector.
-//   search_main_kernel    sweep_main_kernel's loop (one THREAD per vector, documents as LDS broadcasts, two vector instructions per exit), the
+//   search_main_kernel    ranked_walk (ranked_common.h: one THREAD per vector, documents as LDS broadcasts, two vector instructions per exit), the
 //                         thread's rank words built from its digits -- decoded from the vector's index (grid), hashed (sampled) or loaded
 //                         (mixtures) -- through trank in LDS.  Under the POLICY's semantics the last rank word is 0: every document "fires" at
 //                         the final exit, which makes it the fallback with no branch in the loop.  One 64-bit atomic max per vector:
 //                         bucket[exit_sum] = max(hits << 32 | ~v): the most hits per exit sum, ties to the LOWEST vector index.  Deterministic.
 //   search_front_kernel   one workgroup over the buckets in ascending exit sum: a bucket is on the front iff its hits exceed every lower
-//                         bucket's (prefix max with a running carry), compacted by ballot / popcount (the pattern of emit_leavers_kernel).
-#include "search_common.h"
+//                         bucket's (prefix max with a running carry), compacted by its dense place among the kept (block1024_scan and
+//                         block1024_count, ranked_common.h).
+#include "ranked_common.h"
 
 namespace mmee {
+
+__global__ __launch_bounds__(256) void search_table_kernel(const double* __restrict__ sorted, int E1, int N, int P, SearchPercentiles pc, int strict,
+                                                           double* __restrict__ table, unsigned* __restrict__ trank) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= E1 * P) return;
+    const int e = i / P, j = i - e * P;
+    const double* row = sorted + (size_t)e * N;
+    const double t = e < E1 - 1 ? percentile_lerp(row[pc.lo[j]], row[pc.hi[j]], pc.t[j]) : 0.0;      // the final exit's row: 0.0 (generate_thresholds)
+    int lo = 0, hi = N;                                              // sweep_thr_kernel's search and its rank word
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (strict ? row[mid] <= t : row[mid] < t) lo = mid + 1;
+        else hi = mid;
+    }
+    table[i] = t;
+    trank[i] = t != t ? 0xffffffffu : (unsigned)lo << 8;
+}
+
+void launch_search_table(const double* sorted, int E1, int N, int P, const SearchPercentiles& pc, int strict, double* table, unsigned* trank, hipStream_t s) {
+    hipLaunchKernelGGL(search_table_kernel, dim3((E1 * P + 255) / 256), dim3(256), 0, s, sorted, E1, N, P, pc, strict, table, trank);
+}
 
 template <int E1C>      // E1C > 0: compile-time exit count (unrolled, rank words in registers); 0: run-time E1 (rank words in the thread's private array)
 __global__ __launch_bounds__(256, 2) void search_main_kernel(const unsigned* __restrict__ rec, const unsigned* __restrict__ trank, SearchVectors sv,
@@ -41,47 +63,11 @@ __global__ __launch_bounds__(256, 2) void search_main_kernel(const unsigned* __r
         search_digits(sv, vv, E1, P, E1 - 1, [&](int e, unsigned d) { tq[e] = s_trank[e * P + d]; });
     }
     tq[n_e - 1] = policy ? 0u : s_trank[(n_e - 1) * P];              // POLICY: the final exit takes whoever is left; REFERENCE: the rank of 0.0
-    unsigned n_correct = 0, sum_exit = 0;
-    for (int n0 = 0; n0 < N; n0 += chunk) {
-        const int cnt = N - n0 < chunk ? N - n0 : chunk;
-        __syncthreads();
-        {
-            const uint4* src = reinterpret_cast<const uint4*>(rec + (size_t)n0 * E1P);
-            uint4* dst = reinterpret_cast<uint4*>(s_rec);
-            const int n16 = cnt * E1P / 4;
-            for (int i = threadIdx.x; i < n16; i += 256) dst[i] = src[i];
-        }
-        __syncthreads();
-        if (E1C > 0) {
-#pragma unroll 4
-            for (int i = 0; i < cnt; ++i) {
-                const unsigned* d = s_rec + i * E1P;                 // the same address in every lane: a broadcast read
-                const unsigned d0 = d[0];
-                unsigned r = d0;                                     // no exit fires: exit 0 (REFERENCE; under POLICY the final exit always fires)
-#pragma unroll
-                for (int e = E1C - 1; e >= 1; --e) {
-                    const unsigned x = d[e];
-                    r = x >= tq[e] ? x : r;
-                }
-                r = d0 >= tq[0] ? d0 : r;                            // exit 0 fires: it is the first
-                n_correct += (r >> 6) & 1u;
-                sum_exit += r & 63u;
-            }
-        } else {
-            for (int i = 0; i < cnt; ++i) {
-                const unsigned* d = s_rec + i * E1P;
-                const unsigned d0 = d[0];
-                unsigned r = d0;
-                for (int e = E1 - 1; e >= 1; --e) {
-                    const unsigned x = d[e];
-                    r = x >= tq[e] ? x : r;
-                }
-                r = d0 >= tq[0] ? d0 : r;
-                n_correct += (r >> 6) & 1u;
-                sum_exit += r & 63u;
-            }
-        }
-    }
+    unsigned n_correct = 0, sum_exit = 0;                            // REFERENCE: no exit fires -> exit 0; under POLICY the final exit always fires
+    ranked_walk<E1C>(rec, s_rec, E1, E1P, N, chunk, [&](int e) { return tq[e]; }, [](int, int) {}, [&](int, unsigned r) {
+        n_correct += (r >> 6) & 1u;
+        sum_exit += r & 63u;
+    });
     if (v < sv.V) {
         if (acc) acc[v] = (double)n_correct / (double)N;
         if (mean_exit) mean_exit[v] = (double)sum_exit / (double)N;
@@ -91,8 +77,8 @@ __global__ __launch_bounds__(256, 2) void search_main_kernel(const unsigned* __r
 
 // One workgroup of 1024 threads walks the buckets in chunks of 1024, ascending exit sum.  A bucket word is 0 (no vector has this exit sum: the
 // low half of a written word is 0xFFFFFFFF - v >= 1) or hits << 32 | ~v of its best vector.
-//   on the front  <=>  hits > the hits of every LOWER bucket: wave prefix max by shuffles -> cross-wave prefix in LDS -> running carry;
-//   dense place   ballot -> popcount prefix -> cross-wave prefix in LDS -> running carry: ascending exit sum, as emit_leavers_kernel ranks.
+//   on the front  <=>  hits > the hits of every LOWER bucket: the exclusive prefix max of the chunk and a running carry;
+//   dense place   the exclusive count of the kept and a running carry: ascending exit sum, as emit_leavers_kernel ranks.
 // Each kept thread writes its entry and gathers its threshold row from `table` by the vector's digits.
 __global__ __launch_bounds__(1024) void search_front_kernel(const unsigned long long* __restrict__ buckets, int n_buckets, SearchVectors sv, int E1,
                                                             int P, const double* __restrict__ table, int cap, int* __restrict__ front_count,
@@ -100,38 +86,17 @@ __global__ __launch_bounds__(1024) void search_front_kernel(const unsigned long 
                                                             unsigned* __restrict__ front_vector, double* __restrict__ front_thr) {
     __shared__ int s_max[16];
     __shared__ int s_cnt[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const auto imax = [](int a, int b) { return a > b ? a : b; };
+    const int tid = threadIdx.x;
     int carry_max = -1, carry_cnt = 0;                               // over the chunks so far: the same values in every thread
     for (int base = 0; base < n_buckets; base += 1024) {
         const int i = base + tid;
         const unsigned long long w = i < n_buckets ? buckets[i] : 0ull;
         const int h = w ? (int)(w >> 32) : -1;                       // hits <= N < 2^24
-        int m = h;                                                   // inclusive prefix max inside the wave
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(m, o, 64);
-            if (lane >= o) m = t > m ? t : m;
-        }
-        int below_max = __shfl_up(m, 1, 64);
-        if (lane == 0) below_max = -1;
-        if (lane == 63) s_max[wave] = m;
-        __syncthreads();
-        int chunk_max = carry_max;
-        for (int k = 0; k < 16; ++k) {
-            if (k < wave) below_max = s_max[k] > below_max ? s_max[k] : below_max;
-            chunk_max = s_max[k] > chunk_max ? s_max[k] : chunk_max;
-        }
-        below_max = carry_max > below_max ? carry_max : below_max;
-        const bool keep = h > below_max;                             // an empty bucket (h = -1) never is
-        const unsigned long long ballot = __ballot(keep);
-        const int below = __popcll(ballot & ((1ull << lane) - 1ull));
-        if (lane == 0) s_cnt[wave] = __popcll(ballot);
-        __syncthreads();
-        int wbefore = 0, total = 0;
-        for (int k = 0; k < 16; ++k) {
-            if (k < wave) wbefore += s_cnt[k];
-            total += s_cnt[k];
-        }
-        const int pos = carry_cnt + wbefore + below;
+        const BlockScan<int> lower = block1024_scan(h, -1, imax, s_max);
+        const bool keep = h > imax(carry_max, lower.exclusive);      // an empty bucket (h = -1) never is
+        const BlockScan<int> kept = block1024_count(keep, s_cnt);
+        const int pos = carry_cnt + kept.exclusive;
         if (keep && pos < cap) {
             const unsigned v = 0xFFFFFFFFu - (unsigned)(w & 0xFFFFFFFFull);
             front_exit_sum[pos] = i;
@@ -141,8 +106,8 @@ __global__ __launch_bounds__(1024) void search_front_kernel(const unsigned long 
             search_digits(sv, v, E1, P, E1 - 1, [&](int e, unsigned d) { row[e] = table[e * P + d]; });
             row[E1 - 1] = table[(E1 - 1) * P];
         }
-        carry_max = chunk_max;
-        carry_cnt += total;
+        carry_max = imax(carry_max, lower.total);
+        carry_cnt += kept.total;
         __syncthreads();                                             // s_max and s_cnt are rewritten by the next chunk
     }
     if (tid == 0) front_count[0] = carry_cnt;
@@ -161,7 +126,7 @@ bool launch_threshold_search(const SearchArgs& a, const SearchPercentiles& pc, h
         return false;
     }
     (void)hipMemsetAsync(buckets, 0, (size_t)n_buckets * 8, s);
-    hipLaunchKernelGGL(search_table_kernel, dim3((a.E1 * a.P + 255) / 256), dim3(256), 0, s, r.sorted, a.E1, a.N, a.P, pc, policy, a.table, trank);
+    launch_search_table(r.sorted, a.E1, a.N, a.P, pc, policy, a.table, trank, s);
     const SearchVectors sv{a.source, a.V, a.seed, a.mixtures};
     const unsigned grid = (unsigned)(((unsigned long long)a.V + 255) / 256);
     const size_t lds = (size_t)kSearchChunkWords * 4 + (size_t)a.E1 * a.P * 4;

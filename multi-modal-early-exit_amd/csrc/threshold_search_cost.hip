@@ -1,20 +1,22 @@
 // The cost-weighted threshold search (ee_threshold_search_cost, include/mmee.h): ee_threshold_search's candidates and exit rules, but a vector is
 // charged cost_sum(v) = sum_n cost[exit(v, n)][n] -- what the caller says a document costs when it leaves at an exit (FLOPs of the packed path:
 // sweep.exit_costs) -- and the front is the one of (cost_sum down, hits up).  The ranking pass, the percentile table and the digits are the
-// search's own (SweepRanks, search_common.h).
+// search's own (SweepRanks, launch_search_table, ranked_common.h).
 //   search_cost_pack_kernel   cost (E1, N) -> (N, E1P): the rank records' layout, so that a chunk of documents is one contiguous copy.
-//   search_cost_main_kernel   search_main_kernel's loop over chunks of HALF as many documents: rank records and cost rows of the same documents
-//                             side by side in LDS.  The selected record carries its exit in r & 63, so the document's cost is ONE per-lane LDS
-//                             read of s_cost[i * E1P + (r & 63)] (at most E1 consecutive words across the wave: distinct banks or the same
-//                             address) and a 64-bit add; no second select per exit.  Per vector: (hits, exit_sum) and cost_sum to the workspace
-//                             (cost_sum to the caller's array when given) and one 64-bit atomicMin(best_cost[hits], cost_sum).
+//   search_cost_main_kernel   ranked_walk (ranked_common.h) over chunks of HALF as many documents: rank records and cost rows of the same
+//                             documents side by side in LDS, the cost rows copied by the walk's staging hook.  The selected record carries its
+//                             exit in r & 63, so the document's cost is ONE per-lane LDS read of s_cost[i * E1P + (r & 63)] (at most E1
+//                             consecutive words across the wave: distinct banks or the same address) and a 64-bit add; no second select per
+//                             exit.  Per vector: (hits, exit_sum) and cost_sum to the workspace (cost_sum to the caller's array when given)
+//                             and one 64-bit atomicMin(best_cost[hits], cost_sum).
 //   search_cost_pick_kernel   over the vectors: cost_sum[v] == best_cost[hits[v]] -> atomicMin(best_vec[hits[v]], v): the lowest index among the
 //                             cheapest of a hits bucket, without 64 + 32 bits in one word.
 //   search_cost_front_kernel  one workgroup over the N + 1 hits buckets from the most hits down: a bucket is on the front iff its cost is below
-//                             that of every non-empty bucket with MORE hits (prefix min with a running carry), compacted by ballot / popcount
-//                             (search_front_kernel's pattern); counted in a first pass, placed from the end in a second: ascending in cost.
+//                             that of every non-empty bucket with MORE hits (prefix min with a running carry), compacted by its dense place
+//                             among the kept (block1024_scan, block1024_count); counted in a first pass, placed from the end in a second:
+//                             ascending in cost.
 // Buckets are by hits and not by cost because hits <= N is the small integer of the pair: cost sums reach 2^56.
-#include "search_common.h"
+#include "ranked_common.h"
 
 namespace mmee {
 
@@ -55,55 +57,15 @@ __global__ __launch_bounds__(256, 2) void search_cost_main_kernel(const unsigned
     tq[n_e - 1] = policy ? 0u : s_trank[(n_e - 1) * P];              // POLICY: the final exit takes whoever is left; REFERENCE: the rank of 0.0
     unsigned n_correct = 0, sum_exit = 0;
     unsigned long long sum_cost = 0;
-    for (int n0 = 0; n0 < N; n0 += chunk) {
-        const int cnt = N - n0 < chunk ? N - n0 : chunk;
-        __syncthreads();
-        {
-            const uint4* src = reinterpret_cast<const uint4*>(rec + (size_t)n0 * E1P);
-            const uint4* csrc = reinterpret_cast<const uint4*>(cost_t + (size_t)n0 * E1P);
-            uint4* dst = reinterpret_cast<uint4*>(s_rec);
-            uint4* cdst = reinterpret_cast<uint4*>(s_cost);
-            const int n16 = cnt * E1P / 4;
-            for (int i = threadIdx.x; i < n16; i += 256) {
-                dst[i] = src[i];
-                cdst[i] = csrc[i];
-            }
-        }
-        __syncthreads();
-        if (E1C > 0) {
-#pragma unroll 4
-            for (int i = 0; i < cnt; ++i) {
-                const unsigned* d = s_rec + i * E1P;                 // the same address in every lane: a broadcast read
-                const unsigned d0 = d[0];
-                unsigned r = d0;                                     // no exit fires: exit 0 (REFERENCE; under POLICY the final exit always fires)
-#pragma unroll
-                for (int e = E1C - 1; e >= 1; --e) {
-                    const unsigned x = d[e];
-                    r = x >= tq[e] ? x : r;
-                }
-                r = d0 >= tq[0] ? d0 : r;                            // exit 0 fires: it is the first
-                const unsigned ex = r & 63u;
-                n_correct += (r >> 6) & 1u;
-                sum_exit += ex;
-                sum_cost += s_cost[i * E1P + ex];                    // the gather: one LDS read per lane, the exit is already in the record
-            }
-        } else {
-            for (int i = 0; i < cnt; ++i) {
-                const unsigned* d = s_rec + i * E1P;
-                const unsigned d0 = d[0];
-                unsigned r = d0;
-                for (int e = E1 - 1; e >= 1; --e) {
-                    const unsigned x = d[e];
-                    r = x >= tq[e] ? x : r;
-                }
-                r = d0 >= tq[0] ? d0 : r;
-                const unsigned ex = r & 63u;
-                n_correct += (r >> 6) & 1u;
-                sum_exit += ex;
-                sum_cost += s_cost[i * E1P + ex];
-            }
-        }
-    }
+    const auto stage_cost = [&](int n0, int i) {                     // the chunk's cost rows, in the same loop as its rank records
+        reinterpret_cast<uint4*>(s_cost)[i] = reinterpret_cast<const uint4*>(cost_t + (size_t)n0 * E1P)[i];
+    };
+    ranked_walk<E1C>(rec, s_rec, E1, E1P, N, chunk, [&](int e) { return tq[e]; }, stage_cost, [&](int i, unsigned r) {
+        const unsigned ex = r & 63u;
+        n_correct += (r >> 6) & 1u;
+        sum_exit += ex;
+        sum_cost += s_cost[i * E1P + ex];                            // the gather: one LDS read per lane, the exit is already in the record
+    });
     if (v < sv.V) {
         if (acc) acc[v] = (double)n_correct / (double)N;
         if (mean_exit) mean_exit[v] = (double)sum_exit / (double)N;
@@ -123,10 +85,10 @@ __global__ __launch_bounds__(256) void search_cost_pick_kernel(const uint2* __re
 }
 
 // One workgroup of 1024 threads walks the hits buckets in chunks of 1024 from the MOST hits down: position j is bucket n_buckets - 1 - j.
-//   on the front  <=>  cost < the cost of every bucket with more hits: wave prefix min by shuffles -> cross-wave prefix in LDS -> running carry
-//                      (an empty bucket holds all-ones and is below nothing);
-//   dense place   ballot -> popcount prefix -> cross-wave prefix in LDS -> running carry gives the entry's rank from the END; the first pass only
-//                 counts, the second writes entry count - 1 - rank: ascending in cost and in hits.
+//   on the front  <=>  cost < the cost of every bucket with more hits: the exclusive prefix min of the chunk and a running carry (an empty
+//                      bucket holds all-ones and is below nothing);
+//   dense place   the exclusive count of the kept and a running carry give the entry's rank from the END; the first pass only counts, the
+//                 second writes entry count - 1 - rank: ascending in cost and in hits.
 // Each kept thread writes its entry and gathers its threshold row from `table` by the vector's digits.
 __global__ __launch_bounds__(1024) void search_cost_front_kernel(const unsigned long long* __restrict__ best_cost, const unsigned* __restrict__ best_vec,
                                                                  const uint2* __restrict__ hits_exits, int n_buckets, SearchVectors sv, int E1, int P,
@@ -136,7 +98,8 @@ __global__ __launch_bounds__(1024) void search_cost_front_kernel(const unsigned 
                                                                  double* __restrict__ front_thr) {
     __shared__ unsigned long long s_min[16];
     __shared__ int s_cnt[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const auto umin = [](unsigned long long a, unsigned long long b) { return a < b ? a : b; };
+    const int tid = threadIdx.x;
     int n_kept = 0;
     for (int pass = 0; pass < 2; ++pass) {
         unsigned long long carry_min = kNoCost;                      // over the chunks so far: the same values in every thread
@@ -144,33 +107,11 @@ __global__ __launch_bounds__(1024) void search_cost_front_kernel(const unsigned 
         for (int base = 0; base < n_buckets; base += 1024) {
             const int j = base + tid, h = n_buckets - 1 - j;
             const unsigned long long c = j < n_buckets ? best_cost[h] : kNoCost;
-            unsigned long long m = c;                                // inclusive prefix min inside the wave
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned long long t = __shfl_up(m, o, 64);
-                if (lane >= o) m = t < m ? t : m;
-            }
-            unsigned long long above_min = __shfl_up(m, 1, 64);
-            if (lane == 0) above_min = kNoCost;
-            if (lane == 63) s_min[wave] = m;
-            __syncthreads();
-            unsigned long long chunk_min = carry_min;
-            for (int k = 0; k < 16; ++k) {
-                if (k < wave) above_min = s_min[k] < above_min ? s_min[k] : above_min;
-                chunk_min = s_min[k] < chunk_min ? s_min[k] : chunk_min;
-            }
-            above_min = carry_min < above_min ? carry_min : above_min;
-            const bool keep = c < above_min;                         // an empty bucket (all-ones) never is
-            const unsigned long long ballot = __ballot(keep);
-            const int below = __popcll(ballot & ((1ull << lane) - 1ull));
-            if (lane == 0) s_cnt[wave] = __popcll(ballot);
-            __syncthreads();
-            int wbefore = 0, total = 0;
-            for (int k = 0; k < 16; ++k) {
-                if (k < wave) wbefore += s_cnt[k];
-                total += s_cnt[k];
-            }
+            const BlockScan<unsigned long long> above = block1024_scan(c, kNoCost, umin, s_min);
+            const bool keep = c < umin(carry_min, above.exclusive);  // an empty bucket (all-ones) never is
+            const BlockScan<int> kept = block1024_count(keep, s_cnt);
             if (pass == 1 && keep) {
-                const int pos = n_kept - 1 - (carry_cnt + wbefore + below);      // 0 <= pos < n_kept <= n_buckets = the outputs' N + 1 entries
+                const int pos = n_kept - 1 - (carry_cnt + kept.exclusive);        // 0 <= pos < n_kept <= n_buckets = the outputs' N + 1 entries
                 const unsigned v = best_vec[h];
                 front_cost_sum[pos] = c;
                 front_exit_sum[pos] = (int)hits_exits[v].y;
@@ -180,8 +121,8 @@ __global__ __launch_bounds__(1024) void search_cost_front_kernel(const unsigned 
                 search_digits(sv, v, E1, P, E1 - 1, [&](int e, unsigned d) { row[e] = table[e * P + d]; });
                 row[E1 - 1] = table[(E1 - 1) * P];
             }
-            carry_min = chunk_min;
-            carry_cnt += total;
+            carry_min = umin(carry_min, above.total);
+            carry_cnt += kept.total;
             __syncthreads();                                         // s_min and s_cnt are rewritten by the next chunk
         }
         n_kept = carry_cnt;
@@ -214,7 +155,7 @@ bool launch_threshold_search_cost(const SearchCostArgs& ca, const SearchPercenti
     (void)hipMemsetAsync(best_cost, 0xFF, (size_t)n_buckets * 8, s);
     (void)hipMemsetAsync(best_vec, 0xFF, (size_t)n_buckets * 4, s);
     hipLaunchKernelGGL(search_cost_pack_kernel, dim3((unsigned)(((long long)a.N * E1P + 255) / 256)), dim3(256), 0, s, ca.cost, a.E1, E1P, a.N, cost_t);
-    hipLaunchKernelGGL(search_table_kernel, dim3((a.E1 * a.P + 255) / 256), dim3(256), 0, s, r.sorted, a.E1, a.N, a.P, pc, policy, a.table, trank);
+    launch_search_table(r.sorted, a.E1, a.N, a.P, pc, policy, a.table, trank, s);
     const SearchVectors sv{a.source, a.V, a.seed, a.mixtures};
     const unsigned grid = (unsigned)(((unsigned long long)a.V + 255) / 256);
     const size_t lds = (size_t)kSearchChunkWords * 4 + (size_t)a.E1 * a.P * 4;
