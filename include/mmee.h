@@ -634,6 +634,42 @@ int ee_temperature_fit(const double* logits, const int64_t* labels, int32_t E1, 
                        void* stream);
 
 /*
+ * Exit heads fitted on the device from a frozen backbone's CLS rows (the two-stage strategies of the reference train only the heads,
+ * EE/models/EE_modules.py:91, 108-113 with the backbone frozen at EE/IC_only.py:189-207; a one-layer ramp head, exit_head_num_layers = 1,
+ * EE/models/LayoutLMv3.py:84-93, is one Linear).  Solved per exit e, independently:
+ *
+ *     L_e(theta) = (1/N) sum_n [ logsumexp(z_n) - z_n[y_n] ] + (l2 / 2) (||W||^2 + ||b||^2),      z_n = W x_n + b
+ *
+ * with the features X_e (N,H) float32, the labels y (N,) int64 in [0,K) and theta_e = (W_e (K,H), b_e (K,)).  The bias is penalised too:
+ * without that the optimum is unique only up to a common shift of b.  With l2 > 0 the objective is l2-strongly convex; l2 <= 0 is refused.
+ * All arithmetic is float64 on the float32 features (widening is exact), the logsumexp is max-shifted.
+ *
+ * ee_head_fit: L-BFGS (`history` pairs, 1 <= history <= 32) from theta = 0 as a fixed launch list of max_evals ticks of [loss / gradient,
+ *   controller]; no host round trip between them.  The controller accepts a trial point by the Armijo test (c1 = 1e-4, halving; step 1
+ *   except the very first, 1 / ||g||), skips a pair with s.y <= 0 and writes the next trial point.  The test reads
+ *   L(trial) <= L + c1 step g.d + 8 eps |L|: the last term allows for the rounding of L, without which nothing passes once a good step's
+ *   decrease is below the resolution of L (gradient norms of a few 1e-9).  An exit stops with
+ *   status 0 when ||grad L||_2 <= gtol, 1 after max_evals evaluations, 2 after 30 halvings without progress; a stopped exit costs nothing
+ *   more.  features dev (E,N,H), 16-byte aligned, H % 4 == 0, 4 <= H <= 1024; 2 <= K <= 64; workspace dev of
+ *   ee_head_fit_workspace_bytes(E,N,H,K,history) bytes.  Outputs dev: weight (E,K,H), bias (E,K) float32; optional weight64 / bias64 (the
+ *   float64 solution the float32 pair is rounded from), loss, grad_norm (of the returned point), evals, status (E,).
+ *   A label outside [0,K) raises the error word at the head of the workspace: the call then fails with a message and has written no
+ *   output.  To know that, the call waits for its stream before it returns.
+ *   The sums are taken in a fixed order that depends on N alone: two calls return the same bits, and an exit fitted together with others
+ *   gets the bits it gets alone.
+ * ee_debug_head_lossgrad: ONE evaluation of L_e and grad L_e (the launch a tick makes) at theta64 dev (E, K*H + K): W_e then b_e;
+ *   loss dev (E,), grad dev (E, K*H + K).
+ * MMEE_HEAD_FIT_SLAB: the rows a workgroup keeps on chip between its logits and its gradient pass.
+ */
+#define MMEE_HEAD_FIT_SLAB 32
+int ee_head_fit(const float* features, const int64_t* labels, int32_t E, int32_t N, int32_t H, int32_t K, double l2, double gtol,
+                int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* weight, float* bias, double* weight64,
+                double* bias64, double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream);
+size_t ee_head_fit_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history);
+int ee_debug_head_lossgrad(const float* features, const int64_t* labels, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K,
+                           double l2, double* loss, double* grad, void* stream);
+
+/*
  * Device-side input feed (replaces the host image processor + collator in front of the model, EE/data/RVL_CDIP.py:246-262
  * and EE/utils.py:93-98, 173).
  *

@@ -1,5 +1,5 @@
 // Entry points of libmmee_hip.so that never see a handle: bucket LUT, shader-clock stamps, policy / patience / threshold sweeps, temperature
-// fit, the evaluation report (ee_exit_metrics), result packing, the device-side input feed, and the ee_debug_* hooks that run one kernel on
+// fit, the exit-head fit (ee_head_fit), the evaluation report (ee_exit_metrics), result packing, the device-side input feed, and the ee_debug_* hooks that run one kernel on
 // caller-provided buffers.
 #include <math.h>
 #include <string.h>
@@ -362,6 +362,74 @@ int ee_temperature_fit(const double* logits, const int64_t* labels, int32_t E1, 
     launch_temperature_fit(logits, (const long long*)labels, E1, N, K, max_iter > 0 ? max_iter : 100, temperature, nll, accuracy,
                            avg_confidence, iterations, reinterpret_cast<hipStream_t>(stream));
     return launch_status(nullptr, "ee_temperature_fit");
+}
+
+// ---- exit heads from CLS rows (head_fit.hip) -----------------------------------------------------------------------------
+static_assert(kHeadFitSlab == MMEE_HEAD_FIT_SLAB, "the kernel's slab height is the ABI's");
+// the refusals ee_head_fit and ee_debug_head_lossgrad share, before any device call
+static int head_fit_refuse(const char* who, const float* features, int32_t E, int32_t N, int32_t H, int32_t K, double l2) {
+    if (E < 1 || E > 65535) return fail(nullptr, "%s: E = %d, need 1 <= E <= 65535", who, E);
+    if (N < 1) return fail(nullptr, "%s: N = %d, need N >= 1", who, N);
+    if (K < 2 || K > 64) return fail(nullptr, "%s: K = %d, need 2 <= K <= 64 (ee_create's limit)", who, K);
+    if (H < 4 || H > kHeadFitMaxH || H % 4 != 0)
+        return fail(nullptr, "%s: H = %d, need 4 <= H <= %d and H %% 4 == 0 (a slab of %d rows stays in LDS)", who, H, kHeadFitMaxH, kHeadFitSlab);
+    if (!(l2 > 0.0)) return fail(nullptr, "%s: l2 = %g, need l2 > 0 (the objective is strongly convex only then)", who, l2);
+    if (reinterpret_cast<uintptr_t>(features) % 16 != 0) return fail(nullptr, "%s: features must be 16-byte aligned", who);
+    return 0;
+}
+
+size_t ee_head_fit_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history) {
+    if (E < 1 || N < 1 || H < 1 || K < 1 || history < 1) return 0;
+    return head_fit_workspace_bytes(E, N, H, K, history);
+}
+
+int ee_head_fit(const float* features, const int64_t* labels, int32_t E, int32_t N, int32_t H, int32_t K, double l2, double gtol,
+                int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* weight, float* bias, double* weight64,
+                double* bias64, double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
+    const char* who = "ee_head_fit";
+    if (!features || !labels || !workspace || !weight || !bias)
+        return fail(nullptr, "%s: NULL argument (features, labels, workspace, weight and bias are required)", who);
+    if (head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
+    if (!(gtol >= 0.0)) return fail(nullptr, "%s: gtol = %g, need gtol >= 0", who, gtol);
+    if (max_evals < 1) return fail(nullptr, "%s: max_evals = %d, need max_evals >= 1", who, max_evals);
+    if (history < 1 || history > kHeadFitMaxHistory) return fail(nullptr, "%s: history = %d, need 1 <= history <= %d", who, history, kHeadFitMaxHistory);
+    const size_t need = head_fit_workspace_bytes(E, N, H, K, history);
+    if (workspace_bytes < need) return fail(nullptr, "%s: workspace of %zu bytes, needs %zu bytes", who, workspace_bytes, need);
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HeadFitArgs a{};
+    a.features = features; a.labels = reinterpret_cast<const long long*>(labels); a.E = E; a.N = N; a.H = H; a.K = K; a.l2 = l2; a.gtol = gtol;
+    a.max_evals = max_evals; a.history = history; a.workspace = workspace; a.weight = weight; a.bias = bias; a.weight64 = weight64;
+    a.bias64 = bias64; a.loss = loss; a.grad_norm = grad_norm; a.evals = evals; a.status = status;
+    if (!launch_head_fit(a, s)) return fail(nullptr, "%s: memset of the workspace failed", who);
+    if (launch_status(nullptr, who)) return 1;
+    int err = 0;
+    if (hipMemcpyAsync(&err, workspace, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return fail(nullptr, "%s: reading the error word failed: %s", who, hipGetErrorString(hipGetLastError()));
+    if (err & 1) return fail(nullptr, "%s: a label is outside [0, K = %d); no output was written", who, K);
+    return 0;
+}
+
+int ee_debug_head_lossgrad(const float* features, const int64_t* labels, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K,
+                           double l2, double* loss, double* grad, void* stream) {
+    const char* who = "ee_debug_head_lossgrad";
+    if (!features || !labels || !theta64 || !loss || !grad) return fail(nullptr, "%s: NULL argument", who);
+    if (head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    Scratch sc;
+    double* partial = nullptr;
+    int* err_dev = nullptr;
+    if (!sc.get(&partial, head_fit_partial_bytes(E, N, H, K) / sizeof(double)) || !sc.get(&err_dev, 1))
+        return fail(nullptr, "%s: hipMalloc of the scratch failed", who);
+    launch_head_lossgrad(features, reinterpret_cast<const long long*>(labels), theta64, E, N, H, K, l2, partial, err_dev, loss, grad, s);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(nullptr, "%s: launch failed: %s", who, hipGetErrorString(e));
+    int err = 0;
+    if (hipMemcpy(&err, err_dev, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of the error word failed", who);
+    if (launch_status(nullptr, who)) return 1;
+    if (err & 1) return fail(nullptr, "%s: a label is outside [0, K = %d)", who, K);
+    return 0;
 }
 
 // ---- device-side input feed (N2) ----------------------------------------------------------------------------------------

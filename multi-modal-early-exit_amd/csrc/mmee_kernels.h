@@ -311,6 +311,31 @@ void launch_csf_table(const double* logits, const long long* refs, int E1, int N
                       hipStream_t s);
 void launch_temperature_fit(const double* logits, const long long* labels, int E1, int N, int K, int max_iter, double* T_out,
                             double* nll_out, double* acc_out, double* conf_out, int* iters_out, hipStream_t s);
+// ee_head_fit (head_fit.hip): softmax-regression heads per exit, float64 on float32 features; include/mmee.h states the objective
+constexpr int kHeadFitSlab = 32;             // rows a workgroup keeps in LDS between the logits and the gradient pass (MMEE_HEAD_FIT_SLAB)
+constexpr int kHeadFitMaxChunks = 128;       // row chunks (= partial gradients) per exit
+constexpr int kHeadFitMaxH = 1024;           // a slab of kHeadFitSlab float32 rows stays inside the 160 KB of LDS
+constexpr int kHeadFitMaxHistory = 32;
+struct HeadFitArgs {
+    const float* features;           // (E,N,H)
+    const long long* labels;         // (N,)
+    int E, N, H, K;
+    double l2, gtol;
+    int max_evals, history;
+    void* workspace;                 // head_fit_workspace_bytes
+    float *weight, *bias;            // (E,K,H), (E,K)
+    double *weight64, *bias64;       // the same in float64, or null
+    double *loss, *grad_norm;        // (E,) or null
+    int *evals, *status;             // (E,) or null
+};
+int head_fit_chunks(int N);
+size_t head_fit_workspace_bytes(int E, int N, int H, int K, int history);
+size_t head_fit_partial_bytes(int E, int N, int H, int K);
+// false: the memset of the workspace failed.  The error word is the first int of the workspace (bit 0: a label outside [0,K)).
+bool launch_head_fit(const HeadFitArgs& a, hipStream_t s);
+// one evaluation at theta (E, K*H + K): loss (E,), grad (E, K*H + K); partial: head_fit_partial_bytes; err: one zeroed int
+void launch_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* partial, int* err,
+                          double* loss, double* grad, hipStream_t s);
 void launch_build_value_tables(const float* w1, const float* wx, const float* wy, const unsigned char* lut1,
                                const unsigned char* lut2, int heads, int bins1, int bins2, int n1, int n2, float inv_sqrt_d,
                                float* t1, float* tx, float* ty, hipStream_t s);
