@@ -670,6 +670,46 @@ int ee_debug_head_lossgrad(const float* features, const int64_t* labels, const d
                            double l2, double* loss, double* grad, void* stream);
 
 /*
+ * Two-layer exit heads fitted on the device from the same CLS rows: the reference's default head, exit_head_num_layers = 2
+ * (LayoutLMv3Exit, EE/models/LayoutLMv3.py:70-93): dense (H,H) -> tanh -> out_proj (K,H); dropout is the identity (eval).  Solved per
+ * exit e, independently, float64 throughout on the float32 features:
+ *
+ *     a_n = tanh(W1 x_n + b1)                                      W1 (H,H) [out,in], b1 (H,)
+ *     z_n = W2 a_n + b2                                            W2 (K,H), b2 (K,)
+ *     L(theta) = (1/N) sum_n [ logsumexp(z_n) - z_n[y_n] ] + (l2 / 2) ||theta||^2
+ *     theta = W1 row-major, b1, W2 row-major, b2                   P = H*H + H + K*H + K
+ *
+ * Every block is penalised, the biases included; l2 <= 0 (and NaN) is refused; the logsumexp is max-shifted.  The objective is not convex:
+ * the fit promises a stationary point reached by descent from the stated start, not a unique optimum.
+ *
+ * ee_mlp_head_fit: the L-BFGS of ee_head_fit (the same controller: Armijo test with c1 = 1e-4 and the 8 eps |L| allowance, halving, first
+ *   step 1 / ||g||, a pair with s.y <= 0 skipped, restart from steepest descent when the direction is no descent, status 2 after 30 halvings)
+ *   from theta0, dev (E,P) float64, which is required: theta = 0 is a saddle the iteration never leaves (with W1 = W2 = 0 only b2 has a
+ *   gradient).  A fixed launch list of max_evals ticks of [loss / gradient, controller], no host round trip between them; a stopped exit's
+ *   workgroups return at once.  Stopping rules and status codes are those of ee_head_fit: 0 when ||grad L||_2 <= gtol, 1 after max_evals
+ *   evaluations, 2 when the line search made no progress.  Limits are those of ee_head_fit: features dev (E,N,H), 16-byte aligned,
+ *   H % 4 == 0, 4 <= H <= 1024; 2 <= K <= 64; 1 <= history <= 32.  workspace dev of ee_mlp_head_fit_workspace_bytes(E,N,H,K,history) bytes:
+ *   8 E P (5 + 2 history) for the controller's vectors + 8 E N (H + K + 1) for the hidden rows, the logits and the rows' losses (+ < 2 KB
+ *   of control words) -- at N = 40 000, H = 768, K = 16, history = 8: 100 MB + 251 MB an exit.
+ *   Outputs dev: dense_weight (E,H,H), dense_bias (E,H), weight (E,K,H), bias (E,K) float32; optional theta64 (E,P), the float64 point they
+ *   are rounded from; optional loss, grad_norm (of the returned point), evals, status (E,).
+ *   A label outside [0,K) fails the call with no output written; the call learns of it by the one wait after the last launch.
+ *   No floating-point atomics: every sum runs in an order that depends on (N, H, K) alone, so two calls return the same bits and an exit
+ *   fitted together with others gets the bits it gets alone.
+ * ee_debug_mlp_head_lossgrad: ONE evaluation of L_e and grad L_e (the launches a tick makes) at theta64 dev (E,P); loss dev (E,), grad dev
+ *   (E,P) in the layout of theta.
+ * MMEE_MLP_HEAD_FIT_ROWS: the largest number of rows any of the fit's kernels treats as one tile (the row tile of its two GEMM kernels).
+ */
+#define MMEE_MLP_HEAD_FIT_ROWS 64
+int ee_mlp_head_fit(const float* features, const int64_t* labels, const double* theta0, int32_t E, int32_t N, int32_t H, int32_t K, double l2,
+                    double gtol, int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* dense_weight,
+                    float* dense_bias, float* weight, float* bias, double* theta64, double* loss, double* grad_norm, int32_t* evals,
+                    int32_t* status, void* stream);
+size_t ee_mlp_head_fit_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history);
+int ee_debug_mlp_head_lossgrad(const float* features, const int64_t* labels, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K,
+                               double l2, double* loss, double* grad, void* stream);
+
+/*
  * Device-side input feed (replaces the host image processor + collator in front of the model, EE/data/RVL_CDIP.py:246-262
  * and EE/utils.py:93-98, 173).
  *

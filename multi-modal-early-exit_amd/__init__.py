@@ -21,4 +21,4 @@ from . import metrics  # noqa: F401,E402
 from .metrics import ExitReport, exit_report  # noqa: F401,E402
 from . import feed  # noqa: F401,E402
 from . import heads  # noqa: F401,E402
-from .heads import HeadFit, collect_exit_features, fit_exit_heads  # noqa: F401,E402
+from .heads import HeadFit, MlpHeadFit, collect_exit_features, fit_exit_heads, fit_mlp_exit_heads  # noqa: F401,E402

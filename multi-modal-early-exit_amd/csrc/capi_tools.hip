@@ -432,6 +432,66 @@ int ee_debug_head_lossgrad(const float* features, const int64_t* labels, const d
     return 0;
 }
 
+// ---- two-layer exit heads from CLS rows (mlp_head_fit.hip) ---------------------------------------------------------------------------
+static_assert(kMlpHeadFitRows == MMEE_MLP_HEAD_FIT_ROWS, "the kernels' row tile is the ABI's");
+
+size_t ee_mlp_head_fit_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history) {
+    if (E < 1 || N < 1 || H < 1 || K < 1 || history < 1) return 0;
+    return mlp_head_fit_workspace_bytes(E, N, H, K, history);
+}
+
+int ee_mlp_head_fit(const float* features, const int64_t* labels, const double* theta0, int32_t E, int32_t N, int32_t H, int32_t K, double l2,
+                    double gtol, int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* dense_weight,
+                    float* dense_bias, float* weight, float* bias, double* theta64, double* loss, double* grad_norm, int32_t* evals,
+                    int32_t* status, void* stream) {
+    const char* who = "ee_mlp_head_fit";
+    if (!features || !labels || !theta0 || !workspace || !dense_weight || !dense_bias || !weight || !bias)
+        return fail(nullptr, "%s: NULL argument (features, labels, theta0, workspace, dense_weight, dense_bias, weight and bias are required; "
+                             "theta = 0 is a saddle the iteration never leaves, so there is no default start)", who);
+    if (head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
+    if (!(gtol >= 0.0)) return fail(nullptr, "%s: gtol = %g, need gtol >= 0", who, gtol);
+    if (max_evals < 1) return fail(nullptr, "%s: max_evals = %d, need max_evals >= 1", who, max_evals);
+    if (history < 1 || history > kHeadFitMaxHistory) return fail(nullptr, "%s: history = %d, need 1 <= history <= %d", who, history, kHeadFitMaxHistory);
+    const size_t need = mlp_head_fit_workspace_bytes(E, N, H, K, history);
+    if (workspace_bytes < need) return fail(nullptr, "%s: workspace of %zu bytes, needs %zu bytes", who, workspace_bytes, need);
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    MlpHeadFitArgs a{};
+    a.features = features; a.labels = reinterpret_cast<const long long*>(labels); a.theta0 = theta0; a.E = E; a.N = N; a.H = H; a.K = K;
+    a.l2 = l2; a.gtol = gtol; a.max_evals = max_evals; a.history = history; a.workspace = workspace; a.dense_weight = dense_weight;
+    a.dense_bias = dense_bias; a.weight = weight; a.bias = bias; a.theta64 = theta64; a.loss = loss; a.grad_norm = grad_norm; a.evals = evals;
+    a.status = status;
+    if (!launch_mlp_head_fit(a, s)) return fail(nullptr, "%s: preparing the workspace (memset, copy of theta0) failed", who);
+    if (launch_status(nullptr, who)) return 1;
+    int err = 0;
+    if (hipMemcpyAsync(&err, workspace, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return fail(nullptr, "%s: reading the error word failed: %s", who, hipGetErrorString(hipGetLastError()));
+    if (err & 1) return fail(nullptr, "%s: a label is outside [0, K = %d); no output was written", who, K);
+    return 0;
+}
+
+int ee_debug_mlp_head_lossgrad(const float* features, const int64_t* labels, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K,
+                               double l2, double* loss, double* grad, void* stream) {
+    const char* who = "ee_debug_mlp_head_lossgrad";
+    if (!features || !labels || !theta64 || !loss || !grad) return fail(nullptr, "%s: NULL argument", who);
+    if (head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    Scratch sc;
+    double* scratch = nullptr;
+    int* err_dev = nullptr;
+    if (!sc.get(&scratch, mlp_head_fit_scratch_doubles(E, N, H, K)) || !sc.get(&err_dev, 1))
+        return fail(nullptr, "%s: hipMalloc of the scratch failed", who);
+    launch_mlp_head_lossgrad(features, reinterpret_cast<const long long*>(labels), theta64, E, N, H, K, l2, scratch, err_dev, loss, grad, s);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(nullptr, "%s: launch failed: %s", who, hipGetErrorString(e));
+    int err = 0;
+    if (hipMemcpy(&err, err_dev, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of the error word failed", who);
+    if (launch_status(nullptr, who)) return 1;
+    if (err & 1) return fail(nullptr, "%s: a label is outside [0, K = %d)", who, K);
+    return 0;
+}
+
 // ---- device-side input feed (N2) ----------------------------------------------------------------------------------------
 int ee_preprocess_images(const uint8_t* images, const void* desc, int32_t B, int32_t R, int32_t max_h, void* workspace,
                          size_t workspace_bytes, float* pixel_values, uint8_t* resized_u8, void* stream) {

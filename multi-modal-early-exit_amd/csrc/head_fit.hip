@@ -8,6 +8,8 @@
 //   head_fit_reduce_kernel      sums the chunk partials in chunk order, divides by N, adds the penalty: L and grad L of the trial point.
 //   head_fit_controller_kernel  one workgroup per exit: Armijo test, history update, two-loop recursion, next trial point.
 //   head_fit_finish_kernel      copies the result out -- unless the error word is set, in which case no output is touched.
+// The controller and the finish kernel are written over a parameter count P and serve the two-layer fit (mlp_head_fit.hip) too, through the
+// launchers of head_fit_common.h, which also holds the workspace layout and the control words the two fits share.
 //
 // Arithmetic form: plain float64 FMAs.  The matrix form (v_mfma_f64_16x16x4_f64) was NOT built, so not measured against it.  Measured for this
 // form (profiles/head_fit.txt): 446 GB/s on the feature bytes at N = 40 000, H = 768, K = 16, E = 6 -- latency-bound, not bandwidth-bound; DESIGN.md
@@ -15,7 +17,7 @@
 //
 // Determinism: the chunking is a function of N alone, every sum has a fixed order, an element of a parameter-sized vector is always touched
 // by the same thread of the controller, and nothing depends on E -- an exit fitted alone gets the bits it gets among others.
-#include "mmee_kernels.h"
+#include "head_fit_common.h"
 
 namespace mmee {
 
@@ -24,17 +26,13 @@ namespace {
 constexpr int S = kHeadFitSlab;
 constexpr int kThreads = 256;
 constexpr int kLogitTile = 8;            // classes per logits-pass round
-constexpr int kCtrlThreads = 1024;
+constexpr int kCtrlThreads = kFitCtrlThreads;
 constexpr double kArmijo = 1e-4;
 // The Armijo test allows for the rounding of L: below a gradient norm of a few 1e-9 the decrease a good step brings is smaller than the
 // resolution of L in float64, and without the allowance no trial point passes any more (measured on the host restatement: 3 of 36 problems
 // stall at 1.2e-9 ... 2.4e-9 for 200 evaluations; with 1, 4 or 16 epsilon |L| none does).
 constexpr double kArmijoSlack = 8.0 * 2.220446049250313e-16;
 constexpr int kMaxHalvings = 30;
-
-// per-exit control words / scalars of the workspace
-enum { CI_STOP = 0, CI_EVALS, CI_HALVINGS, CI_COUNT, CI_HEAD, kCtrlInts = 8 };          // CI_STOP: 0 running, else status + 1 (4: bad label)
-enum { CD_F = 0, CD_STEP, CD_DG, CD_GNORM, CD_GAMMA, kCtrlDoubles = 8 };
 
 __host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -217,20 +215,6 @@ __global__ __launch_bounds__(kThreads) void head_fit_lossgrad_kernel(LossGradArg
     }
 }
 
-// the sum of v[t], v[t + kCtrlThreads], ... over the workgroup, the same bits in every thread; red: kCtrlThreads doubles of LDS
-template <int THREADS>
-__device__ double block_sum(double v, double* red) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    red[t] = v;
-    __syncthreads();
-    for (int s = THREADS / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 struct ReduceArgs {
     const double* partial;
     const double* theta;
@@ -269,26 +253,10 @@ __global__ __launch_bounds__(kThreads) void head_fit_reduce_kernel(ReduceArgs a)
     }
 }
 
-// The workspace of one fit.  Per exit: control words, scalars, then the parameter-sized vectors.
-struct FitLayout {
-    int E, P, M, chunks;
-    size_t o_ctrl, o_scal, o_ftrial, o_rho, o_vec, o_partial, zero_bytes, bytes;
-    size_t vec_stride;               // doubles per exit: (5 + 2 M) * P
-    FitLayout(int E_, int N, int H, int K, int M_) : E(E_), P(K * H + K), M(M_) {
-        chunks = head_fit_chunks(N);
-        auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        o_ctrl = 256;                                                    // the error word lives at 0
-        o_scal = al(o_ctrl + sizeof(int) * kCtrlInts * (size_t)E);
-        o_ftrial = al(o_scal + sizeof(double) * kCtrlDoubles * (size_t)E);
-        o_rho = al(o_ftrial + sizeof(double) * (size_t)E);
-        o_vec = al(o_rho + sizeof(double) * (size_t)M * E);
-        vec_stride = (size_t)(5 + 2 * M) * P;
-        zero_bytes = al(o_vec + sizeof(double) * vec_stride * E);       // everything in front of the partials starts from zero
-        o_partial = zero_bytes;
-        bytes = o_partial + sizeof(double) * (size_t)E * chunks * (size_t)(P + 1);
-    }
-};
-enum { V_THETA = 0, V_TRIAL, V_G, V_GTRIAL, V_DIR, V_HIST };            // V_HIST: s[0 .. M), then y[0 .. M)
+// the one-layer fit's workspace: behind the shared part, one partial (dW, db, loss) per (exit, chunk)
+FitLayout one_layer_layout(int E, int N, int H, int K, int M) {
+    return FitLayout(E, K * H + K, M, head_fit_partial_bytes(E, N, H, K));
+}
 
 struct CtrlArgs {
     char* ws;
@@ -408,26 +376,19 @@ __global__ __launch_bounds__(kCtrlThreads) void head_fit_controller_kernel(CtrlA
     }
 }
 
-struct FinishArgs {
-    const char* ws;
-    FitLayout lay;
-    int K, H;
-    float *weight, *bias;
-    double *weight64, *bias64, *loss, *grad_norm;
-    int *evals, *status;
-};
-
 // grid (ceil(P / 256), E)
-__global__ __launch_bounds__(kThreads) void head_fit_finish_kernel(FinishArgs a) {
+__global__ __launch_bounds__(kThreads) void head_fit_finish_kernel(FitFinishArgs a) {
     if (*reinterpret_cast<const int*>(a.ws) != 0) return;                      // a bad label: the call fails, the outputs stay as they were
-    const int e = blockIdx.y, i = blockIdx.x * kThreads + threadIdx.x, P = a.lay.P, KH = a.K * a.H;
+    const int e = blockIdx.y, i = blockIdx.x * kThreads + threadIdx.x, P = a.lay.P;
     const double* th = reinterpret_cast<const double*>(a.ws + a.lay.o_vec) + (size_t)e * a.lay.vec_stride + (size_t)V_THETA * P;
-    if (i < KH) {
-        a.weight[(size_t)e * KH + i] = (float)th[i];
-        if (a.weight64) a.weight64[(size_t)e * KH + i] = th[i];
-    } else if (i < P) {
-        a.bias[(size_t)e * a.K + i - KH] = (float)th[i];
-        if (a.bias64) a.bias64[(size_t)e * a.K + i - KH] = th[i];
+    if (i < P) {
+        for (int q = 0; q < a.n_seg; ++q) {
+            const FitOutSeg& sg = a.seg[q];
+            if (i < sg.begin || i >= sg.begin + sg.len) continue;
+            sg.out32[(size_t)e * sg.len + i - sg.begin] = (float)th[i];
+            if (sg.out64) sg.out64[(size_t)e * sg.len + i - sg.begin] = th[i];
+        }
+        if (a.theta64) a.theta64[(size_t)e * P + i] = th[i];
     }
     if (i == 0) {
         const int* ci = reinterpret_cast<const int*>(a.ws + a.lay.o_ctrl) + e * kCtrlInts;
@@ -483,9 +444,18 @@ int head_fit_chunks(int N) {
     return (n_slabs + per - 1) / per;
 }
 
-size_t head_fit_workspace_bytes(int E, int N, int H, int K, int history) { return FitLayout(E, N, H, K, history).bytes; }
+size_t head_fit_workspace_bytes(int E, int N, int H, int K, int history) { return one_layer_layout(E, N, H, K, history).bytes; }
 
 size_t head_fit_partial_bytes(int E, int N, int H, int K) { return sizeof(double) * (size_t)E * head_fit_chunks(N) * (size_t)(K * H + K + 1); }
+
+void launch_head_fit_controller(char* ws, const FitLayout& lay, double gtol, int max_evals, hipStream_t s) {
+    CtrlArgs c{ws, lay, gtol, max_evals};
+    hipLaunchKernelGGL(head_fit_controller_kernel, dim3(lay.E), dim3(kCtrlThreads), 0, s, c);
+}
+
+void launch_head_fit_finish(const FitFinishArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(head_fit_finish_kernel, dim3((a.lay.P + kThreads - 1) / kThreads, a.lay.E), dim3(kThreads), 0, s, a);
+}
 
 void launch_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* partial, int* err,
                           double* loss, double* grad, hipStream_t s) {
@@ -496,7 +466,7 @@ void launch_head_lossgrad(const float* X, const long long* y, const double* thet
 }
 
 bool launch_head_fit(const HeadFitArgs& f, hipStream_t s) {
-    const FitLayout lay(f.E, f.N, f.H, f.K, f.history);
+    const FitLayout lay = one_layer_layout(f.E, f.N, f.H, f.K, f.history);
     char* ws = static_cast<char*>(f.workspace);
     if (hipMemsetAsync(ws, 0, lay.zero_bytes, s) != hipSuccess) return false;           // theta = 0, no history, every exit running
     double* vec = reinterpret_cast<double*>(ws + lay.o_vec);
@@ -504,14 +474,14 @@ bool launch_head_fit(const HeadFitArgs& f, hipStream_t s) {
     LossGradArgs a{};
     a.X = f.features; a.y = f.labels; a.theta = vec + V_TRIAL * P; a.theta_stride = lay.vec_stride;
     a.ctrl = reinterpret_cast<const int*>(ws + lay.o_ctrl); a.err = reinterpret_cast<int*>(ws);
-    a.partial = reinterpret_cast<double*>(ws + lay.o_partial); a.N = f.N; a.H = f.H; a.K = f.K;
-    CtrlArgs c{ws, lay, f.gtol, f.max_evals};
+    a.partial = reinterpret_cast<double*>(ws + lay.o_tail); a.N = f.N; a.H = f.H; a.K = f.K;
     for (int tick = 0; tick < f.max_evals; ++tick) {
         launch_eval(a, f.E, f.l2, reinterpret_cast<double*>(ws + lay.o_ftrial), 1, vec + V_GTRIAL * P, lay.vec_stride, s);
-        hipLaunchKernelGGL(head_fit_controller_kernel, dim3(f.E), dim3(kCtrlThreads), 0, s, c);
+        launch_head_fit_controller(ws, lay, f.gtol, f.max_evals, s);
     }
-    FinishArgs o{ws, lay, f.K, f.H, f.weight, f.bias, f.weight64, f.bias64, f.loss, f.grad_norm, f.evals, f.status};
-    hipLaunchKernelGGL(head_fit_finish_kernel, dim3((lay.P + kThreads - 1) / kThreads, f.E), dim3(kThreads), 0, s, o);
+    const int KH = f.K * f.H;
+    FitFinishArgs o{ws, lay, 2, {{0, KH, f.weight, f.weight64}, {KH, f.K, f.bias, f.bias64}, {}, {}}, nullptr, f.loss, f.grad_norm, f.evals, f.status};
+    launch_head_fit_finish(o, s);
     return true;
 }
 

@@ -336,6 +336,28 @@ bool launch_head_fit(const HeadFitArgs& a, hipStream_t s);
 // one evaluation at theta (E, K*H + K): loss (E,), grad (E, K*H + K); partial: head_fit_partial_bytes; err: one zeroed int
 void launch_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* partial, int* err,
                           double* loss, double* grad, hipStream_t s);
+// ee_mlp_head_fit (mlp_head_fit.hip): two-layer heads (dense + tanh + out_proj) per exit; theta = W1 (H,H), b1 (H,), W2 (K,H), b2 (K,)
+constexpr int kMlpHeadFitRows = 64;          // the row tile of the GEMM kernels, the largest of the new kernels' tiles (MMEE_MLP_HEAD_FIT_ROWS)
+struct MlpHeadFitArgs {
+    const float* features;           // (E,N,H)
+    const long long* labels;         // (N,)
+    const double* theta0;            // (E,P): the start
+    int E, N, H, K;
+    double l2, gtol;
+    int max_evals, history;
+    void* workspace;                 // mlp_head_fit_workspace_bytes
+    float *dense_weight, *dense_bias, *weight, *bias;   // (E,H,H), (E,H), (E,K,H), (E,K)
+    double* theta64;                 // (E,P) or null
+    double *loss, *grad_norm;        // (E,) or null
+    int *evals, *status;             // (E,) or null
+};
+size_t mlp_head_fit_workspace_bytes(int E, int N, int H, int K, int history);
+size_t mlp_head_fit_scratch_doubles(int E, int N, int H, int K);
+// false: preparing the workspace failed.  The error word is the first int of the workspace (bit 0: a label outside [0,K)).
+bool launch_mlp_head_fit(const MlpHeadFitArgs& a, hipStream_t s);
+// one evaluation at theta (E,P): loss (E,), grad (E,P); scratch: mlp_head_fit_scratch_doubles doubles; err: one zeroed int
+void launch_mlp_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* scratch,
+                              int* err, double* loss, double* grad, hipStream_t s);
 void launch_build_value_tables(const float* w1, const float* wx, const float* wy, const unsigned char* lut1,
                                const unsigned char* lut2, int heads, int bins1, int bins2, int n1, int n2, float inv_sqrt_d,
                                float* t1, float* tx, float* ty, hipStream_t s);

@@ -1,12 +1,20 @@
-"""One-layer ramp exit heads fitted on the device from a frozen backbone's CLS rows (``ee_head_fit``, include/mmee.h).
+"""Ramp exit heads fitted on the device from a frozen backbone's CLS rows (``ee_head_fit`` and ``ee_mlp_head_fit``, include/mmee.h).
 
 The reference's two-stage strategies train only the heads on a frozen backbone (EE/models/EE_modules.py:91, 108-113;
 EE/IC_only.py:189-207).  Then the training set of the head at encoder layer l is the CLS row leaving that layer, which a dump-all
-forward already returns (``hidden_cls``), and for ``exit_head_num_layers = 1`` (one Linear, EE/models/LayoutLMv3.py:84-93) the fit is
-L2-regularised softmax regression: strongly convex, one optimum.  ``collect_exit_features`` gathers the rows, ``fit_exit_heads``
-solves the regression per exit with L-BFGS in float64 on the device, and ``HeadFit.state_dict`` names the result the way
-``EarlyExitEngine.load_weights`` expects it.  This is not a trainer: two-layer heads, gates, the LTE classifier, embedding-level
-exits, mini-batches and an unfrozen backbone are out of scope.
+forward already returns (``hidden_cls``).  ``collect_exit_features`` gathers the rows.
+
+For ``exit_head_num_layers = 1`` (one Linear, EE/models/LayoutLMv3.py:84-93) the fit is L2-regularised softmax regression: strongly
+convex, one optimum.  ``fit_exit_heads`` solves it per exit with L-BFGS in float64 on the device, and ``HeadFit.state_dict`` names the
+result the way ``EarlyExitEngine.load_weights`` expects it.
+
+For ``exit_head_num_layers = 2``, the reference's default (dense -> tanh -> out_proj, EE/models/LayoutLMv3.py:70-93),
+``fit_mlp_exit_heads`` runs the same L-BFGS on the two-layer objective from a stated start (``init="identity"``: the one-layer head on
+tanh(x)), and ``MlpHeadFit.state_dict`` names the four tensors per exit.  That objective is not convex: the fit returns a stationary
+point reached by descent from the start (``status`` 0: gradient norm <= gtol), reproducible bit for bit, not a unique optimum.
+
+This is not a trainer: gates, the LTE classifier, embedding-level exits, the final classifier, mini-batches and an unfrozen backbone are
+out of scope.
 
 Reloading heads into an engine that holds captured graphs does not re-capture them: capture again after ``load_weights``.
 """
@@ -25,24 +33,31 @@ from .engine import _require_torch_cuda, torch
 STATUS = {0: "converged", 1: "max_evals", 2: "line_search"}
 
 
-def _check_fittable(cfg: ModelConfig):
+def _check_fittable(cfg: ModelConfig, head_layers: int = 1):
     ec = cfg.exit_config
     if str(ec.encoder_layer_strategy) != "ramp":
         raise ValueError("exit heads are fitted for the ramp strategy only: a gate shows the policy the final classifier's logits, "
                          "there is no head to fit")
-    if ec.exit_head_num_layers != 1:
-        raise ValueError("exit heads are fitted for exit_head_num_layers == 1 only (a two-layer head is not a convex problem)")
+    if head_layers == 2:
+        if ec.exit_head_num_layers != 2:
+            raise ValueError("two-layer exit heads are fitted for exit_head_num_layers == 2 only (fit_exit_heads fits the one-layer head)")
+    elif head_layers != 1:
+        raise ValueError(f"head_layers = {head_layers}: the heads of the reference have one or two layers")
+    elif ec.exit_head_num_layers != 1:
+        raise ValueError("exit heads are fitted for exit_head_num_layers == 1 only (a two-layer head is not a convex problem: "
+                         "fit_mlp_exit_heads fits it, collect_exit_features(..., head_layers=2) gathers its rows)")
     if ec.embedding_exits:
         raise ValueError(f"embedding-level exits {ec.embedding_exits} cannot be fitted: the forward does not return their pooled inputs")
     if not ec.encoder_exit_layers:
         raise ValueError("the configuration has no encoder exits")
 
 
-def collect_exit_features(engine, batches: Iterable[Mapping]):
+def collect_exit_features(engine, batches: Iterable[Mapping], head_layers: int = 1):
     """Dump-all forwards of ``engine`` over ``batches`` (dicts of ``engine.forward`` keyword inputs: ``input_ids``, ``attention_mask``,
     ``bbox``, ``pixel_values``, ...; ``pixel_values`` alone for the image-only DiT handle).  Returns the device tensor (E,N,H) float32
-    of the CLS rows leaving the configured encoder exit layers -- the inputs of the heads ``encoder.early_exits.0 .. E-1``."""
-    _check_fittable(engine.cfg)
+    of the CLS rows leaving the configured encoder exit layers -- the inputs of the heads ``encoder.early_exits.0 .. E-1``.
+    ``head_layers`` states which heads the rows are for: 1 (``fit_exit_heads``) or 2 (``fit_mlp_exit_heads``); the configuration must agree."""
+    _check_fittable(engine.cfg, head_layers)
     layers = torch.tensor(engine.cfg.exit_config.encoder_exit_layers, dtype=torch.int64, device=engine.device)
     keys = ("input_ids", "attention_mask", "bbox", "pixel_values", "token_type_ids", "position_ids")
     rows = []
@@ -132,4 +147,126 @@ def fit_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-9, max_e
         capi.check(lib.ee_head_fit(p(X), p(y), E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), p(ws), need, p(fit.weight),
                                    p(fit.bias), p(fit.weight64), p(fit.bias64), p(fit.loss), p(fit.grad_norm), p(fit.evals), p(fit.status),
                                    stream), None, "ee_head_fit")
+    return fit
+
+
+# ---- two-layer heads: dense + tanh + out_proj -----------------------------------------------------------------------------------------
+_MLP_BLOCKS = ("dense.weight", "dense.bias", "out_proj.weight", "out_proj.bias")
+
+
+def mlp_param_count(H: int, K: int) -> int:
+    return H * H + H + K * H + K
+
+
+@dataclass
+class MlpHeadFit:
+    dense_weight: "torch.Tensor"  # (E,H,H) float32, device: W1 [out,in]
+    dense_bias: "torch.Tensor"    # (E,H)
+    weight: "torch.Tensor"        # (E,K,H): out_proj
+    bias: "torch.Tensor"          # (E,K)
+    theta64: "torch.Tensor"       # (E,P) float64: W1 row-major, b1, W2 row-major, b2 -- the point the float32 tensors are rounded from
+    loss: "torch.Tensor"          # (E,) float64: the objective at the returned point
+    grad_norm: "torch.Tensor"     # (E,) float64
+    evals: "torch.Tensor"         # (E,) int32
+    status: "torch.Tensor"        # (E,) int32: 0 stationary (grad_norm <= gtol), 1 max_evals, 2 the line search made no progress
+    l2: float
+
+    def logits(self, features) -> "torch.Tensor":
+        """(E,N,K) float64 logits of the float32 heads on ``features`` (E,N,H), on the device."""
+        f64 = torch.float64
+        X = _to_device(features, torch.float32, self.weight.device).to(f64)
+        if X.dim() == 2:
+            X = X.unsqueeze(0)
+        A = torch.tanh(torch.baddbmm(self.dense_bias.to(f64).unsqueeze(1), X, self.dense_weight.to(f64).transpose(1, 2)))
+        return torch.baddbmm(self.bias.to(f64).unsqueeze(1), A, self.weight.to(f64).transpose(1, 2))
+
+    def state_dict(self, cfg: ModelConfig) -> Dict[str, np.ndarray]:
+        """``{prefix}encoder.early_exits.{k}.dense.weight / .bias`` and ``.out_proj.weight / .bias`` (host float32), ready for
+        ``engine.load_weights`` next to the backbone's tensors."""
+        _check_fittable(cfg, 2)
+        E, K, H = self.weight.shape
+        if E != len(cfg.exit_config.encoder_exit_layers) or K != cfg.num_labels or H != cfg.hidden_size:
+            raise ValueError(f"the fit is (E,K,H) = {(E, K, H)}, the configuration wants "
+                             f"{(len(cfg.exit_config.encoder_exit_layers), cfg.num_labels, cfg.hidden_size)}")
+        p = "beit." if cfg.arch == "beit" else "layoutlmv3."
+        blocks = [t.cpu().numpy() for t in (self.dense_weight, self.dense_bias, self.weight, self.bias)]
+        out = {}
+        for k in range(E):
+            for name, a in zip(_MLP_BLOCKS, blocks):
+                out[f"{p}encoder.early_exits.{k}.{name}"] = np.ascontiguousarray(a[k])
+        return out
+
+
+def _mlp_theta0(init, E, H, K, dev):
+    """The start as a device tensor (E,P) float64."""
+    P = mlp_param_count(H, K)
+    if isinstance(init, str):
+        if init != "identity":
+            raise ValueError(f"init = {init!r}: 'identity', an (E,P) array or a mapping of head tensors")
+        th = torch.zeros((E, P), dtype=torch.float64, device=dev)
+        th[:, :H * H].view(E, H, H).diagonal(dim1=1, dim2=2).fill_(1.0)
+        return th
+    if isinstance(init, Mapping):
+        shapes = ((H, H), (H,), (K, H), (K,))
+        rows = []
+        for k in range(E):
+            parts = []
+            for name, shape in zip(_MLP_BLOCKS, shapes):
+                found = [v for key, v in init.items() if key.endswith(f"encoder.early_exits.{k}.{name}")]
+                if len(found) != 1:
+                    raise ValueError(f"init names {len(found)} tensors ending in encoder.early_exits.{k}.{name}, need one")
+                a = _to_device(found[0], torch.float64, dev)
+                if tuple(a.shape) != shape:
+                    raise ValueError(f"encoder.early_exits.{k}.{name} is {tuple(a.shape)}, need {shape}")
+                parts.append(a.reshape(-1))
+            rows.append(torch.cat(parts))
+        return torch.stack(rows).contiguous()
+    th = _to_device(init, torch.float64, dev)
+    if th.dim() == 1:
+        th = th.unsqueeze(0)
+    if tuple(th.shape) != (E, P):
+        raise ValueError(f"init is {tuple(th.shape)}, need (E,P) = {(E, P)}")
+    return th
+
+
+def fit_mlp_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-6, max_evals: int = 4000, history: int = 8, init="identity",
+                       device=None, num_labels: int = None) -> MlpHeadFit:
+    """Two-layer heads (dense + tanh + out_proj) per exit.  ``features`` (E,N,H) float32 (numpy or device tensor; (N,H) is one exit),
+    ``labels`` (N,) integers in [0,K) with K = ``num_labels`` (default: ``labels.max() + 1``).  Minimises, per exit, mean cross-entropy of
+    W2 tanh(W1 x + b1) + b2 plus (l2 / 2) ||theta||^2 over all four blocks, in float64 (include/mmee.h), by the L-BFGS of ``fit_exit_heads``.
+
+    ``init``: ``"identity"`` (W1 = I, everything else 0: the one-layer head on tanh(x); zero itself is a saddle the iteration never
+    leaves), an (E,P) array or tensor in the layout W1 row-major, b1, W2 row-major, b2, or a mapping holding, per exit k, the tensors
+    ``...encoder.early_exits.{k}.dense.weight / .dense.bias / .out_proj.weight / .out_proj.bias`` of a checkpoint (a warm start).
+
+    The objective is not convex.  ``status`` 0 says the gradient norm of the returned point is <= ``gtol``: a stationary point reached by
+    descent from ``init``.  Unit-variance features of a few hundred rows need 600 - 1800 evaluations to ``gtol = 1e-6``: hence the default
+    budget of 4000; a stopped exit costs nothing more.
+
+    Host synchronisation: as for ``fit_exit_heads``, one wait after the last launch (plus one for ``labels.max()`` without ``num_labels``)."""
+    lib = capi.load()
+    dev = features.device if (torch is not None and isinstance(features, torch.Tensor) and features.is_cuda and device is None) \
+        else _require_torch_cuda(device)
+    X = _to_device(features, torch.float32, dev)
+    if X.dim() == 2:
+        X = X.unsqueeze(0)
+    y = _to_device(labels, torch.int64, dev).view(-1)
+    E, N, H = X.shape
+    K = int(y.max()) + 1 if num_labels is None else int(num_labels)
+    if y.shape[0] != N:
+        raise ValueError("labels must have one entry per feature row")
+    theta0 = _mlp_theta0(init, E, H, K, dev)
+    P = mlp_param_count(H, K)
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+    fit = MlpHeadFit(z((E, H, H), torch.float32), z((E, H), torch.float32), z((E, K, H), torch.float32), z((E, K), torch.float32),
+                     z((E, P), torch.float64), z((E,), torch.float64), z((E,), torch.float64), z((E,), torch.int32),
+                     torch.full((E,), -1, dtype=torch.int32, device=dev), float(l2))
+    need = int(lib.ee_mlp_head_fit_workspace_bytes(E, N, H, K, history))
+    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        capi.check(lib.ee_mlp_head_fit(p(X), p(y), p(theta0), E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), p(ws), need,
+                                       p(fit.dense_weight), p(fit.dense_bias), p(fit.weight), p(fit.bias), p(fit.theta64), p(fit.loss),
+                                       p(fit.grad_norm), p(fit.evals), p(fit.status), stream), None, "ee_mlp_head_fit")
     return fit
