@@ -710,6 +710,58 @@ int ee_debug_mlp_head_lossgrad(const float* features, const int64_t* labels, con
                                double l2, double* loss, double* grad, void* stream);
 
 /*
+ * The learning-to-exit classifier (ee_config.use_lte) fitted on the device from the CLS rows of a frozen backbone.  The reference trains it
+ * inside EETrainer (EE/models/LayoutLMv3.py:795-857: lte_loss_fct = MSELoss against 1 - lte_gold, one MSE per exit, summed); here it is one
+ * deterministic batch problem.  ONE classifier theta = (w (H,), b) is shared by all encoder exits, as in the reference (init_lte: one
+ * nn.Linear(H, 1)).  With x_{e,n} the float32 CLS row leaving encoder exit e (out_hidden_cls), a = w . x + b, s = 1 / (1 + exp(-a)) and
+ * targets t_{e,n} in [0, 1] ("exit e is wrong on document n"):
+ *
+ *     L(theta) = sum_e (1/N) sum_n l(a_{e,n}, t_{e,n}) + (l2 / 2) (||w||^2 + b^2)
+ *     MMEE_LTE_LOSS_MSE = 0:  l = (s - t)^2                               dl/da = 2 (s - t) s (1 - s)
+ *     MMEE_LTE_LOSS_BCE = 1:  l = max(a, 0) + log1p(exp(-|a|)) - t a      dl/da = s - t
+ *
+ * MSE is the reference's loss.  It is not convex: status 0 promises a stationary point reached by descent from the start, not a unique
+ * optimum.  BCE is the convex alternative: l2-strongly convex, one optimum.  All arithmetic is float64 on the float32 rows (widening is exact);
+ * the softplus of BCE is shifted, so |a| of several hundred is finite.  l2 <= 0 (and NaN) is refused.  The bias is penalised, as in ee_head_fit.
+ * Deviation from the reference, deliberate: an exit at the last layer is not special-cased (the reference substitutes the final logits there);
+ * its rows and targets enter like any other exit's.  Per-exit loss weights, embedding-level exits, BEiT handles and an unfrozen backbone are out
+ * of scope; so are gates (under the gate strategy the policy reads classifier(gate input): the 2-logit gate head decides nothing here).
+ *
+ * ee_lte_fit: the L-BFGS of ee_head_fit -- the same controller kernel on one vector of H + 1 parameters: Armijo test with c1 = 1e-4 and the
+ *   8 eps |L| allowance, halving, first step 1 / ||g||, a pair with s.y <= 0 skipped -- from theta0, dev (H + 1,) float64: w then b; NULL = 0.
+ *   A fixed launch list of max_evals ticks of [loss / gradient, reduce, controller], no host round trip between them; once stopped, the
+ *   remaining workgroups return at once.  Stopping rules and status codes are ee_head_fit's: 0 when ||grad L||_2 <= gtol, 1 after max_evals
+ *   evaluations, 2 after 30 halvings without progress.  features dev (E,N,H) float32, 16-byte aligned, H % 4 == 0, 4 <= H <= 1024; targets dev
+ *   (E,N) float64; 1 <= E <= 64; 1 <= history <= 32; workspace dev of ee_lte_fit_workspace_bytes(E,N,H,history) bytes.  Outputs dev: weight
+ *   (1,H), bias (1,) float32 -- the tensors layoutlmv3.encoder.lte_classifier.weight / .bias; optional theta64 (H + 1,), the float64 point
+ *   they are rounded from; optional loss_out, grad_norm (of the returned point), evals, status (one element each).
+ *   A target outside [0, 1] or NaN fails the call with no output written; the call learns of it by the one wait after the last launch.
+ *   One evaluation reads every feature row from HBM once: a wave holds a row in registers (lane l: columns 4l + 256k + j, the order of the
+ *   forward's score) between its dot product and its contribution dl/da * x to the gradient.  No floating-point atomics: a workgroup adds
+ *   its waves in LDS in wave order and writes one partial (dw, db, loss) per row chunk; the chunking is a function of N alone; the partials
+ *   are added in chunk order, the exits in ascending order, then the penalty.  Two calls return the same bits.
+ * ee_debug_lte_lossgrad: ONE evaluation of L and grad L (the launches a tick makes) at theta64 dev (H + 1,); loss_out dev one double, grad dev
+ *   (H + 1,).  A bad target fails the call.
+ * ee_lte_targets: from the policy logits dev float32 (E,N,K) (out_all_logits of the encoder exits) and labels dev int64 (N,):
+ *   targets[e,n] = 1 - [argmax_k logits[e,n,k] == labels[n]], the first maximum winning, dev float64 (E,N).  A label outside [0,K) or a NaN
+ *   logit (a row its document never reached) fails the call with nothing written.  Waits for the stream once.
+ * ee_lte_scores: scores[e,n] = 1 / (1 + exp(-(w . x_{e,n} + b))) dev float64 (E,N) from a float32 weight (1,H) (16-byte aligned) and bias (1,):
+ *   the expression and summation order of ee_config.use_lte, unrounded -- the rows sweep.lte_sweep and ee_lte_scan take.
+ * MMEE_LTE_FIT_ROWS: the rows a workgroup of the loss / gradient kernel treats as a unit (four waves, four rows in flight each).
+ */
+#define MMEE_LTE_LOSS_MSE 0
+#define MMEE_LTE_LOSS_BCE 1
+#define MMEE_LTE_FIT_ROWS 16
+int ee_lte_fit(const float* features, const double* targets, const double* theta0, int32_t E, int32_t N, int32_t H, int32_t loss, double l2,
+               double gtol, int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* weight, float* bias,
+               double* theta64, double* loss_out, double* grad_norm, int32_t* evals, int32_t* status, void* stream);
+size_t ee_lte_fit_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t history);
+int ee_debug_lte_lossgrad(const float* features, const double* targets, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t loss,
+                          double l2, double* loss_out, double* grad, void* stream);
+int ee_lte_targets(const float* logits, const int64_t* labels, int32_t E, int32_t N, int32_t K, double* targets, void* stream);
+int ee_lte_scores(const float* features, const float* weight, const float* bias, int32_t E, int32_t N, int32_t H, double* scores, void* stream);
+
+/*
  * Device-side input feed (replaces the host image processor + collator in front of the model, EE/data/RVL_CDIP.py:246-262
  * and EE/utils.py:93-98, 173).
  *

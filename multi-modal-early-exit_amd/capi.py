@@ -32,6 +32,8 @@ CLOCK_STAMP_WORDS = 4096       # MMEE_CLOCK_STAMP_WORDS
 ATTN_KERNEL_F32, ATTN_KERNEL_PAIR, ATTN_KERNEL_IDX, ATTN_KERNEL_IDX_NOBIAS = 0, 1, 2, 3
 HEAD_FIT_SLAB = 32             # MMEE_HEAD_FIT_SLAB
 MLP_HEAD_FIT_ROWS = 64         # MMEE_MLP_HEAD_FIT_ROWS
+LTE_FIT_ROWS = 16              # MMEE_LTE_FIT_ROWS
+LTE_LOSS_MSE, LTE_LOSS_BCE = 0, 1
 
 _LIB_NAME = "libmmee_hip.so"
 _LIB_PATH = os.environ.get("MMEE_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), _LIB_NAME)
@@ -148,6 +150,12 @@ SYMBOLS = {
                                   _vp, _vp, _vp, _vp, _vp, _vp]),
     "ee_mlp_head_fit_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, _i32]),
     "ee_debug_mlp_head_lossgrad": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp]),
+    "ee_lte_fit": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _vp, _vp]),
+    "ee_lte_fit_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32]),
+    "ee_debug_lte_lossgrad": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp]),
+    "ee_lte_targets": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "ee_lte_scores": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "ee_preprocess_images": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp]),
     "ee_preprocess_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32]),
     "ee_collate_pad": (C.c_int, [_vp, _vp, _vp, _i32, _i32, C.c_int64, _vp, _vp, _vp, _vp]),

@@ -358,6 +358,35 @@ bool launch_mlp_head_fit(const MlpHeadFitArgs& a, hipStream_t s);
 // one evaluation at theta (E,P): loss (E,), grad (E,P); scratch: mlp_head_fit_scratch_doubles doubles; err: one zeroed int
 void launch_mlp_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* scratch,
                               int* err, double* loss, double* grad, hipStream_t s);
+// ee_lte_fit (lte_fit.hip): the learning-to-exit classifier, one Linear(H, 1) for all encoder exits; theta = w (H,), b
+constexpr int kLteFitRows = 16;              // the rows a workgroup treats as a unit: four waves, four rows in flight each (MMEE_LTE_FIT_ROWS)
+constexpr int kLteFitMaxChunks = 128;        // row chunks (= partial gradients) per exit
+constexpr int kLteFitMaxExits = 64;          // the reduce kernel keeps one sum per exit in LDS
+enum { kLteLossMse = 0, kLteLossBce = 1 };   // MMEE_LTE_LOSS_*
+struct LteFitArgs {
+    const float* features;           // (E,N,H)
+    const double* targets;           // (E,N) in [0,1]
+    const double* theta0;            // (H + 1,) or null: the start (null = 0)
+    int E, N, H, loss_kind;
+    double l2, gtol;
+    int max_evals, history;
+    void* workspace;                 // lte_fit_workspace_bytes
+    float *weight, *bias;            // (1,H), (1,)
+    double* theta64;                 // (H + 1,) or null
+    double *loss, *grad_norm;        // one double each, or null
+    int *evals, *status;             // one int each, or null
+};
+int lte_fit_chunks(int N);
+size_t lte_fit_workspace_bytes(int E, int N, int H, int history);
+size_t lte_fit_partial_doubles(int E, int N, int H);
+// false: preparing the workspace failed.  The error word is the first int of the workspace (bit 0: a target outside [0,1] or NaN).
+bool launch_lte_fit(const LteFitArgs& a, hipStream_t s);
+// one evaluation at theta (H + 1,): loss_out one double, grad (H + 1,); partial: lte_fit_partial_doubles doubles; err: one zeroed int
+void launch_lte_lossgrad(const float* X, const double* T, const double* theta, int E, int N, int H, int loss, double l2, double* partial, int* err,
+                         double* loss_out, double* grad, hipStream_t s);
+// targets (E,N) = 1 - [argmax(logits (E,N,K)) == y]; err: one zeroed int, bit 0 = a label outside [0,K) or a NaN logit (then nothing is written)
+void launch_lte_targets(const float* logits, const long long* y, int E, int N, int K, double* targets, int* err, hipStream_t s);
+void launch_lte_scores(const float* X, const float* wgt, const float* bias, int E, int N, int H, double* scores, hipStream_t s);
 void launch_build_value_tables(const float* w1, const float* wx, const float* wy, const unsigned char* lut1,
                                const unsigned char* lut2, int heads, int bins1, int bins2, int n1, int n2, float inv_sqrt_d,
                                float* t1, float* tx, float* ty, hipStream_t s);

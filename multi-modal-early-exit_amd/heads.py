@@ -13,8 +13,14 @@ For ``exit_head_num_layers = 2``, the reference's default (dense -> tanh -> out_
 tanh(x)), and ``MlpHeadFit.state_dict`` names the four tensors per exit.  That objective is not convex: the fit returns a stationary
 point reached by descent from the start (``status`` 0: gradient norm <= gtol), reproducible bit for bit, not a unique optimum.
 
-This is not a trainer: gates, the LTE classifier, embedding-level exits, the final classifier, mini-batches and an unfrozen backbone are
-out of scope.
+The learning-to-exit classifier (``use_lte``: ONE ``nn.Linear(H, 1)`` + sigmoid shared by every encoder exit, scored on the CLS row leaving
+the exit's layer) is fitted from the same dump-all forwards (``ee_lte_fit``): ``collect_lte_features`` gathers the CLS rows and the exits'
+policy logits, ``lte_targets`` turns logits and labels into the targets "this exit is wrong here", ``fit_lte_classifier`` minimises the
+reference's summed per-exit MSE (or the convex BCE) and ``LteFit.state_dict`` names ``encoder.lte_classifier.weight / .bias``.  The MSE
+objective is not convex: ``status`` 0 is a stationary point reached by descent from the start.
+
+This is not a trainer: gates, embedding-level exits, the final classifier, per-exit LTE loss weights, mini-batches and an unfrozen backbone
+are out of scope.
 
 Reloading heads into an engine that holds captured graphs does not re-capture them: capture again after ``load_weights``.
 """
@@ -31,6 +37,7 @@ from .config import ModelConfig
 from .engine import _require_torch_cuda, torch
 
 STATUS = {0: "converged", 1: "max_evals", 2: "line_search"}
+LTE_MAX_EVALS = 1000           # fit_lte_classifier's default budget; its docstring says where it comes from
 
 
 def _check_fittable(cfg: ModelConfig, head_layers: int = 1):
@@ -269,4 +276,166 @@ def fit_mlp_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-6, m
         capi.check(lib.ee_mlp_head_fit(p(X), p(y), p(theta0), E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), p(ws), need,
                                        p(fit.dense_weight), p(fit.dense_bias), p(fit.weight), p(fit.bias), p(fit.theta64), p(fit.loss),
                                        p(fit.grad_norm), p(fit.evals), p(fit.status), stream), None, "ee_mlp_head_fit")
+    return fit
+
+
+# ---- the learning-to-exit classifier: one Linear(H, 1) for all encoder exits ---------------------------------------------------------------------
+LTE_LOSSES = {"mse": capi.LTE_LOSS_MSE, "bce": capi.LTE_LOSS_BCE}
+_LTE_W, _LTE_B = "encoder.lte_classifier.weight", "encoder.lte_classifier.bias"
+
+
+def _check_lte_cfg(cfg: ModelConfig):
+    if cfg.arch == "beit":
+        raise ValueError("the LTE classifier is fitted for LayoutLMv3 configurations only: use_lte is refused on BEiT / DiT handles")
+    if not cfg.exit_config.encoder_exit_layers:
+        raise ValueError("the configuration has no encoder exits: the LTE classifier scores the CLS rows leaving encoder exit layers")
+
+
+def collect_lte_features(engine, batches: Iterable[Mapping]):
+    """Dump-all forwards of ``engine`` over ``batches`` (dicts of ``engine.forward`` keyword inputs).  Returns two device tensors from the
+    same forwards: ``features`` (E,N,H) float32, the CLS rows leaving the E configured encoder exit layers, and ``logits`` (E,N,K) float32,
+    those exits' policy logits (``all_logits``: ramps the head's logits, gates ``classifier(gate input)``).  Any LayoutLMv3 engine with an
+    encoder exit will do -- ramp or gate, 1- or 2-layer heads, with or without ``use_lte``; embedding-level exits are skipped."""
+    _check_lte_cfg(engine.cfg)
+    ec = engine.cfg.exit_config
+    n_emb, n_enc = len(ec.embedding_exits), len(ec.encoder_exit_layers)
+    layers = torch.tensor(ec.encoder_exit_layers, dtype=torch.int64, device=engine.device)
+    keys = ("input_ids", "attention_mask", "bbox", "pixel_values", "token_type_ids", "position_ids")
+    rows, logits = [], []
+    for b in batches:
+        out = engine.forward(**{k: b[k] for k in keys if k in b and b[k] is not None}, dump_all=True, want_all=True, want_hidden_cls=True)
+        rows.append(out.hidden_cls.index_select(0, layers))
+        logits.append(out.all_logits[n_emb:n_emb + n_enc].to(torch.float32))
+    if not rows:
+        raise ValueError("no batches")
+    return torch.cat(rows, dim=1).contiguous(), torch.cat(logits, dim=1).contiguous()
+
+
+def lte_targets(logits, labels, device=None) -> "torch.Tensor":
+    """(E,N) float64 device tensor: 1 where the argmax (first maximum) of ``logits`` (E,N,K) float32 differs from ``labels`` (N,), else 0 --
+    the reference's ``1 - lte_gold``.  A label outside [0,K) or a NaN logit (a row its document never reached) fails the call."""
+    lib = capi.load()
+    dev = logits.device if (torch is not None and isinstance(logits, torch.Tensor) and logits.is_cuda and device is None) \
+        else _require_torch_cuda(device)
+    Z = _to_device(logits, torch.float32, dev)
+    if Z.dim() == 2:
+        Z = Z.unsqueeze(0)
+    y = _to_device(labels, torch.int64, dev).view(-1)
+    E, N, K = Z.shape
+    if y.shape[0] != N:
+        raise ValueError("labels must have one entry per document")
+    out = torch.zeros((E, N), dtype=torch.float64, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        capi.check(lib.ee_lte_targets(p(Z), p(y), E, N, K, p(out), stream), None, "ee_lte_targets")
+    return out
+
+
+@dataclass
+class LteFit:
+    weight: "torch.Tensor"       # (1,H) float32, device
+    bias: "torch.Tensor"         # (1,)  float32
+    theta64: "torch.Tensor"      # (H+1,) float64: w then b, the point the float32 pair is rounded from
+    loss: "torch.Tensor"         # (1,) float64: the objective at the returned point
+    grad_norm: "torch.Tensor"    # (1,) float64
+    evals: "torch.Tensor"        # (1,) int32
+    status: "torch.Tensor"       # (1,) int32: 0 stationary (grad_norm <= gtol), 1 max_evals, 2 the line search made no progress
+    l2: float
+    loss_kind: str
+
+    def scores(self, features) -> "torch.Tensor":
+        """(E,N) float64 scores sigmoid(w . x + b) of the float32 classifier on ``features`` (E,N,H), on the device, in the forward's
+        summation order: the rows ``sweep.lte_sweep`` and ``lte_scan_device`` take."""
+        lib = capi.load()
+        dev = self.weight.device
+        X = _to_device(features, torch.float32, dev)
+        if X.dim() == 2:
+            X = X.unsqueeze(0)
+        E, N, H = X.shape
+        if H != self.weight.shape[1]:
+            raise ValueError(f"features have H = {H}, the classifier {self.weight.shape[1]}")
+        out = torch.empty((E, N), dtype=torch.float64, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            capi.check(lib.ee_lte_scores(p(X), p(self.weight), p(self.bias), E, N, H, p(out), stream), None, "ee_lte_scores")
+        return out
+
+    def state_dict(self, cfg: ModelConfig) -> Dict[str, np.ndarray]:
+        """``layoutlmv3.encoder.lte_classifier.weight`` (1,H) and ``.bias`` (1,) (host float32), ready for ``engine.load_weights`` of a
+        ``use_lte`` engine next to the other tensors."""
+        _check_lte_cfg(cfg)
+        if tuple(self.weight.shape) != (1, cfg.hidden_size):
+            raise ValueError(f"the fit has weight {tuple(self.weight.shape)}, the configuration wants {(1, cfg.hidden_size)}")
+        return {f"layoutlmv3.{_LTE_W}": np.ascontiguousarray(self.weight.cpu().numpy()).reshape(1, -1),
+                f"layoutlmv3.{_LTE_B}": np.ascontiguousarray(self.bias.cpu().numpy()).reshape(1)}
+
+
+def _lte_theta0(init, H):
+    """The start as a host (H+1,) float64 array, or None for zero."""
+    if init is None:
+        return None
+    if isinstance(init, Mapping):
+        parts = []
+        for name, shape in ((_LTE_W, (1, H)), (_LTE_B, (1,))):
+            found = [v for key, v in init.items() if key.endswith(name)]
+            if len(found) != 1:
+                raise ValueError(f"init names {len(found)} tensors ending in {name}, need one")
+            a = found[0].detach().cpu().numpy() if (torch is not None and isinstance(found[0], torch.Tensor)) else np.asarray(found[0])
+            if tuple(a.shape) != shape:
+                raise ValueError(f"{name} is {tuple(a.shape)}, need {shape}")
+            parts.append(a.astype(np.float64).reshape(-1))
+        return np.concatenate(parts)
+    a = init.detach().cpu().numpy() if (torch is not None and isinstance(init, torch.Tensor)) else np.asarray(init)
+    if tuple(a.shape) != (H + 1,):
+        raise ValueError(f"init is {tuple(a.shape)}, need (H+1,) = {(H + 1,)}: w then b")
+    return a.astype(np.float64)
+
+
+def fit_lte_classifier(features, targets, loss: str = "mse", l2: float = 1e-2, gtol: float = 1e-9, max_evals: int = LTE_MAX_EVALS,
+                       history: int = 8, init=None, device=None) -> LteFit:
+    """``features`` (E,N,H) float32 (numpy or device tensor; (N,H) is one exit), ``targets`` (E,N) in [0,1] (``lte_targets``; soft targets
+    are allowed).  Minimises sum_e mean_n l(w . x + b, t) + (l2 / 2)(||w||^2 + b^2) over ONE (w, b) in float64 (include/mmee.h), by the
+    L-BFGS of ``fit_exit_heads``.  ``loss="mse"`` is the reference's (sigmoid + MSE per exit, summed; not convex: ``status`` 0 is a stationary
+    point reached by descent from ``init``); ``loss="bce"`` is the strongly convex alternative with one optimum.
+
+    ``init``: ``None`` (zero), an (H+1,) array (w then b), or a mapping holding ``...encoder.lte_classifier.weight`` (1,H) and ``.bias`` (1,)
+    of a checkpoint (a warm start).
+
+    ``status`` says how the fit stopped.  Evaluations to ``gtol = 1e-9`` as tests/test_gpu_lte_fit.py prints them: unit-variance features
+    19 - 72 (MSE 22 / 40 / 32 / 55 / 72, BCE 19 / 34 / 25 / 56 / 72 on its five problems), the CLS rows of the synthetic backbones, which share a
+    large common component, 130 (H = 128) and 283 (H = 256, split precision); 40 000 well-conditioned rows an exit need 12 - 13.  Hence the
+    default budget of 1000, 3.5 times the largest count seen (the C entry point has no default).  The launch list is fixed, so every unused tick
+    still costs its three empty launches (about 9 microseconds): raise ``max_evals`` when ``status`` is 1, lower it when the call's latency matters.
+
+    Host synchronisation: one wait after the last launch, to read the error word (a target outside [0,1] or NaN fails the call)."""
+    if loss not in LTE_LOSSES:
+        raise ValueError(f"loss = {loss!r}: 'mse' (the reference's) or 'bce'")
+    H_in = int(features.shape[-1])
+    theta0 = _lte_theta0(init, H_in)
+    lib = capi.load()
+    dev = features.device if (torch is not None and isinstance(features, torch.Tensor) and features.is_cuda and device is None) \
+        else _require_torch_cuda(device)
+    X = _to_device(features, torch.float32, dev)
+    if X.dim() == 2:
+        X = X.unsqueeze(0)
+    E, N, H = X.shape
+    T = _to_device(targets, torch.float64, dev)
+    if T.dim() == 1:
+        T = T.unsqueeze(0)
+    if tuple(T.shape) != (E, N):
+        raise ValueError(f"targets are {tuple(targets.shape)}, need (E,N) = {(E, N)}")
+    th0 = None if theta0 is None else _to_device(theta0, torch.float64, dev)
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+    fit = LteFit(z((1, H), torch.float32), z((1,), torch.float32), z((H + 1,), torch.float64), z((1,), torch.float64), z((1,), torch.float64),
+                 z((1,), torch.int32), torch.full((1,), -1, dtype=torch.int32, device=dev), float(l2), loss)
+    need = int(lib.ee_lte_fit_workspace_bytes(E, N, H, history))
+    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        capi.check(lib.ee_lte_fit(p(X), p(T), p(th0), E, N, H, LTE_LOSSES[loss], float(l2), float(gtol), int(max_evals), int(history), p(ws),
+                                  need, p(fit.weight), p(fit.bias), p(fit.theta64), p(fit.loss), p(fit.grad_norm), p(fit.evals), p(fit.status),
+                                  stream), None, "ee_lte_fit")
     return fit
