@@ -1,0 +1,211 @@
+// Entry points of the device fits, none of which sees a handle: one-layer and two-layer exit heads (ee_head_fit, ee_mlp_head_fit) and the
+// learning-to-exit classifier (ee_lte_fit, with ee_lte_targets and ee_lte_scores) from dumped CLS rows, their workspace queries, and the
+// ee_debug_*_lossgrad hooks that run one evaluation of an objective on caller-provided buffers.  The L-BFGS is fit_lbfgs.hip.
+#include "capi_internal.h"
+
+using namespace mmee;
+using namespace mmee::capi;
+
+static_assert(kHeadFitSlab == MMEE_HEAD_FIT_SLAB, "the kernel's slab height is the ABI's");
+static_assert(kMlpHeadFitRows == MMEE_MLP_HEAD_FIT_ROWS, "the kernels' row tile is the ABI's");
+static_assert(kLteFitRows == MMEE_LTE_FIT_ROWS, "the kernel's unit of rows is the ABI's");
+static_assert(kLteLossMse == MMEE_LTE_LOSS_MSE && kLteLossBce == MMEE_LTE_LOSS_BCE, "the loss codes are the ABI's");
+
+// ---- what the fits share -----------------------------------------------------------------------------------------------------------------
+// the refusals of a fit's budget, in this order, behind those of its problem; need_bytes() is only asked about a valid history
+template <typename Need>
+static int budget_refuse(const char* who, double gtol, int32_t max_evals, int32_t history, size_t workspace_bytes, Need need_bytes) {
+    if (!(gtol >= 0.0)) return fail(nullptr, "%s: gtol = %g, need gtol >= 0", who, gtol);
+    if (max_evals < 1) return fail(nullptr, "%s: max_evals = %d, need max_evals >= 1", who, max_evals);
+    if (history < 1 || history > kHeadFitMaxHistory) return fail(nullptr, "%s: history = %d, need 1 <= history <= %d", who, history, kHeadFitMaxHistory);
+    const size_t need = need_bytes();
+    if (workspace_bytes < need) return fail(nullptr, "%s: workspace of %zu bytes, needs %zu bytes", who, workspace_bytes, need);
+    return 0;
+}
+
+// The tail of a call that left an error word on the device: the launch status, the word read on the stream, one synchronise.  bad: the
+// message for bit 0 (bad input), a format of (who, K).
+static int finish_call(const char* who, bool prepared, const void* err_word, hipStream_t s, const char* bad, int K) {
+    if (!prepared) return fail(nullptr, "%s: preparing the workspace (memset, copy of theta0) failed", who);
+    if (launch_status(nullptr, who)) return 1;
+    int err = 0;
+    if (hipMemcpyAsync(&err, err_word, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return fail(nullptr, "%s: reading the error word failed: %s", who, hipGetErrorString(hipGetLastError()));
+    if (err & 1) return fail(nullptr, bad, who, K);
+    return 0;
+}
+
+// One evaluation of an objective for a debug entry point: launch(scratch, err) gets n zeroed doubles and a zeroed error word.  bad: as above.
+template <typename Launch>
+static int debug_lossgrad(const char* who, size_t n, hipStream_t s, Launch launch, const char* bad, int K) {
+    if (!have_device(who)) return 1;
+    Scratch sc;
+    double* scratch = nullptr;
+    int* err_dev = nullptr;
+    if (!sc.get(&scratch, n) || !sc.get(&err_dev, 1)) return fail(nullptr, "%s: hipMalloc of the scratch failed", who);
+    launch(scratch, err_dev);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(nullptr, "%s: launch failed: %s", who, hipGetErrorString(e));
+    int err = 0;
+    if (hipMemcpy(&err, err_dev, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of the error word failed", who);
+    if (launch_status(nullptr, who)) return 1;
+    if (err & 1) return fail(nullptr, bad, who, K);
+    return 0;
+}
+
+// the refusals the head fits and their debug hooks share, before any device call
+static int head_fit_refuse(const char* who, const float* features, int32_t E, int32_t N, int32_t H, int32_t K, double l2) {
+    if (E < 1 || E > 65535) return fail(nullptr, "%s: E = %d, need 1 <= E <= 65535", who, E);
+    if (N < 1) return fail(nullptr, "%s: N = %d, need N >= 1", who, N);
+    if (K < 2 || K > 64) return fail(nullptr, "%s: K = %d, need 2 <= K <= 64 (ee_create's limit)", who, K);
+    if (H < 4 || H > kHeadFitMaxH || H % 4 != 0)
+        return fail(nullptr, "%s: H = %d, need 4 <= H <= %d and H %% 4 == 0 (a slab of %d rows stays in LDS)", who, H, kHeadFitMaxH, kHeadFitSlab);
+    if (!(l2 > 0.0)) return fail(nullptr, "%s: l2 = %g, need l2 > 0 (the objective is strongly convex only then)", who, l2);
+    if (reinterpret_cast<uintptr_t>(features) % 16 != 0) return fail(nullptr, "%s: features must be 16-byte aligned", who);
+    return 0;
+}
+// the refusals of the LTE entry points that read feature rows, before any device call
+static int lte_rows_refuse(const char* who, const float* features, int32_t E, int32_t N, int32_t H) {
+    if (E < 1 || E > kLteFitMaxExits) return fail(nullptr, "%s: E = %d, need 1 <= E <= %d", who, E, kLteFitMaxExits);
+    if (N < 1) return fail(nullptr, "%s: N = %d, need N >= 1", who, N);
+    if (H < 4 || H > kHeadFitMaxH || H % 4 != 0) return fail(nullptr, "%s: H = %d, need 4 <= H <= %d and H %% 4 == 0", who, H, kHeadFitMaxH);
+    if (reinterpret_cast<uintptr_t>(features) % 16 != 0) return fail(nullptr, "%s: features must be 16-byte aligned", who);
+    return 0;
+}
+static int lte_objective_refuse(const char* who, int32_t loss, double l2) {
+    if (loss != MMEE_LTE_LOSS_MSE && loss != MMEE_LTE_LOSS_BCE)
+        return fail(nullptr, "%s: loss = %d, need MMEE_LTE_LOSS_MSE (0) or MMEE_LTE_LOSS_BCE (1)", who, loss);
+    if (!(l2 > 0.0)) return fail(nullptr, "%s: l2 = %g, need l2 > 0", who, l2);
+    return 0;
+}
+
+static const char* const kBadLabelFit = "%s: a label is outside [0, K = %d); no output was written";
+static const char* const kBadLabel = "%s: a label is outside [0, K = %d)";
+
+extern "C" {
+
+// ---- exit heads from CLS rows (head_fit.hip) ---------------------------------------------------------------------------------------------
+size_t ee_head_fit_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history) {
+    if (E < 1 || N < 1 || H < 1 || K < 1 || history < 1) return 0;
+    return head_fit_workspace_bytes(E, N, H, K, history);
+}
+
+int ee_head_fit(const float* features, const int64_t* labels, int32_t E, int32_t N, int32_t H, int32_t K, double l2, double gtol,
+                int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* weight, float* bias, double* weight64,
+                double* bias64, double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
+    const char* who = "ee_head_fit";
+    if (!features || !labels || !workspace || !weight || !bias)
+        return fail(nullptr, "%s: NULL argument (features, labels, workspace, weight and bias are required)", who);
+    if (head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
+    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return head_fit_workspace_bytes(E, N, H, K, history); })) return 1;
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const HeadFitArgs a{{features, E, N, H, l2, gtol, max_evals, history, workspace, nullptr, nullptr, loss, grad_norm, evals, status},
+                        reinterpret_cast<const long long*>(labels), K, weight, bias, weight64, bias64};
+    return finish_call(who, launch_head_fit(a, s), workspace, s, kBadLabelFit, K);
+}
+
+int ee_debug_head_lossgrad(const float* features, const int64_t* labels, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K,
+                           double l2, double* loss, double* grad, void* stream) {
+    const char* who = "ee_debug_head_lossgrad";
+    if (!features || !labels || !theta64 || !loss || !grad) return fail(nullptr, "%s: NULL argument", who);
+    if (head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return debug_lossgrad(who, head_fit_partial_bytes(E, N, H, K) / sizeof(double), s, [&](double* partial, int* err) {
+        launch_head_lossgrad(features, reinterpret_cast<const long long*>(labels), theta64, E, N, H, K, l2, partial, err, loss, grad, s);
+    }, kBadLabel, K);
+}
+
+// ---- two-layer exit heads from CLS rows (mlp_head_fit.hip) -------------------------------------------------------------------------------
+size_t ee_mlp_head_fit_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history) {
+    if (E < 1 || N < 1 || H < 1 || K < 1 || history < 1) return 0;
+    return mlp_head_fit_workspace_bytes(E, N, H, K, history);
+}
+
+int ee_mlp_head_fit(const float* features, const int64_t* labels, const double* theta0, int32_t E, int32_t N, int32_t H, int32_t K, double l2,
+                    double gtol, int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* dense_weight,
+                    float* dense_bias, float* weight, float* bias, double* theta64, double* loss, double* grad_norm, int32_t* evals,
+                    int32_t* status, void* stream) {
+    const char* who = "ee_mlp_head_fit";
+    if (!features || !labels || !theta0 || !workspace || !dense_weight || !dense_bias || !weight || !bias)
+        return fail(nullptr, "%s: NULL argument (features, labels, theta0, workspace, dense_weight, dense_bias, weight and bias are required; "
+                             "theta = 0 is a saddle the iteration never leaves, so there is no default start)", who);
+    if (head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
+    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return mlp_head_fit_workspace_bytes(E, N, H, K, history); })) return 1;
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const MlpHeadFitArgs a{{features, E, N, H, l2, gtol, max_evals, history, workspace, theta0, theta64, loss, grad_norm, evals, status},
+                           reinterpret_cast<const long long*>(labels), K, dense_weight, dense_bias, weight, bias};
+    return finish_call(who, launch_mlp_head_fit(a, s), workspace, s, kBadLabelFit, K);
+}
+
+int ee_debug_mlp_head_lossgrad(const float* features, const int64_t* labels, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K,
+                               double l2, double* loss, double* grad, void* stream) {
+    const char* who = "ee_debug_mlp_head_lossgrad";
+    if (!features || !labels || !theta64 || !loss || !grad) return fail(nullptr, "%s: NULL argument", who);
+    if (head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return debug_lossgrad(who, mlp_head_fit_scratch_doubles(E, N, H, K), s, [&](double* scratch, int* err) {
+        launch_mlp_head_lossgrad(features, reinterpret_cast<const long long*>(labels), theta64, E, N, H, K, l2, scratch, err, loss, grad, s);
+    }, kBadLabel, K);
+}
+
+// ---- the LTE classifier from CLS rows (lte_fit.hip) --------------------------------------------------------------------------------------
+size_t ee_lte_fit_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t history) {
+    if (E < 1 || N < 1 || H < 1 || history < 1) return 0;
+    return lte_fit_workspace_bytes(E, N, H, history);
+}
+
+int ee_lte_fit(const float* features, const double* targets, const double* theta0, int32_t E, int32_t N, int32_t H, int32_t loss, double l2,
+               double gtol, int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* weight, float* bias,
+               double* theta64, double* loss_out, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
+    const char* who = "ee_lte_fit";
+    if (!features || !targets || !workspace || !weight || !bias)
+        return fail(nullptr, "%s: NULL argument (features, targets, workspace, weight and bias are required)", who);
+    if (lte_rows_refuse(who, features, E, N, H) || lte_objective_refuse(who, loss, l2)) return 1;
+    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return lte_fit_workspace_bytes(E, N, H, history); })) return 1;
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const LteFitArgs a{{features, E, N, H, l2, gtol, max_evals, history, workspace, theta0, theta64, loss_out, grad_norm, evals, status},
+                       targets, loss, weight, bias};
+    return finish_call(who, launch_lte_fit(a, s), workspace, s, "%s: a target is outside [0, 1] or NaN; no output was written", 0);
+}
+
+int ee_debug_lte_lossgrad(const float* features, const double* targets, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t loss,
+                          double l2, double* loss_out, double* grad, void* stream) {
+    const char* who = "ee_debug_lte_lossgrad";
+    if (!features || !targets || !theta64 || !loss_out || !grad) return fail(nullptr, "%s: NULL argument", who);
+    if (lte_rows_refuse(who, features, E, N, H) || lte_objective_refuse(who, loss, l2)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return debug_lossgrad(who, lte_fit_partial_doubles(E, N, H), s, [&](double* partial, int* err) {
+        launch_lte_lossgrad(features, targets, theta64, E, N, H, loss, l2, partial, err, loss_out, grad, s);
+    }, "%s: a target is outside [0, 1] or NaN", 0);
+}
+
+int ee_lte_targets(const float* logits, const int64_t* labels, int32_t E, int32_t N, int32_t K, double* targets, void* stream) {
+    const char* who = "ee_lte_targets";
+    if (!logits || !labels || !targets) return fail(nullptr, "%s: NULL argument", who);
+    if (E < 1 || N < 1 || K < 1) return fail(nullptr, "%s: (E, N, K) = (%d, %d, %d), need each >= 1", who, E, N, K);
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    Scratch sc;
+    int* err_dev = nullptr;
+    if (!sc.get(&err_dev, 1)) return fail(nullptr, "%s: hipMalloc of the error word failed", who);
+    launch_lte_targets(logits, reinterpret_cast<const long long*>(labels), E, N, K, targets, err_dev, s);
+    return finish_call(who, true, err_dev, s,
+                       "%s: a label is outside [0, K = %d) or a logit is NaN (a row its document never reached); nothing was written", K);
+}
+
+int ee_lte_scores(const float* features, const float* weight, const float* bias, int32_t E, int32_t N, int32_t H, double* scores, void* stream) {
+    const char* who = "ee_lte_scores";
+    if (!features || !weight || !bias || !scores) return fail(nullptr, "%s: NULL argument", who);
+    if ((long long)E * N < 1 || E < 1 || N < 1) return fail(nullptr, "%s: (E, N) = (%d, %d), need each >= 1", who, E, N);
+    if (H < 4 || H > kHeadFitMaxH || H % 4 != 0) return fail(nullptr, "%s: H = %d, need 4 <= H <= %d and H %% 4 == 0", who, H, kHeadFitMaxH);
+    if (reinterpret_cast<uintptr_t>(features) % 16 != 0 || reinterpret_cast<uintptr_t>(weight) % 16 != 0)
+        return fail(nullptr, "%s: features and weight must be 16-byte aligned", who);
+    if (!have_device(who)) return 1;
+    launch_lte_scores(features, weight, bias, E, N, H, scores, reinterpret_cast<hipStream_t>(stream));
+    return launch_status(nullptr, who);
+}
+
+}  // extern "C"

@@ -4,6 +4,7 @@
 //   capi_forward.hip  the forward schedule (Forward, ee_forward) and its captured-graph form (ee_graph_*)
 //   capi_query.hip    what reads the last forward back or arms the next one (ee_profile*, ee_stream_next, ee_last_*, ee_suggest_probe_mask, ee_set_*)
 //   capi_tools.hip    entry points that never see a handle (clock stamps, policy sweeps, pack / unpack, image feed, ee_debug_*)
+//   capi_fit.hip      the device fits, no handle either (ee_head_fit, ee_mlp_head_fit, ee_lte_*, ee_debug_*_lossgrad)
 #pragma once
 #include <cstdint>
 #include <map>
@@ -207,7 +208,7 @@ int dev_alloc(ee_handle* h, T** p, size_t count) {
     return 0;
 }
 
-// ---- shared by the handle-free entry points (capi_tools.hip, capi_debug_rows.hip) ----
+// ---- shared by the handle-free entry points (capi_tools.hip, capi_fit.hip, capi_debug_rows.hip) ----
 // false (and the error message of `who` set) when there is no HIP device
 inline bool have_device(const char* who) {
     int ndev = 0;

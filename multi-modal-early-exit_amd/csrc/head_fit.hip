@@ -6,17 +6,15 @@
 //                               softmax (D = P - Y in place of Z) and the gradient pass (D^T X), whose sums stay in registers across the
 //                               chunk.  One partial (dW, db, loss) per (exit, chunk) goes to the workspace: no atomics.
 //   head_fit_reduce_kernel      sums the chunk partials in chunk order, divides by N, adds the penalty: L and grad L of the trial point.
-//   head_fit_controller_kernel  one workgroup per exit: Armijo test, history update, two-loop recursion, next trial point.
-//   head_fit_finish_kernel      copies the result out -- unless the error word is set, in which case no output is touched.
-// The controller and the finish kernel are written over a parameter count P and serve the two-layer fit (mlp_head_fit.hip) too, through the
-// launchers of head_fit_common.h, which also holds the workspace layout and the control words the two fits share.
+// This file is the objective; the L-BFGS around it is run_lbfgs_fit (fit_lbfgs.hip), the workspace layout and the control words are in
+// head_fit_common.h.
 //
 // Arithmetic form: plain float64 FMAs.  The matrix form (v_mfma_f64_16x16x4_f64) was NOT built, so not measured against it.  Measured for this
 // form (profiles/head_fit.txt): 446 GB/s on the feature bytes at N = 40 000, H = 768, K = 16, E = 6 -- latency-bound, not bandwidth-bound; DESIGN.md
 // section 7 says where the time goes and why the logits pass is the place to try the matrix form.
 //
-// Determinism: the chunking is a function of N alone, every sum has a fixed order, an element of a parameter-sized vector is always touched
-// by the same thread of the controller, and nothing depends on E -- an exit fitted alone gets the bits it gets among others.
+// Determinism: the chunking is a function of N alone, every sum has a fixed order, and nothing depends on E -- an exit fitted alone gets
+// the bits it gets among others.
 #include "head_fit_common.h"
 
 namespace mmee {
@@ -26,13 +24,6 @@ namespace {
 constexpr int S = kHeadFitSlab;
 constexpr int kThreads = 256;
 constexpr int kLogitTile = 8;            // classes per logits-pass round
-constexpr int kCtrlThreads = kFitCtrlThreads;
-constexpr double kArmijo = 1e-4;
-// The Armijo test allows for the rounding of L: below a gradient norm of a few 1e-9 the decrease a good step brings is smaller than the
-// resolution of L in float64, and without the allowance no trial point passes any more (measured on the host restatement: 3 of 36 problems
-// stall at 1.2e-9 ... 2.4e-9 for 200 evaluations; with 1, 4 or 16 epsilon |L| none does).
-constexpr double kArmijoSlack = 8.0 * 2.220446049250313e-16;
-constexpr int kMaxHalvings = 30;
 
 __host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -258,148 +249,6 @@ FitLayout one_layer_layout(int E, int N, int H, int K, int M) {
     return FitLayout(E, K * H + K, M, head_fit_partial_bytes(E, N, H, K));
 }
 
-struct CtrlArgs {
-    char* ws;
-    FitLayout lay;
-    double gtol;
-    int max_evals;
-};
-
-__global__ __launch_bounds__(kCtrlThreads) void head_fit_controller_kernel(CtrlArgs a) {
-    const int e = blockIdx.x, t = threadIdx.x, P = a.lay.P, M = a.lay.M;
-    __shared__ double red[kCtrlThreads];
-    __shared__ double alpha[kHeadFitMaxHistory];
-    int* ci = reinterpret_cast<int*>(a.ws + a.lay.o_ctrl) + e * kCtrlInts;
-    double* cd = reinterpret_cast<double*>(a.ws + a.lay.o_scal) + e * kCtrlDoubles;
-    double* rho = reinterpret_cast<double*>(a.ws + a.lay.o_rho) + (size_t)e * M;
-    double* vec = reinterpret_cast<double*>(a.ws + a.lay.o_vec) + (size_t)e * a.lay.vec_stride;
-    double *th = vec + (size_t)V_THETA * P, *tr = vec + (size_t)V_TRIAL * P, *g = vec + (size_t)V_G * P, *gt = vec + (size_t)V_GTRIAL * P,
-           *d = vec + (size_t)V_DIR * P, *hs = vec + (size_t)V_HIST * P, *hy = hs + (size_t)M * P;
-    const int stop_in = ci[CI_STOP], err = *reinterpret_cast<const int*>(a.ws);
-    const int evals = ci[CI_EVALS] + 1;
-    int halvings = ci[CI_HALVINGS], count = ci[CI_COUNT], head = ci[CI_HEAD];
-    const double f = cd[CD_F], dg_in = cd[CD_DG], f_trial = reinterpret_cast<const double*>(a.ws + a.lay.o_ftrial)[e];
-    double step = cd[CD_STEP], gamma = cd[CD_GAMMA];
-    __syncthreads();                                          // every thread has read the state before thread 0 rewrites it
-    if (stop_in != 0) return;
-    if (err != 0) {
-        if (t == 0) ci[CI_STOP] = 4;
-        return;
-    }
-    const bool first = evals == 1;
-    if (!first && !(f_trial <= f + kArmijo * step * dg_in + kArmijoSlack * fabs(f))) {                  // a NaN trial loss halves too
-        ++halvings;
-        step *= 0.5;
-        const int stop = halvings >= kMaxHalvings ? 3 : evals >= a.max_evals ? 2 : 0;
-        if (!stop)
-            for (int i = t; i < P; i += kCtrlThreads) tr[i] = fma(step, d[i], th[i]);
-        if (t == 0) {
-            ci[CI_EVALS] = evals; ci[CI_HALVINGS] = halvings; ci[CI_STOP] = stop;
-            cd[CD_STEP] = step;
-        }
-        return;
-    }
-    // ---- accepted: the pair (s, y), unless s.y <= 0 ----
-    if (!first) {
-        double sy = 0.0, yy = 0.0;
-        for (int i = t; i < P; i += kCtrlThreads) {
-            const double s_ = tr[i] - th[i], y_ = gt[i] - g[i];
-            sy = fma(s_, y_, sy);
-            yy = fma(y_, y_, yy);
-        }
-        sy = block_sum<kCtrlThreads>(sy, red);
-        yy = block_sum<kCtrlThreads>(yy, red);
-        if (sy > 0.0) {
-            int slot;
-            if (count < M) slot = (head + count++) % M;
-            else { slot = head; head = (head + 1) % M; }
-            for (int i = t; i < P; i += kCtrlThreads) {
-                hs[(size_t)slot * P + i] = tr[i] - th[i];
-                hy[(size_t)slot * P + i] = gt[i] - g[i];
-            }
-            if (t == 0) rho[slot] = 1.0 / sy;
-            gamma = sy / yy;
-        }
-    }
-    double gg = 0.0;
-    for (int i = t; i < P; i += kCtrlThreads) {
-        th[i] = tr[i];
-        g[i] = gt[i];
-        gg = fma(gt[i], gt[i], gg);
-    }
-    gg = block_sum<kCtrlThreads>(gg, red);
-    const double gnorm = sqrt(gg);
-    halvings = 0;
-    const int stop = gnorm <= a.gtol ? 1 : evals >= a.max_evals ? 2 : 0;
-    double dg = 0.0;
-    step = 1.0;
-    if (!stop) {
-        // ---- two-loop recursion: d = -H g ----
-        for (int i = t; i < P; i += kCtrlThreads) d[i] = g[i];
-        for (int q = count - 1; q >= 0; --q) {                                  // newest pair first
-            const int slot = (head + q) % M;
-            const double *s_ = hs + (size_t)slot * P, *y_ = hy + (size_t)slot * P;
-            double sd = 0.0;
-            for (int i = t; i < P; i += kCtrlThreads) sd = fma(s_[i], d[i], sd);
-            const double al = rho[slot] * block_sum<kCtrlThreads>(sd, red);
-            if (t == 0) alpha[q] = al;
-            for (int i = t; i < P; i += kCtrlThreads) d[i] = fma(-al, y_[i], d[i]);
-        }
-        if (count > 0)
-            for (int i = t; i < P; i += kCtrlThreads) d[i] *= gamma;
-        for (int q = 0; q < count; ++q) {
-            const int slot = (head + q) % M;
-            const double *s_ = hs + (size_t)slot * P, *y_ = hy + (size_t)slot * P;
-            double yd = 0.0;
-            for (int i = t; i < P; i += kCtrlThreads) yd = fma(y_[i], d[i], yd);
-            const double beta = rho[slot] * block_sum<kCtrlThreads>(yd, red);       // its barriers publish alpha[]
-            const double co = alpha[q] - beta;
-            for (int i = t; i < P; i += kCtrlThreads) d[i] = fma(co, s_[i], d[i]);
-        }
-        for (int i = t; i < P; i += kCtrlThreads) {
-            d[i] = -d[i];
-            dg = fma(g[i], d[i], dg);
-        }
-        dg = block_sum<kCtrlThreads>(dg, red);
-        if (!(dg < 0.0)) {                                                      // no descent direction: start again from steepest descent
-            for (int i = t; i < P; i += kCtrlThreads) d[i] = -g[i];
-            dg = -gg;
-            count = 0;
-            head = 0;
-        }
-        if (first) step = 1.0 / gnorm;                                          // the very first step; every later one starts at 1
-        for (int i = t; i < P; i += kCtrlThreads) tr[i] = fma(step, d[i], th[i]);
-    }
-    if (t == 0) {
-        ci[CI_STOP] = stop; ci[CI_EVALS] = evals; ci[CI_HALVINGS] = halvings; ci[CI_COUNT] = count; ci[CI_HEAD] = head;
-        cd[CD_F] = f_trial; cd[CD_STEP] = step; cd[CD_DG] = dg; cd[CD_GNORM] = gnorm; cd[CD_GAMMA] = gamma;
-    }
-}
-
-// grid (ceil(P / 256), E)
-__global__ __launch_bounds__(kThreads) void head_fit_finish_kernel(FitFinishArgs a) {
-    if (*reinterpret_cast<const int*>(a.ws) != 0) return;                      // a bad label: the call fails, the outputs stay as they were
-    const int e = blockIdx.y, i = blockIdx.x * kThreads + threadIdx.x, P = a.lay.P;
-    const double* th = reinterpret_cast<const double*>(a.ws + a.lay.o_vec) + (size_t)e * a.lay.vec_stride + (size_t)V_THETA * P;
-    if (i < P) {
-        for (int q = 0; q < a.n_seg; ++q) {
-            const FitOutSeg& sg = a.seg[q];
-            if (i < sg.begin || i >= sg.begin + sg.len) continue;
-            sg.out32[(size_t)e * sg.len + i - sg.begin] = (float)th[i];
-            if (sg.out64) sg.out64[(size_t)e * sg.len + i - sg.begin] = th[i];
-        }
-        if (a.theta64) a.theta64[(size_t)e * P + i] = th[i];
-    }
-    if (i == 0) {
-        const int* ci = reinterpret_cast<const int*>(a.ws + a.lay.o_ctrl) + e * kCtrlInts;
-        const double* cd = reinterpret_cast<const double*>(a.ws + a.lay.o_scal) + e * kCtrlDoubles;
-        if (a.loss) a.loss[e] = cd[CD_F];
-        if (a.grad_norm) a.grad_norm[e] = cd[CD_GNORM];
-        if (a.evals) a.evals[e] = ci[CI_EVALS];
-        if (a.status) a.status[e] = ci[CI_STOP] - 1;
-    }
-}
-
 size_t lossgrad_lds_bytes(int H, int K) {
     return sizeof(float) * S * (size_t)(H + 4) + sizeof(double) * S * (size_t)round_up(K, 16) + sizeof(double) * 4 * S * kLogitTile;
 }
@@ -422,15 +271,18 @@ void launch_lossgrad_k(const LossGradArgs& a, int E, hipStream_t s) {
 }
 
 // one evaluation: the partials of every running exit, then their fixed-order sums
-void launch_eval(LossGradArgs a, int E, double l2, double* loss, size_t loss_stride, double* grad, size_t grad_stride, hipStream_t s) {
+void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, int E, int N, int H, int K, double l2, hipStream_t s) {
+    LossGradArgs a{};
+    a.X = X; a.y = y; a.theta = p.theta; a.theta_stride = p.theta_stride; a.ctrl = p.ctrl; a.err = p.err;
+    a.partial = static_cast<double*>(p.tail); a.N = N; a.H = H; a.K = K;
     const int n_slabs = (a.N + S - 1) / S;
     a.chunks = head_fit_chunks(a.N);
     a.slabs_per_chunk = (n_slabs + a.chunks - 1) / a.chunks;
     if (a.K <= 4) launch_lossgrad_k<4>(a, E, s);
     else launch_lossgrad_k<16>(a, E, s);
     ReduceArgs r{};
-    r.partial = a.partial; r.theta = a.theta; r.theta_stride = a.theta_stride; r.ctrl = a.ctrl; r.loss = loss; r.loss_stride = loss_stride;
-    r.grad = grad; r.grad_stride = grad_stride; r.N = a.N; r.P = a.K * a.H + a.K; r.chunks = a.chunks; r.l2 = l2;
+    r.partial = a.partial; r.theta = a.theta; r.theta_stride = a.theta_stride; r.ctrl = a.ctrl; r.loss = p.loss; r.loss_stride = 1;
+    r.grad = p.grad; r.grad_stride = p.grad_stride; r.N = a.N; r.P = a.K * a.H + a.K; r.chunks = a.chunks; r.l2 = l2;
     hipLaunchKernelGGL(head_fit_reduce_kernel, dim3((r.P + kThreads - 1) / kThreads + 1, E), dim3(kThreads), 0, s, r);
 }
 
@@ -448,41 +300,17 @@ size_t head_fit_workspace_bytes(int E, int N, int H, int K, int history) { retur
 
 size_t head_fit_partial_bytes(int E, int N, int H, int K) { return sizeof(double) * (size_t)E * head_fit_chunks(N) * (size_t)(K * H + K + 1); }
 
-void launch_head_fit_controller(char* ws, const FitLayout& lay, double gtol, int max_evals, hipStream_t s) {
-    CtrlArgs c{ws, lay, gtol, max_evals};
-    hipLaunchKernelGGL(head_fit_controller_kernel, dim3(lay.E), dim3(kCtrlThreads), 0, s, c);
-}
-
-void launch_head_fit_finish(const FitFinishArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(head_fit_finish_kernel, dim3((a.lay.P + kThreads - 1) / kThreads, a.lay.E), dim3(kThreads), 0, s, a);
-}
-
 void launch_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* partial, int* err,
                           double* loss, double* grad, hipStream_t s) {
-    LossGradArgs a{};
-    a.X = X; a.y = y; a.theta = theta; a.theta_stride = (size_t)K * H + K; a.ctrl = nullptr; a.err = err; a.partial = partial;
-    a.N = N; a.H = H; a.K = K;
-    launch_eval(a, E, l2, loss, 1, grad, a.theta_stride, s);
+    const size_t P = (size_t)K * H + K;
+    launch_eval({theta, P, nullptr, err, loss, grad, P, partial}, X, y, E, N, H, K, l2, s);
 }
 
 bool launch_head_fit(const HeadFitArgs& f, hipStream_t s) {
-    const FitLayout lay = one_layer_layout(f.E, f.N, f.H, f.K, f.history);
-    char* ws = static_cast<char*>(f.workspace);
-    if (hipMemsetAsync(ws, 0, lay.zero_bytes, s) != hipSuccess) return false;           // theta = 0, no history, every exit running
-    double* vec = reinterpret_cast<double*>(ws + lay.o_vec);
-    const size_t P = lay.P;
-    LossGradArgs a{};
-    a.X = f.features; a.y = f.labels; a.theta = vec + V_TRIAL * P; a.theta_stride = lay.vec_stride;
-    a.ctrl = reinterpret_cast<const int*>(ws + lay.o_ctrl); a.err = reinterpret_cast<int*>(ws);
-    a.partial = reinterpret_cast<double*>(ws + lay.o_tail); a.N = f.N; a.H = f.H; a.K = f.K;
-    for (int tick = 0; tick < f.max_evals; ++tick) {
-        launch_eval(a, f.E, f.l2, reinterpret_cast<double*>(ws + lay.o_ftrial), 1, vec + V_GTRIAL * P, lay.vec_stride, s);
-        launch_head_fit_controller(ws, lay, f.gtol, f.max_evals, s);
-    }
     const int KH = f.K * f.H;
-    FitFinishArgs o{ws, lay, 2, {{0, KH, f.weight, f.weight64}, {KH, f.K, f.bias, f.bias64}, {}, {}}, nullptr, f.loss, f.grad_norm, f.evals, f.status};
-    launch_head_fit_finish(o, s);
-    return true;
+    return run_lbfgs_fit(f, one_layer_layout(f.E, f.N, f.H, f.K, f.history),
+                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.labels, f.E, f.N, f.H, f.K, f.l2, s); },
+                         {{0, KH, f.weight, f.weight64}, {KH, f.K, f.bias, f.bias64}}, s);
 }
 
 }  // namespace mmee

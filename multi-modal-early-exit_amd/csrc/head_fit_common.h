@@ -1,7 +1,10 @@
-// What the exit-head fits share (head_fit.hip: one Linear; mlp_head_fit.hip: dense + tanh + out_proj): the workspace of a fit, the control
-// words the loss / gradient kernels read to skip a stopped exit, the workgroup sum, and the launchers of the L-BFGS controller and of the
-// finish step.  The controller and the finish kernel themselves live in head_fit.hip, one copy: they are written over a parameter count P.
+// What the device fits share (head_fit.hip: one Linear; mlp_head_fit.hip: dense + tanh + out_proj; lte_fit.hip: the LTE classifier): the
+// workspace of a fit, the control words the loss / gradient kernels read to skip a stopped exit, the workgroup sum, and the L-BFGS driver
+// (fit_lbfgs.hip: the controller and the finish kernel, one copy, written over a parameter count P) with the point it has an objective evaluate.
 #pragma once
+#include <functional>
+#include <initializer_list>
+
 #include "mmee_kernels.h"
 
 namespace mmee {
@@ -47,8 +50,17 @@ struct FitLayout {
 };
 enum { V_THETA = 0, V_TRIAL, V_G, V_GTRIAL, V_DIR, V_HIST };            // V_HIST: s[0 .. M), then y[0 .. M)
 
-// one tick's decision for every exit: reads L(trial) at o_ftrial and grad L(trial) in V_GTRIAL, writes the next trial point into V_TRIAL
-void launch_head_fit_controller(char* ws, const FitLayout& lay, double gtol, int max_evals, hipStream_t s);
+// Where one evaluation of an objective reads theta and writes L and grad L: the driver's trial point, or a debug call's own buffers.  Host only.
+struct FitEvalPoint {
+    const double* theta;             // exit e: theta + e * theta_stride
+    size_t theta_stride;
+    const int* ctrl;                 // per exit kCtrlInts words, or null: every exit runs
+    int* err;                        // the error word
+    double* loss;                    // exit e: loss[e]
+    double* grad;                    // exit e: grad + e * grad_stride
+    size_t grad_stride;
+    void* tail;                      // the objective's scratch: FitLayout's tail
+};
 
 // theta[begin, begin + len) of exit e goes to out32 + e * len (and to out64 + e * len when given)
 struct FitOutSeg {
@@ -65,7 +77,11 @@ struct FitFinishArgs {
     double *loss, *grad_norm;        // (E,) or null
     int *evals, *status;             // (E,) or null
 };
-// copies the result out -- unless the error word is set, in which case no output is touched
-void launch_head_fit_finish(const FitFinishArgs& a, hipStream_t s);
+
+// The whole fit on stream s: the workspace zeroed, f.theta0 ((lay.E, lay.P), null = 0) as the first trial point, f.max_evals ticks of
+// { eval(trial point); controller }, then theta[seg] of every exit to the segments' outputs and f's result pointers.  false: preparing the
+// workspace failed.
+bool run_lbfgs_fit(const FitArgs& f, const FitLayout& lay, const std::function<void(const FitEvalPoint&)>& eval,
+                   std::initializer_list<FitOutSeg> segs, hipStream_t s);
 
 }  // namespace mmee

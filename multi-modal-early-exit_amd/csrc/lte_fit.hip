@@ -1,6 +1,6 @@
 // ee_lte_fit (include/mmee.h): the learning-to-exit classifier -- ONE Linear(H, 1) shared by every encoder exit -- fitted on the device from the
 // CLS rows a dump-all forward leaves (hidden_cls) and the targets "this exit is wrong here" made from its policy logits.  float64 arithmetic on
-// the float32 rows, the L-BFGS of ee_head_fit (head_fit_common.h: the same controller and finish kernels, one "exit" of H + 1 parameters).
+// the float32 rows, the L-BFGS of ee_head_fit (run_lbfgs_fit, fit_lbfgs.hip: the same controller and finish kernels, one "exit" of H + 1 parameters).
 //
 //   lte_fit_lossgrad_kernel  the hot kernel: one pass over the features.  Grid (row chunk, exit), four waves a workgroup, one wave a row.  A wave
 //                            loads kRowsPerWave rows at once (lane l holds columns 4l + 256k + j, the order of head_out_lte_kernel), makes their
@@ -218,7 +218,9 @@ void launch_lossgrad_nv(const LossGradArgs& a, int E, int loss, hipStream_t s) {
 }
 
 // one evaluation: the partials, then their fixed-order sums
-void launch_eval(LossGradArgs a, int E, int loss, double l2, double* loss_out, double* grad, hipStream_t s) {
+void launch_eval(const FitEvalPoint& p, const float* X, const double* T, int E, int N, int H, int loss, double l2, hipStream_t s) {
+    LossGradArgs a{};
+    a.X = X; a.T = T; a.theta = p.theta; a.ctrl = p.ctrl; a.err = p.err; a.partial = static_cast<double*>(p.tail); a.N = N; a.H = H;
     const int n_units = (a.N + R - 1) / R;
     a.chunks = lte_fit_chunks(a.N);
     a.units_per_chunk = (n_units + a.chunks - 1) / a.chunks;
@@ -228,7 +230,7 @@ void launch_eval(LossGradArgs a, int E, int loss, double l2, double* loss_out, d
         case 3: launch_lossgrad_nv<3>(a, E, loss, s); break;
         default: launch_lossgrad_nv<4>(a, E, loss, s); break;
     }
-    ReduceArgs r{a.partial, a.theta, a.ctrl, loss_out, grad, E, a.N, a.H, a.chunks, l2};
+    ReduceArgs r{a.partial, a.theta, a.ctrl, p.loss, p.grad, E, a.N, a.H, a.chunks, l2};
     const int G = E < 16 ? E : 16;
     hipLaunchKernelGGL(lte_fit_reduce_kernel, dim3((a.H + 2 + 63) / 64), dim3(64 * G), 0, s, r);
 }
@@ -301,29 +303,13 @@ size_t lte_fit_workspace_bytes(int E, int N, int H, int history) { return lte_la
 
 void launch_lte_lossgrad(const float* X, const double* T, const double* theta, int E, int N, int H, int loss, double l2, double* partial, int* err,
                          double* loss_out, double* grad, hipStream_t s) {
-    LossGradArgs a{};
-    a.X = X; a.T = T; a.theta = theta; a.ctrl = nullptr; a.err = err; a.partial = partial; a.N = N; a.H = H;
-    launch_eval(a, E, loss, l2, loss_out, grad, s);
+    launch_eval({theta, 0, nullptr, err, loss_out, grad, 0, partial}, X, T, E, N, H, loss, l2, s);
 }
 
 bool launch_lte_fit(const LteFitArgs& f, hipStream_t s) {
-    const FitLayout lay = lte_layout(f.E, f.N, f.H, f.history);
-    char* ws = static_cast<char*>(f.workspace);
-    if (hipMemsetAsync(ws, 0, lay.zero_bytes, s) != hipSuccess) return false;           // theta = 0, no history, running
-    double* vec = reinterpret_cast<double*>(ws + lay.o_vec);
-    const size_t P = lay.P;
-    // the first trial point is theta0: the controller's first tick accepts it as the start
-    if (f.theta0 && hipMemcpyAsync(vec + V_TRIAL * P, f.theta0, sizeof(double) * P, hipMemcpyDeviceToDevice, s) != hipSuccess) return false;
-    LossGradArgs a{};
-    a.X = f.features; a.T = f.targets; a.theta = vec + V_TRIAL * P; a.ctrl = reinterpret_cast<const int*>(ws + lay.o_ctrl);
-    a.err = reinterpret_cast<int*>(ws); a.partial = reinterpret_cast<double*>(ws + lay.o_tail); a.N = f.N; a.H = f.H;
-    for (int tick = 0; tick < f.max_evals; ++tick) {
-        launch_eval(a, f.E, f.loss_kind, f.l2, reinterpret_cast<double*>(ws + lay.o_ftrial), vec + V_GTRIAL * P, s);
-        launch_head_fit_controller(ws, lay, f.gtol, f.max_evals, s);
-    }
-    FitFinishArgs o{ws, lay, 2, {{0, f.H, f.weight, nullptr}, {f.H, 1, f.bias, nullptr}, {}, {}}, f.theta64, f.loss, f.grad_norm, f.evals, f.status};
-    launch_head_fit_finish(o, s);
-    return true;
+    return run_lbfgs_fit(f, lte_layout(f.E, f.N, f.H, f.history),
+                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.targets, f.E, f.N, f.H, f.loss_kind, f.l2, s); },
+                         {{0, f.H, f.weight, nullptr}, {f.H, 1, f.bias, nullptr}}, s);
 }
 
 void launch_lte_targets(const float* logits, const long long* y, int E, int N, int K, double* targets, int* err, hipStream_t s) {

@@ -1,5 +1,5 @@
 // ee_mlp_head_fit (include/mmee.h): two-layer ramp exit heads (dense + tanh + out_proj) fitted on the device from a frozen backbone's CLS rows,
-// float64 arithmetic on the float32 features.  The L-BFGS controller, the workspace layout and the finish step are the one-layer fit's
+// float64 arithmetic on the float32 features.  The L-BFGS is run_lbfgs_fit (fit_lbfgs.hip), the workspace layout the one-layer fit's
 // (head_fit_common.h); this file is the objective: one evaluation of L and grad L at theta = (W1, b1, W2, b2) is seven launches.
 //
 //   mlp_nt_gemm_kernel<float, tanh>   A = tanh(X W1^T + b1)            (N,H) float64, kept in the workspace          2 N H^2 FLOP
@@ -340,9 +340,12 @@ __global__ __launch_bounds__(kFitCtrlThreads) void mlp_loss_kernel(EvalArgs a) {
 
 int ceil_div(int v, int d) { return (v + d - 1) / d; }
 
-// one evaluation: L and grad L of every running exit
-void launch_eval(const EvalArgs& a, int E, hipStream_t s) {
-    const int N = a.N, H = a.H, K = a.K;
+// one evaluation: L and grad L of every running exit; p.tail: mlp_head_fit_scratch_doubles doubles -- hidden rows, logits, the rows' losses
+void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, int E, int N, int H, int K, double l2, hipStream_t s) {
+    EvalArgs a{};
+    a.X = X; a.y = y; a.theta = p.theta; a.theta_stride = p.theta_stride; a.ctrl = p.ctrl; a.err = p.err;
+    a.A = static_cast<double*>(p.tail); a.Z = a.A + (size_t)E * N * H; a.rowloss = a.Z + (size_t)E * N * K;
+    a.loss = p.loss; a.loss_stride = 1; a.grad = p.grad; a.grad_stride = p.grad_stride; a.N = N; a.H = H; a.K = K; a.l2 = l2;
     const size_t HH = (size_t)H * H, oW1 = 0, ob1 = HH, oW2 = HH + H, ob2 = HH + H + (size_t)K * H;
     NtArgs hid{a.X, (size_t)N * H, a.theta, a.theta_stride, oW1, ob1, a.A, (size_t)N * H, a.ctrl, N, H, H};
     hipLaunchKernelGGL((mlp_nt_gemm_kernel<float, true>), dim3(ceil_div(N, TM), ceil_div(H, TN), E), dim3(kThreads), 0, s, hid);
@@ -365,13 +368,6 @@ void launch_eval(const EvalArgs& a, int E, hipStream_t s) {
 
 size_t params(int H, int K) { return (size_t)H * H + H + (size_t)K * H + K; }
 
-// the scratch of an evaluation inside `base`: hidden rows, logits, the rows' losses
-void carve_scratch(double* base, int E, int N, int H, int K, EvalArgs* a) {
-    a->A = base;
-    a->Z = a->A + (size_t)E * N * H;
-    a->rowloss = a->Z + (size_t)E * N * K;
-}
-
 FitLayout mlp_layout(int E, int N, int H, int K, int M) {
     return FitLayout(E, (int)params(H, K), M, sizeof(double) * mlp_head_fit_scratch_doubles(E, N, H, K));
 }
@@ -384,39 +380,15 @@ size_t mlp_head_fit_workspace_bytes(int E, int N, int H, int K, int history) { r
 
 void launch_mlp_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* scratch,
                               int* err, double* loss, double* grad, hipStream_t s) {
-    EvalArgs a{};
-    a.X = X; a.y = y; a.theta = theta; a.theta_stride = params(H, K); a.ctrl = nullptr; a.err = err;
-    a.loss = loss; a.loss_stride = 1; a.grad = grad; a.grad_stride = a.theta_stride; a.N = N; a.H = H; a.K = K; a.l2 = l2;
-    carve_scratch(scratch, E, N, H, K, &a);
-    launch_eval(a, E, s);
+    launch_eval({theta, params(H, K), nullptr, err, loss, grad, params(H, K), scratch}, X, y, E, N, H, K, l2, s);
 }
 
 bool launch_mlp_head_fit(const MlpHeadFitArgs& f, hipStream_t s) {
-    const FitLayout lay = mlp_layout(f.E, f.N, f.H, f.K, f.history);
-    char* ws = static_cast<char*>(f.workspace);
-    if (hipMemsetAsync(ws, 0, lay.zero_bytes, s) != hipSuccess) return false;           // no history, every exit running
-    double* vec = reinterpret_cast<double*>(ws + lay.o_vec);
-    const size_t P = lay.P;
-    // the first trial point is theta0: the controller's first tick accepts it as the start
-    for (int e = 0; e < f.E; ++e)
-        if (hipMemcpyAsync(vec + (size_t)e * lay.vec_stride + V_TRIAL * P, f.theta0 + (size_t)e * P, sizeof(double) * P, hipMemcpyDeviceToDevice,
-                           s) != hipSuccess)
-            return false;
-    EvalArgs a{};
-    a.X = f.features; a.y = f.labels; a.theta = vec + V_TRIAL * P; a.theta_stride = lay.vec_stride;
-    a.ctrl = reinterpret_cast<const int*>(ws + lay.o_ctrl); a.err = reinterpret_cast<int*>(ws);
-    a.loss = reinterpret_cast<double*>(ws + lay.o_ftrial); a.loss_stride = 1; a.grad = vec + V_GTRIAL * P; a.grad_stride = lay.vec_stride;
-    a.N = f.N; a.H = f.H; a.K = f.K; a.l2 = f.l2;
-    carve_scratch(reinterpret_cast<double*>(ws + lay.o_tail), f.E, f.N, f.H, f.K, &a);
-    for (int tick = 0; tick < f.max_evals; ++tick) {
-        launch_eval(a, f.E, s);
-        launch_head_fit_controller(ws, lay, f.gtol, f.max_evals, s);
-    }
     const int H = f.H, K = f.K, HH = H * H;
-    FitFinishArgs o{ws, lay, 4, {{0, HH, f.dense_weight, nullptr}, {HH, H, f.dense_bias, nullptr}, {HH + H, K * H, f.weight, nullptr},
-                                 {HH + H + K * H, K, f.bias, nullptr}}, f.theta64, f.loss, f.grad_norm, f.evals, f.status};
-    launch_head_fit_finish(o, s);
-    return true;
+    return run_lbfgs_fit(f, mlp_layout(f.E, f.N, H, K, f.history),
+                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.labels, f.E, f.N, H, K, f.l2, s); },
+                         {{0, HH, f.dense_weight, nullptr}, {HH, H, f.dense_bias, nullptr}, {HH + H, K * H, f.weight, nullptr},
+                          {HH + H + K * H, K, f.bias, nullptr}}, s);
 }
 
 }  // namespace mmee

@@ -316,17 +316,23 @@ constexpr int kHeadFitSlab = 32;             // rows a workgroup keeps in LDS be
 constexpr int kHeadFitMaxChunks = 128;       // row chunks (= partial gradients) per exit
 constexpr int kHeadFitMaxH = 1024;           // a slab of kHeadFitSlab float32 rows stays inside the 160 KB of LDS
 constexpr int kHeadFitMaxHistory = 32;
-struct HeadFitArgs {
+// what every device fit carries (fit_lbfgs.hip); P: the parameters of one exit
+struct FitArgs {
     const float* features;           // (E,N,H)
-    const long long* labels;         // (N,)
-    int E, N, H, K;
+    int E, N, H;
     double l2, gtol;
     int max_evals, history;
-    void* workspace;                 // head_fit_workspace_bytes
+    void* workspace;                 // the fit's *_workspace_bytes
+    const double* theta0;            // the start, or null = 0
+    double* theta64;                 // the solution in float64, or null
+    double *loss, *grad_norm;        // one per fitted parameter set, or null
+    int *evals, *status;             // one per fitted parameter set, or null
+};
+struct HeadFitArgs : FitArgs {       // E parameter sets; theta0 and theta64 null
+    const long long* labels;         // (N,)
+    int K;
     float *weight, *bias;            // (E,K,H), (E,K)
     double *weight64, *bias64;       // the same in float64, or null
-    double *loss, *grad_norm;        // (E,) or null
-    int *evals, *status;             // (E,) or null
 };
 int head_fit_chunks(int N);
 size_t head_fit_workspace_bytes(int E, int N, int H, int K, int history);
@@ -338,18 +344,10 @@ void launch_head_lossgrad(const float* X, const long long* y, const double* thet
                           double* loss, double* grad, hipStream_t s);
 // ee_mlp_head_fit (mlp_head_fit.hip): two-layer heads (dense + tanh + out_proj) per exit; theta = W1 (H,H), b1 (H,), W2 (K,H), b2 (K,)
 constexpr int kMlpHeadFitRows = 64;          // the row tile of the GEMM kernels, the largest of the new kernels' tiles (MMEE_MLP_HEAD_FIT_ROWS)
-struct MlpHeadFitArgs {
-    const float* features;           // (E,N,H)
+struct MlpHeadFitArgs : FitArgs {    // E parameter sets; theta0 (E,P) required, theta64 (E,P)
     const long long* labels;         // (N,)
-    const double* theta0;            // (E,P): the start
-    int E, N, H, K;
-    double l2, gtol;
-    int max_evals, history;
-    void* workspace;                 // mlp_head_fit_workspace_bytes
+    int K;
     float *dense_weight, *dense_bias, *weight, *bias;   // (E,H,H), (E,H), (E,K,H), (E,K)
-    double* theta64;                 // (E,P) or null
-    double *loss, *grad_norm;        // (E,) or null
-    int *evals, *status;             // (E,) or null
 };
 size_t mlp_head_fit_workspace_bytes(int E, int N, int H, int K, int history);
 size_t mlp_head_fit_scratch_doubles(int E, int N, int H, int K);
@@ -363,18 +361,10 @@ constexpr int kLteFitRows = 16;              // the rows a workgroup treats as a
 constexpr int kLteFitMaxChunks = 128;        // row chunks (= partial gradients) per exit
 constexpr int kLteFitMaxExits = 64;          // the reduce kernel keeps one sum per exit in LDS
 enum { kLteLossMse = 0, kLteLossBce = 1 };   // MMEE_LTE_LOSS_*
-struct LteFitArgs {
-    const float* features;           // (E,N,H)
+struct LteFitArgs : FitArgs {        // one parameter set over E data exits; theta0 and theta64 (H + 1,)
     const double* targets;           // (E,N) in [0,1]
-    const double* theta0;            // (H + 1,) or null: the start (null = 0)
-    int E, N, H, loss_kind;
-    double l2, gtol;
-    int max_evals, history;
-    void* workspace;                 // lte_fit_workspace_bytes
+    int loss_kind;
     float *weight, *bias;            // (1,H), (1,)
-    double* theta64;                 // (H + 1,) or null
-    double *loss, *grad_norm;        // one double each, or null
-    int *evals, *status;             // one int each, or null
 };
 int lte_fit_chunks(int N);
 size_t lte_fit_workspace_bytes(int E, int N, int H, int history);

@@ -26,7 +26,6 @@ Reloading heads into an engine that holds captured graphs does not re-capture th
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Dict, Iterable, Mapping
 
@@ -38,6 +37,23 @@ from .engine import _require_torch_cuda, torch
 
 STATUS = {0: "converged", 1: "max_evals", 2: "line_search"}
 LTE_MAX_EVALS = 1000           # fit_lte_classifier's default budget; its docstring says where it comes from
+
+
+def _dump_all(engine, batches, **want):
+    """Per batch: the CLS rows (E,n,H) leaving the configured encoder exit layers, and the dump-all forward's whole output."""
+    layers = torch.tensor(engine.cfg.exit_config.encoder_exit_layers, dtype=torch.int64, device=engine.device)
+    keys = ("input_ids", "attention_mask", "bbox", "pixel_values", "token_type_ids", "position_ids")
+    for b in batches:
+        out = engine.forward(**{k: b[k] for k in keys if k in b and b[k] is not None}, dump_all=True, want_hidden_cls=True, **want)
+        yield out.hidden_cls.index_select(0, layers), out
+
+
+def _cat_batches(per_batch):
+    """The batches' tensors joined along the document axis, one result per position."""
+    cols = list(zip(*per_batch))
+    if not cols:
+        raise ValueError("no batches")
+    return [torch.cat(c, dim=1).contiguous() for c in cols]
 
 
 def _check_fittable(cfg: ModelConfig, head_layers: int = 1):
@@ -65,15 +81,7 @@ def collect_exit_features(engine, batches: Iterable[Mapping], head_layers: int =
     of the CLS rows leaving the configured encoder exit layers -- the inputs of the heads ``encoder.early_exits.0 .. E-1``.
     ``head_layers`` states which heads the rows are for: 1 (``fit_exit_heads``) or 2 (``fit_mlp_exit_heads``); the configuration must agree."""
     _check_fittable(engine.cfg, head_layers)
-    layers = torch.tensor(engine.cfg.exit_config.encoder_exit_layers, dtype=torch.int64, device=engine.device)
-    keys = ("input_ids", "attention_mask", "bbox", "pixel_values", "token_type_ids", "position_ids")
-    rows = []
-    for b in batches:
-        out = engine.forward(**{k: b[k] for k in keys if k in b and b[k] is not None}, dump_all=True, want_hidden_cls=True)
-        rows.append(out.hidden_cls.index_select(0, layers))
-    if not rows:
-        raise ValueError("no batches")
-    return torch.cat(rows, dim=1).contiguous()
+    return _cat_batches((rows,) for rows, _ in _dump_all(engine, batches))[0]
 
 
 @dataclass
@@ -90,20 +98,14 @@ class HeadFit:
 
     def logits(self, features) -> "torch.Tensor":
         """(E,N,K) float64 logits of the float32 heads on ``features`` (E,N,H), on the device."""
-        X = _to_device(features, torch.float32, self.weight.device).to(torch.float64)
-        if X.dim() == 2:
-            X = X.unsqueeze(0)
+        X = _rows(features, on=self.weight.device)[1].to(torch.float64)
         return torch.baddbmm(self.bias.to(torch.float64).unsqueeze(1), X, self.weight.to(torch.float64).transpose(1, 2))
 
     def state_dict(self, cfg: ModelConfig) -> Dict[str, np.ndarray]:
         """``{prefix}encoder.early_exits.{k}.out_proj.weight / .bias`` (host float32), ready for ``engine.load_weights`` next to the
         backbone's tensors."""
         _check_fittable(cfg)
-        E, K, H = self.weight.shape
-        if E != len(cfg.exit_config.encoder_exit_layers) or K != cfg.num_labels or H != cfg.hidden_size:
-            raise ValueError(f"the fit is (E,K,H) = {(E, K, H)}, the configuration wants "
-                             f"{(len(cfg.exit_config.encoder_exit_layers), cfg.num_labels, cfg.hidden_size)}")
-        p = "beit." if cfg.arch == "beit" else "layoutlmv3."
+        E, p = _head_prefix(self, cfg)
         w, b = self.weight.cpu().numpy(), self.bias.cpu().numpy()
         out = {}
         for k in range(E):
@@ -116,6 +118,56 @@ def _to_device(x, dtype, dev):
     if isinstance(x, np.ndarray):
         x = torch.from_numpy(np.ascontiguousarray(x) if x.flags.writeable else np.array(x))
     return x.to(dev, dtype).contiguous()
+
+
+def _rows(x, device=None, on=None):
+    """``x`` (E,N,H), or (N,H) for one exit -> (dev, the (E,N,H) float32 tensor on it).  dev: ``on``, else ``x``'s own CUDA device unless
+    ``device`` names one."""
+    dev = on if on is not None else x.device if (torch is not None and isinstance(x, torch.Tensor) and x.is_cuda and device is None) \
+        else _require_torch_cuda(device)
+    X = _to_device(x, torch.float32, dev)
+    return dev, X.unsqueeze(0) if X.dim() == 2 else X
+
+
+def _labels(labels, dev, N, num_labels):
+    """-> (y (N,) int64 on dev, K)"""
+    y = _to_device(labels, torch.int64, dev).view(-1)
+    K = int(y.max()) + 1 if num_labels is None else int(num_labels)
+    if y.shape[0] != N:
+        raise ValueError("labels must have one entry per feature row")
+    return y, K
+
+
+def _workspace(query, dev, *dims):
+    """-> (a device buffer of the bytes ``ee_*_workspace_bytes`` symbol ``query`` asks for ``dims``, their count)"""
+    need = int(getattr(capi.load(), query)(*dims))
+    return torch.empty((max(need, 1),), dtype=torch.uint8, device=dev), need
+
+
+def _call(name, dev, *args):
+    """The library's ``name`` on ``dev``'s current stream (its last argument); tensors go as their addresses, ``None`` as NULL."""
+    fn = getattr(capi.load(), name)
+    with torch.cuda.device(dev):
+        capi.check(fn(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], torch.cuda.current_stream().cuda_stream), None, name)
+
+
+def _named(init, suffix, shape):
+    """The one tensor of the mapping ``init`` whose key ends in ``suffix``; it must have ``shape``."""
+    found = [v for key, v in init.items() if key.endswith(suffix)]
+    if len(found) != 1:
+        raise ValueError(f"init names {len(found)} tensors ending in {suffix}, need one")
+    if tuple(np.shape(found[0])) != shape:
+        raise ValueError(f"{suffix} is {tuple(np.shape(found[0]))}, need {shape}")
+    return found[0]
+
+
+def _head_prefix(fit, cfg: ModelConfig):
+    """``fit.weight`` (E,K,H) against the configuration -> (E, the checkpoint prefix of the architecture)"""
+    E, K, H = fit.weight.shape
+    if E != len(cfg.exit_config.encoder_exit_layers) or K != cfg.num_labels or H != cfg.hidden_size:
+        raise ValueError(f"the fit is (E,K,H) = {(E, K, H)}, the configuration wants "
+                         f"{(len(cfg.exit_config.encoder_exit_layers), cfg.num_labels, cfg.hidden_size)}")
+    return E, "beit." if cfg.arch == "beit" else "layoutlmv3."
 
 
 def fit_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-9, max_evals: int = 2000, history: int = 8, device=None,
@@ -131,29 +183,17 @@ def fit_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-9, max_e
 
     Host synchronisation: the call waits for its stream once, after the last launch, to read the error word (a label outside [0,K) fails
     the call); with ``num_labels=None`` reading ``labels.max()`` is a second wait, before the first launch."""
-    lib = capi.load()
-    dev = features.device if (torch is not None and isinstance(features, torch.Tensor) and features.is_cuda and device is None) \
-        else _require_torch_cuda(device)
-    X = _to_device(features, torch.float32, dev)
-    if X.dim() == 2:
-        X = X.unsqueeze(0)
-    y = _to_device(labels, torch.int64, dev).view(-1)
+    capi.load()
+    dev, X = _rows(features, device)
     E, N, H = X.shape
-    K = int(y.max()) + 1 if num_labels is None else int(num_labels)
-    if y.shape[0] != N:
-        raise ValueError("labels must have one entry per feature row")
+    y, K = _labels(labels, dev, N, num_labels)
     f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
     fit = HeadFit(torch.zeros((E, K, H), dtype=torch.float32, device=dev), torch.zeros((E, K), dtype=torch.float32, device=dev),
                   f64(E, K, H), f64(E, K), f64(E), f64(E), torch.zeros((E,), dtype=torch.int32, device=dev),
                   torch.full((E,), -1, dtype=torch.int32, device=dev), float(l2))
-    need = int(lib.ee_head_fit_workspace_bytes(E, N, H, K, history))
-    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        capi.check(lib.ee_head_fit(p(X), p(y), E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), p(ws), need, p(fit.weight),
-                                   p(fit.bias), p(fit.weight64), p(fit.bias64), p(fit.loss), p(fit.grad_norm), p(fit.evals), p(fit.status),
-                                   stream), None, "ee_head_fit")
+    ws, need = _workspace("ee_head_fit_workspace_bytes", dev, E, N, H, K, history)
+    _call("ee_head_fit", dev, X, y, E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.weight, fit.bias,
+          fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status)
     return fit
 
 
@@ -181,9 +221,7 @@ class MlpHeadFit:
     def logits(self, features) -> "torch.Tensor":
         """(E,N,K) float64 logits of the float32 heads on ``features`` (E,N,H), on the device."""
         f64 = torch.float64
-        X = _to_device(features, torch.float32, self.weight.device).to(f64)
-        if X.dim() == 2:
-            X = X.unsqueeze(0)
+        X = _rows(features, on=self.weight.device)[1].to(f64)
         A = torch.tanh(torch.baddbmm(self.dense_bias.to(f64).unsqueeze(1), X, self.dense_weight.to(f64).transpose(1, 2)))
         return torch.baddbmm(self.bias.to(f64).unsqueeze(1), A, self.weight.to(f64).transpose(1, 2))
 
@@ -191,11 +229,7 @@ class MlpHeadFit:
         """``{prefix}encoder.early_exits.{k}.dense.weight / .bias`` and ``.out_proj.weight / .bias`` (host float32), ready for
         ``engine.load_weights`` next to the backbone's tensors."""
         _check_fittable(cfg, 2)
-        E, K, H = self.weight.shape
-        if E != len(cfg.exit_config.encoder_exit_layers) or K != cfg.num_labels or H != cfg.hidden_size:
-            raise ValueError(f"the fit is (E,K,H) = {(E, K, H)}, the configuration wants "
-                             f"{(len(cfg.exit_config.encoder_exit_layers), cfg.num_labels, cfg.hidden_size)}")
-        p = "beit." if cfg.arch == "beit" else "layoutlmv3."
+        E, p = _head_prefix(self, cfg)
         blocks = [t.cpu().numpy() for t in (self.dense_weight, self.dense_bias, self.weight, self.bias)]
         out = {}
         for k in range(E):
@@ -217,16 +251,8 @@ def _mlp_theta0(init, E, H, K, dev):
         shapes = ((H, H), (H,), (K, H), (K,))
         rows = []
         for k in range(E):
-            parts = []
-            for name, shape in zip(_MLP_BLOCKS, shapes):
-                found = [v for key, v in init.items() if key.endswith(f"encoder.early_exits.{k}.{name}")]
-                if len(found) != 1:
-                    raise ValueError(f"init names {len(found)} tensors ending in encoder.early_exits.{k}.{name}, need one")
-                a = _to_device(found[0], torch.float64, dev)
-                if tuple(a.shape) != shape:
-                    raise ValueError(f"encoder.early_exits.{k}.{name} is {tuple(a.shape)}, need {shape}")
-                parts.append(a.reshape(-1))
-            rows.append(torch.cat(parts))
+            rows.append(torch.cat([_to_device(_named(init, f"encoder.early_exits.{k}.{name}", shape), torch.float64, dev).reshape(-1)
+                                   for name, shape in zip(_MLP_BLOCKS, shapes)]))
         return torch.stack(rows).contiguous()
     th = _to_device(init, torch.float64, dev)
     if th.dim() == 1:
@@ -251,31 +277,19 @@ def fit_mlp_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-6, m
     budget of 4000; a stopped exit costs nothing more.
 
     Host synchronisation: as for ``fit_exit_heads``, one wait after the last launch (plus one for ``labels.max()`` without ``num_labels``)."""
-    lib = capi.load()
-    dev = features.device if (torch is not None and isinstance(features, torch.Tensor) and features.is_cuda and device is None) \
-        else _require_torch_cuda(device)
-    X = _to_device(features, torch.float32, dev)
-    if X.dim() == 2:
-        X = X.unsqueeze(0)
-    y = _to_device(labels, torch.int64, dev).view(-1)
+    capi.load()
+    dev, X = _rows(features, device)
     E, N, H = X.shape
-    K = int(y.max()) + 1 if num_labels is None else int(num_labels)
-    if y.shape[0] != N:
-        raise ValueError("labels must have one entry per feature row")
+    y, K = _labels(labels, dev, N, num_labels)
     theta0 = _mlp_theta0(init, E, H, K, dev)
     P = mlp_param_count(H, K)
     z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
     fit = MlpHeadFit(z((E, H, H), torch.float32), z((E, H), torch.float32), z((E, K, H), torch.float32), z((E, K), torch.float32),
                      z((E, P), torch.float64), z((E,), torch.float64), z((E,), torch.float64), z((E,), torch.int32),
                      torch.full((E,), -1, dtype=torch.int32, device=dev), float(l2))
-    need = int(lib.ee_mlp_head_fit_workspace_bytes(E, N, H, K, history))
-    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        capi.check(lib.ee_mlp_head_fit(p(X), p(y), p(theta0), E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), p(ws), need,
-                                       p(fit.dense_weight), p(fit.dense_bias), p(fit.weight), p(fit.bias), p(fit.theta64), p(fit.loss),
-                                       p(fit.grad_norm), p(fit.evals), p(fit.status), stream), None, "ee_mlp_head_fit")
+    ws, need = _workspace("ee_mlp_head_fit_workspace_bytes", dev, E, N, H, K, history)
+    _call("ee_mlp_head_fit", dev, X, y, theta0, E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.dense_weight,
+          fit.dense_bias, fit.weight, fit.bias, fit.theta64, fit.loss, fit.grad_norm, fit.evals, fit.status)
     return fit
 
 
@@ -299,36 +313,21 @@ def collect_lte_features(engine, batches: Iterable[Mapping]):
     _check_lte_cfg(engine.cfg)
     ec = engine.cfg.exit_config
     n_emb, n_enc = len(ec.embedding_exits), len(ec.encoder_exit_layers)
-    layers = torch.tensor(ec.encoder_exit_layers, dtype=torch.int64, device=engine.device)
-    keys = ("input_ids", "attention_mask", "bbox", "pixel_values", "token_type_ids", "position_ids")
-    rows, logits = [], []
-    for b in batches:
-        out = engine.forward(**{k: b[k] for k in keys if k in b and b[k] is not None}, dump_all=True, want_all=True, want_hidden_cls=True)
-        rows.append(out.hidden_cls.index_select(0, layers))
-        logits.append(out.all_logits[n_emb:n_emb + n_enc].to(torch.float32))
-    if not rows:
-        raise ValueError("no batches")
-    return torch.cat(rows, dim=1).contiguous(), torch.cat(logits, dim=1).contiguous()
+    return tuple(_cat_batches((rows, out.all_logits[n_emb:n_emb + n_enc].to(torch.float32))
+                              for rows, out in _dump_all(engine, batches, want_all=True)))
 
 
 def lte_targets(logits, labels, device=None) -> "torch.Tensor":
     """(E,N) float64 device tensor: 1 where the argmax (first maximum) of ``logits`` (E,N,K) float32 differs from ``labels`` (N,), else 0 --
     the reference's ``1 - lte_gold``.  A label outside [0,K) or a NaN logit (a row its document never reached) fails the call."""
-    lib = capi.load()
-    dev = logits.device if (torch is not None and isinstance(logits, torch.Tensor) and logits.is_cuda and device is None) \
-        else _require_torch_cuda(device)
-    Z = _to_device(logits, torch.float32, dev)
-    if Z.dim() == 2:
-        Z = Z.unsqueeze(0)
+    capi.load()
+    dev, Z = _rows(logits, device)
     y = _to_device(labels, torch.int64, dev).view(-1)
     E, N, K = Z.shape
     if y.shape[0] != N:
         raise ValueError("labels must have one entry per document")
     out = torch.zeros((E, N), dtype=torch.float64, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        capi.check(lib.ee_lte_targets(p(Z), p(y), E, N, K, p(out), stream), None, "ee_lte_targets")
+    _call("ee_lte_targets", dev, Z, y, E, N, K, out)
     return out
 
 
@@ -347,19 +346,12 @@ class LteFit:
     def scores(self, features) -> "torch.Tensor":
         """(E,N) float64 scores sigmoid(w . x + b) of the float32 classifier on ``features`` (E,N,H), on the device, in the forward's
         summation order: the rows ``sweep.lte_sweep`` and ``lte_scan_device`` take."""
-        lib = capi.load()
-        dev = self.weight.device
-        X = _to_device(features, torch.float32, dev)
-        if X.dim() == 2:
-            X = X.unsqueeze(0)
+        dev, X = _rows(features, on=self.weight.device)
         E, N, H = X.shape
         if H != self.weight.shape[1]:
             raise ValueError(f"features have H = {H}, the classifier {self.weight.shape[1]}")
         out = torch.empty((E, N), dtype=torch.float64, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            capi.check(lib.ee_lte_scores(p(X), p(self.weight), p(self.bias), E, N, H, p(out), stream), None, "ee_lte_scores")
+        _call("ee_lte_scores", dev, X, self.weight, self.bias, E, N, H, out)
         return out
 
     def state_dict(self, cfg: ModelConfig) -> Dict[str, np.ndarray]:
@@ -376,18 +368,11 @@ def _lte_theta0(init, H):
     """The start as a host (H+1,) float64 array, or None for zero."""
     if init is None:
         return None
+    host = lambda v: v.detach().cpu().numpy() if (torch is not None and isinstance(v, torch.Tensor)) else np.asarray(v)
     if isinstance(init, Mapping):
-        parts = []
-        for name, shape in ((_LTE_W, (1, H)), (_LTE_B, (1,))):
-            found = [v for key, v in init.items() if key.endswith(name)]
-            if len(found) != 1:
-                raise ValueError(f"init names {len(found)} tensors ending in {name}, need one")
-            a = found[0].detach().cpu().numpy() if (torch is not None and isinstance(found[0], torch.Tensor)) else np.asarray(found[0])
-            if tuple(a.shape) != shape:
-                raise ValueError(f"{name} is {tuple(a.shape)}, need {shape}")
-            parts.append(a.astype(np.float64).reshape(-1))
-        return np.concatenate(parts)
-    a = init.detach().cpu().numpy() if (torch is not None and isinstance(init, torch.Tensor)) else np.asarray(init)
+        return np.concatenate([host(_named(init, name, shape)).astype(np.float64).reshape(-1)
+                               for name, shape in ((_LTE_W, (1, H)), (_LTE_B, (1,)))])
+    a = host(init)
     if tuple(a.shape) != (H + 1,):
         raise ValueError(f"init is {tuple(a.shape)}, need (H+1,) = {(H + 1,)}: w then b")
     return a.astype(np.float64)
@@ -414,12 +399,8 @@ def fit_lte_classifier(features, targets, loss: str = "mse", l2: float = 1e-2, g
         raise ValueError(f"loss = {loss!r}: 'mse' (the reference's) or 'bce'")
     H_in = int(features.shape[-1])
     theta0 = _lte_theta0(init, H_in)
-    lib = capi.load()
-    dev = features.device if (torch is not None and isinstance(features, torch.Tensor) and features.is_cuda and device is None) \
-        else _require_torch_cuda(device)
-    X = _to_device(features, torch.float32, dev)
-    if X.dim() == 2:
-        X = X.unsqueeze(0)
+    capi.load()
+    dev, X = _rows(features, device)
     E, N, H = X.shape
     T = _to_device(targets, torch.float64, dev)
     if T.dim() == 1:
@@ -430,12 +411,7 @@ def fit_lte_classifier(features, targets, loss: str = "mse", l2: float = 1e-2, g
     z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
     fit = LteFit(z((1, H), torch.float32), z((1,), torch.float32), z((H + 1,), torch.float64), z((1,), torch.float64), z((1,), torch.float64),
                  z((1,), torch.int32), torch.full((1,), -1, dtype=torch.int32, device=dev), float(l2), loss)
-    need = int(lib.ee_lte_fit_workspace_bytes(E, N, H, history))
-    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        capi.check(lib.ee_lte_fit(p(X), p(T), p(th0), E, N, H, LTE_LOSSES[loss], float(l2), float(gtol), int(max_evals), int(history), p(ws),
-                                  need, p(fit.weight), p(fit.bias), p(fit.theta64), p(fit.loss), p(fit.grad_norm), p(fit.evals), p(fit.status),
-                                  stream), None, "ee_lte_fit")
+    ws, need = _workspace("ee_lte_fit_workspace_bytes", dev, E, N, H, history)
+    _call("ee_lte_fit", dev, X, T, th0, E, N, H, LTE_LOSSES[loss], float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.weight,
+          fit.bias, fit.theta64, fit.loss, fit.grad_norm, fit.evals, fit.status)
     return fit

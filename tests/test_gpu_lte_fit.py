@@ -13,6 +13,7 @@ import pytest
 
 from . import lte_fit_ref as LR
 from .conftest import H256_KW
+from .fit_util import _ptr, _stream, _torch
 from .lte_ref import gap_thresholds, lte_exits
 
 pytestmark = pytest.mark.gpu
@@ -23,22 +24,9 @@ FIT_SHAPES = [(300, 64, 3), (257, 64, 1), (1000, 256, 2), (600, 768, 1), (96, 25
 W_NAME, B_NAME = "layoutlmv3.encoder.lte_classifier.weight", "layoutlmv3.encoder.lte_classifier.bias"
 
 
-def _torch():
-    import torch
-    return torch
-
-
 def _dev(a, dtype=None):
     torch = _torch()
     return torch.from_numpy(np.array(a)).to(device="cuda", dtype=dtype)          # a copy: the cached problems are read-only
-
-
-def _ptr(x):
-    return C.c_void_p(x.data_ptr()) if x is not None else None
-
-
-def _stream():
-    return C.c_void_p(_torch().cuda.current_stream().cuda_stream)
 
 
 def _code(pkg, loss):

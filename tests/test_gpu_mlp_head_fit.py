@@ -13,6 +13,7 @@ import pytest
 from . import headfit_ref as HR
 from . import mlp_headfit_ref as MR
 from .conftest import H256_KW
+from .fit_util import _dev, _gap_thresholds, _ptr, _stream, _torch
 
 pytestmark = pytest.mark.gpu
 
@@ -20,24 +21,6 @@ L2, GTOL = 1e-2, 1e-6
 RTOL, ATOL = 1e-10, 1e-12
 FIT_SHAPES = [(300, 64, 10, 3), (257, 64, 2, 1), (600, 128, 16, 2)]
 OUTPUTS = ("dense_weight", "dense_bias", "weight", "bias", "theta64", "loss", "grad_norm", "evals", "status")
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def _dev(a, dtype=None):
-    torch = _torch()
-    return torch.from_numpy(np.ascontiguousarray(a)).to(device="cuda", dtype=dtype)
-
-
-def _ptr(x):
-    return C.c_void_p(x.data_ptr()) if x is not None else None
-
-
-def _stream():
-    return C.c_void_p(_torch().cuda.current_stream().cuda_stream)
 
 
 def _lossgrad(pkg, X, y, theta, K, l2=L2):
@@ -310,16 +293,6 @@ def test_a_label_out_of_range_fails_the_call_and_leaves_the_outputs_untouched(pk
 
 # ---- 5. through the engine ----------------------------------------------------------------------------------------------------------------------
 EE_2LAYER = dict(exits=[1, 2, 3], encoder_layer_strategy="ramp", inference_strategy="max_confidence", exit_head_num_layers=2)
-
-
-def _gap_thresholds(conf):
-    """Per exit, the middle of the widest gap between neighbouring confidences that leaves documents on both sides."""
-    thr = np.empty(conf.shape[0])
-    for e, row in enumerate(conf):
-        s = np.sort(row)
-        j = int(np.argmax(np.diff(s)))
-        thr[e] = 0.5 * (s[j] + s[j + 1])
-    return thr
 
 
 @pytest.mark.parametrize("name", ["tiny_f32", "h256_split", "dit_tiny"])

@@ -13,6 +13,7 @@ import pytest
 
 from . import headfit_ref as HR
 from .conftest import ROOT
+from .fit_util import _HostTensor
 
 NAMES = ("ee_head_fit", "ee_head_fit_workspace_bytes", "ee_debug_head_lossgrad")
 ONE_LAYER_RAMP = dict(exits=[1, 2, 4], encoder_layer_strategy="ramp", exit_head_num_layers=1)
@@ -126,19 +127,6 @@ def test_workspace_grows_with_every_dimension(pkg):
     base = lib.ee_head_fit_workspace_bytes(2, 1000, 64, 10, 8)
     for args in ((3, 1000, 64, 10, 8), (2, 5000, 64, 10, 8), (2, 1000, 128, 10, 8), (2, 1000, 64, 11, 8), (2, 1000, 64, 10, 9)):
         assert lib.ee_head_fit_workspace_bytes(*args) > base, args
-
-
-class _HostTensor:
-    """What HeadFit.state_dict asks of a tensor: shape and .cpu().numpy()."""
-
-    def __init__(self, a):
-        self.a, self.shape = a, a.shape
-
-    def cpu(self):
-        return self
-
-    def numpy(self):
-        return self.a
 
 
 def _host_fit(pkg, E, K, H):

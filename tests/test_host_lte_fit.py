@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from . import lte_fit_ref as LR
+from .fit_util import _HostTensor
 
 L2 = 1e-2
 FIT_SHAPES = [(300, 64, 3), (257, 64, 1), (1000, 256, 2), (600, 768, 1), (96, 256, 3)]       # (N, H, E)
@@ -114,19 +115,6 @@ def test_the_scipy_reference_reaches_one_point_from_four_starts(N, H, E, loss):
     print(f"(N,H,E) = {(N, H, E)} {loss}: largest distance between four starts {spread:.3e}")
     assert spread <= 1e-6, spread
     assert LR.loss_grad(pts[0], X, T, loss, L2)[0] < LR.loss_grad(np.zeros(H + 1), X, T, loss, L2)[0]
-
-
-class _HostTensor:
-    """What LteFit.state_dict asks of a tensor: shape and .cpu().numpy()."""
-
-    def __init__(self, a):
-        self.a, self.shape = a, a.shape
-
-    def cpu(self):
-        return self
-
-    def numpy(self):
-        return self.a
 
 
 def _host_fit(pkg, H):

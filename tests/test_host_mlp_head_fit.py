@@ -15,6 +15,7 @@ import pytest
 from . import headfit_ref as HR
 from . import mlp_headfit_ref as MR
 from .conftest import ROOT
+from .fit_util import _HostTensor
 
 NAMES = ("ee_mlp_head_fit", "ee_mlp_head_fit_workspace_bytes", "ee_debug_mlp_head_lossgrad")
 TWO_LAYER_RAMP = dict(exits=[1, 2, 4], encoder_layer_strategy="ramp", exit_head_num_layers=2)
@@ -140,19 +141,6 @@ def test_workspace_grows_with_every_dimension_and_holds_the_controller_vectors(p
     stated = 8 * E * MR.param_count(H, K) * (5 + 2 * M) + 8 * E * N * (H + K + 1)
     got = lib.ee_mlp_head_fit_workspace_bytes(E, N, H, K, M)
     assert stated <= got <= stated + 2048 * E, (got, stated)
-
-
-class _HostTensor:
-    """What MlpHeadFit.state_dict asks of a tensor: shape and .cpu().numpy()."""
-
-    def __init__(self, a):
-        self.a, self.shape = a, a.shape
-
-    def cpu(self):
-        return self
-
-    def numpy(self):
-        return self.a
 
 
 def _host_fit(pkg, E, K, H):
