@@ -875,6 +875,43 @@ int ee_debug_ln_rows(const float* src, float* dst, const int32_t* row_src, const
                      const float* pre_bias, const void* pre_resid, const int32_t* pre_resid_rows, float pre_resid_inv, int32_t* err_flag_out,
                      void* stream);
 
+/* Unit-test hook of the X-space CLS probe (csrc/xprobe.hip), the counterpart of ee_debug_attention: the three kernels of launch_xprobe on
+ * caller-provided DEVICE buffers, fed as layer_probe() of the forward feeds them; no handle.
+ *   The stage-0 batch the pair index is built from: n_orig documents, orig_doc_off int32 [n_orig + 1] (first entry 0), and per row pos, x0,
+ *     y1, masked (int32) with the meaning and ranges of ee_debug_attention.
+ *   The stage the probe runs on: n_docs documents (0 allowed), max_docs >= max(n_docs, 1) sizes the grids and the scratch as the forward's
+ *     batch size does; doc_off int32 [n_docs + 1] (first entry 0; the context row of document d is row doc_off[d] of ctx), doc_orig [n_docs]
+ *     the original document (pair-index slab; equal length required), x_phys [n_docs] the first row of the document in xs.
+ *   xs     split-f16 rows [x_rows][H] scaled by 16 (64-byte groups [hi 16 f16 | lo 16 f16]): the LayerNorm rows
+ *   qc     f32 [n_docs][H]: Q of the CLS rows, already divided by sqrt(d);  wk, wv f32 [H][H] (rows = outputs), bk, bv f32 [H]; wv is split here
+ *          with ee_finalize's per-tensor power-of-two scale
+ *   w1, wx, wy   f32 [heads][bins1], [heads][bins2], [heads][bins2]
+ *   index_form   0: the 32-bit pair index (launch_pair_index); 1: the query-block-0 output of the 16-bit form, which only the diagnostic
+ *                library builds -- the release library refuses it
+ *   cus          0: the device's CU count, else the num_cus handed to launch_xprobe (the probe's grid is min(max_docs, cus) workgroups)
+ *   ctx          out, split-f16 rows [ctx_rows][H] scaled by 64: row doc_off[d] of every stage document is written, every other row keeps its bytes
+ *   u_out [n_docs][heads][H], s0_out [n_docs][heads][2] (q . b_k, plane scale of u), cvec_out [n_docs][heads][H] f32, order_out int32
+ *                [n_docs] (documents by falling length, ties by rising index): copies of the intermediates, each may be NULL
+ *   err_flag_out host int32: the kernels' error word (16 = a context value left the range of the split planes)
+ * The probe's scratch is filled with a non-zero byte pattern first, as a workspace that is not zeroed between forwards may hold anything.
+ * Refused, not launched: what xprobe_supports() refuses (anything but 12 heads x 768 and 16 x 1024, more than 255 bins, a longest document
+ * whose LDS layout exceeds 160 KB), a stage document whose length differs from its original's, rows outside xs or ctx, integers outside
+ * their ranges.  Synchronises the stream. */
+typedef struct ee_debug_xprobe_args {
+    int32_t n_orig;
+    const int32_t *orig_doc_off, *pos, *x0, *y1, *masked;
+    int32_t n_docs, max_docs;
+    const int32_t *doc_off, *doc_orig, *x_phys;
+    const void* xs;
+    int32_t x_rows, ctx_rows;
+    const float *qc, *wk, *bk, *bv, *wv, *w1, *wx, *wy;
+    int32_t H, heads, bins1, bins2, max_rel_pos, max_rel_2d_pos, max_pos, max_coord, index_form, cus;
+    void* ctx;
+    float *u_out, *s0_out, *cvec_out;
+    int32_t* order_out;
+} ee_debug_xprobe_args;
+int ee_debug_xprobe(const ee_debug_xprobe_args* args, int32_t* err_flag_out, void* stream);
+
 /* Diagnostic of the two-heads-per-item attention kernel (attention_pair.hip): with MMEE_ATTN_STAMPS=1 in the environment the
  * launches run a build with in-kernel s_memtime stamps; this call synchronises, copies the eight phase sums (shader cycles summed over
  * waves: 0 wait for the tile's LDS-DMA, 1 DMA issue, 2 bias gathers, 3 Q K^T MFMAs, 4 / 5 softmax + P V of head A / B, 6 item prologue,

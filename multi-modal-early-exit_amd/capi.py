@@ -83,6 +83,15 @@ class DebugEmbedArgs(C.Structure):
                                       "pooled_text", "pooled_vis", "pooled_cat")])
 
 
+class DebugXProbeArgs(C.Structure):
+    """ee_debug_xprobe_args of include/mmee.h: device pointers (or None) and sizes."""
+    _fields_ = ([("n_orig", _i32)] + [(n, _vp) for n in ("orig_doc_off", "pos", "x0", "y1", "masked")]
+                + [(n, _i32) for n in ("n_docs", "max_docs")] + [(n, _vp) for n in ("doc_off", "doc_orig", "x_phys", "xs")]
+                + [(n, _i32) for n in ("x_rows", "ctx_rows")] + [(n, _vp) for n in ("qc", "wk", "bk", "bv", "wv", "w1", "wx", "wy")]
+                + [(n, _i32) for n in ("H", "heads", "bins1", "bins2", "max_rel_pos", "max_rel_2d_pos", "max_pos", "max_coord", "index_form", "cus")]
+                + [(n, _vp) for n in ("ctx", "u_out", "s0_out", "cvec_out", "order_out")])
+
+
 SYMBOLS = {
     "ee_create": (C.c_int, [C.POINTER(EEConfig), C.POINTER(_vp)]),
     "ee_destroy": (C.c_int, [_vp]),
@@ -141,6 +150,7 @@ SYMBOLS = {
     "ee_debug_embed": (C.c_int, [C.POINTER(DebugEmbedArgs), C.POINTER(_i32), _vp]),
     "ee_debug_ln_rows": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, C.c_float, _vp, C.c_float, _i32, C.c_size_t, _vp, _vp, _vp, C.c_float,
                                    C.POINTER(_i32), _vp]),
+    "ee_debug_xprobe": (C.c_int, [C.POINTER(DebugXProbeArgs), C.POINTER(_i32), _vp]),
     "ee_temperature_fit": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ee_head_fit": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _vp]),

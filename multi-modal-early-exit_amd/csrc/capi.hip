@@ -398,12 +398,7 @@ int build_split(ee_handle* h, const float* w, int N, int K, float** out, float* 
     float mx = 0.f;
     HIP_OK(h, hipMemcpy(&mx, h->absmax_dev, sizeof(float), hipMemcpyDeviceToHost));
     if (!(mx < 3.0e38f)) return fail(h, "ee_finalize: a weight tensor holds inf/nan");
-    int e = 8;
-    if (mx > 0.f) {
-        int ex = 0;
-        (void)std::frexp(mx, &ex);            // mx = m * 2^ex, m in [0.5, 1)
-        e = std::min(8, 13 - ex);
-    }
+    const int e = split_weight_exponent(mx);
     const float scale = std::ldexp(1.0f, e);
     *inv = std::ldexp(1.0f, -e);
     mmee::launch_split_rows(w, *out, nullptr, N, N, K, scale, h->num_cus, nullptr);

@@ -4,8 +4,11 @@
 //   capi_forward.hip  the forward schedule (Forward, ee_forward) and its captured-graph form (ee_graph_*)
 //   capi_query.hip    what reads the last forward back or arms the next one (ee_profile*, ee_stream_next, ee_last_*, ee_suggest_probe_mask, ee_set_*)
 //   capi_tools.hip    entry points that never see a handle (clock stamps, policy sweeps, pack / unpack, image feed, ee_debug_*)
+//   capi_debug_rows.hip, capi_debug_xprobe.hip   the ee_debug_* hooks of the row kernels and of the X-space CLS probe
 //   capi_fit.hip      the device fits, no handle either (ee_head_fit, ee_mlp_head_fit, ee_lte_*, ee_debug_*_lossgrad)
 #pragma once
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <map>
 #include <string>
@@ -216,6 +219,19 @@ inline bool have_device(const char* who) {
     fail(nullptr, "%s: no HIP device", who);
     return false;
 }
+
+// The per-tensor scale of a weight's split-f16 rows (build_split under ee_finalize; ee_debug_xprobe): 2^e with the e that puts max |w| in
+// [2^12, 2^13), capped at 8 (typical |w| ~ 0.02 then sits near 5, its lo plane well inside the f16 normal range); 8 for an all-zero tensor.
+inline int split_weight_exponent(float mx) {
+    if (!(mx > 0.f)) return 8;
+    int ex = 0;
+    (void)std::frexp(mx, &ex);            // mx = m * 2^ex, m in [0.5, 1)
+    return std::min(8, 13 - ex);
+}
+
+// Row metadata from the caller's integers by the expression of row_meta_kernel (make_row_meta): the ee_debug_* hooks that take rows as
+// pos / x0 / y1 / masked (capi_tools.hip holds the kernel)
+void launch_debug_row_meta(const int* pos, const int* x0, const int* y1, const int* masked, int rows, int coord_hi, RowMeta* meta, hipStream_t s);
 
 // Device scratch of one debug entry point: zeroed hipMalloc, freed on every way out of the scope.
 struct Scratch {

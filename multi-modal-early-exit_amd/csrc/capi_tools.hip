@@ -28,12 +28,20 @@ struct TempUpload {
     ~TempUpload() { if (dev) (void)hipFreeAsync(dev, s); }
 };
 
-// ee_debug_attention: the rows' metadata from the caller's integers, by the expression of row_meta_kernel (make_row_meta)
+// ee_debug_attention, ee_debug_xprobe: the rows' metadata from the caller's integers, by the expression of row_meta_kernel (make_row_meta)
 __global__ void debug_row_meta_kernel(const int* __restrict__ pos, const int* __restrict__ x0, const int* __restrict__ y1,
                                       const int* __restrict__ masked, int rows, int coord_hi, RowMeta* __restrict__ meta) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < rows) meta[i] = make_row_meta(pos[i], x0[i], y1[i], coord_hi, masked[i] == 0);
 }
+
+}  // namespace
+
+void mmee::capi::launch_debug_row_meta(const int* pos, const int* x0, const int* y1, const int* masked, int rows, int coord_hi, RowMeta* meta, hipStream_t s) {
+    hipLaunchKernelGGL(debug_row_meta_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, pos, x0, y1, masked, rows, coord_hi, meta);
+}
+
+namespace {
 
 // The common tail of the threshold scans: device check, the thresholds (n_up doubles: ee_rule_scan packs its patience behind them) to the
 // device, counts zeroed, one launch.  what: the upload's name in the error message.
@@ -588,7 +596,7 @@ int ee_debug_attention(const float* qkv, int32_t qkv_rows, const int32_t* doc_of
     int *err_flag = nullptr, *heads_q = nullptr, *doc_orig = nullptr, *doc_flags = nullptr;
     if (!sc.get(&meta, rows) || !sc.get(&counts, 1) || !sc.get(&err_flag, 1) || !sc.get(&heads_q, 128) || !sc.get(&doc_orig, n_docs) || !sc.get(&doc_flags, n_docs))
         return fail(nullptr, oom, who);
-    hipLaunchKernelGGL(debug_row_meta_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, pos, x0, y1, masked, rows, max_coord, meta);
+    launch_debug_row_meta(pos, x0, y1, masked, rows, max_coord, meta, s);
     const StageCounts hc{n_docs, rows, sum_sq};
     std::vector<int> iota(n_docs);
     for (int d = 0; d < n_docs; ++d) iota[d] = d;

@@ -65,24 +65,33 @@ __global__ __launch_bounds__(256) void xprobe_u_kernel(const XProbeArgs a) {
         q_s[g][t] = d < n_docs ? a.qc[(size_t)d * H + h * 64 + t] : 0.f;
     }
     __syncthreads();
+    // The 64 products of an element are summed in float64 and rounded to float32 ONCE.  An error of u is not an error of one score: the
+    // scores are x . u over H columns, so it is amplified by |x| sqrt(H); the float32 fma chain that stood here (64 roundings) put 2e-5 into
+    // the context of documents of two or three rows at |x| ~ 4, twice to four times what a float32 attention errs by
+    // (tests/test_gpu_xprobe.py, test_document_counts).  The products are exact in float64 (24 x 24 bits).
+    double accd[8][4];
+#pragma unroll
+    for (int g = 0; g < 8; ++g)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) accd[g][i] = 0.0;
+#pragma unroll 4
+    for (int t = 0; t < 64; ++t) {
+        const float* wr = a.wk + (size_t)(h * 64 + t) * H;
+        double w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[i] = tid + 256 * i < H ? (double)wr[tid + 256 * i] : 0.0;
+#pragma unroll
+        for (int g = 0; g < 8; ++g) {
+            const double qv = (double)q_s[g][t];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) accd[g][i] = fma(qv, w[i], accd[g][i]);
+        }
+    }
     float acc[8][4];
 #pragma unroll
     for (int g = 0; g < 8; ++g)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) acc[g][i] = 0.f;
-#pragma unroll 8
-    for (int t = 0; t < 64; ++t) {
-        const float* wr = a.wk + (size_t)(h * 64 + t) * H;
-        float w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w[i] = tid + 256 * i < H ? wr[tid + 256 * i] : 0.f;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) {
-            const float qv = q_s[g][t];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[g][i] = fmaf(qv, w[i], acc[g][i]);
-        }
-    }
+        for (int i = 0; i < 4; ++i) acc[g][i] = (float)accd[g][i];
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
         const int d = d0 + g;
@@ -256,17 +265,19 @@ __global__ __launch_bounds__(XP_THREADS) void xprobe_attn_kernel(const XProbeArg
             // partial scores of the wave's three k-steps
             {
                 const char* pa = tile + m * ROWB;
-                f32x4 ps = {0.f, 0.f, 0.f, 0.f};
+                // the cross terms (2^-11 of hi x hi) in an accumulator of their own: a score of 30 carries an ulp of 2e-6, and every rounding
+                // of the running sum at that magnitude shows in the softmax of a document of a few rows (tests/test_gpu_xprobe.py)
+                f32x4 ps = {0.f, 0.f, 0.f, 0.f}, psx = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int i = 0; i < KSW; ++i) {
                     const int c = 8 * (KSW * wave + i) + 4 * (kq >> 1) + (kq & 1);     // 16-byte chunk of the hi plane; lo two chunks on
                     const f16x8 ah = *reinterpret_cast<const f16x8*>(pa + 16 * (c ^ swm));
                     const f16x8 al = *reinterpret_cast<const f16x8*>(pa + 16 * ((c + 2) ^ swm));
-                    ps = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[i], ps, 0, 0, 0);
-                    ps = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[i], ps, 0, 0, 0);
+                    psx = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[i], psx, 0, 0, 0);
+                    psx = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[i], psx, 0, 0, 0);
                     ps = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[i], ps, 0, 0, 0);
                 }
-                if (m < HEADS) part[(wave * 4 + kq) * HEADS + m] = ps;
+                if (m < HEADS) part[(wave * 4 + kq) * HEADS + m] = ps + psx;
             }
             __syncthreads();
             f32x4 sc = part[kq * HEADS + mh];
@@ -280,7 +291,7 @@ __global__ __launch_bounds__(XP_THREADS) void xprobe_attn_kernel(const XProbeArg
             for (int r = 0; r < 4; ++r) {
                 const int j = r0 + 4 * kq + r;
                 const float b1 = th[ib1[j]], bx = th[a.bins1 + 1 + ibx[j]], by = th[a.bins1 + 1 + a.bins2 + iby[j]];
-                const float v = (j < len && m < heads) ? sc[r] * inv + s0 + (b1 + (bx + by)) : kNegBig;
+                const float v = (j < len && m < heads) ? fmaf(sc[r], inv, s0 + (b1 + (bx + by))) : kNegBig;     // one rounding at the score's magnitude
                 sv[r] = v;
                 tmax = fmaxf(tmax, v);
             }
@@ -362,30 +373,46 @@ __global__ __launch_bounds__(256) void xprobe_v_kernel(const XProbeArgs a) {
     const char* wp = reinterpret_cast<const char*>(a.wv_s) + (size_t)(h * 64 + m) * H * 4 + (kq >> 1) * 64 + (kq & 1) * 16;
     const size_t wtile = (size_t)16 * H * 4;                       // 16 output rows further
     constexpr float kSc = 16.0f;                                   // = kSplitScaleX
-    f32x4 acc[4];
+    // Accumulation order.  Added one by one into ONE accumulator, each of the 3 H / 32 MFMAs rounds the running sum at ITS magnitude (72 / 96
+    // roundings of 2^-22 at |ctx| ~ 2 .. 4): documents of one to four rows, whose context is as large as a V row, missed the float64 rule of
+    // tests/test_gpu_xprobe.py by that alone (a one-row document: c is its row exactly, err 1.9e-6 against a tolerance of 1.7e-6).  So: the two
+    // cross terms (2^-11 of hi x hi) have an accumulator of their own, and hi x hi goes to four accumulators by k-step modulo 4, added pairwise at
+    // the end -- H / 128 roundings each at a quarter of the magnitude, then three.  The same MFMAs, sixteen more independent chains.
+    f32x4 acc[4][4], accx[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-    for (int ks = 0; ks < H / 32; ++ks) {
-        const f32x4 c0 = *reinterpret_cast<const f32x4*>(cp + 32 * ks), c1 = *reinterpret_cast<const f32x4*>(cp + 32 * ks + 4);
-        f16x8 ah, al;
+    for (int j = 0; j < 4; ++j) {
+        accx[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float v = (e < 4 ? c0[e] : c1[e - 4]) * kSc;
-            const _Float16 hi = (_Float16)v;
-            ah[e] = hi;
-            al[e] = (_Float16)(v - (float)hi);
-        }
+        for (int q = 0; q < 4; ++q) acc[q][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    static_assert((H / 32) % 4 == 0, "k-steps go to four accumulators in turn");
+    for (int ks0 = 0; ks0 < H / 32; ks0 += 4) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const f16x8 bh = *reinterpret_cast<const f16x8*>(wp + j * wtile + 128 * ks);
-            const f16x8 bl = *reinterpret_cast<const f16x8*>(wp + j * wtile + 128 * ks + 32);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[j], 0, 0, 0);
+        for (int q = 0; q < 4; ++q) {
+            const int ks = ks0 + q;
+            const f32x4 c0 = *reinterpret_cast<const f32x4*>(cp + 32 * ks), c1 = *reinterpret_cast<const f32x4*>(cp + 32 * ks + 4);
+            f16x8 ah, al;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float v = (e < 4 ? c0[e] : c1[e - 4]) * kSc;
+                const _Float16 hi = (_Float16)v;
+                ah[e] = hi;
+                al[e] = (_Float16)(v - (float)hi);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f16x8 bh = *reinterpret_cast<const f16x8*>(wp + j * wtile + 128 * ks);
+                const f16x8 bl = *reinterpret_cast<const f16x8*>(wp + j * wtile + 128 * ks + 32);
+                accx[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, accx[j], 0, 0, 0);
+                accx[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, accx[j], 0, 0, 0);
+                acc[q][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[q][j], 0, 0, 0);
+            }
         }
     }
-    // acc[j][r] <-> (document d0 + 4 kq + r, output 16 j + m): bias, then the split planes of the context row (one f16 per plane and lane:
+    f32x4 sum[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sum[j] = ((acc[0][j] + acc[1][j]) + (acc[2][j] + acc[3][j])) + accx[j];
+    // sum[j][r] <-> (document d0 + 4 kq + r, output 16 j + m): bias, then the split planes of the context row (one f16 per plane and lane:
     // 16 lanes write 32 contiguous bytes)
     const float inv = a.wv_inv / kSc;
     float amax = 0.f;
@@ -397,7 +424,7 @@ __global__ __launch_bounds__(256) void xprobe_v_kernel(const XProbeArgs a) {
         for (int r = 0; r < 4; ++r) {
             const int d = d0 + 4 * kq + r;
             if (d < n_docs) {
-                const float v = (acc[j][r] * inv + bias) * a.ctx_scale;
+                const float v = (sum[j][r] * inv + bias) * a.ctx_scale;
                 amax = fmaxf(amax, fabsf(v));
                 const float vc = fminf(fmaxf(v, -kSplitClamp), kSplitClamp);
                 const _Float16 hi = (_Float16)vc;
