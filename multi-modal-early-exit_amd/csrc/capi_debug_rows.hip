@@ -2,7 +2,7 @@
 // Each entry point makes the calls of the path's own launchers that capi_forward.hip makes (launch_prep; launch_embed_text,
 // launch_embed_visual, launch_pool_finish; launch_ln_rows), synchronises and hands the kernels' error word to a host int32.  No kernel is
 // defined here; what the launchers cannot take is refused, not launched.  tests/test_gpu_rows.py drives them against tests/rows_ref.py.
-#include "capi_internal.h"
+#include "capi_debug.h"
 
 using namespace mmee;
 using namespace mmee::capi;
@@ -26,11 +26,19 @@ int check_prep(const char* who, const void* input_ids, const void* bbox, int B, 
     return 0;
 }
 
-int finish(const char* who, hipStream_t s, const int* err_flag, int32_t* err_flag_out) {
-    const hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(nullptr, "%s: launch failed: %s", who, hipGetErrorString(e));
-    if (hipMemcpy(err_flag_out, err_flag, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of err_flag failed", who);
-    return launch_status(nullptr, who);
+// launch_prep's arguments from the caller's inputs and ranges (checked by check_prep) and the buffers it writes
+PrepArgs prep_args(const int64_t* input_ids, const int64_t* attention_mask, const int64_t* bbox, const int64_t* position_ids, const int64_t* token_type_ids,
+                   int B, int T, int G, int pad_id, int vocab, int max_2d, int max_pos, int type_vocab, int dense_rows, int* text_dst, int* emb_pos,
+                   int* ntext, int* doc_off, int* x_src, int* doc_orig, RowMeta* meta, StageCounts* counts, int* err_flag) {
+    PrepArgs pa{};
+    pa.input_ids = (const long long*)input_ids; pa.attention_mask = (const long long*)attention_mask; pa.bbox = (const long long*)bbox;
+    pa.position_ids = (const long long*)position_ids; pa.token_type_ids = (const long long*)token_type_ids;
+    pa.B = B; pa.T = T; pa.G = G; pa.Pv = G * G + 1;
+    pa.pad_id = pad_id; pa.vocab = vocab; pa.max_2d = max_2d; pa.max_pos = max_pos; pa.type_vocab = type_vocab;
+    pa.dense_rows = dense_rows ? 1 : 0;
+    pa.text_dst = text_dst; pa.emb_pos = emb_pos; pa.ntext = ntext; pa.doc_off = doc_off; pa.x_src = x_src; pa.doc_orig = doc_orig;
+    pa.meta = meta; pa.counts = counts; pa.err_flag = err_flag;
+    return pa;
 }
 
 }  // namespace
@@ -50,15 +58,10 @@ int ee_debug_prep(const int64_t* input_ids, const int64_t* attention_mask, const
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     Scratch sc;
     int* err_flag = nullptr;
-    if (!sc.get(&err_flag, 1)) return fail(nullptr, "%s: hipMalloc of the scratch failed", who);
-    PrepArgs pa{};
-    pa.input_ids = (const long long*)input_ids; pa.attention_mask = (const long long*)attention_mask; pa.bbox = (const long long*)bbox;
-    pa.position_ids = (const long long*)position_ids; pa.token_type_ids = (const long long*)token_type_ids;
-    pa.B = B; pa.T = T; pa.G = G; pa.Pv = G * G + 1;
-    pa.pad_id = pad_id; pa.vocab = vocab; pa.max_2d = max_2d; pa.max_pos = max_pos; pa.type_vocab = type_vocab;
-    pa.dense_rows = dense_rows ? 1 : 0;
-    pa.text_dst = text_dst; pa.emb_pos = emb_pos; pa.ntext = ntext; pa.doc_off = doc_off; pa.x_src = x_src; pa.doc_orig = doc_orig;
-    pa.meta = reinterpret_cast<RowMeta*>(meta); pa.counts = reinterpret_cast<StageCounts*>(counts); pa.err_flag = err_flag;
+    if (!sc.get(&err_flag, 1)) return fail(nullptr, kScratchFailed, who);
+    const PrepArgs pa = prep_args(input_ids, attention_mask, bbox, position_ids, token_type_ids, B, T, G, pad_id, vocab, max_2d, max_pos, type_vocab, dense_rows,
+                                  text_dst, emb_pos, ntext, doc_off, x_src, doc_orig, reinterpret_cast<RowMeta*>(meta),
+                                  reinterpret_cast<StageCounts*>(counts), err_flag);
     launch_prep(pa, s);
     return finish(who, s, err_flag, err_flag_out);
 }
@@ -90,15 +93,9 @@ int ee_debug_embed(const ee_debug_embed_args* a, int32_t* err_flag_out, void* st
     StageCounts* counts = nullptr;
     if (!sc.get(&text_dst, (size_t)B * T) || !sc.get(&emb_pos, (size_t)B * T) || !sc.get(&ntext, B) || !sc.get(&doc_off, (size_t)B + 1) ||
         !sc.get(&x_src, B) || !sc.get(&doc_orig, B) || !sc.get(&meta, rows) || !sc.get(&counts, 1) || !sc.get(&err_flag, 1))
-        return fail(nullptr, "%s: hipMalloc of the scratch failed", who);
-    PrepArgs pa{};
-    pa.input_ids = (const long long*)a->input_ids; pa.attention_mask = (const long long*)a->attention_mask; pa.bbox = (const long long*)a->bbox;
-    pa.position_ids = (const long long*)a->position_ids; pa.token_type_ids = (const long long*)a->token_type_ids;
-    pa.B = B; pa.T = T; pa.G = a->G; pa.Pv = Pv;
-    pa.pad_id = a->pad_id; pa.vocab = a->vocab; pa.max_2d = a->max_2d; pa.max_pos = a->max_pos; pa.type_vocab = a->type_vocab;
-    pa.dense_rows = a->dense_rows ? 1 : 0;
-    pa.text_dst = text_dst; pa.emb_pos = emb_pos; pa.ntext = ntext; pa.doc_off = doc_off; pa.x_src = x_src; pa.doc_orig = doc_orig;
-    pa.meta = meta; pa.counts = counts; pa.err_flag = err_flag;
+        return fail(nullptr, kScratchFailed, who);
+    const PrepArgs pa = prep_args(a->input_ids, a->attention_mask, a->bbox, a->position_ids, a->token_type_ids, B, T, a->G, a->pad_id, a->vocab, a->max_2d,
+                                  a->max_pos, a->type_vocab, a->dense_rows, text_dst, emb_pos, ntext, doc_off, x_src, doc_orig, meta, counts, err_flag);
     launch_prep(pa, s);
 
     const int tch = (T + 31) / 32, vch = (Pv + 31) / 32;
@@ -146,15 +143,13 @@ int ee_debug_ln_rows(const float* src, float* dst, const int32_t* row_src, const
     int n = 0;
     if (hipMemcpy(&n, n_rows, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of n_rows failed", who);
     if (n < 0 || n > max_rows) return fail(nullptr, "%s: n_rows = %d outside [0, max_rows = %d] (the buffers are sized by max_rows)", who, n, max_rows);
-    hipDeviceProp_t prop;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(nullptr, "%s: no device", who);
+    const int cus = device_cus(who);
+    if (!cus) return 1;
     Scratch sc;
     int* err_flag = nullptr;
-    if (!sc.get(&err_flag, 1)) return fail(nullptr, "%s: hipMalloc of the scratch failed", who);
-    launch_ln_rows(src, dst, row_src, n_rows, max_rows, H, gamma, beta, eps, prop.multiProcessorCount, s, dst_split, split_scale, err_flag, pre_parts,
-                   pre_stride, pre_bias, pre_resid, pre_resid_rows, pre_resid_inv);
+    if (!sc.get(&err_flag, 1)) return fail(nullptr, kScratchFailed, who);
+    launch_ln_rows(src, dst, row_src, n_rows, max_rows, H, gamma, beta, eps, cus, s, dst_split, split_scale, err_flag, pre_parts, pre_stride, pre_bias,
+                   pre_resid, pre_resid_rows, pre_resid_inv);
     return finish(who, s, err_flag, err_flag_out);
 }
 

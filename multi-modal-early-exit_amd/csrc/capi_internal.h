@@ -3,8 +3,9 @@
 //   capi.hip          the handle's error ring and allocator, and the loader (ee_create, ee_load_tensor, ee_finalize, ee_destroy)
 //   capi_forward.hip  the forward schedule (Forward, ee_forward) and its captured-graph form (ee_graph_*)
 //   capi_query.hip    what reads the last forward back or arms the next one (ee_profile*, ee_stream_next, ee_last_*, ee_suggest_probe_mask, ee_set_*)
-//   capi_tools.hip    entry points that never see a handle (clock stamps, policy sweeps, pack / unpack, image feed, ee_debug_*)
-//   capi_debug_rows.hip, capi_debug_xprobe.hip   the ee_debug_* hooks of the row kernels and of the X-space CLS probe
+//   capi_tools.hip    entry points that never see a handle (clock stamps, policy sweeps, pack / unpack, image feed, the GEMM micro-benchmarks)
+//   capi_debug_attention.hip, capi_debug_rows.hip, capi_debug_xprobe.hip   the ee_debug_* hooks of the attention kernels, of the row kernels and
+//                     of the X-space CLS probe; what only they share is in capi_debug.h
 //   capi_fit.hip      the device fits, no handle either (ee_head_fit, ee_mlp_head_fit, ee_lte_*, ee_debug_*_lossgrad)
 #pragma once
 #include <algorithm>
@@ -211,7 +212,7 @@ int dev_alloc(ee_handle* h, T** p, size_t count) {
     return 0;
 }
 
-// ---- shared by the handle-free entry points (capi_tools.hip, capi_fit.hip, capi_debug_rows.hip) ----
+// ---- shared by the handle-free entry points (capi_tools.hip, capi_fit.hip, capi_debug_*.hip) ----
 // false (and the error message of `who` set) when there is no HIP device
 inline bool have_device(const char* who) {
     int ndev = 0;
@@ -229,11 +230,7 @@ inline int split_weight_exponent(float mx) {
     return std::min(8, 13 - ex);
 }
 
-// Row metadata from the caller's integers by the expression of row_meta_kernel (make_row_meta): the ee_debug_* hooks that take rows as
-// pos / x0 / y1 / masked (capi_tools.hip holds the kernel)
-void launch_debug_row_meta(const int* pos, const int* x0, const int* y1, const int* masked, int rows, int coord_hi, RowMeta* meta, hipStream_t s);
-
-// Device scratch of one debug entry point: zeroed hipMalloc, freed on every way out of the scope.
+// Device scratch of one entry point (the ee_debug_* hooks, ee_lte_targets): zeroed hipMalloc, freed on every way out of the scope.
 struct Scratch {
     std::vector<void*> ptrs;
     Scratch() = default;

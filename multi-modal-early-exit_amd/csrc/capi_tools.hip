@@ -1,12 +1,13 @@
 // Entry points of libmmee_hip.so that never see a handle: bucket LUT, shader-clock stamps, policy / patience / threshold sweeps, temperature
-// fit, the evaluation report (ee_exit_metrics), result packing, the device-side input feed, and the ee_debug_* hooks that run one kernel on
-// caller-provided buffers.  The L-BFGS fits are in capi_fit.hip.
+// fit, the evaluation report (ee_exit_metrics), result packing, the device-side input feed, and the GEMM micro-benchmark hooks (ee_debug_gemm,
+// ee_debug_gemm_split, ee_debug_attn_stamps).  The L-BFGS fits are in capi_fit.hip, the hooks that run one kernel of the path alone for its
+// float64 test in capi_debug_*.hip.
 #include <math.h>
 #include <string.h>
 
 #include <vector>
 
-#include "capi_internal.h"
+#include "capi_debug.h"
 
 using namespace mmee;
 using namespace mmee::capi;
@@ -27,21 +28,6 @@ struct TempUpload {
     TempUpload(const TempUpload&) = delete;
     ~TempUpload() { if (dev) (void)hipFreeAsync(dev, s); }
 };
-
-// ee_debug_attention, ee_debug_xprobe: the rows' metadata from the caller's integers, by the expression of row_meta_kernel (make_row_meta)
-__global__ void debug_row_meta_kernel(const int* __restrict__ pos, const int* __restrict__ x0, const int* __restrict__ y1,
-                                      const int* __restrict__ masked, int rows, int coord_hi, RowMeta* __restrict__ meta) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < rows) meta[i] = make_row_meta(pos[i], x0[i], y1[i], coord_hi, masked[i] == 0);
-}
-
-}  // namespace
-
-void mmee::capi::launch_debug_row_meta(const int* pos, const int* x0, const int* y1, const int* masked, int rows, int coord_hi, RowMeta* meta, hipStream_t s) {
-    hipLaunchKernelGGL(debug_row_meta_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, pos, x0, y1, masked, rows, coord_hi, meta);
-}
-
-namespace {
 
 // The common tail of the threshold scans: device check, the thresholds (n_up doubles: ee_rule_scan packs its patience behind them) to the
 // device, counts zeroed, one launch.  what: the upload's name in the error message.
@@ -417,10 +403,8 @@ int ee_collate_pad(const int64_t* ids, const int64_t* boxes, const int64_t* offs
 int ee_debug_gemm(const float* A, const float* W, const float* bias, const float* resid, float* Cout, int32_t M, int32_t N,
                   int32_t K, int32_t epi, int32_t wgs_per_cu, const int32_t* row_src, uint64_t* clk_probe, void* stream) {
     if (!A || !W || !Cout || M < 1 || N % 128 || K % 32 || epi < 0 || (epi & 15) > 3) return fail(nullptr, "ee_debug_gemm: bad argument");
-    hipDeviceProp_t prop;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(nullptr, "ee_debug_gemm: no device");
+    const int cus = device_cus("ee_debug_gemm");
+    if (!cus) return 1;
     GemmArgs g{};
     g.A = A; g.lda = K; g.W = W; g.bias = bias; g.C = Cout; g.ldc = N; g.resid = resid; g.ldr = N; g.m_static = M; g.N = N; g.K = K;
     g.scale = 1.f;
@@ -440,10 +424,10 @@ int ee_debug_gemm(const float* A, const float* W, const float* bias, const float
     g.resid_row_src = row_src;
     if (epi == EPI_RESID && !resid) return fail(nullptr, "ee_debug_gemm: residual epilogue without a residual");
     if (wgs_per_cu < 0) {   // diagnostic: stamped build, |wgs_per_cu| workgroups per CU, 8 uint64 per workgroup in clk_probe
-        launch_gemm_f32_stamped(g, epi, -wgs_per_cu * prop.multiProcessorCount, reinterpret_cast<hipStream_t>(stream));
+        launch_gemm_f32_stamped(g, epi, -wgs_per_cu * cus, reinterpret_cast<hipStream_t>(stream));
     } else {
         set_gemm_wgs_per_cu(wgs_per_cu);
-        launch_gemm_f32(g, epi, AMODE_ROWS, M, prop.multiProcessorCount, reinterpret_cast<hipStream_t>(stream));
+        launch_gemm_f32(g, epi, AMODE_ROWS, M, cus, reinterpret_cast<hipStream_t>(stream));
         set_gemm_wgs_per_cu(0);
     }
     return launch_status(nullptr, "ee_debug_gemm");
@@ -470,10 +454,8 @@ int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const
         return fail(nullptr, "ee_debug_gemm_split: bad argument (N %% 256, K %% 32)");
     if (epi == EPI_RESID && !resid) return fail(nullptr, "ee_debug_gemm_split: residual epilogue without a residual");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipDeviceProp_t prop;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(nullptr, "ee_debug_gemm_split: no device");
+    const int cus = device_cus("ee_debug_gemm_split");
+    if (!cus) return 1;
     float *As = nullptr, *Ws = nullptr;
     int* heads = nullptr;
     if (hipMalloc((void**)&As, (size_t)rows_A * K * 4) != hipSuccess || hipMalloc((void**)&Ws, (size_t)N * K * 4) != hipSuccess ||
@@ -481,8 +463,8 @@ int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const
         (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads);
         return fail(nullptr, "ee_debug_gemm_split: hipMalloc failed");
     }
-    mmee::launch_split_rows(A, As, nullptr, rows_A, rows_A, K, a_scale, prop.multiProcessorCount, s);
-    mmee::launch_split_rows(W, Ws, nullptr, N, N, K, w_scale, prop.multiProcessorCount, s);
+    mmee::launch_split_rows(A, As, nullptr, rows_A, rows_A, K, a_scale, cus, s);
+    mmee::launch_split_rows(W, Ws, nullptr, N, N, K, w_scale, cus, s);
     GemmArgs g{};
     g.A = As; g.lda = K; g.W = Ws; g.bias = bias; g.C = Cout; g.ldc = N; g.resid = resid; g.ldr = N; g.m_static = M; g.N = N; g.K = K;
     g.scale = 1.f; g.alpha = 1.0f / (a_scale * w_scale); g.out_split = out_split ? 1 : 0; g.out_scale = out_scale;
@@ -490,7 +472,7 @@ int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const
     // diagnostic builds (any dbg bit; bit 256 = "diagnostic build, nothing removed") report the shader clock they ran at:
     // ms_out[1] = GHz averaged over the workgroups of the last launch
     unsigned long long* clk = nullptr;
-    const int n_clk = 2 * 2 * prop.multiProcessorCount;
+    const int n_clk = 2 * 2 * cus;
     if (dbg && ms_out) {
         if (hipMalloc((void**)&clk, n_clk * 8) == hipSuccess) (void)hipMemsetAsync(clk, 0, n_clk * 8, s);
         g.clk_probe = clk;
@@ -499,11 +481,11 @@ int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const
     (void)hipEventCreate(&e0);
     (void)hipEventCreate(&e1);
     (void)hipMemsetAsync(heads, 0, 512, s);
-    launch_gemm_split(g, epi, M, prop.multiProcessorCount, s);          // first launch untimed (code object load)
+    launch_gemm_split(g, epi, M, cus, s);          // first launch untimed (code object load)
     (void)hipEventRecord(e0, s);
     for (int i = 1; i < iters; ++i) {
         (void)hipMemsetAsync(heads, 0, 512, s);
-        launch_gemm_split(g, epi, M, prop.multiProcessorCount, s);
+        launch_gemm_split(g, epi, M, cus, s);
     }
     (void)hipEventRecord(e1, s);
     const hipError_t err = hipStreamSynchronize(s);
@@ -525,135 +507,6 @@ int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const
     (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads);
     if (err != hipSuccess || hipGetLastError() != hipSuccess) return fail(nullptr, "ee_debug_gemm_split: launch failed: %s", hipGetErrorString(err));
     return 0;
-}
-
-int ee_debug_attention(const float* qkv, int32_t qkv_rows, const int32_t* doc_off, int32_t n_docs, const int32_t* qkv_doc_off, const int32_t* pos,
-                       const int32_t* x0, const int32_t* y1, const int32_t* masked, const float* w1, const float* wx, const float* wy, int32_t heads,
-                       int32_t bins1, int32_t bins2, int32_t max_rel_pos, int32_t max_rel_2d_pos, int32_t max_pos, int32_t max_coord, int32_t kernel,
-                       int32_t use_queue, int32_t q_limit, int32_t terms, void* ctx, int32_t* err_flag_out, void* stream) {
-    const char* who = "ee_debug_attention";
-    const bool f32k = kernel == MMEE_ATTN_KERNEL_F32, pairk = kernel == MMEE_ATTN_KERNEL_PAIR, idxk = kernel == MMEE_ATTN_KERNEL_IDX,
-               plaink = kernel == MMEE_ATTN_KERNEL_IDX_NOBIAS;
-    if (!f32k && !pairk && !idxk && !plaink) return fail(nullptr, "%s: kernel %d is none of MMEE_ATTN_KERNEL_F32, _PAIR, _IDX, _IDX_NOBIAS", who, kernel);
-    if (!qkv || !doc_off || !pos || !x0 || !y1 || !masked || !ctx || !err_flag_out || n_docs < 1 || heads < 1 || heads > 64 || qkv_rows < 1 ||
-        q_limit < 0 || max_pos < 0 || max_pos > 4095 || max_coord < 0 || max_coord > 65535)
-        return fail(nullptr, "%s: bad argument (pointers not NULL, n_docs >= 1, 1 <= heads <= 64, q_limit >= 0, max_pos <= 4095, max_coord <= 65535)", who);
-    if (!plaink && (!w1 || !wx || !wy || bins1 < 4 || bins1 > 256 || bins2 < 4 || bins2 > 256 || max_rel_pos < 1 || max_rel_2d_pos < 1))
-        return fail(nullptr, "%s: the bias needs w1 / wx / wy, 4 <= bins <= 256 and max_rel_pos, max_rel_2d_pos >= 1", who);
-    if (terms != 3 && !(terms == 1 && idxk)) return fail(nullptr, "%s: terms is 3, or 1 for MMEE_ATTN_KERNEL_IDX (the one-term mode is built for that kernel only)", who);
-    if (f32k && (q_limit > 0 || qkv_doc_off)) return fail(nullptr, "%s: attention_f32 takes neither q_limit nor qkv_doc_off (probe-first layers are split-precision)", who);
-    if (!have_device(who)) return 1;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipDeviceProp_t prop;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(nullptr, "%s: no device", who);
-    const int cus = prop.multiProcessorCount, H = 64 * heads;
-
-    // ---- the documents: offsets, lengths, every row inside the buffers, every integer inside its range (host copies: this is a test hook) ----
-    std::vector<int> off(n_docs + 1), qoff;
-    if (hipMemcpy(off.data(), doc_off, sizeof(int) * (n_docs + 1), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of doc_off failed", who);
-    if (qkv_doc_off) {
-        qoff.resize(n_docs);
-        if (hipMemcpy(qoff.data(), qkv_doc_off, sizeof(int) * n_docs, hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of qkv_doc_off failed", who);
-    }
-    if (off[0] != 0) return fail(nullptr, "%s: doc_off[0] = %d, must be 0", who, off[0]);
-    int max_len = 0;
-    unsigned long long sum_sq = 0;
-    for (int d = 0; d < n_docs; ++d) {
-        const int len = off[d + 1] - off[d];
-        if (len < 1) return fail(nullptr, "%s: document %d has %d rows", who, d, len);
-        const int q = qkv_doc_off ? qoff[d] : off[d];
-        if (q < 0 || (long)q + len > qkv_rows) return fail(nullptr, "%s: the Q | K | V rows of document %d (%d .. %d) leave the %d rows of qkv", who, d, q, q + len, qkv_rows);
-        max_len = len > max_len ? len : max_len;
-        sum_sq += (unsigned long long)len * len;
-    }
-    const int rows = off[n_docs];
-    {
-        std::vector<int> hp(rows), hx(rows), hy(rows), hm(rows);
-        if (hipMemcpy(hp.data(), pos, sizeof(int) * rows, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hx.data(), x0, sizeof(int) * rows, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(hy.data(), y1, sizeof(int) * rows, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hm.data(), masked, sizeof(int) * rows, hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(nullptr, "%s: copy of the row integers failed", who);
-        for (int i = 0; i < rows; ++i) {
-            if (hp[i] < 0 || hp[i] > max_pos) return fail(nullptr, "%s: pos[%d] = %d outside [0, max_pos = %d]", who, i, hp[i], max_pos);
-            if (hx[i] < 0 || hx[i] > max_coord || hy[i] < 0 || hy[i] > max_coord)
-                return fail(nullptr, "%s: x0 / y1 of row %d = %d / %d outside [0, max_coord = %d]", who, i, hx[i], hy[i], max_coord);
-            if (plaink && hm[i] != 0) return fail(nullptr, "%s: row %d is masked, and the image-only form of attention_idx (no pair index) has no key mask", who, i);
-        }
-    }
-
-    // ---- the operands, by the path's own code ----
-    Scratch sc;
-    const char* oom = "%s: hipMalloc of the scratch failed";
-    AttnArgs at{};
-    at.c1 = max_pos; at.n1 = 2 * max_pos + 1; at.c2 = max_coord; at.n2 = 2 * max_coord + 1;
-    at.H = H; at.heads = heads; at.max_len = max_len; at.ld = 3 * H; at.ldc = H; at.ctx = static_cast<float*>(ctx);
-    at.doc_off = doc_off; at.qkv_doc_off = qkv_doc_off; at.q_limit = q_limit; at.terms = terms;
-    at.ctx_split = f32k ? 0 : 1; at.ctx_scale = kSplitScaleCtx; at.qkv_scale = kSplitScaleQKV;
-    at.w1 = w1; at.wx = wx; at.wy = wy; at.bins1 = bins1; at.bins2 = bins2; at.inv_sqrt_d = 0.125f;      // 1 / sqrt(64)
-    RowMeta* meta = nullptr;
-    StageCounts* counts = nullptr;
-    int *err_flag = nullptr, *heads_q = nullptr, *doc_orig = nullptr, *doc_flags = nullptr;
-    if (!sc.get(&meta, rows) || !sc.get(&counts, 1) || !sc.get(&err_flag, 1) || !sc.get(&heads_q, 128) || !sc.get(&doc_orig, n_docs) || !sc.get(&doc_flags, n_docs))
-        return fail(nullptr, oom, who);
-    launch_debug_row_meta(pos, x0, y1, masked, rows, max_coord, meta, s);
-    const StageCounts hc{n_docs, rows, sum_sq};
-    std::vector<int> iota(n_docs);
-    for (int d = 0; d < n_docs; ++d) iota[d] = d;
-    if (hipMemcpyAsync(counts, &hc, sizeof(hc), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(doc_orig, iota.data(), sizeof(int) * n_docs, hipMemcpyHostToDevice, s) != hipSuccess)
-        return fail(nullptr, "%s: host-to-device copy failed", who);
-    launch_doc_flags(meta, doc_off, n_docs, doc_flags, s);
-    at.meta = meta; at.counts = counts; at.err_flag = err_flag; at.doc_orig = doc_orig; at.doc_flags = doc_flags;
-    at.item_counter = use_queue ? heads_q : nullptr;      // 8 XCD-local counters x 16 ints, zeroed
-    unsigned char *lut1 = nullptr, *lut2 = nullptr;
-    std::vector<unsigned char> l1(at.n1), l2(at.n2);      // outlive the asynchronous copies below: the stream is synchronised before the return
-    if (!plaink) {
-        float *t1 = nullptr, *tx = nullptr, *ty = nullptr;
-        if (!sc.get(&lut1, (size_t)at.n1 + 4) || !sc.get(&lut2, (size_t)at.n2 + 4) || !sc.get(&t1, (size_t)heads * at.n1) ||
-            !sc.get(&tx, (size_t)heads * at.n2) || !sc.get(&ty, (size_t)heads * at.n2))
-            return fail(nullptr, oom, who);
-        bucket_lut_host(bins1, max_rel_pos, at.c1, l1.data());
-        bucket_lut_host(bins2, max_rel_2d_pos, at.c2, l2.data());
-        if (hipMemcpyAsync(lut1, l1.data(), at.n1, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(lut2, l2.data(), at.n2, hipMemcpyHostToDevice, s) != hipSuccess)
-            return fail(nullptr, "%s: host-to-device copy failed", who);
-        launch_build_value_tables(w1, wx, wy, lut1, lut2, heads, bins1, bins2, at.n1, at.n2, at.inv_sqrt_d, t1, tx, ty, s);
-        at.t1 = t1; at.tx = tx; at.ty = ty; at.lut1 = lut1;
-    }
-    if (f32k) {
-        at.qkv = qkv;
-        if (attention_f32_lds_bytes(at) > 160 * 1024) return fail(nullptr, "%s: the value tables of max_pos %d / max_coord %d do not fit attention_f32's LDS", who, max_pos, max_coord);
-        launch_attention_f32(at, n_docs, cus, s);
-    } else {
-        float* qkv_s = nullptr;
-        if (!sc.get(&qkv_s, (size_t)qkv_rows * 3 * H)) return fail(nullptr, oom, who);
-        launch_split_rows(qkv, qkv_s, nullptr, qkv_rows, qkv_rows, 3 * H, kSplitScaleQKV, cus, s, err_flag);
-        at.qkv = qkv_s;
-        if (idxk) {
-            at.idx_nb = (max_len + 31) / 32;
-            at.idx_doc_stride = (size_t)at.idx_nb * at.idx_nb * 1024;
-            unsigned* pair_idx = nullptr;
-            if (!sc.get(&pair_idx, (size_t)n_docs * at.idx_doc_stride)) return fail(nullptr, oom, who);
-            at.pair_idx = pair_idx;
-        }
-        if (pairk) {
-            if (!attention_pair_supports(at, max_rel_pos, max_rel_2d_pos))
-                return fail(nullptr, "%s: attention_pair holds Delta tables of distances <= 128 / 256 (got %d / %d)", who, max_rel_pos, max_rel_2d_pos);
-            launch_attention_pair(at, n_docs, cus, max_rel_pos, max_rel_2d_pos, s);
-        } else {
-            if (!attention_idx_supports(at)) return fail(nullptr, "%s: attention_idx holds bucket tables of <= 64 bins (got %d / %d)", who, bins1, bins2);
-            if (idxk) {
-                if ((size_t)max_len * sizeof(RowMeta) + (size_t)at.n1 + at.n2 + 32 > 64 * 1024)
-                    return fail(nullptr, "%s: the pair-index kernel stages max_len rows and both LUTs in 64 KB of LDS (max_len %d, max_pos %d, max_coord %d)", who, max_len, max_pos, max_coord);
-                launch_pair_index(meta, doc_off, n_docs, at.idx_nb, lut1, at.c1, at.n1, lut2, at.c2, at.n2, bins1, const_cast<unsigned*>(at.pair_idx), at.idx_doc_stride, max_len, s);
-            }
-            launch_attention_idx(at, n_docs, cus, s);
-        }
-    }
-    const hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(nullptr, "%s: launch failed: %s", who, hipGetErrorString(e));
-    if (hipMemcpy(err_flag_out, err_flag, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of err_flag failed", who);
-    return launch_status(nullptr, who);
 }
 
 }  // extern "C"

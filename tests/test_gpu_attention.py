@@ -17,6 +17,7 @@ import pytest
 
 from . import attn_ref as R
 from .conftest import report_measured
+from .hook_util import ERR_SPLIT_OVERFLOW, SENTINEL, _decode_split, _dev, _ptr, _stream, _torch
 
 pytestmark = pytest.mark.gpu
 
@@ -24,26 +25,8 @@ F32K, PAIR, IDX, NOBIAS = 0, 1, 2, 3                    # include/mmee.h MMEE_AT
 NAMES = {F32K: "f32", PAIR: "pair", IDX: "idx", NOBIAS: "idx_nobias"}
 SPLIT_KERNELS = [PAIR, IDX, NOBIAS]
 MASKING_KERNELS = [F32K, PAIR, IDX]                     # the image-only form of attention_idx has no key mask
-ERR_SPLIT_OVERFLOW = 16                                 # csrc/mmee_common.h kErrSplitOverflow
 GUARD = 8                                               # rows past the last one in every context buffer; they must keep SENTINEL's bits
-SENTINEL = 0x7FA5A5A5                                   # a NaN bit pattern no kernel writes
 kid = lambda k: NAMES[k]
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def _dev(a, dtype=None):
-    torch = _torch()
-    return torch.from_numpy(np.ascontiguousarray(a)).to(device="cuda", dtype=dtype)
-
-
-def _decode_split(rows_i32, N, scale):
-    torch = _torch()
-    h = rows_i32.view(torch.float16).view(rows_i32.shape[0], N // 16, 2, 16)       # 64-byte groups [hi 16 | lo 16]
-    return (h[:, :, 0].double() + h[:, :, 1].double()).reshape(rows_i32.shape[0], N) / scale
 
 
 def _launch(pkg, b, kernel, queue=1, q_limit=0, qkv=None, qkv_doc_off=None, terms=3, expect_err=0, **over):
@@ -56,15 +39,14 @@ def _launch(pkg, b, kernel, queue=1, q_limit=0, qkv=None, qkv_doc_off=None, term
     t_qoff = None if qkv_doc_off is None else _dev(qkv_doc_off, torch.int32)
     w = [None] * 3 if kernel == NOBIAS else [_dev(a, torch.float32) for a in (b.w1, b.wx, b.wy)]
     ctx = torch.full((rows + GUARD, H), SENTINEL, dtype=torch.int32, device="cuda")
-    p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
     err = C.c_int32(-1)
     a = dict(bins1=b.w1.shape[1], bins2=b.wx.shape[1], max_rel_pos=R.MAX_REL_POS, max_rel_2d_pos=R.MAX_REL_2D_POS, max_pos=b.max_pos,
              max_coord=R.MAX_COORD)
     a.update(over)
     lib = pkg.capi.load()
-    pkg.capi.check(lib.ee_debug_attention(p(t_qkv), t_qkv.shape[0], p(t[0]), b.n_docs, p(t_qoff), p(t[1]), p(t[2]), p(t[3]), p(t[4]), p(w[0]), p(w[1]),
-                                          p(w[2]), b.heads, a["bins1"], a["bins2"], a["max_rel_pos"], a["max_rel_2d_pos"], a["max_pos"], a["max_coord"],
-                                          kernel, queue, q_limit, terms, p(ctx), C.byref(err), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+    pkg.capi.check(lib.ee_debug_attention(_ptr(t_qkv), t_qkv.shape[0], _ptr(t[0]), b.n_docs, _ptr(t_qoff), *[_ptr(x) for x in t[1:] + w], b.heads, a["bins1"],
+                                          a["bins2"], a["max_rel_pos"], a["max_rel_2d_pos"], a["max_pos"], a["max_coord"], kernel, queue, q_limit, terms,
+                                          _ptr(ctx), C.byref(err), _stream()),
                    None, "ee_debug_attention")
     torch.cuda.synchronize()
     assert err.value == expect_err, f"err_flag {err.value}"

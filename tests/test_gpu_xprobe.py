@@ -30,19 +30,13 @@ import pytest
 from . import attn_ref as R
 from . import xprobe_ref as X
 from .conftest import report_measured
+from .hook_util import ERR_SPLIT_OVERFLOW, SENTINEL, _stream, _torch
 
 pytestmark = pytest.mark.gpu
 
 HEADS = [12, 16]
-ERR_SPLIT_OVERFLOW = 16                                 # csrc/mmee_common.h kErrSplitOverflow
 GUARD = 8                                               # rows past the last one in every output buffer; they must keep SENTINEL's bits
-SENTINEL = 0x7FA5A5A5                                   # a NaN bit pattern no kernel writes
 hid = lambda h: f"{h}x{64 * h}"
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def _dev(a, dtype):
@@ -80,7 +74,7 @@ def _launch(pkg, c, cus=0, index_form=0, expect_err=0, refused=False, **over):
     for k, v in vals.items():
         setattr(a, k, v)
     err = C.c_int32(-1)
-    rc = pkg.capi.load().ee_debug_xprobe(C.byref(a), C.byref(err), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    rc = pkg.capi.load().ee_debug_xprobe(C.byref(a), C.byref(err), _stream())
     torch.cuda.synchronize()
     if refused:
         assert rc != 0, "the hook accepted what it must refuse"

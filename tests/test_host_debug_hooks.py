@@ -1,0 +1,194 @@
+"""What the five stand-alone kernel hooks (ee_debug_attention, ee_debug_xprobe, ee_debug_prep, ee_debug_embed, ee_debug_ln_rows) refuse before
+they ask for a device: every refusal below is decided on the host from the arguments alone, so the message is asserted whole, on a machine
+without a GPU too.  The pointers are fake and never dereferenced: every call in this file is refused first."""
+import ctypes as C
+
+P = C.c_void_p(4096)
+
+
+def _refused(pkg, who, rc, text, what):
+    msg = pkg.capi.last_error()
+    assert rc != 0, (who, what)
+    assert msg == f"{who}: {text}", (what, msg)
+
+
+def test_attention_refusals(pkg):
+    lib, who = pkg.capi.load(), "ee_debug_attention"
+    err = C.c_int32(-1)
+
+    def call(**over):
+        a = dict(qkv=P, qkv_rows=100, doc_off=P, n_docs=2, qkv_doc_off=None, pos=P, x0=P, y1=P, masked=P, w1=P, wx=P, wy=P, heads=2, bins1=32, bins2=64,
+                 max_rel_pos=128, max_rel_2d_pos=256, max_pos=300, max_coord=1000, kernel=2, use_queue=1, q_limit=0, terms=3, ctx=P,
+                 err=C.byref(err))
+        a.update(over)
+        return lib.ee_debug_attention(*a.values(), None)
+
+    bad = "bad argument (pointers not NULL, n_docs >= 1, 1 <= heads <= 64, q_limit >= 0, max_pos <= 4095, max_coord <= 65535)"
+    bias = "the bias needs w1 / wx / wy, 4 <= bins <= 256 and max_rel_pos, max_rel_2d_pos >= 1"
+    terms = "terms is 3, or 1 for MMEE_ATTN_KERNEL_IDX (the one-term mode is built for that kernel only)"
+    f32 = "attention_f32 takes neither q_limit nor qkv_doc_off (probe-first layers are split-precision)"
+    cases = [
+        (dict(kernel=4), "kernel 4 is none of MMEE_ATTN_KERNEL_F32, _PAIR, _IDX, _IDX_NOBIAS"),
+        (dict(kernel=-1), "kernel -1 is none of MMEE_ATTN_KERNEL_F32, _PAIR, _IDX, _IDX_NOBIAS"),
+        (dict(kernel=4, qkv=None), "kernel 4 is none of MMEE_ATTN_KERNEL_F32, _PAIR, _IDX, _IDX_NOBIAS"),      # the kernel id is looked at first
+        (dict(qkv=None), bad), (dict(doc_off=None), bad), (dict(pos=None), bad), (dict(x0=None), bad), (dict(y1=None), bad), (dict(masked=None), bad),
+        (dict(ctx=None), bad), (dict(err=None), bad), (dict(n_docs=0), bad), (dict(heads=0), bad), (dict(heads=65), bad), (dict(qkv_rows=0), bad),
+        (dict(q_limit=-1), bad), (dict(max_pos=-1), bad), (dict(max_pos=4096), bad), (dict(max_coord=-1), bad), (dict(max_coord=65536), bad),
+        (dict(kernel=3, masked=None), bad),                                     # the image-only form too
+        (dict(w1=None), bias), (dict(kernel=0, wx=None), bias), (dict(kernel=1, wy=None), bias), (dict(bins1=3), bias), (dict(bins1=257), bias),
+        (dict(bins2=3), bias), (dict(bins2=257), bias), (dict(max_rel_pos=0), bias), (dict(max_rel_2d_pos=0), bias),
+        (dict(w1=None, terms=2), bias),                                         # the bias operands before terms
+        (dict(terms=2), terms), (dict(terms=0), terms), (dict(kernel=1, terms=1), terms), (dict(kernel=0, terms=1), terms),
+        (dict(kernel=3, terms=1, w1=None, wx=None, wy=None), terms),            # the image-only form needs no bias operands, and has no one-term mode
+        (dict(kernel=0, q_limit=32), f32), (dict(kernel=0, qkv_doc_off=P), f32),
+    ]
+    for over, text in cases:
+        _refused(pkg, who, call(**over), text, over)
+
+
+def _xprobe_args(pkg, **over):
+    a = pkg.capi.DebugXProbeArgs()
+    for name, kind in a._fields_:
+        if kind is C.c_void_p:
+            setattr(a, name, 4096)
+    vals = dict(n_orig=3, n_docs=2, max_docs=4, x_rows=100, ctx_rows=100, H=768, heads=12, bins1=32, bins2=64, max_rel_pos=128, max_rel_2d_pos=256,
+                max_pos=300, max_coord=1000, index_form=0, cus=0)
+    vals.update(over)
+    for k, v in vals.items():
+        setattr(a, k, v)
+    return a
+
+
+def test_xprobe_refusals(pkg):
+    lib, who = pkg.capi.load(), "ee_debug_xprobe"
+    err = C.c_int32(-1)
+    call = lambda **over: lib.ee_debug_xprobe(C.byref(_xprobe_args(pkg, **over)), C.byref(err), None)
+    _refused(pkg, who, lib.ee_debug_xprobe(None, C.byref(err), None), "args and err_flag_out must not be NULL", "args")
+    _refused(pkg, who, lib.ee_debug_xprobe(C.byref(_xprobe_args(pkg)), None, None), "args and err_flag_out must not be NULL", "err_flag_out")
+    null = "an input pointer or ctx is NULL (only u_out, s0_out, cvec_out and order_out may be)"
+    counts = "bad counts (n_orig >= 1, 0 <= n_docs <= max_docs, 1 <= max_docs <= 2^20, x_rows >= 1, ctx_rows >= 1)"
+    bins = "the bias needs 4 <= bins <= 256, max_rel_pos, max_rel_2d_pos >= 1, max_pos <= 4095, max_coord <= 65535"
+    cases = [(dict([(k, None)]), null) for k in ("orig_doc_off", "pos", "x0", "y1", "masked", "doc_off", "doc_orig", "x_phys", "xs", "qc", "wk", "bk", "bv", "wv",
+                                                  "w1", "wx", "wy", "ctx")]
+    cases += [
+        (dict(wk=None, n_orig=0), null),                                        # the pointers before the counts
+        (dict(n_orig=0), counts), (dict(n_docs=-1), counts), (dict(max_docs=0, n_docs=0), counts), (dict(n_docs=5), counts),
+        (dict(max_docs=(1 << 20) + 1), counts), (dict(x_rows=0), counts), (dict(ctx_rows=0), counts),
+        (dict(H=32), "hidden size 32 outside [64, 4096] or 12 heads outside [1, 64]"),
+        (dict(H=4160), "hidden size 4160 outside [64, 4096] or 12 heads outside [1, 64]"),
+        (dict(heads=0), "hidden size 768 outside [64, 4096] or 0 heads outside [1, 64]"),
+        (dict(heads=65), "hidden size 768 outside [64, 4096] or 65 heads outside [1, 64]"),
+        (dict(bins1=3), bins), (dict(bins1=257), bins), (dict(bins2=3), bins), (dict(bins2=257), bins), (dict(max_rel_pos=0), bins),
+        (dict(max_rel_2d_pos=0), bins), (dict(max_pos=-1), bins), (dict(max_pos=4096), bins), (dict(max_coord=-1), bins), (dict(max_coord=65536), bins),
+        (dict(index_form=2), "index_form 2 is neither 0 (32-bit pair index) nor 1 (query block 0 of the 16-bit form)"),
+        (dict(index_form=-1), "index_form -1 is neither 0 (32-bit pair index) nor 1 (query block 0 of the 16-bit form)"),
+        (dict(cus=-1), "cus -1 outside [0, 4096] (0: the device's count)"), (dict(cus=4097), "cus 4097 outside [0, 4096] (0: the device's count)"),
+        (dict(index_form=2, cus=-1), "index_form 2 is neither 0 (32-bit pair index) nor 1 (query block 0 of the 16-bit form)"),
+    ]
+    for over, text in cases:
+        _refused(pkg, who, call(**over), text, over)
+
+
+# what check_prep says for ee_debug_prep and ee_debug_embed alike: (changed arguments, text)
+PREP_CASES = [
+    (dict(input_ids=None), "input_ids and bbox must not be NULL"), (dict(bbox=None), "input_ids and bbox must not be NULL"),
+    (dict(B=0), "bad shape (B >= 1, T >= 1, 1 <= G <= 64, B (T + G G + 1) <= 2^30), got B 0, T 8, G 2"),
+    (dict(T=0), "bad shape (B >= 1, T >= 1, 1 <= G <= 64, B (T + G G + 1) <= 2^30), got B 2, T 0, G 2"),
+    (dict(G=0), "bad shape (B >= 1, T >= 1, 1 <= G <= 64, B (T + G G + 1) <= 2^30), got B 2, T 8, G 0"),
+    (dict(G=65), "bad shape (B >= 1, T >= 1, 1 <= G <= 64, B (T + G G + 1) <= 2^30), got B 2, T 8, G 65"),
+    (dict(B=1 << 20, T=1 << 10), "bad shape (B >= 1, T >= 1, 1 <= G <= 64, B (T + G G + 1) <= 2^30), got B 1048576, T 1024, G 2"),
+] + [(over, "bad range limits (vocab, max_2d, max_pos, type_vocab >= 1, 0 <= pad_id < max_pos)")
+     for over in (dict(vocab=0), dict(max_2d=0), dict(max_pos=0), dict(type_vocab=0), dict(pad_id=-1), dict(pad_id=10))]
+PREP_VALUES = dict(B=2, T=8, G=2, pad_id=1, vocab=100, max_2d=1024, max_pos=10, type_vocab=1, dense_rows=0)
+
+
+def test_prep_refusals(pkg):
+    lib, who = pkg.capi.load(), "ee_debug_prep"
+    err = C.c_int32(-1)
+    outputs = ("text_dst", "emb_pos", "ntext", "doc_off", "x_src", "doc_orig", "meta", "counts")
+
+    def call(**over):
+        a = dict(input_ids=P, attention_mask=P, bbox=P, position_ids=None, token_type_ids=None, **PREP_VALUES)
+        a.update({k: P for k in outputs}, err=C.byref(err))
+        a.update(over)
+        return lib.ee_debug_prep(*a.values(), None)
+
+    cases = PREP_CASES + [(dict([(k, None)]), "every output pointer must be given") for k in outputs + ("err",)]
+    cases.append((dict(bbox=None, meta=None), "input_ids and bbox must not be NULL"))       # the inputs before the outputs
+    for over, text in cases:
+        _refused(pkg, who, call(**over), text, over)
+
+
+def _embed_args(pkg, **over):
+    a = pkg.capi.DebugEmbedArgs()
+    optional = ("position_ids", "token_type_ids", "inputs_embeds", "Xs", "text_part", "vis_part", "cat_part", "pooled_text", "pooled_vis", "pooled_cat")
+    for name, kind in a._fields_:
+        if kind is C.c_void_p and name not in optional:
+            setattr(a, name, 4096)
+    vals = dict(PREP_VALUES, H=128, cs=24, ss=16, text_eps=1e-5, vis_eps=1e-6, eps2=1e-5, split_scale=0.0)
+    vals.update(over)
+    for k, v in vals.items():
+        setattr(a, k, v)
+    return a
+
+
+def test_embed_refusals(pkg):
+    lib, who = pkg.capi.load(), "ee_debug_embed"
+    err = C.c_int32(-1)
+    call = lambda **over: lib.ee_debug_embed(C.byref(_embed_args(pkg, **over)), C.byref(err), None)
+    _refused(pkg, who, lib.ee_debug_embed(None, C.byref(err), None), "args and err_flag_out must not be NULL", "args")
+    _refused(pkg, who, lib.ee_debug_embed(C.byref(_embed_args(pkg)), None, None), "args and err_flag_out must not be NULL", "err_flag_out")
+    table = "a table, LayerNorm vector or visual input is NULL (word may be NULL with inputs_embeds)"
+    one = "exactly one of X and Xs receives the rows"
+    pair = "a partial-sum buffer and its pooled output are given together or not at all"
+    split = dict(X=None, Xs=4096, H=256, cs=48, ss=32, split_scale=16.0)
+    cases = list(PREP_CASES) + [
+        (dict(H=192, cs=32, ss=32), "hidden size 192 is not a multiple of 128 in [128, 1024]"),
+        (dict(H=1152, cs=192, ss=192), "hidden size 1152 is not a multiple of 128 in [128, 1024]"),
+        (dict(H=0), "hidden size 0 is not a multiple of 128 in [128, 1024]"),
+        (dict(B=0, H=192), "bad shape (B >= 1, T >= 1, 1 <= G <= 64, B (T + G G + 1) <= 2^30), got B 0, T 8, G 2"),      # check_prep before check_hidden
+        (dict(cs=25), "4 coordinate_size + 2 shape_size = 132 is not the hidden size 128"),
+        (dict(cs=0, ss=64), "4 coordinate_size + 2 shape_size = 128 is not the hidden size 128"),        # the sum is right, a size is not
+        (dict(cs=32, ss=0), "4 coordinate_size + 2 shape_size = 128 is not the hidden size 128"),
+    ]
+    cases += [(dict([(k, None)]), table) for k in ("type", "pos", "xtab", "ytab", "htab", "wtab", "text_ln_g", "text_ln_b", "vis_ln_g", "vis_ln_b", "ln2_g",
+                                                   "ln2_b", "cls_token", "pos_embed", "vis_raw", "word")]
+    cases += [
+        (dict(Xs=4096), one), (dict(X=None), one),
+        (dict(X=None, Xs=4096, split_scale=16.0), "split rows need a hidden size that is a multiple of 256 (got 128)"),
+        (dict(split, H=384, cs=64, ss=64), "split rows need a hidden size that is a multiple of 256 (got 384)"),
+        (dict(split, split_scale=0.0), "split_scale must be positive"), (dict(split, split_scale=-1.0), "split_scale must be positive"),
+        (dict(split, split_scale=float("nan")), "split_scale must be positive"),
+        (dict(text_part=4096), pair), (dict(pooled_text=4096), pair), (dict(vis_part=4096), pair), (dict(pooled_vis=4096), pair),
+        (dict(cat_part=4096), pair), (dict(pooled_cat=4096), pair),
+    ]
+    for over, text in cases:
+        _refused(pkg, who, call(**over), text, over)
+
+
+def test_ln_rows_refusals(pkg):
+    lib, who = pkg.capi.load(), "ee_debug_ln_rows"
+    err = C.c_int32(-1)
+
+    def call(**over):
+        a = dict(src=P, dst=P, row_src=None, n_rows=P, max_rows=5, H=256, gamma=P, beta=P, eps=1e-5, dst_split=None, split_scale=0.0, pre_parts=0,
+                 pre_stride=0, pre_bias=None, pre_resid=None, pre_resid_rows=None, pre_resid_inv=0.0, err=C.byref(err))
+        a.update(over)
+        return lib.ee_debug_ln_rows(*a.values(), None)
+
+    null = "src, n_rows, gamma, beta, err_flag_out must not be NULL, max_rows >= 0"
+    need = "a bias or residual needs pre_parts >= 1"
+    cases = [
+        (dict(src=None), null), (dict(n_rows=None), null), (dict(gamma=None), null), (dict(beta=None), null), (dict(err=None), null), (dict(max_rows=-1), null),
+        (dict(H=192), "hidden size 192 is not a multiple of 128 in [128, 1024]"), (dict(H=1152), "hidden size 1152 is not a multiple of 128 in [128, 1024]"),
+        (dict(src=None, H=192), null),                                          # in the order of the entry point
+        (dict(dst=None), "neither dst nor dst_split is given"),
+        (dict(H=384, dst_split=P, split_scale=16.0), "split rows need a hidden size that is a multiple of 256 (got 384)"),
+        (dict(dst=None, dst_split=P, H=128, split_scale=16.0), "split rows need a hidden size that is a multiple of 256 (got 128)"),
+        (dict(dst_split=P), "split_scale must be positive"), (dict(dst_split=P, split_scale=-16.0), "split_scale must be positive"),
+        (dict(pre_parts=-1), "pre_parts -1 outside [0, 8]"), (dict(pre_parts=9), "pre_parts 9 outside [0, 8]"),
+        (dict(pre_bias=P), need), (dict(pre_resid=P), need), (dict(pre_resid_rows=P), need),
+        (dict(pre_parts=1, pre_resid_rows=P), "pre_resid_rows without pre_resid"),
+    ]
+    for over, text in cases:
+        _refused(pkg, who, call(**over), text, over)
