@@ -912,6 +912,83 @@ typedef struct ee_debug_xprobe_args {
 } ee_debug_xprobe_args;
 int ee_debug_xprobe(const ee_debug_xprobe_args* args, int32_t* err_flag_out, void* stream);
 
+/* Unit-test hooks of the exit stage (csrc/exit_stage.hip), the counterparts of ee_debug_attention: the path's own launchers on
+ * caller-provided DEVICE buffers; no handle.  Each synchronises the stream; these kernels have no error word.  Every buffer must be as
+ * large as the shapes say: the hooks check shapes and the index arrays they can read, not buffer sizes.
+ *
+ * ee_debug_head_out: one launch_head_out.  out[i][o] = <in[gather ? gather[i] : i], W[o]> + b[o] for i < *n_docs (a DEVICE word,
+ *   <= max_docs, which sizes the grid), o < Ko; in f32 [in_rows][ld], W f32 [Ko][H], b f32 [Ko].  With lte_out (double [n_docs]) the same
+ *   launch scores every document: sigmoid(<lte_in[lte_gather ? lte_gather[i] : i], lte_w> + lte_b[0]) in float64, lte_in [lte_rows][lte_ld]
+ *   f32 rows (lte_split_inv 0) or split-f16 rows (64-byte groups [hi 16 f16 | lo 16 f16], lte_split_inv = 1 / plane scale).  Refused: H
+ *   outside [4, 1024] or no multiple of 4, ld / lte_ld below H or no multiple of 4, Ko < 1, a gather entry outside its rows.
+ *
+ * ee_debug_exit_decide: one exit of one stage through launch_decide, and launch_compact_rows behind it when meta_old, meta_new and
+ *   row_src are given (all three or none).  mode: 0 threshold criterion, 1 patience, 2 LTE; rule: MMEE_RULE_*; criterion: MMEE_CRIT_*
+ *   (ignored under mode 1).  pol_logits f32 [n_docs][K]; head_logits f32 [n_docs][Kh] or NULL; lte_score double [n_docs] or NULL (an
+ *   exit without a score: nobody leaves).  thr, temp, patience: this exit's; by_pointer != 0 hands them to the kernel as a captured
+ *   graph's replay does, at [exit_index] of device vectors (the patience at [0] of its own).  The current stage: counts (16 bytes
+ *   {int32 n_docs, int32 n_rows, uint64 sum_len_sq}), doc_orig [n_docs] (slots in [0, B)), doc_off [n_docs + 1], x_phys [n_docs].
+ *   prev, run int32 [B]: the caller's per-document state by original slot, needed by mode 1 and by every rule but PLAIN; exit 0 does not
+ *   read it.  Outputs: the next stage n_counts, n_doc_orig, n_doc_off (one more entry than survivors), n_x_src, n_meta_src; out_exit
+ *   [B]; and, each or NULL, out_logits (B,K), out_conf (B), out_all_logits (E1,B,K), out_all_crit (E1,B), out_head_logits (E1,B,Kh),
+ *   out_head_crit (E1,B), written at exit_index.  Rows: meta_old / meta_new int32 (rows,4), row_src int32 (rows).  Refused: a (mode, rule)
+ *   pair launch_decide has no kernel for, K or Kh < 1, a stateful pair without prev / run, exit_index < 0, a document table that does not
+ *   start at 0 or holds an empty document, counts.n_rows != doc_off[n_docs], doc_orig outside [0, B).
+ *
+ * ee_debug_rows_out: which = 0, launch_gather_cls: out[doc_orig ? doc_orig[i] : i] = X[x_phys[i]] for i < *n_docs (DEVICE word, <=
+ *   max_docs); which = 1, launch_rows_to_padded: out (B, T + Pv, H), position p < T of document d = X row doc_off[d] + text_dst[d][p]
+ *   (zeros when text_dst[d][p] < 0), position T + v = X row doc_off[d] + ntext[d] + v; text_dst NULL (image-only): T = 0 and no ntext.
+ *   X [x_rows][H] f32 rows (split_inv 0) or split-f16 rows (split_inv = 1 / plane scale); out f32 [out_rows][H].  Refused: a row index
+ *   outside X or out. */
+typedef struct ee_debug_head_out_args {
+    const float* in;
+    int32_t in_rows, ld;
+    const int32_t* gather;
+    const float *W, *b;
+    int32_t H, Ko;
+    const int32_t* n_docs;
+    int32_t max_docs;
+    float* out;
+    const void* lte_in;
+    int32_t lte_rows, lte_ld;
+    const int32_t* lte_gather;
+    float lte_split_inv;
+    const float *lte_w, *lte_b;
+    double* lte_out;
+} ee_debug_head_out_args;
+typedef struct ee_debug_exit_decide_args {
+    int32_t mode, rule, criterion;
+    const float *pol_logits, *head_logits;
+    int32_t K, Kh;
+    const double* lte_score;
+    double thr, temp;
+    int32_t patience, by_pointer, exit_index, is_final, no_exit, B;
+    const void* counts;
+    const int32_t *doc_orig, *doc_off, *x_phys;
+    int32_t *prev, *run;
+    void* n_counts;
+    int32_t *n_doc_orig, *n_doc_off, *n_x_src, *n_meta_src;
+    float* out_logits;
+    int32_t* out_exit;
+    float *out_conf, *out_all_logits, *out_all_crit, *out_head_logits, *out_head_crit;
+    const int32_t* meta_old;
+    int32_t *meta_new, *row_src;
+} ee_debug_exit_decide_args;
+typedef struct ee_debug_rows_out_args {
+    int32_t which;
+    const void* X;
+    int32_t x_rows, H;
+    float split_inv;
+    const int32_t *x_phys, *doc_orig, *n_docs;
+    int32_t max_docs, B, T, Pv;
+    const int32_t *text_dst, *ntext, *doc_off;
+    float* out;
+    int32_t out_rows;
+} ee_debug_rows_out_args;
+int ee_debug_head_out(const ee_debug_head_out_args* args, void* stream);
+int ee_debug_exit_decide(const ee_debug_exit_decide_args* args, void* stream);
+int ee_debug_rows_out(const ee_debug_rows_out_args* args, void* stream);
+
 /* Diagnostic of the two-heads-per-item attention kernel (attention_pair.hip): with MMEE_ATTN_STAMPS=1 in the environment the
  * launches run a build with in-kernel s_memtime stamps; this call synchronises, copies the eight phase sums (shader cycles summed over
  * waves: 0 wait for the tile's LDS-DMA, 1 DMA issue, 2 bias gathers, 3 Q K^T MFMAs, 4 / 5 softmax + P V of head A / B, 6 item prologue,

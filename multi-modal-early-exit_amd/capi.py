@@ -92,6 +92,30 @@ class DebugXProbeArgs(C.Structure):
                 + [(n, _vp) for n in ("ctx", "u_out", "s0_out", "cvec_out", "order_out")])
 
 
+class DebugHeadOutArgs(C.Structure):
+    """ee_debug_head_out_args of include/mmee.h: device pointers (or None) and sizes."""
+    _fields_ = [("in_", _vp), ("in_rows", _i32), ("ld", _i32), ("gather", _vp), ("W", _vp), ("b", _vp), ("H", _i32), ("Ko", _i32), ("n_docs", _vp),
+                ("max_docs", _i32), ("out", _vp), ("lte_in", _vp), ("lte_rows", _i32), ("lte_ld", _i32), ("lte_gather", _vp),
+                ("lte_split_inv", C.c_float), ("lte_w", _vp), ("lte_b", _vp), ("lte_out", _vp)]
+
+
+class DebugExitDecideArgs(C.Structure):
+    """ee_debug_exit_decide_args of include/mmee.h: device pointers (or None), this exit's scalars and sizes."""
+    _fields_ = ([(n, _i32) for n in ("mode", "rule", "criterion")] + [(n, _vp) for n in ("pol_logits", "head_logits")]
+                + [(n, _i32) for n in ("K", "Kh")] + [("lte_score", _vp), ("thr", C.c_double), ("temp", C.c_double)]
+                + [(n, _i32) for n in ("patience", "by_pointer", "exit_index", "is_final", "no_exit", "B")]
+                + [(n, _vp) for n in ("counts", "doc_orig", "doc_off", "x_phys", "prev", "run", "n_counts", "n_doc_orig", "n_doc_off", "n_x_src",
+                                      "n_meta_src", "out_logits", "out_exit", "out_conf", "out_all_logits", "out_all_crit", "out_head_logits",
+                                      "out_head_crit", "meta_old", "meta_new", "row_src")])
+
+
+class DebugRowsOutArgs(C.Structure):
+    """ee_debug_rows_out_args of include/mmee.h: device pointers (or None) and sizes."""
+    _fields_ = ([("which", _i32), ("X", _vp), ("x_rows", _i32), ("H", _i32), ("split_inv", C.c_float)]
+                + [(n, _vp) for n in ("x_phys", "doc_orig", "n_docs")] + [(n, _i32) for n in ("max_docs", "B", "T", "Pv")]
+                + [(n, _vp) for n in ("text_dst", "ntext", "doc_off", "out")] + [("out_rows", _i32)])
+
+
 SYMBOLS = {
     "ee_create": (C.c_int, [C.POINTER(EEConfig), C.POINTER(_vp)]),
     "ee_destroy": (C.c_int, [_vp]),
@@ -151,6 +175,9 @@ SYMBOLS = {
     "ee_debug_ln_rows": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, C.c_float, _vp, C.c_float, _i32, C.c_size_t, _vp, _vp, _vp, C.c_float,
                                    C.POINTER(_i32), _vp]),
     "ee_debug_xprobe": (C.c_int, [C.POINTER(DebugXProbeArgs), C.POINTER(_i32), _vp]),
+    "ee_debug_head_out": (C.c_int, [C.POINTER(DebugHeadOutArgs), _vp]),
+    "ee_debug_exit_decide": (C.c_int, [C.POINTER(DebugExitDecideArgs), _vp]),
+    "ee_debug_rows_out": (C.c_int, [C.POINTER(DebugRowsOutArgs), _vp]),
     "ee_temperature_fit": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ee_head_fit": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _vp]),

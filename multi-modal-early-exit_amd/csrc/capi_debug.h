@@ -1,5 +1,5 @@
 // What the ee_debug_* hooks that run one kernel of the path on caller-provided device buffers share (capi_debug_attention.hip,
-// capi_debug_rows.hip, capi_debug_xprobe.hip; the two GEMM hooks of capi_tools.hip take the device query).  Host code with internal linkage:
+// capi_debug_rows.hip, capi_debug_xprobe.hip, capi_debug_exit.hip; the two GEMM hooks of capi_tools.hip take the device query).  Host code with internal linkage:
 // the library exports none of it.  What every hook words alike is worded here; the refusals of a document table keep each hook's own words.
 #pragma once
 #include "capi_internal.h"
@@ -94,11 +94,11 @@ int upload_bias_luts(const char* who, BiasLuts& b, Scratch& sc, int bins1, int m
     return 0;
 }
 
-// the tail of a hook: synchronise, the kernels' error word to the host, the launch status
+// the tail of a hook: synchronise, the kernels' error word to the host (err_flag null: the kernels have none), the launch status
 int finish(const char* who, hipStream_t s, const int* err_flag, int32_t* err_flag_out) {
     const hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(nullptr, "%s: launch failed: %s", who, hipGetErrorString(e));
-    if (hipMemcpy(err_flag_out, err_flag, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of err_flag failed", who);
+    if (err_flag && hipMemcpy(err_flag_out, err_flag, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of err_flag failed", who);
     return launch_status(nullptr, who);
 }
 

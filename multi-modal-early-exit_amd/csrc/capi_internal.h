@@ -4,8 +4,8 @@
 //   capi_forward.hip  the forward schedule (Forward, ee_forward) and its captured-graph form (ee_graph_*)
 //   capi_query.hip    what reads the last forward back or arms the next one (ee_profile*, ee_stream_next, ee_last_*, ee_suggest_probe_mask, ee_set_*)
 //   capi_tools.hip    entry points that never see a handle (clock stamps, policy sweeps, pack / unpack, image feed, the GEMM micro-benchmarks)
-//   capi_debug_attention.hip, capi_debug_rows.hip, capi_debug_xprobe.hip   the ee_debug_* hooks of the attention kernels, of the row kernels and
-//                     of the X-space CLS probe; what only they share is in capi_debug.h
+//   capi_debug_attention.hip, capi_debug_rows.hip, capi_debug_xprobe.hip, capi_debug_exit.hip   the ee_debug_* hooks of the attention kernels, of the
+//                     row kernels, of the X-space CLS probe and of the exit stage; what only they share is in capi_debug.h
 //   capi_fit.hip      the device fits, no handle either (ee_head_fit, ee_mlp_head_fit, ee_lte_*, ee_debug_*_lossgrad)
 #pragma once
 #include <algorithm>

@@ -1,4 +1,4 @@
-"""What the tests of the stand-alone kernel hooks (test_gpu_attention.py, test_gpu_rows.py, test_gpu_xprobe.py) share.  A plain module, not a
+"""What the tests of the stand-alone kernel hooks (test_gpu_attention.py, test_gpu_rows.py, test_gpu_xprobe.py, test_gpu_exit_stage.py) share.  A plain module, not a
 conftest: nothing here is a fixture or a hook of pytest."""
 import ctypes as C
 

@@ -1,5 +1,5 @@
-"""What the five stand-alone kernel hooks (ee_debug_attention, ee_debug_xprobe, ee_debug_prep, ee_debug_embed, ee_debug_ln_rows) refuse before
-they ask for a device: every refusal below is decided on the host from the arguments alone, so the message is asserted whole, on a machine
+"""What the eight stand-alone kernel hooks (ee_debug_attention, ee_debug_xprobe, ee_debug_prep, ee_debug_embed, ee_debug_ln_rows,
+ee_debug_head_out, ee_debug_exit_decide, ee_debug_rows_out) refuse before they ask for a device: every refusal below is decided on the host from the arguments alone, so the message is asserted whole, on a machine
 without a GPU too.  The pointers are fake and never dereferenced: every call in this file is refused first."""
 import ctypes as C
 
@@ -189,6 +189,116 @@ def test_ln_rows_refusals(pkg):
         (dict(pre_parts=-1), "pre_parts -1 outside [0, 8]"), (dict(pre_parts=9), "pre_parts 9 outside [0, 8]"),
         (dict(pre_bias=P), need), (dict(pre_resid=P), need), (dict(pre_resid_rows=P), need),
         (dict(pre_parts=1, pre_resid_rows=P), "pre_resid_rows without pre_resid"),
+    ]
+    for over, text in cases:
+        _refused(pkg, who, call(**over), text, over)
+
+
+def _struct(cls, optional, **vals):
+    a = cls()
+    for name, kind in a._fields_:
+        if kind is C.c_void_p and name not in optional:
+            setattr(a, name, 4096)
+    for k, v in vals.items():
+        setattr(a, k, v)
+    return a
+
+
+def test_head_out_refusals(pkg):
+    lib, who = pkg.capi.load(), "ee_debug_head_out"
+    lte_block = ("lte_in", "lte_gather", "lte_w", "lte_b", "lte_out")
+
+    def call(lte=False, **over):
+        vals = dict(in_rows=10, ld=128, H=128, Ko=2, max_docs=8, lte_rows=10, lte_ld=128, lte_split_inv=0.0)
+        vals.update(over)
+        return lib.ee_debug_head_out(C.byref(_struct(pkg.capi.DebugHeadOutArgs, () if lte else lte_block + ("gather",), **vals)), None)
+
+    _refused(pkg, who, lib.ee_debug_head_out(None, None), "args must not be NULL", "args")
+    null = "in, W, b, n_docs and out must not be NULL"
+    counts = "bad counts (in_rows >= 1, 1 <= max_docs <= 2^20)"
+    cases = [(dict([(k, None)]), null) for k in ("in_", "W", "b", "n_docs", "out")]
+    cases += [
+        (dict(W=None, H=3), null),                                              # the pointers before the sizes
+        (dict(H=0), "hidden size 0 is not a multiple of 4 in [4, 1024]"), (dict(H=126), "hidden size 126 is not a multiple of 4 in [4, 1024]"),
+        (dict(H=1028, ld=1028), "hidden size 1028 is not a multiple of 4 in [4, 1024]"),
+        (dict(ld=124), "ld 124 is below the hidden size 128 or no multiple of 4"), (dict(ld=130), "ld 130 is below the hidden size 128 or no multiple of 4"),
+        (dict(Ko=0), "Ko 0 is below 1"), (dict(Ko=-3), "Ko -3 is below 1"),
+        (dict(in_rows=0), counts), (dict(max_docs=0), counts), (dict(max_docs=(1 << 20) + 1), counts),
+        (dict(lte_w=4096), "the LTE block is given without lte_out"), (dict(lte_gather=4096), "the LTE block is given without lte_out"),
+        (dict(lte=True, lte_in=None), "lte_out needs lte_in, lte_w and lte_b"), (dict(lte=True, lte_b=None), "lte_out needs lte_in, lte_w and lte_b"),
+        (dict(lte=True, lte_ld=124), "lte_ld 124 is below the hidden size 128 or no multiple of 4"),
+        (dict(lte=True, lte_ld=134), "lte_ld 134 is below the hidden size 128 or no multiple of 4"),
+        (dict(lte=True, lte_rows=0), "lte_rows 0 is below 1"),
+        (dict(lte=True, lte_split_inv=-1.0), "lte_split_inv must be 0 (f32 rows) or positive"),
+        (dict(lte=True, lte_split_inv=float("nan")), "lte_split_inv must be 0 (f32 rows) or positive"),
+        (dict(lte=True, lte_split_inv=0.0625, H=136, ld=136, lte_ld=136), "split rows need a hidden size that is a multiple of 16 (got 136)"),
+    ]
+    for over, text in cases:
+        _refused(pkg, who, call(**over), text, over)
+
+
+def test_exit_decide_refusals(pkg):
+    lib, who = pkg.capi.load(), "ee_debug_exit_decide"
+    optional = ("head_logits", "lte_score", "prev", "run", "out_logits", "out_conf", "out_all_logits", "out_all_crit", "out_head_logits", "out_head_crit",
+                "meta_old", "meta_new", "row_src")
+
+    def call(**over):
+        vals = dict(mode=0, rule=0, criterion=0, K=4, Kh=2, thr=0.5, temp=1.0, patience=1, by_pointer=0, exit_index=0, is_final=0, no_exit=0, B=8)
+        vals.update(over)
+        return lib.ee_debug_exit_decide(C.byref(_struct(pkg.capi.DebugExitDecideArgs, optional, **vals)), None)
+
+    _refused(pkg, who, lib.ee_debug_exit_decide(None, None), "args must not be NULL", "args")
+    pair = ("launch_decide has no kernel for mode %d with rule %d (modes 0 threshold, 1 patience, 2 LTE; rules 0 plain, 1 streak, 2 either; patience "
+            "takes the plain rule only)")
+    crit = "criterion %d is none of MMEE_CRIT_MAX_CONFIDENCE, _ENTROPY, _MARGIN"
+    cur = "pol_logits and the current stage (counts, doc_orig, doc_off, x_phys) must not be NULL"
+    nxt = "the next stage (n_counts, n_doc_orig, n_doc_off, n_x_src, n_meta_src) and out_exit must not be NULL"
+    state = "mode %d with rule %d keeps state per document: prev and run must be given"
+    meta = "meta_old, meta_new and row_src are given together or not at all"
+    cases = [(dict(mode=m, rule=r), pair % (m, r)) for m, r in ((-1, 0), (3, 0), (0, -1), (0, 3), (2, 3), (1, 1), (1, 2))]
+    cases += [(dict(criterion=c), crit % c) for c in (-1, 2, 4)] + [(dict(mode=2, criterion=2), crit % 2)]
+    cases += [
+        (dict(mode=1, rule=1, K=0), pair % (1, 1)),                             # the pair is looked at first
+        (dict(K=0), "K 0 or Kh 2 is below 1"), (dict(Kh=0), "K 4 or Kh 0 is below 1"),
+        (dict(exit_index=-1), "exit_index -1 outside [0, 255]"), (dict(exit_index=256), "exit_index 256 outside [0, 255]"),
+        (dict(B=0), "B 0 outside [1, 2^20]"), (dict(B=(1 << 20) + 1), "B 1048577 outside [1, 2^20]"),
+        (dict(patience=-1), "patience -1 is negative"),
+    ]
+    cases += [(dict([(k, None)]), cur) for k in ("pol_logits", "counts", "doc_orig", "doc_off", "x_phys")]
+    cases += [(dict([(k, None)]), nxt) for k in ("n_counts", "n_doc_orig", "n_doc_off", "n_x_src", "n_meta_src", "out_exit")]
+    cases += [(dict(mode=m, rule=r, **given), state % (m, r)) for m, r in ((1, 0), (0, 1), (0, 2), (2, 1), (2, 2))
+              for given in (dict(), dict(prev=4096), dict(run=4096))]
+    cases += [(dict(given), meta) for given in (dict(meta_old=4096), dict(meta_new=4096), dict(row_src=4096), dict(meta_old=4096, meta_new=4096),
+                                                dict(meta_new=4096, row_src=4096))]
+    for over, text in cases:
+        _refused(pkg, who, call(**over), text, over)
+
+
+def test_rows_out_refusals(pkg):
+    lib, who = pkg.capi.load(), "ee_debug_rows_out"
+
+    def call(**over):
+        vals = dict(which=0, x_rows=20, H=128, split_inv=0.0, max_docs=4, B=3, T=5, Pv=2, out_rows=30)
+        vals.update(over)
+        return lib.ee_debug_rows_out(C.byref(_struct(pkg.capi.DebugRowsOutArgs, (), **vals)), None)
+
+    _refused(pkg, who, lib.ee_debug_rows_out(None, None), "args must not be NULL", "args")
+    shape = "bad shape (B >= 1, T >= 0, Pv >= 0, T + Pv >= 1, B (T + Pv) <= 2^28), got B %d, T %d, Pv %d"
+    cases = [
+        (dict(which=2), "which 2 is neither 0 (gather_cls) nor 1 (rows_to_padded)"), (dict(which=-1), "which -1 is neither 0 (gather_cls) nor 1 (rows_to_padded)"),
+        (dict(X=None), "X and out must not be NULL"), (dict(which=1, out=None), "X and out must not be NULL"),
+        (dict(H=0), "hidden size 0 is not a multiple of 4 in [4, 4096]"), (dict(H=130), "hidden size 130 is not a multiple of 4 in [4, 4096]"),
+        (dict(H=4100), "hidden size 4100 is not a multiple of 4 in [4, 4096]"),
+        (dict(split_inv=-0.5), "split_inv must be 0 (f32 rows) or positive"), (dict(split_inv=float("nan")), "split_inv must be 0 (f32 rows) or positive"),
+        (dict(split_inv=0.0625, H=136), "split rows need a hidden size that is a multiple of 16 (got 136)"),
+        (dict(x_rows=0), "bad counts (x_rows >= 1, out_rows >= 0)"), (dict(which=1, out_rows=-1), "bad counts (x_rows >= 1, out_rows >= 0)"),
+        (dict(x_phys=None), "gather_cls needs x_phys and n_docs"), (dict(n_docs=None), "gather_cls needs x_phys and n_docs"),
+        (dict(max_docs=0), "max_docs 0 outside [1, 2^20]"), (dict(max_docs=(1 << 20) + 1), "max_docs 1048577 outside [1, 2^20]"),
+        (dict(which=1, doc_off=None), "rows_to_padded needs doc_off"),
+        (dict(which=1, B=0), shape % (0, 5, 2)), (dict(which=1, T=-1), shape % (3, -1, 2)), (dict(which=1, Pv=-1), shape % (3, 5, -1)),
+        (dict(which=1, T=0, Pv=0), shape % (3, 0, 0)), (dict(which=1, B=1 << 20, T=1 << 9), shape % (1 << 20, 1 << 9, 2)),
+        (dict(which=1, text_dst=None), "without text_dst (image-only) T must be 0, got 5"),
+        (dict(which=1, ntext=None), "text_dst without ntext"),
     ]
     for over, text in cases:
         _refused(pkg, who, call(**over), text, over)
