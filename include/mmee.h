@@ -710,6 +710,49 @@ int ee_debug_mlp_head_lossgrad(const float* features, const int64_t* labels, con
                                double l2, double* loss, double* grad, void* stream);
 
 /*
+ * Exit heads fitted by distillation from the final classifier, for CLS rows that have no labels (self-distillation with the backbone frozen,
+ * as FastBERT trains its exits; the reference declares the knobs -- EETrainingArguments(alpha = 1, temperature = 1), EE/models/EE_modules.py:
+ * 288-298 -- and implements nothing behind them).  Both head types, per exit e, independently; t (N,K) float32 are the final classifier's
+ * logits on the same documents, the same for every exit:
+ *
+ *     z_n = head_theta(x_n)                  one Linear (ee_head_fit), or dense -> tanh -> out_proj (ee_mlp_head_fit)
+ *     q_n = softmax(t_n / T)                 p_n = softmax(z_n)                 pT_n = softmax(z_n / T)
+ *     L_e(theta) = (1/N) sum_n [ (1 - alpha) (logsumexp(z_n) - z_n[y_n]) + alpha T^2 KL(q_n || pT_n) ] + (l2 / 2) ||theta||^2
+ *     KL(q || p) = sum_k q_k (log q_k - log p_k)
+ *     dL/dz_n = (1/N) [ (1 - alpha) (p_n - onehot(y_n)) + alpha T (pT_n - q_n) ]
+ *
+ * All arithmetic is float64 on the float32 inputs.  Every softmax and log-softmax is max-shifted; log q and log pT are the shifted logits
+ * minus the log of their sum of exponentials, never the log of a probability, so a q_k that underflows to 0 contributes exactly 0.  The sum
+ * q log q is kept: L's soft term is a true KL, >= 0 up to rounding.  0 <= alpha <= 1; the temperature T is finite and > 0; l2 > 0 as for the
+ * fits above (every parameter is penalised, and for 0 <= alpha <= 1 the one-layer objective stays l2-strongly convex).  At alpha = 1 the
+ * labels are ignored entirely: the pointer may be NULL and is not range-checked.  At alpha < 1 labels are required and checked as above.
+ * At alpha = 0 the objective is ee_head_fit's (ee_mlp_head_fit's); the teacher is still required and checked.
+ *
+ * ee_head_fit_distill / ee_mlp_head_fit_distill: limits, workspaces (ee_head_fit_workspace_bytes / ee_mlp_head_fit_workspace_bytes), outputs,
+ *   the L-BFGS, stopping rules and status codes are those of ee_head_fit / ee_mlp_head_fit (theta0 required for the two-layer head).
+ *   The error word at the head of the workspace: bit 0 a label outside [0,K), bit 1 a teacher logit that is not finite (a dump-all forward
+ *   marks the rows a document never reached with NaN).  Either fails the call with a message and leaves no output written; the call learns
+ *   of it by the one wait after its last launch.  Sums run in the fixed orders of ee_head_fit / ee_mlp_head_fit: two calls return the same
+ *   bits, and an exit fitted together with others gets the bits it gets alone.
+ * ee_debug_head_distill_lossgrad / ee_debug_mlp_head_distill_lossgrad: ONE evaluation of L_e and grad L_e at theta64 dev (E,P), as
+ *   ee_debug_head_lossgrad / ee_debug_mlp_head_lossgrad.
+ */
+int ee_head_fit_distill(const float* features, const float* teacher_logits, const int64_t* labels, int32_t E, int32_t N, int32_t H, int32_t K,
+                        double alpha, double temperature, double l2, double gtol, int32_t max_evals, int32_t history, void* workspace,
+                        size_t workspace_bytes, float* weight, float* bias, double* weight64, double* bias64, double* loss, double* grad_norm,
+                        int32_t* evals, int32_t* status, void* stream);
+int ee_debug_head_distill_lossgrad(const float* features, const float* teacher_logits, const int64_t* labels, const double* theta64, int32_t E,
+                                   int32_t N, int32_t H, int32_t K, double alpha, double temperature, double l2, double* loss, double* grad,
+                                   void* stream);
+int ee_mlp_head_fit_distill(const float* features, const float* teacher_logits, const int64_t* labels, const double* theta0, int32_t E, int32_t N,
+                            int32_t H, int32_t K, double alpha, double temperature, double l2, double gtol, int32_t max_evals, int32_t history,
+                            void* workspace, size_t workspace_bytes, float* dense_weight, float* dense_bias, float* weight, float* bias,
+                            double* theta64, double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream);
+int ee_debug_mlp_head_distill_lossgrad(const float* features, const float* teacher_logits, const int64_t* labels, const double* theta64, int32_t E,
+                                       int32_t N, int32_t H, int32_t K, double alpha, double temperature, double l2, double* loss, double* grad,
+                                       void* stream);
+
+/*
  * The learning-to-exit classifier (ee_config.use_lte) fitted on the device from the CLS rows of a frozen backbone.  The reference trains it
  * inside EETrainer (EE/models/LayoutLMv3.py:795-857: lte_loss_fct = MSELoss against 1 - lte_gold, one MSE per exit, summed); here it is one
  * deterministic batch problem.  ONE classifier theta = (w (H,), b) is shared by all encoder exits, as in the reference (init_lte: one

@@ -1,4 +1,5 @@
-// Entry points of the device fits, none of which sees a handle: one-layer and two-layer exit heads (ee_head_fit, ee_mlp_head_fit) and the
+// Entry points of the device fits, none of which sees a handle: one-layer and two-layer exit heads (ee_head_fit, ee_mlp_head_fit; against the
+// final classifier's logits instead of labels: ee_head_fit_distill, ee_mlp_head_fit_distill, through the same bodies) and the
 // learning-to-exit classifier (ee_lte_fit, with ee_lte_targets and ee_lte_scores) from dumped CLS rows, their workspace queries, and the
 // ee_debug_*_lossgrad hooks that run one evaluation of an objective on caller-provided buffers.  The L-BFGS is fit_lbfgs.hip.
 #include "capi_internal.h"
@@ -23,8 +24,10 @@ static int budget_refuse(const char* who, double gtol, int32_t max_evals, int32_
     return 0;
 }
 
+static const char* const kBadTeacher = "%s: a teacher logit is not finite (dump-all marks the rows a document never reached with NaN)%s";
+
 // The tail of a call that left an error word on the device: the launch status, the word read on the stream, one synchronise.  bad: the
-// message for bit 0 (bad input), a format of (who, K).
+// message for bit 0 (bad input), a format of (who, K).  Bit 1 is the distilled fits': a teacher logit that is not finite.
 static int finish_call(const char* who, bool prepared, const void* err_word, hipStream_t s, const char* bad, int K) {
     if (!prepared) return fail(nullptr, "%s: preparing the workspace (memset, copy of theta0) failed", who);
     if (launch_status(nullptr, who)) return 1;
@@ -32,6 +35,7 @@ static int finish_call(const char* who, bool prepared, const void* err_word, hip
     if (hipMemcpyAsync(&err, err_word, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
         return fail(nullptr, "%s: reading the error word failed: %s", who, hipGetErrorString(hipGetLastError()));
     if (err & 1) return fail(nullptr, bad, who, K);
+    if (err & 2) return fail(nullptr, kBadTeacher, who, "; no output was written");
     return 0;
 }
 
@@ -50,6 +54,7 @@ static int debug_lossgrad(const char* who, size_t n, hipStream_t s, Launch launc
     if (hipMemcpy(&err, err_dev, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of the error word failed", who);
     if (launch_status(nullptr, who)) return 1;
     if (err & 1) return fail(nullptr, bad, who, K);
+    if (err & 2) return fail(nullptr, kBadTeacher, who, "");
     return 0;
 }
 
@@ -82,6 +87,66 @@ static int lte_objective_refuse(const char* who, int32_t loss, double l2) {
 static const char* const kBadLabelFit = "%s: a label is outside [0, K = %d); no output was written";
 static const char* const kBadLabel = "%s: a label is outside [0, K = %d)";
 
+// ---- the head fits' entry points, hard-label and distilled, as one body each ---------------------------------------------------------------------
+// soft: null for the entry points that fit against labels; else the distilled objective's targets, refused here before any device call
+static int distill_refuse(const char* who, const int64_t* labels, const DistillTargets* soft) {
+    if (!soft) return 0;
+    if (!soft->teacher) return fail(nullptr, "%s: NULL argument (teacher_logits are required)", who);
+    if (!(soft->alpha >= 0.0 && soft->alpha <= 1.0)) return fail(nullptr, "%s: alpha = %g, need 0 <= alpha <= 1", who, soft->alpha);
+    if (!(soft->temperature > 0.0) || std::isinf(soft->temperature))
+        return fail(nullptr, "%s: temperature = %g, need a finite temperature > 0", who, soft->temperature);
+    if (soft->alpha < 1.0 && !labels) return fail(nullptr, "%s: NULL labels at alpha = %g: only alpha == 1 does without them", who, soft->alpha);
+    return 0;
+}
+
+static int head_fit_call(const char* who, const float* features, const int64_t* labels, const DistillTargets* soft, int32_t E, int32_t N,
+                         int32_t H, int32_t K, double l2, double gtol, int32_t max_evals, int32_t history, void* workspace,
+                         size_t workspace_bytes, float* weight, float* bias, double* weight64, double* bias64, double* loss, double* grad_norm,
+                         int32_t* evals, int32_t* status, void* stream) {
+    if (!features || (!soft && !labels) || !workspace || !weight || !bias)
+        return fail(nullptr, "%s: NULL argument (features, %s, workspace, weight and bias are required)", who, soft ? "teacher_logits" : "labels");
+    if (distill_refuse(who, labels, soft) || head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
+    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return head_fit_workspace_bytes(E, N, H, K, history); })) return 1;
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const HeadFitArgs a{{features, E, N, H, l2, gtol, max_evals, history, workspace, nullptr, nullptr, loss, grad_norm, evals, status},
+                        reinterpret_cast<const long long*>(labels), K, weight, bias, weight64, bias64, soft ? *soft : DistillTargets{}};
+    return finish_call(who, launch_head_fit(a, s), workspace, s, kBadLabelFit, K);
+}
+
+static int mlp_head_fit_call(const char* who, const float* features, const int64_t* labels, const DistillTargets* soft, const double* theta0,
+                             int32_t E, int32_t N, int32_t H, int32_t K, double l2, double gtol, int32_t max_evals, int32_t history,
+                             void* workspace, size_t workspace_bytes, float* dense_weight, float* dense_bias, float* weight, float* bias,
+                             double* theta64, double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
+    if (!features || (!soft && !labels) || !theta0 || !workspace || !dense_weight || !dense_bias || !weight || !bias)
+        return fail(nullptr, "%s: NULL argument (features, %s, theta0, workspace, dense_weight, dense_bias, weight and bias are required; "
+                             "theta = 0 is a saddle the iteration never leaves, so there is no default start)", who,
+                    soft ? "teacher_logits" : "labels");
+    if (distill_refuse(who, labels, soft) || head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
+    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return mlp_head_fit_workspace_bytes(E, N, H, K, history); })) return 1;
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const MlpHeadFitArgs a{{features, E, N, H, l2, gtol, max_evals, history, workspace, theta0, theta64, loss, grad_norm, evals, status},
+                           reinterpret_cast<const long long*>(labels), K, dense_weight, dense_bias, weight, bias, soft ? *soft : DistillTargets{}};
+    return finish_call(who, launch_mlp_head_fit(a, s), workspace, s, kBadLabelFit, K);
+}
+
+// ONE evaluation of a head objective: mlp selects the two-layer head
+static int head_lossgrad_call(const char* who, bool mlp, const float* features, const int64_t* labels, const DistillTargets* soft,
+                              const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K, double l2, double* loss, double* grad,
+                              void* stream) {
+    if (!features || (!soft && !labels) || !theta64 || !loss || !grad) return fail(nullptr, "%s: NULL argument", who);
+    if (distill_refuse(who, labels, soft) || head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const long long* y = reinterpret_cast<const long long*>(labels);
+    const DistillTargets targets = soft ? *soft : DistillTargets{};
+    const size_t n = mlp ? mlp_head_fit_scratch_doubles(E, N, H, K) : head_fit_partial_bytes(E, N, H, K) / sizeof(double);
+    return debug_lossgrad(who, n, s, [&](double* scratch, int* err) {
+        if (mlp) launch_mlp_head_lossgrad(features, y, theta64, E, N, H, K, l2, scratch, err, loss, grad, s, targets);
+        else launch_head_lossgrad(features, y, theta64, E, N, H, K, l2, scratch, err, loss, grad, s, targets);
+    }, kBadLabel, K);
+}
+
 extern "C" {
 
 // ---- exit heads from CLS rows (head_fit.hip) ---------------------------------------------------------------------------------------------
@@ -93,27 +158,29 @@ size_t ee_head_fit_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, i
 int ee_head_fit(const float* features, const int64_t* labels, int32_t E, int32_t N, int32_t H, int32_t K, double l2, double gtol,
                 int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* weight, float* bias, double* weight64,
                 double* bias64, double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
-    const char* who = "ee_head_fit";
-    if (!features || !labels || !workspace || !weight || !bias)
-        return fail(nullptr, "%s: NULL argument (features, labels, workspace, weight and bias are required)", who);
-    if (head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
-    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return head_fit_workspace_bytes(E, N, H, K, history); })) return 1;
-    if (!have_device(who)) return 1;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const HeadFitArgs a{{features, E, N, H, l2, gtol, max_evals, history, workspace, nullptr, nullptr, loss, grad_norm, evals, status},
-                        reinterpret_cast<const long long*>(labels), K, weight, bias, weight64, bias64};
-    return finish_call(who, launch_head_fit(a, s), workspace, s, kBadLabelFit, K);
+    return head_fit_call("ee_head_fit", features, labels, nullptr, E, N, H, K, l2, gtol, max_evals, history, workspace, workspace_bytes, weight,
+                         bias, weight64, bias64, loss, grad_norm, evals, status, stream);
+}
+
+int ee_head_fit_distill(const float* features, const float* teacher_logits, const int64_t* labels, int32_t E, int32_t N, int32_t H, int32_t K,
+                        double alpha, double temperature, double l2, double gtol, int32_t max_evals, int32_t history, void* workspace,
+                        size_t workspace_bytes, float* weight, float* bias, double* weight64, double* bias64, double* loss, double* grad_norm,
+                        int32_t* evals, int32_t* status, void* stream) {
+    const DistillTargets soft{teacher_logits, alpha, temperature};
+    return head_fit_call("ee_head_fit_distill", features, labels, &soft, E, N, H, K, l2, gtol, max_evals, history, workspace, workspace_bytes,
+                         weight, bias, weight64, bias64, loss, grad_norm, evals, status, stream);
 }
 
 int ee_debug_head_lossgrad(const float* features, const int64_t* labels, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K,
                            double l2, double* loss, double* grad, void* stream) {
-    const char* who = "ee_debug_head_lossgrad";
-    if (!features || !labels || !theta64 || !loss || !grad) return fail(nullptr, "%s: NULL argument", who);
-    if (head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return debug_lossgrad(who, head_fit_partial_bytes(E, N, H, K) / sizeof(double), s, [&](double* partial, int* err) {
-        launch_head_lossgrad(features, reinterpret_cast<const long long*>(labels), theta64, E, N, H, K, l2, partial, err, loss, grad, s);
-    }, kBadLabel, K);
+    return head_lossgrad_call("ee_debug_head_lossgrad", false, features, labels, nullptr, theta64, E, N, H, K, l2, loss, grad, stream);
+}
+
+int ee_debug_head_distill_lossgrad(const float* features, const float* teacher_logits, const int64_t* labels, const double* theta64, int32_t E,
+                                   int32_t N, int32_t H, int32_t K, double alpha, double temperature, double l2, double* loss, double* grad,
+                                   void* stream) {
+    const DistillTargets soft{teacher_logits, alpha, temperature};
+    return head_lossgrad_call("ee_debug_head_distill_lossgrad", false, features, labels, &soft, theta64, E, N, H, K, l2, loss, grad, stream);
 }
 
 // ---- two-layer exit heads from CLS rows (mlp_head_fit.hip) -------------------------------------------------------------------------------
@@ -126,28 +193,29 @@ int ee_mlp_head_fit(const float* features, const int64_t* labels, const double* 
                     double gtol, int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* dense_weight,
                     float* dense_bias, float* weight, float* bias, double* theta64, double* loss, double* grad_norm, int32_t* evals,
                     int32_t* status, void* stream) {
-    const char* who = "ee_mlp_head_fit";
-    if (!features || !labels || !theta0 || !workspace || !dense_weight || !dense_bias || !weight || !bias)
-        return fail(nullptr, "%s: NULL argument (features, labels, theta0, workspace, dense_weight, dense_bias, weight and bias are required; "
-                             "theta = 0 is a saddle the iteration never leaves, so there is no default start)", who);
-    if (head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
-    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return mlp_head_fit_workspace_bytes(E, N, H, K, history); })) return 1;
-    if (!have_device(who)) return 1;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const MlpHeadFitArgs a{{features, E, N, H, l2, gtol, max_evals, history, workspace, theta0, theta64, loss, grad_norm, evals, status},
-                           reinterpret_cast<const long long*>(labels), K, dense_weight, dense_bias, weight, bias};
-    return finish_call(who, launch_mlp_head_fit(a, s), workspace, s, kBadLabelFit, K);
+    return mlp_head_fit_call("ee_mlp_head_fit", features, labels, nullptr, theta0, E, N, H, K, l2, gtol, max_evals, history, workspace,
+                             workspace_bytes, dense_weight, dense_bias, weight, bias, theta64, loss, grad_norm, evals, status, stream);
+}
+
+int ee_mlp_head_fit_distill(const float* features, const float* teacher_logits, const int64_t* labels, const double* theta0, int32_t E, int32_t N,
+                            int32_t H, int32_t K, double alpha, double temperature, double l2, double gtol, int32_t max_evals, int32_t history,
+                            void* workspace, size_t workspace_bytes, float* dense_weight, float* dense_bias, float* weight, float* bias,
+                            double* theta64, double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
+    const DistillTargets soft{teacher_logits, alpha, temperature};
+    return mlp_head_fit_call("ee_mlp_head_fit_distill", features, labels, &soft, theta0, E, N, H, K, l2, gtol, max_evals, history, workspace,
+                             workspace_bytes, dense_weight, dense_bias, weight, bias, theta64, loss, grad_norm, evals, status, stream);
 }
 
 int ee_debug_mlp_head_lossgrad(const float* features, const int64_t* labels, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K,
                                double l2, double* loss, double* grad, void* stream) {
-    const char* who = "ee_debug_mlp_head_lossgrad";
-    if (!features || !labels || !theta64 || !loss || !grad) return fail(nullptr, "%s: NULL argument", who);
-    if (head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return debug_lossgrad(who, mlp_head_fit_scratch_doubles(E, N, H, K), s, [&](double* scratch, int* err) {
-        launch_mlp_head_lossgrad(features, reinterpret_cast<const long long*>(labels), theta64, E, N, H, K, l2, scratch, err, loss, grad, s);
-    }, kBadLabel, K);
+    return head_lossgrad_call("ee_debug_mlp_head_lossgrad", true, features, labels, nullptr, theta64, E, N, H, K, l2, loss, grad, stream);
+}
+
+int ee_debug_mlp_head_distill_lossgrad(const float* features, const float* teacher_logits, const int64_t* labels, const double* theta64, int32_t E,
+                                       int32_t N, int32_t H, int32_t K, double alpha, double temperature, double l2, double* loss, double* grad,
+                                       void* stream) {
+    const DistillTargets soft{teacher_logits, alpha, temperature};
+    return head_lossgrad_call("ee_debug_mlp_head_distill_lossgrad", true, features, labels, &soft, theta64, E, N, H, K, l2, loss, grad, stream);
 }
 
 // ---- the LTE classifier from CLS rows (lte_fit.hip) --------------------------------------------------------------------------------------

@@ -6,6 +6,9 @@
 //                               softmax (D = P - Y in place of Z) and the gradient pass (D^T X), whose sums stay in registers across the
 //                               chunk.  One partial (dW, db, loss) per (exit, chunk) goes to the workspace: no atomics.
 //   head_fit_reduce_kernel      sums the chunk partials in chunk order, divides by N, adds the penalty: L and grad L of the trial point.
+// ee_head_fit_distill runs the same two kernels: head_fit_lossgrad_kernel is a template over its argument struct, and what the struct selects
+// (if constexpr) is the row step between the two passes -- the labelled softmax, or the mixed step against the final classifier's logits
+// (distill_row, head_fit_common.h), which reads the teacher's row from global memory: no LDS and no workspace beyond the labelled fit's.
 // This file is the objective; the L-BFGS around it is run_lbfgs_fit (fit_lbfgs.hip), the workspace layout and the control words are in
 // head_fit_common.h.
 //
@@ -15,6 +18,8 @@
 //
 // Determinism: the chunking is a function of N alone, every sum has a fixed order, and nothing depends on E -- an exit fitted alone gets
 // the bits it gets among others.
+#include <type_traits>
+
 #include "head_fit_common.h"
 
 namespace mmee {
@@ -37,10 +42,44 @@ struct LossGradArgs {
     double* partial;                 // (E, chunks, K*H + K + 1)
     int N, H, K, chunks, slabs_per_chunk;
 };
+// ee_head_fit_distill: err bit 1 is a teacher logit that is not finite; y is null at alpha = 1
+struct DistillLossGradArgs : LossGradArgs {
+    const float* teacher;            // (N,K)
+    double alpha, temperature;
+};
 
-// KT classes x HC columns (h = t + 256 i) of the gradient per thread
-template <int KT, int HC>
-__global__ __launch_bounds__(kThreads) void head_fit_lossgrad_kernel(LossGradArgs a) {
+// The mixed row step (distill_row, head_fit_common.h) of the slab walk below: the row's logits and the teacher's row -- float32 from global memory,
+// each element read once -- in registers, eight threads a row.  Z [S][Kp] holds the slab's logits and leaves as N dL/dz (zero beyond the slab's
+// rows and beyond K); the row's loss goes to `loss` of the first of its eight threads.  Every thread reads its logits before any of the row
+// writes: they are lanes of one wave.
+__device__ inline void distill_row_step(const DistillLossGradArgs& a, double* Z, int n0, int rows, int K, int Kp, double& loss) {
+    const int t = threadIdx.x, row = t >> 3, sub = t & 7;
+    const bool valid = row < rows, hard = a.alpha < 1.0;
+    long long y = -1;
+    if (hard) {
+        y = valid ? a.y[n0 + row] : 0;
+        if (y < 0 || y >= K) {
+            atomicOr(a.err, 1);
+            y = -1;
+        }
+    }
+    float tv[kRowSlots];
+    load_teacher_row(a.teacher + (size_t)(n0 + row) * K, valid, sub, K, tv, a.err);
+    double v[kRowSlots];
+#pragma unroll
+    for (int i = 0; i < kRowSlots; ++i) v[i] = sub + 8 * i < K ? Z[row * Kp + sub + 8 * i] : 0.0;
+    const double l = distill_row(v, tv, sub, K, y, hard, a.alpha, a.temperature);
+    if (sub == 0 && valid) loss += l;
+#pragma unroll
+    for (int i = 0; i < kRowSlots; ++i) {
+        const int k = sub + 8 * i;
+        if (k < Kp) Z[row * Kp + k] = (valid && k < K) ? v[i] : 0.0;
+    }
+}
+
+// KT classes x HC columns (h = t + 256 i) of the gradient per thread; Args: LossGradArgs (labels) or DistillLossGradArgs (soft targets)
+template <int KT, int HC, typename Args>
+__global__ __launch_bounds__(kThreads) void head_fit_lossgrad_kernel(Args a) {
     const int kt = blockIdx.x, c = blockIdx.y, e = blockIdx.z, t = threadIdx.x, lane = t & 63, w = t >> 6;
     if (a.ctrl && a.ctrl[e * kCtrlInts + CI_STOP] != 0) return;
     const int N = a.N, H = a.H, K = a.K, H4 = H >> 2, ld = H + 4, Kp = round_up(K, 16), P = K * H + K;
@@ -132,8 +171,10 @@ __global__ __launch_bounds__(kThreads) void head_fit_lossgrad_kernel(LossGradArg
             }
         }
 
-        // ---- max-shifted softmax, loss, D = P - Y: eight threads a row ----
-        {
+        // ---- the row step, the compile-time difference between the two objectives: the row's loss, N dL/dz in place of Z ----
+        if constexpr (std::is_same_v<Args, DistillLossGradArgs>) distill_row_step(a, Z, n0, rows, K, Kp, loss);
+        else {
+            // max-shifted softmax, loss, D = P - Y: eight threads a row
             const int row = t >> 3, sub = t & 7;
             const bool valid = row < rows;
             long long y = valid ? a.y[n0 + row] : 0;
@@ -253,15 +294,15 @@ size_t lossgrad_lds_bytes(int H, int K) {
     return sizeof(float) * S * (size_t)(H + 4) + sizeof(double) * S * (size_t)round_up(K, 16) + sizeof(double) * 4 * S * kLogitTile;
 }
 
-template <int KT, int HC>
-void launch_lossgrad_as(const LossGradArgs& a, int E, hipStream_t s) {
+template <int KT, int HC, typename Args>
+void launch_lossgrad_as(const Args& a, int E, hipStream_t s) {
     const size_t lds = lossgrad_lds_bytes(a.H, a.K);
-    (void)ensure_dynamic_lds<&head_fit_lossgrad_kernel<KT, HC>>("head_fit_lossgrad_kernel", 160 * 1024);
-    hipLaunchKernelGGL((head_fit_lossgrad_kernel<KT, HC>), dim3((a.K + KT - 1) / KT, a.chunks, E), dim3(kThreads), lds, s, a);
+    (void)ensure_dynamic_lds<&head_fit_lossgrad_kernel<KT, HC, Args>>("head_fit_lossgrad_kernel", 160 * 1024);
+    hipLaunchKernelGGL((head_fit_lossgrad_kernel<KT, HC, Args>), dim3((a.K + KT - 1) / KT, a.chunks, E), dim3(kThreads), lds, s, a);
 }
 
-template <int KT>
-void launch_lossgrad_k(const LossGradArgs& a, int E, hipStream_t s) {
+template <int KT, typename Args>
+void launch_lossgrad_k(const Args& a, int E, hipStream_t s) {
     switch ((a.H + kThreads - 1) / kThreads) {
         case 1: launch_lossgrad_as<KT, 1>(a, E, s); break;
         case 2: launch_lossgrad_as<KT, 2>(a, E, s); break;
@@ -270,16 +311,23 @@ void launch_lossgrad_k(const LossGradArgs& a, int E, hipStream_t s) {
     }
 }
 
-// one evaluation: the partials of every running exit, then their fixed-order sums
-void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, int E, int N, int H, int K, double l2, hipStream_t s) {
+template <typename Args>
+void launch_lossgrad(const Args& a, int E, hipStream_t s) {
+    if (a.K <= 4) launch_lossgrad_k<4>(a, E, s);
+    else launch_lossgrad_k<16>(a, E, s);
+}
+
+// one evaluation: the partials of every running exit, then their fixed-order sums; soft.teacher null: the hard-label objective
+void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, const DistillTargets& soft, int E, int N, int H, int K, double l2,
+                 hipStream_t s) {
     LossGradArgs a{};
     a.X = X; a.y = y; a.theta = p.theta; a.theta_stride = p.theta_stride; a.ctrl = p.ctrl; a.err = p.err;
     a.partial = static_cast<double*>(p.tail); a.N = N; a.H = H; a.K = K;
     const int n_slabs = (a.N + S - 1) / S;
     a.chunks = head_fit_chunks(a.N);
     a.slabs_per_chunk = (n_slabs + a.chunks - 1) / a.chunks;
-    if (a.K <= 4) launch_lossgrad_k<4>(a, E, s);
-    else launch_lossgrad_k<16>(a, E, s);
+    if (soft.teacher) launch_lossgrad(DistillLossGradArgs{a, soft.teacher, soft.alpha, soft.temperature}, E, s);
+    else launch_lossgrad(a, E, s);
     ReduceArgs r{};
     r.partial = a.partial; r.theta = a.theta; r.theta_stride = a.theta_stride; r.ctrl = a.ctrl; r.loss = p.loss; r.loss_stride = 1;
     r.grad = p.grad; r.grad_stride = p.grad_stride; r.N = a.N; r.P = a.K * a.H + a.K; r.chunks = a.chunks; r.l2 = l2;
@@ -301,15 +349,15 @@ size_t head_fit_workspace_bytes(int E, int N, int H, int K, int history) { retur
 size_t head_fit_partial_bytes(int E, int N, int H, int K) { return sizeof(double) * (size_t)E * head_fit_chunks(N) * (size_t)(K * H + K + 1); }
 
 void launch_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* partial, int* err,
-                          double* loss, double* grad, hipStream_t s) {
+                          double* loss, double* grad, hipStream_t s, const DistillTargets& soft) {
     const size_t P = (size_t)K * H + K;
-    launch_eval({theta, P, nullptr, err, loss, grad, P, partial}, X, y, E, N, H, K, l2, s);
+    launch_eval({theta, P, nullptr, err, loss, grad, P, partial}, X, y, soft, E, N, H, K, l2, s);
 }
 
 bool launch_head_fit(const HeadFitArgs& f, hipStream_t s) {
     const int KH = f.K * f.H;
     return run_lbfgs_fit(f, one_layer_layout(f.E, f.N, f.H, f.K, f.history),
-                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.labels, f.E, f.N, f.H, f.K, f.l2, s); },
+                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.labels, f.soft, f.E, f.N, f.H, f.K, f.l2, s); },
                          {{0, KH, f.weight, f.weight64}, {KH, f.K, f.bias, f.bias64}}, s);
 }
 

@@ -29,6 +29,90 @@ __device__ inline double block_sum(double v, double* red) {
     return red[0];
 }
 
+// ---- the distilled row step (ee_head_fit_distill, ee_mlp_head_fit_distill; include/mmee.h states the objective) ----------------------------
+// A row of K <= 64 classes lies over eight neighbouring lanes: lane `sub` holds class sub + 8 i in slot i.  Both head types call the two
+// functions below from every lane of a wave (they shuffle), the one-layer fit from its slab walk, the two-layer fit from its softmax kernel.
+constexpr int kRowSlots = 8;
+
+__device__ inline double row8_max(double v) {
+    v = fmax(v, __shfl_xor(v, 1));
+    v = fmax(v, __shfl_xor(v, 2));
+    return fmax(v, __shfl_xor(v, 4));
+}
+__device__ inline double row8_sum(double v) {
+    v += __shfl_xor(v, 1);
+    v += __shfl_xor(v, 2);
+    return v + __shfl_xor(v, 4);
+}
+
+// The teacher's row into registers, each element read once; a row that does not exist reads as zeros.  A logit that is not finite (dump-all
+// marks the rows a document never reached with NaN) raises bit 1 of the error word.
+__device__ inline void load_teacher_row(const float* trow, bool valid, int sub, int K, float (&tv)[kRowSlots], int* err) {
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < kRowSlots; ++i) {
+        const int k = sub + 8 * i;
+        tv[i] = (valid && k < K) ? trow[k] : 0.f;
+        bad |= !__builtin_isfinite(tv[i]);
+    }
+    if (bad) atomicOr(err, 2);
+}
+
+// v: the row's logits z, replaced by N dL/dz = (1 - alpha)(p - onehot(y)) + alpha T (pT - q); returns the row's
+// (1 - alpha)(logsumexp(z) - z[y]) + alpha T^2 KL(q || pT), the same bits in the row's eight lanes.  q = softmax(tv / T), p = softmax(z),
+// pT = softmax(z / T), all max-shifted; log q and log pT are shifted logits minus the log of their sum, so a q_k that underflows to zero
+// contributes exactly zero.  hard = alpha < 1: without it neither y nor p is looked at.  y < 0 (a label out of range, the error word is
+// raised) leaves the hard target out.  At T = 1 pT is p and its exponentials are taken once.
+__device__ inline double distill_row(double (&v)[kRowSlots], const float (&tv)[kRowSlots], int sub, int K, long long y, bool hard, double alpha,
+                                     double T) {
+    double m = -INFINITY, tm = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < kRowSlots; ++i)
+        if (sub + 8 * i < K) {
+            m = fmax(m, v[i]);
+            tm = fmax(tm, (double)tv[i]);
+        }
+    m = row8_max(m);
+    tm = row8_max(tm);
+    const bool own = hard && T != 1.0;                       // p needs exponentials of its own
+    double eT[kRowSlots], eq[kRowSlots], e1[kRowSlots];
+    double sT = 0.0, sq = 0.0, s1 = 0.0, zy = 0.0;
+#pragma unroll
+    for (int i = 0; i < kRowSlots; ++i) {
+        const int k = sub + 8 * i;
+        const bool in = k < K;
+        if (in && k == (int)y) zy = v[i];
+        v[i] = in ? v[i] - m : 0.0;
+        eT[i] = in ? exp(v[i] / T) : 0.0;
+        eq[i] = in ? exp(((double)tv[i] - tm) / T) : 0.0;
+        e1[i] = (own && in) ? exp(v[i]) : eT[i];
+        sT += eT[i];
+        sq += eq[i];
+        s1 += e1[i];
+    }
+    sT = row8_sum(sT);
+    sq = row8_sum(sq);
+    s1 = row8_sum(s1);
+    zy = row8_sum(zy);
+    const double log_sT = log(sT), log_sq = log(sq), inv_sT = 1.0 / sT, inv_sq = 1.0 / sq, inv_s1 = 1.0 / s1;
+    const double soft = alpha * T, keep = hard ? 1.0 - alpha : 0.0;
+    double kl = 0.0;
+#pragma unroll
+    for (int i = 0; i < kRowSlots; ++i) {
+        const int k = sub + 8 * i;
+        if (k < K) {
+            const double q = eq[i] * inv_sq;
+            const double log_q = ((double)tv[i] - tm) / T - log_sq, log_pT = v[i] / T - log_sT;
+            kl = fma(q, log_q - log_pT, kl);
+            double d = soft * (eT[i] * inv_sT - q);
+            if (hard) d += keep * (e1[i] * inv_s1 - (k == (int)y ? 1.0 : 0.0));
+            v[i] = d;
+        }
+    }
+    kl = row8_sum(kl);
+    return (hard && y >= 0 ? keep * ((m + log(s1)) - zy) : 0.0) + soft * T * kl;
+}
+
 // The workspace of one fit.  Per exit: control words, scalars, then the parameter-sized vectors; behind them `tail_bytes` of whatever an
 // evaluation of the objective needs (the one-layer fit's chunk partials, the two-layer fit's hidden rows).  The error word lives at 0.
 struct FitLayout {

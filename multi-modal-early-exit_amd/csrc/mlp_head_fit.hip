@@ -5,6 +5,7 @@
 //   mlp_nt_gemm_kernel<float, tanh>   A = tanh(X W1^T + b1)            (N,H) float64, kept in the workspace          2 N H^2 FLOP
 //   mlp_nt_gemm_kernel<double>        Z = A W2^T + b2                  (N,K)
 //   mlp_softmax_kernel                D = softmax(Z) - Y in place of Z, the rows' losses, the label check
+//                                     (ee_mlp_head_fit_distill: mlp_distill_softmax_kernel in its place, D = N dL/dZ of the mixed objective)
 //   mlp_tn_gemm_kernel<double>        dW2 = D^T A, db2 = D^T 1         written as gradient: / N + l2 theta
 //   mlp_dact_kernel                   dA = (D W2) (1 - A^2)            in place of A
 //   mlp_tn_gemm_kernel<float>         dW1 = dA^T X, db1 = dA^T 1       written as gradient                           2 N H^2 FLOP
@@ -45,6 +46,11 @@ struct EvalArgs {
     size_t grad_stride;
     int N, H, K;
     double l2;
+};
+// ee_mlp_head_fit_distill: err bit 1 is a teacher logit that is not finite; y is null at alpha = 1
+struct DistillEvalArgs : EvalArgs {
+    const float* teacher;            // (N,K)
+    double alpha, temperature;
 };
 
 __device__ inline bool stopped(const int* ctrl, int e) { return ctrl && ctrl[e * kCtrlInts + CI_STOP] != 0; }
@@ -278,6 +284,36 @@ __global__ __launch_bounds__(kThreads) void mlp_softmax_kernel(EvalArgs a) {
     if (sub == 0) a.rowloss[(size_t)e * a.N + row] = y >= 0 ? (m + log(sum)) - zy : 0.0;
 }
 
+// ---- the distilled counterpart (ee_mlp_head_fit_distill): the mixed row step of distill_row (head_fit_common.h) on the same rows, writing the
+// same D in place of Z and the same row losses; the teacher's row comes from global memory, each element read once ----------------------------
+// grid (ceil(N / kSoftRows), E)
+__global__ __launch_bounds__(kThreads) void mlp_distill_softmax_kernel(DistillEvalArgs a) {
+    const int e = blockIdx.y, t = threadIdx.x, sub = t & 7, K = a.K;
+    if (stopped(a.ctrl, e)) return;
+    const int row = blockIdx.x * kSoftRows + (t >> 3);
+    const bool valid = row < a.N, hard = a.alpha < 1.0;
+    double* Z = a.Z + ((size_t)e * a.N + (valid ? row : 0)) * K;
+    long long y = -1;
+    if (hard) {
+        y = valid ? a.y[row] : 0;
+        if (y < 0 || y >= K) {
+            atomicOr(a.err, 1);
+            y = -1;
+        }
+    }
+    float tv[kRowSlots];
+    load_teacher_row(a.teacher + (size_t)(valid ? row : 0) * K, valid, sub, K, tv, a.err);
+    double v[kRowSlots];
+#pragma unroll
+    for (int i = 0; i < kRowSlots; ++i) v[i] = (valid && sub + 8 * i < K) ? Z[sub + 8 * i] : 0.0;
+    const double l = distill_row(v, tv, sub, K, y, hard, a.alpha, a.temperature);
+    if (!valid) return;
+#pragma unroll
+    for (int i = 0; i < kRowSlots; ++i)
+        if (sub + 8 * i < K) Z[sub + 8 * i] = v[i];
+    if (sub == 0) a.rowloss[(size_t)e * a.N + row] = l;
+}
+
 // ---- dA = (D W2) (1 - A^2) in place of A: thread = columns t + 256 i of four rows at a time, so a W2 element serves four rows -----------------
 // grid (ceil(N / kDactRows), E)
 template <int HC>
@@ -340,8 +376,10 @@ __global__ __launch_bounds__(kFitCtrlThreads) void mlp_loss_kernel(EvalArgs a) {
 
 int ceil_div(int v, int d) { return (v + d - 1) / d; }
 
-// one evaluation: L and grad L of every running exit; p.tail: mlp_head_fit_scratch_doubles doubles -- hidden rows, logits, the rows' losses
-void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, int E, int N, int H, int K, double l2, hipStream_t s) {
+// one evaluation: L and grad L of every running exit; p.tail: mlp_head_fit_scratch_doubles doubles -- hidden rows, logits, the rows' losses;
+// soft.teacher null: the hard-label objective
+void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, const DistillTargets& soft, int E, int N, int H, int K, double l2,
+                 hipStream_t s) {
     EvalArgs a{};
     a.X = X; a.y = y; a.theta = p.theta; a.theta_stride = p.theta_stride; a.ctrl = p.ctrl; a.err = p.err;
     a.A = static_cast<double*>(p.tail); a.Z = a.A + (size_t)E * N * H; a.rowloss = a.Z + (size_t)E * N * K;
@@ -351,7 +389,10 @@ void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, int 
     hipLaunchKernelGGL((mlp_nt_gemm_kernel<float, true>), dim3(ceil_div(N, TM), ceil_div(H, TN), E), dim3(kThreads), 0, s, hid);
     NtArgs out{a.A, (size_t)N * H, a.theta, a.theta_stride, oW2, ob2, a.Z, (size_t)N * K, a.ctrl, N, K, H};
     hipLaunchKernelGGL((mlp_nt_gemm_kernel<double, false>), dim3(ceil_div(N, TM), ceil_div(K, TN), E), dim3(kThreads), 0, s, out);
-    hipLaunchKernelGGL(mlp_softmax_kernel, dim3(ceil_div(N, kSoftRows), E), dim3(kThreads), 0, s, a);
+    if (soft.teacher)
+        hipLaunchKernelGGL(mlp_distill_softmax_kernel, dim3(ceil_div(N, kSoftRows), E), dim3(kThreads), 0, s,
+                           DistillEvalArgs{a, soft.teacher, soft.alpha, soft.temperature});
+    else hipLaunchKernelGGL(mlp_softmax_kernel, dim3(ceil_div(N, kSoftRows), E), dim3(kThreads), 0, s, a);
     TnArgs g2{a.Z, (size_t)N * K, a.A, (size_t)N * H, a.theta, a.theta_stride, a.grad, a.grad_stride, oW2, ob2, a.ctrl, N, K, H, a.l2};
     hipLaunchKernelGGL((mlp_tn_gemm_kernel<double>), dim3(ceil_div(K, TM), ceil_div(H, TN), E), dim3(kThreads), 0, s, g2);
     const dim3 dgrid(ceil_div(N, kDactRows), E);
@@ -379,14 +420,14 @@ size_t mlp_head_fit_scratch_doubles(int E, int N, int H, int K) { return (size_t
 size_t mlp_head_fit_workspace_bytes(int E, int N, int H, int K, int history) { return mlp_layout(E, N, H, K, history).bytes; }
 
 void launch_mlp_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* scratch,
-                              int* err, double* loss, double* grad, hipStream_t s) {
-    launch_eval({theta, params(H, K), nullptr, err, loss, grad, params(H, K), scratch}, X, y, E, N, H, K, l2, s);
+                              int* err, double* loss, double* grad, hipStream_t s, const DistillTargets& soft) {
+    launch_eval({theta, params(H, K), nullptr, err, loss, grad, params(H, K), scratch}, X, y, soft, E, N, H, K, l2, s);
 }
 
 bool launch_mlp_head_fit(const MlpHeadFitArgs& f, hipStream_t s) {
     const int H = f.H, K = f.K, HH = H * H;
     return run_lbfgs_fit(f, mlp_layout(f.E, f.N, H, K, f.history),
-                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.labels, f.E, f.N, H, K, f.l2, s); },
+                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.labels, f.soft, f.E, f.N, H, K, f.l2, s); },
                          {{0, HH, f.dense_weight, nullptr}, {HH, H, f.dense_bias, nullptr}, {HH + H, K * H, f.weight, nullptr},
                           {HH + H + K * H, K, f.bias, nullptr}}, s);
 }

@@ -13,6 +13,11 @@ For ``exit_head_num_layers = 2``, the reference's default (dense -> tanh -> out_
 tanh(x)), and ``MlpHeadFit.state_dict`` names the four tensors per exit.  That objective is not convex: the fit returns a stationary
 point reached by descent from the start (``status`` 0: gradient norm <= gtol), reproducible bit for bit, not a unique optimum.
 
+Neither fit needs labels: with a fine-tuned checkpoint and unlabelled documents, ``collect_distill_features`` returns the final classifier's
+logits next to the CLS rows, and ``fit_distilled_exit_heads`` / ``fit_distilled_mlp_exit_heads`` fit the same heads to reproduce its
+distribution (``ee_head_fit_distill``, ``ee_mlp_head_fit_distill``: KL at a temperature, optionally mixed with the label loss by ``alpha``;
+the reference declares ``alpha = 1, temperature = 1`` in EETrainingArguments, EE/models/EE_modules.py:288-298, and builds nothing on them).
+
 The learning-to-exit classifier (``use_lte``: ONE ``nn.Linear(H, 1)`` + sigmoid shared by every encoder exit, scored on the CLS row leaving
 the exit's layer) is fitted from the same dump-all forwards (``ee_lte_fit``): ``collect_lte_features`` gathers the CLS rows and the exits'
 policy logits, ``lte_targets`` turns logits and labels into the targets "this exit is wrong here", ``fit_lte_classifier`` minimises the
@@ -84,6 +89,16 @@ def collect_exit_features(engine, batches: Iterable[Mapping], head_layers: int =
     return _cat_batches((rows,) for rows, _ in _dump_all(engine, batches))[0]
 
 
+def collect_distill_features(engine, batches: Iterable[Mapping], head_layers: int = 1):
+    """``collect_exit_features`` for documents without labels.  Returns two device tensors from the same dump-all forwards: ``features``
+    (E,N,H) float32 as above, and ``teacher_logits`` (N,K) float32, the final classifier's logits on the same documents (the last row of
+    ``all_logits``) -- the targets of ``fit_distilled_exit_heads`` / ``fit_distilled_mlp_exit_heads``.  Refusals and inputs are those of
+    ``collect_exit_features``; LayoutLMv3 handles and the image-only DiT handle are supported."""
+    _check_fittable(engine.cfg, head_layers)
+    feats, teacher = _cat_batches((rows, out.all_logits[-1:].to(torch.float32)) for rows, out in _dump_all(engine, batches, want_all=True))
+    return feats, teacher[0]
+
+
 @dataclass
 class HeadFit:
     weight: "torch.Tensor"       # (E,K,H) float32, device
@@ -95,6 +110,8 @@ class HeadFit:
     evals: "torch.Tensor"        # (E,) int32: loss / gradient evaluations used
     status: "torch.Tensor"       # (E,) int32: 0 converged (grad_norm <= gtol), 1 max_evals, 2 the line search made no progress
     l2: float
+    alpha: float = 0.0           # weight of the distillation term (fit_distilled_exit_heads); 0: fitted against labels alone
+    temperature: float = 1.0     # the distillation temperature
 
     def logits(self, features) -> "torch.Tensor":
         """(E,N,K) float64 logits of the float32 heads on ``features`` (E,N,H), on the device."""
@@ -187,13 +204,68 @@ def fit_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-9, max_e
     dev, X = _rows(features, device)
     E, N, H = X.shape
     y, K = _labels(labels, dev, N, num_labels)
-    f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
-    fit = HeadFit(torch.zeros((E, K, H), dtype=torch.float32, device=dev), torch.zeros((E, K), dtype=torch.float32, device=dev),
-                  f64(E, K, H), f64(E, K), f64(E), f64(E), torch.zeros((E,), dtype=torch.int32, device=dev),
-                  torch.full((E,), -1, dtype=torch.int32, device=dev), float(l2))
+    fit = _new_head_fit(dev, E, K, H, l2)
     ws, need = _workspace("ee_head_fit_workspace_bytes", dev, E, N, H, K, history)
     _call("ee_head_fit", dev, X, y, E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.weight, fit.bias,
           fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status)
+    return fit
+
+
+def _new_head_fit(dev, E, K, H, l2, alpha=0.0, temperature=1.0) -> HeadFit:
+    """The outputs of a one-layer fit on ``dev``: zeros, status -1."""
+    f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
+    return HeadFit(torch.zeros((E, K, H), dtype=torch.float32, device=dev), torch.zeros((E, K), dtype=torch.float32, device=dev),
+                   f64(E, K, H), f64(E, K), f64(E), f64(E), torch.zeros((E,), dtype=torch.int32, device=dev),
+                   torch.full((E,), -1, dtype=torch.int32, device=dev), float(l2), float(alpha), float(temperature))
+
+
+# ---- distillation from the final classifier: no labels needed ----------------------------------------------------------------------------
+def _distill_check(features, teacher_logits, labels, alpha, temperature, num_labels) -> int:
+    """The refusals of the distilled fits, from shapes and scalars alone (nothing touches a device) -> K"""
+    fs, ts = tuple(features.shape), tuple(teacher_logits.shape)
+    if len(fs) not in (2, 3):
+        raise ValueError(f"features are {fs}, need (E,N,H), or (N,H) for one exit")
+    N = fs[-2]
+    if len(ts) != 2 or ts[0] != N:
+        raise ValueError(f"teacher_logits are {ts}, need (N,K) with N = {N}: one row of the final classifier's logits per feature row")
+    K = ts[1]
+    if num_labels is not None and int(num_labels) != K:
+        raise ValueError(f"num_labels = {num_labels}, but teacher_logits have K = {K} classes")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha = {alpha}, need 0 <= alpha <= 1")
+    if not 0.0 < temperature < float("inf"):
+        raise ValueError(f"temperature = {temperature}, need a finite temperature > 0")
+    if alpha < 1.0 and labels is None:
+        raise ValueError(f"labels are required at alpha = {alpha} < 1: only alpha = 1 (pure distillation) does without them")
+    return K
+
+
+def _distill_inputs(features, teacher_logits, labels, alpha, temperature, num_labels, device):
+    """-> (dev, X (E,N,H) float32, teacher (N,K) float32, y (N,) int64 or None, K), all on dev"""
+    K = _distill_check(features, teacher_logits, labels, alpha, temperature, num_labels)
+    capi.load()
+    dev, X = _rows(features, device)
+    y = None if labels is None else _labels(labels, dev, X.shape[1], K)[0]
+    return dev, X, _to_device(teacher_logits, torch.float32, dev), y, K
+
+
+def fit_distilled_exit_heads(features, teacher_logits, labels=None, alpha: float = 1.0, temperature: float = 1.0, l2: float = 1e-2,
+                             gtol: float = 1e-9, max_evals: int = 2000, history: int = 8, device=None, num_labels: int = None) -> HeadFit:
+    """``fit_exit_heads`` against the final classifier instead of (or mixed with) labels: ``features`` (E,N,H) float32, ``teacher_logits``
+    (N,K) float32 (``collect_distill_features``), K = ``teacher_logits.shape[1]`` (``num_labels``, when given, must agree).  Minimises, per
+    exit, the mean of (1 - alpha) CE(z, y) + alpha T^2 KL(softmax(t / T) || softmax(z / T)) plus (l2 / 2)(||W||^2 + ||b||^2) in float64
+    (include/mmee.h, ee_head_fit_distill).  The defaults ``alpha = 1, temperature = 1`` are the reference's declared ones
+    (EETrainingArguments): pure self-distillation, and then ``labels`` are not needed and not looked at.  ``alpha < 1`` needs ``labels`` (N,)
+    in [0,K); ``alpha = 0`` is ``fit_exit_heads``' objective.  For 0 <= alpha <= 1 the problem stays strongly convex: one optimum.
+
+    A teacher logit that is not finite (dump-all marks the rows a document never reached with NaN) fails the call, as a label out of range
+    does.  Budget, ``status`` and the one host wait after the last launch are ``fit_exit_heads``'; no wait is spent on ``labels.max()``."""
+    dev, X, T, y, K = _distill_inputs(features, teacher_logits, labels, alpha, temperature, num_labels, device)
+    E, N, H = X.shape
+    fit = _new_head_fit(dev, E, K, H, l2, alpha, temperature)
+    ws, need = _workspace("ee_head_fit_workspace_bytes", dev, E, N, H, K, history)
+    _call("ee_head_fit_distill", dev, X, T, y, E, N, H, K, float(alpha), float(temperature), float(l2), float(gtol), int(max_evals),
+          int(history), ws, need, fit.weight, fit.bias, fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status)
     return fit
 
 
@@ -217,6 +289,8 @@ class MlpHeadFit:
     evals: "torch.Tensor"         # (E,) int32
     status: "torch.Tensor"        # (E,) int32: 0 stationary (grad_norm <= gtol), 1 max_evals, 2 the line search made no progress
     l2: float
+    alpha: float = 0.0            # weight of the distillation term (fit_distilled_mlp_exit_heads); 0: fitted against labels alone
+    temperature: float = 1.0      # the distillation temperature
 
     def logits(self, features) -> "torch.Tensor":
         """(E,N,K) float64 logits of the float32 heads on ``features`` (E,N,H), on the device."""
@@ -282,14 +356,36 @@ def fit_mlp_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-6, m
     E, N, H = X.shape
     y, K = _labels(labels, dev, N, num_labels)
     theta0 = _mlp_theta0(init, E, H, K, dev)
-    P = mlp_param_count(H, K)
-    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-    fit = MlpHeadFit(z((E, H, H), torch.float32), z((E, H), torch.float32), z((E, K, H), torch.float32), z((E, K), torch.float32),
-                     z((E, P), torch.float64), z((E,), torch.float64), z((E,), torch.float64), z((E,), torch.int32),
-                     torch.full((E,), -1, dtype=torch.int32, device=dev), float(l2))
+    fit = _new_mlp_head_fit(dev, E, K, H, l2)
     ws, need = _workspace("ee_mlp_head_fit_workspace_bytes", dev, E, N, H, K, history)
     _call("ee_mlp_head_fit", dev, X, y, theta0, E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.dense_weight,
           fit.dense_bias, fit.weight, fit.bias, fit.theta64, fit.loss, fit.grad_norm, fit.evals, fit.status)
+    return fit
+
+
+def _new_mlp_head_fit(dev, E, K, H, l2, alpha=0.0, temperature=1.0) -> MlpHeadFit:
+    """The outputs of a two-layer fit on ``dev``: zeros, status -1."""
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+    return MlpHeadFit(z((E, H, H), torch.float32), z((E, H), torch.float32), z((E, K, H), torch.float32), z((E, K), torch.float32),
+                      z((E, mlp_param_count(H, K)), torch.float64), z((E,), torch.float64), z((E,), torch.float64), z((E,), torch.int32),
+                      torch.full((E,), -1, dtype=torch.int32, device=dev), float(l2), float(alpha), float(temperature))
+
+
+def fit_distilled_mlp_exit_heads(features, teacher_logits, labels=None, alpha: float = 1.0, temperature: float = 1.0, l2: float = 1e-2,
+                                 gtol: float = 1e-6, max_evals: int = 4000, history: int = 8, init="identity", device=None,
+                                 num_labels: int = None) -> MlpHeadFit:
+    """``fit_mlp_exit_heads`` against the final classifier: the objective of ``fit_distilled_exit_heads`` on the two-layer head
+    (include/mmee.h, ee_mlp_head_fit_distill), from the start ``init`` (``"identity"`` needs no labels either).  Inputs, ``alpha``,
+    ``temperature`` and the failures are those of ``fit_distilled_exit_heads``; budget, ``status`` (a stationary point reached by descent from
+    ``init``: the objective is not convex) and ``init`` are ``fit_mlp_exit_heads``'."""
+    dev, X, T, y, K = _distill_inputs(features, teacher_logits, labels, alpha, temperature, num_labels, device)
+    E, N, H = X.shape
+    theta0 = _mlp_theta0(init, E, H, K, dev)
+    fit = _new_mlp_head_fit(dev, E, K, H, l2, alpha, temperature)
+    ws, need = _workspace("ee_mlp_head_fit_workspace_bytes", dev, E, N, H, K, history)
+    _call("ee_mlp_head_fit_distill", dev, X, T, y, theta0, E, N, H, K, float(alpha), float(temperature), float(l2), float(gtol),
+          int(max_evals), int(history), ws, need, fit.dense_weight, fit.dense_bias, fit.weight, fit.bias, fit.theta64, fit.loss, fit.grad_norm,
+          fit.evals, fit.status)
     return fit
 
 
