@@ -753,6 +753,52 @@ int ee_debug_mlp_head_distill_lossgrad(const float* features, const float* teach
                                        void* stream);
 
 /*
+ * The four head fits above with a weight per (exit, document): exit e under an early-exit policy only sees the documents no earlier exit
+ * released ("train by exiting already when CSF is high enough", EE/models/EE_modules.py:33-37), a class-imbalanced set wants balanced
+ * classes, and a held-out fold is a 0/1 mask over features that stay where they are.  Per exit e, independently, with w (E,N) float32,
+ * w[e][n] >= 0 and finite, W_e = sum_n w[e][n] > 0:
+ *
+ *     L_e(theta) = (1 / W_e) sum_n w[e][n] l_n(theta) + (l2 / 2) ||theta||^2
+ *
+ * l_n is the row loss of the unweighted fit: logsumexp(z_n) - z_n[y_n] (ee_head_fit, ee_mlp_head_fit), or the mixed
+ * (1 - alpha) CE + alpha T^2 KL row loss of the distilled fits.  The penalty, the L-BFGS, the stopping rules, the status codes and the
+ * limits are those of the unweighted fits; the one-layer problem stays l2-strongly convex.  All-ones weights are the unweighted fit bit
+ * for bit, and w and c w with c a power of two return the same bits.
+ *
+ * teacher_logits == NULL selects the labelled objective: alpha must then be 0, temperature is ignored and labels are required.  Otherwise
+ * the arguments are those of the distilled fits (labels may be NULL at alpha == 1).  weights dev (E,N) float32 is required.
+ * How: one kernel per call sums W_e in float64 in a fixed order and writes scale[e][n] = (double) w[e][n] * ((double) N / W_e) into the
+ * workspace (8 bytes per (exit, row) on top of the unweighted workspace: ee_head_fit_weighted_workspace_bytes /
+ * ee_mlp_head_fit_weighted_workspace_bytes); the row step multiplies the row's N dL/dz and its loss by it, as one last multiplication, and
+ * everything behind the row step is the unweighted fit's, division by N included.  A row with w[e][n] == 0 contributes zeros: neither its
+ * label nor its teacher row is read or checked, so they may hold anything.  Its FEATURES still pass through the gradient sums as 0 * x
+ * and must be finite: 0 * NaN is not defended against.
+ * The error word: bits 0 and 1 as above (on rows of positive weight), bit 2 a weight that is negative or not finite, bit 3 an exit whose
+ * weights sum to zero.  Each fails the call with a message and leaves no output written; the call learns of it by the one wait after its
+ * last launch.  Determinism as above: no floating-point atomics, every sum in an order that depends on (N, H, K) alone, nothing depends
+ * on E, two calls return the same bits.
+ * ee_debug_head_weighted_lossgrad / ee_debug_mlp_head_weighted_lossgrad: ONE evaluation of L_e and grad L_e at theta64 dev (E,P), as the
+ *   hooks above; the row scales are made inside the call.
+ */
+int ee_head_fit_weighted(const float* features, const int64_t* labels, const float* teacher_logits, const float* weights, int32_t E, int32_t N,
+                         int32_t H, int32_t K, double alpha, double temperature, double l2, double gtol, int32_t max_evals, int32_t history,
+                         void* workspace, size_t workspace_bytes, float* weight, float* bias, double* weight64, double* bias64, double* loss,
+                         double* grad_norm, int32_t* evals, int32_t* status, void* stream);
+size_t ee_head_fit_weighted_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history);
+int ee_debug_head_weighted_lossgrad(const float* features, const int64_t* labels, const float* teacher_logits, const float* weights,
+                                    const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K, double alpha, double temperature, double l2,
+                                    double* loss, double* grad, void* stream);
+int ee_mlp_head_fit_weighted(const float* features, const int64_t* labels, const float* teacher_logits, const float* weights, const double* theta0,
+                             int32_t E, int32_t N, int32_t H, int32_t K, double alpha, double temperature, double l2, double gtol,
+                             int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* dense_weight, float* dense_bias,
+                             float* weight, float* bias, double* theta64, double* loss, double* grad_norm, int32_t* evals, int32_t* status,
+                             void* stream);
+size_t ee_mlp_head_fit_weighted_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history);
+int ee_debug_mlp_head_weighted_lossgrad(const float* features, const int64_t* labels, const float* teacher_logits, const float* weights,
+                                        const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K, double alpha, double temperature,
+                                        double l2, double* loss, double* grad, void* stream);
+
+/*
  * The learning-to-exit classifier (ee_config.use_lte) fitted on the device from the CLS rows of a frozen backbone.  The reference trains it
  * inside EETrainer (EE/models/LayoutLMv3.py:795-857: lte_loss_fct = MSELoss against 1 - lte_gold, one MSE per exit, summed); here it is one
  * deterministic batch problem.  ONE classifier theta = (w (H,), b) is shared by all encoder exits, as in the reference (init_lte: one

@@ -21,6 +21,6 @@ from . import metrics  # noqa: F401,E402
 from .metrics import ExitReport, exit_report  # noqa: F401,E402
 from . import feed  # noqa: F401,E402
 from . import heads  # noqa: F401,E402
-from .heads import (HeadFit, LteFit, MlpHeadFit, collect_distill_features, collect_exit_features, collect_lte_features,  # noqa: F401,E402
-                    fit_distilled_exit_heads, fit_distilled_mlp_exit_heads, fit_exit_heads, fit_lte_classifier, fit_mlp_exit_heads,
-                    lte_targets)
+from .heads import (HeadFit, LteFit, MlpHeadFit, balanced_class_weights, collect_distill_features, collect_exit_features,  # noqa: F401,E402
+                    collect_lte_features, fit_distilled_exit_heads, fit_distilled_mlp_exit_heads, fit_exit_heads, fit_lte_classifier,
+                    fit_mlp_exit_heads, lte_targets, reach_weights)

@@ -1,5 +1,6 @@
 // Entry points of the device fits, none of which sees a handle: one-layer and two-layer exit heads (ee_head_fit, ee_mlp_head_fit; against the
-// final classifier's logits instead of labels: ee_head_fit_distill, ee_mlp_head_fit_distill, through the same bodies) and the
+// final classifier's logits instead of labels: ee_head_fit_distill, ee_mlp_head_fit_distill; either with sample weights: ee_head_fit_weighted,
+// ee_mlp_head_fit_weighted; all through the same bodies) and the
 // learning-to-exit classifier (ee_lte_fit, with ee_lte_targets and ee_lte_scores) from dumped CLS rows, their workspace queries, and the
 // ee_debug_*_lossgrad hooks that run one evaluation of an objective on caller-provided buffers.  The L-BFGS is fit_lbfgs.hip.
 #include "capi_internal.h"
@@ -26,14 +27,23 @@ static int budget_refuse(const char* who, double gtol, int32_t max_evals, int32_
 
 static const char* const kBadTeacher = "%s: a teacher logit is not finite (dump-all marks the rows a document never reached with NaN)%s";
 
+// bits 2 and 3 of the error word are the weighted head fits' (launch_row_scale); checked first: labels and teacher rows mean nothing under them
+static int weight_error(const char* who, int err, const char* tail) {
+    if (err & 4) return fail(nullptr, "%s: a sample weight is negative or not finite%s", who, tail);
+    if (err & 8) return fail(nullptr, "%s: an exit's weights sum to zero%s", who, tail);
+    return 0;
+}
+
 // The tail of a call that left an error word on the device: the launch status, the word read on the stream, one synchronise.  bad: the
-// message for bit 0 (bad input), a format of (who, K).  Bit 1 is the distilled fits': a teacher logit that is not finite.
+// message for bit 0 (bad input), a format of (who, K).  Bit 1 is the distilled fits': a teacher logit that is not finite; bits 2 and 3 are the
+// weighted fits'.
 static int finish_call(const char* who, bool prepared, const void* err_word, hipStream_t s, const char* bad, int K) {
     if (!prepared) return fail(nullptr, "%s: preparing the workspace (memset, copy of theta0) failed", who);
     if (launch_status(nullptr, who)) return 1;
     int err = 0;
     if (hipMemcpyAsync(&err, err_word, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
         return fail(nullptr, "%s: reading the error word failed: %s", who, hipGetErrorString(hipGetLastError()));
+    if (weight_error(who, err, "; no output was written")) return 1;
     if (err & 1) return fail(nullptr, bad, who, K);
     if (err & 2) return fail(nullptr, kBadTeacher, who, "; no output was written");
     return 0;
@@ -53,6 +63,7 @@ static int debug_lossgrad(const char* who, size_t n, hipStream_t s, Launch launc
     int err = 0;
     if (hipMemcpy(&err, err_dev, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of the error word failed", who);
     if (launch_status(nullptr, who)) return 1;
+    if (weight_error(who, err, "")) return 1;
     if (err & 1) return fail(nullptr, bad, who, K);
     if (err & 2) return fail(nullptr, kBadTeacher, who, "");
     return 0;
@@ -87,7 +98,7 @@ static int lte_objective_refuse(const char* who, int32_t loss, double l2) {
 static const char* const kBadLabelFit = "%s: a label is outside [0, K = %d); no output was written";
 static const char* const kBadLabel = "%s: a label is outside [0, K = %d)";
 
-// ---- the head fits' entry points, hard-label and distilled, as one body each ---------------------------------------------------------------------
+// ---- the head fits' entry points, hard-label, distilled and weighted, as one body each ---------------------------------------------------------
 // soft: null for the entry points that fit against labels; else the distilled objective's targets, refused here before any device call
 static int distill_refuse(const char* who, const int64_t* labels, const DistillTargets* soft) {
     if (!soft) return 0;
@@ -99,23 +110,35 @@ static int distill_refuse(const char* who, const int64_t* labels, const DistillT
     return 0;
 }
 
-static int head_fit_call(const char* who, const float* features, const int64_t* labels, const DistillTargets* soft, int32_t E, int32_t N,
-                         int32_t H, int32_t K, double l2, double gtol, int32_t max_evals, int32_t history, void* workspace,
+// The weighted entry points name their objective by teacher_logits, which may be NULL (labels alone): their refusals in front of the shared
+// ones.  -> the soft targets to hand on, null for the labelled objective
+static int weighted_refuse(const char* who, const float* weights, const DistillTargets& soft) {
+    if (!weights) return fail(nullptr, "%s: NULL argument (weights are required: (E,N) float32; the unweighted entry points take none)", who);
+    if (!soft.teacher && soft.alpha != 0.0)
+        return fail(nullptr, "%s: alpha = %g without teacher_logits: NULL teacher_logits select the labelled objective, alpha must be 0", who,
+                    soft.alpha);
+    return 0;
+}
+
+// weights: null for the entry points that have none; the weighted ones have refused a NULL table before they come here
+static int head_fit_call(const char* who, const float* features, const int64_t* labels, const DistillTargets* soft, const float* weights,
+                         int32_t E, int32_t N, int32_t H, int32_t K, double l2, double gtol, int32_t max_evals, int32_t history, void* workspace,
                          size_t workspace_bytes, float* weight, float* bias, double* weight64, double* bias64, double* loss, double* grad_norm,
                          int32_t* evals, int32_t* status, void* stream) {
     if (!features || (!soft && !labels) || !workspace || !weight || !bias)
         return fail(nullptr, "%s: NULL argument (features, %s, workspace, weight and bias are required)", who, soft ? "teacher_logits" : "labels");
     if (distill_refuse(who, labels, soft) || head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
-    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return head_fit_workspace_bytes(E, N, H, K, history); })) return 1;
+    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return head_fit_workspace_bytes(E, N, H, K, history, weights != nullptr); }))
+        return 1;
     if (!have_device(who)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const HeadFitArgs a{{features, E, N, H, l2, gtol, max_evals, history, workspace, nullptr, nullptr, loss, grad_norm, evals, status},
-                        reinterpret_cast<const long long*>(labels), K, weight, bias, weight64, bias64, soft ? *soft : DistillTargets{}};
+                        reinterpret_cast<const long long*>(labels), K, weight, bias, weight64, bias64, soft ? *soft : DistillTargets{}, weights};
     return finish_call(who, launch_head_fit(a, s), workspace, s, kBadLabelFit, K);
 }
 
-static int mlp_head_fit_call(const char* who, const float* features, const int64_t* labels, const DistillTargets* soft, const double* theta0,
-                             int32_t E, int32_t N, int32_t H, int32_t K, double l2, double gtol, int32_t max_evals, int32_t history,
+static int mlp_head_fit_call(const char* who, const float* features, const int64_t* labels, const DistillTargets* soft, const float* weights,
+                             const double* theta0, int32_t E, int32_t N, int32_t H, int32_t K, double l2, double gtol, int32_t max_evals, int32_t history,
                              void* workspace, size_t workspace_bytes, float* dense_weight, float* dense_bias, float* weight, float* bias,
                              double* theta64, double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
     if (!features || (!soft && !labels) || !theta0 || !workspace || !dense_weight || !dense_bias || !weight || !bias)
@@ -123,27 +146,31 @@ static int mlp_head_fit_call(const char* who, const float* features, const int64
                              "theta = 0 is a saddle the iteration never leaves, so there is no default start)", who,
                     soft ? "teacher_logits" : "labels");
     if (distill_refuse(who, labels, soft) || head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
-    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return mlp_head_fit_workspace_bytes(E, N, H, K, history); })) return 1;
+    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes,
+                      [&] { return mlp_head_fit_workspace_bytes(E, N, H, K, history, weights != nullptr); }))
+        return 1;
     if (!have_device(who)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const MlpHeadFitArgs a{{features, E, N, H, l2, gtol, max_evals, history, workspace, theta0, theta64, loss, grad_norm, evals, status},
-                           reinterpret_cast<const long long*>(labels), K, dense_weight, dense_bias, weight, bias, soft ? *soft : DistillTargets{}};
+                           reinterpret_cast<const long long*>(labels), K, dense_weight, dense_bias, weight, bias, soft ? *soft : DistillTargets{},
+                           weights};
     return finish_call(who, launch_mlp_head_fit(a, s), workspace, s, kBadLabelFit, K);
 }
 
 // ONE evaluation of a head objective: mlp selects the two-layer head
 static int head_lossgrad_call(const char* who, bool mlp, const float* features, const int64_t* labels, const DistillTargets* soft,
-                              const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K, double l2, double* loss, double* grad,
+                              const float* weights, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K, double l2, double* loss, double* grad,
                               void* stream) {
     if (!features || (!soft && !labels) || !theta64 || !loss || !grad) return fail(nullptr, "%s: NULL argument", who);
     if (distill_refuse(who, labels, soft) || head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long long* y = reinterpret_cast<const long long*>(labels);
     const DistillTargets targets = soft ? *soft : DistillTargets{};
-    const size_t n = mlp ? mlp_head_fit_scratch_doubles(E, N, H, K) : head_fit_partial_bytes(E, N, H, K) / sizeof(double);
+    const size_t n = (mlp ? mlp_head_fit_scratch_doubles(E, N, H, K) : head_fit_partial_bytes(E, N, H, K) / sizeof(double)) +
+                     (weights ? (size_t)E * N : 0);                                 // the row scales lie behind the unweighted scratch
     return debug_lossgrad(who, n, s, [&](double* scratch, int* err) {
-        if (mlp) launch_mlp_head_lossgrad(features, y, theta64, E, N, H, K, l2, scratch, err, loss, grad, s, targets);
-        else launch_head_lossgrad(features, y, theta64, E, N, H, K, l2, scratch, err, loss, grad, s, targets);
+        if (mlp) launch_mlp_head_lossgrad(features, y, theta64, E, N, H, K, l2, scratch, err, loss, grad, s, targets, weights);
+        else launch_head_lossgrad(features, y, theta64, E, N, H, K, l2, scratch, err, loss, grad, s, targets, weights);
     }, kBadLabel, K);
 }
 
@@ -158,7 +185,7 @@ size_t ee_head_fit_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, i
 int ee_head_fit(const float* features, const int64_t* labels, int32_t E, int32_t N, int32_t H, int32_t K, double l2, double gtol,
                 int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* weight, float* bias, double* weight64,
                 double* bias64, double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
-    return head_fit_call("ee_head_fit", features, labels, nullptr, E, N, H, K, l2, gtol, max_evals, history, workspace, workspace_bytes, weight,
+    return head_fit_call("ee_head_fit", features, labels, nullptr, nullptr, E, N, H, K, l2, gtol, max_evals, history, workspace, workspace_bytes, weight,
                          bias, weight64, bias64, loss, grad_norm, evals, status, stream);
 }
 
@@ -167,20 +194,20 @@ int ee_head_fit_distill(const float* features, const float* teacher_logits, cons
                         size_t workspace_bytes, float* weight, float* bias, double* weight64, double* bias64, double* loss, double* grad_norm,
                         int32_t* evals, int32_t* status, void* stream) {
     const DistillTargets soft{teacher_logits, alpha, temperature};
-    return head_fit_call("ee_head_fit_distill", features, labels, &soft, E, N, H, K, l2, gtol, max_evals, history, workspace, workspace_bytes,
+    return head_fit_call("ee_head_fit_distill", features, labels, &soft, nullptr, E, N, H, K, l2, gtol, max_evals, history, workspace, workspace_bytes,
                          weight, bias, weight64, bias64, loss, grad_norm, evals, status, stream);
 }
 
 int ee_debug_head_lossgrad(const float* features, const int64_t* labels, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K,
                            double l2, double* loss, double* grad, void* stream) {
-    return head_lossgrad_call("ee_debug_head_lossgrad", false, features, labels, nullptr, theta64, E, N, H, K, l2, loss, grad, stream);
+    return head_lossgrad_call("ee_debug_head_lossgrad", false, features, labels, nullptr, nullptr, theta64, E, N, H, K, l2, loss, grad, stream);
 }
 
 int ee_debug_head_distill_lossgrad(const float* features, const float* teacher_logits, const int64_t* labels, const double* theta64, int32_t E,
                                    int32_t N, int32_t H, int32_t K, double alpha, double temperature, double l2, double* loss, double* grad,
                                    void* stream) {
     const DistillTargets soft{teacher_logits, alpha, temperature};
-    return head_lossgrad_call("ee_debug_head_distill_lossgrad", false, features, labels, &soft, theta64, E, N, H, K, l2, loss, grad, stream);
+    return head_lossgrad_call("ee_debug_head_distill_lossgrad", false, features, labels, &soft, nullptr, theta64, E, N, H, K, l2, loss, grad, stream);
 }
 
 // ---- two-layer exit heads from CLS rows (mlp_head_fit.hip) -------------------------------------------------------------------------------
@@ -193,7 +220,7 @@ int ee_mlp_head_fit(const float* features, const int64_t* labels, const double* 
                     double gtol, int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* dense_weight,
                     float* dense_bias, float* weight, float* bias, double* theta64, double* loss, double* grad_norm, int32_t* evals,
                     int32_t* status, void* stream) {
-    return mlp_head_fit_call("ee_mlp_head_fit", features, labels, nullptr, theta0, E, N, H, K, l2, gtol, max_evals, history, workspace,
+    return mlp_head_fit_call("ee_mlp_head_fit", features, labels, nullptr, nullptr, theta0, E, N, H, K, l2, gtol, max_evals, history, workspace,
                              workspace_bytes, dense_weight, dense_bias, weight, bias, theta64, loss, grad_norm, evals, status, stream);
 }
 
@@ -202,20 +229,72 @@ int ee_mlp_head_fit_distill(const float* features, const float* teacher_logits, 
                             void* workspace, size_t workspace_bytes, float* dense_weight, float* dense_bias, float* weight, float* bias,
                             double* theta64, double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
     const DistillTargets soft{teacher_logits, alpha, temperature};
-    return mlp_head_fit_call("ee_mlp_head_fit_distill", features, labels, &soft, theta0, E, N, H, K, l2, gtol, max_evals, history, workspace,
+    return mlp_head_fit_call("ee_mlp_head_fit_distill", features, labels, &soft, nullptr, theta0, E, N, H, K, l2, gtol, max_evals, history, workspace,
                              workspace_bytes, dense_weight, dense_bias, weight, bias, theta64, loss, grad_norm, evals, status, stream);
 }
 
 int ee_debug_mlp_head_lossgrad(const float* features, const int64_t* labels, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K,
                                double l2, double* loss, double* grad, void* stream) {
-    return head_lossgrad_call("ee_debug_mlp_head_lossgrad", true, features, labels, nullptr, theta64, E, N, H, K, l2, loss, grad, stream);
+    return head_lossgrad_call("ee_debug_mlp_head_lossgrad", true, features, labels, nullptr, nullptr, theta64, E, N, H, K, l2, loss, grad, stream);
 }
 
 int ee_debug_mlp_head_distill_lossgrad(const float* features, const float* teacher_logits, const int64_t* labels, const double* theta64, int32_t E,
                                        int32_t N, int32_t H, int32_t K, double alpha, double temperature, double l2, double* loss, double* grad,
                                        void* stream) {
     const DistillTargets soft{teacher_logits, alpha, temperature};
-    return head_lossgrad_call("ee_debug_mlp_head_distill_lossgrad", true, features, labels, &soft, theta64, E, N, H, K, l2, loss, grad, stream);
+    return head_lossgrad_call("ee_debug_mlp_head_distill_lossgrad", true, features, labels, &soft, nullptr, theta64, E, N, H, K, l2, loss, grad, stream);
+}
+
+// ---- the head fits with sample weights: weights (E,N); teacher_logits NULL selects the labelled objective ------------------------------------
+size_t ee_head_fit_weighted_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history) {
+    if (E < 1 || N < 1 || H < 1 || K < 1 || history < 1) return 0;
+    return head_fit_workspace_bytes(E, N, H, K, history, true);
+}
+
+int ee_head_fit_weighted(const float* features, const int64_t* labels, const float* teacher_logits, const float* weights, int32_t E, int32_t N,
+                         int32_t H, int32_t K, double alpha, double temperature, double l2, double gtol, int32_t max_evals, int32_t history,
+                         void* workspace, size_t workspace_bytes, float* weight, float* bias, double* weight64, double* bias64, double* loss,
+                         double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
+    const char* who = "ee_head_fit_weighted";
+    const DistillTargets soft{teacher_logits, alpha, temperature};
+    if (weighted_refuse(who, weights, soft)) return 1;
+    return head_fit_call(who, features, labels, teacher_logits ? &soft : nullptr, weights, E, N, H, K, l2, gtol, max_evals, history, workspace,
+                         workspace_bytes, weight, bias, weight64, bias64, loss, grad_norm, evals, status, stream);
+}
+
+int ee_debug_head_weighted_lossgrad(const float* features, const int64_t* labels, const float* teacher_logits, const float* weights,
+                                    const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K, double alpha, double temperature, double l2,
+                                    double* loss, double* grad, void* stream) {
+    const char* who = "ee_debug_head_weighted_lossgrad";
+    const DistillTargets soft{teacher_logits, alpha, temperature};
+    if (weighted_refuse(who, weights, soft)) return 1;
+    return head_lossgrad_call(who, false, features, labels, teacher_logits ? &soft : nullptr, weights, theta64, E, N, H, K, l2, loss, grad, stream);
+}
+
+size_t ee_mlp_head_fit_weighted_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history) {
+    if (E < 1 || N < 1 || H < 1 || K < 1 || history < 1) return 0;
+    return mlp_head_fit_workspace_bytes(E, N, H, K, history, true);
+}
+
+int ee_mlp_head_fit_weighted(const float* features, const int64_t* labels, const float* teacher_logits, const float* weights, const double* theta0,
+                             int32_t E, int32_t N, int32_t H, int32_t K, double alpha, double temperature, double l2, double gtol,
+                             int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* dense_weight, float* dense_bias,
+                             float* weight, float* bias, double* theta64, double* loss, double* grad_norm, int32_t* evals, int32_t* status,
+                             void* stream) {
+    const char* who = "ee_mlp_head_fit_weighted";
+    const DistillTargets soft{teacher_logits, alpha, temperature};
+    if (weighted_refuse(who, weights, soft)) return 1;
+    return mlp_head_fit_call(who, features, labels, teacher_logits ? &soft : nullptr, weights, theta0, E, N, H, K, l2, gtol, max_evals, history,
+                             workspace, workspace_bytes, dense_weight, dense_bias, weight, bias, theta64, loss, grad_norm, evals, status, stream);
+}
+
+int ee_debug_mlp_head_weighted_lossgrad(const float* features, const int64_t* labels, const float* teacher_logits, const float* weights,
+                                        const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K, double alpha, double temperature,
+                                        double l2, double* loss, double* grad, void* stream) {
+    const char* who = "ee_debug_mlp_head_weighted_lossgrad";
+    const DistillTargets soft{teacher_logits, alpha, temperature};
+    if (weighted_refuse(who, weights, soft)) return 1;
+    return head_lossgrad_call(who, true, features, labels, teacher_logits ? &soft : nullptr, weights, theta64, E, N, H, K, l2, loss, grad, stream);
 }
 
 // ---- the LTE classifier from CLS rows (lte_fit.hip) --------------------------------------------------------------------------------------

@@ -9,6 +9,9 @@
 // ee_head_fit_distill runs the same two kernels: head_fit_lossgrad_kernel is a template over its argument struct, and what the struct selects
 // (if constexpr) is the row step between the two passes -- the labelled softmax, or the mixed step against the final classifier's logits
 // (distill_row, head_fit_common.h), which reads the teacher's row from global memory: no LDS and no workspace beyond the labelled fit's.
+// ee_head_fit_weighted adds sample weights to either objective, again as argument structs of the same kernel: head_fit_row_scale_kernel makes
+// scale[e][n] = w[e][n] N / W_e once per call, the weighted row steps multiply a row's N dL/dz and its loss by it and skip a row whose scale is
+// zero, and everything behind the row step is shared, division by N included.  The unweighted instantiations are the code they were.
 // This file is the objective; the L-BFGS around it is run_lbfgs_fit (fit_lbfgs.hip), the workspace layout and the control words are in
 // head_fit_common.h.
 //
@@ -47,14 +50,30 @@ struct DistillLossGradArgs : LossGradArgs {
     const float* teacher;            // (N,K)
     double alpha, temperature;
 };
+// ee_head_fit_weighted: either objective with the row-scale table of launch_row_scale; err bits 2 and 3 are the table's
+struct WeightedLossGradArgs : LossGradArgs {
+    const double* scale;             // (E,N): w[e][n] N / W_e
+};
+struct WeightedDistillLossGradArgs : DistillLossGradArgs {
+    const double* scale;
+};
+template <typename Args>
+constexpr bool kDistilled = std::is_base_of_v<DistillLossGradArgs, Args>;
+template <typename Args>
+constexpr bool kWeighted = std::is_same_v<Args, WeightedLossGradArgs> || std::is_same_v<Args, WeightedDistillLossGradArgs>;
 
 // The mixed row step (distill_row, head_fit_common.h) of the slab walk below: the row's logits and the teacher's row -- float32 from global memory,
 // each element read once -- in registers, eight threads a row.  Z [S][Kp] holds the slab's logits and leaves as N dL/dz (zero beyond the slab's
 // rows and beyond K); the row's loss goes to `loss` of the first of its eight threads.  Every thread reads its logits before any of the row
-// writes: they are lanes of one wave.
-__device__ inline void distill_row_step(const DistillLossGradArgs& a, double* Z, int n0, int rows, int K, int Kp, double& loss) {
+// writes: they are lanes of one wave.  The weighted form multiplies the row's N dL/dz and its loss by the row's scale sc (zero for a row
+// that does not exist), last of all, and takes a row whose scale is zero for one that does not exist: neither its label nor its teacher row
+// is read.
+template <typename Args>
+__device__ inline void distill_row_step(const Args& a, double* Z, double sc, int n0, int rows, int K, int Kp, double& loss) {
     const int t = threadIdx.x, row = t >> 3, sub = t & 7;
-    const bool valid = row < rows, hard = a.alpha < 1.0;
+    bool valid = row < rows;
+    const bool hard = a.alpha < 1.0;
+    if constexpr (kWeighted<Args>) valid = sc != 0.0;        // true for a NaN scale too: the error word is raised then
     long long y = -1;
     if (hard) {
         y = valid ? a.y[n0 + row] : 0;
@@ -69,15 +88,16 @@ __device__ inline void distill_row_step(const DistillLossGradArgs& a, double* Z,
 #pragma unroll
     for (int i = 0; i < kRowSlots; ++i) v[i] = sub + 8 * i < K ? Z[row * Kp + sub + 8 * i] : 0.0;
     const double l = distill_row(v, tv, sub, K, y, hard, a.alpha, a.temperature);
-    if (sub == 0 && valid) loss += l;
+    if (sub == 0 && valid) loss += scaled<kWeighted<Args>>(l, sc);
 #pragma unroll
     for (int i = 0; i < kRowSlots; ++i) {
         const int k = sub + 8 * i;
-        if (k < Kp) Z[row * Kp + k] = (valid && k < K) ? v[i] : 0.0;
+        if (k < Kp) Z[row * Kp + k] = (valid && k < K) ? scaled<kWeighted<Args>>(v[i], sc) : 0.0;
     }
 }
 
-// KT classes x HC columns (h = t + 256 i) of the gradient per thread; Args: LossGradArgs (labels) or DistillLossGradArgs (soft targets)
+// KT classes x HC columns (h = t + 256 i) of the gradient per thread; Args: LossGradArgs (labels) or DistillLossGradArgs (soft targets), or
+// the Weighted form of either (sample weights)
 template <int KT, int HC, typename Args>
 __global__ __launch_bounds__(kThreads) void head_fit_lossgrad_kernel(Args a) {
     const int kt = blockIdx.x, c = blockIdx.y, e = blockIdx.z, t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -102,9 +122,12 @@ __global__ __launch_bounds__(kThreads) void head_fit_lossgrad_kernel(Args a) {
     const int slab0 = c * a.slabs_per_chunk, n_slabs = (N + S - 1) / S;
     const int slab1 = slab0 + a.slabs_per_chunk < n_slabs ? slab0 + a.slabs_per_chunk : n_slabs;
 
-    // wave w stages rows w, w + 4, ...: S / 4 rows of HC float4 per lane
+    // wave w stages rows w, w + 4, ...: S / 4 rows of HC float4 per lane; the weighted form fetches the scale of the row whose row step
+    // this thread takes part in (row t >> 3 of the slab; zero beyond N) with them, a gradient pass ahead of its use
     f32x4 pre[S / 4][HC];
+    double sc = 1.0;
     auto fetch = [&](int slab) {
+        if constexpr (kWeighted<Args>) sc = row_scale(a.scale, e, N, (long long)slab * S + (t >> 3));
 #pragma unroll
         for (int r = 0; r < S / 4; ++r) {
             const long long n = (long long)slab * S + w + 4 * r;
@@ -172,11 +195,13 @@ __global__ __launch_bounds__(kThreads) void head_fit_lossgrad_kernel(Args a) {
         }
 
         // ---- the row step, the compile-time difference between the two objectives: the row's loss, N dL/dz in place of Z ----
-        if constexpr (std::is_same_v<Args, DistillLossGradArgs>) distill_row_step(a, Z, n0, rows, K, Kp, loss);
+        if constexpr (kDistilled<Args>) distill_row_step(a, Z, sc, n0, rows, K, Kp, loss);
         else {
-            // max-shifted softmax, loss, D = P - Y: eight threads a row
+            // max-shifted softmax, loss, D = P - Y: eight threads a row.  The weighted form multiplies D and the loss by the row's scale, last
+            // of all; a row whose scale is zero counts as one that does not exist, and its label is not read.
             const int row = t >> 3, sub = t & 7;
-            const bool valid = row < rows;
+            bool valid = row < rows;
+            if constexpr (kWeighted<Args>) valid = sc != 0.0;
             long long y = valid ? a.y[n0 + row] : 0;
             if (y < 0 || y >= K) {
                 atomicOr(a.err, 1);
@@ -195,10 +220,10 @@ __global__ __launch_bounds__(kThreads) void head_fit_lossgrad_kernel(Args a) {
             // read before the loop below turns Z into D: the eight threads of a row are lanes of one wave and LDS operations issue in program
             // order, so no sibling has overwritten Z[row][y] yet.  A mapping that spreads a row over waves needs a barrier here.
             const double zy = y >= 0 ? Z[row * Kp + (int)y] : 0.0;
-            if (sub == 0 && valid && y >= 0) loss += (m + log(sum)) - zy;
+            if (sub == 0 && valid && y >= 0) loss += scaled<kWeighted<Args>>((m + log(sum)) - zy, sc);
             const double inv = 1.0 / sum;
             for (int k = sub; k < Kp; k += 8) {
-                const double d = (valid && k < K) ? exp(Z[row * Kp + k] - m) * inv - (k == (int)y ? 1.0 : 0.0) : 0.0;
+                const double d = (valid && k < K) ? scaled<kWeighted<Args>>(exp(Z[row * Kp + k] - m) * inv - (k == (int)y ? 1.0 : 0.0), sc) : 0.0;
                 Z[row * Kp + k] = d;
             }
         }
@@ -285,10 +310,33 @@ __global__ __launch_bounds__(kThreads) void head_fit_reduce_kernel(ReduceArgs a)
     }
 }
 
-// the one-layer fit's workspace: behind the shared part, one partial (dW, db, loss) per (exit, chunk)
-FitLayout one_layer_layout(int E, int N, int H, int K, int M) {
-    return FitLayout(E, K * H + K, M, head_fit_partial_bytes(E, N, H, K));
+// ---- the weighted fits' row scales: scale[e][n] = w[e][n] N / W_e, W_e = sum_n w[e][n] in float64 -- strided partial sums, then the fixed tree
+// of block_sum, as mlp_loss_kernel sums the rows' losses.  Bit 2 of the error word: a weight that is negative or not finite; bit 3: W_e == 0.
+// grid (E): one workgroup an exit, once per call
+__global__ __launch_bounds__(kFitCtrlThreads) void head_fit_row_scale_kernel(const float* weights, int N, double* scale, int* err) {
+    const int e = blockIdx.x, t = threadIdx.x;
+    __shared__ double red[kFitCtrlThreads];
+    const float* w = weights + (size_t)e * N;
+    double sum = 0.0;
+    bool bad = false;
+    for (int i = t; i < N; i += kFitCtrlThreads) {
+        const float v = w[i];
+        bad |= !(v >= 0.f) || !__builtin_isfinite(v);
+        sum += (double)v;
+    }
+    if (bad) atomicOr(err, 4);
+    sum = block_sum<kFitCtrlThreads>(sum, red);
+    if (t == 0 && sum == 0.0) atomicOr(err, 8);
+    const double unit = (double)N / sum;
+    double* out = scale + (size_t)e * N;
+    for (int i = t; i < N; i += kFitCtrlThreads) out[i] = (double)w[i] * unit;
 }
+
+// the one-layer fit's workspace: behind the shared part, one partial (dW, db, loss) per (exit, chunk), then the weighted fit's row scales
+FitLayout one_layer_layout(int E, int N, int H, int K, int M, bool weighted) {
+    return FitLayout(E, K * H + K, M, head_fit_partial_bytes(E, N, H, K) + (weighted ? sizeof(double) * (size_t)E * N : 0));
+}
+double* scale_table(void* tail, int E, int N, int H, int K) { return reinterpret_cast<double*>(static_cast<char*>(tail) + head_fit_partial_bytes(E, N, H, K)); }
 
 size_t lossgrad_lds_bytes(int H, int K) {
     return sizeof(float) * S * (size_t)(H + 4) + sizeof(double) * S * (size_t)round_up(K, 16) + sizeof(double) * 4 * S * kLogitTile;
@@ -317,16 +365,21 @@ void launch_lossgrad(const Args& a, int E, hipStream_t s) {
     else launch_lossgrad_k<16>(a, E, s);
 }
 
-// one evaluation: the partials of every running exit, then their fixed-order sums; soft.teacher null: the hard-label objective
-void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, const DistillTargets& soft, int E, int N, int H, int K, double l2,
-                 hipStream_t s) {
+// one evaluation: the partials of every running exit, then their fixed-order sums; soft.teacher null: the hard-label objective; weighted: the
+// row scales lie behind the partials in p.tail
+void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, const DistillTargets& soft, bool weighted, int E, int N, int H, int K,
+                 double l2, hipStream_t s) {
     LossGradArgs a{};
     a.X = X; a.y = y; a.theta = p.theta; a.theta_stride = p.theta_stride; a.ctrl = p.ctrl; a.err = p.err;
     a.partial = static_cast<double*>(p.tail); a.N = N; a.H = H; a.K = K;
     const int n_slabs = (a.N + S - 1) / S;
     a.chunks = head_fit_chunks(a.N);
     a.slabs_per_chunk = (n_slabs + a.chunks - 1) / a.chunks;
-    if (soft.teacher) launch_lossgrad(DistillLossGradArgs{a, soft.teacher, soft.alpha, soft.temperature}, E, s);
+    const DistillLossGradArgs d{a, soft.teacher, soft.alpha, soft.temperature};
+    const double* scale = weighted ? scale_table(p.tail, E, N, H, K) : nullptr;
+    if (scale && soft.teacher) launch_lossgrad(WeightedDistillLossGradArgs{d, scale}, E, s);
+    else if (scale) launch_lossgrad(WeightedLossGradArgs{a, scale}, E, s);
+    else if (soft.teacher) launch_lossgrad(d, E, s);
     else launch_lossgrad(a, E, s);
     ReduceArgs r{};
     r.partial = a.partial; r.theta = a.theta; r.theta_stride = a.theta_stride; r.ctrl = a.ctrl; r.loss = p.loss; r.loss_stride = 1;
@@ -344,21 +397,32 @@ int head_fit_chunks(int N) {
     return (n_slabs + per - 1) / per;
 }
 
-size_t head_fit_workspace_bytes(int E, int N, int H, int K, int history) { return one_layer_layout(E, N, H, K, history).bytes; }
+size_t head_fit_workspace_bytes(int E, int N, int H, int K, int history, bool weighted) {
+    return one_layer_layout(E, N, H, K, history, weighted).bytes;
+}
 
 size_t head_fit_partial_bytes(int E, int N, int H, int K) { return sizeof(double) * (size_t)E * head_fit_chunks(N) * (size_t)(K * H + K + 1); }
 
+void launch_row_scale(const float* weights, int E, int N, double* scale, int* err, hipStream_t s) {
+    hipLaunchKernelGGL(head_fit_row_scale_kernel, dim3(E), dim3(kFitCtrlThreads), 0, s, weights, N, scale, err);
+}
+
 void launch_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* partial, int* err,
-                          double* loss, double* grad, hipStream_t s, const DistillTargets& soft) {
+                          double* loss, double* grad, hipStream_t s, const DistillTargets& soft, const float* weights) {
     const size_t P = (size_t)K * H + K;
-    launch_eval({theta, P, nullptr, err, loss, grad, P, partial}, X, y, soft, E, N, H, K, l2, s);
+    if (weights) launch_row_scale(weights, E, N, scale_table(partial, E, N, H, K), err, s);
+    launch_eval({theta, P, nullptr, err, loss, grad, P, partial}, X, y, soft, weights != nullptr, E, N, H, K, l2, s);
 }
 
 bool launch_head_fit(const HeadFitArgs& f, hipStream_t s) {
     const int KH = f.K * f.H;
-    return run_lbfgs_fit(f, one_layer_layout(f.E, f.N, f.H, f.K, f.history),
-                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.labels, f.soft, f.E, f.N, f.H, f.K, f.l2, s); },
-                         {{0, KH, f.weight, f.weight64}, {KH, f.K, f.bias, f.bias64}}, s);
+    const bool weighted = f.weights != nullptr;
+    return run_lbfgs_fit(f, one_layer_layout(f.E, f.N, f.H, f.K, f.history, weighted),
+                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.labels, f.soft, weighted, f.E, f.N, f.H, f.K, f.l2, s); },
+                         {{0, KH, f.weight, f.weight64}, {KH, f.K, f.bias, f.bias64}}, s,
+                         weighted ? std::function<void(const FitEvalPoint&)>([&](const FitEvalPoint& p) {
+                             launch_row_scale(f.weights, f.E, f.N, scale_table(p.tail, f.E, f.N, f.H, f.K), p.err, s);
+                         }) : nullptr);
 }
 
 }  // namespace mmee

@@ -113,6 +113,25 @@ __device__ inline double distill_row(double (&v)[kRowSlots], const float (&tv)[k
     return (hard && y >= 0 ? keep * ((m + log(s1)) - zy) : 0.0) + soft * T * kl;
 }
 
+// ---- sample weights (ee_head_fit_weighted, ee_mlp_head_fit_weighted; include/mmee.h states the objective) ------------------------------------
+// The weighted fits scale a row's N dL/dz and its loss by scale[e][n] = w[e][n] N / W_e and change nothing behind the row step: every later
+// kernel divides by N as before.  launch_row_scale (head_fit.hip) makes the table once per call, one workgroup per exit: W_e in float64 in a
+// fixed order (strided partial sums, then the tree of block_sum), error-word bit 2 for a weight that is negative or not finite, bit 3 for
+// W_e == 0.  A row whose scale is zero is treated by the row steps as a row that does not exist: zeros are written, no loss is added, and
+// neither its label nor its teacher row is read.  Its FEATURES still take part in the gradient pass as 0 * x and must be finite: 0 * NaN is
+// not defended against.
+void launch_row_scale(const float* weights, int E, int N, double* scale, int* err, hipStream_t s);
+
+// scale[e][n] of a row, zero for a row that does not exist
+__device__ inline double row_scale(const double* scale, int e, int N, long long n) { return n < N ? scale[(size_t)e * N + n] : 0.0; }
+
+// v * sc in the weighted form of a row step, v itself in the unweighted one, whose instruction stream has no multiplication to skip
+template <bool WEIGHTED>
+__device__ inline double scaled(double v, double sc) {
+    if constexpr (WEIGHTED) return v * sc;
+    else return v;
+}
+
 // The workspace of one fit.  Per exit: control words, scalars, then the parameter-sized vectors; behind them `tail_bytes` of whatever an
 // evaluation of the objective needs (the one-layer fit's chunk partials, the two-layer fit's hidden rows).  The error word lives at 0.
 struct FitLayout {
@@ -163,9 +182,9 @@ struct FitFinishArgs {
 };
 
 // The whole fit on stream s: the workspace zeroed, f.theta0 ((lay.E, lay.P), null = 0) as the first trial point, f.max_evals ticks of
-// { eval(trial point); controller }, then theta[seg] of every exit to the segments' outputs and f's result pointers.  false: preparing the
-// workspace failed.
+// { eval(trial point); controller }, then theta[seg] of every exit to the segments' outputs and f's result pointers.  prepare, when given,
+// runs once on the zeroed workspace in front of the first tick (the weighted fits' row-scale table).  false: preparing the workspace failed.
 bool run_lbfgs_fit(const FitArgs& f, const FitLayout& lay, const std::function<void(const FitEvalPoint&)>& eval,
-                   std::initializer_list<FitOutSeg> segs, hipStream_t s);
+                   std::initializer_list<FitOutSeg> segs, hipStream_t s, const std::function<void(const FitEvalPoint&)>& prepare = nullptr);
 
 }  // namespace mmee

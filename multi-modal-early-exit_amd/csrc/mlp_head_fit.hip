@@ -10,6 +10,10 @@
 //   mlp_dact_kernel                   dA = (D W2) (1 - A^2)            in place of A
 //   mlp_tn_gemm_kernel<float>         dW1 = dA^T X, db1 = dA^T 1       written as gradient                           2 N H^2 FLOP
 //   mlp_loss_kernel                   L = (sum of the rows' losses) / N + (l2 / 2) ||theta||^2
+// ee_mlp_head_fit_weighted: the two softmax kernels are templates over their argument struct, and the weighted structs select (if constexpr)
+// the row step that multiplies D and the row's loss by scale[e][n] = w[e][n] N / W_e (launch_row_scale, head_fit_common.h, once per call) and
+// skips a row whose scale is zero.  The other six launches are shared, division by N included; the unweighted instantiations are the code
+// they were.
 //
 // Both GEMM kernels are LDS-tiled with BOTH operands staged (64 x 64 output tile, 16 deep, the next tile's global loads in flight behind the
 // products) and multiply with v_mfma_f64_16x16x4_f64: four waves of 32 x 32, four accumulators each.  Its C/D map is NOT the f32 one: lane l,
@@ -18,6 +22,8 @@
 // Determinism: no atomics on floating-point data.  A workgroup owns its output tile and walks the whole summation index in order (H for the
 // NT form, all N rows for the TN form), so every sum has an order that depends on (N, H, K) alone; the exit is the grid's z and nothing
 // depends on E.  The price is paid at small H: the TN form has (H / 64)^2 workgroups an exit, each N / 16 steps long.
+#include <type_traits>
+
 #include "head_fit_common.h"
 
 namespace mmee {
@@ -52,6 +58,15 @@ struct DistillEvalArgs : EvalArgs {
     const float* teacher;            // (N,K)
     double alpha, temperature;
 };
+// ee_mlp_head_fit_weighted: either objective with the row-scale table of launch_row_scale (head_fit_common.h); err bits 2 and 3 are the table's
+struct WeightedEvalArgs : EvalArgs {
+    const double* scale;             // (E,N): w[e][n] N / W_e
+};
+struct WeightedDistillEvalArgs : DistillEvalArgs {
+    const double* scale;
+};
+template <typename Args>
+constexpr bool kWeighted = std::is_same_v<Args, WeightedEvalArgs> || std::is_same_v<Args, WeightedDistillEvalArgs>;
 
 __device__ inline bool stopped(const int* ctrl, int e) { return ctrl && ctrl[e * kCtrlInts + CI_STOP] != 0; }
 
@@ -234,15 +249,30 @@ __global__ __launch_bounds__(kThreads) void mlp_tn_gemm_kernel(TnArgs a) {
     }
 }
 
+// a row whose scale is zero: D = 0 in place of its logits, no loss; Z: the row, sub: the thread's place among the row's eight
+__device__ inline void zero_row(double* Z, double* rowloss, int sub, int K) {
+    for (int k = sub; k < K; k += 8) Z[k] = 0.0;
+    if (sub == 0) *rowloss = 0.0;
+}
+
 // ---- max-shifted softmax of the logits, D = P - Y in their place, the rows' losses: eight threads a row, a row's values in registers ------------
+// Args: EvalArgs, or WeightedEvalArgs: D and the row's loss times the row's scale, last of all; a row whose scale is zero gets zeros and
+// its label is not read (live: the row exists and counts).
 // grid (ceil(N / kSoftRows), E)
-__global__ __launch_bounds__(kThreads) void mlp_softmax_kernel(EvalArgs a) {
+template <typename Args>
+__global__ __launch_bounds__(kThreads) void mlp_softmax_kernel(Args a) {
     const int e = blockIdx.y, t = threadIdx.x, sub = t & 7, K = a.K;
     if (stopped(a.ctrl, e)) return;
     const int row = blockIdx.x * kSoftRows + (t >> 3);
     const bool valid = row < a.N;
+    bool live = valid;
+    double sc = 1.0;
+    if constexpr (kWeighted<Args>) {
+        sc = row_scale(a.scale, e, a.N, row);
+        live = sc != 0.0;
+    }
     double* Z = a.Z + ((size_t)e * a.N + (valid ? row : 0)) * K;
-    long long y = valid ? a.y[row] : 0;
+    long long y = live ? a.y[row] : 0;
     if (y < 0 || y >= K) {
         atomicOr(a.err, 1);
         y = -1;
@@ -252,18 +282,18 @@ __global__ __launch_bounds__(kThreads) void mlp_softmax_kernel(EvalArgs a) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int k = sub + 8 * i;
-        v[i] = (valid && k < K) ? Z[k] : -INFINITY;
+        v[i] = (live && k < K) ? Z[k] : -INFINITY;
         m = fmax(m, v[i]);
     }
     m = fmax(m, __shfl_xor(m, 1));
     m = fmax(m, __shfl_xor(m, 2));
     m = fmax(m, __shfl_xor(m, 4));
-    if (!valid) m = 0.0;
+    if (!live) m = 0.0;
     double sum = 0.0, zy = 0.0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int k = sub + 8 * i;
-        const bool in = valid && k < K;
+        const bool in = live && k < K;
         if (in && k == (int)y) zy = v[i];
         v[i] = in ? exp(v[i] - m) : 0.0;
         sum += v[i];
@@ -275,43 +305,64 @@ __global__ __launch_bounds__(kThreads) void mlp_softmax_kernel(EvalArgs a) {
     zy += __shfl_xor(zy, 2);
     zy += __shfl_xor(zy, 4);
     if (!valid) return;
+    if constexpr (kWeighted<Args>) {
+        if (!live) {
+            zero_row(Z, a.rowloss + (size_t)e * a.N + row, sub, K);
+            return;
+        }
+    }
     const double inv = 1.0 / sum;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int k = sub + 8 * i;
-        if (k < K) Z[k] = v[i] * inv - (k == (int)y ? 1.0 : 0.0);
+        if (k < K) Z[k] = scaled<kWeighted<Args>>(v[i] * inv - (k == (int)y ? 1.0 : 0.0), sc);
     }
-    if (sub == 0) a.rowloss[(size_t)e * a.N + row] = y >= 0 ? (m + log(sum)) - zy : 0.0;
+    if (sub == 0) a.rowloss[(size_t)e * a.N + row] = y >= 0 ? scaled<kWeighted<Args>>((m + log(sum)) - zy, sc) : 0.0;
 }
 
 // ---- the distilled counterpart (ee_mlp_head_fit_distill): the mixed row step of distill_row (head_fit_common.h) on the same rows, writing the
 // same D in place of Z and the same row losses; the teacher's row comes from global memory, each element read once ----------------------------
+// Args: DistillEvalArgs, or WeightedDistillEvalArgs: as for mlp_softmax_kernel; neither the label nor the teacher's row of a row whose scale
+// is zero is read.
 // grid (ceil(N / kSoftRows), E)
-__global__ __launch_bounds__(kThreads) void mlp_distill_softmax_kernel(DistillEvalArgs a) {
+template <typename Args>
+__global__ __launch_bounds__(kThreads) void mlp_distill_softmax_kernel(Args a) {
     const int e = blockIdx.y, t = threadIdx.x, sub = t & 7, K = a.K;
     if (stopped(a.ctrl, e)) return;
     const int row = blockIdx.x * kSoftRows + (t >> 3);
     const bool valid = row < a.N, hard = a.alpha < 1.0;
+    bool live = valid;
+    double sc = 1.0;
+    if constexpr (kWeighted<Args>) {
+        sc = row_scale(a.scale, e, a.N, row);
+        live = sc != 0.0;
+    }
     double* Z = a.Z + ((size_t)e * a.N + (valid ? row : 0)) * K;
     long long y = -1;
     if (hard) {
-        y = valid ? a.y[row] : 0;
+        y = live ? a.y[row] : 0;
         if (y < 0 || y >= K) {
             atomicOr(a.err, 1);
             y = -1;
         }
     }
     float tv[kRowSlots];
-    load_teacher_row(a.teacher + (size_t)(valid ? row : 0) * K, valid, sub, K, tv, a.err);
+    load_teacher_row(a.teacher + (size_t)(valid ? row : 0) * K, live, sub, K, tv, a.err);
     double v[kRowSlots];
 #pragma unroll
-    for (int i = 0; i < kRowSlots; ++i) v[i] = (valid && sub + 8 * i < K) ? Z[sub + 8 * i] : 0.0;
+    for (int i = 0; i < kRowSlots; ++i) v[i] = (live && sub + 8 * i < K) ? Z[sub + 8 * i] : 0.0;
     const double l = distill_row(v, tv, sub, K, y, hard, a.alpha, a.temperature);
     if (!valid) return;
+    if constexpr (kWeighted<Args>) {
+        if (!live) {
+            zero_row(Z, a.rowloss + (size_t)e * a.N + row, sub, K);
+            return;
+        }
+    }
 #pragma unroll
     for (int i = 0; i < kRowSlots; ++i)
-        if (sub + 8 * i < K) Z[sub + 8 * i] = v[i];
-    if (sub == 0) a.rowloss[(size_t)e * a.N + row] = l;
+        if (sub + 8 * i < K) Z[sub + 8 * i] = scaled<kWeighted<Args>>(v[i], sc);
+    if (sub == 0) a.rowloss[(size_t)e * a.N + row] = scaled<kWeighted<Args>>(l, sc);
 }
 
 // ---- dA = (D W2) (1 - A^2) in place of A: thread = columns t + 256 i of four rows at a time, so a W2 element serves four rows -----------------
@@ -377,9 +428,9 @@ __global__ __launch_bounds__(kFitCtrlThreads) void mlp_loss_kernel(EvalArgs a) {
 int ceil_div(int v, int d) { return (v + d - 1) / d; }
 
 // one evaluation: L and grad L of every running exit; p.tail: mlp_head_fit_scratch_doubles doubles -- hidden rows, logits, the rows' losses;
-// soft.teacher null: the hard-label objective
-void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, const DistillTargets& soft, int E, int N, int H, int K, double l2,
-                 hipStream_t s) {
+// soft.teacher null: the hard-label objective; weighted: the row scales (E,N) lie behind the rows' losses
+void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, const DistillTargets& soft, bool weighted, int E, int N, int H, int K,
+                 double l2, hipStream_t s) {
     EvalArgs a{};
     a.X = X; a.y = y; a.theta = p.theta; a.theta_stride = p.theta_stride; a.ctrl = p.ctrl; a.err = p.err;
     a.A = static_cast<double*>(p.tail); a.Z = a.A + (size_t)E * N * H; a.rowloss = a.Z + (size_t)E * N * K;
@@ -389,10 +440,14 @@ void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, cons
     hipLaunchKernelGGL((mlp_nt_gemm_kernel<float, true>), dim3(ceil_div(N, TM), ceil_div(H, TN), E), dim3(kThreads), 0, s, hid);
     NtArgs out{a.A, (size_t)N * H, a.theta, a.theta_stride, oW2, ob2, a.Z, (size_t)N * K, a.ctrl, N, K, H};
     hipLaunchKernelGGL((mlp_nt_gemm_kernel<double, false>), dim3(ceil_div(N, TM), ceil_div(K, TN), E), dim3(kThreads), 0, s, out);
-    if (soft.teacher)
-        hipLaunchKernelGGL(mlp_distill_softmax_kernel, dim3(ceil_div(N, kSoftRows), E), dim3(kThreads), 0, s,
-                           DistillEvalArgs{a, soft.teacher, soft.alpha, soft.temperature});
-    else hipLaunchKernelGGL(mlp_softmax_kernel, dim3(ceil_div(N, kSoftRows), E), dim3(kThreads), 0, s, a);
+    const dim3 sgrid(ceil_div(N, kSoftRows), E);
+    const DistillEvalArgs d{a, soft.teacher, soft.alpha, soft.temperature};
+    const double* scale = weighted ? a.rowloss + (size_t)E * N : nullptr;
+    if (scale && soft.teacher)
+        hipLaunchKernelGGL(mlp_distill_softmax_kernel<WeightedDistillEvalArgs>, sgrid, dim3(kThreads), 0, s, WeightedDistillEvalArgs{d, scale});
+    else if (scale) hipLaunchKernelGGL(mlp_softmax_kernel<WeightedEvalArgs>, sgrid, dim3(kThreads), 0, s, WeightedEvalArgs{a, scale});
+    else if (soft.teacher) hipLaunchKernelGGL(mlp_distill_softmax_kernel<DistillEvalArgs>, sgrid, dim3(kThreads), 0, s, d);
+    else hipLaunchKernelGGL(mlp_softmax_kernel<EvalArgs>, sgrid, dim3(kThreads), 0, s, a);
     TnArgs g2{a.Z, (size_t)N * K, a.A, (size_t)N * H, a.theta, a.theta_stride, a.grad, a.grad_stride, oW2, ob2, a.ctrl, N, K, H, a.l2};
     hipLaunchKernelGGL((mlp_tn_gemm_kernel<double>), dim3(ceil_div(K, TM), ceil_div(H, TN), E), dim3(kThreads), 0, s, g2);
     const dim3 dgrid(ceil_div(N, kDactRows), E);
@@ -409,27 +464,36 @@ void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, cons
 
 size_t params(int H, int K) { return (size_t)H * H + H + (size_t)K * H + K; }
 
-FitLayout mlp_layout(int E, int N, int H, int K, int M) {
-    return FitLayout(E, (int)params(H, K), M, sizeof(double) * mlp_head_fit_scratch_doubles(E, N, H, K));
+// the weighted fit's row scales (E,N) lie behind the unweighted scratch
+FitLayout mlp_layout(int E, int N, int H, int K, int M, bool weighted) {
+    return FitLayout(E, (int)params(H, K), M, sizeof(double) * (mlp_head_fit_scratch_doubles(E, N, H, K) + (weighted ? (size_t)E * N : 0)));
 }
+double* scale_table(void* tail, int E, int N, int H, int K) { return static_cast<double*>(tail) + mlp_head_fit_scratch_doubles(E, N, H, K); }
 
 }  // namespace
 
 size_t mlp_head_fit_scratch_doubles(int E, int N, int H, int K) { return (size_t)E * N * ((size_t)H + K + 1); }
 
-size_t mlp_head_fit_workspace_bytes(int E, int N, int H, int K, int history) { return mlp_layout(E, N, H, K, history).bytes; }
+size_t mlp_head_fit_workspace_bytes(int E, int N, int H, int K, int history, bool weighted) {
+    return mlp_layout(E, N, H, K, history, weighted).bytes;
+}
 
 void launch_mlp_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* scratch,
-                              int* err, double* loss, double* grad, hipStream_t s, const DistillTargets& soft) {
-    launch_eval({theta, params(H, K), nullptr, err, loss, grad, params(H, K), scratch}, X, y, soft, E, N, H, K, l2, s);
+                              int* err, double* loss, double* grad, hipStream_t s, const DistillTargets& soft, const float* weights) {
+    if (weights) launch_row_scale(weights, E, N, scale_table(scratch, E, N, H, K), err, s);
+    launch_eval({theta, params(H, K), nullptr, err, loss, grad, params(H, K), scratch}, X, y, soft, weights != nullptr, E, N, H, K, l2, s);
 }
 
 bool launch_mlp_head_fit(const MlpHeadFitArgs& f, hipStream_t s) {
     const int H = f.H, K = f.K, HH = H * H;
-    return run_lbfgs_fit(f, mlp_layout(f.E, f.N, H, K, f.history),
-                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.labels, f.soft, f.E, f.N, H, K, f.l2, s); },
+    const bool weighted = f.weights != nullptr;
+    return run_lbfgs_fit(f, mlp_layout(f.E, f.N, H, K, f.history, weighted),
+                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.labels, f.soft, weighted, f.E, f.N, H, K, f.l2, s); },
                          {{0, HH, f.dense_weight, nullptr}, {HH, H, f.dense_bias, nullptr}, {HH + H, K * H, f.weight, nullptr},
-                          {HH + H + K * H, K, f.bias, nullptr}}, s);
+                          {HH + H + K * H, K, f.bias, nullptr}}, s,
+                         weighted ? std::function<void(const FitEvalPoint&)>([&](const FitEvalPoint& p) {
+                             launch_row_scale(f.weights, f.E, f.N, scale_table(p.tail, f.E, f.N, H, K), p.err, s);
+                         }) : nullptr);
 }
 
 }  // namespace mmee

@@ -340,16 +340,19 @@ struct HeadFitArgs : FitArgs {       // E parameter sets; theta0 and theta64 nul
     float *weight, *bias;            // (E,K,H), (E,K)
     double *weight64, *bias64;       // the same in float64, or null
     DistillTargets soft;
+    const float* weights = nullptr;  // (E,N) sample weights (ee_head_fit_weighted), or null: every row counts once
 };
 int head_fit_chunks(int N);
-size_t head_fit_workspace_bytes(int E, int N, int H, int K, int history);
+// weighted: the fit carries sample weights, and its workspace the row-scale table (E,N) float64 behind the partials
+size_t head_fit_workspace_bytes(int E, int N, int H, int K, int history, bool weighted = false);
 size_t head_fit_partial_bytes(int E, int N, int H, int K);
 // false: the memset of the workspace failed.  The error word is the first int of the workspace (bit 0: a label outside [0,K); bit 1: a
-// teacher logit that is not finite).
+// teacher logit that is not finite; bit 2: a sample weight that is negative or not finite; bit 3: an exit whose weights sum to zero).
 bool launch_head_fit(const HeadFitArgs& a, hipStream_t s);
-// one evaluation at theta (E, K*H + K): loss (E,), grad (E, K*H + K); partial: head_fit_partial_bytes; err: one zeroed int
+// one evaluation at theta (E, K*H + K): loss (E,), grad (E, K*H + K); partial: head_fit_partial_bytes, with weights (E,N) E * N doubles
+// more behind them; err: one zeroed int
 void launch_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* partial, int* err,
-                          double* loss, double* grad, hipStream_t s, const DistillTargets& soft = {});
+                          double* loss, double* grad, hipStream_t s, const DistillTargets& soft = {}, const float* weights = nullptr);
 // ee_mlp_head_fit (mlp_head_fit.hip): two-layer heads (dense + tanh + out_proj) per exit; theta = W1 (H,H), b1 (H,), W2 (K,H), b2 (K,)
 constexpr int kMlpHeadFitRows = 64;          // the row tile of the GEMM kernels, the largest of the new kernels' tiles (MMEE_MLP_HEAD_FIT_ROWS)
 struct MlpHeadFitArgs : FitArgs {    // E parameter sets; theta0 (E,P) required, theta64 (E,P)
@@ -357,15 +360,18 @@ struct MlpHeadFitArgs : FitArgs {    // E parameter sets; theta0 (E,P) required,
     int K;
     float *dense_weight, *dense_bias, *weight, *bias;   // (E,H,H), (E,H), (E,K,H), (E,K)
     DistillTargets soft;
+    const float* weights = nullptr;  // (E,N) sample weights (ee_mlp_head_fit_weighted), or null: every row counts once
 };
-size_t mlp_head_fit_workspace_bytes(int E, int N, int H, int K, int history);
+size_t mlp_head_fit_workspace_bytes(int E, int N, int H, int K, int history, bool weighted = false);
 size_t mlp_head_fit_scratch_doubles(int E, int N, int H, int K);
 // false: preparing the workspace failed.  The error word is the first int of the workspace (bit 0: a label outside [0,K); bit 1: a teacher
-// logit that is not finite).
+// logit that is not finite; bits 2 and 3: the sample weights, as for launch_head_fit).
 bool launch_mlp_head_fit(const MlpHeadFitArgs& a, hipStream_t s);
-// one evaluation at theta (E,P): loss (E,), grad (E,P); scratch: mlp_head_fit_scratch_doubles doubles; err: one zeroed int
+// one evaluation at theta (E,P): loss (E,), grad (E,P); scratch: mlp_head_fit_scratch_doubles doubles, with weights (E,N) E * N doubles
+// more behind them; err: one zeroed int
 void launch_mlp_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* scratch,
-                              int* err, double* loss, double* grad, hipStream_t s, const DistillTargets& soft = {});
+                              int* err, double* loss, double* grad, hipStream_t s, const DistillTargets& soft = {},
+                              const float* weights = nullptr);
 // ee_lte_fit (lte_fit.hip): the learning-to-exit classifier, one Linear(H, 1) for all encoder exits; theta = w (H,), b
 constexpr int kLteFitRows = 16;              // the rows a workgroup treats as a unit: four waves, four rows in flight each (MMEE_LTE_FIT_ROWS)
 constexpr int kLteFitMaxChunks = 128;        // row chunks (= partial gradients) per exit

@@ -18,6 +18,11 @@ logits next to the CLS rows, and ``fit_distilled_exit_heads`` / ``fit_distilled_
 distribution (``ee_head_fit_distill``, ``ee_mlp_head_fit_distill``: KL at a temperature, optionally mixed with the label loss by ``alpha``;
 the reference declares ``alpha = 1, temperature = 1`` in EETrainingArguments, EE/models/EE_modules.py:288-298, and builds nothing on them).
 
+All four head fits take ``sample_weight``: one weight per document, or one per (exit, document) (``ee_head_fit_weighted``,
+``ee_mlp_head_fit_weighted``: the weighted mean of the same row losses).  ``reach_weights`` turns a policy scan's ``exits`` into the table
+"exit e is asked about document n" (cascade-aware heads), ``balanced_class_weights`` weighs every class alike, and a 0/1 row is a held-out
+mask over features that stay where they are.
+
 The learning-to-exit classifier (``use_lte``: ONE ``nn.Linear(H, 1)`` + sigmoid shared by every encoder exit, scored on the CLS row leaving
 the exit's layer) is fitted from the same dump-all forwards (``ee_lte_fit``): ``collect_lte_features`` gathers the CLS rows and the exits'
 policy logits, ``lte_targets`` turns logits and labels into the targets "this exit is wrong here", ``fit_lte_classifier`` minimises the
@@ -155,6 +160,48 @@ def _labels(labels, dev, N, num_labels):
     return y, K
 
 
+def _weight_shape(features, sample_weight):
+    """The refusal of a ``sample_weight`` of the wrong shape, from shapes alone (nothing touches the library or a device)."""
+    if sample_weight is None:
+        return
+    fs, ws = tuple(features.shape), tuple(np.shape(sample_weight))
+    if len(fs) not in (2, 3):
+        raise ValueError(f"features are {fs}, need (E,N,H), or (N,H) for one exit")
+    E, N = (1 if len(fs) == 2 else fs[0]), fs[-2]
+    if ws != (N,) and ws != (E, N):
+        raise ValueError(f"sample_weight is {ws}, need (N,) = {(N,)} (the same for every exit) or (E,N) = {(E, N)}")
+
+
+def _weights(sample_weight, dev, E, N):
+    """``sample_weight`` (N,) or (E,N), numpy or tensor of any real dtype -> the (E,N) float32 table on dev"""
+    w = _to_device(sample_weight, torch.float32, dev)
+    return (w.unsqueeze(0).expand(E, N) if w.dim() == 1 else w).contiguous()
+
+
+def reach_weights(exits, num_exits: int, device=None) -> "torch.Tensor":
+    """The weight table of cascade-aware heads.  ``exits`` (N,): the exit index at which each document leaves under a policy, as a policy
+    scan returns it (``criterion_scan_device``, ``early_exit``; a document no exit releases has index ``num_exits`` or more).  Returns
+    (num_exits, N) float32 on the device: 1.0 where ``exits[n] >= e`` -- exit e is asked about document n because no earlier exit released
+    it -- else 0.0.  With embedding-level exits refused by the fits, the scan's exit index e < E is encoder head e.  Plain torch, no host
+    synchronisation; a device tensor stays on its device."""
+    dev = exits.device if (torch is not None and isinstance(exits, torch.Tensor) and exits.is_cuda and device is None) \
+        else _require_torch_cuda(device)
+    x = _to_device(exits, torch.int64, dev).view(1, -1)
+    return (x >= torch.arange(int(num_exits), dtype=torch.int64, device=dev).view(-1, 1)).to(torch.float32)
+
+
+def balanced_class_weights(labels, num_labels: int, device=None) -> "torch.Tensor":
+    """(N,) float32 on the device: w_n = N / (K count[y_n]) with K = ``num_labels`` and count[k] the documents of class k, so that every
+    class present weighs N / K in total (scikit-learn's "balanced").  ``labels`` (N,) integers in [0,K).  Plain torch, no host
+    synchronisation."""
+    dev = labels.device if (torch is not None and isinstance(labels, torch.Tensor) and labels.is_cuda and device is None) \
+        else _require_torch_cuda(device)
+    y = _to_device(labels, torch.int64, dev).view(-1)
+    K, N = int(num_labels), y.shape[0]
+    count = torch.zeros((K,), dtype=torch.float64, device=dev).scatter_add_(0, y, torch.ones((N,), dtype=torch.float64, device=dev))
+    return (N / (K * count[y])).to(torch.float32)
+
+
 def _workspace(query, dev, *dims):
     """-> (a device buffer of the bytes ``ee_*_workspace_bytes`` symbol ``query`` asks for ``dims``, their count)"""
     need = int(getattr(capi.load(), query)(*dims))
@@ -188,7 +235,7 @@ def _head_prefix(fit, cfg: ModelConfig):
 
 
 def fit_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-9, max_evals: int = 2000, history: int = 8, device=None,
-                   num_labels: int = None) -> HeadFit:
+                   num_labels: int = None, sample_weight=None) -> HeadFit:
     """``features`` (E,N,H) float32 (numpy or device tensor; (N,H) is one exit), ``labels`` (N,) integers in [0,K) with
     K = ``num_labels`` (default: ``labels.max() + 1``; state it when a class may be absent).  Minimises, per exit, mean cross-entropy +
     (l2 / 2)(||W||^2 + ||b||^2) in float64 (include/mmee.h).  Features and parameters stay on the device.
@@ -198,17 +245,44 @@ def fit_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-9, max_e
     hence the default budget of 2000 (the C entry point has no default) -- a stopped exit costs nothing more, so a generous budget is only
     paid by the exits that use it.  Raise ``max_evals`` when ``status`` is 1.
 
+    ``sample_weight``: ``None`` (every row counts once: ``ee_head_fit``, unchanged), (N,) for every exit alike, or (E,N), one row per exit
+    (``reach_weights``, ``balanced_class_weights``, a 0/1 mask of held-out rows); numpy or device tensor of any real dtype, taken as float32.
+    The mean becomes the weighted mean (1 / W_e) sum_n w[e][n] l_n (``ee_head_fit_weighted``); the problem stays strongly convex.  A row of
+    weight zero is not looked at beyond its features, which must be finite: its label may be anything.  A weight that is negative or not
+    finite, or an exit whose weights sum to zero, fails the call.
+
     Host synchronisation: the call waits for its stream once, after the last launch, to read the error word (a label outside [0,K) fails
     the call); with ``num_labels=None`` reading ``labels.max()`` is a second wait, before the first launch."""
+    _weight_shape(features, sample_weight)
     capi.load()
     dev, X = _rows(features, device)
     E, N, H = X.shape
     y, K = _labels(labels, dev, N, num_labels)
     fit = _new_head_fit(dev, E, K, H, l2)
-    ws, need = _workspace("ee_head_fit_workspace_bytes", dev, E, N, H, K, history)
-    _call("ee_head_fit", dev, X, y, E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.weight, fit.bias,
-          fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status)
+    if sample_weight is None:
+        ws, need = _workspace("ee_head_fit_workspace_bytes", dev, E, N, H, K, history)
+        _call("ee_head_fit", dev, X, y, E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.weight, fit.bias,
+              fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status)
+    else:
+        _weighted_head_fit(fit, dev, X, y, None, _weights(sample_weight, dev, E, N), K, 0.0, 1.0, l2, gtol, max_evals, history)
     return fit
+
+
+def _weighted_head_fit(fit, dev, X, y, teacher, w, K, alpha, temperature, l2, gtol, max_evals, history):
+    """ee_head_fit_weighted into ``fit``; teacher None: the labelled objective (alpha 0)"""
+    E, N, H = X.shape
+    ws, need = _workspace("ee_head_fit_weighted_workspace_bytes", dev, E, N, H, K, history)
+    _call("ee_head_fit_weighted", dev, X, y, teacher, w, E, N, H, K, float(alpha), float(temperature), float(l2), float(gtol), int(max_evals),
+          int(history), ws, need, fit.weight, fit.bias, fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status)
+
+
+def _weighted_mlp_head_fit(fit, dev, X, y, teacher, w, theta0, K, alpha, temperature, l2, gtol, max_evals, history):
+    """ee_mlp_head_fit_weighted into ``fit``; teacher None: the labelled objective (alpha 0)"""
+    E, N, H = X.shape
+    ws, need = _workspace("ee_mlp_head_fit_weighted_workspace_bytes", dev, E, N, H, K, history)
+    _call("ee_mlp_head_fit_weighted", dev, X, y, teacher, w, theta0, E, N, H, K, float(alpha), float(temperature), float(l2), float(gtol),
+          int(max_evals), int(history), ws, need, fit.dense_weight, fit.dense_bias, fit.weight, fit.bias, fit.theta64, fit.loss, fit.grad_norm,
+          fit.evals, fit.status)
 
 
 def _new_head_fit(dev, E, K, H, l2, alpha=0.0, temperature=1.0) -> HeadFit:
@@ -240,9 +314,10 @@ def _distill_check(features, teacher_logits, labels, alpha, temperature, num_lab
     return K
 
 
-def _distill_inputs(features, teacher_logits, labels, alpha, temperature, num_labels, device):
+def _distill_inputs(features, teacher_logits, labels, alpha, temperature, num_labels, device, sample_weight=None):
     """-> (dev, X (E,N,H) float32, teacher (N,K) float32, y (N,) int64 or None, K), all on dev"""
     K = _distill_check(features, teacher_logits, labels, alpha, temperature, num_labels)
+    _weight_shape(features, sample_weight)
     capi.load()
     dev, X = _rows(features, device)
     y = None if labels is None else _labels(labels, dev, X.shape[1], K)[0]
@@ -250,7 +325,8 @@ def _distill_inputs(features, teacher_logits, labels, alpha, temperature, num_la
 
 
 def fit_distilled_exit_heads(features, teacher_logits, labels=None, alpha: float = 1.0, temperature: float = 1.0, l2: float = 1e-2,
-                             gtol: float = 1e-9, max_evals: int = 2000, history: int = 8, device=None, num_labels: int = None) -> HeadFit:
+                             gtol: float = 1e-9, max_evals: int = 2000, history: int = 8, device=None, num_labels: int = None,
+                             sample_weight=None) -> HeadFit:
     """``fit_exit_heads`` against the final classifier instead of (or mixed with) labels: ``features`` (E,N,H) float32, ``teacher_logits``
     (N,K) float32 (``collect_distill_features``), K = ``teacher_logits.shape[1]`` (``num_labels``, when given, must agree).  Minimises, per
     exit, the mean of (1 - alpha) CE(z, y) + alpha T^2 KL(softmax(t / T) || softmax(z / T)) plus (l2 / 2)(||W||^2 + ||b||^2) in float64
@@ -259,13 +335,18 @@ def fit_distilled_exit_heads(features, teacher_logits, labels=None, alpha: float
     in [0,K); ``alpha = 0`` is ``fit_exit_heads``' objective.  For 0 <= alpha <= 1 the problem stays strongly convex: one optimum.
 
     A teacher logit that is not finite (dump-all marks the rows a document never reached with NaN) fails the call, as a label out of range
-    does.  Budget, ``status`` and the one host wait after the last launch are ``fit_exit_heads``'; no wait is spent on ``labels.max()``."""
-    dev, X, T, y, K = _distill_inputs(features, teacher_logits, labels, alpha, temperature, num_labels, device)
+    does.  Budget, ``status`` and the one host wait after the last launch are ``fit_exit_heads``'; no wait is spent on ``labels.max()``.
+    ``sample_weight`` is ``fit_exit_heads``': it weighs the whole mixed row loss, and neither the label nor the teacher row of a row of weight
+    zero is looked at."""
+    dev, X, T, y, K = _distill_inputs(features, teacher_logits, labels, alpha, temperature, num_labels, device, sample_weight)
     E, N, H = X.shape
     fit = _new_head_fit(dev, E, K, H, l2, alpha, temperature)
-    ws, need = _workspace("ee_head_fit_workspace_bytes", dev, E, N, H, K, history)
-    _call("ee_head_fit_distill", dev, X, T, y, E, N, H, K, float(alpha), float(temperature), float(l2), float(gtol), int(max_evals),
-          int(history), ws, need, fit.weight, fit.bias, fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status)
+    if sample_weight is None:
+        ws, need = _workspace("ee_head_fit_workspace_bytes", dev, E, N, H, K, history)
+        _call("ee_head_fit_distill", dev, X, T, y, E, N, H, K, float(alpha), float(temperature), float(l2), float(gtol), int(max_evals),
+              int(history), ws, need, fit.weight, fit.bias, fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status)
+    else:
+        _weighted_head_fit(fit, dev, X, y, T, _weights(sample_weight, dev, E, N), K, alpha, temperature, l2, gtol, max_evals, history)
     return fit
 
 
@@ -337,7 +418,7 @@ def _mlp_theta0(init, E, H, K, dev):
 
 
 def fit_mlp_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-6, max_evals: int = 4000, history: int = 8, init="identity",
-                       device=None, num_labels: int = None) -> MlpHeadFit:
+                       device=None, num_labels: int = None, sample_weight=None) -> MlpHeadFit:
     """Two-layer heads (dense + tanh + out_proj) per exit.  ``features`` (E,N,H) float32 (numpy or device tensor; (N,H) is one exit),
     ``labels`` (N,) integers in [0,K) with K = ``num_labels`` (default: ``labels.max() + 1``).  Minimises, per exit, mean cross-entropy of
     W2 tanh(W1 x + b1) + b2 plus (l2 / 2) ||theta||^2 over all four blocks, in float64 (include/mmee.h), by the L-BFGS of ``fit_exit_heads``.
@@ -350,16 +431,22 @@ def fit_mlp_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-6, m
     descent from ``init``.  Unit-variance features of a few hundred rows need 600 - 1800 evaluations to ``gtol = 1e-6``: hence the default
     budget of 4000; a stopped exit costs nothing more.
 
+    ``sample_weight`` is ``fit_exit_heads``' (``ee_mlp_head_fit_weighted``).
+
     Host synchronisation: as for ``fit_exit_heads``, one wait after the last launch (plus one for ``labels.max()`` without ``num_labels``)."""
+    _weight_shape(features, sample_weight)
     capi.load()
     dev, X = _rows(features, device)
     E, N, H = X.shape
     y, K = _labels(labels, dev, N, num_labels)
     theta0 = _mlp_theta0(init, E, H, K, dev)
     fit = _new_mlp_head_fit(dev, E, K, H, l2)
-    ws, need = _workspace("ee_mlp_head_fit_workspace_bytes", dev, E, N, H, K, history)
-    _call("ee_mlp_head_fit", dev, X, y, theta0, E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.dense_weight,
-          fit.dense_bias, fit.weight, fit.bias, fit.theta64, fit.loss, fit.grad_norm, fit.evals, fit.status)
+    if sample_weight is None:
+        ws, need = _workspace("ee_mlp_head_fit_workspace_bytes", dev, E, N, H, K, history)
+        _call("ee_mlp_head_fit", dev, X, y, theta0, E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), ws, need,
+              fit.dense_weight, fit.dense_bias, fit.weight, fit.bias, fit.theta64, fit.loss, fit.grad_norm, fit.evals, fit.status)
+    else:
+        _weighted_mlp_head_fit(fit, dev, X, y, None, _weights(sample_weight, dev, E, N), theta0, K, 0.0, 1.0, l2, gtol, max_evals, history)
     return fit
 
 
@@ -373,19 +460,23 @@ def _new_mlp_head_fit(dev, E, K, H, l2, alpha=0.0, temperature=1.0) -> MlpHeadFi
 
 def fit_distilled_mlp_exit_heads(features, teacher_logits, labels=None, alpha: float = 1.0, temperature: float = 1.0, l2: float = 1e-2,
                                  gtol: float = 1e-6, max_evals: int = 4000, history: int = 8, init="identity", device=None,
-                                 num_labels: int = None) -> MlpHeadFit:
+                                 num_labels: int = None, sample_weight=None) -> MlpHeadFit:
     """``fit_mlp_exit_heads`` against the final classifier: the objective of ``fit_distilled_exit_heads`` on the two-layer head
     (include/mmee.h, ee_mlp_head_fit_distill), from the start ``init`` (``"identity"`` needs no labels either).  Inputs, ``alpha``,
     ``temperature`` and the failures are those of ``fit_distilled_exit_heads``; budget, ``status`` (a stationary point reached by descent from
-    ``init``: the objective is not convex) and ``init`` are ``fit_mlp_exit_heads``'."""
-    dev, X, T, y, K = _distill_inputs(features, teacher_logits, labels, alpha, temperature, num_labels, device)
+    ``init``: the objective is not convex) and ``init`` are ``fit_mlp_exit_heads``'; ``sample_weight`` is ``fit_distilled_exit_heads``'."""
+    dev, X, T, y, K = _distill_inputs(features, teacher_logits, labels, alpha, temperature, num_labels, device, sample_weight)
     E, N, H = X.shape
     theta0 = _mlp_theta0(init, E, H, K, dev)
     fit = _new_mlp_head_fit(dev, E, K, H, l2, alpha, temperature)
-    ws, need = _workspace("ee_mlp_head_fit_workspace_bytes", dev, E, N, H, K, history)
-    _call("ee_mlp_head_fit_distill", dev, X, T, y, theta0, E, N, H, K, float(alpha), float(temperature), float(l2), float(gtol),
-          int(max_evals), int(history), ws, need, fit.dense_weight, fit.dense_bias, fit.weight, fit.bias, fit.theta64, fit.loss, fit.grad_norm,
-          fit.evals, fit.status)
+    if sample_weight is None:
+        ws, need = _workspace("ee_mlp_head_fit_workspace_bytes", dev, E, N, H, K, history)
+        _call("ee_mlp_head_fit_distill", dev, X, T, y, theta0, E, N, H, K, float(alpha), float(temperature), float(l2), float(gtol),
+              int(max_evals), int(history), ws, need, fit.dense_weight, fit.dense_bias, fit.weight, fit.bias, fit.theta64, fit.loss,
+              fit.grad_norm, fit.evals, fit.status)
+    else:
+        _weighted_mlp_head_fit(fit, dev, X, y, T, _weights(sample_weight, dev, E, N), theta0, K, alpha, temperature, l2, gtol, max_evals,
+                               history)
     return fit
 
 
