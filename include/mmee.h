@@ -896,6 +896,17 @@ int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const
                         int32_t K, int32_t epi, int32_t out_split, float a_scale, float w_scale, float out_scale,
                         const int32_t* row_src, int32_t rows_A, int32_t iters, float* ms_out, void* stream);
 
+/* The same hook for the residual epilogue as the layers launch it (attention output, FFN down): f32 output, a residual of its own rows.
+ * resid is f32 [rows_resid, N]; resid_scale > 0 (a power of two) converts it to split-f16 rows of that scale first, as the layers' residual
+ * (a LayerNorm output) is kept, resid_scale == 0 passes it on as f32.  Cout[r] = A[row_src ? row_src[r] : r] W^T + bias +
+ * resid[resid_row_src ? resid_row_src[r] : r]; row_src must be non-decreasing, resid_row_src may be any rows; both are checked against
+ * rows_A / rows_resid.  route: 0 = the tile configuration the row count selects, as in a forward; 1 = the 128 x 128 configuration (small
+ * launches, probes), which reads the residual straight into registers; 2 = the 256 x 256 configuration, which takes a split residual
+ * through LDS.  All compute the same bits.  ms_out (host float[1], may be NULL): average milliseconds per launch. */
+int ee_debug_gemm_split_resid(const float* A, const float* W, const float* bias, const float* resid, float* Cout, int32_t M, int32_t N,
+                              int32_t K, float a_scale, float w_scale, float resid_scale, const int32_t* row_src, int32_t rows_A,
+                              const int32_t* resid_row_src, int32_t rows_resid, int32_t route, int32_t iters, float* ms_out, void* stream);
+
 /* Unit-test hook of the fused attention kernels: ONE launch of one kernel of the path on caller-provided DEVICE buffers; no handle.
  *   qkv            f32 [qkv_rows][3 H], H = 64 * heads: Q (already divided by sqrt(d)) | K | V of every row
  *   doc_off        int32 [n_docs + 1], doc_off[0] = 0: the ragged documents; row r of document d is context row doc_off[d] + r

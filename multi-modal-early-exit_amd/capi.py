@@ -166,6 +166,8 @@ SYMBOLS = {
     "ee_debug_gemm": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_debug_gemm_split": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp,
                                       _i32, _i32, C.POINTER(C.c_float), _vp]),
+    "ee_debug_gemm_split_resid": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp, _i32, _vp, _i32,
+                                            _i32, _i32, C.POINTER(C.c_float), _vp]),
     "ee_debug_attn_stamps": (C.c_int, [_vp]),
     "ee_debug_attention": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                      _i32, _i32, _i32, _vp, C.POINTER(_i32), _vp]),

@@ -442,33 +442,29 @@ int ee_debug_attn_stamps(uint64_t* out8) {
     return 0;
 }
 
-int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const float* resid, float* Cout, int32_t M, int32_t N,
-                        int32_t K, int32_t epi, int32_t out_split, float a_scale, float w_scale, float out_scale,
-                        const int32_t* row_src, int32_t rows_A, int32_t iters, float* ms_out, void* stream) {
-    const int dbg = epi >> 4;            // diagnostic bits (timing only): 16 no in-loop DMA, 32 no barrier, 64 no DMA wait, 128 no epilogue
-    epi &= 15;
-#ifndef MMEE_DIAG
-    if (dbg) return fail(nullptr, "ee_debug_gemm_split: timing variants (wrong results) exist in the diagnostic library only (make diag)");
-#endif
-    if (!A || !W || !Cout || M < 1 || rows_A < 1 || !mmee::gemm_split_supports(N, K) || epi < 0 || epi > 3 || iters < 1)
-        return fail(nullptr, "ee_debug_gemm_split: bad argument (N %% 256, K %% 32)");
-    if (epi == EPI_RESID && !resid) return fail(nullptr, "ee_debug_gemm_split: residual epilogue without a residual");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int cus = device_cus("ee_debug_gemm_split");
+// What the two split-GEMM hooks share: the operands to split planes, `iters` launches (the first untimed), the time per launch.  `g` arrives
+// with everything but A / W set; resid_scale != 0 converts the f32 residual (rows_resid rows of N) to split planes of that scale first.
+static int run_debug_gemm_split(const char* who, GemmArgs g, int epi, const float* A, const float* W, int rows_A, float a_scale, float w_scale,
+                                const float* resid, int rows_resid, float resid_scale, int M, int iters, float* ms_out, hipStream_t s) {
+    const int dbg = g.dbg_noload;
+    const int N = g.N, K = g.K;
+    const int cus = device_cus(who);
     if (!cus) return 1;
-    float *As = nullptr, *Ws = nullptr;
+    float *As = nullptr, *Ws = nullptr, *Rs = nullptr;
     int* heads = nullptr;
     if (hipMalloc((void**)&As, (size_t)rows_A * K * 4) != hipSuccess || hipMalloc((void**)&Ws, (size_t)N * K * 4) != hipSuccess ||
-        hipMalloc((void**)&heads, 512) != hipSuccess) {
-        (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads);
-        return fail(nullptr, "ee_debug_gemm_split: hipMalloc failed");
+        hipMalloc((void**)&heads, 512) != hipSuccess ||
+        (resid_scale != 0.f && hipMalloc((void**)&Rs, (size_t)rows_resid * N * 4) != hipSuccess)) {
+        (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads); (void)hipFree(Rs);
+        return fail(nullptr, "%s: hipMalloc failed", who);
     }
     mmee::launch_split_rows(A, As, nullptr, rows_A, rows_A, K, a_scale, cus, s);
     mmee::launch_split_rows(W, Ws, nullptr, N, N, K, w_scale, cus, s);
-    GemmArgs g{};
-    g.A = As; g.lda = K; g.W = Ws; g.bias = bias; g.C = Cout; g.ldc = N; g.resid = resid; g.ldr = N; g.m_static = M; g.N = N; g.K = K;
-    g.scale = 1.f; g.alpha = 1.0f / (a_scale * w_scale); g.out_split = out_split ? 1 : 0; g.out_scale = out_scale;
-    g.row_src = row_src; g.resid_row_src = row_src; g.tile_counter = heads; g.dbg_noload = dbg;
+    g.A = As; g.W = Ws; g.tile_counter = heads;
+    if (resid_scale != 0.f) {
+        mmee::launch_split_rows(resid, Rs, nullptr, rows_resid, rows_resid, N, resid_scale, cus, s);
+        g.resid = Rs; g.resid_split_inv = 1.0f / resid_scale;
+    }
     // diagnostic builds (any dbg bit; bit 256 = "diagnostic build, nothing removed") report the shader clock they ran at:
     // ms_out[1] = GHz averaged over the workgroups of the last launch
     unsigned long long* clk = nullptr;
@@ -504,9 +500,56 @@ int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads);
-    if (err != hipSuccess || hipGetLastError() != hipSuccess) return fail(nullptr, "ee_debug_gemm_split: launch failed: %s", hipGetErrorString(err));
+    (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads); (void)hipFree(Rs);
+    if (err != hipSuccess || hipGetLastError() != hipSuccess) return fail(nullptr, "%s: launch failed: %s", who, hipGetErrorString(err));
     return 0;
+}
+
+int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const float* resid, float* Cout, int32_t M, int32_t N,
+                        int32_t K, int32_t epi, int32_t out_split, float a_scale, float w_scale, float out_scale,
+                        const int32_t* row_src, int32_t rows_A, int32_t iters, float* ms_out, void* stream) {
+    const int dbg = epi >> 4;            // diagnostic bits (timing only): 16 no in-loop DMA, 32 no barrier, 64 no DMA wait, 128 no epilogue
+    epi &= 15;
+#ifndef MMEE_DIAG
+    if (dbg) return fail(nullptr, "ee_debug_gemm_split: timing variants (wrong results) exist in the diagnostic library only (make diag)");
+#endif
+    if (!A || !W || !Cout || M < 1 || rows_A < 1 || !mmee::gemm_split_supports(N, K) || epi < 0 || epi > 3 || iters < 1)
+        return fail(nullptr, "ee_debug_gemm_split: bad argument (N %% 256, K %% 32)");
+    if (epi == EPI_RESID && !resid) return fail(nullptr, "ee_debug_gemm_split: residual epilogue without a residual");
+    GemmArgs g{};
+    g.lda = K; g.bias = bias; g.C = Cout; g.ldc = N; g.resid = resid; g.ldr = N; g.m_static = M; g.N = N; g.K = K;
+    g.scale = 1.f; g.alpha = 1.0f / (a_scale * w_scale); g.out_split = out_split ? 1 : 0; g.out_scale = out_scale;
+    g.row_src = row_src; g.resid_row_src = row_src; g.dbg_noload = dbg;
+    return run_debug_gemm_split("ee_debug_gemm_split", g, epi, A, W, rows_A, a_scale, w_scale, nullptr, 0, 0.f, M, iters, ms_out,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
+// a row map of the caller's, on a host copy: every entry inside [0, rows)
+static int check_row_map(const char* who, const char* what, const int32_t* map, int M, int rows) {
+    std::vector<int> h;
+    if (!to_host(h, map, (size_t)M)) return fail(nullptr, "%s: copy of %s failed", who, what);
+    for (int i = 0; i < M; ++i)
+        if (h[i] < 0 || h[i] >= rows) return fail(nullptr, "%s: %s[%d] = %d outside [0, %d)", who, what, i, h[i], rows);
+    return 0;
+}
+
+int ee_debug_gemm_split_resid(const float* A, const float* W, const float* bias, const float* resid, float* Cout, int32_t M, int32_t N,
+                              int32_t K, float a_scale, float w_scale, float resid_scale, const int32_t* row_src, int32_t rows_A,
+                              const int32_t* resid_row_src, int32_t rows_resid, int32_t route, int32_t iters, float* ms_out, void* stream) {
+    const char* who = "ee_debug_gemm_split_resid";
+    if (!A || !W || !resid || !Cout || M < 1 || rows_A < 1 || rows_resid < 1 || !mmee::gemm_split_supports(N, K) || iters < 1 || route < 0 ||
+        route > 2 || !(a_scale > 0.f) || !(w_scale > 0.f) || resid_scale < 0.f)
+        return fail(nullptr, "%s: bad argument (N %% 256, K %% 32, route 0 / 1 / 2)", who);
+    if ((!row_src && M > rows_A) || (!resid_row_src && M > rows_resid)) return fail(nullptr, "%s: M rows without a row map need M rows of A / of the residual", who);
+    if (row_src) { const int rc = check_row_map(who, "row_src", row_src, M, rows_A); if (rc) return rc; }
+    if (resid_row_src) { const int rc = check_row_map(who, "resid_row_src", resid_row_src, M, rows_resid); if (rc) return rc; }
+    GemmArgs g{};
+    g.lda = K; g.bias = bias; g.C = Cout; g.ldc = N; g.resid = resid; g.ldr = N; g.m_static = M; g.N = N; g.K = K;
+    g.scale = 1.f; g.alpha = 1.0f / (a_scale * w_scale);
+    g.row_src = row_src; g.resid_row_src = resid_row_src; g.route = route;
+    g.role_tag = K > N ? 3 : 2;          // the layer's kernel names: FFN down / attention output
+    return run_debug_gemm_split(who, g, EPI_RESID, A, W, rows_A, a_scale, w_scale, resid, rows_resid, resid_scale, M, iters, ms_out,
+                                reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

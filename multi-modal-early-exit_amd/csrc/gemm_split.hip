@@ -65,11 +65,18 @@ void launch_gemm_split(const GemmArgs& a_in, int epi, int max_m, int num_cus, hi
         return;
     }
     a.k_splits = 1;      // every kernel below writes ONE part
+    // ee_debug_gemm_split_resid's forced routes (residual epilogue, f32 output, three terms): the two configurations that compute the same bits,
+    // one reading the residual straight into registers, one through LDS
+    if (a.route == 1 && !a.out_split && epi == EPI_RESID) {
+        a.tile_counter = nullptr;
+        launch_split_one<CfgP, EPI_RESID, false, false, 1>(a, max_m, num_cus, s);
+        return;
+    }
     // Round 6, small batches (the reference evaluates at eval_batch_size = 1, EE/configs.py:36; bench.py `small_batch`): a forward of one document is
     // 709 rows -- 27 of the default 256 x 256 tiles in the Q|K|V projection, 9 in the attention-output GEMM, on 256 CUs.  When the default tiles
     // would leave more than half of the chip without one, a layer GEMM takes the CLS-probe launches' 128 x 128 / 4-wave configuration (four
     // times the tiles, static assignment): same MFMA form, k order and term order => the same bits, so nothing observable changes but the time.
-    if (a.terms != 1 && (long)((max_m + 255) / 256) * (a.N / 256) * 2 <= (long)num_cus) {
+    if (a.terms != 1 && a.route != 2 && (long)((max_m + 255) / 256) * (a.N / 256) * 2 <= (long)num_cus) {
         a.tile_counter = nullptr;
         if (a.out_split && epi == EPI_GELU) { launch_split_one<CfgP, EPI_GELU, true, false, 1>(a, max_m, num_cus, s); return; }
         if (a.out_split && epi == EPI_BIAS) { launch_split_one<CfgP, EPI_BIAS, true, false, 1>(a, max_m, num_cus, s); return; }

@@ -40,6 +40,9 @@ struct SplitCfg {
     static_assert(THREADS <= 1024, "a workgroup is at most 16 waves");
     static_assert(WGS * (LOOP_BYTES + 16) <= 160 * 1024, "LDS budget of a CU (160 KiB) for WGS workgroups");
     static_assert(WGS * NW <= 32, "wave slots of a CU");
+    // residual tile staged through LDS (resid_lds_staged below): one dedicated 1 KiB slot per wave above the ring and the queue slot
+    // and two 256-byte row maps (this tile's and the next one's)
+    static constexpr int RESID_OFF = LOOP_BYTES + 16, RESID_MAP_OFF = RESID_OFF + NW * 1024, RESID_BYTES = NW * (1024 + 2 * 256);
 };
 using CfgA = SplitCfg<128, 256, 64, 3, 2, 4, 2>;
 using CfgB = SplitCfg<256, 256, 128, 2, 4, 4, 1>;
@@ -62,6 +65,60 @@ __device__ __forceinline__ void dma_piece(unsigned voff, unsigned long long base
                  : "=&s"(keep)
                  : "v"(voff), "s"(lds_addr), "s"(base)
                  : "memory");
+}
+
+// the same piece from a 64-bit per-lane address (the residual rows of the epilogue: a row map may point anywhere in a buffer of > 4 GB)
+__device__ __forceinline__ void dma_piece_addr(unsigned long long addr, unsigned lds_addr) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(addr), "s"(lds_addr)
+                 : "memory");
+}
+
+// RESIDUAL THROUGH LDS.  The instantiations that resid_lds_staged() names (256 x 256 tile on the 16x16x32 form with the hand-over, residual
+// epilogue, f32 output: the attention-output and FFN-down GEMMs of a layer) take a SPLIT residual (resid_split_inv != 0) by LDS-DMA instead
+// of two 8-byte loads per lane and epilogue iteration: no register holds a load in flight, every access is 16 bytes wide, and nothing waits
+// with vmcnt(0).  An f32 residual, and every other configuration, keeps the direct read in split_store_tile16.
+//   piece g (0..15) of a wave = the residual of rows 4g .. 4g+3 of its 64 x 64 sub-tile: 4 rows x 256 contiguous bytes (64 columns of split
+//   planes, four 64-byte groups [hi 16 | lo 16]) = one 1 KiB global_load_lds_dwordx4.  Lane l fetches 16-byte chunk (l & 15) ^ 2 (r & 1) of
+//   row r = l >> 4 (odd rows swap the hi and lo halves of a group, so the two rows a 32-lane read group covers hit disjoint banks) from
+//   source row rmap[4g + r], read from the wave's row map in LDS: 64 row numbers fetched once per tile (setup: the output row clamped to
+//   M - 1, through resid_row_src when that is set; in LDS and not in a register, which would have to live through the k-loop).
+//   slots: D, the wave's own 1 KiB above the ring, and S0 / S1, the first two 1 KiB row groups of its 4 KiB accumulator staging block,
+//   each free again as soon as iteration 0 / 1 of a 16-row slice has read its accumulators.  In slice h: piece 4h -> D, 4h+1 -> S0,
+//   4h+2 -> D, 4h+3 -> S1.  Iteration j = 0 issues 4h+1 and 4h+2 once it has read D and S0; j = 1 issues 4h+3; j = 2 issues 4(h+1).
+//   Piece 0 is issued behind the wait and barrier of the LAST k-stage (nothing waits vmcnt(0) after it before the loop ends) and has landed
+//   at the vmcnt(0) behind the per-column constants.  Two to three pieces are in flight per wave except across iteration 3.
+//   waits: the counter retires in issue order, and between two waits the wave issues only these pieces and ONE global store per iteration
+//   (the hand-over pieces of the next tile and its row numbers are older than piece 1), so iteration g waits for piece g with vmcnt(N),
+//   N = what was issued behind it: g % 4 = 0 -> stores g-2, g-1: 2; 1 -> piece g+1, store g-1: 2; 2 -> store g-2, piece g+1, store g-1: 3;
+//   3 -> store g-2, piece g+1, store g-1: 3 (g = 15: no piece 16: 2).  A store that a wave skips because all its rows are >= M can only make
+//   a wait return early for rows that are never stored: rows past M are the LAST rows of a tile, every later iteration is dead too.
+// LDS budget (why this layout): the ring is 128 KiB and both of its slots are taken during the epilogue (accumulator staging in one, the next
+// tile's first stage in the other); two dedicated 1 KiB slots per wave are 32 KiB, which do not fit beside the 16-byte queue slot under
+// 160 KiB (allocated in 1280-byte granules).  Moving the hand-over DMA behind the epilogue would give 64 KiB but exposes a whole stage's
+// latency per tile (the k-loop's lead matters: see the round-4 note at the in-loop issue); slots of fewer rows break the 4-row iteration.  So
+// one dedicated slot (16 KiB) and the already-consumed part of the staging block; with the row maps (2 x 256 B per wave)
+// 128 KiB + 16 B + 16 KiB + 8 KiB = 155 664 B, 122 granules of 128.
+template <typename Cfg, int EPI, bool OUT_SPLIT, bool DIAG>
+constexpr bool resid_lds_staged() {
+    return Cfg::MF == 16 && Cfg::NST == 2 && Cfg::NW * 4096 <= Cfg::STAGE_BYTES && Cfg::BM == 256 && EPI == EPI_RESID && !OUT_SPLIT && !DIAG;
+}
+struct ResidStage {
+    const int* rmap;             // LDS, the wave's own: [l] = source row of the residual of row l of its 64
+    unsigned long long base;     // bytes: resid + the first of the wave's 64 columns (uniform)
+    unsigned ldr4;               // bytes per residual row
+    unsigned d_lds, s_lds;       // LDS byte addresses of slot D and of the wave's staging block (S0 = + 0, S1 = + 1024)
+    const char* d_ptr;           // slot D as a pointer
+};
+__device__ __forceinline__ void resid_piece_issue(const ResidStage& rs, int g, unsigned lds_addr, int lane) {
+    // (the lane number through an empty asm: the per-lane constants below are cheap to recompute, and hipcc otherwise hoists all of them to
+    // kernel entry and spills them around the k-loop)
+    asm volatile("" : "+v"(lane));
+    const int src = rs.rmap[4 * g + (lane >> 4)];
+    const unsigned chunk = 16u * (unsigned)((lane & 15) ^ (2 * ((lane >> 4) & 1)));
+    dma_piece_addr(rs.base + (unsigned long long)(unsigned)src * rs.ldr4 + chunk, lds_addr);
 }
 
 template <int EPI, bool OUT_SPLIT, int WN>
@@ -162,12 +219,16 @@ __device__ __forceinline__ void split_store_tile(const GemmArgs& g, float* smem,
 // at a time issued as soon as the previous 16 rows' registers are free -- 290, +5 spilled registers at the 128-VGPR cap; (3) the same with
 // two register sets -- 21 spills; (4) the add moved into the LayerNorm kernel that follows (bias epilogue + f32 store + residual there: the
 // same bits, all 57 GPU tests green): attention-output share of the step 8.1 -> 6.3 %, FFN-down 22.5 -> 21.2 %, LayerNorm 5.0 -> 8.0 %,
-// 6750 vs 6757 docs/s -- the 0.73 GB cost the same HBM time wherever they are read, so the residual stays here.  What remains is holding
-// the first rows' residual across the last k-stages, which needs 16 registers the 16-wave configuration does not have, or 4 KB of LDS
-// per wave where 2 KB are free.
-template <int EPI, bool OUT_SPLIT, int WN, int RB>
+// 6750 vs 6757 docs/s -- the 0.73 GB cost the same HBM time wherever they are read, so the residual stays here.  (5) ships for the layers'
+// split residual: the tile's residual through LDS by DMA, register-free, 16 bytes wide, behind counted waits ("RESIDUAL THROUGH LDS" above):
+// attention output 310 -> 332 TFLOP/s, FFN down 415 -> 418, +0.85 % of the step (profiles/gemm_resid_lds_ab.txt).  The read below is what
+// an f32 residual and the other configurations keep.
+// RSTG (with rst): the split residual arrives through LDS -- "RESIDUAL THROUGH LDS" above.
+template <int EPI, bool OUT_SPLIT, int WN, int RB, bool RSTG = false>
 __device__ __forceinline__ void split_store_tile16(const GemmArgs& g, float* smem, f32x4 (&acc)[4][4], int m0, int n0, int M,
-                                                   int wave, int lane, const f32x4 bv, const f32x4 lam, const size_t c_shift = 0) {
+                                                   int wave, int lane, const f32x4 bv, const f32x4 lam, const size_t c_shift = 0,
+                                                   const ResidStage* rst = nullptr) {
+    static_assert(!RSTG || (EPI == EPI_RESID && !OUT_SPLIT && RB == 16), "the staged residual: 16-row slices, f32 output");
     const int wr = wave / WN, wc = wave % WN;
     const int l15 = lane & 15, gq = lane >> 4;
     float* stg = smem + wave * (RB * 64);
@@ -209,7 +270,35 @@ __device__ __forceinline__ void split_store_tile16(const GemmArgs& g, float* sme
         for (int j = 0; j < RB / 4; ++j) {
             const int rl = (lane >> 4) + 4 * j;
             const int row = rbase + 4 * j;
+            u32x2_t rhi = u32x2_t{0u, 0u}, rlo = u32x2_t{0u, 0u};
+            if constexpr (RSTG) {
+                const int gp = 4 * half + j;                 // this iteration's piece
+                if (gp > 0) {
+                    if ((j & 2) && gp != 15) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+                    else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+                }
+                const char* slot = (j & 1) ? reinterpret_cast<const char*>(stg) + (j >> 1) * 1024 : rst->d_ptr;
+                int ln = lane;
+                asm volatile("" : "+v"(ln));      // not hoisted out of the tile loop: resid_piece_issue
+                const unsigned hi_off = (unsigned)(ln >> 4) * 256u + (unsigned)((ln & 15) >> 2) * 64u +
+                                        (((unsigned)(ln & 3) * 8u) ^ (32u * (unsigned)((ln >> 4) & 1)));
+                rhi = *reinterpret_cast<const u32x2_t*>(slot + hi_off);
+                rlo = *reinterpret_cast<const u32x2_t*>(slot + (hi_off ^ 32u));
+            }
             f32x4 v = *reinterpret_cast<const f32x4*>(stg + rl * 64 + (c4 ^ (16 * ((rl >> 2) & 1))));
+            if constexpr (RSTG) {
+                // the reads of slot D / staging rows 4j .. 4j+3 have returned: refill
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rhi), "+v"(rlo), "+v"(v) :: "memory");
+                const int gp = 4 * half + j;
+                if (j == 0) {
+                    resid_piece_issue(*rst, gp + 1, rst->s_lds, lane);
+                    resid_piece_issue(*rst, gp + 2, rst->d_lds, lane);
+                } else if (j == 1) {
+                    resid_piece_issue(*rst, gp + 2, rst->s_lds + 1024u, lane);
+                } else if (j == 2 && gp + 2 < 16) {
+                    resid_piece_issue(*rst, gp + 2, rst->d_lds, lane);
+                }
+            }
             // (rows past M compute on whatever the clamped A rows gave and are not stored; the quad permute below needs every lane)
 #pragma unroll
             for (int t = 0; t < 4; t += 2) {
@@ -221,8 +310,17 @@ __device__ __forceinline__ void split_store_tile16(const GemmArgs& g, float* sme
                 v[t] = x[0];
                 v[t + 1] = x[1];
             }
+            if constexpr (RSTG) {      // the staged planes: the same hi + lo and the same fma as the direct read below (rows past M hold row M - 1's and are not stored)
+                const f32x4 r = split4_sum(rhi, rlo);
+#pragma unroll
+                for (int t = 0; t < 4; t += 2) {
+                    const f32x2 y = __builtin_elementwise_fma(f32x2{r[t], r[t + 1]}, (f32x2)(g.resid_split_inv), f32x2{v[t], v[t + 1]});
+                    v[t] = y[0];
+                    v[t + 1] = y[1];
+                }
+            }
             if (row < M) {
-                if (EPI == EPI_RESID) {
+                if (EPI == EPI_RESID && !RSTG) {
                     const int rs = g.resid_row_src ? g.resid_row_src[row] : row;
                     if (g.resid_split_inv != 0.f) {      // split planes: hi + lo by v_fma_mix_f32, the power-of-two 1 / scale folded into the add
                         const f32x4 r = load_split4_sum(g.resid + (size_t)rs * g.ldr, col);
@@ -331,6 +429,11 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
     // HANDOVER (the default configuration): the epilogue stages through ONE ring slot (4 KB per wave), so the next tile is drawn
     // from the queue as soon as the k-loop ends and its first stage lands in the other slot while the epilogue runs.
     constexpr bool HANDOVER = Cfg::MF == 16 && NST == 2 && Cfg::NW * 4096 <= STAGE_BYTES;
+    // residual through LDS ("RESIDUAL THROUGH LDS" above): these instantiations, when the residual is split planes
+    constexpr bool RSTG = resid_lds_staged<Cfg, EPI, OUT_SPLIT, DIAG>();
+    static_assert(!RSTG || (HANDOVER && (Cfg::RESID_OFF + Cfg::RESID_BYTES + 1279) / 1280 * 1280 <= 160 * 1024),
+                  "the staged residual needs the 4 KiB staging blocks of the hand-over and its slots inside the CU's 160 KiB of LDS");
+    const bool rstg = RSTG && g.resid_split_inv != 0.f;
 
     auto pop = [&](int& tm, int& tn) __attribute__((always_inline)) -> bool {
         if (g.tile_counter) {
@@ -404,22 +507,50 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
 
     // per-tile DMA sources: SGPR base + 32-bit lane offset (A rows may be gathered; row_src is increasing).
     // Wave w owns A pieces w, w + NW, ... and W pieces likewise.
+    int rpar_next = 0;
+    auto rmap_of = [&](int par) __attribute__((always_inline)) -> int* {
+        return reinterpret_cast<int*>(reinterpret_cast<char*>(smem) + Cfg::RESID_MAP_OFF + (wave * 2 + par) * 256);
+    };
     struct TileCtx {
         int m0, n0;
         int kt0;                                     // split-K: first k-stage of this workgroup's part
         unsigned a_voff[PA], w_voff[PW];
         unsigned long long a_base, w_base;
+        int rpar;                                    // residual through LDS: which of the wave's two row maps is this tile's
     };
     auto setup = [&](int tm, int tn, TileCtx& t) __attribute__((always_inline)) {
         t.m0 = __builtin_amdgcn_readfirstlane(tm * BM);
         t.n0 = __builtin_amdgcn_readfirstlane(tn * BN);
         t.kt0 = KSPLIT ? __builtin_amdgcn_readfirstlane(ks_pop * nk) : 0;
+        t.rpar = rpar_next;
+        if constexpr (RSTG) {
+            if (rstg) {
+                // the wave's 64 residual row numbers, once per tile, into its row map in LDS (no register lives through the k-loop).  An ordinary
+                // load, consumed here: no DMA piece is in flight at a setup (the first tile's, or behind the vmcnt(0) of the per-column
+                // constants), and the compiler knows of no pending load afterwards that could turn a counted wait of the epilogue into vmcnt(0).
+                // Two maps: the next tile's setup runs in front of this tile's epilogue.
+                int ln = lane;
+                asm volatile("" : "+v"(ln));      // not hoisted to kernel entry (resid_piece_issue)
+                int rr = t.m0 + wr * 64 + ln;
+                rr = rr < M ? rr : M - 1;
+                rmap_of(t.rpar)[ln] = g.resid_row_src ? g.resid_row_src[rr] : rr;
+                rpar_next ^= 1;
+            }
+        }
         int first = g.row_src ? g.row_src[t.m0] : t.m0;
+        // (RSTG: the lane's row of a piece recomputed per tile -- held from kernel entry, the two sums PROWS * piece + p_row below were the two
+        // registers these instantiations spilled around the k-loop)
+        int p_row_s = p_row;
+        if constexpr (RSTG) {
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            p_row_s = ln / CPR;
+        }
         if (DIAG && (dbg & 16)) first = 0;
 #pragma unroll
         for (int j = 0; j < PA; ++j) {
             const int piece = wave + Cfg::NW * j;
-            int ra = t.m0 + Cfg::PROWS * piece + p_row;
+            int ra = t.m0 + Cfg::PROWS * piece + p_row_s;
             ra = ra < M ? ra : M - 1;
             if (DIAG && (dbg & 16)) ra = Cfg::PROWS * piece + p_row;      // timing variant (wrong results): every tile streams A panel 0, an L2-resident A operand
             const int sa = g.row_src ? g.row_src[ra] : ra;
@@ -436,6 +567,17 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
                    (unsigned)__builtin_amdgcn_readfirstlane((int)(a_base_v & 0xffffffffu));
         t.w_base = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(w_base_v >> 32)) << 32) |
                    (unsigned)__builtin_amdgcn_readfirstlane((int)(w_base_v & 0xffffffffu));
+    };
+    // the residual stage of a tile: uniform but for rmap
+    auto resid_stage = [&](const TileCtx& t) __attribute__((always_inline)) -> ResidStage {
+        ResidStage r;
+        r.rmap = rmap_of(t.rpar);
+        r.base = (unsigned long long)(size_t)g.resid + (unsigned long long)(unsigned)(t.n0 + wc * 64) * 4ull;
+        r.ldr4 = (unsigned)g.ldr * 4u;
+        r.d_lds = lds0 + (unsigned)Cfg::RESID_OFF + (unsigned)wave * 1024u;
+        r.s_lds = 0;
+        r.d_ptr = sbytes + Cfg::RESID_OFF + wave * 1024;
+        return r;
     };
     auto issue = [&](const TileCtx& t, int kt, int buf) __attribute__((always_inline)) {
         const unsigned long long koff = (unsigned long long)(kt + (KSPLIT ? t.kt0 : 0)) * (unsigned)ROWB;
@@ -501,6 +643,12 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
             // (measured, round 4: issuing this DMA behind the MFMAs of the first / second / third W fragment instead costs 1-4 % / 3-8 % / 4-8 % on
             // the four layer shapes -- the lead of a stage's DMA matters; profiles/r04_gemm_epilogue_experiments.txt section 10)
             if (kt + NST - 1 < nk && !(dbg & 1)) issue(cur, kt + NST - 1, bufn);
+            if constexpr (RSTG) {      // piece 0 of the residual lands under this last stage's MFMAs
+                if (rstg && kt == nk - 1) {
+                    const ResidStage r0 = resid_stage(cur);
+                    resid_piece_issue(r0, 0, r0.d_lds, lane);
+                }
+            }
             const char* sb = sbytes + buf * STAGE_BYTES;
             if constexpr (Cfg::MF == 16) {
                 // A fragments of the four 16-row tiles stay in registers; W fragments come one 16-column tile at a time
@@ -572,7 +720,12 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
         if (HANDOVER && have) issue(nxt, 0, nbuf0);
         if (!(dbg & 8)) {
             if constexpr (Cfg::MF == 16) {
-                if constexpr (HANDOVER)
+                if constexpr (RSTG) {
+                    ResidStage rst = resid_stage(cur);
+                    rst.s_lds = lds0 + (unsigned)last_slot * STAGE_BYTES + (unsigned)wave * 4096u;
+                    if (rstg) split_store_tile16<EPI, OUT_SPLIT, WN, 16, true>(g, smem + last_slot * (STAGE_BYTES / 4), acc16, m0, n0, M, wave, lane, bv, lam, 0, &rst);
+                    else split_store_tile16<EPI, OUT_SPLIT, WN, 16>(g, smem + last_slot * (STAGE_BYTES / 4), acc16, m0, n0, M, wave, lane, bv, lam);
+                } else if constexpr (HANDOVER)
                     split_store_tile16<EPI, OUT_SPLIT, WN, 16>(g, smem + last_slot * (STAGE_BYTES / 4), acc16, m0, n0, M, wave, lane, bv, lam);
                 else
                     split_store_tile16<EPI, OUT_SPLIT, WN, 32>(g, smem, acc16, m0, n0, M, wave, lane, bv, lam, c_shift);
@@ -598,7 +751,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
 
 template <typename Cfg, int EPI, bool OUT_SPLIT, bool DIAG = false, int TAG = 0, int TERMS = 3>
 static void launch_split_one(const GemmArgs& a, int max_m, int num_cus, hipStream_t s) {
-    const size_t lds = Cfg::LOOP_BYTES + 16;
+    const size_t lds = Cfg::LOOP_BYTES + 16 + (resid_lds_staged<Cfg, EPI, OUT_SPLIT, DIAG>() ? Cfg::RESID_BYTES : 0);
     (void)ensure_dynamic_lds<&gemm_split_kernel<Cfg, EPI, OUT_SPLIT, DIAG, TAG, TERMS>>("gemm_split_kernel", (int)lds);
     const int tiles = ((max_m + Cfg::BM - 1) / Cfg::BM) * (a.N / Cfg::BN) * (TAG == 1 && a.k_splits > 1 ? a.k_splits : 1);
     int grid = Cfg::WGS * num_cus;

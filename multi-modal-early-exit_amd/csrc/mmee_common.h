@@ -348,9 +348,7 @@ typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 // v_fma_mix_f32 per value computes it straight from the two f16 halves (fma(hi, 1.0, lo) with f16 sources 0 and 2) instead of two
 // conversions and an add; the plane scale is a power of two, so multiplying by its inverse -- or folding it into an fma with the value the
 // row is added to, as the GEMM's residual epilogue does -- rounds nothing: the same bits as ((float)hi + (float)lo) * inv_scale.
-__device__ __forceinline__ f32x4 load_split4_sum(const void* row_base, int col) {      // hi + lo, still carrying the plane scale
-    const char* p = reinterpret_cast<const char*>(row_base) + (col >> 4) * 64 + (col & 15) * 2;
-    const u32x2_t hi = *reinterpret_cast<const u32x2_t*>(p), lo = *reinterpret_cast<const u32x2_t*>(p + 32);
+__device__ __forceinline__ f32x4 split4_sum(const u32x2_t hi, const u32x2_t lo) {      // the 8 + 8 bytes of four columns, wherever they were read from
     float r0, r1, r2, r3;
     asm("v_fma_mix_f32 %0, %4, 1.0, %6 op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"
         "v_fma_mix_f32 %1, %4, 1.0, %6 op_sel:[1,0,1] op_sel_hi:[1,0,1]\n\t"
@@ -359,6 +357,10 @@ __device__ __forceinline__ f32x4 load_split4_sum(const void* row_base, int col) 
         : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
         : "v"(hi[0]), "v"(hi[1]), "v"(lo[0]), "v"(lo[1]));
     return f32x4{r0, r1, r2, r3};
+}
+__device__ __forceinline__ f32x4 load_split4_sum(const void* row_base, int col) {      // hi + lo, still carrying the plane scale
+    const char* p = reinterpret_cast<const char*>(row_base) + (col >> 4) * 64 + (col & 15) * 2;
+    return split4_sum(*reinterpret_cast<const u32x2_t*>(p), *reinterpret_cast<const u32x2_t*>(p + 32));
 }
 __device__ __forceinline__ f32x4 load_split4(const void* row_base, int col, float inv_scale) {
     return load_split4_sum(row_base, col) * inv_scale;
@@ -406,6 +408,8 @@ struct GemmArgs {
     int probe;                       // split kernel: 1 = the CLS-probe instantiation (same code, its own kernel name for the profiler)
     int role_tag;                    // split kernel, residual epilogue: 2 = attention output, 3 = FFN down (same code, own kernel names: the two
                                      // share every template argument, and a profiler could not tell them apart)
+    int route;                       // split kernel: 0 = the tile configuration launch_gemm_split's rules pick; ee_debug_gemm_split_resid alone forces 1 = the
+                                     //   128 x 128 one (residual read straight into registers) or 2 = the 256 x 256 one, whatever the row count
     int tile_order;                  // work-queue order inside a group of 8 M-tiles: 0 = M fastest (eight tiles share a W tile back to back),
                                      // 1 = N fastest (the N-tiles of one M-panel follow each other: they share the A panel)
     int prio_mode;                   // 0 none, 1 raise the priority of odd hardware wave slots, 2 of the second half of the grid

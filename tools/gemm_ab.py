@@ -1,6 +1,6 @@
 """Same-process A/B of the split GEMM between builds of the library (GPU box only):
 
-    python tools/gemm_ab.py [--rounds 3] [--iters 24] [--m 236544] lib_a.so lib_b.so ...      ("" / "tree" = the in-tree release library)
+    python tools/gemm_ab.py [--rounds 3] [--iters 24] [--m 236544] [--split-resid] lib_a.so lib_b.so ...      ("" / "tree" = the in-tree release library)
 
 Every layer shape (QKV, attention output, FFN up, FFN down at LayoutLMv3-base widths) is timed through `ee_debug_gemm_split` for each
 library in turn, `rounds` times over, so that clock drift of the box hits all builds alike (guide rule 24: interleaved rounds in ONE
@@ -28,6 +28,11 @@ def load(path):
     f = lib.ee_debug_gemm_split
     f.restype = C.c_int
     f.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_float] * 3 + [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_void_p]
+    if hasattr(lib, "ee_debug_gemm_split_resid"):
+        f = lib.ee_debug_gemm_split_resid
+        f.restype = C.c_int
+        f.argtypes = ([C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_float] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                                              C.POINTER(C.c_float), C.c_void_p])
     return lib, os.path.basename(path)
 
 
@@ -40,6 +45,8 @@ def main():
     ap.add_argument("--shapes", default="qkv,attn_out,ffn_up,ffn_down")
     ap.add_argument("--dbg", default="0", help="comma list of timing-variant bits (diagnostic libraries only; wrong results): 1 no in-loop DMA, "
                                                "8 no epilogue, 16 diagnostic build with nothing removed")
+    ap.add_argument("--split-resid", action="store_true", help="the residual shapes with a SPLIT-PLANE residual, as the layers launch them, through "
+                                                               "ee_debug_gemm_split_resid (every library must have it); default: f32 residual")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     libs = [load(p) for p in a.libs]
@@ -61,7 +68,10 @@ def main():
             for lib, tag in libs:
                 for d in dbgs:
                     ms = (C.c_float * 8)(*([0.0] * 8))
-                    rc = lib.ee_debug_gemm_split(p(A), p(W), p(b), p(R), p(Cc), M, N, K, epi | (d << 4), osp, 16.0, 256.0, 16.0, None, M, a.iters, ms, st)
+                    if a.split_resid and epi == 2:
+                        rc = lib.ee_debug_gemm_split_resid(p(A), p(W), p(b), p(R), p(Cc), M, N, K, 16.0, 256.0, 16.0, None, M, None, M, 0, a.iters, ms, st)
+                    else:
+                        rc = lib.ee_debug_gemm_split(p(A), p(W), p(b), p(R), p(Cc), M, N, K, epi | (d << 4), osp, 16.0, 256.0, 16.0, None, M, a.iters, ms, st)
                     torch.cuda.synchronize()
                     if rc != 0:
                         raise SystemExit(f"{tag}: ee_debug_gemm_split failed ({rc})")
