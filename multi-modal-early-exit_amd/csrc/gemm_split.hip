@@ -38,7 +38,7 @@ namespace mmee {
 
 bool gemm_split_supports(int N, int K) { return N > 0 && K > 0 && N % 256 == 0 && K % 32 == 0; }
 
-// the FFN-up instantiation lives in gemm_split_ffn_up.hip (its own scheduling strategy: gemm_split_kernel.h)
+// the FFN-up instantiation lives in gemm_split_ffn_up.hip (a unit that can take its own scheduling strategy: gemm_split_kernel.h)
 void launch_split_ffn_up(const GemmArgs& a, int max_m, int num_cus, hipStream_t s);
 
 void launch_gemm_split(const GemmArgs& a_in, int epi, int max_m, int num_cus, hipStream_t s) {

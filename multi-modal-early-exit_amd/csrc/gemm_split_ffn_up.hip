@@ -1,5 +1,6 @@
 // FFN-up instantiation of the split GEMM kernel (256 x 256 tile, GELU epilogue, split output, three MFMA terms) in a translation unit of
-// its own, so that the Makefile can give it its own instruction-scheduling strategy (gemm_split_kernel.h).
+// its own, so that the Makefile can give it its own instruction-scheduling strategy (gemm_split_kernel.h: max-ilp until the k-loop was staggered,
+// none today).
 #include "gemm_split_kernel.h"
 
 namespace mmee {

@@ -1,10 +1,12 @@
 // The split-precision GEMM kernel template and its launcher (see gemm_split.hip for the design notes).  A header because the kernel is
 // instantiated in TWO translation units: gemm_split.hip (every instantiation but one) and gemm_split_ffn_up.hip, which holds the FFN-up
-// instantiation (256 x 256 tile, GELU epilogue, split output, three terms) and is compiled with -mllvm -amdgpu-sched-strategy=max-ilp: that
-// scheduler is worth +1.3-1.7 % on this instantiation and -0.4...-0.9 % on the others (round 4, tools/gemm_ab.py and tools/lib_ab.sh;
-// profiles/r04_gemm_epilogue_experiments.txt section 22).  Same source, same arithmetic, same bits.
+// instantiation (256 x 256 tile, GELU epilogue, split output, three terms).  That unit was compiled with -mllvm -amdgpu-sched-strategy=max-ilp
+// from round 4 (+1.3-1.7 % on this instantiation, -0.4...-0.9 % on the others; profiles/r04_gemm_epilogue_experiments.txt section 22) until the
+// k-loop was staggered: with the stagger the default scheduler is the faster one here too (385.3 against 378.2 TFLOP/s, the parent's max-ilp
+// build 376.7; profiles/gemm_stagger_ab.txt), so the Makefile gives it no flag of its own today.  Same source, same arithmetic, same bits.
 #pragma once
 #include <cstdlib>
+#include <type_traits>
 #include "mmee_common.h"
 
 namespace mmee {
@@ -58,6 +60,28 @@ using CfgC = SplitCfg<256, 256, 128, 2, 4, 4, 1, 16>;
 // 16x16x32 form, same k order, same term order), so the results are CfgC's bit for bit.
 using CfgP = SplitCfg<128, 128, 128, 3, 2, 2, 1, 16>;
 
+// STAGGERED K-LOOP.  The 16 waves of the 256 x 256 tile sit four to a SIMD and run one program with one barrier per k32 stage, so they reach
+// the barrier, the DMA issue, the fragment reads and the matrix work together: right behind a barrier no wave of a SIMD has a fragment in
+// registers and the matrix pipe waits for the first reads of all four.  So waves NW / 2 .. NW - 1 (the second-dispatched half; waves w, w + 4,
+// w + 8, w + 12 share a SIMD under the usual round-robin placement) run a quarter of a stage behind: a stage's last block -- the 4 or 12 MFMAs
+// of W tile 3 -- is held back with its operands in registers (A fragments 32, W fragments 8: what a wave holds at the end of a stage anyway)
+// and issued right BEHIND the next stage's barrier, where the two early waves of the SIMD issue DMA and wait for fragments; the early waves'
+// own W-tile-3 block at the end of the stage covers the late waves' last reads.  The last stage's block runs behind the barrier that ends the
+// k-loop, under the latency of the epilogue's per-column constants.  One loop body in the source, instantiated twice (k_loop in the kernel):
+// a wave takes the early or the late instance by a wave-uniform branch once per tile; both execute the same waits and barriers in the same
+// order, neither one the other does not.  Every accumulator receives its terms in the same order, so every output bit is what it was.  A late
+// wave waits lgkmcnt(0) behind the reads of W tile 3: behind the next barrier the slot is overwritten.  The late waves issue their DMA BEHIND
+// the held-back block: in front of it, or one piece per three MFMAs, is 3-6 % slower; delaying the odd waves instead of waves 8-15 loses
+// against the unstaggered loop (which confirms the pairing).
+// Configurations: the 16x16x32 form on the 2-deep ring with 16 waves (CfgC, both TERMS); CfgP has one wave per SIMD and keeps its loop.
+// Registers: each instance needs what the unstaggered loop needs (104), but what is held across the loops is held across both, so these
+// configurations recompute per tile what derives from the lane number (fresh_lane()).  Measured against the unstaggered build: Q|K|V +1.9 %,
+// attention output +2.1 %, FFN up +2.6 %, FFN down +3.4 %, the step +1.9 % (profiles/gemm_stagger_ab.txt).
+template <typename Cfg>
+constexpr bool stagger_k_loop() {
+    return Cfg::MF == 16 && Cfg::NST == 2 && Cfg::NW == 16;
+}
+
 
 __device__ __forceinline__ void dma_piece(unsigned voff, unsigned long long base, unsigned lds_addr) {
     unsigned keep;   // m0 is saved and restored: the compiler does not accept it in a clobber list
@@ -101,6 +125,9 @@ __device__ __forceinline__ void dma_piece_addr(unsigned long long addr, unsigned
 // latency per tile (the k-loop's lead matters: see the round-4 note at the in-loop issue); slots of fewer rows break the 4-row iteration.  So
 // one dedicated slot (16 KiB) and the already-consumed part of the staging block; with the row maps (2 x 256 B per wave)
 // 128 KiB + 16 B + 16 KiB + 8 KiB = 155 664 B, 122 granules of 128.
+// Vector-memory order under the STAGGERED K-LOOP below: unchanged for every wave.  A late wave still issues the stage's pieces, then
+// residual piece 0 in the last stage, and no vector-memory operation of its own moves relative to another (only MFMAs move), so the counted
+// vmcnt(2) / vmcnt(3) waits above and the vmcnt(0) of every stage hold as they are.
 template <typename Cfg, int EPI, bool OUT_SPLIT, bool DIAG>
 constexpr bool resid_lds_staged() {
     return Cfg::MF == 16 && Cfg::NST == 2 && Cfg::NW * 4096 <= Cfg::STAGE_BYTES && Cfg::BM == 256 && EPI == EPI_RESID && !OUT_SPLIT && !DIAG;
@@ -392,6 +419,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave / WN, wc = wave % WN;
     const int l31 = lane & 31, hh = lane >> 5;
+    int lane_m = lane;      // the lane number again, re-made in place by fresh_lane()
 
     unsigned long long clk0 = 0, rt0 = 0;
     if (DIAG && g.clk_probe) { clk0 = __builtin_amdgcn_s_memtime(); rt0 = __builtin_amdgcn_s_memrealtime(); }
@@ -434,6 +462,22 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
     static_assert(!RSTG || (HANDOVER && (Cfg::RESID_OFF + Cfg::RESID_BYTES + 1279) / 1280 * 1280 <= 160 * 1024),
                   "the staged residual needs the 4 KiB staging blocks of the hand-over and its slots inside the CU's 160 KiB of LDS");
     const bool rstg = RSTG && g.resid_split_inv != 0.f;
+    // the k-loop stagger ("STAGGERED K-LOOP" above): the second-dispatched half of the 16 waves runs a quarter of a stage behind
+    constexpr bool STAGGER = stagger_k_loop<Cfg>();
+    const bool late = STAGGER && wave >= Cfg::NW / 2;
+    // The lane number through an empty asm: what is derived from it is recomputed where it is needed instead of being hoisted to kernel entry
+    // and held in registers through the k-loop and the epilogue (resid_piece_issue).  The staggered configurations re-make ONE variable in
+    // place, so that no second copy of the lane number lives beside it.
+    auto fresh_lane = [&]() __attribute__((always_inline)) -> int {
+        if constexpr (STAGGER) {
+            asm volatile("" : "+v"(lane_m));
+            return lane_m;
+        } else {
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            return ln;
+        }
+    };
 
     auto pop = [&](int& tm, int& tn) __attribute__((always_inline)) -> bool {
         if (g.tile_counter) {
@@ -518,6 +562,17 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
         unsigned long long a_base, w_base;
         int rpar;                                    // residual through LDS: which of the wave's two row maps is this tile's
     };
+    // the W offsets of a wave's DMA pieces from a lane number the compiler cannot trace (128-byte rows: the staggered configurations)
+    auto w_voffs = [&](TileCtx& t, int ln) __attribute__((always_inline)) {
+        const int pr = ln / CPR, pc = ln % CPR, sw = (pr >> 1) & 7;
+#pragma unroll
+        for (int j = 0; j < PW; ++j) {
+            const int piece = wave + Cfg::NW * j;
+            unsigned row_off = (unsigned)(Cfg::PROWS * piece + pr) * (unsigned)g.K * 4u;
+            asm volatile("" : "+v"(row_off));      // a 32-bit product: fused with the add, hipcc forms it in a register pair
+            t.w_voff[j] = row_off + 16u * (unsigned)(pc ^ ((piece & 1) ? ((sw + 4) & 7) : sw));
+        }
+    };
     auto setup = [&](int tm, int tn, TileCtx& t) __attribute__((always_inline)) {
         t.m0 = __builtin_amdgcn_readfirstlane(tm * BM);
         t.n0 = __builtin_amdgcn_readfirstlane(tn * BN);
@@ -529,8 +584,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
                 // load, consumed here: no DMA piece is in flight at a setup (the first tile's, or behind the vmcnt(0) of the per-column
                 // constants), and the compiler knows of no pending load afterwards that could turn a counted wait of the epilogue into vmcnt(0).
                 // Two maps: the next tile's setup runs in front of this tile's epilogue.
-                int ln = lane;
-                asm volatile("" : "+v"(ln));      // not hoisted to kernel entry (resid_piece_issue)
+                const int ln = fresh_lane();      // not hoisted to kernel entry
                 int rr = t.m0 + wr * 64 + ln;
                 rr = rr < M ? rr : M - 1;
                 rmap_of(t.rpar)[ln] = g.resid_row_src ? g.resid_row_src[rr] : rr;
@@ -540,11 +594,18 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
         int first = g.row_src ? g.row_src[t.m0] : t.m0;
         // (RSTG: the lane's row of a piece recomputed per tile -- held from kernel entry, the two sums PROWS * piece + p_row below were the two
         // registers these instantiations spilled around the k-loop)
+        // (the staggered k-loop has two instances, and what is held over them is held over both: its configurations recompute the chunk
+        // offsets as well)
         int p_row_s = p_row;
-        if constexpr (RSTG) {
-            int ln = lane;
-            asm volatile("" : "+v"(ln));
+        unsigned chunk_even_s = chunk_even, chunk_odd_s = chunk_odd;
+        if constexpr (RSTG || STAGGER) {
+            const int ln = fresh_lane();
             p_row_s = ln / CPR;
+            if constexpr (STAGGER) {
+                const int pc = ln % CPR, sw = (p_row_s >> 1) & 7;
+                chunk_even_s = 16u * (unsigned)(pc ^ sw);
+                chunk_odd_s = 16u * (unsigned)(pc ^ ((sw + 4) & 7));
+            }
         }
         if (DIAG && (dbg & 16)) first = 0;
 #pragma unroll
@@ -554,12 +615,18 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
             ra = ra < M ? ra : M - 1;
             if (DIAG && (dbg & 16)) ra = Cfg::PROWS * piece + p_row;      // timing variant (wrong results): every tile streams A panel 0, an L2-resident A operand
             const int sa = g.row_src ? g.row_src[ra] : ra;
-            t.a_voff[j] = (unsigned)(sa - first) * (unsigned)g.lda * 4u + ((piece & 1) ? chunk_odd : chunk_even);
+            unsigned row_off = (unsigned)(sa - first) * (unsigned)g.lda * 4u;
+            if constexpr (STAGGER) asm volatile("" : "+v"(row_off));      // a 32-bit product: fused with the add, hipcc forms it in a register pair
+            t.a_voff[j] = row_off + ((piece & 1) ? chunk_odd_s : chunk_even_s);
         }
+        if constexpr (STAGGER) {
+            w_voffs(t, fresh_lane());
+        } else {
 #pragma unroll
-        for (int j = 0; j < PW; ++j) {
-            const int piece = wave + Cfg::NW * j;
-            t.w_voff[j] = (unsigned)(Cfg::PROWS * piece + p_row) * (unsigned)g.K * 4u + ((piece & 1) ? chunk_odd : chunk_even);
+            for (int j = 0; j < PW; ++j) {
+                const int piece = wave + Cfg::NW * j;
+                t.w_voff[j] = (unsigned)(Cfg::PROWS * piece + p_row) * (unsigned)g.K * 4u + ((piece & 1) ? chunk_odd : chunk_even);
+            }
         }
         const unsigned long long a_base_v = (unsigned long long)(size_t)g.A + (unsigned long long)first * (unsigned)g.lda * 4ull;
         const unsigned long long w_base_v = (unsigned long long)(size_t)g.W + (unsigned long long)t.n0 * (unsigned)g.K * 4ull;
@@ -618,6 +685,37 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
                 for (int j = 0; j < 4; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
 
+        f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f}, lam = f32x4{1.f, 1.f, 1.f, 1.f};      // the epilogue's per-column constants
+        // The k-loop of a tile up to the barrier that ends it, written once and instantiated twice: LATE = the late waves of the stagger
+        // ("STAGGERED K-LOOP" above).  Both instances execute the same waits and barriers in the same order -- a barrier counts arrivals, not
+        // addresses.  (One instance with the placement of the W-tile-3 block behind wave-uniform branches: hipcc gives the block's accumulators
+        // a second set of 16 registers on one side of the branch and copies them back every stage; 68 - 212 bytes of scratch in every 256 x 256 instantiation.)
+        auto k_loop = [&](auto late_c) __attribute__((always_inline)) {
+        constexpr bool LATE = decltype(late_c)::value;
+        // 16x16x32 form: the A fragments of a stage and the fragments of its last W tile; a late wave carries them over the loop edge
+        f16x8 ah[4], al[4], wh_d, wl_d;
+        // (the staggered configurations recompute the fragment addresses per tile: held from kernel entry they are four more registers that
+        // live through the epilogue)
+        unsigned fa_hi = a_row16 + c16_hi, fa_lo = a_row16 + c16_lo, fw_hi = w_row16 + c16_hi, fw_lo = w_row16 + c16_lo;
+        if constexpr (STAGGER) {
+            const int ln = fresh_lane();
+            const unsigned r15 = (unsigned)(ln & 15), q = (unsigned)(ln >> 4), sw = (r15 >> 1) & 7u;
+            const unsigned hi = 16u * (((q & 1u) + 4u * (q >> 1)) ^ sw), lo = 16u * (((q & 1u) + 4u * (q >> 1) + 2u) ^ sw);
+            const unsigned ar = ((unsigned)(wr * 64) + r15) * ROWB, wrw = (unsigned)A_BYTES + ((unsigned)(wc * 64) + r15) * ROWB;
+            fa_hi = ar + hi; fa_lo = ar + lo; fw_hi = wrw + hi; fw_lo = wrw + lo;
+            // ... and the W offsets of the DMA, which do not depend on the tile: set again here, the ones a setup made for the hand-over die with it
+            w_voffs(cur, ln);
+        }
+        // the 4 (TERMS == 1) or 12 MFMAs of W tile j, and MFMA n of them alone: per accumulator the order is al x wh, ah x wl, ah x wh
+        auto mfma_one = [&](int j, int n, const f16x8 wh, const f16x8 wl) __attribute__((always_inline)) {
+            const int i = n & 3, term = TERMS == 3 ? n >> 2 : 2;
+            acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(term == 0 ? al[i] : ah[i], term == 1 ? wl : wh, acc16[i][j], 0, 0, 0);
+        };
+        auto mfma_tile = [&](int j, const f16x8 wh, const f16x8 wl) __attribute__((always_inline)) {
+#pragma unroll
+            for (int n = 0; n < 4 * TERMS; ++n) mfma_one(j, n, wh, wl);
+        };
+
         int buf = buf0, bufn = (buf0 + NST - 1) % NST;     // slots of stage kt and of stage kt + NST - 1
         // (measured, round 3: forcing the k-loop's first instruction onto a 32 / 64 / 256-byte boundary with .p2align changes nothing: 6564-6593
         // docs/s for all four builds on one box, tools/lib_ab.sh)
@@ -642,34 +740,50 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
             }
             // (measured, round 4: issuing this DMA behind the MFMAs of the first / second / third W fragment instead costs 1-4 % / 3-8 % / 4-8 % on
             // the four layer shapes -- the lead of a stage's DMA matters; profiles/r04_gemm_epilogue_experiments.txt section 10)
-            if (kt + NST - 1 < nk && !(dbg & 1)) issue(cur, kt + NST - 1, bufn);
+            const bool more = kt + NST - 1 < nk && !(dbg & 1);
+            if (LATE && kt > 0) {
+                // a late wave: W tile 3 of stage kt - 1 out of registers, under the early waves' DMA issue and first reads.  (the scheduling
+                // barriers keep the block where it is written: behind the barrier, in front of this stage's reads)
+                __builtin_amdgcn_sched_barrier(0);
+                mfma_tile(3, wh_d, wl_d);
+                __builtin_amdgcn_sched_barrier(0);
+                if (more) issue(cur, kt + NST - 1, bufn);
+                __builtin_amdgcn_sched_barrier(0);
+            } else if (more) {
+                issue(cur, kt + NST - 1, bufn);
+            }
             if constexpr (RSTG) {      // piece 0 of the residual lands under this last stage's MFMAs
                 if (rstg && kt == nk - 1) {
                     const ResidStage r0 = resid_stage(cur);
-                    resid_piece_issue(r0, 0, r0.d_lds, lane);
+                    resid_piece_issue(r0, 0, r0.d_lds, STAGGER ? lane_m : lane);
                 }
             }
             const char* sb = sbytes + buf * STAGE_BYTES;
             if constexpr (Cfg::MF == 16) {
                 // A fragments of the four 16-row tiles stay in registers; W fragments come one 16-column tile at a time
-                f16x8 ah[4], al[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    ah[i] = *reinterpret_cast<const f16x8*>(sb + a_row16 + c16_hi + i * 16 * ROWB);
-                    al[i] = *reinterpret_cast<const f16x8*>(sb + a_row16 + c16_lo + i * 16 * ROWB);
+                    ah[i] = *reinterpret_cast<const f16x8*>(sb + fa_hi + i * 16 * ROWB);
+                    al[i] = *reinterpret_cast<const f16x8*>(sb + fa_lo + i * 16 * ROWB);
                 }
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const f16x8 wh = *reinterpret_cast<const f16x8*>(sb + w_row16 + c16_hi + j * 16 * ROWB);
-                    const f16x8 wl = *reinterpret_cast<const f16x8*>(sb + w_row16 + c16_lo + j * 16 * ROWB);
-                    if (TERMS == 3) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], wh, acc16[i][j], 0, 0, 0);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], wl, acc16[i][j], 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], wh, acc16[i][j], 0, 0, 0);
+                for (int j = 0; j < 3; ++j) {
+                    const f16x8 wh = *reinterpret_cast<const f16x8*>(sb + fw_hi + j * 16 * ROWB);
+                    const f16x8 wl = *reinterpret_cast<const f16x8*>(sb + fw_lo + j * 16 * ROWB);
+                    mfma_tile(j, wh, wl);
+                }
+                // (a late wave: not hoisted over W tile 2's MFMAs, so that the fragments it carries take the registers of that tile's)
+                if constexpr (LATE) __builtin_amdgcn_sched_barrier(0);
+                wh_d = *reinterpret_cast<const f16x8*>(sb + fw_hi + 3 * 16 * ROWB);
+                wl_d = *reinterpret_cast<const f16x8*>(sb + fw_lo + 3 * 16 * ROWB);
+                if constexpr (!LATE) {
+                    mfma_tile(3, wh_d, wl_d);
+                } else {
+                    // a late wave keeps W tile 3 for behind the next barrier.  Its reads must have returned before that barrier: behind it the
+                    // other waves' DMA overwrites this slot, and s_barrier does not wait for LDS reads.  (the scheduling barrier keeps the wait
+                    // behind W tile 2's MFMAs, which cover the reads)
+                    __builtin_amdgcn_sched_barrier(0);
+                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wh_d), "+v"(wl_d) :: "memory");
                 }
             } else
 #pragma unroll
@@ -699,13 +813,26 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
         __syncthreads();                             // every wave is done with the ring before (part of) it becomes the staging area
         // the epilogue's per-column constants are fetched BEFORE the hand-over DMA is issued: hipcc waits vmcnt(0) at the first use of
         // an ordinary load, which would otherwise also wait for the LDS-DMA pieces issued below
-        f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f}, lam = f32x4{1.f, 1.f, 1.f, 1.f};
         if constexpr (Cfg::MF == 16) {
-            const int col = n0 + wc * 64 + (lane & 15) * 4;
+            const int ln = STAGGER ? fresh_lane() : lane;      // not held over the loops: setup
+            const int col = n0 + wc * 64 + (ln & 15) * 4;
             if (g.bias) bv = *reinterpret_cast<const f32x4*>(g.bias + col);
             if (g.col_scale) lam = *reinterpret_cast<const f32x4*>(g.col_scale + col);
-            asm volatile("s_waitcnt vmcnt(0)" : "+v"(bv), "+v"(lam) :: "memory");
+            if constexpr (LATE) {
+                // the late waves' pending block of the last stage, under the latency of the two loads above (a tile has at least one stage)
+                __builtin_amdgcn_sched_barrier(0);
+                mfma_tile(3, wh_d, wl_d);
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
+        };
+        if constexpr (STAGGER) {
+            if (late) k_loop(std::true_type{});
+            else k_loop(std::false_type{});
+        } else {
+            k_loop(std::false_type{});
+        }
+        if constexpr (Cfg::MF == 16) asm volatile("s_waitcnt vmcnt(0)" : "+v"(bv), "+v"(lam) :: "memory");
         // draw the next tile now; with HANDOVER its first stage goes into the slot the last stage did NOT use, and the epilogue
         // below stages through the last stage's slot only
         TileCtx nxt;
@@ -720,15 +847,17 @@ __global__ __launch_bounds__(Cfg::THREADS, 4) void gemm_split_kernel(const GemmA
         if (HANDOVER && have) issue(nxt, 0, nbuf0);
         if (!(dbg & 8)) {
             if constexpr (Cfg::MF == 16) {
+                // (the staggered configurations: the epilogue's per-lane constants are recomputed per tile, not held over the k-loops)
+                const int lane_e = STAGGER ? fresh_lane() : lane;
                 if constexpr (RSTG) {
                     ResidStage rst = resid_stage(cur);
                     rst.s_lds = lds0 + (unsigned)last_slot * STAGE_BYTES + (unsigned)wave * 4096u;
-                    if (rstg) split_store_tile16<EPI, OUT_SPLIT, WN, 16, true>(g, smem + last_slot * (STAGE_BYTES / 4), acc16, m0, n0, M, wave, lane, bv, lam, 0, &rst);
-                    else split_store_tile16<EPI, OUT_SPLIT, WN, 16>(g, smem + last_slot * (STAGE_BYTES / 4), acc16, m0, n0, M, wave, lane, bv, lam);
+                    if (rstg) split_store_tile16<EPI, OUT_SPLIT, WN, 16, true>(g, smem + last_slot * (STAGE_BYTES / 4), acc16, m0, n0, M, wave, lane_e, bv, lam, 0, &rst);
+                    else split_store_tile16<EPI, OUT_SPLIT, WN, 16>(g, smem + last_slot * (STAGE_BYTES / 4), acc16, m0, n0, M, wave, lane_e, bv, lam);
                 } else if constexpr (HANDOVER)
-                    split_store_tile16<EPI, OUT_SPLIT, WN, 16>(g, smem + last_slot * (STAGE_BYTES / 4), acc16, m0, n0, M, wave, lane, bv, lam);
+                    split_store_tile16<EPI, OUT_SPLIT, WN, 16>(g, smem + last_slot * (STAGE_BYTES / 4), acc16, m0, n0, M, wave, lane_e, bv, lam);
                 else
-                    split_store_tile16<EPI, OUT_SPLIT, WN, 32>(g, smem, acc16, m0, n0, M, wave, lane, bv, lam, c_shift);
+                    split_store_tile16<EPI, OUT_SPLIT, WN, 32>(g, smem, acc16, m0, n0, M, wave, lane_e, bv, lam, c_shift);
             } else {
                 split_store_tile<EPI, OUT_SPLIT, WN>(g, smem, acc, m0, n0, M, wave, lane);
             }
