@@ -53,7 +53,29 @@ enum { MMEE_EXIT_VISION_AVG = 0, MMEE_EXIT_TEXT_AVG = 1, MMEE_EXIT_TEXT_VISUAL_C
 /* encoder_layer_strategy (EE/models/EE_modules.py:167-172) */
 enum { MMEE_STRATEGY_RAMP = 0, MMEE_STRATEGY_GATE = 1 };
 /* inference_strategy (EE/models/EE_modules.py:116-146): max_confidence exits on crit > thr, entropy on crit < thr, patience and margin as below */
-enum { MMEE_CRIT_MAX_CONFIDENCE = 0, MMEE_CRIT_ENTROPY = 1, MMEE_CRIT_PATIENCE = 2, MMEE_CRIT_MARGIN = 3 };
+enum { MMEE_CRIT_MAX_CONFIDENCE = 0, MMEE_CRIT_ENTROPY = 1, MMEE_CRIT_PATIENCE = 2, MMEE_CRIT_MARGIN = 3, MMEE_CRIT_GATE = 4 };
+/*
+ * MMEE_CRIT_GATE (the gate decides).  The reference's design note says what a gate head is for -- "binary gates on some encoder layers - if binary
+ * gate confidence > threshold, exit" (EE/models/EE_modules.py:21-31) -- and trains gates with BCEWithLogitsLoss against the one-hot of
+ * "classifier(gate input) is right here" (EE/models/LayoutLMv3.py:764-781), but its evaluation never lets one decide: under the gate strategy the
+ * policy thresholds the max-softmax of classifier(gate input) (EE/utils.py:183-188), which MMEE_CRIT_MAX_CONFIDENCE on a gate handle still does.
+ * Valid only with MMEE_STRATEGY_GATE.  Exit e below the final one has gate logits h = (h0, h1): float32, the head's raw output, exactly what
+ * out_head_logits holds.  Column 1 is "correctly gated" (y[range, correctly_gated.long()] = 1, LayoutLMv3.py:772-773).  The gate score is
+ *     g_e = 1 / (1 + exp((double)h0 - (double)h1))   in float64,
+ * the 2-way softmax's probability of column 1 (h0 == h1: exactly 0.5; exp overflowing: exactly 0; exp underflowing: exactly 1).  Exit e fires
+ * when g_e > thresholds[e]: strict, as under max_confidence; a NaN score never fires; if nothing fires the document leaves at the final exit.
+ * temperatures[e] keeps scaling the policy logits that are written out, exactly as under every other criterion, and does not enter g_e: a
+ * temperature on a two-way score only moves the threshold, and the threshold is already per exit.
+ * What leaves is unchanged: the scaled classifier(gate input) row.  out_conf, out_all_crit and out_head_crit carry g_e (rounded once to float32)
+ * at exits below the final one; at the final exit, which has no gate and where everybody leaves, out_conf and out_all_crit carry the max-softmax
+ * of the scaled final logits.  Embedding-level exits have gate heads like any other exit and behave the same.  MMEE_RULE_STREAK / MMEE_RULE_EITHER
+ * take g_e > thr_e as their event.  MMEE_FLAG_NO_EXIT, compaction, probes, MMEE_FLAG_LOW_LATENCY, the result stream and captured graphs (the
+ * criterion is bound at capture) are as under the other threshold criteria.  The decision reads the two gate logits and nothing else.
+ * Cost: the gate head's launches (dense layer of a 2-layer head, output projection) at every exit, which a gate handle under another criterion
+ * issues only when out_head_logits / out_head_crit are asked for.  A handle that does not select the criterion launches what it launched before.
+ * Refused, each with a message: the criterion on a MMEE_STRATEGY_RAMP handle (ee_create and ee_set_criterion) and together with use_lte.
+ * On dumped arrays: ee_gate_table, ee_gate_scan.
+ */
 /*
  * MMEE_CRIT_MARGIN (top-1 minus top-2 softmax probability; the third confidence scoring function the reference names, CSF_dict in
  * EE/large_scale.py:12-18 and EE/thresh.py:55-61, whose own top12_margin_np subtracts the two SMALLEST raw logits and is never called: this
@@ -422,6 +444,15 @@ int ee_patience_scan(const double* logits, int32_t E1, int32_t N, int32_t K, int
 int ee_lte_scan(const double* scores, const double* logits, int32_t E1, int32_t N, int32_t K, const double* thresholds, int32_t* exits,
                 double* predictions, int32_t* counts, void* stream);
 /*
+ * The gate policy (MMEE_CRIT_GATE semantics) on dumped arrays: scores dev double (E1,N) (ee_gate_table: the gate score of every exit below the
+ * final one; row E1-1 is never tested), logits dev double (E1,N,K) or NULL with predictions NULL (the policy logits, classifier(gate input)),
+ * thresholds host double [E1] (entry E1-1 unused).  exit(n) = the first e < E1-1 with scores[e,n] > thresholds[e] (strict), else E1-1.  exits
+ * dev int32 (N,), predictions dev double (N,K) or NULL (the logits row of the chosen exit), confidence dev double (N,) or NULL (the table entry
+ * of the chosen exit), counts dev int32 [E1] or NULL (documents per exit).  The scan loop of ee_lte_scan with the other sign.
+ */
+int ee_gate_scan(const double* scores, const double* logits, int32_t E1, int32_t N, int32_t K, const double* thresholds, int32_t* exits,
+                 double* predictions, double* confidence, int32_t* counts, void* stream);
+/*
  * MMEE_RULE_STREAK / MMEE_RULE_EITHER on dumped arrays.  criterion dev double (E1,N): the criterion table (ee_csf_table; max-softmax: ee_msp_table)
  * or the LTE scores; sign +1: the event is criterion > threshold (max_confidence), -1: criterion < threshold (entropy, LTE; rows of embedding
  * exits hold 1.0 under LTE, which no threshold <= 1 releases).  logits dev double (E1,N,K) for the agreement counter (argmax of the float64
@@ -487,6 +518,12 @@ int ee_msp_table(const double* logits, const int64_t* references, int32_t E1, in
  * NULL, references dev int64 (N,) (may be NULL with correct NULL). */
 int ee_csf_table(const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, int32_t criterion, double* table,
                  uint8_t* correct, void* stream);
+/* The criterion table of MMEE_CRIT_GATE, for ee_gate_scan, ee_threshold_sweep, ee_rule_scan / ee_rule_sweep (sign +1), ee_threshold_search and
+ * ee_exit_metrics' table form: head_logits dev float32 (E,N,2) (out_head_logits of a dump-all forward), final_logits dev double (N,K) (the
+ * final exit's policy logits), E >= 0, N >= 1, K >= 1.  table dev double (E+1,N): rows 0 .. E-1 the gate score g_e by the device function the
+ * decide kernels use (the bits of the forward's decision), row E the max-softmax of final_logits as ee_msp_table writes it.  The `correct`
+ * table that goes with it is ee_msp_table's on the policy logits: what leaves under the gate is the classifier(gate input) row. */
+int ee_gate_table(const float* head_logits, const double* final_logits, int32_t E, int32_t N, int32_t K, double* table, void* stream);
 
 /*
  * The threshold search: which thresholds should a deployment run?  Candidate thresholds from the percentiles of the confidence table, V candidate
@@ -851,6 +888,29 @@ int ee_lte_targets(const float* logits, const int64_t* labels, int32_t E, int32_
 int ee_lte_scores(const float* features, const float* weight, const float* bias, int32_t E, int32_t N, int32_t H, double* scores, void* stream);
 
 /*
+ * 2-way gate heads from a frozen backbone's CLS rows: the heads MMEE_CRIT_GATE scores (one-layer gates, exit_head_num_layers == 1).  The
+ * reference trains gates with nn.BCEWithLogitsLoss() against the one-hot of "classifier(gate input) is right here"
+ * (EE/models/LayoutLMv3.py:764-781); on a frozen backbone that is, per exit e, with targets c[e][n] in [0, 1] (hard 0 / 1, or soft) and
+ * z = W x + b in R^2,
+ *     L_e(W, b) = (1 / (2N)) sum_n [ bce(z_1, c) + bce(z_0, 1 - c) ] + (l2 / 2)(||W||^2 + ||b||^2),     bce(z, t) = softplus(z) - t z,
+ * the mean over the 2N elements of the (N, 2) logits that BCEWithLogitsLoss takes; column 1 is "correctly gated".  Arithmetic is float64 on the
+ * float32 rows; softplus(z) = max(z, 0) + log1p(exp(-|z|)) does not overflow.  Strongly convex for l2 > 0: one optimum.  The two columns do
+ * not interact: column j is ee_lte_fit's MMEE_LTE_LOSS_BCE problem on one exit with targets t_j and 2 l2 (the objectives differ by the factor 1/2).
+ * ee_head_fit_gate: features dev float32 (E,N,H), targets dev double (E,N); everything else -- l2, gtol, max_evals, history, the workspace
+ *   (ee_head_fit_workspace_bytes(E, N, H, 2, history)), the outputs weight (E,2,H) / bias (E,2) and their float64 forms, loss, grad_norm, evals,
+ *   status -- is ee_head_fit's at K = 2, and so are the kernels (the same slab walk with another row step), the L-BFGS driver and the launch
+ *   list: no floating-point atomics, every sum in a fixed order that is a function of N alone, deterministic to the bit, an exit fitted
+ *   alone gets the bits it gets among others.  A target that is not finite or lies outside [0, 1] fails the call through the error word; no
+ *   output is written then.  Limits: 4 <= H <= 1024, H % 4 == 0.
+ * ee_debug_head_gate_lossgrad: ONE evaluation at theta64 dev double (E, 2H + 2) (W row-major, then b): loss dev double (E,), grad (E, 2H + 2).
+ */
+int ee_head_fit_gate(const float* features, const double* targets, int32_t E, int32_t N, int32_t H, double l2, double gtol, int32_t max_evals,
+                     int32_t history, void* workspace, size_t workspace_bytes, float* weight, float* bias, double* weight64, double* bias64,
+                     double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream);
+int ee_debug_head_gate_lossgrad(const float* features, const double* targets, const double* theta64, int32_t E, int32_t N, int32_t H, double l2,
+                                double* loss, double* grad, void* stream);
+
+/*
  * Device-side input feed (replaces the host image processor + collator in front of the model, EE/data/RVL_CDIP.py:246-262
  * and EE/utils.py:93-98, 173).
  *
@@ -1024,7 +1084,7 @@ int ee_debug_xprobe(const ee_debug_xprobe_args* args, int32_t* err_flag_out, voi
  *
  * ee_debug_exit_decide: one exit of one stage through launch_decide, and launch_compact_rows behind it when meta_old, meta_new and
  *   row_src are given (all three or none).  mode: 0 threshold criterion, 1 patience, 2 LTE; rule: MMEE_RULE_*; criterion: MMEE_CRIT_*
- *   (ignored under mode 1).  pol_logits f32 [n_docs][K]; head_logits f32 [n_docs][Kh] or NULL; lte_score double [n_docs] or NULL (an
+ *   (ignored under mode 1; MMEE_CRIT_GATE: mode 0 only, and a criterion of the call only with head_logits given and Kh == 2: refused otherwise).  pol_logits f32 [n_docs][K]; head_logits f32 [n_docs][Kh] or NULL; lte_score double [n_docs] or NULL (an
  *   exit without a score: nobody leaves).  thr, temp, patience: this exit's; by_pointer != 0 hands them to the kernel as a captured
  *   graph's replay does, at [exit_index] of device vectors (the patience at [0] of its own).  The current stage: counts (16 bytes
  *   {int32 n_docs, int32 n_rows, uint64 sum_len_sq}), doc_orig [n_docs] (slots in [0, B)), doc_off [n_docs + 1], x_phys [n_docs].

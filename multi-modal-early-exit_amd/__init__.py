@@ -12,7 +12,7 @@ from .engine import (CapturedForward, EarlyExitEngine, EngineOutput, ResultChunk
 from .microbatch import MicroBatchedEngine  # noqa: F401,E402
 from .modeling import (DiTEEForImageClassification, EEModelOutput, EESequenceClassifierOutput,  # noqa: F401,E402
                        LayoutLMv3EEForSequenceClassification, load_local_processor)
-from .policy import Policy, criterion_scan_device, lte_scan_device, patience_scan_device, policy_scan_device, rule_scan_device  # noqa: F401,E402
+from .policy import Policy, criterion_scan_device, gate_scan_device, lte_scan_device, patience_scan_device, policy_scan_device, rule_scan_device  # noqa: F401,E402
 from . import harness  # noqa: F401,E402
 from . import dist  # noqa: F401,E402
 from . import sweep  # noqa: F401,E402
@@ -21,6 +21,6 @@ from . import metrics  # noqa: F401,E402
 from .metrics import ExitReport, exit_report  # noqa: F401,E402
 from . import feed  # noqa: F401,E402
 from . import heads  # noqa: F401,E402
-from .heads import (HeadFit, LteFit, MlpHeadFit, balanced_class_weights, collect_distill_features, collect_exit_features,  # noqa: F401,E402
-                    collect_lte_features, fit_distilled_exit_heads, fit_distilled_mlp_exit_heads, fit_exit_heads, fit_lte_classifier,
-                    fit_mlp_exit_heads, lte_targets, reach_weights)
+from .heads import (GateFit, HeadFit, LteFit, MlpHeadFit, balanced_class_weights, collect_distill_features, collect_exit_features,  # noqa: F401,E402
+                    collect_gate_features, collect_lte_features, fit_distilled_exit_heads, fit_distilled_mlp_exit_heads, fit_exit_heads,
+                    fit_gate_heads, fit_lte_classifier, fit_mlp_exit_heads, gate_targets, lte_targets, reach_weights)

@@ -20,7 +20,7 @@ FLAG_XPROBE = 16
 FLAG_ONE_TERM = 32
 FLAG_LOW_LATENCY = 64
 FLAG_STREAM_RESULTS = 128
-CRIT_MAX_CONFIDENCE, CRIT_ENTROPY, CRIT_PATIENCE, CRIT_MARGIN = 0, 1, 2, 3
+CRIT_MAX_CONFIDENCE, CRIT_ENTROPY, CRIT_PATIENCE, CRIT_MARGIN, CRIT_GATE = 0, 1, 2, 3, 4
 RULE_PLAIN, RULE_STREAK, RULE_EITHER = 0, 1, 2
 SEARCH_GRID, SEARCH_SAMPLED, SEARCH_MIXTURES = 0, 1, 2
 SEARCH_REFERENCE, SEARCH_POLICY = 0, 1
@@ -151,6 +151,7 @@ SYMBOLS = {
     "ee_criterion_scan": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _vp]),
     "ee_patience_scan": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ee_lte_scan": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _vp, _vp, _vp]),
+    "ee_gate_scan": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _vp]),
     "ee_rule_scan": (C.c_int, [_vp, C.c_double, _vp, _i32, _i32, _i32, C.POINTER(C.c_double), C.POINTER(_i32), _i32, _vp, _vp, _vp, _vp, _vp]),
     "ee_rule_sweep": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, C.POINTER(_i32), _i32, _i32, _vp, _vp, _vp, _vp]),
     "ee_patience_sweep": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
@@ -162,6 +163,7 @@ SYMBOLS = {
                                            _vp, _vp, _vp]),
     "ee_msp_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_csf_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ee_gate_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "ee_exit_metrics": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ee_debug_gemm": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_debug_gemm_split": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp,
@@ -185,6 +187,9 @@ SYMBOLS = {
                               _vp, _vp, _vp]),
     "ee_head_fit_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, _i32]),
     "ee_debug_head_lossgrad": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp]),
+    "ee_head_fit_gate": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp]),
+    "ee_debug_head_gate_lossgrad": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp]),
     "ee_mlp_head_fit": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp,
                                   _vp, _vp, _vp, _vp, _vp, _vp]),
     "ee_mlp_head_fit_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, _i32]),

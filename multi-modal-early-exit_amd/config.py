@@ -42,11 +42,12 @@ class EarlyExitInference(_StrEnum):
     PATIENCE = "patience"
     LTE = "lte"
     MARGIN = "margin"                                   # top-1 minus top-2 softmax probability (include/mmee.h MMEE_CRIT_MARGIN)
+    GATE = "gate"                                       # the 2-way gate head's probability of "correctly gated" (include/mmee.h MMEE_CRIT_GATE)
 
     def get_sign(self) -> Callable:
         # EE/models/EE_modules.py:137-144: max_confidence exits when crit > thr, entropy when crit < thr; patience has no threshold;
-        # margin is a confidence like max_confidence (higher is surer)
-        if self in (EarlyExitInference.MAX_CONFIDENCE, EarlyExitInference.MARGIN):
+        # margin and the gate score are confidences like max_confidence (higher is surer)
+        if self in (EarlyExitInference.MAX_CONFIDENCE, EarlyExitInference.MARGIN, EarlyExitInference.GATE):
             return operator.gt
         if self == EarlyExitInference.ENTROPY:
             return operator.lt
@@ -63,6 +64,8 @@ class EarlyExitInference(_StrEnum):
             return 2
         if self == EarlyExitInference.MARGIN:
             return 3
+        if self == EarlyExitInference.GATE:
+            return 4
         raise NotImplementedError(f"{self} not implemented")
 
 
@@ -160,6 +163,13 @@ class ExitConfig:
         # learning-to-exit (EE/models/LayoutLMv3.py:140): the exit test is sigmoid(lte_classifier(CLS row)) < threshold (include/mmee.h);
         # the reference's real switch -- inference_strategy = "lte" stays unimplemented, as its get_function() is
         self.use_lte = bool(kwargs.get("use_lte", False))
+        # inference_strategy == "gate": the 2-way gate heads decide (include/mmee.h MMEE_CRIT_GATE), so there must be gate heads, and one decision
+        if self.inference_strategy == EarlyExitInference.GATE:
+            if self.encoder_layer_strategy != EarlyExitHead.GATE:
+                raise ValueError('inference_strategy "gate" lets the 2-way gate heads decide: it needs encoder_layer_strategy "gate" '
+                                 f'(got "{self.encoder_layer_strategy}")')
+            if self.use_lte:
+                raise ValueError('inference_strategy "gate" and use_lte are two exit decisions; a configuration takes one of them')
 
     # ---- derived views used by the hot path -------------------------------------------------
     @property

@@ -158,8 +158,13 @@ int check_config(const ee_config& c) {
     if (c.precision == MMEE_PREC_F32_SPLIT && (c.num_attention_heads < 1 || c.rel_pos_bins < 2 || c.rel_2d_pos_bins < 2) && !beit)
         return fail(nullptr, "bad relative-position configuration");
     if (c.exit_head_num_layers != 1 && c.exit_head_num_layers != 2) return fail(nullptr, "exit_head_num_layers must be 1 or 2");
-    if (c.criterion != MMEE_CRIT_MAX_CONFIDENCE && c.criterion != MMEE_CRIT_ENTROPY && c.criterion != MMEE_CRIT_PATIENCE && c.criterion != MMEE_CRIT_MARGIN)
+    if (c.criterion != MMEE_CRIT_MAX_CONFIDENCE && c.criterion != MMEE_CRIT_ENTROPY && c.criterion != MMEE_CRIT_PATIENCE && c.criterion != MMEE_CRIT_MARGIN &&
+        c.criterion != MMEE_CRIT_GATE)
         return fail(nullptr, "ee_create: unknown criterion %d", c.criterion);
+    if (c.criterion == MMEE_CRIT_GATE && c.strategy != MMEE_STRATEGY_GATE)
+        return fail(nullptr, "ee_create: MMEE_CRIT_GATE needs MMEE_STRATEGY_GATE: a ramp handle has no 2-way gate heads to score");
+    if (c.criterion == MMEE_CRIT_GATE && c.use_lte)
+        return fail(nullptr, "use_lte: learning-to-exit and MMEE_CRIT_GATE are two exit decisions; a handle takes one of them");
     if (c.use_lte && beit)
         return fail(nullptr, "use_lte: learning-to-exit is built for MMEE_ARCH_LAYOUTLMV3 only (the BEiT / DiT variant has no lte_classifier)");
     if (c.use_lte && c.criterion == MMEE_CRIT_PATIENCE)

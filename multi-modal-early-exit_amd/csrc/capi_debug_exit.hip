@@ -80,7 +80,12 @@ int ee_debug_exit_decide(const ee_debug_exit_decide_args* a, void* stream) {
     if (a->mode < DECIDE_THRESHOLD || a->mode > DECIDE_LTE || a->rule < RULE_PLAIN || a->rule > RULE_EITHER || (a->mode == DECIDE_PATIENCE && a->rule != RULE_PLAIN))
         return fail(nullptr, "%s: launch_decide has no kernel for mode %d with rule %d (modes 0 threshold, 1 patience, 2 LTE; rules 0 plain, 1 streak, 2 either; patience takes the plain rule only)",
                     who, a->mode, a->rule);
-    if (a->mode != DECIDE_PATIENCE && a->criterion != CRIT_MAX_CONFIDENCE && a->criterion != CRIT_ENTROPY && a->criterion != CRIT_MARGIN)
+    // MMEE_CRIT_GATE is a criterion of this call only where the kernel can read two gate logits (mode 0, head_logits given, Kh == 2); without
+    // them the criteria a call can name are the three functions of the policy row, and the refusal says so
+    const bool gate_ok = a->criterion == CRIT_GATE && a->mode == DECIDE_THRESHOLD && a->head_logits && a->Kh == 2;
+    if (a->criterion == CRIT_GATE && a->mode == DECIDE_PATIENCE)
+        return fail(nullptr, "%s: MMEE_CRIT_GATE is a threshold criterion (mode 0), got mode %d", who, a->mode);
+    if (a->mode != DECIDE_PATIENCE && a->criterion != CRIT_MAX_CONFIDENCE && a->criterion != CRIT_ENTROPY && a->criterion != CRIT_MARGIN && !gate_ok)
         return fail(nullptr, "%s: criterion %d is none of MMEE_CRIT_MAX_CONFIDENCE, _ENTROPY, _MARGIN", who, a->criterion);
     if (a->K < 1 || a->Kh < 1) return fail(nullptr, "%s: K %d or Kh %d is below 1", who, a->K, a->Kh);
     if (a->exit_index < 0 || a->exit_index > 255) return fail(nullptr, "%s: exit_index %d outside [0, 255]", who, a->exit_index);

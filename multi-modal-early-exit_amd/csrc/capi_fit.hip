@@ -210,6 +210,42 @@ int ee_debug_head_distill_lossgrad(const float* features, const float* teacher_l
     return head_lossgrad_call("ee_debug_head_distill_lossgrad", false, features, labels, &soft, nullptr, theta64, E, N, H, K, l2, loss, grad, stream);
 }
 
+// ---- 2-way gate heads from CLS rows: the gate objective (include/mmee.h) on the labelled fit's kernels at K = 2 ---------------------------------
+static const char* const kBadGateTarget = "%s: a target is not finite or lies outside [0, 1]%s";
+
+int ee_head_fit_gate(const float* features, const double* targets, int32_t E, int32_t N, int32_t H, double l2, double gtol, int32_t max_evals,
+                     int32_t history, void* workspace, size_t workspace_bytes, float* weight, float* bias, double* weight64, double* bias64,
+                     double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
+    const char* who = "ee_head_fit_gate";
+    if (!features || !targets || !workspace || !weight || !bias)
+        return fail(nullptr, "%s: NULL argument (features, targets, workspace, weight and bias are required)", who);
+    if (head_fit_refuse(who, features, E, N, H, 2, l2)) return 1;
+    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return head_fit_workspace_bytes(E, N, H, 2, history); })) return 1;
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HeadFitArgs a{{features, E, N, H, l2, gtol, max_evals, history, workspace, nullptr, nullptr, loss, grad_norm, evals, status},
+                  nullptr, 2, weight, bias, weight64, bias64, DistillTargets{}, nullptr};
+    a.gate_targets = targets;
+    if (!launch_head_fit(a, s)) return fail(nullptr, "%s: preparing the workspace (memset, copy of theta0) failed", who);
+    if (launch_status(nullptr, who)) return 1;
+    int err = 0;
+    if (hipMemcpyAsync(&err, workspace, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return fail(nullptr, "%s: reading the error word failed: %s", who, hipGetErrorString(hipGetLastError()));
+    if (err & 1) return fail(nullptr, kBadGateTarget, who, "; no output was written");
+    return 0;
+}
+
+int ee_debug_head_gate_lossgrad(const float* features, const double* targets, const double* theta64, int32_t E, int32_t N, int32_t H, double l2,
+                                double* loss, double* grad, void* stream) {
+    const char* who = "ee_debug_head_gate_lossgrad";
+    if (!features || !targets || !theta64 || !loss || !grad) return fail(nullptr, "%s: NULL argument", who);
+    if (head_fit_refuse(who, features, E, N, H, 2, l2)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return debug_lossgrad(who, head_fit_partial_bytes(E, N, H, 2) / sizeof(double), s, [&](double* scratch, int* err) {
+        launch_head_lossgrad(features, nullptr, theta64, E, N, H, 2, l2, scratch, err, loss, grad, s, DistillTargets{}, nullptr, targets);
+    }, "%s: a target is not finite or lies outside [0, 1] (K = %d)", 2);
+}
+
 // ---- two-layer exit heads from CLS rows (mlp_head_fit.hip) -------------------------------------------------------------------------------
 size_t ee_mlp_head_fit_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history) {
     if (E < 1 || N < 1 || H < 1 || K < 1 || history < 1) return 0;

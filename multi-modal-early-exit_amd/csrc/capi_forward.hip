@@ -595,8 +595,8 @@ struct Forward {
                 pol = h->pol_logits;
             } else if (c.strategy == MMEE_STRATEGY_GATE) {
                 // the policy only ever sees classifier(gate input) (EE/utils.py:183-188); the 2-way gate logits (exit_states) are
-                // computed when the caller asked for them (the dump of model.forward), not in the fast path
-                const bool want_gate = a.out_head_logits || a.out_head_crit;
+                // computed when the caller asked for them (the dump of model.forward) or when they decide (MMEE_CRIT_GATE), else not
+                const bool want_gate = a.out_head_logits || a.out_head_crit || c.criterion == MMEE_CRIT_GATE;
                 if (want_gate) run_head(*hw, in, ld, gather, h->hid, h->head_logits, in_split, split_rows);
                 run_head(h->classifier, in, ld, gather, h->hid2, h->pol_logits, in_split, split_rows, lte);  // gated_logits, EE/models/LayoutLMv3.py:768
                 pol = h->pol_logits; head = want_gate ? h->head_logits : nullptr; Kh = 2;      // 2-way gate heads, EE/models/LayoutLMv3.py:83
@@ -803,7 +803,7 @@ struct Forward {
         final_exit();
         if (stream_results) h->stream_armed = true;
         r.last_B = B; r.last_T = T; r.last_stages = E + 1; r.last_flags = a.flags;
-        r.last_gate_heads = a.out_head_logits || a.out_head_crit;
+        r.last_gate_heads = a.out_head_logits || a.out_head_crit || c.criterion == MMEE_CRIT_GATE;
         if (!cap) { const int rc_post = forward_post(h, s); if (rc_post) return rc_post; }
         return launch_status(h, cap ? "ee_graph_capture" : "ee_forward");
     }

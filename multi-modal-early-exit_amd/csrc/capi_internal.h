@@ -20,7 +20,7 @@
 #include "mmee_kernels.h"
 
 static_assert(mmee::CRIT_MAX_CONFIDENCE == MMEE_CRIT_MAX_CONFIDENCE && mmee::CRIT_ENTROPY == MMEE_CRIT_ENTROPY &&
-              mmee::CRIT_PATIENCE == MMEE_CRIT_PATIENCE && mmee::CRIT_MARGIN == MMEE_CRIT_MARGIN, "the kernels' criterion codes are the ABI's");
+              mmee::CRIT_PATIENCE == MMEE_CRIT_PATIENCE && mmee::CRIT_MARGIN == MMEE_CRIT_MARGIN && mmee::CRIT_GATE == MMEE_CRIT_GATE, "the kernels' criterion codes are the ABI's");
 static_assert(mmee::SEARCH_GRID == MMEE_SEARCH_GRID && mmee::SEARCH_SAMPLED == MMEE_SEARCH_SAMPLED && mmee::SEARCH_MIXTURES == MMEE_SEARCH_MIXTURES &&
               mmee::SEARCH_REFERENCE == MMEE_SEARCH_REFERENCE && mmee::SEARCH_POLICY == MMEE_SEARCH_POLICY, "the search's codes are the ABI's");
 

@@ -142,8 +142,14 @@ int ee_set_attentions_out(ee_handle* h, float* out) {
 
 int ee_set_criterion(ee_handle* h, int32_t criterion) {
     if (!h) return 1;
-    if (criterion != MMEE_CRIT_MAX_CONFIDENCE && criterion != MMEE_CRIT_ENTROPY && criterion != MMEE_CRIT_PATIENCE && criterion != MMEE_CRIT_MARGIN)
+    if (criterion != MMEE_CRIT_MAX_CONFIDENCE && criterion != MMEE_CRIT_ENTROPY && criterion != MMEE_CRIT_PATIENCE && criterion != MMEE_CRIT_MARGIN &&
+        criterion != MMEE_CRIT_GATE)
         return fail(h, "ee_set_criterion: unknown criterion %d", criterion);
+    if (criterion == MMEE_CRIT_GATE && h->cfg.strategy != MMEE_STRATEGY_GATE)
+        return fail(h, "ee_set_criterion: unknown criterion %d on a MMEE_STRATEGY_RAMP handle: MMEE_CRIT_GATE scores the 2-way heads of MMEE_STRATEGY_GATE, "
+                       "which this handle does not have", criterion);
+    if (criterion == MMEE_CRIT_GATE && h->cfg.use_lte)
+        return fail(h, "ee_set_criterion: MMEE_CRIT_GATE on a use_lte handle: learning-to-exit and the gate score are two exit decisions");
     if (criterion == MMEE_CRIT_PATIENCE && h->cfg.use_lte)
         return fail(h, "ee_set_criterion: MMEE_CRIT_PATIENCE on a use_lte handle: learning-to-exit and patience are two exit decisions");
     if (criterion == MMEE_CRIT_PATIENCE && h->rule != MMEE_RULE_PLAIN)

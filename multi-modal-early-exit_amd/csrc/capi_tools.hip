@@ -153,6 +153,16 @@ int ee_lte_scan(const double* scores, const double* logits, int32_t E1, int32_t 
     return run_threshold_scan("ee_lte_scan", "threshold", a, thresholds, E1, SCAN_TABLE, RULE_PLAIN, stream);
 }
 
+int ee_gate_scan(const double* scores, const double* logits, int32_t E1, int32_t N, int32_t K, const double* thresholds, int32_t* exits,
+                 double* predictions, double* confidence, int32_t* counts, void* stream) {
+    if (!thresholds || E1 < 1 || E1 > 256 || N < 0 || K < 1 || (N > 0 && (!scores || !exits)) || (predictions && !logits))
+        return fail(nullptr, "ee_gate_scan: bad argument (1 <= E1 <= 256, N >= 0, K >= 1, scores / thresholds / exits not NULL, predictions need the logits)");
+    ScanArgs a{};
+    a.logits = logits; a.crit = scores; a.sign = 1.0; a.E1 = E1; a.N = N; a.K = K;       // score > threshold
+    a.exits = exits; a.pred = predictions; a.conf = confidence; a.counts = counts;
+    return run_threshold_scan("ee_gate_scan", "threshold", a, thresholds, E1, SCAN_TABLE, RULE_PLAIN, stream);
+}
+
 int ee_rule_scan(const double* criterion, double sign, const double* logits, int32_t E1, int32_t N, int32_t K, const double* thresholds,
                  const int32_t* patience, int32_t rule, int32_t* exits, double* predictions, double* confidence, int32_t* counts, void* stream) {
     if (!thresholds || !patience || E1 < 1 || E1 > 256 || N < 0 || K < 1 || (N > 0 && (!criterion || !exits)) || (sign != 1.0 && sign != -1.0))
@@ -319,6 +329,14 @@ int ee_csf_table(const double* logits, const int64_t* references, int32_t E1, in
     if (!have_device("ee_csf_table")) return 1;
     launch_csf_table(logits, (const long long*)references, E1, N, K, criterion, table, correct, reinterpret_cast<hipStream_t>(stream));
     return launch_status(nullptr, "ee_csf_table");
+}
+
+int ee_gate_table(const float* head_logits, const double* final_logits, int32_t E, int32_t N, int32_t K, double* table, void* stream) {
+    if (!final_logits || !table || E < 0 || N < 1 || K < 1 || (E > 0 && !head_logits))
+        return fail(nullptr, "ee_gate_table: bad argument (final_logits / table not NULL, head_logits not NULL when E > 0, E >= 0, N, K >= 1)");
+    if (!have_device("ee_gate_table")) return 1;
+    launch_gate_table(head_logits, final_logits, E, N, K, table, reinterpret_cast<hipStream_t>(stream));
+    return launch_status(nullptr, "ee_gate_table");
 }
 
 static_assert(kMetricAccuracy == MMEE_METRIC_ACCURACY && kMetricBrier == MMEE_METRIC_BRIER && kMetricNll == MMEE_METRIC_NLL &&

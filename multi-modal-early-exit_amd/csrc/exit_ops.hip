@@ -626,6 +626,19 @@ void launch_csf_table(const double* logits, const long long* refs, int E1, int N
     hipLaunchKernelGGL(k, dim3(grid_1d((long long)E1 * N, 256, 4096)), dim3(256), 0, s, logits, refs, E1, N, K, table, correct);
 }
 
+// The criterion table of MMEE_CRIT_GATE (ee_gate_table): table[e][n] = gate_score_f64 of the raw gate logits head[e][n][0 .. 1], the function
+// the decide kernels call, for the E exits that have a gate; row E, the final exit's max-softmax, is csf_table_kernel<CRIT_MAX_CONFIDENCE>'s
+__global__ __launch_bounds__(256) void gate_table_kernel(const float* __restrict__ head, size_t total, double* __restrict__ table) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256)
+        table[i] = gate_score_f64(head[2 * i], head[2 * i + 1]);
+}
+
+void launch_gate_table(const float* head_logits, const double* final_logits, int E, int N, int K, double* table, hipStream_t s) {
+    const size_t total = (size_t)E * N;
+    if (total) hipLaunchKernelGGL(gate_table_kernel, dim3(grid_1d((long long)total, 256, 4096)), dim3(256), 0, s, head_logits, total, table);
+    launch_csf_table(final_logits, nullptr, 1, N, K, CRIT_MAX_CONFIDENCE, table + total, nullptr, s);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Per-exit temperature fit: argmin_T mean NLL(softmax(z / T), y)   (TemperatureScaler.set_temperature,
 // EE/generic_scaling.py:64-111, L-BFGS-B on sklearn log_loss).  In beta = 1/T the objective

@@ -83,8 +83,8 @@ void launch_head_out(const HeadOutArgs& a, int max_docs, hipStream_t s) {
 // largest value counting multiplicity and S = sum_k exp(x_k - m1) in label order.  m1 and S are the max-softmax's own two passes; m2 comes from a
 // third pass that skips ONE label holding m1 (no exp inside it: the decide kernels sit at their register limit in the second pass, and a value
 // kept live through it went to scratch).  K = 1: m2 = -inf, exp = 0, margin 1.
-// float32, as the model computes exit_states[j][1] (EE/models/EE_modules.py:149-160)
-__device__ inline float crit_f32(const float* z, int K, int criterion) {
+// float32, as the model computes exit_states[j][1] (EE/models/EE_modules.py:149-160): the criteria that are functions of a logits row
+__device__ inline float crit_row_f32(const float* z, int K, int criterion) {
     if (criterion != CRIT_ENTROPY) {
         float m = z[0];
         for (int k = 1; k < K; ++k) m = fmaxf(m, z[k]);
@@ -109,7 +109,15 @@ __device__ inline float crit_f32(const float* z, int K, int criterion) {
     return logf(A) - B / A;
 }
 
-// float64 on (double)logit / T, as the policy computes it (scipy.special.softmax on the float64 store, EE/policy.py:30-32)
+// crit_row_f32, and CRIT_GATE: z is the gate's two logits and the value the float64 gate score rounded once.  The LTE decide kernels call
+// crit_row_f32 itself (use_lte and the gate criterion exclude each other: ee_create), and stay the code they were
+__device__ inline float crit_f32(const float* z, int K, int criterion) {
+    return criterion == CRIT_GATE ? (float)gate_score_f64(z[0], z[1]) : crit_row_f32(z, K, criterion);
+}
+
+// float64 on (double)logit / T, as the policy computes it (scipy.special.softmax on the float64 store, EE/policy.py:30-32).  CRIT_GATE: the
+// max-softmax, which is what a gate handle reports where there is no gate (the final exit); the gate score itself takes no temperature and
+// is gate_score_f64 on the head's logits (exit_decide_body)
 __device__ inline double crit_f64(const float* z, int K, double temp, int criterion) {
     if (criterion != CRIT_ENTROPY) {
         double m = (double)z[0] / temp;
@@ -149,6 +157,8 @@ __device__ inline double crit_f64(const float* z, int K, double temp, int criter
 // LTE (ee_config.use_lte): the test is "the float64 score head_out_lte_kernel left in a.lte_score is strictly below the threshold"; the score
 // is what the outputs carry as the criterion.  Embedding exits have no score (a.lte_score null): 1.0, nobody leaves.
 // The max_confidence / entropy / margin kernel is the DECIDE_THRESHOLD instantiation.
+// GATE (MMEE_CRIT_GATE; gate strategy, DECIDE_THRESHOLD): below the final exit the criterion is the gate score of a.head_logits (Kh == 2),
+// g = gate_score_f64(h0, h1), the test g > thr; what leaves is still the scaled row of a.pol_logits.  The final exit has no gate: the max-softmax.
 // RULE (ee_set_exit_rule; THRESHOLD and LTE modes): the mode's test is the EVENT f_e and the rule decides on it.  MMEE_RULE_STREAK: the event
 // must have held at t_e exits in a row (s_e = f_e ? s_{e-1} + 1 : 0 in p.run[orig]).  MMEE_RULE_EITHER: the event, or PABEE's counter
 // c_e >= t_e ((p.prev[orig], p.run[orig]) exactly as under PATIENCE).  The same state arrays, written unconditionally at exit 0; t_e is the
@@ -202,6 +212,10 @@ __device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const Pati
             } else if constexpr (MODE == DECIDE_LTE) {
                 crit = a.lte_score ? a.lte_score[i] : 1.0;
                 leave = a.lte_score && crit < thr;                        // strict, EE/models/LayoutLMv3.py:262
+            } else if (a.criterion == CRIT_GATE && !a.is_final && a.head_logits) {
+                const float* hz = a.head_logits + (size_t)i * a.Kh;      // the decision reads the two gate logits and nothing else
+                crit = gate_score_f64(hz[0], hz[1]);
+                leave = crit_fires(CRIT_GATE, crit, thr);                 // strict
             } else {
                 crit = crit_f64(z, a.K, temp, a.criterion);
                 leave = crit_fires(a.criterion, crit, thr);               // strict, EE/policy.py:33
@@ -226,9 +240,13 @@ __device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const Pati
                 float* o = a.out_head_logits + ((size_t)a.exit_index * a.B + orig) * a.Kh;
                 for (int k = 0; k < a.Kh; ++k) o[k] = hz[k];
             }
-            if (a.head_logits && a.out_head_crit)
-                a.out_head_crit[(size_t)a.exit_index * a.B + orig] =
-                    crit_f32(a.head_logits + (size_t)i * a.Kh, a.Kh, PATIENCE ? CRIT_MAX_CONFIDENCE : a.criterion);
+            if (a.head_logits && a.out_head_crit) {
+                const float* hz = a.head_logits + (size_t)i * a.Kh;
+                float hc;
+                if constexpr (MODE == DECIDE_THRESHOLD) hc = crit_f32(hz, a.Kh, a.criterion);
+                else hc = crit_row_f32(hz, a.Kh, PATIENCE ? CRIT_MAX_CONFIDENCE : a.criterion);
+                a.out_head_crit[(size_t)a.exit_index * a.B + orig] = hc;
+            }
             if (leave) {
                 if (a.out_logits)
                     for (int k = 0; k < a.K; ++k) a.out_logits[(size_t)orig * a.K + k] = (float)((double)z[k] / temp);

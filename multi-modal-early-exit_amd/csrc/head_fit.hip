@@ -12,6 +12,9 @@
 // ee_head_fit_weighted adds sample weights to either objective, again as argument structs of the same kernel: head_fit_row_scale_kernel makes
 // scale[e][n] = w[e][n] N / W_e once per call, the weighted row steps multiply a row's N dL/dz and its loss by it and skip a row whose scale is
 // zero, and everything behind the row step is shared, division by N included.  The unweighted instantiations are the code they were.
+// ee_head_fit_gate (2-way gate heads, K = 2) is one more argument struct of the same kernel: its row step is the two binary cross-entropies of
+// the gate objective against a target in [0, 1] per (exit, row) (gate_row_step), everything else -- slabs, logits pass, gradient pass, partials,
+// reduce, driver, workspace -- is the labelled fit's at K = 2.
 // This file is the objective; the L-BFGS around it is run_lbfgs_fit (fit_lbfgs.hip), the workspace layout and the control words are in
 // head_fit_common.h.
 //
@@ -57,6 +60,12 @@ struct WeightedLossGradArgs : LossGradArgs {
 struct WeightedDistillLossGradArgs : DistillLossGradArgs {
     const double* scale;
 };
+// ee_head_fit_gate: K == 2 and y null; err bit 0 is a target that is not finite or lies outside [0,1]
+struct GateLossGradArgs : LossGradArgs {
+    const double* targets;           // (E,N): c[e][n] = how right classifier(gate input) is at exit e on row n
+};
+template <typename Args>
+constexpr bool kGate = std::is_same_v<Args, GateLossGradArgs>;
 template <typename Args>
 constexpr bool kDistilled = std::is_base_of_v<DistillLossGradArgs, Args>;
 template <typename Args>
@@ -94,6 +103,32 @@ __device__ inline void distill_row_step(const Args& a, double* Z, double sc, int
         const int k = sub + 8 * i;
         if (k < Kp) Z[row * Kp + k] = (valid && k < K) ? scaled<kWeighted<Args>>(v[i], sc) : 0.0;
     }
+}
+
+// bce(z, t) = softplus(z) - t z with softplus(z) = max(z, 0) + log1p(exp(-|z|)), which does not overflow; its derivative sigmoid(z) - t from the
+// same exponential
+__device__ inline double gate_bce(double z, double t, double& dz) {
+    const double ez = exp(-fabs(z)), inv = 1.0 / (1.0 + ez);
+    dz = (z >= 0.0 ? inv : ez * inv) - t;
+    return (fmax(z, 0.0) + log1p(ez)) - t * z;
+}
+
+// The gate row step (include/mmee.h, ee_head_fit_gate): the row's loss (bce(z_1, c) + bce(z_0, 1 - c)) / 2 -- the reduce kernel divides by N,
+// which makes the objective's 1 / (2N) -- and N dL/dz in place of the two logits, zeros in the padding columns.  Eight threads a row, as in the
+// other row steps; each reads both logits before any of the row writes (lanes of one wave, LDS operations in program order).
+__device__ inline void gate_row_step(const GateLossGradArgs& a, double* Z, int e, int n0, int rows, int Kp, double& loss) {
+    const int t = threadIdx.x, row = t >> 3, sub = t & 7;
+    const bool valid = row < rows;
+    double c = valid ? a.targets[(size_t)e * a.N + n0 + row] : 0.0;
+    if (!(c >= 0.0 && c <= 1.0)) {                           // a NaN fails both compares
+        atomicOr(a.err, 1);
+        c = 0.0;
+    }
+    const double z0 = Z[row * Kp], z1 = Z[row * Kp + 1];
+    double d0, d1;
+    const double l = 0.5 * (gate_bce(z1, c, d1) + gate_bce(z0, 1.0 - c, d0));
+    if (sub == 0 && valid) loss += l;
+    for (int k = sub; k < Kp; k += 8) Z[row * Kp + k] = (valid && k < 2) ? 0.5 * (k == 0 ? d0 : d1) : 0.0;
 }
 
 // KT classes x HC columns (h = t + 256 i) of the gradient per thread; Args: LossGradArgs (labels) or DistillLossGradArgs (soft targets), or
@@ -196,6 +231,7 @@ __global__ __launch_bounds__(kThreads) void head_fit_lossgrad_kernel(Args a) {
 
         // ---- the row step, the compile-time difference between the two objectives: the row's loss, N dL/dz in place of Z ----
         if constexpr (kDistilled<Args>) distill_row_step(a, Z, sc, n0, rows, K, Kp, loss);
+        else if constexpr (kGate<Args>) gate_row_step(a, Z, e, n0, rows, Kp, loss);
         else {
             // max-shifted softmax, loss, D = P - Y: eight threads a row.  The weighted form multiplies D and the loss by the row's scale, last
             // of all; a row whose scale is zero counts as one that does not exist, and its label is not read.
@@ -366,9 +402,9 @@ void launch_lossgrad(const Args& a, int E, hipStream_t s) {
 }
 
 // one evaluation: the partials of every running exit, then their fixed-order sums; soft.teacher null: the hard-label objective; weighted: the
-// row scales lie behind the partials in p.tail
+// row scales lie behind the partials in p.tail; gate_targets given (K == 2, y null, no teacher, no weights): the gate objective
 void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, const DistillTargets& soft, bool weighted, int E, int N, int H, int K,
-                 double l2, hipStream_t s) {
+                 double l2, hipStream_t s, const double* gate_targets = nullptr) {
     LossGradArgs a{};
     a.X = X; a.y = y; a.theta = p.theta; a.theta_stride = p.theta_stride; a.ctrl = p.ctrl; a.err = p.err;
     a.partial = static_cast<double*>(p.tail); a.N = N; a.H = H; a.K = K;
@@ -377,7 +413,8 @@ void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, cons
     a.slabs_per_chunk = (n_slabs + a.chunks - 1) / a.chunks;
     const DistillLossGradArgs d{a, soft.teacher, soft.alpha, soft.temperature};
     const double* scale = weighted ? scale_table(p.tail, E, N, H, K) : nullptr;
-    if (scale && soft.teacher) launch_lossgrad(WeightedDistillLossGradArgs{d, scale}, E, s);
+    if (gate_targets) launch_lossgrad(GateLossGradArgs{a, gate_targets}, E, s);
+    else if (scale && soft.teacher) launch_lossgrad(WeightedDistillLossGradArgs{d, scale}, E, s);
     else if (scale) launch_lossgrad(WeightedLossGradArgs{a, scale}, E, s);
     else if (soft.teacher) launch_lossgrad(d, E, s);
     else launch_lossgrad(a, E, s);
@@ -408,17 +445,17 @@ void launch_row_scale(const float* weights, int E, int N, double* scale, int* er
 }
 
 void launch_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* partial, int* err,
-                          double* loss, double* grad, hipStream_t s, const DistillTargets& soft, const float* weights) {
+                          double* loss, double* grad, hipStream_t s, const DistillTargets& soft, const float* weights, const double* gate_targets) {
     const size_t P = (size_t)K * H + K;
     if (weights) launch_row_scale(weights, E, N, scale_table(partial, E, N, H, K), err, s);
-    launch_eval({theta, P, nullptr, err, loss, grad, P, partial}, X, y, soft, weights != nullptr, E, N, H, K, l2, s);
+    launch_eval({theta, P, nullptr, err, loss, grad, P, partial}, X, y, soft, weights != nullptr, E, N, H, K, l2, s, gate_targets);
 }
 
 bool launch_head_fit(const HeadFitArgs& f, hipStream_t s) {
     const int KH = f.K * f.H;
     const bool weighted = f.weights != nullptr;
     return run_lbfgs_fit(f, one_layer_layout(f.E, f.N, f.H, f.K, f.history, weighted),
-                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.labels, f.soft, weighted, f.E, f.N, f.H, f.K, f.l2, s); },
+                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.labels, f.soft, weighted, f.E, f.N, f.H, f.K, f.l2, s, f.gate_targets); },
                          {{0, KH, f.weight, f.weight64}, {KH, f.K, f.bias, f.bias64}}, s,
                          weighted ? std::function<void(const FitEvalPoint&)>([&](const FitEvalPoint& p) {
                              launch_row_scale(f.weights, f.E, f.N, scale_table(p.tail, f.E, f.N, f.H, f.K), p.err, s);

@@ -79,7 +79,8 @@ struct ThrPack {
 
 struct DecideArgs {
     const float* pol_logits;         // [n_docs][K]   logits the policy sees (ramp: head logits; gate: classifier(gate input))
-    const float* head_logits;        // [n_docs][Kh]  raw exit-head logits (== pol_logits for ramps); null for the final stage
+    const float* head_logits;        // [n_docs][Kh]  raw exit-head logits (== pol_logits for ramps); null for the final stage.  CRIT_GATE: the two
+                                     // gate logits the decision reads (Kh == 2), and nothing else
     int K, Kh;
     double thr, temp;
     const double* thr_ptr;           // captured-graph forwards (ee_graph_capture): threshold / temperature of exit e at [exit_index] of device
@@ -135,10 +136,14 @@ struct EmitArgs {
 };
 
 // ee_config.criterion (include/mmee.h MMEE_CRIT_*; capi_internal.h asserts the values agree)
-enum { CRIT_MAX_CONFIDENCE = 0, CRIT_ENTROPY = 1, CRIT_PATIENCE = 2, CRIT_MARGIN = 3 };
-// the direction of a threshold criterion: max-softmax and margin leave on crit > thr, entropy on crit < thr; strict, so a NaN never fires
+enum { CRIT_MAX_CONFIDENCE = 0, CRIT_ENTROPY = 1, CRIT_PATIENCE = 2, CRIT_MARGIN = 3, CRIT_GATE = 4 };
+// the direction of a threshold criterion: max-softmax, margin and the gate score leave on crit > thr, entropy on crit < thr; strict, so a NaN never fires
 __host__ __device__ inline bool crit_fires(int criterion, double crit, double thr) { return criterion == CRIT_ENTROPY ? crit < thr : crit > thr; }
 __host__ __device__ inline double crit_sign(int criterion) { return criterion == CRIT_ENTROPY ? -1.0 : 1.0; }
+// The gate score (MMEE_CRIT_GATE; include/mmee.h): the 2-way softmax's probability of column 1 ("correctly gated") of the raw float32 gate
+// logits, in float64.  h0 - h1 large: exp overflows to inf and the score is exactly 0; large negative: exactly 1; equal: exactly 0.5.  The one
+// copy the decide kernels (exit_stage.hip) and the table kernel of the dumped-array tools (exit_ops.hip) share, so their bits agree.
+__device__ inline double gate_score_f64(float h0, float h1) { return 1.0 / (1.0 + exp((double)h0 - (double)h1)); }
 
 // how launch_decide picks its kernel: the exit test (MODE) and the rule built on it (RULE = MMEE_RULE_*; DECIDE_PATIENCE takes RULE_PLAIN only)
 enum { DECIDE_THRESHOLD = 0, DECIDE_PATIENCE = 1, DECIDE_LTE = 2 };
@@ -309,6 +314,8 @@ bool launch_exit_metrics(const MetricsArgs& a, hipStream_t s);
 // criterion: CRIT_MAX_CONFIDENCE, CRIT_ENTROPY or CRIT_MARGIN
 void launch_csf_table(const double* logits, const long long* refs, int E1, int N, int K, int criterion, double* table, unsigned char* correct,
                       hipStream_t s);
+// ee_gate_table: table (E+1,N); rows 0 .. E-1 = gate_score_f64 of head_logits (E,N,2), row E = the max-softmax of final_logits (N,K) (launch_csf_table's)
+void launch_gate_table(const float* head_logits, const double* final_logits, int E, int N, int K, double* table, hipStream_t s);
 void launch_temperature_fit(const double* logits, const long long* labels, int E1, int N, int K, int max_iter, double* T_out,
                             double* nll_out, double* acc_out, double* conf_out, int* iters_out, hipStream_t s);
 // ee_head_fit (head_fit.hip): softmax-regression heads per exit, float64 on float32 features; include/mmee.h states the objective
@@ -341,18 +348,21 @@ struct HeadFitArgs : FitArgs {       // E parameter sets; theta0 and theta64 nul
     double *weight64, *bias64;       // the same in float64, or null
     DistillTargets soft;
     const float* weights = nullptr;  // (E,N) sample weights (ee_head_fit_weighted), or null: every row counts once
+    const double* gate_targets = nullptr;    // (E,N) in [0,1] (ee_head_fit_gate: K == 2, labels null, no teacher, no weights), or null
 };
 int head_fit_chunks(int N);
 // weighted: the fit carries sample weights, and its workspace the row-scale table (E,N) float64 behind the partials
 size_t head_fit_workspace_bytes(int E, int N, int H, int K, int history, bool weighted = false);
 size_t head_fit_partial_bytes(int E, int N, int H, int K);
 // false: the memset of the workspace failed.  The error word is the first int of the workspace (bit 0: a label outside [0,K); bit 1: a
-// teacher logit that is not finite; bit 2: a sample weight that is negative or not finite; bit 3: an exit whose weights sum to zero).
+// teacher logit that is not finite; bit 2: a sample weight that is negative or not finite; bit 3: an exit whose weights sum to zero; the gate
+// objective: bit 0 is a target that is not finite or outside [0,1]).
 bool launch_head_fit(const HeadFitArgs& a, hipStream_t s);
 // one evaluation at theta (E, K*H + K): loss (E,), grad (E, K*H + K); partial: head_fit_partial_bytes, with weights (E,N) E * N doubles
 // more behind them; err: one zeroed int
 void launch_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* partial, int* err,
-                          double* loss, double* grad, hipStream_t s, const DistillTargets& soft = {}, const float* weights = nullptr);
+                          double* loss, double* grad, hipStream_t s, const DistillTargets& soft = {}, const float* weights = nullptr,
+                          const double* gate_targets = nullptr);
 // ee_mlp_head_fit (mlp_head_fit.hip): two-layer heads (dense + tanh + out_proj) per exit; theta = W1 (H,H), b1 (H,), W2 (K,H), b2 (K,)
 constexpr int kMlpHeadFitRows = 64;          // the row tile of the GEMM kernels, the largest of the new kernels' tiles (MMEE_MLP_HEAD_FIT_ROWS)
 struct MlpHeadFitArgs : FitArgs {    // E parameter sets; theta0 (E,P) required, theta64 (E,P)

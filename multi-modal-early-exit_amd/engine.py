@@ -521,7 +521,8 @@ class EarlyExitEngine:
         return layers
 
     def set_criterion(self, strategy):
-        """Exit criterion of every later forward ("max_confidence" / "entropy" / "margin" / "patience"; ee_set_criterion).  The reference's driver overrides
+        """Exit criterion of every later forward ("max_confidence" / "entropy" / "margin" / "patience" / "gate", the last on gate handles
+        only; ee_set_criterion).  The reference's driver overrides
         ``model.config.exit_config["inference_strategy"]`` after construction (EE/utils.py:62-78); modeling.py forwards that write here."""
         from .config import EarlyExitInference
         st = strategy if isinstance(strategy, EarlyExitInference) else EarlyExitInference(str(strategy))

@@ -29,7 +29,13 @@ policy logits, ``lte_targets`` turns logits and labels into the targets "this ex
 reference's summed per-exit MSE (or the convex BCE) and ``LteFit.state_dict`` names ``encoder.lte_classifier.weight / .bias``.  The MSE
 objective is not convex: ``status`` 0 is a stationary point reached by descent from the start.
 
-This is not a trainer: gates, embedding-level exits, the final classifier, per-exit LTE loss weights, mini-batches and an unfrozen backbone
+The 2-way gate heads of the gate strategy -- the heads ``inference_strategy="gate"`` lets decide (include/mmee.h MMEE_CRIT_GATE) -- are fitted
+from the same forwards too (``ee_head_fit_gate``): ``collect_gate_features`` gathers the CLS rows and the gated logits ``classifier(gate
+input)``, ``gate_targets`` turns those and labels into "the classifier is right here", ``fit_gate_heads`` minimises the reference's
+``BCEWithLogitsLoss`` against the one-hot of that (strongly convex: one optimum) and ``GateFit.state_dict`` names the heads.  One-layer gates
+only.
+
+This is not a trainer: two-layer gates, embedding-level exits, the final classifier, per-exit LTE loss weights, mini-batches and an unfrozen backbone
 are out of scope.
 
 Reloading heads into an engine that holds captured graphs does not re-capture them: capture again after ``load_weights``.
@@ -69,8 +75,8 @@ def _cat_batches(per_batch):
 def _check_fittable(cfg: ModelConfig, head_layers: int = 1):
     ec = cfg.exit_config
     if str(ec.encoder_layer_strategy) != "ramp":
-        raise ValueError("exit heads are fitted for the ramp strategy only: a gate shows the policy the final classifier's logits, "
-                         "there is no head to fit")
+        raise ValueError("ramp exit heads are fitted for the ramp strategy only: the 2-way heads of a gate configuration are fitted by "
+                         "fit_gate_heads (collect_gate_features, gate_targets)")
     if head_layers == 2:
         if ec.exit_head_num_layers != 2:
             raise ValueError("two-layer exit heads are fitted for exit_head_num_layers == 2 only (fit_exit_heads fits the one-layer head)")
@@ -601,4 +607,116 @@ def fit_lte_classifier(features, targets, loss: str = "mse", l2: float = 1e-2, g
     ws, need = _workspace("ee_lte_fit_workspace_bytes", dev, E, N, H, history)
     _call("ee_lte_fit", dev, X, T, th0, E, N, H, LTE_LOSSES[loss], float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.weight,
           fit.bias, fit.theta64, fit.loss, fit.grad_norm, fit.evals, fit.status)
+    return fit
+
+
+# ---- 2-way gate heads: the heads inference_strategy = "gate" lets decide ---------------------------------------------------------------------
+def _check_gate_cfg(cfg: ModelConfig):
+    ec = cfg.exit_config
+    if cfg.arch == "beit":
+        raise ValueError("gate heads are fitted for LayoutLMv3 configurations only")
+    if str(ec.encoder_layer_strategy) != "gate":
+        raise ValueError("gate heads are fitted for the gate strategy only (encoder_layer_strategy = 'gate'): fit_exit_heads fits ramps")
+    if ec.exit_head_num_layers != 1:
+        raise ValueError("gate heads are fitted for exit_head_num_layers == 1 only: a two-layer gate is not a convex problem and is not built")
+    if ec.embedding_exits:
+        raise ValueError(f"embedding-level exits {ec.embedding_exits} cannot be fitted: the forward does not return their pooled inputs")
+    if not ec.encoder_exit_layers:
+        raise ValueError("the configuration has no encoder exits")
+
+
+def collect_gate_features(engine, batches: Iterable[Mapping]):
+    """Dump-all forwards of a gate-strategy ``engine`` over ``batches`` (dicts of ``engine.forward`` keyword inputs).  Returns two device
+    tensors from the same forwards: ``features`` (E,N,H) float32, the CLS rows leaving the E configured encoder exit layers -- the inputs of
+    the gates ``encoder.early_exits.0 .. E-1`` --, and ``gated_logits`` (E,N,K) float32, ``classifier(gate input)`` at those exits (the
+    policy logits, ``all_logits``).  Encoder exits only: embedding-level exits are skipped, as ``collect_lte_features`` skips them."""
+    ec = engine.cfg.exit_config
+    if engine.cfg.arch == "beit" or str(ec.encoder_layer_strategy) != "gate":
+        raise ValueError("collect_gate_features needs a LayoutLMv3 engine of the gate strategy (encoder_layer_strategy = 'gate')")
+    if not ec.encoder_exit_layers:
+        raise ValueError("the configuration has no encoder exits")
+    n_emb, n_enc = len(ec.embedding_exits), len(ec.encoder_exit_layers)
+    return tuple(_cat_batches((rows, out.all_logits[n_emb:n_emb + n_enc].to(torch.float32))
+                              for rows, out in _dump_all(engine, batches, want_all=True)))
+
+
+def gate_targets(gated_logits, labels, device=None) -> "torch.Tensor":
+    """(E,N) float64 device tensor: 1 where the argmax (first maximum) of ``gated_logits`` (E,N,K) float32 equals ``labels`` (N,), else 0 --
+    the reference's ``correctly_gated`` (EE/models/LayoutLMv3.py:770-773), and ``1 - lte_targets``: the launch of ``ee_lte_targets`` and one
+    subtraction on the device (exact).  A label outside [0,K) or a NaN logit fails the call."""
+    return 1.0 - lte_targets(gated_logits, labels, device)
+
+
+@dataclass
+class GateFit:
+    weight: "torch.Tensor"       # (E,2,H) float32, device
+    bias: "torch.Tensor"         # (E,2)   float32
+    weight64: "torch.Tensor"     # the float64 solution the float32 pair is rounded from
+    bias64: "torch.Tensor"
+    loss: "torch.Tensor"         # (E,) float64: the objective at the returned point
+    grad_norm: "torch.Tensor"    # (E,) float64
+    evals: "torch.Tensor"        # (E,) int32: loss / gradient evaluations used
+    status: "torch.Tensor"       # (E,) int32: 0 converged (grad_norm <= gtol), 1 max_evals, 2 the line search made no progress
+    l2: float
+
+    def logits(self, features) -> "torch.Tensor":
+        """(E,N,2) float64 gate logits of the float32 heads on ``features`` (E,N,H), on the device."""
+        X = _rows(features, on=self.weight.device)[1].to(torch.float64)
+        return torch.baddbmm(self.bias.to(torch.float64).unsqueeze(1), X, self.weight.to(torch.float64).transpose(1, 2))
+
+    def scores(self, features) -> "torch.Tensor":
+        """(E,N) float64 gate scores 1 / (1 + exp(h0 - h1)) of the float32 heads' float32 logits on ``features`` (E,N,H), on the device, by the
+        device function the forward decides with (``sweep.gate_table``'s rows)."""
+        from .sweep import gate_table
+        h = self.logits(features).to(torch.float32).contiguous()
+        dummy = torch.zeros((h.shape[1], 1), dtype=torch.float64, device=h.device)
+        return gate_table(h, dummy, device=h.device)[:-1]
+
+    def state_dict(self, cfg: ModelConfig) -> Dict[str, np.ndarray]:
+        """``layoutlmv3.encoder.early_exits.{k}.out_proj.weight`` (2,H) / ``.bias`` (2,) (host float32), ready for ``engine.load_weights`` next
+        to the backbone's tensors."""
+        _check_gate_cfg(cfg)
+        E, K, H = self.weight.shape
+        if E != len(cfg.exit_config.encoder_exit_layers) or K != 2 or H != cfg.hidden_size:
+            raise ValueError(f"the fit is (E,2,H) = {(E, K, H)}, the configuration wants {(len(cfg.exit_config.encoder_exit_layers), 2, cfg.hidden_size)}")
+        w, b = self.weight.cpu().numpy(), self.bias.cpu().numpy()
+        out = {}
+        for k in range(E):
+            out[f"layoutlmv3.encoder.early_exits.{k}.out_proj.weight"] = np.ascontiguousarray(w[k])
+            out[f"layoutlmv3.encoder.early_exits.{k}.out_proj.bias"] = np.ascontiguousarray(b[k])
+        return out
+
+
+def fit_gate_heads(features, targets, l2: float = 1e-2, gtol: float = 1e-9, max_evals: int = 2000, history: int = 8, device=None,
+                   sample_weight=None) -> GateFit:
+    """``features`` (E,N,H) float32 (numpy or device tensor; (N,H) is one exit; ``collect_gate_features``), ``targets`` (E,N) in [0,1]
+    (``gate_targets``; soft targets are allowed).  Minimises, per exit, (1 / (2N)) sum_n [bce(z_1, c) + bce(z_0, 1 - c)] +
+    (l2 / 2)(||W||^2 + ||b||^2) over W (2,H), b (2,) in float64 (include/mmee.h, ee_head_fit_gate): ``nn.BCEWithLogitsLoss()`` on the (N,2)
+    gate logits against the one-hot of the target, the reference's gate loss.  Strongly convex: one optimum.  The kernels, the L-BFGS and the
+    budget are ``fit_exit_heads``' at K = 2.  Limits: H <= 1024 and a multiple of 4; ``sample_weight`` is not built for gates and is refused.
+
+    Host synchronisation: one wait after the last launch, to read the error word (a target outside [0,1] or not finite fails the call)."""
+    if sample_weight is not None:
+        raise ValueError("fit_gate_heads: sample_weight is not built for gate heads (the ramp fits take it)")
+    fs = tuple(features.shape)
+    if len(fs) not in (2, 3):
+        raise ValueError(f"features are {fs}, need (E,N,H), or (N,H) for one exit")
+    E, N, H = (1,) + fs if len(fs) == 2 else fs
+    if H > 1024 or H % 4:
+        raise ValueError(f"fit_gate_heads: H = {H}, need H <= 1024 and a multiple of 4")
+    ts = tuple(np.shape(targets))
+    if ts != (E, N) and not (E == 1 and ts == (N,)):
+        raise ValueError(f"targets are {ts}, need (E,N) = {(E, N)}")
+    if not l2 > 0.0:
+        raise ValueError(f"fit_gate_heads: l2 = {l2}, need l2 > 0 (the objective is strongly convex only then)")
+    capi.load()
+    dev, X = _rows(features, device)
+    T = _to_device(targets, torch.float64, dev).view(E, N)
+    f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
+    fit = GateFit(torch.zeros((E, 2, H), dtype=torch.float32, device=dev), torch.zeros((E, 2), dtype=torch.float32, device=dev),
+                  f64(E, 2, H), f64(E, 2), f64(E), f64(E), torch.zeros((E,), dtype=torch.int32, device=dev),
+                  torch.full((E,), -1, dtype=torch.int32, device=dev), float(l2))
+    ws, need = _workspace("ee_head_fit_workspace_bytes", dev, E, N, H, 2, history)
+    _call("ee_head_fit_gate", dev, X, T, E, N, H, float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.weight, fit.bias,
+          fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status)
     return fit

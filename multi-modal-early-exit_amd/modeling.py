@@ -159,6 +159,8 @@ class LayoutLMv3EEForSequenceClassification:
     def exit_criterion(self, logits):
         """``max_confidence`` / ``entropy`` on a logits tensor (EE/models/EE_modules.py:149-160), and ``margin`` (include/mmee.h
         MMEE_CRIT_MARGIN: top-1 minus top-2 softmax probability as ``(1 - exp(m2 - m1)) / S``, exactly 0 on a tie, 1 for a single label).
+        ``gate`` (include/mmee.h MMEE_CRIT_GATE): ``logits`` are a gate head's two logits and the criterion the 2-way softmax's probability of
+        column 1, in float64, rounded once -- what ``forward`` reports as ``exit_states[j][1]`` under it.
         Patience has no per-exit criterion (the reference's ``get_function`` has none for it, EE/models/EE_modules.py:130-137):
         ``NotImplementedError``."""
         self._sync_exit_config()
@@ -166,6 +168,10 @@ class LayoutLMv3EEForSequenceClassification:
         strategy = str(self.model_config.exit_config.inference_strategy)
         if strategy == "max_confidence":
             return torch.softmax(logits, dim=1).max(dim=1)[0]
+        if strategy == "gate":
+            if logits.shape[1] != 2:
+                raise ValueError(f"exit_criterion under inference_strategy 'gate' reads a gate head's two logits, got {logits.shape[1]} columns")
+            return (1.0 / (1.0 + torch.exp(logits[:, 0].double() - logits[:, 1].double()))).to(logits.dtype)
         if strategy == "margin":
             if logits.shape[1] == 1:
                 return torch.ones_like(logits[:, 0])

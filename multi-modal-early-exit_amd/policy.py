@@ -128,6 +128,22 @@ def lte_scan_device(scores, logits, thresholds, device=None):
     return exits, pred, counts
 
 
+def gate_scan_device(scores, logits, thresholds, device=None, want_conf: bool = False):
+    """The gate decision (include/mmee.h MMEE_CRIT_GATE) on dumped arrays (ee_gate_scan): the first exit e < E1 - 1 whose gate score is strictly
+    above its threshold, else the last exit.  ``scores`` (E1,N) (``sweep.gate_table``), ``logits`` (E1,N,K) (the policy logits,
+    ``classifier(gate input)``), ``thresholds`` scalar or (E1,).  Returns device tensors (exits int32, predictions float64, confidence
+    float64 | None = the table entry of the chosen exit, counts int32)."""
+    lib = capi.load()
+    dev = _require_torch_cuda(device)
+    S, L = _f64_on(dev, scores), _f64_on(dev, logits)
+    if L.dim() != 3 or tuple(S.shape) != tuple(L.shape[:2]):
+        raise ValueError("scores must have shape (num_exits + 1, num_samples) and logits (num_exits + 1, num_samples, num_labels)")
+    E1, N, K = L.shape
+    thr_c = _threshold_vector(thresholds, E1)
+    return _run_scan("ee_gate_scan", dev, L.shape, want_conf,
+                     lambda exits, pred, conf, counts, stream: lib.ee_gate_scan(_ptr(S), _ptr(L), E1, N, K, thr_c, exits, pred, conf, counts, stream))
+
+
 def rule_scan_device(criterion, logits, thresholds, patience, rule, sign: float = 1.0, device=None, want_conf: bool = False):
     """The combined exit rules (include/mmee.h MMEE_RULE_*) on dumped arrays (ee_rule_scan).  ``criterion`` (E1,N): the criterion table
     (``sweep.msp_table`` for max-softmax) or the LTE scores; ``sign`` +1: the test is ``criterion > threshold``, -1: ``criterion <
@@ -160,9 +176,11 @@ class Policy:
         self.logits = logits
         self.config = config
 
-    def _finish(self, thresholds=None, patience=None, lte_scores=None, rule=None, criterion=None):
+    def _finish(self, thresholds=None, patience=None, lte_scores=None, rule=None, criterion=None, gate_scores=None):
         num_exits, num_samples = self.logits.shape[0], self.logits.shape[1]
-        if rule is not None:
+        if gate_scores is not None:
+            exits, pred, _, counts = gate_scan_device(gate_scores, self.logits, thresholds)
+        elif rule is not None:
             if lte_scores is not None:
                 crit, sign = lte_scores, -1.0
             else:
@@ -232,6 +250,20 @@ class Policy:
                 raise ValueError('lte_policy needs config["lte_thresholds"] (per exit) or config["exit_threshold"]')
             thr = float(self.config["exit_threshold"])
         return self._finish(thr, lte_scores=self.config["lte_scores"])
+
+    def gate_policy(self):
+        """The gate decision (include/mmee.h MMEE_CRIT_GATE; the reference's design note EE/models/EE_modules.py:21-31, which its evaluation never
+        runs) on dumped arrays: ``config["gate_scores"]`` (E1,N), ``sweep.gate_table`` of a gate handle's dump; exit at the first e before the
+        last whose gate score is strictly above ``config["exit_thresholds"][e]`` (per exit) or the global ``config["exit_threshold"]``, else
+        the last.  ``self.logits`` are the policy logits (``classifier(gate input)``), whose rows are the predictions.
+        ``config["exit_policy"] = "gate_policy"`` selects it through EE/eval.py:91-98's ``getattr`` dispatch."""
+        scores = self.config.get("gate_scores")
+        if scores is None:
+            raise ValueError('gate_policy needs config["gate_scores"] (the (num_exits + 1, num_samples) table of sweep.gate_table)')
+        if tuple(np.shape(scores)) != tuple(self.logits.shape[:2]):
+            raise ValueError(f'gate_policy: config["gate_scores"] has shape {tuple(np.shape(scores))}, the logits say '
+                             f'{tuple(self.logits.shape[:2])} (num_exits + 1, num_samples)')
+        return self._finish(self._exit_thresholds("gate_policy"), gate_scores=scores)
 
     def _rule_policy(self, rule):
         if self.config.get("patience") is None:

@@ -66,6 +66,24 @@ def csf_table(logits, references=None, criterion="max_confidence", as_csf: bool 
     return table, corr
 
 
+def gate_table(head_logits, final_logits, device=None):
+    """The criterion table of the gate decision (include/mmee.h MMEE_CRIT_GATE; ee_gate_table): float64 (E+1,N) on the device from a gate
+    handle's dump, ``head_logits`` (E,N,2) float32 (``EngineOutput.head_logits``) and ``final_logits`` (N,K) (the last row of ``all_logits``).
+    Rows 0 .. E-1 are the gate scores with the bits the forward decides on, row E the max-softmax of the final logits (``msp_table``'s).
+    With ``msp_table(all_logits, references)[1]`` as ``correct`` it goes unchanged into ``threshold_sweep``, ``rule_sweep`` (sign +1),
+    ``threshold_search`` and ``metrics.exit_report(conf=, correct=)``; ``policy.gate_scan_device`` runs the policy on it."""
+    lib = capi.load()
+    dev = _require_torch_cuda(device)
+    Hl, F = _on(dev, head_logits, torch.float32), _f64_on(dev, final_logits)
+    if Hl.dim() != 3 or Hl.shape[2] != 2 or F.dim() != 2 or F.shape[0] != Hl.shape[1] or F.shape[0] < 1:
+        raise ValueError("head_logits must have shape (num_exits, num_samples, 2) and final_logits (num_samples, num_labels)")
+    E, N, K = Hl.shape[0], F.shape[0], F.shape[1]
+    table = torch.empty((E + 1, N), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        capi.check(lib.ee_gate_table(_ptr(Hl), _ptr(F), E, N, K, _ptr(table), _stream()), None, "ee_gate_table")
+    return table
+
+
 def patience_sweep(logits, references, patiences, want_hist: bool = False, device=None):
     """Every patience value of ``patiences`` (V,) over one dumped array ``logits`` (E1,N,K) with labels ``references`` (N,): for each t the
     exits of the patience policy (include/mmee.h), the accuracy of the predictions at those exits and the mean exit (ee_patience_sweep: the
