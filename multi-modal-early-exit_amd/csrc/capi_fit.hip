@@ -1,8 +1,13 @@
-// Entry points of the device fits, none of which sees a handle: one-layer and two-layer exit heads (ee_head_fit, ee_mlp_head_fit; against the
-// final classifier's logits instead of labels: ee_head_fit_distill, ee_mlp_head_fit_distill; either with sample weights: ee_head_fit_weighted,
-// ee_mlp_head_fit_weighted; all through the same bodies) and the
-// learning-to-exit classifier (ee_lte_fit, with ee_lte_targets and ee_lte_scores) from dumped CLS rows, their workspace queries, and the
-// ee_debug_*_lossgrad hooks that run one evaluation of an objective on caller-provided buffers.  The L-BFGS is fit_lbfgs.hip.
+// Entry points of the device fits, none of which sees a handle: one-layer and two-layer exit heads from dumped CLS rows against labels
+// (ee_head_fit, ee_mlp_head_fit), against the final classifier's logits (ee_head_fit_distill, ee_mlp_head_fit_distill), either with sample
+// weights (ee_head_fit_weighted, ee_mlp_head_fit_weighted), the 2-way gate heads (ee_head_fit_gate), and the learning-to-exit classifier
+// (ee_lte_fit, with ee_lte_targets and ee_lte_scores); their workspace queries, and the ee_debug_*_lossgrad hooks that run one evaluation of an
+// objective on caller-provided buffers.  The L-BFGS is fit_lbfgs.hip.
+//
+// What a head is fitted against is one value, HeadObjective (mmee_kernels.h).  Each head entry point builds it from its own arguments
+// (labelled, distilled, weighted, gate) and calls one of three bodies -- head_fit_call, mlp_head_fit_call, head_lossgrad_call -- which hand it
+// down unchanged; objective_refuse holds the objective's own refusals, and error_word_fail is the one decoder of the error word, for the head
+// fits, the LTE entry points and the debug hooks alike.
 #include "capi_internal.h"
 
 using namespace mmee;
@@ -25,33 +30,48 @@ static int budget_refuse(const char* who, double gtol, int32_t max_evals, int32_
     return 0;
 }
 
-static const char* const kBadTeacher = "%s: a teacher logit is not finite (dump-all marks the rows a document never reached with NaN)%s";
+// ---- the error word, decoded once ---------------------------------------------------------------------------------------------------------
+// Which objective an entry point states.  For the head fits it is the family of entry points that built the HeadObjective, which the value
+// alone does not say: a distilled entry point that was handed NULL teacher_logits is refused, a weighted one fits against labels then.
+enum class Objective { kLabelled, kDistilled, kWeighted, kGate, kLte, kLteTargets };
 
-// bits 2 and 3 of the error word are the weighted head fits' (launch_row_scale); checked first: labels and teacher rows mean nothing under them
-static int weight_error(const char* who, int err, const char* tail) {
+// bit 0: a bad label or target -- which, and so the message, is the objective's; bit 1: a teacher logit that is not finite (the distilled
+// objectives); bit 2: a sample weight that is negative or not finite, bit 3: an exit whose weights sum to zero (launch_row_scale).  Bits 2 and 3
+// are looked at first: labels and teacher rows mean nothing under them.  fit: a fit's call, which has then written no output and says so;
+// else a debug hook's one evaluation.  -> 0 for a clean word
+static int error_word_fail(const char* who, int err, Objective of, bool fit, int K) {
+    const char* tail = fit ? "; no output was written" : "";
     if (err & 4) return fail(nullptr, "%s: a sample weight is negative or not finite%s", who, tail);
     if (err & 8) return fail(nullptr, "%s: an exit's weights sum to zero%s", who, tail);
+    if (err & 1) switch (of) {
+        default:
+            return fail(nullptr, fit ? "%s: a label is outside [0, K = %d); no output was written" : "%s: a label is outside [0, K = %d)", who, K);
+        case Objective::kGate:
+            return fit ? fail(nullptr, "%s: a target is not finite or lies outside [0, 1]%s", who, tail)
+                       : fail(nullptr, "%s: a target is not finite or lies outside [0, 1] (K = %d)", who, K);
+        case Objective::kLte:
+            return fail(nullptr, fit ? "%s: a target is outside [0, 1] or NaN; no output was written" : "%s: a target is outside [0, 1] or NaN", who);
+        case Objective::kLteTargets:
+            return fail(nullptr, "%s: a label is outside [0, K = %d) or a logit is NaN (a row its document never reached); nothing was written", who, K);
+    }
+    if (err & 2)
+        return fail(nullptr, "%s: a teacher logit is not finite (dump-all marks the rows a document never reached with NaN)%s", who, tail);
     return 0;
 }
 
-// The tail of a call that left an error word on the device: the launch status, the word read on the stream, one synchronise.  bad: the
-// message for bit 0 (bad input), a format of (who, K).  Bit 1 is the distilled fits': a teacher logit that is not finite; bits 2 and 3 are the
-// weighted fits'.
-static int finish_call(const char* who, bool prepared, const void* err_word, hipStream_t s, const char* bad, int K) {
+// The tail of a call that left an error word on the device: the launch status, the word read on the stream, one synchronise.
+static int finish_call(const char* who, bool prepared, const void* err_word, hipStream_t s, Objective of, int K) {
     if (!prepared) return fail(nullptr, "%s: preparing the workspace (memset, copy of theta0) failed", who);
     if (launch_status(nullptr, who)) return 1;
     int err = 0;
     if (hipMemcpyAsync(&err, err_word, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
         return fail(nullptr, "%s: reading the error word failed: %s", who, hipGetErrorString(hipGetLastError()));
-    if (weight_error(who, err, "; no output was written")) return 1;
-    if (err & 1) return fail(nullptr, bad, who, K);
-    if (err & 2) return fail(nullptr, kBadTeacher, who, "; no output was written");
-    return 0;
+    return error_word_fail(who, err, of, true, K);
 }
 
-// One evaluation of an objective for a debug entry point: launch(scratch, err) gets n zeroed doubles and a zeroed error word.  bad: as above.
+// One evaluation of an objective for a debug entry point: launch(scratch, err) gets n zeroed doubles and a zeroed error word.
 template <typename Launch>
-static int debug_lossgrad(const char* who, size_t n, hipStream_t s, Launch launch, const char* bad, int K) {
+static int debug_lossgrad(const char* who, size_t n, hipStream_t s, Launch launch, Objective of, int K) {
     if (!have_device(who)) return 1;
     Scratch sc;
     double* scratch = nullptr;
@@ -63,10 +83,7 @@ static int debug_lossgrad(const char* who, size_t n, hipStream_t s, Launch launc
     int err = 0;
     if (hipMemcpy(&err, err_dev, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of the error word failed", who);
     if (launch_status(nullptr, who)) return 1;
-    if (weight_error(who, err, "")) return 1;
-    if (err & 1) return fail(nullptr, bad, who, K);
-    if (err & 2) return fail(nullptr, kBadTeacher, who, "");
-    return 0;
+    return error_word_fail(who, err, of, false, K);
 }
 
 // the refusals the head fits and their debug hooks share, before any device call
@@ -95,97 +112,111 @@ static int lte_objective_refuse(const char* who, int32_t loss, double l2) {
     return 0;
 }
 
-static const char* const kBadLabelFit = "%s: a label is outside [0, K = %d); no output was written";
-static const char* const kBadLabel = "%s: a label is outside [0, K = %d)";
+// ---- the head fits' entry points: each builds its HeadObjective and calls one of three bodies ------------------------------------------------
+// what a head entry point asks for: the objective it built, and which family of entry points it belongs to
+struct Asked {
+    Objective by;
+    HeadObjective o;
+};
+static const long long* int64_labels(const int64_t* labels) { return reinterpret_cast<const long long*>(labels); }
+static Asked labelled(const int64_t* labels) { return {Objective::kLabelled, {int64_labels(labels), {}, nullptr, nullptr}}; }
+static Asked distilled(const int64_t* labels, const float* teacher_logits, double alpha, double temperature) {
+    return {Objective::kDistilled, {int64_labels(labels), {teacher_logits, alpha, temperature}, nullptr, nullptr}};
+}
+static Asked weighted(const int64_t* labels, const float* teacher_logits, double alpha, double temperature, const float* weights) {
+    return {Objective::kWeighted, {int64_labels(labels), {teacher_logits, alpha, temperature}, weights, nullptr}};
+}
+static Asked gate(const double* targets) { return {Objective::kGate, {nullptr, {}, nullptr, targets}}; }
 
-// ---- the head fits' entry points, hard-label, distilled and weighted, as one body each ---------------------------------------------------------
-// soft: null for the entry points that fit against labels; else the distilled objective's targets, refused here before any device call
-static int distill_refuse(const char* who, const int64_t* labels, const DistillTargets* soft) {
-    if (!soft) return 0;
-    if (!soft->teacher) return fail(nullptr, "%s: NULL argument (teacher_logits are required)", who);
-    if (!(soft->alpha >= 0.0 && soft->alpha <= 1.0)) return fail(nullptr, "%s: alpha = %g, need 0 <= alpha <= 1", who, soft->alpha);
-    if (!(soft->temperature > 0.0) || std::isinf(soft->temperature))
-        return fail(nullptr, "%s: temperature = %g, need a finite temperature > 0", who, soft->temperature);
-    if (soft->alpha < 1.0 && !labels) return fail(nullptr, "%s: NULL labels at alpha = %g: only alpha == 1 does without them", who, soft->alpha);
+// The refusals of the objective itself, with the body's NULL check among them, in the order they have always been tried: the weighted entry
+// points' own, the NULL check, the distilled objective's.  missing: one of the body's other required pointers is NULL; null_fmt: the body's
+// message for a NULL pointer, a format of (who, the name of the target the objective cannot do without).
+static int objective_refuse(const char* who, const Asked& q, bool missing, const char* null_fmt) {
+    const HeadObjective& o = q.o;
+    const DistillTargets& soft = o.soft;
+    if (q.by == Objective::kWeighted) {                     // teacher_logits may be NULL here: labels alone
+        if (!o.weights) return fail(nullptr, "%s: NULL argument (weights are required: (E,N) float32; the unweighted entry points take none)", who);
+        if (!soft.teacher && soft.alpha != 0.0)
+            return fail(nullptr, "%s: alpha = %g without teacher_logits: NULL teacher_logits select the labelled objective, alpha must be 0", who,
+                        soft.alpha);
+    }
+    const bool to_gate = q.by == Objective::kGate, to_teacher = q.by == Objective::kDistilled || (q.by == Objective::kWeighted && soft.teacher);
+    if (missing || (to_gate ? !o.gate_targets : !to_teacher && !o.labels))
+        return fail(nullptr, null_fmt, who, to_gate ? "targets" : to_teacher ? "teacher_logits" : "labels");
+    if (!to_teacher) return 0;
+    if (!soft.teacher) return fail(nullptr, "%s: NULL argument (teacher_logits are required)", who);
+    if (!(soft.alpha >= 0.0 && soft.alpha <= 1.0)) return fail(nullptr, "%s: alpha = %g, need 0 <= alpha <= 1", who, soft.alpha);
+    if (!(soft.temperature > 0.0) || std::isinf(soft.temperature))
+        return fail(nullptr, "%s: temperature = %g, need a finite temperature > 0", who, soft.temperature);
+    if (soft.alpha < 1.0 && !o.labels) return fail(nullptr, "%s: NULL labels at alpha = %g: only alpha == 1 does without them", who, soft.alpha);
     return 0;
 }
 
-// The weighted entry points name their objective by teacher_logits, which may be NULL (labels alone): their refusals in front of the shared
-// ones.  -> the soft targets to hand on, null for the labelled objective
-static int weighted_refuse(const char* who, const float* weights, const DistillTargets& soft) {
-    if (!weights) return fail(nullptr, "%s: NULL argument (weights are required: (E,N) float32; the unweighted entry points take none)", who);
-    if (!soft.teacher && soft.alpha != 0.0)
-        return fail(nullptr, "%s: alpha = %g without teacher_logits: NULL teacher_logits select the labelled objective, alpha must be 0", who,
-                    soft.alpha);
-    return 0;
-}
-
-// weights: null for the entry points that have none; the weighted ones have refused a NULL table before they come here
-static int head_fit_call(const char* who, const float* features, const int64_t* labels, const DistillTargets* soft, const float* weights,
-                         int32_t E, int32_t N, int32_t H, int32_t K, double l2, double gtol, int32_t max_evals, int32_t history, void* workspace,
-                         size_t workspace_bytes, float* weight, float* bias, double* weight64, double* bias64, double* loss, double* grad_norm,
-                         int32_t* evals, int32_t* status, void* stream) {
-    if (!features || (!soft && !labels) || !workspace || !weight || !bias)
-        return fail(nullptr, "%s: NULL argument (features, %s, workspace, weight and bias are required)", who, soft ? "teacher_logits" : "labels");
-    if (distill_refuse(who, labels, soft) || head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
-    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return head_fit_workspace_bytes(E, N, H, K, history, weights != nullptr); }))
+static int head_fit_call(const char* who, const Asked& q, const float* features, int32_t E, int32_t N, int32_t H, int32_t K,
+                         double l2, double gtol, int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* weight,
+                         float* bias, double* weight64, double* bias64, double* loss, double* grad_norm, int32_t* evals, int32_t* status,
+                         void* stream) {
+    if (objective_refuse(who, q, !features || !workspace || !weight || !bias,
+                         "%s: NULL argument (features, %s, workspace, weight and bias are required)") ||
+        head_fit_refuse(who, features, E, N, H, K, l2))
+        return 1;
+    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return head_fit_workspace_bytes(E, N, H, K, history, q.o.weights != nullptr); }))
         return 1;
     if (!have_device(who)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const HeadFitArgs a{{features, E, N, H, l2, gtol, max_evals, history, workspace, nullptr, nullptr, loss, grad_norm, evals, status},
-                        reinterpret_cast<const long long*>(labels), K, weight, bias, weight64, bias64, soft ? *soft : DistillTargets{}, weights};
-    return finish_call(who, launch_head_fit(a, s), workspace, s, kBadLabelFit, K);
+                        q.o, K, weight, bias, weight64, bias64};
+    return finish_call(who, launch_head_fit(a, s), workspace, s, q.by, K);
 }
 
-static int mlp_head_fit_call(const char* who, const float* features, const int64_t* labels, const DistillTargets* soft, const float* weights,
-                             const double* theta0, int32_t E, int32_t N, int32_t H, int32_t K, double l2, double gtol, int32_t max_evals, int32_t history,
-                             void* workspace, size_t workspace_bytes, float* dense_weight, float* dense_bias, float* weight, float* bias,
-                             double* theta64, double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
-    if (!features || (!soft && !labels) || !theta0 || !workspace || !dense_weight || !dense_bias || !weight || !bias)
-        return fail(nullptr, "%s: NULL argument (features, %s, theta0, workspace, dense_weight, dense_bias, weight and bias are required; "
-                             "theta = 0 is a saddle the iteration never leaves, so there is no default start)", who,
-                    soft ? "teacher_logits" : "labels");
-    if (distill_refuse(who, labels, soft) || head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
+static int mlp_head_fit_call(const char* who, const Asked& q, const float* features, const double* theta0, int32_t E,
+                             int32_t N, int32_t H, int32_t K, double l2, double gtol, int32_t max_evals, int32_t history, void* workspace,
+                             size_t workspace_bytes, float* dense_weight, float* dense_bias, float* weight, float* bias, double* theta64,
+                             double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
+    if (objective_refuse(who, q, !features || !theta0 || !workspace || !dense_weight || !dense_bias || !weight || !bias,
+                         "%s: NULL argument (features, %s, theta0, workspace, dense_weight, dense_bias, weight and bias are required; "
+                         "theta = 0 is a saddle the iteration never leaves, so there is no default start)") ||
+        head_fit_refuse(who, features, E, N, H, K, l2))
+        return 1;
     if (budget_refuse(who, gtol, max_evals, history, workspace_bytes,
-                      [&] { return mlp_head_fit_workspace_bytes(E, N, H, K, history, weights != nullptr); }))
+                      [&] { return mlp_head_fit_workspace_bytes(E, N, H, K, history, q.o.weights != nullptr); }))
         return 1;
     if (!have_device(who)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const MlpHeadFitArgs a{{features, E, N, H, l2, gtol, max_evals, history, workspace, theta0, theta64, loss, grad_norm, evals, status},
-                           reinterpret_cast<const long long*>(labels), K, dense_weight, dense_bias, weight, bias, soft ? *soft : DistillTargets{},
-                           weights};
-    return finish_call(who, launch_mlp_head_fit(a, s), workspace, s, kBadLabelFit, K);
+                           q.o, K, dense_weight, dense_bias, weight, bias};
+    return finish_call(who, launch_mlp_head_fit(a, s), workspace, s, q.by, K);
 }
 
 // ONE evaluation of a head objective: mlp selects the two-layer head
-static int head_lossgrad_call(const char* who, bool mlp, const float* features, const int64_t* labels, const DistillTargets* soft,
-                              const float* weights, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K, double l2, double* loss, double* grad,
-                              void* stream) {
-    if (!features || (!soft && !labels) || !theta64 || !loss || !grad) return fail(nullptr, "%s: NULL argument", who);
-    if (distill_refuse(who, labels, soft) || head_fit_refuse(who, features, E, N, H, K, l2)) return 1;
+static int head_lossgrad_call(const char* who, bool mlp, const Asked& q, const float* features, const double* theta64,
+                              int32_t E, int32_t N, int32_t H, int32_t K, double l2, double* loss, double* grad, void* stream) {
+    if (objective_refuse(who, q, !features || !theta64 || !loss || !grad, "%s: NULL argument") ||
+        head_fit_refuse(who, features, E, N, H, K, l2))
+        return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const long long* y = reinterpret_cast<const long long*>(labels);
-    const DistillTargets targets = soft ? *soft : DistillTargets{};
     const size_t n = (mlp ? mlp_head_fit_scratch_doubles(E, N, H, K) : head_fit_partial_bytes(E, N, H, K) / sizeof(double)) +
-                     (weights ? (size_t)E * N : 0);                                 // the row scales lie behind the unweighted scratch
+                     (q.o.weights ? (size_t)E * N : 0);                               // the row scales lie behind the unweighted scratch
     return debug_lossgrad(who, n, s, [&](double* scratch, int* err) {
-        if (mlp) launch_mlp_head_lossgrad(features, y, theta64, E, N, H, K, l2, scratch, err, loss, grad, s, targets, weights);
-        else launch_head_lossgrad(features, y, theta64, E, N, H, K, l2, scratch, err, loss, grad, s, targets, weights);
-    }, kBadLabel, K);
+        if (mlp) launch_mlp_head_lossgrad(features, q.o, theta64, E, N, H, K, l2, scratch, err, loss, grad, s);
+        else launch_head_lossgrad(features, q.o, theta64, E, N, H, K, l2, scratch, err, loss, grad, s);
+    }, q.by, K);
 }
+
+// the workspace queries' answer to arguments no fit accepts
+static bool no_workspace(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history) { return E < 1 || N < 1 || H < 1 || K < 1 || history < 1; }
 
 extern "C" {
 
 // ---- exit heads from CLS rows (head_fit.hip) ---------------------------------------------------------------------------------------------
 size_t ee_head_fit_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history) {
-    if (E < 1 || N < 1 || H < 1 || K < 1 || history < 1) return 0;
-    return head_fit_workspace_bytes(E, N, H, K, history);
+    return no_workspace(E, N, H, K, history) ? 0 : head_fit_workspace_bytes(E, N, H, K, history, false);
 }
 
 int ee_head_fit(const float* features, const int64_t* labels, int32_t E, int32_t N, int32_t H, int32_t K, double l2, double gtol,
                 int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* weight, float* bias, double* weight64,
                 double* bias64, double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
-    return head_fit_call("ee_head_fit", features, labels, nullptr, nullptr, E, N, H, K, l2, gtol, max_evals, history, workspace, workspace_bytes, weight,
+    return head_fit_call("ee_head_fit", labelled(labels), features, E, N, H, K, l2, gtol, max_evals, history, workspace, workspace_bytes, weight,
                          bias, weight64, bias64, loss, grad_norm, evals, status, stream);
 }
 
@@ -193,70 +224,45 @@ int ee_head_fit_distill(const float* features, const float* teacher_logits, cons
                         double alpha, double temperature, double l2, double gtol, int32_t max_evals, int32_t history, void* workspace,
                         size_t workspace_bytes, float* weight, float* bias, double* weight64, double* bias64, double* loss, double* grad_norm,
                         int32_t* evals, int32_t* status, void* stream) {
-    const DistillTargets soft{teacher_logits, alpha, temperature};
-    return head_fit_call("ee_head_fit_distill", features, labels, &soft, nullptr, E, N, H, K, l2, gtol, max_evals, history, workspace, workspace_bytes,
-                         weight, bias, weight64, bias64, loss, grad_norm, evals, status, stream);
+    return head_fit_call("ee_head_fit_distill", distilled(labels, teacher_logits, alpha, temperature), features, E, N, H, K, l2, gtol, max_evals,
+                         history, workspace, workspace_bytes, weight, bias, weight64, bias64, loss, grad_norm, evals, status, stream);
 }
 
 int ee_debug_head_lossgrad(const float* features, const int64_t* labels, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K,
                            double l2, double* loss, double* grad, void* stream) {
-    return head_lossgrad_call("ee_debug_head_lossgrad", false, features, labels, nullptr, nullptr, theta64, E, N, H, K, l2, loss, grad, stream);
+    return head_lossgrad_call("ee_debug_head_lossgrad", false, labelled(labels), features, theta64, E, N, H, K, l2, loss, grad, stream);
 }
 
 int ee_debug_head_distill_lossgrad(const float* features, const float* teacher_logits, const int64_t* labels, const double* theta64, int32_t E,
                                    int32_t N, int32_t H, int32_t K, double alpha, double temperature, double l2, double* loss, double* grad,
                                    void* stream) {
-    const DistillTargets soft{teacher_logits, alpha, temperature};
-    return head_lossgrad_call("ee_debug_head_distill_lossgrad", false, features, labels, &soft, nullptr, theta64, E, N, H, K, l2, loss, grad, stream);
+    return head_lossgrad_call("ee_debug_head_distill_lossgrad", false, distilled(labels, teacher_logits, alpha, temperature), features, theta64, E, N,
+                              H, K, l2, loss, grad, stream);
 }
 
 // ---- 2-way gate heads from CLS rows: the gate objective (include/mmee.h) on the labelled fit's kernels at K = 2 ---------------------------------
-static const char* const kBadGateTarget = "%s: a target is not finite or lies outside [0, 1]%s";
-
 int ee_head_fit_gate(const float* features, const double* targets, int32_t E, int32_t N, int32_t H, double l2, double gtol, int32_t max_evals,
                      int32_t history, void* workspace, size_t workspace_bytes, float* weight, float* bias, double* weight64, double* bias64,
                      double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
-    const char* who = "ee_head_fit_gate";
-    if (!features || !targets || !workspace || !weight || !bias)
-        return fail(nullptr, "%s: NULL argument (features, targets, workspace, weight and bias are required)", who);
-    if (head_fit_refuse(who, features, E, N, H, 2, l2)) return 1;
-    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return head_fit_workspace_bytes(E, N, H, 2, history); })) return 1;
-    if (!have_device(who)) return 1;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    HeadFitArgs a{{features, E, N, H, l2, gtol, max_evals, history, workspace, nullptr, nullptr, loss, grad_norm, evals, status},
-                  nullptr, 2, weight, bias, weight64, bias64, DistillTargets{}, nullptr};
-    a.gate_targets = targets;
-    if (!launch_head_fit(a, s)) return fail(nullptr, "%s: preparing the workspace (memset, copy of theta0) failed", who);
-    if (launch_status(nullptr, who)) return 1;
-    int err = 0;
-    if (hipMemcpyAsync(&err, workspace, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return fail(nullptr, "%s: reading the error word failed: %s", who, hipGetErrorString(hipGetLastError()));
-    if (err & 1) return fail(nullptr, kBadGateTarget, who, "; no output was written");
-    return 0;
+    return head_fit_call("ee_head_fit_gate", gate(targets), features, E, N, H, 2, l2, gtol, max_evals, history, workspace, workspace_bytes, weight,
+                         bias, weight64, bias64, loss, grad_norm, evals, status, stream);
 }
 
 int ee_debug_head_gate_lossgrad(const float* features, const double* targets, const double* theta64, int32_t E, int32_t N, int32_t H, double l2,
                                 double* loss, double* grad, void* stream) {
-    const char* who = "ee_debug_head_gate_lossgrad";
-    if (!features || !targets || !theta64 || !loss || !grad) return fail(nullptr, "%s: NULL argument", who);
-    if (head_fit_refuse(who, features, E, N, H, 2, l2)) return 1;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return debug_lossgrad(who, head_fit_partial_bytes(E, N, H, 2) / sizeof(double), s, [&](double* scratch, int* err) {
-        launch_head_lossgrad(features, nullptr, theta64, E, N, H, 2, l2, scratch, err, loss, grad, s, DistillTargets{}, nullptr, targets);
-    }, "%s: a target is not finite or lies outside [0, 1] (K = %d)", 2);
+    return head_lossgrad_call("ee_debug_head_gate_lossgrad", false, gate(targets), features, theta64, E, N, H, 2, l2, loss, grad, stream);
 }
 
 // ---- two-layer exit heads from CLS rows (mlp_head_fit.hip) -------------------------------------------------------------------------------
 size_t ee_mlp_head_fit_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history) {
-    if (E < 1 || N < 1 || H < 1 || K < 1 || history < 1) return 0;
-    return mlp_head_fit_workspace_bytes(E, N, H, K, history);
+    return no_workspace(E, N, H, K, history) ? 0 : mlp_head_fit_workspace_bytes(E, N, H, K, history, false);
 }
 
 int ee_mlp_head_fit(const float* features, const int64_t* labels, const double* theta0, int32_t E, int32_t N, int32_t H, int32_t K, double l2,
                     double gtol, int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* dense_weight,
                     float* dense_bias, float* weight, float* bias, double* theta64, double* loss, double* grad_norm, int32_t* evals,
                     int32_t* status, void* stream) {
-    return mlp_head_fit_call("ee_mlp_head_fit", features, labels, nullptr, nullptr, theta0, E, N, H, K, l2, gtol, max_evals, history, workspace,
+    return mlp_head_fit_call("ee_mlp_head_fit", labelled(labels), features, theta0, E, N, H, K, l2, gtol, max_evals, history, workspace,
                              workspace_bytes, dense_weight, dense_bias, weight, bias, theta64, loss, grad_norm, evals, status, stream);
 }
 
@@ -264,52 +270,45 @@ int ee_mlp_head_fit_distill(const float* features, const float* teacher_logits, 
                             int32_t H, int32_t K, double alpha, double temperature, double l2, double gtol, int32_t max_evals, int32_t history,
                             void* workspace, size_t workspace_bytes, float* dense_weight, float* dense_bias, float* weight, float* bias,
                             double* theta64, double* loss, double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
-    const DistillTargets soft{teacher_logits, alpha, temperature};
-    return mlp_head_fit_call("ee_mlp_head_fit_distill", features, labels, &soft, nullptr, theta0, E, N, H, K, l2, gtol, max_evals, history, workspace,
-                             workspace_bytes, dense_weight, dense_bias, weight, bias, theta64, loss, grad_norm, evals, status, stream);
+    return mlp_head_fit_call("ee_mlp_head_fit_distill", distilled(labels, teacher_logits, alpha, temperature), features, theta0, E, N, H, K, l2, gtol,
+                             max_evals, history, workspace, workspace_bytes, dense_weight, dense_bias, weight, bias, theta64, loss, grad_norm, evals,
+                             status, stream);
 }
 
 int ee_debug_mlp_head_lossgrad(const float* features, const int64_t* labels, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K,
                                double l2, double* loss, double* grad, void* stream) {
-    return head_lossgrad_call("ee_debug_mlp_head_lossgrad", true, features, labels, nullptr, nullptr, theta64, E, N, H, K, l2, loss, grad, stream);
+    return head_lossgrad_call("ee_debug_mlp_head_lossgrad", true, labelled(labels), features, theta64, E, N, H, K, l2, loss, grad, stream);
 }
 
 int ee_debug_mlp_head_distill_lossgrad(const float* features, const float* teacher_logits, const int64_t* labels, const double* theta64, int32_t E,
                                        int32_t N, int32_t H, int32_t K, double alpha, double temperature, double l2, double* loss, double* grad,
                                        void* stream) {
-    const DistillTargets soft{teacher_logits, alpha, temperature};
-    return head_lossgrad_call("ee_debug_mlp_head_distill_lossgrad", true, features, labels, &soft, nullptr, theta64, E, N, H, K, l2, loss, grad, stream);
+    return head_lossgrad_call("ee_debug_mlp_head_distill_lossgrad", true, distilled(labels, teacher_logits, alpha, temperature), features, theta64, E,
+                              N, H, K, l2, loss, grad, stream);
 }
 
 // ---- the head fits with sample weights: weights (E,N); teacher_logits NULL selects the labelled objective ------------------------------------
 size_t ee_head_fit_weighted_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history) {
-    if (E < 1 || N < 1 || H < 1 || K < 1 || history < 1) return 0;
-    return head_fit_workspace_bytes(E, N, H, K, history, true);
+    return no_workspace(E, N, H, K, history) ? 0 : head_fit_workspace_bytes(E, N, H, K, history, true);
 }
 
 int ee_head_fit_weighted(const float* features, const int64_t* labels, const float* teacher_logits, const float* weights, int32_t E, int32_t N,
                          int32_t H, int32_t K, double alpha, double temperature, double l2, double gtol, int32_t max_evals, int32_t history,
                          void* workspace, size_t workspace_bytes, float* weight, float* bias, double* weight64, double* bias64, double* loss,
                          double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
-    const char* who = "ee_head_fit_weighted";
-    const DistillTargets soft{teacher_logits, alpha, temperature};
-    if (weighted_refuse(who, weights, soft)) return 1;
-    return head_fit_call(who, features, labels, teacher_logits ? &soft : nullptr, weights, E, N, H, K, l2, gtol, max_evals, history, workspace,
-                         workspace_bytes, weight, bias, weight64, bias64, loss, grad_norm, evals, status, stream);
+    return head_fit_call("ee_head_fit_weighted", weighted(labels, teacher_logits, alpha, temperature, weights), features, E, N, H, K, l2, gtol,
+                         max_evals, history, workspace, workspace_bytes, weight, bias, weight64, bias64, loss, grad_norm, evals, status, stream);
 }
 
 int ee_debug_head_weighted_lossgrad(const float* features, const int64_t* labels, const float* teacher_logits, const float* weights,
                                     const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K, double alpha, double temperature, double l2,
                                     double* loss, double* grad, void* stream) {
-    const char* who = "ee_debug_head_weighted_lossgrad";
-    const DistillTargets soft{teacher_logits, alpha, temperature};
-    if (weighted_refuse(who, weights, soft)) return 1;
-    return head_lossgrad_call(who, false, features, labels, teacher_logits ? &soft : nullptr, weights, theta64, E, N, H, K, l2, loss, grad, stream);
+    return head_lossgrad_call("ee_debug_head_weighted_lossgrad", false, weighted(labels, teacher_logits, alpha, temperature, weights), features,
+                              theta64, E, N, H, K, l2, loss, grad, stream);
 }
 
 size_t ee_mlp_head_fit_weighted_workspace_bytes(int32_t E, int32_t N, int32_t H, int32_t K, int32_t history) {
-    if (E < 1 || N < 1 || H < 1 || K < 1 || history < 1) return 0;
-    return mlp_head_fit_workspace_bytes(E, N, H, K, history, true);
+    return no_workspace(E, N, H, K, history) ? 0 : mlp_head_fit_workspace_bytes(E, N, H, K, history, true);
 }
 
 int ee_mlp_head_fit_weighted(const float* features, const int64_t* labels, const float* teacher_logits, const float* weights, const double* theta0,
@@ -317,20 +316,16 @@ int ee_mlp_head_fit_weighted(const float* features, const int64_t* labels, const
                              int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* dense_weight, float* dense_bias,
                              float* weight, float* bias, double* theta64, double* loss, double* grad_norm, int32_t* evals, int32_t* status,
                              void* stream) {
-    const char* who = "ee_mlp_head_fit_weighted";
-    const DistillTargets soft{teacher_logits, alpha, temperature};
-    if (weighted_refuse(who, weights, soft)) return 1;
-    return mlp_head_fit_call(who, features, labels, teacher_logits ? &soft : nullptr, weights, theta0, E, N, H, K, l2, gtol, max_evals, history,
-                             workspace, workspace_bytes, dense_weight, dense_bias, weight, bias, theta64, loss, grad_norm, evals, status, stream);
+    return mlp_head_fit_call("ee_mlp_head_fit_weighted", weighted(labels, teacher_logits, alpha, temperature, weights), features, theta0, E, N, H, K,
+                             l2, gtol, max_evals, history, workspace, workspace_bytes, dense_weight, dense_bias, weight, bias, theta64, loss,
+                             grad_norm, evals, status, stream);
 }
 
 int ee_debug_mlp_head_weighted_lossgrad(const float* features, const int64_t* labels, const float* teacher_logits, const float* weights,
                                         const double* theta64, int32_t E, int32_t N, int32_t H, int32_t K, double alpha, double temperature,
                                         double l2, double* loss, double* grad, void* stream) {
-    const char* who = "ee_debug_mlp_head_weighted_lossgrad";
-    const DistillTargets soft{teacher_logits, alpha, temperature};
-    if (weighted_refuse(who, weights, soft)) return 1;
-    return head_lossgrad_call(who, true, features, labels, teacher_logits ? &soft : nullptr, weights, theta64, E, N, H, K, l2, loss, grad, stream);
+    return head_lossgrad_call("ee_debug_mlp_head_weighted_lossgrad", true, weighted(labels, teacher_logits, alpha, temperature, weights), features,
+                              theta64, E, N, H, K, l2, loss, grad, stream);
 }
 
 // ---- the LTE classifier from CLS rows (lte_fit.hip) --------------------------------------------------------------------------------------
@@ -351,7 +346,7 @@ int ee_lte_fit(const float* features, const double* targets, const double* theta
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const LteFitArgs a{{features, E, N, H, l2, gtol, max_evals, history, workspace, theta0, theta64, loss_out, grad_norm, evals, status},
                        targets, loss, weight, bias};
-    return finish_call(who, launch_lte_fit(a, s), workspace, s, "%s: a target is outside [0, 1] or NaN; no output was written", 0);
+    return finish_call(who, launch_lte_fit(a, s), workspace, s, Objective::kLte, 0);
 }
 
 int ee_debug_lte_lossgrad(const float* features, const double* targets, const double* theta64, int32_t E, int32_t N, int32_t H, int32_t loss,
@@ -362,7 +357,7 @@ int ee_debug_lte_lossgrad(const float* features, const double* targets, const do
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     return debug_lossgrad(who, lte_fit_partial_doubles(E, N, H), s, [&](double* partial, int* err) {
         launch_lte_lossgrad(features, targets, theta64, E, N, H, loss, l2, partial, err, loss_out, grad, s);
-    }, "%s: a target is outside [0, 1] or NaN", 0);
+    }, Objective::kLte, 0);
 }
 
 int ee_lte_targets(const float* logits, const int64_t* labels, int32_t E, int32_t N, int32_t K, double* targets, void* stream) {
@@ -375,8 +370,7 @@ int ee_lte_targets(const float* logits, const int64_t* labels, int32_t E, int32_
     int* err_dev = nullptr;
     if (!sc.get(&err_dev, 1)) return fail(nullptr, "%s: hipMalloc of the error word failed", who);
     launch_lte_targets(logits, reinterpret_cast<const long long*>(labels), E, N, K, targets, err_dev, s);
-    return finish_call(who, true, err_dev, s,
-                       "%s: a label is outside [0, K = %d) or a logit is NaN (a row its document never reached); nothing was written", K);
+    return finish_call(who, true, err_dev, s, Objective::kLteTargets, K);
 }
 
 int ee_lte_scores(const float* features, const float* weight, const float* bias, int32_t E, int32_t N, int32_t H, double* scores, void* stream) {

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(kThreads) void head_fit_finish_kernel(FitFinishArgs
 }  // namespace
 
 bool run_lbfgs_fit(const FitArgs& f, const FitLayout& lay, const std::function<void(const FitEvalPoint&)>& eval,
-                   std::initializer_list<FitOutSeg> segs, hipStream_t s, const std::function<void(const FitEvalPoint&)>& prepare) {
+                   std::initializer_list<FitOutSeg> segs, hipStream_t s, const float* weights, size_t scratch_bytes) {
     char* ws = static_cast<char*>(f.workspace);
     if (hipMemsetAsync(ws, 0, lay.zero_bytes, s) != hipSuccess) return false;           // theta = 0, no history, every exit running
     double* vec = reinterpret_cast<double*>(ws + lay.o_vec);
@@ -183,7 +183,7 @@ bool run_lbfgs_fit(const FitArgs& f, const FitLayout& lay, const std::function<v
     const FitEvalPoint p{vec + V_TRIAL * P, lay.vec_stride, reinterpret_cast<const int*>(ws + lay.o_ctrl), reinterpret_cast<int*>(ws),
                          reinterpret_cast<double*>(ws + lay.o_ftrial), vec + V_GTRIAL * P, lay.vec_stride, ws + lay.o_tail};
     const CtrlArgs c{ws, lay, f.gtol, f.max_evals};
-    if (prepare) prepare(p);
+    if (weights) launch_row_scale(weights, f.E, f.N, scale_table(p.tail, scratch_bytes), p.err, s);
     for (int tick = 0; tick < f.max_evals; ++tick) {
         eval(p);
         hipLaunchKernelGGL(head_fit_controller_kernel, dim3(lay.E), dim3(kCtrlThreads), 0, s, c);

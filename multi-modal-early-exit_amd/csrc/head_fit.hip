@@ -15,8 +15,9 @@
 // ee_head_fit_gate (2-way gate heads, K = 2) is one more argument struct of the same kernel: its row step is the two binary cross-entropies of
 // the gate objective against a target in [0, 1] per (exit, row) (gate_row_step), everything else -- slabs, logits pass, gradient pass, partials,
 // reduce, driver, workspace -- is the labelled fit's at K = 2.
-// This file is the objective; the L-BFGS around it is run_lbfgs_fit (fit_lbfgs.hip), the workspace layout and the control words are in
-// head_fit_common.h.
+// Which of the five argument structs a call launches is read off its HeadObjective (mmee_kernels.h) in one place, launch_eval.
+// This file is the objective; the L-BFGS around it is run_lbfgs_fit (fit_lbfgs.hip), which also makes the weighted fits' row-scale table in
+// front of the first tick; the workspace layout, the control words and the table's place (scale_table) are in head_fit_common.h.
 //
 // Arithmetic form: plain float64 FMAs.  The matrix form (v_mfma_f64_16x16x4_f64) was NOT built, so not measured against it.  Measured for this
 // form (profiles/head_fit.txt): 446 GB/s on the feature bytes at N = 40 000, H = 768, K = 16, E = 6 -- latency-bound, not bandwidth-bound; DESIGN.md
@@ -372,7 +373,6 @@ __global__ __launch_bounds__(kFitCtrlThreads) void head_fit_row_scale_kernel(con
 FitLayout one_layer_layout(int E, int N, int H, int K, int M, bool weighted) {
     return FitLayout(E, K * H + K, M, head_fit_partial_bytes(E, N, H, K) + (weighted ? sizeof(double) * (size_t)E * N : 0));
 }
-double* scale_table(void* tail, int E, int N, int H, int K) { return reinterpret_cast<double*>(static_cast<char*>(tail) + head_fit_partial_bytes(E, N, H, K)); }
 
 size_t lossgrad_lds_bytes(int H, int K) {
     return sizeof(float) * S * (size_t)(H + 4) + sizeof(double) * S * (size_t)round_up(K, 16) + sizeof(double) * 4 * S * kLogitTile;
@@ -401,22 +401,22 @@ void launch_lossgrad(const Args& a, int E, hipStream_t s) {
     else launch_lossgrad_k<16>(a, E, s);
 }
 
-// one evaluation: the partials of every running exit, then their fixed-order sums; soft.teacher null: the hard-label objective; weighted: the
-// row scales lie behind the partials in p.tail; gate_targets given (K == 2, y null, no teacher, no weights): the gate objective
-void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, const DistillTargets& soft, bool weighted, int E, int N, int H, int K,
-                 double l2, hipStream_t s, const double* gate_targets = nullptr) {
+// one evaluation: the partials of every running exit, then their fixed-order sums.  What o holds picks the kernel's argument struct: gate
+// targets (K == 2) the gate objective, a teacher the distilled one, weights the weighted form of either, whose row scales lie behind the
+// partials in p.tail
+void launch_eval(const FitEvalPoint& p, const float* X, const HeadObjective& o, int E, int N, int H, int K, double l2, hipStream_t s) {
     LossGradArgs a{};
-    a.X = X; a.y = y; a.theta = p.theta; a.theta_stride = p.theta_stride; a.ctrl = p.ctrl; a.err = p.err;
+    a.X = X; a.y = o.labels; a.theta = p.theta; a.theta_stride = p.theta_stride; a.ctrl = p.ctrl; a.err = p.err;
     a.partial = static_cast<double*>(p.tail); a.N = N; a.H = H; a.K = K;
     const int n_slabs = (a.N + S - 1) / S;
     a.chunks = head_fit_chunks(a.N);
     a.slabs_per_chunk = (n_slabs + a.chunks - 1) / a.chunks;
-    const DistillLossGradArgs d{a, soft.teacher, soft.alpha, soft.temperature};
-    const double* scale = weighted ? scale_table(p.tail, E, N, H, K) : nullptr;
-    if (gate_targets) launch_lossgrad(GateLossGradArgs{a, gate_targets}, E, s);
-    else if (scale && soft.teacher) launch_lossgrad(WeightedDistillLossGradArgs{d, scale}, E, s);
+    const DistillLossGradArgs d{a, o.soft.teacher, o.soft.alpha, o.soft.temperature};
+    const double* scale = o.weights ? scale_table(p.tail, head_fit_partial_bytes(E, N, H, K)) : nullptr;
+    if (o.gate_targets) launch_lossgrad(GateLossGradArgs{a, o.gate_targets}, E, s);
+    else if (scale && d.teacher) launch_lossgrad(WeightedDistillLossGradArgs{d, scale}, E, s);
     else if (scale) launch_lossgrad(WeightedLossGradArgs{a, scale}, E, s);
-    else if (soft.teacher) launch_lossgrad(d, E, s);
+    else if (d.teacher) launch_lossgrad(d, E, s);
     else launch_lossgrad(a, E, s);
     ReduceArgs r{};
     r.partial = a.partial; r.theta = a.theta; r.theta_stride = a.theta_stride; r.ctrl = a.ctrl; r.loss = p.loss; r.loss_stride = 1;
@@ -444,22 +444,19 @@ void launch_row_scale(const float* weights, int E, int N, double* scale, int* er
     hipLaunchKernelGGL(head_fit_row_scale_kernel, dim3(E), dim3(kFitCtrlThreads), 0, s, weights, N, scale, err);
 }
 
-void launch_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* partial, int* err,
-                          double* loss, double* grad, hipStream_t s, const DistillTargets& soft, const float* weights, const double* gate_targets) {
+void launch_head_lossgrad(const float* X, const HeadObjective& o, const double* theta, int E, int N, int H, int K, double l2, double* partial,
+                          int* err, double* loss, double* grad, hipStream_t s) {
     const size_t P = (size_t)K * H + K;
-    if (weights) launch_row_scale(weights, E, N, scale_table(partial, E, N, H, K), err, s);
-    launch_eval({theta, P, nullptr, err, loss, grad, P, partial}, X, y, soft, weights != nullptr, E, N, H, K, l2, s, gate_targets);
+    if (o.weights) launch_row_scale(o.weights, E, N, scale_table(partial, head_fit_partial_bytes(E, N, H, K)), err, s);
+    launch_eval({theta, P, nullptr, err, loss, grad, P, partial}, X, o, E, N, H, K, l2, s);
 }
 
 bool launch_head_fit(const HeadFitArgs& f, hipStream_t s) {
     const int KH = f.K * f.H;
-    const bool weighted = f.weights != nullptr;
-    return run_lbfgs_fit(f, one_layer_layout(f.E, f.N, f.H, f.K, f.history, weighted),
-                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.labels, f.soft, weighted, f.E, f.N, f.H, f.K, f.l2, s, f.gate_targets); },
-                         {{0, KH, f.weight, f.weight64}, {KH, f.K, f.bias, f.bias64}}, s,
-                         weighted ? std::function<void(const FitEvalPoint&)>([&](const FitEvalPoint& p) {
-                             launch_row_scale(f.weights, f.E, f.N, scale_table(p.tail, f.E, f.N, f.H, f.K), p.err, s);
-                         }) : nullptr);
+    const HeadObjective& o = f.objective;
+    return run_lbfgs_fit(f, one_layer_layout(f.E, f.N, f.H, f.K, f.history, o.weights != nullptr),
+                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, o, f.E, f.N, f.H, f.K, f.l2, s); },
+                         {{0, KH, f.weight, f.weight64}, {KH, f.K, f.bias, f.bias64}}, s, o.weights, head_fit_partial_bytes(f.E, f.N, f.H, f.K));
 }
 
 }  // namespace mmee

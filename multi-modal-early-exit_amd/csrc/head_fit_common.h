@@ -122,6 +122,10 @@ __device__ inline double distill_row(double (&v)[kRowSlots], const float (&tv)[k
 // not defended against.
 void launch_row_scale(const float* weights, int E, int N, double* scale, int* err, hipStream_t s);
 
+// The table lies behind the objective's own scratch (the one-layer fit's chunk partials, the two-layer fit's rows): `scratch_bytes` into the
+// tail of a fit's workspace, or into a debug call's buffer
+inline double* scale_table(void* tail, size_t scratch_bytes) { return reinterpret_cast<double*>(static_cast<char*>(tail) + scratch_bytes); }
+
 // scale[e][n] of a row, zero for a row that does not exist
 __device__ inline double row_scale(const double* scale, int e, int N, long long n) { return n < N ? scale[(size_t)e * N + n] : 0.0; }
 
@@ -182,9 +186,10 @@ struct FitFinishArgs {
 };
 
 // The whole fit on stream s: the workspace zeroed, f.theta0 ((lay.E, lay.P), null = 0) as the first trial point, f.max_evals ticks of
-// { eval(trial point); controller }, then theta[seg] of every exit to the segments' outputs and f's result pointers.  prepare, when given,
-// runs once on the zeroed workspace in front of the first tick (the weighted fits' row-scale table).  false: preparing the workspace failed.
+// { eval(trial point); controller }, then theta[seg] of every exit to the segments' outputs and f's result pointers.  weights, when not null (the
+// weighted head fits' (E,N) table): launch_row_scale once on the zeroed workspace in front of the first tick, to scale_table(tail,
+// scratch_bytes), where the objective's own scratch ends.  false: preparing the workspace failed.
 bool run_lbfgs_fit(const FitArgs& f, const FitLayout& lay, const std::function<void(const FitEvalPoint&)>& eval,
-                   std::initializer_list<FitOutSeg> segs, hipStream_t s, const std::function<void(const FitEvalPoint&)>& prepare = nullptr);
+                   std::initializer_list<FitOutSeg> segs, hipStream_t s, const float* weights, size_t scratch_bytes);
 
 }  // namespace mmee

@@ -309,7 +309,7 @@ void launch_lte_lossgrad(const float* X, const double* T, const double* theta, i
 bool launch_lte_fit(const LteFitArgs& f, hipStream_t s) {
     return run_lbfgs_fit(f, lte_layout(f.E, f.N, f.H, f.history),
                          [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.targets, f.E, f.N, f.H, f.loss_kind, f.l2, s); },
-                         {{0, f.H, f.weight, nullptr}, {f.H, 1, f.bias, nullptr}}, s);
+                         {{0, f.H, f.weight, nullptr}, {f.H, 1, f.bias, nullptr}}, s, nullptr, 0);
 }
 
 void launch_lte_targets(const float* logits, const long long* y, int E, int N, int K, double* targets, int* err, hipStream_t s) {

@@ -13,7 +13,8 @@
 // ee_mlp_head_fit_weighted: the two softmax kernels are templates over their argument struct, and the weighted structs select (if constexpr)
 // the row step that multiplies D and the row's loss by scale[e][n] = w[e][n] N / W_e (launch_row_scale, head_fit_common.h, once per call) and
 // skips a row whose scale is zero.  The other six launches are shared, division by N included; the unweighted instantiations are the code
-// they were.
+// they were.  launch_eval reads which of the four a call launches off its HeadObjective (mmee_kernels.h); run_lbfgs_fit makes the table, behind
+// this file's scratch (scale_table, head_fit_common.h).
 //
 // Both GEMM kernels are LDS-tiled with BOTH operands staged (64 x 64 output tile, 16 deep, the next tile's global loads in flight behind the
 // products) and multiply with v_mfma_f64_16x16x4_f64: four waves of 32 x 32, four accumulators each.  Its C/D map is NOT the f32 one: lane l,
@@ -426,13 +427,15 @@ __global__ __launch_bounds__(kFitCtrlThreads) void mlp_loss_kernel(EvalArgs a) {
 }
 
 int ceil_div(int v, int d) { return (v + d - 1) / d; }
+size_t params(int H, int K) { return (size_t)H * H + H + (size_t)K * H + K; }
+size_t scratch_bytes(int E, int N, int H, int K) { return sizeof(double) * mlp_head_fit_scratch_doubles(E, N, H, K); }
 
 // one evaluation: L and grad L of every running exit; p.tail: mlp_head_fit_scratch_doubles doubles -- hidden rows, logits, the rows' losses;
-// soft.teacher null: the hard-label objective; weighted: the row scales (E,N) lie behind the rows' losses
-void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, const DistillTargets& soft, bool weighted, int E, int N, int H, int K,
-                 double l2, hipStream_t s) {
+// what o holds picks the softmax kernel and its argument struct: a teacher the distilled objective, weights the weighted form of either,
+// whose row scales (E,N) lie behind the rows' losses
+void launch_eval(const FitEvalPoint& p, const float* X, const HeadObjective& o, int E, int N, int H, int K, double l2, hipStream_t s) {
     EvalArgs a{};
-    a.X = X; a.y = y; a.theta = p.theta; a.theta_stride = p.theta_stride; a.ctrl = p.ctrl; a.err = p.err;
+    a.X = X; a.y = o.labels; a.theta = p.theta; a.theta_stride = p.theta_stride; a.ctrl = p.ctrl; a.err = p.err;
     a.A = static_cast<double*>(p.tail); a.Z = a.A + (size_t)E * N * H; a.rowloss = a.Z + (size_t)E * N * K;
     a.loss = p.loss; a.loss_stride = 1; a.grad = p.grad; a.grad_stride = p.grad_stride; a.N = N; a.H = H; a.K = K; a.l2 = l2;
     const size_t HH = (size_t)H * H, oW1 = 0, ob1 = HH, oW2 = HH + H, ob2 = HH + H + (size_t)K * H;
@@ -441,12 +444,12 @@ void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, cons
     NtArgs out{a.A, (size_t)N * H, a.theta, a.theta_stride, oW2, ob2, a.Z, (size_t)N * K, a.ctrl, N, K, H};
     hipLaunchKernelGGL((mlp_nt_gemm_kernel<double, false>), dim3(ceil_div(N, TM), ceil_div(K, TN), E), dim3(kThreads), 0, s, out);
     const dim3 sgrid(ceil_div(N, kSoftRows), E);
-    const DistillEvalArgs d{a, soft.teacher, soft.alpha, soft.temperature};
-    const double* scale = weighted ? a.rowloss + (size_t)E * N : nullptr;
-    if (scale && soft.teacher)
+    const DistillEvalArgs d{a, o.soft.teacher, o.soft.alpha, o.soft.temperature};
+    const double* scale = o.weights ? scale_table(p.tail, scratch_bytes(E, N, H, K)) : nullptr;
+    if (scale && d.teacher)
         hipLaunchKernelGGL(mlp_distill_softmax_kernel<WeightedDistillEvalArgs>, sgrid, dim3(kThreads), 0, s, WeightedDistillEvalArgs{d, scale});
     else if (scale) hipLaunchKernelGGL(mlp_softmax_kernel<WeightedEvalArgs>, sgrid, dim3(kThreads), 0, s, WeightedEvalArgs{a, scale});
-    else if (soft.teacher) hipLaunchKernelGGL(mlp_distill_softmax_kernel<DistillEvalArgs>, sgrid, dim3(kThreads), 0, s, d);
+    else if (d.teacher) hipLaunchKernelGGL(mlp_distill_softmax_kernel<DistillEvalArgs>, sgrid, dim3(kThreads), 0, s, d);
     else hipLaunchKernelGGL(mlp_softmax_kernel<EvalArgs>, sgrid, dim3(kThreads), 0, s, a);
     TnArgs g2{a.Z, (size_t)N * K, a.A, (size_t)N * H, a.theta, a.theta_stride, a.grad, a.grad_stride, oW2, ob2, a.ctrl, N, K, H, a.l2};
     hipLaunchKernelGGL((mlp_tn_gemm_kernel<double>), dim3(ceil_div(K, TM), ceil_div(H, TN), E), dim3(kThreads), 0, s, g2);
@@ -462,13 +465,10 @@ void launch_eval(const FitEvalPoint& p, const float* X, const long long* y, cons
     hipLaunchKernelGGL(mlp_loss_kernel, dim3(E), dim3(kFitCtrlThreads), 0, s, a);
 }
 
-size_t params(int H, int K) { return (size_t)H * H + H + (size_t)K * H + K; }
-
 // the weighted fit's row scales (E,N) lie behind the unweighted scratch
 FitLayout mlp_layout(int E, int N, int H, int K, int M, bool weighted) {
-    return FitLayout(E, (int)params(H, K), M, sizeof(double) * (mlp_head_fit_scratch_doubles(E, N, H, K) + (weighted ? (size_t)E * N : 0)));
+    return FitLayout(E, (int)params(H, K), M, scratch_bytes(E, N, H, K) + (weighted ? sizeof(double) * (size_t)E * N : 0));
 }
-double* scale_table(void* tail, int E, int N, int H, int K) { return static_cast<double*>(tail) + mlp_head_fit_scratch_doubles(E, N, H, K); }
 
 }  // namespace
 
@@ -478,22 +478,19 @@ size_t mlp_head_fit_workspace_bytes(int E, int N, int H, int K, int history, boo
     return mlp_layout(E, N, H, K, history, weighted).bytes;
 }
 
-void launch_mlp_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* scratch,
-                              int* err, double* loss, double* grad, hipStream_t s, const DistillTargets& soft, const float* weights) {
-    if (weights) launch_row_scale(weights, E, N, scale_table(scratch, E, N, H, K), err, s);
-    launch_eval({theta, params(H, K), nullptr, err, loss, grad, params(H, K), scratch}, X, y, soft, weights != nullptr, E, N, H, K, l2, s);
+void launch_mlp_head_lossgrad(const float* X, const HeadObjective& o, const double* theta, int E, int N, int H, int K, double l2, double* scratch,
+                              int* err, double* loss, double* grad, hipStream_t s) {
+    if (o.weights) launch_row_scale(o.weights, E, N, scale_table(scratch, scratch_bytes(E, N, H, K)), err, s);
+    launch_eval({theta, params(H, K), nullptr, err, loss, grad, params(H, K), scratch}, X, o, E, N, H, K, l2, s);
 }
 
 bool launch_mlp_head_fit(const MlpHeadFitArgs& f, hipStream_t s) {
     const int H = f.H, K = f.K, HH = H * H;
-    const bool weighted = f.weights != nullptr;
-    return run_lbfgs_fit(f, mlp_layout(f.E, f.N, H, K, f.history, weighted),
-                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, f.labels, f.soft, weighted, f.E, f.N, H, K, f.l2, s); },
+    const HeadObjective& o = f.objective;
+    return run_lbfgs_fit(f, mlp_layout(f.E, f.N, H, K, f.history, o.weights != nullptr),
+                         [&](const FitEvalPoint& p) { launch_eval(p, f.features, o, f.E, f.N, H, K, f.l2, s); },
                          {{0, HH, f.dense_weight, nullptr}, {HH, H, f.dense_bias, nullptr}, {HH + H, K * H, f.weight, nullptr},
-                          {HH + H + K * H, K, f.bias, nullptr}}, s,
-                         weighted ? std::function<void(const FitEvalPoint&)>([&](const FitEvalPoint& p) {
-                             launch_row_scale(f.weights, f.E, f.N, scale_table(p.tail, f.E, f.N, H, K), p.err, s);
-                         }) : nullptr);
+                          {HH + H + K * H, K, f.bias, nullptr}}, s, o.weights, scratch_bytes(f.E, f.N, H, K));
 }
 
 }  // namespace mmee

@@ -341,18 +341,23 @@ struct DistillTargets {
     double alpha = 0.0;              // weight of the soft term; at 1 the labels are not looked at and may be null
     double temperature = 1.0;
 };
+// What a head is fitted against.  Host only: an entry point (capi_fit.hip) builds it once from its own arguments and it is handed down
+// unchanged to the launch that picks the kernel's argument struct.  Null or default means absent.
+struct HeadObjective {
+    const long long* labels = nullptr;       // (N,); null: the distilled objective at alpha = 1, the gate objective
+    DistillTargets soft;                     // teacher null: no soft term
+    const float* weights = nullptr;          // (E,N) sample weights (ee_*_fit_weighted), or null: every row counts once
+    const double* gate_targets = nullptr;    // (E,N) in [0,1] (ee_head_fit_gate: K == 2, one layer, nothing else given), or null
+};
 struct HeadFitArgs : FitArgs {       // E parameter sets; theta0 and theta64 null
-    const long long* labels;         // (N,)
+    HeadObjective objective;
     int K;
     float *weight, *bias;            // (E,K,H), (E,K)
     double *weight64, *bias64;       // the same in float64, or null
-    DistillTargets soft;
-    const float* weights = nullptr;  // (E,N) sample weights (ee_head_fit_weighted), or null: every row counts once
-    const double* gate_targets = nullptr;    // (E,N) in [0,1] (ee_head_fit_gate: K == 2, labels null, no teacher, no weights), or null
 };
 int head_fit_chunks(int N);
 // weighted: the fit carries sample weights, and its workspace the row-scale table (E,N) float64 behind the partials
-size_t head_fit_workspace_bytes(int E, int N, int H, int K, int history, bool weighted = false);
+size_t head_fit_workspace_bytes(int E, int N, int H, int K, int history, bool weighted);
 size_t head_fit_partial_bytes(int E, int N, int H, int K);
 // false: the memset of the workspace failed.  The error word is the first int of the workspace (bit 0: a label outside [0,K); bit 1: a
 // teacher logit that is not finite; bit 2: a sample weight that is negative or not finite; bit 3: an exit whose weights sum to zero; the gate
@@ -360,28 +365,24 @@ size_t head_fit_partial_bytes(int E, int N, int H, int K);
 bool launch_head_fit(const HeadFitArgs& a, hipStream_t s);
 // one evaluation at theta (E, K*H + K): loss (E,), grad (E, K*H + K); partial: head_fit_partial_bytes, with weights (E,N) E * N doubles
 // more behind them; err: one zeroed int
-void launch_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* partial, int* err,
-                          double* loss, double* grad, hipStream_t s, const DistillTargets& soft = {}, const float* weights = nullptr,
-                          const double* gate_targets = nullptr);
+void launch_head_lossgrad(const float* X, const HeadObjective& o, const double* theta, int E, int N, int H, int K, double l2, double* partial,
+                          int* err, double* loss, double* grad, hipStream_t s);
 // ee_mlp_head_fit (mlp_head_fit.hip): two-layer heads (dense + tanh + out_proj) per exit; theta = W1 (H,H), b1 (H,), W2 (K,H), b2 (K,)
 constexpr int kMlpHeadFitRows = 64;          // the row tile of the GEMM kernels, the largest of the new kernels' tiles (MMEE_MLP_HEAD_FIT_ROWS)
 struct MlpHeadFitArgs : FitArgs {    // E parameter sets; theta0 (E,P) required, theta64 (E,P)
-    const long long* labels;         // (N,)
+    HeadObjective objective;         // no gate targets: the gate heads have one layer
     int K;
     float *dense_weight, *dense_bias, *weight, *bias;   // (E,H,H), (E,H), (E,K,H), (E,K)
-    DistillTargets soft;
-    const float* weights = nullptr;  // (E,N) sample weights (ee_mlp_head_fit_weighted), or null: every row counts once
 };
-size_t mlp_head_fit_workspace_bytes(int E, int N, int H, int K, int history, bool weighted = false);
+size_t mlp_head_fit_workspace_bytes(int E, int N, int H, int K, int history, bool weighted);
 size_t mlp_head_fit_scratch_doubles(int E, int N, int H, int K);
 // false: preparing the workspace failed.  The error word is the first int of the workspace (bit 0: a label outside [0,K); bit 1: a teacher
 // logit that is not finite; bits 2 and 3: the sample weights, as for launch_head_fit).
 bool launch_mlp_head_fit(const MlpHeadFitArgs& a, hipStream_t s);
 // one evaluation at theta (E,P): loss (E,), grad (E,P); scratch: mlp_head_fit_scratch_doubles doubles, with weights (E,N) E * N doubles
 // more behind them; err: one zeroed int
-void launch_mlp_head_lossgrad(const float* X, const long long* y, const double* theta, int E, int N, int H, int K, double l2, double* scratch,
-                              int* err, double* loss, double* grad, hipStream_t s, const DistillTargets& soft = {},
-                              const float* weights = nullptr);
+void launch_mlp_head_lossgrad(const float* X, const HeadObjective& o, const double* theta, int E, int N, int H, int K, double l2, double* scratch,
+                              int* err, double* loss, double* grad, hipStream_t s);
 // ee_lte_fit (lte_fit.hip): the learning-to-exit classifier, one Linear(H, 1) for all encoder exits; theta = w (H,), b
 constexpr int kLteFitRows = 16;              // the rows a workgroup treats as a unit: four waves, four rows in flight each (MMEE_LTE_FIT_ROWS)
 constexpr int kLteFitMaxChunks = 128;        // row chunks (= partial gradients) per exit

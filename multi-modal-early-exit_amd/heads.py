@@ -100,6 +100,14 @@ def collect_exit_features(engine, batches: Iterable[Mapping], head_layers: int =
     return _cat_batches((rows,) for rows, _ in _dump_all(engine, batches))[0]
 
 
+def _encoder_rows_and_logits(engine, batches):
+    """-> (the CLS rows (E,N,H) leaving the encoder exit layers, those exits' policy logits (E,N,K) float32), embedding-level exits skipped"""
+    ec = engine.cfg.exit_config
+    n_emb, n_enc = len(ec.embedding_exits), len(ec.encoder_exit_layers)
+    return tuple(_cat_batches((rows, out.all_logits[n_emb:n_emb + n_enc].to(torch.float32))
+                              for rows, out in _dump_all(engine, batches, want_all=True)))
+
+
 def collect_distill_features(engine, batches: Iterable[Mapping], head_layers: int = 1):
     """``collect_exit_features`` for documents without labels.  Returns two device tensors from the same dump-all forwards: ``features``
     (E,N,H) float32 as above, and ``teacher_logits`` (N,K) float32, the final classifier's logits on the same documents (the last row of
@@ -126,20 +134,29 @@ class HeadFit:
 
     def logits(self, features) -> "torch.Tensor":
         """(E,N,K) float64 logits of the float32 heads on ``features`` (E,N,H), on the device."""
-        X = _rows(features, on=self.weight.device)[1].to(torch.float64)
-        return torch.baddbmm(self.bias.to(torch.float64).unsqueeze(1), X, self.weight.to(torch.float64).transpose(1, 2))
+        return _linear_logits(self, features)
 
     def state_dict(self, cfg: ModelConfig) -> Dict[str, np.ndarray]:
         """``{prefix}encoder.early_exits.{k}.out_proj.weight / .bias`` (host float32), ready for ``engine.load_weights`` next to the
         backbone's tensors."""
         _check_fittable(cfg)
-        E, p = _head_prefix(self, cfg)
-        w, b = self.weight.cpu().numpy(), self.bias.cpu().numpy()
-        out = {}
-        for k in range(E):
-            out[f"{p}encoder.early_exits.{k}.out_proj.weight"] = np.ascontiguousarray(w[k])
-            out[f"{p}encoder.early_exits.{k}.out_proj.bias"] = np.ascontiguousarray(b[k])
-        return out
+        return _out_proj_state(self, *_head_prefix(self, cfg))
+
+
+def _linear_logits(fit, features):
+    """(E,N,K) float64 logits of the float32 one-layer heads ``fit.weight`` (E,K,H), ``fit.bias`` (E,K) on ``features`` (E,N,H)"""
+    X = _rows(features, on=fit.weight.device)[1].to(torch.float64)
+    return torch.baddbmm(fit.bias.to(torch.float64).unsqueeze(1), X, fit.weight.to(torch.float64).transpose(1, 2))
+
+
+def _out_proj_state(fit, E, prefix):
+    """``{prefix}encoder.early_exits.{k}.out_proj.weight / .bias`` of the one-layer heads ``fit.weight``, ``fit.bias``, as host float32"""
+    w, b = fit.weight.cpu().numpy(), fit.bias.cpu().numpy()
+    out = {}
+    for k in range(E):
+        out[f"{prefix}encoder.early_exits.{k}.out_proj.weight"] = np.ascontiguousarray(w[k])
+        out[f"{prefix}encoder.early_exits.{k}.out_proj.bias"] = np.ascontiguousarray(b[k])
+    return out
 
 
 def _to_device(x, dtype, dev):
@@ -259,44 +276,58 @@ def fit_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-9, max_e
 
     Host synchronisation: the call waits for its stream once, after the last launch, to read the error word (a label outside [0,K) fails
     the call); with ``num_labels=None`` reading ``labels.max()`` is a second wait, before the first launch."""
+    return _fit_heads(features, labels, None, l2, gtol, max_evals, history, device, num_labels, sample_weight)
+
+
+def _new_head_fit(cls, dev, E, K, H, l2, *more):
+    """The outputs of a one-layer fit on ``dev`` as a ``cls`` (HeadFit, GateFit): zeros, status -1; more: the fields behind ``l2``."""
+    f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
+    return cls(torch.zeros((E, K, H), dtype=torch.float32, device=dev), torch.zeros((E, K), dtype=torch.float32, device=dev),
+               f64(E, K, H), f64(E, K), f64(E), f64(E), torch.zeros((E,), dtype=torch.int32, device=dev),
+               torch.full((E,), -1, dtype=torch.int32, device=dev), float(l2), *more)
+
+
+def _ramp_problem(features, labels, soft, num_labels, device, sample_weight):
+    """What the ramp fits are handed, on the device.  soft: None (the labelled objective), or (teacher_logits, alpha, temperature).  The
+    refusals from shapes and scalars alone come first, before anything touches the library or a device.
+    -> (dev, X (E,N,H) float32, y (N,) int64 or None, teacher (N,K) float32 or None, alpha, temperature, K)"""
+    if soft is not None:
+        K = _distill_check(features, soft[0], labels, soft[1], soft[2], num_labels)
     _weight_shape(features, sample_weight)
     capi.load()
     dev, X = _rows(features, device)
+    if soft is None:
+        y, K = _labels(labels, dev, X.shape[1], num_labels)
+        return dev, X, y, None, 0.0, 1.0, K
+    y = None if labels is None else _labels(labels, dev, X.shape[1], K)[0]
+    return dev, X, y, _to_device(soft[0], torch.float32, dev), soft[1], soft[2], K
+
+
+def _run_ramp_fit(stem, dev, X, y, teacher, alpha, temperature, sample_weight, start, K, l2, gtol, max_evals, history, outs):
+    """One call of the C fit of the family ``stem`` ("ee_head_fit", "ee_mlp_head_fit"): ``stem`` itself against labels, ``stem_distill`` with a
+    teacher, ``stem_weighted`` (either objective; teacher None: alpha 0) with a ``sample_weight``.  start: () or (theta0,); outs: the
+    entry point's output tensors, in its order."""
     E, N, H = X.shape
-    y, K = _labels(labels, dev, N, num_labels)
-    fit = _new_head_fit(dev, E, K, H, l2)
-    if sample_weight is None:
-        ws, need = _workspace("ee_head_fit_workspace_bytes", dev, E, N, H, K, history)
-        _call("ee_head_fit", dev, X, y, E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.weight, fit.bias,
-              fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status)
+    mix = (float(alpha), float(temperature))
+    if sample_weight is not None:
+        name, lead = f"{stem}_weighted", (X, y, teacher, _weights(sample_weight, dev, E, N))
+    elif teacher is not None:
+        name, lead = f"{stem}_distill", (X, teacher, y)
     else:
-        _weighted_head_fit(fit, dev, X, y, None, _weights(sample_weight, dev, E, N), K, 0.0, 1.0, l2, gtol, max_evals, history)
+        name, lead, mix = stem, (X, y), ()
+    query = f"{stem}_weighted_workspace_bytes" if sample_weight is not None else f"{stem}_workspace_bytes"
+    ws, need = _workspace(query, dev, E, N, H, K, history)
+    _call(name, dev, *lead, *start, E, N, H, K, *mix, float(l2), float(gtol), int(max_evals), int(history), ws, need, *outs)
+
+
+def _fit_heads(features, labels, soft, l2, gtol, max_evals, history, device, num_labels, sample_weight) -> HeadFit:
+    """The one-layer ramp fits' body; soft: as for _ramp_problem"""
+    dev, X, y, teacher, alpha, temperature, K = _ramp_problem(features, labels, soft, num_labels, device, sample_weight)
+    E, _, H = X.shape
+    fit = _new_head_fit(HeadFit, dev, E, K, H, l2, float(alpha), float(temperature))
+    _run_ramp_fit("ee_head_fit", dev, X, y, teacher, alpha, temperature, sample_weight, (), K, l2, gtol, max_evals, history,
+                  (fit.weight, fit.bias, fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status))
     return fit
-
-
-def _weighted_head_fit(fit, dev, X, y, teacher, w, K, alpha, temperature, l2, gtol, max_evals, history):
-    """ee_head_fit_weighted into ``fit``; teacher None: the labelled objective (alpha 0)"""
-    E, N, H = X.shape
-    ws, need = _workspace("ee_head_fit_weighted_workspace_bytes", dev, E, N, H, K, history)
-    _call("ee_head_fit_weighted", dev, X, y, teacher, w, E, N, H, K, float(alpha), float(temperature), float(l2), float(gtol), int(max_evals),
-          int(history), ws, need, fit.weight, fit.bias, fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status)
-
-
-def _weighted_mlp_head_fit(fit, dev, X, y, teacher, w, theta0, K, alpha, temperature, l2, gtol, max_evals, history):
-    """ee_mlp_head_fit_weighted into ``fit``; teacher None: the labelled objective (alpha 0)"""
-    E, N, H = X.shape
-    ws, need = _workspace("ee_mlp_head_fit_weighted_workspace_bytes", dev, E, N, H, K, history)
-    _call("ee_mlp_head_fit_weighted", dev, X, y, teacher, w, theta0, E, N, H, K, float(alpha), float(temperature), float(l2), float(gtol),
-          int(max_evals), int(history), ws, need, fit.dense_weight, fit.dense_bias, fit.weight, fit.bias, fit.theta64, fit.loss, fit.grad_norm,
-          fit.evals, fit.status)
-
-
-def _new_head_fit(dev, E, K, H, l2, alpha=0.0, temperature=1.0) -> HeadFit:
-    """The outputs of a one-layer fit on ``dev``: zeros, status -1."""
-    f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
-    return HeadFit(torch.zeros((E, K, H), dtype=torch.float32, device=dev), torch.zeros((E, K), dtype=torch.float32, device=dev),
-                   f64(E, K, H), f64(E, K), f64(E), f64(E), torch.zeros((E,), dtype=torch.int32, device=dev),
-                   torch.full((E,), -1, dtype=torch.int32, device=dev), float(l2), float(alpha), float(temperature))
 
 
 # ---- distillation from the final classifier: no labels needed ----------------------------------------------------------------------------
@@ -320,16 +351,6 @@ def _distill_check(features, teacher_logits, labels, alpha, temperature, num_lab
     return K
 
 
-def _distill_inputs(features, teacher_logits, labels, alpha, temperature, num_labels, device, sample_weight=None):
-    """-> (dev, X (E,N,H) float32, teacher (N,K) float32, y (N,) int64 or None, K), all on dev"""
-    K = _distill_check(features, teacher_logits, labels, alpha, temperature, num_labels)
-    _weight_shape(features, sample_weight)
-    capi.load()
-    dev, X = _rows(features, device)
-    y = None if labels is None else _labels(labels, dev, X.shape[1], K)[0]
-    return dev, X, _to_device(teacher_logits, torch.float32, dev), y, K
-
-
 def fit_distilled_exit_heads(features, teacher_logits, labels=None, alpha: float = 1.0, temperature: float = 1.0, l2: float = 1e-2,
                              gtol: float = 1e-9, max_evals: int = 2000, history: int = 8, device=None, num_labels: int = None,
                              sample_weight=None) -> HeadFit:
@@ -344,16 +365,7 @@ def fit_distilled_exit_heads(features, teacher_logits, labels=None, alpha: float
     does.  Budget, ``status`` and the one host wait after the last launch are ``fit_exit_heads``'; no wait is spent on ``labels.max()``.
     ``sample_weight`` is ``fit_exit_heads``': it weighs the whole mixed row loss, and neither the label nor the teacher row of a row of weight
     zero is looked at."""
-    dev, X, T, y, K = _distill_inputs(features, teacher_logits, labels, alpha, temperature, num_labels, device, sample_weight)
-    E, N, H = X.shape
-    fit = _new_head_fit(dev, E, K, H, l2, alpha, temperature)
-    if sample_weight is None:
-        ws, need = _workspace("ee_head_fit_workspace_bytes", dev, E, N, H, K, history)
-        _call("ee_head_fit_distill", dev, X, T, y, E, N, H, K, float(alpha), float(temperature), float(l2), float(gtol), int(max_evals),
-              int(history), ws, need, fit.weight, fit.bias, fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status)
-    else:
-        _weighted_head_fit(fit, dev, X, y, T, _weights(sample_weight, dev, E, N), K, alpha, temperature, l2, gtol, max_evals, history)
-    return fit
+    return _fit_heads(features, labels, (teacher_logits, alpha, temperature), l2, gtol, max_evals, history, device, num_labels, sample_weight)
 
 
 # ---- two-layer heads: dense + tanh + out_proj -----------------------------------------------------------------------------------------
@@ -440,28 +452,21 @@ def fit_mlp_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-6, m
     ``sample_weight`` is ``fit_exit_heads``' (``ee_mlp_head_fit_weighted``).
 
     Host synchronisation: as for ``fit_exit_heads``, one wait after the last launch (plus one for ``labels.max()`` without ``num_labels``)."""
-    _weight_shape(features, sample_weight)
-    capi.load()
-    dev, X = _rows(features, device)
-    E, N, H = X.shape
-    y, K = _labels(labels, dev, N, num_labels)
+    return _fit_mlp_heads(features, labels, None, l2, gtol, max_evals, history, init, device, num_labels, sample_weight)
+
+
+def _fit_mlp_heads(features, labels, soft, l2, gtol, max_evals, history, init, device, num_labels, sample_weight) -> MlpHeadFit:
+    """The two-layer ramp fits' body: _fit_heads' with a start and MlpHeadFit's outputs (zeros, status -1)"""
+    dev, X, y, teacher, alpha, temperature, K = _ramp_problem(features, labels, soft, num_labels, device, sample_weight)
+    E, _, H = X.shape
     theta0 = _mlp_theta0(init, E, H, K, dev)
-    fit = _new_mlp_head_fit(dev, E, K, H, l2)
-    if sample_weight is None:
-        ws, need = _workspace("ee_mlp_head_fit_workspace_bytes", dev, E, N, H, K, history)
-        _call("ee_mlp_head_fit", dev, X, y, theta0, E, N, H, K, float(l2), float(gtol), int(max_evals), int(history), ws, need,
-              fit.dense_weight, fit.dense_bias, fit.weight, fit.bias, fit.theta64, fit.loss, fit.grad_norm, fit.evals, fit.status)
-    else:
-        _weighted_mlp_head_fit(fit, dev, X, y, None, _weights(sample_weight, dev, E, N), theta0, K, 0.0, 1.0, l2, gtol, max_evals, history)
-    return fit
-
-
-def _new_mlp_head_fit(dev, E, K, H, l2, alpha=0.0, temperature=1.0) -> MlpHeadFit:
-    """The outputs of a two-layer fit on ``dev``: zeros, status -1."""
     z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-    return MlpHeadFit(z((E, H, H), torch.float32), z((E, H), torch.float32), z((E, K, H), torch.float32), z((E, K), torch.float32),
-                      z((E, mlp_param_count(H, K)), torch.float64), z((E,), torch.float64), z((E,), torch.float64), z((E,), torch.int32),
-                      torch.full((E,), -1, dtype=torch.int32, device=dev), float(l2), float(alpha), float(temperature))
+    fit = MlpHeadFit(z((E, H, H), torch.float32), z((E, H), torch.float32), z((E, K, H), torch.float32), z((E, K), torch.float32),
+                     z((E, mlp_param_count(H, K)), torch.float64), z((E,), torch.float64), z((E,), torch.float64), z((E,), torch.int32),
+                     torch.full((E,), -1, dtype=torch.int32, device=dev), float(l2), float(alpha), float(temperature))
+    _run_ramp_fit("ee_mlp_head_fit", dev, X, y, teacher, alpha, temperature, sample_weight, (theta0,), K, l2, gtol, max_evals, history,
+                  (fit.dense_weight, fit.dense_bias, fit.weight, fit.bias, fit.theta64, fit.loss, fit.grad_norm, fit.evals, fit.status))
+    return fit
 
 
 def fit_distilled_mlp_exit_heads(features, teacher_logits, labels=None, alpha: float = 1.0, temperature: float = 1.0, l2: float = 1e-2,
@@ -471,19 +476,8 @@ def fit_distilled_mlp_exit_heads(features, teacher_logits, labels=None, alpha: f
     (include/mmee.h, ee_mlp_head_fit_distill), from the start ``init`` (``"identity"`` needs no labels either).  Inputs, ``alpha``,
     ``temperature`` and the failures are those of ``fit_distilled_exit_heads``; budget, ``status`` (a stationary point reached by descent from
     ``init``: the objective is not convex) and ``init`` are ``fit_mlp_exit_heads``'; ``sample_weight`` is ``fit_distilled_exit_heads``'."""
-    dev, X, T, y, K = _distill_inputs(features, teacher_logits, labels, alpha, temperature, num_labels, device, sample_weight)
-    E, N, H = X.shape
-    theta0 = _mlp_theta0(init, E, H, K, dev)
-    fit = _new_mlp_head_fit(dev, E, K, H, l2, alpha, temperature)
-    if sample_weight is None:
-        ws, need = _workspace("ee_mlp_head_fit_workspace_bytes", dev, E, N, H, K, history)
-        _call("ee_mlp_head_fit_distill", dev, X, T, y, theta0, E, N, H, K, float(alpha), float(temperature), float(l2), float(gtol),
-              int(max_evals), int(history), ws, need, fit.dense_weight, fit.dense_bias, fit.weight, fit.bias, fit.theta64, fit.loss,
-              fit.grad_norm, fit.evals, fit.status)
-    else:
-        _weighted_mlp_head_fit(fit, dev, X, y, T, _weights(sample_weight, dev, E, N), theta0, K, alpha, temperature, l2, gtol, max_evals,
-                               history)
-    return fit
+    return _fit_mlp_heads(features, labels, (teacher_logits, alpha, temperature), l2, gtol, max_evals, history, init, device, num_labels,
+                          sample_weight)
 
 
 # ---- the learning-to-exit classifier: one Linear(H, 1) for all encoder exits ---------------------------------------------------------------------
@@ -504,10 +498,7 @@ def collect_lte_features(engine, batches: Iterable[Mapping]):
     those exits' policy logits (``all_logits``: ramps the head's logits, gates ``classifier(gate input)``).  Any LayoutLMv3 engine with an
     encoder exit will do -- ramp or gate, 1- or 2-layer heads, with or without ``use_lte``; embedding-level exits are skipped."""
     _check_lte_cfg(engine.cfg)
-    ec = engine.cfg.exit_config
-    n_emb, n_enc = len(ec.embedding_exits), len(ec.encoder_exit_layers)
-    return tuple(_cat_batches((rows, out.all_logits[n_emb:n_emb + n_enc].to(torch.float32))
-                              for rows, out in _dump_all(engine, batches, want_all=True)))
+    return _encoder_rows_and_logits(engine, batches)
 
 
 def lte_targets(logits, labels, device=None) -> "torch.Tensor":
@@ -635,9 +626,7 @@ def collect_gate_features(engine, batches: Iterable[Mapping]):
         raise ValueError("collect_gate_features needs a LayoutLMv3 engine of the gate strategy (encoder_layer_strategy = 'gate')")
     if not ec.encoder_exit_layers:
         raise ValueError("the configuration has no encoder exits")
-    n_emb, n_enc = len(ec.embedding_exits), len(ec.encoder_exit_layers)
-    return tuple(_cat_batches((rows, out.all_logits[n_emb:n_emb + n_enc].to(torch.float32))
-                              for rows, out in _dump_all(engine, batches, want_all=True)))
+    return _encoder_rows_and_logits(engine, batches)
 
 
 def gate_targets(gated_logits, labels, device=None) -> "torch.Tensor":
@@ -661,8 +650,7 @@ class GateFit:
 
     def logits(self, features) -> "torch.Tensor":
         """(E,N,2) float64 gate logits of the float32 heads on ``features`` (E,N,H), on the device."""
-        X = _rows(features, on=self.weight.device)[1].to(torch.float64)
-        return torch.baddbmm(self.bias.to(torch.float64).unsqueeze(1), X, self.weight.to(torch.float64).transpose(1, 2))
+        return _linear_logits(self, features)
 
     def scores(self, features) -> "torch.Tensor":
         """(E,N) float64 gate scores 1 / (1 + exp(h0 - h1)) of the float32 heads' float32 logits on ``features`` (E,N,H), on the device, by the
@@ -679,12 +667,7 @@ class GateFit:
         E, K, H = self.weight.shape
         if E != len(cfg.exit_config.encoder_exit_layers) or K != 2 or H != cfg.hidden_size:
             raise ValueError(f"the fit is (E,2,H) = {(E, K, H)}, the configuration wants {(len(cfg.exit_config.encoder_exit_layers), 2, cfg.hidden_size)}")
-        w, b = self.weight.cpu().numpy(), self.bias.cpu().numpy()
-        out = {}
-        for k in range(E):
-            out[f"layoutlmv3.encoder.early_exits.{k}.out_proj.weight"] = np.ascontiguousarray(w[k])
-            out[f"layoutlmv3.encoder.early_exits.{k}.out_proj.bias"] = np.ascontiguousarray(b[k])
-        return out
+        return _out_proj_state(self, E, "layoutlmv3.")
 
 
 def fit_gate_heads(features, targets, l2: float = 1e-2, gtol: float = 1e-9, max_evals: int = 2000, history: int = 8, device=None,
@@ -712,10 +695,7 @@ def fit_gate_heads(features, targets, l2: float = 1e-2, gtol: float = 1e-9, max_
     capi.load()
     dev, X = _rows(features, device)
     T = _to_device(targets, torch.float64, dev).view(E, N)
-    f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
-    fit = GateFit(torch.zeros((E, 2, H), dtype=torch.float32, device=dev), torch.zeros((E, 2), dtype=torch.float32, device=dev),
-                  f64(E, 2, H), f64(E, 2), f64(E), f64(E), torch.zeros((E,), dtype=torch.int32, device=dev),
-                  torch.full((E,), -1, dtype=torch.int32, device=dev), float(l2))
+    fit = _new_head_fit(GateFit, dev, E, 2, H, l2)
     ws, need = _workspace("ee_head_fit_workspace_bytes", dev, E, N, H, 2, history)
     _call("ee_head_fit_gate", dev, X, T, E, N, H, float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.weight, fit.bias,
           fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status)

@@ -4,9 +4,6 @@ restatement of tests/distill_headfit_ref.py against central differences and agai
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -15,6 +12,7 @@ from . import distill_headfit_ref as DR
 from . import headfit_ref as HR
 from . import mlp_headfit_ref as MR
 from .conftest import ROOT
+from .fit_util import _refused, compiles_as_c, exported_symbols
 
 NAMES = ("ee_head_fit_distill", "ee_debug_head_distill_lossgrad", "ee_mlp_head_fit_distill", "ee_debug_mlp_head_distill_lossgrad")
 PAIRS = [(1.0, 1.0), (0.5, 2.0), (0.3, 4.0), (0.0, 1.0)]
@@ -46,50 +44,25 @@ def test_capi_mirrors_the_header(pkg):
 
 
 def test_header_compiles_as_c_and_is_at_abi_4():
-    if not shutil.which("gcc"):
-        pytest.skip("no gcc")
-    with tempfile.TemporaryDirectory() as d:
-        src = os.path.join(d, "t.c")
-        with open(src, "w") as f:
-            f.write('#include "mmee.h"\n'
-                    'int main(void) {\n'
-                    '    int (*a)(const float*, const float*, const int64_t*, int32_t, int32_t, int32_t, int32_t, double, double, double, double,'
-                    ' int32_t, int32_t, void*, size_t, float*, float*, double*, double*, double*, double*, int32_t*, int32_t*, void*) ='
-                    ' ee_head_fit_distill;\n'
-                    '    int (*b)(const float*, const float*, const int64_t*, const double*, int32_t, int32_t, int32_t, int32_t, double, double,'
-                    ' double, double*, double*, void*) = ee_debug_head_distill_lossgrad;\n'
-                    '    int (*c)(const float*, const float*, const int64_t*, const double*, int32_t, int32_t, int32_t, int32_t, double, double,'
-                    ' double, double, int32_t, int32_t, void*, size_t, float*, float*, float*, float*, double*, double*, double*, int32_t*,'
-                    ' int32_t*, void*) = ee_mlp_head_fit_distill;\n'
-                    '    int (*d)(const float*, const float*, const int64_t*, const double*, int32_t, int32_t, int32_t, int32_t, double, double,'
-                    ' double, double*, double*, void*) = ee_debug_mlp_head_distill_lossgrad;\n'
-                    '    (void)a; (void)b; (void)c; (void)d;\n'
-                    '    return MMEE_ABI_VERSION != 4;\n'
-                    '}\n')
-        r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), src],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
+    compiles_as_c('    int (*a)(const float*, const float*, const int64_t*, int32_t, int32_t, int32_t, int32_t, double, double, double, double,'
+                  ' int32_t, int32_t, void*, size_t, float*, float*, double*, double*, double*, double*, int32_t*, int32_t*, void*) ='
+                  ' ee_head_fit_distill;\n'
+                  '    int (*b)(const float*, const float*, const int64_t*, const double*, int32_t, int32_t, int32_t, int32_t, double, double,'
+                  ' double, double*, double*, void*) = ee_debug_head_distill_lossgrad;\n'
+                  '    int (*c)(const float*, const float*, const int64_t*, const double*, int32_t, int32_t, int32_t, int32_t, double, double,'
+                  ' double, double, int32_t, int32_t, void*, size_t, float*, float*, float*, float*, double*, double*, double*, int32_t*,'
+                  ' int32_t*, void*) = ee_mlp_head_fit_distill;\n'
+                  '    int (*d)(const float*, const float*, const int64_t*, const double*, int32_t, int32_t, int32_t, int32_t, double, double,'
+                  ' double, double*, double*, void*) = ee_debug_mlp_head_distill_lossgrad;\n'
+                  '    (void)a; (void)b; (void)c; (void)d;\n'
+                  '    return MMEE_ABI_VERSION != 4;\n')
 
 
 def test_library_exports_the_four_symbols(pkg):
     """Read the built library's dynamic symbol table (no GPU, no loading)."""
-    path = pkg.capi.lib_path()
-    if not os.path.exists(path):
-        pytest.fail(f"{path} is missing: build() first")
-    tool = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/llvm/bin/llvm-nm"
-    r = subprocess.run([tool, "-D", "--defined-only", path], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    exported = {ln.split()[-1] for ln in r.stdout.splitlines() if ln.strip()}
+    exported = exported_symbols(pkg.capi.lib_path())
     for name in NAMES:
         assert name in exported, name
-
-
-def _refused(pkg, name, call, cases):
-    for what, (kw, needle) in cases.items():
-        assert call(**kw) != 0, (name, what)
-        msg = pkg.capi.last_error()
-        assert msg.startswith(name + ":") and "no HIP device" not in msg, (name, what, msg)
-        assert needle in msg, (name, what, msg)
 
 
 def test_entry_points_refuse_bad_arguments_before_any_device_call(pkg):

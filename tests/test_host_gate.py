@@ -4,15 +4,13 @@ C-ABI (header declarations, plain-C compile, the symbols the built library expor
 import operator
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 from . import gate_ref as G
 from .conftest import ROOT
+from .fit_util import compiles_as_c, exported_symbols
 
 GATE_EE = dict(exits=["text_avg", 1, 2], encoder_layer_strategy="gate", inference_strategy="gate")
 NEW_SYMBOLS = ("ee_gate_table", "ee_gate_scan", "ee_head_fit_gate", "ee_debug_head_gate_lossgrad")
@@ -175,31 +173,14 @@ def test_header_declares_the_gate_entry_points(pkg):
 
 
 def test_header_with_the_gate_compiles_as_c():
-    if not shutil.which("gcc"):
-        pytest.skip("no gcc")
-    with tempfile.TemporaryDirectory() as d:
-        src = os.path.join(d, "t.c")
-        with open(src, "w") as f:
-            f.write('#include "mmee.h"\n'
-                    'int main(void) {\n'
-                    '    int (*a)(const float*, const double*, int32_t, int32_t, int32_t, double*, void*) = ee_gate_table;\n'
-                    '    int (*b)(const double*, const double*, int32_t, int32_t, int32_t, const double*, int32_t*, double*, double*, int32_t*, void*) = ee_gate_scan;\n'
-                    '    (void)a; (void)b;\n'
-                    '    return !(MMEE_CRIT_GATE == 4 && MMEE_CRIT_MARGIN == 3);\n'
-                    '}\n')
-        r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), src],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
+    compiles_as_c('    int (*a)(const float*, const double*, int32_t, int32_t, int32_t, double*, void*) = ee_gate_table;\n'
+                  '    int (*b)(const double*, const double*, int32_t, int32_t, int32_t, const double*, int32_t*, double*, double*, int32_t*, void*) = ee_gate_scan;\n'
+                  '    (void)a; (void)b;\n'
+                  '    return !(MMEE_CRIT_GATE == 4 && MMEE_CRIT_MARGIN == 3);\n')
 
 
 def test_library_exports_the_gate_entry_points(pkg):
     """Read the built library's dynamic symbol table (no GPU, no loading)."""
-    path = pkg.capi.lib_path()
-    if not os.path.exists(path):
-        pytest.fail(f"{path} is missing: build() first")
-    tool = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/llvm/bin/llvm-nm"
-    r = subprocess.run([tool, "-D", "--defined-only", path], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    exported = {ln.split()[-1] for ln in r.stdout.splitlines() if ln.strip()}
+    exported = exported_symbols(pkg.capi.lib_path())
     for name in NEW_SYMBOLS:
         assert name in exported, name

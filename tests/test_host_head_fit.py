@@ -4,16 +4,13 @@ float64 restatement of tests/headfit_ref.py against central differences."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 from . import headfit_ref as HR
 from .conftest import ROOT
-from .fit_util import _HostTensor
+from .fit_util import _HostTensor, _refused, compiles_as_c, exported_symbols
 
 NAMES = ("ee_head_fit", "ee_head_fit_workspace_bytes", "ee_debug_head_lossgrad")
 ONE_LAYER_RAMP = dict(exits=[1, 2, 4], encoder_layer_strategy="ramp", exit_head_num_layers=1)
@@ -40,35 +37,18 @@ def test_capi_mirrors_the_header(pkg):
 
 
 def test_header_compiles_as_c_and_is_at_abi_4():
-    if not shutil.which("gcc"):
-        pytest.skip("no gcc")
-    with tempfile.TemporaryDirectory() as d:
-        src = os.path.join(d, "t.c")
-        with open(src, "w") as f:
-            f.write('#include "mmee.h"\n'
-                    'int main(void) {\n'
-                    '    int (*a)(const float*, const int64_t*, int32_t, int32_t, int32_t, int32_t, double, double, int32_t, int32_t, void*, size_t, float*,'
-                    ' float*, double*, double*, double*, double*, int32_t*, int32_t*, void*) = ee_head_fit;\n'
-                    '    size_t (*b)(int32_t, int32_t, int32_t, int32_t, int32_t) = ee_head_fit_workspace_bytes;\n'
-                    '    int (*c)(const float*, const int64_t*, const double*, int32_t, int32_t, int32_t, int32_t, double, double*, double*, void*) ='
-                    ' ee_debug_head_lossgrad;\n'
-                    '    (void)a; (void)b; (void)c;\n'
-                    '    return MMEE_ABI_VERSION != 4 || MMEE_HEAD_FIT_SLAB < 1;\n'
-                    '}\n')
-        r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), src],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
+    compiles_as_c('    int (*a)(const float*, const int64_t*, int32_t, int32_t, int32_t, int32_t, double, double, int32_t, int32_t, void*, size_t, float*,'
+                  ' float*, double*, double*, double*, double*, int32_t*, int32_t*, void*) = ee_head_fit;\n'
+                  '    size_t (*b)(int32_t, int32_t, int32_t, int32_t, int32_t) = ee_head_fit_workspace_bytes;\n'
+                  '    int (*c)(const float*, const int64_t*, const double*, int32_t, int32_t, int32_t, int32_t, double, double*, double*, void*) ='
+                  ' ee_debug_head_lossgrad;\n'
+                  '    (void)a; (void)b; (void)c;\n'
+                  '    return MMEE_ABI_VERSION != 4 || MMEE_HEAD_FIT_SLAB < 1;\n')
 
 
 def test_library_exports_the_three_symbols(pkg):
     """Read the built library's dynamic symbol table (no GPU, no loading)."""
-    path = pkg.capi.lib_path()
-    if not os.path.exists(path):
-        pytest.fail(f"{path} is missing: build() first")
-    tool = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/llvm/bin/llvm-nm"
-    r = subprocess.run([tool, "-D", "--defined-only", path], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    exported = {ln.split()[-1] for ln in r.stdout.splitlines() if ln.strip()}
+    exported = exported_symbols(pkg.capi.lib_path())
     for name in NAMES:
         assert name in exported, name
 
@@ -106,20 +86,14 @@ def test_entry_points_refuse_bad_arguments_before_any_device_call(pkg):
         "unaligned features": (dict(X=C.c_void_p(4100)), "aligned"),
         "small workspace": (dict(ws_bytes=need - 1), f"needs {need} bytes"),
     }
-    for what, (kw, needle) in cases.items():
-        assert fit(**kw) != 0, what
-        msg = pkg.capi.last_error()
-        assert msg.startswith("ee_head_fit:") and "no HIP device" not in msg, (what, msg)
-        assert needle in msg, (what, msg)
+    _refused(pkg, "ee_head_fit", fit, cases)
 
     def lossgrad(X=p, y=p, th=p, K=K, l2=1e-2, loss=p, grad=p):
         return lib.ee_debug_head_lossgrad(X, y, th, E, N, H, K, l2, loss, grad, None)
 
-    for what, (kw, needle) in {"null theta": (dict(th=None), "NULL"), "null grad": (dict(grad=None), "NULL"), "l2 = 0": (dict(l2=0.0), "l2 = 0"),
-                               "K = 1": (dict(K=1), "K = 1"), "K = 65": (dict(K=65), "K = 65")}.items():
-        assert lossgrad(**kw) != 0, what
-        msg = pkg.capi.last_error()
-        assert msg.startswith("ee_debug_head_lossgrad:") and "no HIP device" not in msg and needle in msg, (what, msg)
+    _refused(pkg, "ee_debug_head_lossgrad", lossgrad,
+             {"null theta": (dict(th=None), "NULL"), "null grad": (dict(grad=None), "NULL"),
+              "l2 = 0": (dict(l2=0.0), "l2 = 0"), "K = 1": (dict(K=1), "K = 1"), "K = 65": (dict(K=65), "K = 65")})
 
 
 def test_workspace_grows_with_every_dimension(pkg):

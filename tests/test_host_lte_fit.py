@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from . import lte_fit_ref as LR
-from .fit_util import _HostTensor
+from .fit_util import _HostTensor, _refused
 
 L2 = 1e-2
 FIT_SHAPES = [(300, 64, 3), (257, 64, 1), (1000, 256, 2), (600, 768, 1), (96, 256, 3)]       # (N, H, E)
@@ -192,10 +192,7 @@ def test_c_entry_points_refuse_bad_arguments_before_any_device_call(pkg):
         "max_evals = 0": (dict(evals=0), "max_evals = 0"), "history = 0": (dict(hist=0), "history = 0"), "history = 33": (dict(hist=33), "history = 33"),
         "unaligned features": (dict(X=C.c_void_p(4100)), "aligned"), "small workspace": (dict(ws_bytes=need - 1), f"needs {need} bytes"),
     }
-    for what, (kw, needle) in cases.items():
-        assert fit(**kw) != 0, what
-        msg = pkg.capi.last_error()
-        assert msg.startswith("ee_lte_fit:") and "no HIP device" not in msg and needle in msg, (what, msg)
+    _refused(pkg, "ee_lte_fit", fit, cases)
     assert lib.ee_debug_lte_lossgrad(p, p, None, E, N, H, 0, 1e-2, p, p, None) != 0 and "NULL" in pkg.capi.last_error()
     assert lib.ee_debug_lte_lossgrad(p, p, p, E, N, H, 0, -1.0, p, p, None) != 0 and "l2 = -1" in pkg.capi.last_error()
     assert lib.ee_lte_targets(p, p, E, N, 0, p, None) != 0 and "ee_lte_targets" in pkg.capi.last_error()

@@ -5,9 +5,6 @@ all-ones weights are the unweighted restatements."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -17,6 +14,7 @@ from . import headfit_ref as HR
 from . import mlp_headfit_ref as MR
 from . import weighted_headfit_ref as WR
 from .conftest import ROOT
+from .fit_util import _refused, compiles_as_c, exported_symbols
 
 NAMES = ("ee_head_fit_weighted", "ee_head_fit_weighted_workspace_bytes", "ee_debug_head_weighted_lossgrad", "ee_mlp_head_fit_weighted",
          "ee_mlp_head_fit_weighted_workspace_bytes", "ee_debug_mlp_head_weighted_lossgrad")
@@ -50,42 +48,25 @@ def test_capi_mirrors_the_header(pkg):
 
 
 def test_header_compiles_as_c_and_is_at_abi_4():
-    if not shutil.which("gcc"):
-        pytest.skip("no gcc")
-    with tempfile.TemporaryDirectory() as d:
-        src = os.path.join(d, "t.c")
-        with open(src, "w") as f:
-            f.write('#include "mmee.h"\n'
-                    'int main(void) {\n'
-                    '    int (*a)(const float*, const int64_t*, const float*, const float*, int32_t, int32_t, int32_t, int32_t, double, double, double,'
-                    ' double, int32_t, int32_t, void*, size_t, float*, float*, double*, double*, double*, double*, int32_t*, int32_t*, void*) ='
-                    ' ee_head_fit_weighted;\n'
-                    '    int (*b)(const float*, const int64_t*, const float*, const float*, const double*, int32_t, int32_t, int32_t, int32_t, double,'
-                    ' double, double, double*, double*, void*) = ee_debug_head_weighted_lossgrad;\n'
-                    '    int (*c)(const float*, const int64_t*, const float*, const float*, const double*, int32_t, int32_t, int32_t, int32_t, double,'
-                    ' double, double, double, int32_t, int32_t, void*, size_t, float*, float*, float*, float*, double*, double*, double*, int32_t*,'
-                    ' int32_t*, void*) = ee_mlp_head_fit_weighted;\n'
-                    '    int (*d)(const float*, const int64_t*, const float*, const float*, const double*, int32_t, int32_t, int32_t, int32_t, double,'
-                    ' double, double, double*, double*, void*) = ee_debug_mlp_head_weighted_lossgrad;\n'
-                    '    size_t (*e)(int32_t, int32_t, int32_t, int32_t, int32_t) = ee_head_fit_weighted_workspace_bytes;\n'
-                    '    size_t (*g)(int32_t, int32_t, int32_t, int32_t, int32_t) = ee_mlp_head_fit_weighted_workspace_bytes;\n'
-                    '    (void)a; (void)b; (void)c; (void)d; (void)e; (void)g;\n'
-                    '    return MMEE_ABI_VERSION != 4;\n'
-                    '}\n')
-        r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), src],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
+    compiles_as_c('    int (*a)(const float*, const int64_t*, const float*, const float*, int32_t, int32_t, int32_t, int32_t, double, double, double,'
+                  ' double, int32_t, int32_t, void*, size_t, float*, float*, double*, double*, double*, double*, int32_t*, int32_t*, void*) ='
+                  ' ee_head_fit_weighted;\n'
+                  '    int (*b)(const float*, const int64_t*, const float*, const float*, const double*, int32_t, int32_t, int32_t, int32_t, double,'
+                  ' double, double, double*, double*, void*) = ee_debug_head_weighted_lossgrad;\n'
+                  '    int (*c)(const float*, const int64_t*, const float*, const float*, const double*, int32_t, int32_t, int32_t, int32_t, double,'
+                  ' double, double, double, int32_t, int32_t, void*, size_t, float*, float*, float*, float*, double*, double*, double*, int32_t*,'
+                  ' int32_t*, void*) = ee_mlp_head_fit_weighted;\n'
+                  '    int (*d)(const float*, const int64_t*, const float*, const float*, const double*, int32_t, int32_t, int32_t, int32_t, double,'
+                  ' double, double, double*, double*, void*) = ee_debug_mlp_head_weighted_lossgrad;\n'
+                  '    size_t (*e)(int32_t, int32_t, int32_t, int32_t, int32_t) = ee_head_fit_weighted_workspace_bytes;\n'
+                  '    size_t (*g)(int32_t, int32_t, int32_t, int32_t, int32_t) = ee_mlp_head_fit_weighted_workspace_bytes;\n'
+                  '    (void)a; (void)b; (void)c; (void)d; (void)e; (void)g;\n'
+                  '    return MMEE_ABI_VERSION != 4;\n')
 
 
 def test_library_exports_the_six_symbols(pkg):
     """Read the built library's dynamic symbol table (no GPU, no loading)."""
-    path = pkg.capi.lib_path()
-    if not os.path.exists(path):
-        pytest.fail(f"{path} is missing: build() first")
-    tool = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/llvm/bin/llvm-nm"
-    r = subprocess.run([tool, "-D", "--defined-only", path], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    exported = {ln.split()[-1] for ln in r.stdout.splitlines() if ln.strip()}
+    exported = exported_symbols(pkg.capi.lib_path())
     for name in NAMES:
         assert name in exported, name
 
@@ -96,14 +77,6 @@ def test_workspace_is_the_unweighted_one_plus_the_scale_table(pkg):
         assert lib.ee_head_fit_weighted_workspace_bytes(E, N, H, K, M) == lib.ee_head_fit_workspace_bytes(E, N, H, K, M) + 8 * E * N
         assert lib.ee_mlp_head_fit_weighted_workspace_bytes(E, N, H, K, M) == lib.ee_mlp_head_fit_workspace_bytes(E, N, H, K, M) + 8 * E * N
     assert lib.ee_head_fit_weighted_workspace_bytes(0, 1, 4, 2, 1) == 0 and lib.ee_mlp_head_fit_weighted_workspace_bytes(1, 1, 4, 2, 0) == 0
-
-
-def _refused(pkg, name, call, cases):
-    for what, (kw, needle) in cases.items():
-        assert call(**kw) != 0, (name, what)
-        msg = pkg.capi.last_error()
-        assert msg.startswith(name + ":") and "no HIP device" not in msg, (name, what, msg)
-        assert needle in msg, (name, what, msg)
 
 
 def test_entry_points_refuse_bad_arguments_before_any_device_call(pkg):
