@@ -911,6 +911,51 @@ int ee_debug_head_gate_lossgrad(const float* features, const double* targets, co
                                 double* loss, double* grad, void* stream);
 
 /*
+ * Two-layer 2-way gate heads (exit_head_num_layers == 2, the reference's default depth: dense (H,H) -> tanh -> out_proj (2,H)) from the same
+ * CLS rows and the same targets: the gate objective above on ee_mlp_head_fit's head.  Per exit e, independently, with x_n the float32 CLS row,
+ * c = targets[e][n] in [0, 1] and theta = (W1 (H,H), b1 (H,), W2 (2,H), b2 (2,)) in ee_mlp_head_fit's layout at K = 2 (P = H*H + 3H + 2):
+ *
+ *     z_n = W2 tanh(W1 x_n + b1) + b2                              in R^2; column 1 is "correctly gated"
+ *     L_e(theta) = (1 / (2N)) sum_n [ bce(z_1, c) + bce(z_0, 1 - c) ] + (l2 / 2) ||theta||^2
+ *     bce(z, t) = max(z, 0) + log1p(exp(-|z|)) - t z               dL/dz_j = (sigmoid(z_j) - t_j) / (2N),  t_1 = c, t_0 = 1 - c
+ *
+ * nn.BCEWithLogitsLoss() on the (N, 2) gate logits, as for ee_head_fit_gate.  Arithmetic is float64 on the float32 rows; the softplus does not
+ * overflow (logits of several hundred stay finite).  Every block is penalised; l2 <= 0 (and NaN) is refused.  The objective is NOT convex:
+ * status 0 promises ||grad L||_2 <= gtol at a point reached by descent from theta0, as for ee_mlp_head_fit, not a unique optimum.
+ *
+ * ee_mlp_head_fit_gate: features dev float32 (E,N,H), targets dev double (E,N), theta0 dev double (E,P), required (theta = 0 is a saddle).
+ *   Everything else -- l2, gtol, max_evals, history, the workspace (ee_mlp_head_fit_workspace_bytes(E, N, H, 2, history)), the outputs
+ *   dense_weight (E,H,H), dense_bias (E,H), weight (E,2,H), bias (E,2), theta64 (E,P), loss, grad_norm, evals, status, the L-BFGS, the stopping
+ *   rules and the status codes -- is ee_mlp_head_fit's at K = 2, and so are six of the seven launches of an evaluation: one row kernel takes the
+ *   softmax kernel's place.  Limits: 4 <= H <= 1024, H % 4 == 0, features 16-byte aligned, 1 <= history <= 32.
+ *   A target that is not finite or lies outside [0, 1] raises bit 0 of the error word: the call fails with a message and has written no
+ *   output; it learns of it by the one wait after its last launch.
+ * ee_mlp_head_fit_gate_weighted: the same with weights dev float32 (E,N), required (the unweighted entry point takes none), w[e][n] >= 0 and
+ *   finite, W_e = sum_n w[e][n] > 0: the data term becomes (1 / (2 W_e)) sum_n w[e][n] [ ... ].  How: scale[e][n] = w[e][n] N / W_e, made once
+ *   per call as for ee_mlp_head_fit_weighted, multiplies the row's loss and its N dL/dz as the last multiplication; the workspace is
+ *   ee_mlp_head_fit_weighted_workspace_bytes(E, N, H, 2, history).  A row of weight zero contributes zeros and its target is not read or
+ *   checked (it may be NaN); its features must be finite.  Error-word bit 2 a weight that is negative or not finite, bit 3 an exit whose
+ *   weights sum to zero, both looked at before bit 0.  All-ones weights are the unweighted fit bit for bit; w and c w with c a power of two
+ *   return the same bits.
+ *   Determinism, both: no floating-point atomics, every sum in an order that depends on (N, H) alone, nothing depends on E -- two calls return
+ *   the same bits, and an exit fitted together with others gets the bits it gets alone.
+ * ee_debug_mlp_head_gate_lossgrad / ee_debug_mlp_head_gate_weighted_lossgrad: ONE evaluation of L_e and grad L_e at theta64 dev (E,P): loss dev
+ *   (E,), grad dev (E,P) in the layout of theta; the weighted hook makes the row scales inside the call.
+ */
+int ee_mlp_head_fit_gate(const float* features, const double* targets, const double* theta0, int32_t E, int32_t N, int32_t H, double l2, double gtol,
+                         int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* dense_weight, float* dense_bias,
+                         float* weight, float* bias, double* theta64, double* loss, double* grad_norm, int32_t* evals, int32_t* status,
+                         void* stream);
+int ee_mlp_head_fit_gate_weighted(const float* features, const double* targets, const float* weights, const double* theta0, int32_t E, int32_t N,
+                                  int32_t H, double l2, double gtol, int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes,
+                                  float* dense_weight, float* dense_bias, float* weight, float* bias, double* theta64, double* loss,
+                                  double* grad_norm, int32_t* evals, int32_t* status, void* stream);
+int ee_debug_mlp_head_gate_lossgrad(const float* features, const double* targets, const double* theta64, int32_t E, int32_t N, int32_t H, double l2,
+                                    double* loss, double* grad, void* stream);
+int ee_debug_mlp_head_gate_weighted_lossgrad(const float* features, const double* targets, const float* weights, const double* theta64, int32_t E,
+                                             int32_t N, int32_t H, double l2, double* loss, double* grad, void* stream);
+
+/*
  * Device-side input feed (replaces the host image processor + collator in front of the model, EE/data/RVL_CDIP.py:246-262
  * and EE/utils.py:93-98, 173).
  *

@@ -211,6 +211,12 @@ SYMBOLS = {
     "ee_mlp_head_fit_weighted_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, _i32]),
     "ee_debug_mlp_head_weighted_lossgrad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _vp,
                                                       _vp, _vp]),
+    "ee_mlp_head_fit_gate": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp]),
+    "ee_mlp_head_fit_gate_weighted": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _i32, _vp, C.c_size_t, _vp, _vp,
+                                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ee_debug_mlp_head_gate_lossgrad": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp]),
+    "ee_debug_mlp_head_gate_weighted_lossgrad": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp]),
     "ee_lte_fit": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp]),
     "ee_lte_fit_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32]),

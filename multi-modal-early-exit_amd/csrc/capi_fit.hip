@@ -1,7 +1,7 @@
 // Entry points of the device fits, none of which sees a handle: one-layer and two-layer exit heads from dumped CLS rows against labels
 // (ee_head_fit, ee_mlp_head_fit), against the final classifier's logits (ee_head_fit_distill, ee_mlp_head_fit_distill), either with sample
-// weights (ee_head_fit_weighted, ee_mlp_head_fit_weighted), the 2-way gate heads (ee_head_fit_gate), and the learning-to-exit classifier
-// (ee_lte_fit, with ee_lte_targets and ee_lte_scores); their workspace queries, and the ee_debug_*_lossgrad hooks that run one evaluation of an
+// weights (ee_head_fit_weighted, ee_mlp_head_fit_weighted), the 2-way gate heads of either depth (ee_head_fit_gate; ee_mlp_head_fit_gate and
+// ee_mlp_head_fit_gate_weighted), and the learning-to-exit classifier (ee_lte_fit, with ee_lte_targets and ee_lte_scores); their workspace queries, and the ee_debug_*_lossgrad hooks that run one evaluation of an
 // objective on caller-provided buffers.  The L-BFGS is fit_lbfgs.hip.
 //
 // What a head is fitted against is one value, HeadObjective (mmee_kernels.h).  Each head entry point builds it from its own arguments
@@ -33,7 +33,7 @@ static int budget_refuse(const char* who, double gtol, int32_t max_evals, int32_
 // ---- the error word, decoded once ---------------------------------------------------------------------------------------------------------
 // Which objective an entry point states.  For the head fits it is the family of entry points that built the HeadObjective, which the value
 // alone does not say: a distilled entry point that was handed NULL teacher_logits is refused, a weighted one fits against labels then.
-enum class Objective { kLabelled, kDistilled, kWeighted, kGate, kLte, kLteTargets };
+enum class Objective { kLabelled, kDistilled, kWeighted, kGate, kWeightedGate, kLte, kLteTargets };
 
 // bit 0: a bad label or target -- which, and so the message, is the objective's; bit 1: a teacher logit that is not finite (the distilled
 // objectives); bit 2: a sample weight that is negative or not finite, bit 3: an exit whose weights sum to zero (launch_row_scale).  Bits 2 and 3
@@ -47,6 +47,7 @@ static int error_word_fail(const char* who, int err, Objective of, bool fit, int
         default:
             return fail(nullptr, fit ? "%s: a label is outside [0, K = %d); no output was written" : "%s: a label is outside [0, K = %d)", who, K);
         case Objective::kGate:
+        case Objective::kWeightedGate:
             return fit ? fail(nullptr, "%s: a target is not finite or lies outside [0, 1]%s", who, tail)
                        : fail(nullptr, "%s: a target is not finite or lies outside [0, 1] (K = %d)", who, K);
         case Objective::kLte:
@@ -127,6 +128,7 @@ static Asked weighted(const int64_t* labels, const float* teacher_logits, double
     return {Objective::kWeighted, {int64_labels(labels), {teacher_logits, alpha, temperature}, weights, nullptr}};
 }
 static Asked gate(const double* targets) { return {Objective::kGate, {nullptr, {}, nullptr, targets}}; }
+static Asked weighted_gate(const double* targets, const float* weights) { return {Objective::kWeightedGate, {nullptr, {}, weights, targets}}; }
 
 // The refusals of the objective itself, with the body's NULL check among them, in the order they have always been tried: the weighted entry
 // points' own, the NULL check, the distilled objective's.  missing: one of the body's other required pointers is NULL; null_fmt: the body's
@@ -134,13 +136,13 @@ static Asked gate(const double* targets) { return {Objective::kGate, {nullptr, {
 static int objective_refuse(const char* who, const Asked& q, bool missing, const char* null_fmt) {
     const HeadObjective& o = q.o;
     const DistillTargets& soft = o.soft;
-    if (q.by == Objective::kWeighted) {                     // teacher_logits may be NULL here: labels alone
-        if (!o.weights) return fail(nullptr, "%s: NULL argument (weights are required: (E,N) float32; the unweighted entry points take none)", who);
-        if (!soft.teacher && soft.alpha != 0.0)
-            return fail(nullptr, "%s: alpha = %g without teacher_logits: NULL teacher_logits select the labelled objective, alpha must be 0", who,
-                        soft.alpha);
-    }
-    const bool to_gate = q.by == Objective::kGate, to_teacher = q.by == Objective::kDistilled || (q.by == Objective::kWeighted && soft.teacher);
+    const bool to_gate = q.by == Objective::kGate || q.by == Objective::kWeightedGate;
+    if ((q.by == Objective::kWeighted || q.by == Objective::kWeightedGate) && !o.weights)
+        return fail(nullptr, "%s: NULL argument (weights are required: (E,N) float32; the unweighted entry points take none)", who);
+    if (q.by == Objective::kWeighted && !soft.teacher && soft.alpha != 0.0)                  // teacher_logits may be NULL here: labels alone
+        return fail(nullptr, "%s: alpha = %g without teacher_logits: NULL teacher_logits select the labelled objective, alpha must be 0", who,
+                    soft.alpha);
+    const bool to_teacher = q.by == Objective::kDistilled || (q.by == Objective::kWeighted && soft.teacher);
     if (missing || (to_gate ? !o.gate_targets : !to_teacher && !o.labels))
         return fail(nullptr, null_fmt, who, to_gate ? "targets" : to_teacher ? "teacher_logits" : "labels");
     if (!to_teacher) return 0;
@@ -326,6 +328,35 @@ int ee_debug_mlp_head_weighted_lossgrad(const float* features, const int64_t* la
                                         double l2, double* loss, double* grad, void* stream) {
     return head_lossgrad_call("ee_debug_mlp_head_weighted_lossgrad", true, weighted(labels, teacher_logits, alpha, temperature, weights), features,
                               theta64, E, N, H, K, l2, loss, grad, stream);
+}
+
+// ---- two-layer 2-way gate heads: the gate objective on the two-layer fit's launches at K = 2, with or without sample weights ------------------
+int ee_mlp_head_fit_gate(const float* features, const double* targets, const double* theta0, int32_t E, int32_t N, int32_t H, double l2, double gtol,
+                         int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, float* dense_weight, float* dense_bias,
+                         float* weight, float* bias, double* theta64, double* loss, double* grad_norm, int32_t* evals, int32_t* status,
+                         void* stream) {
+    return mlp_head_fit_call("ee_mlp_head_fit_gate", gate(targets), features, theta0, E, N, H, 2, l2, gtol, max_evals, history, workspace,
+                             workspace_bytes, dense_weight, dense_bias, weight, bias, theta64, loss, grad_norm, evals, status, stream);
+}
+
+int ee_mlp_head_fit_gate_weighted(const float* features, const double* targets, const float* weights, const double* theta0, int32_t E, int32_t N,
+                                  int32_t H, double l2, double gtol, int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes,
+                                  float* dense_weight, float* dense_bias, float* weight, float* bias, double* theta64, double* loss,
+                                  double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
+    return mlp_head_fit_call("ee_mlp_head_fit_gate_weighted", weighted_gate(targets, weights), features, theta0, E, N, H, 2, l2, gtol, max_evals,
+                             history, workspace, workspace_bytes, dense_weight, dense_bias, weight, bias, theta64, loss, grad_norm, evals, status,
+                             stream);
+}
+
+int ee_debug_mlp_head_gate_lossgrad(const float* features, const double* targets, const double* theta64, int32_t E, int32_t N, int32_t H, double l2,
+                                    double* loss, double* grad, void* stream) {
+    return head_lossgrad_call("ee_debug_mlp_head_gate_lossgrad", true, gate(targets), features, theta64, E, N, H, 2, l2, loss, grad, stream);
+}
+
+int ee_debug_mlp_head_gate_weighted_lossgrad(const float* features, const double* targets, const float* weights, const double* theta64, int32_t E,
+                                             int32_t N, int32_t H, double l2, double* loss, double* grad, void* stream) {
+    return head_lossgrad_call("ee_debug_mlp_head_gate_weighted_lossgrad", true, weighted_gate(targets, weights), features, theta64, E, N, H, 2, l2,
+                              loss, grad, stream);
 }
 
 // ---- the LTE classifier from CLS rows (lte_fit.hip) --------------------------------------------------------------------------------------

@@ -106,14 +106,6 @@ __device__ inline void distill_row_step(const Args& a, double* Z, double sc, int
     }
 }
 
-// bce(z, t) = softplus(z) - t z with softplus(z) = max(z, 0) + log1p(exp(-|z|)), which does not overflow; its derivative sigmoid(z) - t from the
-// same exponential
-__device__ inline double gate_bce(double z, double t, double& dz) {
-    const double ez = exp(-fabs(z)), inv = 1.0 / (1.0 + ez);
-    dz = (z >= 0.0 ? inv : ez * inv) - t;
-    return (fmax(z, 0.0) + log1p(ez)) - t * z;
-}
-
 // The gate row step (include/mmee.h, ee_head_fit_gate): the row's loss (bce(z_1, c) + bce(z_0, 1 - c)) / 2 -- the reduce kernel divides by N,
 // which makes the objective's 1 / (2N) -- and N dL/dz in place of the two logits, zeros in the padding columns.  Eight threads a row, as in the
 // other row steps; each reads both logits before any of the row writes (lanes of one wave, LDS operations in program order).

@@ -113,6 +113,15 @@ __device__ inline double distill_row(double (&v)[kRowSlots], const float (&tv)[k
     return (hard && y >= 0 ? keep * ((m + log(s1)) - zy) : 0.0) + soft * T * kl;
 }
 
+// ---- the gate objective's element (ee_head_fit_gate, ee_mlp_head_fit_gate; include/mmee.h states the objective) ------------------------------
+// bce(z, t) = softplus(z) - t z with softplus(z) = max(z, 0) + log1p(exp(-|z|)), which does not overflow; its derivative sigmoid(z) - t from the
+// same exponential.  The one-layer fit calls it from its slab walk (gate_row_step), the two-layer fit from its gate row kernel.
+__device__ inline double gate_bce(double z, double t, double& dz) {
+    const double ez = exp(-fabs(z)), inv = 1.0 / (1.0 + ez);
+    dz = (z >= 0.0 ? inv : ez * inv) - t;
+    return (fmax(z, 0.0) + log1p(ez)) - t * z;
+}
+
 // ---- sample weights (ee_head_fit_weighted, ee_mlp_head_fit_weighted; include/mmee.h states the objective) ------------------------------------
 // The weighted fits scale a row's N dL/dz and its loss by scale[e][n] = w[e][n] N / W_e and change nothing behind the row step: every later
 // kernel divides by N as before.  launch_row_scale (head_fit.hip) makes the table once per call, one workgroup per exit: W_e in float64 in a

@@ -5,7 +5,8 @@
 //   mlp_nt_gemm_kernel<float, tanh>   A = tanh(X W1^T + b1)            (N,H) float64, kept in the workspace          2 N H^2 FLOP
 //   mlp_nt_gemm_kernel<double>        Z = A W2^T + b2                  (N,K)
 //   mlp_softmax_kernel                D = softmax(Z) - Y in place of Z, the rows' losses, the label check
-//                                     (ee_mlp_head_fit_distill: mlp_distill_softmax_kernel in its place, D = N dL/dZ of the mixed objective)
+//                                     (ee_mlp_head_fit_distill: mlp_distill_softmax_kernel in its place, D = N dL/dZ of the mixed objective;
+//                                      ee_mlp_head_fit_gate: mlp_gate_kernel, D = (sigmoid(Z) - T) / 2 and the target check)
 //   mlp_tn_gemm_kernel<double>        dW2 = D^T A, db2 = D^T 1         written as gradient: / N + l2 theta
 //   mlp_dact_kernel                   dA = (D W2) (1 - A^2)            in place of A
 //   mlp_tn_gemm_kernel<float>         dW1 = dA^T X, db1 = dA^T 1       written as gradient                           2 N H^2 FLOP
@@ -13,8 +14,10 @@
 // ee_mlp_head_fit_weighted: the two softmax kernels are templates over their argument struct, and the weighted structs select (if constexpr)
 // the row step that multiplies D and the row's loss by scale[e][n] = w[e][n] N / W_e (launch_row_scale, head_fit_common.h, once per call) and
 // skips a row whose scale is zero.  The other six launches are shared, division by N included; the unweighted instantiations are the code
-// they were.  launch_eval reads which of the four a call launches off its HeadObjective (mmee_kernels.h); run_lbfgs_fit makes the table, behind
-// this file's scratch (scale_table, head_fit_common.h).
+// they were.  ee_mlp_head_fit_gate (two-layer 2-way gate heads, K = 2) puts a third row kernel in the same place: mlp_gate_kernel, the two
+// binary cross-entropies of the gate objective against a target in [0, 1] per (exit, row) (gate_bce, head_fit_common.h), with the same
+// weighted form (ee_mlp_head_fit_gate_weighted).  launch_eval reads which of the six a call launches off its HeadObjective (mmee_kernels.h);
+// run_lbfgs_fit makes the table, behind this file's scratch (scale_table, head_fit_common.h).
 //
 // Both GEMM kernels are LDS-tiled with BOTH operands staged (64 x 64 output tile, 16 deep, the next tile's global loads in flight behind the
 // products) and multiply with v_mfma_f64_16x16x4_f64: four waves of 32 x 32, four accumulators each.  Its C/D map is NOT the f32 one: lane l,
@@ -66,8 +69,17 @@ struct WeightedEvalArgs : EvalArgs {
 struct WeightedDistillEvalArgs : DistillEvalArgs {
     const double* scale;
 };
+// ee_mlp_head_fit_gate: K == 2 and y null; err bit 0 is a target that is not finite or lies outside [0,1]
+struct GateEvalArgs : EvalArgs {
+    const double* targets;           // (E,N): c[e][n] = how right classifier(gate input) is at exit e on row n
+};
+// ee_mlp_head_fit_gate_weighted
+struct WeightedGateEvalArgs : GateEvalArgs {
+    const double* scale;
+};
 template <typename Args>
-constexpr bool kWeighted = std::is_same_v<Args, WeightedEvalArgs> || std::is_same_v<Args, WeightedDistillEvalArgs>;
+constexpr bool kWeighted = std::is_same_v<Args, WeightedEvalArgs> || std::is_same_v<Args, WeightedDistillEvalArgs> ||
+                           std::is_same_v<Args, WeightedGateEvalArgs>;
 
 __device__ inline bool stopped(const int* ctrl, int e) { return ctrl && ctrl[e * kCtrlInts + CI_STOP] != 0; }
 
@@ -366,6 +378,45 @@ __global__ __launch_bounds__(kThreads) void mlp_distill_softmax_kernel(Args a) {
     if (sub == 0) a.rowloss[(size_t)e * a.N + row] = scaled<kWeighted<Args>>(l, sc);
 }
 
+// ---- the gate counterpart (ee_mlp_head_fit_gate): the two binary cross-entropies of the gate objective on the row's two logits against the
+// target c[e][n]; D = N dL/dz = (sigmoid(z_j) - t_j) / 2 in place of Z with t_1 = c, t_0 = 1 - c, the row's loss (bce(z_1, c) + bce(z_0, 1 - c)) / 2
+// -- mlp_loss_kernel divides by N, which makes the objective's 1 / (2N).  The rows keep the softmax kernels' place in the grid, eight lanes a
+// row: lane `sub` takes column sub & 1, lanes 0 and 1 write, and the pair's losses meet by one shuffle.  Every lane reads its logit before
+// any of the row writes: they are lanes of one wave.
+// Args: GateEvalArgs, or WeightedGateEvalArgs: as for mlp_softmax_kernel; the target of a row whose scale is zero is not read.
+// grid (ceil(N / kSoftRows), E)
+template <typename Args>
+__global__ __launch_bounds__(kThreads) void mlp_gate_kernel(Args a) {
+    const int e = blockIdx.y, t = threadIdx.x, sub = t & 7, j = sub & 1;
+    if (stopped(a.ctrl, e)) return;
+    const int row = blockIdx.x * kSoftRows + (t >> 3);
+    const bool valid = row < a.N;
+    bool live = valid;
+    double sc = 1.0;
+    if constexpr (kWeighted<Args>) {
+        sc = row_scale(a.scale, e, a.N, row);
+        live = sc != 0.0;                                    // true for a NaN scale too: the error word is raised then
+    }
+    double* Z = a.Z + ((size_t)e * a.N + (valid ? row : 0)) * 2;
+    double c = live ? a.targets[(size_t)e * a.N + row] : 0.0;
+    if (!(c >= 0.0 && c <= 1.0)) {                           // a NaN fails both compares
+        atomicOr(a.err, 1);
+        c = 0.0;
+    }
+    double d;
+    double l = gate_bce(live ? Z[j] : 0.0, j ? c : 1.0 - c, d);
+    l += __shfl_xor(l, 1);
+    if (!valid) return;
+    if constexpr (kWeighted<Args>) {
+        if (!live) {
+            zero_row(Z, a.rowloss + (size_t)e * a.N + row, sub, 2);
+            return;
+        }
+    }
+    if (sub < 2) Z[j] = scaled<kWeighted<Args>>(0.5 * d, sc);
+    if (sub == 0) a.rowloss[(size_t)e * a.N + row] = scaled<kWeighted<Args>>(0.5 * l, sc);
+}
+
 // ---- dA = (D W2) (1 - A^2) in place of A: thread = columns t + 256 i of four rows at a time, so a W2 element serves four rows -----------------
 // grid (ceil(N / kDactRows), E)
 template <int HC>
@@ -431,8 +482,8 @@ size_t params(int H, int K) { return (size_t)H * H + H + (size_t)K * H + K; }
 size_t scratch_bytes(int E, int N, int H, int K) { return sizeof(double) * mlp_head_fit_scratch_doubles(E, N, H, K); }
 
 // one evaluation: L and grad L of every running exit; p.tail: mlp_head_fit_scratch_doubles doubles -- hidden rows, logits, the rows' losses;
-// what o holds picks the softmax kernel and its argument struct: a teacher the distilled objective, weights the weighted form of either,
-// whose row scales (E,N) lie behind the rows' losses
+// what o holds picks the row kernel and its argument struct: gate targets (K == 2) the gate objective, a teacher the distilled one, weights
+// the weighted form of any of the three, whose row scales (E,N) lie behind the rows' losses
 void launch_eval(const FitEvalPoint& p, const float* X, const HeadObjective& o, int E, int N, int H, int K, double l2, hipStream_t s) {
     EvalArgs a{};
     a.X = X; a.y = o.labels; a.theta = p.theta; a.theta_stride = p.theta_stride; a.ctrl = p.ctrl; a.err = p.err;
@@ -446,7 +497,10 @@ void launch_eval(const FitEvalPoint& p, const float* X, const HeadObjective& o, 
     const dim3 sgrid(ceil_div(N, kSoftRows), E);
     const DistillEvalArgs d{a, o.soft.teacher, o.soft.alpha, o.soft.temperature};
     const double* scale = o.weights ? scale_table(p.tail, scratch_bytes(E, N, H, K)) : nullptr;
-    if (scale && d.teacher)
+    const GateEvalArgs g{a, o.gate_targets};
+    if (g.targets && scale) hipLaunchKernelGGL(mlp_gate_kernel<WeightedGateEvalArgs>, sgrid, dim3(kThreads), 0, s, WeightedGateEvalArgs{g, scale});
+    else if (g.targets) hipLaunchKernelGGL(mlp_gate_kernel<GateEvalArgs>, sgrid, dim3(kThreads), 0, s, g);
+    else if (scale && d.teacher)
         hipLaunchKernelGGL(mlp_distill_softmax_kernel<WeightedDistillEvalArgs>, sgrid, dim3(kThreads), 0, s, WeightedDistillEvalArgs{d, scale});
     else if (scale) hipLaunchKernelGGL(mlp_softmax_kernel<WeightedEvalArgs>, sgrid, dim3(kThreads), 0, s, WeightedEvalArgs{a, scale});
     else if (d.teacher) hipLaunchKernelGGL(mlp_distill_softmax_kernel<DistillEvalArgs>, sgrid, dim3(kThreads), 0, s, d);

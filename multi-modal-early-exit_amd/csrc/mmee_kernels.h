@@ -347,7 +347,8 @@ struct HeadObjective {
     const long long* labels = nullptr;       // (N,); null: the distilled objective at alpha = 1, the gate objective
     DistillTargets soft;                     // teacher null: no soft term
     const float* weights = nullptr;          // (E,N) sample weights (ee_*_fit_weighted), or null: every row counts once
-    const double* gate_targets = nullptr;    // (E,N) in [0,1] (ee_head_fit_gate: K == 2, one layer, nothing else given), or null
+    const double* gate_targets = nullptr;    // (E,N) in [0,1] (ee_head_fit_gate, ee_mlp_head_fit_gate: K == 2, no labels, no teacher; the two-layer
+                                             // fit alone takes weights with them), or null
 };
 struct HeadFitArgs : FitArgs {       // E parameter sets; theta0 and theta64 null
     HeadObjective objective;
@@ -370,14 +371,15 @@ void launch_head_lossgrad(const float* X, const HeadObjective& o, const double* 
 // ee_mlp_head_fit (mlp_head_fit.hip): two-layer heads (dense + tanh + out_proj) per exit; theta = W1 (H,H), b1 (H,), W2 (K,H), b2 (K,)
 constexpr int kMlpHeadFitRows = 64;          // the row tile of the GEMM kernels, the largest of the new kernels' tiles (MMEE_MLP_HEAD_FIT_ROWS)
 struct MlpHeadFitArgs : FitArgs {    // E parameter sets; theta0 (E,P) required, theta64 (E,P)
-    HeadObjective objective;         // no gate targets: the gate heads have one layer
+    HeadObjective objective;         // gate targets (ee_mlp_head_fit_gate): K == 2, the two-layer gate heads
     int K;
     float *dense_weight, *dense_bias, *weight, *bias;   // (E,H,H), (E,H), (E,K,H), (E,K)
 };
 size_t mlp_head_fit_workspace_bytes(int E, int N, int H, int K, int history, bool weighted);
 size_t mlp_head_fit_scratch_doubles(int E, int N, int H, int K);
 // false: preparing the workspace failed.  The error word is the first int of the workspace (bit 0: a label outside [0,K); bit 1: a teacher
-// logit that is not finite; bits 2 and 3: the sample weights, as for launch_head_fit).
+// logit that is not finite; bits 2 and 3: the sample weights, as for launch_head_fit; the gate objective: bit 0 is a target that is not finite
+// or outside [0,1]).
 bool launch_mlp_head_fit(const MlpHeadFitArgs& a, hipStream_t s);
 // one evaluation at theta (E,P): loss (E,), grad (E,P); scratch: mlp_head_fit_scratch_doubles doubles, with weights (E,N) E * N doubles
 // more behind them; err: one zeroed int

@@ -32,11 +32,15 @@ objective is not convex: ``status`` 0 is a stationary point reached by descent f
 The 2-way gate heads of the gate strategy -- the heads ``inference_strategy="gate"`` lets decide (include/mmee.h MMEE_CRIT_GATE) -- are fitted
 from the same forwards too (``ee_head_fit_gate``): ``collect_gate_features`` gathers the CLS rows and the gated logits ``classifier(gate
 input)``, ``gate_targets`` turns those and labels into "the classifier is right here", ``fit_gate_heads`` minimises the reference's
-``BCEWithLogitsLoss`` against the one-hot of that (strongly convex: one optimum) and ``GateFit.state_dict`` names the heads.  One-layer gates
-only.
+``BCEWithLogitsLoss`` against the one-hot of that (strongly convex: one optimum) and ``GateFit.state_dict`` names the heads.  That is the
+one-layer gate (``exit_head_num_layers = 1``).  For the default depth of two, ``fit_mlp_gate_heads`` minimises the same loss on
+W2 tanh(W1 x + b1) + b2 (``ee_mlp_head_fit_gate``: the two-layer ramp fit's launches with one row kernel exchanged) from a stated start, and
+``MlpGateFit.state_dict`` names the four tensors per exit.  Like the two-layer ramp objective it is not convex: ``status`` 0 is a stationary
+point reached by descent from the start.  It takes ``sample_weight`` (``ee_mlp_head_fit_gate_weighted``): with ``reach_weights`` gate e is fitted
+on the documents no earlier exit released, the only ones it is ever asked about.
 
-This is not a trainer: two-layer gates, embedding-level exits, the final classifier, per-exit LTE loss weights, mini-batches and an unfrozen backbone
-are out of scope.
+This is not a trainer: distilled gates, sample weights for one-layer gates, embedding-level exits, the final classifier, per-exit LTE loss
+weights, mini-batches and an unfrozen backbone are out of scope.
 
 Reloading heads into an engine that holds captured graphs does not re-capture them: capture again after ``load_weights``.
 """
@@ -76,7 +80,7 @@ def _check_fittable(cfg: ModelConfig, head_layers: int = 1):
     ec = cfg.exit_config
     if str(ec.encoder_layer_strategy) != "ramp":
         raise ValueError("ramp exit heads are fitted for the ramp strategy only: the 2-way heads of a gate configuration are fitted by "
-                         "fit_gate_heads (collect_gate_features, gate_targets)")
+                         "fit_gate_heads, or fit_mlp_gate_heads for two layers (collect_gate_features, gate_targets)")
     if head_layers == 2:
         if ec.exit_head_num_layers != 2:
             raise ValueError("two-layer exit heads are fitted for exit_head_num_layers == 2 only (fit_exit_heads fits the one-layer head)")
@@ -393,10 +397,7 @@ class MlpHeadFit:
 
     def logits(self, features) -> "torch.Tensor":
         """(E,N,K) float64 logits of the float32 heads on ``features`` (E,N,H), on the device."""
-        f64 = torch.float64
-        X = _rows(features, on=self.weight.device)[1].to(f64)
-        A = torch.tanh(torch.baddbmm(self.dense_bias.to(f64).unsqueeze(1), X, self.dense_weight.to(f64).transpose(1, 2)))
-        return torch.baddbmm(self.bias.to(f64).unsqueeze(1), A, self.weight.to(f64).transpose(1, 2))
+        return _mlp_logits(self, features)
 
     def state_dict(self, cfg: ModelConfig) -> Dict[str, np.ndarray]:
         """``{prefix}encoder.early_exits.{k}.dense.weight / .bias`` and ``.out_proj.weight / .bias`` (host float32), ready for
@@ -409,6 +410,15 @@ class MlpHeadFit:
             for name, a in zip(_MLP_BLOCKS, blocks):
                 out[f"{p}encoder.early_exits.{k}.{name}"] = np.ascontiguousarray(a[k])
         return out
+
+
+def _mlp_logits(fit, features):
+    """(E,N,K) float64 logits of the float32 two-layer heads ``fit.dense_weight`` (E,H,H), ``fit.dense_bias`` (E,H), ``fit.weight`` (E,K,H),
+    ``fit.bias`` (E,K) on ``features`` (E,N,H)"""
+    f64 = torch.float64
+    X = _rows(features, on=fit.weight.device)[1].to(f64)
+    A = torch.tanh(torch.baddbmm(fit.dense_bias.to(f64).unsqueeze(1), X, fit.dense_weight.to(f64).transpose(1, 2)))
+    return torch.baddbmm(fit.bias.to(f64).unsqueeze(1), A, fit.weight.to(f64).transpose(1, 2))
 
 
 def _mlp_theta0(init, E, H, K, dev):
@@ -602,14 +612,18 @@ def fit_lte_classifier(features, targets, loss: str = "mse", l2: float = 1e-2, g
 
 
 # ---- 2-way gate heads: the heads inference_strategy = "gate" lets decide ---------------------------------------------------------------------
-def _check_gate_cfg(cfg: ModelConfig):
+def _check_gate_cfg(cfg: ModelConfig, head_layers: int = 1):
     ec = cfg.exit_config
     if cfg.arch == "beit":
         raise ValueError("gate heads are fitted for LayoutLMv3 configurations only")
     if str(ec.encoder_layer_strategy) != "gate":
         raise ValueError("gate heads are fitted for the gate strategy only (encoder_layer_strategy = 'gate'): fit_exit_heads fits ramps")
-    if ec.exit_head_num_layers != 1:
-        raise ValueError("gate heads are fitted for exit_head_num_layers == 1 only: a two-layer gate is not a convex problem and is not built")
+    if head_layers == 2:
+        if ec.exit_head_num_layers != 2:
+            raise ValueError("two-layer gate heads are fitted for exit_head_num_layers == 2 only (fit_gate_heads fits the one-layer gate)")
+    elif ec.exit_head_num_layers != 1:
+        raise ValueError("gate heads are fitted for exit_head_num_layers == 1 only: a two-layer gate is not a convex problem, "
+                         "fit_mlp_gate_heads fits it")
     if ec.embedding_exits:
         raise ValueError(f"embedding-level exits {ec.embedding_exits} cannot be fitted: the forward does not return their pooled inputs")
     if not ec.encoder_exit_layers:
@@ -636,6 +650,14 @@ def gate_targets(gated_logits, labels, device=None) -> "torch.Tensor":
     return 1.0 - lte_targets(gated_logits, labels, device)
 
 
+def _gate_scores(logits):
+    """(E,N) float64 gate scores of the float32 roundings of ``logits`` (E,N,2), by the device function the forward decides with"""
+    from .sweep import gate_table
+    h = logits.to(torch.float32).contiguous()
+    dummy = torch.zeros((h.shape[1], 1), dtype=torch.float64, device=h.device)
+    return gate_table(h, dummy, device=h.device)[:-1]
+
+
 @dataclass
 class GateFit:
     weight: "torch.Tensor"       # (E,2,H) float32, device
@@ -655,10 +677,7 @@ class GateFit:
     def scores(self, features) -> "torch.Tensor":
         """(E,N) float64 gate scores 1 / (1 + exp(h0 - h1)) of the float32 heads' float32 logits on ``features`` (E,N,H), on the device, by the
         device function the forward decides with (``sweep.gate_table``'s rows)."""
-        from .sweep import gate_table
-        h = self.logits(features).to(torch.float32).contiguous()
-        dummy = torch.zeros((h.shape[1], 1), dtype=torch.float64, device=h.device)
-        return gate_table(h, dummy, device=h.device)[:-1]
+        return _gate_scores(self.logits(features))
 
     def state_dict(self, cfg: ModelConfig) -> Dict[str, np.ndarray]:
         """``layoutlmv3.encoder.early_exits.{k}.out_proj.weight`` (2,H) / ``.bias`` (2,) (host float32), ready for ``engine.load_weights`` next
@@ -676,11 +695,12 @@ def fit_gate_heads(features, targets, l2: float = 1e-2, gtol: float = 1e-9, max_
     (``gate_targets``; soft targets are allowed).  Minimises, per exit, (1 / (2N)) sum_n [bce(z_1, c) + bce(z_0, 1 - c)] +
     (l2 / 2)(||W||^2 + ||b||^2) over W (2,H), b (2,) in float64 (include/mmee.h, ee_head_fit_gate): ``nn.BCEWithLogitsLoss()`` on the (N,2)
     gate logits against the one-hot of the target, the reference's gate loss.  Strongly convex: one optimum.  The kernels, the L-BFGS and the
-    budget are ``fit_exit_heads``' at K = 2.  Limits: H <= 1024 and a multiple of 4; ``sample_weight`` is not built for gates and is refused.
+    budget are ``fit_exit_heads``' at K = 2.  Limits: H <= 1024 and a multiple of 4; ``sample_weight`` is not built for one-layer gates and is
+    refused (``fit_mlp_gate_heads``, the two-layer gates' fit, takes it).
 
     Host synchronisation: one wait after the last launch, to read the error word (a target outside [0,1] or not finite fails the call)."""
     if sample_weight is not None:
-        raise ValueError("fit_gate_heads: sample_weight is not built for gate heads (the ramp fits take it)")
+        raise ValueError("fit_gate_heads: sample_weight is not built for one-layer gate heads (the ramp fits and fit_mlp_gate_heads take it)")
     fs = tuple(features.shape)
     if len(fs) not in (2, 3):
         raise ValueError(f"features are {fs}, need (E,N,H), or (N,H) for one exit")
@@ -699,4 +719,84 @@ def fit_gate_heads(features, targets, l2: float = 1e-2, gtol: float = 1e-9, max_
     ws, need = _workspace("ee_head_fit_workspace_bytes", dev, E, N, H, 2, history)
     _call("ee_head_fit_gate", dev, X, T, E, N, H, float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.weight, fit.bias,
           fit.weight64, fit.bias64, fit.loss, fit.grad_norm, fit.evals, fit.status)
+    return fit
+
+
+# ---- two-layer 2-way gate heads: dense + tanh + out_proj (2,H), the default depth --------------------------------------------------------------
+@dataclass
+class MlpGateFit:
+    dense_weight: "torch.Tensor"  # (E,H,H) float32, device: W1 [out,in]
+    dense_bias: "torch.Tensor"    # (E,H)
+    weight: "torch.Tensor"        # (E,2,H): out_proj; row 1 is "correctly gated"
+    bias: "torch.Tensor"          # (E,2)
+    theta64: "torch.Tensor"       # (E,P) float64: W1 row-major, b1, W2 row-major, b2 -- the point the float32 tensors are rounded from
+    loss: "torch.Tensor"          # (E,) float64: the objective at the returned point
+    grad_norm: "torch.Tensor"     # (E,) float64
+    evals: "torch.Tensor"         # (E,) int32
+    status: "torch.Tensor"        # (E,) int32: 0 stationary (grad_norm <= gtol), 1 max_evals, 2 the line search made no progress
+    l2: float
+
+    def logits(self, features) -> "torch.Tensor":
+        """(E,N,2) float64 gate logits of the float32 heads on ``features`` (E,N,H), on the device."""
+        return _mlp_logits(self, features)
+
+    def scores(self, features) -> "torch.Tensor":
+        """(E,N) float64 gate scores of the float32 heads' float32 logits on ``features`` (E,N,H), as ``GateFit.scores``."""
+        return _gate_scores(self.logits(features))
+
+    def state_dict(self, cfg: ModelConfig) -> Dict[str, np.ndarray]:
+        """``layoutlmv3.encoder.early_exits.{k}.dense.weight`` (H,H) / ``.dense.bias`` (H,) / ``.out_proj.weight`` (2,H) / ``.out_proj.bias`` (2,)
+        (host float32), ready for ``engine.load_weights`` next to the backbone's tensors."""
+        _check_gate_cfg(cfg, 2)
+        E, K, H = self.weight.shape
+        if E != len(cfg.exit_config.encoder_exit_layers) or K != 2 or H != cfg.hidden_size:
+            raise ValueError(f"the fit is (E,2,H) = {(E, K, H)}, the configuration wants {(len(cfg.exit_config.encoder_exit_layers), 2, cfg.hidden_size)}")
+        blocks = [t.cpu().numpy() for t in (self.dense_weight, self.dense_bias, self.weight, self.bias)]
+        return {f"layoutlmv3.encoder.early_exits.{k}.{name}": np.ascontiguousarray(a[k]) for k in range(E) for name, a in zip(_MLP_BLOCKS, blocks)}
+
+
+def fit_mlp_gate_heads(features, targets, l2: float = 1e-2, gtol: float = 1e-6, max_evals: int = 4000, history: int = 8, init="identity",
+                       device=None, sample_weight=None) -> MlpGateFit:
+    """Two-layer gate heads (dense + tanh + out_proj (2,H)) per exit.  ``features`` (E,N,H) float32 (numpy or device tensor; (N,H) is one exit;
+    ``collect_gate_features``), ``targets`` (E,N) in [0,1] (``gate_targets``; soft targets are allowed).  Minimises, per exit,
+    (1 / (2N)) sum_n [bce(z_1, c) + bce(z_0, 1 - c)] + (l2 / 2) ||theta||^2 with z = W2 tanh(W1 x + b1) + b2, in float64 (include/mmee.h,
+    ee_mlp_head_fit_gate): ``fit_gate_heads``' loss on ``fit_mlp_exit_heads``' head at K = 2, by the same L-BFGS.  Limits: H <= 1024 and a
+    multiple of 4.
+
+    ``init`` is ``fit_mlp_exit_heads``' at K = 2: ``"identity"`` (W1 = I, everything else 0: the one-layer gate on tanh(x)), an (E,P) array or
+    tensor, or a mapping holding a checkpoint's four tensors per exit (a warm start).  The objective is not convex: ``status`` 0 says the
+    gradient norm of the returned point is <= ``gtol``, a stationary point reached by descent from ``init``; budget as ``fit_mlp_exit_heads``.
+
+    ``sample_weight``: ``None`` (``ee_mlp_head_fit_gate``), (N,) or (E,N) as for the ramp fits (``ee_mlp_head_fit_gate_weighted``): the mean
+    becomes the weighted mean.  ``reach_weights(exits, E)`` of a policy scan fits gate e on the documents that reach it.  The target of a row of
+    weight zero is not looked at; a weight that is negative or not finite, or an exit whose weights sum to zero, fails the call.
+
+    Host synchronisation: one wait after the last launch, to read the error word (a target outside [0,1] or not finite fails the call)."""
+    fs = tuple(features.shape)
+    if len(fs) not in (2, 3):
+        raise ValueError(f"features are {fs}, need (E,N,H), or (N,H) for one exit")
+    E, N, H = (1,) + fs if len(fs) == 2 else fs
+    if H > 1024 or H % 4:
+        raise ValueError(f"fit_mlp_gate_heads: H = {H}, need H <= 1024 and a multiple of 4")
+    ts = tuple(np.shape(targets))
+    if ts != (E, N) and not (E == 1 and ts == (N,)):
+        raise ValueError(f"targets are {ts}, need (E,N) = {(E, N)}")
+    if not l2 > 0.0:
+        raise ValueError(f"fit_mlp_gate_heads: l2 = {l2}, need l2 > 0")
+    _weight_shape(features, sample_weight)
+    capi.load()
+    dev, X = _rows(features, device)
+    T = _to_device(targets, torch.float64, dev).view(E, N)
+    theta0 = _mlp_theta0(init, E, H, 2, dev)
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+    fit = MlpGateFit(z((E, H, H), torch.float32), z((E, H), torch.float32), z((E, 2, H), torch.float32), z((E, 2), torch.float32),
+                     z((E, mlp_param_count(H, 2)), torch.float64), z((E,), torch.float64), z((E,), torch.float64), z((E,), torch.int32),
+                     torch.full((E,), -1, dtype=torch.int32, device=dev), float(l2))
+    if sample_weight is None:
+        name, query, lead = "ee_mlp_head_fit_gate", "ee_mlp_head_fit_workspace_bytes", (X, T)
+    else:
+        name, query, lead = "ee_mlp_head_fit_gate_weighted", "ee_mlp_head_fit_weighted_workspace_bytes", (X, T, _weights(sample_weight, dev, E, N))
+    ws, need = _workspace(query, dev, E, N, H, 2, history)
+    _call(name, dev, *lead, theta0, E, N, H, float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.dense_weight, fit.dense_bias,
+          fit.weight, fit.bias, fit.theta64, fit.loss, fit.grad_norm, fit.evals, fit.status)
     return fit
