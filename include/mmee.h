@@ -962,8 +962,12 @@ int ee_debug_mlp_head_gate_weighted_lossgrad(const float* features, const double
  * ee_preprocess_images: B raw page images -> pixel_values (B,3,R,R) float32.  `images` dev uint8: the images packed back to
  *   back, each HWC RGB (c = 3) or HW greyscale (c = 1, replicated to 3 channels like Image.convert("RGB")); `desc` dev array
  *   of B records {int64 offset; int32 h, w, c, pad}.  Resize = Pillow Image.resize(BILINEAR) bit for bit, then HF rescale
- *   (1/255) and normalise (mean = std = 0.5).  in/out size ratio must be <= 31.  `workspace` dev scratch of
+ *   (1/255) and normalise (mean = std = 0.5).  `workspace` dev scratch of
  *   ee_preprocess_workspace_bytes(B, R, max_h) bytes (max_h = largest image height).  resized_u8 (B,R,R,3) optional.
+ *   The caller's duty: every side h, w of every image is in [1, 31 R], every h <= max_h, and every image lies inside `images` (any byte
+ *   offset; no alignment is needed).  The descriptors are on the device, so the entry point cannot check them; a side above 31 R needs
+ *   more than the 64 filter taps the tables hold per output pixel, the taps are cut off and the pixels are wrong WITHOUT an error (the
+ *   package's feed.preprocess_images / DeviceFeeder check the sides on the host and raise).  max_h <= 31 R is checked here.
  * ee_collate_pad: ragged token streams (ids dev int64 [total], boxes dev int64 [total,4], offsets dev int64 [B+1]) ->
  *   max_length tensors (B,T): input_ids padded with pad_id, attention_mask, bbox padded with zeros; longer inputs truncated.
  */
@@ -1193,6 +1197,27 @@ typedef struct ee_debug_rows_out_args {
 int ee_debug_head_out(const ee_debug_head_out_args* args, void* stream);
 int ee_debug_exit_decide(const ee_debug_exit_decide_args* args, void* stream);
 int ee_debug_rows_out(const ee_debug_rows_out_args* args, void* stream);
+
+/* Unit-test hook of the patch projection (Conv2d with kernel = stride = patch as a GEMM over flattened patches), the counterpart of
+ * ee_debug_attention: what patch_projection() of the forward launches, on caller-provided DEVICE buffers; no handle.
+ *   pixel_values   f32 [B][C][R][R]; weight f32 [H][C P P] (k = (c, ky, kx), as Conv2d's weight flattens); bias f32 [H]
+ *   form           0 = the f32 GEMM with the LDS-DMA kernel (what an MMEE_PREC_F32 forward runs), 1 = the f32 GEMM with the register-staged
+ *                  kernel, 2 = split precision: launch_patch_split writes the patches as split-f16 rows scaled by 16, the weight becomes split
+ *                  rows with ee_finalize's per-tensor scale, and the split GEMM multiplies them
+ *   out            f32 [B (R / P)^2][H]: row b (R / P)^2 + gy (R / P) + gx = patch (gy, gx) of image b; rows past that keep their bytes
+ *   a_split_out    NULL, or (form 2) [B (R / P)^2][C P P] 32-bit words: the split rows (64-byte groups [hi 16 f16 | lo 16 f16]) are
+ *                  written here instead of into scratch, and the GEMM reads them from here
+ *   err_flag_out   host int32: the kernels' error word (16 = a pixel left the range of the split planes)
+ * Refused, not launched: NULL pointers, B < 1; a geometry ee_create refuses (R % P, P % 4, R % 4, C P P % 32); more than 2^24 rows;
+ * H % 128 or H > 1024; form outside 0..2; form 2 with H % 256; a_split_out with form 0 or 1.  Synchronises the stream. */
+typedef struct ee_debug_patch_project_args {
+    const float *pixel_values, *weight, *bias;
+    int32_t B, C, R, P, H, form;
+    float* out;
+    void* a_split_out;
+    int32_t* err_flag_out;
+} ee_debug_patch_project_args;
+int ee_debug_patch_project(const ee_debug_patch_project_args* args, void* stream);
 
 /* Diagnostic of the two-heads-per-item attention kernel (attention_pair.hip): with MMEE_ATTN_STAMPS=1 in the environment the
  * launches run a build with in-kernel s_memtime stamps; this call synchronises, copies the eight phase sums (shader cycles summed over

@@ -116,6 +116,12 @@ class DebugRowsOutArgs(C.Structure):
                 + [(n, _vp) for n in ("text_dst", "ntext", "doc_off", "out")] + [("out_rows", _i32)])
 
 
+class DebugPatchProjectArgs(C.Structure):
+    """ee_debug_patch_project_args of include/mmee.h: device pointers (or None) and sizes."""
+    _fields_ = ([(n, _vp) for n in ("pixel_values", "weight", "bias")] + [(n, _i32) for n in ("B", "C", "R", "P", "H", "form")]
+                + [(n, _vp) for n in ("out", "a_split_out")] + [("err_flag_out", C.POINTER(_i32))])
+
+
 SYMBOLS = {
     "ee_create": (C.c_int, [C.POINTER(EEConfig), C.POINTER(_vp)]),
     "ee_destroy": (C.c_int, [_vp]),
@@ -182,6 +188,7 @@ SYMBOLS = {
     "ee_debug_head_out": (C.c_int, [C.POINTER(DebugHeadOutArgs), _vp]),
     "ee_debug_exit_decide": (C.c_int, [C.POINTER(DebugExitDecideArgs), _vp]),
     "ee_debug_rows_out": (C.c_int, [C.POINTER(DebugRowsOutArgs), _vp]),
+    "ee_debug_patch_project": (C.c_int, [C.POINTER(DebugPatchProjectArgs), _vp]),
     "ee_temperature_fit": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ee_head_fit": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _vp]),

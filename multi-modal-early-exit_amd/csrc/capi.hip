@@ -91,6 +91,19 @@ void bucket_lut_host(int num_buckets, int max_distance, int max_delta, unsigned 
     }
 }
 
+// per-tensor power-of-two scale by split_weight_exponent (capi_internal.h)
+int split_weight_rows(ee_handle* h, const char* who, const float* w, int N, int K, float* out, float* absmax_dev, int num_cus, hipStream_t s, float* inv) {
+    mmee::launch_absmax(w, (size_t)N * K, absmax_dev, s);
+    float mx = 0.f;
+    if (hipMemcpyAsync(&mx, absmax_dev, sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return fail(h, "%s: the maximum of a weight tensor could not be read", who);
+    if (!(mx < 3.0e38f)) return fail(h, "%s: a weight tensor holds inf/nan", who);
+    const int e = split_weight_exponent(mx);
+    *inv = std::ldexp(1.0f, -e);
+    mmee::launch_split_rows(w, out, nullptr, N, N, K, std::ldexp(1.0f, e), num_cus, s);
+    return 0;
+}
+
 }  // namespace capi
 }  // namespace mmee
 
@@ -129,8 +142,7 @@ int check_config(const ee_config& c) {
     if (!beit && 4 * c.coordinate_size + 2 * c.shape_size != H) return fail(nullptr, "4*coordinate_size + 2*shape_size != hidden_size");
     if (beit && c.n_embedding_exits) return fail(nullptr, "the BEiT / DiT variant has encoder-layer exits only");
     if (beit && !c.use_mean_pooling) return fail(nullptr, "BEiT / DiT: only use_mean_pooling = 1 is built");
-    if (c.input_size % c.patch_size || (c.num_channels * c.patch_size * c.patch_size) % 32 || c.patch_size % 4 || c.input_size % 4)
-        return fail(nullptr, "unsupported patch geometry");
+    if (!patch_geometry_ok(c.num_channels, c.input_size, c.patch_size)) return fail(nullptr, "unsupported patch geometry");
     if (K < 1 || K > 64) return fail(nullptr, "num_labels must be in [1,64]");
     if (c.n_embedding_exits < 0 || c.n_embedding_exits > 3 || c.n_encoder_exits < 0 || c.n_encoder_exits > MMEE_MAX_ENCODER_EXITS)
         return fail(nullptr, "bad exit counts");
@@ -399,15 +411,7 @@ int report_missing(ee_handle* h) {
 // sits near 5, its lo plane well inside the f16 normal range)
 int build_split(ee_handle* h, const float* w, int N, int K, float** out, float* inv) {
     if (!*out && dev_alloc(h, out, (size_t)N * K)) return 1;
-    mmee::launch_absmax(w, (size_t)N * K, h->absmax_dev, nullptr);
-    float mx = 0.f;
-    HIP_OK(h, hipMemcpy(&mx, h->absmax_dev, sizeof(float), hipMemcpyDeviceToHost));
-    if (!(mx < 3.0e38f)) return fail(h, "ee_finalize: a weight tensor holds inf/nan");
-    const int e = split_weight_exponent(mx);
-    const float scale = std::ldexp(1.0f, e);
-    *inv = std::ldexp(1.0f, -e);
-    mmee::launch_split_rows(w, *out, nullptr, N, N, K, scale, h->num_cus, nullptr);
-    return 0;
+    return split_weight_rows(h, "ee_finalize", w, N, K, *out, h->absmax_dev, h->num_cus, nullptr, inv);
 }
 
 // ee_finalize, step 2 (MMEE_PREC_F32_SPLIT): split-f16 rows of the four big weights of every layer, of the heads' dense layers and of the

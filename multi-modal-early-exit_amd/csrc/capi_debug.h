@@ -1,5 +1,5 @@
 // What the ee_debug_* hooks that run one kernel of the path on caller-provided device buffers share (capi_debug_attention.hip,
-// capi_debug_rows.hip, capi_debug_xprobe.hip, capi_debug_exit.hip; the GEMM hooks of capi_tools.hip take the device query and to_host).  Host code with internal linkage:
+// capi_debug_rows.hip, capi_debug_xprobe.hip, capi_debug_exit.hip, capi_debug_patch.hip; the GEMM hooks of capi_tools.hip take the device query and to_host).  Host code with internal linkage:
 // the library exports none of it.  What every hook words alike is worded here; the refusals of a document table keep each hook's own words.
 #pragma once
 #include "capi_internal.h"
@@ -16,6 +16,13 @@ namespace {
 // the refusals every hook words alike
 constexpr const char* kScratchFailed = "%s: hipMalloc of the scratch failed";
 constexpr const char* kUploadFailed = "%s: host-to-device copy failed";
+
+// the hidden sizes ee_create takes: the multiples of 128 up to 1024 (the row kernels hold a row as ceil(H / 256) x 4 floats per lane, the f32
+// GEMM writes 128 columns per tile)
+int check_hidden(const char* who, int H) {
+    if (H < 128 || H > 1024 || H % 128 != 0) return fail(nullptr, "%s: hidden size %d is not a multiple of 128 in [128, 1024]", who, H);
+    return 0;
+}
 
 // the device's CU count; 0 (and the error message of `who` set) when its properties cannot be read
 int device_cus(const char* who) {

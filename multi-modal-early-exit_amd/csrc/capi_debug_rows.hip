@@ -9,12 +9,6 @@ using namespace mmee::capi;
 
 namespace {
 
-// the row kernels hold a row as ceil(H / 256) x 4 floats per lane; ee_create takes the multiples of 128 up to 1024
-int check_hidden(const char* who, int H) {
-    if (H < 128 || H > 1024 || H % 128 != 0) return fail(nullptr, "%s: hidden size %d is not a multiple of 128 in [128, 1024]", who, H);
-    return 0;
-}
-
 // what launch_prep reads and the sizes it writes by
 int check_prep(const char* who, const void* input_ids, const void* bbox, int B, int T, int G, int pad_id, int vocab, int max_2d, int max_pos,
                int type_vocab) {

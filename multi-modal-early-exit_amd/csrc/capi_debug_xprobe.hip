@@ -1,7 +1,7 @@
 // ee_debug_xprobe: the X-space CLS probe of xprobe.hip alone, on caller-provided device buffers; no handle.  The entry point makes the
 // calls layer_probe() of capi_forward.hip makes for an X-space layer (launch_xprobe) and what feeds it: the row metadata and pair index of
 // the stage-0 batch as ee_forward builds them (launch_pair_index; launch_pair_index16 in the diagnostic library, where the forward can pick
-// it) and the split-f16 rows of the value weight as ee_finalize builds them (the scale rule of build_split).  No kernel is defined here; what
+// it) and the split-f16 rows of the value weight as ee_finalize builds them (split_weight_rows).  No kernel is defined here; what
 // xprobe_supports() refuses is refused, not launched, and so is every row, document or offset outside the caller's buffers.  It
 // synchronises and hands the kernels' error word to a host int32.  tests/test_gpu_xprobe.py drives it against tests/xprobe_ref.py.
 #include "capi_debug.h"
@@ -104,14 +104,8 @@ int ee_debug_xprobe(const ee_debug_xprobe_args* a, int32_t* err_flag_out, void* 
 #endif
     }
     // the value weight as split-f16 rows, with ee_finalize's per-tensor scale
-    launch_absmax(a->wv, (size_t)H * H, absmax, s);
-    float mx = 0.f;
-    if (hipMemcpyAsync(&mx, absmax, sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return fail(nullptr, "%s: the maximum of wv could not be read", who);
-    if (!(mx < 3.0e38f)) return fail(nullptr, "%s: wv holds inf/nan", who);
-    const int e = split_weight_exponent(mx);
-    launch_split_rows(a->wv, wv_s, nullptr, H, H, H, std::ldexp(1.0f, e), dev_cus, s);
-    xa.wv_s = wv_s; xa.wv_inv = std::ldexp(1.0f, -e);
+    if (int rc = split_weight_rows(nullptr, who, a->wv, H, H, wv_s, absmax, dev_cus, s, &xa.wv_inv)) return rc;
+    xa.wv_s = wv_s;
     xa.pair_idx = pair_idx; xa.counts = counts; xa.err_flag = err_flag;
     xa.u = u; xa.s0 = s0; xa.cvec = cvec; xa.order = order; xa.ticket = ticket;
     launch_xprobe(xa, max_docs, max_len, cus, s);

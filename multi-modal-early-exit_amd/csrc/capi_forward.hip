@@ -13,6 +13,35 @@ using namespace mmee::capi;
 
 namespace {
 
+// the fields every GEMM of the forward shares; a launch sets its own on top
+GemmArgs forward_gemm_args(int* err_flag) {
+    GemmArgs g{};
+    g.scale = 1.f; g.prio_mode = 1; g.err_flag = err_flag;
+    return g;
+}
+
+}  // namespace
+
+void mmee::capi::launch_patch_projection(const PatchProjection& p, int num_cus, hipStream_t s, ee_handle* prof) {
+    const int G = p.R / p.P, M = p.B * G * G;
+    GemmArgs pg = forward_gemm_args(p.err_flag);
+    pg.bias = p.bias; pg.C = p.out; pg.ldc = p.H; pg.m_static = M; pg.N = p.H;
+    pg.K = p.C * p.P * p.P; pg.tile_counter = p.tile_counter;
+    if (p.w_split) {
+        auto split = [&] { mmee::launch_patch_split(p.pix, p.split_rows, p.B, p.C, p.R, p.P, mmee::kSplitScaleX, num_cus, s, p.err_flag); };
+        if (prof) { ProfScope pp(prof, P_PSPLIT, s); split(); }
+        else split();
+        pg.A = p.split_rows; pg.lda = pg.K; pg.W = p.w_split; pg.alpha = p.w_inv / mmee::kSplitScaleX;
+        launch_gemm_split(pg, EPI_BIAS, M, num_cus, s);
+        return;
+    }
+    pg.W = p.w; pg.use_dma = p.use_dma;
+    pg.pix = p.pix; pg.C_in = p.C; pg.R = p.R; pg.P = p.P; pg.G = G;
+    launch_gemm_f32(pg, EPI_BIAS, AMODE_IM2COL, M, num_cus, s);
+}
+
+namespace {
+
 __global__ void zero_words_kernel(int* __restrict__ a, int na, int* __restrict__ b, int nb) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < na + nb; i += gridDim.x * blockDim.x) {
         if (i < na) a[i] = 0;
@@ -180,12 +209,7 @@ struct Forward {
         return p;
     }
 
-    // the fields every GEMM of the forward shares; a launch sets its own on top
-    GemmArgs gemm_args() const {
-        GemmArgs g{};
-        g.scale = 1.f; g.prio_mode = 1; g.err_flag = h->err_flag;
-        return g;
-    }
+    GemmArgs gemm_args() const { return forward_gemm_args(h->err_flag); }
 
     void run_gemm(GemmArgs g, int epi) {
         g.terms = one_term ? 1 : 3;
@@ -242,23 +266,16 @@ struct Forward {
     const float* x_out() const { return x_split ? h->Xs : h->X; }
     float x_inv() const { return x_split ? 1.0f / mmee::kSplitScaleX : 0.f; }
 
-    // patch projection (Conv2d with stride = kernel = a GEMM over flattened patches, HF:75-81) -> vis_raw [B * NP][H].  Split mode:
-    // the patches are written once as split rows (into H1, idle until the first FFN) and the split kernel runs the GEMM; otherwise
-    // the f32 kernel gathers the patches itself.
+    // patch projection -> vis_raw [B * NP][H] (launch_patch_projection).  Split mode: the split patches are staged in H1, idle until the
+    // first FFN.
     void patch_projection() {
         ProfScope ps(h, P_GPATCH, s);
-        GemmArgs pg = gemm_args();
-        pg.bias = h->patch_b; pg.C = h->vis_raw; pg.ldc = H; pg.m_static = B * NP; pg.N = H;
-        pg.K = c.num_channels * c.patch_size * c.patch_size; pg.tile_counter = next_head();
-        if (sp && h->patch_s) {
-            { ProfScope pp(h, P_PSPLIT, s); mmee::launch_patch_split(a.pixel_values, h->H1, B, c.num_channels, c.input_size, c.patch_size, mmee::kSplitScaleX, cus, s, h->err_flag); }
-            pg.A = h->H1; pg.lda = pg.K; pg.W = h->patch_s; pg.alpha = h->patch_inv / mmee::kSplitScaleX;
-            launch_gemm_split(pg, EPI_BIAS, B * NP, cus, s);
-            return;
-        }
-        pg.W = h->patch_w;
-        pg.pix = a.pixel_values; pg.C_in = c.num_channels; pg.R = c.input_size; pg.P = c.patch_size; pg.G = G;
-        launch_gemm_f32(pg, EPI_BIAS, AMODE_IM2COL, B * NP, cus, s);
+        PatchProjection p{};
+        p.pix = a.pixel_values; p.B = B; p.C = c.num_channels; p.R = c.input_size; p.P = c.patch_size; p.H = H;
+        p.w = h->patch_w; p.bias = h->patch_b; p.out = h->vis_raw;
+        if (sp && h->patch_s) { p.w_split = h->patch_s; p.w_inv = h->patch_inv; p.split_rows = h->H1; }
+        p.tile_counter = next_head(); p.err_flag = h->err_flag;
+        launch_patch_projection(p, cus, s, h);
     }
 
     // ---- BEiT / DiT: uniform 197-row documents, BeitEmbeddings = patch conv + cls + absolute position embeddings ----

@@ -4,8 +4,9 @@
 //   capi_forward.hip  the forward schedule (Forward, ee_forward) and its captured-graph form (ee_graph_*)
 //   capi_query.hip    what reads the last forward back or arms the next one (ee_profile*, ee_stream_next, ee_last_*, ee_suggest_probe_mask, ee_set_*)
 //   capi_tools.hip    entry points that never see a handle (clock stamps, policy sweeps, pack / unpack, image feed, the GEMM micro-benchmarks)
-//   capi_debug_attention.hip, capi_debug_rows.hip, capi_debug_xprobe.hip, capi_debug_exit.hip   the ee_debug_* hooks of the attention kernels, of the
-//                     row kernels, of the X-space CLS probe and of the exit stage; what only they share is in capi_debug.h
+//   capi_debug_attention.hip, capi_debug_rows.hip, capi_debug_xprobe.hip, capi_debug_exit.hip, capi_debug_patch.hip   the ee_debug_* hooks of the
+//                     attention kernels, of the row kernels, of the X-space CLS probe, of the exit stage and of the patch projection; what only
+//                     they share is in capi_debug.h
 //   capi_fit.hip      the device fits, no handle either (ee_head_fit, ee_mlp_head_fit, ee_lte_*, ee_debug_*_lossgrad)
 #pragma once
 #include <algorithm>
@@ -221,7 +222,7 @@ inline bool have_device(const char* who) {
     return false;
 }
 
-// The per-tensor scale of a weight's split-f16 rows (build_split under ee_finalize; ee_debug_xprobe): 2^e with the e that puts max |w| in
+// The per-tensor scale of a weight's split-f16 rows (split_weight_rows): 2^e with the e that puts max |w| in
 // [2^12, 2^13), capped at 8 (typical |w| ~ 0.02 then sits near 5, its lo plane well inside the f16 normal range); 8 for an all-zero tensor.
 inline int split_weight_exponent(float mx) {
     if (!(mx > 0.f)) return 8;
@@ -229,6 +230,31 @@ inline int split_weight_exponent(float mx) {
     (void)std::frexp(mx, &ex);            // mx = m * 2^ex, m in [0.5, 1)
     return std::min(8, 13 - ex);
 }
+
+// One weight [N][K] as split-f16 rows in `out` with that scale, and 1 / scale in *inv (capi.hip; build_split under ee_finalize,
+// ee_debug_xprobe and ee_debug_patch_project).  absmax_dev: one device float of scratch.  Synchronises s.  0, or the refusal in the name of `who`.
+int split_weight_rows(ee_handle* h, const char* who, const float* w, int N, int K, float* out, float* absmax_dev, int num_cus, hipStream_t s, float* inv);
+
+// The patch geometries the kernels take (ee_create, ee_debug_patch_project): whole patches, and float4 loads that stay inside one pixel
+// row of one patch (P % 4, R % 4) over k-slabs of 32 (C P P % 32).
+inline bool patch_geometry_ok(int C, int R, int P) { return C >= 1 && R >= 1 && P >= 1 && R % P == 0 && (C * P * P) % 32 == 0 && P % 4 == 0 && R % 4 == 0; }
+
+// The patch projection (Conv2d with stride = kernel = a GEMM over flattened patches, HF:75-81): out [B * NP][H] = patches W^T + bias, as
+// ee_forward and ee_debug_patch_project launch it (capi_forward.hip).  w_split given: launch_patch_split writes the patches once as split rows
+// scaled by kSplitScaleX into split_rows ([B * NP][C P P] words) and the split kernel runs the GEMM; otherwise the f32 kernel gathers the
+// patches itself.  prof: the handle whose ee_profile times the split launch, or null.
+struct PatchProjection {
+    const float* pix;                // [B][C][R][R]
+    int B, C, R, P, H;
+    const float *w, *bias;           // [H][C P P], [H]
+    const float* w_split;            // split-f16 rows of w, or null
+    float w_inv;                     //   and 1 / their scale
+    float* split_rows;
+    float* out;
+    int use_dma;                     // GemmArgs::use_dma of the f32 form
+    int *tile_counter, *err_flag;
+};
+void launch_patch_projection(const PatchProjection& p, int num_cus, hipStream_t s, ee_handle* prof);
 
 // Device scratch of one entry point (the ee_debug_* hooks, ee_lte_targets): zeroed hipMalloc, freed on every way out of the scope.
 struct Scratch {

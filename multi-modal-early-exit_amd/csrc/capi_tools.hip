@@ -381,6 +381,10 @@ int ee_preprocess_images(const uint8_t* images, const void* desc, int32_t B, int
                          size_t workspace_bytes, float* pixel_values, uint8_t* resized_u8, void* stream) {
     constexpr int KMAX = 64;
     if (!images || !desc || !workspace || !pixel_values || B < 1 || R < 1 || max_h < 1) return fail(nullptr, "ee_preprocess_images: bad argument");
+    // the one side the host can see: a taller page needs more than KMAX taps per output pixel (the widths are the caller's duty, include/mmee.h)
+    if ((long long)max_h > (long long)((KMAX - 1) / 2) * R)
+        return fail(nullptr, "ee_preprocess_images: max_h %d is above %d R = %lld (the tap tables hold %d taps per output pixel)", max_h, (KMAX - 1) / 2,
+                    (long long)((KMAX - 1) / 2) * R, KMAX);
     if (!have_device("ee_preprocess_images")) return 1;
     // workspace layout: lut[256] f32 | bounds[B*2*R] int2 | kk[B*2*R*KMAX] int | tmp[B*max_h*R*3] u8
     const size_t o_lut = 0, o_b = 1024, o_k = o_b + sizeof(int2) * (size_t)B * 2 * R;

@@ -200,8 +200,8 @@ __global__ __launch_bounds__(256, GEMM_WGS) void gemm_f32_kernel(const GemmArgs 
                 const int np = g.G * g.G;
                 const int b = r / np, p = r - b * np;
                 const int py = p / g.G, px = p - py * g.G;
-                // k = ld_c4 + k0 with k0 a multiple of 32: c = k / P^2, ky = (k % P^2) / P, kx = k % P; kx is fixed
-                a_ptr[i] = g.pix + (size_t)b * g.C_in * g.R * g.R + (size_t)(py * g.P) * g.R + px * g.P + (ld_c4 % g.P);
+                // the patch's first pixel; k = ld_c4 + k0 adds (c, ky, kx) per stage (load_stage): kx changes from slab to slab unless P divides 32
+                a_ptr[i] = g.pix + (size_t)b * g.C_in * g.R * g.R + (size_t)(py * g.P) * g.R + px * g.P;
             }
             w_ptr[i] = g.W + (size_t)(n0 + ld_row + LD_RPP * i) * g.K + ld_c4;
         }
@@ -215,8 +215,8 @@ __global__ __launch_bounds__(256, GEMM_WGS) void gemm_f32_kernel(const GemmArgs 
                 const int k = k0 + ld_c4;
                 const int pp = g.P * g.P;
                 const int c = k / pp, rem = k - c * pp;
-                const int ky = rem / g.P;
-                a_off = (size_t)c * g.R * g.R + (size_t)ky * g.R;
+                const int ky = rem / g.P, kx = rem - ky * g.P;      // c = k / P^2, ky = (k % P^2) / P, kx = k % P
+                a_off = (size_t)c * g.R * g.R + (size_t)ky * g.R + kx;
             }
 #pragma unroll
             for (int i = 0; i < LD_NP; ++i) ra[i] = *reinterpret_cast<const f32x4*>(a_ptr[i] + a_off);

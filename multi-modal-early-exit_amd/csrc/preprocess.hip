@@ -4,7 +4,9 @@
 //               normalize_coeffs_8bpc, ImagingResampleHorizontal_8bpc, ImagingResampleVertical_8bpc) — the resampler behind
 //               the HF LayoutLMv3 image processor the reference builds (EE/models/LayoutLMv3.py:674-677) and applies in
 //               EE/data/RVL_CDIP.py:246-262.  Antialiased triangle filter with support max(in/out, 1), 22-bit fixed-point
-//               weights, each pass rounded to 8 bits: reproduced bit for bit (coefficients in float64 like Pillow).
+//               weights, each pass rounded to 8 bits: reproduced bit for bit (coefficients in float64 like Pillow).  The passes run
+//               in Pillow's order: horizontal then vertical, but vertical FIRST for a page more than 100 times as tall as wide that
+//               shrinks vertically (Image.resize makes two calls for it, PIL/Image.py; the rounding between the passes shows the order).
 //   * rescale / normalise: uint8 -> float32 through a 256-entry table built on the host exactly as HF does
 //               (u * (1/255) in float64 -> float32, then (v - 0.5f) / 0.5f).
 //   * collate : DataCollatorWithPadding(padding="max_length") of EE/utils.py:93-98: pad input_ids with <pad>,
@@ -57,13 +59,42 @@ __device__ __forceinline__ unsigned char clip8(int v) {
     return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
-// horizontal pass: tmp[doc][y][xx][c] (uint8, row stride R*3, plane stride max_h*R*3)
-__global__ __launch_bounds__(256) void resize_horizontal_kernel(const unsigned char* __restrict__ images, const ImageDesc* __restrict__ desc,
+// Image.resize's rule for the vertical pass first (uniform over a document's blocks)
+__device__ __forceinline__ bool vertical_first(const ImageDesc& d, int R) { return (long long)d.h > 100ll * d.w && R < d.h; }
+
+// first pass.  Horizontal: tmp[doc][y][xx][c] (uint8, row stride R*3, plane stride max_h*R*3).  A vertical-first page: the vertical pass
+// straight from the page, tmp[doc][yy][x][c] with row stride w*3 (R rows of w < h / 100 pixels: inside the same plane)
+__global__ __launch_bounds__(256) void resize_first_pass_kernel(const unsigned char* __restrict__ images, const ImageDesc* __restrict__ desc,
                                                                 int R, int KMAX, int max_h, const int2* __restrict__ bounds,
                                                                 const int* __restrict__ kk, unsigned char* __restrict__ tmp) {
     const int doc = blockIdx.y;
     const ImageDesc d = desc[doc];
     const unsigned char* img = images + d.offset;
+    if (vertical_first(d, R)) {
+        const int total = R * d.w;
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+            const int yy = i / d.w, x = i - yy * d.w;
+            const int2 b = bounds[(size_t)(doc * 2 + 1) * R + yy];
+            const int* k = kk + ((size_t)(doc * 2 + 1) * R + yy) * KMAX;
+            unsigned char* o = tmp + (size_t)doc * max_h * R * 3 + ((size_t)yy * d.w + x) * 3;
+            int s0 = 1 << (kPrecisionBits - 1), s1 = s0, s2 = s0;
+            if (d.c == 1) {
+                const unsigned char* p = img + (size_t)b.x * d.w + x;
+                for (int y = 0; y < b.y; ++y) s0 += (int)p[(size_t)y * d.w] * k[y];
+                s1 = s2 = s0;
+            } else {
+                const unsigned char* p = img + ((size_t)b.x * d.w + x) * 3;
+                for (int y = 0; y < b.y; ++y) {
+                    const unsigned char* q = p + (size_t)y * d.w * 3;
+                    s0 += (int)q[0] * k[y];
+                    s1 += (int)q[1] * k[y];
+                    s2 += (int)q[2] * k[y];
+                }
+            }
+            o[0] = clip8(s0); o[1] = clip8(s1); o[2] = clip8(s2);
+        }
+        return;
+    }
     const int total = d.h * R;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         const int y = i / R, xx = i - y * R;
@@ -89,21 +120,26 @@ __global__ __launch_bounds__(256) void resize_horizontal_kernel(const unsigned c
     }
 }
 
-// vertical pass + uint8 -> float table + HWC -> CHW: out[doc][c][yy][xx]
-__global__ __launch_bounds__(256) void resize_vertical_kernel(const unsigned char* __restrict__ tmp, int R, int KMAX, int max_h,
+// second pass (vertical; horizontal over the w columns of a vertical-first page) + uint8 -> float table + HWC -> CHW: out[doc][c][yy][xx]
+__global__ __launch_bounds__(256) void resize_second_pass_kernel(const unsigned char* __restrict__ tmp, const ImageDesc* __restrict__ desc, int R, int KMAX, int max_h,
                                                               const int2* __restrict__ bounds, const int* __restrict__ kk,
                                                               const float* __restrict__ lut, float* __restrict__ out,
                                                               unsigned char* __restrict__ out_u8) {
     const int doc = blockIdx.y;
+    const ImageDesc d = desc[doc];
+    const bool vfirst = vertical_first(d, R);
     const int total = R * R;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         const int yy = i / R, xx = i - yy * R;
-        const int2 b = bounds[(size_t)(doc * 2 + 1) * R + yy];
-        const int* k = kk + ((size_t)(doc * 2 + 1) * R + yy) * KMAX;
+        // the taps of this pass and the bytes between two of them: down a column of tmp rows, or along a row of w pixels
+        const int axis = vfirst ? 0 : 1, at = vfirst ? xx : yy;
+        const int2 b = bounds[(size_t)(doc * 2 + axis) * R + at];
+        const int* k = kk + ((size_t)(doc * 2 + axis) * R + at) * KMAX;
+        const size_t step = vfirst ? 3 : (size_t)R * 3;
         int s0 = 1 << (kPrecisionBits - 1), s1 = s0, s2 = s0;
-        const unsigned char* p = tmp + ((size_t)doc * max_h + b.x) * R * 3 + (size_t)xx * 3;
+        const unsigned char* p = tmp + (size_t)doc * max_h * R * 3 + (vfirst ? ((size_t)yy * d.w + b.x) * 3 : ((size_t)b.x * R + xx) * 3);
         for (int y = 0; y < b.y; ++y) {
-            const unsigned char* q = p + (size_t)y * R * 3;
+            const unsigned char* q = p + (size_t)y * step;
             s0 += (int)q[0] * k[y];
             s1 += (int)q[1] * k[y];
             s2 += (int)q[2] * k[y];
@@ -125,9 +161,9 @@ void launch_preprocess_images(const unsigned char* images, const ImageDesc* desc
     hipLaunchKernelGGL(resize_coeffs_kernel, dim3(B, 2), dim3(256), 0, s, desc, R, KMAX, bounds, kk);
     int gx = (max_h * R + 255) / 256;
     if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(resize_horizontal_kernel, dim3(gx, B), dim3(256), 0, s, images, desc, R, KMAX, max_h, bounds, kk, tmp);
+    hipLaunchKernelGGL(resize_first_pass_kernel, dim3(gx, B), dim3(256), 0, s, images, desc, R, KMAX, max_h, bounds, kk, tmp);
     int gy = (R * R + 255) / 256;
-    hipLaunchKernelGGL(resize_vertical_kernel, dim3(gy, B), dim3(256), 0, s, tmp, R, KMAX, max_h, bounds, kk, lut, out, out_u8);
+    hipLaunchKernelGGL(resize_second_pass_kernel, dim3(gy, B), dim3(256), 0, s, tmp, desc, R, KMAX, max_h, bounds, kk, lut, out, out_u8);
 }
 
 // ragged token streams -> max_length tensors

@@ -500,27 +500,38 @@ def pil_bilinear_coeffs(in_size: int, out_size: int):
 
 def pil_bilinear_resize_u8(img: np.ndarray, out_h: int, out_w: int) -> np.ndarray:
     """img (H,W,C) uint8 -> (out_h,out_w,C) uint8: horizontal pass then vertical pass, each rounded to 8 bits
-    (ImagingResample with both passes needed; a pass whose size does not change is skipped, as in Resample.c)."""
+    (ImagingResample with both passes needed; a pass whose size does not change is skipped, as in Resample.c).  A page more than 100
+    times as tall as wide that shrinks vertically takes the vertical pass FIRST: Image.resize makes two calls for it (PIL/Image.py,
+    "self.size[1] > self.size[0] * 100 and size[1] < self.size[1]"), and the 8-bit rounding between the passes makes the order visible."""
     img = np.asarray(img, dtype=np.uint8)
     H, W, C = img.shape
-    cur = img
-    if W != out_w:
-        b, kk = pil_bilinear_coeffs(W, out_w)
-        tmp = np.zeros((H, out_w, C), dtype=np.uint8)
+    half = 1 << (_PRECISION_BITS - 1)
+
+    def horizontal(cur):
+        if cur.shape[1] == out_w:
+            return cur
+        b, kk = pil_bilinear_coeffs(cur.shape[1], out_w)
+        tmp = np.zeros((cur.shape[0], out_w, C), dtype=np.uint8)
         for xx in range(out_w):
             xmin, xmax = b[xx]
-            acc = (cur[:, xmin:xmin + xmax, :].astype(np.int64) * kk[xx, :xmax][None, :, None]).sum(1) + (1 << (_PRECISION_BITS - 1))
+            acc = (cur[:, xmin:xmin + xmax, :].astype(np.int64) * kk[xx, :xmax][None, :, None]).sum(1) + half
             tmp[:, xx, :] = np.clip(acc >> _PRECISION_BITS, 0, 255)
-        cur = tmp
-    if H != out_h:
-        b, kk = pil_bilinear_coeffs(H, out_h)
+        return tmp
+
+    def vertical(cur):
+        if cur.shape[0] == out_h:
+            return cur
+        b, kk = pil_bilinear_coeffs(cur.shape[0], out_h)
         tmp = np.zeros((out_h, cur.shape[1], C), dtype=np.uint8)
         for yy in range(out_h):
             ymin, ymax = b[yy]
-            acc = (cur[ymin:ymin + ymax, :, :].astype(np.int64) * kk[yy, :ymax][:, None, None]).sum(0) + (1 << (_PRECISION_BITS - 1))
+            acc = (cur[ymin:ymin + ymax, :, :].astype(np.int64) * kk[yy, :ymax][:, None, None]).sum(0) + half
             tmp[yy] = np.clip(acc >> _PRECISION_BITS, 0, 255)
-        cur = tmp
-    return cur
+        return tmp
+
+    if H > W * 100 and out_h < H:
+        return horizontal(vertical(img))
+    return vertical(horizontal(img))
 
 
 def rescale_normalize_lut() -> np.ndarray:

@@ -229,6 +229,19 @@ def make_preprocess_golden():
     print("preprocess golden done")
 
 
+def make_preprocess_edges_golden():
+    """Pillow's own Image.resize(BILINEAR) at the edge shapes of tests/pixel_ref.py (GOLDEN_CASES: the small output sizes, and the one- and
+    two-pixel sides at 224); pages from their seeds, the fixture holds Pillow's outputs and the case list."""
+    from PIL import Image
+    from tests import pixel_ref as X
+    out = {"cases": np.array([(R,) + s for R, s in X.GOLDEN_CASES])}
+    for i, (R, s) in enumerate(X.GOLDEN_CASES):
+        img = Image.fromarray(X.make_page(pkg.synth, R, s)).convert("RGB")
+        out[f"res{i}"] = np.asarray(img.resize((R, R), resample=Image.BILINEAR))
+    np.savez_compressed(os.path.join(HERE, "preprocess_edges.npz"), **out)
+    print("preprocess_edges golden done")
+
+
 DIT_EE = dict(exits=[1, 2, 3, 4], encoder_layer_strategy="ramp", inference_strategy="max_confidence")
 DIT_BASE_EE = dict(exits=[2, 4, 6, 8, 10], encoder_layer_strategy="ramp", inference_strategy="max_confidence")
 
@@ -440,6 +453,8 @@ if __name__ == "__main__":
         make_matrix_golden()
     elif len(sys.argv) > 1 and sys.argv[1] == "preprocess":
         make_preprocess_golden()
+    elif len(sys.argv) > 1 and sys.argv[1] == "preprocess_edges":
+        make_preprocess_edges_golden()
     elif len(sys.argv) > 1 and sys.argv[1] == "dit":
         make_dit_golden()
     elif len(sys.argv) > 1 and sys.argv[1] == "sweep":
@@ -453,6 +468,7 @@ if __name__ == "__main__":
     else:
         main()
         make_preprocess_golden()
+        make_preprocess_edges_golden()
         make_dit_golden()
         make_matrix_golden()
         make_sweep_golden()

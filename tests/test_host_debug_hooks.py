@@ -1,5 +1,5 @@
-"""What the eight stand-alone kernel hooks (ee_debug_attention, ee_debug_xprobe, ee_debug_prep, ee_debug_embed, ee_debug_ln_rows,
-ee_debug_head_out, ee_debug_exit_decide, ee_debug_rows_out) refuse before they ask for a device: every refusal below is decided on the host from the arguments alone, so the message is asserted whole, on a machine
+"""What the nine stand-alone kernel hooks (ee_debug_attention, ee_debug_xprobe, ee_debug_prep, ee_debug_embed, ee_debug_ln_rows,
+ee_debug_head_out, ee_debug_exit_decide, ee_debug_rows_out, ee_debug_patch_project) refuse before they ask for a device: every refusal below is decided on the host from the arguments alone, so the message is asserted whole, on a machine
 without a GPU too.  The pointers are fake and never dereferenced: every call in this file is refused first."""
 import ctypes as C
 
@@ -302,3 +302,44 @@ def test_rows_out_refusals(pkg):
     ]
     for over, text in cases:
         _refused(pkg, who, call(**over), text, over)
+
+
+def test_patch_project_refusals(pkg):
+    lib, who = pkg.capi.load(), "ee_debug_patch_project"
+    err = C.c_int32(-1)
+
+    def call(**over):
+        vals = dict(B=2, C=3, R=64, P=16, H=256, form=0)
+        vals.update(over)
+        a = _struct(pkg.capi.DebugPatchProjectArgs, ("a_split_out",), **vals)
+        a.err_flag_out = None if over.get("err_flag_out", 1) is None else C.pointer(err)
+        return lib.ee_debug_patch_project(C.byref(a), None)
+
+    _refused(pkg, who, lib.ee_debug_patch_project(None, None), "args must not be NULL", "args")
+    null = "pixel_values, weight, bias, out and err_flag_out must not be NULL, B >= 1"
+    geo = "unsupported patch geometry (R %% P == 0, P %% 4 == 0, R %% 4 == 0, C P P %% 32 == 0), got C %d, R %d, P %d"
+    hidden = "hidden size %d is not a multiple of 128 in [128, 1024]"
+    form = "form %d is none of 0 (f32, LDS-DMA kernel), 1 (f32, register-staged kernel), 2 (split)"
+    split = "form 2 needs a shape gemm_split_supports takes (H %% 256 == 0, C P P %% 32 == 0), got H %d, C P P %d"
+    cases = [(dict([(k, None)]), null) for k in ("pixel_values", "weight", "bias", "out", "err_flag_out")]
+    cases += [
+        (dict(B=0), null), (dict(B=-3), null), (dict(B=0, P=0), null),         # the pointers and B before the geometry
+        (dict(R=72), geo % (3, 72, 16)),                                        # R % P
+        (dict(C=2, R=36, P=6), geo % (2, 36, 6)), (dict(C=8, R=4, P=2), geo % (8, 4, 2)),      # P % 4, with C P P % 32 == 0
+        (dict(C=1, R=48, P=12), geo % (1, 48, 12)), (dict(C=3, R=40, P=20), geo % (3, 40, 20)), (dict(C=1, R=32, P=4), geo % (1, 32, 4)),      # C P P % 32
+        (dict(P=0), geo % (3, 64, 0)), (dict(C=0), geo % (0, 64, 16)), (dict(R=0), geo % (3, 0, 16)), (dict(P=-16), geo % (3, 64, -16)),
+        (dict(R=72, H=100), geo % (3, 72, 16)),                                 # the geometry before the hidden size
+        (dict(B=1 << 15, R=1024, P=4, C=2), "B (R / P)^2 = 2147483648 rows above 2^24, or B C R R above 2^30"),
+        (dict(H=192), hidden % 192), (dict(H=0), hidden % 0), (dict(H=1152), hidden % 1152), (dict(H=192, form=7), hidden % 192),
+        (dict(form=3), form % 3), (dict(form=-1), form % -1),
+        (dict(form=2, H=128), split % (128, 768)), (dict(form=2, H=384), split % (384, 768)),
+        (dict(a_split_out=4096), "a_split_out is written by form 2 only"), (dict(form=1, a_split_out=4096), "a_split_out is written by form 2 only"),
+    ]
+    for over, text in cases:
+        _refused(pkg, who, call(**over), text, over)
+    # every geometry class tests/pixel_ref.py lists passes the geometry rule: the checks BEHIND it are what refuses these calls, on the host
+    from . import pixel_ref
+    for (c, r, p), _ in pixel_ref.GEOMETRIES:
+        _refused(pkg, who, call(C=c, R=r, P=p, H=192), hidden % 192, (c, r, p))
+        _refused(pkg, who, call(C=c, R=r, P=p, form=3), form % 3, (c, r, p))
+        _refused(pkg, who, call(C=c, R=r, P=p, H=128, form=2), split % (128, c * p * p), (c, r, p))
