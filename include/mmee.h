@@ -1016,6 +1016,45 @@ int ee_debug_gemm_split_resid(const float* A, const float* W, const float* bias,
                               int32_t K, float a_scale, float w_scale, float resid_scale, const int32_t* row_src, int32_t rows_A,
                               const int32_t* resid_row_src, int32_t rows_resid, int32_t route, int32_t iters, float* ms_out, void* stream);
 
+/* The hook the two above are wrappers of: one call of launch_gemm_split with every operand a forward can set, so that each of its routes can be
+ * launched alone (tests/test_gpu_gemm_routes.py).  The operands of ee_debug_gemm_split and ee_debug_gemm_split_resid keep their meaning (A, W,
+ * bias, resid f32 on the device; resid_scale > 0 converts the residual to split-f16 rows of that scale, 0 passes it on as f32; out_scale is
+ * read with out_split only; row_src non-decreasing, resid_row_src any rows, both checked against rows_A / rows_resid).  Beyond them:
+ *   k_splits, split_stride   S > 1: split-K as MMEE_FLAG_LOW_LATENCY and the X-space probe launch it -- part p of C = alpha * acc over k-stages
+ *                            [p K / 32 / S, (p + 1) K / 32 / S) is written as f32 rows at Cout + p * split_stride (floats); no bias: the LayerNorm
+ *                            kernel behind it (ee_debug_ln_rows, pre_parts = S) adds the parts in order, the bias and the residual
+ *   probe                    != 0: the CLS-probe launches of a forward (128 x 128 tiles under their own kernel name, static tile assignment,
+ *                            three terms whatever `terms` says)
+ *   terms                    3, or 1 = MMEE_FLAG_ONE_TERM (hi x hi only; the pairs GELU -> split, bias -> split, residual -> f32 have such a kernel,
+ *                            every other pair runs the three terms)
+ *   role_tag                 0, or 2 / 3: the kernel names of the attention-output / FFN-down GEMM (residual epilogue)
+ *   route                    as ee_debug_gemm_split_resid's (residual epilogue, f32 output), else 0
+ *   scale_cols, scale        columns [0, scale_cols) are multiplied by `scale` behind the bias (Q / sqrt(d) of the fused Q | K | V GEMM)
+ *   col_scale                NULL, or f32 [N]: a factor per column on (acc + bias), in front of the residual (BEiT's lambda)
+ *   max_m, m_on_device       m_on_device != 0: the launch is sized by max_m and the kernel reads M from a device word the hook uploads, as in
+ *                            every forward; Cout and the row maps still hold M rows.  m_on_device == 0: max_m is not read.
+ * Refused before any device work: k_splits outside {1, 2, 4, 8} or not a divisor of the K / 32 k-stages (the kernel's integer division would
+ * drop the tail); k_splits > 1 with anything but the bias epilogue, an f32 output, three terms and no bias pointer (launch_gemm_split would
+ * write ONE part); terms outside {1, 3}; M > max_m; scale_cols no multiple of 64 in [0, N].  ms_out as ee_debug_gemm_split's. */
+typedef struct ee_debug_gemm_routes_args {
+    const float *A, *W, *bias, *resid;
+    float* Cout;
+    int32_t M, N, K, epi, out_split;
+    float a_scale, w_scale, out_scale, resid_scale;
+    const int32_t* row_src;
+    int32_t rows_A;
+    const int32_t* resid_row_src;
+    int32_t rows_resid;
+    int32_t route, role_tag, probe, terms;
+    int32_t k_splits;
+    size_t split_stride;
+    int32_t scale_cols;
+    float scale;
+    const float* col_scale;
+    int32_t max_m, m_on_device, iters;
+} ee_debug_gemm_routes_args;
+int ee_debug_gemm_routes(const ee_debug_gemm_routes_args* args, float* ms_out, void* stream);
+
 /* Unit-test hook of the fused attention kernels: ONE launch of one kernel of the path on caller-provided DEVICE buffers; no handle.
  *   qkv            f32 [qkv_rows][3 H], H = 64 * heads: Q (already divided by sqrt(d)) | K | V of every row
  *   doc_off        int32 [n_docs + 1], doc_off[0] = 0: the ragged documents; row r of document d is context row doc_off[d] + r

@@ -122,6 +122,16 @@ class DebugPatchProjectArgs(C.Structure):
                 + [(n, _vp) for n in ("out", "a_split_out")] + [("err_flag_out", C.POINTER(_i32))])
 
 
+class DebugGemmRoutesArgs(C.Structure):
+    """ee_debug_gemm_routes_args of include/mmee.h: device pointers (or None), sizes and scales."""
+    _fields_ = ([(n, _vp) for n in ("A", "W", "bias", "resid", "Cout")] + [(n, _i32) for n in ("M", "N", "K", "epi", "out_split")]
+                + [(n, C.c_float) for n in ("a_scale", "w_scale", "out_scale", "resid_scale")]
+                + [("row_src", _vp), ("rows_A", _i32), ("resid_row_src", _vp), ("rows_resid", _i32)]
+                + [(n, _i32) for n in ("route", "role_tag", "probe", "terms", "k_splits")] + [("split_stride", C.c_size_t), ("scale_cols", _i32),
+                                                                                             ("scale", C.c_float), ("col_scale", _vp)]
+                + [(n, _i32) for n in ("max_m", "m_on_device", "iters")])
+
+
 SYMBOLS = {
     "ee_create": (C.c_int, [C.POINTER(EEConfig), C.POINTER(_vp)]),
     "ee_destroy": (C.c_int, [_vp]),
@@ -176,6 +186,7 @@ SYMBOLS = {
                                       _i32, _i32, C.POINTER(C.c_float), _vp]),
     "ee_debug_gemm_split_resid": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp, _i32, _vp, _i32,
                                             _i32, _i32, C.POINTER(C.c_float), _vp]),
+    "ee_debug_gemm_routes": (C.c_int, [C.POINTER(DebugGemmRoutesArgs), C.POINTER(C.c_float), _vp]),
     "ee_debug_attn_stamps": (C.c_int, [_vp]),
     "ee_debug_attention": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                      _i32, _i32, _i32, _vp, C.POINTER(_i32), _vp]),

@@ -1,6 +1,6 @@
 // Entry points of libmmee_hip.so that never see a handle: bucket LUT, shader-clock stamps, policy / patience / threshold sweeps, temperature
 // fit, the evaluation report (ee_exit_metrics), result packing, the device-side input feed, and the GEMM micro-benchmark hooks (ee_debug_gemm,
-// ee_debug_gemm_split, ee_debug_attn_stamps).  The L-BFGS fits are in capi_fit.hip, the hooks that run one kernel of the path alone for its
+// ee_debug_gemm_split, ee_debug_gemm_split_resid, ee_debug_gemm_routes, ee_debug_attn_stamps).  The L-BFGS fits are in capi_fit.hip, the hooks that run one kernel of the path alone for its
 // float64 test in capi_debug_*.hip.
 #include <math.h>
 #include <string.h>
@@ -464,28 +464,48 @@ int ee_debug_attn_stamps(uint64_t* out8) {
     return 0;
 }
 
-// What the two split-GEMM hooks share: the operands to split planes, `iters` launches (the first untimed), the time per launch.  `g` arrives
-// with everything but A / W set; resid_scale != 0 converts the f32 residual (rows_resid rows of N) to split planes of that scale first.
-static int run_debug_gemm_split(const char* who, GemmArgs g, int epi, const float* A, const float* W, int rows_A, float a_scale, float w_scale,
-                                const float* resid, int rows_resid, float resid_scale, int M, int iters, float* ms_out, hipStream_t s) {
-    const int dbg = g.dbg_noload;
-    const int N = g.N, K = g.K;
+// a row map of the caller's, on a host copy: every entry inside [0, rows)
+static int check_row_map(const char* who, const char* what, const int32_t* map, int M, int rows) {
+    std::vector<int> h;
+    if (!to_host(h, map, (size_t)M)) return fail(nullptr, "%s: copy of %s failed", who, what);
+    for (int i = 0; i < M; ++i)
+        if (h[i] < 0 || h[i] >= rows) return fail(nullptr, "%s: %s[%d] = %d outside [0, %d)", who, what, i, h[i], rows);
+    return 0;
+}
+
+// What the three split-GEMM hooks share: the operands to split planes (resid_scale != 0: the f32 residual too), M to the device when the
+// kernel is to read it there, `iters` launches (the first untimed), the time per launch.  dbg: the timing-diagnostic bits of ee_debug_gemm_split.
+static int run_debug_gemm_split(const char* who, const ee_debug_gemm_routes_args& a, int dbg, float* ms_out, hipStream_t s) {
+    const int N = a.N, K = a.K, M = a.M, rows_A = a.rows_A, rows_resid = a.rows_resid, iters = a.iters;
+    const int max_m = a.m_on_device ? a.max_m : M;
+    GemmArgs g{};
+    g.lda = K; g.bias = a.bias; g.C = a.Cout; g.ldc = N; g.resid = a.resid; g.ldr = N; g.m_static = M; g.N = N; g.K = K;
+    g.scale_cols = a.scale_cols; g.scale = a.scale; g.col_scale = a.col_scale;
+    g.alpha = 1.0f / (a.a_scale * a.w_scale); g.out_split = a.out_split ? 1 : 0; g.out_scale = a.out_scale;
+    g.row_src = a.row_src; g.resid_row_src = a.resid_row_src; g.route = a.route; g.role_tag = a.role_tag; g.probe = a.probe ? 1 : 0;
+    g.terms = a.terms; g.k_splits = a.k_splits; g.split_stride = a.split_stride; g.dbg_noload = dbg;
     const int cus = device_cus(who);
     if (!cus) return 1;
+    const bool split_resid = a.resid && a.resid_scale != 0.f;
     float *As = nullptr, *Ws = nullptr, *Rs = nullptr;
-    int* heads = nullptr;
+    int *heads = nullptr, *m_dev = nullptr;
     if (hipMalloc((void**)&As, (size_t)rows_A * K * 4) != hipSuccess || hipMalloc((void**)&Ws, (size_t)N * K * 4) != hipSuccess ||
-        hipMalloc((void**)&heads, 512) != hipSuccess ||
-        (resid_scale != 0.f && hipMalloc((void**)&Rs, (size_t)rows_resid * N * 4) != hipSuccess)) {
-        (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads); (void)hipFree(Rs);
+        hipMalloc((void**)&heads, 512) != hipSuccess || (a.m_on_device && hipMalloc((void**)&m_dev, sizeof(int)) != hipSuccess) ||
+        (split_resid && hipMalloc((void**)&Rs, (size_t)rows_resid * N * 4) != hipSuccess)) {
+        (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads); (void)hipFree(m_dev); (void)hipFree(Rs);
         return fail(nullptr, "%s: hipMalloc failed", who);
     }
-    mmee::launch_split_rows(A, As, nullptr, rows_A, rows_A, K, a_scale, cus, s);
-    mmee::launch_split_rows(W, Ws, nullptr, N, N, K, w_scale, cus, s);
-    g.A = As; g.W = Ws; g.tile_counter = heads;
-    if (resid_scale != 0.f) {
-        mmee::launch_split_rows(resid, Rs, nullptr, rows_resid, rows_resid, N, resid_scale, cus, s);
-        g.resid = Rs; g.resid_split_inv = 1.0f / resid_scale;
+    mmee::launch_split_rows(a.A, As, nullptr, rows_A, rows_A, K, a.a_scale, cus, s);
+    mmee::launch_split_rows(a.W, Ws, nullptr, N, N, K, a.w_scale, cus, s);
+    // the probes of a forward take their tiles statically (capi_forward.hip layer_probe): no queue head
+    g.A = As; g.W = Ws; g.tile_counter = a.probe ? nullptr : heads;
+    if (split_resid) {
+        mmee::launch_split_rows(a.resid, Rs, nullptr, rows_resid, rows_resid, N, a.resid_scale, cus, s);
+        g.resid = Rs; g.resid_split_inv = 1.0f / a.resid_scale;
+    }
+    if (m_dev) {      // (M lives until the synchronisation below)
+        (void)hipMemcpyAsync(m_dev, &M, sizeof(int), hipMemcpyHostToDevice, s);
+        g.m_ptr = m_dev;
     }
     // diagnostic builds (any dbg bit; bit 256 = "diagnostic build, nothing removed") report the shader clock they ran at:
     // ms_out[1] = GHz averaged over the workgroups of the last launch
@@ -499,11 +519,11 @@ static int run_debug_gemm_split(const char* who, GemmArgs g, int epi, const floa
     (void)hipEventCreate(&e0);
     (void)hipEventCreate(&e1);
     (void)hipMemsetAsync(heads, 0, 512, s);
-    launch_gemm_split(g, epi, M, cus, s);          // first launch untimed (code object load)
+    launch_gemm_split(g, a.epi, max_m, cus, s);          // first launch untimed (code object load)
     (void)hipEventRecord(e0, s);
     for (int i = 1; i < iters; ++i) {
         (void)hipMemsetAsync(heads, 0, 512, s);
-        launch_gemm_split(g, epi, M, cus, s);
+        launch_gemm_split(g, a.epi, max_m, cus, s);
     }
     (void)hipEventRecord(e1, s);
     const hipError_t err = hipStreamSynchronize(s);
@@ -522,9 +542,19 @@ static int run_debug_gemm_split(const char* who, GemmArgs g, int epi, const floa
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads); (void)hipFree(Rs);
+    (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads); (void)hipFree(m_dev); (void)hipFree(Rs);
     if (err != hipSuccess || hipGetLastError() != hipSuccess) return fail(nullptr, "%s: launch failed: %s", who, hipGetErrorString(err));
     return 0;
+}
+
+// the operands ee_debug_gemm_split and ee_debug_gemm_split_resid share, as the arguments of the hook they wrap: one part, three terms, no
+// column factors, M from the host
+static ee_debug_gemm_routes_args plain_split_args(const float* A, const float* W, const float* bias, const float* resid, float* Cout, int M, int N, int K,
+                                                  int epi, float a_scale, float w_scale, const int32_t* row_src, int rows_A, int iters) {
+    ee_debug_gemm_routes_args a{};
+    a.A = A; a.W = W; a.bias = bias; a.resid = resid; a.Cout = Cout; a.M = M; a.N = N; a.K = K; a.epi = epi;
+    a.a_scale = a_scale; a.w_scale = w_scale; a.row_src = row_src; a.rows_A = rows_A; a.terms = 3; a.k_splits = 1; a.scale = 1.f; a.iters = iters;
+    return a;
 }
 
 int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const float* resid, float* Cout, int32_t M, int32_t N,
@@ -538,21 +568,10 @@ int ee_debug_gemm_split(const float* A, const float* W, const float* bias, const
     if (!A || !W || !Cout || M < 1 || rows_A < 1 || !mmee::gemm_split_supports(N, K) || epi < 0 || epi > 3 || iters < 1)
         return fail(nullptr, "ee_debug_gemm_split: bad argument (N %% 256, K %% 32)");
     if (epi == EPI_RESID && !resid) return fail(nullptr, "ee_debug_gemm_split: residual epilogue without a residual");
-    GemmArgs g{};
-    g.lda = K; g.bias = bias; g.C = Cout; g.ldc = N; g.resid = resid; g.ldr = N; g.m_static = M; g.N = N; g.K = K;
-    g.scale = 1.f; g.alpha = 1.0f / (a_scale * w_scale); g.out_split = out_split ? 1 : 0; g.out_scale = out_scale;
-    g.row_src = row_src; g.resid_row_src = row_src; g.dbg_noload = dbg;
-    return run_debug_gemm_split("ee_debug_gemm_split", g, epi, A, W, rows_A, a_scale, w_scale, nullptr, 0, 0.f, M, iters, ms_out,
-                                reinterpret_cast<hipStream_t>(stream));
-}
-
-// a row map of the caller's, on a host copy: every entry inside [0, rows)
-static int check_row_map(const char* who, const char* what, const int32_t* map, int M, int rows) {
-    std::vector<int> h;
-    if (!to_host(h, map, (size_t)M)) return fail(nullptr, "%s: copy of %s failed", who, what);
-    for (int i = 0; i < M; ++i)
-        if (h[i] < 0 || h[i] >= rows) return fail(nullptr, "%s: %s[%d] = %d outside [0, %d)", who, what, i, h[i], rows);
-    return 0;
+    ee_debug_gemm_routes_args a = plain_split_args(A, W, bias, resid, Cout, M, N, K, epi, a_scale, w_scale, row_src, rows_A, iters);
+    a.out_split = out_split; a.out_scale = out_scale;
+    a.resid_row_src = row_src; a.rows_resid = rows_A;      // an f32 residual, gathered as A is
+    return run_debug_gemm_split("ee_debug_gemm_split", a, dbg, ms_out, reinterpret_cast<hipStream_t>(stream));
 }
 
 int ee_debug_gemm_split_resid(const float* A, const float* W, const float* bias, const float* resid, float* Cout, int32_t M, int32_t N,
@@ -565,13 +584,44 @@ int ee_debug_gemm_split_resid(const float* A, const float* W, const float* bias,
     if ((!row_src && M > rows_A) || (!resid_row_src && M > rows_resid)) return fail(nullptr, "%s: M rows without a row map need M rows of A / of the residual", who);
     if (row_src) { const int rc = check_row_map(who, "row_src", row_src, M, rows_A); if (rc) return rc; }
     if (resid_row_src) { const int rc = check_row_map(who, "resid_row_src", resid_row_src, M, rows_resid); if (rc) return rc; }
-    GemmArgs g{};
-    g.lda = K; g.bias = bias; g.C = Cout; g.ldc = N; g.resid = resid; g.ldr = N; g.m_static = M; g.N = N; g.K = K;
-    g.scale = 1.f; g.alpha = 1.0f / (a_scale * w_scale);
-    g.row_src = row_src; g.resid_row_src = resid_row_src; g.route = route;
-    g.role_tag = K > N ? 3 : 2;          // the layer's kernel names: FFN down / attention output
-    return run_debug_gemm_split(who, g, EPI_RESID, A, W, rows_A, a_scale, w_scale, resid, rows_resid, resid_scale, M, iters, ms_out,
-                                reinterpret_cast<hipStream_t>(stream));
+    ee_debug_gemm_routes_args a = plain_split_args(A, W, bias, resid, Cout, M, N, K, EPI_RESID, a_scale, w_scale, row_src, rows_A, iters);
+    a.resid_scale = resid_scale; a.resid_row_src = resid_row_src; a.rows_resid = rows_resid; a.route = route;
+    a.role_tag = K > N ? 3 : 2;          // the layer's kernel names: FFN down / attention output
+    return run_debug_gemm_split(who, a, 0, ms_out, reinterpret_cast<hipStream_t>(stream));
+}
+
+int ee_debug_gemm_routes(const ee_debug_gemm_routes_args* args, float* ms_out, void* stream) {
+    const char* who = "ee_debug_gemm_routes";
+    if (!args) return fail(nullptr, "%s: args must not be NULL", who);
+    const ee_debug_gemm_routes_args& a = *args;
+    if (!a.A || !a.W || !a.Cout || a.M < 1 || a.rows_A < 1 || !mmee::gemm_split_supports(a.N, a.K) || a.epi < 0 || a.epi > 3 || a.iters < 1 ||
+        !(a.a_scale > 0.f) || !(a.w_scale > 0.f) || (a.out_split && !(a.out_scale > 0.f)))
+        return fail(nullptr, "%s: bad argument (A, W, Cout not NULL, M, rows_A, iters >= 1, N %% 256, K %% 32, epi 0 .. 3, scales positive)", who);
+    if (a.epi == EPI_RESID && (!a.resid || a.rows_resid < 1 || a.resid_scale < 0.f || a.resid_scale != a.resid_scale))
+        return fail(nullptr, "%s: the residual epilogue needs resid, rows_resid >= 1 and resid_scale >= 0", who);
+    if (a.terms != 1 && a.terms != 3) return fail(nullptr, "%s: terms %d is neither 1 nor 3", who, a.terms);
+    if (a.k_splits != 1 && a.k_splits != 2 && a.k_splits != 4 && a.k_splits != 8) return fail(nullptr, "%s: k_splits %d is none of 1, 2, 4, 8", who, a.k_splits);
+    if ((a.K / 32) % a.k_splits != 0)
+        return fail(nullptr, "%s: k_splits %d does not divide the %d k-stages of K = %d (the kernel would drop the last %d)", who, a.k_splits, a.K / 32, a.K,
+                    (a.K / 32) % a.k_splits);
+    if (a.k_splits > 1 && (a.epi != EPI_BIAS || a.out_split || a.terms == 1 || a.bias))
+        return fail(nullptr, "%s: k_splits %d needs the bias epilogue, an f32 output, three terms and no bias pointer (anything else writes one part)", who,
+                    a.k_splits);
+    if (a.m_on_device && a.M > a.max_m) return fail(nullptr, "%s: M %d is above max_m %d", who, a.M, a.max_m);
+    if (a.scale_cols < 0 || a.scale_cols > a.N || a.scale_cols % 64 != 0)
+        return fail(nullptr, "%s: scale_cols %d is not a multiple of 64 in [0, N = %d]", who, a.scale_cols, a.N);
+    if (a.route < 0 || a.route > 2 || (a.role_tag != 0 && a.role_tag != 2 && a.role_tag != 3))
+        return fail(nullptr, "%s: route %d outside 0 / 1 / 2 or role_tag %d none of 0, 2, 3", who, a.route, a.role_tag);
+    if (a.k_splits > 1 && a.split_stride < (size_t)(a.m_on_device ? a.max_m : a.M) * a.N)
+        return fail(nullptr, "%s: split_stride %zu is below the %d x %d floats of a part", who, a.split_stride, a.m_on_device ? a.max_m : a.M, a.N);
+    const bool resid = a.epi == EPI_RESID;
+    if ((!a.row_src && a.M > a.rows_A) || (resid && !a.resid_row_src && a.M > a.rows_resid))
+        return fail(nullptr, "%s: M rows without a row map need M rows of A / of the residual", who);
+    if (a.row_src) { const int rc = check_row_map(who, "row_src", a.row_src, a.M, a.rows_A); if (rc) return rc; }
+    if (resid && a.resid_row_src) { const int rc = check_row_map(who, "resid_row_src", a.resid_row_src, a.M, a.rows_resid); if (rc) return rc; }
+    ee_debug_gemm_routes_args b = a;
+    if (!resid) { b.resid = nullptr; b.resid_row_src = nullptr; }
+    return run_debug_gemm_split(who, b, 0, ms_out, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

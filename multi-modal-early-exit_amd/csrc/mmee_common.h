@@ -153,7 +153,13 @@ __device__ __forceinline__ float wave_sum_uniform(float v) {
 // Row-wise LayerNorm on a row held by one wave: lane owns columns c = 4*lane + 256*i + e (i < NV, e < 4).
 // Two-pass (mean, then centred variance), biased variance, as torch.nn.LayerNorm.  FULL: H == 256 * NV, no column is ever masked (the
 // per-chunk `c < H` tests cost an exec-mask branch and register copies each when H is a run-time value).
-template <int NV, bool FULL = false>
+// REFINE: the mean as two words.  The f32 sum of a row and its division by H are each rounded (half an ulp of the sum / H, half an ulp of the
+// mean); on a row whose mean is many times its deviation that rounding, divided by the deviation, is the whole error of the output: a row of
+// 384 values around 2.0 +- 0.04 came out 3.4e-6 off where every later step contributes 3e-7 (tests/test_gpu_rows.py, eight split-K parts).  One
+// correction step removes it: mean_lo = the mean of (x - mean), whose terms are small and (nearly) exact, and every deviation is
+// (x - mean) - mean_lo.  One wave reduction more per row; ln_rows_kernel's PRE form takes it (rows completed from split-K parts: the low-latency
+// layers and the X-space probe, a few hundred rows a launch), the layers' own LayerNorm launches and the embedding kernels keep their bits.
+template <int NV, bool FULL = false, bool REFINE = false>
 __device__ __forceinline__ void wave_layernorm(f32x4 (&x)[NV], int H, int lane, const float* __restrict__ gamma,
                                                const float* __restrict__ beta, float eps) {
     float s = 0.f;
@@ -163,6 +169,16 @@ __device__ __forceinline__ void wave_layernorm(f32x4 (&x)[NV], int H, int lane, 
         if (FULL || c < H) s += (x[i][0] + x[i][1]) + (x[i][2] + x[i][3]);
     }
     const float mean = wave_sum_uniform(s) / (float)H;
+    float mean_lo = 0.f;
+    if constexpr (REFINE) {
+        float sd = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = 4 * lane + 256 * i;
+            if (FULL || c < H) sd += ((x[i][0] - mean) + (x[i][1] - mean)) + ((x[i][2] - mean) + (x[i][3] - mean));
+        }
+        mean_lo = wave_sum_uniform(sd) / (float)H;
+    }
     float v = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -170,7 +186,7 @@ __device__ __forceinline__ void wave_layernorm(f32x4 (&x)[NV], int H, int lane, 
         if (FULL || c < H) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float d = x[i][e] - mean;
+                const float d = REFINE ? (x[i][e] - mean) - mean_lo : x[i][e] - mean;
                 v += d * d;
             }
         }
@@ -183,7 +199,7 @@ __device__ __forceinline__ void wave_layernorm(f32x4 (&x)[NV], int H, int lane, 
             const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + c);
             const f32x4 b = *reinterpret_cast<const f32x4*>(beta + c);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) x[i][e] = (x[i][e] - mean) * rstd * g[e] + b[e];
+            for (int e = 0; e < 4; ++e) x[i][e] = (REFINE ? (x[i][e] - mean) - mean_lo : x[i][e] - mean) * rstd * g[e] + b[e];
         }
     }
 }

@@ -481,7 +481,7 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const float* __restrict__ 
                 }
             }
         }
-        wave_layernorm<NV, FULL>(x, H, lane, g, b, eps);
+        wave_layernorm<NV, FULL, PRE>(x, H, lane, g, b, eps);      // PRE: the mean as two words (mmee_common.h)
         if (dst) wave_store_row<NV, FULL>(dst + (size_t)r * H, x, H, lane);
         if (dst_split) {
 #pragma unroll

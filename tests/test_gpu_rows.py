@@ -15,7 +15,7 @@ Which case reaches which instantiation (NV = ceil(H / 256), FULL = (H == 256 NV)
   embed_visual_rows<NV[, FULL]>               every configuration, modes rows, text_avg, embeds, types (no vis / cat partial sums)
   embed_visual<NV[, FULL]> + pool_finish      every configuration, mode pooled;  split rows: 256, 512, 768, 1024 in modes rows and pooled
   ln_rows<1, plain, FULL / not>               256 / 128                       ln_rows<2, plain>                  384, 512
-  ln_rows<3 / 4, plain, FULL / not>           768, 1024 / 640, 896            ln_rows<NV, PRE[, FULL]>           all eight sizes, parts 1, 2, 4
+  ln_rows<3 / 4, plain, FULL / not>           768, 1024 / 640, 896            ln_rows<NV, PRE[, FULL]>           all eight sizes, parts 1, 2, 4, 8
   doc_prep with two and more positions per thread: T = 257, 512;  doc_scan's second sweep: B = 1025."""
 import ctypes as C
 import functools
@@ -391,7 +391,7 @@ def test_ln_rows_against_float64(pkg, H, n):
     _ln_check(f"ln_rows H={H} n={n} inplace", d, _ln(pkg, d, "inplace"))
 
 
-@pytest.mark.parametrize("parts", [1, 2, 4])
+@pytest.mark.parametrize("parts", [1, 2, 4, 8])
 @pytest.mark.parametrize("H", R.HIDDEN_SIZES)
 def test_ln_rows_completes_the_row_from_split_k_parts(pkg, H, parts):
     """The PRE form: parts a stride larger than n H apart, with and without the bias, the split-plane residual gathered, dense and absent."""

@@ -1,5 +1,5 @@
-"""What the nine stand-alone kernel hooks (ee_debug_attention, ee_debug_xprobe, ee_debug_prep, ee_debug_embed, ee_debug_ln_rows,
-ee_debug_head_out, ee_debug_exit_decide, ee_debug_rows_out, ee_debug_patch_project) refuse before they ask for a device: every refusal below is decided on the host from the arguments alone, so the message is asserted whole, on a machine
+"""What the ten stand-alone kernel hooks (ee_debug_attention, ee_debug_xprobe, ee_debug_prep, ee_debug_embed, ee_debug_ln_rows,
+ee_debug_head_out, ee_debug_exit_decide, ee_debug_rows_out, ee_debug_patch_project, ee_debug_gemm_routes) refuse before they ask for a device: every refusal below is decided on the host from the arguments alone, so the message is asserted whole, on a machine
 without a GPU too.  The pointers are fake and never dereferenced: every call in this file is refused first."""
 import ctypes as C
 
@@ -343,3 +343,46 @@ def test_patch_project_refusals(pkg):
         _refused(pkg, who, call(C=c, R=r, P=p, H=192), hidden % 192, (c, r, p))
         _refused(pkg, who, call(C=c, R=r, P=p, form=3), form % 3, (c, r, p))
         _refused(pkg, who, call(C=c, R=r, P=p, H=128, form=2), split % (128, c * p * p), (c, r, p))
+
+
+def test_gemm_routes_refusals(pkg):
+    lib, who = pkg.capi.load(), "ee_debug_gemm_routes"
+    optional = ("bias", "resid", "row_src", "resid_row_src", "col_scale")
+
+    def call(**over):
+        vals = dict(M=129, N=768, K=768, epi=0, out_split=0, a_scale=16.0, w_scale=256.0, out_scale=1.0, resid_scale=0.0, rows_A=300, rows_resid=0, route=0,
+                    role_tag=0, probe=0, terms=3, k_splits=1, split_stride=0, scale_cols=0, scale=1.0, max_m=0, m_on_device=0, iters=1)
+        vals.update(over)
+        return lib.ee_debug_gemm_routes(C.byref(_struct(pkg.capi.DebugGemmRoutesArgs, optional, **vals)), None, None)
+
+    _refused(pkg, who, lib.ee_debug_gemm_routes(None, None, None), "args must not be NULL", "args")
+    bad = "bad argument (A, W, Cout not NULL, M, rows_A, iters >= 1, N % 256, K % 32, epi 0 .. 3, scales positive)"
+    resid = "the residual epilogue needs resid, rows_resid >= 1 and resid_scale >= 0"
+    parts = "k_splits %d is none of 1, 2, 4, 8"
+    tail = "k_splits %d does not divide the %d k-stages of K = %d (the kernel would drop the last %d)"
+    one = "k_splits %d needs the bias epilogue, an f32 output, three terms and no bias pointer (anything else writes one part)"
+    cols = "scale_cols %d is not a multiple of 64 in [0, N = 768]"
+    split = dict(k_splits=8, split_stride=(129 + 64) * 768)
+    cases = [(dict([(k, None)]), bad) for k in ("A", "W", "Cout")]
+    cases += [
+        (dict(M=0), bad), (dict(rows_A=0), bad), (dict(iters=0), bad), (dict(N=128), bad), (dict(N=0), bad), (dict(K=48), bad), (dict(epi=4), bad),
+        (dict(epi=-1), bad), (dict(a_scale=0.0), bad), (dict(w_scale=-1.0), bad), (dict(a_scale=float("nan")), bad), (dict(out_split=1, out_scale=0.0), bad),
+        (dict(A=None, terms=2), bad),                                           # the pointers before everything else
+        (dict(epi=2), resid), (dict(epi=2, resid=4096), resid), (dict(epi=2, resid=4096, rows_resid=300, resid_scale=-16.0), resid),
+        (dict(terms=0), "terms 0 is neither 1 nor 3"), (dict(terms=2), "terms 2 is neither 1 nor 3"), (dict(terms=2, k_splits=3), "terms 2 is neither 1 nor 3"),
+        (dict(k_splits=0), parts % 0), (dict(k_splits=3), parts % 3), (dict(k_splits=16), parts % 16), (dict(k_splits=-2), parts % -2),
+        (dict(K=96, k_splits=2), tail % (2, 3, 96, 1)), (dict(K=96, k_splits=8), tail % (8, 3, 96, 3)), (dict(K=3232, k_splits=4), tail % (4, 101, 3232, 1)),
+        (dict(K=128, k_splits=8), tail % (8, 4, 128, 4)),
+        (dict(split, epi=1), one % 8), (dict(split, epi=3), one % 8), (dict(split, epi=2, resid=4096, rows_resid=300), one % 8),
+        (dict(split, out_split=1), one % 8), (dict(split, terms=1), one % 8), (dict(split, bias=4096), one % 8), (dict(split, k_splits=2, bias=4096), one % 2),
+        (dict(m_on_device=1, max_m=128), "M 129 is above max_m 128"), (dict(m_on_device=1), "M 129 is above max_m 0"),
+        (dict(scale_cols=-64), cols % -64), (dict(scale_cols=100), cols % 100), (dict(scale_cols=832), cols % 832), (dict(scale_cols=255), cols % 255),
+        (dict(route=3), "route 3 outside 0 / 1 / 2 or role_tag 0 none of 0, 2, 3"), (dict(role_tag=1), "route 0 outside 0 / 1 / 2 or role_tag 1 none of 0, 2, 3"),
+        (dict(split, split_stride=129 * 768 - 1), "split_stride 99071 is below the 129 x 768 floats of a part"),
+        (dict(split, m_on_device=1, max_m=300), "split_stride 148224 is below the 300 x 768 floats of a part"),
+        (dict(rows_A=100), "M rows without a row map need M rows of A / of the residual"),
+        (dict(epi=2, resid=4096, rows_resid=100), "M rows without a row map need M rows of A / of the residual"),
+    ]
+    for over, text in cases:
+        _refused(pkg, who, call(**over), text, over)
+    # what the hook lets through is what the rule of MMEE_FLAG_LOW_LATENCY produces: its S divides the k-stages (tests/test_host_gemm_routes.py)
