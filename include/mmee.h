@@ -15,6 +15,9 @@
  *                                                 Policy.max_confidence_global_thresholding_policy /
  *                                                 accuracy_calibration_heuristic (EE/policy.py:12-111) fused in,
  *                                                 per-exit temperature of EE/generic_scaling.py:54-61 applied first.
+ *   ee_embedding_inputs                         <- the three pooled rows the embedding-level exit heads read, `visual_embeddings.mean(1)`,
+ *                                                 `embedding_output.mean(1)` and `LayerNorm(cat).mean(1)` (EE/models/LayoutLMv3.py:466, 520, 582),
+ *                                                 without the encoder behind them: the training set of those heads.
  *   ee_policy_scan                              <- Policy.* on a dumped (E+1, N, K) logits array (EE/policy.py:28-45,
  *                                                 87-104; called from EE/eval.py:87-98).
  *   ee_threshold_sweep                          <- thresh.opt1 / large_scale.opt0_2D vectorised exit-index search
@@ -303,6 +306,32 @@ int ee_graph_capture(ee_handle* h, const int64_t* input_ids, const int64_t* atte
                      float* out_head_logits, float* out_head_crit, float* out_hidden_cls, void* stream, int32_t* graph_id);
 int ee_graph_launch(ee_handle* h, int32_t graph_id, const double* thresholds, const double* temperatures, void* stream);
 int ee_graph_destroy(ee_handle* h, int32_t graph_id);
+
+/*
+ * The inputs of the embedding-level exit heads, from stage 0 of the forward alone: no encoder layer, no head, no exit stage.  Each output is a
+ * dev float (B,H) or NULL (at least one must be given):
+ *   out_vision   visual_embeddings.mean(1)          the row layoutlmv3.vision_exit_embeddings reads  (EE/models/LayoutLMv3.py:466)
+ *   out_text     embedding_output.mean(1), text     the row layoutlmv3.text_exit_embeddings reads    (EE/models/LayoutLMv3.py:520)
+ *   out_concat   LayerNorm(cat(text, visual)).mean(1)  the row layoutlmv3.concat_exit_embeddings reads  (EE/models/LayoutLMv3.py:582)
+ * The means run over EVERY position of the call, padded text positions included, as in the reference: the same page padded to another T has
+ * another text and concat row.  The launches are the ones ee_forward opens with (one definition serves both), so the rows are, bit for bit,
+ * the rows the heads of a forward on the same handle and inputs read, and an output does not depend on which other outputs are asked for or
+ * on which embedding exits the handle's configuration names.  The training set of these heads needs no encoder: this is the call that
+ * collects it (heads.py collect_embedding_features).
+ * Inputs and their checks are ee_forward's.  Refused with a message, nothing written: a MMEE_ARCH_BEIT handle (it has no such exits), all three
+ * outputs NULL, B outside [1, max_docs], T outside [1, max_text_len], a missing input_ids / bbox / pixel_values.  An id, box, position or
+ * token type out of range is flagged on the device and reported as after ee_forward -- by the next call on the handle or by
+ * ee_last_stage_counts -- and the rows of that call are invalid.  An armed ee_set_inputs_embeds is consumed by this call as ee_forward
+ * would consume it (its rows replace the word embeddings); the other one-shot side inputs / outputs stay armed for the next ee_forward.
+ * Handle state: the call runs on `stream`, ordered behind the handle's previous call as a forward is, and only enqueues.  What the handle
+ * records of its LAST FORWARD is untouched: ee_last_stage_counts, ee_last_flops, ee_last_k_splits, ee_last_layer_plan, ee_suggest_probe_mask
+ * and ee_profile_read answer as if this call had not happened (an armed ee_profile stays armed and times nothing here).  It writes only
+ * buffers that every forward and graph replay rewrites before reading them (the packed rows go to the handle's X rows as scratch), so
+ * captured graphs stay valid and an undrained result stream keeps its chunks.
+ */
+int ee_embedding_inputs(ee_handle* h, const int64_t* input_ids, const int64_t* attention_mask, const int64_t* bbox,
+                        const float* pixel_values, const int64_t* token_type_ids, const int64_t* position_ids,
+                        int32_t B, int32_t T, float* out_vision, float* out_text, float* out_concat, void* stream);
 
 /*
  * The result stream of the handle's most recent ee_forward with MMEE_FLAG_STREAM_RESULTS: one chunk per evaluated exit, in the path's order

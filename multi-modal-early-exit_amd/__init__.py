@@ -22,6 +22,6 @@ from .metrics import ExitReport, exit_report  # noqa: F401,E402
 from . import feed  # noqa: F401,E402
 from . import heads  # noqa: F401,E402
 from .heads import (GateFit, HeadFit, LteFit, MlpGateFit, MlpHeadFit, balanced_class_weights, collect_distill_features,  # noqa: F401,E402
-                    collect_exit_features, collect_gate_features, collect_lte_features, fit_distilled_exit_heads,
+                    collect_embedding_features, collect_exit_features, collect_gate_features, collect_lte_features, fit_distilled_exit_heads,
                     fit_distilled_mlp_exit_heads, fit_exit_heads, fit_gate_heads, fit_lte_classifier, fit_mlp_exit_heads,
                     fit_mlp_gate_heads, gate_targets, lte_targets, reach_weights)

@@ -142,6 +142,7 @@ SYMBOLS = {
     "ee_expected_tensor_name": (C.c_char_p, [_vp, _i32]),
     "ee_forward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(C.c_double),
                              C.POINTER(C.c_double), _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ee_embedding_inputs": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ee_graph_capture": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32)]),
     "ee_graph_launch": (C.c_int, [_vp, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),

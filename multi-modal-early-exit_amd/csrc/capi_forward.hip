@@ -42,6 +42,80 @@ void mmee::capi::launch_patch_projection(const PatchProjection& p, int num_cus, 
 
 namespace {
 
+// patch projection of the handle's model -> vis_raw [B * NP][H] (launch_patch_projection).  Split mode: the split patches are staged in H1,
+// idle until the first FFN.
+void handle_patch_projection(ee_handle* h, const float* pix, int B, int* tile_counter, hipStream_t s) {
+    const ee_config& c = h->cfg;
+    ProfScope ps(h, P_GPATCH, s);
+    PatchProjection p{};
+    p.pix = pix; p.B = B; p.C = c.num_channels; p.R = c.input_size; p.P = c.patch_size; p.H = c.hidden_size;
+    p.w = h->patch_w; p.bias = h->patch_b; p.out = h->vis_raw;
+    if (h->split && h->patch_s) { p.w_split = h->patch_s; p.w_inv = h->patch_inv; p.split_rows = h->H1; }
+    p.tile_counter = tile_counter; p.err_flag = h->err_flag;
+    launch_patch_projection(p, h->num_cus, s, h);
+}
+
+}  // namespace
+
+// ---- LayoutLMv3, stage 0 (Stage0, capi_internal.h), shared by ee_forward and ee_embedding_inputs: the packed layout of the batch ... ----
+void mmee::capi::stage0_prep(ee_handle* h, const Stage0& a, hipStream_t s) {
+    const ee_config& c = h->cfg;
+    const int G = c.input_size / c.patch_size;
+    const size_t off = (size_t)a.slot * ((size_t)c.max_docs + 1);
+    PrepArgs pa{};
+    pa.input_ids = (const long long*)a.input_ids;
+    pa.attention_mask = (const long long*)a.attention_mask;
+    pa.bbox = (const long long*)a.bbox;
+    pa.position_ids = (const long long*)a.position_ids;
+    pa.token_type_ids = (const long long*)a.token_type_ids; pa.type_vocab = c.type_vocab_size;
+    pa.B = a.B; pa.T = a.T; pa.Pv = G * G + 1; pa.G = G;
+    pa.pad_id = c.pad_token_id; pa.vocab = c.vocab_size; pa.max_2d = c.max_2d_position_embeddings; pa.max_pos = c.max_position_embeddings;
+    pa.dense_rows = a.dense_rows;
+    pa.text_dst = h->text_dst; pa.emb_pos = h->emb_pos; pa.ntext = h->ntext;
+    pa.doc_off = h->doc_off + off; pa.x_src = h->x_src + off; pa.doc_orig = h->doc_orig + off;
+    pa.meta = h->meta[0]; pa.counts = h->counts + a.slot; pa.err_flag = h->err_flag;
+    launch_prep(pa, s);
+}
+
+// ... text and visual embeddings, the inputs of the embedding exits
+void mmee::capi::stage0_embed(ee_handle* h, const Stage0& a, hipStream_t s) {
+    const ee_config& c = h->cfg;
+    const int G = c.input_size / c.patch_size, Pv = G * G + 1, H = c.hidden_size, B = a.B, T = a.T;
+    const int tch = (T + 31) / 32, vch = (Pv + 31) / 32;
+    EmbedArgs ea{};
+    ea.input_ids = (const long long*)a.input_ids; ea.token_type_ids = (const long long*)a.token_type_ids; ea.bbox = (const long long*)a.bbox;
+    ea.emb_pos = h->emb_pos; ea.text_dst = h->text_dst; ea.ntext = h->ntext; ea.doc_off = h->doc_off + (size_t)a.slot * ((size_t)c.max_docs + 1);
+    ea.B = B; ea.T = T; ea.Pv = Pv; ea.H = H; ea.cs = c.coordinate_size; ea.ss = c.shape_size; ea.max_2d = c.max_2d_position_embeddings;
+    ea.vocab = c.vocab_size; ea.type_vocab = c.type_vocab_size;
+    ea.inputs_embeds = a.inputs_embeds;
+    ea.word = h->word; ea.type = h->type; ea.pos = h->pos; ea.xtab = h->xtab; ea.ytab = h->ytab; ea.htab = h->htab; ea.wtab = h->wtab;
+    ea.ln1_g = h->emb_g; ea.ln1_b = h->emb_b; ea.eps1 = c.layer_norm_eps;
+    ea.ln2_g = h->ln_g; ea.ln2_b = h->ln_b; ea.eps2 = c.layer_norm_eps;
+    ea.X = h->X;
+    if (h->split) { ea.Xs = h->Xs; ea.split_scale = mmee::kSplitScaleX; ea.err_flag = h->err_flag; }      // split mode: the embeddings exist as split planes only
+    ea.text_part = a.pooled[MMEE_EXIT_TEXT_AVG] ? h->text_part : nullptr;
+    ea.cat_part = a.pooled[MMEE_EXIT_TEXT_VISUAL_CONCAT] ? h->cat_part : nullptr;
+    ea.cat_chunks = tch + vch;
+    { ProfScope ps(h, P_EMBT, s); launch_embed_text(ea, s); }
+
+    handle_patch_projection(h, a.pixel_values, B, a.patch_tile_counter, s);
+
+    EmbedArgs va = ea;
+    va.ln1_g = h->norm_g; va.ln1_b = h->norm_b; va.eps1 = 1e-6f;        // layoutlmv3.norm = LayerNorm(eps=1e-6), HF:563
+    va.cls_token = h->cls_token; va.pos_embed = h->pos_embed; va.vis_raw = h->vis_raw;
+    va.vis_part = a.pooled[MMEE_EXIT_VISION_AVG] ? h->vis_part : nullptr;
+    {
+        ProfScope ps(h, P_EMBV, s);
+        launch_embed_visual(va, s);
+        if (a.pooled[MMEE_EXIT_VISION_AVG]) launch_pool_finish(h->vis_part, vch, H, (float)Pv, a.pooled[MMEE_EXIT_VISION_AVG], B, s);
+        if (a.pooled[MMEE_EXIT_TEXT_AVG]) launch_pool_finish(h->text_part, tch, H, (float)T, a.pooled[MMEE_EXIT_TEXT_AVG], B, s);
+        if (a.pooled[MMEE_EXIT_TEXT_VISUAL_CONCAT])
+            launch_pool_finish(h->cat_part, tch + vch, H, (float)(T + Pv), a.pooled[MMEE_EXIT_TEXT_VISUAL_CONCAT], B, s);
+    }
+}
+
+namespace {
+
 __global__ void zero_words_kernel(int* __restrict__ a, int na, int* __restrict__ b, int nb) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < na + nb; i += gridDim.x * blockDim.x) {
         if (i < na) a[i] = 0;
@@ -266,17 +340,7 @@ struct Forward {
     const float* x_out() const { return x_split ? h->Xs : h->X; }
     float x_inv() const { return x_split ? 1.0f / mmee::kSplitScaleX : 0.f; }
 
-    // patch projection -> vis_raw [B * NP][H] (launch_patch_projection).  Split mode: the split patches are staged in H1, idle until the
-    // first FFN.
-    void patch_projection() {
-        ProfScope ps(h, P_GPATCH, s);
-        PatchProjection p{};
-        p.pix = a.pixel_values; p.B = B; p.C = c.num_channels; p.R = c.input_size; p.P = c.patch_size; p.H = H;
-        p.w = h->patch_w; p.bias = h->patch_b; p.out = h->vis_raw;
-        if (sp && h->patch_s) { p.w_split = h->patch_s; p.w_inv = h->patch_inv; p.split_rows = h->H1; }
-        p.tile_counter = next_head(); p.err_flag = h->err_flag;
-        launch_patch_projection(p, cus, s, h);
-    }
+    void patch_projection() { handle_patch_projection(h, a.pixel_values, B, next_head(), s); }
 
     // ---- BEiT / DiT: uniform 197-row documents, BeitEmbeddings = patch conv + cls + absolute position embeddings ----
     void embed_beit() {
@@ -285,23 +349,16 @@ struct Forward {
         { ProfScope ps(h, P_EMBV, s); launch_embed_beit(h->vis_raw, h->cls_token, c.use_abs_pos ? h->pos_embed : nullptr, B, Pv, H, h->X, s); }
     }
 
-    // ---- LayoutLMv3: packed layout of stage 0, text and visual embeddings, the inputs of the embedding exits ----
+    // ---- LayoutLMv3: stage 0 (stage0_prep / stage0_embed above), with the attention index of the call's layers between its two halves ----
     void embed_layoutlmv3() {
-        PrepArgs pa{};
-        pa.input_ids = (const long long*)a.input_ids;
-        pa.attention_mask = (const long long*)a.attention_mask;
-        pa.bbox = (const long long*)a.bbox;
-        pa.position_ids = (const long long*)a.position_ids;
-        pa.token_type_ids = (const long long*)a.token_type_ids; pa.type_vocab = c.type_vocab_size;
-        pa.B = B; pa.T = T; pa.Pv = Pv; pa.G = G;
-        pa.pad_id = c.pad_token_id; pa.vocab = c.vocab_size; pa.max_2d = c.max_2d_position_embeddings; pa.max_pos = c.max_position_embeddings;
-        pa.dense_rows = (a.flags & MMEE_FLAG_DENSE_ROWS) ? 1 : 0;
-        pa.text_dst = h->text_dst; pa.emb_pos = h->emb_pos; pa.ntext = h->ntext;
-        pa.doc_off = S_doc_off(0); pa.x_src = S_x_src(0); pa.doc_orig = S_doc_orig(0);
-        pa.meta = h->meta[0]; pa.counts = h->counts; pa.err_flag = h->err_flag;
+        Stage0 st{};
+        st.input_ids = a.input_ids; st.attention_mask = a.attention_mask; st.bbox = a.bbox; st.pixel_values = a.pixel_values;
+        st.token_type_ids = a.token_type_ids; st.position_ids = a.position_ids; st.inputs_embeds = embeds_in;
+        st.B = B; st.T = T; st.dense_rows = (a.flags & MMEE_FLAG_DENSE_ROWS) ? 1 : 0; st.slot = 0;
+        for (int i = 0; i < c.n_embedding_exits; ++i) st.pooled[c.embedding_exits[i]] = h->pooled[c.embedding_exits[i]];
         {
             ProfScope ps(h, P_PREP, s);
-            launch_prep(pa, s);
+            stage0_prep(h, st, s);
             // attention_pair.hip skips the key flags in the full key tiles of a document without a masked key inside: one word per document
             if (sp && !use_idx) launch_doc_flags(h->meta[0], S_doc_off(0), B, h->doc_flags, s);
             if (h->pair_idx && use_idx) {    // bucket indices of every (query, key) pair, once per forward: shared by all heads and layers
@@ -316,39 +373,8 @@ struct Forward {
                                             h->pair_idx, h->idx_stride, max_len, s);
             }
         }
-
-        bool need[3] = {false, false, false};
-        for (int i = 0; i < c.n_embedding_exits; ++i) need[c.embedding_exits[i]] = true;
-        const int tch = (T + 31) / 32, vch = (Pv + 31) / 32;
-        EmbedArgs ea{};
-        ea.input_ids = pa.input_ids; ea.token_type_ids = (const long long*)a.token_type_ids; ea.bbox = pa.bbox;
-        ea.emb_pos = h->emb_pos; ea.text_dst = h->text_dst; ea.ntext = h->ntext; ea.doc_off = S_doc_off(0);
-        ea.B = B; ea.T = T; ea.Pv = Pv; ea.H = H; ea.cs = c.coordinate_size; ea.ss = c.shape_size; ea.max_2d = c.max_2d_position_embeddings;
-        ea.vocab = c.vocab_size; ea.type_vocab = c.type_vocab_size;
-        ea.inputs_embeds = embeds_in;
-        ea.word = h->word; ea.type = h->type; ea.pos = h->pos; ea.xtab = h->xtab; ea.ytab = h->ytab; ea.htab = h->htab; ea.wtab = h->wtab;
-        ea.ln1_g = h->emb_g; ea.ln1_b = h->emb_b; ea.eps1 = c.layer_norm_eps;
-        ea.ln2_g = h->ln_g; ea.ln2_b = h->ln_b; ea.eps2 = c.layer_norm_eps;
-        ea.X = h->X;
-        if (sp) { ea.Xs = h->Xs; ea.split_scale = mmee::kSplitScaleX; ea.err_flag = h->err_flag; }      // split mode: the embeddings exist as split planes only
-        ea.text_part = need[MMEE_EXIT_TEXT_AVG] ? h->text_part : nullptr;
-        ea.cat_part = need[MMEE_EXIT_TEXT_VISUAL_CONCAT] ? h->cat_part : nullptr;
-        ea.cat_chunks = tch + vch;
-        { ProfScope ps(h, P_EMBT, s); launch_embed_text(ea, s); }
-
-        patch_projection();
-
-        EmbedArgs va = ea;
-        va.ln1_g = h->norm_g; va.ln1_b = h->norm_b; va.eps1 = 1e-6f;        // layoutlmv3.norm = LayerNorm(eps=1e-6), HF:563
-        va.cls_token = h->cls_token; va.pos_embed = h->pos_embed; va.vis_raw = h->vis_raw;
-        va.vis_part = need[MMEE_EXIT_VISION_AVG] ? h->vis_part : nullptr;
-        {
-            ProfScope ps(h, P_EMBV, s);
-            launch_embed_visual(va, s);
-            if (need[MMEE_EXIT_VISION_AVG]) launch_pool_finish(h->vis_part, vch, H, (float)Pv, h->pooled[0], B, s);
-            if (need[MMEE_EXIT_TEXT_AVG]) launch_pool_finish(h->text_part, tch, H, (float)T, h->pooled[1], B, s);
-            if (need[MMEE_EXIT_TEXT_VISUAL_CONCAT]) launch_pool_finish(h->cat_part, tch + vch, H, (float)(T + Pv), h->pooled[2], B, s);
-        }
+        st.patch_tile_counter = next_head();
+        stage0_embed(h, st, s);
     }
 
     // Q | K | V projection of every row of the stage, A row r read from A[rows[r]] (rows null: dense)
@@ -911,6 +937,42 @@ int ee_graph_launch(ee_handle* h, int32_t graph_id, const double* thresholds, co
     const int rc_post = forward_post(h, s);
     if (rc_post) return rc_post;
     return launch_status(h, "ee_graph_launch");
+}
+
+// ---- stage 0 alone: the inputs of the embedding-level exit heads without the encoder behind them (include/mmee.h) ------------------------
+// Its layout goes to the stage slot no forward reads back (E + 1), so the stage counts of the last forward stay what they were; the packed
+// rows land in X / Xs, which every forward rewrites first.
+int ee_embedding_inputs(ee_handle* h, const int64_t* input_ids, const int64_t* attention_mask, const int64_t* bbox, const float* pixel_values,
+                        const int64_t* token_type_ids, const int64_t* position_ids, int32_t B, int32_t T, float* out_vision, float* out_text,
+                        float* out_concat, void* stream) {
+    if (!h) return 1;
+    const ee_config& c = h->cfg;
+    if (c.arch == MMEE_ARCH_BEIT)
+        return fail(h, "ee_embedding_inputs: embedding-level exits belong to LayoutLMv3 handles; this is an MMEE_ARCH_BEIT handle");
+    if (!h->finalized) return fail(h, "ee_embedding_inputs: call ee_finalize after loading the parameters");
+    if (!out_vision && !out_text && !out_concat) return fail(h, "ee_embedding_inputs: out_vision, out_text and out_concat are all NULL: nothing to compute");
+    if (!input_ids || !bbox || !pixel_values) return fail(h, "ee_embedding_inputs: input_ids, bbox and pixel_values are required");
+    if (B < 1 || B > c.max_docs) return fail(h, "ee_embedding_inputs: B=%d outside [1, max_docs=%d]", B, c.max_docs);
+    if (T < 1 || T > c.max_text_len) return fail(h, "ee_embedding_inputs: T=%d outside [1, max_text_len=%d]", T, c.max_text_len);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (const int rc = forward_pre(h, s)) return rc;
+    Stage0 st{};
+    st.input_ids = input_ids; st.attention_mask = attention_mask; st.bbox = bbox; st.pixel_values = pixel_values;
+    st.token_type_ids = token_type_ids; st.position_ids = position_ids;
+    st.inputs_embeds = h->next_inputs_embeds;          // one-shot, as in ee_forward: this call consumes it
+    h->next_inputs_embeds = nullptr;
+    st.B = B; st.T = T; st.slot = c.n_embedding_exits + c.n_encoder_exits + 1;
+    st.pooled[MMEE_EXIT_VISION_AVG] = out_vision; st.pooled[MMEE_EXIT_TEXT_AVG] = out_text; st.pooled[MMEE_EXIT_TEXT_VISUAL_CONCAT] = out_concat;
+    // the error word and the patch GEMM's queue heads, as in front of a forward (which zeroes all heads again before it hands any out)
+    hipLaunchKernelGGL(zero_words_kernel, dim3(32), dim3(256), 0, s, h->err_flag, 4, h->queue_heads, std::min(h->n_queue_heads, 128));
+    st.patch_tile_counter = h->n_queue_heads >= 128 ? h->queue_heads : nullptr;
+    const bool prof = h->prof_on;                      // ee_profile times forwards: its records stay those of the last one
+    h->prof_on = false;
+    stage0_prep(h, st, s);
+    stage0_embed(h, st, s);
+    h->prof_on = prof;
+    if (const int rc = forward_post(h, s)) return rc;
+    return launch_status(h, "ee_embedding_inputs");
 }
 
 int ee_graph_destroy(ee_handle* h, int32_t graph_id) {

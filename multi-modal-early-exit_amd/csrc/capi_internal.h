@@ -1,7 +1,7 @@
 // What the translation units of the C-ABI (include/mmee.h) share: the handle, its parameter / weight records, the error helpers every entry
 // point returns through, the allocator and the profiling scope.  Private to csrc/capi*.hip:
 //   capi.hip          the handle's error ring and allocator, and the loader (ee_create, ee_load_tensor, ee_finalize, ee_destroy)
-//   capi_forward.hip  the forward schedule (Forward, ee_forward) and its captured-graph form (ee_graph_*)
+//   capi_forward.hip  the forward schedule (Forward, ee_forward), its captured-graph form (ee_graph_*) and its stage 0 alone (ee_embedding_inputs)
 //   capi_query.hip    what reads the last forward back or arms the next one (ee_profile*, ee_stream_next, ee_last_*, ee_suggest_probe_mask, ee_set_*)
 //   capi_tools.hip    entry points that never see a handle (clock stamps, policy sweeps, pack / unpack, image feed, the GEMM micro-benchmarks)
 //   capi_debug_attention.hip, capi_debug_rows.hip, capi_debug_xprobe.hip, capi_debug_exit.hip, capi_debug_patch.hip   the ee_debug_* hooks of the
@@ -255,6 +255,24 @@ struct PatchProjection {
     int *tile_counter, *err_flag;
 };
 void launch_patch_projection(const PatchProjection& p, int num_cus, hipStream_t s, ee_handle* prof);
+
+// Stage 0 of a LayoutLMv3 call, as ee_forward and ee_embedding_inputs run it (capi_forward.hip): the packed layout of the batch, the text
+// and visual embeddings into the handle's X / Xs, and the (B, H) means over every position that the embedding-level exits read.
+// stage0_prep is launch_prep; stage0_embed is launch_embed_text, the patch projection, launch_embed_visual and one launch_pool_finish per
+// mean that is asked for.  The forward builds its attention index between the two.  Both time their launches under the handle's ee_profile.
+struct Stage0 {
+    const int64_t *input_ids, *attention_mask, *bbox;
+    const float* pixel_values;
+    const int64_t *token_type_ids, *position_ids;
+    const float* inputs_embeds;      // (B, T, H) read in place of the word-embedding rows, or null
+    int B, T;
+    int dense_rows;                  // MMEE_FLAG_DENSE_ROWS
+    int slot;                        // which stage's doc_off / x_src / doc_orig / counts receive the layout (the forward: 0)
+    float* pooled[3];                // by MMEE_EXIT_*: where the (B, H) mean goes; null: not computed
+    int* patch_tile_counter;         // the patch GEMM's work-queue heads (zeroed), or null: static grid
+};
+void stage0_prep(ee_handle* h, const Stage0& a, hipStream_t s);
+void stage0_embed(ee_handle* h, const Stage0& a, hipStream_t s);
 
 // Device scratch of one entry point (the ee_debug_* hooks, ee_lte_targets): zeroed hipMalloc, freed on every way out of the scope.
 struct Scratch {

@@ -15,7 +15,7 @@ from typing import Dict, Mapping, Optional, Sequence, Union
 import numpy as np
 
 from . import capi
-from .config import ExitRule, ModelConfig, check_patience_spec
+from .config import EMBEDDING_EXITS, ExitRule, ModelConfig, check_patience_spec
 
 try:  # torch is plumbing (device tensors / streams); importing it must not be the reason the product "works"
     import torch
@@ -415,6 +415,54 @@ class EarlyExitEngine:
         return EngineOutput(out_logits, out_exit, out_conf, all_logits, all_crit, head_logits, head_crit, hidden, hs, att)
 
     __call__ = forward
+
+    def embedding_inputs(self, input_ids=None, attention_mask=None, bbox=None, pixel_values=None, token_type_ids=None, position_ids=None,
+                         kinds: Optional[Sequence[str]] = None) -> Dict[str, "torch.Tensor"]:
+        """The rows the embedding-level exit heads read, from stage 0 of the forward alone (``ee_embedding_inputs``, include/mmee.h): no
+        encoder layer runs.  Returns ``{kind: (B,H) float32 device tensor}`` for ``kinds``, any non-empty subset of
+        ``config.EMBEDDING_EXITS``, in the reference's order (vision, text, concat); default: the configuration's embedding exits.  Works
+        on every LayoutLMv3 engine, whichever embedding exits it names; the bits are those a ``forward`` of this engine feeds the heads.
+        The text and concat means run over all T positions of the call, padding included (the reference pads to ``max_length``): call at
+        the T that deployment runs.  Inputs are converted as in ``forward``; the call only enqueues on the current stream, and out-of-range
+        inputs are reported as after ``forward`` (by the next call, or ``check()`` once a forward has run)."""
+        if not self._finalized:
+            raise capi.MMEEError("load_weights() has not been called")
+        if self.beit:
+            raise ValueError("embedding_inputs: embedding-level exits belong to LayoutLMv3; an image-only model has none")
+        kinds = list(self.exit_config.embedding_exits) if kinds is None else [str(k) for k in kinds]
+        unknown = [k for k in kinds if k not in EMBEDDING_EXITS]
+        if unknown:
+            raise ValueError(f"embedding_inputs: {unknown} not among {list(EMBEDDING_EXITS)}")
+        kinds = [k for k in EMBEDDING_EXITS if k in kinds]
+        if not kinds:
+            raise ValueError("embedding_inputs: no kinds (the configuration names no embedding-level exit: pass kinds=)")
+        R, H = self.cfg.input_size, self.cfg.hidden_size
+        px = self._dev(pixel_values, torch.float32, "pixel_values")
+        ids = self._dev(input_ids, torch.int64, "input_ids")
+        if ids.dim() != 2:
+            raise ValueError("input_ids must be (B,T)")
+        B, T = ids.shape
+        if bbox is None:
+            bbox = torch.zeros((B, T, 4), dtype=torch.int64, device=self.device)       # EE/models/LayoutLMv3.py:433-436
+        am = self._dev(attention_mask, torch.int64, "attention_mask", required=False)
+        bb = self._dev(bbox, torch.int64, "bbox")
+        tt = self._dev(token_type_ids, torch.int64, "token_type_ids", required=False)
+        ps = self._dev(position_ids, torch.int64, "position_ids", required=False)
+        if tuple(bb.shape) != (B, T, 4) or tuple(px.shape) != (B, self.cfg.num_channels, R, R):
+            raise ValueError(f"bbox must be (B,T,4) and pixel_values (B,{self.cfg.num_channels},{R},{R}); got "
+                             f"{tuple(bb.shape)} / {tuple(px.shape)}")
+        for t, n in ((am, "attention_mask"), (tt, "token_type_ids"), (ps, "position_ids")):
+            if t is not None and tuple(t.shape) != (B, T):
+                raise ValueError(f"{n} must be (B,T)")
+        out = {k: torch.empty((B, H), dtype=torch.float32, device=self.device) for k in kinds}
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            rc = self.lib.ee_embedding_inputs(self._h, p(ids), p(am), p(bb), p(px), p(tt), p(ps), B, T, *[p(out.get(k)) for k in EMBEDDING_EXITS],
+                                              stream)
+        capi.check(rc, self._h, "ee_embedding_inputs")
+        self._keepalive = (ids, am, bb, px, tt, ps)   # borrowed by the enqueued kernels until the stream drains
+        return out
 
     def forward_stream(self, *args, **kw) -> ResultStream:
         """``forward`` with MMEE_FLAG_STREAM_RESULTS (include/mmee.h): same arguments, same device outputs (``.output``), and the returned

@@ -39,8 +39,18 @@ W2 tanh(W1 x + b1) + b2 (``ee_mlp_head_fit_gate``: the two-layer ramp fit's laun
 point reached by descent from the start.  It takes ``sample_weight`` (``ee_mlp_head_fit_gate_weighted``): with ``reach_weights`` gate e is fitted
 on the documents no earlier exit released, the only ones it is ever asked about.
 
-This is not a trainer: distilled gates, sample weights for one-layer gates, embedding-level exits, the final classifier, per-exit LTE loss
-weights, mini-batches and an unfrozen backbone are out of scope.
+The embedding-level exit heads (``vision_exit_embeddings``, ``text_exit_embeddings``, ``concat_exit_embeddings``; EE/models/LayoutLMv3.py:320-340)
+are heads of the same kind on other rows: the (B,H) means over every position of the visual embeddings, the text embeddings and the
+LayerNorm of both (:466, 520, 582), which do not depend on the encoder.  ``engine.embedding_inputs`` (``ee_embedding_inputs``) returns them
+from stage 0 of the forward alone, ``collect_embedding_features`` gathers them without running a layer, and ``embedding_exits=True`` on
+``collect_exit_features`` / ``collect_distill_features`` / ``collect_gate_features`` puts them in front of the CLS rows, in the forward's exit
+order.  The fits take that as any (E,N,H); ``state_dict(cfg, embedding_exits=True)`` of the four fit classes names the first heads by their
+modules; a policy scan's exit index is then the feature row, which is all ``reach_weights`` needs.  Without the flag a configuration that
+names an embedding-level exit is refused, as before.  The text and concat means run over all T positions of the call, padding included:
+the same page padded to another T has another feature, so collect at the T that deployment runs (the reference pads to ``max_length``).
+
+This is not a trainer: distilled gates, sample weights for one-layer gates, the LTE classifier at embedding-level exits, the final
+classifier, per-exit LTE loss weights, mini-batches and an unfrozen backbone are out of scope.
 
 Reloading heads into an engine that holds captured graphs does not re-capture them: capture again after ``load_weights``.
 """
@@ -57,15 +67,21 @@ from .engine import _require_torch_cuda, torch
 
 STATUS = {0: "converged", 1: "max_evals", 2: "line_search"}
 LTE_MAX_EVALS = 1000           # fit_lte_classifier's default budget; its docstring says where it comes from
+_KEYS = ("input_ids", "attention_mask", "bbox", "pixel_values", "token_type_ids", "position_ids")
+# checkpoint module of each embedding-level exit head (EE/models/LayoutLMv3.py:320-340)
+_EMB_HEAD = {"vision_avg": "vision_exit_embeddings", "text_avg": "text_exit_embeddings", "text_visual_concat": "concat_exit_embeddings"}
 
 
-def _dump_all(engine, batches, **want):
-    """Per batch: the CLS rows (E,n,H) leaving the configured encoder exit layers, and the dump-all forward's whole output."""
-    layers = torch.tensor(engine.cfg.exit_config.encoder_exit_layers, dtype=torch.int64, device=engine.device)
-    keys = ("input_ids", "attention_mask", "bbox", "pixel_values", "token_type_ids", "position_ids")
+def _dump_all(engine, batches, embedding_exits=False, **want):
+    """Per batch: the CLS rows (E,n,H) leaving the configured encoder exit layers, and the dump-all forward's whole output.  With
+    ``embedding_exits`` the (n_emb,n,H) pooled rows of ``engine.embedding_inputs`` stand in front of the CLS rows: the forward's exit order."""
+    ec = engine.cfg.exit_config
+    layers = torch.tensor(ec.encoder_exit_layers, dtype=torch.int64, device=engine.device)
+    n_emb = len(ec.embedding_exits) if embedding_exits else 0
     for b in batches:
-        out = engine.forward(**{k: b[k] for k in keys if k in b and b[k] is not None}, dump_all=True, want_hidden_cls=True, **want)
-        yield out.hidden_cls.index_select(0, layers), out
+        out = engine.forward(**{k: b[k] for k in _KEYS if k in b and b[k] is not None}, dump_all=True, want_hidden_cls=True, **want)
+        rows = out.hidden_cls.index_select(0, layers)
+        yield (torch.cat([_embedding_rows(engine, b), rows]) if n_emb else rows), out
 
 
 def _cat_batches(per_batch):
@@ -76,7 +92,19 @@ def _cat_batches(per_batch):
     return [torch.cat(c, dim=1).contiguous() for c in cols]
 
 
-def _check_fittable(cfg: ModelConfig, head_layers: int = 1):
+def _check_embedding_exits(cfg: ModelConfig, embedding_exits: bool):
+    """What the ramp and the gate checks say about a configuration's embedding-level exits.  -> True when the configuration needs no
+    encoder exit (it has embedding-level ones and they are being fitted)."""
+    ec = cfg.exit_config
+    if embedding_exits and cfg.arch == "beit":
+        raise ValueError("embedding_exits=True: embedding-level exits belong to LayoutLMv3; a BEiT / DiT configuration has none")
+    if ec.embedding_exits and not embedding_exits:
+        raise ValueError(f"embedding-level exits {ec.embedding_exits} cannot be fitted by this call: the forward does not return their pooled "
+                         "inputs.  Pass embedding_exits=True to the collector and to state_dict (collect_embedding_features gathers the rows)")
+    return bool(embedding_exits and ec.embedding_exits)
+
+
+def _check_fittable(cfg: ModelConfig, head_layers: int = 1, embedding_exits: bool = False):
     ec = cfg.exit_config
     if str(ec.encoder_layer_strategy) != "ramp":
         raise ValueError("ramp exit heads are fitted for the ramp strategy only: the 2-way heads of a gate configuration are fitted by "
@@ -89,36 +117,63 @@ def _check_fittable(cfg: ModelConfig, head_layers: int = 1):
     elif ec.exit_head_num_layers != 1:
         raise ValueError("exit heads are fitted for exit_head_num_layers == 1 only (a two-layer head is not a convex problem: "
                          "fit_mlp_exit_heads fits it, collect_exit_features(..., head_layers=2) gathers its rows)")
-    if ec.embedding_exits:
-        raise ValueError(f"embedding-level exits {ec.embedding_exits} cannot be fitted: the forward does not return their pooled inputs")
-    if not ec.encoder_exit_layers:
+    if not _check_embedding_exits(cfg, embedding_exits) and not ec.encoder_exit_layers:
         raise ValueError("the configuration has no encoder exits")
 
 
-def collect_exit_features(engine, batches: Iterable[Mapping], head_layers: int = 1):
+def _embedding_rows(engine, batch, kinds=None):
+    """(n_emb,n,H): the pooled rows of one batch from ``engine.embedding_inputs``, stacked in the reference's order"""
+    rows = engine.embedding_inputs(**{k: batch[k] for k in _KEYS if k in batch and batch[k] is not None}, kinds=kinds)
+    return torch.stack(list(rows.values()))
+
+
+def collect_embedding_features(engine, batches: Iterable[Mapping], kinds=None):
+    """The inputs of the embedding-level exit heads over ``batches`` (dicts of ``engine.forward`` keyword inputs), from
+    ``engine.embedding_inputs`` alone: stage 0 of the forward, no encoder layer.  Returns the device tensor (n_emb,N,H) float32, one slab
+    per kind in the reference's order (vision, text, concat) -- ``kinds`` defaults to the configuration's embedding exits; any non-empty
+    subset of ``config.EMBEDDING_EXITS`` is allowed on any LayoutLMv3 engine.  Batches are concatenated in order.
+
+    The text and concat rows are means over all T positions of the call, padding included: the same page padded to another T has another
+    feature.  Collect at the T that deployment runs (the reference pads to ``max_length``)."""
+    if engine.cfg.arch == "beit":
+        raise ValueError("collect_embedding_features: embedding-level exits belong to LayoutLMv3; a BEiT / DiT engine has none")
+    return _cat_batches((_embedding_rows(engine, b, kinds),) for b in batches)[0]
+
+
+def collect_exit_features(engine, batches: Iterable[Mapping], head_layers: int = 1, embedding_exits: bool = False):
     """Dump-all forwards of ``engine`` over ``batches`` (dicts of ``engine.forward`` keyword inputs: ``input_ids``, ``attention_mask``,
     ``bbox``, ``pixel_values``, ...; ``pixel_values`` alone for the image-only DiT handle).  Returns the device tensor (E,N,H) float32
     of the CLS rows leaving the configured encoder exit layers -- the inputs of the heads ``encoder.early_exits.0 .. E-1``.
-    ``head_layers`` states which heads the rows are for: 1 (``fit_exit_heads``) or 2 (``fit_mlp_exit_heads``); the configuration must agree."""
-    _check_fittable(engine.cfg, head_layers)
-    return _cat_batches((rows,) for rows, _ in _dump_all(engine, batches))[0]
+    ``head_layers`` states which heads the rows are for: 1 (``fit_exit_heads``) or 2 (``fit_mlp_exit_heads``); the configuration must agree.
+
+    ``embedding_exits=True`` (LayoutLMv3): the configuration's embedding-level exits are fitted too.  The result is (n_emb + E,N,H) in the
+    forward's exit order -- the pooled rows of the embedding exits first, in the reference's order (vision, text, concat), then the encoder
+    exits -- from one dump-all forward plus one ``engine.embedding_inputs`` call per batch; a configuration without an encoder exit is then
+    allowed.  Without it a configuration that names an embedding-level exit is refused.  The pitfall of ``collect_embedding_features``
+    holds: the text and concat rows depend on the T the batch is padded to."""
+    _check_fittable(engine.cfg, head_layers, embedding_exits)
+    return _cat_batches((rows,) for rows, _ in _dump_all(engine, batches, embedding_exits))[0]
 
 
-def _encoder_rows_and_logits(engine, batches):
-    """-> (the CLS rows (E,N,H) leaving the encoder exit layers, those exits' policy logits (E,N,K) float32), embedding-level exits skipped"""
+def _rows_and_logits(engine, batches, embedding_exits=False):
+    """-> (the heads' input rows (E,N,H), those exits' policy logits (E,N,K) float32): the encoder exits, behind the embedding-level exits
+    when ``embedding_exits`` (else those are skipped)"""
     ec = engine.cfg.exit_config
     n_emb, n_enc = len(ec.embedding_exits), len(ec.encoder_exit_layers)
-    return tuple(_cat_batches((rows, out.all_logits[n_emb:n_emb + n_enc].to(torch.float32))
-                              for rows, out in _dump_all(engine, batches, want_all=True)))
+    first = 0 if embedding_exits else n_emb
+    return tuple(_cat_batches((rows, out.all_logits[first:n_emb + n_enc].to(torch.float32))
+                              for rows, out in _dump_all(engine, batches, embedding_exits, want_all=True)))
 
 
-def collect_distill_features(engine, batches: Iterable[Mapping], head_layers: int = 1):
+def collect_distill_features(engine, batches: Iterable[Mapping], head_layers: int = 1, embedding_exits: bool = False):
     """``collect_exit_features`` for documents without labels.  Returns two device tensors from the same dump-all forwards: ``features``
-    (E,N,H) float32 as above, and ``teacher_logits`` (N,K) float32, the final classifier's logits on the same documents (the last row of
-    ``all_logits``) -- the targets of ``fit_distilled_exit_heads`` / ``fit_distilled_mlp_exit_heads``.  Refusals and inputs are those of
-    ``collect_exit_features``; LayoutLMv3 handles and the image-only DiT handle are supported."""
-    _check_fittable(engine.cfg, head_layers)
-    feats, teacher = _cat_batches((rows, out.all_logits[-1:].to(torch.float32)) for rows, out in _dump_all(engine, batches, want_all=True))
+    (E,N,H) float32 as above ((n_emb + E,N,H) with ``embedding_exits=True``), and ``teacher_logits`` (N,K) float32, the final classifier's
+    logits on the same documents (the last row of ``all_logits``) -- the targets of ``fit_distilled_exit_heads`` /
+    ``fit_distilled_mlp_exit_heads``.  Refusals and inputs are those of ``collect_exit_features``; LayoutLMv3 handles and the image-only DiT
+    handle are supported."""
+    _check_fittable(engine.cfg, head_layers, embedding_exits)
+    feats, teacher = _cat_batches((rows, out.all_logits[-1:].to(torch.float32))
+                                  for rows, out in _dump_all(engine, batches, embedding_exits, want_all=True))
     return feats, teacher[0]
 
 
@@ -140,11 +195,13 @@ class HeadFit:
         """(E,N,K) float64 logits of the float32 heads on ``features`` (E,N,H), on the device."""
         return _linear_logits(self, features)
 
-    def state_dict(self, cfg: ModelConfig) -> Dict[str, np.ndarray]:
+    def state_dict(self, cfg: ModelConfig, embedding_exits: bool = False) -> Dict[str, np.ndarray]:
         """``{prefix}encoder.early_exits.{k}.out_proj.weight / .bias`` (host float32), ready for ``engine.load_weights`` next to the
-        backbone's tensors."""
-        _check_fittable(cfg)
-        return _out_proj_state(self, *_head_prefix(self, cfg))
+        backbone's tensors.  ``embedding_exits=True``: the fit's leading axis is n_emb + E (``collect_exit_features(...,
+        embedding_exits=True)``) and its first n_emb heads are named ``layoutlmv3.vision_exit_embeddings`` / ``.text_exit_embeddings`` /
+        ``.concat_exit_embeddings``, whichever the configuration has."""
+        _check_fittable(cfg, 1, embedding_exits)
+        return _out_proj_state(self, _head_stems(self, cfg, cfg.num_labels, "K", embedding_exits))
 
 
 def _linear_logits(fit, features):
@@ -153,14 +210,20 @@ def _linear_logits(fit, features):
     return torch.baddbmm(fit.bias.to(torch.float64).unsqueeze(1), X, fit.weight.to(torch.float64).transpose(1, 2))
 
 
-def _out_proj_state(fit, E, prefix):
-    """``{prefix}encoder.early_exits.{k}.out_proj.weight / .bias`` of the one-layer heads ``fit.weight``, ``fit.bias``, as host float32"""
+def _out_proj_state(fit, stems):
+    """``{stem}.out_proj.weight / .bias`` of the one-layer heads ``fit.weight``, ``fit.bias``, as host float32; ``stems``: ``_head_stems``"""
     w, b = fit.weight.cpu().numpy(), fit.bias.cpu().numpy()
     out = {}
-    for k in range(E):
-        out[f"{prefix}encoder.early_exits.{k}.out_proj.weight"] = np.ascontiguousarray(w[k])
-        out[f"{prefix}encoder.early_exits.{k}.out_proj.bias"] = np.ascontiguousarray(b[k])
+    for k, stem in enumerate(stems):
+        out[f"{stem}.out_proj.weight"] = np.ascontiguousarray(w[k])
+        out[f"{stem}.out_proj.bias"] = np.ascontiguousarray(b[k])
     return out
+
+
+def _mlp_state(fit, stems):
+    """``{stem}.dense.weight / .dense.bias / .out_proj.weight / .out_proj.bias`` of the two-layer heads of ``fit``, as host float32"""
+    blocks = [t.cpu().numpy() for t in (fit.dense_weight, fit.dense_bias, fit.weight, fit.bias)]
+    return {f"{stem}.{name}": np.ascontiguousarray(a[k]) for k, stem in enumerate(stems) for name, a in zip(_MLP_BLOCKS, blocks)}
 
 
 def _to_device(x, dtype, dev):
@@ -209,7 +272,8 @@ def reach_weights(exits, num_exits: int, device=None) -> "torch.Tensor":
     """The weight table of cascade-aware heads.  ``exits`` (N,): the exit index at which each document leaves under a policy, as a policy
     scan returns it (``criterion_scan_device``, ``early_exit``; a document no exit releases has index ``num_exits`` or more).  Returns
     (num_exits, N) float32 on the device: 1.0 where ``exits[n] >= e`` -- exit e is asked about document n because no earlier exit released
-    it -- else 0.0.  With embedding-level exits refused by the fits, the scan's exit index e < E is encoder head e.  Plain torch, no host
+    it -- else 0.0.  The scan's exit index is the row of features collected in exit order: encoder head e without
+    embedding-level exits, row e of ``collect_exit_features(..., embedding_exits=True)`` (embedding-level heads first) with them.  Plain torch, no host
     synchronisation; a device tensor stays on its device."""
     dev = exits.device if (torch is not None and isinstance(exits, torch.Tensor) and exits.is_cuda and device is None) \
         else _require_torch_cuda(device)
@@ -252,13 +316,18 @@ def _named(init, suffix, shape):
     return found[0]
 
 
-def _head_prefix(fit, cfg: ModelConfig):
-    """``fit.weight`` (E,K,H) against the configuration -> (E, the checkpoint prefix of the architecture)"""
-    E, K, H = fit.weight.shape
-    if E != len(cfg.exit_config.encoder_exit_layers) or K != cfg.num_labels or H != cfg.hidden_size:
-        raise ValueError(f"the fit is (E,K,H) = {(E, K, H)}, the configuration wants "
-                         f"{(len(cfg.exit_config.encoder_exit_layers), cfg.num_labels, cfg.hidden_size)}")
-    return E, "beit." if cfg.arch == "beit" else "layoutlmv3."
+def _head_stems(fit, cfg: ModelConfig, K: int, k_name: str, embedding_exits: bool = False):
+    """``fit.weight`` (E,K,H) against the configuration (``k_name``: how the message writes K) -> the checkpoint name of every head of the
+    fit without its tensor suffix, in the fit's row order: the forward's exit order.  With ``embedding_exits`` the configuration's
+    embedding-level heads come first, in the reference's order, then ``encoder.early_exits.{k}``."""
+    ec = cfg.exit_config
+    n_emb, n_enc = (len(ec.embedding_exits) if embedding_exits else 0), len(ec.encoder_exit_layers)
+    E, Kf, H = fit.weight.shape
+    if (E, Kf, H) != (n_emb + n_enc, K, cfg.hidden_size):
+        count = f"{n_emb} embedding-level + {n_enc} encoder exits: " if embedding_exits else ""
+        raise ValueError(f"the fit is (E,{k_name},H) = {(E, Kf, H)}, the configuration wants {count}{(n_emb + n_enc, K, cfg.hidden_size)}")
+    p = "beit." if cfg.arch == "beit" else "layoutlmv3."
+    return [p + _EMB_HEAD[kind] for kind in ec.embedding_exits[:n_emb]] + [f"{p}encoder.early_exits.{k}" for k in range(n_enc)]
 
 
 def fit_exit_heads(features, labels, l2: float = 1e-2, gtol: float = 1e-9, max_evals: int = 2000, history: int = 8, device=None,
@@ -399,17 +468,12 @@ class MlpHeadFit:
         """(E,N,K) float64 logits of the float32 heads on ``features`` (E,N,H), on the device."""
         return _mlp_logits(self, features)
 
-    def state_dict(self, cfg: ModelConfig) -> Dict[str, np.ndarray]:
+    def state_dict(self, cfg: ModelConfig, embedding_exits: bool = False) -> Dict[str, np.ndarray]:
         """``{prefix}encoder.early_exits.{k}.dense.weight / .bias`` and ``.out_proj.weight / .bias`` (host float32), ready for
-        ``engine.load_weights`` next to the backbone's tensors."""
-        _check_fittable(cfg, 2)
-        E, p = _head_prefix(self, cfg)
-        blocks = [t.cpu().numpy() for t in (self.dense_weight, self.dense_bias, self.weight, self.bias)]
-        out = {}
-        for k in range(E):
-            for name, a in zip(_MLP_BLOCKS, blocks):
-                out[f"{p}encoder.early_exits.{k}.{name}"] = np.ascontiguousarray(a[k])
-        return out
+        ``engine.load_weights`` next to the backbone's tensors.  ``embedding_exits=True``: as ``HeadFit.state_dict``, the first n_emb of the
+        fit's n_emb + E heads are the configuration's embedding-level heads."""
+        _check_fittable(cfg, 2, embedding_exits)
+        return _mlp_state(self, _head_stems(self, cfg, cfg.num_labels, "K", embedding_exits))
 
 
 def _mlp_logits(fit, features):
@@ -508,7 +572,7 @@ def collect_lte_features(engine, batches: Iterable[Mapping]):
     those exits' policy logits (``all_logits``: ramps the head's logits, gates ``classifier(gate input)``).  Any LayoutLMv3 engine with an
     encoder exit will do -- ramp or gate, 1- or 2-layer heads, with or without ``use_lte``; embedding-level exits are skipped."""
     _check_lte_cfg(engine.cfg)
-    return _encoder_rows_and_logits(engine, batches)
+    return _rows_and_logits(engine, batches)
 
 
 def lte_targets(logits, labels, device=None) -> "torch.Tensor":
@@ -612,7 +676,7 @@ def fit_lte_classifier(features, targets, loss: str = "mse", l2: float = 1e-2, g
 
 
 # ---- 2-way gate heads: the heads inference_strategy = "gate" lets decide ---------------------------------------------------------------------
-def _check_gate_cfg(cfg: ModelConfig, head_layers: int = 1):
+def _check_gate_cfg(cfg: ModelConfig, head_layers: int = 1, embedding_exits: bool = False):
     ec = cfg.exit_config
     if cfg.arch == "beit":
         raise ValueError("gate heads are fitted for LayoutLMv3 configurations only")
@@ -624,23 +688,24 @@ def _check_gate_cfg(cfg: ModelConfig, head_layers: int = 1):
     elif ec.exit_head_num_layers != 1:
         raise ValueError("gate heads are fitted for exit_head_num_layers == 1 only: a two-layer gate is not a convex problem, "
                          "fit_mlp_gate_heads fits it")
-    if ec.embedding_exits:
-        raise ValueError(f"embedding-level exits {ec.embedding_exits} cannot be fitted: the forward does not return their pooled inputs")
-    if not ec.encoder_exit_layers:
+    if not _check_embedding_exits(cfg, embedding_exits) and not ec.encoder_exit_layers:
         raise ValueError("the configuration has no encoder exits")
 
 
-def collect_gate_features(engine, batches: Iterable[Mapping]):
+def collect_gate_features(engine, batches: Iterable[Mapping], embedding_exits: bool = False):
     """Dump-all forwards of a gate-strategy ``engine`` over ``batches`` (dicts of ``engine.forward`` keyword inputs).  Returns two device
     tensors from the same forwards: ``features`` (E,N,H) float32, the CLS rows leaving the E configured encoder exit layers -- the inputs of
     the gates ``encoder.early_exits.0 .. E-1`` --, and ``gated_logits`` (E,N,K) float32, ``classifier(gate input)`` at those exits (the
-    policy logits, ``all_logits``).  Encoder exits only: embedding-level exits are skipped, as ``collect_lte_features`` skips them."""
+    policy logits, ``all_logits``).  By default encoder exits only: embedding-level exits are skipped, as ``collect_lte_features`` skips them.
+    ``embedding_exits=True``: the features are ``collect_exit_features(..., embedding_exits=True)``'s, (n_emb + E,N,H) with the pooled rows
+    of the embedding-level gates first, and ``gated_logits`` is (n_emb + E,N,K), ``all_logits[:n_emb + E]``; the same pitfall holds (the text
+    and concat rows depend on the T the batch is padded to)."""
     ec = engine.cfg.exit_config
     if engine.cfg.arch == "beit" or str(ec.encoder_layer_strategy) != "gate":
         raise ValueError("collect_gate_features needs a LayoutLMv3 engine of the gate strategy (encoder_layer_strategy = 'gate')")
-    if not ec.encoder_exit_layers:
+    if not ec.encoder_exit_layers and not (embedding_exits and ec.embedding_exits):
         raise ValueError("the configuration has no encoder exits")
-    return _encoder_rows_and_logits(engine, batches)
+    return _rows_and_logits(engine, batches, embedding_exits)
 
 
 def gate_targets(gated_logits, labels, device=None) -> "torch.Tensor":
@@ -679,14 +744,12 @@ class GateFit:
         device function the forward decides with (``sweep.gate_table``'s rows)."""
         return _gate_scores(self.logits(features))
 
-    def state_dict(self, cfg: ModelConfig) -> Dict[str, np.ndarray]:
+    def state_dict(self, cfg: ModelConfig, embedding_exits: bool = False) -> Dict[str, np.ndarray]:
         """``layoutlmv3.encoder.early_exits.{k}.out_proj.weight`` (2,H) / ``.bias`` (2,) (host float32), ready for ``engine.load_weights`` next
-        to the backbone's tensors."""
-        _check_gate_cfg(cfg)
-        E, K, H = self.weight.shape
-        if E != len(cfg.exit_config.encoder_exit_layers) or K != 2 or H != cfg.hidden_size:
-            raise ValueError(f"the fit is (E,2,H) = {(E, K, H)}, the configuration wants {(len(cfg.exit_config.encoder_exit_layers), 2, cfg.hidden_size)}")
-        return _out_proj_state(self, E, "layoutlmv3.")
+        to the backbone's tensors.  ``embedding_exits=True``: as ``HeadFit.state_dict``, the first n_emb of the fit's n_emb + E gates are the
+        configuration's embedding-level heads."""
+        _check_gate_cfg(cfg, 1, embedding_exits)
+        return _out_proj_state(self, _head_stems(self, cfg, 2, "2", embedding_exits))
 
 
 def fit_gate_heads(features, targets, l2: float = 1e-2, gtol: float = 1e-9, max_evals: int = 2000, history: int = 8, device=None,
@@ -744,15 +807,12 @@ class MlpGateFit:
         """(E,N) float64 gate scores of the float32 heads' float32 logits on ``features`` (E,N,H), as ``GateFit.scores``."""
         return _gate_scores(self.logits(features))
 
-    def state_dict(self, cfg: ModelConfig) -> Dict[str, np.ndarray]:
+    def state_dict(self, cfg: ModelConfig, embedding_exits: bool = False) -> Dict[str, np.ndarray]:
         """``layoutlmv3.encoder.early_exits.{k}.dense.weight`` (H,H) / ``.dense.bias`` (H,) / ``.out_proj.weight`` (2,H) / ``.out_proj.bias`` (2,)
-        (host float32), ready for ``engine.load_weights`` next to the backbone's tensors."""
-        _check_gate_cfg(cfg, 2)
-        E, K, H = self.weight.shape
-        if E != len(cfg.exit_config.encoder_exit_layers) or K != 2 or H != cfg.hidden_size:
-            raise ValueError(f"the fit is (E,2,H) = {(E, K, H)}, the configuration wants {(len(cfg.exit_config.encoder_exit_layers), 2, cfg.hidden_size)}")
-        blocks = [t.cpu().numpy() for t in (self.dense_weight, self.dense_bias, self.weight, self.bias)]
-        return {f"layoutlmv3.encoder.early_exits.{k}.{name}": np.ascontiguousarray(a[k]) for k in range(E) for name, a in zip(_MLP_BLOCKS, blocks)}
+        (host float32), ready for ``engine.load_weights`` next to the backbone's tensors.  ``embedding_exits=True``: as
+        ``HeadFit.state_dict``, the first n_emb of the fit's n_emb + E gates are the configuration's embedding-level heads."""
+        _check_gate_cfg(cfg, 2, embedding_exits)
+        return _mlp_state(self, _head_stems(self, cfg, 2, "2", embedding_exits))
 
 
 def fit_mlp_gate_heads(features, targets, l2: float = 1e-2, gtol: float = 1e-6, max_evals: int = 4000, history: int = 8, init="identity",
