@@ -25,6 +25,8 @@
  *                                                 (EE/thresh.py:184-215, EE/large_scale.py:68-84).
  *   ee_threshold_search_cost                    <- the same search against the reference's efficiency figures: per-exit cost weighted by the exit
  *                                                 distribution ("GFLOPs reduction", "Latency reduction": EE/eval.py:62-84, EE/analysis.py:29-102).
+ *   ee_threshold_refine                         <- no counterpart: a coordinate search on the same percentile grid that improves a search's vectors where
+ *                                                 the grid (P^(E1-1) vectors) cannot be enumerated; semantics below.
  *   ee_set_patience / ee_patience_scan /        <- EarlyExitInference.PATIENCE, declared by the reference (EE/models/EE_modules.py:
  *   ee_patience_sweep                              123-124, PABEE: Zhou et al., NeurIPS 2020) but not implemented there; semantics below.
  *   ee_set_exit_rule / ee_set_patience_vector / <- no counterpart: the reference implements neither rule.  Patient-and-confident (PCEE-BERT, Zhang et al.,
@@ -630,6 +632,56 @@ int ee_threshold_search_cost(const double* conf, const uint8_t* correct, const u
                              int64_t V, uint64_t seed, const uint8_t* mixtures, int32_t semantics, double* table, double* acc, double* mean_exit,
                              uint64_t* cost_sum, int32_t* front_count, uint64_t* front_cost_sum, int32_t* front_exit_sum, int32_t* front_hits,
                              uint32_t* front_vector, double* front_thresholds, void* stream);
+
+/*
+ * The threshold refinement: a local search on the device that IMPROVES candidate threshold vectors, for the models whose grid no search can
+ * enumerate (E1 = 24, P = 10: 10^23 vectors).  S independent chains of steepest-ascent coordinate search on the percentile grid, each from its
+ * own start, with no host round trip between rounds.  Starts are typically the front of a sampled ee_threshold_search_cost, or the vector under
+ * which nobody leaves early.
+ *
+ * Inputs: those of ee_threshold_search_cost -- conf dev double (E1,N) (for a '<' criterion pass the negated table, which is exact), correct dev
+ * uint8 (E1,N), cost dev uint32 (E1,N) or NULL for cost[e][n] = e, P thresholds per exit; 2 <= E1 <= 64, 1 <= N < 2^24, 2 <= P <= 64.
+ * Percentile table (E1,P): ee_threshold_search's, bit for bit; row E1-1 is 0.0.
+ * Exit rule: MMEE_SEARCH_POLICY only, what a forward does: exit(d, n) = the first e < E1-1 with conf[e][n] > table[e][d_e] (strict), else E1-1.
+ * MMEE_SEARCH_REFERENCE is not offered: nothing deploys it.
+ *
+ * Chains: 1 <= S <= 4096.  Chain s has a start, start[s] dev uint8 (E1,) digits in [0, P) (a digit >= P is clamped to P-1 as in the search; the
+ * last digit is unused), a hit value w_s, hit_value dev uint64 (S,), taken as min(w_s, 2^32 - 1): what one more correct document is worth in cost
+ * units, and a budget B_s, budget dev uint64 (S,); a NULL budget array means no budget.
+ *
+ * Score of a digit vector d: hits(d) = sum_n correct[exit(d,n)][n], exit_sum(d) = sum_n exit(d,n), cost_sum(d) = sum_n cost[exit(d,n)][n], an
+ * exact uint64 below 2^56, and J(d) = w hits(d) - cost_sum(d) as a signed 64-bit integer (|w hits| < 2^56: it cannot overflow).
+ *
+ * One round of a live chain at d: the neighbours of d are all d' that differ from d in exactly one digit (e in [0, E1-1), p in [0, P), d'_e = p);
+ * a neighbour is admissible iff cost_sum(d') <= B; the best neighbour is the admissible one with the largest J, ties to the lowest e, then the
+ * lowest p.  If J(best) > J(d) the chain moves there; otherwise it stops with status 0: no admissible single-exit change improves J.  A chain
+ * that has moved in every one of max_rounds rounds (1 <= max_rounds <= 4096) ends with status 1.  A chain whose start already has
+ * cost_sum > B ends with status 2, rounds 0, and its outputs describe the start.  J rises strictly with every move, so a chain cannot cycle.
+ *
+ * As it is computed: for a document with exit x0 under d and next firing exit x1 behind it (E1-1 when none), changing exit e < x0 moves it to e
+ * for exactly the digits whose threshold it beats -- a prefix of p, the table ascends --, changing e = x0 moves it on to x1 for the digits whose
+ * threshold it does not beat -- a suffix --, and changing e > x0 does nothing: all (E1-1) P neighbour scores come out of one pass of O(E1) work per
+ * document, as differences accumulated by integer atomics.  Where a prefix ends is decided by the strict compare of the values (through the
+ * searches' rank words), duplicated table values and confidences equal to a threshold included.
+ *
+ * Outputs, all dev; the first five describe the FINAL vector: digits uint8 (S,E1) (last column 0; required: it holds the chains' vectors while
+ * the call runs), thresholds double (S,E1) = table[e][d_e] (last column 0.0), hits int32 (S,), exit_sum int32 (S,), cost_sum uint64 (S,); rounds
+ * int32 (S,) = moves made, status int32 (S,) as above, start_hits int32 (S,), start_cost_sum uint64 (S,), table double (E1,P).  Every output but
+ * digits is optional (may be NULL).
+ *
+ * Everything is integers or copied doubles: the result is a pure function of the inputs and does not depend on the launch shape, on the order in
+ * which atomics arrive or on which other chains share the call.  The call only enqueues on `stream` -- a fixed list of max_rounds x 2 launches, in
+ * which the workgroups of a finished chain return at once --: nothing is uploaded, downloaded or waited for.  Its workspace holds
+ * S (E1-1) (P+1) x 16 bytes of difference arrays (ee_threshold_refine_workspace_bytes: all of it).
+ *
+ * Refusals, all before any device call: NULL conf / correct / start / hit_value / digits, the search's range checks of E1, N and P, S, max_rounds.
+ */
+int ee_threshold_refine(const double* conf, const uint8_t* correct, const uint32_t* cost, int32_t E1, int32_t N, int32_t P, int32_t S,
+                        const uint8_t* start, const uint64_t* hit_value, const uint64_t* budget, int32_t max_rounds, uint8_t* digits,
+                        double* thresholds, int32_t* hits, int32_t* exit_sum, uint64_t* cost_sum, int32_t* rounds, int32_t* status,
+                        int32_t* start_hits, uint64_t* start_cost_sum, double* table, void* stream);
+/* The bytes ee_threshold_refine allocates for its rounds (0 for arguments it would refuse): a pure function, no device. */
+size_t ee_threshold_refine_workspace_bytes(int32_t E1, int32_t N, int32_t P, int32_t S);
 
 /*
  * The evaluation report: the seven metrics the reference scores every exit and every policy's predictions with (METRICS of evaluate_checkpoint,

@@ -178,6 +178,8 @@ SYMBOLS = {
     "ee_threshold_search": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.c_int64, C.c_uint64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ee_threshold_search_cost": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_int64, C.c_uint64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp, _vp]),
+    "ee_threshold_refine": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ee_threshold_refine_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32]),
     "ee_msp_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_csf_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_gate_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),

@@ -311,6 +311,35 @@ int ee_threshold_search_cost(const double* conf, const uint8_t* correct, const u
     return launch_status(nullptr, who);
 }
 
+int ee_threshold_refine(const double* conf, const uint8_t* correct, const uint32_t* cost, int32_t E1, int32_t N, int32_t P, int32_t S,
+                        const uint8_t* start, const uint64_t* hit_value, const uint64_t* budget, int32_t max_rounds, uint8_t* digits,
+                        double* thresholds, int32_t* hits, int32_t* exit_sum, uint64_t* cost_sum, int32_t* rounds, int32_t* status,
+                        int32_t* start_hits, uint64_t* start_cost_sum, double* table, void* stream) {
+    const char* who = "ee_threshold_refine";
+    if (!conf || !correct || !start || !hit_value || !digits)
+        return fail(nullptr, "%s: NULL argument (conf, correct, start, hit_value and digits are required; cost, budget and the other outputs may be NULL)", who);
+    int64_t one = 1;                                                 // the searches' range checks of E1, N and P
+    if (search_refuse(who, E1, N, P, MMEE_SEARCH_SAMPLED, &one, nullptr, MMEE_SEARCH_POLICY)) return 1;
+    if (S < 1 || S > 4096) return fail(nullptr, "%s: S = %d chains, need 1 <= S <= 4096", who, S);
+    if (max_rounds < 1 || max_rounds > 4096) return fail(nullptr, "%s: max_rounds = %d, need 1 <= max_rounds <= 4096", who, max_rounds);
+    if (!have_device(who)) return 1;
+    const SearchPercentiles pc = search_percentiles(N, P);
+    RefineArgs a{};
+    a.conf = conf; a.correct = correct; a.cost = cost; a.E1 = E1; a.N = N; a.P = P; a.S = S; a.max_rounds = max_rounds; a.start = start;
+    a.hit_value = reinterpret_cast<const unsigned long long*>(hit_value); a.budget = reinterpret_cast<const unsigned long long*>(budget);
+    a.digits = digits; a.thresholds = thresholds; a.hits = hits; a.exit_sum = exit_sum; a.cost_sum = reinterpret_cast<unsigned long long*>(cost_sum);
+    a.rounds = rounds; a.status = status; a.start_hits = start_hits; a.start_cost_sum = reinterpret_cast<unsigned long long*>(start_cost_sum);
+    a.table = table;
+    if (!launch_threshold_refine(a, pc, reinterpret_cast<hipStream_t>(stream)))
+        return fail(nullptr, "%s: hipMallocAsync of the workspace failed (%zu bytes for the rounds)", who, threshold_refine_workspace_bytes(E1, N, P, S));
+    return launch_status(nullptr, who);
+}
+
+size_t ee_threshold_refine_workspace_bytes(int32_t E1, int32_t N, int32_t P, int32_t S) {
+    if (E1 < 2 || E1 > 64 || N < 1 || N >= (1 << 24) || P < 2 || P > 64 || S < 1 || S > 4096) return 0;
+    return threshold_refine_workspace_bytes(E1, N, P, S);
+}
+
 int ee_msp_table(const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, double* conf, uint8_t* correct,
                  void* stream) {
     if (!logits || !conf || E1 < 1 || N < 1 || K < 1) return fail(nullptr, "ee_msp_table: bad argument");

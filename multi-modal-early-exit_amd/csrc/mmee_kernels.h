@@ -293,6 +293,23 @@ struct SearchCostArgs {
     unsigned long long* front_cost_sum;      // [N + 1]
 };
 bool launch_threshold_search_cost(const SearchCostArgs& a, const SearchPercentiles& pc, hipStream_t s);
+// ee_threshold_refine (threshold_refine.hip): S chains of coordinate search on the searches' percentile grid, MMEE_SEARCH_POLICY's exit rule
+struct RefineArgs {
+    const double* conf;              // (E1,N)
+    const unsigned char* correct;    // (E1,N)
+    const unsigned* cost;            // (E1,N), or null: cost[e][n] = e
+    int E1, N, P, S, max_rounds;
+    const unsigned char* start;      // (S,E1) digits
+    const unsigned long long* hit_value;     // (S,)
+    const unsigned long long* budget;        // (S,) or null: none
+    unsigned char* digits;           // (S,E1): the chains' vectors, from the first launch on
+    double* thresholds;              // (S,E1) or null
+    int *hits, *exit_sum, *rounds, *status, *start_hits;             // (S,) or null
+    unsigned long long *cost_sum, *start_cost_sum;                   // (S,) or null
+    double* table;                   // (E1,P) or null
+};
+bool launch_threshold_refine(const RefineArgs& a, const SearchPercentiles& pc, hipStream_t s);
+size_t threshold_refine_workspace_bytes(int E1, int N, int P, int S);
 // ee_exit_metrics (exit_metrics.hip; include/mmee.h MMEE_METRIC_*, capi_tools.hip asserts the values agree)
 enum { kMetricAccuracy = 0, kMetricBrier = 1, kMetricNll = 2, kMetricF1Micro = 3, kMetricF1Macro = 4, kMetricEce = 5, kMetricAurc = 6,
        kMetricAvgConf = 7, kMetricCount = 8 };

@@ -216,6 +216,7 @@ class SearchResult:
     front_cost_sum: Optional[np.ndarray] = None      # (F,) uint64
     front_mean_cost: Optional[np.ndarray] = None     # (F,) cost_sum / N
     cost_sum: Optional["torch.Tensor"] = None        # (V,) int64 device tensor (``want_all=True``)
+    semantics: Optional[str] = None                  # "policy" / "reference", as ``threshold_search`` ran; ``threshold_refine(start=)`` asks for it
 
     def digits(self, v):
         """The percentile index per exit (E1 - 1 of them) of candidate vector ``v``: ``table[e, digits(v)[e]]`` are its thresholds."""
@@ -362,7 +363,7 @@ def threshold_search(logits, references=None, criterion="max_confidence", num_pe
     return SearchResult(table=sign * table.cpu().numpy(), front_thresholds=sign * f_thr[:F].cpu().numpy(), front_accuracy=hits / float(N),
                         front_mean_exit=sums / float(N), front_vector=f_vec[:F].cpu().numpy().view(np.uint32), front_hits=hits, front_exit_sum=sums,
                         num_vectors=V, num_samples=int(N), source=source, seed=int(seed) & _MASK64, mixtures=mix_host, accuracy=acc, mean_exit=mex,
-                        **extra)
+                        semantics=semantics, **extra)
 
 
 def exit_costs(cfg, attention_mask=None, text_rows=None, unit: float = 1e6) -> np.ndarray:
@@ -400,3 +401,226 @@ def exit_costs(cfg, attention_mask=None, text_rows=None, unit: float = 1e6) -> n
     if out.size and out.max() >= float(1 << 32):
         raise ValueError(f"exit_costs: {out.max():.0f} units of {unit:g} FLOPs do not fit 32 bits: choose a larger unit")
     return out.astype(np.uint32)
+
+
+# ---- the threshold refinement (ee_threshold_refine) -------------------------------------------------------------------------------------------
+_REFINE_STATUS = {0: "no admissible single-exit change improves J", 1: "max_rounds reached", 2: "the start is over its budget"}
+
+
+def _pareto_min_cost_max_hits(cost_sum, hits):
+    """Indices of the strict Pareto front of (cost down, hits up), ascending in cost (and, strictly, in hits); among equal (cost, hits) the
+    lowest index."""
+    order = sorted(range(len(hits)), key=lambda i: (int(cost_sum[i]), -int(hits[i]), i))
+    keep, best = [], -1
+    for i in order:
+        if int(hits[i]) > best:
+            keep.append(i)
+            best = int(hits[i])
+    return keep
+
+
+@dataclass
+class RefineResult:
+    """What ``threshold_refine`` found: one row per chain, numpy on the host.  ``thresholds`` are REAL thresholds of the criterion (for entropy
+    the negated table negated back), so that a row goes to ``forward(thresholds=)`` unchanged.  ``status``: 0 -- no admissible single-exit change
+    improves J --, 1 -- ``max_rounds`` moves made --, 2 -- the start was already over its budget (the row describes the start)."""
+    table: np.ndarray                       # (E1, P)
+    digits: np.ndarray                      # (S, E1) uint8, last column 0
+    thresholds: np.ndarray                  # (S, E1)
+    hits: np.ndarray                        # (S,) int32
+    exit_sum: np.ndarray                    # (S,) int32
+    cost_sum: np.ndarray                    # (S,) uint64
+    rounds: np.ndarray                      # (S,) int32: moves made
+    status: np.ndarray                      # (S,) int32
+    start_hits: np.ndarray                  # (S,) int32
+    start_cost_sum: np.ndarray              # (S,) uint64
+    hit_value: np.ndarray                   # (S,) uint64, as the chains took it (min(w, 2^32 - 1))
+    num_samples: int
+
+    @property
+    def accuracy(self):
+        return self.hits / float(self.num_samples)
+
+    @property
+    def mean_cost(self):
+        return self.cost_sum / float(self.num_samples)
+
+    @property
+    def mean_exit(self):
+        return self.exit_sum / float(self.num_samples)
+
+    @property
+    def J(self):
+        """w hits - cost_sum of every chain's final vector: Python ints."""
+        return [int(w) * int(h) - int(c) for w, h, c in zip(self.hit_value, self.hits, self.cost_sum)]
+
+    @property
+    def start_J(self):
+        return [int(w) * int(h) - int(c) for w, h, c in zip(self.hit_value, self.start_hits, self.start_cost_sum)]
+
+    def front(self):
+        """The chains on the strict Pareto front of (cost_sum down, hits up), as indices ascending in cost; ties go to the lowest chain."""
+        return _pareto_min_cost_max_hits(self.cost_sum, self.hits)
+
+    def select_index(self, min_accuracy=None, max_mean_cost=None, max_mean_exit=None) -> int:
+        if sum(x is not None for x in (min_accuracy, max_mean_cost, max_mean_exit)) != 1:
+            raise ValueError("select takes exactly one of min_accuracy, max_mean_cost and max_mean_exit")
+        acc, mc, me = self.accuracy, self.mean_cost, self.mean_exit
+        if min_accuracy is not None:
+            ok = [i for i in self.front() if acc[i] >= float(min_accuracy)]
+            if not ok:
+                raise ValueError(f"no chain reaches accuracy {min_accuracy} (best: {acc.max() if len(acc) else None})")
+            return ok[0]                         # accuracy rises along the front: the first is the cheapest
+        if max_mean_cost is not None:
+            ok = [i for i in self.front() if mc[i] <= float(max_mean_cost)]
+            if not ok:
+                raise ValueError(f"no chain has a mean cost <= {max_mean_cost} (lowest: {mc.min() if len(mc) else None})")
+            return ok[-1]
+        ok = [i for i in range(len(me)) if me[i] <= float(max_mean_exit)]
+        if not ok:
+            raise ValueError(f"no chain has a mean exit <= {max_mean_exit} (lowest: {me.min() if len(me) else None})")
+        return max(ok, key=lambda i: (int(self.hits[i]), -int(self.exit_sum[i]), -i))
+
+    def select(self, min_accuracy=None, max_mean_cost=None, max_mean_exit=None):
+        """One chain's thresholds as a plain list of E1 floats (what ``forward(thresholds=)`` takes), with ``SearchResult.select``'s meaning:
+        ``min_accuracy`` -- the CHEAPEST chain whose accuracy reaches it --, ``max_mean_cost`` / ``max_mean_exit`` -- the chain of HIGHEST accuracy
+        within the budget (the mean exit is not monotone along a cost front, so that one looks at every chain; at equal hits the lower mean exit,
+        then the lower chain).  Exactly one of the three; ``ValueError`` when no chain qualifies."""
+        return self.thresholds[self.select_index(min_accuracy, max_mean_cost, max_mean_exit)].tolist()
+
+
+def front_hit_values(result: SearchResult) -> np.ndarray:
+    """The natural trade-offs along a cost front, for ``threshold_refine(hit_value=)``: the ceilings of ``d cost_sum / d hits`` between
+    neighbouring front entries (F - 1 of them, uint64, clipped to 2^32 - 1): what the front itself pays for one more correct document there.
+    A front without costs (``threshold_search`` without ``cost=``) is read with its exit sums, the cost ``cost[e][n] = e``."""
+    cost = result.front_cost_sum if result.front_cost_sum is not None else result.front_exit_sum
+    out = []
+    for i in range(len(result.front_hits) - 1):
+        dc, dh = int(cost[i + 1]) - int(cost[i]), int(result.front_hits[i + 1]) - int(result.front_hits[i])
+        if dh <= 0 or dc < 0:
+            raise ValueError("not a front: hits and cost must rise along it")
+        out.append(min(-(-dc // dh), (1 << 32) - 1))
+    return np.array(out, dtype=np.uint64)
+
+
+def _host_ints(x, what):
+    a = x.cpu().numpy() if torch is not None and isinstance(x, torch.Tensor) else np.asarray(x)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{what}: integers, not {a.dtype}")
+    return a
+
+
+def threshold_refine(logits, references=None, criterion="max_confidence", num_per_exit: int = 10, start=None, hit_value=None, budget=None,
+                     cost=None, max_rounds: int = 256, device=None, budget_mean=None) -> RefineResult:
+    """Improve candidate threshold vectors by coordinate search on the device (ee_threshold_refine; include/mmee.h): every chain repeatedly takes
+    the single-exit change of largest ``J = hit_value * hits - cost_sum`` among those within its budget, until none improves J or ``max_rounds``
+    moves are made.  For the models whose grid ``threshold_search`` cannot enumerate (any E1 <= 64); the exit rule is the policy's.
+
+    ``logits`` / ``references`` / ``criterion`` / ``num_per_exit`` / ``cost``: as in ``threshold_search`` (an array with references, or a pair
+    ``(table, correct)``; ``cost`` (E1,) or (E1,N) integers, ``None``: the exit index).  ``start``: ``None`` -- one start with every digit
+    ``P - 1``: each exit's threshold is its maximum, nobody leaves early --, an integer array (S0,E1) of digits, or a ``SearchResult`` of the SAME
+    table with ``semantics="policy"``: its front entries are the starts.  ``hit_value``: an int or an integer array (W,) in [0, 2^32): what one
+    more correct document is worth in cost units (``front_hit_values``); with W > 1 the chains are the cross product, S = S0 W, chain s = (start
+    s // W, value s % W).  ``budget``: ``None``, an int or (S,) ints on ``cost_sum``; ``budget_mean`` the same divided by N."""
+    from .policy import threshold_criterion
+    st = threshold_criterion(criterion)
+    P = int(num_per_exit)
+    if not 2 <= P <= 64:
+        raise ValueError(f"num_per_exit = {num_per_exit}: 2 .. 64 thresholds per exit")
+    if not 1 <= int(max_rounds) <= 4096:
+        raise ValueError(f"max_rounds = {max_rounds}: 1 .. 4096")
+    pair = isinstance(logits, tuple)
+    if pair:
+        if len(logits) != 2:
+            raise ValueError("a precomputed table is the pair (table (E1,N), correct (E1,N))")
+        E1, n_docs = int(logits[0].shape[0]), int(logits[0].shape[1])
+    else:
+        if references is None:
+            raise ValueError("logits need the references")
+        E1, n_docs = int(np.shape(logits)[0]), int(np.shape(logits)[1])
+    if not 2 <= E1 <= 64:
+        raise ValueError(f"E1 = {E1}: 2 .. 64 exits")
+    if hit_value is None:
+        raise ValueError("hit_value: what one more correct document is worth in cost units (an int, or an integer array; front_hit_values)")
+    w = np.atleast_1d(_host_ints(hit_value, "hit_value"))
+    if w.ndim != 1 or w.size < 1 or int(w.min()) < 0 or int(w.max()) >= 1 << 32:
+        raise ValueError("hit_value: an int or an integer array (W,) with W >= 1 and values in [0, 2^32)")
+    start_result = start if isinstance(start, SearchResult) else None
+    if start is None:
+        dg = np.full((1, E1), P - 1, dtype=np.int64)
+    elif start_result is not None:
+        if start_result.table.shape != (E1, P):
+            raise ValueError(f"start: a SearchResult with a table {start_result.table.shape}, this call's is ({E1}, {P})")
+        if start_result.semantics != "policy":
+            raise ValueError('start: a SearchResult of semantics="policy" (the refinement walks as a forward does)')
+        if len(start_result.front_vector) < 1:
+            raise ValueError("start: an empty front")
+        dg = np.zeros((len(start_result.front_vector), E1), dtype=np.int64)
+        for i, v in enumerate(start_result.front_vector):
+            dg[i, :E1 - 1] = start_result.digits(v)
+    else:
+        dg = _host_ints(start, "start")
+        if dg.ndim != 2 or dg.shape[1] != E1 or dg.shape[0] < 1:
+            raise ValueError(f"start: an integer array (S0,{E1}) of percentile indices, S0 >= 1")
+        if dg[:, :E1 - 1].min() < 0 or dg[:, :E1 - 1].max() >= P:
+            raise ValueError(f"start: every percentile index must be in [0, {P})")
+    S0, W = int(dg.shape[0]), int(w.size)
+    S = S0 * W
+    if S > 4096:
+        raise ValueError(f"{S0} starts x {W} hit values = {S} chains, more than 4096")
+    dg = np.repeat(np.clip(dg, 0, P - 1).astype(np.uint8), W, axis=0)                    # chain s = (start s // W, value s % W)
+    dg[:, E1 - 1] = 0
+    w_s = np.tile(w.astype(np.uint64), S0)
+    if budget is not None and budget_mean is not None:
+        raise ValueError("budget and budget_mean are one argument in two units: give one")
+    if budget_mean is not None:
+        bm = np.atleast_1d(np.asarray(budget_mean, dtype=np.float64))
+        if (bm < 0).any():
+            raise ValueError("budget_mean must be >= 0")
+        budget = np.floor(bm * n_docs).astype(np.uint64)
+    b_s = None
+    if budget is not None:
+        b = np.atleast_1d(_host_ints(budget, "budget"))
+        if b.shape not in ((1,), (S,)) or (b.dtype.kind == "i" and int(b.min()) < 0):
+            raise ValueError(f"budget: an int or ({S},) ints >= 0 (one per chain), not {b.shape}")
+        b_s = np.broadcast_to(b.astype(np.uint64), (S,)).copy()
+    cost_host = None
+    if cost is not None:
+        cost_host = _host_ints(cost, "cost")
+        if cost_host.shape not in ((E1,), (E1, n_docs)):
+            raise ValueError(f"cost: shape ({E1},) or ({E1},{n_docs}), not {cost_host.shape}")
+        if cost_host.size and (int(cost_host.min()) < 0 or int(cost_host.max()) >= 1 << 32):
+            raise ValueError("cost: every value must be in [0, 2^32)")
+    lib = capi.load()
+    dev = _require_torch_cuda(device)
+    if pair:
+        cf, cr = _f64_on(dev, logits[0]), _on(dev, logits[1], torch.uint8)
+    else:
+        cf, cr = csf_table(logits, references, criterion=st, as_csf=True, device=dev)
+    if cf.dim() != 2 or tuple(cr.shape) != tuple(cf.shape):
+        raise ValueError("table (E1,N), correct (E1,N)")
+    E1, N = cf.shape
+    cs = None
+    if cost_host is not None:
+        c2 = cost_host if cost_host.ndim == 2 else np.broadcast_to(cost_host[:, None], (E1, N))
+        cs = torch.from_numpy(np.ascontiguousarray(c2.astype(np.uint32)).view(np.int32)).to(dev)      # uint32 words
+    u64 = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to(dev)                   # uint64 words
+    st_dev, w_dev, b_dev = torch.from_numpy(dg).to(dev), u64(w_s), (u64(b_s) if b_s is not None else None)
+    i32 = lambda: torch.empty((S,), dtype=torch.int32, device=dev)
+    i64 = lambda: torch.empty((S,), dtype=torch.int64, device=dev)
+    digits = torch.empty((S, E1), dtype=torch.uint8, device=dev)
+    thr = torch.empty((S, E1), dtype=torch.float64, device=dev)
+    table = torch.empty((E1, P), dtype=torch.float64, device=dev)
+    hits, xsum, rounds, status, s_hits, csum, s_csum = i32(), i32(), i32(), i32(), i32(), i64(), i64()
+    with torch.cuda.device(dev):
+        capi.check(lib.ee_threshold_refine(_ptr(cf), _ptr(cr), _ptr(cs), E1, N, P, S, _ptr(st_dev), _ptr(w_dev), _ptr(b_dev), int(max_rounds),
+                                           _ptr(digits), _ptr(thr), _ptr(hits), _ptr(xsum), _ptr(csum), _ptr(rounds), _ptr(status), _ptr(s_hits),
+                                           _ptr(s_csum), _ptr(table), _stream()), None, "ee_threshold_refine")
+    sign = -1.0 if st.value == "entropy" else 1.0                       # the chains ran on the negated entropy: real thresholds back (exact)
+    table_host = sign * table.cpu().numpy()
+    if start_result is not None and not np.array_equal(np.ascontiguousarray(start_result.table).view(np.int64), np.ascontiguousarray(table_host).view(np.int64)):
+        raise ValueError("start: the SearchResult's percentile table is not this call's, bit for bit: another table, criterion or num_per_exit")
+    host = lambda t: t.cpu().numpy()
+    return RefineResult(table=table_host, digits=host(digits), thresholds=sign * host(thr), hits=host(hits), exit_sum=host(xsum),
+                        cost_sum=host(csum).view(np.uint64), rounds=host(rounds), status=host(status), start_hits=host(s_hits),
+                        start_cost_sum=host(s_csum).view(np.uint64), hit_value=w_s, num_samples=int(N))
