@@ -397,6 +397,35 @@ int ee_set_patience_vector(ee_handle* h, const int32_t* t, int32_t n);
 /* The exit rule (MMEE_RULE_*, semantics above) of every LATER ee_forward and ee_graph_capture; MMEE_RULE_PLAIN after ee_create. */
 int ee_set_exit_rule(ee_handle* h, int32_t rule);
 
+/* Exit ensemble (Zero Time Waste, Wolczyk et al., NeurIPS 2021): the decision at exit m sees a weighted geometric ensemble of the exits the
+ * document has passed, instead of exit m's row alone.  No backbone work is added: a document that reaches exit m has run every head below it.
+ * THE definition (the forward, ee_ensemble_logits and the stand-alone hook all refer to it).  Exits e = 0 .. E in the path's order,
+ * E1 = E + 1, K labels:
+ *   x_e[k] = (float)((double)z_e[k] / T_e)          the scaled row of exit e as the path writes it out (what dump-all stores in all_logits);
+ *   l_e[k] = (x_e[k] - M) - log(S)                   in float64: M = max_k x_e[k], S = sum_k exp(x_e[k] - M) over k = 0 .. K-1 in label order
+ *                                                    (the max-shifted log-softmax);
+ *   a_m[k] = b[m][k] + sum_{j = 0 .. m} w[m][j] l_j[k]   in float64, accumulated with fma, j ascending, starting from b[m][k];
+ *   y_m[k] = (float)a_m[k]                           the ensemble row.
+ * w is (E1, E1) lower triangular in float64 (an entry with j > m must be 0), b is (E1, K) in float64, NULL meaning 0.
+ * With an ensemble set, y_m takes the place of the scaled policy row everywhere behind it: the decision sees y_m with temperature 1 (every
+ * threshold criterion, MMEE_CRIT_PATIENCE and the two rules, whose argmax is y_m's); out_logits, out_all_logits and the result stream carry
+ * y_m; out_conf and out_all_crit are the criterion of y_m; out_head_logits and out_head_crit stay the head's own raw values.  The final exit
+ * is ensembled like any other.  On gate-strategy handles under the threshold criteria the ensemble is over classifier(gate input).
+ * Special cases: w = I, b = 0 gives y_m = logsoftmax(x_m), the plain exit up to one rounding (the same decisions for max-confidence, entropy
+ * and margin up to that rounding; not the same bits); w[m][j] = 1 / (m + 1) is the running geometric mean of the exits' distributions.
+ * One launch per exit (exit_ensemble_kernel, between the head's and the decision's); per-document state l_e in the handle's workspace,
+ * indexed by the document's slot in the call, written at every exit the document reaches: nothing carries over from one forward to the next.
+ *
+ * ee_set_ensemble: w host (E1 * E1) doubles, b host (E1 * K) doubles or NULL; both are copied.  w == NULL clears the ensemble: the handle then
+ * issues the launches and returns the bits it did before one was ever set.  Applies to every later ee_forward and ee_graph_capture; the first
+ * call allocates E1 * max_docs * K doubles of state.  Refused, with a message and nothing changed: an entry that is not finite; a non-zero entry
+ * of w above the diagonal; a handle under MMEE_CRIT_GATE or with use_lte (their decision does not read the policy row; not built); a handle
+ * that holds captured graphs when the call would switch the ensemble on or off (a graph's launch list is the one of its capture; new weights for
+ * a set ensemble are fine, replays read them).  While an ensemble is set, ee_set_criterion refuses MMEE_CRIT_GATE.  Synchronises the device.
+ * ee_has_ensemble: 1 when an ensemble is set, else 0. */
+int ee_set_ensemble(ee_handle* h, const double* w, const double* b);
+int ee_has_ensemble(const ee_handle* h);
+
 /* Pin the exit-layer schedule.  DEFAULT (enabled == 0): every layer that ends in a decision is probed first.  Rounds 2-4 chose per layer
  * from the stage populations of "the handle's most recent FINISHED forward" -- a timing-dependent host decision, and under MMEE_FLAG_XPROBE
  * (whose probe is a re-association) the same inputs could return different low bits from run to run.  Round 5: the library never picks a
@@ -555,6 +584,13 @@ int ee_csf_table(const double* logits, const int64_t* references, int32_t E1, in
  * decide kernels use (the bits of the forward's decision), row E the max-softmax of final_logits as ee_msp_table writes it.  The `correct`
  * table that goes with it is ee_msp_table's on the policy logits: what leaves under the gate is the classifier(gate input) row. */
 int ee_gate_table(const float* head_logits, const double* final_logits, int32_t E, int32_t N, int32_t K, double* table, void* stream);
+/* The exit ensemble (definition at ee_set_ensemble) on a dumped array: logits dev double (E1,N,K), the UN-ensembled scaled rows x_e as a
+ * dump-all forward returns them in out_all_logits; w dev double (E1,E1), b dev double (E1,K) or NULL; out dev double (E1,N,K), which may not
+ * overlap logits.  out[m][n] = y_m of document n by the two device functions the forward's launch calls, so for float32-valued input every
+ * output value is exactly a float32 and has the forward's bits.  A NaN input row (an exit the document never reached) gives NaN from that exit
+ * on.  The result is a logits array like any other: it goes unchanged into ee_csf_table, the scans, the sweeps, the searches and
+ * ee_exit_metrics.  Refused: a NULL logits / w / out, E1, N or K below 1. */
+int ee_ensemble_logits(const double* logits, int32_t E1, int32_t N, int32_t K, const double* w, const double* b, double* out, void* stream);
 
 /*
  * The threshold search: which thresholds should a deployment run?  Candidate thresholds from the percentiles of the confidence table, V candidate
@@ -969,6 +1005,26 @@ int ee_lte_targets(const float* logits, const int64_t* labels, int32_t E, int32_
 int ee_lte_scores(const float* features, const float* weight, const float* bias, int32_t E, int32_t N, int32_t H, double* scores, void* stream);
 
 /*
+ * The exit ensemble's weights (definition at ee_set_ensemble) from a dumped array, on the device.  Per exit m, in float64,
+ *     L_m(w_m, b_m) = (1/N) sum_n [logsumexp(a_m,n) - a_m,n[y_n]] + (l2/2) (|w_m - e_m|^2 + |b_m|^2)
+ * with a_m,n the ensemble row of document n before its rounding to float32 and e_m the unit vector of the plain exit: the penalty pulls toward
+ * "no ensemble".  Entries j > m of w_m have zero gradient and stay exactly 0.  l2 > 0 makes every L_m strongly convex: one optimum.  The start
+ * is w_m = e_m, b_m = 0 (or w0 / b0, dev double (E1,E1) / (E1,K), each or NULL; entries of w0 above the diagonal are ignored).  Because the
+ * penalty vanishes at the default start and the driver only accepts descent steps, loss[m] never exceeds the plain exit's mean NLL.
+ *   logits dev double (E1,N,K): UN-ensembled scaled rows, as a dump-all forward returns them; labels dev int64 (N,).
+ *   Outputs, dev: w double (E1,E1), b double (E1,K) -- what ee_set_ensemble and ee_ensemble_logits take, after a copy to the host for the
+ *   former; loss, grad_norm double (E1,), evals, status int32 (E1,), each or NULL, as ee_head_fit reports them (status 0: converged to gtol).
+ * The L-BFGS driver, its budget (gtol, max_evals, history), the workspace convention and the error convention are ee_head_fit's: a label outside
+ * [0,K) or a logit that is not finite (a NaN row: an exit a document never reached) fails the call and no output is written.  Deterministic to the
+ * bit (no floating-point atomics, every sum in a fixed order), and an exit gets the same bits whatever E1 is: alone, in a table cut behind it, or
+ * among all.  Refused: E1 outside [1, MMEE_MAX_ENCODER_EXITS + 4], K outside [2, 64], E1 (3 K + E1 + 2) > 7680 (a workgroup holds one
+ * document's rows of every exit in LDS), l2 <= 0.  Not built: sample or reach weights, per-class weights. */
+size_t ee_ensemble_fit_workspace_bytes(int32_t E1, int32_t N, int32_t K, int32_t history);
+int ee_ensemble_fit(const double* logits, const int64_t* labels, const double* w0, const double* b0, int32_t E1, int32_t N, int32_t K, double l2,
+                    double gtol, int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, double* w, double* b, double* loss,
+                    double* grad_norm, int32_t* evals, int32_t* status, void* stream);
+
+/*
  * 2-way gate heads from a frozen backbone's CLS rows: the heads MMEE_CRIT_GATE scores (one-layer gates, exit_head_num_layers == 1).  The
  * reference trains gates with nn.BCEWithLogitsLoss() against the one-hot of "classifier(gate input) is right here"
  * (EE/models/LayoutLMv3.py:764-781); on a frozen backbone that is, per exit e, with targets c[e][n] in [0, 1] (hard 0 / 1, or soft) and
@@ -1268,7 +1324,28 @@ int ee_debug_xprobe(const ee_debug_xprobe_args* args, int32_t* err_flag_out, voi
  *   max_docs); which = 1, launch_rows_to_padded: out (B, T + Pv, H), position p < T of document d = X row doc_off[d] + text_dst[d][p]
  *   (zeros when text_dst[d][p] < 0), position T + v = X row doc_off[d] + ntext[d] + v; text_dst NULL (image-only): T = 0 and no ntext.
  *   X [x_rows][H] f32 rows (split_inv 0) or split-f16 rows (split_inv = 1 / plane scale); out f32 [out_rows][H].  Refused: a row index
- *   outside X or out. */
+ *   outside X or out.
+ *
+ * ee_debug_exit_ensemble: one launch_exit_ensemble (the exit ensemble's launch; definition at ee_set_ensemble) for exit exit_index of E1.
+ *   pol_logits f32 [pol_rows][K], the head's rows of the stage's documents; temp: this exit's temperature (by_pointer != 0: read at
+ *   [exit_index] of a device vector, as a replay does); counts and doc_orig as for ee_debug_exit_decide (slots in [0, B)); w dev double
+ *   (E1,E1), b dev double (E1,K) or NULL; state dev double (E1,B,K), the caller's per-document rows l_e by original slot: row exit_index of
+ *   every active slot is written, rows 0 .. exit_index-1 of those slots are read, nothing else is touched; out f32 [out_rows][K] receives
+ *   y of document i at row i.  Refused: K, E1 or B below 1 (B above 2^20), exit_index outside [0, E1), n_docs outside [0, B] or above
+ *   pol_rows / out_rows, doc_orig outside [0, B), E1 * B * K above 2^31. */
+typedef struct ee_debug_exit_ensemble_args {
+    const float* pol_logits;
+    int32_t pol_rows, K, E1, exit_index, B;
+    double temp;
+    int32_t by_pointer;
+    const void* counts;
+    const int32_t* doc_orig;
+    const double *w, *b;
+    double* state;
+    float* out;
+    int32_t out_rows;
+} ee_debug_exit_ensemble_args;
+int ee_debug_exit_ensemble(const ee_debug_exit_ensemble_args* args, void* stream);
 typedef struct ee_debug_head_out_args {
     const float* in;
     int32_t in_rows, ld;

@@ -25,3 +25,4 @@ from .heads import (GateFit, HeadFit, LteFit, MlpGateFit, MlpHeadFit, balanced_c
                     collect_embedding_features, collect_exit_features, collect_gate_features, collect_lte_features, fit_distilled_exit_heads,
                     fit_distilled_mlp_exit_heads, fit_exit_heads, fit_gate_heads, fit_lte_classifier, fit_mlp_exit_heads,
                     fit_mlp_gate_heads, gate_targets, lte_targets, reach_weights)
+from .heads import EnsembleFit, fit_exit_ensemble  # noqa: F401,E402

@@ -109,6 +109,12 @@ class DebugExitDecideArgs(C.Structure):
                                       "out_head_crit", "meta_old", "meta_new", "row_src")])
 
 
+class DebugExitEnsembleArgs(C.Structure):
+    """ee_debug_exit_ensemble_args of include/mmee.h: device pointers (or None), this exit's temperature and sizes."""
+    _fields_ = ([("pol_logits", _vp)] + [(n, _i32) for n in ("pol_rows", "K", "E1", "exit_index", "B")] + [("temp", C.c_double), ("by_pointer", _i32)]
+                + [(n, _vp) for n in ("counts", "doc_orig", "w", "b", "state", "out")] + [("out_rows", _i32)])
+
+
 class DebugRowsOutArgs(C.Structure):
     """ee_debug_rows_out_args of include/mmee.h: device pointers (or None) and sizes."""
     _fields_ = ([("which", _i32), ("X", _vp), ("x_rows", _i32), ("H", _i32), ("split_inv", C.c_float)]
@@ -158,6 +164,8 @@ SYMBOLS = {
     "ee_set_patience": (C.c_int, [_vp, _i32]),
     "ee_set_patience_vector": (C.c_int, [_vp, C.POINTER(_i32), _i32]),
     "ee_set_exit_rule": (C.c_int, [_vp, _i32]),
+    "ee_set_ensemble": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "ee_has_ensemble": (C.c_int, [_vp]),
     "ee_suggest_probe_mask": (C.c_int, [_vp, _u32, C.POINTER(C.c_uint64), _vp]),
     "ee_clock_stamp": (C.c_int, [_vp, _vp]),
     "ee_set_inputs_embeds": (C.c_int, [_vp, _vp]),
@@ -183,6 +191,10 @@ SYMBOLS = {
     "ee_msp_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_csf_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_gate_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "ee_ensemble_logits": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ee_ensemble_fit": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _vp]),
+    "ee_ensemble_fit_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32]),
     "ee_exit_metrics": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ee_debug_gemm": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_debug_gemm_split": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp,
@@ -201,6 +213,7 @@ SYMBOLS = {
     "ee_debug_xprobe": (C.c_int, [C.POINTER(DebugXProbeArgs), C.POINTER(_i32), _vp]),
     "ee_debug_head_out": (C.c_int, [C.POINTER(DebugHeadOutArgs), _vp]),
     "ee_debug_exit_decide": (C.c_int, [C.POINTER(DebugExitDecideArgs), _vp]),
+    "ee_debug_exit_ensemble": (C.c_int, [C.POINTER(DebugExitEnsembleArgs), _vp]),
     "ee_debug_rows_out": (C.c_int, [C.POINTER(DebugRowsOutArgs), _vp]),
     "ee_debug_patch_project": (C.c_int, [C.POINTER(DebugPatchProjectArgs), _vp]),
     "ee_temperature_fit": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1,6 +1,6 @@
-// ee_debug_head_out, ee_debug_exit_decide, ee_debug_rows_out: the exit stage of exit_stage.hip alone, on caller-provided device buffers; no
-// handle.  Each entry point makes the calls of the path's own launchers that capi_forward.hip makes (launch_head_out; launch_decide and,
-// behind it, launch_compact_rows as compact() does; launch_gather_cls / launch_rows_to_padded) and synchronises.  No kernel is defined or
+// ee_debug_head_out, ee_debug_exit_ensemble, ee_debug_exit_decide, ee_debug_rows_out: the exit stage of exit_stage.hip alone, on caller-provided
+// device buffers; no handle.  Each entry point makes the calls of the path's own launchers that capi_forward.hip makes (launch_head_out;
+// launch_exit_ensemble; launch_decide and, behind it, launch_compact_rows as compact() does; launch_gather_cls / launch_rows_to_padded) and synchronises.  No kernel is defined or
 // instantiated here; what the launchers cannot take is refused, not launched, and so is every row, document or offset outside the caller's
 // buffers.  The stage arrays and the per-document state are the caller's, so a test chains exits: the n_* outputs of one call are the stage
 // of the next.  tests/test_gpu_exit_stage.py drives them against tests/exit_stage_ref.py.
@@ -152,6 +152,45 @@ int ee_debug_exit_decide(const ee_debug_exit_decide_args* a, void* stream) {
         launch_compact_rows(d.n_counts, a->n_doc_off, a->n_x_src, a->n_meta_src, reinterpret_cast<const RowMeta*>(a->meta_old),
                             reinterpret_cast<RowMeta*>(a->meta_new), a->row_src, a->B, cus, s);
     }
+    return finish(who, s, nullptr, nullptr);
+}
+
+int ee_debug_exit_ensemble(const ee_debug_exit_ensemble_args* a, void* stream) {
+    const char* who = "ee_debug_exit_ensemble";
+    if (!a) return fail(nullptr, "%s: args must not be NULL", who);
+    if (!a->pol_logits || !a->counts || !a->doc_orig || !a->w || !a->state || !a->out)
+        return fail(nullptr, "%s: pol_logits, counts, doc_orig, w, state and out must not be NULL", who);
+    if (a->K < 1 || a->E1 < 1) return fail(nullptr, "%s: K %d or E1 %d is below 1", who, a->K, a->E1);
+    if (a->exit_index < 0 || a->exit_index >= a->E1) return fail(nullptr, "%s: exit_index %d outside [0, E1 = %d)", who, a->exit_index, a->E1);
+    if (a->B < 1 || a->B > (1 << 20)) return fail(nullptr, "%s: B %d outside [1, 2^20]", who, a->B);
+    if ((long long)a->E1 * a->B * a->K > (1ll << 31)) return fail(nullptr, "%s: a state of E1 B K = %lld doubles is above 2^31", who, (long long)a->E1 * a->B * a->K);
+    if (a->pol_rows < 0 || a->out_rows < 0) return fail(nullptr, "%s: pol_rows %d or out_rows %d is negative", who, a->pol_rows, a->out_rows);
+    if (!have_device(who)) return 1;
+    static_assert(sizeof(StageCounts) == 16, "the layout include/mmee.h documents");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (hipStreamSynchronize(s) != hipSuccess) return fail(nullptr, "%s: the stream is in error", who);
+    StageCounts hc{};
+    if (hipMemcpy(&hc, a->counts, sizeof(hc), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of counts failed", who);
+    const int n = hc.n_docs;
+    if (n < 0 || n > a->B) return fail(nullptr, "%s: counts.n_docs = %d outside [0, B = %d]", who, n, a->B);
+    if (n > a->pol_rows || n > a->out_rows) return fail(nullptr, "%s: %d documents leave the %d rows of pol_logits or the %d rows of out", who, n, a->pol_rows, a->out_rows);
+    if (int rc = check_row_map(who, "doc_orig", a->doc_orig, n, a->B)) return rc;
+    Scratch sc;
+    EnsembleArgs en{};
+    en.pol_logits = a->pol_logits; en.K = a->K; en.E1 = a->E1; en.exit_index = a->exit_index; en.B = a->B;
+    en.temp = a->temp;
+    en.counts = reinterpret_cast<const StageCounts*>(a->counts); en.doc_orig = a->doc_orig;
+    en.w = a->w; en.b = a->b; en.state = a->state; en.out = a->out;
+    if (a->by_pointer) {
+        // as a replay reads it: the temperature of exit e at [e] of a device vector
+        double* temp = nullptr;
+        if (!get_dirty(sc, &temp, (size_t)a->exit_index + 1, s)) return fail(nullptr, kScratchFailed, who);
+        if (hipMemcpyAsync(temp + a->exit_index, &a->temp, sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+            return fail(nullptr, kUploadFailed, who);
+        en.temp_ptr = temp;
+        en.temp = __builtin_nan("");                               // the by-value form must not be what the kernel reads
+    }
+    launch_exit_ensemble(en, s);
     return finish(who, s, nullptr, nullptr);
 }
 

@@ -1,7 +1,7 @@
 // Entry points of the device fits, none of which sees a handle: one-layer and two-layer exit heads from dumped CLS rows against labels
 // (ee_head_fit, ee_mlp_head_fit), against the final classifier's logits (ee_head_fit_distill, ee_mlp_head_fit_distill), either with sample
 // weights (ee_head_fit_weighted, ee_mlp_head_fit_weighted), the 2-way gate heads of either depth (ee_head_fit_gate; ee_mlp_head_fit_gate and
-// ee_mlp_head_fit_gate_weighted), and the learning-to-exit classifier (ee_lte_fit, with ee_lte_targets and ee_lte_scores); their workspace queries, and the ee_debug_*_lossgrad hooks that run one evaluation of an
+// ee_mlp_head_fit_gate_weighted), the learning-to-exit classifier (ee_lte_fit, with ee_lte_targets and ee_lte_scores) and the exit ensemble's weights (ee_ensemble_fit); their workspace queries, and the ee_debug_*_lossgrad hooks that run one evaluation of an
 // objective on caller-provided buffers.  The L-BFGS is fit_lbfgs.hip.
 //
 // What a head is fitted against is one value, HeadObjective (mmee_kernels.h).  Each head entry point builds it from its own arguments
@@ -33,7 +33,7 @@ static int budget_refuse(const char* who, double gtol, int32_t max_evals, int32_
 // ---- the error word, decoded once ---------------------------------------------------------------------------------------------------------
 // Which objective an entry point states.  For the head fits it is the family of entry points that built the HeadObjective, which the value
 // alone does not say: a distilled entry point that was handed NULL teacher_logits is refused, a weighted one fits against labels then.
-enum class Objective { kLabelled, kDistilled, kWeighted, kGate, kWeightedGate, kLte, kLteTargets };
+enum class Objective { kLabelled, kDistilled, kWeighted, kGate, kWeightedGate, kLte, kLteTargets, kEnsemble };
 
 // bit 0: a bad label or target -- which, and so the message, is the objective's; bit 1: a teacher logit that is not finite (the distilled
 // objectives); bit 2: a sample weight that is negative or not finite, bit 3: an exit whose weights sum to zero (launch_row_scale).  Bits 2 and 3
@@ -55,6 +55,8 @@ static int error_word_fail(const char* who, int err, Objective of, bool fit, int
         case Objective::kLteTargets:
             return fail(nullptr, "%s: a label is outside [0, K = %d) or a logit is NaN (a row its document never reached); nothing was written", who, K);
     }
+    if ((err & 2) && of == Objective::kEnsemble)
+        return fail(nullptr, "%s: a logit is not finite (dump-all marks the rows a document never reached with NaN)%s", who, tail);
     if (err & 2)
         return fail(nullptr, "%s: a teacher logit is not finite (dump-all marks the rows a document never reached with NaN)%s", who, tail);
     return 0;
@@ -402,6 +404,37 @@ int ee_lte_targets(const float* logits, const int64_t* labels, int32_t E, int32_
     if (!sc.get(&err_dev, 1)) return fail(nullptr, "%s: hipMalloc of the error word failed", who);
     launch_lte_targets(logits, reinterpret_cast<const long long*>(labels), E, N, K, targets, err_dev, s);
     return finish_call(who, true, err_dev, s, Objective::kLteTargets, K);
+}
+
+// ---- the exit ensemble's weights from a dumped array (ensemble_fit.hip) ---------------------------------------------------------------------
+static int ensemble_fit_refuse(const char* who, int32_t E1, int32_t N, int32_t K, double l2) {
+    if (E1 < 1 || E1 > MMEE_MAX_ENCODER_EXITS + 4) return fail(nullptr, "%s: E1 = %d, need 1 <= E1 <= %d", who, E1, MMEE_MAX_ENCODER_EXITS + 4);
+    if (N < 1) return fail(nullptr, "%s: N = %d, need N >= 1", who, N);
+    if (K < 2 || K > 64) return fail(nullptr, "%s: K = %d, need 2 <= K <= 64 (ee_create's limit)", who, K);
+    if (!ensemble_fit_supports(E1, K))
+        return fail(nullptr, "%s: (E1, K) = (%d, %d): one document's rows and an exit-by-parameter table, E1 (3 K + E1 + 2) = %lld doubles, leave the 7680 "
+                             "doubles of LDS the row kernel takes", who, E1, K, (long long)E1 * (3 * K + E1 + 2));
+    if (!(l2 > 0.0)) return fail(nullptr, "%s: l2 = %g, need l2 > 0 (the objective is strongly convex only then)", who, l2);
+    return 0;
+}
+
+size_t ee_ensemble_fit_workspace_bytes(int32_t E1, int32_t N, int32_t K, int32_t history) {
+    if (E1 < 1 || N < 1 || K < 1 || history < 1) return 0;
+    return ensemble_fit_workspace_bytes(E1, N, K, history);
+}
+
+int ee_ensemble_fit(const double* logits, const int64_t* labels, const double* w0, const double* b0, int32_t E1, int32_t N, int32_t K, double l2,
+                    double gtol, int32_t max_evals, int32_t history, void* workspace, size_t workspace_bytes, double* w, double* b, double* loss,
+                    double* grad_norm, int32_t* evals, int32_t* status, void* stream) {
+    const char* who = "ee_ensemble_fit";
+    if (!logits || !labels || !workspace || !w || !b) return fail(nullptr, "%s: NULL argument (logits, labels, workspace, w and b are required)", who);
+    if (ensemble_fit_refuse(who, E1, N, K, l2)) return 1;
+    if (budget_refuse(who, gtol, max_evals, history, workspace_bytes, [&] { return ensemble_fit_workspace_bytes(E1, N, K, history); })) return 1;
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const EnsembleFitArgs a{{nullptr, E1, N, 0, l2, gtol, max_evals, history, workspace, nullptr, nullptr, loss, grad_norm, evals, status},
+                            logits, int64_labels(labels), w0, b0, K, w, b};
+    return finish_call(who, launch_ensemble_fit(a, s), workspace, s, Objective::kEnsemble, K);
 }
 
 int ee_lte_scores(const float* features, const float* weight, const float* bias, int32_t E, int32_t N, int32_t H, double* scores, void* stream) {

@@ -653,6 +653,17 @@ struct Forward {
         d.thr = a.thresholds ? a.thresholds[exit_index] : 0.0;
         d.temp = a.temperatures ? a.temperatures[exit_index] : 1.0;
         if (cap) { d.thr_ptr = cap->thr_dev; d.temp_ptr = cap->thr_dev + (E + 1); }      // replays read the vector of THEIR launch
+        if (h->ens_on) {
+            // exit ensemble (ee_set_ensemble): y_m of every active document into a second policy buffer; the decision reads that with temperature 1
+            EnsembleArgs en{};
+            en.pol_logits = pol; en.K = K; en.E1 = E + 1; en.exit_index = exit_index; en.B = c.max_docs;
+            en.temp = d.temp; en.temp_ptr = d.temp_ptr;
+            en.counts = &h->counts[cur]; en.doc_orig = S_doc_orig(cur);
+            en.w = h->ens_w; en.b = h->ens_b; en.state = h->ens_state; en.out = h->ens_logits;
+            { ProfScope ps(h, P_ENSEMBLE, s); launch_exit_ensemble(en, s); }
+            d.pol_logits = h->ens_logits; d.temp = 1.0;
+            if (cap) d.temp_ptr = h->ens_ones;
+        }
         d.criterion = c.criterion; d.is_final = is_final ? 1 : 0; d.no_exit = no_exit ? 1 : 0; d.exit_index = exit_index; d.B = B;
         d.counts = &h->counts[cur]; d.doc_orig = S_doc_orig(cur); d.doc_off = S_doc_off(cur); d.x_phys = x_phys;
         d.n_counts = &h->counts[cur + 1]; d.n_doc_orig = S_doc_orig(cur + 1); d.n_doc_off = S_doc_off(cur + 1);

@@ -7,7 +7,7 @@
 //   capi_debug_attention.hip, capi_debug_rows.hip, capi_debug_xprobe.hip, capi_debug_exit.hip, capi_debug_patch.hip   the ee_debug_* hooks of the
 //                     attention kernels, of the row kernels, of the X-space CLS probe, of the exit stage and of the patch projection; what only
 //                     they share is in capi_debug.h
-//   capi_fit.hip      the device fits, no handle either (ee_head_fit, ee_mlp_head_fit, ee_lte_*, ee_debug_*_lossgrad)
+//   capi_fit.hip      the device fits, no handle either (ee_head_fit, ee_mlp_head_fit, ee_lte_*, ee_ensemble_fit, ee_debug_*_lossgrad)
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -128,6 +128,13 @@ struct ee_handle {
     // learning-to-exit (ee_config.use_lte): encoder.lte_classifier (weight [H], bias [1]) and the float64 scores of the exit being decided
     float *lte_w = nullptr, *lte_b = nullptr;
     double* lte_score = nullptr;                  // [max_docs], by the stage's document index
+    // exit ensemble (ee_set_ensemble; include/mmee.h): device copies of w and b, the per-document state and the rows the decision reads instead
+    // of the head's.  Allocated by the first ee_set_ensemble; ens_on says whether the forwards launch exit_ensemble_kernel
+    bool ens_on = false;
+    double *ens_w = nullptr, *ens_b = nullptr;    // (E1,E1), (E1,K): replays of a captured graph read them here
+    double* ens_state = nullptr;                  // (E1,max_docs,K): l_e by original document slot (compaction never moves it)
+    double* ens_ones = nullptr;                   // [E1] of 1.0: the temperatures a captured decide launch reads behind the ensemble
+    float* ens_logits = nullptr;                  // [max_docs][K]: y of the exit being decided, by the stage's document index
     // optional per-kernel event timing (ee_profile)
     bool prof_on = false;
     struct ProfRec { int id; hipEvent_t a, b; double flops; };
@@ -293,7 +300,7 @@ struct Scratch {
 
 // kernel roles reported by ee_profile_read (their names: kProfNames in capi_query.hip)
 enum { P_PREP = 0, P_EMBT, P_GPATCH, P_EMBV, P_GQKV, P_ATTN, P_GAO, P_LN, P_GUP, P_GDOWN, P_HEAD, P_DECIDE, P_COMPACT, P_GCLS, P_PROBE,
-       P_PAIRIDX, P_PSPLIT, P_HEADOUT, P_EMIT, P_COUNT };
+       P_PAIRIDX, P_PSPLIT, P_HEADOUT, P_EMIT, P_ENSEMBLE, P_COUNT };
 
 struct ProfScope {
     ee_handle* h;

@@ -33,6 +33,8 @@ const char* const kProfNames[] = {
     "head_out|head_out_kernel / head_out_lte_kernel [inside exit_head]",
     // (not nested) MMEE_FLAG_STREAM_RESULTS: one launch behind every exit's decide launch
     "emit_leavers|emit_leavers_kernel",
+    // (not nested) ee_set_ensemble: one launch between every exit's head and its decide launch
+    "exit_ensemble|exit_ensemble_kernel",
 };
 static_assert(sizeof(kProfNames) / sizeof(kProfNames[0]) == P_COUNT, "one name per profile role");
 
@@ -155,9 +157,65 @@ int ee_set_criterion(ee_handle* h, int32_t criterion) {
     if (criterion == MMEE_CRIT_PATIENCE && h->rule != MMEE_RULE_PLAIN)
         return fail(h, "ee_set_criterion: MMEE_CRIT_PATIENCE under exit rule %d: PABEE has no threshold event for MMEE_RULE_STREAK / MMEE_RULE_EITHER "
                        "to build on (ee_set_exit_rule(h, MMEE_RULE_PLAIN) first)", h->rule);
+    if (criterion == MMEE_CRIT_GATE && h->ens_on)
+        return fail(h, "ee_set_criterion: MMEE_CRIT_GATE while an exit ensemble is set: the gate decision does not read the policy row the ensemble "
+                       "replaces (not built); clear it first, ee_set_ensemble(h, NULL, NULL)");
     h->cfg.criterion = criterion;      // read by the decide kernel's arguments of every later ee_forward
     return 0;
 }
+
+int ee_set_ensemble(ee_handle* h, const double* w, const double* b) {
+    if (!h) return 1;
+    const ee_config& c = h->cfg;
+    const int E1 = c.n_embedding_exits + c.n_encoder_exits + 1, K = c.num_labels;
+    const bool on = w != nullptr;
+    if (!on && b) return fail(h, "ee_set_ensemble: b without w (w == NULL clears the ensemble)");
+    if (on) {
+        for (int m = 0; m < E1; ++m)
+            for (int j = 0; j < E1; ++j) {
+                const double v = w[(size_t)m * E1 + j];
+                if (!std::isfinite(v)) return fail(h, "ee_set_ensemble: w[%d][%d] is not finite", m, j);
+                if (j > m && v != 0.0)
+                    return fail(h, "ee_set_ensemble: w[%d][%d] = %g above the diagonal: exit %d has not run when exit %d decides (w is lower triangular)", m, j,
+                                v, j, m);
+            }
+        for (int i = 0; b && i < E1 * K; ++i)
+            if (!std::isfinite(b[i])) return fail(h, "ee_set_ensemble: b[%d][%d] is not finite", i / K, i % K);
+        if (c.criterion == MMEE_CRIT_GATE)
+            return fail(h, "ee_set_ensemble: a handle under MMEE_CRIT_GATE: the gate decision does not read the policy row the ensemble replaces, only "
+                           "what leaves would change (not built)");
+        if (c.use_lte)
+            return fail(h, "ee_set_ensemble: a use_lte handle: the learning-to-exit decision does not read the policy row the ensemble replaces, only "
+                           "what leaves would change (not built)");
+    }
+    if (on != h->ens_on)
+        for (const auto& g : h->graphs)
+            if (g.exec)
+                return fail(h, "ee_set_ensemble: the handle holds captured graphs and the call would switch the ensemble %s: a graph's launch list is the "
+                               "one of its capture (ee_graph_destroy them first)", on ? "on" : "off");
+    if (!on) {
+        h->ens_on = false;
+        return 0;
+    }
+    HIP_OK(h, hipDeviceSynchronize());      // a forward in flight (or a replay) still reads the buffers
+    if (!h->ens_state) {
+        double *ew = nullptr, *eb = nullptr, *es = nullptr, *eo = nullptr;
+        float* el = nullptr;
+        if (dev_alloc(h, &ew, (size_t)E1 * E1) || dev_alloc(h, &eb, (size_t)E1 * K) || dev_alloc(h, &eo, (size_t)E1) ||
+            dev_alloc(h, &el, (size_t)c.max_docs * K) || dev_alloc(h, &es, (size_t)E1 * c.max_docs * K))
+            return 1;
+        const std::vector<double> ones((size_t)E1, 1.0);
+        HIP_OK(h, hipMemcpy(eo, ones.data(), sizeof(double) * E1, hipMemcpyHostToDevice));
+        h->ens_w = ew; h->ens_b = eb; h->ens_ones = eo; h->ens_logits = el; h->ens_state = es;
+    }
+    const std::vector<double> zeros((size_t)E1 * K, 0.0);
+    HIP_OK(h, hipMemcpy(h->ens_w, w, sizeof(double) * E1 * E1, hipMemcpyHostToDevice));
+    HIP_OK(h, hipMemcpy(h->ens_b, b ? b : zeros.data(), sizeof(double) * E1 * K, hipMemcpyHostToDevice));
+    h->ens_on = true;
+    return 0;
+}
+
+int ee_has_ensemble(const ee_handle* h) { return h && h->ens_on ? 1 : 0; }
 
 int ee_set_exit_rule(ee_handle* h, int32_t rule) {
     if (!h) return 1;

@@ -368,6 +368,14 @@ int ee_gate_table(const float* head_logits, const double* final_logits, int32_t 
     return launch_status(nullptr, "ee_gate_table");
 }
 
+int ee_ensemble_logits(const double* logits, int32_t E1, int32_t N, int32_t K, const double* w, const double* b, double* out, void* stream) {
+    if (!logits || !w || !out || E1 < 1 || N < 1 || K < 1)
+        return fail(nullptr, "ee_ensemble_logits: bad argument (logits / w / out not NULL, E1, N, K >= 1)");
+    if (!have_device("ee_ensemble_logits")) return 1;
+    launch_ensemble_logits(logits, E1, N, K, w, b, out, reinterpret_cast<hipStream_t>(stream));
+    return launch_status(nullptr, "ee_ensemble_logits");
+}
+
 static_assert(kMetricAccuracy == MMEE_METRIC_ACCURACY && kMetricBrier == MMEE_METRIC_BRIER && kMetricNll == MMEE_METRIC_NLL &&
               kMetricF1Micro == MMEE_METRIC_F1_MICRO && kMetricF1Macro == MMEE_METRIC_F1_MACRO && kMetricEce == MMEE_METRIC_ECE &&
               kMetricAurc == MMEE_METRIC_AURC && kMetricAvgConf == MMEE_METRIC_AVG_CONF && kMetricCount == MMEE_METRIC_COUNT,

@@ -639,6 +639,41 @@ void launch_gate_table(const float* head_logits, const double* final_logits, int
     launch_csf_table(final_logits, nullptr, 1, N, K, CRIT_MAX_CONFIDENCE, table + total, nullptr, s);
 }
 
+// The exit ensemble on a dumped array (ee_ensemble_logits; definition in include/mmee.h), by the two device functions of the forward's launch
+// (mmee_kernels.h).  Two launches: l[e][n][k] of every row into `out` (also the l table of the ensemble fit, ensemble_fit.hip), then the
+// combination in place -- a thread owns one (n, k) column of `out` and walks the exits from the last down, so what it reads below exit m is
+// still l.  A NaN row gives NaN l, and fma(0, NaN, a) is NaN: NaN from that exit on, whatever w holds.  Every value rounded through float32,
+// as the forward writes it.
+__global__ __launch_bounds__(256) void ensemble_logsoftmax_kernel(const double* __restrict__ logits, size_t rows, int K, double* __restrict__ l) {
+    const size_t total = rows * (size_t)K;
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const size_t r = t / K;
+        const double* x = logits + r * K;
+        l[t] = ens_logsoftmax_f64([&](int j) { return x[j]; }, K, (int)(t - r * K));
+    }
+}
+
+__global__ __launch_bounds__(256) void ensemble_combine_kernel(int E1, size_t slab, int K, const double* __restrict__ w, const double* __restrict__ b,
+                                                               double* out) {
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < slab; t += (size_t)gridDim.x * 256) {
+        const int k = (int)(t % K);
+        for (int m = E1 - 1; m >= 0; --m) {
+            const double y = ens_combine_f64(w + (size_t)m * E1, b ? b[(size_t)m * K + k] : 0.0, m, [&](int j) { return out[(size_t)j * slab + t]; });
+            out[(size_t)m * slab + t] = (double)(float)y;
+        }
+    }
+}
+
+void launch_ensemble_logsoftmax(const double* logits, size_t rows, int K, double* l, hipStream_t s) {
+    hipLaunchKernelGGL(ensemble_logsoftmax_kernel, dim3(grid_1d((long long)rows * K, 256, 4096)), dim3(256), 0, s, logits, rows, K, l);
+}
+
+void launch_ensemble_logits(const double* logits, int E1, int N, int K, const double* w, const double* b, double* out, hipStream_t s) {
+    const size_t slab = (size_t)N * K;
+    launch_ensemble_logsoftmax(logits, (size_t)E1 * N, K, out, s);
+    hipLaunchKernelGGL(ensemble_combine_kernel, dim3(grid_1d((long long)slab, 256, 4096)), dim3(256), 0, s, E1, slab, K, w, b, out);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Per-exit temperature fit: argmin_T mean NLL(softmax(z / T), y)   (TemperatureScaler.set_temperature,
 // EE/generic_scaling.py:64-111, L-BFGS-B on sklearn log_loss).  In beta = 1/T the objective

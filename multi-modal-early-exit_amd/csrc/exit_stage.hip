@@ -314,6 +314,36 @@ void launch_decide(const DecideArgs& a, const PatienceArgs* p, int mode, int rul
     else hipLaunchKernelGGL(stateful[mode][rule], dim3(1), dim3(1024), 0, s, a, *p);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The exit ensemble (ee_set_ensemble; definition in include/mmee.h): a launch of its own between an exit's head and its decision, because the
+// decide kernels sit at their register limit (above).  One thread per (active document, label): it walks its document's K logits for the
+// row's maximum and sum itself (K <= 64 values one wave shares through the cache; nothing to reduce across lanes, so the sum is in label
+// order), writes l_m[k] to the state row of the document's ORIGINAL slot -- compaction never moves it, and every exit a document reaches
+// rewrites its row, so no launch resets it -- and combines the rows 0 .. m-1 that earlier launches left with its own l_m.  Lanes of a
+// document read consecutive doubles of every state row.  Latency-bound integer and small-vector work, like decide.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void exit_ensemble_kernel(EnsembleArgs a) {
+    const int n = a.counts->n_docs, K = a.K, m = a.exit_index;
+    const double temp = a.temp_ptr ? a.temp_ptr[m] : a.temp;
+    const double* w_row = a.w + (size_t)m * a.E1;
+    const size_t slab = (size_t)a.B * K;                                   // one exit's rows of the state
+    const long long total = (long long)n * K;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+        const int i = (int)(t / K), k = (int)(t - (long long)i * K);
+        const float* z = a.pol_logits + (size_t)i * K;
+        const size_t slot = (size_t)a.doc_orig[i] * K + k;
+        const double l = ens_logsoftmax_f64([&](int j) { return (double)(float)((double)z[j] / temp); }, K, k);
+        a.state[(size_t)m * slab + slot] = l;
+        const double* st = a.state;
+        const double y = ens_combine_f64(w_row, a.b ? a.b[(size_t)m * K + k] : 0.0, m, [&](int j) { return j == m ? l : st[(size_t)j * slab + slot]; });
+        a.out[(size_t)i * K + k] = (float)y;
+    }
+}
+
+void launch_exit_ensemble(const EnsembleArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(exit_ensemble_kernel, dim3(grid_1d((long long)a.B * a.K, 256, 1024)), dim3(256), 0, s, a);
+}
+
 // Round 6: the head's output projection and the decision were built as ONE launch (every workgroup writes its documents' logits, fences,
 // takes a ticket; the last arrival runs the scan: nobody waits, same bits, 91 GPU tests green) and measured on config 3 (2 x 512 documents, 48 exits per step):
 // 52.7 us per exit against 31 + 16 us for the two launches -- the fences and the serial scan behind the last arrival cost what the launch saved.  Removed.

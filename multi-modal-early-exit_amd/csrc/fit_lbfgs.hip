@@ -152,7 +152,7 @@ __global__ __launch_bounds__(kThreads) void head_fit_finish_kernel(FitFinishArgs
         for (int q = 0; q < a.n_seg; ++q) {
             const FitOutSeg& sg = a.seg[q];
             if (i < sg.begin || i >= sg.begin + sg.len) continue;
-            sg.out32[(size_t)e * sg.len + i - sg.begin] = (float)th[i];
+            if (sg.out32) sg.out32[(size_t)e * sg.len + i - sg.begin] = (float)th[i];      // null: a float64 fit (ee_ensemble_fit)
             if (sg.out64) sg.out64[(size_t)e * sg.len + i - sg.begin] = th[i];
         }
         if (a.theta64) a.theta64[(size_t)e * P + i] = th[i];

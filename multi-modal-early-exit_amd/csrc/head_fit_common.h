@@ -178,7 +178,7 @@ struct FitEvalPoint {
     void* tail;                      // the objective's scratch: FitLayout's tail
 };
 
-// theta[begin, begin + len) of exit e goes to out32 + e * len (and to out64 + e * len when given)
+// theta[begin, begin + len) of exit e goes to out32 + e * len and to out64 + e * len, each when given
 struct FitOutSeg {
     int begin, len;
     float* out32;

@@ -145,6 +145,45 @@ __host__ __device__ inline double crit_sign(int criterion) { return criterion ==
 // copy the decide kernels (exit_stage.hip) and the table kernel of the dumped-array tools (exit_ops.hip) share, so their bits agree.
 __device__ inline double gate_score_f64(float h0, float h1) { return 1.0 / (1.0 + exp((double)h0 - (double)h1)); }
 
+// The exit ensemble (include/mmee.h, at ee_set_ensemble): its two functions, the one copy the forward's launch (exit_stage.hip) and the
+// dumped-array tool (exit_ops.hip) share, so their bits agree.  Each returns ONE label's value; a thread per (document, label) walks the row
+// for M and S itself, in label order, so no value depends on how the threads are grouped.
+// l[k] of the row x(0 .. K-1): x is a callable int -> double
+template <typename Row>
+__device__ inline double ens_logsoftmax_f64(Row x, int K, int k) {
+    double m = x(0);
+    for (int j = 1; j < K; ++j) m = fmax(m, x(j));
+    double s = 0.0;
+    for (int j = 0; j < K; ++j) s += exp(x(j) - m);
+    return (x(k) - m) - log(s);
+}
+// a_m[k] = b + sum_{j = 0 .. m} w_row[j] * l(j), fma, j ascending from b: l is a callable int -> double, w_row is row m of w
+template <typename Rows>
+__device__ inline double ens_combine_f64(const double* w_row, double b, int m, Rows l) {
+    double a = b;
+#pragma unroll 4
+    for (int j = 0; j <= m; ++j) a = fma(w_row[j], l(j), a);
+    return a;
+}
+
+// the exit ensemble's launch of the forward, between an exit's head and its decision (exit_stage.hip)
+struct EnsembleArgs {
+    const float* pol_logits;         // [n_docs][K] the head's policy rows of the current stage
+    int K, E1, exit_index, B;        // B: the slots of the state (the handle's max_docs)
+    double temp;
+    const double* temp_ptr;          // captured-graph forwards: the temperature at [exit_index] of the replay's device vector; null: `temp`
+    const StageCounts* counts;
+    const int* doc_orig;
+    const double* w;                 // (E1,E1) on the device
+    const double* b;                 // (E1,K) on the device, or null: 0
+    double* state;                   // (E1,B,K): l_e of every slot; row exit_index written, rows below it read
+    float* out;                      // [n_docs][K] y of the current stage's documents: the policy rows the decision reads
+};
+void launch_exit_ensemble(const EnsembleArgs& a, hipStream_t s);
+// ee_ensemble_logits (exit_ops.hip): the same two functions over a dumped array; out (E1,N,K) holds l between its two launches
+void launch_ensemble_logits(const double* logits, int E1, int N, int K, const double* w, const double* b, double* out, hipStream_t s);
+void launch_ensemble_logsoftmax(const double* logits, size_t rows, int K, double* l, hipStream_t s);      // its first launch alone: l of every row
+
 // how launch_decide picks its kernel: the exit test (MODE) and the rule built on it (RULE = MMEE_RULE_*; DECIDE_PATIENCE takes RULE_PLAIN only)
 enum { DECIDE_THRESHOLD = 0, DECIDE_PATIENCE = 1, DECIDE_LTE = 2 };
 enum { RULE_PLAIN = 0, RULE_STREAK = 1, RULE_EITHER = 2, RULE_AGREE = 3 };      // RULE_AGREE: PABEE's counter alone (exit_scan_kernel only)
@@ -423,6 +462,19 @@ void launch_lte_lossgrad(const float* X, const double* T, const double* theta, i
 // targets (E,N) = 1 - [argmax(logits (E,N,K)) == y]; err: one zeroed int, bit 0 = a label outside [0,K) or a NaN logit (then nothing is written)
 void launch_lte_targets(const float* logits, const long long* y, int E, int N, int K, double* targets, int* err, hipStream_t s);
 void launch_lte_scores(const float* X, const float* wgt, const float* bias, int E, int N, int H, double* scores, hipStream_t s);
+// ee_ensemble_fit (ensemble_fit.hip): the exit ensemble's w and b per exit from a dumped array; theta of exit m = b_m (K,), w_m (E1,)
+struct EnsembleFitArgs : FitArgs {   // E = E1 parameter sets; features null, H 0; theta0 and theta64 null (the start is w0 / b0)
+    const double* logits;            // (E1,N,K) un-ensembled scaled rows
+    const long long* labels;         // (N,)
+    const double *w0, *b0;           // the start (E1,E1), (E1,K); null: w = I, b = 0
+    int K;
+    double *w, *b;                   // (E1,E1), (E1,K)
+};
+bool ensemble_fit_supports(int E1, int K);       // a tile of one document fits the 60 KB of LDS the row kernel takes
+size_t ensemble_fit_workspace_bytes(int E1, int N, int K, int history);
+// false: preparing the workspace failed.  The error word is the first int of the workspace (bit 0: a label outside [0,K); bit 1: a logit
+// that is not finite).
+bool launch_ensemble_fit(const EnsembleFitArgs& a, hipStream_t s);
 void launch_build_value_tables(const float* w1, const float* wx, const float* wy, const unsigned char* lut1,
                                const unsigned char* lut2, int heads, int bins1, int bins2, int n1, int n2, float inv_sqrt_d,
                                float* t1, float* tx, float* ty, hipStream_t s);

@@ -157,6 +157,7 @@ class EarlyExitEngine:
             capi.check(self.lib.ee_create(C.byref(c), C.byref(self._h)), None, "ee_create")
         self._finalized = False
         self._stream_generation = 0         # forward_stream() calls so far: a ResultStream belongs to one of them
+        self.ensemble = None                # set_ensemble(): the host copies of (weights, bias), or None
         self.patience = None
         if ec.patience is not None:
             self.set_patience(ec.patience)
@@ -599,6 +600,36 @@ class EarlyExitEngine:
         capi.check(self.lib.ee_set_exit_rule(self._h, r.code), self._h, "ee_set_exit_rule")
         self.exit_rule = r
         return r
+
+    def set_ensemble(self, ensemble=None):
+        """The exit ensemble of every later forward and capture (ee_set_ensemble; the definition is in include/mmee.h): the decision at exit m
+        sees ``y_m = float32(bias[m] + sum_{j <= m} weights[m][j] * logsoftmax(scaled row of exit j))`` instead of exit m's scaled row alone,
+        and ``logits`` / ``all_logits`` / ``confidence`` / ``all_crit`` and the result stream carry it; ``head_logits`` / ``head_crit`` stay the
+        head's own.  ``ensemble``: an ``EnsembleFit`` (``heads.fit_exit_ensemble``), a ``(weights (E+1,E+1), bias (E+1,K) | None)`` pair (numpy
+        or tensors; weights lower triangular), or ``None`` to clear it -- the engine then issues the launches and returns the bits it did
+        before.  One small launch per exit, no backbone work.  Refused under the "gate" criterion and ``use_lte``, and, while the engine
+        holds captured graphs, when the call would switch the ensemble on or off.  Synchronises the device."""
+        if ensemble is None:
+            capi.check(self.lib.ee_set_ensemble(self._h, None, None), self._h, "ee_set_ensemble")
+            self.ensemble = None
+            return None
+        w, b = (ensemble.weights, ensemble.bias) if hasattr(ensemble, "weights") else ensemble
+        host = lambda v: np.ascontiguousarray(v.detach().cpu().numpy() if (torch is not None and isinstance(v, torch.Tensor)) else np.asarray(v),
+                                              dtype=np.float64)
+        E1, K = self.E + 1, self.K
+        w = host(w)
+        b = None if b is None else host(b)
+        if w.shape != (E1, E1) or (b is not None and b.shape != (E1, K)):
+            raise ValueError(f"set_ensemble: weights must be (E+1,E+1) = {(E1, E1)} and bias (E+1,K) = {(E1, K)} or None")
+        dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+        with torch.cuda.device(self.device):
+            capi.check(self.lib.ee_set_ensemble(self._h, dp(w), dp(b)), self._h, "ee_set_ensemble")
+        self.ensemble = (w, b)
+        return self.ensemble
+
+    @property
+    def has_ensemble(self) -> bool:
+        return bool(self.lib.ee_has_ensemble(self._h))
 
     def clock_stamp(self):
         """Device tensor of capi.CLOCK_STAMP_WORDS int64: one (s_memtime, s_memrealtime) pair per CU as seen by one-wave workgroups enqueued on

@@ -860,3 +860,64 @@ def fit_mlp_gate_heads(features, targets, l2: float = 1e-2, gtol: float = 1e-6, 
     _call(name, dev, *lead, theta0, E, N, H, float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.dense_weight, fit.dense_bias,
           fit.weight, fit.bias, fit.theta64, fit.loss, fit.grad_norm, fit.evals, fit.status)
     return fit
+
+
+# ---- the exit ensemble: earlier heads' predictions join each decision --------------------------------------------------------------------------
+@dataclass
+class EnsembleFit:
+    weights: "torch.Tensor"      # (E1,E1) float64, device: lower triangular, row m = the weights of exit m over exits 0 .. m
+    bias: "torch.Tensor"         # (E1,K)  float64
+    loss: "torch.Tensor"         # (E1,) float64: the objective at the returned point; never above the plain exit's mean NLL
+    grad_norm: "torch.Tensor"    # (E1,) float64
+    evals: "torch.Tensor"        # (E1,) int32
+    status: "torch.Tensor"       # (E1,) int32: 0 converged (grad_norm <= gtol), 1 max_evals, 2 the line search made no progress
+    l2: float
+
+    def apply(self, logits) -> "torch.Tensor":
+        """``sweep.ensemble_logits(logits, self.weights, self.bias)``: the ensembled (E1,N,K) float64 array of un-ensembled dumped ``logits``,
+        with the bits a forward returns after ``engine.set_ensemble(self)``."""
+        from .sweep import ensemble_logits
+        return ensemble_logits(logits, self.weights, self.bias, device=self.weights.device)
+
+
+def fit_exit_ensemble(logits, labels, l2: float = 1e-2, gtol: float = 1e-9, max_evals: int = 1000, history: int = 8, init=None,
+                      device=None) -> EnsembleFit:
+    """The weights of the exit ensemble (include/mmee.h, at ee_set_ensemble; Zero Time Waste's weighted geometric ensemble of the exits seen so
+    far) from a dumped array, on the device (``ee_ensemble_fit``).  ``logits`` (E1,N,K): the UN-ensembled scaled rows of a dump-all forward
+    (``all_logits``; numpy or device tensor, taken as float64); ``labels`` (N,) integers in [0,K).  Per exit m it minimises, in float64,
+    mean cross-entropy of the ensemble row + (l2 / 2)(||w_m - e_m||^2 + ||b_m||^2): the penalty pulls toward the plain exit, where the fit
+    starts (``init=None``), so ``loss[m]`` never exceeds the plain exit's mean NLL.  Strongly convex: one optimum, reached by the L-BFGS of
+    ``fit_exit_heads``; deterministic to the bit.  ``init``: an ``EnsembleFit`` or a ``(weights, bias)`` pair to start from.
+
+    The result goes to ``engine.set_ensemble(fit)`` and, through ``fit.apply(logits)``, to every dumped-array tool (``sweep.csf_table``,
+    ``threshold_search``, ``metrics.exit_report``, ``Policy``) -- fit on one split, search thresholds on the ensembled array of another.
+
+    Not built: ``sample_weight`` and reach weights, per-class weights, and the ensemble under the "gate" criterion or ``use_lte``.
+    Host synchronisation: one wait after the last launch, to read the error word (a label outside [0,K) or a logit that is not finite -- a
+    NaN row is an exit the document never reached -- fails the call)."""
+    if not (l2 > 0):
+        raise ValueError(f"fit_exit_ensemble: l2 = {l2}, need l2 > 0")
+    capi.load()
+    dev = logits.device if (torch is not None and isinstance(logits, torch.Tensor) and logits.is_cuda and device is None) \
+        else _require_torch_cuda(device)
+    L = _to_device(logits, torch.float64, dev)
+    if L.dim() != 3:
+        raise ValueError("logits must have shape (num_exits + 1, num_samples, num_labels)")
+    E1, N, K = L.shape
+    y = _to_device(labels, torch.int64, dev).view(-1)
+    if y.shape[0] != N:
+        raise ValueError("labels must have one entry per document")
+    w0 = b0 = None
+    if init is not None:
+        iw, ib = (init.weights, init.bias) if isinstance(init, EnsembleFit) else init
+        w0 = _to_device(iw, torch.float64, dev)
+        b0 = None if ib is None else _to_device(ib, torch.float64, dev)
+        if tuple(w0.shape) != (E1, E1) or (b0 is not None and tuple(b0.shape) != (E1, K)):
+            raise ValueError(f"init must be weights (E1,E1) = {(E1, E1)} and bias (E1,K) = {(E1, K)}")
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+    fit = EnsembleFit(z((E1, E1), torch.float64), z((E1, K), torch.float64), z((E1,), torch.float64), z((E1,), torch.float64),
+                      z((E1,), torch.int32), torch.full((E1,), -1, dtype=torch.int32, device=dev), float(l2))
+    ws, need = _workspace("ee_ensemble_fit_workspace_bytes", dev, E1, N, K, history)
+    _call("ee_ensemble_fit", dev, L, y, w0, b0, E1, N, K, float(l2), float(gtol), int(max_evals), int(history), ws, need, fit.weights, fit.bias,
+          fit.loss, fit.grad_norm, fit.evals, fit.status)
+    return fit

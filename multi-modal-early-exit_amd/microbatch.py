@@ -204,6 +204,20 @@ class MicroBatchedEngine:
             rule = e.set_exit_rule(rule)
         return rule
 
+    def set_ensemble(self, ensemble=None):
+        out = None
+        for e in self.engines:
+            out = e.set_ensemble(ensemble)
+        return out
+
+    @property
+    def ensemble(self):
+        return self.engines[0].ensemble
+
+    @property
+    def has_ensemble(self):
+        return self.engines[0].has_ensemble
+
     @property
     def patience(self):
         return self.engines[0].patience

@@ -199,6 +199,11 @@ class LayoutLMv3EEForSequenceClassification:
             self.model_config.EE_config["inference_strategy"] = want
             self.config.EE_config["inference_strategy"] = want
 
+    def set_ensemble(self, ensemble=None):
+        """The exit ensemble of every later ``early_exit`` / ``forward`` (``EarlyExitEngine.set_ensemble``): an ``EnsembleFit``, a
+        ``(weights, bias)`` pair, or ``None`` to clear it.  Handed to every handle the model runs on."""
+        return self.engine.set_ensemble(ensemble)
+
     def _is_patience(self) -> bool:
         want = self.config.exit_config["inference_strategy"]
         return str(getattr(want, "value", want)) == "patience"

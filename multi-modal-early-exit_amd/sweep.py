@@ -84,6 +84,30 @@ def gate_table(head_logits, final_logits, device=None):
     return table
 
 
+def ensemble_logits(logits, weights, bias=None, device=None):
+    """The exit ensemble (include/mmee.h, at ee_set_ensemble) on a dumped array (ee_ensemble_logits): ``logits`` (E1,N,K), the UN-ensembled
+    scaled rows a dump-all forward returns in ``all_logits``; ``weights`` (E1,E1) lower triangular, ``bias`` (E1,K) or None (numpy or device
+    tensors, taken as float64; an ``EnsembleFit`` holds both).  Returns float64 (E1,N,K) on the device: row m of document n is the ensemble
+    row y_m by the device functions of the forward's own launch -- every value exactly a float32, with the bits ``engine.forward`` returns
+    after ``engine.set_ensemble``.  A NaN row (an exit the document never reached) gives NaN from that exit on.  The result is a logits array
+    like any other: it goes unchanged into ``csf_table``, ``criterion_scan_device`` / ``patience_scan_device`` / ``rule_scan_device``,
+    ``threshold_sweep``, ``threshold_search`` (also with ``cost=``), ``threshold_refine``, ``metrics.exit_report`` and ``Policy``."""
+    lib = capi.load()
+    dev = _require_torch_cuda(device)
+    L = _f64_on(dev, logits)
+    if L.dim() != 3:
+        raise ValueError("logits must have shape (num_exits + 1, num_samples, num_labels)")
+    E1, N, K = L.shape
+    W = _f64_on(dev, weights)
+    Bs = None if bias is None else _f64_on(dev, bias)
+    if tuple(W.shape) != (E1, E1) or (Bs is not None and tuple(Bs.shape) != (E1, K)):
+        raise ValueError(f"weights must be (E1,E1) = {(E1, E1)} and bias (E1,K) = {(E1, K)} or None")
+    out = torch.empty((E1, N, K), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        capi.check(lib.ee_ensemble_logits(_ptr(L), E1, N, K, _ptr(W), _ptr(Bs), _ptr(out), _stream()), None, "ee_ensemble_logits")
+    return out
+
+
 def patience_sweep(logits, references, patiences, want_hist: bool = False, device=None):
     """Every patience value of ``patiences`` (V,) over one dumped array ``logits`` (E1,N,K) with labels ``references`` (N,): for each t the
     exits of the patience policy (include/mmee.h), the accuracy of the predictions at those exits and the mean exit (ee_patience_sweep: the
