@@ -144,6 +144,36 @@ enum { MMEE_CRIT_MAX_CONFIDENCE = 0, MMEE_CRIT_ENTROPY = 1, MMEE_CRIT_PATIENCE =
  * is not E + 1.  MMEE_CRIT_PATIENCE itself also takes the vector: c_e >= t_e (per-exit patience).
  */
 enum { MMEE_RULE_PLAIN = 0, MMEE_RULE_STREAK = 1, MMEE_RULE_EITHER = 2 };
+/*
+ * Budgeted exits (ee_set_quotas): every exit releases the most confident documents of THIS CALL, a chosen number of them -- the budgeted batch
+ * classification setting of MSDNet (Huang et al., ICLR 2018).  THE definition (the forward, ee_quota_scan and the stand-alone hook refer to it).
+ * Exit e below the final one has a quota q_e >= 0, an integer number of documents of this call.  For the n documents that reach exit e:
+ *   c_i    the float64 criterion the decide kernel computes for active document i without quotas: the criterion of the scaled policy row,
+ *          temperature included; under MMEE_CRIT_GATE the gate score of the document's two gate logits; with an ensemble set (ee_set_ensemble)
+ *          the criterion of the ensemble row y_e.
+ *   s_i    = sign * c_i, sign = -1 for MMEE_CRIT_ENTROPY and +1 otherwise: larger is more confident under every criterion.
+ *   i PRECEDES j when s_i > s_j, or s_i == s_j and i's original slot (its index in the call) is lower.  A NaN criterion precedes nothing and
+ *          is preceded by every number; NaNs order among themselves by slot.  (-0.0 == +0.0: a tie.)
+ *   rank_i = the number of active documents that precede i: a permutation of 0 .. n-1.
+ *   MMEE_QUOTA_EXACT    = 1  i leaves iff rank_i < q_e.  Thresholds are not read and may be NULL.  If fewer than q_e documents reach the exit
+ *                            all of them leave and the later stages run empty, as in a forward at threshold 0.
+ *   MMEE_QUOTA_AT_LEAST = 2  i leaves iff the threshold test fires (strict, as without quotas) or rank_i < q_e.  Firing is monotone in s, so
+ *                            this is "the top max(q_e, #fired)": compute has an upper bound that holds for any data, and confident documents
+ *                            still leave early.
+ * What leaves is what leaves without quotas: the scaled policy row, confidence = (float)c_i.  The final exit takes everybody; under
+ * MMEE_FLAG_NO_EXIT quotas are ignored like thresholds; the documents that stay keep their order (compaction stays stable).
+ * A document's logits still do not depend on its batch mates.  Only WHERE IT LEAVES does: this is the first decision of the library with that
+ * property, and it is so by definition -- the same page may leave at another exit in another batch, with that exit's logits.
+ * Under MMEE_QUOTA_EXACT the size of every stage is known before the call, n_{e+1} = max(0, n_e - q_e), whatever the pages are: so are the
+ * FLOPs of the forward, the chunk sizes of the result stream and the work of a captured graph.
+ * Cost: two launches per exit below the final one (exit_quota_crit_kernel writes c_i, exit_quota_rank_kernel counts rank_i: 256 documents per
+ * workgroup, the stage tiled through LDS, O(n^2) integer compares, deterministic to the bit) and the QUOTA form of the decide kernel in place
+ * of the plain one; none at the final exit or in dump-all calls; a handle without quotas issues the launches it always did.
+ * Refused, each with a message: MMEE_CRIT_PATIENCE, MMEE_RULE_STREAK / MMEE_RULE_EITHER and use_lte handles (their decisions carry
+ * per-document state or another score; no rank is defined for them) -- by ee_set_quotas, and by ee_set_criterion / ee_set_exit_rule while
+ * quotas are set.  Not built: quotas across micro-batches or ranks (each would rank alone), an "at most" mode.
+ */
+enum { MMEE_QUOTA_OFF = 0, MMEE_QUOTA_EXACT = 1, MMEE_QUOTA_AT_LEAST = 2 };
 /* model family: LayoutLMv3 (text + layout + image, the reference's EE model) or BEiT / DiT (image only; BASELINE configs[4],
  * the reference's "dit" branch EE/configs.py:429-449 — exit heads there are this build's extrapolation) */
 enum { MMEE_ARCH_LAYOUTLMV3 = 0, MMEE_ARCH_BEIT = 1 };
@@ -291,11 +321,13 @@ int ee_forward(ee_handle* h, const int64_t* input_ids, const int64_t* attention_
  * Neither is the patience: under MMEE_CRIT_PATIENCE, MMEE_RULE_STREAK and MMEE_RULE_EITHER the decide kernel of exit e reads t_e from the
  * same vector (E + 1 entries behind the temperatures), which ee_graph_launch fills with the handle's CURRENT patience (ee_set_patience /
  * ee_set_patience_vector between replays take effect).  The criterion and the exit rule themselves are bound at capture.
+ * Quotas (ee_set_quotas) likewise: whether they are on, and the mode, are bound at capture; the values are a fourth section of the vector
+ * (E + 1 entries behind the patience), filled with the handle's CURRENT quotas by every ee_graph_launch.
  * `stream` must be a created stream (the legacy null stream cannot be captured).  Not capturable: the one-shot side inputs / outputs
  * (ee_set_inputs_embeds, ee_set_hidden_states_out, ee_set_head_mask, ee_set_attentions_out) and an armed ee_profile.
  *
  * ee_graph_launch replays it on `stream` (any stream, the null stream included) with this launch's thresholds (host double [E+1]; may be NULL
- * for a graph captured with MMEE_FLAG_NO_EXIT or under MMEE_CRIT_PATIENCE) and temperatures (host double [E+1] or NULL = 1.0: a division by 1.0 is exact, so a graph
+ * for a graph captured with MMEE_FLAG_NO_EXIT, under MMEE_CRIT_PATIENCE or under MMEE_QUOTA_EXACT) and temperatures (host double [E+1] or NULL = 1.0: a division by 1.0 is exact, so a graph
  * replayed without temperatures returns the bits of the eager call without them).  Same arithmetic, same launch order, same bits as
  * ee_forward on the same inputs (tests/test_gpu_round6.py).  Error reporting, ee_last_stage_counts, ee_last_flops and ee_last_layer_plan work
  * as after ee_forward.  Rows of out_all_* / out_head_* that a replay does not reach keep what the buffers held before (as ee_forward).
@@ -425,6 +457,20 @@ int ee_set_exit_rule(ee_handle* h, int32_t rule);
  * ee_has_ensemble: 1 when an ensemble is set, else 0. */
 int ee_set_ensemble(ee_handle* h, const double* w, const double* b);
 int ee_has_ensemble(const ee_handle* h);
+
+/* The quotas (budgeted exits, semantics above) of every LATER ee_forward, ee_graph_capture and ee_graph_launch: quotas[0 .. n-1] host int32,
+ * n must equal E, the number of exits below the final one; mode MMEE_QUOTA_EXACT or MMEE_QUOTA_AT_LEAST.  Copied; part of the handle's state
+ * until changed, like ee_set_patience_vector.  quotas == NULL switches quotas off (n and mode are then ignored).  The first call allocates
+ * max_docs doubles and max_docs ints of stage scratch.
+ * Captured graphs: whether quotas are on, and in which mode, is bound at capture; the quota VALUES are not -- ee_graph_launch writes the
+ * handle's current quotas into the device vector it refreshes anyway (a fourth section behind thresholds, temperatures and patience), so
+ * ee_set_quotas between two replays takes effect.  A graph captured under MMEE_QUOTA_EXACT replays without thresholds (NULL is accepted).
+ * Refused, with a message and nothing changed: n != E; a negative entry; an unknown mode; a handle under MMEE_CRIT_PATIENCE, under
+ * MMEE_RULE_STREAK / MMEE_RULE_EITHER or with use_lte; a call that would switch quotas on or off, or change the mode, while the handle holds
+ * captured graphs (ee_graph_destroy them first).
+ * ee_has_quotas: the mode (MMEE_QUOTA_EXACT / MMEE_QUOTA_AT_LEAST) when quotas are set, else 0. */
+int ee_set_quotas(ee_handle* h, const int32_t* quotas, int32_t n, int32_t mode);
+int ee_has_quotas(const ee_handle* h);
 
 /* Pin the exit-layer schedule.  DEFAULT (enabled == 0): every layer that ends in a decision is probed first.  Rounds 2-4 chose per layer
  * from the stage populations of "the handle's most recent FINISHED forward" -- a timing-dependent host decision, and under MMEE_FLAG_XPROBE
@@ -591,6 +637,19 @@ int ee_gate_table(const float* head_logits, const double* final_logits, int32_t 
  * on.  The result is a logits array like any other: it goes unchanged into ee_csf_table, the scans, the sweeps, the searches and
  * ee_exit_metrics.  Refused: a NULL logits / w / out, E1, N or K below 1. */
 int ee_ensemble_logits(const double* logits, int32_t E1, int32_t N, int32_t K, const double* w, const double* b, double* out, void* stream);
+/* Budgeted exits (definition at MMEE_QUOTA_*) on a criterion table: table dev double (E1,N), the criterion c of every document at every exit
+ * (ee_csf_table / ee_gate_table / the table of an ensembled array); sign +1 or -1 (-1: entropy); quotas host int32 [E1 - 1], every entry >= 0;
+ * mode MMEE_QUOTA_EXACT or MMEE_QUOTA_AT_LEAST; thresholds host double [E1], needed by AT_LEAST (the event is sign * c > sign * thr[e],
+ * strict), ignored and may be NULL under EXACT; G >= 1 the group size.  Consecutive groups of G documents are ranked independently, as
+ * ceil(N / G) forwards of G documents would be (the last group may be short; a document's slot is its index in the table); the documents
+ * that stay at exit e are the ones ranked at exit e + 1; the last exit takes everybody.  exits dev int32 (N).  cuts dev double
+ * (groups, E1 - 1, 2) or NULL: the criterion of the last leaver (the leaver every other leaver precedes) and of the first stayer (the stayer
+ * that precedes every other stayer) of every group at every exit, NaN where there is none (and where that document's criterion is NaN).
+ * workspace dev int32 (N) of scratch.  Two launches per exit below the last one.  With G = N the midpoints of a row of cuts are MSDNet's
+ * thresholds: a plain thresholded forward then releases that share of a like batch.  Refused: a NULL table / quotas / exits / workspace,
+ * E1 below 1 or above 256, N below 0, G below 1, a sign that is not +-1, an unknown mode, AT_LEAST without thresholds, a negative quota. */
+int ee_quota_scan(const double* table, double sign, int32_t E1, int32_t N, const int32_t* quotas, int32_t mode, const double* thresholds,
+                  int32_t G, int32_t* exits, double* cuts, int32_t* workspace, void* stream);
 
 /*
  * The threshold search: which thresholds should a deployment run?  Candidate thresholds from the percentiles of the confidence table, V candidate
@@ -1394,6 +1453,22 @@ typedef struct ee_debug_rows_out_args {
 int ee_debug_head_out(const ee_debug_head_out_args* args, void* stream);
 int ee_debug_exit_decide(const ee_debug_exit_decide_args* args, void* stream);
 int ee_debug_rows_out(const ee_debug_rows_out_args* args, void* stream);
+/* ee_debug_exit_quota: one exit of one stage under a quota (budgeted exits, definition at MMEE_QUOTA_*): the two ranking launches
+ *   (launch_exit_quota_rank) and the QUOTA form of the decide kernel (launch_decide_quota), then launch_compact_rows as ee_debug_exit_decide.
+ *   decide: the stage, the logits, this exit's thr / temp and every output exactly as for ee_debug_exit_decide; mode must be 0 and rule
+ *   MMEE_RULE_PLAIN (prev / run / patience / lte_score are not read), is_final and no_exit must be 0 (the forward runs the plain kernels
+ *   there).  quota >= 0: this exit's q_e; quota_mode MMEE_QUOTA_EXACT or MMEE_QUOTA_AT_LEAST.  by_pointer != 0 hands thr, temp and the quota
+ *   to the kernels as a captured graph's replay does.  crit dev double [n_docs] and rank dev int32 [n_docs] receive c_i and rank_i by the
+ *   stage's document index; nothing behind n_docs entries is written.  doc_orig may list the slots in any order: the tie-break is by slot.
+ *   Refused: what ee_debug_exit_decide refuses, a NULL crit / rank, a negative quota, an unknown quota_mode, a mode / rule / is_final /
+ *   no_exit other than above. */
+typedef struct ee_debug_exit_quota_args {
+    ee_debug_exit_decide_args decide;
+    int32_t quota, quota_mode;
+    double* crit;
+    int32_t* rank;
+} ee_debug_exit_quota_args;
+int ee_debug_exit_quota(const ee_debug_exit_quota_args* args, void* stream);
 
 /* Unit-test hook of the patch projection (Conv2d with kernel = stride = patch as a GEMM over flattened patches), the counterpart of
  * ee_debug_attention: what patch_projection() of the forward launches, on caller-provided DEVICE buffers; no handle.

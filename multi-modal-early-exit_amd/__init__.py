@@ -13,6 +13,7 @@ from .microbatch import MicroBatchedEngine  # noqa: F401,E402
 from .modeling import (DiTEEForImageClassification, EEModelOutput, EESequenceClassifierOutput,  # noqa: F401,E402
                        LayoutLMv3EEForSequenceClassification, load_local_processor)
 from .policy import Policy, criterion_scan_device, gate_scan_device, lte_scan_device, patience_scan_device, policy_scan_device, rule_scan_device  # noqa: F401,E402
+from .policy import QuotaScan, quota_scan_device  # noqa: F401,E402
 from . import harness  # noqa: F401,E402
 from . import dist  # noqa: F401,E402
 from . import sweep  # noqa: F401,E402

@@ -22,6 +22,8 @@ FLAG_LOW_LATENCY = 64
 FLAG_STREAM_RESULTS = 128
 CRIT_MAX_CONFIDENCE, CRIT_ENTROPY, CRIT_PATIENCE, CRIT_MARGIN, CRIT_GATE = 0, 1, 2, 3, 4
 RULE_PLAIN, RULE_STREAK, RULE_EITHER = 0, 1, 2
+QUOTA_OFF, QUOTA_EXACT, QUOTA_AT_LEAST = 0, 1, 2
+QUOTA_MODES = {"exact": QUOTA_EXACT, "at_least": QUOTA_AT_LEAST}
 SEARCH_GRID, SEARCH_SAMPLED, SEARCH_MIXTURES = 0, 1, 2
 SEARCH_REFERENCE, SEARCH_POLICY = 0, 1
 # the columns of ee_exit_metrics' output rows (MMEE_METRIC_*)
@@ -109,6 +111,11 @@ class DebugExitDecideArgs(C.Structure):
                                       "out_head_crit", "meta_old", "meta_new", "row_src")])
 
 
+class DebugExitQuotaArgs(C.Structure):
+    """ee_debug_exit_quota_args of include/mmee.h: the decide call's arguments, this exit's quota and mode, the two device arrays the ranking fills."""
+    _fields_ = [("decide", DebugExitDecideArgs), ("quota", _i32), ("quota_mode", _i32), ("crit", _vp), ("rank", _vp)]
+
+
 class DebugExitEnsembleArgs(C.Structure):
     """ee_debug_exit_ensemble_args of include/mmee.h: device pointers (or None), this exit's temperature and sizes."""
     _fields_ = ([("pol_logits", _vp)] + [(n, _i32) for n in ("pol_rows", "K", "E1", "exit_index", "B")] + [("temp", C.c_double), ("by_pointer", _i32)]
@@ -166,6 +173,10 @@ SYMBOLS = {
     "ee_set_exit_rule": (C.c_int, [_vp, _i32]),
     "ee_set_ensemble": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "ee_has_ensemble": (C.c_int, [_vp]),
+    "ee_set_quotas": (C.c_int, [_vp, C.POINTER(_i32), _i32, _i32]),
+    "ee_has_quotas": (C.c_int, [_vp]),
+    "ee_quota_scan": (C.c_int, [_vp, C.c_double, _i32, _i32, C.POINTER(_i32), _i32, C.POINTER(C.c_double), _i32, _vp, _vp, _vp, _vp]),
+    "ee_debug_exit_quota": (C.c_int, [C.POINTER(DebugExitQuotaArgs), _vp]),
     "ee_suggest_probe_mask": (C.c_int, [_vp, _u32, C.POINTER(C.c_uint64), _vp]),
     "ee_clock_stamp": (C.c_int, [_vp, _vp]),
     "ee_set_inputs_embeds": (C.c_int, [_vp, _vp]),

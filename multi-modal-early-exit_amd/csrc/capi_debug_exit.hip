@@ -1,6 +1,7 @@
-// ee_debug_head_out, ee_debug_exit_ensemble, ee_debug_exit_decide, ee_debug_rows_out: the exit stage of exit_stage.hip alone, on caller-provided
+// ee_debug_head_out, ee_debug_exit_ensemble, ee_debug_exit_decide, ee_debug_exit_quota, ee_debug_rows_out: the exit stage of exit_stage.hip alone, on caller-provided
 // device buffers; no handle.  Each entry point makes the calls of the path's own launchers that capi_forward.hip makes (launch_head_out;
-// launch_exit_ensemble; launch_decide and, behind it, launch_compact_rows as compact() does; launch_gather_cls / launch_rows_to_padded) and synchronises.  No kernel is defined or
+// launch_exit_ensemble; launch_decide -- under a quota launch_exit_quota_crit, launch_exit_quota_rank and launch_decide_quota -- and, behind it,
+// launch_compact_rows as compact() does; launch_gather_cls / launch_rows_to_padded) and synchronises.  No kernel is defined or
 // instantiated here; what the launchers cannot take is refused, not launched, and so is every row, document or offset outside the caller's
 // buffers.  The stage arrays and the per-document state are the caller's, so a test chains exits: the n_* outputs of one call are the stage
 // of the next.  tests/test_gpu_exit_stage.py drives them against tests/exit_stage_ref.py.
@@ -74,9 +75,25 @@ int ee_debug_head_out(const ee_debug_head_out_args* a, void* stream) {
     return finish(who, s, nullptr, nullptr);
 }
 
-int ee_debug_exit_decide(const ee_debug_exit_decide_args* a, void* stream) {
-    const char* who = "ee_debug_exit_decide";
+}  // extern "C"
+
+namespace {
+
+// ee_debug_exit_decide (qa null) and ee_debug_exit_quota (qa: the quota, its mode and the two arrays the ranking launches fill): the same
+// checks of the stage, the same DecideArgs; the quota form runs the ranking launches and the QUOTA decide kernel in place of launch_decide
+int run_exit_decide(const char* who, const ee_debug_exit_decide_args* a, const ee_debug_exit_quota_args* qa, void* stream) {
     if (!a) return fail(nullptr, "%s: args must not be NULL", who);
+    if (qa) {
+        if (a->mode != DECIDE_THRESHOLD || a->rule != RULE_PLAIN)
+            return fail(nullptr, "%s: a rank is defined for the threshold criteria under the plain rule: mode must be 0 and rule MMEE_RULE_PLAIN, got mode %d, rule %d",
+                        who, a->mode, a->rule);
+        if (a->is_final || a->no_exit)
+            return fail(nullptr, "%s: is_final and no_exit must be 0: the final exit and dump-all calls run the plain decide kernels (ee_debug_exit_decide)", who);
+        if (qa->quota_mode != QUOTA_EXACT && qa->quota_mode != QUOTA_AT_LEAST)
+            return fail(nullptr, "%s: unknown quota_mode %d (MMEE_QUOTA_EXACT = %d, MMEE_QUOTA_AT_LEAST = %d)", who, qa->quota_mode, QUOTA_EXACT, QUOTA_AT_LEAST);
+        if (qa->quota < 0) return fail(nullptr, "%s: quota %d is negative", who, qa->quota);
+        if (!qa->crit || !qa->rank) return fail(nullptr, "%s: crit and rank must not be NULL", who);
+    }
     if (a->mode < DECIDE_THRESHOLD || a->mode > DECIDE_LTE || a->rule < RULE_PLAIN || a->rule > RULE_EITHER || (a->mode == DECIDE_PATIENCE && a->rule != RULE_PLAIN))
         return fail(nullptr, "%s: launch_decide has no kernel for mode %d with rule %d (modes 0 threshold, 1 patience, 2 LTE; rules 0 plain, 1 streak, 2 either; patience takes the plain rule only)",
                     who, a->mode, a->rule);
@@ -132,20 +149,29 @@ int ee_debug_exit_decide(const ee_debug_exit_decide_args* a, void* stream) {
     d.out_all_crit = a->out_all_crit; d.out_head_logits = a->out_head_logits; d.out_head_crit = a->out_head_crit;
     PatienceArgs pa{};
     pa.t = a->patience; pa.prev = a->prev; pa.run = a->run;
+    QuotaArgs q{};
+    if (qa) { q.q = qa->quota; q.crit = qa->crit; q.rank = qa->rank; }
     if (a->by_pointer) {
-        // as a replay reads them: exit e's threshold and temperature at [e] of device vectors, its patience at [0] of the pointer handed over
+        // as a replay reads them: exit e's threshold and temperature at [e] of device vectors, its patience (its quota) at [0] of the pointer handed over
         double *thr = nullptr, *temp = nullptr, *t = nullptr;
         const size_t e1 = (size_t)a->exit_index + 1;
         if (!get_dirty(sc, &thr, e1, s) || !get_dirty(sc, &temp, e1, s) || !get_dirty(sc, &t, 1, s)) return fail(nullptr, kScratchFailed, who);
-        const double hv[3] = {a->thr, a->temp, (double)a->patience};
+        const double hv[3] = {a->thr, a->temp, qa ? (double)qa->quota : (double)a->patience};
         if (hipMemcpyAsync(thr + a->exit_index, &hv[0], sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess ||
             hipMemcpyAsync(temp + a->exit_index, &hv[1], sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess ||
             hipMemcpyAsync(t, &hv[2], sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
             return fail(nullptr, kUploadFailed, who);
         d.thr_ptr = thr; d.temp_ptr = temp; pa.t_ptr = t;
         d.thr = d.temp = __builtin_nan(""); pa.t = -1;             // the by-value forms must not be what the kernel reads
+        if (qa) { q.q_ptr = t; q.q = -1; }
     }
-    launch_decide(d, stateful ? &pa : nullptr, a->mode, a->rule, s);
+    if (qa) {
+        launch_exit_quota_crit(d, q, a->B, s);
+        launch_exit_quota_rank(d, q, a->B, s);
+        launch_decide_quota(d, q, qa->quota_mode, s);
+    } else {
+        launch_decide(d, stateful ? &pa : nullptr, a->mode, a->rule, s);
+    }
     if (compact) {
         const int cus = device_cus(who);
         if (!cus) return 1;
@@ -153,6 +179,17 @@ int ee_debug_exit_decide(const ee_debug_exit_decide_args* a, void* stream) {
                             reinterpret_cast<RowMeta*>(a->meta_new), a->row_src, a->B, cus, s);
     }
     return finish(who, s, nullptr, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ee_debug_exit_decide(const ee_debug_exit_decide_args* a, void* stream) { return run_exit_decide("ee_debug_exit_decide", a, nullptr, stream); }
+
+int ee_debug_exit_quota(const ee_debug_exit_quota_args* a, void* stream) {
+    if (!a) return fail(nullptr, "ee_debug_exit_quota: args must not be NULL");
+    return run_exit_decide("ee_debug_exit_quota", &a->decide, a, stream);
 }
 
 int ee_debug_exit_ensemble(const ee_debug_exit_ensemble_args* a, void* stream) {

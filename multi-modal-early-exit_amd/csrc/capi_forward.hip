@@ -240,8 +240,11 @@ struct Forward {
             return fail(h, "ee_forward: pixel_values and out_exit (and input_ids, bbox for LayoutLMv3) are required");
         if (B < 1 || B > c.max_docs) return fail(h, "ee_forward: B=%d outside [1, max_docs=%d]", B, c.max_docs);
         if (!beit && (T < 1 || T > c.max_text_len)) return fail(h, "ee_forward: T=%d outside [1, max_text_len=%d]", T, c.max_text_len);
-        if (!a.thresholds && !cap && !patience && !no_exit)
-            return fail(h, "ee_forward: thresholds required unless MMEE_FLAG_NO_EXIT or MMEE_CRIT_PATIENCE");
+        if (!a.thresholds && !cap && !patience && !no_exit && h->quota_mode != MMEE_QUOTA_EXACT)
+            return fail(h, "ee_forward: thresholds required unless MMEE_FLAG_NO_EXIT, MMEE_CRIT_PATIENCE or MMEE_QUOTA_EXACT");
+        if (h->quota_mode != MMEE_QUOTA_OFF && (patience || h->rule != MMEE_RULE_PLAIN || c.use_lte))
+            return fail(h, "ee_forward: quotas are set, and no rank is defined under MMEE_CRIT_PATIENCE, MMEE_RULE_STREAK / MMEE_RULE_EITHER or use_lte "
+                           "(ee_set_quotas(h, NULL, 0, 0) first)");
         if (patience && !h->has_patience() && !no_exit)
             return fail(h, "ee_forward: the patience criterion needs ee_set_patience(h, t) with t >= 1 before the first forward");
         if (h->rule != MMEE_RULE_PLAIN && patience)
@@ -679,7 +682,17 @@ struct Forward {
             if (cap) pa.t_ptr = cap->thr_dev + 2 * (E + 1) + exit_index;                  // replays read the patience of THEIR launch
             pa.prev = h->pat_state; pa.run = h->pat_state + c.max_docs;
         }
-        {
+        if (h->quota_mode != MMEE_QUOTA_OFF && !no_exit && !is_final) {
+            // budgeted exits (ee_set_quotas): the stage's criteria and ranks into the scratch, then the QUOTA form of the decide kernel.  The final
+            // exit takes everybody and a dump keeps everybody: the plain kernels below, no launch added
+            QuotaArgs qa{};
+            qa.q = h->quotas[exit_index];
+            if (cap) qa.q_ptr = cap->thr_dev + 3 * (E + 1) + exit_index;                  // replays read the quota of THEIR launch
+            qa.crit = h->quota_crit; qa.rank = h->quota_rank;
+            { ProfScope ps(h, P_QUOTA, s); launch_exit_quota_crit(d, qa, B, s); }
+            { ProfScope ps(h, P_QUOTA, s); launch_exit_quota_rank(d, qa, B, s); }
+            { ProfScope ps(h, P_DECIDE, s); launch_decide_quota(d, qa, h->quota_mode, s); }
+        } else {
             ProfScope ps(h, P_DECIDE, s);
             launch_decide(d, stateful ? &pa : nullptr, patience ? DECIDE_PATIENCE : c.use_lte ? DECIDE_LTE : DECIDE_THRESHOLD, h->rule, s);
         }
@@ -908,7 +921,8 @@ int ee_graph_capture(ee_handle* h, const int64_t* input_ids, const int64_t* atte
     g.n_exits1 = E1;
     g.no_exit = (flags & MMEE_FLAG_NO_EXIT) != 0;
     g.patience = h->cfg.criterion == MMEE_CRIT_PATIENCE;
-    if (dev_alloc(h, &g.thr_dev, (size_t)3 * E1)) return 1;
+    g.quota_mode = h->quota_mode;
+    if (dev_alloc(h, &g.thr_dev, (size_t)4 * E1)) return 1;
     // (2) the launch list again, captured
     hipGraph_t graph = nullptr;
     HIP_OK(h, hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
@@ -929,18 +943,19 @@ int ee_graph_launch(ee_handle* h, int32_t graph_id, const double* thresholds, co
     if (!h) return 1;
     if (graph_id < 0 || graph_id >= (int32_t)h->graphs.size() || !h->graphs[graph_id].exec) return fail(h, "ee_graph_launch: no such graph (%d)", graph_id);
     const ee_handle::GraphRec& g = h->graphs[graph_id];
-    if (!thresholds && !g.no_exit && !g.patience)
-        return fail(h, "ee_graph_launch: thresholds required (the graph was captured without MMEE_FLAG_NO_EXIT or MMEE_CRIT_PATIENCE)");
+    if (!thresholds && !g.no_exit && !g.patience && g.quota_mode != MMEE_QUOTA_EXACT)
+        return fail(h, "ee_graph_launch: thresholds required (the graph was captured without MMEE_FLAG_NO_EXIT, MMEE_CRIT_PATIENCE or MMEE_QUOTA_EXACT)");
     if (h->prof_on) return fail(h, "ee_graph_launch: ee_profile times eager launches; disarm it first");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int rc_pre = forward_pre(h, s);
     if (rc_pre) return rc_pre;
     ThrPack p{};
-    p.n = 3 * g.n_exits1;
+    p.n = 4 * g.n_exits1;
     for (int i = 0; i < g.n_exits1; ++i) {
         p.v[i] = thresholds ? thresholds[i] : 0.0;
         p.v[g.n_exits1 + i] = temperatures ? temperatures[i] : 1.0;
         p.v[2 * g.n_exits1 + i] = (double)h->patience_at(i);
+        p.v[3 * g.n_exits1 + i] = i < (int)h->quotas.size() ? (double)h->quotas[i] : 0.0;      // the handle's CURRENT quotas (the mode is the capture's)
     }
     hipLaunchKernelGGL(set_thresholds_kernel, dim3(1), dim3(64), 0, s, p, g.thr_dev);
     HIP_OK(h, hipGraphLaunch(g.exec, s));

@@ -24,6 +24,7 @@ static_assert(mmee::CRIT_MAX_CONFIDENCE == MMEE_CRIT_MAX_CONFIDENCE && mmee::CRI
               mmee::CRIT_PATIENCE == MMEE_CRIT_PATIENCE && mmee::CRIT_MARGIN == MMEE_CRIT_MARGIN && mmee::CRIT_GATE == MMEE_CRIT_GATE, "the kernels' criterion codes are the ABI's");
 static_assert(mmee::SEARCH_GRID == MMEE_SEARCH_GRID && mmee::SEARCH_SAMPLED == MMEE_SEARCH_SAMPLED && mmee::SEARCH_MIXTURES == MMEE_SEARCH_MIXTURES &&
               mmee::SEARCH_REFERENCE == MMEE_SEARCH_REFERENCE && mmee::SEARCH_POLICY == MMEE_SEARCH_POLICY, "the search's codes are the ABI's");
+static_assert(mmee::QUOTA_OFF == MMEE_QUOTA_OFF && mmee::QUOTA_EXACT == MMEE_QUOTA_EXACT && mmee::QUOTA_AT_LEAST == MMEE_QUOTA_AT_LEAST, "the kernels' quota modes are the ABI's");
 
 namespace mmee {
 namespace capi {
@@ -135,6 +136,11 @@ struct ee_handle {
     double* ens_state = nullptr;                  // (E1,max_docs,K): l_e by original document slot (compaction never moves it)
     double* ens_ones = nullptr;                   // [E1] of 1.0: the temperatures a captured decide launch reads behind the ensemble
     float* ens_logits = nullptr;                  // [max_docs][K]: y of the exit being decided, by the stage's document index
+    // budgeted exits (ee_set_quotas; include/mmee.h): the mode picks the decide kernel and adds the two ranking launches in front of it
+    int32_t quota_mode = MMEE_QUOTA_OFF;
+    std::vector<int32_t> quotas;                  // [E]: q_e of every exit below the final one (empty while quotas are off)
+    double* quota_crit = nullptr;                 // [max_docs]: c_i of the exit being decided, by the stage's document index
+    int* quota_rank = nullptr;                    // [max_docs]: rank_i
     // optional per-kernel event timing (ee_profile)
     bool prof_on = false;
     struct ProfRec { int id; hipEvent_t a, b; double flops; };
@@ -165,10 +171,12 @@ struct ee_handle {
     // thresholds / temperatures live in a device buffer the decide kernels read, refreshed in front of every replay
     struct GraphRec {
         hipGraphExec_t exec = nullptr;
-        double* thr_dev = nullptr;                // [3 * (E + 1)]: thresholds, then temperatures (1.0 when the launch passes none), then the per-exit patience
+        double* thr_dev = nullptr;                // [4 * (E + 1)]: thresholds, then temperatures (1.0 when the launch passes none), then the per-exit patience,
+                                                  // then the quotas (the final exit's entry unused)
         int n_exits1 = 0;
         bool no_exit = false;
         bool patience = false;                    // captured under MMEE_CRIT_PATIENCE: launches need no thresholds
+        int32_t quota_mode = MMEE_QUOTA_OFF;      // the handle's quota mode at capture (MMEE_QUOTA_EXACT: launches need no thresholds)
         mmee::capi::ForwardRecord rec;            // bookkeeping of the captured forward, restored by every launch
     };
     std::vector<GraphRec> graphs;
@@ -300,7 +308,7 @@ struct Scratch {
 
 // kernel roles reported by ee_profile_read (their names: kProfNames in capi_query.hip)
 enum { P_PREP = 0, P_EMBT, P_GPATCH, P_EMBV, P_GQKV, P_ATTN, P_GAO, P_LN, P_GUP, P_GDOWN, P_HEAD, P_DECIDE, P_COMPACT, P_GCLS, P_PROBE,
-       P_PAIRIDX, P_PSPLIT, P_HEADOUT, P_EMIT, P_ENSEMBLE, P_COUNT };
+       P_PAIRIDX, P_PSPLIT, P_HEADOUT, P_EMIT, P_ENSEMBLE, P_QUOTA, P_COUNT };
 
 struct ProfScope {
     ee_handle* h;

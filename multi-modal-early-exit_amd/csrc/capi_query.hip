@@ -35,6 +35,7 @@ const char* const kProfNames[] = {
     "emit_leavers|emit_leavers_kernel",
     // (not nested) ee_set_ensemble: one launch between every exit's head and its decide launch
     "exit_ensemble|exit_ensemble_kernel",
+    "exit_quota_rank|exit_quota_crit_kernel+exit_quota_rank_kernel",
 };
 static_assert(sizeof(kProfNames) / sizeof(kProfNames[0]) == P_COUNT, "one name per profile role");
 
@@ -160,9 +161,55 @@ int ee_set_criterion(ee_handle* h, int32_t criterion) {
     if (criterion == MMEE_CRIT_GATE && h->ens_on)
         return fail(h, "ee_set_criterion: MMEE_CRIT_GATE while an exit ensemble is set: the gate decision does not read the policy row the ensemble "
                        "replaces (not built); clear it first, ee_set_ensemble(h, NULL, NULL)");
+    if (criterion == MMEE_CRIT_PATIENCE && h->quota_mode != MMEE_QUOTA_OFF)
+        return fail(h, "ee_set_criterion: MMEE_CRIT_PATIENCE while quotas are set: PABEE's decision carries per-document state, no rank is defined for it "
+                       "(ee_set_quotas(h, NULL, 0, 0) first)");
     h->cfg.criterion = criterion;      // read by the decide kernel's arguments of every later ee_forward
     return 0;
 }
+
+int ee_set_quotas(ee_handle* h, const int32_t* quotas, int32_t n, int32_t mode) {
+    if (!h) return 1;
+    const ee_config& c = h->cfg;
+    const int E = c.n_embedding_exits + c.n_encoder_exits;
+    const int32_t want = quotas ? mode : MMEE_QUOTA_OFF;
+    if (quotas) {
+        if (mode != MMEE_QUOTA_EXACT && mode != MMEE_QUOTA_AT_LEAST)
+            return fail(h, "ee_set_quotas: unknown mode %d (MMEE_QUOTA_EXACT = %d, MMEE_QUOTA_AT_LEAST = %d)", mode, MMEE_QUOTA_EXACT, MMEE_QUOTA_AT_LEAST);
+        if (n != E) return fail(h, "ee_set_quotas: %d entries, the handle has E = %d exits below the final one (one quota per exit)", n, E);
+        for (int e = 0; e < n; ++e)
+            if (quotas[e] < 0) return fail(h, "ee_set_quotas: quotas[%d]=%d, a quota is a number of documents (>= 0)", e, quotas[e]);
+        if (c.criterion == MMEE_CRIT_PATIENCE)
+            return fail(h, "ee_set_quotas: a handle under MMEE_CRIT_PATIENCE: PABEE's decision carries per-document state, no rank is defined for it (not built)");
+        if (h->rule != MMEE_RULE_PLAIN)
+            return fail(h, "ee_set_quotas: a handle under MMEE_RULE_STREAK / MMEE_RULE_EITHER (rule %d): their decisions carry per-document state, no rank "
+                           "is defined for them (not built; ee_set_exit_rule(h, MMEE_RULE_PLAIN) first)", h->rule);
+        if (c.use_lte)
+            return fail(h, "ee_set_quotas: a use_lte handle: the learning-to-exit decision reads another score, no rank is defined for it (not built)");
+    }
+    if (want != h->quota_mode)
+        for (const auto& g : h->graphs)
+            if (g.exec)
+                return fail(h, "ee_set_quotas: the handle holds captured graphs and the call would switch the quota mode from %d to %d: a graph's launch "
+                               "list is the one of its capture (ee_graph_destroy them first; new quota values under the same mode are fine)",
+                            h->quota_mode, want);
+    if (!quotas) {
+        h->quota_mode = MMEE_QUOTA_OFF;
+        h->quotas.clear();
+        return 0;
+    }
+    if (!h->quota_crit) {
+        double* qc = nullptr;
+        int* qr = nullptr;
+        if (dev_alloc(h, &qc, (size_t)c.max_docs) || dev_alloc(h, &qr, (size_t)c.max_docs)) return 1;
+        h->quota_crit = qc; h->quota_rank = qr;
+    }
+    h->quotas.assign(quotas, quotas + n);      // eager forwards pass q_e by value; ee_graph_launch writes them to the graph's device vector
+    h->quota_mode = mode;
+    return 0;
+}
+
+int ee_has_quotas(const ee_handle* h) { return h ? h->quota_mode : 0; }
 
 int ee_set_ensemble(ee_handle* h, const double* w, const double* b) {
     if (!h) return 1;
@@ -223,6 +270,9 @@ int ee_set_exit_rule(ee_handle* h, int32_t rule) {
     if (rule != MMEE_RULE_PLAIN && h->cfg.criterion == MMEE_CRIT_PATIENCE)
         return fail(h, "ee_set_exit_rule: rule %d under MMEE_CRIT_PATIENCE: PABEE has no threshold event for MMEE_RULE_STREAK / MMEE_RULE_EITHER to build on",
                     rule);
+    if (rule != MMEE_RULE_PLAIN && h->quota_mode != MMEE_QUOTA_OFF)
+        return fail(h, "ee_set_exit_rule: rule %d while quotas are set: MMEE_RULE_STREAK / MMEE_RULE_EITHER carry per-document state, no rank is defined "
+                       "for them (ee_set_quotas(h, NULL, 0, 0) first)", rule);
     h->rule = rule;                    // picks the decide kernel of every later ee_forward / ee_graph_capture
     return 0;
 }

@@ -180,6 +180,46 @@ int ee_rule_scan(const double* criterion, double sign, const double* logits, int
     return run_threshold_scan("ee_rule_scan", "threshold / patience", a, packed.data(), packed.size(), SCAN_TABLE, rule, stream);
 }
 
+int ee_quota_scan(const double* table, double sign, int32_t E1, int32_t N, const int32_t* quotas, int32_t mode, const double* thresholds, int32_t G,
+                  int32_t* exits, double* cuts, int32_t* workspace, void* stream) {
+    const char* who = "ee_quota_scan";
+    if (E1 < 1 || E1 > 256 || N < 0 || N >= (1 << 28) || G < 1 || (sign != 1.0 && sign != -1.0))
+        return fail(nullptr, "%s: bad argument (1 <= E1 <= 256, 0 <= N < 2^28, G >= 1, sign is +1 or -1)", who);
+    if ((E1 > 1 && !quotas) || (N > 0 && (!table || !exits || !workspace))) return fail(nullptr, "%s: table, quotas, exits and workspace must not be NULL", who);
+    if (mode != MMEE_QUOTA_EXACT && mode != MMEE_QUOTA_AT_LEAST)
+        return fail(nullptr, "%s: unknown mode %d (MMEE_QUOTA_EXACT = %d, MMEE_QUOTA_AT_LEAST = %d)", who, mode, MMEE_QUOTA_EXACT, MMEE_QUOTA_AT_LEAST);
+    if (mode == MMEE_QUOTA_AT_LEAST && !thresholds) return fail(nullptr, "%s: MMEE_QUOTA_AT_LEAST needs the thresholds", who);
+    for (int e = 0; e + 1 < E1; ++e)
+        if (quotas[e] < 0) return fail(nullptr, "%s: quotas[%d]=%d, a quota is a number of documents (>= 0)", who, e, quotas[e]);
+    if (!have_device(who)) return 1;
+    if (N == 0) return 0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (G > N) G = N;
+    const int groups = (N + G - 1) / G;
+    // exits = -1 (still active) and cuts = NaN (no such document): both are the all-ones byte pattern
+    if (hipMemsetAsync(exits, 0xFF, sizeof(int32_t) * (size_t)N, s) != hipSuccess ||
+        (cuts && E1 > 1 && hipMemsetAsync(cuts, 0xFF, sizeof(double) * 2 * (size_t)groups * (E1 - 1), s) != hipSuccess))
+        return fail(nullptr, "%s: memset failed", who);
+    QuotaScanArgs a{};
+    a.table = table; a.sign = sign; a.mode = mode; a.E1 = E1; a.N = N; a.G = G;
+    a.exits = exits; a.cuts = cuts; a.rank = workspace;
+    if (E1 == 1) {                                          // the last exit takes everybody: nothing to rank
+        launch_quota_scan(a, s);
+        return launch_status(nullptr, who);
+    }
+    // one upload (the caller's arrays, as the threshold scans do): the thresholds [E1] doubles when they are read, then the quotas [E1 - 1] ints
+    const bool at_least = mode == MMEE_QUOTA_AT_LEAST;
+    std::vector<double> packed((at_least ? E1 : 0) + E1 / 2 + 1);
+    if (at_least) memcpy(packed.data(), thresholds, sizeof(double) * E1);
+    memcpy(packed.data() + (at_least ? E1 : 0), quotas, sizeof(int32_t) * (E1 - 1));
+    const TempUpload<double> up(packed.data(), packed.size(), s);
+    if (up.err) return fail(nullptr, "%s: threshold / quota %s", who, up.err);
+    a.thr = at_least ? up.dev : nullptr;
+    a.quotas = reinterpret_cast<const int*>(up.dev + (at_least ? E1 : 0));
+    launch_quota_scan(a, s);
+    return launch_status(nullptr, who);
+}
+
 int ee_rule_sweep(const double* conf, const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, const double* thr, int32_t V,
                   const int32_t* patiences, int32_t P, int32_t rule, double* acc, double* mean_exit, int32_t* exit_hist, void* stream) {
     if (!conf || !logits || !references || !thr || !patiences || !acc || !mean_exit || E1 < 1 || E1 > 64 || N < 1 || N >= (1 << 24) || K < 1 || V < 0 ||

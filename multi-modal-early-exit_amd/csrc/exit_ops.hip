@@ -675,6 +675,84 @@ void launch_ensemble_logits(const double* logits, int E1, int N, int K, const do
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Budgeted exits on a criterion table (ee_quota_scan; definition in include/mmee.h): consecutive groups of G documents, each ranked as one
+// forward's stage would be.  exits[n] < 0 marks a document that is still active; nothing is compacted, a document's slot is its index in its
+// group, so "the survivors in their order" is the group with the leavers masked out (quota_key 0 = no document).  Per exit below the last:
+//   quota_scan_rank_kernel    the forward's counting (quota_rank_by_counting), 256 documents per workgroup, ceil(G / 256) workgroups per group;
+//   quota_scan_decide_kernel  one workgroup per group: the active and the fired documents counted (integers), then the decision by the
+//                             definition's own expression, rank < q or the event, and the two cut criteria: the documents ranked m - 1 and m
+//                             with m the number of leavers.
+// The rank launch reads exits, the decide launch writes it: two launches, not one.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void quota_scan_rank_kernel(QuotaScanArgs a, int e, int blocks_per_group) {
+    __shared__ unsigned long long t_key[2048];
+    __shared__ int t_slot[2048];
+    const int g = blockIdx.x / blocks_per_group, lb = blockIdx.x - g * blocks_per_group;
+    const long long start = (long long)g * a.G;
+    const int ng = (long long)a.N - start < a.G ? (int)(a.N - start) : a.G;
+    if (lb * 256 >= ng) return;                                            // the same for every thread of the workgroup
+    const double* row = a.table + (size_t)e * a.N + start;
+    const int* ex = a.exits + start;
+    const double sign = a.sign;
+    const int i = lb * 256 + threadIdx.x;
+    const bool active = i < ng && ex[i] < 0;
+    const unsigned long long key = active ? quota_key(row[i], sign) : 0ull;
+    const unsigned r = quota_rank_by_counting(key, i, ng, [&](int j) { return ex[j] < 0 ? quota_key(row[j], sign) : 0ull; }, [](int j) { return j; }, t_key,
+                                              t_slot);
+    if (active) a.rank[start + i] = (int)r;
+}
+
+__global__ __launch_bounds__(256) void quota_scan_decide_kernel(QuotaScanArgs a, int e) {
+    __shared__ int s_cnt[2][4];
+    const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long start = (long long)g * a.G;
+    const int ng = (long long)a.N - start < a.G ? (int)(a.N - start) : a.G;
+    const double* row = a.table + (size_t)e * a.N + start;
+    int* ex = a.exits + start;
+    const int q = a.quotas[e];
+    const bool at_least = a.mode == QUOTA_AT_LEAST;
+    const double sthr = at_least ? a.sign * a.thr[e] : 0.0;
+    int na = 0, nf = 0;
+    for (int i = threadIdx.x; i < ng; i += 256) {
+        const bool active = ex[i] < 0;
+        na += active ? 1 : 0;
+        nf += (active && at_least && a.sign * row[i] > sthr) ? 1 : 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) { na += __shfl_xor(na, o, 64); nf += __shfl_xor(nf, o, 64); }
+    if (lane == 0) { s_cnt[0][wave] = na; s_cnt[1][wave] = nf; }
+    __syncthreads();                                                       // also: every read of exits above is behind us
+    na = s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3];
+    nf = s_cnt[1][0] + s_cnt[1][1] + s_cnt[1][2] + s_cnt[1][3];
+    const int mq = q < na ? q : na;
+    const int m = mq > nf ? mq : nf;                                       // the leavers: the top max(q, #fired) (the event is monotone in s)
+    double* cut = a.cuts ? a.cuts + ((size_t)g * (a.E1 - 1) + e) * 2 : nullptr;
+    for (int i = threadIdx.x; i < ng; i += 256) {
+        if (ex[i] >= 0) continue;
+        const int r = a.rank[start + i];
+        const double c = row[i];
+        const bool leave = r < q || (at_least && a.sign * c > sthr);
+        if (cut && r == m - 1) cut[0] = c;
+        if (cut && r == m) cut[1] = c;
+        if (leave) ex[i] = e;
+    }
+}
+
+__global__ __launch_bounds__(256) void quota_scan_final_kernel(int* __restrict__ exits, int N, int last) {
+    for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += gridDim.x * 256)
+        if (exits[n] < 0) exits[n] = last;
+}
+
+void launch_quota_scan(const QuotaScanArgs& a, hipStream_t s) {
+    const int group = a.G < a.N ? a.G : a.N;
+    const int groups = (a.N + a.G - 1) / a.G, bpg = (group + 255) / 256;
+    for (int e = 0; e + 1 < a.E1; ++e) {
+        hipLaunchKernelGGL(quota_scan_rank_kernel, dim3((unsigned)groups * (unsigned)bpg), dim3(256), 0, s, a, e, bpg);
+        hipLaunchKernelGGL(quota_scan_decide_kernel, dim3(groups), dim3(256), 0, s, a, e);
+    }
+    hipLaunchKernelGGL(quota_scan_final_kernel, dim3(grid_1d(a.N, 256, 4096)), dim3(256), 0, s, a.exits, a.N, a.E1 - 1);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Per-exit temperature fit: argmin_T mean NLL(softmax(z / T), y)   (TemperatureScaler.set_temperature,
 // EE/generic_scaling.py:64-111, L-BFGS-B on sklearn log_loss).  In beta = 1/T the objective
 //     f(beta) = mean( logsumexp(beta z) - beta z_y )

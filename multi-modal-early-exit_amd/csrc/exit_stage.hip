@@ -10,6 +10,7 @@
 //     outputs and removed, deeper layers run on the survivors only.  (The same policy on a dumped array: exit_ops.hip.)
 // All of it is HBM/latency-bound integer + small-vector work; none of it is shaped into a GEMM.
 #include "mmee_kernels.h"
+#include "ranked_common.h"
 
 namespace mmee {
 
@@ -163,6 +164,10 @@ __device__ inline double crit_f64(const float* z, int K, double temp, int criter
 // must have held at t_e exits in a row (s_e = f_e ? s_{e-1} + 1 : 0 in p.run[orig]).  MMEE_RULE_EITHER: the event, or PABEE's counter
 // c_e >= t_e ((p.prev[orig], p.run[orig]) exactly as under PATIENCE).  The same state arrays, written unconditionally at exit 0; t_e is the
 // launch's own patience (by value, or at p.t_ptr[0]: the host hands every exit its own entry).  RULE_PLAIN compiles to the kernels as they were.
+// QUOTA (ee_set_quotas; DECIDE_THRESHOLD with RULE_PLAIN only): the criterion is the one exit_quota_crit_kernel left in q.crit -- the value this
+// kernel's own branches below would compute, the gate score under CRIT_GATE -- and the test is on q.rank, the document's place among the stage's
+// documents: QUOTA_EXACT rank < q_e, QUOTA_AT_LEAST the threshold test or rank < q_e.  Everything below the `leave` line is shared.  QUOTA_OFF
+// compiles to the kernels as they were.
 // ---------------------------------------------------------------------------------------------------------------
 // PABEE's counter: argmax of the scaled logits as they are written out (two f32 logits can round to one scaled value; first maximum wins),
 // c_e = the argmax equals the one at the previous exit ? c_{e-1} + 1 : 0, state by original slot
@@ -179,10 +184,11 @@ __device__ __forceinline__ int agreement_run(const float* z, int K, double temp,
     return run;
 }
 
-template <int MODE, int RULE = RULE_PLAIN>
-__device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const PatienceArgs& p) {
+template <int MODE, int RULE = RULE_PLAIN, int QUOTA = QUOTA_OFF>
+__device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const PatienceArgs& p, const QuotaArgs& q = QuotaArgs{}) {
     constexpr bool PATIENCE = MODE == DECIDE_PATIENCE;
     static_assert(RULE == RULE_PLAIN || !PATIENCE, "PABEE has no threshold event to build a rule on");
+    static_assert(QUOTA == QUOTA_OFF || (MODE == DECIDE_THRESHOLD && RULE == RULE_PLAIN), "a rank is defined for the threshold criteria under the plain rule");
     __shared__ int s_cnt[16], s_rows[16];
     __shared__ unsigned long long s_sq[16];
     __shared__ int s_carry_docs, s_carry_rows;
@@ -192,6 +198,8 @@ __device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const Pati
     const double temp = a.temp_ptr ? a.temp_ptr[a.exit_index] : a.temp;
     int patience = 0;
     if constexpr (PATIENCE || RULE != RULE_PLAIN) patience = p.t_ptr ? (int)p.t_ptr[0] : p.t;
+    int quota = 0;
+    if constexpr (QUOTA != QUOTA_OFF) quota = q.q_ptr ? (int)q.q_ptr[0] : q.q;
     if (tid == 0) { s_carry_docs = 0; s_carry_rows = 0; }
     unsigned long long sq = 0;
     __syncthreads();
@@ -206,7 +214,11 @@ __device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const Pati
             const float* z = a.pol_logits + (size_t)i * a.K;
             double crit;
             bool leave;
-            if constexpr (PATIENCE) {
+            if constexpr (QUOTA != QUOTA_OFF) {
+                crit = q.crit[i];
+                leave = q.rank[i] < quota;
+                if constexpr (QUOTA == QUOTA_AT_LEAST) leave = leave || crit_fires(a.criterion, crit, thr);      // strict, as below
+            } else if constexpr (PATIENCE) {
                 crit = crit_f64(z, a.K, temp, CRIT_MAX_CONFIDENCE);
                 leave = agreement_run(z, a.K, temp, a.exit_index, orig, p) >= patience;
             } else if constexpr (MODE == DECIDE_LTE) {
@@ -302,6 +314,9 @@ __global__ __launch_bounds__(1024) void exit_decide_either_kernel(DecideArgs a, 
 __global__ __launch_bounds__(1024) void exit_decide_lte_streak_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<DECIDE_LTE, RULE_STREAK>(a, p); }
 __global__ __launch_bounds__(1024) void exit_decide_lte_either_kernel(DecideArgs a, PatienceArgs p) { exit_decide_body<DECIDE_LTE, RULE_EITHER>(a, p); }
 
+__global__ __launch_bounds__(1024) void exit_decide_quota_exact_kernel(DecideArgs a, QuotaArgs q) { exit_decide_body<DECIDE_THRESHOLD, RULE_PLAIN, QUOTA_EXACT>(a, PatienceArgs{}, q); }
+__global__ __launch_bounds__(1024) void exit_decide_quota_at_least_kernel(DecideArgs a, QuotaArgs q) { exit_decide_body<DECIDE_THRESHOLD, RULE_PLAIN, QUOTA_AT_LEAST>(a, PatienceArgs{}, q); }
+
 // mode: DECIDE_*, rule: RULE_PLAIN / _STREAK / _EITHER.  The plain threshold and LTE kernels keep no state and take no PatienceArgs (p may be null)
 void launch_decide(const DecideArgs& a, const PatienceArgs* p, int mode, int rule, hipStream_t s) {
     using Plain = void (*)(DecideArgs);
@@ -312,6 +327,57 @@ void launch_decide(const DecideArgs& a, const PatienceArgs* p, int mode, int rul
                                             {nullptr, exit_decide_lte_streak_kernel, exit_decide_lte_either_kernel}};
     if (plain[mode] && rule == RULE_PLAIN) hipLaunchKernelGGL(plain[mode], dim3(1), dim3(1024), 0, s, a);
     else hipLaunchKernelGGL(stateful[mode][rule], dim3(1), dim3(1024), 0, s, a, *p);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Budgeted exits (ee_set_quotas; definition in include/mmee.h): the ranking step, two launches between an exit's head (or ensemble launch) and
+// its decision.  exit_quota_crit_kernel: one thread per active document, c_i by the expressions of exit_decide_body<DECIDE_THRESHOLD> into the
+// stage scratch.  exit_quota_rank_kernel: 256 documents per workgroup, the whole stage tiled through LDS as keys (quota_key) and original
+// slots, rank_i by counting (quota_rank_by_counting) -- O(n^2) compares over ceil(n / 256) workgroups, integers only, so the ranks are the same
+// bits whatever the grid.  The grid is sized by the call's static document count; a workgroup past the stage's n_docs returns before any barrier.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void exit_quota_crit_kernel(DecideArgs a, QuotaArgs q) {
+    const int n = a.counts->n_docs;
+    const double temp = a.temp_ptr ? a.temp_ptr[a.exit_index] : a.temp;
+    const bool gate = a.criterion == CRIT_GATE && !a.is_final && a.head_logits;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        double crit;
+        if (gate) {
+            const float* hz = a.head_logits + (size_t)i * a.Kh;
+            crit = gate_score_f64(hz[0], hz[1]);
+        } else {
+            crit = crit_f64(a.pol_logits + (size_t)i * a.K, a.K, temp, a.criterion);
+        }
+        q.crit[i] = crit;
+    }
+}
+
+__global__ __launch_bounds__(256) void exit_quota_rank_kernel(DecideArgs a, QuotaArgs q) {
+    __shared__ unsigned long long t_key[2048];
+    __shared__ int t_slot[2048];
+    const int n = a.counts->n_docs;
+    if ((int)blockIdx.x * 256 >= n) return;                                // the same for every thread of the workgroup
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const double sign = crit_sign(a.criterion);
+    const double* crit = q.crit;
+    const int* orig = a.doc_orig;
+    const unsigned long long key = i < n ? quota_key(crit[i], sign) : 0ull;
+    const int slot = i < n ? orig[i] : 0;
+    const unsigned r = quota_rank_by_counting(key, slot, n, [&](int j) { return quota_key(crit[j], sign); }, [&](int j) { return orig[j]; }, t_key, t_slot);
+    if (i < n) q.rank[i] = (int)r;
+}
+
+void launch_exit_quota_crit(const DecideArgs& a, const QuotaArgs& q, int max_docs, hipStream_t s) {
+    hipLaunchKernelGGL(exit_quota_crit_kernel, dim3(grid_1d(max_docs, 256, 1024)), dim3(256), 0, s, a, q);
+}
+
+void launch_exit_quota_rank(const DecideArgs& a, const QuotaArgs& q, int max_docs, hipStream_t s) {
+    hipLaunchKernelGGL(exit_quota_rank_kernel, dim3((max_docs + 255) / 256), dim3(256), 0, s, a, q);
+}
+
+void launch_decide_quota(const DecideArgs& a, const QuotaArgs& q, int quota_mode, hipStream_t s) {
+    if (quota_mode == QUOTA_EXACT) hipLaunchKernelGGL(exit_decide_quota_exact_kernel, dim3(1), dim3(1024), 0, s, a, q);
+    else hipLaunchKernelGGL(exit_decide_quota_at_least_kernel, dim3(1), dim3(1024), 0, s, a, q);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -71,9 +71,9 @@ struct HeadOutArgs {
     double* lte_out;                 // [n_docs] u = sigmoid(w . x + b), float64
 };
 
-// thresholds, then temperatures, then the per-exit patience, of one ee_graph_launch: a kernel ARGUMENT of set_thresholds_kernel (no host buffer has to outlive the call)
+// thresholds, then temperatures, then the per-exit patience, then the quotas, of one ee_graph_launch: a kernel ARGUMENT of set_thresholds_kernel (no host buffer has to outlive the call)
 struct ThrPack {
-    double v[3 * (64 + 4)];          // 3 x (MMEE_MAX_ENCODER_EXITS + 3 embedding exits + final): thresholds, temperatures, per-exit patience
+    double v[4 * (64 + 4)];          // 4 x (MMEE_MAX_ENCODER_EXITS + 3 embedding exits + final): thresholds, temperatures, per-exit patience, quotas
     int n;
 };
 
@@ -187,6 +187,42 @@ void launch_ensemble_logsoftmax(const double* logits, size_t rows, int K, double
 // how launch_decide picks its kernel: the exit test (MODE) and the rule built on it (RULE = MMEE_RULE_*; DECIDE_PATIENCE takes RULE_PLAIN only)
 enum { DECIDE_THRESHOLD = 0, DECIDE_PATIENCE = 1, DECIDE_LTE = 2 };
 enum { RULE_PLAIN = 0, RULE_STREAK = 1, RULE_EITHER = 2, RULE_AGREE = 3 };      // RULE_AGREE: PABEE's counter alone (exit_scan_kernel only)
+
+// Budgeted exits (ee_set_quotas; the definition is in include/mmee.h): the decision compares a document with its batch mates.  Between an
+// exit's head (or ensemble launch) and its decision two launches rank the stage: exit_quota_crit_kernel writes the float64 criterion of every
+// active document to `crit`, exit_quota_rank_kernel turns the criteria into rank[i] = the number of active documents that precede i.  The
+// QUOTA instantiations of the decide kernel read both; the final exit and dump-all calls run the plain kernels and neither launch.
+enum { QUOTA_OFF = 0, QUOTA_EXACT = 1, QUOTA_AT_LEAST = 2 };                    // MMEE_QUOTA_* (capi_internal.h asserts the values agree)
+struct QuotaArgs {
+    int q;                           // THIS exit's quota q_e: the documents of the call that leave here (EXACT), or at least leave here (AT_LEAST)
+    const double* q_ptr;             // captured-graph forwards: q_e at [0], as PatienceArgs::t_ptr; null: `q`
+    double* crit;                    // [n_docs] stage scratch: c_i, by the stage's document index
+    int* rank;                       // [n_docs] stage scratch: rank_i
+};
+// The order of the ranking as one unsigned compare: s = sign * c, a larger key is a more confident document.  -0.0 and +0.0 share a key
+// (s + 0.0); every NaN takes key 1, below every number; 0 is left to "no document" (the dumped-array tool's documents that have left).
+__host__ __device__ inline unsigned long long quota_key(double c, double sign) {
+    const double s = sign * c + 0.0;
+    if (s != s) return 1ull;
+    unsigned long long u;
+    __builtin_memcpy(&u, &s, sizeof(u));
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+void launch_exit_quota_crit(const DecideArgs& a, const QuotaArgs& q, int max_docs, hipStream_t s);      // the two ranking launches: c_i,
+void launch_exit_quota_rank(const DecideArgs& a, const QuotaArgs& q, int max_docs, hipStream_t s);      // then rank_i (max_docs >= n_docs sizes the grids)
+void launch_decide_quota(const DecideArgs& a, const QuotaArgs& q, int quota_mode, hipStream_t s);        // QUOTA_EXACT / QUOTA_AT_LEAST; threshold criteria, plain rule
+// ee_quota_scan (exit_ops.hip): the same decision on a criterion table (E1,N), consecutive groups of G documents ranked independently
+struct QuotaScanArgs {
+    const double* table;             // (E1,N) on the device
+    double sign;
+    const int* quotas;               // [E1 - 1] on the device
+    const double* thr;               // [E1] on the device (QUOTA_AT_LEAST), or null
+    int mode, E1, N, G;
+    int* exits;                      // (N)
+    double* cuts;                    // (groups, E1 - 1, 2) or null: criterion of the last leaver / of the first stayer, NaN where there is none
+    int* rank;                       // (N) scratch
+};
+void launch_quota_scan(const QuotaScanArgs& a, hipStream_t s);
 
 // exit_scan_kernel<EVENT, RULE>: the exit decision on dumped arrays (ee_policy_scan, ee_patience_scan, ee_lte_scan, ee_rule_scan)
 // the event's criterion: float64 max-softmax of the logits row, crit[e][n], no event, float64 entropy / margin of the logits row

@@ -1,7 +1,8 @@
 // Device code shared by the tools that work on dumped (E1, N, K) arrays -- the ranked sweeps (exit_ops.hip), the two threshold searches
-// (threshold_search.hip, threshold_search_cost.hip) and the evaluation report (exit_metrics.hip).  __device__ __forceinline__ functions only:
-// the percentile lerp and the candidate vectors' digits of the searches, and the three loops these tools are built from, each written here
-// and nowhere else (metrics_curve_kernel excepted, see exit_metrics.hip): ranked_walk, stable_rank_by_counting, block1024_scan.
+// (threshold_search.hip, threshold_search_cost.hip) and the evaluation report (exit_metrics.hip) -- and, for the quota rank, by the forward's
+// exit stage (exit_stage.hip).  __device__ __forceinline__ functions only:
+// the percentile lerp and the candidate vectors' digits of the searches, and the loops these tools are built from, each written here
+// and nowhere else (metrics_curve_kernel excepted, see exit_metrics.hip): ranked_walk, stable_rank_by_counting, quota_rank_by_counting, block1024_scan.
 // SearchVectors and SweepRanks are declared in mmee_kernels.h.
 #pragma once
 #include "mmee_kernels.h"
@@ -122,6 +123,35 @@ __device__ __forceinline__ uint2 stable_rank_by_counting(const double* __restric
         }
     }
     return make_uint2(lt, eq_before);
+}
+
+// The quota rank (include/mmee.h, at ee_set_quotas) by the same counting, for a workgroup of 256 threads: how many of the n documents
+// (key_at(j), slot_at(j)), j = 0 .. n-1, precede the thread's own (key, slot) -- a larger quota_key, or the same key and a lower slot.  Slots
+// are distinct, so over the n documents the result is a permutation of 0 .. n-1.  The documents pass through t_key / t_slot (2048 entries of
+// LDS each); a key of 0 ("no document") precedes nobody, and a thread without a document of its own still loads and counts, its result ignored.
+// Per pair: two broadcast LDS reads, two 64-bit compares and one 32-bit compare; nothing is added in floating point.
+template <typename KeyAt, typename SlotAt>
+__device__ __forceinline__ unsigned quota_rank_by_counting(unsigned long long key, int slot, int n, KeyAt&& key_at, SlotAt&& slot_at,
+                                                           unsigned long long* t_key, int* t_slot) {
+    unsigned before = 0;
+    for (int m0 = 0; m0 < n; m0 += 2048) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < 2048; i += 256) {
+            const bool in = m0 + i < n;
+            t_key[i] = in ? key_at(m0 + i) : 0ull;
+            t_slot[i] = in ? slot_at(m0 + i) : 0;
+        }
+        __syncthreads();
+        const int cnt = n - m0 < 2048 ? n - m0 : 2048;
+#pragma unroll 4
+        for (int i = 0; i < cnt; ++i) {
+            const unsigned long long k = t_key[i];
+            const int sl = t_slot[i];
+            before += k > key ? 1u : 0u;
+            before += (k == key && sl < slot) ? 1u : 0u;
+        }
+    }
+    return before;
 }
 
 // A scan over the 1024 threads of a workgroup in thread order, for an associative and commutative `op` on integers (any order of combining

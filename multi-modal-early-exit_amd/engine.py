@@ -158,6 +158,7 @@ class EarlyExitEngine:
         self._finalized = False
         self._stream_generation = 0         # forward_stream() calls so far: a ResultStream belongs to one of them
         self.ensemble = None                # set_ensemble(): the host copies of (weights, bias), or None
+        self.quotas, self.quota_mode = None, None      # set_quotas(): the per-exit quotas and "exact" / "at_least", or None
         self.patience = None
         if ec.patience is not None:
             self.set_patience(ec.patience)
@@ -251,7 +252,8 @@ class EarlyExitEngine:
                 validate: bool = False, whole_layers: bool = False, probe_always: bool = False, xprobe: Optional[bool] = None,
                 one_term: bool = False, inputs_embeds=None, want_hidden_states: bool = False, out=None, head_mask=None,
                 want_attentions: bool = False, patience: Optional[Union[int, Sequence[int]]] = None, exit_rule=None,
-                low_latency: bool = False, _capture: bool = False, _stream: bool = False) -> EngineOutput:
+                low_latency: bool = False, quotas: Optional[Sequence[int]] = None, quota_mode: Optional[str] = None,
+                quota_fractions: Optional[Sequence[float]] = None, _capture: bool = False, _stream: bool = False) -> EngineOutput:
         """``out``: optional preallocated ``(logits (B,K) f32, exit_layer (B,) i32, confidence (B,) f32)`` device tensors (contiguous; row
         slices of larger tensors qualify) the kernels write into instead of fresh allocations -- MicroBatchedEngine hands each half its slice.
         ``patience``: when given, ``set_patience(patience)`` before the call (an int, or one entry per exit; it matters under the "patience"
@@ -259,7 +261,11 @@ class EarlyExitEngine:
         given, ``set_exit_rule(exit_rule)`` before the call.  Both stay set for later calls; a capture binds the rule.
         ``low_latency``: MMEE_FLAG_LOW_LATENCY, for batches of a few documents (the reference's ``eval_batch_size = 1``): the attention-output and
         FFN-down GEMMs of every layer run as split-K wherever ``capi`` ``ee_low_latency_k_splits`` allows it for this (B, T) -- see
-        ``last_k_splits()``.  Same exits, logits within the 1e-4 bar, not the bits of the call without it; split precision, LayoutLMv3 only."""
+        ``last_k_splits()``.  Same exits, logits within the 1e-4 bar, not the bits of the call without it; split precision, LayoutLMv3 only.
+        ``quotas`` / ``quota_fractions`` / ``quota_mode``: when given, ``set_quotas(...)`` before the call (budgeted exits: every exit releases
+        the most confident documents of THIS call, a chosen number of them; ``set_quotas``).  ``quota_fractions`` is the convenience: the share
+        of the call's B documents per exit, turned into integers by ``sweep.quotas_from_fractions``.  They stay set for later calls, like the
+        patience; ``set_quotas(None)`` switches them off.  Under ``quota_mode="exact"`` the thresholds are not read."""
         if not self._finalized:
             raise capi.MMEEError("load_weights() has not been called")
         if patience is not None:
@@ -307,6 +313,15 @@ class EarlyExitEngine:
             if t is not None and tuple(t.shape) != (B, T):
                 raise ValueError(f"{n} must be (B,T)")
         E, K = self.E, self.K
+        if quotas is not None and quota_fractions is not None:
+            raise ValueError("quotas and quota_fractions are two ways to say the same thing: pass one")
+        if quota_fractions is not None:
+            from .sweep import quotas_from_fractions
+            quotas = quotas_from_fractions(B, quota_fractions, E)
+        if quotas is not None:
+            self.set_quotas(quotas, mode=quota_mode or self.quota_mode or "exact")
+        elif quota_mode is not None:
+            raise ValueError("quota_mode= goes with quotas= or quota_fractions= (set_quotas(None) switches quotas off)")
         if thresholds is None:
             thresholds = self.exit_config.global_threshold
         thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float64).reshape(-1), (E + 1,)).copy() \
@@ -631,6 +646,33 @@ class EarlyExitEngine:
     def has_ensemble(self) -> bool:
         return bool(self.lib.ee_has_ensemble(self._h))
 
+    def set_quotas(self, quotas: Optional[Sequence[int]] = None, mode: str = "exact"):
+        """Budgeted exits of every later forward, capture and graph launch (ee_set_quotas; the definition is in include/mmee.h): ``quotas``, one
+        non-negative integer per exit below the final classifier, is how many documents OF EACH CALL leave at that exit -- the most confident
+        ones by the engine's criterion, ties to the lower slot.  ``mode="exact"``: exactly those (fewer when fewer arrive), thresholds are not
+        read, so the size of every stage is ``n_{e+1} = max(0, n_e - q_e)`` whatever the pages are.  ``mode="at_least"``: those, and whoever
+        passes the threshold test as well -- an upper bound on compute that holds for any data.  A document's logits still do not depend on
+        its batch mates; only where it leaves does.  ``None`` switches quotas off: the engine then issues the launches and returns the bits
+        it did before.  Two small launches per exit.  Refused under the "patience" criterion, the exit rules other than "plain" and
+        ``use_lte``, and, while the engine holds captured graphs, when the call would switch quotas on or off or change the mode (new
+        values under the same mode are read by the next replay)."""
+        if quotas is None:
+            capi.check(self.lib.ee_set_quotas(self._h, None, 0, 0), self._h, "ee_set_quotas")
+            self.quotas, self.quota_mode = None, None
+            return None
+        if str(mode) not in capi.QUOTA_MODES:
+            raise ValueError(f'set_quotas: mode "{mode}" is neither "exact" nor "at_least"')
+        q = [int(v) for v in np.asarray(quotas).reshape(-1)]
+        if any(float(a) != float(b) for a, b in zip(q, np.asarray(quotas).reshape(-1))):
+            raise ValueError("set_quotas: quotas are whole numbers of documents (quota_fractions= takes shares)")
+        capi.check(self.lib.ee_set_quotas(self._h, (C.c_int32 * max(len(q), 1))(*q), len(q), capi.QUOTA_MODES[str(mode)]), self._h, "ee_set_quotas")
+        self.quotas, self.quota_mode = q, str(mode)
+        return q
+
+    @property
+    def has_quotas(self) -> bool:
+        return bool(self.lib.ee_has_quotas(self._h))
+
     def clock_stamp(self):
         """Device tensor of capi.CLOCK_STAMP_WORDS int64: one (s_memtime, s_memrealtime) pair per CU as seen by one-wave workgroups enqueued on
         the current stream (ee_clock_stamp).  ``clock_ghz(a, b)`` turns two stamps into the shader clock held between them."""
@@ -673,13 +715,20 @@ class CapturedForward:
         self.engine, self.graph_id, self.inputs, self.outputs = engine, graph_id, inputs, outputs
 
     def launch(self, thresholds: Optional[Union[float, Sequence[float]]] = None, temperatures: Optional[Sequence[float]] = None,
-               validate: bool = False, patience: Optional[Union[int, Sequence[int]]] = None) -> EngineOutput:
+               validate: bool = False, patience: Optional[Union[int, Sequence[int]]] = None,
+               quotas: Optional[Sequence[int]] = None) -> EngineOutput:
         """Replay on torch's current stream with this launch's thresholds / temperatures; returns ``self.outputs`` (the same tensors every
         time: copy what must outlive the next launch).  ``patience``: ``engine.set_patience(patience)`` first (an int or one entry per exit); a
-        graph captured under the patience criterion or a combined exit rule replays with the engine's current patience either way."""
+        graph captured under the patience criterion or a combined exit rule replays with the engine's current patience either way.
+        ``quotas``: ``engine.set_quotas(quotas, mode=<the engine's mode>)`` first; a graph captured with quotas set replays with the engine's
+        current quotas either way (whether quotas are on, and the mode, are the capture's)."""
         eng = self.engine
         if patience is not None:
             eng.set_patience(patience)
+        if quotas is not None:
+            if eng.quota_mode is None:
+                raise ValueError("launch(quotas=): the graph was captured without quotas (whether they are on is bound at capture)")
+            eng.set_quotas(quotas, mode=eng.quota_mode)
         E = eng.E
         if thresholds is None:
             thresholds = eng.exit_config.global_threshold

@@ -68,6 +68,15 @@ class MicroBatchedEngine:
         base, extra = divmod(B, n)
         return [base + (1 if i < extra else 0) for i in range(n)]
 
+    _NO_QUOTAS = ("MicroBatchedEngine refuses quotas: a quota ranks the documents of ONE call against each other, and the slices of a "
+                  "micro-batched call would each rank alone -- the result would not be the single-handle result.  Use EarlyExitEngine")
+
+    def set_quotas(self, quotas=None, mode: str = "exact"):
+        """Not built: budgeted exits compare a document with its batch mates, and every handle here sees a slice of the batch only."""
+        if quotas is None:
+            return None
+        raise ValueError(self._NO_QUOTAS)
+
     def forward_stream(self, *args, **kw):
         """Not built (module docstring): interleaving the result streams of several handles is a host policy of its own."""
         raise NotImplementedError("MicroBatchedEngine has no result stream: use EarlyExitEngine.forward_stream (one handle, one stream)")
@@ -79,6 +88,8 @@ class MicroBatchedEngine:
         batches of a few documents, micro-batches are for large ones."""
         if kw.pop("low_latency", False):
             raise ValueError("low_latency is a small-batch mode of EarlyExitEngine; MicroBatchedEngine runs large batches")
+        if any(kw.get(k) is not None for k in ("quotas", "quota_fractions", "quota_mode")):
+            raise ValueError(self._NO_QUOTAS)
         ref = pixel_values if pixel_values is not None else input_ids
         if ref is None:
             raise ValueError("pixel_values is required")

@@ -240,6 +240,9 @@ class LayoutLMv3EEForSequenceClassification:
         mb = eng.max_docs
         if B <= mb:
             return eng.forward(**tensors, **kw)
+        if any(kw.get(k) is not None for k in ("quotas", "quota_fractions")) or getattr(eng, "quota_mode", None):
+            raise ValueError(f"quotas rank the documents of one call: {B} documents do not fit the engine's max_docs = {mb}, and slices would "
+                             "each rank alone")
         parts = []
         for s in range(0, B, mb):
             sl = {k: (v[s:s + mb] if v is not None else None) for k, v in tensors.items()}
@@ -331,7 +334,10 @@ class LayoutLMv3EEForSequenceClassification:
         ``enable_lte()`` repeats its one threshold (EE/models/LayoutLMv3.py:147-149); ``confidence`` is the LTE score.  Under
         ``config.exit_config["exit_rule"]`` "patient_confident" / "patience_or_threshold" the thresholds feed the rule's event and the patience
         is read as under "patience" (include/mmee.h MMEE_RULE_*); ``forward`` (dump-all) does not look at the rule.
-        ``low_latency=True`` (batches of a few documents, one handle): the engine's split-K mode, ``EarlyExitEngine.forward(low_latency=True)``."""
+        ``low_latency=True`` (batches of a few documents, one handle): the engine's split-K mode, ``EarlyExitEngine.forward(low_latency=True)``.
+        ``quotas=`` / ``quota_fractions=`` / ``quota_mode=`` (budgeted exits, ``EarlyExitEngine.set_quotas``): every exit releases the most
+        confident documents of THIS call, a chosen number of them; they stay set on the engine until ``engine.set_quotas(None)``.  One handle, one
+        call: refused with ``micro_batches`` and for a batch above the engine's ``max_docs``."""
         self._patience_kw(patience, kw)
         if low_latency:
             kw["low_latency"] = True

@@ -10,6 +10,7 @@ There is no CPU fallback: without the HIP library / a GPU the call raises.
 from __future__ import annotations
 
 import ctypes as C
+from typing import Optional
 
 import numpy as np
 
@@ -171,6 +172,71 @@ def rule_scan_device(criterion, logits, thresholds, patience, rule, sign: float 
                                                                                 exits, pred, conf, counts, stream))
 
 
+class QuotaScan:
+    """What ``quota_scan_device`` returns: ``exits`` (N,) int32 on the device -- it goes unchanged into ``metrics.exit_report(exits=)``,
+    ``reach_weights`` and ``ExitReport.efficiency`` -- and ``cuts`` (groups, E1 - 1, 2) float64 on the device or ``None``: the criterion of the
+    last leaver and of the first stayer of every group at every exit, NaN where there is none."""
+
+    def __init__(self, exits, cuts, sign: float, group: int, quotas, mode: str):
+        self.exits, self.cuts, self.sign, self.group, self.quotas, self.mode = exits, cuts, float(sign), int(group), list(quotas), mode
+
+    def counts(self) -> np.ndarray:
+        """The exit histogram (E1,) of ``exits``, on the host."""
+        return np.bincount(self.exits.cpu().numpy(), minlength=len(self.quotas) + 1)
+
+    def thresholds(self, group: int = 0) -> np.ndarray:
+        """MSDNet's thresholds from the cuts of one group (scan a validation table with ``group_size = N``): per exit the midpoint between the
+        criterion of the last leaver and of the first stayer, (E1,) float64 with the final exit's entry 0 (never read: the final exit takes
+        everybody).  A plain thresholded forward with these releases, on the scanned table, exactly the scan's leavers (when no cut
+        straddles a tie), and about that share of a like batch.  Where nobody left the threshold is the unreachable side of the
+        criterion's direction (``sign * inf``), where nobody stayed the other one."""
+        if self.cuts is None:
+            raise ValueError("QuotaScan.thresholds: the scan ran with want_cuts=False")
+        c = self.cuts[group].cpu().numpy()
+        last, first = c[:, 0], c[:, 1]
+        thr = 0.5 * (last + first)
+        thr = np.where(np.isnan(last), self.sign * np.inf, np.where(np.isnan(first), -self.sign * np.inf, thr))
+        return np.concatenate([thr, [0.0]])
+
+
+def quota_scan_device(table, quotas, mode: str = "exact", thresholds=None, group_size: Optional[int] = None, sign: float = 1.0,
+                      want_cuts: bool = True, device=None) -> QuotaScan:
+    """Budgeted exits (include/mmee.h MMEE_QUOTA_*) on a criterion table (ee_quota_scan).  ``table`` (E1,N): the criterion of every document
+    at every exit (``sweep.csf_table`` / ``sweep.gate_table`` / the table of an ensembled array); ``sign`` -1 for entropy, else +1;
+    ``quotas``: one integer per exit below the last; ``mode`` "exact" or "at_least" (which needs ``thresholds``, scalar or (E1,));
+    ``group_size`` G (default N): consecutive groups of G documents are ranked independently, as N / G forwards of G documents would be."""
+    if str(mode) not in capi.QUOTA_MODES:
+        raise ValueError(f'quota_scan_device: mode "{mode}" is neither "exact" nor "at_least"')
+    if float(sign) not in (1.0, -1.0):
+        raise ValueError("sign must be +1 (larger is more confident) or -1 (entropy)")
+    lib = capi.load()
+    dev = _require_torch_cuda(device)
+    T = _f64_on(dev, table)
+    if T.dim() != 2:
+        raise ValueError("table must have shape (num_exits + 1, num_samples)")
+    E1, N = T.shape
+    q = [int(v) for v in np.asarray(quotas).reshape(-1)]
+    if len(q) != E1 - 1:
+        raise ValueError(f"quota_scan_device: {len(q)} quotas, the table has {E1 - 1} exits below the last one")
+    if mode == "at_least" and thresholds is None:
+        raise ValueError('quota_scan_device: mode "at_least" needs thresholds')
+    G = N if group_size is None else int(group_size)
+    if G < 1 and N > 0:
+        raise ValueError("group_size must be >= 1")
+    G = max(G, 1)
+    groups = (N + G - 1) // G if N else 0
+    exits = torch.empty((N,), dtype=torch.int32, device=dev)
+    work = torch.empty((max(N, 1),), dtype=torch.int32, device=dev)
+    cuts = torch.empty((groups, E1 - 1, 2), dtype=torch.float64, device=dev) if want_cuts else None
+    q_c = (C.c_int32 * max(E1 - 1, 1))(*q)
+    thr_c = None if thresholds is None else _threshold_vector(thresholds, E1)
+    with torch.cuda.device(dev):
+        rc = lib.ee_quota_scan(_ptr(T), float(sign), E1, N, q_c, capi.QUOTA_MODES[str(mode)], thr_c, G, _ptr(exits), _ptr(cuts), _ptr(work),
+                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    capi.check(rc, None, "ee_quota_scan")
+    return QuotaScan(exits, cuts, sign, G, q, str(mode))
+
+
 class Policy:
     def __init__(self, logits, config) -> None:
         self.logits = logits
@@ -291,6 +357,31 @@ class Policy:
         the argmax has stayed the same for ``config["patience"]`` exits in a row: the earlier of the threshold policy's and
         ``patience_policy``'s exits.  Same configuration keys as ``patient_confident_policy``."""
         return self._rule_policy("patience_or_threshold")
+
+    def quota_policy(self):
+        """Budgeted exits (include/mmee.h MMEE_QUOTA_*; MSDNet's budgeted batch classification) on dumped arrays: ``config["quotas"]``, one
+        integer per exit below the last, is how many documents of every group of ``config["quota_group"]`` consecutive documents (default:
+        all of them, one group) leave at that exit, the most confident by ``config["criterion"]`` ("max_confidence", the default; "entropy";
+        "margin") first.  ``config["quota_mode"]`` "exact" (default) or "at_least", which also releases whoever passes
+        ``config["exit_thresholds"]`` / ``config["exit_threshold"]``.  Unlike every other policy here, a document's exit depends on the
+        other documents of its group.  ``config["exit_policy"] = "quota_policy"`` selects it through EE/eval.py:91-98's ``getattr`` dispatch."""
+        from .sweep import csf_table
+        if self.config.get("quotas") is None:
+            raise ValueError('quota_policy needs config["quotas"] (one integer per exit below the last)')
+        st = threshold_criterion(self.config.get("criterion", "max_confidence"))
+        mode = str(self.config.get("quota_mode", "exact"))
+        thr = self._exit_thresholds("quota_policy (quota_mode at_least)") if mode == "at_least" else None
+        table = csf_table(self.logits, criterion=st)[0]
+        scan = quota_scan_device(table, self.config["quotas"], mode=mode, thresholds=thr, group_size=self.config.get("quota_group"),
+                                 sign=-1.0 if st.value == "entropy" else 1.0, want_cuts=False)
+        num_exits, num_samples = self.logits.shape[0], self.logits.shape[1]
+        L = _f64_on(scan.exits.device, self.logits)
+        pred = L[scan.exits.long(), torch.arange(num_samples, device=L.device)]
+        exits_store = scan.exits.cpu().numpy().astype(np.int32)
+        tgt = self.config.get("device", "cpu")
+        predictions = pred.to(tgt) if str(tgt) != str(pred.device) else pred
+        c = np.bincount(exits_store, minlength=num_exits)
+        return exits_store, predictions, {exit_id: int(c[exit_id]) / num_samples for exit_id in range(0, num_exits)}
 
     def accuracy_calibration_heuristic(self):
         """EE/policy.py:55-111: per-exit thresholds minmax_eps(1 - accuracy/ece)."""

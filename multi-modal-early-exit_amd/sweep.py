@@ -427,6 +427,72 @@ def exit_costs(cfg, attention_mask=None, text_rows=None, unit: float = 1e6) -> n
     return out.astype(np.uint32)
 
 
+# ---- budgeted exits: quotas from shares and from a compute budget (host code; include/mmee.h MMEE_QUOTA_*) ---------------------------------------
+def quotas_from_fractions(B: int, fractions, num_exits: Optional[int] = None) -> list:
+    """Integer quotas of a call of ``B`` documents from per-exit shares: ``q_e = R(B * sum_{j <= e} f_j) - R(B * sum_{j < e} f_j)`` with
+    ``R(x) = floor(x + 0.5)`` and the running sums ``np.cumsum`` of the float64 shares.  The rounding never drifts: the quotas through exit e sum to
+    ``R(B * sum_{j <= e} f_j)``, so shares summing to 1 release everybody before the final exit only when they say so.  ``fractions``: one
+    share per exit below the final one (``num_exits`` of them when given; one more entry, the final exit's own share, is accepted and not
+    used: the final exit takes whoever is left).  Shares are >= 0 and sum to at most 1 (+ 1e-9)."""
+    f = np.asarray(fractions, dtype=np.float64).reshape(-1)
+    B = int(B)
+    if B < 0:
+        raise ValueError("quotas_from_fractions: B must be >= 0")
+    if num_exits is not None:
+        if f.shape[0] == num_exits + 1:
+            f = f[:num_exits]
+        elif f.shape[0] != num_exits:
+            raise ValueError(f"quota_fractions: {f.shape[0]} shares, the model has {num_exits} exits below the final one")
+    if f.size and (not np.isfinite(f).all() or f.min() < 0 or f.sum() > 1.0 + 1e-9):
+        raise ValueError("quota_fractions: shares are finite, >= 0 and sum to at most 1")
+    edges = np.floor(B * np.cumsum(f) + 0.5).astype(np.int64)
+    return [int(v) for v in np.diff(np.concatenate([[0], edges]))]
+
+
+def budget_quotas(cost, budget: float, B: int, q: Optional[float] = None):
+    """MSDNet's budgeted batch classification (Huang et al., ICLR 2018, section 4 and appendix): the share of a batch that leaves at exit e is
+    geometric, ``p_e = q^e / sum_j q^j`` over the ``E1`` exits, and the batch then costs ``sum_e p_e cost_e`` per document.  ``cost`` (E1,): the
+    cost of a document that leaves at exit e, rising with e -- e.g. ``exit_costs(...).mean(1)``.  Without ``q`` it is found by bisection (on
+    log q) so that the expected cost equals ``budget``; ``ValueError`` when the budget is outside ``[cost[0], cost[E1 - 1]]``, the cost of
+    releasing everybody at the first / the final exit.  With ``q`` given the budget is not read.  Returns ``(quotas, p, q)``: the integer
+    quotas of a call of ``B`` documents for the E1 - 1 exits below the final one (``quotas_from_fractions``), the shares ``p`` (E1,) and q.
+    Host code; no device."""
+    c = np.asarray(cost, dtype=np.float64).reshape(-1)
+    E1 = c.shape[0]
+    if E1 < 1 or not np.isfinite(c).all() or (np.diff(c) < 0).any():
+        raise ValueError("budget_quotas: cost is (E1,), finite and non-decreasing in the exit")
+    e = np.arange(E1, dtype=np.float64)
+
+    def shares(logq):
+        w = e * logq
+        w = np.exp(w - w.max())
+        return w / w.sum()
+
+    if q is None:
+        budget = float(budget)
+        if not (c[0] <= budget <= c[-1]):
+            raise ValueError(f"budget_quotas: budget {budget:g} outside [cost_0, cost_E] = [{c[0]:g}, {c[-1]:g}]")
+        if c[-1] == c[0]:
+            logq = 0.0
+        else:
+            lo, hi = -745.0 / max(E1 - 1, 1) - 1.0, 745.0 / max(E1 - 1, 1) + 1.0      # p = (1, 0, ..) and (.., 0, 1) to the last bit of float64
+            for _ in range(200):                                                       # the expected cost rises with q
+                mid = 0.5 * (lo + hi)
+                if float(shares(mid) @ c) < budget:
+                    lo = mid
+                else:
+                    hi = mid
+            logq = 0.5 * (lo + hi)
+        p = shares(logq)
+        qv = float(np.exp(logq))
+    else:
+        qv = float(q)
+        if not (qv > 0 and np.isfinite(qv)):
+            raise ValueError("budget_quotas: q must be positive and finite")
+        p = shares(np.log(qv))
+    return quotas_from_fractions(B, p[:-1]), p, qv
+
+
 # ---- the threshold refinement (ee_threshold_refine) -------------------------------------------------------------------------------------------
 _REFINE_STATUS = {0: "no admissible single-exit change improves J", 1: "max_rounds reached", 2: "the start is over its budget"}
 
