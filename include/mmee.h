@@ -174,6 +174,40 @@ enum { MMEE_RULE_PLAIN = 0, MMEE_RULE_STREAK = 1, MMEE_RULE_EITHER = 2 };
  * quotas are set.  Not built: quotas across micro-batches or ranks (each would rank alone), an "at most" mode.
  */
 enum { MMEE_QUOTA_OFF = 0, MMEE_QUOTA_EXACT = 1, MMEE_QUOTA_AT_LEAST = 2 };
+/*
+ * Model cascades (ee_cascade_select / _gather / _merge; the Python CascadeEngine): the cheap model runs on every document and passes on only
+ * the ones it is unsure about -- CascadeBERT (Li et al., Findings of EMNLP 2021).  THE definition (the three entry points and CascadeEngine
+ * refer to it).
+ * Stages s = 0 .. S-1, S >= 2, each a finalised handle on the same device with the same num_labels K.  Stage s has E1_s = E_s + 1 exits; its
+ * offset is off_s = sum_{r < s} E1_r, the GLOBAL exit index of its local exit e is off_s + e, and SE1 = sum_s E1_s.
+ * A stage runs its ordinary ee_forward on its documents, under its own thresholds, temperatures, criterion, rule, ensemble and quotas: that
+ * code is not touched, and a handle outside a cascade issues the launches it always did.
+ * A document of stage s < S-1 is DEFERRED when it left at the stage's final exit (exit_layer == E_s) and the deferral criterion does not fire
+ * on the row the stage delivered for it:
+ *   c      the criterion, in float64, of (double) of the delivered float32 logits row (temperature already applied by the forward), by the
+ *          functions the criterion table of ee_csf_table is made of: the max-softmax 1 / sum_k exp(z_k - m) with m the first maximum and the
+ *          sum in label order, the entropy log A - B / A, the margin of MMEE_CRIT_MARGIN.
+ *   the document STAYS iff c passes thresholds_s[E_s] in the criterion's direction, strictly ('>'; entropy '<'): a NaN row never fires and is
+ *          deferred.  The threshold is the stage's own final entry, which ee_forward carries and never reads.
+ *   the criterion is the handle's own threshold criterion; handles under MMEE_CRIT_GATE, MMEE_CRIT_PATIENCE or use_lte take
+ *          MMEE_CRIT_MAX_CONFIDENCE, which is what they report at the final exit anyway.  A caller may override it per stage.
+ * Documents that left before the final exit are never deferred; the last stage defers nobody.
+ * The deferred documents keep their order (ascending original slot) and are stage s+1's batch; their inputs are rows of the caller's arrays
+ * for that stage.  A document's result is the result of the last stage it ran in: logits and confidence are that stage's, exit_layer is the
+ * global index, stage the stage index.
+ * The equivalence that makes the dumped-array tools apply.  When every stage is under one and the same plain threshold criterion, all
+ * temperatures are 1 and the early-exit rows are the dump-all rows bit for bit (the K | V probe; not MMEE_FLAG_XPROBE), let D be the
+ * (SE1, B, K) concatenation of the stages' dump-all out_all_logits over all B documents and t the (SE1) concatenation of their thresholds.
+ * Then ee_criterion_scan(D, t, criterion) returns the cascade's global exit_layer for every document whose criteria are not within rounding
+ * of a threshold: a cascade is ONE early-exit model whose exit list is the concatenation of its stages' exit lists, and ee_csf_table, the
+ * scans, the sweeps, the searches (also with a cost), ee_threshold_refine, ee_exit_metrics and ee_quota_scan take D unchanged.  Choosing the
+ * deferral threshold is the search that already exists.
+ * Cost per stage boundary: three launches (select; gather, skipped when the caller supplies the deferred inputs itself; merge) and ONE host
+ * read of 4 bytes, the number of deferred documents, because the next ee_forward takes its batch size by value.  Nothing else crosses.
+ * Not built: a deferral quota (when fewer documents reach the final exit than the quota the count falls short: it needs a forward that takes
+ * its batch size from the device), streaming across stages, captured cascades (a later stage's batch size depends on the data), stages on
+ * different GPUs, a deferral that reads anything but the delivered row.
+ */
 /* model family: LayoutLMv3 (text + layout + image, the reference's EE model) or BEiT / DiT (image only; BASELINE configs[4],
  * the reference's "dit" branch EE/configs.py:429-449 — exit heads there are this build's extrapolation) */
 enum { MMEE_ARCH_LAYOUTLMV3 = 0, MMEE_ARCH_BEIT = 1 };
@@ -650,6 +684,34 @@ int ee_ensemble_logits(const double* logits, int32_t E1, int32_t N, int32_t K, c
  * E1 below 1 or above 256, N below 0, G below 1, a sign that is not +-1, an unknown mode, AT_LEAST without thresholds, a negative quota. */
 int ee_quota_scan(const double* table, double sign, int32_t E1, int32_t N, const int32_t* quotas, int32_t mode, const double* thresholds,
                   int32_t G, int32_t* exits, double* cuts, int32_t* workspace, void* stream);
+/* Model cascades (definition above, behind MMEE_QUOTA_*): the three launches of a stage boundary, handle-free like the other tools; every
+ * pointer is a device pointer unless it says host.
+ * ee_cascade_select: which of a stage's n documents are deferred.  logits float (n,K) and exit_layer int32 (n): what the stage's forward
+ *   delivered, by the stage's document index; orig int32 (n): the documents' original slots, ascending, or NULL: the identity (stage 0);
+ *   final_exit = E_s; criterion MMEE_CRIT_MAX_CONFIDENCE, _ENTROPY or _MARGIN; threshold = thresholds_s[E_s].  Writes next_orig int32 (n):
+ *   the original slots of the deferred documents in their order (entries past the count are not written), count_dev int32 (1): their
+ *   number, and crit_out double (n) or NULL: c of EVERY document.  One workgroup, one launch.
+ * ee_cascade_gather: dst[j] <- src[slots[j]] for j < *count_dev, for n_arrays <= 8 arrays at once.  descs HOST array of n_arrays
+ *   descriptors; a row is row_bytes bytes, a multiple of 4; src and dst 4-byte aligned and not overlapping; copied in 16-byte pieces when
+ *   src, dst and row_bytes are all multiples of 16, else in 8- or 4-byte ones.  slots int32 (cap) with slots[j] a row of every src;
+ *   cap >= *count_dev is the static bound that sizes the grid (cap == 0: nothing is launched).  Rows of dst from *count_dev on are not
+ *   written.
+ * ee_cascade_merge: a later stage's results into the cascade's outputs.  logits float (n,K), exit_layer int32 (n), confidence float (n) by
+ *   the stage's document index, slots int32 (n) their original slots; writes out_logits (B,K), out_exit (B) = exit_layer + exit_offset,
+ *   out_confidence (B) and out_stage (B) = stage at those slots and nowhere else.  n == 0: nothing is launched.
+ * Refused: n or cap below 0, K below 1, final_exit / exit_offset / stage below 0, a criterion that is not one of the three, n_arrays outside
+ *   0 .. 8, a row_bytes that is below 4 or no multiple of 4, a misaligned src / dst, NULL pointers where n (cap, n_arrays) is above 0. */
+typedef struct ee_cascade_desc {
+    const void* src;
+    void* dst;
+    int64_t row_bytes;
+} ee_cascade_desc;
+int ee_cascade_select(const float* logits, const int32_t* exit_layer, const int32_t* orig, int32_t n, int32_t K, int32_t final_exit,
+                      int32_t criterion, double threshold, int32_t* next_orig, int32_t* count_dev, double* crit_out, void* stream);
+int ee_cascade_gather(const ee_cascade_desc* descs, int32_t n_arrays, const int32_t* slots, const int32_t* count_dev, int32_t cap, void* stream);
+int ee_cascade_merge(const float* logits, const int32_t* exit_layer, const float* confidence, const int32_t* slots, int32_t n, int32_t K,
+                     int32_t exit_offset, int32_t stage, float* out_logits, int32_t* out_exit, float* out_confidence, int32_t* out_stage,
+                     void* stream);
 
 /*
  * The threshold search: which thresholds should a deployment run?  Candidate thresholds from the percentiles of the confidence table, V candidate

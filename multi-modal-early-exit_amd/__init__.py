@@ -27,3 +27,5 @@ from .heads import (GateFit, HeadFit, LteFit, MlpGateFit, MlpHeadFit, balanced_c
                     fit_distilled_mlp_exit_heads, fit_exit_heads, fit_gate_heads, fit_lte_classifier, fit_mlp_exit_heads,
                     fit_mlp_gate_heads, gate_targets, lte_targets, reach_weights)
 from .heads import EnsembleFit, fit_exit_ensemble  # noqa: F401,E402
+from . import cascade  # noqa: F401,E402
+from .cascade import CascadeEngine, CascadeOutput  # noqa: F401,E402

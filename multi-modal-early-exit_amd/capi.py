@@ -145,7 +145,17 @@ class DebugGemmRoutesArgs(C.Structure):
                 + [(n, _i32) for n in ("max_m", "m_on_device", "iters")])
 
 
+class CascadeDesc(C.Structure):
+    """ee_cascade_desc of include/mmee.h: one array of ee_cascade_gather (device pointers, bytes per row)."""
+    _fields_ = [("src", _vp), ("dst", _vp), ("row_bytes", C.c_int64)]
+
+
+CASCADE_MAX_ARRAYS = 8         # descriptors one ee_cascade_gather launch takes
+
 SYMBOLS = {
+    "ee_cascade_select": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp]),
+    "ee_cascade_gather": (C.c_int, [C.POINTER(CascadeDesc), _i32, _vp, _vp, _i32, _vp]),
+    "ee_cascade_merge": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ee_create": (C.c_int, [C.POINTER(EEConfig), C.POINTER(_vp)]),
     "ee_destroy": (C.c_int, [_vp]),
     "ee_last_error": (C.c_char_p, [_vp]),

@@ -1,5 +1,6 @@
 // Entry points of libmmee_hip.so that never see a handle: bucket LUT, shader-clock stamps, policy / patience / threshold sweeps, temperature
-// fit, the evaluation report (ee_exit_metrics), result packing, the device-side input feed, and the GEMM micro-benchmark hooks (ee_debug_gemm,
+// fit, the evaluation report (ee_exit_metrics), result packing, the three launches of a cascade's stage boundary (ee_cascade_select / _gather /
+// _merge), the device-side input feed, and the GEMM micro-benchmark hooks (ee_debug_gemm,
 // ee_debug_gemm_split, ee_debug_gemm_split_resid, ee_debug_gemm_routes, ee_debug_attn_stamps).  The L-BFGS fits are in capi_fit.hip, the hooks that run one kernel of the path alone for its
 // float64 test in capi_debug_*.hip.
 #include <math.h>
@@ -218,6 +219,56 @@ int ee_quota_scan(const double* table, double sign, int32_t E1, int32_t N, const
     a.quotas = reinterpret_cast<const int*>(up.dev + (at_least ? E1 : 0));
     launch_quota_scan(a, s);
     return launch_status(nullptr, who);
+}
+
+int ee_cascade_select(const float* logits, const int32_t* exit_layer, const int32_t* orig, int32_t n, int32_t K, int32_t final_exit,
+                      int32_t criterion, double threshold, int32_t* next_orig, int32_t* count_dev, double* crit_out, void* stream) {
+    if (n < 0 || K < 1 || final_exit < 0 || !count_dev || (n > 0 && (!logits || !exit_layer || !next_orig)))
+        return fail(nullptr, "ee_cascade_select: bad argument (n >= 0, K >= 1, final_exit >= 0, count_dev not NULL, logits / exit_layer / "
+                             "next_orig not NULL when n > 0)");
+    if (criterion != MMEE_CRIT_MAX_CONFIDENCE && criterion != MMEE_CRIT_ENTROPY && criterion != MMEE_CRIT_MARGIN)
+        return fail(nullptr, "ee_cascade_select: criterion %d is not a threshold criterion (MMEE_CRIT_MAX_CONFIDENCE, _ENTROPY, _MARGIN)", criterion);
+    if (!have_device("ee_cascade_select")) return 1;
+    CascadeSelectArgs a{};
+    a.logits = logits; a.exit_layer = exit_layer; a.orig = orig; a.n = n; a.K = K; a.final_exit = final_exit; a.criterion = criterion;
+    a.thr = threshold; a.next_orig = next_orig; a.count = count_dev; a.crit = crit_out;
+    launch_cascade_select(a, reinterpret_cast<hipStream_t>(stream));     // n == 0 too: the count is written
+    return launch_status(nullptr, "ee_cascade_select");
+}
+
+int ee_cascade_gather(const ee_cascade_desc* descs, int32_t n_arrays, const int32_t* slots, const int32_t* count_dev, int32_t cap, void* stream) {
+    if (n_arrays < 0 || n_arrays > kCascadeMaxArrays)
+        return fail(nullptr, "ee_cascade_gather: %d arrays (one launch takes 0 .. %d descriptors)", n_arrays, kCascadeMaxArrays);
+    if (cap < 0 || (n_arrays > 0 && !descs) || (n_arrays > 0 && cap > 0 && (!slots || !count_dev)))
+        return fail(nullptr, "ee_cascade_gather: bad argument (cap >= 0, descs / slots / count_dev not NULL when there is something to copy)");
+    CascadeGatherArgs a{};
+    a.n_arrays = n_arrays; a.slots = slots; a.count = count_dev;
+    for (int r = 0; r < n_arrays; ++r) {
+        const ee_cascade_desc& d = descs[r];
+        if (!d.src || !d.dst) return fail(nullptr, "ee_cascade_gather: descriptor %d has a NULL src / dst", r);
+        if (d.row_bytes < 4 || d.row_bytes % 4 != 0)
+            return fail(nullptr, "ee_cascade_gather: descriptor %d: row_bytes %lld is not a positive multiple of 4", r, (long long)d.row_bytes);
+        if (reinterpret_cast<uintptr_t>(d.src) % 4 != 0 || reinterpret_cast<uintptr_t>(d.dst) % 4 != 0)
+            return fail(nullptr, "ee_cascade_gather: descriptor %d: src / dst is not 4-byte aligned", r);
+        a.src[r] = static_cast<const char*>(d.src); a.dst[r] = static_cast<char*>(d.dst); a.row_bytes[r] = (size_t)d.row_bytes;
+    }
+    if (!have_device("ee_cascade_gather")) return 1;
+    if (n_arrays > 0 && cap > 0) launch_cascade_gather(a, cap, reinterpret_cast<hipStream_t>(stream));
+    return launch_status(nullptr, "ee_cascade_gather");
+}
+
+int ee_cascade_merge(const float* logits, const int32_t* exit_layer, const float* confidence, const int32_t* slots, int32_t n, int32_t K,
+                     int32_t exit_offset, int32_t stage, float* out_logits, int32_t* out_exit, float* out_confidence, int32_t* out_stage,
+                     void* stream) {
+    if (n < 0 || K < 1 || exit_offset < 0 || stage < 0 ||
+        (n > 0 && (!logits || !exit_layer || !confidence || !slots || !out_logits || !out_exit || !out_confidence || !out_stage)))
+        return fail(nullptr, "ee_cascade_merge: bad argument (n >= 0, K >= 1, exit_offset, stage >= 0, no NULL pointer when n > 0)");
+    if (!have_device("ee_cascade_merge")) return 1;
+    CascadeMergeArgs a{};
+    a.logits = logits; a.exit_layer = exit_layer; a.conf = confidence; a.slots = slots; a.n = n; a.K = K; a.exit_offset = exit_offset;
+    a.stage = stage; a.out_logits = out_logits; a.out_exit = out_exit; a.out_conf = out_confidence; a.out_stage = out_stage;
+    if (n > 0) launch_cascade_merge(a, reinterpret_cast<hipStream_t>(stream));
+    return launch_status(nullptr, "ee_cascade_merge");
 }
 
 int ee_rule_sweep(const double* conf, const double* logits, const int64_t* references, int32_t E1, int32_t N, int32_t K, const double* thr, int32_t V,

@@ -10,38 +10,8 @@
 
 namespace mmee {
 
-// float64 max-softmax of one row, as the policy computes it (scipy.special.softmax on the float64 store, EE/policy.py:30-32)
-__device__ __forceinline__ double max_softmax_f64(const double* z, int K) {
-    double m = z[0];
-    for (int k = 1; k < K; ++k) m = fmax(m, z[k]);
-    double s = 0.0;
-    for (int k = 0; k < K; ++k) s += exp(z[k] - m);
-    return 1.0 / s;
-}
-
-// float64 entropy of one row, the reference's expression: log A - B / A with A = sum e^z, B = sum z e^z, no max shift (EE/thresh.py:41-45)
-__device__ __forceinline__ double entropy_f64(const double* z, int K) {
-    double A = 0.0, B = 0.0;
-    for (int k = 0; k < K; ++k) {
-        const double e = exp(z[k]);
-        A += e;
-        B += z[k] * e;
-    }
-    return log(A) - B / A;
-}
-
-// float64 margin of one row (MMEE_CRIT_MARGIN, include/mmee.h): (1 - exp(m2 - m1)) / S, m1 the maximum, m2 the second largest value counting
-// multiplicity (the pass that finds the maximum keeps both), S = sum_k exp(z_k - m1) in label order.  >= 0, exactly 0 on a tie, 1 when K = 1
-__device__ __forceinline__ double margin_f64(const double* z, int K) {
-    double m1 = z[0], m2 = -INFINITY;
-    for (int k = 1; k < K; ++k) {
-        m2 = z[k] > m1 ? m1 : fmax(m2, z[k]);
-        m1 = fmax(m1, z[k]);
-    }
-    double s = 0.0;
-    for (int k = 0; k < K; ++k) s += exp(z[k] - m1);
-    return (1.0 - exp(m2 - m1)) / s;
-}
+// the float64 max-softmax, entropy and margin of one row (max_softmax_f64, entropy_f64, margin_f64) and the row of a criterion table
+// (csf_row_f64) are in mmee_kernels.h: the cascade's deferral test (cascade.hip) calls the same functions
 
 // the criterion a scan event computes from the row itself
 template <int EVENT>
@@ -600,20 +570,8 @@ __global__ __launch_bounds__(256) void csf_table_kernel(const double* __restrict
                                                         unsigned char* __restrict__ correct) {
     const size_t total = (size_t)E1 * N;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const double* z = logits + i * K;
-        double m = z[0];
-        int am = 0;
-        for (int k = 1; k < K; ++k)
-            if (z[k] > m) { m = z[k]; am = k; }
-        if constexpr (CRIT == CRIT_MAX_CONFIDENCE) {
-            double s = 0.0;
-            for (int k = 0; k < K; ++k) s += exp(z[k] - m);
-            conf[i] = 1.0 / s;
-        } else if constexpr (CRIT == CRIT_ENTROPY) {
-            conf[i] = entropy_f64(z, K);
-        } else {
-            conf[i] = margin_f64(z, K);
-        }
+        int am;
+        conf[i] = csf_row_f64(CRIT, logits + i * K, K, am);
         if (correct) correct[i] = refs ? (unsigned char)(refs[i % N] == am) : 0;
     }
 }

@@ -145,6 +145,58 @@ __host__ __device__ inline double crit_sign(int criterion) { return criterion ==
 // copy the decide kernels (exit_stage.hip) and the table kernel of the dumped-array tools (exit_ops.hip) share, so their bits agree.
 __device__ inline double gate_score_f64(float h0, float h1) { return 1.0 / (1.0 + exp((double)h0 - (double)h1)); }
 
+// The three confidence scoring functions of a row in float64: the one copy the dumped-array tools (exit_ops.hip: the scans, csf_table_kernel)
+// and the cascade's deferral test (cascade.hip) share, so their bits agree.  T: double (a dumped array) or float (a delivered row, widened
+// value by value, which is exact).
+// float64 max-softmax of one row, as the policy computes it (scipy.special.softmax on the float64 store, EE/policy.py:30-32)
+template <typename T>
+__device__ __forceinline__ double max_softmax_f64(const T* z, int K) {
+    double m = (double)z[0];
+    for (int k = 1; k < K; ++k) m = fmax(m, (double)z[k]);
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) s += exp((double)z[k] - m);
+    return 1.0 / s;
+}
+// float64 entropy of one row, the reference's expression: log A - B / A with A = sum e^z, B = sum z e^z, no max shift (EE/thresh.py:41-45)
+template <typename T>
+__device__ __forceinline__ double entropy_f64(const T* z, int K) {
+    double A = 0.0, B = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const double x = (double)z[k], e = exp(x);
+        A += e;
+        B += x * e;
+    }
+    return log(A) - B / A;
+}
+// float64 margin of one row (MMEE_CRIT_MARGIN, include/mmee.h): (1 - exp(m2 - m1)) / S, m1 the maximum, m2 the second largest value counting
+// multiplicity (the pass that finds the maximum keeps both), S = sum_k exp(z_k - m1) in label order.  >= 0, exactly 0 on a tie, 1 when K = 1
+template <typename T>
+__device__ __forceinline__ double margin_f64(const T* z, int K) {
+    double m1 = (double)z[0], m2 = -INFINITY;
+    for (int k = 1; k < K; ++k) {
+        const double x = (double)z[k];
+        m2 = x > m1 ? m1 : fmax(m2, x);
+        m1 = fmax(m1, x);
+    }
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) s += exp((double)z[k] - m1);
+    return (1.0 - exp(m2 - m1)) / s;
+}
+// The row of a criterion table (ee_csf_table): the criterion, and am = the argmax, first maximum (as numpy).  The max-softmax here is
+// 1 / sum_k exp(z_k - m) in label order with m that first maximum.
+template <typename T>
+__device__ __forceinline__ double csf_row_f64(int criterion, const T* z, int K, int& am) {
+    double m = (double)z[0];
+    am = 0;
+    for (int k = 1; k < K; ++k)
+        if ((double)z[k] > m) { m = (double)z[k]; am = k; }
+    if (criterion == CRIT_ENTROPY) return entropy_f64(z, K);
+    if (criterion == CRIT_MARGIN) return margin_f64(z, K);
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) s += exp((double)z[k] - m);
+    return 1.0 / s;
+}
+
 // The exit ensemble (include/mmee.h, at ee_set_ensemble): its two functions, the one copy the forward's launch (exit_stage.hip) and the
 // dumped-array tool (exit_ops.hip) share, so their bits agree.  Each returns ONE label's value; a thread per (document, label) walks the row
 // for M and S itself, in label order, so no value depends on how the threads are grouped.
@@ -408,6 +460,41 @@ void launch_csf_table(const double* logits, const long long* refs, int E1, int N
                       hipStream_t s);
 // ee_gate_table: table (E+1,N); rows 0 .. E-1 = gate_score_f64 of head_logits (E,N,2), row E = the max-softmax of final_logits (N,K) (launch_csf_table's)
 void launch_gate_table(const float* head_logits, const double* final_logits, int E, int N, int K, double* table, hipStream_t s);
+
+// Model cascades (cascade.hip; the definition is in include/mmee.h): the three launches of a stage boundary
+struct CascadeSelectArgs {
+    const float* logits;             // (n,K) the rows the stage delivered, by the stage's document index
+    const int* exit_layer;           // (n) the stage's local exit index of every document
+    const int* orig;                 // (n) original slot of every document (ascending), or null: the identity (stage 0)
+    int n, K, final_exit, criterion; // criterion: CRIT_MAX_CONFIDENCE, CRIT_ENTROPY or CRIT_MARGIN
+    double thr;                      // the stage's final threshold entry
+    int* next_orig;                  // (n) original slots of the deferred documents, in their order; entries past the count are not written
+    int* count;                      // device word: the deferred documents
+    double* crit;                    // (n) or null: c of every document
+};
+void launch_cascade_select(const CascadeSelectArgs& a, hipStream_t s);
+constexpr int kCascadeMaxArrays = 8;
+struct CascadeGatherArgs {
+    const char* src[kCascadeMaxArrays];
+    char* dst[kCascadeMaxArrays];
+    size_t row_bytes[kCascadeMaxArrays];   // multiples of 4
+    int n_arrays;
+    const int* slots;                // (cap) source row of destination row j
+    const int* count;                // device word: the rows to copy, <= cap
+};
+void launch_cascade_gather(const CascadeGatherArgs& a, int cap, hipStream_t s);     // cap >= 1 sizes the grid
+struct CascadeMergeArgs {
+    const float* logits;             // (n,K) a later stage's results, by the stage's document index
+    const int* exit_layer;           // (n)
+    const float* conf;               // (n)
+    const int* slots;                // (n) original slot of every document
+    int n, K, exit_offset, stage;
+    float* out_logits;               // (B,K) the cascade's outputs, written at the documents' slots only
+    int* out_exit;                   // (B)   exit_layer + exit_offset
+    float* out_conf;                 // (B)
+    int* out_stage;                  // (B)   stage
+};
+void launch_cascade_merge(const CascadeMergeArgs& a, hipStream_t s);                // n >= 1
 void launch_temperature_fit(const double* logits, const long long* labels, int E1, int N, int K, int max_iter, double* T_out,
                             double* nll_out, double* acc_out, double* conf_out, int* iters_out, hipStream_t s);
 // ee_head_fit (head_fit.hip): softmax-regression heads per exit, float64 on float32 features; include/mmee.h states the objective
