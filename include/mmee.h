@@ -208,6 +208,40 @@ enum { MMEE_QUOTA_OFF = 0, MMEE_QUOTA_EXACT = 1, MMEE_QUOTA_AT_LEAST = 2 };
  * its batch size from the device), streaming across stages, captured cascades (a later stage's batch size depends on the data), stages on
  * different GPUs, a deferral that reads anything but the delivered row.
  */
+/*
+ * Audited exits (ee_set_audit; EarlyExitEngine.set_audit, audit.py): a deterministic, content-blind sample of the call's documents gets its
+ * result exactly where and as the plain forward gives it, and then runs on to the final exit as a shadow, so that its columns of the
+ * out_all_* / out_head_* arrays come back complete: an unbiased sampled dump-all table of the traffic that was served, from which the
+ * agreement of the early answer with the full model's can be counted -- the consistency that CATs (Schuster et al., EMNLP 2021) and "Fast
+ * yet Safe" (Jazbec et al., NeurIPS 2024) control.  THE definition (the decide kernels, ee_audit_selected, the stand-alone hook and the Python
+ * mask refer to it).
+ * Selection.  slot = the document's index in the caller's batch: its index in the call (doc_orig) plus the handle's slot_base.  In arithmetic
+ * mod 2^32:
+ *   x = (uint32)slot * 0x9E3779B1u ^ seed;
+ *   x ^= x >> 16;  x *= 0x85EBCA6Bu;  x ^= x >> 13;  x *= 0xC2B2AE35u;  x ^= x >> 16;        (murmur3's fmix32)
+ * The document is audited iff (uint64)x < cut, cut = floor(fraction 2^32 + 0.5) in [0, 2^32]: fraction 1 selects everybody, cut 0 is "audit
+ * off".  (seed 0, slot 0) hashes to 0 and is selected under every cut > 0: callers vary the seed per call.  One __host__ __device__ function
+ * (audit_selected, csrc/mmee_kernels.h) is the test of the kernels and of ee_audit_selected.
+ * Semantics.  The audit is on when cut > 0 and the call is not MMEE_FLAG_NO_EXIT.  At an exit below the final one, a document whose decision
+ * is `leave` -- under whatever criterion, rule, learning-to-exit score or ensemble the handle runs -- and which is selected gets out_logits /
+ * out_exit / out_conf written exactly as without the audit, is marked delivered, and is KEPT in the next stage.  A delivered document at a
+ * later exit always stays, never writes out_logits / out_exit / out_conf again (the final exit included), still writes its out_all_* /
+ * out_head_* rows and still updates its patience / streak / ensemble state like any active document.  Documents that are not selected behave
+ * exactly as without the audit.  Hence out_logits, out_exit and out_conf of an audited call are bit for bit those of the same call without
+ * the audit.
+ * Compute.  The documents active at exit e are #{exit_i >= e} + #{selected_i and exit_i < e}; ee_last_stage_counts and ee_last_flops report
+ * that number: it is what ran.  With share p a forward costs about p x (dump-all - early-exit) more.
+ * Cost in launches: none.  The AUDIT forms of the seven decide kernels (threshold, patience, LTE, streak, either, LTE + streak, LTE +
+ * either) run in place of the plain ones at every exit of an audited call; the delivered marks live by original slot in max_docs ints of the
+ * handle and are written, not read, at the call's first exit, so no launch zeroes them.  A handle without an audit issues the launches it
+ * always did and returns the same bits.
+ * Refused, each with a message: together with quotas, in either order (a rank would count the shadows, and n_{e+1} would no longer be
+ * n_e - q_e); MMEE_FLAG_STREAM_RESULTS (emit_leavers infers who left from stage membership); ee_graph_capture while an audit is set and
+ * ee_set_audit while graphs are held (the seed is per call and by value); cut > 2^32; slot_base < 0.  The Python CascadeEngine refuses a
+ * stage handle with an audit set.
+ * Not built: audit under quotas, with the result stream, in captured graphs, on cascade stages; a per-exit share; a selection that depends
+ * on content; a confidence bound on the agreement rate.
+ */
 /* model family: LayoutLMv3 (text + layout + image, the reference's EE model) or BEiT / DiT (image only; BASELINE configs[4],
  * the reference's "dit" branch EE/configs.py:429-449 — exit heads there are this build's extrapolation) */
 enum { MMEE_ARCH_LAYOUTLMV3 = 0, MMEE_ARCH_BEIT = 1 };
@@ -505,6 +539,18 @@ int ee_has_ensemble(const ee_handle* h);
  * ee_has_quotas: the mode (MMEE_QUOTA_EXACT / MMEE_QUOTA_AT_LEAST) when quotas are set, else 0. */
 int ee_set_quotas(ee_handle* h, const int32_t* quotas, int32_t n, int32_t mode);
 int ee_has_quotas(const ee_handle* h);
+
+/* The audit (audited exits, definition above, behind the cascades) of every LATER ee_forward: cut = floor(fraction 2^32 + 0.5) in [0, 2^32],
+ * 0 switches the audit off; seed: vary it per call; slot_base >= 0: the index of the call's document 0 in the caller's batch (0 unless the
+ * call is a slice of a larger batch).  Part of the handle's state until changed, passed by value to the decide launches.  The first call with
+ * cut > 0 allocates max_docs ints (the delivered marks).  MMEE_FLAG_NO_EXIT calls ignore the audit.
+ * Refused, with a message and nothing changed: cut > 2^32; slot_base < 0; cut > 0 while quotas are set (and ee_set_quotas while an audit is
+ * set); cut > 0 while the handle holds captured graphs.  ee_forward refuses MMEE_FLAG_STREAM_RESULTS, and ee_graph_capture refuses, while an
+ * audit is set.
+ * ee_has_audit: 1 while cut > 0.  ee_audit_selected: the selection test itself, 1 or 0; no handle, no device. */
+int ee_set_audit(ee_handle* h, uint64_t cut, uint32_t seed, int32_t slot_base);
+int ee_has_audit(const ee_handle* h);
+int ee_audit_selected(uint64_t cut, uint32_t seed, int32_t slot);
 
 /* Pin the exit-layer schedule.  DEFAULT (enabled == 0): every layer that ends in a decision is probed first.  Rounds 2-4 chose per layer
  * from the stage populations of "the handle's most recent FINISHED forward" -- a timing-dependent host decision, and under MMEE_FLAG_XPROBE
@@ -1531,6 +1577,21 @@ typedef struct ee_debug_exit_quota_args {
     int32_t* rank;
 } ee_debug_exit_quota_args;
 int ee_debug_exit_quota(const ee_debug_exit_quota_args* args, void* stream);
+/* ee_debug_exit_audit: one exit of one stage of an audited call (audited exits, definition behind the cascades): launch_decide with its
+ *   AuditArgs -- the AUDIT form of the (mode, rule) kernel -- then launch_compact_rows as ee_debug_exit_decide.  decide: everything exactly as
+ *   for ee_debug_exit_decide, is_final included; no_exit must be 0 (a dump-all call runs the plain kernels).  cut in [1, 2^32], seed and
+ *   slot_base >= 0 as for ee_set_audit.  delivered dev int32 [B] by original slot goes in and comes out: at exit_index 0 the entries of the
+ *   stage's documents are written without being read; at a later exit they are read, and written where a document is delivered here; entries
+ *   of slots outside the stage are never touched.
+ *   Refused: what ee_debug_exit_decide refuses, no_exit != 0, a cut outside [1, 2^32], a negative slot_base, a NULL delivered. */
+typedef struct ee_debug_exit_audit_args {
+    ee_debug_exit_decide_args decide;
+    uint64_t cut;
+    uint32_t seed;
+    int32_t slot_base;
+    int32_t* delivered;
+} ee_debug_exit_audit_args;
+int ee_debug_exit_audit(const ee_debug_exit_audit_args* args, void* stream);
 
 /* Unit-test hook of the patch projection (Conv2d with kernel = stride = patch as a GEMM over flattened patches), the counterpart of
  * ee_debug_attention: what patch_projection() of the forward launches, on caller-provided DEVICE buffers; no handle.

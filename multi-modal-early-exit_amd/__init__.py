@@ -29,3 +29,5 @@ from .heads import (GateFit, HeadFit, LteFit, MlpGateFit, MlpHeadFit, balanced_c
 from .heads import EnsembleFit, fit_exit_ensemble  # noqa: F401,E402
 from . import cascade  # noqa: F401,E402
 from .cascade import CascadeEngine, CascadeOutput  # noqa: F401,E402
+from . import audit  # noqa: F401,E402
+from .audit import AuditSample, ConsistencyReport  # noqa: F401,E402

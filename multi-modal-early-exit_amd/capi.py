@@ -6,6 +6,7 @@ The library is the product: if it cannot be loaded (not built, or no ROCm runtim
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional
 
@@ -116,6 +117,19 @@ class DebugExitQuotaArgs(C.Structure):
     _fields_ = [("decide", DebugExitDecideArgs), ("quota", _i32), ("quota_mode", _i32), ("crit", _vp), ("rank", _vp)]
 
 
+class DebugExitAuditArgs(C.Structure):
+    """ee_debug_exit_audit_args of include/mmee.h: the decide call's arguments, the audit's cut, seed and slot base, the device array of delivered marks."""
+    _fields_ = [("decide", DebugExitDecideArgs), ("cut", C.c_uint64), ("seed", _u32), ("slot_base", _i32), ("delivered", _vp)]
+
+
+def audit_cut(fraction: float) -> int:
+    """cut = floor(fraction 2^32 + 0.5) of include/mmee.h's audited exits; the fraction must lie in [0, 1]."""
+    f = float(fraction)
+    if not 0.0 <= f <= 1.0:
+        raise ValueError(f"audit fraction {fraction!r} outside [0, 1]")
+    return int(math.floor(f * 4294967296.0 + 0.5))
+
+
 class DebugExitEnsembleArgs(C.Structure):
     """ee_debug_exit_ensemble_args of include/mmee.h: device pointers (or None), this exit's temperature and sizes."""
     _fields_ = ([("pol_logits", _vp)] + [(n, _i32) for n in ("pol_rows", "K", "E1", "exit_index", "B")] + [("temp", C.c_double), ("by_pointer", _i32)]
@@ -187,6 +201,10 @@ SYMBOLS = {
     "ee_has_quotas": (C.c_int, [_vp]),
     "ee_quota_scan": (C.c_int, [_vp, C.c_double, _i32, _i32, C.POINTER(_i32), _i32, C.POINTER(C.c_double), _i32, _vp, _vp, _vp, _vp]),
     "ee_debug_exit_quota": (C.c_int, [C.POINTER(DebugExitQuotaArgs), _vp]),
+    "ee_set_audit": (C.c_int, [_vp, C.c_uint64, _u32, _i32]),
+    "ee_has_audit": (C.c_int, [_vp]),
+    "ee_audit_selected": (C.c_int, [C.c_uint64, _u32, _i32]),
+    "ee_debug_exit_audit": (C.c_int, [C.POINTER(DebugExitAuditArgs), _vp]),
     "ee_suggest_probe_mask": (C.c_int, [_vp, _u32, C.POINTER(C.c_uint64), _vp]),
     "ee_clock_stamp": (C.c_int, [_vp, _vp]),
     "ee_set_inputs_embeds": (C.c_int, [_vp, _vp]),

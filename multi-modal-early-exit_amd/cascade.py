@@ -182,6 +182,9 @@ class CascadeEngine:
     def _run_stage(self, s, arrays, n, out, thr, tmp, flags):
         """Stage s on n documents in consecutive chunks of at most its max_docs (documents are independent), results into row slices of `out`."""
         eng = self.stages[s]
+        if eng.has_audit():
+            raise ValueError(f"stage {s} has an audit set: audited exits on cascade stages are not built (a stage sees deferred documents under "
+                             "new slots, and a shadow's final row is not a deferral); set_audit(None) on the stage's engine")
         if n > eng.max_docs and eng.has_quotas:
             raise ValueError(f"stage {s} has quotas set and {n} documents for max_docs = {eng.max_docs}: the chunks would each rank alone "
                              "(set_quotas(None), or a handle that takes the stage whole)")

@@ -1,4 +1,4 @@
-// ee_debug_head_out, ee_debug_exit_ensemble, ee_debug_exit_decide, ee_debug_exit_quota, ee_debug_rows_out: the exit stage of exit_stage.hip alone, on caller-provided
+// ee_debug_head_out, ee_debug_exit_ensemble, ee_debug_exit_decide, ee_debug_exit_quota, ee_debug_exit_audit, ee_debug_rows_out: the exit stage of exit_stage.hip alone, on caller-provided
 // device buffers; no handle.  Each entry point makes the calls of the path's own launchers that capi_forward.hip makes (launch_head_out;
 // launch_exit_ensemble; launch_decide -- under a quota launch_exit_quota_crit, launch_exit_quota_rank and launch_decide_quota -- and, behind it,
 // launch_compact_rows as compact() does; launch_gather_cls / launch_rows_to_padded) and synchronises.  No kernel is defined or
@@ -80,9 +80,17 @@ int ee_debug_head_out(const ee_debug_head_out_args* a, void* stream) {
 namespace {
 
 // ee_debug_exit_decide (qa null) and ee_debug_exit_quota (qa: the quota, its mode and the two arrays the ranking launches fill): the same
-// checks of the stage, the same DecideArgs; the quota form runs the ranking launches and the QUOTA decide kernel in place of launch_decide
-int run_exit_decide(const char* who, const ee_debug_exit_decide_args* a, const ee_debug_exit_quota_args* qa, void* stream) {
+// checks of the stage, the same DecideArgs; the quota form runs the ranking launches and the QUOTA decide kernel in place of launch_decide.
+// ee_debug_exit_audit (aa: the cut, the seed, the slot base and the caller's delivered array): launch_decide with its AuditArgs
+int run_exit_decide(const char* who, const ee_debug_exit_decide_args* a, const ee_debug_exit_quota_args* qa, void* stream,
+                    const ee_debug_exit_audit_args* aa = nullptr) {
     if (!a) return fail(nullptr, "%s: args must not be NULL", who);
+    if (aa) {
+        if (a->no_exit) return fail(nullptr, "%s: no_exit must be 0: dump-all calls ignore the audit and run the plain decide kernels (ee_debug_exit_decide)", who);
+        if (aa->cut < 1 || aa->cut > (1ull << 32)) return fail(nullptr, "%s: cut %llu outside [1, 2^32]", who, (unsigned long long)aa->cut);
+        if (aa->slot_base < 0) return fail(nullptr, "%s: slot_base %d is negative", who, aa->slot_base);
+        if (!aa->delivered) return fail(nullptr, "%s: delivered must not be NULL", who);
+    }
     if (qa) {
         if (a->mode != DECIDE_THRESHOLD || a->rule != RULE_PLAIN)
             return fail(nullptr, "%s: a rank is defined for the threshold criteria under the plain rule: mode must be 0 and rule MMEE_RULE_PLAIN, got mode %d, rule %d",
@@ -170,7 +178,9 @@ int run_exit_decide(const char* who, const ee_debug_exit_decide_args* a, const e
         launch_exit_quota_rank(d, q, a->B, s);
         launch_decide_quota(d, q, qa->quota_mode, s);
     } else {
-        launch_decide(d, stateful ? &pa : nullptr, a->mode, a->rule, s);
+        AuditArgs au{};
+        if (aa) { au.delivered = aa->delivered; au.cut = aa->cut; au.seed = aa->seed; au.slot_base = aa->slot_base; }
+        launch_decide(d, stateful ? &pa : nullptr, a->mode, a->rule, s, aa ? &au : nullptr);
     }
     if (compact) {
         const int cus = device_cus(who);
@@ -190,6 +200,11 @@ int ee_debug_exit_decide(const ee_debug_exit_decide_args* a, void* stream) { ret
 int ee_debug_exit_quota(const ee_debug_exit_quota_args* a, void* stream) {
     if (!a) return fail(nullptr, "ee_debug_exit_quota: args must not be NULL");
     return run_exit_decide("ee_debug_exit_quota", &a->decide, a, stream);
+}
+
+int ee_debug_exit_audit(const ee_debug_exit_audit_args* a, void* stream) {
+    if (!a) return fail(nullptr, "ee_debug_exit_audit: args must not be NULL");
+    return run_exit_decide("ee_debug_exit_audit", &a->decide, nullptr, stream, a);
 }
 
 int ee_debug_exit_ensemble(const ee_debug_exit_ensemble_args* a, void* stream) {

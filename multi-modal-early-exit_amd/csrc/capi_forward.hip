@@ -204,6 +204,8 @@ struct Forward {
     size_t ll_stride = 0;                    // floats between two parts: (rows padded to whole 128-row tiles) x H
     // MMEE_FLAG_STREAM_RESULTS: behind every exit's decide launch, the leavers' rows into the handle's pinned segment buffer and an event (result_stream.hip)
     const bool stream_results = a.flags & MMEE_FLAG_STREAM_RESULTS;
+    // audited exits (ee_set_audit): every decide launch of the call is the AUDIT form; a dump-all call ignores the audit, everybody stays anyway
+    const bool audit = h->audit_cut != 0 && !no_exit;
     // split precision attention: attention_idx.hip (pair index built once per forward; default) or, with MMEE_ATTN_V=2 or bucket tables
     // beyond 64 bins, attention_pair.hip (clamped Delta tables gathered per layer and head)
     const bool use_idx = sp && attn_variant() == 0 && c.rel_pos_bins <= 64 && c.rel_2d_pos_bins <= 64;
@@ -271,6 +273,9 @@ struct Forward {
         if (stream_results && cap)
             return fail(h, "ee_graph_capture: MMEE_FLAG_STREAM_RESULTS belongs to eager calls (the events between the launches are not part of a captured "
                            "launch list)");
+        if (audit && stream_results)
+            return fail(h, "ee_forward: MMEE_FLAG_STREAM_RESULTS while an audit is set: emit_leavers infers who left from stage membership, and an audited "
+                           "document stays in the stage after its result is out (not built; ee_set_audit(h, 0, 0, 0) first)");
         if (stream_results && (!a.out_logits || !a.out_conf))
             return fail(h, "ee_forward: MMEE_FLAG_STREAM_RESULTS needs out_logits and out_conf (a streamed row carries both)");
         if (cap && (hs_out || embeds_in || head_mask || attn_out || h->prof_on))
@@ -694,7 +699,8 @@ struct Forward {
             { ProfScope ps(h, P_DECIDE, s); launch_decide_quota(d, qa, h->quota_mode, s); }
         } else {
             ProfScope ps(h, P_DECIDE, s);
-            launch_decide(d, stateful ? &pa : nullptr, patience ? DECIDE_PATIENCE : c.use_lte ? DECIDE_LTE : DECIDE_THRESHOLD, h->rule, s);
+            const AuditArgs au{h->audit_delivered, h->audit_cut, h->audit_seed, h->audit_slot_base};
+            launch_decide(d, stateful ? &pa : nullptr, patience ? DECIDE_PATIENCE : c.use_lte ? DECIDE_LTE : DECIDE_THRESHOLD, h->rule, s, audit ? &au : nullptr);
         }
         h->rec.exit_stage[exit_index] = cur;
         if (stream_results) emit_leavers(is_final);
@@ -905,6 +911,9 @@ int ee_graph_capture(ee_handle* h, const int64_t* input_ids, const int64_t* atte
     if (flags & MMEE_FLAG_STREAM_RESULTS)          // before the eager warm-up call, which would otherwise run (and stream) first
         return fail(h, "ee_graph_capture: MMEE_FLAG_STREAM_RESULTS belongs to eager calls (the events between the launches are not part of a captured "
                        "launch list)");
+    if (h->audit_cut)                              // likewise before the warm-up call: the handle's state decides, whatever the flags
+        return fail(h, "ee_graph_capture: an audit is set: its seed changes per call and is passed by value, so audited calls are eager "
+                       "(not built; ee_set_audit(h, 0, 0, 0) first)");
     const int E1 = h->cfg.n_embedding_exits + h->cfg.n_encoder_exits + 1;
     const ForwardArgs a{input_ids, attention_mask, bbox, pixel_values, token_type_ids, position_ids, B, T, thresholds, temperatures, flags,
                         out_logits, out_exit, out_conf, out_all_logits, out_all_crit, out_head_logits, out_head_crit, out_hidden_cls, stream};

@@ -141,6 +141,11 @@ struct ee_handle {
     std::vector<int32_t> quotas;                  // [E]: q_e of every exit below the final one (empty while quotas are off)
     double* quota_crit = nullptr;                 // [max_docs]: c_i of the exit being decided, by the stage's document index
     int* quota_rank = nullptr;                    // [max_docs]: rank_i
+    // audited exits (ee_set_audit; include/mmee.h): cut > 0 picks the AUDIT form of the decide kernels in calls that are not dump-all
+    uint64_t audit_cut = 0;
+    uint32_t audit_seed = 0;
+    int32_t audit_slot_base = 0;
+    int* audit_delivered = nullptr;               // [max_docs] by original slot, allocated at the first ee_set_audit
     // optional per-kernel event timing (ee_profile)
     bool prof_on = false;
     struct ProfRec { int id; hipEvent_t a, b; double flops; };

@@ -23,7 +23,7 @@ const char* const kProfNames[] = {
     "gemm_ffn_up|gemm_f32_kernel<1,0>",
     "gemm_ffn_down|gemm_f32_kernel<2,0>",
     "exit_head|gemm_f32_kernel<3,0>+head_out_kernel (use_lte: head_out_lte_kernel)",
-    "exit_decide|exit_decide_kernel (patience: exit_decide_patience_kernel, use_lte: exit_decide_lte_kernel; exit rules: exit_decide_[lte_]{streak,either}_kernel)",
+    "exit_decide|exit_decide[_patience|_lte][_streak|_either][_audit]_kernel (by criterion / use_lte, exit rule, audited call)",
     "compact|compact_rows_kernel",
     "gather_cls|gather_cls_kernel",
     "cls_probe|attention_idx_kernel+gemm_split_kernel<.., 1>+ln_rows_kernel+gather_cls_kernel (CLS rows of an exit layer, before its decision)",
@@ -186,6 +186,9 @@ int ee_set_quotas(ee_handle* h, const int32_t* quotas, int32_t n, int32_t mode) 
                            "is defined for them (not built; ee_set_exit_rule(h, MMEE_RULE_PLAIN) first)", h->rule);
         if (c.use_lte)
             return fail(h, "ee_set_quotas: a use_lte handle: the learning-to-exit decision reads another score, no rank is defined for it (not built)");
+        if (h->audit_cut)
+            return fail(h, "ee_set_quotas: an audit is set: a rank would count the audited documents that stay as shadows, and n_{e+1} would no longer "
+                           "be n_e - q_e (not built; ee_set_audit(h, 0, 0, 0) first)");
     }
     if (want != h->quota_mode)
         for (const auto& g : h->graphs)
@@ -210,6 +213,31 @@ int ee_set_quotas(ee_handle* h, const int32_t* quotas, int32_t n, int32_t mode) 
 }
 
 int ee_has_quotas(const ee_handle* h) { return h ? h->quota_mode : 0; }
+
+int ee_set_audit(ee_handle* h, uint64_t cut, uint32_t seed, int32_t slot_base) {
+    if (!h) return 1;
+    if (cut > (1ull << 32)) return fail(h, "ee_set_audit: cut %llu is above 2^32 (cut = floor(fraction 2^32 + 0.5), fraction in [0, 1])", (unsigned long long)cut);
+    if (slot_base < 0) return fail(h, "ee_set_audit: slot_base %d is negative (it is the index of the call's first document in the caller's batch)", slot_base);
+    if (cut && h->quota_mode != MMEE_QUOTA_OFF)
+        return fail(h, "ee_set_audit: quotas are set: a rank would count the audited documents that stay as shadows, and n_{e+1} would no longer be "
+                       "n_e - q_e (not built; ee_set_quotas(h, NULL, 0, 0) first)");
+    if (cut)                                       // (a capture is refused while an audit is set, so held graphs mean the audit is off)
+        for (const auto& g : h->graphs)
+            if (g.exec)
+                return fail(h, "ee_set_audit: the handle holds captured graphs: a graph's launch list is the one of its capture, and audited calls "
+                               "are eager (ee_graph_destroy them first)");
+    if (cut && !h->audit_delivered) {
+        int* d = nullptr;
+        if (dev_alloc(h, &d, (size_t)h->cfg.max_docs)) return 1;
+        h->audit_delivered = d;
+    }
+    h->audit_cut = cut; h->audit_seed = seed; h->audit_slot_base = slot_base;      // passed by value to the decide launches of every later ee_forward
+    return 0;
+}
+
+int ee_has_audit(const ee_handle* h) { return h && h->audit_cut ? 1 : 0; }
+
+int ee_audit_selected(uint64_t cut, uint32_t seed, int32_t slot) { return audit_selected(cut, seed, slot) ? 1 : 0; }
 
 int ee_set_ensemble(ee_handle* h, const double* w, const double* b) {
     if (!h) return 1;

@@ -168,6 +168,11 @@ __device__ inline double crit_f64(const float* z, int K, double temp, int criter
 // kernel's own branches below would compute, the gate score under CRIT_GATE -- and the test is on q.rank, the document's place among the stage's
 // documents: QUOTA_EXACT rank < q_e, QUOTA_AT_LEAST the threshold test or rank < q_e.  Everything below the `leave` line is shared.  QUOTA_OFF
 // compiles to the kernels as they were.
+// AUDIT (ee_set_audit; definition in include/mmee.h): a document whose decision is `leave` and that audit_selected picks gets its result as
+// always, is marked au.delivered[orig] = 1 and is KEPT; a delivered document decides nothing any more -- it stays until the final exit, writes
+// no out_logits / out_exit / out_conf there or anywhere, and still writes its out_all_* / out_head_* rows and its patience / streak state like
+// any active document, because everything above the `leave` line runs for it unchanged.  au.delivered is by original slot and is written, not
+// read, at exit 0, which every document reaches (no reset launch).  AUDIT = false compiles to the kernels as they were.
 // ---------------------------------------------------------------------------------------------------------------
 // PABEE's counter: argmax of the scaled logits as they are written out (two f32 logits can round to one scaled value; first maximum wins),
 // c_e = the argmax equals the one at the previous exit ? c_{e-1} + 1 : 0, state by original slot
@@ -184,9 +189,10 @@ __device__ __forceinline__ int agreement_run(const float* z, int K, double temp,
     return run;
 }
 
-template <int MODE, int RULE = RULE_PLAIN, int QUOTA = QUOTA_OFF>
-__device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const PatienceArgs& p, const QuotaArgs& q = QuotaArgs{}) {
+template <int MODE, int RULE = RULE_PLAIN, int QUOTA = QUOTA_OFF, bool AUDIT = false>
+__device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const PatienceArgs& p, const QuotaArgs& q = QuotaArgs{}, const AuditArgs& au = AuditArgs{}) {
     constexpr bool PATIENCE = MODE == DECIDE_PATIENCE;
+    static_assert(!AUDIT || QUOTA == QUOTA_OFF, "a rank would count the shadows: n_{e+1} would no longer be n_e - q_e");
     static_assert(RULE == RULE_PLAIN || !PATIENCE, "PABEE has no threshold event to build a rule on");
     static_assert(QUOTA == QUOTA_OFF || (MODE == DECIDE_THRESHOLD && RULE == RULE_PLAIN), "a rank is defined for the threshold criteria under the plain rule");
     __shared__ int s_cnt[16], s_rows[16];
@@ -259,6 +265,13 @@ __device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const Pati
                 else hc = crit_row_f32(hz, a.Kh, PATIENCE ? CRIT_MAX_CONFIDENCE : a.criterion);
                 a.out_head_crit[(size_t)a.exit_index * a.B + orig] = hc;
             }
+            bool shadow = false;                                          // AUDIT: the document's result is out and it stays in the batch
+            if constexpr (AUDIT) {
+                const bool was = a.exit_index > 0 && au.delivered[orig] != 0;
+                shadow = was || (leave && !a.is_final && audit_selected(au.cut, au.seed, (int)((unsigned)orig + (unsigned)au.slot_base)));
+                if (a.exit_index == 0 || shadow != was) au.delivered[orig] = shadow ? 1 : 0;
+                leave = leave && !was;                                    // a delivered document writes no result again, the final exit included
+            }
             if (leave) {
                 if (a.out_logits)
                     for (int k = 0; k < a.K; ++k) a.out_logits[(size_t)orig * a.K + k] = (float)((double)z[k] / temp);
@@ -266,6 +279,7 @@ __device__ __forceinline__ void exit_decide_body(const DecideArgs& a, const Pati
                 if (a.out_conf) a.out_conf[orig] = (float)crit;
             }
             keep = !leave;
+            if constexpr (AUDIT) keep = !a.is_final && (keep || shadow);
         }
         // ---- wavefront ballot + prefix sums ------------------------------------------------------------------
         const unsigned long long ballot = __ballot(keep);
@@ -317,10 +331,33 @@ __global__ __launch_bounds__(1024) void exit_decide_lte_either_kernel(DecideArgs
 __global__ __launch_bounds__(1024) void exit_decide_quota_exact_kernel(DecideArgs a, QuotaArgs q) { exit_decide_body<DECIDE_THRESHOLD, RULE_PLAIN, QUOTA_EXACT>(a, PatienceArgs{}, q); }
 __global__ __launch_bounds__(1024) void exit_decide_quota_at_least_kernel(DecideArgs a, QuotaArgs q) { exit_decide_body<DECIDE_THRESHOLD, RULE_PLAIN, QUOTA_AT_LEAST>(a, PatienceArgs{}, q); }
 
-// mode: DECIDE_*, rule: RULE_PLAIN / _STREAK / _EITHER.  The plain threshold and LTE kernels keep no state and take no PatienceArgs (p may be null)
-void launch_decide(const DecideArgs& a, const PatienceArgs* p, int mode, int rule, hipStream_t s) {
+// the AUDIT forms of the seven kernels above: one signature, the stateless ones ignore their PatienceArgs
+#define MMEE_DECIDE_AUDIT_KERNEL(name, ...)                                                                  \
+    __global__ __launch_bounds__(1024) void name(DecideArgs a, PatienceArgs p, AuditArgs au) {              \
+        exit_decide_body<__VA_ARGS__, QUOTA_OFF, true>(a, p, QuotaArgs{}, au);                               \
+    }
+MMEE_DECIDE_AUDIT_KERNEL(exit_decide_audit_kernel, DECIDE_THRESHOLD, RULE_PLAIN)
+MMEE_DECIDE_AUDIT_KERNEL(exit_decide_patience_audit_kernel, DECIDE_PATIENCE, RULE_PLAIN)
+MMEE_DECIDE_AUDIT_KERNEL(exit_decide_lte_audit_kernel, DECIDE_LTE, RULE_PLAIN)
+MMEE_DECIDE_AUDIT_KERNEL(exit_decide_streak_audit_kernel, DECIDE_THRESHOLD, RULE_STREAK)
+MMEE_DECIDE_AUDIT_KERNEL(exit_decide_either_audit_kernel, DECIDE_THRESHOLD, RULE_EITHER)
+MMEE_DECIDE_AUDIT_KERNEL(exit_decide_lte_streak_audit_kernel, DECIDE_LTE, RULE_STREAK)
+MMEE_DECIDE_AUDIT_KERNEL(exit_decide_lte_either_audit_kernel, DECIDE_LTE, RULE_EITHER)
+#undef MMEE_DECIDE_AUDIT_KERNEL
+
+// mode: DECIDE_*, rule: RULE_PLAIN / _STREAK / _EITHER.  The plain threshold and LTE kernels keep no state and take no PatienceArgs (p may be null).
+// audit: null launches the kernels as they always were; an audited call (never a dump-all one: the callers see to it) passes its AuditArgs
+void launch_decide(const DecideArgs& a, const PatienceArgs* p, int mode, int rule, hipStream_t s, const AuditArgs* audit) {
     using Plain = void (*)(DecideArgs);
     using Stateful = void (*)(DecideArgs, PatienceArgs);
+    if (audit) {
+        using Audited = void (*)(DecideArgs, PatienceArgs, AuditArgs);
+        static const Audited audited[3][3] = {{exit_decide_audit_kernel, exit_decide_streak_audit_kernel, exit_decide_either_audit_kernel},
+                                              {exit_decide_patience_audit_kernel, nullptr, nullptr},
+                                              {exit_decide_lte_audit_kernel, exit_decide_lte_streak_audit_kernel, exit_decide_lte_either_audit_kernel}};
+        hipLaunchKernelGGL(audited[mode][rule], dim3(1), dim3(1024), 0, s, a, p ? *p : PatienceArgs{}, *audit);
+        return;
+    }
     static const Plain plain[3] = {exit_decide_kernel, nullptr, exit_decide_lte_kernel};
     static const Stateful stateful[3][3] = {{nullptr, exit_decide_streak_kernel, exit_decide_either_kernel},
                                             {exit_decide_patience_kernel, nullptr, nullptr},

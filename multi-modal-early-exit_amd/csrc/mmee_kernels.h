@@ -263,6 +263,29 @@ __host__ __device__ inline unsigned long long quota_key(double c, double sign) {
 void launch_exit_quota_crit(const DecideArgs& a, const QuotaArgs& q, int max_docs, hipStream_t s);      // the two ranking launches: c_i,
 void launch_exit_quota_rank(const DecideArgs& a, const QuotaArgs& q, int max_docs, hipStream_t s);      // then rank_i (max_docs >= n_docs sizes the grids)
 void launch_decide_quota(const DecideArgs& a, const QuotaArgs& q, int quota_mode, hipStream_t s);        // QUOTA_EXACT / QUOTA_AT_LEAST; threshold criteria, plain rule
+
+// Audited exits (ee_set_audit; the definition is in include/mmee.h): a hashed, content-blind sample of the call's documents is delivered where
+// it leaves and stays in the batch as a shadow until the final exit.  The selection test, the one copy the AUDIT decide kernels, ee_audit_selected
+// and (through it) the Python mask share: x = (uint32)slot * 0x9E3779B1 ^ seed through murmur3's fmix32, selected iff x < cut, cut in [0, 2^32].
+// (seed 0, slot 0) hashes to 0 and is selected under every cut > 0.
+__host__ __device__ inline bool audit_selected(unsigned long long cut, unsigned seed, int slot) {
+    unsigned x = (unsigned)slot * 0x9E3779B1u ^ seed;
+    x ^= x >> 16;
+    x *= 0x85EBCA6Bu;
+    x ^= x >> 13;
+    x *= 0xC2B2AE35u;
+    x ^= x >> 16;
+    return (unsigned long long)x < cut;
+}
+// the AUDIT decide kernels' third argument
+struct AuditArgs {
+    int* delivered;                  // [max_docs] by original slot: 1 once the document's result is written; written (not read) at exit_index 0
+    unsigned long long cut;          // floor(fraction 2^32 + 0.5) in (0, 2^32]
+    unsigned seed;
+    int slot_base;                   // the call's slot 0 in the caller's batch (MicroBatchedEngine: the slice's first document)
+};
+// launch_decide (below) takes it as its last argument: non-null picks the AUDIT form of its seven kernels, at every exit of an audited call, the
+// final one included (delivered documents write no result there); null launches the kernels as they were
 // ee_quota_scan (exit_ops.hip): the same decision on a criterion table (E1,N), consecutive groups of G documents ranked independently
 struct QuotaScanArgs {
     const double* table;             // (E1,N) on the device
@@ -344,7 +367,8 @@ void launch_embed_beit(const float* patch, const float* cls, const float* pos, i
 void launch_patch_mean(const float* X, int H, const int* x_phys, const int* doc_off, const int* n_docs_ptr, float* pooled,
                        int max_docs, hipStream_t s);
 void launch_head_out(const HeadOutArgs& a, int max_docs, hipStream_t s);
-void launch_decide(const DecideArgs& a, const PatienceArgs* p, int mode, int rule, hipStream_t s);   // p: null where (mode, rule) keeps no state
+void launch_decide(const DecideArgs& a, const PatienceArgs* p, int mode, int rule, hipStream_t s,    // p: null where (mode, rule) keeps no state
+                   const AuditArgs* audit = nullptr);                                                 // audit: null, or an audited call (not a dump-all one)
 void launch_emit_leavers(const EmitArgs& a, hipStream_t s);      // result_stream.hip
 void launch_pack_results(const float* logits, const int* exit_layer, const float* conf, int n, int K, int* rows, hipStream_t s);
 void launch_unpack_results(const int* rows, int n, int K, float* logits, int* exit_layer, float* conf, hipStream_t s);

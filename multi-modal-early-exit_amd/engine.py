@@ -36,6 +36,7 @@ class EngineOutput:
     hidden_cls: Optional["torch.Tensor"] = None   # (L+1,B,H)
     hidden_states: Optional["torch.Tensor"] = None   # (L+1,B,T+Pv,H): the state entering every layer and the last layer's output
     attentions: Optional["torch.Tensor"] = None      # (L,B,heads,T+Pv,T+Pv): attention probabilities of every layer (after the head mask)
+    audit_mask: Optional["torch.Tensor"] = None      # (B,) bool: the documents an audited call ran on to the final exit (set_audit); None without an audit
 
 
 @dataclass
@@ -159,6 +160,7 @@ class EarlyExitEngine:
         self._stream_generation = 0         # forward_stream() calls so far: a ResultStream belongs to one of them
         self.ensemble = None                # set_ensemble(): the host copies of (weights, bias), or None
         self.quotas, self.quota_mode = None, None      # set_quotas(): the per-exit quotas and "exact" / "at_least", or None
+        self.audit = None                   # set_audit(): (fraction, seed, slot_base), or None
         self.patience = None
         if ec.patience is not None:
             self.set_patience(ec.patience)
@@ -253,7 +255,8 @@ class EarlyExitEngine:
                 one_term: bool = False, inputs_embeds=None, want_hidden_states: bool = False, out=None, head_mask=None,
                 want_attentions: bool = False, patience: Optional[Union[int, Sequence[int]]] = None, exit_rule=None,
                 low_latency: bool = False, quotas: Optional[Sequence[int]] = None, quota_mode: Optional[str] = None,
-                quota_fractions: Optional[Sequence[float]] = None, _capture: bool = False, _stream: bool = False) -> EngineOutput:
+                quota_fractions: Optional[Sequence[float]] = None, audit_fraction: Optional[float] = None,
+                audit_seed: Optional[int] = None, _capture: bool = False, _stream: bool = False) -> EngineOutput:
         """``out``: optional preallocated ``(logits (B,K) f32, exit_layer (B,) i32, confidence (B,) f32)`` device tensors (contiguous; row
         slices of larger tensors qualify) the kernels write into instead of fresh allocations -- MicroBatchedEngine hands each half its slice.
         ``patience``: when given, ``set_patience(patience)`` before the call (an int, or one entry per exit; it matters under the "patience"
@@ -265,7 +268,11 @@ class EarlyExitEngine:
         ``quotas`` / ``quota_fractions`` / ``quota_mode``: when given, ``set_quotas(...)`` before the call (budgeted exits: every exit releases
         the most confident documents of THIS call, a chosen number of them; ``set_quotas``).  ``quota_fractions`` is the convenience: the share
         of the call's B documents per exit, turned into integers by ``sweep.quotas_from_fractions``.  They stay set for later calls, like the
-        patience; ``set_quotas(None)`` switches them off.  Under ``quota_mode="exact"`` the thresholds are not read."""
+        patience; ``set_quotas(None)`` switches them off.  Under ``quota_mode="exact"`` the thresholds are not read.
+        ``audit_fraction`` / ``audit_seed``: when given, ``set_audit(audit_fraction, seed=audit_seed)`` before the call (audited exits: a hashed
+        sample of the call's documents is delivered where it leaves and runs on to the final exit; with ``want_all=True`` its columns come
+        back complete, ``output.audit_mask`` says which).  ``audit_seed`` alone re-seeds the audit that is set (vary it per call).  Both stay
+        set for later calls; ``set_audit(None)`` switches the audit off."""
         if not self._finalized:
             raise capi.MMEEError("load_weights() has not been called")
         if patience is not None:
@@ -322,6 +329,8 @@ class EarlyExitEngine:
             self.set_quotas(quotas, mode=quota_mode or self.quota_mode or "exact")
         elif quota_mode is not None:
             raise ValueError("quota_mode= goes with quotas= or quota_fractions= (set_quotas(None) switches quotas off)")
+        if audit_fraction is not None or audit_seed is not None:
+            self.forward_audit_args(audit_fraction, audit_seed)
         if thresholds is None:
             thresholds = self.exit_config.global_threshold
         thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float64).reshape(-1), (E + 1,)).copy() \
@@ -428,7 +437,10 @@ class EarlyExitEngine:
         self._keepalive = (ids, am, bb, px, tt, ps, emb, hm)   # borrowed by the enqueued kernels until the stream drains
         if validate:
             self.stage_counts()                        # synchronises; raises on out-of-range inputs
-        return EngineOutput(out_logits, out_exit, out_conf, all_logits, all_crit, head_logits, head_crit, hidden, hs, att)
+        mask = None
+        if self.audit and not dump_all:                # the library's own rule: a dump-all call ignores the audit
+            mask = torch.from_numpy(self.audit_mask(B, *self.audit)).to(dev, non_blocking=True)
+        return EngineOutput(out_logits, out_exit, out_conf, all_logits, all_crit, head_logits, head_crit, hidden, hs, att, mask)
 
     __call__ = forward
 
@@ -672,6 +684,60 @@ class EarlyExitEngine:
     @property
     def has_quotas(self) -> bool:
         return bool(self.lib.ee_has_quotas(self._h))
+
+    def set_audit(self, fraction: Optional[float] = None, seed: int = 0, slot_base: int = 0):
+        """Audited exits of every later forward (ee_set_audit; the definition is in include/mmee.h): a deterministic, content-blind sample of each
+        call's documents -- chosen by hashing ``(seed, slot_base + index in the call)``, the share ``fraction`` of them on average -- gets its
+        result exactly where and as the plain forward gives it and then runs on to the final exit as a shadow.  ``logits`` / ``exit_layer`` /
+        ``confidence`` are bit for bit those of the call without the audit; with ``want_all=True`` (``want_head=True``) the sampled columns
+        of ``all_logits`` / ``all_crit`` (``head_*``) come back complete, and ``output.audit_mask`` says which they are (``audit.sample``,
+        ``audit.consistency``).  ``stage_counts()`` and ``flops()`` report what ran, shadows included.  Vary ``seed`` per call: slot 0 is
+        always selected under seed 0.  ``None`` or 0 switches the audit off: the engine then issues the launches and returns the bits it did
+        before.  No launch is added.  Refused together with quotas, with ``forward_stream``, with ``capture`` and while the engine holds
+        captured graphs; dump-all calls ignore it.  Returns ``(fraction, seed, slot_base)`` or None."""
+        if fraction is None or float(fraction) == 0.0:
+            capi.check(self.lib.ee_set_audit(self._h, 0, 0, 0), self._h, "ee_set_audit")
+            self.audit = None
+            return None
+        cut = capi.audit_cut(fraction)
+        seed, slot_base = int(seed), int(slot_base)
+        if not 0 <= seed < 2 ** 32:
+            raise ValueError(f"set_audit: seed {seed} is not a 32-bit unsigned value")
+        if not 0 <= slot_base < 2 ** 31:
+            raise ValueError(f"set_audit: slot_base {slot_base} outside [0, 2^31)")
+        capi.check(self.lib.ee_set_audit(self._h, cut, seed, slot_base), self._h, "ee_set_audit")
+        self.audit = (float(fraction), seed, slot_base) if cut else None
+        return self.audit
+
+    def has_audit(self) -> bool:
+        return bool(self.lib.ee_has_audit(self._h))
+
+    def forward_audit_args(self, audit_fraction=None, audit_seed=None):
+        """``forward(audit_fraction=, audit_seed=)`` as a ``set_audit`` call: the seed and the slot base that are set are kept where the call
+        names none; ``audit_seed`` alone re-seeds the audit that is set."""
+        cur = self.audit
+        if audit_fraction is not None:
+            return self.set_audit(audit_fraction, seed=cur[1] if audit_seed is None and cur else int(audit_seed or 0), slot_base=cur[2] if cur else 0)
+        if audit_seed is not None:
+            if not cur:
+                raise ValueError("audit_seed= goes with audit_fraction= or an audit that is set (set_audit)")
+            return self.set_audit(cur[0], seed=audit_seed, slot_base=cur[2])
+        return cur
+
+    @staticmethod
+    def audit_mask(B: int, fraction: float, seed: int = 0, slot_base: int = 0) -> np.ndarray:
+        """(B,) bool: which documents of a call of B an audit of (fraction, seed, slot_base) selects -- include/mmee.h's hash in numpy, the
+        bits of ``ee_audit_selected``.  Needs no GPU and no library."""
+        cut = capi.audit_cut(fraction)
+        x = (np.arange(int(B), dtype=np.uint64) + np.uint64(int(slot_base))) & np.uint64(0xFFFFFFFF)
+        m = np.uint64(0xFFFFFFFF)
+        x = ((x * np.uint64(0x9E3779B1)) & m) ^ np.uint64(int(seed) & 0xFFFFFFFF)
+        x ^= x >> np.uint64(16)
+        x = (x * np.uint64(0x85EBCA6B)) & m
+        x ^= x >> np.uint64(13)
+        x = (x * np.uint64(0xC2B2AE35)) & m
+        x ^= x >> np.uint64(16)
+        return x < np.uint64(cut)
 
     def clock_stamp(self):
         """Device tensor of capi.CLOCK_STAMP_WORDS int64: one (s_memtime, s_memrealtime) pair per CU as seen by one-wave workgroups enqueued on

@@ -46,6 +46,7 @@ class MicroBatchedEngine:
             self.streams = [torch.cuda.Stream(device=self.device) for _ in range(self.n)]
         self._sizes: List[int] = []
         self._ran = [False] * self.n          # handles that have run a forward (check() visits every one of them, not only the last call's)
+        self.audit = None                     # set_audit(): (fraction, seed, slot_base), or None; every call hands each handle its slice's slot base
 
     # ---- lifetime / parameters -------------------------------------------------------------------------------------------
     def close(self):
@@ -77,6 +78,25 @@ class MicroBatchedEngine:
             return None
         raise ValueError(self._NO_QUOTAS)
 
+    def set_audit(self, fraction=None, seed: int = 0, slot_base: int = 0):
+        """Audited exits (``EarlyExitEngine.set_audit``; include/mmee.h): the selection hashes a document's index in the caller's batch, so every
+        call hands the handle of slice ``[lo, hi)`` the slot base ``slot_base + lo``: the mask and the results are the single-handle ones."""
+        if fraction is None or float(fraction) == 0.0:
+            for e in self.engines:
+                e.set_audit(None)
+            self.audit = None
+            return None
+        for e in self.engines:                # refusals (a fraction outside [0, 1], captured graphs) surface here, not in the middle of a call
+            e.set_audit(fraction, seed=seed, slot_base=slot_base)
+        self.audit = (float(fraction), int(seed), int(slot_base))
+        return self.audit
+
+    def has_audit(self) -> bool:
+        return self.engines[0].has_audit()
+
+    audit_mask = staticmethod(EarlyExitEngine.audit_mask)
+    forward_audit_args = EarlyExitEngine.forward_audit_args
+
     def forward_stream(self, *args, **kw):
         """Not built (module docstring): interleaving the result streams of several handles is a host policy of its own."""
         raise NotImplementedError("MicroBatchedEngine has no result stream: use EarlyExitEngine.forward_stream (one handle, one stream)")
@@ -90,6 +110,9 @@ class MicroBatchedEngine:
             raise ValueError("low_latency is a small-batch mode of EarlyExitEngine; MicroBatchedEngine runs large batches")
         if any(kw.get(k) is not None for k in ("quotas", "quota_fractions", "quota_mode")):
             raise ValueError(self._NO_QUOTAS)
+        audit_fraction, audit_seed = kw.pop("audit_fraction", None), kw.pop("audit_seed", None)
+        if audit_fraction is not None or audit_seed is not None:
+            self.forward_audit_args(audit_fraction, audit_seed)
         ref = pixel_values if pixel_values is not None else input_ids
         if ref is None:
             raise ValueError("pixel_values is required")
@@ -124,6 +147,8 @@ class MicroBatchedEngine:
         for i, n in enumerate(sizes):
             sl = {k: (v[lo:lo + n] if v is not None else None) for k, v in tens.items()}
             outs = (out_logits[lo:lo + n], out_exit[lo:lo + n], out_conf[lo:lo + n])
+            if self.audit:
+                self.engines[i].set_audit(self.audit[0], seed=self.audit[1], slot_base=self.audit[2] + lo)
             if serial:
                 parts.append(self.engines[i].forward(**sl, out=outs, **kw))
             else:
@@ -136,7 +161,8 @@ class MicroBatchedEngine:
                 cur.wait_event(done)
                 # the optional outputs were allocated on the side stream: their memory must not be handed out again before the current
                 # stream (their reader) has passed this point
-                for t in (parts[-1].all_logits, parts[-1].all_crit, parts[-1].head_logits, parts[-1].head_crit, parts[-1].hidden_cls, parts[-1].attentions):
+                for t in (parts[-1].all_logits, parts[-1].all_crit, parts[-1].head_logits, parts[-1].head_crit, parts[-1].hidden_cls, parts[-1].attentions,
+                          parts[-1].audit_mask):
                     if t is not None:
                         t.record_stream(cur)
             self._ran[i] = True
@@ -146,7 +172,8 @@ class MicroBatchedEngine:
         cat = lambda xs, d: None if xs[0] is None else (xs[0] if len(xs) == 1 else torch.cat(xs, dim=d))
         return EngineOutput(out_logits, out_exit, out_conf, cat([p.all_logits for p in parts], 1), cat([p.all_crit for p in parts], 1),
                             cat([p.head_logits for p in parts], 1), cat([p.head_crit for p in parts], 1),
-                            cat([p.hidden_cls for p in parts], 1), None, cat([p.attentions for p in parts], 1))
+                            cat([p.hidden_cls for p in parts], 1), None, cat([p.attentions for p in parts], 1),
+                            cat([p.audit_mask for p in parts], 0))
 
     __call__ = forward
 

@@ -243,16 +243,27 @@ class LayoutLMv3EEForSequenceClassification:
         if any(kw.get(k) is not None for k in ("quotas", "quota_fractions")) or getattr(eng, "quota_mode", None):
             raise ValueError(f"quotas rank the documents of one call: {B} documents do not fit the engine's max_docs = {mb}, and slices would "
                              "each rank alone")
+        # audited exits hash a document's index in the caller's batch: every chunk runs under its own slot base
+        if kw.get("audit_fraction") is not None or kw.get("audit_seed") is not None:
+            eng.forward_audit_args(kw.pop("audit_fraction", None), kw.pop("audit_seed", None))
+        audit = getattr(eng, "audit", None)
         parts = []
-        for s in range(0, B, mb):
-            sl = {k: (v[s:s + mb] if v is not None else None) for k, v in tensors.items()}
-            parts.append(eng.forward(**sl, **kw))
+        try:
+            for s in range(0, B, mb):
+                sl = {k: (v[s:s + mb] if v is not None else None) for k, v in tensors.items()}
+                if audit:
+                    eng.set_audit(audit[0], seed=audit[1], slot_base=audit[2] + s)
+                parts.append(eng.forward(**sl, **kw))
+        finally:
+            if audit:
+                eng.set_audit(*audit)
         cat = lambda xs, d: None if xs[0] is None else torch.cat(xs, dim=d)
         return EngineOutput(cat([p.logits for p in parts], 0), cat([p.exit_layer for p in parts], 0),
                             cat([p.confidence for p in parts], 0), cat([p.all_logits for p in parts], 1),
                             cat([p.all_crit for p in parts], 1), cat([p.head_logits for p in parts], 1),
                             cat([p.head_crit for p in parts], 1), cat([p.hidden_cls for p in parts], 1),
-                            cat([p.hidden_states for p in parts], 1), cat([p.attentions for p in parts], 1))
+                            cat([p.hidden_states for p in parts], 1), cat([p.attentions for p in parts], 1),
+                            cat([p.audit_mask for p in parts], 0))
 
     # ---- the reference signature -------------------------------------------------------------------------------------
     def forward(self, input_ids=None, attention_mask=None, bbox=None, pixel_values=None, labels=None,
@@ -325,7 +336,7 @@ class LayoutLMv3EEForSequenceClassification:
     def early_exit(self, input_ids, attention_mask=None, bbox=None, pixel_values=None, token_type_ids=None,
                    position_ids=None, thresholds: Optional[Union[float, Sequence[float]]] = None,
                    temperatures: Optional[Sequence[float]] = None, patience: Optional[int] = None, low_latency: bool = False,
-                   **kw) -> EngineOutput:
+                   audit_fraction: Optional[float] = None, audit_seed: Optional[int] = None, **kw) -> EngineOutput:
         """(logits, exit_layer, confidence) with the policy test on the device: identical to running ``forward`` on
         everything and then ``Policy(...)`` (EE/eval.py:87-98), but deeper layers only see the surviving documents.
         ``thresholds`` defaults to ``config.exit_config["global_threshold"]``.  Under ``inference_strategy == "patience"`` the thresholds are
@@ -337,10 +348,17 @@ class LayoutLMv3EEForSequenceClassification:
         ``low_latency=True`` (batches of a few documents, one handle): the engine's split-K mode, ``EarlyExitEngine.forward(low_latency=True)``.
         ``quotas=`` / ``quota_fractions=`` / ``quota_mode=`` (budgeted exits, ``EarlyExitEngine.set_quotas``): every exit releases the most
         confident documents of THIS call, a chosen number of them; they stay set on the engine until ``engine.set_quotas(None)``.  One handle, one
-        call: refused with ``micro_batches`` and for a batch above the engine's ``max_docs``."""
+        call: refused with ``micro_batches`` and for a batch above the engine's ``max_docs``.
+        ``audit_fraction=`` / ``audit_seed=`` (audited exits, ``EarlyExitEngine.set_audit``): a hashed sample of the call's documents is
+        delivered where it leaves and runs on to the final exit; with ``want_all=True`` its columns come back complete
+        (``output.audit_mask``, ``audit.sample``, ``audit.consistency``).  They stay set on the engine until ``engine.set_audit(None)``."""
         self._patience_kw(patience, kw)
         if low_latency:
             kw["low_latency"] = True
+        if audit_fraction is not None:
+            kw["audit_fraction"] = audit_fraction
+        if audit_seed is not None:
+            kw["audit_seed"] = audit_seed
         if thresholds is None:
             thresholds = self.config.exit_config["global_threshold"]
         self._small_batch_schedule(pixel_values, kw)

@@ -38,6 +38,25 @@ def msp_table(logits, references=None, device=None):
     return conf, corr
 
 
+def first_argmax(z):
+    """argmax over the last axis of a device tensor, the lowest index on ties (torch.argmax promises no order among ties); a row without a
+    maximum (NaN) counts as label K - 1."""
+    K = z.shape[-1]
+    idx = torch.arange(K, device=z.device, dtype=torch.int64).expand_as(z)
+    return torch.where(z == z.max(dim=-1, keepdim=True).values, idx, torch.full_like(idx, K)).min(dim=-1).values.clamp_(max=K - 1)
+
+
+def final_predictions(logits, device=None):
+    """(N,) int64 on the device: the argmax of the final exit's row of logits (E1,N,K), the lowest index on ties (as ``exit_report`` counts a
+    prediction).  Handed to ``threshold_search``, ``threshold_refine``, ``exit_report`` or the fits as ``references``, "correct" reads "agrees
+    with the full model": the label-free table of live traffic (``audit.sample``) has nothing else."""
+    dev = _require_torch_cuda(device)
+    L = _f64_on(dev, logits)
+    if L.dim() != 3:
+        raise ValueError("logits must have shape (num_exits + 1, num_samples, num_labels)")
+    return first_argmax(L[-1])
+
+
 def csf_table(logits, references=None, criterion="max_confidence", as_csf: bool = False, device=None):
     """The table of one of the three confidence scoring functions (CSF_dict, EE/thresh.py:55-61) on the device (ee_csf_table):
     ``(table float64 (E1,N), correct uint8 (E1,N) | None)`` from logits (E1,N,K).  ``criterion``: "max_confidence" (``msp_table`` bit for bit),
