@@ -240,7 +240,8 @@ enum { MMEE_QUOTA_OFF = 0, MMEE_QUOTA_EXACT = 1, MMEE_QUOTA_AT_LEAST = 2 };
  * ee_set_audit while graphs are held (the seed is per call and by value); cut > 2^32; slot_base < 0.  The Python CascadeEngine refuses a
  * stage handle with an audit set.
  * Not built: audit under quotas, with the result stream, in captured graphs, on cascade stages; a per-exit share; a selection that depends
- * on content; a confidence bound on the agreement rate.
+ * on content; a confidence bound on the agreement rate (the audit counts; the bound, and thresholds certified on the sampled table, are
+ * ee_binomial_bounds and ee_risk_control, "Risk control" below).
  */
 /* model family: LayoutLMv3 (text + layout + image, the reference's EE model) or BEiT / DiT (image only; BASELINE configs[4],
  * the reference's "dit" branch EE/configs.py:429-449 — exit heads there are this build's extrapolation) */
@@ -885,6 +886,63 @@ int ee_threshold_refine(const double* conf, const uint8_t* correct, const uint32
                         int32_t* start_hits, uint64_t* start_cost_sum, double* table, void* stream);
 /* The bytes ee_threshold_refine allocates for its rounds (0 for arguments it would refuse): a pure function, no device. */
 size_t ee_threshold_refine_workspace_bytes(int32_t E1, int32_t N, int32_t P, int32_t S);
+
+/*
+ * Risk control: which of a list of candidate threshold vectors may be deployed with a PROMISE.  The sweeps, the searches and the refinement
+ * return the point that looks best on the table they were given; ee_risk_control returns the cheapest candidate whose risk is at most alpha
+ * with probability at least 1 - delta over the draw of the calibration table: Learn-then-Test (Angelopoulos et al. 2021) with fixed-sequence
+ * testing, as CATs (Schuster et al., EMNLP 2021) and "Fast yet Safe" (Jazbec et al., NeurIPS 2024) use it; along a front found on OTHER data
+ * it is Pareto testing (Laufer-Goldshtein et al. 2023).  THE definition (csrc/risk_control.hip, risk.py and tests/risk_ref.py refer to it).
+ *
+ * Candidates: thr dev double (V,E1), real thresholds of the criterion, in the caller's order, most conservative first.  conf dev double (E1,N) is
+ * the criterion table itself (not negated), sign +1 or -1 (-1: entropy, a learning-to-exit score).
+ * Exit of document n under vector v: the first e < E1-1 with sign conf[e][n] > sign thr[v][e], else E1-1.  The test is strict, a NaN criterion
+ * never fires, thr[v][E1-1] is not read: the decide kernels' and ee_criterion_scan's rule, for one vector.
+ * Loss: loss_q dev uint32 (E1,N) in units of 2^-30: loss_q[e][n] is what it costs in risk that document n leaves at exit e.  A binary loss is
+ * exactly 0 or 2^30; a real loss l in [0,1] is min(2^30, ceil(l 2^30)), so that rounding never understates a risk.  Alternatively loss_f64 dev
+ * double (E1,N), which the call quantises by that rule into its workspace; a value that is not finite or outside [0,1], and under
+ * MMEE_RISK_BINOMIAL a value that is neither 0 nor 1, fails the call with no output written (one synchronise of the stream, as the fits do for a
+ * bad label).  Exactly one of the two is given.  The values of a loss_q the caller built are the caller's duty (<= 2^30; 0 or 2^30 under
+ * MMEE_RISK_BINOMIAL); whatever they are, nothing is read out of bounds.
+ * Per vector, all integers: loss_sum(v) = sum_n loss_q[exit][n] (uint64), exit_sum(v) = sum_n exit (int64), cost_sum(v) = sum_n cost[exit][n]
+ * (uint64) with cost dev uint32 (E1,N) as ee_threshold_search_cost takes it, = exit_sum when cost is NULL, and hist(v,e) = #{n : exit = e} (int32
+ * (V,E1), optional).  No floating-point atomics: the integers do not depend on the launch shape or on the order in which anything arrives.
+ * p-value of H0: R(v) > alpha, n = N.  F(k) = sum_{i <= k} exp(lgamma(n+1) - lgamma(i+1) - lgamma(n-i+1) + i log(alpha) + (n-i) log1p(-alpha)),
+ * summed ascending in float64 and clamped to 1: the binomial distribution function, one table of n + 1 entries per call.
+ *   MMEE_RISK_BINOMIAL (binary tables only)   p = F(loss_sum / 2^30)
+ *   MMEE_RISK_HB (Hoeffding-Bentkus, any table)   r = loss_sum / (n 2^30);  p_H = exp(-n h(r, alpha)) if r < alpha, else 1, with
+ *       h(a,b) = a log(a/b) + (1-a) log((1-a)/(1-b)) and 0 log 0 = 0;  p_B = min(1, e F(ceil(loss_sum / 2^30))), the ceil in integers;
+ *       p = min(p_H, p_B)
+ * Certification at level delta:  MMEE_RISK_FIXED_SEQUENCE: v is certified iff p_u <= delta for every u <= v;  MMEE_RISK_BONFERRONI: iff
+ * p_v <= delta / V.  Selected: the certified vector of smallest cost_sum, ties to the lowest v; -1 when none is certified.
+ * What is promised, and no more: if the calibration documents are exchangeable with the documents served, and the candidate list was fixed
+ * without looking at the calibration table, then P(risk of the selected vector <= alpha) >= 1 - delta.  A front searched on the same table
+ * does not qualify: split the table, search on one part, certify on the other.  The risk is marginal over all documents; a document that runs
+ * to the final exit contributes its final-exit loss.
+ * Outputs, all dev: loss_sum uint64 (V,), exit_sum int64 (V,), cost_sum uint64 (V,), hist int32 (V,E1) or NULL, pvalue double (V,), certified uint8
+ * (V,), n_certified int32 [1], selected int32 [1].  The floating-point sums are taken in an order fixed by the launch, which is fixed by (N, V):
+ * the outputs are a pure function of the inputs.
+ * As it runs: risk_count_kernel (the shape of ee_threshold_sweep's direct kernel, a workgroup's threads striding over a vector's documents; with
+ * few vectors several workgroups share one vector and add their integer sums with integer atomics; a call has 10^2 .. 10^4 vectors, the ranked
+ * route of the big sweeps is not built here), a lgamma table, risk_cdf_kernel (one workgroup), risk_select_kernel (one workgroup).
+ * Refused, each with a message and before any device call: a NULL pointer (cost and hist may be NULL), both or neither of loss_f64 / loss_q,
+ * E1 < 1 or > 64, N < 1 or >= 2^24, V < 1 or > 65536, alpha or delta outside (0,1), a sign other than +-1, unknown bound / method codes.
+ * Not built: the WSR betting bound, conditional (per-exit) risk control, several risks at once, the ranked scorer for millions of vectors,
+ * patience / rule / learning-to-exit / gate decisions (a gate or LTE table can be passed as conf with plain-threshold semantics only).
+ *
+ * ee_binomial_bounds: one-sided Clopper-Pearson bounds, each at delta, of Q counts: n, k HOST int32 (Q,) (k events in n trials), upper and lower
+ * dev double (Q,).  upper = 1 if k = n, else the theta with F(k; n, theta) = delta;  lower = 0 if k = 0, else the theta with
+ * 1 - F(k-1; n, theta) = delta, where F(.; n, theta) is the sum above with theta in place of alpha (a term with a zero count times log 0 is the
+ * term without it).  Each by exactly 64 bisections of [0,1], every tail one block sum in a fixed order, and the midpoint of the last bracket
+ * is returned: a pure function of (n, k, delta).  Refused: NULL pointers, Q < 1 or > 65536, delta outside (0,1), n < 1 or >= 2^24, k < 0 or
+ * k > n in any query.
+ */
+enum { MMEE_RISK_BINOMIAL = 0, MMEE_RISK_HB = 1 };
+enum { MMEE_RISK_FIXED_SEQUENCE = 0, MMEE_RISK_BONFERRONI = 1 };
+int ee_risk_control(const double* conf, double sign, const double* loss_f64, const uint32_t* loss_q, const uint32_t* cost, int32_t E1, int32_t N,
+                    const double* thr, int32_t V, double alpha, double delta, int32_t bound, int32_t method, uint64_t* loss_sum, int64_t* exit_sum,
+                    uint64_t* cost_sum, int32_t* hist, double* pvalue, uint8_t* certified, int32_t* n_certified, int32_t* selected, void* stream);
+int ee_binomial_bounds(const int32_t* n, const int32_t* k, int32_t Q, double delta, double* upper, double* lower, void* stream);
 
 /*
  * The evaluation report: the seven metrics the reference scores every exit and every policy's predictions with (METRICS of evaluate_checkpoint,

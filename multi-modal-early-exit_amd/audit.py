@@ -11,14 +11,15 @@ Jazbec et al., NeurIPS 2024).
 references; live traffic has none, and ``AuditSample.references()`` -- the final exit's own predictions, ``sweep.final_predictions`` -- makes
 "correct" read "agrees with the full model".
 
-Plain torch ops on the device and one small download per report; no kernel.  Counts and rates only: no confidence bound on the agreement
-rate is computed or promised, and a selection that depends on content, a per-exit share and audits under quotas, result streams, captured
-graphs or cascade stages are not built.
+Plain torch ops on the device and one small download per report.  ``consistency(x, delta=)`` adds a one-sided Clopper-Pearson lower bound on
+every agreement rate (``risk.binomial_bounds``, one launch), and ``certify`` hands the sample to ``risk.risk_control``: thresholds whose
+disagreement with the full model is at most ``alpha`` with probability ``1 - delta``.  Not built: a selection that depends on content, a
+per-exit share, audits under quotas, result streams, captured graphs or cascade stages, and bounds that hold for all exits at once.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -73,18 +74,52 @@ class ConsistencyReport:
     pooled_delivered: int = 0
     pooled_agree: int = 0
     pooled_rate: float = float("nan")
+    # ``consistency(x, delta=)`` only: 1 - the one-sided Clopper-Pearson upper bound, at delta, of the disagreements among the delivered.  Each
+    # entry holds with probability 1 - delta ON ITS OWN: there is no correction across the exits, nor between them and the pooled figure
+    rate_lower: Optional[np.ndarray] = None     # (E,), NaN where nobody was delivered
+    pooled_rate_lower: Optional[float] = None
 
 
-def consistency(out_or_sample) -> ConsistencyReport:
+def _with_bounds(rep: ConsistencyReport, delta) -> ConsistencyReport:
+    """``rep`` with ``rate_lower`` / ``pooled_rate_lower`` at ``delta``: one ``binomial_bounds`` call over the exits that delivered anybody and
+    the pooled counts."""
+    if delta is None:
+        return rep
+    from .risk import binomial_bounds
+    rep.rate_lower, rep.pooled_rate_lower = np.full(rep.delivered.shape, np.nan), float("nan")
+    n = np.append(rep.delivered, rep.pooled_delivered).astype(np.int64)
+    k = n - np.append(rep.agree, rep.pooled_agree).astype(np.int64)
+    at = np.nonzero(n > 0)[0]
+    if len(at):
+        lower = 1.0 - binomial_bounds(n[at], k[at], delta)[0]
+        E = len(rep.delivered)
+        rep.rate_lower[at[at < E]] = lower[at < E]
+        if n[E] > 0:
+            rep.pooled_rate_lower = float(lower[-1])
+    return rep
+
+
+def certify(sample: AuditSample, alpha: float, delta: float, **kw):
+    """``risk.risk_control`` on the audited table with the label-free risk: the cheapest of the candidate thresholds (``lambdas=`` /
+    ``thresholds=``; every other keyword of ``risk_control`` passes through) whose answers disagree with the full model's on at most ``alpha``
+    of the documents, with probability at least ``1 - delta`` over the audited sample.  The sample must be exchangeable with the traffic to be
+    served, and the candidates fixed without looking at it."""
+    from .risk import risk_control
+    return risk_control(sample.logits, risk="consistency", alpha=alpha, delta=delta, **kw)
+
+
+def consistency(out_or_sample, delta: Optional[float] = None) -> ConsistencyReport:
     """``ConsistencyReport`` of an audited output (``want_all=True``) or of an ``AuditSample``.  A document delivered at the final exit is the
-    full model's answer by construction and is counted in ``num_samples`` only.  Counts and rates; no confidence bound."""
+    full model's answer by construction and is counted in ``num_samples`` only.  Counts and rates; with ``delta`` also ``rate_lower`` (E,) and
+    ``pooled_rate_lower``: 1 - the one-sided Clopper-Pearson upper bound of the disagreements at ``delta`` each, with no correction across
+    the exits.  Without ``delta`` the report and its single download are what they were before the bounds existed."""
     from .sweep import first_argmax
     s = out_or_sample if isinstance(out_or_sample, AuditSample) else sample(out_or_sample)
     E1, n, _ = s.logits.shape
     E = E1 - 1
     if n == 0 or E == 0:
         z = np.zeros((E,), dtype=np.int64)
-        return ConsistencyReport(z, z.copy(), np.full((E,), np.nan), int(n))
+        return _with_bounds(ConsistencyReport(z, z.copy(), np.full((E,), np.nan), int(n)), delta)
     ex = s.exit_layer.to(torch.int64)
     early = ex < E
     row = s.logits[ex.clamp(max=E), torch.arange(n, device=ex.device)]                     # (n,K): the row each document was delivered with
@@ -95,4 +130,4 @@ def consistency(out_or_sample) -> ConsistencyReport:
     with np.errstate(invalid="ignore", divide="ignore"):
         rate = np.where(d > 0, a / np.maximum(d, 1), np.nan)
     pd, pa = int(d.sum()), int(a.sum())
-    return ConsistencyReport(d, a, rate, int(n), pd, pa, pa / pd if pd else float("nan"))
+    return _with_bounds(ConsistencyReport(d, a, rate, int(n), pd, pa, pa / pd if pd else float("nan")), delta)

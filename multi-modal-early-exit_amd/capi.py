@@ -27,6 +27,8 @@ QUOTA_OFF, QUOTA_EXACT, QUOTA_AT_LEAST = 0, 1, 2
 QUOTA_MODES = {"exact": QUOTA_EXACT, "at_least": QUOTA_AT_LEAST}
 SEARCH_GRID, SEARCH_SAMPLED, SEARCH_MIXTURES = 0, 1, 2
 SEARCH_REFERENCE, SEARCH_POLICY = 0, 1
+RISK_BINOMIAL, RISK_HB = 0, 1
+RISK_FIXED_SEQUENCE, RISK_BONFERRONI = 0, 1
 # the columns of ee_exit_metrics' output rows (MMEE_METRIC_*)
 (METRIC_ACCURACY, METRIC_BRIER, METRIC_NLL, METRIC_F1_MICRO, METRIC_F1_MACRO, METRIC_ECE, METRIC_AURC, METRIC_AVG_CONF,
  METRIC_COUNT) = range(9)
@@ -227,6 +229,9 @@ SYMBOLS = {
                                            _vp, _vp, _vp]),
     "ee_threshold_refine": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ee_threshold_refine_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32]),
+    "ee_risk_control": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp, _i32, _i32, _vp, _i32, C.c_double, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _vp, _vp]),
+    "ee_binomial_bounds": (C.c_int, [C.POINTER(_i32), C.POINTER(_i32), _i32, C.c_double, _vp, _vp, _vp]),
     "ee_msp_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_csf_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_gate_table": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
