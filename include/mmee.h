@@ -243,6 +243,52 @@ enum { MMEE_QUOTA_OFF = 0, MMEE_QUOTA_EXACT = 1, MMEE_QUOTA_AT_LEAST = 2 };
  * on content; a confidence bound on the agreement rate (the audit counts; the bound, and thresholds certified on the sampled table, are
  * ee_binomial_bounds and ee_risk_control, "Risk control" below).
  */
+/*
+ * Online exit control (ee_set_controller; EarlyExitEngine.set_controller, risk.rolling_control): the thresholds of a handle follow the
+ * disagreement its own audit observes, between forwards, on the device.  Rolling risk control -- Gibbs and Candes, "Adaptive conformal
+ * inference under distribution shift" (NeurIPS 2021); Feldman, Ringel, Bates and Romano, "Achieving risk control in online learning settings"
+ * (TMLR 2023).  THE definition (the forward's two launches, ee_rolling_control, the two stand-alone hooks and the numpy restatement of
+ * tests/controller_ref.py refer to it).
+ * A controller has a path[V][E1] of float64 threshold vectors, V >= 2, ordered from the most conservative (index 0) to the most aggressive (the
+ * order of ee_risk_control's candidates); a position p (float64), started at p0 in [0, V - 1]; a risk level alpha in (0, 1); a step gamma > 0;
+ * a base seed.  It needs an audit (ee_set_audit with cut > 0).
+ * Thresholds of a call, computed on the device from p.  p < 0: every exit below the final one gets the value that never fires, +inf under the
+ * `>` criteria and -inf under entropy.  Otherwise p' = min(p, V - 1), i = min(floor(p'), V - 2), t = p' - i and
+ *   thr[e] = a + (b - a) t,   a = path[i][e], b = path[i + 1][e],
+ * the product rounded before the add (no fused multiply-add).  thr[E1 - 1] is path[i][E1 - 1] (path[0]'s when p < 0); no forward reads it.
+ * Loss of a call of B documents, all integers.  sampled = #{slot < B : selected(cut, seed_t, slot + slot_base)} by the audit's hash.
+ * disagree = the shadows -- documents delivered below the final exit that ran on -- whose delivered row out_logits[slot], the float32 row as
+ * written, has another argmax than their final-exit policy row, the row the final exit's decide launch read, scaled as that launch writes it.
+ * The argmax takes the lowest index on ties; a row with a NaN counts as K - 1.  delivered[e] and agree[e] count the same per exit, by
+ * out_exit[slot]: the numbers of audit.consistency, without the dump of every exit.
+ * Step, by one thread.  sampled == 0: nothing changes.  Otherwise p <- min(V - 1, p - gamma ((double)disagree / (double)sampled - alpha)), the
+ * product rounded before the subtraction.
+ * Seed.  Call number t = 0, 1, ... since ee_set_controller audits under seed (seed + t) mod 2^32; the seed of ee_set_audit is not read.
+ * Promise.  With l_t = disagree / sampled of the calls that sampled anybody, for every T:  sum_{t <= T} (l_t - alpha) <= p0 / gamma + 1 - alpha.
+ * Why: while p < 0 nobody leaves early, so the loss is 0 and p rises by gamma alpha; from p >= 0 one step lowers p by at most gamma (1 - alpha);
+ * so p >= -gamma (1 - alpha) always, and p_T = p0 - gamma sum (l_t - alpha) unless the clamp at V - 1 made it smaller still.  It is an
+ * inequality on the observed sequence: it holds for any data, in any order, with no exchangeability assumed.
+ * Limit.  The bound is on the AUDITED estimate: the true disagreement rate follows only up to the sampling error of the audit, and nothing
+ * is promised for a single call.
+ * Forward.  While a controller is set, every decide launch of a call that is not dump-all is the AUDIT form and reads its threshold from the
+ * handle's device vector; behind the final exit run audit_tally_kernel and controller_step_kernel (profile role "controller"), which leave
+ * the next call's thresholds in that vector and one row in a device ring log.  No host step, no synchronisation.  Dump-all calls and
+ * MMEE_FLAG_NO_EXIT calls ignore the controller: no step is taken and no seed is used.  A handle without a controller issues the launches it
+ * issued before and returns the same bits.
+ * Log row, controller_log_words = 5 + 2 (E1 - 1) + E1 64-bit words: call index, p before, p after (float64 bits), sampled, disagree,
+ * delivered[E1 - 1], agree[E1 - 1], thresholds[E1] the call ran with (float64 bits).
+ * Allowed unchanged: the four threshold criteria (gate included), temperatures, an ensemble (the tally reads the row the decision read),
+ * MMEE_FLAG_LOW_LATENCY, ramp, gate and DiT handles.
+ * Refused, each with a message and nothing changed: no audit set; MMEE_CRIT_PATIENCE, an exit rule other than MMEE_RULE_PLAIN, use_lte; quotas (by
+ * ee_set_quotas itself: a controller needs an audit, and an audit and quotas refuse each other);
+ * MMEE_FLAG_STREAM_RESULTS and ee_graph_capture while a controller is set, ee_set_controller while graphs are held; a non-NULL thresholds
+ * argument or a NULL out_logits on a controlled ee_forward; V < 2, E1 < 2 or E1 > 64, alpha outside (0, 1), gamma <= 0 or not finite, p0
+ * outside [0, V - 1], a path entry that is not finite; ee_set_audit(h, 0, ...), a change of criterion and a non-plain exit rule while a
+ * controller is set.  The Python MicroBatchedEngine and CascadeEngine refuse a controlled handle.
+ * Not built: controllers under captured graphs, with the result stream, over micro-batches, on cascade stages; losses other than consistency
+ * in the forward (ee_rolling_control takes any 0 / 1 table); a per-exit (conditional) risk; step-size schedules; one controller shared across
+ * ranks.
+ */
 /* model family: LayoutLMv3 (text + layout + image, the reference's EE model) or BEiT / DiT (image only; BASELINE configs[4],
  * the reference's "dit" branch EE/configs.py:429-449 — exit heads there are this build's extrapolation) */
 enum { MMEE_ARCH_LAYOUTLMV3 = 0, MMEE_ARCH_BEIT = 1 };
@@ -552,6 +598,31 @@ int ee_has_quotas(const ee_handle* h);
 int ee_set_audit(ee_handle* h, uint64_t cut, uint32_t seed, int32_t slot_base);
 int ee_has_audit(const ee_handle* h);
 int ee_audit_selected(uint64_t cut, uint32_t seed, int32_t slot);
+
+/* The controller (online exit control, definition above, behind the audit's) of every LATER ee_forward.  path HOST float64 (V,E1), most
+ * conservative first, copied; NULL switches the controller off (the other arguments are then not read).  p0: the starting position; seed: call
+ * t audits under seed + t; log_cap: rows of the device ring log, 0 for none.  Setting a controller restarts the call count, the position
+ * and the log.  Synchronises the device.  Refusals: the definition's list.
+ * ee_has_controller: 1 while one is set.
+ * ee_controller_state: synchronises the stream and reads the position, the controlled calls so far, those that sampled anybody (steps), the
+ * sums of sampled and disagree over them, and (thr_out HOST float64 [E1], or NULL) the thresholds the NEXT call will run with.  Any output
+ * may be NULL.
+ * ee_controller_log: synchronises the stream; *n = rows the ring holds (min(calls, log_cap)); the latest min(*n, cap) of them, oldest first,
+ * into rows_out HOST int64 (cap, controller_log_words).  The one download. */
+int ee_set_controller(ee_handle* h, const double* path, int32_t V, double alpha, double gamma, double p0, uint32_t seed, int32_t log_cap);
+int ee_has_controller(const ee_handle* h);
+int ee_controller_state(ee_handle* h, double* p, int64_t* calls, int64_t* steps, int64_t* sampled_sum, int64_t* disagree_sum, double* thr_out,
+                        void* stream);
+int ee_controller_log(ee_handle* h, int64_t* rows_out, int32_t cap, int32_t* n, void* stream);
+/* The same loop replayed on dumped arrays in one launch (no handle): table dev float64 (E1,N), a criterion table (ee_csf_table, ee_gate_table)
+ * and its sign (+1: leave on c > thr, -1: on c < thr; strict, a NaN never fires); bad dev uint8 (E1,N), row e: delivering document n at exit e
+ * is a loss; path dev float64 (V,E1).  Consecutive groups of G documents play the calls: group t audits its slots 0 .. G-1 under seed + t,
+ * the exit of a document is the first e < E1 - 1 whose test fires under the group's thresholds, else E1 - 1.  exits dev int32 (N); log dev
+ * int64 (ceil(N / G), controller_log_words), one row per group; p_out dev float64 [1] or NULL: the position after the last group.
+ * Refused: E1 outside [2, 64], N outside [1, 2^28), G < 1, V < 2, a sign that is not +-1, cut outside [1, 2^32], alpha, gamma, p0 as for
+ * ee_set_controller. */
+int ee_rolling_control(const double* table, double sign, const uint8_t* bad, int32_t E1, int32_t N, const double* path, int32_t V, uint64_t cut,
+                       uint32_t seed, double alpha, double gamma, double p0, int32_t G, int32_t* exits, int64_t* log, double* p_out, void* stream);
 
 /* Pin the exit-layer schedule.  DEFAULT (enabled == 0): every layer that ends in a decision is probed first.  Rounds 2-4 chose per layer
  * from the stage populations of "the handle's most recent FINISHED forward" -- a timing-dependent host decision, and under MMEE_FLAG_XPROBE
@@ -1650,6 +1721,40 @@ typedef struct ee_debug_exit_audit_args {
     int32_t* delivered;
 } ee_debug_exit_audit_args;
 int ee_debug_exit_audit(const ee_debug_exit_audit_args* args, void* stream);
+/* ee_debug_audit_tally / ee_debug_controller_step: the two launches a controlled forward adds behind its final exit (online exit control,
+ *   definition behind the audit's), each alone.
+ *   tally: the final stage (counts dev StageCounts, doc_orig dev int32 [n_docs], every entry in [0, B)), pol_logits dev float [pol_rows][K] the
+ *   rows the final decide launch read and temp what it scaled them by, delivered dev int32 [B] the audit's marks, out_logits dev float (B,K),
+ *   out_exit dev int32 (B), the audit's cut in [1, 2^32], seed and slot_base >= 0.  tally dev int64 [2 + 2 (E1 - 1)] is written: sampled,
+ *   disagree, delivered[E1 - 1], agree[E1 - 1]; a shadow whose out_exit lies outside [0, E1 - 1) counts in disagree only.
+ *   step: path dev float64 (V,E1); state dev int64 [5]: p (float64 bits), calls, steps, sampled_sum, disagree_sum, updated; tally as above,
+ *   read; thr dev float64 [E1]: the thresholds the call ran with go in (they are logged), the next call's come out; log dev int64
+ *   (log_cap, controller_log_words) or NULL: row calls % log_cap is written.
+ *   Refused: NULL pointers, E1 outside [2, 64], counts or slots outside the buffers, and the parameter ranges of ee_set_controller. */
+typedef struct ee_debug_audit_tally_args {
+    const float* pol_logits;
+    int32_t pol_rows, K, B, E1;
+    double temp;
+    const int32_t *counts, *doc_orig, *delivered;
+    const float* out_logits;
+    const int32_t* out_exit;
+    uint64_t cut;
+    uint32_t seed;
+    int32_t slot_base;
+    int64_t* tally;
+} ee_debug_audit_tally_args;
+int ee_debug_audit_tally(const ee_debug_audit_tally_args* args, void* stream);
+typedef struct ee_debug_controller_step_args {
+    const double* path;
+    int32_t V, E1;
+    double sign, alpha, gamma;
+    int64_t* state;
+    const int64_t* tally;
+    double* thr;
+    int64_t* log;
+    int32_t log_cap;
+} ee_debug_controller_step_args;
+int ee_debug_controller_step(const ee_debug_controller_step_args* args, void* stream);
 
 /* Unit-test hook of the patch projection (Conv2d with kernel = stride = patch as a GEMM over flattened patches), the counterpart of
  * ee_debug_attention: what patch_projection() of the forward launches, on caller-provided DEVICE buffers; no handle.

@@ -32,4 +32,5 @@ from .cascade import CascadeEngine, CascadeOutput  # noqa: F401,E402
 from . import audit  # noqa: F401,E402
 from .audit import AuditSample, ConsistencyReport  # noqa: F401,E402
 from . import risk  # noqa: F401,E402
-from .risk import RiskResult, risk_control  # noqa: F401,E402
+from .risk import RiskResult, RollingResult, risk_control, rolling_control  # noqa: F401,E402
+from .engine import ControllerLog  # noqa: F401,E402

@@ -132,6 +132,28 @@ def audit_cut(fraction: float) -> int:
     return int(math.floor(f * 4294967296.0 + 0.5))
 
 
+class DebugAuditTallyArgs(C.Structure):
+    """ee_debug_audit_tally_args of include/mmee.h: the final stage, the audit's marks and selection, the call's results; device pointers."""
+    _fields_ = ([("pol_logits", _vp)] + [(n, _i32) for n in ("pol_rows", "K", "B", "E1")] + [("temp", C.c_double)]
+                + [(n, _vp) for n in ("counts", "doc_orig", "delivered", "out_logits", "out_exit")]
+                + [("cut", C.c_uint64), ("seed", _u32), ("slot_base", _i32), ("tally", _vp)])
+
+
+class DebugControllerStepArgs(C.Structure):
+    """ee_debug_controller_step_args of include/mmee.h: the path, the controller's parameters, state / tally / thresholds / log on the device."""
+    _fields_ = ([("path", _vp), ("V", _i32), ("E1", _i32)] + [(n, C.c_double) for n in ("sign", "alpha", "gamma")]
+                + [(n, _vp) for n in ("state", "tally", "thr", "log")] + [("log_cap", _i32)])
+
+
+CTL_STATE_WORDS = 5            # p (float64 bits), calls, steps, sampled_sum, disagree_sum
+CTL_MAX_E1 = 64
+
+
+def controller_log_words(E1: int) -> int:
+    """64-bit words of a controller log row (include/mmee.h): call, p before, p after, sampled, disagree, delivered[E], agree[E], thresholds[E1]."""
+    return 5 + 2 * (E1 - 1) + E1
+
+
 class DebugExitEnsembleArgs(C.Structure):
     """ee_debug_exit_ensemble_args of include/mmee.h: device pointers (or None), this exit's temperature and sizes."""
     _fields_ = ([("pol_logits", _vp)] + [(n, _i32) for n in ("pol_rows", "K", "E1", "exit_index", "B")] + [("temp", C.c_double), ("by_pointer", _i32)]
@@ -207,6 +229,15 @@ SYMBOLS = {
     "ee_has_audit": (C.c_int, [_vp]),
     "ee_audit_selected": (C.c_int, [C.c_uint64, _u32, _i32]),
     "ee_debug_exit_audit": (C.c_int, [C.POINTER(DebugExitAuditArgs), _vp]),
+    "ee_set_controller": (C.c_int, [_vp, C.POINTER(C.c_double), _i32, C.c_double, C.c_double, C.c_double, _u32, _i32]),
+    "ee_has_controller": (C.c_int, [_vp]),
+    "ee_controller_state": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_int64), C.POINTER(C.c_double), _vp]),
+    "ee_controller_log": (C.c_int, [_vp, _vp, _i32, C.POINTER(_i32), _vp]),
+    "ee_rolling_control": (C.c_int, [_vp, C.c_double, _vp, _i32, _i32, _vp, _i32, C.c_uint64, _u32, C.c_double, C.c_double, C.c_double, _i32, _vp,
+                                     _vp, _vp, _vp]),
+    "ee_debug_audit_tally": (C.c_int, [C.POINTER(DebugAuditTallyArgs), _vp]),
+    "ee_debug_controller_step": (C.c_int, [C.POINTER(DebugControllerStepArgs), _vp]),
     "ee_suggest_probe_mask": (C.c_int, [_vp, _u32, C.POINTER(C.c_uint64), _vp]),
     "ee_clock_stamp": (C.c_int, [_vp, _vp]),
     "ee_set_inputs_embeds": (C.c_int, [_vp, _vp]),

@@ -182,6 +182,9 @@ class CascadeEngine:
     def _run_stage(self, s, arrays, n, out, thr, tmp, flags):
         """Stage s on n documents in consecutive chunks of at most its max_docs (documents are independent), results into row slices of `out`."""
         eng = self.stages[s]
+        if getattr(eng, "has_controller", None) and eng.has_controller():
+            raise ValueError(f"stage {s} has a controller set: online exit control on cascade stages is not built (a stage's calls are the deferred "
+                             "documents of another); set_controller(None) on the stage's engine")
         if eng.has_audit():
             raise ValueError(f"stage {s} has an audit set: audited exits on cascade stages are not built (a stage sees deferred documents under "
                              "new slots, and a shadow's final row is not a deferral); set_audit(None) on the stage's engine")

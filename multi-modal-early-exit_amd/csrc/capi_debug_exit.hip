@@ -1,4 +1,5 @@
-// ee_debug_head_out, ee_debug_exit_ensemble, ee_debug_exit_decide, ee_debug_exit_quota, ee_debug_exit_audit, ee_debug_rows_out: the exit stage of exit_stage.hip alone, on caller-provided
+// ee_debug_head_out, ee_debug_exit_ensemble, ee_debug_exit_decide, ee_debug_exit_quota, ee_debug_exit_audit, ee_debug_rows_out: the exit stage of exit_stage.hip alone,
+// and ee_debug_audit_tally, ee_debug_controller_step: the controller's two launches (controller.hip) alone, on caller-provided
 // device buffers; no handle.  Each entry point makes the calls of the path's own launchers that capi_forward.hip makes (launch_head_out;
 // launch_exit_ensemble; launch_decide -- under a quota launch_exit_quota_crit, launch_exit_quota_rank and launch_decide_quota -- and, behind it,
 // launch_compact_rows as compact() does; launch_gather_cls / launch_rows_to_padded) and synchronises.  No kernel is defined or
@@ -243,6 +244,60 @@ int ee_debug_exit_ensemble(const ee_debug_exit_ensemble_args* a, void* stream) {
         en.temp = __builtin_nan("");                               // the by-value form must not be what the kernel reads
     }
     launch_exit_ensemble(en, s);
+    return finish(who, s, nullptr, nullptr);
+}
+
+int ee_debug_audit_tally(const ee_debug_audit_tally_args* a, void* stream) {
+    const char* who = "ee_debug_audit_tally";
+    if (!a) return fail(nullptr, "%s: args must not be NULL", who);
+    if (!a->pol_logits || !a->counts || !a->doc_orig || !a->delivered || !a->out_logits || !a->out_exit || !a->tally)
+        return fail(nullptr, "%s: pol_logits, counts, doc_orig, delivered, out_logits, out_exit and tally must not be NULL", who);
+    if (a->K < 1) return fail(nullptr, "%s: K %d is below 1", who, a->K);
+    if (a->E1 < 2 || a->E1 > kCtlMaxE1) return fail(nullptr, "%s: E1 = %d, need 2 <= E1 <= %d", who, a->E1, kCtlMaxE1);
+    if (a->B < 1 || a->B > (1 << 20)) return fail(nullptr, "%s: B %d outside [1, 2^20]", who, a->B);
+    if (a->pol_rows < 0) return fail(nullptr, "%s: pol_rows %d is negative", who, a->pol_rows);
+    if (a->cut < 1 || a->cut > (1ull << 32)) return fail(nullptr, "%s: cut %llu outside [1, 2^32]", who, (unsigned long long)a->cut);
+    if (a->slot_base < 0) return fail(nullptr, "%s: slot_base %d is negative", who, a->slot_base);
+    if (!(a->temp > 0.0)) return fail(nullptr, "%s: temp %g is not positive", who, a->temp);
+    if (!have_device(who)) return 1;
+    static_assert(sizeof(StageCounts) == 16, "the layout include/mmee.h documents");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (hipStreamSynchronize(s) != hipSuccess) return fail(nullptr, "%s: the stream is in error", who);
+    StageCounts hc{};
+    if (hipMemcpy(&hc, a->counts, sizeof(hc), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of counts failed", who);
+    const int n = hc.n_docs;
+    if (n < 0 || n > a->B) return fail(nullptr, "%s: counts.n_docs = %d outside [0, B = %d]", who, n, a->B);
+    if (n > a->pol_rows) return fail(nullptr, "%s: %d documents leave the %d rows of pol_logits", who, n, a->pol_rows);
+    if (int rc = check_row_map(who, "doc_orig", a->doc_orig, n, a->B)) return rc;
+    AuditTallyArgs t{};
+    t.counts = reinterpret_cast<const StageCounts*>(a->counts); t.doc_orig = a->doc_orig; t.pol_logits = a->pol_logits; t.temp = a->temp;
+    t.K = a->K; t.B = a->B; t.E1 = a->E1; t.delivered = a->delivered; t.out_logits = a->out_logits; t.out_exit = a->out_exit;
+    t.cut = a->cut; t.seed = a->seed; t.slot_base = a->slot_base; t.tally = reinterpret_cast<long long*>(a->tally);
+    launch_audit_tally(t, s);
+    return finish(who, s, nullptr, nullptr);
+}
+
+int ee_debug_controller_step(const ee_debug_controller_step_args* a, void* stream) {
+    const char* who = "ee_debug_controller_step";
+    if (!a) return fail(nullptr, "%s: args must not be NULL", who);
+    if (!a->path || !a->state || !a->tally || !a->thr) return fail(nullptr, "%s: path, state, tally and thr must not be NULL", who);
+    if (a->E1 < 2 || a->E1 > kCtlMaxE1) return fail(nullptr, "%s: E1 = %d, need 2 <= E1 <= %d", who, a->E1, kCtlMaxE1);
+    if (a->V < 2 || a->V > (1 << 20)) return fail(nullptr, "%s: V = %d vectors, a path needs 2 <= V <= 2^20", who, a->V);
+    if (a->sign != 1.0 && a->sign != -1.0) return fail(nullptr, "%s: sign is +1 or -1", who);
+    if (!(a->alpha > 0.0 && a->alpha < 1.0)) return fail(nullptr, "%s: alpha = %g, the risk level must lie in (0, 1)", who, a->alpha);
+    if (!(a->gamma > 0.0) || !std::isfinite(a->gamma)) return fail(nullptr, "%s: gamma = %g, the step must be positive and finite", who, a->gamma);
+    if (a->log_cap < 0 || (a->log_cap > 0 && !a->log)) return fail(nullptr, "%s: log_cap = %d rows without a log", who, a->log_cap);
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (hipStreamSynchronize(s) != hipSuccess) return fail(nullptr, "%s: the stream is in error", who);
+    long long calls = 0;
+    if (hipMemcpy(&calls, a->state + 1, sizeof(calls), hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, "%s: copy of the state failed", who);
+    if (calls < 0) return fail(nullptr, "%s: state.calls = %lld is negative (it picks the row of the log ring)", who, calls);
+    ControllerStepArgs st{};
+    st.path = a->path; st.V = a->V; st.E1 = a->E1; st.sign = a->sign; st.alpha = a->alpha; st.gamma = a->gamma;
+    st.state = reinterpret_cast<long long*>(a->state); st.tally = reinterpret_cast<const long long*>(a->tally); st.thr = a->thr;
+    st.log = reinterpret_cast<long long*>(a->log); st.log_cap = a->log ? a->log_cap : 0;
+    launch_controller_step(st, s);
     return finish(who, s, nullptr, nullptr);
 }
 

@@ -206,6 +206,11 @@ struct Forward {
     const bool stream_results = a.flags & MMEE_FLAG_STREAM_RESULTS;
     // audited exits (ee_set_audit): every decide launch of the call is the AUDIT form; a dump-all call ignores the audit, everybody stays anyway
     const bool audit = h->audit_cut != 0 && !no_exit;
+    // online exit control (ee_set_controller): every decide launch reads its threshold at h->ctl_thr_dev and audits under the call's own seed;
+    // audit_tally_kernel and controller_step_kernel run behind the final exit.  A dump-all call ignores the controller: no step, no seed used
+    const bool ctl = h->ctl_on && !no_exit;
+    const float* fin_pol = nullptr;          // the rows the final exit's decide launch read, and the temperature it scaled them by
+    double fin_temp = 1.0;
     // split precision attention: attention_idx.hip (pair index built once per forward; default) or, with MMEE_ATTN_V=2 or bucket tables
     // beyond 64 bins, attention_pair.hip (clamped Delta tables gathered per layer and head)
     const bool use_idx = sp && attn_variant() == 0 && c.rel_pos_bins <= 64 && c.rel_2d_pos_bins <= 64;
@@ -242,8 +247,19 @@ struct Forward {
             return fail(h, "ee_forward: pixel_values and out_exit (and input_ids, bbox for LayoutLMv3) are required");
         if (B < 1 || B > c.max_docs) return fail(h, "ee_forward: B=%d outside [1, max_docs=%d]", B, c.max_docs);
         if (!beit && (T < 1 || T > c.max_text_len)) return fail(h, "ee_forward: T=%d outside [1, max_text_len=%d]", T, c.max_text_len);
-        if (!a.thresholds && !cap && !patience && !no_exit && h->quota_mode != MMEE_QUOTA_EXACT)
+        if (!a.thresholds && !cap && !patience && !no_exit && h->quota_mode != MMEE_QUOTA_EXACT && !ctl)
             return fail(h, "ee_forward: thresholds required unless MMEE_FLAG_NO_EXIT, MMEE_CRIT_PATIENCE or MMEE_QUOTA_EXACT");
+        if (ctl && cap)
+            return fail(h, "ee_graph_capture: a controller is set: its seed changes per call and the step reads the call's own results, so controlled "
+                           "calls are eager (not built; ee_set_controller(h, NULL, ...) first)");
+        if (ctl && a.thresholds)
+            return fail(h, "ee_forward: thresholds are given while a controller is set: the controller's position decides them "
+                           "(pass NULL, or ee_set_controller(h, NULL, ...) first)");
+        if (ctl && !a.out_logits)
+            return fail(h, "ee_forward: out_logits is NULL while a controller is set: the loss compares the delivered row with the final exit's");
+        if (ctl && stream_results)
+            return fail(h, "ee_forward: MMEE_FLAG_STREAM_RESULTS while a controller is set: its audit keeps delivered documents in the stage, which "
+                           "emit_leavers cannot tell from the ones that stay (not built; ee_set_controller(h, NULL, ...) first)");
         if (h->quota_mode != MMEE_QUOTA_OFF && (patience || h->rule != MMEE_RULE_PLAIN || c.use_lte))
             return fail(h, "ee_forward: quotas are set, and no rank is defined under MMEE_CRIT_PATIENCE, MMEE_RULE_STREAK / MMEE_RULE_EITHER or use_lte "
                            "(ee_set_quotas(h, NULL, 0, 0) first)");
@@ -661,6 +677,7 @@ struct Forward {
         d.thr = a.thresholds ? a.thresholds[exit_index] : 0.0;
         d.temp = a.temperatures ? a.temperatures[exit_index] : 1.0;
         if (cap) { d.thr_ptr = cap->thr_dev; d.temp_ptr = cap->thr_dev + (E + 1); }      // replays read the vector of THEIR launch
+        if (ctl) d.thr_ptr = h->ctl_thr_dev;                                             // the vector the previous call's step left
         if (h->ens_on) {
             // exit ensemble (ee_set_ensemble): y_m of every active document into a second policy buffer; the decision reads that with temperature 1
             EnsembleArgs en{};
@@ -699,10 +716,11 @@ struct Forward {
             { ProfScope ps(h, P_DECIDE, s); launch_decide_quota(d, qa, h->quota_mode, s); }
         } else {
             ProfScope ps(h, P_DECIDE, s);
-            const AuditArgs au{h->audit_delivered, h->audit_cut, h->audit_seed, h->audit_slot_base};
+            const AuditArgs au{h->audit_delivered, h->audit_cut, ctl ? (uint32_t)(h->ctl_seed + (uint32_t)h->ctl_calls) : h->audit_seed, h->audit_slot_base};
             launch_decide(d, stateful ? &pa : nullptr, patience ? DECIDE_PATIENCE : c.use_lte ? DECIDE_LTE : DECIDE_THRESHOLD, h->rule, s, audit ? &au : nullptr);
         }
         h->rec.exit_stage[exit_index] = cur;
+        if (is_final) { fin_pol = d.pol_logits; fin_temp = d.temp; }
         if (stream_results) emit_leavers(is_final);
         if (!is_final) compact();
         exit_index += 1;
@@ -813,6 +831,22 @@ struct Forward {
         ++next_enc;
     }
 
+    // online exit control: what the audit saw in this call (the final stage is still `cur`: the final exit compacts nothing), then the step
+    // and the thresholds of the next call.  The call's seed is the one its decide launches audited under.
+    void control() {
+        const int E1 = E + 1;
+        AuditTallyArgs t{};
+        t.counts = &h->counts[cur]; t.doc_orig = S_doc_orig(cur); t.pol_logits = fin_pol; t.temp = fin_temp; t.K = K; t.B = B; t.E1 = E1;
+        t.delivered = h->audit_delivered; t.out_logits = a.out_logits; t.out_exit = a.out_exit;
+        t.cut = h->audit_cut; t.seed = (uint32_t)(h->ctl_seed + (uint32_t)h->ctl_calls); t.slot_base = h->audit_slot_base; t.tally = h->ctl_tally;
+        { ProfScope ps(h, P_CONTROLLER, s); launch_audit_tally(t, s); }
+        ControllerStepArgs st{};
+        st.path = h->ctl_path; st.V = h->ctl_V; st.E1 = E1; st.sign = crit_sign(c.criterion); st.alpha = h->ctl_alpha; st.gamma = h->ctl_gamma;
+        st.state = h->ctl_state; st.tally = h->ctl_tally; st.thr = h->ctl_thr_dev; st.log = h->ctl_log; st.log_cap = h->ctl_log_cap;
+        { ProfScope ps(h, P_CONTROLLER, s); launch_controller_step(st, s); }
+        ++h->ctl_calls;
+    }
+
     void final_exit() {
         if (beit) {
             // BeitPooler (BEIT:563-572): LayerNorm(mean of the patch tokens), then the Linear classifier
@@ -874,6 +908,7 @@ struct Forward {
         // the caller decides whether to pin it).  The same inputs therefore always run the same launch sequence and return the same bits.
         for (int l = 0; l < L; ++l) layer(l);
         final_exit();
+        if (ctl) control();
         if (stream_results) h->stream_armed = true;
         r.last_B = B; r.last_T = T; r.last_stages = E + 1; r.last_flags = a.flags;
         r.last_gate_heads = a.out_head_logits || a.out_head_crit || c.criterion == MMEE_CRIT_GATE;
@@ -911,6 +946,9 @@ int ee_graph_capture(ee_handle* h, const int64_t* input_ids, const int64_t* atte
     if (flags & MMEE_FLAG_STREAM_RESULTS)          // before the eager warm-up call, which would otherwise run (and stream) first
         return fail(h, "ee_graph_capture: MMEE_FLAG_STREAM_RESULTS belongs to eager calls (the events between the launches are not part of a captured "
                        "launch list)");
+    if (h->ctl_on)                                 // before the audit's refusal: a controller implies an audit
+        return fail(h, "ee_graph_capture: a controller is set: its seed changes per call and the step reads the call's own results, so controlled "
+                       "calls are eager (not built; ee_set_controller(h, NULL, ...) first)");
     if (h->audit_cut)                              // likewise before the warm-up call: the handle's state decides, whatever the flags
         return fail(h, "ee_graph_capture: an audit is set: its seed changes per call and is passed by value, so audited calls are eager "
                        "(not built; ee_set_audit(h, 0, 0, 0) first)");

@@ -146,6 +146,16 @@ struct ee_handle {
     uint32_t audit_seed = 0;
     int32_t audit_slot_base = 0;
     int* audit_delivered = nullptr;               // [max_docs] by original slot, allocated at the first ee_set_audit
+    // online exit control (ee_set_controller; include/mmee.h): while ctl_on, every decide launch of a call that is not dump-all reads its
+    // threshold at ctl_thr_dev, audits under seed ctl_seed + ctl_calls, and two launches behind the final exit step the position
+    bool ctl_on = false;
+    int32_t ctl_V = 0, ctl_log_cap = 0;
+    double ctl_alpha = 0.0, ctl_gamma = 0.0;
+    uint32_t ctl_seed = 0;
+    uint64_t ctl_calls = 0;                       // controlled calls enqueued since ee_set_controller (the device state counts them too)
+    double* ctl_path = nullptr;                   // (V,E1)
+    double* ctl_thr_dev = nullptr;                // [E1]: the thresholds of the NEXT controlled call, rewritten by controller_step_kernel
+    long long *ctl_state = nullptr, *ctl_tally = nullptr, *ctl_log = nullptr;      // kCtlStateWords; controller_tally_words; the ring of log rows
     // optional per-kernel event timing (ee_profile)
     bool prof_on = false;
     struct ProfRec { int id; hipEvent_t a, b; double flops; };
@@ -313,7 +323,7 @@ struct Scratch {
 
 // kernel roles reported by ee_profile_read (their names: kProfNames in capi_query.hip)
 enum { P_PREP = 0, P_EMBT, P_GPATCH, P_EMBV, P_GQKV, P_ATTN, P_GAO, P_LN, P_GUP, P_GDOWN, P_HEAD, P_DECIDE, P_COMPACT, P_GCLS, P_PROBE,
-       P_PAIRIDX, P_PSPLIT, P_HEADOUT, P_EMIT, P_ENSEMBLE, P_QUOTA, P_COUNT };
+       P_PAIRIDX, P_PSPLIT, P_HEADOUT, P_EMIT, P_ENSEMBLE, P_QUOTA, P_CONTROLLER, P_COUNT };
 
 struct ProfScope {
     ee_handle* h;

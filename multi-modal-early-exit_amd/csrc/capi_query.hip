@@ -1,5 +1,7 @@
 // What reads the last forward of a handle back (ee_profile*, ee_stream_next, ee_last_stage_counts, ee_last_flops, ee_last_layer_plan, ee_suggest_probe_mask)
 // and the one-line setters that arm the next one (ee_set_*).
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -36,6 +38,8 @@ const char* const kProfNames[] = {
     // (not nested) ee_set_ensemble: one launch between every exit's head and its decide launch
     "exit_ensemble|exit_ensemble_kernel",
     "exit_quota_rank|exit_quota_crit_kernel+exit_quota_rank_kernel",
+    // (not nested) ee_set_controller: two launches behind the final exit's decide launch
+    "controller|audit_tally_kernel+controller_step_kernel",
 };
 static_assert(sizeof(kProfNames) / sizeof(kProfNames[0]) == P_COUNT, "one name per profile role");
 
@@ -45,6 +49,18 @@ int read_stage_counts(ee_handle* h, void* stream, int n, std::vector<StageCounts
     sc.resize(n);
     HIP_OK(h, hipMemcpy(sc.data(), h->counts, sizeof(StageCounts) * n, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// a device array of the controller's, replaced: the old one leaves the handle's allocations and is freed (the caller has synchronised)
+template <typename T>
+int ctl_realloc(ee_handle* h, T** p, size_t count) {
+    if (*p) {
+        auto it = std::find(h->allocs.begin(), h->allocs.end(), static_cast<void*>(*p));
+        if (it != h->allocs.end()) h->allocs.erase(it);
+        (void)hipFree(*p);
+        *p = nullptr;
+    }
+    return count ? dev_alloc(h, p, count) : 0;
 }
 
 }  // namespace
@@ -164,6 +180,9 @@ int ee_set_criterion(ee_handle* h, int32_t criterion) {
     if (criterion == MMEE_CRIT_PATIENCE && h->quota_mode != MMEE_QUOTA_OFF)
         return fail(h, "ee_set_criterion: MMEE_CRIT_PATIENCE while quotas are set: PABEE's decision carries per-document state, no rank is defined for it "
                        "(ee_set_quotas(h, NULL, 0, 0) first)");
+    if (h->ctl_on && criterion != h->cfg.criterion)
+        return fail(h, "ee_set_criterion: a controller is set: its path is ordered for the direction of the criterion it was set under, and the "
+                       "patience criterion has no threshold to steer (ee_set_controller(h, NULL, ...) first)");
     h->cfg.criterion = criterion;      // read by the decide kernel's arguments of every later ee_forward
     return 0;
 }
@@ -226,6 +245,8 @@ int ee_set_audit(ee_handle* h, uint64_t cut, uint32_t seed, int32_t slot_base) {
             if (g.exec)
                 return fail(h, "ee_set_audit: the handle holds captured graphs: a graph's launch list is the one of its capture, and audited calls "
                                "are eager (ee_graph_destroy them first)");
+    if (!cut && h->ctl_on)
+        return fail(h, "ee_set_audit: a controller is set: the audit is the sample its loss is counted on (ee_set_controller(h, NULL, ...) first)");
     if (cut && !h->audit_delivered) {
         int* d = nullptr;
         if (dev_alloc(h, &d, (size_t)h->cfg.max_docs)) return 1;
@@ -236,6 +257,90 @@ int ee_set_audit(ee_handle* h, uint64_t cut, uint32_t seed, int32_t slot_base) {
 }
 
 int ee_has_audit(const ee_handle* h) { return h && h->audit_cut ? 1 : 0; }
+
+int ee_set_controller(ee_handle* h, const double* path, int32_t V, double alpha, double gamma, double p0, uint32_t seed, int32_t log_cap) {
+    if (!h) return 1;
+    if (!path) { h->ctl_on = false; return 0; }                       // the arrays stay until the next controller or ee_destroy
+    const ee_config& c = h->cfg;
+    const int E1 = c.n_embedding_exits + c.n_encoder_exits + 1;
+    for (const auto& g : h->graphs)
+        if (g.exec)
+            return fail(h, "ee_set_controller: the handle holds captured graphs: a graph's launch list is the one of its capture, and controlled calls "
+                           "are eager (not built; ee_graph_destroy them first)");
+    if (!h->audit_cut)
+        return fail(h, "ee_set_controller: no audit is set: the controller's loss is counted on the audited sample (ee_set_audit with cut > 0 first)");
+    if (c.criterion == MMEE_CRIT_PATIENCE)
+        return fail(h, "ee_set_controller: a handle under MMEE_CRIT_PATIENCE: PABEE has no threshold for the controller to steer (not built)");
+    if (h->rule != MMEE_RULE_PLAIN)
+        return fail(h, "ee_set_controller: a handle under MMEE_RULE_STREAK / MMEE_RULE_EITHER (rule %d): the controller steers the thresholds of the "
+                       "plain rule (not built; ee_set_exit_rule(h, MMEE_RULE_PLAIN) first)", h->rule);
+    if (c.use_lte) return fail(h, "ee_set_controller: a use_lte handle: the learning-to-exit decision reads another score (not built)");
+    // (quotas need no refusal of their own: a controller needs an audit, and ee_set_audit / ee_set_quotas refuse each other)
+    if (E1 < 2 || E1 > kCtlMaxE1) return fail(h, "ee_set_controller: the handle has E1 = %d exits, need 2 <= E1 <= %d", E1, kCtlMaxE1);
+    if (V < 2 || V > (1 << 20)) return fail(h, "ee_set_controller: V = %d vectors, a path needs 2 <= V <= 2^20", V);
+    if (!(alpha > 0.0 && alpha < 1.0)) return fail(h, "ee_set_controller: alpha = %g, the risk level must lie in (0, 1)", alpha);
+    if (!(gamma > 0.0) || !std::isfinite(gamma)) return fail(h, "ee_set_controller: gamma = %g, the step must be positive and finite", gamma);
+    if (!(p0 >= 0.0 && p0 <= (double)(V - 1))) return fail(h, "ee_set_controller: p0 = %g outside [0, V - 1 = %d]", p0, V - 1);
+    if (log_cap < 0 || log_cap > (1 << 24)) return fail(h, "ee_set_controller: log_cap = %d outside [0, 2^24]", log_cap);
+    for (size_t i = 0; i < (size_t)V * E1; ++i)
+        if (!std::isfinite(path[i]))
+            return fail(h, "ee_set_controller: path[%zu][%zu] = %g is not finite", i / E1, i % E1, path[i]);
+    HIP_OK(h, hipDeviceSynchronize());                                // an earlier forward may still read the arrays that are replaced
+    const int W = controller_log_words(E1);
+    if (ctl_realloc(h, &h->ctl_path, (size_t)V * E1) || ctl_realloc(h, &h->ctl_log, (size_t)log_cap * W)) { h->ctl_on = false; return 1; }
+    if (!h->ctl_thr_dev &&
+        (dev_alloc(h, &h->ctl_thr_dev, (size_t)E1) || dev_alloc(h, &h->ctl_state, (size_t)kCtlStateWords) ||
+         dev_alloc(h, &h->ctl_tally, (size_t)controller_tally_words(E1)))) { h->ctl_on = false; return 1; }
+    std::vector<double> thr(E1);
+    controller_thresholds(path, V, E1, p0, crit_sign(c.criterion), thr.data());      // the first call's, by the function the step kernel runs
+    long long state[kCtlStateWords] = {0, 0, 0, 0, 0};
+    memcpy(&state[0], &p0, sizeof(double));
+    HIP_OK(h, hipMemcpy(h->ctl_path, path, sizeof(double) * (size_t)V * E1, hipMemcpyHostToDevice));
+    HIP_OK(h, hipMemcpy(h->ctl_thr_dev, thr.data(), sizeof(double) * E1, hipMemcpyHostToDevice));
+    HIP_OK(h, hipMemcpy(h->ctl_state, state, sizeof(state), hipMemcpyHostToDevice));
+    h->ctl_V = V; h->ctl_alpha = alpha; h->ctl_gamma = gamma; h->ctl_seed = seed; h->ctl_log_cap = log_cap; h->ctl_calls = 0;
+    h->ctl_on = true;
+    return 0;
+}
+
+int ee_has_controller(const ee_handle* h) { return h && h->ctl_on ? 1 : 0; }
+
+int ee_controller_state(ee_handle* h, double* p, int64_t* calls, int64_t* steps, int64_t* sampled_sum, int64_t* disagree_sum, double* thr_out,
+                        void* stream) {
+    if (!h) return 1;
+    if (!h->ctl_on) return fail(h, "ee_controller_state: no controller is set (ee_set_controller)");
+    const int E1 = h->cfg.n_embedding_exits + h->cfg.n_encoder_exits + 1;
+    HIP_OK(h, hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
+    long long state[kCtlStateWords];
+    HIP_OK(h, hipMemcpy(state, h->ctl_state, sizeof(state), hipMemcpyDeviceToHost));
+    if (thr_out) HIP_OK(h, hipMemcpy(thr_out, h->ctl_thr_dev, sizeof(double) * E1, hipMemcpyDeviceToHost));
+    if (p) memcpy(p, &state[0], sizeof(double));
+    if (calls) *calls = state[1];
+    if (steps) *steps = state[2];
+    if (sampled_sum) *sampled_sum = state[3];
+    if (disagree_sum) *disagree_sum = state[4];
+    return 0;
+}
+
+int ee_controller_log(ee_handle* h, int64_t* rows_out, int32_t cap, int32_t* n, void* stream) {
+    if (!h || !n) return fail(h, "ee_controller_log: null argument");
+    if (!h->ctl_on) return fail(h, "ee_controller_log: no controller is set (ee_set_controller)");
+    if (cap < 0 || (cap > 0 && !rows_out)) return fail(h, "ee_controller_log: cap = %d rows without a buffer", cap);
+    const int E1 = h->cfg.n_embedding_exits + h->cfg.n_encoder_exits + 1, W = controller_log_words(E1);
+    HIP_OK(h, hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
+    long long calls = 0;
+    HIP_OK(h, hipMemcpy(&calls, h->ctl_state + 1, sizeof(calls), hipMemcpyDeviceToHost));
+    const long long held = std::min<long long>(calls, h->ctl_log_cap);
+    const int take = (int)std::min<long long>(held, cap);
+    *n = (int32_t)held;                                               // the rows the ring holds; the last `take` of them are copied, oldest first
+    std::vector<long long> ring((size_t)held * W);                    // one copy of the rows the ring holds, put in order on the host
+    if (held) HIP_OK(h, hipMemcpy(ring.data(), h->ctl_log, sizeof(long long) * ring.size(), hipMemcpyDeviceToHost));
+    for (int j = 0; j < take; ++j) {
+        const long long call = calls - take + j;
+        memcpy(rows_out + (size_t)j * W, ring.data() + (size_t)(call % h->ctl_log_cap) * W, sizeof(long long) * W);
+    }
+    return 0;
+}
 
 int ee_audit_selected(uint64_t cut, uint32_t seed, int32_t slot) { return audit_selected(cut, seed, slot) ? 1 : 0; }
 
@@ -301,6 +406,9 @@ int ee_set_exit_rule(ee_handle* h, int32_t rule) {
     if (rule != MMEE_RULE_PLAIN && h->quota_mode != MMEE_QUOTA_OFF)
         return fail(h, "ee_set_exit_rule: rule %d while quotas are set: MMEE_RULE_STREAK / MMEE_RULE_EITHER carry per-document state, no rank is defined "
                        "for them (ee_set_quotas(h, NULL, 0, 0) first)", rule);
+    if (rule != MMEE_RULE_PLAIN && h->ctl_on)
+        return fail(h, "ee_set_exit_rule: rule %d while a controller is set: the controller steers the thresholds of the plain rule, and its replay "
+                       "(ee_rolling_control) knows no other (ee_set_controller(h, NULL, ...) first)", rule);
     h->rule = rule;                    // picks the decide kernel of every later ee_forward / ee_graph_capture
     return 0;
 }

@@ -221,6 +221,28 @@ int ee_quota_scan(const double* table, double sign, int32_t E1, int32_t N, const
     return launch_status(nullptr, who);
 }
 
+int ee_rolling_control(const double* table, double sign, const uint8_t* bad, int32_t E1, int32_t N, const double* path, int32_t V, uint64_t cut,
+                       uint32_t seed, double alpha, double gamma, double p0, int32_t G, int32_t* exits, int64_t* log, double* p_out, void* stream) {
+    const char* who = "ee_rolling_control";
+    if (!table || !bad || !path || !exits || !log) return fail(nullptr, "%s: NULL argument (table, bad, path, exits and log are required; p_out may be NULL)", who);
+    if (E1 < 2 || E1 > kCtlMaxE1) return fail(nullptr, "%s: E1 = %d, need 2 <= E1 <= %d", who, E1, kCtlMaxE1);
+    if (N < 1 || N >= (1 << 28)) return fail(nullptr, "%s: N = %d, need 1 <= N < 2^28", who, N);
+    if (G < 1) return fail(nullptr, "%s: G = %d, a group holds at least one document", who, G);
+    if (V < 2 || V > (1 << 20)) return fail(nullptr, "%s: V = %d vectors, a path needs 2 <= V <= 2^20", who, V);
+    if (sign != 1.0 && sign != -1.0) return fail(nullptr, "%s: sign is +1 or -1", who);
+    if (cut < 1 || cut > (1ull << 32)) return fail(nullptr, "%s: cut %llu outside [1, 2^32]", who, (unsigned long long)cut);
+    if (!(alpha > 0.0 && alpha < 1.0)) return fail(nullptr, "%s: alpha = %g, the risk level must lie in (0, 1)", who, alpha);
+    if (!(gamma > 0.0) || !std::isfinite(gamma)) return fail(nullptr, "%s: gamma = %g, the step must be positive and finite", who, gamma);
+    if (!(p0 >= 0.0 && p0 <= (double)(V - 1))) return fail(nullptr, "%s: p0 = %g outside [0, V - 1 = %d]", who, p0, V - 1);
+    if (!have_device(who)) return 1;
+    RollingControlArgs a{};
+    a.table = table; a.bad = bad; a.path = path; a.E1 = E1; a.N = N; a.V = V; a.G = G > N ? N : G;
+    a.sign = sign; a.alpha = alpha; a.gamma = gamma; a.p0 = p0; a.cut = cut; a.seed = seed;
+    a.exits = exits; a.log = reinterpret_cast<long long*>(log); a.p_out = p_out;
+    launch_rolling_control(a, reinterpret_cast<hipStream_t>(stream));
+    return launch_status(nullptr, who);
+}
+
 int ee_cascade_select(const float* logits, const int32_t* exit_layer, const int32_t* orig, int32_t n, int32_t K, int32_t final_exit,
                       int32_t criterion, double threshold, int32_t* next_orig, int32_t* count_dev, double* crit_out, void* stream) {
     if (n < 0 || K < 1 || final_exit < 0 || !count_dev || (n > 0 && (!logits || !exit_layer || !next_orig)))

@@ -138,8 +138,10 @@ struct EmitArgs {
 // ee_config.criterion (include/mmee.h MMEE_CRIT_*; capi_internal.h asserts the values agree)
 enum { CRIT_MAX_CONFIDENCE = 0, CRIT_ENTROPY = 1, CRIT_PATIENCE = 2, CRIT_MARGIN = 3, CRIT_GATE = 4 };
 // the direction of a threshold criterion: max-softmax, margin and the gate score leave on crit > thr, entropy on crit < thr; strict, so a NaN never fires
-__host__ __device__ inline bool crit_fires(int criterion, double crit, double thr) { return criterion == CRIT_ENTROPY ? crit < thr : crit > thr; }
+// sign_fires is THE test: the decide kernels reach it through crit_fires, the controller's replay (rolling_control_kernel) by the table's sign
 __host__ __device__ inline double crit_sign(int criterion) { return criterion == CRIT_ENTROPY ? -1.0 : 1.0; }
+__host__ __device__ inline bool sign_fires(double sign, double c, double thr) { return sign < 0.0 ? c < thr : c > thr; }
+__host__ __device__ inline bool crit_fires(int criterion, double crit, double thr) { return sign_fires(crit_sign(criterion), crit, thr); }
 // The gate score (MMEE_CRIT_GATE; include/mmee.h): the 2-way softmax's probability of column 1 ("correctly gated") of the raw float32 gate
 // logits, in float64.  h0 - h1 large: exp overflows to inf and the score is exactly 0; large negative: exactly 1; equal: exactly 0.5.  The one
 // copy the decide kernels (exit_stage.hip) and the table kernel of the dumped-array tools (exit_ops.hip) share, so their bits agree.
@@ -286,6 +288,107 @@ struct AuditArgs {
 };
 // launch_decide (below) takes it as its last argument: non-null picks the AUDIT form of its seven kernels, at every exit of an audited call, the
 // final one included (delivered documents write no result there); null launches the kernels as they were
+
+// Online exit control (ee_set_controller; the definition is in include/mmee.h, behind the audit's): a position p on a path of threshold
+// vectors steps against the disagreement the audit observes.  The three functions below are the one copy the forward's two launches, the
+// replay tool (ee_rolling_control) and the stand-alone hooks share (controller.hip), so their bits agree; ee_set_controller calls the first
+// on the host for the thresholds of the first call.
+constexpr int kCtlMaxE1 = 64;                                         // exits a controller takes (the kernels hold a vector per exit in LDS)
+constexpr int kCtlStateWords = 5;                                     // the device state: p (float64 bits), calls, steps, sampled_sum, disagree_sum
+// the 64-bit words of a log row, and of a tally (sampled, disagree, delivered[E], agree[E]): E = E1 - 1
+__host__ __device__ inline int controller_log_words(int E1) { return 5 + 2 * (E1 - 1) + E1; }
+__host__ __device__ inline int controller_tally_words(int E1) { return 2 + 2 * (E1 - 1); }
+// thr_out[E1] of position p on path (V,E1), V >= 2: below 0 the value that never fires at every exit below the final one; else the lerp between
+// rows i = min(floor(p'), V - 2) and i + 1 at t = p' - i, p' = min(p, V - 1), every product rounded before the add.  The final entry is
+// path[i]'s (path[0]'s below 0); no forward reads it.
+__host__ __device__ inline void controller_thresholds(const double* path, int V, int E1, double p, double sign, double* thr_out) {
+#pragma clang fp contract(off)
+    if (p < 0.0) {
+        for (int e = 0; e < E1 - 1; ++e) thr_out[e] = sign < 0.0 ? -INFINITY : INFINITY;
+        thr_out[E1 - 1] = path[E1 - 1];
+        return;
+    }
+    const double top = (double)(V - 1);
+    const double q = p < top ? p : top;
+    int i = (int)floor(q);
+    if (i > V - 2) i = V - 2;
+    const double t = q - (double)i;
+    const double *a = path + (size_t)i * E1, *b = a + E1;
+    for (int e = 0; e < E1 - 1; ++e) {
+        const double diff = b[e] - a[e];
+        thr_out[e] = a[e] + diff * t;
+    }
+    thr_out[E1 - 1] = a[E1 - 1];
+}
+// p after a call that audited `sampled` documents of which `disagree` were delivered early with another answer than the full model's:
+// unchanged when nobody was sampled, else min(V - 1, p - gamma (disagree / sampled - alpha)), the product rounded before the subtraction
+__host__ __device__ inline double controller_step(double p, long long sampled, long long disagree, double alpha, double gamma, int V) {
+#pragma clang fp contract(off)
+    if (sampled == 0) return p;
+    const double loss = (double)disagree / (double)sampled;
+    const double move = gamma * (loss - alpha);
+    const double q = p - move;
+    const double top = (double)(V - 1);
+    return q < top ? q : top;
+}
+// argmax of the row x(0 .. K-1), x a callable int -> float or double: the lowest index on ties; a row without a maximum (a NaN in it) counts
+// as K - 1, exactly like sweep.first_argmax
+template <typename Row>
+__host__ __device__ inline int row_first_argmax(Row x, int K) {
+    auto best = x(0);
+    bool nan = best != best;
+    int am = 0;
+    for (int k = 1; k < K; ++k) {
+        const auto v = x(k);
+        nan = nan || v != v;
+        if (v > best) { best = v; am = k; }
+    }
+    return nan ? K - 1 : am;
+}
+// audit_tally_kernel: what the audit saw in one call.  The final stage (counts, doc_orig, the policy rows the final decide launch read and its
+// temperature), the delivered marks, the call's results and the audit's selection; tally[controller_tally_words(E1)] is written, not added to
+struct AuditTallyArgs {
+    const StageCounts* counts;       // the final stage
+    const int* doc_orig;
+    const float* pol_logits;         // [n_docs][K]: the rows the final decide launch read
+    double temp;                     //   and scaled by, (float)((double)z / temp), as it writes them
+    int K, B, E1;                    // B: the call's documents (the slots the hash runs over)
+    const int* delivered;            // [B] by original slot: the AUDIT decide kernels' marks
+    const float* out_logits;         // (B,K)
+    const int* out_exit;             // (B)
+    unsigned long long cut;
+    unsigned seed;
+    int slot_base;
+    long long* tally;
+};
+void launch_audit_tally(const AuditTallyArgs& a, hipStream_t s);
+// controller_step_kernel: the step behind a tally.  state[kCtlStateWords]; thr[E1] holds the thresholds the call ran with and receives the
+// next call's; log: the ring of log_cap rows of controller_log_words(E1) words, or null
+struct ControllerStepArgs {
+    const double* path;              // (V,E1) on the device
+    int V, E1;
+    double sign, alpha, gamma;
+    long long* state;
+    const long long* tally;
+    double* thr;
+    long long* log;
+    int log_cap;
+};
+void launch_controller_step(const ControllerStepArgs& a, hipStream_t s);
+// rolling_control_kernel (ee_rolling_control): the same loop on a dumped criterion table, groups of G consecutive documents as the calls
+struct RollingControlArgs {
+    const double* table;             // (E1,N)
+    const unsigned char* bad;        // (E1,N) 0 / 1: delivering document n at exit e is a loss
+    const double* path;              // (V,E1)
+    int E1, N, V, G;
+    double sign, alpha, gamma, p0;
+    unsigned long long cut;
+    unsigned seed;
+    int* exits;                      // (N)
+    long long* log;                  // (ceil(N / G), controller_log_words(E1))
+    double* p_out;                   // [1] the position after the last group, or null
+};
+void launch_rolling_control(const RollingControlArgs& a, hipStream_t s);
 // ee_quota_scan (exit_ops.hip): the same decision on a criterion table (E1,N), consecutive groups of G documents ranked independently
 struct QuotaScanArgs {
     const double* table;             // (E1,N) on the device

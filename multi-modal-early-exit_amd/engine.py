@@ -89,6 +89,39 @@ class ResultStream:
         return ResultChunk(e.value, *unpack_stream_rows(words, eng.K))
 
 
+@dataclass
+class ControllerLog:
+    """The log of a controller (``EarlyExitEngine.controller_log``) or of its replay (``risk.rolling_control``): one row per call (per group),
+    numpy on the host.  ``loss = disagree / sampled`` of the rows that sampled anybody is what the promise of include/mmee.h bounds."""
+    call: np.ndarray                        # (T,) int64
+    p_before: np.ndarray                    # (T,) float64: the position the call ran at
+    p_after: np.ndarray                     # (T,) float64
+    sampled: np.ndarray                     # (T,) int64: audited documents of the call
+    disagree: np.ndarray                    # (T,) int64: of those, delivered early with another answer than the full model's
+    delivered: np.ndarray                   # (T,E) int64: audited documents delivered at exit e
+    agree: np.ndarray                       # (T,E) int64
+    thresholds: np.ndarray                  # (T,E1) float64: the thresholds the call ran with
+
+    @staticmethod
+    def from_rows(rows, E1: int) -> "ControllerLog":
+        """From (T, controller_log_words(E1)) int64 words as the device writes them (include/mmee.h)."""
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, capi.controller_log_words(E1))
+        E = E1 - 1
+        f = lambda a: np.ascontiguousarray(a).view(np.float64)
+        return ControllerLog(r[:, 0].copy(), f(r[:, 1]), f(r[:, 2]), r[:, 3].copy(), r[:, 4].copy(), r[:, 5:5 + E].copy(),
+                             r[:, 5 + E:5 + 2 * E].copy(), f(r[:, 5 + 2 * E:]).reshape(-1, E1))
+
+    @property
+    def loss(self) -> np.ndarray:
+        """(T,) disagree / sampled, NaN where nobody was sampled."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.sampled > 0, self.disagree / np.maximum(self.sampled, 1), np.nan)
+
+    def excess(self, alpha: float) -> np.ndarray:
+        """(T,) running sum of ``loss - alpha`` over the rows that sampled anybody: what stays at or below ``start / gamma + 1 - alpha``."""
+        return np.cumsum(np.where(self.sampled > 0, np.nan_to_num(self.loss) - float(alpha), 0.0))
+
+
 def _require_torch_cuda(device=None):
     if torch is None:
         raise capi.MMEEUnavailable(f"PyTorch-ROCm is required for device tensors: {_torch_err}")
@@ -161,6 +194,8 @@ class EarlyExitEngine:
         self.ensemble = None                # set_ensemble(): the host copies of (weights, bias), or None
         self.quotas, self.quota_mode = None, None      # set_quotas(): the per-exit quotas and "exact" / "at_least", or None
         self.audit = None                   # set_audit(): (fraction, seed, slot_base), or None
+        self.controller = None              # set_controller(): dict(path, alpha, gamma, start, seed, log_cap), or None
+        self._ctl_calls = 0                 # controlled calls since set_controller: call t audits under seed + t
         self.patience = None
         if ec.patience is not None:
             self.set_patience(ec.patience)
@@ -331,11 +366,15 @@ class EarlyExitEngine:
             raise ValueError("quota_mode= goes with quotas= or quota_fractions= (set_quotas(None) switches quotas off)")
         if audit_fraction is not None or audit_seed is not None:
             self.forward_audit_args(audit_fraction, audit_seed)
+        controlled = self.controller is not None and not dump_all      # the library's own rule: a dump-all call ignores the controller
+        if controlled and thresholds is not None:
+            raise ValueError("forward(thresholds=) on a controlled engine: the controller's position decides the thresholds "
+                             "(controller_state()[\"thresholds\"] shows them; set_controller(None) switches it off)")
         if thresholds is None:
             thresholds = self.exit_config.global_threshold
         thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float64).reshape(-1), (E + 1,)).copy() \
             if np.ndim(thresholds) else np.full((E + 1,), float(thresholds))
-        thr_c = (C.c_double * (E + 1))(*thr.tolist())
+        thr_c = None if controlled else (C.c_double * (E + 1))(*thr.tolist())
         tmp_c = None
         if temperatures is not None:
             tm = np.asarray(temperatures, dtype=np.float64).reshape(-1)
@@ -434,12 +473,18 @@ class EarlyExitEngine:
                                      p(out_logits), p(out_exit), p(out_conf), p(all_logits), p(all_crit),
                                      p(head_logits), p(head_crit), p(hidden), stream)
         capi.check(rc, self._h, "ee_forward")
+        ctl_call = self._ctl_calls
+        if controlled:                                 # the library has used this call's seed: count it before anything else can raise
+            self._ctl_calls += 1
         self._keepalive = (ids, am, bb, px, tt, ps, emb, hm)   # borrowed by the enqueued kernels until the stream drains
         if validate:
             self.stage_counts()                        # synchronises; raises on out-of-range inputs
         mask = None
         if self.audit and not dump_all:                # the library's own rule: a dump-all call ignores the audit
-            mask = torch.from_numpy(self.audit_mask(B, *self.audit)).to(dev, non_blocking=True)
+            fraction, seed, slot_base = self.audit
+            if controlled:                             # call t of a controller audits under seed + t
+                seed = (self.controller["seed"] + ctl_call) & 0xFFFFFFFF
+            mask = torch.from_numpy(self.audit_mask(B, fraction, seed, slot_base)).to(dev, non_blocking=True)
         return EngineOutput(out_logits, out_exit, out_conf, all_logits, all_crit, head_logits, head_crit, hidden, hs, att, mask)
 
     __call__ = forward
@@ -738,6 +783,78 @@ class EarlyExitEngine:
         x = (x * np.uint64(0xC2B2AE35)) & m
         x ^= x >> np.uint64(16)
         return x < np.uint64(cut)
+
+    def set_controller(self, path=None, *, alpha: Optional[float] = None, gamma: Optional[float] = None, start: Optional[float] = None,
+                       seed: int = 0, log_cap: int = 1024):
+        """Online exit control of every later forward (ee_set_controller; the definition, its promise and its limit are in include/mmee.h): the
+        thresholds follow the disagreement the engine's own audit observes, between forwards, on the device.  ``path``: a ``(V,E1)`` array
+        of threshold vectors, most conservative first; a ``RiskResult`` (its candidates are the path, ``start`` defaults to its selected
+        index); or a ``SearchResult`` / ``RefineResult`` (through ``risk.path_from_front``).  ``alpha``: the level the audited disagreement
+        rate is held to on average; ``gamma``: the step of the position per unit of excess loss; ``start``: the position of the first call
+        (default 0, the most conservative vector); ``seed``: call t audits under ``seed + t``; ``log_cap``: rows of the device ring log
+        ``controller_log()`` downloads.  Needs ``set_audit`` first.  ``None`` switches the controller off: the engine then issues the launches
+        and returns the bits it did before.  Refused under the patience criterion, the combined exit rules, learning-to-exit and quotas, with
+        ``forward_stream`` and ``capture``; ``forward(thresholds=)`` raises while it is set; dump-all calls ignore it."""
+        if path is None:
+            capi.check(self.lib.ee_set_controller(self._h, None, 0, 0.0, 0.0, 0.0, 0, 0), self._h, "ee_set_controller")
+            self.controller = None
+            return None
+        from .risk import RiskResult, path_from_front
+        from .sweep import RefineResult, SearchResult
+        if isinstance(path, RiskResult):
+            if start is None and path.selected >= 0:
+                start = float(path.selected)
+            path = path.thresholds
+        elif isinstance(path, (SearchResult, RefineResult)):
+            path = path_from_front(path)
+        if alpha is None or gamma is None:
+            raise ValueError("set_controller: alpha= (the risk level) and gamma= (the step) are required")
+        th = np.ascontiguousarray(np.asarray(path, dtype=np.float64))
+        E1 = self.E + 1
+        if th.ndim != 2 or th.shape[1] != E1 or th.shape[0] < 2:
+            raise ValueError(f"set_controller: path is an array (V,{E1}), V >= 2, most conservative first")
+        sign = -1.0 if self.exit_config.inference_strategy.value == "entropy" else 1.0
+        if E1 > 1 and not np.all(sign * np.diff(th[:, :E1 - 1], axis=0) <= 0):
+            raise ValueError("set_controller: path must move towards the aggressive side at every exit, never back: falling for max_confidence / "
+                             "margin / gate, rising for entropy")
+        start = 0.0 if start is None else float(start)
+        seed, log_cap = int(seed), int(log_cap)
+        if not 0 <= seed < 2 ** 32:
+            raise ValueError(f"set_controller: seed {seed} is not a 32-bit unsigned value")
+        V = int(th.shape[0])
+        capi.check(self.lib.ee_set_controller(self._h, th.ctypes.data_as(C.POINTER(C.c_double)), V, float(alpha), float(gamma), start, seed, log_cap),
+                   self._h, "ee_set_controller")
+        self.controller = dict(path=th, alpha=float(alpha), gamma=float(gamma), start=start, seed=seed, log_cap=log_cap)
+        self._ctl_calls = 0
+        return self.controller
+
+    def has_controller(self) -> bool:
+        return bool(self.lib.ee_has_controller(self._h))
+
+    def controller_state(self) -> dict:
+        """The controller's position and sums (ee_controller_state; synchronises the stream): ``position``, ``calls``, ``steps`` (calls that
+        sampled anybody), ``sampled``, ``disagree`` (sums over them) and ``thresholds`` (E1,), the vector the NEXT call runs with."""
+        p = C.c_double()
+        n = [C.c_int64() for _ in range(4)]
+        thr = (C.c_double * (self.E + 1))()
+        with torch.cuda.device(self.device):
+            capi.check(self.lib.ee_controller_state(self._h, C.byref(p), *[C.byref(x) for x in n], thr,
+                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), self._h, "ee_controller_state")
+        return dict(position=p.value, calls=n[0].value, steps=n[1].value, sampled=n[2].value, disagree=n[3].value,
+                    thresholds=np.array(list(thr), dtype=np.float64))
+
+    def controller_log(self) -> "ControllerLog":
+        """The device ring log, oldest row first (ee_controller_log; synchronises the stream): one row per controlled call, the latest
+        ``log_cap`` of them.  The one download."""
+        if self.controller is None:
+            raise capi.MMEEError("controller_log: no controller is set (set_controller)")
+        W, cap = capi.controller_log_words(self.E + 1), self.controller["log_cap"]
+        rows = np.zeros((max(cap, 1), W), dtype=np.int64)
+        n = C.c_int32(0)
+        with torch.cuda.device(self.device):
+            capi.check(self.lib.ee_controller_log(self._h, rows.ctypes.data_as(C.c_void_p), cap, C.byref(n),
+                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)), self._h, "ee_controller_log")
+        return ControllerLog.from_rows(rows[:n.value], self.E + 1)
 
     def clock_stamp(self):
         """Device tensor of capi.CLOCK_STAMP_WORDS int64: one (s_memtime, s_memrealtime) pair per CU as seen by one-wave workgroups enqueued on

@@ -94,6 +94,17 @@ class MicroBatchedEngine:
     def has_audit(self) -> bool:
         return self.engines[0].has_audit()
 
+    def set_controller(self, path=None, **kw):
+        """Online exit control (``EarlyExitEngine.set_controller``) is one position stepped call by call on one handle; over micro-batches it is
+        not built.  ``None`` is accepted (nothing is set)."""
+        if path is not None:
+            raise ValueError("a controller over micro-batches is not built: the slices run on separate handles, each of which would step a position "
+                             "of its own (use EarlyExitEngine)")
+        return None
+
+    def has_controller(self) -> bool:
+        return any(e.has_controller() for e in self.engines)
+
     audit_mask = staticmethod(EarlyExitEngine.audit_mask)
     forward_audit_args = EarlyExitEngine.forward_audit_args
 
@@ -110,6 +121,9 @@ class MicroBatchedEngine:
             raise ValueError("low_latency is a small-batch mode of EarlyExitEngine; MicroBatchedEngine runs large batches")
         if any(kw.get(k) is not None for k in ("quotas", "quota_fractions", "quota_mode")):
             raise ValueError(self._NO_QUOTAS)
+        if self.has_controller():
+            raise ValueError("a handle of this MicroBatchedEngine has a controller set: a controller over micro-batches is not built "
+                             "(set_controller(None) on it, or use EarlyExitEngine)")
         audit_fraction, audit_seed = kw.pop("audit_fraction", None), kw.pop("audit_seed", None)
         if audit_fraction is not None or audit_seed is not None:
             self.forward_audit_args(audit_fraction, audit_seed)

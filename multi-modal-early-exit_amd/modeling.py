@@ -204,6 +204,11 @@ class LayoutLMv3EEForSequenceClassification:
         ``(weights, bias)`` pair, or ``None`` to clear it.  Handed to every handle the model runs on."""
         return self.engine.set_ensemble(ensemble)
 
+    def set_controller(self, path=None, **kw):
+        """Online exit control of every later ``early_exit`` (``EarlyExitEngine.set_controller``; needs ``engine.set_audit`` first): the thresholds
+        follow the audited disagreement with the full model.  One handle: refused on a model that runs on micro-batches."""
+        return self.engine.set_controller(path, **kw)
+
     def _is_patience(self) -> bool:
         want = self.config.exit_config["inference_strategy"]
         return str(getattr(want, "value", want)) == "patience"
@@ -359,7 +364,7 @@ class LayoutLMv3EEForSequenceClassification:
             kw["audit_fraction"] = audit_fraction
         if audit_seed is not None:
             kw["audit_seed"] = audit_seed
-        if thresholds is None:
+        if thresholds is None and getattr(self.engine, "controller", None) is None:      # a controller decides the thresholds itself
             thresholds = self.config.exit_config["global_threshold"]
         self._small_batch_schedule(pixel_values, kw)
         return self._run(dict(input_ids=input_ids, attention_mask=attention_mask, bbox=bbox, pixel_values=pixel_values,

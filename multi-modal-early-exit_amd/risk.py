@@ -12,6 +12,10 @@ The promise holds if the calibration documents are exchangeable with the documen
 the calibration table.  A front searched on the same table does not qualify: split the table, search on one part, certify on the other.  The
 risk is marginal over all documents; a document that runs to the final exit contributes its final-exit loss.
 
+``rolling_control`` replays the online controller (``EarlyExitEngine.set_controller``; include/mmee.h, "Online exit control") on a dumped
+table before deployment: the same kernels' arithmetic, group by group, in one launch.  Its promise needs no exchangeability -- it is an
+inequality on the observed sequence -- and is about the audited estimate only.
+
 Not built: the WSR betting bound, conditional (per-exit) risk control, several risks at once, a ranked scorer for millions of vectors, and
 patience / rule / learning-to-exit / gate decisions (a gate or LTE table can be passed as a precomputed table, with plain-threshold semantics).
 """
@@ -25,7 +29,7 @@ from typing import Optional
 import numpy as np
 
 from . import capi
-from .engine import _require_torch_cuda, torch
+from .engine import ControllerLog, _require_torch_cuda, torch
 from .policy import _f64_on, _on, _ptr, threshold_criterion
 from .sweep import RefineResult, SearchResult, _stream, csf_table, final_predictions
 
@@ -230,3 +234,84 @@ def risk_control(logits, references=None, *, criterion="max_confidence", risk: s
                       risk=loss_sum / (float(N) * LOSS_ONE), pvalue=pval.cpu().numpy(), certified=cert.cpu().numpy().astype(bool),
                       n_certified=int(picked_h[0]), selected=int(picked_h[1]), num_samples=N, alpha=float(alpha), delta=float(delta), bound=bound,
                       method=method, binary=binary, hist=None if hist is None else hist.cpu().numpy())
+
+
+@dataclass
+class RollingResult:
+    """What ``rolling_control`` replayed: ``exits`` goes unchanged into ``metrics.exit_report(exits=)``; ``log`` has one row per group."""
+    exits: "torch.Tensor"                   # (N,) int32 on the device: where every document left under its group's thresholds
+    log: ControllerLog                      # numpy on the host
+    position: float                         # the position after the last group
+    alpha: float
+    gamma: float
+    start: float
+    group_size: int
+
+    def bound(self) -> float:
+        """``start / gamma + 1 - alpha``: what ``log.excess(alpha)`` stays at or below at every prefix."""
+        return self.start / self.gamma + 1.0 - self.alpha
+
+
+def rolling_control(logits, path, *, criterion="max_confidence", alpha: float, gamma: float, group_size: int, fraction: float, seed: int = 0,
+                    start: float = 0.0, bad=None, device=None) -> RollingResult:
+    """Replay online exit control on a dumped table (ee_rolling_control; the definition is in include/mmee.h): consecutive groups of
+    ``group_size`` documents play the forwards of an engine under ``set_audit(fraction)`` and ``set_controller(path, alpha=, gamma=, start=,
+    seed=)``; group t audits its slots under ``seed + t``.  One launch, with the functions the forward's own launches call, so a forward's
+    ``controller_log()`` and this replay of its concatenated dump-all table agree bit for bit.
+
+    ``logits`` (E1,N,K), or a precomputed criterion table (E1,N) -- real thresholds' scale, e.g. ``sweep.gate_table`` -- with ``bad=``.
+    ``path``: (V,E1), a ``RiskResult`` (its candidates; pass ``start=result.selected`` to begin where it certified) or a
+    ``SearchResult`` / ``RefineResult`` through ``path_from_front``.  ``bad`` (E1,N) 0 / 1: delivering document n at exit e is a loss; ``None`` builds the
+    consistency table on the device -- ``csf_table``'s ``correct`` against ``final_predictions``, as ``risk_control(risk="consistency")`` --
+    and any other table is an offline what-if."""
+    st = threshold_criterion(criterion)
+    sign = -1.0 if st.value == "entropy" else 1.0
+    if isinstance(path, RiskResult):
+        path = path.thresholds
+    elif isinstance(path, (SearchResult, RefineResult)):
+        path = path_from_front(path)
+    if not (0.0 < float(alpha) < 1.0):
+        raise ValueError("alpha must lie in (0, 1)")
+    if not (float(gamma) > 0.0 and math.isfinite(float(gamma))):
+        raise ValueError("gamma must be positive and finite")
+    if int(group_size) < 1:
+        raise ValueError("group_size: a group holds at least one document")
+    cut = capi.audit_cut(fraction)
+    if cut < 1:
+        raise ValueError("fraction 0 audits nobody: the controller would never step")
+    lib = capi.load()
+    dev = _require_torch_cuda(device)
+    L = _f64_on(dev, logits)
+    if L.dim() == 3:
+        table, corr = csf_table(L, final_predictions(L, device=dev) if bad is None else None, criterion=st, device=dev)
+        if bad is None:
+            bad = corr == 0
+    elif L.dim() == 2:
+        table = L.contiguous()
+        if bad is None:
+            raise ValueError("a precomputed criterion table (E1,N) needs bad= (E1,N): there are no logits to build the consistency table from")
+    else:
+        raise ValueError("logits (E1,N,K), or a criterion table (E1,N) with bad=")
+    E1, N = (int(x) for x in table.shape)
+    bad_t = (_on(dev, bad, torch.uint8) != 0).to(torch.uint8).contiguous()
+    if tuple(bad_t.shape) != (E1, N):
+        raise ValueError(f"bad: a 0 / 1 table ({E1},{N})")
+    th = np.ascontiguousarray(np.asarray(path, dtype=np.float64))
+    if th.ndim != 2 or th.shape[1] != E1 or th.shape[0] < 2:
+        raise ValueError(f"path: an array (V,{E1}), V >= 2, most conservative first")
+    if not np.all(np.isfinite(th)):
+        raise ValueError("path: every entry must be finite")
+    V, G = int(th.shape[0]), min(int(group_size), N)
+    if not 0.0 <= float(start) <= V - 1:
+        raise ValueError(f"start {start} outside [0, V - 1 = {V - 1}]")
+    T = (N + G - 1) // G
+    W = capi.controller_log_words(E1)
+    th_dev = torch.from_numpy(th).to(dev)
+    exits = torch.empty((N,), dtype=torch.int32, device=dev)
+    log = torch.empty((T, W), dtype=torch.int64, device=dev)
+    pos = torch.empty((1,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        capi.check(lib.ee_rolling_control(_ptr(table), sign, _ptr(bad_t), E1, N, _ptr(th_dev), V, cut, int(seed) & 0xFFFFFFFF, float(alpha),
+                                          float(gamma), float(start), G, _ptr(exits), _ptr(log), _ptr(pos), _stream()), None, "ee_rolling_control")
+    return RollingResult(exits=exits, log=ControllerLog.from_rows(log.cpu().numpy(), E1), position=float(pos.cpu().numpy()[0]), alpha=float(alpha),
+                         gamma=float(gamma), start=float(start), group_size=G)
