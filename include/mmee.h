@@ -1488,6 +1488,45 @@ typedef struct ee_debug_gemm_routes_args {
 } ee_debug_gemm_routes_args;
 int ee_debug_gemm_routes(const ee_debug_gemm_routes_args* args, float* ms_out, void* stream);
 
+/* The f32 counterpart of ee_debug_gemm_routes: ONE call of launch_gemm_f32 (csrc/gemm_f32.hip) with every operand a forward can set, so that the
+ * kernel can be launched alone as Forward::qkv, layer_rest, beit_rest and run_head launch it (tests/test_gpu_gemm_f32_routes.py).  The arguments
+ * are those every GEMM of a forward starts from (scale 1, the static priority of the odd wave slots) plus the caller's; lda = K, ldc = ldr = N.
+ * Cout[r] = epi((A[row_src ? row_src[r] : r] W^T + bias) * (column < scale_cols ? scale : 1)) * col_scale (+ resid[resid_row_src ? resid_row_src[r] : r]).
+ *   A, W, bias, resid        dev f32: A [rows_A][K], W [N][K], bias [N] or NULL, resid [rows_resid][N] (residual epilogue) or NULL
+ *   Cout                     dev f32 [>= max(M, max_m)][N]; rows >= M keep their bytes
+ *   epi                      0 = bias, 1 = GELU(erf), 2 = + residual, 3 = tanh; no flag bits (ee_debug_gemm keeps the diagnostic ones)
+ *   staging                  0 = the LDS-DMA kernel (what the path runs), 1 = the register-staged kernel
+ *   use_queue                != 0: XCD-local work queues (the hook zeroes the heads), 0: static grid stride
+ *   row_src, rows_A          NULL (dense), or dev int32 [M] into the rows_A rows of A: any order, repeats allowed
+ *   resid_row_src, rows_resid  the same for the residual, independent of row_src (read with the residual epilogue only)
+ *   scale_cols, scale        columns [0, scale_cols) are multiplied by `scale` behind the bias (Q / sqrt(d) of the fused Q | K | V GEMM)
+ *   col_scale                NULL, or f32 [N]: a factor per column behind the epilogue function, in front of the residual (BEiT's lambda)
+ *   max_m, m_on_device       m_on_device != 0: the launch is sized by max_m and the kernel reads M from a device word the hook uploads, as in
+ *                            every forward; the row maps still hold M entries.  m_on_device == 0: max_m is not read, the launch is sized by M.
+ *   wgs_per_cu               workgroups per CU of the persistent grid, 0 = default
+ * M = 0 is legal: the kernel returns without touching anything.  Refused on the host before any device call, each with its own message: args,
+ * A, W or Cout NULL; N or K below 1, N % 128, K % 32; M < 0; epi outside 0 .. 3; staging outside {0, 1}; the residual epilogue without resid, or
+ * resid with another epilogue; scale_cols no multiple of 128 in [0, N] (the kernel decides per 128-column tile side); m_on_device with
+ * max_m < 1 or M > max_m; wgs_per_cu < 0; M rows without a row map and fewer than M rows of A / of the residual.  The row maps are checked
+ * against rows_A / rows_resid on host copies.  Synchronises the stream. */
+typedef struct ee_debug_gemm_f32_args {
+    const float *A, *W, *bias, *resid;
+    float* Cout;
+    int32_t M, N, K, epi;
+    int32_t staging;
+    int32_t use_queue;
+    const int32_t* row_src;
+    int32_t rows_A;
+    const int32_t* resid_row_src;
+    int32_t rows_resid;
+    int32_t scale_cols;
+    float scale;
+    const float* col_scale;
+    int32_t max_m, m_on_device;
+    int32_t wgs_per_cu;
+} ee_debug_gemm_f32_args;
+int ee_debug_gemm_f32(const ee_debug_gemm_f32_args* args, void* stream);
+
 /* Unit-test hook of the fused attention kernels: ONE launch of one kernel of the path on caller-provided DEVICE buffers; no handle.
  *   qkv            f32 [qkv_rows][3 H], H = 64 * heads: Q (already divided by sqrt(d)) | K | V of every row
  *   doc_off        int32 [n_docs + 1], doc_off[0] = 0: the ragged documents; row r of document d is context row doc_off[d] + r

@@ -183,6 +183,13 @@ class DebugGemmRoutesArgs(C.Structure):
                 + [(n, _i32) for n in ("max_m", "m_on_device", "iters")])
 
 
+class DebugGemmF32Args(C.Structure):
+    """ee_debug_gemm_f32_args of include/mmee.h: device pointers (or None), sizes and the epilogue operands."""
+    _fields_ = ([(n, _vp) for n in ("A", "W", "bias", "resid", "Cout")] + [(n, _i32) for n in ("M", "N", "K", "epi", "staging", "use_queue")]
+                + [("row_src", _vp), ("rows_A", _i32), ("resid_row_src", _vp), ("rows_resid", _i32), ("scale_cols", _i32), ("scale", C.c_float),
+                   ("col_scale", _vp)] + [(n, _i32) for n in ("max_m", "m_on_device", "wgs_per_cu")])
+
+
 class CascadeDesc(C.Structure):
     """ee_cascade_desc of include/mmee.h: one array of ee_cascade_gather (device pointers, bytes per row)."""
     _fields_ = [("src", _vp), ("dst", _vp), ("row_bytes", C.c_int64)]
@@ -277,6 +284,7 @@ SYMBOLS = {
     "ee_debug_gemm_split_resid": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp, _i32, _vp, _i32,
                                             _i32, _i32, C.POINTER(C.c_float), _vp]),
     "ee_debug_gemm_routes": (C.c_int, [C.POINTER(DebugGemmRoutesArgs), C.POINTER(C.c_float), _vp]),
+    "ee_debug_gemm_f32": (C.c_int, [C.POINTER(DebugGemmF32Args), _vp]),
     "ee_debug_attn_stamps": (C.c_int, [_vp]),
     "ee_debug_attention": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                      _i32, _i32, _i32, _vp, C.POINTER(_i32), _vp]),

@@ -11,16 +11,12 @@
 using namespace mmee;
 using namespace mmee::capi;
 
-namespace {
-
 // the fields every GEMM of the forward shares; a launch sets its own on top
-GemmArgs forward_gemm_args(int* err_flag) {
+GemmArgs mmee::capi::forward_gemm_args(int* err_flag) {
     GemmArgs g{};
     g.scale = 1.f; g.prio_mode = 1; g.err_flag = err_flag;
     return g;
 }
-
-}  // namespace
 
 void mmee::capi::launch_patch_projection(const PatchProjection& p, int num_cus, hipStream_t s, ee_handle* prof) {
     const int G = p.R / p.P, M = p.B * G * G;

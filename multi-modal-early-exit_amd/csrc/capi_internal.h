@@ -269,6 +269,10 @@ int split_weight_rows(ee_handle* h, const char* who, const float* w, int N, int 
 // row of one patch (P % 4, R % 4) over k-slabs of 32 (C P P % 32).
 inline bool patch_geometry_ok(int C, int R, int P) { return C >= 1 && R >= 1 && P >= 1 && R % P == 0 && (C * P * P) % 32 == 0 && P % 4 == 0 && R % 4 == 0; }
 
+// The fields every GEMM of a forward shares (capi_forward.hip; ee_debug_gemm_f32 starts from them too): scale 1, the static priority of the odd
+// wave slots, the handle's error word.  A launch sets its own on top.
+GemmArgs forward_gemm_args(int* err_flag);
+
 // The patch projection (Conv2d with stride = kernel = a GEMM over flattened patches, HF:75-81): out [B * NP][H] = patches W^T + bias, as
 // ee_forward and ee_debug_patch_project launch it (capi_forward.hip).  w_split given: launch_patch_split writes the patches once as split rows
 // scaled by kSplitScaleX into split_rows ([B * NP][C P P] words) and the split kernel runs the GEMM; otherwise the f32 kernel gathers the

@@ -1,7 +1,7 @@
 // Entry points of libmmee_hip.so that never see a handle: bucket LUT, shader-clock stamps, policy / patience / threshold sweeps, temperature
 // fit, the evaluation report (ee_exit_metrics), result packing, the three launches of a cascade's stage boundary (ee_cascade_select / _gather /
 // _merge), the device-side input feed, and the GEMM micro-benchmark hooks (ee_debug_gemm,
-// ee_debug_gemm_split, ee_debug_gemm_split_resid, ee_debug_gemm_routes, ee_debug_attn_stamps).  The L-BFGS fits are in capi_fit.hip, the hooks that run one kernel of the path alone for its
+// ee_debug_gemm_split, ee_debug_gemm_split_resid, ee_debug_gemm_routes, ee_debug_gemm_f32, ee_debug_attn_stamps).  The L-BFGS fits are in capi_fit.hip, the hooks that run one kernel of the path alone for its
 // float64 test in capi_debug_*.hip.
 #include <math.h>
 #include <string.h>
@@ -772,6 +772,56 @@ int ee_debug_gemm_routes(const ee_debug_gemm_routes_args* args, float* ms_out, v
     ee_debug_gemm_routes_args b = a;
     if (!resid) { b.resid = nullptr; b.resid_row_src = nullptr; }
     return run_debug_gemm_split(who, b, 0, ms_out, reinterpret_cast<hipStream_t>(stream));
+}
+
+// The f32 counterpart: one launch_gemm_f32 on the arguments of a forward (forward_gemm_args) plus the caller's.  lda = K, ldc = ldr = N: no
+// launch of a forward uses other strides.
+int ee_debug_gemm_f32(const ee_debug_gemm_f32_args* args, void* stream) {
+    const char* who = "ee_debug_gemm_f32";
+    if (!args) return fail(nullptr, "%s: args must not be NULL", who);
+    const ee_debug_gemm_f32_args& a = *args;
+    if (!a.A || !a.W || !a.Cout) return fail(nullptr, "%s: A, W and Cout must not be NULL", who);
+    if (a.N < 1 || a.K < 1 || a.N % 128 != 0 || a.K % 32 != 0)
+        return fail(nullptr, "%s: N %d is not a positive multiple of 128 or K %d not one of 32", who, a.N, a.K);
+    if (a.M < 0) return fail(nullptr, "%s: M %d is negative", who, a.M);
+    if (a.epi < 0 || a.epi > 3) return fail(nullptr, "%s: epi %d outside 0 .. 3 (bias, GELU, residual, tanh; this hook takes no flag bits)", who, a.epi);
+    if (a.staging != 0 && a.staging != 1) return fail(nullptr, "%s: staging %d is neither 0 (LDS-DMA kernel) nor 1 (register-staged kernel)", who, a.staging);
+    if (a.epi == EPI_RESID && !a.resid) return fail(nullptr, "%s: the residual epilogue needs resid", who);
+    if (a.epi != EPI_RESID && a.resid) return fail(nullptr, "%s: resid is read by the residual epilogue (epi 2) alone, got epi %d", who, a.epi);
+    if (a.scale_cols < 0 || a.scale_cols > a.N || a.scale_cols % 128 != 0)
+        return fail(nullptr, "%s: scale_cols %d is not a multiple of 128 in [0, N = %d] (the kernel decides per 128-column tile side)", who, a.scale_cols, a.N);
+    if (a.m_on_device && a.max_m < 1) return fail(nullptr, "%s: max_m %d is below 1", who, a.max_m);
+    if (a.m_on_device && a.M > a.max_m) return fail(nullptr, "%s: M %d is above max_m %d", who, a.M, a.max_m);
+    if (a.wgs_per_cu < 0) return fail(nullptr, "%s: wgs_per_cu %d is negative (0: the default)", who, a.wgs_per_cu);
+    const bool resid = a.epi == EPI_RESID;
+    if (!a.row_src && a.M > a.rows_A) return fail(nullptr, "%s: M %d rows without row_src need M rows of A, rows_A is %d", who, a.M, a.rows_A);
+    if (resid && !a.resid_row_src && a.M > a.rows_resid)
+        return fail(nullptr, "%s: M %d rows without resid_row_src need M rows of the residual, rows_resid is %d", who, a.M, a.rows_resid);
+    const int cus = device_cus(who);
+    if (!cus) return 1;
+    if (a.row_src) { const int rc = check_row_map(who, "row_src", a.row_src, a.M, a.rows_A); if (rc) return rc; }
+    if (resid && a.resid_row_src) { const int rc = check_row_map(who, "resid_row_src", a.resid_row_src, a.M, a.rows_resid); if (rc) return rc; }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // 8 XCD-local queue heads x one 64-byte line, then the device word of M; reused by every call (the hook synchronises before it returns)
+    static int* words = nullptr;
+    if (!words && hipMalloc((void**)&words, 512 + 64) != hipSuccess) { words = nullptr; return fail(nullptr, "%s: hipMalloc failed", who); }
+    if (hipMemsetAsync(words, 0, 512 + 64, s) != hipSuccess) return fail(nullptr, "%s: memset failed", who);
+    GemmArgs g = forward_gemm_args(nullptr);
+    g.A = a.A; g.lda = a.K; g.W = a.W; g.bias = a.bias; g.C = a.Cout; g.ldc = a.N; g.N = a.N; g.K = a.K; g.m_static = a.M;
+    g.row_src = a.row_src;
+    if (resid) { g.resid = a.resid; g.ldr = a.N; g.resid_row_src = a.resid_row_src; }
+    g.scale_cols = a.scale_cols; g.scale = a.scale; g.col_scale = a.col_scale;
+    g.use_dma = a.staging == 0 ? 1 : 2;
+    g.tile_counter = a.use_queue ? words : nullptr;
+    const int M = a.M;                   // (lives until the synchronisation below)
+    if (a.m_on_device) {
+        if (hipMemcpyAsync(words + 128, &M, sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return fail(nullptr, kUploadFailed, who);
+        g.m_ptr = words + 128;
+    }
+    set_gemm_wgs_per_cu(a.wgs_per_cu);
+    launch_gemm_f32(g, a.epi, AMODE_ROWS, a.m_on_device ? a.max_m : M, cus, s);
+    set_gemm_wgs_per_cu(0);
+    return finish(who, s, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-"""What the ten stand-alone kernel hooks (ee_debug_attention, ee_debug_xprobe, ee_debug_prep, ee_debug_embed, ee_debug_ln_rows,
-ee_debug_head_out, ee_debug_exit_decide, ee_debug_rows_out, ee_debug_patch_project, ee_debug_gemm_routes) refuse before they ask for a device: every refusal below is decided on the host from the arguments alone, so the message is asserted whole, on a machine
+"""What the eleven stand-alone kernel hooks (ee_debug_attention, ee_debug_xprobe, ee_debug_prep, ee_debug_embed, ee_debug_ln_rows,
+ee_debug_head_out, ee_debug_exit_decide, ee_debug_rows_out, ee_debug_patch_project, ee_debug_gemm_routes, ee_debug_gemm_f32) refuse before they ask for a device: every refusal below is decided on the host from the arguments alone, so the message is asserted whole, on a machine
 without a GPU too.  The pointers are fake and never dereferenced: every call in this file is refused first."""
 import ctypes as C
 
@@ -386,3 +386,45 @@ def test_gemm_routes_refusals(pkg):
     for over, text in cases:
         _refused(pkg, who, call(**over), text, over)
     # what the hook lets through is what the rule of MMEE_FLAG_LOW_LATENCY produces: its S divides the k-stages (tests/test_host_gemm_routes.py)
+
+
+def test_gemm_f32_refusals(pkg):
+    lib, who = pkg.capi.load(), "ee_debug_gemm_f32"
+    optional = ("bias", "resid", "row_src", "resid_row_src", "col_scale")
+
+    def call(**over):
+        vals = dict(M=129, N=256, K=64, epi=0, staging=0, use_queue=1, rows_A=300, rows_resid=0, scale_cols=0, scale=1.0, max_m=0, m_on_device=0,
+                    wgs_per_cu=0)
+        vals.update(over)
+        return lib.ee_debug_gemm_f32(C.byref(_struct(pkg.capi.DebugGemmF32Args, optional, **vals)), None)
+
+    _refused(pkg, who, lib.ee_debug_gemm_f32(None, None), "args must not be NULL", "args")
+    null = "A, W and Cout must not be NULL"
+    shape = "N %d is not a positive multiple of 128 or K %d not one of 32"
+    epi = "epi %d outside 0 .. 3 (bias, GELU, residual, tanh; this hook takes no flag bits)"
+    staging = "staging %d is neither 0 (LDS-DMA kernel) nor 1 (register-staged kernel)"
+    other = "resid is read by the residual epilogue (epi 2) alone, got epi %d"
+    cols = "scale_cols %d is not a multiple of 128 in [0, N = 256] (the kernel decides per 128-column tile side)"
+    with_resid = dict(epi=2, resid=4096, rows_resid=300)
+    cases = [(dict([(k, None)]), null) for k in ("A", "W", "Cout")]
+    cases += [
+        (dict(A=None, N=100), null),                                            # the pointers before everything else
+        (dict(N=0), shape % (0, 64)), (dict(N=-128), shape % (-128, 64)), (dict(N=192), shape % (192, 64)), (dict(N=64), shape % (64, 64)),
+        (dict(K=0), shape % (256, 0)), (dict(K=-32), shape % (256, -32)), (dict(K=48), shape % (256, 48)), (dict(K=16), shape % (256, 16)),
+        (dict(N=192, M=-1), shape % (192, 64)),                                 # in the order of the entry point
+        (dict(M=-1), "M -1 is negative"), (dict(M=-1, epi=7), "M -1 is negative"),
+        (dict(epi=4), epi % 4), (dict(epi=-1), epi % -1), (dict(epi=256), epi % 256), (dict(epi=16 | 1), epi % 17),
+        (dict(staging=2), staging % 2), (dict(staging=-1), staging % -1),
+        (dict(epi=2), "the residual epilogue needs resid"),
+        (dict(resid=4096), other % 0), (dict(epi=1, resid=4096), other % 1), (dict(epi=3, resid=4096, rows_resid=300), other % 3),
+        (dict(scale_cols=-128), cols % -128), (dict(scale_cols=64), cols % 64), (dict(scale_cols=100), cols % 100), (dict(scale_cols=384), cols % 384),
+        (dict(scale_cols=255), cols % 255),
+        (dict(m_on_device=1), "max_m 0 is below 1"), (dict(m_on_device=1, max_m=-5), "max_m -5 is below 1"), (dict(M=0, m_on_device=1), "max_m 0 is below 1"),
+        (dict(m_on_device=1, max_m=128), "M 129 is above max_m 128"), (dict(M=2, m_on_device=1, max_m=1), "M 2 is above max_m 1"),
+        (dict(wgs_per_cu=-1), "wgs_per_cu -1 is negative (0: the default)"), (dict(with_resid, wgs_per_cu=-2), "wgs_per_cu -2 is negative (0: the default)"),
+        (dict(rows_A=128), "M 129 rows without row_src need M rows of A, rows_A is 128"),
+        (dict(with_resid, rows_resid=100), "M 129 rows without resid_row_src need M rows of the residual, rows_resid is 100"),
+        (dict(with_resid, rows_A=100, rows_resid=100), "M 129 rows without row_src need M rows of A, rows_A is 100"),
+    ]
+    for over, text in cases:
+        _refused(pkg, who, call(**over), text, over)
