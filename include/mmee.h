@@ -18,6 +18,9 @@
  *   ee_embedding_inputs                         <- the three pooled rows the embedding-level exit heads read, `visual_embeddings.mean(1)`,
  *                                                 `embedding_output.mean(1)` and `LayerNorm(cat).mean(1)` (EE/models/LayoutLMv3.py:466, 520, 582),
  *                                                 without the encoder behind them: the training set of those heads.
+ *   ee_forward_vision                           <- no counterpart: the forward from the pixels alone up to the vision_avg exit (EE/models/LayoutLMv3.py:
+ *                                                 465-483), phase 1 of a vision-first call -- what the reference prices with --benchmark_OCR
+ *                                                 (EE/utils.py:127, 176) and never collects; definition below.
  *   ee_policy_scan                              <- Policy.* on a dumped (E+1, N, K) logits array (EE/policy.py:28-45,
  *                                                 87-104; called from EE/eval.py:87-98).
  *   ee_threshold_sweep                          <- thresh.opt1 / large_scale.opt0_2D vectorised exit-index search
@@ -481,6 +484,48 @@ int ee_graph_destroy(ee_handle* h, int32_t graph_id);
 int ee_embedding_inputs(ee_handle* h, const int64_t* input_ids, const int64_t* attention_mask, const int64_t* bbox,
                         const float* pixel_values, const int64_t* token_type_ids, const int64_t* position_ids,
                         int32_t B, int32_t T, float* out_vision, float* out_text, float* out_concat, void* stream);
+
+/*
+ * The vision-first call: OCR only for the documents the image keeps.  DEFINITION (engine.py, modeling.py, README and DESIGN refer to this one).
+ * On a LayoutLMv3 handle whose exit list contains vision_avg that exit is exit 0, it reads visual_embeddings.mean(1) -- a function of the
+ * document's own pixels -- and every later exit needs text.  A vision-first call over B documents has two phases.
+ *   Phase 1, pixels only, all B documents (ee_forward_vision): the patch projection, the visual rows up to layoutlmv3.norm (LayerNorm, eps 1e-6)
+ *     and their mean over the Pv positions (vision_pool_kernel + pool_finish: the bits of ee_embedding_inputs' out_vision), then exit 0 exactly
+ *     as ee_forward runs it: the head (one or two layers; gate handles: classifier(gate input) and, under MMEE_CRIT_GATE, the gate head), the
+ *     temperature, the ensemble row y_0 if an ensemble is set, the handle's criterion, its exit rule and patience entry 0, thresholds[0].
+ *     A document that leaves gets out_logits / out_exit = 0 / out_conf with the bits the one-call ee_forward gives it; for a document that
+ *     stays nothing is written, its slot goes into survivors (ascending; entries from the count on are not written) and their number to *count.
+ *   Phase 2, survivors only: an ordinary ee_forward on the survivors' rows -- their pixel rows and the text the caller supplies NOW -- whose
+ *     results go to the survivors' slots (ee_cascade_gather, ee_cascade_merge with exit offset 0 and stage 1).  Phase 2 evaluates exit 0
+ *     again for its documents: a document's bits do not depend on its batch mates, so none of them leaves there, and the per-slot state
+ *     (patience / streak run, ensemble state, audit marks) is rebuilt at exit 0 as in any forward.  The patch projection is 0.23 of 139 GFLOP
+ *     per document, so phase 2 needs no new forward code, no stash of rows and no state handed over; ee_forward_vision keeps nothing that
+ *     phase 2 needs, and phase 1 of the next batch may run while the text of this one is being read.
+ *   The composition returns, bit for bit, what ee_forward returns on the full inputs (same flags); the text is needed for exactly the
+ *   survivors, and not at all when nobody survives.  With MMEE_FLAG_LOW_LATENCY on phase 2 the bits are those of that flagged forward on
+ *   the survivors' sub-batch, a pure function of its (B', T).  The text and concat means run over all T positions: pad phase 2 to the T
+ *   deployment runs.
+ * ee_forward_vision: pixel_values dev float (B,C,R,R); thresholds / temperatures host double [E+1] as in ee_forward (entry 0 is read);
+ *   flags: the layer flags of ee_forward are accepted and read by nothing; out_logits dev float (B,K) or NULL, out_exit dev int32 (B),
+ *   out_conf dev float (B) or NULL; survivors dev int32 (B); count dev int32 (1).  It only enqueues.  Launches: the error-word zeroing, the
+ *   uniform layout of the decide kernel's bookkeeping, the patch projection, vision_pool_kernel, pool_finish, exit 0's head / ensemble /
+ *   decide launches, one copy of the next stage's slots and count.
+ *   Handle state: as ee_embedding_inputs.  What the handle records of its LAST FORWARD is untouched (ee_last_stage_counts, ee_last_flops,
+ *   ee_last_k_splits, ee_last_layer_plan, ee_suggest_probe_mask, ee_profile_read; an armed ee_profile times nothing here); it writes only
+ *   workspace that every forward and graph replay rewrites before reading it, so captured graphs stay valid and an undrained result stream
+ *   keeps its chunks.
+ *   Refused with a message, nothing written: a MMEE_ARCH_BEIT handle; a handle without vision_avg; B outside [1, max_docs]; a NULL
+ *   pixel_values / out_exit / survivors / count; MMEE_FLAG_NO_EXIT, MMEE_FLAG_STREAM_RESULTS, MMEE_FLAG_DENSE_ROWS; quotas set (a rank over B
+ *   and a second rank over the survivors are not the one-call ranking); an audit or a controller set (the audit hashes the slot in the
+ *   call, which phase 2 renumbers); an armed one-shot side input / output (it stays armed); missing thresholds (unless MMEE_CRIT_PATIENCE)
+ *   and the patience / exit-rule combinations ee_forward refuses.  Allowed unchanged: the four threshold criteria, patience, both exit
+ *   rules, use_lte (nobody leaves at an embedding exit: correct and pointless), the gate criterion, temperatures, an ensemble, ramp and
+ *   gate handles, 1- and 2-layer heads.
+ *   NOT BUILT: a row stash between the phases; vision-first under audits / controllers / quotas / captured graphs / the result stream /
+ *   micro-batches / as a cascade stage; the dump-all outputs (out_all_*, out_head_*, out_hidden_cls); a text-first counterpart for text_avg.
+ */
+int ee_forward_vision(ee_handle* h, const float* pixel_values, int32_t B, const double* thresholds, const double* temperatures, uint32_t flags,
+                      float* out_logits, int32_t* out_exit, float* out_conf, int32_t* survivors, int32_t* count, void* stream);
 
 /*
  * The result stream of the handle's most recent ee_forward with MMEE_FLAG_STREAM_RESULTS: one chunk per evaluated exit, in the path's order
@@ -1594,6 +1639,13 @@ int ee_debug_ln_rows(const float* src, float* dst, const int32_t* row_src, const
                      const float* beta, float eps, void* dst_split, float split_scale, int32_t pre_parts, size_t pre_stride,
                      const float* pre_bias, const void* pre_resid, const int32_t* pre_resid_rows, float pre_resid_inv, int32_t* err_flag_out,
                      void* stream);
+/* ee_debug_vision_pool: the phase-1 kernel of a vision-first call (csrc/vision_first.hip) alone, as ee_forward_vision launches it behind the
+ *   patch projection: vision_pool_kernel, then pool_finish; no handle.  vis_raw dev float (B,Pv - 1,H) = the patch projection's output,
+ *   cls_token (H), pos_embed (Pv,H), ln_g / ln_b (H) and eps = layoutlmv3.norm; vis_part dev float (B,ceil(Pv/32),H) scratch that receives
+ *   the partial sums per (document, 32-row chunk); pooled dev float (B,H) = the mean over the Pv rows.  Refused, not launched: a NULL
+ *   pointer, a hidden size that is not a multiple of 4 in [4, 1024], B < 1, Pv < 2, B Pv > 2^24, eps <= 0.  Synchronises the stream. */
+int ee_debug_vision_pool(const float* vis_raw, const float* cls_token, const float* pos_embed, const float* ln_g, const float* ln_b, float eps,
+                         int32_t B, int32_t Pv, int32_t H, float* vis_part, float* pooled, void* stream);
 
 /* Unit-test hook of the X-space CLS probe (csrc/xprobe.hip), the counterpart of ee_debug_attention: the three kernels of launch_xprobe on
  * caller-provided DEVICE buffers, fed as layer_probe() of the forward feeds them; no handle.

@@ -34,3 +34,4 @@ from .audit import AuditSample, ConsistencyReport  # noqa: F401,E402
 from . import risk  # noqa: F401,E402
 from .risk import RiskResult, RollingResult, risk_control, rolling_control  # noqa: F401,E402
 from .engine import ControllerLog  # noqa: F401,E402
+from .engine import VisionFirstOutput, VisionPhase  # noqa: F401,E402

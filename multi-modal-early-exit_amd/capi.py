@@ -211,6 +211,7 @@ SYMBOLS = {
     "ee_forward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(C.c_double),
                              C.POINTER(C.c_double), _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ee_embedding_inputs": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ee_forward_vision": (C.c_int, [_vp, _vp, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ee_graph_capture": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32)]),
     "ee_graph_launch": (C.c_int, [_vp, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
@@ -293,6 +294,7 @@ SYMBOLS = {
     "ee_debug_embed": (C.c_int, [C.POINTER(DebugEmbedArgs), C.POINTER(_i32), _vp]),
     "ee_debug_ln_rows": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, C.c_float, _vp, C.c_float, _i32, C.c_size_t, _vp, _vp, _vp, C.c_float,
                                    C.POINTER(_i32), _vp]),
+    "ee_debug_vision_pool": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_float, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ee_debug_xprobe": (C.c_int, [C.POINTER(DebugXProbeArgs), C.POINTER(_i32), _vp]),
     "ee_debug_head_out": (C.c_int, [C.POINTER(DebugHeadOutArgs), _vp]),
     "ee_debug_exit_decide": (C.c_int, [C.POINTER(DebugExitDecideArgs), _vp]),

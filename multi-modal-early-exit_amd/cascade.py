@@ -140,6 +140,13 @@ class CascadeEngine:
         raise NotImplementedError("CascadeEngine.capture: a later stage's batch size depends on the data, and a captured launch list has its "
                                   "shapes bound; capture the stages' engines themselves")
 
+    def forward_vision_first(self, *args, **kw):
+        raise NotImplementedError("CascadeEngine.forward_vision_first: a vision-first stage inside a cascade is not built (a stage's forward "
+                                  "takes its whole inputs at once); run EarlyExitEngine.forward_vision_first on the stage's engine, or put an "
+                                  "image-only stage in front and hand the next stage a callable")
+
+    forward_vision = forward_vision_first
+
     # ---- arguments -----------------------------------------------------------------------------------------------------------------------
     def _per_stage(self, v, what):
         """None, one vector per stage, or the flat (SE1,) vector -> a list of S entries (None: the stage's default)."""

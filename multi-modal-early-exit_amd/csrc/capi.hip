@@ -382,12 +382,12 @@ int alloc_workspace(ee_handle* h) {
     rc |= dev_alloc(h, &h->queue_heads, (size_t)h->n_queue_heads);
     rc |= dev_alloc(h, &h->meta[0], rows);
     rc |= dev_alloc(h, &h->meta[1], rows);
-    const size_t st = (size_t)(E + 2) * (Bm + 1);
+    const size_t st = (size_t)(E + 3) * (Bm + 1);      // stages 0 .. E of a forward; E + 1, E + 2: scratch of ee_embedding_inputs / ee_forward_vision
     rc |= dev_alloc(h, &h->doc_orig, st);
     rc |= dev_alloc(h, &h->doc_off, st);
     rc |= dev_alloc(h, &h->x_src, st);
     rc |= dev_alloc(h, &h->meta_src, st);
-    rc |= dev_alloc(h, &h->counts, (size_t)(E + 2));
+    rc |= dev_alloc(h, &h->counts, (size_t)(E + 3));
     rc |= dev_alloc(h, &h->thr_dev, 256);
     rc |= dev_alloc(h, &h->pat_state, 2 * Bm);
     if (c.use_lte) rc |= dev_alloc(h, &h->lte_score, Bm);

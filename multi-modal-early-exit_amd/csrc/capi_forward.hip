@@ -221,6 +221,7 @@ struct Forward {
     const int* x_phys = nullptr;             // physical X row of every row of stage `cur`
     bool use_row_src = false;                // X rows are read through h->row_src (after a compaction, until a layer rewrites X densely)
     bool cls_ready = false;                  // the last layer was a probe: Xcs / cls_f32 hold the final classifier's input
+    bool vision_only = false;                // run_vision: the call ends behind exit 0, nothing is compacted for a layer to read
 
     // diagnostic library only: MMEE_ATTN_V=2 forces attention_pair.hip (A/B)
     static int attn_variant() { static const int v = mmee::diag_env_int("MMEE_ATTN_V", 0); return v; }
@@ -718,7 +719,7 @@ struct Forward {
         h->rec.exit_stage[exit_index] = cur;
         if (is_final) { fin_pol = d.pol_logits; fin_temp = d.temp; }
         if (stream_results) emit_leavers(is_final);
-        if (!is_final) compact();
+        if (!is_final && !vision_only) compact();
         exit_index += 1;
     }
 
@@ -911,6 +912,39 @@ struct Forward {
         if (!cap) { const int rc_post = forward_post(h, s); if (rc_post) return rc_post; }
         return launch_status(h, cap ? "ee_graph_capture" : "ee_forward");
     }
+
+    // ee_forward_vision (include/mmee.h): the forward's opening from the pixels alone, up to and including exit 0; the caller has validated.
+    // The layout is the uniform one of an image-only call (Pv rows per document: the decide kernel's bookkeeping reads nothing else of it),
+    // in the two stage slots no forward reads back (E + 1, E + 2), so the stage counts of the last forward stay what they were; so do its
+    // record and its profile.
+    int run_vision(int32_t* survivors, int32_t* count) {
+        constexpr int kind = MMEE_EXIT_VISION_AVG;
+        const int vch = (Pv + 31) / 32;
+        if (const int rc = forward_pre(h, s)) return rc;
+        // the error word and the patch GEMM's queue heads, as in front of ee_embedding_inputs
+        hipLaunchKernelGGL(zero_words_kernel, dim3(32), dim3(256), 0, s, h->err_flag, 4, h->queue_heads, std::min(h->n_queue_heads, 128));
+        const bool prof = h->prof_on;
+        h->prof_on = false;
+        const ForwardRecord last = h->rec;
+        h->rec.exit_stage.assign(E + 1, 0);
+        vision_only = true;
+        cur = E + 1;
+        launch_prep_uniform(B, Pv, S_doc_off(cur), S_x_src(cur), S_doc_orig(cur), h->meta[0], &h->counts[cur], s);
+        handle_patch_projection(h, a.pixel_values, B, h->n_queue_heads >= 128 ? h->queue_heads : nullptr, s);
+        VisionPoolArgs va{};
+        va.vis_raw = h->vis_raw; va.cls_token = h->cls_token; va.pos_embed = h->pos_embed;
+        va.ln_g = h->norm_g; va.ln_b = h->norm_b; va.eps = 1e-6f;        // layoutlmv3.norm = LayerNorm(eps=1e-6), HF:563
+        va.B = B; va.Pv = Pv; va.H = H; va.vis_part = h->vis_part;
+        launch_vision_pool(va, s);
+        launch_pool_finish(h->vis_part, vch, H, (float)Pv, h->pooled[kind], B, s);
+        x_phys = S_x_src(cur);
+        run_exit(&h->emb_heads[kind], h->pooled[kind], H, S_doc_orig(cur), false, nullptr, nullptr, false);
+        launch_copy_survivors(&h->counts[cur + 1], S_doc_orig(cur + 1), B, survivors, count, s);
+        h->rec = last;
+        h->prof_on = prof;
+        if (const int rc = forward_post(h, s)) return rc;
+        return launch_status(h, "ee_forward_vision");
+    }
 };
 
 }  // namespace
@@ -1042,6 +1076,50 @@ int ee_embedding_inputs(ee_handle* h, const int64_t* input_ids, const int64_t* a
     h->prof_on = prof;
     if (const int rc = forward_post(h, s)) return rc;
     return launch_status(h, "ee_embedding_inputs");
+}
+
+// ---- phase 1 of a vision-first call: the forward from the pixels alone, up to exit 0 (include/mmee.h) ------------------------------------
+// Towards the handle it behaves as ee_embedding_inputs does: the record, the stage counts and the profile of the last forward stay, and it
+// writes only workspace that every forward and graph replay rewrites before reading it.
+int ee_forward_vision(ee_handle* h, const float* pixel_values, int32_t B, const double* thresholds, const double* temperatures, uint32_t flags,
+                      float* out_logits, int32_t* out_exit, float* out_conf, int32_t* survivors, int32_t* count, void* stream) {
+    if (!h) return 1;
+    const ee_config& c = h->cfg;
+    if (c.arch == MMEE_ARCH_BEIT)
+        return fail(h, "ee_forward_vision: embedding-level exits belong to LayoutLMv3 handles; this is an MMEE_ARCH_BEIT handle");
+    if (!h->finalized) return fail(h, "ee_forward_vision: call ee_finalize after loading the parameters");
+    if (c.n_embedding_exits < 1 || c.embedding_exits[0] != MMEE_EXIT_VISION_AVG)
+        return fail(h, "ee_forward_vision: the handle's exit list has no vision_avg exit: there is nothing to decide from the pixels alone");
+    if (!pixel_values || !out_exit || !survivors || !count)
+        return fail(h, "ee_forward_vision: pixel_values, out_exit, survivors and count are required");
+    if (B < 1 || B > c.max_docs) return fail(h, "ee_forward_vision: B=%d outside [1, max_docs=%d]", B, c.max_docs);
+    if (flags & (MMEE_FLAG_NO_EXIT | MMEE_FLAG_STREAM_RESULTS | MMEE_FLAG_DENSE_ROWS))
+        return fail(h, "ee_forward_vision: MMEE_FLAG_NO_EXIT, MMEE_FLAG_STREAM_RESULTS and MMEE_FLAG_DENSE_ROWS do not go with a vision-first call "
+                       "(nobody would leave; the stream's chunks are per call; there are no text rows to keep)");
+    if (h->quota_mode != MMEE_QUOTA_OFF)
+        return fail(h, "ee_forward_vision: quotas are set: a rank over B documents and a second one over the survivors are not the one-call ranking "
+                       "(not built; ee_set_quotas(h, NULL, 0, 0) first)");
+    if (h->ctl_on)                                 // before the audit's refusal: a controller implies an audit
+        return fail(h, "ee_forward_vision: a controller is set: its audit hashes the slot in the call, which phase 2 renumbers "
+                       "(not built; ee_set_controller(h, NULL, ...) first)");
+    if (h->audit_cut)
+        return fail(h, "ee_forward_vision: an audit is set: it hashes the slot in the call, which phase 2 renumbers "
+                       "(not built; ee_set_audit(h, 0, 0, 0) first)");
+    if (h->next_inputs_embeds || h->next_hidden_out || h->next_head_mask || h->next_attn_out)
+        return fail(h, "ee_forward_vision: a one-shot side input / output is armed (inputs_embeds, hidden states, head mask, attention maps): "
+                       "they belong to ee_forward, which consumes them");
+    const bool patience = c.criterion == MMEE_CRIT_PATIENCE;
+    if (!thresholds && !patience) return fail(h, "ee_forward_vision: thresholds required unless MMEE_CRIT_PATIENCE");
+    if (patience && !h->has_patience())
+        return fail(h, "ee_forward_vision: the patience criterion needs ee_set_patience(h, t) with t >= 1 before the first forward");
+    if (h->rule != MMEE_RULE_PLAIN && patience)
+        return fail(h, "ee_forward_vision: MMEE_RULE_STREAK / MMEE_RULE_EITHER build on a threshold event, which MMEE_CRIT_PATIENCE does not have");
+    if (h->rule != MMEE_RULE_PLAIN && !h->has_patience())
+        return fail(h, "ee_forward_vision: MMEE_RULE_STREAK / MMEE_RULE_EITHER need a patience: ee_set_patience or ee_set_patience_vector before the forward");
+    // no text, no dump-all outputs; T is read by nothing on this route (the layout is the uniform one of Pv rows per document)
+    const ForwardArgs a{nullptr, nullptr, nullptr, pixel_values, nullptr, nullptr, B, 1, thresholds, temperatures, flags,
+                        out_logits, out_exit, out_conf, nullptr, nullptr, nullptr, nullptr, nullptr, stream};
+    return Forward(h, a, nullptr).run_vision(survivors, count);
 }
 
 int ee_graph_destroy(ee_handle* h, int32_t graph_id) {

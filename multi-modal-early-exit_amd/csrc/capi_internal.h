@@ -1,11 +1,12 @@
 // What the translation units of the C-ABI (include/mmee.h) share: the handle, its parameter / weight records, the error helpers every entry
 // point returns through, the allocator and the profiling scope.  Private to csrc/capi*.hip:
 //   capi.hip          the handle's error ring and allocator, and the loader (ee_create, ee_load_tensor, ee_finalize, ee_destroy)
-//   capi_forward.hip  the forward schedule (Forward, ee_forward), its captured-graph form (ee_graph_*) and its stage 0 alone (ee_embedding_inputs)
+//   capi_forward.hip  the forward schedule (Forward, ee_forward), its captured-graph form (ee_graph_*), its stage 0 alone (ee_embedding_inputs)
+//                     and its pixels-only opening up to exit 0 (ee_forward_vision)
 //   capi_query.hip    what reads the last forward back or arms the next one (ee_profile*, ee_stream_next, ee_last_*, ee_suggest_probe_mask, ee_set_*)
 //   capi_tools.hip    entry points that never see a handle (clock stamps, policy sweeps, pack / unpack, image feed, the GEMM micro-benchmarks)
-//   capi_debug_attention.hip, capi_debug_rows.hip, capi_debug_xprobe.hip, capi_debug_exit.hip, capi_debug_patch.hip   the ee_debug_* hooks of the
-//                     attention kernels, of the row kernels, of the X-space CLS probe, of the exit stage and of the patch projection; what only
+//   capi_debug_attention.hip, capi_debug_rows.hip, capi_debug_xprobe.hip, capi_debug_exit.hip, capi_debug_patch.hip, capi_debug_vision.hip   the ee_debug_* hooks of the
+//                     attention kernels, of the row kernels, of the X-space CLS probe, of the exit stage, of the patch projection and of the vision pool; what only
 //                     they share is in capi_debug.h
 //   capi_fit.hip      the device fits, no handle either (ee_head_fit, ee_mlp_head_fit, ee_lte_*, ee_ensemble_fit, ee_debug_*_lossgrad)
 #pragma once
@@ -117,8 +118,8 @@ struct ee_handle {
     int* queue_heads = nullptr;                   // one work-queue counter per persistent launch of a forward
     int n_queue_heads = 0, next_queue_head = 0;
     mmee::RowMeta* meta[2];
-    int *doc_orig, *doc_off, *x_src, *meta_src;   // [(E+2)][max_docs+1]
-    mmee::StageCounts* counts;                    // [(E+2)]
+    int *doc_orig, *doc_off, *x_src, *meta_src;   // [(E+3)][max_docs+1]
+    mmee::StageCounts* counts;                    // [(E+3)]
     double* thr_dev = nullptr;                    // scratch for ee_policy_scan
     int32_t patience = 0;                         // ee_set_patience (0: not set): the patience of every exit unless patience_vec is set
     std::vector<int32_t> patience_vec;            // ee_set_patience_vector: [E + 1] per-exit patience (empty: the broadcast above)

@@ -204,6 +204,20 @@ __device__ __forceinline__ void wave_layernorm(f32x4 (&x)[NV], int H, int lane, 
     }
 }
 
+// reduce per-wave column sums of the 4 waves through LDS and write one partial row
+template <int NV>
+__device__ __forceinline__ void block_write_partial(float* lds, float* __restrict__ dst, const f32x4 (&acc)[NV],
+                                                    int H, int lane, int wave) {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = 4 * lane + 256 * i;
+        if (c < H) *reinterpret_cast<f32x4*>(lds + wave * H + c) = acc[i];
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < H; c += 256) dst[c] = (lds[c] + lds[H + c]) + (lds[2 * H + c] + lds[3 * H + c]);
+}
+
 constexpr int kMaxNV = 4;  // hidden_size <= 1024, multiple of 4
 
 // erf for the GELU epilogue: erf(x) = sign(x) * (1 - 2^(-q(|x|))), q = degree-8 polynomial fitted to -log2(erfc(t)) on

@@ -52,6 +52,15 @@ struct EmbedArgs {
     int cat_chunks;
 };
 
+// vision_pool_kernel (vision_first.hip): the visual rows up to layoutlmv3.norm and their partial column sums, nothing stored besides
+struct VisionPoolArgs {
+    const float *vis_raw, *cls_token, *pos_embed;      // [B][Pv - 1][H], [H], [Pv][H]
+    const float *ln_g, *ln_b;                          // layoutlmv3.norm
+    float eps;
+    int B, Pv, H;
+    float* vis_part;                                   // (B, ceil(Pv/32), H)
+};
+
 struct HeadOutArgs {
     const float* in;                 // rows of length H
     int ld;
@@ -461,6 +470,8 @@ void launch_doc_flags(const RowMeta* meta, const int* doc_off, int n_docs, int* 
 void launch_prep_uniform(int B, int Pv, int* doc_off, int* x_src, int* doc_orig, RowMeta* meta, StageCounts* counts, hipStream_t s);
 void launch_embed_text(const EmbedArgs& a, hipStream_t s);
 void launch_embed_visual(const EmbedArgs& a, hipStream_t s);
+void launch_vision_pool(const VisionPoolArgs& a, hipStream_t s);
+void launch_copy_survivors(const StageCounts* n_counts, const int* n_doc_orig, int cap, int* survivors, int* count, hipStream_t s);
 void launch_pool_finish(const float* part, int chunks, int H, float count, float* pooled, int B, hipStream_t s);
 void launch_ln_rows(const float* src, float* dst, const int* row_src, const int* n_rows_ptr, int max_rows, int H,
                     const float* g, const float* b, float eps, int num_cus, hipStream_t s, void* dst_split = nullptr,

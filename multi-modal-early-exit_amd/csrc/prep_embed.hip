@@ -208,20 +208,7 @@ __device__ __forceinline__ void wave_store_row_split(void* dst_row, const f32x4 
     }
 }
 
-// reduce per-wave column sums of the 4 waves through LDS and write one partial row
-template <int NV>
-__device__ __forceinline__ void block_write_partial(float* lds, float* __restrict__ dst, const f32x4 (&acc)[NV],
-                                                    int H, int lane, int wave) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = 4 * lane + 256 * i;
-        if (c < H) *reinterpret_cast<f32x4*>(lds + wave * H + c) = acc[i];
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < H; c += 256) dst[c] = (lds[c] + lds[H + c]) + (lds[2 * H + c] + lds[3 * H + c]);
-}
-
+// (block_write_partial, the partial row of a workgroup's four waves: mmee_common.h, shared with vision_first.hip)
 template <int NV, bool FAST, bool POOLED, bool FULL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void embed_text_kernel(EmbedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];

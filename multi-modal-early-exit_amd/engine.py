@@ -40,6 +40,27 @@ class EngineOutput:
 
 
 @dataclass
+class VisionPhase:
+    """Phase 1 of a vision-first call (``EarlyExitEngine.forward_vision``; the definition is in include/mmee.h at ee_forward_vision)."""
+    output: EngineOutput                    # logits / exit_layer (= 0) / confidence written at the slots that left at exit 0, nothing elsewhere
+    survivors: "torch.Tensor"               # (B,) int32 on the device: the slots that stay, ascending; entries from ``count`` on are not written
+    count: "torch.Tensor"                   # (1,) int32 on the device: how many stay
+
+
+@dataclass
+class VisionFirstOutput:
+    """What ``EarlyExitEngine.forward_vision_first`` returns: the three outputs of ``forward`` on the full inputs, bit for bit."""
+    logits: "torch.Tensor"                  # (B,K) float32
+    exit_layer: "torch.Tensor"              # (B,)  int32
+    confidence: "torch.Tensor"              # (B,)  float32
+    stage: "torch.Tensor"                   # (B,)  int32: 0 = answered from the pixels, 1 = ran with text
+    text_docs: int                          # how many documents needed text (the survivors of exit 0)
+
+
+_TEXT_KEYS = ("input_ids", "attention_mask", "bbox", "token_type_ids", "position_ids")
+
+
+@dataclass
 class ResultChunk:
     """The documents that left at one exit (``EarlyExitEngine.forward_stream``): host numpy arrays, copies of the handle's pinned segment."""
     exit_index: int                         # the exit, in the path's order; E = final classifier
@@ -536,6 +557,138 @@ class EarlyExitEngine:
         capi.check(rc, self._h, "ee_embedding_inputs")
         self._keepalive = (ids, am, bb, px, tt, ps)   # borrowed by the enqueued kernels until the stream drains
         return out
+
+    # ---- vision first: OCR only for the documents the image keeps (the definition is in include/mmee.h at ee_forward_vision) ----------------
+    def _exit_vectors(self, thresholds, temperatures):
+        """thresholds (a scalar, or one entry per exit; None: the configuration's) and temperatures as the (E + 1,) C arrays of ee_forward."""
+        E = self.E
+        if thresholds is None:
+            thresholds = self.exit_config.global_threshold
+        thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float64).reshape(-1), (E + 1,)).copy() \
+            if np.ndim(thresholds) else np.full((E + 1,), float(thresholds))
+        tmp_c = None
+        if temperatures is not None:
+            tm = np.asarray(temperatures, dtype=np.float64).reshape(-1)
+            if tm.shape[0] != E + 1:
+                raise ValueError(f"temperatures must have {E + 1} entries")
+            tmp_c = (C.c_double * (E + 1))(*tm.tolist())
+        return (C.c_double * (E + 1))(*thr.tolist()), tmp_c
+
+    def forward_vision(self, pixel_values, thresholds: Optional[Union[float, Sequence[float]]] = None,
+                       temperatures: Optional[Sequence[float]] = None, out=None) -> VisionPhase:
+        """Phase 1 of a vision-first call (``ee_forward_vision``): from ``pixel_values`` (B,C,R,R) alone, the vision_avg exit -- exit 0 of an
+        engine whose exit list names it -- exactly as ``forward`` decides it.  The documents that leave there get ``logits`` / ``exit_layer``
+        = 0 / ``confidence`` with the bits of the one-call ``forward``; the others have nothing written and their slots come back in
+        ``survivors`` (ascending) with their number in ``count``, both on the device.  ``thresholds`` / ``temperatures`` as in ``forward``
+        (entry 0 is read).  ``out``: as in ``forward``.  The call only enqueues, keeps no state a later call needs and leaves
+        ``stage_counts()`` / ``flops()`` / ``profile_read()`` describing the last ``forward``: phase 1 of the next batch may run while OCR
+        works on this one.  Refused by the library with a message: image-only engines, no vision_avg, quotas, an audit, a controller."""
+        if not self._finalized:
+            raise capi.MMEEError("load_weights() has not been called")
+        R = self.cfg.input_size
+        px = self._dev(pixel_values, torch.float32, "pixel_values")
+        if px.dim() != 4 or tuple(px.shape[1:]) != (self.cfg.num_channels, R, R):
+            raise ValueError(f"pixel_values must be (B,{self.cfg.num_channels},{R},{R})")
+        B, K, dev = int(px.shape[0]), self.K, self.device
+        thr_c, tmp_c = self._exit_vectors(thresholds, temperatures)
+        if out is not None:
+            out_logits, out_exit, out_conf = out
+            for t, shp, dt in ((out_logits, (B, K), torch.float32), (out_exit, (B,), torch.int32), (out_conf, (B,), torch.float32)):
+                if tuple(t.shape) != shp or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                    raise ValueError(f"out: expected a contiguous {dt} tensor of shape {shp} on {dev}")
+        else:
+            out_logits = torch.empty((B, K), dtype=torch.float32, device=dev)
+            out_exit = torch.empty((B,), dtype=torch.int32, device=dev)
+            out_conf = torch.empty((B,), dtype=torch.float32, device=dev)
+        survivors = torch.empty((max(B, 1),), dtype=torch.int32, device=dev)
+        count = torch.empty((1,), dtype=torch.int32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            rc = self.lib.ee_forward_vision(self._h, p(px), B, thr_c, tmp_c, 0, p(out_logits), p(out_exit), p(out_conf), p(survivors), p(count),
+                                            stream)
+        capi.check(rc, self._h, "ee_forward_vision")
+        self._keepalive = (px,)             # borrowed by the enqueued kernels until the stream drains
+        return VisionPhase(EngineOutput(out_logits, out_exit, out_conf), survivors, count)
+
+    def forward_vision_first(self, pixel_values, text, thresholds: Optional[Union[float, Sequence[float]]] = None,
+                             temperatures: Optional[Sequence[float]] = None, low_latency: bool = False, xprobe: Optional[bool] = None,
+                             whole_layers: bool = False, probe_always: bool = False, **not_built) -> VisionFirstOutput:
+        """The vision-first call: ``forward_vision`` on all B documents, then an ordinary ``forward`` on the survivors of exit 0 with text
+        that is supplied only now.  Returns, bit for bit, the ``logits`` / ``exit_layer`` / ``confidence`` of ``forward`` on the full inputs,
+        ``stage`` (0 = answered from the pixels, 1 = ran with text) and ``text_docs``, the number of documents that needed text.
+        ``text`` is either a dict of the caller's full arrays (``input_ids``, ``attention_mask``, ``bbox``, optional ``token_type_ids`` /
+        ``position_ids``, B rows each): the survivors' rows and their pixel rows are gathered in one launch and the count stays on the
+        device; or a callable ``f(slots: np.ndarray) -> dict`` as in ``CascadeEngine``: called once, only when somebody survives, with the
+        survivors' slots (ascending), it returns their rows in that order -- OCR only for the pages the image keeps.  The text and concat
+        exits average over all T positions of the call, padding included: the callable must pad to the T deployment runs, or the bits
+        (and the decisions) are those of another T.  One 4-byte host read (the count) behind one stream wait; the callable route also
+        downloads the slots.  ``low_latency`` / ``xprobe`` / ``whole_layers`` / ``probe_always`` go to phase 2 (they concern the layers, and
+        the equality above is with ``forward`` under the same ones); under ``low_latency=True`` the bits are those of
+        ``forward(low_latency=True)`` on the survivors' sub-batch, not of the one-call forward.
+        Not built, refused: ``want_all`` / ``want_head`` / ``want_hidden_cls`` / ``dump_all`` outputs, a result stream, a captured graph,
+        quotas, audits, controllers (the library's messages), ``MicroBatchedEngine`` and a vision-first stage of a ``CascadeEngine``."""
+        for k in not_built:
+            if k in ("want_all", "want_head", "want_hidden_cls", "want_hidden_states", "want_attentions", "dump_all", "head_mask"):
+                raise ValueError(f"forward_vision_first: {k} belongs to a dump-all forward, where nobody leaves at exit 0 (not built)")
+            if k in ("_stream", "stream", "_capture", "capture"):
+                raise ValueError(f"forward_vision_first: {k}: a vision-first call under a result stream or a captured graph is not built (phase 2's "
+                                 "batch size depends on the data)")
+            raise ValueError(f"forward_vision_first: {k} is not an argument of a vision-first call")
+        if not (callable(text) or isinstance(text, Mapping)):
+            raise ValueError("forward_vision_first: text is a dict of the caller's full arrays or a callable f(slots) -> dict")
+        px = self._dev(pixel_values, torch.float32, "pixel_values")
+        dev, K = self.device, self.K
+        arrays = None
+        if not callable(text):
+            arrays = {k: self._dev(text[k], torch.int64, k) for k in _TEXT_KEYS if text.get(k) is not None}
+            if "input_ids" not in arrays:
+                raise ValueError("forward_vision_first: text needs input_ids")
+            for k, v in arrays.items():
+                if int(v.shape[0]) != int(px.shape[0]):
+                    raise ValueError(f"forward_vision_first: {k} has {int(v.shape[0])} rows for a call of {int(px.shape[0])} documents")
+        with torch.cuda.device(dev):
+            phase = self.forward_vision(px, thresholds, temperatures)
+            B = int(px.shape[0])
+            out = phase.output
+            stage = torch.zeros((B,), dtype=torch.int32, device=dev)
+            if getattr(self, "_vf_count_host", None) is None:
+                self._vf_count_host = torch.empty((1,), dtype=torch.int32).pin_memory()
+            # the one host read of the seam: 4 bytes behind one stream wait (phase 2's ee_forward takes its batch size by value)
+            self._vf_count_host.copy_(phase.count, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            m = int(self._vf_count_host[0])
+            if m == 0:
+                return VisionFirstOutput(out.logits, out.exit_layer, out.confidence, stage, 0)
+            slots = phase.survivors[:m]
+            src = {"pixel_values": px}
+            if callable(text):
+                rows = text(slots.cpu().numpy())
+                sub = {k: self._dev(rows[k], torch.int64, k) for k in _TEXT_KEYS if rows.get(k) is not None}
+                if "input_ids" not in sub:
+                    raise ValueError("forward_vision_first: the callable's dict needs input_ids")
+                bad = {k: int(v.shape[0]) for k, v in sub.items() if int(v.shape[0]) != m}
+                if bad:
+                    raise ValueError(f"forward_vision_first: the callable returned {bad} rows for {m} surviving documents")
+            else:
+                sub = {}
+                src.update(arrays)
+            descs = (capi.CascadeDesc * capi.CASCADE_MAX_ARRAYS)()
+            for i, (k, v) in enumerate(src.items()):
+                sub[k] = torch.empty((m,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev)
+                descs[i].src, descs[i].dst = v.data_ptr(), sub[k].data_ptr()
+                descs[i].row_bytes = (v.numel() // B) * v.element_size()
+            ptr = lambda t: C.c_void_p(t.data_ptr())
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            capi.check(self.lib.ee_cascade_gather(descs, len(src), ptr(slots), ptr(phase.count), m, stream), None, "ee_cascade_gather")
+            res = self.forward(**sub, thresholds=thresholds, temperatures=temperatures, low_latency=low_latency, xprobe=xprobe,
+                               whole_layers=whole_layers, probe_always=probe_always)
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            capi.check(self.lib.ee_cascade_merge(ptr(res.logits), ptr(res.exit_layer), ptr(res.confidence), ptr(slots), m, K, 0, 1,
+                                                 ptr(out.logits), ptr(out.exit_layer), ptr(out.confidence), ptr(stage), stream), None,
+                       "ee_cascade_merge")
+            self._keepalive = (self._keepalive, src, sub, res, phase)      # borrowed by the enqueued launches until the stream drains
+        return VisionFirstOutput(out.logits, out.exit_layer, out.confidence, stage, m)
 
     def forward_stream(self, *args, **kw) -> ResultStream:
         """``forward`` with MMEE_FLAG_STREAM_RESULTS (include/mmee.h): same arguments, same device outputs (``.output``), and the returned

@@ -112,6 +112,13 @@ class MicroBatchedEngine:
         """Not built (module docstring): interleaving the result streams of several handles is a host policy of its own."""
         raise NotImplementedError("MicroBatchedEngine has no result stream: use EarlyExitEngine.forward_stream (one handle, one stream)")
 
+    def forward_vision(self, *args, **kw):
+        """Not built: the survivors of a vision-first call are one list over ONE call's slots (include/mmee.h, ee_forward_vision)."""
+        raise NotImplementedError("MicroBatchedEngine has no vision-first call: the survivors are one ascending list over one handle's call; "
+                                  "use EarlyExitEngine.forward_vision / forward_vision_first")
+
+    forward_vision_first = forward_vision
+
     def forward(self, input_ids=None, attention_mask=None, bbox=None, pixel_values=None, token_type_ids=None, position_ids=None,
                 inputs_embeds=None, serial: bool = False, **kw) -> EngineOutput:
         """Same arguments and result as ``EarlyExitEngine.forward``.  ``serial``: run the slices one after the other on the CURRENT stream

@@ -371,6 +371,45 @@ class LayoutLMv3EEForSequenceClassification:
                               token_type_ids=token_type_ids, position_ids=position_ids),
                          thresholds=thresholds, temperatures=temperatures, **kw)
 
+    def early_exit_vision_first(self, pixel_values=None, input_ids=None, attention_mask=None, bbox=None, token_type_ids=None,
+                                position_ids=None, text=None, thresholds: Optional[Union[float, Sequence[float]]] = None,
+                                temperatures: Optional[Sequence[float]] = None, patience: Optional[int] = None, low_latency: bool = False,
+                                **kw):
+        """``early_exit`` that looks at the pixels first (``EarlyExitEngine.forward_vision_first``; the definition is in include/mmee.h at
+        ee_forward_vision): the vision_avg exit decides on every document from ``pixel_values`` alone, and only the documents that stay are
+        run with text.  The text is either the reference-style keyword inputs over all B documents (``input_ids`` / ``attention_mask`` /
+        ``bbox`` / ``token_type_ids`` / ``position_ids``), or ``text=f`` with ``f(slots: np.ndarray) -> dict`` of the survivors' rows, called
+        only when somebody stays -- OCR for those pages alone; pad to the T deployment runs.  Returns a ``VisionFirstOutput`` whose
+        ``logits`` / ``exit_layer`` / ``confidence`` are, bit for bit, those of ``early_exit`` with the same schedule on the full inputs.
+        One handle, one call: refused with ``micro_batches`` and for a batch above the engine's ``max_docs``."""
+        if pixel_values is None:
+            raise ValueError("early_exit_vision_first: pixel_values is required")
+        if text is None:
+            if input_ids is None:
+                raise ValueError("early_exit_vision_first: pass the text as input_ids / attention_mask / bbox, or text=f(slots) -> dict")
+            text = {k: v for k, v in dict(input_ids=input_ids, attention_mask=attention_mask, bbox=bbox, token_type_ids=token_type_ids,
+                                          position_ids=position_ids).items() if v is not None}
+        elif input_ids is not None:
+            raise ValueError("early_exit_vision_first: text= and input_ids= are two ways to give the text: pass one")
+        self._patience_kw(patience, kw)
+        pat, rule = kw.pop("patience", None), kw.pop("exit_rule", None)
+        if thresholds is None:
+            thresholds = self.config.exit_config["global_threshold"]
+        self._small_batch_schedule(pixel_values, kw)
+        self._sync_exit_config()
+        if hasattr(self.engine, "engines"):
+            raise NotImplementedError("early_exit_vision_first: a vision-first call over micro-batches is not built (the survivors are one "
+                                      "list over one handle's call); build the model without micro_batches")
+        if rule is not None:
+            self.engine.set_exit_rule(rule)
+        if pat is not None:
+            self.engine.set_patience(pat)
+        if int(pixel_values.shape[0]) > self.engine.max_docs:
+            raise ValueError(f"early_exit_vision_first: {int(pixel_values.shape[0])} documents, the engine holds max_docs = "
+                             f"{self.engine.max_docs} (the survivors are one list over one call)")
+        return self.engine.forward_vision_first(pixel_values, text, thresholds=thresholds, temperatures=temperatures, low_latency=low_latency,
+                                                **kw)
+
     def early_exit_stream(self, input_ids=None, attention_mask=None, bbox=None, pixel_values=None, token_type_ids=None,
                           position_ids=None, thresholds: Optional[Union[float, Sequence[float]]] = None,
                           temperatures: Optional[Sequence[float]] = None, patience: Optional[int] = None, low_latency: bool = False,

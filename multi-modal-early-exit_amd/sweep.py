@@ -409,7 +409,7 @@ def threshold_search(logits, references=None, criterion="max_confidence", num_pe
                         semantics=semantics, **extra)
 
 
-def exit_costs(cfg, attention_mask=None, text_rows=None, unit: float = 1e6) -> np.ndarray:
+def exit_costs(cfg, attention_mask=None, text_rows=None, unit: float = 1e6, ocr_cost=None) -> np.ndarray:
     """The path's own cost model, for ``threshold_search(cost=)``: ``(E1, N) uint32``, entry (e, n) = the work of document n when it leaves at
     exit e, in units of ``unit`` FLOPs (``np.rint(F / unit)``).  No device is needed.
 
@@ -420,7 +420,14 @@ def exit_costs(cfg, attention_mask=None, text_rows=None, unit: float = 1e6) -> n
     directly) + ``cfg.visual_len``; for ``arch="beit"`` ``S_n = visual_len`` (N from ``text_rows``' or the mask's length).
 
     This is ALGORITHMIC work, the figure ``roofline.achieved`` divides by: not measured time, and neither the probes nor the exit tail are in
-    it.  ``ValueError`` when an entry would reach 2^32: choose a larger ``unit``."""
+    it.  ``ValueError`` when an entry would reach 2^32: choose a larger ``unit``.
+
+    ``ocr_cost``: what reading a document's text costs, a scalar or ``(N,)`` in the same ``unit`` (already divided by it), finite and >= 0.
+    A vision-first call (``EarlyExitEngine.forward_vision_first``) pays it only for the documents that stay behind ``vision_avg``, so it is
+    added to every exit behind ``vision_avg`` and -- every exit needs the text then -- to none when the exit list has no ``vision_avg``
+    (an image-only model included).  ``None`` (default): the table without it, bit for bit.  ``threshold_search(cost=)``,
+    ``threshold_refine``, ``risk_control(cost=)`` and ``ExitReport.efficiency`` take the table unchanged: which ``thresholds[0]`` is worth
+    how much OCR is then a search that already exists."""
     if (attention_mask is None) == (text_rows is None):
         raise ValueError("exit_costs takes exactly one of attention_mask (N,T) and text_rows (N,)")
     if attention_mask is not None:
@@ -441,6 +448,14 @@ def exit_costs(cfg, attention_mask=None, text_rows=None, unit: float = 1e6) -> n
     patch = 2 * cfg.num_patches * (cfg.num_channels * cfg.patch_size ** 2) * H
     F = patch + np.asarray(layers, dtype=np.int64)[:, None] * per_layer[None, :] + (np.arange(len(layers), dtype=np.int64)[:, None] + 1) * (2 * H * H + 2 * H * K)
     out = np.rint(F / float(unit))
+    if ocr_cost is not None:
+        oc = np.asarray(ocr_cost, dtype=np.float64)
+        if oc.ndim > 1 or (oc.ndim == 1 and oc.shape[0] != rows.shape[0]):
+            raise ValueError(f"exit_costs: ocr_cost is a scalar or ({rows.shape[0]},), one entry per document; got {oc.shape}")
+        if oc.size and (not np.isfinite(oc).all() or oc.min() < 0):
+            raise ValueError("exit_costs: ocr_cost must be finite and >= 0")
+        if len(ee.embedding_exits) and str(ee.embedding_exits[0]) == "vision_avg":
+            out = np.rint(F / float(unit) + np.concatenate([np.zeros((1, rows.shape[0])), np.broadcast_to(oc, (len(layers) - 1, rows.shape[0]))]))
     if out.size and out.max() >= float(1 << 32):
         raise ValueError(f"exit_costs: {out.max():.0f} units of {unit:g} FLOPs do not fit 32 bits: choose a larger unit")
     return out.astype(np.uint32)
