@@ -1513,7 +1513,10 @@ int ee_debug_gemm_split_resid(const float* A, const float* W, const float* bias,
  *                            every forward; Cout and the row maps still hold M rows.  m_on_device == 0: max_m is not read.
  * Refused before any device work: k_splits outside {1, 2, 4, 8} or not a divisor of the K / 32 k-stages (the kernel's integer division would
  * drop the tail); k_splits > 1 with anything but the bias epilogue, an f32 output, three terms and no bias pointer (launch_gemm_split would
- * write ONE part); terms outside {1, 3}; M > max_m; scale_cols no multiple of 64 in [0, N].  ms_out as ee_debug_gemm_split's. */
+ * write ONE part); terms outside {1, 3}; M > max_m; scale_cols no multiple of 64 in [0, N].  ms_out as ee_debug_gemm_split's.
+ *   err_flag_out             NULL: the launches get no error word (as ee_debug_gemm_split and ee_debug_gemm_split_resid run them).  Otherwise a
+ *                            zeroed device word is the err_flag of the GEMM launch and of the launch_split_rows calls that convert A, W and
+ *                            the residual, and its value after the last launch is written here. */
 typedef struct ee_debug_gemm_routes_args {
     const float *A, *W, *bias, *resid;
     float* Cout;
@@ -1530,6 +1533,7 @@ typedef struct ee_debug_gemm_routes_args {
     float scale;
     const float* col_scale;
     int32_t max_m, m_on_device, iters;
+    int32_t* err_flag_out;      /* NULL, or host int32: the error word of the launches (16 = a value left the split planes' range, or is a NaN) */
 } ee_debug_gemm_routes_args;
 int ee_debug_gemm_routes(const ee_debug_gemm_routes_args* args, float* ms_out, void* stream);
 
@@ -1867,6 +1871,20 @@ typedef struct ee_debug_patch_project_args {
     int32_t* err_flag_out;
 } ee_debug_patch_project_args;
 int ee_debug_patch_project(const ee_debug_patch_project_args* args, void* stream);
+
+/* Unit-test hooks of the split-f16 encoders (csrc/mmee_common.h "Split-f16 operand rows"), on caller-provided DEVICE buffers; no handle
+ * (tests/test_gpu_split.py compares their words with tests/split_ref.py bit for bit).
+ * ee_debug_split_rows: ONE launch_split_rows call (the clamp form of the encoder) with a zeroed error word.
+ *   src            f32 [rows][K]; dst_words [rows][K] 32-bit words: the split rows scaled by `scale` (64-byte groups [hi 16 f16 | lo 16 f16])
+ *   err_flag_out   host int32: the kernel's error word (16 = |scale * x| left the planes' range, or x is a NaN)
+ * Refused, not launched: NULL pointers, rows < 0, K no positive multiple of 16, rows K > 2^30, a scale that is not positive and finite.
+ * ee_debug_split_weight: the weight split of ee_finalize (the maximum of |w| on the device, the per-tensor power-of-two scale that puts it
+ * in [2^12, 2^13) capped at 2^8, the clamp-form encoder), as build_split calls it.
+ *   w              f32 [N][K]; dst_words [N][K] 32-bit words; inv_out host float: 1 / scale
+ * Refused, not launched: NULL pointers, N < 1, K no positive multiple of 16, N K > 2^30.  A tensor that holds inf / nan is refused with
+ * ee_finalize's words ("a weight tensor holds inf/nan") and dst_words keeps its bytes.  Both synchronise the stream. */
+int ee_debug_split_rows(const float* src, int32_t rows, int32_t K, float scale, void* dst_words, int32_t* err_flag_out, void* stream);
+int ee_debug_split_weight(const float* w, int32_t N, int32_t K, void* dst_words, float* inv_out, void* stream);
 
 /* Diagnostic of the two-heads-per-item attention kernel (attention_pair.hip): with MMEE_ATTN_STAMPS=1 in the environment the
  * launches run a build with in-kernel s_memtime stamps; this call synchronises, copies the eight phase sums (shader cycles summed over

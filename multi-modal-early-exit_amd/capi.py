@@ -180,7 +180,7 @@ class DebugGemmRoutesArgs(C.Structure):
                 + [("row_src", _vp), ("rows_A", _i32), ("resid_row_src", _vp), ("rows_resid", _i32)]
                 + [(n, _i32) for n in ("route", "role_tag", "probe", "terms", "k_splits")] + [("split_stride", C.c_size_t), ("scale_cols", _i32),
                                                                                              ("scale", C.c_float), ("col_scale", _vp)]
-                + [(n, _i32) for n in ("max_m", "m_on_device", "iters")])
+                + [(n, _i32) for n in ("max_m", "m_on_device", "iters")] + [("err_flag_out", C.POINTER(_i32))])
 
 
 class DebugGemmF32Args(C.Structure):
@@ -301,6 +301,8 @@ SYMBOLS = {
     "ee_debug_exit_ensemble": (C.c_int, [C.POINTER(DebugExitEnsembleArgs), _vp]),
     "ee_debug_rows_out": (C.c_int, [C.POINTER(DebugRowsOutArgs), _vp]),
     "ee_debug_patch_project": (C.c_int, [C.POINTER(DebugPatchProjectArgs), _vp]),
+    "ee_debug_split_rows": (C.c_int, [_vp, _i32, _i32, C.c_float, _vp, C.POINTER(_i32), _vp]),
+    "ee_debug_split_weight": (C.c_int, [_vp, _i32, _i32, _vp, C.POINTER(C.c_float), _vp]),
     "ee_temperature_fit": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ee_head_fit": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _vp]),

@@ -62,9 +62,9 @@ int report_errors(ee_handle* h, int err, const char* whose) {
     if (err & 32)
         return fail(h, "ee_forward: internal error in %s (flags %d): the attention kernel found its dynamic LDS region away from address 0", whose, err);
     if (err & mmee::kErrSplitOverflow)
-        return fail(h, "ee_forward: split-precision overflow in %s (flags %d): an activation left the range of the split-f16 planes (|LayerNorm out|, "
-                       "|Q/sqrt(d)|, |K|, |V|, |GELU out|, |pixel_values| <= 3750, |attention context| <= 937) and was clamped, so its results are WRONG; "
-                       "run this checkpoint with precision \"fp32\"", whose, err);
+        return fail(h, "ee_forward: split-precision overflow or a NaN in %s (flags %d): an activation left the range of the split-f16 planes (|LayerNorm out|, "
+                       "|Q/sqrt(d)|, |K|, |V|, |GELU out|, |pixel_values| <= 3750, |attention context| <= 937) and was clamped, or an input or activation "
+                       "is a NaN, so its results are WRONG; run this checkpoint with precision \"fp32\" (which runs no such check)", whose, err);
     if (err)
         return fail(h, "ee_forward: input out of range in %s (flags %d: 1 = token id, 2 = bbox outside [0, max_2d), 4 = position id, 8 = token_type id); "
                        "its results are invalid", whose, err);
@@ -97,7 +97,7 @@ int split_weight_rows(ee_handle* h, const char* who, const float* w, int N, int 
     float mx = 0.f;
     if (hipMemcpyAsync(&mx, absmax_dev, sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
         return fail(h, "%s: the maximum of a weight tensor could not be read", who);
-    if (!(mx < 3.0e38f)) return fail(h, "%s: a weight tensor holds inf/nan", who);
+    if (!(mx < 3.0e38f)) return fail(h, "%s: a weight tensor holds inf/nan", who);      // launch_absmax hands back inf / a NaN if one element is
     const int e = split_weight_exponent(mx);
     *inv = std::ldexp(1.0f, -e);
     mmee::launch_split_rows(w, out, nullptr, N, N, K, std::ldexp(1.0f, e), num_cus, s);

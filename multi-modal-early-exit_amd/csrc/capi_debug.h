@@ -1,5 +1,5 @@
 // What the ee_debug_* hooks that run one kernel of the path on caller-provided device buffers share (capi_debug_attention.hip,
-// capi_debug_rows.hip, capi_debug_xprobe.hip, capi_debug_exit.hip, capi_debug_patch.hip, capi_debug_vision.hip; the GEMM hooks of capi_tools.hip take the device query and to_host).  Host code with internal linkage:
+// capi_debug_rows.hip, capi_debug_xprobe.hip, capi_debug_exit.hip, capi_debug_patch.hip, capi_debug_split.hip, capi_debug_vision.hip; the GEMM hooks of capi_tools.hip take the device query and to_host).  Host code with internal linkage:
 // the library exports none of it.  What every hook words alike is worded here; the refusals of a document table keep each hook's own words.
 #pragma once
 #include "capi_internal.h"

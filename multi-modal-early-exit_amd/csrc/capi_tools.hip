@@ -638,19 +638,21 @@ static int run_debug_gemm_split(const char* who, const ee_debug_gemm_routes_args
     if (!cus) return 1;
     const bool split_resid = a.resid && a.resid_scale != 0.f;
     float *As = nullptr, *Ws = nullptr, *Rs = nullptr;
-    int *heads = nullptr, *m_dev = nullptr;
+    int *heads = nullptr, *m_dev = nullptr, *err_flag = nullptr;      // err_flag: the launches' error word, for a caller that asks for it
     if (hipMalloc((void**)&As, (size_t)rows_A * K * 4) != hipSuccess || hipMalloc((void**)&Ws, (size_t)N * K * 4) != hipSuccess ||
         hipMalloc((void**)&heads, 512) != hipSuccess || (a.m_on_device && hipMalloc((void**)&m_dev, sizeof(int)) != hipSuccess) ||
-        (split_resid && hipMalloc((void**)&Rs, (size_t)rows_resid * N * 4) != hipSuccess)) {
-        (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads); (void)hipFree(m_dev); (void)hipFree(Rs);
+        (split_resid && hipMalloc((void**)&Rs, (size_t)rows_resid * N * 4) != hipSuccess) ||
+        (a.err_flag_out && (hipMalloc((void**)&err_flag, sizeof(int)) != hipSuccess || hipMemsetAsync(err_flag, 0, sizeof(int), s) != hipSuccess))) {
+        (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads); (void)hipFree(m_dev); (void)hipFree(Rs); (void)hipFree(err_flag);
         return fail(nullptr, "%s: hipMalloc failed", who);
     }
-    mmee::launch_split_rows(a.A, As, nullptr, rows_A, rows_A, K, a.a_scale, cus, s);
-    mmee::launch_split_rows(a.W, Ws, nullptr, N, N, K, a.w_scale, cus, s);
+    g.err_flag = err_flag;
+    mmee::launch_split_rows(a.A, As, nullptr, rows_A, rows_A, K, a.a_scale, cus, s, err_flag);
+    mmee::launch_split_rows(a.W, Ws, nullptr, N, N, K, a.w_scale, cus, s, err_flag);
     // the probes of a forward take their tiles statically (capi_forward.hip layer_probe): no queue head
     g.A = As; g.W = Ws; g.tile_counter = a.probe ? nullptr : heads;
     if (split_resid) {
-        mmee::launch_split_rows(a.resid, Rs, nullptr, rows_resid, rows_resid, N, a.resid_scale, cus, s);
+        mmee::launch_split_rows(a.resid, Rs, nullptr, rows_resid, rows_resid, N, a.resid_scale, cus, s, err_flag);
         g.resid = Rs; g.resid_split_inv = 1.0f / a.resid_scale;
     }
     if (m_dev) {      // (M lives until the synchronisation below)
@@ -692,7 +694,9 @@ static int run_debug_gemm_split(const char* who, const ee_debug_gemm_routes_args
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads); (void)hipFree(m_dev); (void)hipFree(Rs);
+    const bool err_read = !err_flag || hipMemcpy(a.err_flag_out, err_flag, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(As); (void)hipFree(Ws); (void)hipFree(heads); (void)hipFree(m_dev); (void)hipFree(Rs); (void)hipFree(err_flag);
+    if (err == hipSuccess && !err_read) return fail(nullptr, "%s: copy of err_flag failed", who);
     if (err != hipSuccess || hipGetLastError() != hipSuccess) return fail(nullptr, "%s: launch failed: %s", who, hipGetErrorString(err));
     return 0;
 }

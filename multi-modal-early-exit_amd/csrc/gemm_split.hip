@@ -215,11 +215,15 @@ void launch_patch_split(const float* pix, void* dst, int n_docs, int C, int R, i
     hipLaunchKernelGGL(patch_split_kernel, dim3(grid), dim3(256), 0, s, pix, reinterpret_cast<char*>(dst), n_docs * G * G, C, R, P, G, scale, err_flag);
 }
 
+// The maximum is taken over the bit patterns with the sign cleared: non-negative floats order as uints, inf lies above every finite value
+// and a NaN above inf, so *out is the exact max |src[i]| of a finite tensor and inf / a NaN as soon as one element is (fmaxf dropped a NaN:
+// split_weight_rows then let a NaN weight through and split_rows_kernel clamped it to -60000).
 __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ src, size_t n, float* __restrict__ out) {
-    float m = 0.f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) m = fmaxf(m, fabsf(src[i]));
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned*>(out), __float_as_uint(m));   // non-negative floats order as uints
+    unsigned m = 0u;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) m = max(m, __float_as_uint(src[i]) & 0x7fffffffu);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned*>(out), m);
 }
 
 void launch_absmax(const float* src, size_t n, float* out_dev, hipStream_t s) {

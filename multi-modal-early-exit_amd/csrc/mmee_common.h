@@ -309,14 +309,20 @@ __device__ __forceinline__ f32x2 gelu_scaled2(const f32x2 x, const float c0, con
 // ---------------------------------------------------------------------------------------------------------------
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 constexpr float kSplitClamp = 60000.0f;     // < 65504 = largest finite f16
-constexpr int kErrSplitOverflow = 16;       // err_flag bit: a value left the range of the split-f16 planes (it was clamped)
-// `amax` collects max |scale * x| BEFORE the clamp (one v_max3_f32 per pair): the caller raises kErrSplitOverflow in the
-// handle's err_flag when it exceeds kSplitClamp, so that a clamped (= wrong) result never goes unnoticed.
+constexpr int kErrSplitOverflow = 16;       // err_flag bit: a value left the range of the split-f16 planes (it was clamped), or was a NaN
+// `amax` collects max |scale * x| BEFORE the clamp: the caller raises kErrSplitOverflow in the handle's err_flag when it exceeds
+// kSplitClamp, so that a clamped (= wrong) result never goes unnoticed.  The maximum is the NaN-propagating one (split_amax: llvm.maximum,
+// ONE v_maximum3_f32 per pair on gfx950, where fmaxf was one v_max3_f32): fmaxf returns its other operand for a NaN, so a NaN element never
+// reached amax -- the clamp below then made -60000 of it (v_med3_f32 with a NaN returns the smallest operand), split_pair kept it as a NaN
+// in the planes, and neither raised the flag.  Once amax is a NaN it stays one, and split_flag_overflow's !(amax <= clamp) is true for it.
+__device__ __forceinline__ float split_amax(float amax, float x0, float x1) {
+    return __builtin_elementwise_maximum(amax, __builtin_elementwise_maximum(__builtin_fabsf(x0), __builtin_fabsf(x1)));
+}
 __device__ __forceinline__ void split_f16x4(const f32x4& v, float scale, f16x4& hi, f16x4& lo, float& amax) {
 #pragma unroll
     for (int t = 0; t < 4; t += 2) {          // pairs: v_pk_mul_f32, v_cvt_pk_f16_f32, v_pk_add_f32
         f32x2 x = f32x2{v[t], v[t + 1]} * (f32x2)(scale);
-        amax = fmaxf(amax, fmaxf(fabsf(x[0]), fabsf(x[1])));
+        amax = split_amax(amax, x[0], x[1]);
         x = __builtin_elementwise_min(__builtin_elementwise_max(x, (f32x2)(-60000.0f)), (f32x2)(60000.0f));
         const f16x2 h = __builtin_convertvector(x, f16x2);
         const f32x2 hf = __builtin_convertvector(h, f32x2);
@@ -325,12 +331,13 @@ __device__ __forceinline__ void split_f16x4(const f32x4& v, float scale, f16x4& 
         lo[t] = l[0]; lo[t + 1] = l[1];
     }
 }
-// Round 4, the GEMM epilogues' form: (x0, x1) ALREADY scaled -> packed hi pair and packed lo pair in 4 instructions (v_max3_f32,
+// Round 4, the GEMM epilogues' form: (x0, x1) ALREADY scaled -> packed hi pair and packed lo pair in 4 instructions (v_maximum3_f32,
 // v_cvt_pk_f16_f32, and lo = f16(x - float(hi)) by one v_fma_mixlo / mixhi_f16 each: fma(x, 1.0, -hi) in f32 is exact and rounds once) against
 // 11 for the form above.  No clamp: |x| > 65504 becomes inf in the hi plane and the forward is REFUSED through kErrSplitOverflow exactly as
-// before (amax sees every element); values in (60000, 65504] are now converted correctly instead of clamped.
+// before (amax sees every element); values in (60000, 65504] are now converted correctly instead of clamped.  A NaN stays a NaN in both
+// planes and is refused the same way.
 __device__ __forceinline__ void split_pair(const float x0, const float x1, unsigned& hb, unsigned& lb, float& amax) {
-    amax = fmaxf(amax, fmaxf(fabsf(x0), fabsf(x1)));
+    amax = split_amax(amax, x0, x1);
     const f16x2 h = __builtin_convertvector(f32x2{x0, x1}, f16x2);
     hb = __builtin_bit_cast(unsigned, h);
     asm("v_fma_mixlo_f16 %0, %1, 1.0, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
@@ -340,10 +347,12 @@ __device__ __forceinline__ void split_pair(const float x0, const float x1, unsig
         : "=&v"(lb)
         : "v"(x0), "v"(x1), "v"(hb));
 }
-// store 4 consecutive columns [col, col+4) (col % 4 == 0) of a split row
+// What every kernel that encodes does with its amax when it is done: a value beyond the clamp, +-inf or a NaN (amax is then a NaN: split_amax)
+// raises kErrSplitOverflow
 __device__ __forceinline__ void split_flag_overflow(float amax, int* err_flag) {
-    if (err_flag && !(amax <= kSplitClamp)) atomicOr(err_flag, kErrSplitOverflow);      // NaN counts as overflow
+    if (err_flag && !(amax <= kSplitClamp)) atomicOr(err_flag, kErrSplitOverflow);
 }
+// store 4 consecutive columns [col, col+4) (col % 4 == 0) of a split row
 __device__ __forceinline__ void store_split4(void* row_base, int col, const f32x4& v, float scale, float& amax) {
     f16x4 hi, lo;
     split_f16x4(v, scale, hi, lo, amax);

@@ -425,7 +425,7 @@ __global__ __launch_bounds__(256) void xprobe_v_kernel(const XProbeArgs a) {
             const int d = d0 + 4 * kq + r;
             if (d < n_docs) {
                 const float v = (sum[j][r] * inv + bias) * a.ctx_scale;
-                amax = fmaxf(amax, fabsf(v));
+                amax = split_amax(amax, v, v);      // (a NaN reaches the flag: mmee_common.h)
                 const float vc = fminf(fmaxf(v, -kSplitClamp), kSplitClamp);
                 const _Float16 hi = (_Float16)vc;
                 const _Float16 lo = (_Float16)(vc - (float)hi);

@@ -1,5 +1,6 @@
-"""What the eleven stand-alone kernel hooks (ee_debug_attention, ee_debug_xprobe, ee_debug_prep, ee_debug_embed, ee_debug_ln_rows,
-ee_debug_head_out, ee_debug_exit_decide, ee_debug_rows_out, ee_debug_patch_project, ee_debug_gemm_routes, ee_debug_gemm_f32) refuse before they ask for a device: every refusal below is decided on the host from the arguments alone, so the message is asserted whole, on a machine
+"""What the thirteen stand-alone kernel hooks (ee_debug_attention, ee_debug_xprobe, ee_debug_prep, ee_debug_embed, ee_debug_ln_rows,
+ee_debug_head_out, ee_debug_exit_decide, ee_debug_rows_out, ee_debug_patch_project, ee_debug_gemm_routes, ee_debug_gemm_f32, ee_debug_split_rows,
+ee_debug_split_weight) refuse before they ask for a device: every refusal below is decided on the host from the arguments alone, so the message is asserted whole, on a machine
 without a GPU too.  The pointers are fake and never dereferenced: every call in this file is refused first."""
 import ctypes as C
 
@@ -385,6 +386,17 @@ def test_gemm_routes_refusals(pkg):
     ]
     for over, text in cases:
         _refused(pkg, who, call(**over), text, over)
+    # the error word is an output like ms_out: asking for it changes no refusal
+    err = C.c_int32(-1)
+    for over, text in cases:
+        a = _struct(pkg.capi.DebugGemmRoutesArgs, optional, **dict(dict(M=129, N=768, K=768, epi=0, out_split=0, a_scale=16.0, w_scale=256.0, out_scale=1.0,
+                                                                        resid_scale=0.0, rows_A=300, rows_resid=0, route=0, role_tag=0, probe=0, terms=3,
+                                                                        k_splits=1, split_stride=0, scale_cols=0, scale=1.0, max_m=0, m_on_device=0, iters=1),
+                                                                   **over))
+        a.err_flag_out = C.pointer(err)
+        _refused(pkg, who, lib.ee_debug_gemm_routes(C.byref(a), None, None), text, ("err_flag_out", over))
+    assert err.value == -1
+    assert pkg.capi.DebugGemmRoutesArgs._fields_[-1][0] == "err_flag_out"          # appended: every field before it keeps its offset
     # what the hook lets through is what the rule of MMEE_FLAG_LOW_LATENCY produces: its S divides the k-stages (tests/test_host_gemm_routes.py)
 
 
@@ -428,3 +440,49 @@ def test_gemm_f32_refusals(pkg):
     ]
     for over, text in cases:
         _refused(pkg, who, call(**over), text, over)
+
+
+def test_split_rows_refusals(pkg):
+    lib, who = pkg.capi.load(), "ee_debug_split_rows"
+    err = C.c_int32(-1)
+
+    def call(**over):
+        a = dict(src=P, rows=3, K=256, scale=16.0, dst=P, err=C.byref(err))
+        a.update(over)
+        return lib.ee_debug_split_rows(*a.values(), None)
+
+    null = "src, dst_words and err_flag_out must not be NULL"
+    shape = "bad shape (rows >= 0, K a positive multiple of 16, rows K <= 2^30), got rows %d, K %d"
+    scale = "scale must be positive and finite"
+    cases = [
+        (dict(src=None), null), (dict(dst=None), null), (dict(err=None), null), (dict(src=None, K=8), null),      # the pointers before the shape
+        (dict(rows=-1), shape % (-1, 256)), (dict(K=0), shape % (3, 0)), (dict(K=8), shape % (3, 8)), (dict(K=24), shape % (3, 24)),
+        (dict(K=-16), shape % (3, -16)), (dict(K=260), shape % (3, 260)), (dict(rows=1 << 23, K=256), shape % (1 << 23, 256)),
+        (dict(K=24, scale=0.0), shape % (3, 24)),                               # the shape before the scale
+        (dict(scale=0.0), scale), (dict(scale=-16.0), scale), (dict(scale=float("nan")), scale), (dict(scale=float("inf")), scale),
+        (dict(scale=float("-inf")), scale),
+    ]
+    for over, text in cases:
+        _refused(pkg, who, call(**over), text, over)
+    assert err.value == -1
+
+
+def test_split_weight_refusals(pkg):
+    lib, who = pkg.capi.load(), "ee_debug_split_weight"
+    inv = C.c_float(-1.0)
+
+    def call(**over):
+        a = dict(w=P, N=8, K=64, dst=P, inv=C.byref(inv))
+        a.update(over)
+        return lib.ee_debug_split_weight(*a.values(), None)
+
+    null = "w, dst_words and inv_out must not be NULL"
+    shape = "bad shape (N >= 1, K a positive multiple of 16, N K <= 2^30), got N %d, K %d"
+    cases = [
+        (dict(w=None), null), (dict(dst=None), null), (dict(inv=None), null), (dict(w=None, N=0), null),
+        (dict(N=0), shape % (0, 64)), (dict(N=-2), shape % (-2, 64)), (dict(K=0), shape % (8, 0)), (dict(K=40), shape % (8, 40)),
+        (dict(K=-64), shape % (8, -64)), (dict(N=1 << 20, K=2048), shape % (1 << 20, 2048)),
+    ]
+    for over, text in cases:
+        _refused(pkg, who, call(**over), text, over)
+    assert inv.value == -1.0
