@@ -292,6 +292,49 @@ enum { MMEE_QUOTA_OFF = 0, MMEE_QUOTA_EXACT = 1, MMEE_QUOTA_AT_LEAST = 2 };
  * in the forward (ee_rolling_control takes any 0 / 1 table); a per-exit (conditional) risk; step-size schedules; one controller shared across
  * ranks.
  */
+/*
+ * Deadline exits (ee_set_deadline; EarlyExitEngine.set_deadline, request_cut, deadline_log): anytime prediction -- Huang et al., "Multi-scale
+ * dense networks for resource efficient image classification" (ICLR 2018) -- next to the budgeted batch setting of the quotas: a clock on the
+ * device, or the host, releases everybody who is still in the batch at the next exit.  THE definition (the forward's launches, the
+ * stand-alone hook ee_debug_deadline_check and the numpy restatement of tests/deadline_ref.py refer to it).
+ * A handle may carry a deadline: a budget in ns and eta_ns[E1], uint64.  A deadline call is an eager ee_forward on such a handle without
+ * MMEE_FLAG_NO_EXIT; the handle numbers them k = 1, 2, ... over its lifetime.
+ * Begin.  The call's first launch, deadline_begin_kernel, reads t0 from the 100 MHz counter s_memrealtime (one counter chip-wide: measured,
+ * profiles/deadline.txt), copies the call's thresholds -- a kernel argument, E1 <= 64 -- into the device vector dl_thr[E1] and marks "no cut".
+ * Every decide launch of the call reads its threshold at dl_thr[exit].
+ * Check.  In front of the decide launch of every exit e runs deadline_check_kernel, one workgroup of one wave.  elapsed = ((now - t0) mod 2^64)
+ * ticks in ns: with r kHz the runtime's wall-clock rate (hipDeviceAttributeWallClockRate), (d / r) 10^6 + (d % r) 10^6 / r in integers,
+ * 2^64 - 1 where that would not fit.  It goes to the log.  At e < E1 - 1, if the call has not been cut yet, the kernel cuts when
+ *   budget != MMEE_DEADLINE_NONE and sat_add(elapsed, eta_ns[e]) >= budget        (cut_by 1; sat_add saturates at 2^64 - 1), else when
+ *   the host's request word >= k                                                  (cut_by 2; ee_request_cut).
+ * A cut writes the value that fires for everybody into dl_thr[e .. E1 - 2] -- -inf under the `>` criteria, +inf under entropy, the mirror image
+ * of the controller's never-fires value -- and records cut_exit = e.  It is sticky: later checks of the call only stamp.  The final exit's
+ * check stamps and writes nothing else.
+ * Result.  A cut call returns, bit for bit, what ee_forward returns under thresholds thr' with thr'[e] = thr[e] for e < cut_exit and the
+ * always-fires value from cut_exit on: the cut documents leave through the ordinary decide launch, with the ordinary row of the exit they
+ * stand at (ensembled row, temperature, confidence and result stream as ever).  The test is strict, so a NaN criterion does not fire under
+ * -inf / +inf either: such a document runs to the final exit, as everywhere else.
+ * Lookahead.  eta_ns[e] is the caller's estimate of the time from the decision at exit e to the end of the call IF NOBODY IS CUT THERE, so the
+ * cut falls at the last exit the budget still allows, not at the first one after it has passed.  NULL means zeros.  deadline.eta_from_logs
+ * builds the table from the logs of uncut calls.  budget = MMEE_DEADLINE_NONE: the clock never cuts; the calls are stamped and obey
+ * ee_request_cut only.
+ * Host cut.  ee_request_cut stores the number of deadline calls enqueued on the handle so far into a pinned, mapped host word, which the check
+ * reads with a relaxed system-scope atomic load: every call already enqueued is cut at its next check, none enqueued later.  Any thread, no
+ * HIP call; the word only ever grows (a compare-and-swap maximum), so concurrent requesters cannot take a request back.  A call that
+ * ee_forward refuses is not numbered and writes no log row.  How many checks of a running call still see the old word is timing; that the call then equals thr' of its logged cut_exit is not.
+ * Log.  A device ring of log_cap rows of 4 + E1 64-bit words: call number k, budget_ns, cut_exit (-1: none), cut_by (0, 1 clock, 2 host),
+ * elapsed_ns[E1] at every check.  The stamps behind the cut are kept: elapsed[E1 - 1] - elapsed[cut_exit] is the tail of empty launches.
+ * Dump-all calls (MMEE_FLAG_NO_EXIT) ignore the deadline: no launch is added, no row written, no call counted.  A handle without a deadline
+ * issues the launches it issued before and returns the same bits.
+ * Allowed unchanged: the four threshold criteria (gate included), temperatures, an ensemble, MMEE_FLAG_LOW_LATENCY, MMEE_FLAG_STREAM_RESULTS,
+ * ramp, gate and DiT handles, 1- and 2-layer heads.
+ * Refused, each with a message and nothing changed: E1 > 64; MMEE_CRIT_PATIENCE, an exit rule other than MMEE_RULE_PLAIN, use_lte (a cut must
+ * fire at once, and their decisions carry state or another score); quotas in either mode; an audit or a controller (shadows would run past the
+ * cut) -- each in either order of setting; ee_graph_capture while a deadline is set, ee_set_deadline while graphs are held;
+ * ee_forward_vision; a device whose runtime reports a wall-clock rate of 0.  The Python MicroBatchedEngine and CascadeEngine refuse a deadline.
+ * Not built: deadlines in captured graphs; an absolute deadline shared across calls (it needs a host <-> device clock correlation); deadlines
+ * under quotas, audits or the patience rules; forcing out NaN documents; a learned eta.
+ */
 /* model family: LayoutLMv3 (text + layout + image, the reference's EE model) or BEiT / DiT (image only; BASELINE configs[4],
  * the reference's "dit" branch EE/configs.py:429-449 — exit heads there are this build's extrapolation) */
 enum { MMEE_ARCH_LAYOUTLMV3 = 0, MMEE_ARCH_BEIT = 1 };
@@ -668,6 +711,27 @@ int ee_controller_log(ee_handle* h, int64_t* rows_out, int32_t cap, int32_t* n, 
  * ee_set_controller. */
 int ee_rolling_control(const double* table, double sign, const uint8_t* bad, int32_t E1, int32_t N, const double* path, int32_t V, uint64_t cut,
                        uint32_t seed, double alpha, double gamma, double p0, int32_t G, int32_t* exits, int64_t* log, double* p_out, void* stream);
+
+/* The deadline (deadline exits, definition above, behind the controller's) of every LATER ee_forward.  budget_ns: the budget of a call from its
+ * begin launch; MMEE_DEADLINE_NONE: stamp and obey ee_request_cut, never cut by the clock; MMEE_DEADLINE_OFF: remove the deadline (eta_ns is
+ * then not read).  eta_ns HOST uint64 [E1], copied, or NULL for zeros.  Budget and eta travel as kernel arguments, so a handle that has a
+ * deadline takes a new one without synchronising (EarlyExitEngine.forward(deadline_ms=) does); the first ee_set_deadline of a handle
+ * allocates (ee_set_deadline_log with MMEE_DEADLINE_LOG_DEFAULT rows).  Refusals: the definition's list.
+ * ee_set_deadline_log: log_cap rows for the device ring log, 0 for none; restarts the log.  Synchronises the device.  On a handle without a
+ * deadline it refuses what ee_set_deadline refuses, in its words.
+ * ee_has_deadline: 1 while one is set.
+ * ee_request_cut: cut every deadline call enqueued on h so far at its next check, none enqueued later.  Any thread; no HIP call; returns 1
+ * (and does nothing) on a handle that never had a deadline.
+ * ee_deadline_log: synchronises the stream; *n = rows the ring holds (min(deadline calls since the log's restart, log_cap)); the latest
+ * min(*n, cap) of them, oldest first, into rows_out HOST int64 (cap, 4 + E1).  The log outlives ee_set_deadline(h, MMEE_DEADLINE_OFF, NULL). */
+#define MMEE_DEADLINE_NONE 0xFFFFFFFFFFFFFFFFull
+#define MMEE_DEADLINE_OFF 0xFFFFFFFFFFFFFFFEull
+#define MMEE_DEADLINE_LOG_DEFAULT 1024
+int ee_set_deadline(ee_handle* h, uint64_t budget_ns, const uint64_t* eta_ns);
+int ee_set_deadline_log(ee_handle* h, int32_t log_cap);
+int ee_has_deadline(const ee_handle* h);
+int ee_request_cut(ee_handle* h);
+int ee_deadline_log(ee_handle* h, int64_t* rows_out, int32_t cap, int32_t* n, void* stream);
 
 /* Pin the exit-layer schedule.  DEFAULT (enabled == 0): every layer that ends in a decision is probed first.  Rounds 2-4 chose per layer
  * from the stage populations of "the handle's most recent FINISHED forward" -- a timing-dependent host decision, and under MMEE_FLAG_XPROBE
@@ -1850,6 +1914,22 @@ typedef struct ee_debug_controller_step_args {
     int32_t log_cap;
 } ee_debug_controller_step_args;
 int ee_debug_controller_step(const ee_debug_controller_step_args* args, void* stream);
+/* ee_debug_deadline_check: the check launch of a deadline call (deadline exits, definition behind the controller's) alone, with the clock
+ *   injected: the kernel takes `now` and `t0` (ticks of a counter at khz kHz) instead of reading s_memrealtime and state[0], so every branch
+ *   runs without timing.  state dev int64 [3]: t0 (not read here), cut_exit (-1: not cut yet), cut_by, updated; thr dev float64 [E1]:
+ *   entries exit_index .. E1 - 2 receive the always-fires value of `sign` when this check cuts; row dev int64 [4 + E1] or NULL: a log row,
+ *   elapsed_ns[exit_index] and, at a cut, cut_exit / cut_by are written; host_word: the value the host's request word holds.
+ *   Refused: NULL pointers, E1 outside [2, 64], exit_index outside [0, E1), khz == 0, a sign that is not +-1, call == 0. */
+typedef struct ee_debug_deadline_check_args {
+    int32_t E1, exit_index;
+    uint32_t khz;
+    double sign;
+    uint64_t call, budget_ns, eta_ns, host_word, now, t0;
+    int64_t* state;
+    double* thr;
+    int64_t* row;
+} ee_debug_deadline_check_args;
+int ee_debug_deadline_check(const ee_debug_deadline_check_args* args, void* stream);
 
 /* Unit-test hook of the patch projection (Conv2d with kernel = stride = patch as a GEMM over flattened patches), the counterpart of
  * ee_debug_attention: what patch_projection() of the forward launches, on caller-provided DEVICE buffers; no handle.

@@ -34,4 +34,7 @@ from .audit import AuditSample, ConsistencyReport  # noqa: F401,E402
 from . import risk  # noqa: F401,E402
 from .risk import RiskResult, RollingResult, risk_control, rolling_control  # noqa: F401,E402
 from .engine import ControllerLog  # noqa: F401,E402
+from . import deadline  # noqa: F401,E402
+from .engine import DeadlineLog  # noqa: F401,E402
+from .deadline import eta_from_logs, eta_to_next_exit  # noqa: F401,E402
 from .engine import VisionFirstOutput, VisionPhase  # noqa: F401,E402

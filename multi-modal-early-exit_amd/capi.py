@@ -154,6 +154,22 @@ def controller_log_words(E1: int) -> int:
     return 5 + 2 * (E1 - 1) + E1
 
 
+class DebugDeadlineCheckArgs(C.Structure):
+    """ee_debug_deadline_check_args of include/mmee.h: the check launch of a deadline call with an injected clock; state / thr / row on the device."""
+    _fields_ = ([("E1", _i32), ("exit_index", _i32), ("khz", _u32), ("sign", C.c_double)]
+                + [(n, C.c_uint64) for n in ("call", "budget_ns", "eta_ns", "host_word", "now", "t0")] + [(n, _vp) for n in ("state", "thr", "row")])
+
+
+DEADLINE_NONE = 2 ** 64 - 1    # MMEE_DEADLINE_NONE: stamp, never cut by the clock
+DEADLINE_OFF = 2 ** 64 - 2     # MMEE_DEADLINE_OFF: remove the deadline
+DL_STATE_WORDS = 3             # t0 (ticks), cut_exit, cut_by
+
+
+def deadline_log_words(E1: int) -> int:
+    """64-bit words of a deadline log row (include/mmee.h): call, budget_ns, cut_exit, cut_by, elapsed_ns[E1]."""
+    return 4 + E1
+
+
 class DebugExitEnsembleArgs(C.Structure):
     """ee_debug_exit_ensemble_args of include/mmee.h: device pointers (or None), this exit's temperature and sizes."""
     _fields_ = ([("pol_logits", _vp)] + [(n, _i32) for n in ("pol_rows", "K", "E1", "exit_index", "B")] + [("temp", C.c_double), ("by_pointer", _i32)]
@@ -246,6 +262,12 @@ SYMBOLS = {
                                      _vp, _vp, _vp]),
     "ee_debug_audit_tally": (C.c_int, [C.POINTER(DebugAuditTallyArgs), _vp]),
     "ee_debug_controller_step": (C.c_int, [C.POINTER(DebugControllerStepArgs), _vp]),
+    "ee_set_deadline": (C.c_int, [_vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ee_set_deadline_log": (C.c_int, [_vp, _i32]),
+    "ee_has_deadline": (C.c_int, [_vp]),
+    "ee_request_cut": (C.c_int, [_vp]),
+    "ee_deadline_log": (C.c_int, [_vp, _vp, _i32, C.POINTER(_i32), _vp]),
+    "ee_debug_deadline_check": (C.c_int, [C.POINTER(DebugDeadlineCheckArgs), _vp]),
     "ee_suggest_probe_mask": (C.c_int, [_vp, _u32, C.POINTER(C.c_uint64), _vp]),
     "ee_clock_stamp": (C.c_int, [_vp, _vp]),
     "ee_set_inputs_embeds": (C.c_int, [_vp, _vp]),

@@ -189,6 +189,9 @@ class CascadeEngine:
     def _run_stage(self, s, arrays, n, out, thr, tmp, flags):
         """Stage s on n documents in consecutive chunks of at most its max_docs (documents are independent), results into row slices of `out`."""
         eng = self.stages[s]
+        if getattr(eng, "has_deadline", None) and eng.has_deadline():
+            raise ValueError(f"stage {s} has a deadline set: deadlines on cascade stages are not built (a stage runs in chunks, each of which "
+                             "would start a clock of its own, and the cascade's budget spans its stages); set_deadline(None) on the stage's engine")
         if getattr(eng, "has_controller", None) and eng.has_controller():
             raise ValueError(f"stage {s} has a controller set: online exit control on cascade stages is not built (a stage's calls are the deferred "
                              "documents of another); set_controller(None) on the stage's engine")

@@ -529,6 +529,7 @@ int ee_destroy(ee_handle* h) {
     for (auto& es : h->errs) if (es.done) (void)hipEventDestroy(es.done);
     for (auto& ev : h->stream_ev) (void)hipEventDestroy(ev);
     if (h->stream_host) (void)hipHostFree(h->stream_host);
+    if (h->dl_word) (void)hipHostFree(h->dl_word);
     for (void* q : h->allocs) (void)hipFree(q);
     delete h;
     return 0;

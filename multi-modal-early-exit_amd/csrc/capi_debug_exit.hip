@@ -1,5 +1,6 @@
 // ee_debug_head_out, ee_debug_exit_ensemble, ee_debug_exit_decide, ee_debug_exit_quota, ee_debug_exit_audit, ee_debug_rows_out: the exit stage of exit_stage.hip alone,
-// and ee_debug_audit_tally, ee_debug_controller_step: the controller's two launches (controller.hip) alone, on caller-provided
+// and ee_debug_audit_tally, ee_debug_controller_step: the controller's two launches (controller.hip) alone, and ee_debug_deadline_check: the
+// deadline's check launch (deadline.hip) with an injected clock, on caller-provided
 // device buffers; no handle.  Each entry point makes the calls of the path's own launchers that capi_forward.hip makes (launch_head_out;
 // launch_exit_ensemble; launch_decide -- under a quota launch_exit_quota_crit, launch_exit_quota_rank and launch_decide_quota -- and, behind it,
 // launch_compact_rows as compact() does; launch_gather_cls / launch_rows_to_padded) and synchronises.  No kernel is defined or
@@ -298,6 +299,31 @@ int ee_debug_controller_step(const ee_debug_controller_step_args* a, void* strea
     st.state = reinterpret_cast<long long*>(a->state); st.tally = reinterpret_cast<const long long*>(a->tally); st.thr = a->thr;
     st.log = reinterpret_cast<long long*>(a->log); st.log_cap = a->log ? a->log_cap : 0;
     launch_controller_step(st, s);
+    return finish(who, s, nullptr, nullptr);
+}
+
+int ee_debug_deadline_check(const ee_debug_deadline_check_args* a, void* stream) {
+    const char* who = "ee_debug_deadline_check";
+    if (!a) return fail(nullptr, "%s: args must not be NULL", who);
+    if (!a->state || !a->thr) return fail(nullptr, "%s: state and thr must not be NULL", who);
+    if (a->E1 < 2 || a->E1 > kCtlMaxE1) return fail(nullptr, "%s: E1 = %d, need 2 <= E1 <= %d", who, a->E1, kCtlMaxE1);
+    if (a->exit_index < 0 || a->exit_index >= a->E1) return fail(nullptr, "%s: exit_index %d outside [0, E1 = %d)", who, a->exit_index, a->E1);
+    if (a->khz == 0) return fail(nullptr, "%s: khz is 0: ticks cannot be turned into ns", who);
+    if (a->sign != 1.0 && a->sign != -1.0) return fail(nullptr, "%s: sign is +1 or -1", who);
+    if (a->call == 0) return fail(nullptr, "%s: call is 0 (deadline calls are numbered from 1)", who);
+    if (!have_device(who)) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (hipStreamSynchronize(s) != hipSuccess) return fail(nullptr, "%s: the stream is in error", who);
+    Scratch sc;
+    unsigned long long* word = nullptr;                                  // the forward's is pinned host memory; the load is the same
+    if (!sc.get(&word, 1)) return fail(nullptr, kScratchFailed, who);
+    const unsigned long long w = a->host_word;
+    if (hipMemcpy(word, &w, sizeof(w), hipMemcpyHostToDevice) != hipSuccess) return fail(nullptr, kUploadFailed, who);
+    DeadlineCheckArgs k{};
+    k.E1 = a->E1; k.exit_index = a->exit_index; k.khz = a->khz; k.sign = a->sign; k.call = a->call; k.budget = a->budget_ns; k.eta = a->eta_ns;
+    k.host_word = word; k.state = reinterpret_cast<long long*>(a->state); k.thr = a->thr; k.row = reinterpret_cast<long long*>(a->row);
+    k.now_set = 1; k.t0_set = 1; k.now = a->now; k.t0 = a->t0;
+    launch_deadline_check(k, s);
     return finish(who, s, nullptr, nullptr);
 }
 

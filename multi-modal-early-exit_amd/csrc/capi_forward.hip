@@ -207,6 +207,10 @@ struct Forward {
     const bool ctl = h->ctl_on && !no_exit;
     const float* fin_pol = nullptr;          // the rows the final exit's decide launch read, and the temperature it scaled them by
     double fin_temp = 1.0;
+    // deadline exits (ee_set_deadline): deadline_begin_kernel opens the call, every decide launch reads its threshold at h->dl_thr and
+    // deadline_check_kernel runs in front of each.  A dump-all call ignores the deadline: no launch added, no log row, no call counted
+    const bool dl = h->dl_on && !no_exit;
+    uint64_t dl_call = 0;                    // this call's number (1-based), set by deadline_begin
     // split precision attention: attention_idx.hip (pair index built once per forward; default) or, with MMEE_ATTN_V=2 or bucket tables
     // beyond 64 bins, attention_pair.hip (clamped Delta tables gathered per layer and head)
     const bool use_idx = sp && attn_variant() == 0 && c.rel_pos_bins <= 64 && c.rel_2d_pos_bins <= 64;
@@ -257,6 +261,12 @@ struct Forward {
         if (ctl && stream_results)
             return fail(h, "ee_forward: MMEE_FLAG_STREAM_RESULTS while a controller is set: its audit keeps delivered documents in the stage, which "
                            "emit_leavers cannot tell from the ones that stay (not built; ee_set_controller(h, NULL, ...) first)");
+        if (dl && cap)
+            return fail(h, "ee_graph_capture: a deadline is set: the call number and the budget travel by value and the begin launch stamps the "
+                           "call's own start, so deadline calls are eager (not built; ee_set_deadline(h, MMEE_DEADLINE_OFF, NULL) first)");
+        if (dl && (patience || h->rule != MMEE_RULE_PLAIN || c.use_lte || h->quota_mode != MMEE_QUOTA_OFF || h->audit_cut || ctl))
+            return fail(h, "ee_forward: a deadline is set together with MMEE_CRIT_PATIENCE, a non-plain exit rule, use_lte, quotas, an audit or a "
+                           "controller: a cut must fire at once and for everybody (ee_set_deadline(h, MMEE_DEADLINE_OFF, NULL) first)");
         if (h->quota_mode != MMEE_QUOTA_OFF && (patience || h->rule != MMEE_RULE_PLAIN || c.use_lte))
             return fail(h, "ee_forward: quotas are set, and no rank is defined under MMEE_CRIT_PATIENCE, MMEE_RULE_STREAK / MMEE_RULE_EITHER or use_lte "
                            "(ee_set_quotas(h, NULL, 0, 0) first)");
@@ -675,6 +685,7 @@ struct Forward {
         d.temp = a.temperatures ? a.temperatures[exit_index] : 1.0;
         if (cap) { d.thr_ptr = cap->thr_dev; d.temp_ptr = cap->thr_dev + (E + 1); }      // replays read the vector of THEIR launch
         if (ctl) d.thr_ptr = h->ctl_thr_dev;                                             // the vector the previous call's step left
+        if (dl) d.thr_ptr = h->dl_thr;                                                   // the call's own thresholds until a check cuts
         if (h->ens_on) {
             // exit ensemble (ee_set_ensemble): y_m of every active document into a second policy buffer; the decision reads that with temperature 1
             EnsembleArgs en{};
@@ -701,6 +712,7 @@ struct Forward {
             if (cap) pa.t_ptr = cap->thr_dev + 2 * (E + 1) + exit_index;                  // replays read the patience of THEIR launch
             pa.prev = h->pat_state; pa.run = h->pat_state + c.max_docs;
         }
+        if (dl) deadline_check();                                                        // right before the decide launch
         if (h->quota_mode != MMEE_QUOTA_OFF && !no_exit && !is_final) {
             // budgeted exits (ee_set_quotas): the stage's criteria and ranks into the scratch, then the QUOTA form of the decide kernel.  The final
             // exit takes everybody and a dump keeps everybody: the plain kernels below, no launch added
@@ -828,6 +840,25 @@ struct Forward {
         ++next_enc;
     }
 
+    // deadline exits: the call's number, its start on the device clock, its thresholds into h->dl_thr, the head of its log row
+    long long* deadline_row() const {
+        return h->dl_log_cap > 0 ? h->dl_log + (size_t)((dl_call - 1) % (uint64_t)h->dl_log_cap) * deadline_log_words(E + 1) : nullptr;
+    }
+    void deadline_begin() {
+        dl_call = __atomic_add_fetch(&h->dl_calls, 1, __ATOMIC_RELAXED);
+        DeadlineBeginArgs b{};
+        for (int e = 0; e <= E; ++e) b.thr_in[e] = a.thresholds[e];
+        b.E1 = E + 1; b.call = dl_call; b.budget = h->dl_budget; b.state = h->dl_state; b.thr = h->dl_thr; b.row = deadline_row();
+        { ProfScope ps(h, P_DEADLINE, s); launch_deadline_begin(b, s); }
+    }
+    void deadline_check() {
+        DeadlineCheckArgs k{};
+        k.E1 = E + 1; k.exit_index = exit_index; k.khz = h->dl_khz; k.sign = crit_sign(c.criterion);
+        k.call = dl_call; k.budget = h->dl_budget; k.eta = h->dl_eta[exit_index]; k.host_word = h->dl_word_dev;
+        k.state = h->dl_state; k.thr = h->dl_thr; k.row = deadline_row();
+        { ProfScope ps(h, P_DEADLINE, s); launch_deadline_check(k, s); }
+    }
+
     // online exit control: what the audit saw in this call (the final stage is still `cur`: the final exit compacts nothing), then the step
     // and the thresholds of the next call.  The call's seed is the one its decide launches audited under.
     void control() {
@@ -871,11 +902,7 @@ struct Forward {
         }
         if (!cap) { const int rc_pre = forward_pre(h, s); if (rc_pre) return rc_pre; }
         if (stream_results) { const int rc_st = stream_begin(); if (rc_st) return rc_st; }
-        // (a kernel, not hipMemsetAsync: the same launch list then serves the eager call and the captured graph -- replays whose memset NODES were
-        //  preceded by an eager forward on the handle came back with an unzeroed error word on ROCm 7.2, tools/graph_debug2.py)
-        hipLaunchKernelGGL(zero_words_kernel, dim3(32), dim3(256), 0, s, h->err_flag, 4, h->queue_heads, h->n_queue_heads);
-        h->next_queue_head = 0;
-        if (h->prof_on) { h->prof_recs.clear(); h->prof_used = 0; }
+        // (the last refusal, in front of every launch: a deadline call that is refused is not counted and writes no log row)
         if (sp && !use_idx) {          // attention_pair.hip holds Delta tables up to fixed distances: refuse what it cannot hold
             AttnArgs chk{};
             chk.ctx_split = 1; chk.c1 = h->c1; chk.c2 = h->c2; chk.doc_flags = h->doc_flags; chk.doc_orig = S_doc_orig(0);
@@ -883,6 +910,12 @@ struct Forward {
                 return fail(h, "ee_forward: the split-precision attention kernels cannot hold this relative-position configuration "
                                "(bins %d / %d, distances %d / %d); use MMEE_PREC_F32", c.rel_pos_bins, c.rel_2d_pos_bins, c.max_rel_pos, c.max_rel_2d_pos);
         }
+        if (h->prof_on) { h->prof_recs.clear(); h->prof_used = 0; }
+        if (dl) deadline_begin();                                        // the call's first launch: its clock starts here
+        // (a kernel, not hipMemsetAsync: the same launch list then serves the eager call and the captured graph -- replays whose memset NODES were
+        //  preceded by an eager forward on the handle came back with an unzeroed error word on ROCm 7.2, tools/graph_debug2.py)
+        hipLaunchKernelGGL(zero_words_kernel, dim3(32), dim3(256), 0, s, h->err_flag, 4, h->queue_heads, h->n_queue_heads);
+        h->next_queue_head = 0;
         if (beit) embed_beit();
         else embed_layoutlmv3();
 
@@ -976,6 +1009,9 @@ int ee_graph_capture(ee_handle* h, const int64_t* input_ids, const int64_t* atte
     if (flags & MMEE_FLAG_STREAM_RESULTS)          // before the eager warm-up call, which would otherwise run (and stream) first
         return fail(h, "ee_graph_capture: MMEE_FLAG_STREAM_RESULTS belongs to eager calls (the events between the launches are not part of a captured "
                        "launch list)");
+    if (h->dl_on)
+        return fail(h, "ee_graph_capture: a deadline is set: the call number and the budget travel by value and the begin launch stamps the "
+                       "call's own start, so deadline calls are eager (not built; ee_set_deadline(h, MMEE_DEADLINE_OFF, NULL) first)");
     if (h->ctl_on)                                 // before the audit's refusal: a controller implies an audit
         return fail(h, "ee_graph_capture: a controller is set: its seed changes per call and the step reads the call's own results, so controlled "
                        "calls are eager (not built; ee_set_controller(h, NULL, ...) first)");
@@ -1099,6 +1135,9 @@ int ee_forward_vision(ee_handle* h, const float* pixel_values, int32_t B, const 
     if (h->quota_mode != MMEE_QUOTA_OFF)
         return fail(h, "ee_forward_vision: quotas are set: a rank over B documents and a second one over the survivors are not the one-call ranking "
                        "(not built; ee_set_quotas(h, NULL, 0, 0) first)");
+    if (h->dl_on)
+        return fail(h, "ee_forward_vision: a deadline is set: the budget of a vision-first call would have to span both of its phases "
+                       "(not built; ee_set_deadline(h, MMEE_DEADLINE_OFF, NULL) first)");
     if (h->ctl_on)                                 // before the audit's refusal: a controller implies an audit
         return fail(h, "ee_forward_vision: a controller is set: its audit hashes the slot in the call, which phase 2 renumbers "
                        "(not built; ee_set_controller(h, NULL, ...) first)");

@@ -157,6 +157,19 @@ struct ee_handle {
     double* ctl_path = nullptr;                   // (V,E1)
     double* ctl_thr_dev = nullptr;                // [E1]: the thresholds of the NEXT controlled call, rewritten by controller_step_kernel
     long long *ctl_state = nullptr, *ctl_tally = nullptr, *ctl_log = nullptr;      // kCtlStateWords; controller_tally_words; the ring of log rows
+    // deadline exits (ee_set_deadline; include/mmee.h): while dl_on, a call that is not dump-all opens with deadline_begin_kernel, every
+    // decide launch reads its threshold at dl_thr, and deadline_check_kernel runs in front of each.  budget and eta travel by value
+    bool dl_on = false;
+    uint64_t dl_budget = 0;
+    std::vector<uint64_t> dl_eta;                 // [E1]
+    uint32_t dl_khz = 0;                          // the wall-clock rate of the device (hipDeviceAttributeWallClockRate)
+    uint64_t dl_calls = 0;                        // deadline calls enqueued on the handle so far (atomic: ee_request_cut reads it from any thread)
+    uint64_t dl_log_first = 0;                    // dl_calls when the log was last restarted (ee_set_deadline_log)
+    int32_t dl_log_cap = 0;
+    uint64_t* dl_word = nullptr;                  // pinned, mapped host word: calls numbered <= *dl_word are cut at their next check
+    const unsigned long long* dl_word_dev = nullptr;      // the same word as the check kernel addresses it
+    double* dl_thr = nullptr;                     // [E1]
+    long long *dl_state = nullptr, *dl_log = nullptr;     // kDlStateWords; the ring of log rows
     // optional per-kernel event timing (ee_profile)
     bool prof_on = false;
     struct ProfRec { int id; hipEvent_t a, b; double flops; };
@@ -328,7 +341,7 @@ struct Scratch {
 
 // kernel roles reported by ee_profile_read (their names: kProfNames in capi_query.hip)
 enum { P_PREP = 0, P_EMBT, P_GPATCH, P_EMBV, P_GQKV, P_ATTN, P_GAO, P_LN, P_GUP, P_GDOWN, P_HEAD, P_DECIDE, P_COMPACT, P_GCLS, P_PROBE,
-       P_PAIRIDX, P_PSPLIT, P_HEADOUT, P_EMIT, P_ENSEMBLE, P_QUOTA, P_CONTROLLER, P_COUNT };
+       P_PAIRIDX, P_PSPLIT, P_HEADOUT, P_EMIT, P_ENSEMBLE, P_QUOTA, P_CONTROLLER, P_DEADLINE, P_COUNT };
 
 struct ProfScope {
     ee_handle* h;

@@ -40,8 +40,11 @@ const char* const kProfNames[] = {
     "exit_quota_rank|exit_quota_crit_kernel+exit_quota_rank_kernel",
     // (not nested) ee_set_controller: two launches behind the final exit's decide launch
     "controller|audit_tally_kernel+controller_step_kernel",
+    // (not nested) ee_set_deadline: one launch in front of the call and one in front of every exit's decide launch
+    "deadline|deadline_begin_kernel+deadline_check_kernel",
 };
 static_assert(sizeof(kProfNames) / sizeof(kProfNames[0]) == P_COUNT, "one name per profile role");
+static_assert(kDeadlineNone == MMEE_DEADLINE_NONE && kDeadlineNone != MMEE_DEADLINE_OFF, "the values include/mmee.h documents");
 
 // Synchronises the stream, then copies the first n StageCounts (of the last forward) to the host.
 int read_stage_counts(ee_handle* h, void* stream, int n, std::vector<StageCounts>& sc) {
@@ -180,6 +183,9 @@ int ee_set_criterion(ee_handle* h, int32_t criterion) {
     if (criterion == MMEE_CRIT_PATIENCE && h->quota_mode != MMEE_QUOTA_OFF)
         return fail(h, "ee_set_criterion: MMEE_CRIT_PATIENCE while quotas are set: PABEE's decision carries per-document state, no rank is defined for it "
                        "(ee_set_quotas(h, NULL, 0, 0) first)");
+    if (criterion == MMEE_CRIT_PATIENCE && h->dl_on)
+        return fail(h, "ee_set_criterion: MMEE_CRIT_PATIENCE while a deadline is set: a cut must fire at once, and PABEE's decision carries "
+                       "per-document state and no threshold (ee_set_deadline(h, MMEE_DEADLINE_OFF, NULL) first)");
     if (h->ctl_on && criterion != h->cfg.criterion)
         return fail(h, "ee_set_criterion: a controller is set: its path is ordered for the direction of the criterion it was set under, and the "
                        "patience criterion has no threshold to steer (ee_set_controller(h, NULL, ...) first)");
@@ -205,6 +211,9 @@ int ee_set_quotas(ee_handle* h, const int32_t* quotas, int32_t n, int32_t mode) 
                            "is defined for them (not built; ee_set_exit_rule(h, MMEE_RULE_PLAIN) first)", h->rule);
         if (c.use_lte)
             return fail(h, "ee_set_quotas: a use_lte handle: the learning-to-exit decision reads another score, no rank is defined for it (not built)");
+        if (h->dl_on)
+            return fail(h, "ee_set_quotas: a deadline is set: a quota releases a fixed number of documents, a cut releases everybody "
+                           "(not built; ee_set_deadline(h, MMEE_DEADLINE_OFF, NULL) first)");
         if (h->audit_cut)
             return fail(h, "ee_set_quotas: an audit is set: a rank would count the audited documents that stay as shadows, and n_{e+1} would no longer "
                            "be n_e - q_e (not built; ee_set_audit(h, 0, 0, 0) first)");
@@ -240,6 +249,9 @@ int ee_set_audit(ee_handle* h, uint64_t cut, uint32_t seed, int32_t slot_base) {
     if (cut && h->quota_mode != MMEE_QUOTA_OFF)
         return fail(h, "ee_set_audit: quotas are set: a rank would count the audited documents that stay as shadows, and n_{e+1} would no longer be "
                        "n_e - q_e (not built; ee_set_quotas(h, NULL, 0, 0) first)");
+    if (cut && h->dl_on)
+        return fail(h, "ee_set_audit: a deadline is set: the audit's shadows would run on past the cut "
+                       "(not built; ee_set_deadline(h, MMEE_DEADLINE_OFF, NULL) first)");
     if (cut)                                       // (a capture is refused while an audit is set, so held graphs mean the audit is off)
         for (const auto& g : h->graphs)
             if (g.exec)
@@ -267,6 +279,9 @@ int ee_set_controller(ee_handle* h, const double* path, int32_t V, double alpha,
         if (g.exec)
             return fail(h, "ee_set_controller: the handle holds captured graphs: a graph's launch list is the one of its capture, and controlled calls "
                            "are eager (not built; ee_graph_destroy them first)");
+    if (h->dl_on)
+        return fail(h, "ee_set_controller: a deadline is set: the controller's audit shadows would run on past the cut "
+                       "(not built; ee_set_deadline(h, MMEE_DEADLINE_OFF, NULL) first)");
     if (!h->audit_cut)
         return fail(h, "ee_set_controller: no audit is set: the controller's loss is counted on the audited sample (ee_set_audit with cut > 0 first)");
     if (c.criterion == MMEE_CRIT_PATIENCE)
@@ -342,6 +357,115 @@ int ee_controller_log(ee_handle* h, int64_t* rows_out, int32_t cap, int32_t* n, 
     return 0;
 }
 
+// the deadline's device arrays and its pinned request word, at the first ee_set_deadline / ee_set_deadline_log of the handle
+static int deadline_alloc(ee_handle* h, int E1) {
+    if (h->dl_thr) return 0;
+    int dev = 0, khz = 0;
+    HIP_OK(h, hipGetDevice(&dev));
+    HIP_OK(h, hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
+    if (khz <= 0)
+        return fail(h, "ee_set_deadline: the runtime reports a wall-clock rate of %d kHz: the device clock cannot be turned into ns", khz);
+    uint64_t* word = nullptr;
+    HIP_OK(h, hipHostMalloc((void**)&word, sizeof(uint64_t), hipHostMallocMapped));
+    *word = 0;
+    void* wdev = nullptr;
+    if (hipHostGetDevicePointer(&wdev, word, 0) != hipSuccess) { (void)hipHostFree(word); return fail(h, "ee_set_deadline: hipHostGetDevicePointer failed"); }
+    double* thr = nullptr;
+    long long* st = nullptr;
+    if (dev_alloc(h, &thr, (size_t)E1) || dev_alloc(h, &st, (size_t)kDlStateWords)) { (void)hipHostFree(word); return 1; }
+    h->dl_khz = (uint32_t)khz; h->dl_word = word; h->dl_word_dev = reinterpret_cast<const unsigned long long*>(wdev);
+    h->dl_thr = thr; h->dl_state = st;
+    return 0;
+}
+
+// what keeps a handle from carrying a deadline (the definition's list): 0, or the refusal
+static int deadline_refusal(ee_handle* h) {
+    const ee_config& c = h->cfg;
+    const int E1 = c.n_embedding_exits + c.n_encoder_exits + 1;
+    if (E1 > kCtlMaxE1) return fail(h, "ee_set_deadline: the handle has E1 = %d exits, a deadline takes E1 <= %d", E1, kCtlMaxE1);
+    if (c.criterion == MMEE_CRIT_PATIENCE)
+        return fail(h, "ee_set_deadline: a handle under MMEE_CRIT_PATIENCE: a cut must fire at once, and PABEE's decision carries per-document state "
+                       "and no threshold (not built)");
+    if (h->rule != MMEE_RULE_PLAIN)
+        return fail(h, "ee_set_deadline: a handle under MMEE_RULE_STREAK / MMEE_RULE_EITHER (rule %d): a cut must fire at once, and their decisions "
+                       "carry per-document state (not built; ee_set_exit_rule(h, MMEE_RULE_PLAIN) first)", h->rule);
+    if (c.use_lte) return fail(h, "ee_set_deadline: a use_lte handle: the learning-to-exit decision reads another score than the one a cut opens (not built)");
+    if (h->quota_mode != MMEE_QUOTA_OFF)
+        return fail(h, "ee_set_deadline: quotas are set: a quota releases a fixed number of documents, a cut releases everybody "
+                       "(not built; ee_set_quotas(h, NULL, 0, 0) first)");
+    if (h->ctl_on)                                                    // before the audit's refusal: a controller implies an audit
+        return fail(h, "ee_set_deadline: a controller is set: its audit shadows would run on past the cut "
+                       "(not built; ee_set_controller(h, NULL, ...) first)");
+    if (h->audit_cut)
+        return fail(h, "ee_set_deadline: an audit is set: its shadows would run on past the cut (not built; ee_set_audit(h, 0, 0, 0) first)");
+    for (const auto& g : h->graphs)
+        if (g.exec)
+            return fail(h, "ee_set_deadline: the handle holds captured graphs: a graph's launch list is the one of its capture, and deadline calls "
+                           "are eager (not built; ee_graph_destroy them first)");
+    return 0;
+}
+
+int ee_set_deadline_log(ee_handle* h, int32_t log_cap) {
+    if (!h) return 1;
+    const int E1 = h->cfg.n_embedding_exits + h->cfg.n_encoder_exits + 1;
+    if (log_cap < 0 || log_cap > (1 << 24)) return fail(h, "ee_set_deadline_log: log_cap = %d outside [0, 2^24]", log_cap);
+    if (!h->dl_on && deadline_refusal(h)) return 1;                   // a handle that cannot carry a deadline gets no arrays either
+    HIP_OK(h, hipDeviceSynchronize());                                // an earlier forward may still write the ring that is replaced
+    if (deadline_alloc(h, E1)) return 1;
+    if (log_cap != h->dl_log_cap || !h->dl_log) {
+        h->dl_log_cap = 0;
+        if (ctl_realloc(h, &h->dl_log, (size_t)log_cap * deadline_log_words(E1))) return 1;
+        h->dl_log_cap = log_cap;
+    }
+    h->dl_log_first = __atomic_load_n(&h->dl_calls, __ATOMIC_RELAXED);
+    return 0;
+}
+
+int ee_set_deadline(ee_handle* h, uint64_t budget_ns, const uint64_t* eta_ns) {
+    if (!h) return 1;
+    if (budget_ns == MMEE_DEADLINE_OFF) { h->dl_on = false; return 0; }      // the arrays and the log stay until ee_destroy
+    const int E1 = h->cfg.n_embedding_exits + h->cfg.n_encoder_exits + 1;
+    if (deadline_refusal(h)) return 1;
+    if (!h->dl_thr && ee_set_deadline_log(h, MMEE_DEADLINE_LOG_DEFAULT)) return 1;
+    // budget and eta are kernel ARGUMENTS of the launches of later calls: nothing in flight reads them, nothing to wait for
+    h->dl_eta.assign((size_t)E1, 0);
+    if (eta_ns) h->dl_eta.assign(eta_ns, eta_ns + E1);
+    h->dl_budget = budget_ns;
+    h->dl_on = true;
+    return 0;
+}
+
+int ee_has_deadline(const ee_handle* h) { return h && h->dl_on ? 1 : 0; }
+
+int ee_request_cut(ee_handle* h) {
+    if (!h || !h->dl_word) return 1;                                  // no deadline was ever set: there is no call to cut (no message: any thread)
+    // a monotone maximum: of two requesters the later call number stays, whichever of them stores last
+    const uint64_t want = __atomic_load_n(&h->dl_calls, __ATOMIC_RELAXED);
+    uint64_t cur = __atomic_load_n(h->dl_word, __ATOMIC_RELAXED);
+    while (cur < want && !__atomic_compare_exchange_n(h->dl_word, &cur, want, false, __ATOMIC_RELEASE, __ATOMIC_RELAXED)) {}
+    return 0;
+}
+
+int ee_deadline_log(ee_handle* h, int64_t* rows_out, int32_t cap, int32_t* n, void* stream) {
+    if (!h || !n) return fail(h, "ee_deadline_log: null argument");
+    if (!h->dl_thr) return fail(h, "ee_deadline_log: no deadline was set on this handle (ee_set_deadline)");
+    if (cap < 0 || (cap > 0 && !rows_out)) return fail(h, "ee_deadline_log: cap = %d rows without a buffer", cap);
+    const int E1 = h->cfg.n_embedding_exits + h->cfg.n_encoder_exits + 1, W = deadline_log_words(E1);
+    HIP_OK(h, hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
+    const uint64_t calls = __atomic_load_n(&h->dl_calls, __ATOMIC_RELAXED);
+    const long long held = std::min<long long>((long long)(calls - h->dl_log_first), h->dl_log_cap);
+    const int take = (int)std::min<long long>(held, cap);
+    *n = (int32_t)held;                                               // the rows the ring holds; the last `take` of them are copied, oldest first
+    if (!take) return 0;
+    std::vector<long long> ring((size_t)h->dl_log_cap * W);
+    HIP_OK(h, hipMemcpy(ring.data(), h->dl_log, sizeof(long long) * ring.size(), hipMemcpyDeviceToHost));
+    for (int j = 0; j < take; ++j) {
+        const uint64_t call = calls - (uint64_t)take + (uint64_t)j + 1;          // 1-based: row (call - 1) % log_cap
+        memcpy(rows_out + (size_t)j * W, ring.data() + (size_t)((call - 1) % (uint64_t)h->dl_log_cap) * W, sizeof(long long) * W);
+    }
+    return 0;
+}
+
 int ee_audit_selected(uint64_t cut, uint32_t seed, int32_t slot) { return audit_selected(cut, seed, slot) ? 1 : 0; }
 
 int ee_set_ensemble(ee_handle* h, const double* w, const double* b) {
@@ -406,6 +530,9 @@ int ee_set_exit_rule(ee_handle* h, int32_t rule) {
     if (rule != MMEE_RULE_PLAIN && h->quota_mode != MMEE_QUOTA_OFF)
         return fail(h, "ee_set_exit_rule: rule %d while quotas are set: MMEE_RULE_STREAK / MMEE_RULE_EITHER carry per-document state, no rank is defined "
                        "for them (ee_set_quotas(h, NULL, 0, 0) first)", rule);
+    if (rule != MMEE_RULE_PLAIN && h->dl_on)
+        return fail(h, "ee_set_exit_rule: rule %d while a deadline is set: a cut must fire at once, and MMEE_RULE_STREAK / MMEE_RULE_EITHER carry "
+                       "per-document state (ee_set_deadline(h, MMEE_DEADLINE_OFF, NULL) first)", rule);
     if (rule != MMEE_RULE_PLAIN && h->ctl_on)
         return fail(h, "ee_set_exit_rule: rule %d while a controller is set: the controller steers the thresholds of the plain rule, and its replay "
                        "(ee_rolling_control) knows no other (ee_set_controller(h, NULL, ...) first)", rule);

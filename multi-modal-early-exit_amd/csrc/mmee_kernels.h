@@ -398,6 +398,68 @@ struct RollingControlArgs {
     double* p_out;                   // [1] the position after the last group, or null
 };
 void launch_rolling_control(const RollingControlArgs& a, hipStream_t s);
+
+// Deadline exits (ee_set_deadline; the definition is in include/mmee.h, behind the controller's): a launch in front of every exit's decide
+// launch reads the 100 MHz clock and, once the budget is spent or the host has asked, rewrites the rest of the call's thresholds to the value
+// that fires for everybody.  deadline_rule is THE rule: deadline_check_kernel (deadline.hip; the forward and ee_debug_deadline_check launch it)
+// and nothing else calls it.
+constexpr unsigned long long kDeadlineNone = ~0ull;                   // MMEE_DEADLINE_NONE: stamp, never cut by the clock
+constexpr int kDlStateWords = 3;                                      // the device state of the call in flight: t0 (ticks), cut_exit, cut_by
+__host__ __device__ inline int deadline_log_words(int E1) { return 4 + E1; }      // call, budget_ns, cut_exit, cut_by, elapsed_ns[E1]
+__host__ __device__ inline unsigned long long deadline_sat_add(unsigned long long a, unsigned long long b) {
+    const unsigned long long s = a + b;
+    return s < a ? ~0ull : s;
+}
+// ticks of a counter that runs at khz kHz, in ns, rounded down: (d / khz) 10^6 + (d % khz) 10^6 / khz, 2^64 - 1 where that would not fit
+__host__ __device__ inline unsigned long long deadline_ticks_to_ns(unsigned long long d, unsigned khz) {
+    const unsigned long long q = d / khz, r = d % khz;
+    if (q > (~0ull - 999999ull) / 1000000ull) return ~0ull;
+    return q * 1000000ull + r * 1000000ull / khz;
+}
+struct DeadlineVerdict {
+    unsigned long long elapsed_ns;   // (now - t0) in ns, the difference taken modulo 2^64
+    int cut_exit, cut_by;            // after this check: the exit of the call's cut or -1; 0, 1 (the clock) or 2 (the host)
+};
+// The check in front of exit `exit_index` of deadline call number `call` (1-based).  A cut is sticky and the final exit cuts nothing: with
+// prev_cut_exit >= 0 or exit_index == E1 - 1 the previous pair comes back.  Otherwise the clock cuts when budget != kDeadlineNone and
+// sat_add(elapsed, eta) >= budget; else the host does when host_word >= call.
+__host__ __device__ inline DeadlineVerdict deadline_rule(unsigned long long t0, unsigned long long now, unsigned khz, unsigned long long budget,
+                                                         unsigned long long eta, unsigned long long host_word, unsigned long long call,
+                                                         int exit_index, int E1, int prev_cut_exit, int prev_cut_by) {
+    DeadlineVerdict v{deadline_ticks_to_ns(now - t0, khz), prev_cut_exit, prev_cut_by};
+    if (prev_cut_exit >= 0 || exit_index >= E1 - 1) return v;
+    if (budget != kDeadlineNone && deadline_sat_add(v.elapsed_ns, eta) >= budget) { v.cut_exit = exit_index; v.cut_by = 1; }
+    else if (host_word >= call) { v.cut_exit = exit_index; v.cut_by = 2; }
+    return v;
+}
+// the threshold that fires for every criterion that is not a NaN: the mirror image of controller_thresholds' never-fires value
+__host__ __device__ inline double deadline_always_fires(double sign) { return sign < 0.0 ? INFINITY : -INFINITY; }
+// deadline_begin_kernel: the first launch of a deadline call.  t0 <- the clock, no cut yet, thr <- the call's thresholds, the head of the log row
+struct DeadlineBeginArgs {
+    double thr_in[kCtlMaxE1];        // the call's thresholds, by value
+    int E1;
+    unsigned long long call, budget;
+    long long* state;                // [kDlStateWords]
+    double* thr;                     // [E1]: what every decide launch of the call reads
+    long long* row;                  // the call's log row (deadline_log_words(E1) words), or null
+};
+void launch_deadline_begin(const DeadlineBeginArgs& a, hipStream_t s);
+// deadline_check_kernel: one workgroup of one wave in front of an exit's decide launch.  now_set / t0_set: the stand-alone hook's injected
+// clock (the forward leaves both 0: the kernel reads s_memrealtime and state[0])
+struct DeadlineCheckArgs {
+    int E1, exit_index;
+    unsigned khz;                    // the wall-clock rate the runtime reports
+    double sign;
+    unsigned long long call, budget, eta;      // eta: eta_ns[exit_index]
+    const unsigned long long* host_word;       // pinned, mapped: the latest call number ee_request_cut asked to cut
+    long long* state;
+    double* thr;
+    long long* row;
+    int now_set, t0_set;
+    unsigned long long now, t0;
+};
+void launch_deadline_check(const DeadlineCheckArgs& a, hipStream_t s);
+
 // ee_quota_scan (exit_ops.hip): the same decision on a criterion table (E1,N), consecutive groups of G documents ranked independently
 struct QuotaScanArgs {
     const double* table;             // (E1,N) on the device

@@ -143,6 +143,25 @@ class ControllerLog:
         return np.cumsum(np.where(self.sampled > 0, np.nan_to_num(self.loss) - float(alpha), 0.0))
 
 
+@dataclass
+class DeadlineLog:
+    """The device log of a deadline (``EarlyExitEngine.deadline_log``): one row per deadline call, numpy on the host.  ``elapsed_ns[t, e]`` is
+    the device time from the call's begin launch to the check in front of exit ``e``'s decision: the rows are a per-exit device timeline of
+    the forward, and ``elapsed_ns[:, -1] - elapsed_ns[t, cut_exit[t]]`` is the tail of empty launches behind a cut."""
+    call: np.ndarray                        # (T,) int64: the handle's deadline call number, from 1
+    budget_ns: np.ndarray                   # (T,) uint64 (2^64 - 1: stamps only)
+    cut_exit: np.ndarray                    # (T,) int64, -1: not cut
+    cut_by: np.ndarray                      # (T,) int64: 0 nobody, 1 the clock, 2 the host
+    elapsed_ns: np.ndarray                  # (T,E1) uint64
+
+    @staticmethod
+    def from_rows(rows, E1: int) -> "DeadlineLog":
+        """From (T, deadline_log_words(E1)) int64 words as the device writes them (include/mmee.h)."""
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, capi.deadline_log_words(E1))
+        return DeadlineLog(r[:, 0].copy(), r[:, 1].copy().view(np.uint64), r[:, 2].copy(), r[:, 3].copy(),
+                           np.ascontiguousarray(r[:, 4:]).view(np.uint64).reshape(-1, E1))
+
+
 def _require_torch_cuda(device=None):
     if torch is None:
         raise capi.MMEEUnavailable(f"PyTorch-ROCm is required for device tensors: {_torch_err}")
@@ -217,6 +236,8 @@ class EarlyExitEngine:
         self.audit = None                   # set_audit(): (fraction, seed, slot_base), or None
         self.controller = None              # set_controller(): dict(path, alpha, gamma, start, seed, log_cap), or None
         self._ctl_calls = 0                 # controlled calls since set_controller: call t audits under seed + t
+        self.deadline = None                # set_deadline(): dict(budget_ns, eta_ns, log_cap), or None
+        self._dl_last_cap = 0               # the log_cap of the deadline that was removed last: its log stays readable
         self.patience = None
         if ec.patience is not None:
             self.set_patience(ec.patience)
@@ -312,7 +333,8 @@ class EarlyExitEngine:
                 want_attentions: bool = False, patience: Optional[Union[int, Sequence[int]]] = None, exit_rule=None,
                 low_latency: bool = False, quotas: Optional[Sequence[int]] = None, quota_mode: Optional[str] = None,
                 quota_fractions: Optional[Sequence[float]] = None, audit_fraction: Optional[float] = None,
-                audit_seed: Optional[int] = None, _capture: bool = False, _stream: bool = False) -> EngineOutput:
+                audit_seed: Optional[int] = None, deadline_ms: Optional[float] = None, _capture: bool = False,
+                _stream: bool = False) -> EngineOutput:
         """``out``: optional preallocated ``(logits (B,K) f32, exit_layer (B,) i32, confidence (B,) f32)`` device tensors (contiguous; row
         slices of larger tensors qualify) the kernels write into instead of fresh allocations -- MicroBatchedEngine hands each half its slice.
         ``patience``: when given, ``set_patience(patience)`` before the call (an int, or one entry per exit; it matters under the "patience"
@@ -328,7 +350,11 @@ class EarlyExitEngine:
         ``audit_fraction`` / ``audit_seed``: when given, ``set_audit(audit_fraction, seed=audit_seed)`` before the call (audited exits: a hashed
         sample of the call's documents is delivered where it leaves and runs on to the final exit; with ``want_all=True`` its columns come
         back complete, ``output.audit_mask`` says which).  ``audit_seed`` alone re-seeds the audit that is set (vary it per call).  Both stay
-        set for later calls; ``set_audit(None)`` switches the audit off."""
+        set for later calls; ``set_audit(None)`` switches the audit off.
+        ``deadline_ms``: the budget of THIS call on an engine that has a deadline (``set_deadline``), in place of the engine's; the engine's
+        ``eta`` table and log are used, nothing is synchronised, and the engine's own budget is back for the next call.  The override sets
+        and restores the handle's budget around the enqueue: an engine is driven by one thread, and this is not safe next to another thread's
+        ``forward`` or ``set_deadline`` on the same engine (``request_cut`` is).  Refused with ``capture``."""
         if not self._finalized:
             raise capi.MMEEError("load_weights() has not been called")
         if patience is not None:
@@ -462,6 +488,8 @@ class EarlyExitEngine:
         # tolerance, not bit-identical to whole layers
         # whole_layers / probe_always override the handle's schedule for this call (default: every decision layer probed first, or the mask pin_schedule() set)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if deadline_ms is not None and _capture:
+            raise ValueError("capture(deadline_ms=): deadline calls are eager, a captured graph carries no deadline")
         if _capture:
             # ee_graph_capture: the same call eagerly (the outputs hold its results), then its launch list as a hipGraph bound to THESE tensors
             if emb is not None or hs is not None or hm is not None or att is not None or validate:
@@ -480,6 +508,9 @@ class EarlyExitEngine:
             res = EngineOutput(out_logits, out_exit, out_conf, all_logits, all_crit, head_logits, head_crit, hidden, None, None)
             ins = dict(input_ids=ids, attention_mask=am, bbox=bb, pixel_values=px, token_type_ids=tt, position_ids=ps)
             return CapturedForward(self, gid.value, {k: v for k, v in ins.items() if v is not None}, res)
+        if deadline_ms is not None and self.deadline is None:
+            raise ValueError("forward(deadline_ms=) overrides the budget of an engine that has a deadline: set_deadline(...) first "
+                             "(set_deadline(None, stamps_only=True) for an engine whose calls are otherwise not cut)")
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             if emb is not None:
@@ -490,9 +521,13 @@ class EarlyExitEngine:
                 capi.check(self.lib.ee_set_head_mask(self._h, p(hm)), self._h, "ee_set_head_mask")
             if att is not None:
                 capi.check(self.lib.ee_set_attentions_out(self._h, p(att)), self._h, "ee_set_attentions_out")
+            if deadline_ms is not None:                # budget and eta are arguments of this call's launches: set for it, put back behind it
+                self._apply_deadline(self._budget_ns(deadline_ms), self.deadline["eta_ns"])
             rc = self.lib.ee_forward(self._h, p(ids), p(am), p(bb), p(px), p(tt), p(ps), B, T, thr_c, tmp_c, flags,
                                      p(out_logits), p(out_exit), p(out_conf), p(all_logits), p(all_crit),
                                      p(head_logits), p(head_crit), p(hidden), stream)
+            if deadline_ms is not None:
+                self._apply_deadline(self.deadline["budget_ns"], self.deadline["eta_ns"])
         capi.check(rc, self._h, "ee_forward")
         ctl_call = self._ctl_calls
         if controlled:                                 # the library has used this call's seed: count it before anything else can raise
@@ -1008,6 +1043,73 @@ class EarlyExitEngine:
             capi.check(self.lib.ee_controller_log(self._h, rows.ctypes.data_as(C.c_void_p), cap, C.byref(n),
                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), self._h, "ee_controller_log")
         return ControllerLog.from_rows(rows[:n.value], self.E + 1)
+
+    @staticmethod
+    def _budget_ns(budget_ms) -> int:
+        ns = int(round(float(budget_ms) * 1e6))
+        if not 0 <= ns < capi.DEADLINE_OFF:
+            raise ValueError(f"a deadline budget of {budget_ms} ms is not a number of ns in [0, 2^64 - 2)")
+        return ns
+
+    def _apply_deadline(self, budget_ns: int, eta_ns):
+        eta_c = None if eta_ns is None else (C.c_uint64 * (self.E + 1))(*[int(x) for x in eta_ns])
+        capi.check(self.lib.ee_set_deadline(self._h, C.c_uint64(budget_ns), eta_c), self._h, "ee_set_deadline")
+
+    def set_deadline(self, budget_ms: Optional[float] = None, eta_ms=None, stamps_only: bool = False, log_cap: int = 1024):
+        """Deadline exits of every later forward (ee_set_deadline; the definition is in include/mmee.h): anytime prediction.  A clock on the
+        device starts with the call's first launch; in front of every exit's decision a small launch looks at it, and once
+        ``elapsed + eta_ms[e] >= budget_ms`` -- or once ``request_cut()`` has asked -- everybody still in the batch leaves at that exit, with
+        that exit's ordinary row.  The result is, bit for bit, ``forward`` under thresholds that fire for everybody from ``cut_exit`` on;
+        ``deadline_log()`` says where the cut fell.  ``eta_ms``: per exit, the time from the decision at that exit to the end of the call if
+        nobody is cut there (``deadline.eta_from_logs`` measures it; ``None``: zeros, the cut then falls at the first exit after the budget has
+        passed).  ``stamps_only=True`` (``budget_ms`` must be ``None``): the clock never cuts; calls are logged and obey ``request_cut()`` only.
+        ``log_cap``: rows of the device ring log.  The first deadline of an engine, one after ``set_deadline(None)`` and one with another
+        ``log_cap`` restart the log (and synchronise the device); a new budget or ``eta_ms`` on an engine that has a deadline does neither,
+        the log runs on.  ``set_deadline(None)`` removes the deadline (its log stays readable): the
+        engine then issues the launches and returns the bits it did before.  Refused under the patience criterion, the combined exit rules,
+        learning-to-exit, quotas, an audit or a controller, with ``capture`` and ``forward_vision``; dump-all calls ignore it.  A document
+        whose criterion is a NaN is not cut: it runs to the final exit."""
+        if budget_ms is None and not stamps_only:
+            self._apply_deadline(capi.DEADLINE_OFF, None)
+            if self.deadline is not None:
+                self._dl_last_cap = self.deadline["log_cap"]
+            self.deadline = None
+            return None
+        if budget_ms is not None and stamps_only:
+            raise ValueError("set_deadline: stamps_only=True goes with budget_ms=None (the clock then never cuts)")
+        budget_ns = capi.DEADLINE_NONE if stamps_only else self._budget_ns(budget_ms)
+        eta_ns = None
+        if eta_ms is not None:
+            eta = np.asarray(eta_ms, dtype=np.float64).reshape(-1)
+            if eta.shape[0] != self.E + 1 or not np.all(np.isfinite(eta)) or np.any(eta < 0):
+                raise ValueError(f"set_deadline: eta_ms has {self.E + 1} finite entries >= 0, one per exit")
+            eta_ns = [min(int(round(x * 1e6)), capi.DEADLINE_NONE) for x in eta.tolist()]
+        if self.deadline is None or self.deadline["log_cap"] != int(log_cap):
+            # the ring at its size, once; the entry point refuses what ee_set_deadline refuses, before anything is allocated
+            capi.check(self.lib.ee_set_deadline_log(self._h, int(log_cap)), self._h, "ee_set_deadline_log")
+        self._apply_deadline(budget_ns, eta_ns)
+        self.deadline = dict(budget_ns=budget_ns, eta_ns=eta_ns, log_cap=int(log_cap))
+        return self.deadline
+
+    def has_deadline(self) -> bool:
+        return bool(self.lib.ee_has_deadline(self._h))
+
+    def request_cut(self) -> bool:
+        """Cut every deadline forward enqueued on this engine so far at its next check, none enqueued later (ee_request_cut): one store to a
+        pinned word the check launches read.  Any thread, no device call.  False on an engine that never had a deadline."""
+        return self.lib.ee_request_cut(self._h) == 0
+
+    def deadline_log(self) -> "DeadlineLog":
+        """The device ring log, oldest row first (ee_deadline_log; synchronises the stream): one row per deadline call since ``set_deadline``,
+        the latest ``log_cap`` of them.  It stays readable after ``set_deadline(None)``."""
+        cap = self.deadline["log_cap"] if self.deadline else self._dl_last_cap
+        W = capi.deadline_log_words(self.E + 1)
+        rows = np.zeros((max(cap, 1), W), dtype=np.int64)
+        n = C.c_int32(0)
+        with torch.cuda.device(self.device):
+            capi.check(self.lib.ee_deadline_log(self._h, rows.ctypes.data_as(C.c_void_p), cap, C.byref(n),
+                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), self._h, "ee_deadline_log")
+        return DeadlineLog.from_rows(rows[:min(n.value, cap)], self.E + 1)
 
     def clock_stamp(self):
         """Device tensor of capi.CLOCK_STAMP_WORDS int64: one (s_memtime, s_memrealtime) pair per CU as seen by one-wave workgroups enqueued on

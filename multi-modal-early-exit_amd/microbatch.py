@@ -105,6 +105,17 @@ class MicroBatchedEngine:
     def has_controller(self) -> bool:
         return any(e.has_controller() for e in self.engines)
 
+    def set_deadline(self, budget_ms=None, eta_ms=None, stamps_only: bool = False, **kw):
+        """A deadline (``EarlyExitEngine.set_deadline``) is one clock started by one call on one handle; over micro-batches it is not built.
+        ``None`` is accepted (nothing is set)."""
+        if budget_ms is not None or stamps_only:
+            raise ValueError("a deadline over micro-batches is not built: the slices run on separate handles and streams, each of which would "
+                             "start a clock of its own (use EarlyExitEngine)")
+        return None
+
+    def has_deadline(self) -> bool:
+        return any(e.has_deadline() for e in self.engines)
+
     audit_mask = staticmethod(EarlyExitEngine.audit_mask)
     forward_audit_args = EarlyExitEngine.forward_audit_args
 
@@ -128,6 +139,9 @@ class MicroBatchedEngine:
             raise ValueError("low_latency is a small-batch mode of EarlyExitEngine; MicroBatchedEngine runs large batches")
         if any(kw.get(k) is not None for k in ("quotas", "quota_fractions", "quota_mode")):
             raise ValueError(self._NO_QUOTAS)
+        if self.has_deadline() or kw.get("deadline_ms") is not None:
+            raise ValueError("a handle of this MicroBatchedEngine has a deadline set, or deadline_ms= is given: a deadline over micro-batches is "
+                             "not built (set_deadline(None) on it, or use EarlyExitEngine)")
         if self.has_controller():
             raise ValueError("a handle of this MicroBatchedEngine has a controller set: a controller over micro-batches is not built "
                              "(set_controller(None) on it, or use EarlyExitEngine)")

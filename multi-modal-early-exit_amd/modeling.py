@@ -209,6 +209,11 @@ class LayoutLMv3EEForSequenceClassification:
         follow the audited disagreement with the full model.  One handle: refused on a model that runs on micro-batches."""
         return self.engine.set_controller(path, **kw)
 
+    def set_deadline(self, budget_ms=None, **kw):
+        """Deadline exits of every later ``early_exit`` (``EarlyExitEngine.set_deadline``): once the budget is spent, or ``engine.request_cut()``
+        has asked, everybody still in the batch leaves at the next exit.  One handle: refused on a model that runs on micro-batches."""
+        return self.engine.set_deadline(budget_ms, **kw)
+
     def _is_patience(self) -> bool:
         want = self.config.exit_config["inference_strategy"]
         return str(getattr(want, "value", want)) == "patience"
